@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s (+ image-encode ms) of the MI355X MiniGPT-4 engine, measured through the drop-in C ABI.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 13b|7b|tiny]      (N > 1 without a launcher: bench.py starts the N ranks itself)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 13b|7b|tiny] [--dump-outputs DIR] [--full]     (N > 1 without a launcher: bench.py starts the N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one decode step of the hot path (one `minigpt4_end_chat_image` call: sample + 1-token eval) on one conversation.
@@ -9,8 +9,11 @@ N = 1 runs BASELINE.json configs[2] (the headline: MiniGPT4-13B f16 vision + Vic
 written in the reference's two on-disk formats.  With N > 1 every rank is an independent replica with its own conversation
 (requests shard data-parallel; no per-token collective) -> scaling "weak"; `value` = total tokens of all ranks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (see the repo's bench contract) with `roofline` (dominant kernel = fused-dequant Q5_K mat-vec, HBM bound)
-and `cpu_baseline` (the CPU oracle -- a ggml-equivalent restatement, NOT llama.cpp -- timed on this host on a bounded sample).
+A plain run does what the headline needs and nothing else: load, encode the image, prefill, W untimed + K timed decode steps, the outputs
+of the last timed step (--dump-outputs), and ONE JSON line from rank 0 (see the repo's bench contract).  --full adds every other leg to the
+line: image-encode and prefill timings, `roofline` (dominant kernel = fused-dequant Q5_K mat-vec, HBM bound), long context, batched decode,
+parity mode, the other BASELINE.json configs, `parity` and `cpu_baseline` (the CPU oracle -- a ggml-equivalent restatement, NOT
+llama.cpp -- timed on this host on a bounded sample).
 """
 import argparse
 import ctypes
@@ -266,10 +269,16 @@ def main():
     ap.add_argument("--no-long-context", dest="long_context", action="store_false", help="skip the long-context leg (decode rate at 1024 / 2040 cached keys)")
     ap.add_argument("--conversations", type=int, default=4, help="extra leg: batched decode of this many conversations per GPU in one weight pass (BASELINE.json configs[3] "
                     "has 4 requests per replica); reported as `batched_decode`, never as `value`.  0/1 = skip")
+    ap.add_argument("--full", action="store_true", help="run every leg besides the headline too (encode / prefill timings, roofline, long context, batched decode, parity "
+                    "mode, extra configs, oracle parity, cpu_baseline); the --no-* and budget options above apply to these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed to DIR/*.npy: logits.npy (float32 [n_vocab], "
+                    "the logits its 1-token eval produced) and piece_utf8.npy (float32, the UTF-8 bytes of the piece it returned); rank 0's conversation")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
     rank = int(os.environ.get("RANK", "0"))
@@ -330,39 +339,40 @@ def main():
     wbytes = lib.library.minigpt4_amd_weight_bytes_per_token(ctx.ptr)
     log(f"[bench r{rank}] model loaded in {lstats['load_s']:.1f}s ({lstats['mode']}); {wbytes / 1e9:.3f} GB of weights streamed per token")
 
-    # ---- image encode (every rank encodes its own request's image)
+    # ---- image encode (every rank encodes its own request's image); timed over 8 encodes with --full, once otherwise
     img = G.synth_image(42 + rank)
     image = ML.array_to_image_struct(img)
     enc_wall, enc_dev = [], []
-    for i in range(8):                                                    # (the clocks of an idle GPU take a few encodes to come up: bench_encode.py shows 4.0 -> 3.8 ms over 8)
+    n_enc = 8 if args.full else 1
+    for i in range(n_enc):                                                # (the clocks of an idle GPU take a few encodes to come up: bench_encode.py shows 4.0 -> 3.8 ms over 8)
         t0 = time.perf_counter()
         emb = lib.minigpt4_encode_image(ctx, image)
         enc_wall.append((time.perf_counter() - t0) * 1e3)
         enc_dev.append(lib.library.minigpt4_amd_last_encode_ms(ctx.ptr))
-        if i < 7:
+        if i < n_enc - 1:
             lib.minigpt4_free_embedding(emb)
-    image_encode_ms, image_encode_dev_ms = min(enc_wall[1:]), min(enc_dev[1:])
 
     # ---- extra: 4 images in one pass over the vision weights (minigpt4_amd_encode_images; BASELINE.json configs[3] has 4 requests per replica)
     enc_batch = None
-    try:
-        nb = 4
-        imgs = [ML.array_to_image_struct(G.synth_image(100 + rank * 8 + i)) for i in range(nb)]
-        arr = (ML.MiniGPT4Image * nb)(*imgs)
-        batch, outb = ML.MiniGPT4Images(arr, nb), ML.MiniGPT4Embeddings()
-        best = 1e9
-        for _ in range(5):
-            assert lib.library.minigpt4_amd_encode_images(ctx.ptr, ctypes.byref(batch), ctypes.byref(outb), 0) == 0
-            best = min(best, lib.library.minigpt4_amd_last_encode_ms(ctx.ptr))
-            lib.library.minigpt4_amd_free_embeddings(ctypes.byref(outb))
-        enc_batch = {"images": nb, "device_ms": best, "device_ms_per_image": best / nb}
-    except Exception as e:
-        enc_batch = {"error": str(e)}
+    if args.full:
+        try:
+            nb = 4
+            imgs = [ML.array_to_image_struct(G.synth_image(100 + rank * 8 + i)) for i in range(nb)]
+            arr = (ML.MiniGPT4Image * nb)(*imgs)
+            batch, outb = ML.MiniGPT4Images(arr, nb), ML.MiniGPT4Embeddings()
+            best = 1e9
+            for _ in range(5):
+                assert lib.library.minigpt4_amd_encode_images(ctx.ptr, ctypes.byref(batch), ctypes.byref(outb), 0) == 0
+                best = min(best, lib.library.minigpt4_amd_last_encode_ms(ctx.ptr))
+                lib.library.minigpt4_amd_free_embeddings(ctypes.byref(outb))
+            enc_batch = {"images": nb, "device_ms": best, "device_ms_per_image": best / nb}
+        except Exception as e:
+            enc_batch = {"error": str(e)}
 
-    # ---- prefill: system prompt + image turn (reference call sequence, examples/main.cpp:207-293) twice: the first pass of a process also loads the
-    # prompt kernels' code objects and sets their attributes (reported as prefill_first_ms); the chat is reset in between
+    # ---- prefill: system prompt + image turn (reference call sequence, examples/main.cpp:207-293); with --full twice: the first pass of a process also
+    # loads the prompt kernels' code objects and sets their attributes (reported as prefill_first_ms); the chat is reset in between
     prefill_first_ms = None
-    for _pass in range(2):
+    for _pass in range(2 if args.full else 1):
         if _pass:
             lib.minigpt4_reset_chat(ctx)
         lib.library.minigpt4_amd_sync(ctx.ptr)
@@ -394,6 +404,28 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     ctx_mid = n_prompt + W + K // 2
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lib, ctx, pieces[-1])
+
+    out = {
+        "metric": "decode tokens/sec", "value": K * world / dt, "unit": "tokens/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": dt * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "i8", "data": "synthetic",
+        "config": {"workload": {"13b": "MiniGPT4-13B f16 vision + Vicuna-13B Q5_K_M (wv/w2 Q6_K in 'more-bits' layers, output Q6_K), batch 1 per GPU, greedy decode through the C ABI",
+                                "7b": "MiniGPT4-7B f16 vision + Vicuna-7B Q4_0 (output Q6_K), batch 1 per GPU", "tiny": "tiny smoke-test model"}[args.config],
+                   "n_ctx": args.n_ctx, "prompt_tokens": n_prompt, "context_at_mid_run": ctx_mid, "parallelism": f"dp{world} (independent replicas)"},
+        "weight_bytes_per_token": wbytes, "decode_weight_GBps_end_to_end": wbytes * K / dt / 1e9,
+        "model_load_s": load_s, "recv_load_s": recv_load_s, "weight_bcast_ms": bcast_ms,
+        "rccl_ranks": dist.get_world_size() if dist is not None else 1, "collective_backend": dist.get_backend() if dist is not None else None,
+        "rehearsal": ("MG4_BENCH_REHEARSAL=1: the ranks SHARE the visible GPU(s) and talk over gloo -- a functional run of the N > 1 path, every rate in this line is invalid as "
+                      "a measurement") if (world > 1 and os.environ.get("MG4_BENCH_REHEARSAL") == "1") else None,
+        "launcher": os.environ.get("MG4_BENCH_LAUNCHER", "external") if world > 1 else "none",
+        "weight_bcast": D.bcast_report(lstats), "load_mode": lstats["mode"],
+        "full": bool(args.full),
+    }
+    if not args.full:
+        finish(out, lib, ctx, rank, dist)
+        return
 
     # ---- device-side numbers: graph-replayed decode loop (no host round trip), and the per-launch-site table of the SAME launch set the graph
     # replays (eager, a hipEvent pair around every site on the engine's stream; Engine::profile_sites).  The roofline object is computed from that
@@ -440,24 +472,12 @@ def main():
                 "kernel_table": [{"kernel": k["kernel"], "sites": k["sites"], "calls_per_token": round(k["calls_per_token"], 3), "avg_us": round(k["avg_us"], 3), "timing": k["timing"],
                                   "bytes_per_call": round(k["bytes_per_call"], 1), "GBps": round(k["GBps"], 1), "us_per_token": round(k["us_per_token"], 2)} for k in table]}
 
-    out = {
-        "metric": "decode tokens/sec", "value": K * world / dt, "unit": "tokens/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": dt * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "i8", "data": "synthetic",
-        "config": {"workload": {"13b": "MiniGPT4-13B f16 vision + Vicuna-13B Q5_K_M (wv/w2 Q6_K in 'more-bits' layers, output Q6_K), batch 1 per GPU, greedy decode through the C ABI",
-                                "7b": "MiniGPT4-7B f16 vision + Vicuna-7B Q4_0 (output Q6_K), batch 1 per GPU", "tiny": "tiny smoke-test model"}[args.config],
-                   "n_ctx": args.n_ctx, "prompt_tokens": n_prompt, "context_at_mid_run": ctx_mid, "parallelism": f"dp{world} (independent replicas)"},
-        "image_encode_ms": image_encode_ms, "image_encode_device_ms": image_encode_dev_ms, "image_encode_batched": enc_batch, "prefill_ms": prefill_ms, "prefill_first_ms": prefill_first_ms, "prefill_tokens": n_prompt,
+    out.update({
+        "image_encode_ms": min(enc_wall[1:]), "image_encode_device_ms": min(enc_dev[1:]), "image_encode_batched": enc_batch, "prefill_ms": prefill_ms,
+        "prefill_first_ms": prefill_first_ms, "prefill_tokens": n_prompt,
         "device_ms_per_token_graph_loop": dev_ms_per_tok, "device_tokens_per_s_graph_loop": 1e3 / dev_ms_per_tok,
-        "weight_bytes_per_token": wbytes, "decode_weight_GBps_end_to_end": wbytes * K / dt / 1e9,
-        "model_load_s": load_s, "recv_load_s": recv_load_s, "weight_bcast_ms": bcast_ms,
-        "rccl_ranks": dist.get_world_size() if dist is not None else 1, "collective_backend": dist.get_backend() if dist is not None else None,
-        "rehearsal": ("MG4_BENCH_REHEARSAL=1: the ranks SHARE the visible GPU(s) and talk over gloo -- a functional run of the N > 1 path, every rate in this line is invalid as "
-                      "a measurement") if (world > 1 and os.environ.get("MG4_BENCH_REHEARSAL") == "1") else None,
-        "launcher": os.environ.get("MG4_BENCH_LAUNCHER", "external") if world > 1 else "none",
-        "weight_bcast": D.bcast_report(lstats), "load_mode": lstats["mode"],
         "roofline": roofline,
-    }
+    })
     # ---- extra leg (not the headline): decode rate at long contexts (the reference's default n_ctx is 2048, examples/main.cpp:128-131): random
     # prompt rows up to the context, then a device-resident greedy loop.  From 768 cached keys on the step uses the key-split attention launches
     # (k_attn_split_*).
@@ -640,10 +660,23 @@ def main():
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         except Exception as e:
             out["cpu_baseline"] = {"value": None, "error": str(e)}
-    if ctx is not None:
-        lib.minigpt4_free(ctx)
     if isinstance(out.get("configs3_share_per_gpu"), dict):
         out["configs3_share_per_gpu"].pop("_answers", None)
+    finish(out, lib, ctx, rank, dist)
+
+
+def dump_outputs(d: str, lib, ctx, piece: str) -> None:
+    """What the last timed step computed, as a caller of the path receives it: the logits of its 1-token eval and the piece it returned."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "logits.npy"), lib.amd_logits(ctx).astype(np.float32))
+    np.save(os.path.join(d, "piece_utf8.npy"), np.frombuffer(piece.encode("utf-8"), np.uint8).astype(np.float32))
+    log(f"[bench] outputs of the last timed step written to {d}")
+
+
+def finish(out: dict, lib, ctx, rank: int, dist) -> None:
+    if ctx is not None:
+        lib.minigpt4_free(ctx)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -1,7 +1,7 @@
-"""The EFFECTIVE ABI of the reference's Python binding, restated (TEST INFRASTRUCTURE): the ctypes argtypes / restypes `/root/reference/minigpt4/minigpt4_library.py`
-declares at :94-227 -- int32 where the C prototype says size_t / bool, POINTER(c_char) strings, void* contexts.  The reference is not mounted on the GPU box, so the GPU
-boundary test binds the library through THIS table; tests/test_cpu_refwrapper.py checks, where the reference is mounted, that the table equals what the unmodified
-reference module really declares (so it cannot drift)."""
+"""The EFFECTIVE ABI of the reference's Python binding, restated (TEST INFRASTRUCTURE): the ctypes argtypes / restypes the reference's `minigpt4/minigpt4_library.py`
+declares at :94-227 -- int32 where the C prototype says size_t / bool, POINTER(c_char) strings, void* contexts.  The boundary tests bind the library through THIS
+table; tests/test_cpu_refwrapper.py checks that it equals what the unmodified reference module declares, as recorded in tests/golden/reference_binding.json (so it
+cannot drift)."""
 import ctypes
 
 I32, F32, SIZE_T, VOID_PTR = ctypes.c_int32, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p

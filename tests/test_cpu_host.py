@@ -444,20 +444,19 @@ def test_model_load_fails_loudly_without_gpu_or_files(lib, tiny_files):
 
 
 def test_reference_binding_binds_unmodified(lib):
-    """Drop-in check: the reference's own ctypes wrapper resolves every symbol it declares against this library.
-    (Runs only where the reference checkout is mounted; never on the GPU box.)"""
-    ref = "/root/reference/minigpt4/minigpt4_library.py"
-    if not os.path.exists(ref):
-        pytest.skip("reference checkout not mounted")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("ref_minigpt4_library", ref)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    """Drop-in check: every symbol the reference's own ctypes wrapper declares (tests/golden/reference_binding.json) resolves against this library
+    and answers through the wrapper's declarations (tests/ref_abi.py, equal to the recorded ones: tests/test_cpu_refwrapper.py)."""
+    import json
+    import ref_abi
+    decl = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_binding.json")))["declarations"]
     so = os.path.join(ROOT, "minigpt4.cpp_amd", "libminigpt4.so")
-    wrapper = mod.MiniGPT4SharedLibrary(so)
-    assert wrapper.minigpt4_contains_eos_token("##") and wrapper.minigpt4_is_eos("abc###")
+    raw = ctypes.cdll.LoadLibrary(so)
+    for name in decl:
+        assert getattr(raw, name) is not None, name
+    wrapper = ref_abi.bind(so)
+    assert wrapper.minigpt4_contains_eos_token(ref_abi.cstr("##")) and wrapper.minigpt4_is_eos(ref_abi.cstr("abc###"))
     # (the reference's own minigpt4_error_code_to_string wrapper calls .decode() on a POINTER(c_char) and raises; use the raw symbol)
-    assert ctypes.cast(wrapper.library.minigpt4_error_code_to_string(19), ctypes.c_char_p).value == b"OpenCVNotLinked"
+    assert ctypes.cast(wrapper.minigpt4_error_code_to_string(19), ctypes.c_char_p).value == b"OpenCVNotLinked"
 
 
 def test_request_sharding_is_disjoint_and_complete():
