@@ -77,6 +77,18 @@ MINIGPT4_API int minigpt4_amd_eval_batch(struct MiniGPT4Context *ctx, const int3
  * over workgroups (w2), v_dot4 multi-row launches, v_dot4 mixed-type launches, per-matrix k_mul_mat launches, layers on the int8-MFMA set launches (B >= 5)}.  0 / 1. */
 MINIGPT4_API int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]);
 
+/* ---- context shift (llama.cpp's answer to a full context) -------------------------------------------------------------------------------
+ * The reference fails every add once n_past + n > n_ctx (FailedToAddString / FailedToAddEmbedding).  A shift keeps the conversation: rows [n_keep, n_keep + n_discard)
+ * of the SELECTED conversation are dropped, the rows above slide down in place and their cached keys are re-rotated by -n_discard positions (RoPE is relative).
+ * Pending prompt rows are evaluated first, at their current positions.  The last logits stay valid: the next sample uses them.  Shifted keys are rounded to fp16 a
+ * second time, so a shifted history is close to, not bit-identical with, one computed at the new positions.
+ * minigpt4_amd_shift_context: 0, or 1 (n_keep < 0, n_discard < 0, n_keep + n_discard > n_past; text in minigpt4_amd_last_error) with the conversation untouched.
+ * minigpt4_amd_set_context_shift: the automatic policy of this context; n_keep < 0 = off (the default, reference behaviour).  When on, an add that would overflow
+ * first shifts by max(n_past + n - n_ctx, (n_past - n_keep) / 2) rows, and minigpt4_amd_end_chat_batch / _eval_batch shift a full conversation and advance it.  An
+ * add of more than n_ctx - n_keep rows still fails and shifts nothing.  0 / 1 (no context). */
+MINIGPT4_API int minigpt4_amd_shift_context(struct MiniGPT4Context *ctx, int n_keep, int n_discard);
+MINIGPT4_API int minigpt4_amd_set_context_shift(struct MiniGPT4Context *ctx, int n_keep);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

@@ -50,6 +50,9 @@ MINIGPT4_API int minigpt4_amd_bench_attn_f32_b(int heads, int hd, int nq, int nk
 MINIGPT4_API void minigpt4_amd_test_set_attn_qt(int qt);
 /* the F16 feed-forward pair launch: out_h[N][n_out] = fp16(silu_table(w1 x) * (w3 x)) (uint16 bit patterns), w = w1 then w3 as fp16 [n_out][n_in]; 4 = shape outside the path */
 MINIGPT4_API int minigpt4_amd_test_f16_silu_pair(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, unsigned short *out_h, float *out_f);
+/* the context shift's kernel (launch_kv_shift) on host fp16 caches k / v = [n_layer][n_ctx][n_embd] (uint16 bit patterns, shifted in place): rows [n_keep + n_discard, n_rows)
+ * move down by n_discard, keys re-rotated by -n_discard positions with the engine's RoPE table.  ms (may be NULL): hipEvent time of the launch.  1 = bad arguments */
+MINIGPT4_API int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, int n_rows, int n_keep, int n_discard, uint16_t *k, uint16_t *v, float *ms);
 /* Micro-benchmark of the prompt-row attention on a synthetic fp16 K / V cache (tools/timeline_attn_prefill.py); _timeline_attn: its stamps in a -DMG4_TIMELINE build */
 MINIGPT4_API int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int iters, float *us_per_launch);
 MINIGPT4_API int minigpt4_amd_timeline_attn(unsigned long long *out, int max_workgroups);

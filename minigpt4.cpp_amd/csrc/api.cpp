@@ -269,6 +269,15 @@ int minigpt4_amd_eval_batch(struct MiniGPT4Context *ctx, const int32_t *slots, i
         return 0;
     });
 }
+// ---- context shift ----------------------------------------------------------------------------------------------------------------------
+int minigpt4_amd_shift_context(struct MiniGPT4Context *ctx, int n_keep, int n_discard) {
+    if (!ctx) { set_last_error("shift_context: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->shift_context(n_keep, n_discard); });
+}
+int minigpt4_amd_set_context_shift(struct MiniGPT4Context *ctx, int n_keep) {
+    if (!ctx) { set_last_error("set_context_shift: no context"); return 1; }
+    return guarded(1, [&]() -> int { E_(ctx)->set_context_shift(n_keep); return 0; });
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

@@ -596,11 +596,10 @@ void Engine::alloc_buffers() {
     auto takeh = [&](size_t n) { return reinterpret_cast<__half *>(buf_arena_.take(n * 2)); };
     kc_ = takeh(S * L * C * E); vc_ = takeh(S * L * C * E);                // [conversation][layer][n_ctx][n_embd]
     HIP_CHECK(hipMemset(kc_, 0, S * L * C * E * 2)); HIP_CHECK(hipMemset(vc_, 0, S * L * C * E * 2));
-    // RoPE table, exactly ggml's iteration: theta = pos; theta *= theta_scale per pair (fp32), cosf/sinf
+    // RoPE table, exactly ggml's iteration (rope_tables; the context shift reads row n_discard of the same table)
     {
-        std::vector<float> c(C * (hd / 2)), s(C * (hd / 2));
-        const float theta_scale = powf(10000.0f, -2.0f / (float)hd);
-        for (size_t p = 0; p < C; p++) { float theta = (float)p; for (size_t i = 0; i < hd / 2; i++) { c[p * (hd / 2) + i] = cosf(theta); s[p * (hd / 2) + i] = sinf(theta); theta *= theta_scale; } }
+        std::vector<float> c, s;
+        rope_tables((int)C, (int)hd, c, s);
         cos_ = takef(c.size()); sin_ = takef(s.size());
         HIP_CHECK(hipMemcpy(cos_, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(sin_, s.data(), s.size() * 4, hipMemcpyHostToDevice));
     }
@@ -1222,8 +1221,11 @@ int Engine::flush() {
 
 int Engine::add_tokens(const std::vector<int> &tokens, bool flush_now) {
     Conversation &cv = conv_[(size_t)cur_];
-    if (cv.n_past + (int)tokens.size() > n_ctx_) { set_last_error("context overflow: n_past + n_tokens > n_ctx"); MG4_ERR("Failed to add string"); return E_FailedToAddString; }
-    for (int t : tokens) if (t < 0 || t >= (int)llm_.n_vocab) { set_last_error("token id out of range"); MG4_ERR("Failed to add string"); return E_FailedToAddString; }
+    const bool ids_ok = std::all_of(tokens.begin(), tokens.end(), [&](int t) { return t >= 0 && t < (int)llm_.n_vocab; });
+    if (cv.n_past + (int)tokens.size() > n_ctx_ && !(ids_ok && make_room((int)tokens.size()) == 0)) {
+        set_last_error("context overflow: n_past + n_tokens > n_ctx"); MG4_ERR("Failed to add string"); return E_FailedToAddString;
+    }
+    if (!ids_ok) { set_last_error("token id out of range"); MG4_ERR("Failed to add string"); return E_FailedToAddString; }
     cv.pend_tok.insert(cv.pend_tok.end(), tokens.begin(), tokens.end());
     cv.n_past += (int)tokens.size();
     if (flush_now || !defer_) { if (flush()) return E_FailedToAddString; }
@@ -1232,12 +1234,38 @@ int Engine::add_tokens(const std::vector<int> &tokens, bool flush_now) {
 int Engine::add_string(const std::string &s) { return add_tokens(tok_.tokenize(s, true)); }
 int Engine::add_embedding(const float *data, int n_rows) {
     Conversation &cv = conv_[(size_t)cur_];
-    if (n_rows <= 0 || cv.n_past + n_rows > n_ctx_) { set_last_error("context overflow: n_past + n_rows > n_ctx"); MG4_ERR("Failed to add embedding"); return E_FailedToAddEmbedding; }
+    if (n_rows <= 0 || (cv.n_past + n_rows > n_ctx_ && make_room(n_rows))) {
+        set_last_error("context overflow: n_past + n_rows > n_ctx"); MG4_ERR("Failed to add embedding"); return E_FailedToAddEmbedding;
+    }
     cv.pend_tok.insert(cv.pend_tok.end(), (size_t)n_rows, -1);
     cv.pend_embd.insert(cv.pend_embd.end(), data, data + (size_t)n_rows * llm_.n_embd);
     cv.n_past += n_rows;
     if (!defer_) { if (flush()) return E_FailedToAddEmbedding; }
     return E_None;
+}
+// The arguments are checked against n_past before the flush (after it n_committed == n_past), so a refused call evaluates nothing and moves nothing.
+// The kernel rewrites rows in place on stream_: a captured decode step replays at the new position (eval_chunk writes d_npast_, and re-captures when
+// the key-split choice flips back below attn_split_t_), the batched step reads positions from d_npast_ too, parity mode shares the caches.
+int Engine::shift_context(int n_keep, int n_discard) {
+    Conversation &cv = conv_[(size_t)cur_];
+    if (n_keep < 0 || n_discard < 0 || n_keep + n_discard > cv.n_past) {
+        set_last_error("shift_context: need n_keep >= 0, n_discard >= 0 and n_keep + n_discard <= n_past"); return 1;
+    }
+    if (n_discard == 0) return 0;
+    if (weights_missing() || flush()) return 1;
+    const size_t L = layers_.size(), C = (size_t)n_ctx_, E = llm_.n_embd;
+    launch_kv_shift(kc_ + (size_t)cur_ * L * C * E, vc_ + (size_t)cur_ * L * C * E, (int)L, n_ctx_, (int)E, (int)(E / llm_.n_head), n_keep, n_discard, cv.n_committed,
+                    cos_, sin_, stream_);
+    cv.n_committed -= n_discard; cv.n_past -= n_discard;
+    return 0;
+}
+int Engine::make_room(int n) {
+    Conversation &cv = conv_[(size_t)cur_];
+    if (shift_keep_ < 0 || n > n_ctx_ - shift_keep_) return 1;
+    if (cv.n_past + n <= n_ctx_) return 0;
+    if (flush()) return 1;
+    const int need = cv.n_past + n - n_ctx_;
+    return shift_context(shift_keep_, std::max(need, (cv.n_committed - shift_keep_) / 2));
 }
 const float *Engine::logits_host() {
     if (flush()) throw HipError{hipErrorUnknown, "deferred evaluation failed", __FILE__, __LINE__};
@@ -1407,7 +1435,8 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     int B = 0;
     for (int i = 0; i < n; i++) {
         Conversation &cv = conv_[(size_t)slots[i]];
-        if (cv.n_past + 1 > n_ctx_) continue;                               // context full: sampled, not advanced
+        cur_ = slots[i];
+        if (cv.n_past + 1 > n_ctx_ && make_room(1)) continue;               // context full (and no automatic shift): sampled, not advanced
         h_bstage_[B] = forced ? forced[i] : ids_out[i]; h_bstage_[MAX_CONVERSATIONS + B] = slots[i]; h_bstage_[2 * MAX_CONVERSATIONS + B] = cv.n_committed; B++;
     }
     if (!B) return 0;

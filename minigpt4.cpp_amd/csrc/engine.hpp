@@ -65,6 +65,14 @@ public:
     void reset() { Conversation &c = conv_[(size_t)cur_]; c.pend_tok.clear(); c.pend_embd.clear(); c.n_past = 0; c.n_committed = 0; }
     void sync();
     hipStream_t stream() const { return stream_; }
+    // ---- context shift (llama.cpp's answer to a full context), selected conversation: pending rows are evaluated first, then rows
+    // [n_keep, n_keep + n_discard) are dropped and the rows above slide down in place, their keys re-rotated by -n_discard positions
+    // (launch_kv_shift).  The last logits stay valid; captured graphs too (positions are read from d_npast_).  0, or 1 with last_error set and the
+    // conversation untouched (n_keep < 0, n_discard < 0, n_keep + n_discard > n_past).
+    int shift_context(int n_keep, int n_discard);
+    // automatic policy (per context, off = -1 by default): an add that would overflow first shifts by max(need, (n_past - n_keep) / 2) rows; a full
+    // conversation in decode_batch is shifted and advanced.  An add longer than n_ctx - n_keep still fails.
+    void set_context_shift(int n_keep) { shift_keep_ = n_keep < 0 ? -1 : n_keep; }
 
     int n_vocab() const { return (int)llm_.n_vocab; }
     int n_embd() const { return (int)llm_.n_embd; }
@@ -149,6 +157,8 @@ private:
     };
     std::vector<Conversation> conv_ = std::vector<Conversation>(1);
     int cur_ = 0;
+    int shift_keep_ = -1;                  // set_context_shift
+    int make_room(int n);                  // the automatic shift for n more rows of the selected conversation: 0 = room made (or already there), 1 = not
     bool defer_ = true; int max_chunk_ = 512;
     void release_buffers();
 

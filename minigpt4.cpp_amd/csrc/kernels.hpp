@@ -1,5 +1,7 @@
 // Host-callable launchers of the gfx950 kernels (llm_kernels.hip, vision_kernels.hip).
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 namespace mg4 {
@@ -121,6 +123,13 @@ void launch_get_rows(int type, const uint8_t *raw_table, int K, const int *token
 // q,k,v: [N][E] f32.  Rotates q in place, writes rotated k and v as fp16 into the caches at position *n_past + t.
 void launch_rope_kv(float *q, const float *k, const float *v, int N, int n_head, int hd, const int *n_past, const float *cos_tab,
                     const float *sin_tab, __half *kcache, __half *vcache, hipStream_t s);
+// host: the RoPE tables every launch above reads, [n_ctx][hd / 2] fp32 cos / sin with ggml's iterative theta
+void rope_tables(int n_ctx, int hd, std::vector<float> &cos_out, std::vector<float> &sin_out);
+// context shift of ONE conversation: caches kc_slot / vc_slot = [n_layer][n_ctx][E] fp16.  Rows [n_keep + n_discard, n_rows) move to row - n_discard (in place, any
+// overlap); moved keys are rotated by -n_discard positions with the table row cos / sin[n_discard], values copied bit for bit.  Rows below n_keep are not touched.
+// Launches nothing when no row moves.
+void launch_kv_shift(__half *kc_slot, __half *vc_slot, int n_layer, int n_ctx, int E, int hd, int n_keep, int n_discard, int n_rows, const float *cos_tab,
+                     const float *sin_tab, hipStream_t s);
 // out[t][h*hd+i] = softmax(K q / sqrt(hd)) V over keys 0..*n_past+t.  caches: [n_ctx][E] fp16.
 // fused (decode, N == 1): q,k,v are the raw projections; RoPE of q/k and the KV append happen inside the kernel.
 // !fused: launch_rope_kv must have run (q rotated in place, caches appended).

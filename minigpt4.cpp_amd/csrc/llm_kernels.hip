@@ -1546,6 +1546,75 @@ void launch_rope_kv(float *q, const float *k, const float *v, int N, int n_head,
                     __half *kcache, __half *vcache, hipStream_t s) {
     hipLaunchKernelGGL(k_rope_kv, dim3((unsigned)N, (unsigned)n_head), dim3((unsigned)(hd / 2)), 0, s, q, k, v, n_head * hd, hd, n_past, cos_tab, sin_tab, kcache, vcache);
 }
+// The table k_rope_kv reads, exactly ggml's iteration: theta = pos; theta *= theta_scale per pair (fp32), cosf/sinf.  [n_ctx][hd / 2] each
+void rope_tables(int n_ctx, int hd, std::vector<float> &c, std::vector<float> &s) {
+    const size_t C = (size_t)n_ctx, P = (size_t)hd / 2;
+    c.assign(C * P, 0.0f); s.assign(C * P, 0.0f);
+    const float theta_scale = powf(10000.0f, -2.0f / (float)hd);
+    for (size_t p = 0; p < C; p++) { float theta = (float)p; for (size_t i = 0; i < P; i++) { c[p * P + i] = cosf(theta); s[p * P + i] = sinf(theta); theta *= theta_scale; } }
+}
+
+// =====================================================================================================================
+// Context shift: rows [n_keep + n_discard, n_rows) of one conversation's caches move down by n_discard, in place; the moved keys are rotated by
+// -n_discard positions (RoPE is relative: a key rotated to position p, then by -d, is the key at p - d up to the fp16 rounding of both steps).
+// Lane = (K or V, layer, 16-byte column group): it owns that column of every row of its layer and walks the rows upwards in batches of
+// b = min(n_discard, KV_SHIFT_ROWS).  All sources of a batch are loaded before any destination is stored; with b <= n_discard the destinations
+// lie below the batch's sources, and later batches only read rows above every row written so far -- correct for every n_discard >= 1.  A
+// wave's 64 lanes cover 1 KiB of one row (coalesced 16-byte accesses); the kernel is a pure HBM stream.
+// =====================================================================================================================
+constexpr int KV_SHIFT_ROWS = 8, KV_SHIFT_THREADS = 64;
+__global__ __launch_bounds__(KV_SHIFT_THREADS) void k_kv_shift(__half *__restrict__ kc, __half *__restrict__ vc, int n_layer, int n_ctx, int E, int hd, int n_keep,
+                                                             int n_discard, int n_rows, const float *__restrict__ cos_tab, const float *__restrict__ sin_tab) {
+    const int G = E / 8;                                                   // 16-byte column groups per row
+    const long long per = (long long)n_layer * G;
+    const long long lane = (long long)blockIdx.x * KV_SHIFT_THREADS + threadIdx.x;
+    if (lane >= 2 * per) return;
+    const bool is_k = lane < per;
+    const long long lg = is_k ? lane : lane - per;
+    const int layer = (int)(lg / G), g = (int)(lg % G);
+    __half *col = (is_k ? kc : vc) + (size_t)layer * n_ctx * E + (size_t)g * 8;
+    float c[4] = {1.0f, 1.0f, 1.0f, 1.0f}, s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (is_k) {                                                            // a group's 4 pairs lie inside one head (hd % 8 == 0)
+        const size_t t0 = (size_t)n_discard * (hd / 2) + (size_t)((g * 8) % hd) / 2;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { c[j] = cos_tab[t0 + j]; s[j] = sin_tab[t0 + j]; }
+    }
+    const int b = min(n_discard, KV_SHIFT_ROWS);
+    for (int r0 = n_keep + n_discard; r0 < n_rows; r0 += b) {
+        const int nb = min(b, n_rows - r0);
+        uint4 buf[KV_SHIFT_ROWS];
+#pragma unroll
+        for (int t = 0; t < KV_SHIFT_ROWS; t++) if (t < nb) buf[t] = *reinterpret_cast<const uint4 *>(col + (size_t)(r0 + t) * E);
+#pragma unroll
+        for (int t = 0; t < KV_SHIFT_ROWS; t++) {
+            if (t >= nb) continue;
+            uint4 u = buf[t];
+            if (is_k) {
+                unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    // fp16 x fp32 products are exact in double: the sum is rounded once (then to fp16, within one fp16 ulp of the exact rotation even where
+                    // the two terms cancel -- fp32 products would not be)
+                    const float2 kf = __half22float2(*reinterpret_cast<const __half2 *>(&w[j]));
+                    const double k0 = kf.x, k1 = kf.y, cj = c[j], sj = s[j];
+                    const __half2 r = __floats2half2_rn((float)(k0 * cj + k1 * sj), (float)(k1 * cj - k0 * sj));
+                    w[j] = *reinterpret_cast<const unsigned *>(&r);
+                }
+                u = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            *reinterpret_cast<uint4 *>(col + (size_t)(r0 + t - n_discard) * E) = u;
+        }
+    }
+}
+void launch_kv_shift(__half *kc_slot, __half *vc_slot, int n_layer, int n_ctx, int E, int hd, int n_keep, int n_discard, int n_rows, const float *cos_tab,
+                     const float *sin_tab, hipStream_t s) {
+    if (n_discard < 1 || n_keep < 0 || n_keep + n_discard >= n_rows) return;   // no row moves
+    if (n_rows > n_ctx || n_discard > n_ctx - 1 || E % 8 || hd % 8 || E % hd) throw HipError{hipErrorInvalidValue, "launch_kv_shift: bad shape", __FILE__, __LINE__};
+    note_kernel("k_kv_shift");
+    const long long lanes = 2LL * n_layer * (E / 8);
+    hipLaunchKernelGGL(k_kv_shift, dim3((unsigned)((lanes + KV_SHIFT_THREADS - 1) / KV_SHIFT_THREADS)), dim3(KV_SHIFT_THREADS), 0, s, kc_slot, vc_slot, n_layer, n_ctx, E, hd,
+                       n_keep, n_discard, n_rows, cos_tab, sin_tab);
+}
 
 // =====================================================================================================================
 // causal attention over the fp16 KV cache.  One 512-thread workgroup per (head, query token).

@@ -510,6 +510,31 @@ int minigpt4_amd_test_f16_silu_pair(const float *x, const void *w_f16, int64_t N
         return 0;
     });
 }
+// The context shift's kernel (launch_kv_shift) on host caches [n_layer][n_ctx][n_embd] fp16, with the RoPE table the engine builds (rope_tables)
+int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, int n_rows, int n_keep, int n_discard, uint16_t *k, uint16_t *v, float *ms) {
+    if (!k || !v || n_layer < 1 || n_ctx < 1 || n_head < 1 || n_embd % n_head || (n_embd / n_head) % 8 || n_rows < 0 || n_rows > n_ctx || n_keep < 0 || n_discard < 0 ||
+        n_keep + n_discard > n_rows) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const int hd = n_embd / n_head;
+        const size_t n = (size_t)n_layer * n_ctx * n_embd;
+        std::vector<float> c, s;
+        rope_tables(n_ctx, hd, c, s);
+        DevBuf dk(n * 2), dv(n * 2), dc(c.size() * 4), ds(s.size() * 4);
+        HIP_CHECK(hipMemcpy(dk.p, k, n * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, n * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(ds.p, s.data(), s.size() * 4, hipMemcpyHostToDevice));
+        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+        HIP_CHECK(hipEventRecord(a, nullptr));
+        launch_kv_shift(dk.as<__half>(), dv.as<__half>(), n_layer, n_ctx, n_embd, hd, n_keep, n_discard, n_rows, dc.as<float>(), ds.as<float>(), nullptr);
+        HIP_CHECK(hipEventRecord(b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
+        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        if (ms) *ms = t;
+        HIP_CHECK(hipMemcpy(k, dk.p, n * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, n * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // Micro-benchmark of the prompt-row attention (launch_attn_prefill): N query rows at positions n_past .. n_past + N - 1 of an fp16 K / V cache filled with synthetic rows
 int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int iters, float *us_per_launch) {
     if (const char *w8 = getenv("MINIGPT4_ATTN_PREFILL_W8")) set_attn_prefill_w8(atoi(w8));        // micro-benchmark only (no engine in this process)

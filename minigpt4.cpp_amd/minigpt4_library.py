@@ -199,6 +199,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_end_chat_batch.argtypes = [VOID_PTR, INT_PTR, I32, P(ctypes.c_char_p), F32, I32, F32, F32, F32, I32, F32, F32]
         L.minigpt4_amd_eval_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR]
         L.minigpt4_amd_batch_path.argtypes = [VOID_PTR, INT_PTR]
+        L.minigpt4_amd_shift_context.argtypes = [VOID_PTR, I32, I32]
+        L.minigpt4_amd_set_context_shift.argtypes = [VOID_PTR, I32]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -214,6 +216,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_quantize.argtypes = [FLOAT_PTR, FLOAT_PTR, ctypes.c_int64, ctypes.c_int64, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_test_gemm_f16.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_gemm_f16_skinny.argtypes = L.minigpt4_amd_test_gemm_f16.argtypes
+        L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
         L.minigpt4_amd_vocab_load.argtypes = [CHAR_PTR]
         L.minigpt4_amd_vocab_load.restype = VOID_PTR
@@ -376,6 +379,28 @@ class MiniGPT4SharedLibrary:
         if self.library.minigpt4_amd_eval_batch(ctx.ptr, sl, n, tk, out):
             raise RuntimeError("minigpt4_amd_eval_batch failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return [int(x) for x in out]
+
+    def amd_shift_context(self, ctx, n_keep: int, n_discard: int):
+        """Context shift of the selected conversation: drop rows [n_keep, n_keep + n_discard), slide the rest down, re-rotate their keys (include/minigpt4_amd.h)."""
+        if self.library.minigpt4_amd_shift_context(ctx.ptr, int(n_keep), int(n_discard)):
+            raise RuntimeError("shift_context failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+
+    def amd_set_context_shift(self, ctx, n_keep: int):
+        """Automatic context shift of this context when an add would overflow, keeping the first n_keep rows; n_keep < 0 = off (the default)."""
+        if self.library.minigpt4_amd_set_context_shift(ctx.ptr, int(n_keep)):
+            raise RuntimeError("set_context_shift failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+
+    def amd_test_kv_shift(self, k: np.ndarray, v: np.ndarray, n_head: int, n_rows: int, n_keep: int, n_discard: int):
+        """launch_kv_shift on fp16 caches [n_layer][n_ctx][n_embd]; returns (k, v, ms) -- shifted copies and the launch's hipEvent time."""
+        k = np.ascontiguousarray(k, np.float16).copy()
+        v = np.ascontiguousarray(v, np.float16).copy()
+        assert k.ndim == 3 and k.shape == v.shape
+        ms = ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_kv_shift(k.shape[0], k.shape[1], k.shape[2], n_head, n_rows, n_keep, n_discard, k.ctypes.data_as(VOID_PTR),
+                                                     v.ctypes.data_as(VOID_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_shift rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return k, v, float(ms.value)
 
     def amd_batch_path(self, ctx) -> dict:
         """Launch kinds of the batched step as last built (include/minigpt4_amd.h: minigpt4_amd_batch_path)."""

@@ -266,7 +266,7 @@ class _Pool:
 def write_llm_file(path: str, cfg: LLMConfig, seed: int = 1234, std: float = 0.02,
                    unique_layers: Optional[int] = None, vocab: Optional[List[Tuple[bytes, float]]] = None,
                    fast: bool = False, resid_scale: float = 1.0, rotate_layers: bool = False, tok_std: Optional[float] = None,
-                   output_tie: float = 0.0) -> None:
+                   output_tie: float = 0.0, qk_scale: float = 1.0) -> None:
     """Write a GGJT-v3 file with Gaussian weights.  `unique_layers` < n_layer re-uses the quantised bytes
     of layer (i % unique_layers) for layer i (bench-size files: same byte volume, generation in seconds).
     `resid_scale` multiplies the two matrices that write into the residual stream (attention.wo, feed_forward.w2) -- the
@@ -278,7 +278,9 @@ def write_llm_file(path: str, cfg: LLMConfig, seed: int = 1234, std: float = 0.0
     `tok_std`: standard deviation of tok_embeddings (default `std`); ~1 keeps the residual stream correlated with the current token through a deep stack.
     `output_tie` = beta in (0, 1]: output row u = std * (beta * e[p[u]] + sqrt(1 - beta^2) * r_u), e = the unit-variance token embeddings, p a fixed random permutation,
     r Gaussian -- the logit of the token u with p[u] == current token stands out of the Gaussian rest by a margin beta controls: DECISIVE greedy decisions (top-2 margin
-    far above the comparison tolerance) on a walk through the permutation instead of near-ties between 32000 i.i.d. logits."""
+    far above the comparison tolerance) on a walk through the permutation instead of near-ties between 32000 i.i.d. logits.
+    `qk_scale` multiplies attention.wq and attention.wk: the attention scores grow by its square, so the softmax is sharp and WHICH keys sit at which positions decides the
+    logits (tests of the context shift, whose whole point is the positions of cached keys)."""
     rng = np.random.default_rng(seed)
     types, shapes = llm_tensor_types(cfg), llm_tensor_shapes(cfg)
     vocab = vocab if vocab is not None else synth_vocab(cfg.n_vocab)
@@ -318,6 +320,8 @@ def write_llm_file(path: str, cfg: LLMConfig, seed: int = 1234, std: float = 0.0
             x = x * np.float32(tok_std if (name == "tok_embeddings.weight" and tok_std is not None) else std)
         if resid_scale != 1.0 and (name.endswith("attention.wo.weight") or name.endswith("feed_forward.w2.weight")):
             x = x * np.float32(resid_scale)
+        if qk_scale != 1.0 and (name.endswith("attention.wq.weight") or name.endswith("attention.wk.weight")):
+            x = x * np.float32(qk_scale)
         raw = Q.quantize(t, x)
         if key is not None:
             cache[key] = raw
