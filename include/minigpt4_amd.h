@@ -73,6 +73,12 @@ MINIGPT4_API int minigpt4_amd_end_chat_batch(struct MiniGPT4Context *ctx, const 
  * NULL) receives that own greedy choice.  Lets a test / bench leg compare every step's logits of B batched conversations with B independent oracle conversations fed the
  * same ids (reference behaviour: one independent conversation per context, minigpt4.cpp:2513-2521, 2704-2718).  0 / 1. */
 MINIGPT4_API int minigpt4_amd_eval_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const int32_t *tokens, int32_t *greedy_out);
+/* The queued prompt rows (system prompt, image turn, question...) of n DISTINCT conversations in as few passes over the weights as possible: their rows are packed
+ * into chunks of at most n_batch rows, one pass per chunk.  Afterwards each listed conversation is where its own evaluation would have left it (everything queued
+ * evaluated, its last-row logits and greedy token current); one with nothing queued is skipped and keeps its logits.  0, or 1 on a bad slot list (duplicates,
+ * out of range, n < 1 or n > the number of conversations) or a device error (text in minigpt4_amd_last_error; a failed pass drops the queued rows of every
+ * listed conversation, as a failed evaluation of one does). */
+MINIGPT4_API int minigpt4_amd_prefill_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n);
 /* Launch kinds of the batched step as last built (eager or at graph capture): out = {rows, k_matvec_ri launches, k_matvec_ri_mix launches, k_matvec_ri launches that split K
  * over workgroups (w2), v_dot4 multi-row launches, v_dot4 mixed-type launches, per-matrix k_mul_mat launches, layers on the int8-MFMA set launches (B >= 5)}.  0 / 1. */
 MINIGPT4_API int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]);

@@ -53,6 +53,18 @@ MINIGPT4_API int minigpt4_amd_test_f16_silu_pair(const float *x, const void *w_f
 /* the context shift's kernel (launch_kv_shift) on host fp16 caches k / v = [n_layer][n_ctx][n_embd] (uint16 bit patterns, shifted in place): rows [n_keep + n_discard, n_rows)
  * move down by n_discard, keys re-rotated by -n_discard positions with the engine's RoPE table.  ms (may be NULL): hipEvent time of the launch.  1 = bad arguments */
 MINIGPT4_API int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, int n_rows, int n_keep, int n_discard, uint16_t *k, uint16_t *v, float *ms);
+/* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
+ * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
+ * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,
+ * 2 = k_attn_prefill_h QS 2, 3 = QS 1 (both sides), 4 = the exact-f32 kernel (both sides per segment).  *seg_launched = 1 when the one segmented launch ran.
+ * out_h_seg / out_h_ref (both or neither; [N][E] fp16 bits): the launchers may store fp16 rows there instead (the F16 wo's input); wrote_h[0] / [1] = whether the
+ * segmented side / every per-segment launch did.  The caller's form / f16 settings are restored.  1 = bad arguments */
+MINIGPT4_API int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slots, const uint16_t *kc, const uint16_t *vc, int n_seg, const int32_t *segs, const float *q,
+                                                    int form, float *out_seg, float *out_ref, int *seg_launched, uint16_t *out_h_seg, uint16_t *out_h_ref, int *wrote_h);
+/* RoPE + cache append of packed rows (k_rope_kv_seg; ks > 1: its slab form k_rope_kv_seg_slabs over ks copies of q | k | v) against k_rope_kv (_slabs) per segment.  segs as
+ * above; q / k / v = [N][n_head * hd]; outputs: rotated q rows [N][E] and the caches [n_slots][n_ctx][E] (fp16 bits, zero where nothing was appended) of each side */
+MINIGPT4_API int minigpt4_amd_test_rope_kv_seg(int n_head, int hd, int n_ctx, int n_slots, int n_seg, const int32_t *segs, const float *q, const float *k, const float *v, int ks,
+                                               float *q_seg, uint16_t *kc_seg, uint16_t *vc_seg, float *q_ref, uint16_t *kc_ref, uint16_t *vc_ref);
 /* Micro-benchmark of the prompt-row attention on a synthetic fp16 K / V cache (tools/timeline_attn_prefill.py); _timeline_attn: its stamps in a -DMG4_TIMELINE build */
 MINIGPT4_API int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int iters, float *us_per_launch);
 MINIGPT4_API int minigpt4_amd_timeline_attn(unsigned long long *out, int max_workgroups);

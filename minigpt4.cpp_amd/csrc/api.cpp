@@ -269,6 +269,10 @@ int minigpt4_amd_eval_batch(struct MiniGPT4Context *ctx, const int32_t *slots, i
         return 0;
     });
 }
+int minigpt4_amd_prefill_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n) {
+    if (!ctx) { set_last_error("prefill_batch: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->prefill_batch(slots, n); });
+}
 // ---- context shift ----------------------------------------------------------------------------------------------------------------------
 int minigpt4_amd_shift_context(struct MiniGPT4Context *ctx, int n_keep, int n_discard) {
     if (!ctx) { set_last_error("shift_context: no context"); return 1; }

@@ -79,7 +79,8 @@ void Engine::release_buffers() {
     if (h_argmax_) HIP_IGNORE(hipHostFree(h_argmax_));
     if (h_bstage_) HIP_IGNORE(hipHostFree(h_bstage_));
     if (h_logits_) HIP_IGNORE(hipHostFree(h_logits_));
-    h_argmax_ = nullptr; h_bstage_ = nullptr; h_logits_ = nullptr; logits_host_slot_ = -1;
+    if (h_seg_) HIP_IGNORE(hipHostFree(h_seg_));
+    h_argmax_ = nullptr; h_bstage_ = nullptr; h_logits_ = nullptr; h_seg_ = nullptr; logits_host_slot_ = -1;
     buf_arena_.release();
 }
 Engine::~Engine() {
@@ -591,6 +592,7 @@ void Engine::alloc_buffers() {
     sz(VB * (size_t)SPLITK_MAX * 257 * D * 4);
     sz(VB * 9 * NQ * 2304 * 4); sz(VB * 257 * 1536 * 4 * (size_t)std::max(1, v_ncross_)); sz(VB * NQ * 768 * 4); sz(VB * NQ * 768 * 4); sz(VB * NQ * 768 * 2);
     sz(VB * NQ * (size_t)std::max(v_qi_, 768) * 2 * 4); sz(VB * NQ * (size_t)v_out_ * 4); sz(1 << 20);
+    sz(seg_ints() * 4);
     buf_arena_.alloc(total);
     auto takef = [&](size_t n) { return reinterpret_cast<float *>(buf_arena_.take(n * 4)); };
     auto takeh = [&](size_t n) { return reinterpret_cast<__half *>(buf_arena_.take(n * 2)); };
@@ -667,6 +669,9 @@ void Engine::alloc_buffers() {
     // LOAD_RECV: weights_received()
     if (load_mode_ == LOAD_FULL) for (size_t b = 0; b < VB; b++) HIP_CHECK(hipMemcpy(vi_qtok_rep_ + b * NQ * 768, v_qtok_, NQ * 768 * 4, hipMemcpyDeviceToDevice));
     vi_c_a1_ = takef(VB * NQ * 768); vi_c_qq_ = takef(VB * NQ * 768); vi_c_a1_h_ = takeh(VB * NQ * 768);
+    // prefill_batch: the packed chunk's tables (segments, finish rows, last rows, row table, two attention work lists) and their pinned staging
+    d_seg_ = reinterpret_cast<int *>(buf_arena_.take(seg_ints() * 4));
+    HIP_CHECK(hipHostMalloc((void **)&h_seg_, seg_ints() * 4, hipHostMallocDefault));
     if (v_generic_) alloc_vision_generic();
     MG4_INFO("KV cache %.1f MB (fp16, n_ctx %d, %zu conversation%s), activation arena %.1f MB", 2.0 * S * L * C * E * 2 / 1048576.0, n_ctx_, S, S == 1 ? "" : "s", buf_arena_.used / 1048576.0);
 }
@@ -916,14 +921,18 @@ void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
     const size_t C = (size_t)n_ctx_, sl = (size_t)cur_;                     // everything below addresses the selected conversation's cache / scalars
     int *const d_npast = d_npast_ + sl, *const d_argmax = d_argmax_ + sl, *const d_feed = d_feed_ + sl;
     float *const logits = logits_ + sl * (size_t)V;
-    const bool dec = N == 1;
+    // seg_ (prefill_batch): the rows are the packed prompt rows of several conversations; only RoPE + cache append, the attention and the output rows change
+    const SegChunk *const sg = seg_;
+    const size_t seq_stride = layers_.size() * C * (size_t)E;
+    const bool dec = N == 1 && !sg;
     // feed: the row is the decode token kept in d_feed (greedy feedback / set by eval_chunk); otherwise the rows are described by d_tokens_ (id, or
     // -1 = an embedding row already sitting in x_) -- a chunk of exactly ONE embedding row must not pick up the stale decode token
     if (from_tokens) { SiteScope sc(this, "embed", (double)gt_nbytes(tok_type_, (size_t)E) * N, s); launch_get_rows(tok_type_, tok_raw_, E, feed ? d_feed : d_tokens_, N, x_, s); }
     auto fz = [&](int bit) { return dec && (fuse_mask_ >> bit & 1); };
     for (size_t il = 0; il < layers_.size(); il++) {
         const LayerW &L = layers_[il];
-        __half *kc = kc_ + (sl * layers_.size() + il) * C * E, *vc = vc_ + (sl * layers_.size() + il) * C * E;
+        const size_t sl_c = sg ? 0 : sl;                                     // packed rows: conversation 0's layer, the kernels add slot * seq_stride
+        __half *kc = kc_ + (sl_c * layers_.size() + il) * C * E, *vc = vc_ + (sl_c * layers_.size() + il) * C * E;
         const Prep p_attn{1, x_, L.attn_norm}, p_att{2, att_, nullptr}, p_ffn{1, x_, L.ffn_norm}, p_silu{3, h1_, h3_};
         {
             const QWeight *W3[3] = {&L.wq, &L.wk, &L.wv}; float *Y3[3] = {q_, k_, v_};
@@ -939,17 +948,24 @@ void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
         // algorithmic bytes of the attention site: the cached fp16 K and V rows of every head up to the current position
         bool att_in_xh = false;                                             // the attention kernel left fp16 rows in act_.xh
         std::optional<SiteScope> att_sc;
-        if (prof_on_) att_sc.emplace(this, "attention", 4.0 * (double)E * (double)(conv_[sl].n_committed + N), s);
+        if (prof_on_) att_sc.emplace(this, "attention", 4.0 * (double)E * (sg ? sg->key_rows : (double)(conv_[sl].n_committed + N)), s);
         if (dec && attn_split_now_) launch_attn_llm_split(q_, k_, v_, kc, vc, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, attn_ws_, attn_splits_, s);
         else if (dec) launch_attn_llm(q_, k_, v_, kc, vc, 1, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, true, s);
         else {
             if (pend_.ks > 1 && pend_.n == 3 && pend_.y[0] == q_ && pend_.y[1] == k_ && pend_.y[2] == v_ && !pend_.res[0] && !pend_.res[1] && !pend_.res[2] && pend_.stride == (long long)N * E) {
-                launch_rope_kv_slabs(pend_, N, H, hd, d_npast, cos_, sin_, kc, vc, s); pend_ = SlabSrc{};
-            } else { flush_pending(s); launch_rope_kv(q_, k_, v_, N, H, hd, d_npast, cos_, sin_, kc, vc, s); }
+                if (sg) launch_rope_kv_seg_slabs(pend_, N, H, hd, sg->rows, seq_stride, cos_, sin_, kc, vc, s);
+                else launch_rope_kv_slabs(pend_, N, H, hd, d_npast, cos_, sin_, kc, vc, s);
+                pend_ = SlabSrc{};
+            } else {
+                flush_pending(s);
+                if (sg) launch_rope_kv_seg(q_, k_, v_, N, H, hd, sg->rows, seq_stride, cos_, sin_, kc, vc, s);
+                else launch_rope_kv(q_, k_, v_, N, H, hd, d_npast, cos_, sin_, kc, vc, s);
+            }
             // an F16 wo at prompt sizes multiplies fp16(attention output): let the attention kernel store those rows itself (act_.xh), no conversion
             // launch
             const bool want_h = (f16_pair_ & 4) && L.wo.type == GT_F16 && N >= 512 && act_.xh && E % 128 == 0;
-            if (!(attn_prefill_ && launch_attn_prefill(q_, kc, vc, N, H, hd, d_npast, conv_[sl].n_committed + N, tabs_, att_, s, want_h ? act_.xh : nullptr, &att_in_xh)))
+            if (sg) attn_segments(*sg, kc, vc, want_h, &att_in_xh, s);
+            else if (!(attn_prefill_ && launch_attn_prefill(q_, kc, vc, N, H, hd, d_npast, conv_[sl].n_committed + N, tabs_, att_, s, want_h ? act_.xh : nullptr, &att_in_xh)))
                 launch_attn_llm(q_, k_, v_, kc, vc, N, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_, att_, false, s);
         }
         att_sc.reset();
@@ -981,6 +997,16 @@ void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
         mul_mat(L.w2, N, x_, E, x_, s, paired ? &p_h : &p_silu, fz(3), "w2", !dec);
     }
     flush_pending(s);
+    if (sg) {   // the last row of every conversation that ends in this chunk: one output pass over those rows, then each slot's logits / greedy id / position
+        if (sg->n_end > 0) {
+            launch_gather_rows(x_, sg->last, sg->n_end, E, att_, s);
+            const Prep p_last{1, att_, norm_};
+            mul_mat(output_, sg->n_end, blogits_, V, nullptr, s, &p_last, false, "output");
+            SiteScope sc(this, "finish", (double)V * 4 * sg->n_end, s);
+            launch_seg_finish(blogits_, V, sg->n_end, sg->fin, d_npast_, d_argmax_, d_feed_, logits_, s);
+        }
+        return;
+    }
     // only the last token's logits are kept (llama.cpp logits_all = false)
     const Prep p_out{1, x_ + (size_t)(N - 1) * E, norm_};
     mul_mat(output_, 1, logits, V, nullptr, s, &p_out, fz(4), "output");
@@ -1470,6 +1496,97 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
         if (logits_host_slot_ == sl) logits_host_slot_ = -1;
     }
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+    return 0;
+}
+
+// The segmented prompt attention of one packed chunk: one launch over every segment; when it declines (the exact-f32 kernel is selected, or the score
+// rows do not fit LDS), one launch of the single-conversation kernels per segment, with its rows, its cache and its position.
+void Engine::attn_segments(const SegChunk &sg, __half *kc, __half *vc, bool want_h, bool *att_in_xh, hipStream_t s) {
+    const int E = (int)llm_.n_embd, H = (int)llm_.n_head, hd = E / H;
+    if (attn_prefill_ && launch_attn_prefill_seg(q_, kc, vc, sg.att, H, hd, tabs_, att_, s, want_h ? act_.xh : nullptr, att_in_xh)) return;
+    *att_in_xh = false;
+    const size_t seq_stride = layers_.size() * (size_t)n_ctx_ * E;
+    for (int i = 0; i < sg.n_seg; i++) {
+        const int *g = sg.h_segs + 4 * i;
+        const size_t off = (size_t)g[1] * E, cs = (size_t)g[0] * seq_stride;
+        const int *np = sg.att.segs + 4 * i + 3;                            // the segment's first position, in device memory
+        if (!(attn_prefill_ && launch_attn_prefill(q_ + off, kc + cs, vc + cs, g[2], H, hd, np, g[3] + g[2], tabs_, att_ + off, s)))
+            launch_attn_llm(q_ + off, k_ + off, v_ + off, kc + cs, vc + cs, g[2], H, hd, np, n_ctx_, cos_, sin_, tabs_, att_ + off, false, s);
+    }
+}
+
+// Queued prompt rows of several conversations in one pass over the weights per chunk.  Rows do not depend on each other in the mat-muls (activations are
+// quantised per row), so the conversations' rows are packed like flush() packs one conversation's fragments; RoPE + cache append, the attention and the
+// output rows learn each row's conversation from the chunk's tables.  A conversation may continue in the next chunk at its advanced position.
+int Engine::prefill_batch(const int *slots, int n) {
+    if (!slots || n < 1 || n > (int)conv_.size()) { set_last_error("prefill_batch: bad slot list"); return 1; }
+    bool seen[MAX_CONVERSATIONS] = {false};
+    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= (int)conv_.size() || seen[slots[i]]) { set_last_error("prefill_batch: conversations must be distinct and in range"); return 1; } seen[slots[i]] = true; }
+    if (weights_missing()) return 1;
+    const int keep = cur_;
+    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; e->seg_ = nullptr; } } restore{this, keep};
+    auto drop_all = [&] { for (int i = 0; i < n; i++) { Conversation &cv = conv_[(size_t)slots[i]]; cv.pend_tok.clear(); cv.pend_embd.clear(); cv.n_past = cv.n_committed; } };
+    try {
+        // oracle-order arithmetic (parity mode) and the parity trace exist for the single-conversation pass only: one flush per conversation, in slot order
+        if (parity_ || trace_file_) {
+            for (int i = 0; i < n; i++) { cur_ = slots[i]; if (flush()) { drop_all(); return 1; } }
+            return 0;
+        }
+        if (prefill_packed(slots, n)) { drop_all(); return 1; }
+    } catch (...) { drop_all(); throw; }
+    return 0;
+}
+int Engine::prefill_packed(const int *slots, int n) {
+    const int E = (int)llm_.n_embd;
+    struct Src { int slot; size_t row, erow; };                              // next queued row / embedding row of a conversation
+    std::vector<Src> src;
+    for (int i = 0; i < n; i++) if (!conv_[(size_t)slots[i]].pend_tok.empty()) src.push_back({slots[i], 0, 0});
+    if (src.empty()) return 0;
+    std::vector<int> tok;
+    size_t k = 0;
+    while (k < src.size()) {
+        HIP_CHECK(hipStreamSynchronize(stream_));                            // h_seg_ may still feed the previous chunk's copy
+        SegChunk sc;
+        int *const hs = h_seg_, *const fin = hs + SEG_FIN, *const last = hs + SEG_LAST, *const rows = hs + SEG_ROWS;
+        int *const t16 = rows + 2 * (size_t)max_rows_, *const t32 = t16 + 2 * ((size_t)max_rows_ + MAX_CONVERSATIONS);
+        int N = 0;
+        tok.clear();
+        while (k < src.size() && N < max_chunk_) {
+            Src &c = src[k];
+            Conversation &cv = conv_[(size_t)c.slot];
+            const int m = (int)std::min((size_t)(max_chunk_ - N), cv.pend_tok.size() - c.row), pos0 = cv.n_committed;
+            int *g = hs + 4 * sc.n_seg;
+            g[0] = c.slot; g[1] = N; g[2] = m; g[3] = pos0;
+            sc.key_rows += (double)(pos0 + m);
+            sc.att.t_max = std::max(sc.att.t_max, pos0 + m);
+            for (int r = 0; r < m; r++) { rows[2 * (N + r)] = c.slot; rows[2 * (N + r) + 1] = pos0 + r; tok.push_back(cv.pend_tok[c.row + r]); }
+            for (int r = 0; r < m;) {   // contiguous runs of embedding rows go straight into the residual stream at their packed rows
+                if (cv.pend_tok[c.row + r] >= 0) { r++; continue; }
+                int j = r; while (j < m && cv.pend_tok[c.row + j] < 0) j++;
+                HIP_CHECK(hipMemcpyAsync(x_ + (size_t)(N + r) * E, cv.pend_embd.data() + c.erow * E, (size_t)(j - r) * E * 4, hipMemcpyHostToDevice, stream_));
+                c.erow += (size_t)(j - r); r = j;
+            }
+            c.row += (size_t)m;
+            if (c.row == cv.pend_tok.size()) { fin[2 * sc.n_end] = c.slot; fin[2 * sc.n_end + 1] = pos0 + m; last[sc.n_end] = N + m - 1; sc.n_end++; k++; }
+            if (logits_host_slot_ == c.slot) logits_host_slot_ = -1;
+            N += m; sc.n_seg++;
+        }
+        memcpy(sc.h_segs, hs, (size_t)sc.n_seg * 4 * sizeof(int));
+        sc.att.n_tiles[0] = attn_seg_tiles(hs, sc.n_seg, 16, t16);
+        sc.att.n_tiles[1] = attn_seg_tiles(hs, sc.n_seg, 32, t32);
+        sc.att.segs = d_seg_; sc.att.tiles[0] = d_seg_ + (t16 - hs); sc.att.tiles[1] = d_seg_ + (t32 - hs);
+        sc.att.seq_stride = layers_.size() * (size_t)n_ctx_ * E;
+        sc.rows = d_seg_ + SEG_ROWS; sc.fin = d_seg_ + SEG_FIN; sc.last = d_seg_ + SEG_LAST;
+        HIP_CHECK(hipMemcpyAsync(d_seg_, h_seg_, seg_ints() * 4, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(d_tokens_, tok.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));                            // the (pageable) queues may be changed right after this call
+        seg_ = &sc;
+        forward(N, true, stream_);                                           // k_get_rows skips rows whose id is negative
+        seg_ = nullptr;
+        for (int i = 0; i < sc.n_seg; i++) conv_[(size_t)sc.h_segs[4 * i]].n_committed += sc.h_segs[4 * i + 2];
+    }
+    for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.pend_tok.clear(); cv.pend_embd.clear(); }
+    HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));   // greedy sample_token reads this copy
     return 0;
 }
 

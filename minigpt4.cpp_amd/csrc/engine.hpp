@@ -98,6 +98,11 @@ public:
     // forced != null: the step evaluates forced[i] for slots[i] instead of the token it sampled (teacher forcing: tests / bench parity legs compare every step's logits with
     // an oracle conversation that is fed the same ids); ids_out still reports what the conversation's own logits chose
     int decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced = nullptr);
+    // the queued prompt rows of `n` distinct conversations, packed into chunks of <= n_batch rows, one pass over the weights per chunk.  Afterwards each is
+    // where its own flush() leaves it (n_committed == n_past, queue empty, last-row logits / greedy id / feed token in its slot); one with nothing queued is
+    // skipped.  0, or 1 (bad slot list, failed pass: then every listed conversation drops its queue, n_past = n_committed, like a failed flush).  Parity
+    // mode and the parity trace: one flush() per conversation in slot order.
+    int prefill_batch(const int *slots, int n);
     // Which launches the LAST BUILT batched step (forward_batch: eager, or the capture of a graph) took, per kind -- so that a test / the bench can assert that the
     // operating point it means to check (k_matvec_ri, k_matvec_ri_mix, the K-split w2 launch) is the one that ran, instead of a fallback with the same results
     struct BatchPath { int rows = 0, ri = 0, ri_mix = 0, ri_ksplit = 0, dot4 = 0, dot4_mix = 0, mul_mat = 0, sets = 0, ri_plain = 0; };
@@ -124,6 +129,22 @@ private:
     void forward(int N, bool from_tokens, hipStream_t s, bool feed = false);   // feed: N == 1 and the token comes from d_feed_ (decode)
     void forward_ref(int N, bool from_tokens, hipStream_t s, bool feed);   // parity mode: the oracle's accumulation order
     void forward_batch(int B, hipStream_t s);          // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]
+    // prefill_batch: one packed chunk as forward() sees it while seg_ is set (device tables in d_seg_, host copy of the segment table)
+    struct SegChunk {
+        int n_seg = 0, n_end = 0;                      // segments; conversations whose queue ends in this chunk
+        int h_segs[4 * MAX_CONVERSATIONS];            // [segment][slot, first packed row, rows, position of the first row]
+        AttnSegs att;                                  // device segment table + attention work lists
+        const int *rows = nullptr, *fin = nullptr, *last = nullptr;   // device: [row][slot, position]; [ending][slot, end position]; [ending] last packed row
+        double key_rows = 0;                           // cached rows the segments' attention reads (profile_sites)
+    };
+    const SegChunk *seg_ = nullptr;
+    int prefill_packed(const int *slots, int n);
+    void attn_segments(const SegChunk &sg, __half *kc, __half *vc, bool want_h, bool *att_in_xh, hipStream_t s);
+    // d_seg_ / h_seg_ layout (ints): segments [0, 256), finish rows [256, 384), last rows [384, 448), row table [448, + 2 max_rows_), then the 16- and 32-query work
+    // lists, 2 (max_rows_ + 64) each
+    static constexpr int SEG_FIN = 4 * MAX_CONVERSATIONS, SEG_LAST = SEG_FIN + 2 * MAX_CONVERSATIONS, SEG_ROWS = SEG_LAST + MAX_CONVERSATIONS;
+    size_t seg_ints() const { return (size_t)SEG_ROWS + 2 * (size_t)max_rows_ + 4 * ((size_t)max_rows_ + MAX_CONVERSATIONS); }
+    int *d_seg_ = nullptr, *h_seg_ = nullptr;
     struct Prep { int kind; const float *x; const float *w; };   // 1: rms_norm(x)*w, 2: x, 3: silu(x)*w -- then quantised for the consumer's type
     void mul_mat(const QWeight &W, int N, float *y, int ldy, const float *residual, hipStream_t s, const Prep *prep, bool fuse, const char *site = "matmul", bool defer_ok = false, bool keep_pending = false);
     bool mul_mat_set(const QWeight *const *W, float *const *y, const float *const *res, int n, int N, int ldy, hipStream_t s, const Prep *prep, bool fuse, bool silu_pair = false, const char *site = "matmul", bool defer_ok = false, bool keep_pending = false);

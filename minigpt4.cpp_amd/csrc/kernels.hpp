@@ -149,6 +149,23 @@ void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *k
 // per row r, slot = row_slot[r]: argmax[slot] = feed[slot] = argmax(logits[r]); slot_logits[slot] = logits[r]; n_past[slot] += 1
 void launch_batch_finish(const float *logits, int n_vocab, int B, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s);
 void launch_batch_begin(int *n_past, const int *row_slot, const int *row_pos, int B, hipStream_t s);   // n_past[row_slot[r]] = row_pos[r]
+// ---- prompt rows of several conversations packed in one chunk (Engine::prefill_batch) ----
+// rows: device [N][2] = (slot, absolute position) per packed row.  k_rope_kv's arithmetic; cache row = position in kcache / vcache + slot * seq_stride
+void launch_rope_kv_seg(float *q, const float *k, const float *v, int N, int n_head, int hd, const int *rows, size_t seq_stride, const float *cos_tab, const float *sin_tab,
+                        __half *kcache, __half *vcache, hipStream_t s);
+void launch_rope_kv_seg_slabs(const SlabSrc &src, int N, int n_head, int hd, const int *rows, size_t seq_stride, const float *cos_tab, const float *sin_tab, __half *kcache, __half *vcache,
+                              hipStream_t s);   // n == 3, as launch_rope_kv_slabs
+// segs: device [n_seg][4] = (slot, first packed row, rows, position of the first row); tiles[0] / [1]: device work lists of 16- / 32-query tiles built by attn_seg_tiles
+// from the same (host) table; t_max >= every segment's position + rows (sizes the LDS score rows)
+struct AttnSegs { const int *segs = nullptr; const int *tiles[2] = {nullptr, nullptr}; int n_tiles[2] = {0, 0}; int t_max = 0; size_t seq_stride = 0; };
+int attn_seg_tiles(const int *segs, int n_seg, int qt, int *out);   // host: out[2 k] = segment, out[2 k + 1] = first query, longest first; returns the count
+// one launch of the SEG form of k_attn_prefill_h8 / k_attn_prefill_h (same choice rule as launch_attn_prefill); each row bit-identical to its segment's own launch.
+// false -> declined (the exact-f32 kernel is selected, or the score rows do not fit LDS): the caller runs per-segment launches.  out_h as launch_attn_prefill
+bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, hipStream_t s,
+                             __half *out_h = nullptr, bool *wrote_h = nullptr);
+// row r: logits row r belongs to conversation fin[2 r]: slot_logits / argmax / feed as launch_batch_finish, n_past[slot] = fin[2 r + 1]
+void launch_seg_finish(const float *logits, int n_vocab, int B, const int *fin, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s);
+void launch_gather_rows(const float *src, const int *idx, int n, int E, float *dst, hipStream_t s);   // dst[r] = src[idx[r]], rows of E floats
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)
@@ -158,6 +175,9 @@ void launch_attn_ref(const float *q, const __half *kcache, const __half *vcache,
 void launch_attn_ref_fused(const float *q, const float *k, const float *v, __half *kcache, __half *vcache, int n_head, int hd, const int *n_past, int t_max, const float *cos_tab, const float *sin_tab,
                            const Tables &tb, float *out, hipStream_t s);   // one query row: RoPE + cache append inside
 void set_attn_prefill_f16(int v);
+int attn_prefill_form();
+int attn_prefill_f16();
+void set_attn_prefill_form(int v);   // test library: force one fp16 prompt attention form (1 = h8, 2 = h QS 2, 3 = h QS 1; 0 = the size rule)
 void set_attn_prefill_w8(int v);    // 8-wave loader / MFMA form of the fp16 prompt attention (MINIGPT4_ATTN_PREFILL_W8)   // 1 (default): prompt attention on the fp16 matrix cores, 0: the exact-f32 MFMA kernel
 bool attn_head_size_supported(int hd);
 void attn_ref_prepare();        // the oracle-order attention kernels' > 64 KiB LDS opt-in on the current device, checked (throws HipError); outside any stream capture

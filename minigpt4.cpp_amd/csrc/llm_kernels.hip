@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstring>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 #include <hip/hip_ext.h>
 
@@ -1537,6 +1538,40 @@ __global__ void k_rope_kv_slabs(const RopeSlabs rs, const long long stride, floa
     *reinterpret_cast<__half2 *>(kc + co) = __floats2half2_rn(m[1].x * c - m[1].y * s, m[1].x * s + m[1].y * c);
     *reinterpret_cast<__half2 *>(vc + co) = __floats2half2_rn(m[2].x, m[2].y);
 }
+// Packed prompt rows of several conversations (Engine::prefill_batch): row t belongs to conversation rows[2 t] at position rows[2 t + 1]; its cache row is
+// that position in the conversation's region, kc / vc + slot * seq_stride.  Otherwise the arithmetic of k_rope_kv / k_rope_kv_slabs, statement for statement.
+__global__ void k_rope_kv_seg(float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v, int E, int hd, const int *__restrict__ rows, long long seq_stride,
+                              const float *__restrict__ cos_tab, const float *__restrict__ sin_tab, __half *__restrict__ kc, __half *__restrict__ vc) {
+    const int t = blockIdx.x, h = blockIdx.y, i = threadIdx.x;   // i < hd/2
+    const int pos = rows[2 * t + 1];
+    const float c = cos_tab[(size_t)pos * (hd / 2) + i], s = sin_tab[(size_t)pos * (hd / 2) + i];
+    const size_t o = (size_t)t * E + (size_t)h * hd + 2 * i;
+    const float q0 = q[o], q1 = q[o + 1];
+    q[o] = q0 * c - q1 * s; q[o + 1] = q0 * s + q1 * c;
+    const float k0 = k[o], k1 = k[o + 1];
+    const size_t co = (size_t)rows[2 * t] * seq_stride + (size_t)pos * E + (size_t)h * hd + 2 * i;
+    *reinterpret_cast<__half2 *>(kc + co) = __floats2half2_rn(k0 * c - k1 * s, k0 * s + k1 * c);
+    *reinterpret_cast<__half2 *>(vc + co) = __floats2half2_rn(v[o], v[o + 1]);
+}
+__global__ void k_rope_kv_seg_slabs(const RopeSlabs rs, const long long stride, float *__restrict__ q, int E, int hd, const int *__restrict__ rows, long long seq_stride,
+                                    const float *__restrict__ cos_tab, const float *__restrict__ sin_tab, __half *__restrict__ kc, __half *__restrict__ vc) {
+    const int t = blockIdx.x, h = blockIdx.y, i = threadIdx.x;   // i < hd/2
+    const int pos = rows[2 * t + 1];
+    const float c = cos_tab[(size_t)pos * (hd / 2) + i], s = sin_tab[(size_t)pos * (hd / 2) + i];
+    const size_t o = (size_t)t * E + (size_t)h * hd + 2 * i;
+    float2 m[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float *b = rs.base[a] + o;
+        float2 acc = *reinterpret_cast<const float2 *>(b);
+        for (int z = 1; z < rs.ks[a]; z++) { const float2 u = *reinterpret_cast<const float2 *>(b + (size_t)z * stride); acc.x += u.x; acc.y += u.y; }
+        m[a] = acc;
+    }
+    q[o] = m[0].x * c - m[0].y * s; q[o + 1] = m[0].x * s + m[0].y * c;
+    const size_t co = (size_t)rows[2 * t] * seq_stride + (size_t)pos * E + (size_t)h * hd + 2 * i;
+    *reinterpret_cast<__half2 *>(kc + co) = __floats2half2_rn(m[1].x * c - m[1].y * s, m[1].x * s + m[1].y * c);
+    *reinterpret_cast<__half2 *>(vc + co) = __floats2half2_rn(m[2].x, m[2].y);
+}
 void launch_rope_kv_slabs(const SlabSrc &src, int N, int n_head, int hd, const int *n_past, const float *cos_tab, const float *sin_tab, __half *kcache, __half *vcache, hipStream_t s) {
     RopeSlabs rs;
     for (int a = 0; a < 3; a++) { rs.base[a] = src.mbase[a]; rs.ks[a] = src.mks[a]; }
@@ -1545,6 +1580,19 @@ void launch_rope_kv_slabs(const SlabSrc &src, int N, int n_head, int hd, const i
 void launch_rope_kv(float *q, const float *k, const float *v, int N, int n_head, int hd, const int *n_past, const float *cos_tab, const float *sin_tab,
                     __half *kcache, __half *vcache, hipStream_t s) {
     hipLaunchKernelGGL(k_rope_kv, dim3((unsigned)N, (unsigned)n_head), dim3((unsigned)(hd / 2)), 0, s, q, k, v, n_head * hd, hd, n_past, cos_tab, sin_tab, kcache, vcache);
+}
+void launch_rope_kv_seg(float *q, const float *k, const float *v, int N, int n_head, int hd, const int *rows, size_t seq_stride, const float *cos_tab, const float *sin_tab,
+                        __half *kcache, __half *vcache, hipStream_t s) {
+    note_kernel("k_rope_kv_seg");
+    hipLaunchKernelGGL(k_rope_kv_seg, dim3((unsigned)N, (unsigned)n_head), dim3((unsigned)(hd / 2)), 0, s, q, k, v, n_head * hd, hd, rows, (long long)seq_stride, cos_tab, sin_tab, kcache, vcache);
+}
+void launch_rope_kv_seg_slabs(const SlabSrc &src, int N, int n_head, int hd, const int *rows, size_t seq_stride, const float *cos_tab, const float *sin_tab, __half *kcache, __half *vcache,
+                              hipStream_t s) {
+    RopeSlabs rs;
+    for (int a = 0; a < 3; a++) { rs.base[a] = src.mbase[a]; rs.ks[a] = src.mks[a]; }
+    note_kernel("k_rope_kv_seg_slabs");
+    hipLaunchKernelGGL(k_rope_kv_seg_slabs, dim3((unsigned)N, (unsigned)n_head), dim3((unsigned)(hd / 2)), 0, s, rs, src.stride, src.y[0], n_head * hd, hd, rows, (long long)seq_stride, cos_tab,
+                       sin_tab, kcache, vcache);
 }
 // The table k_rope_kv reads, exactly ggml's iteration: theta = pos; theta *= theta_scale per pair (fp32), cosf/sinf.  [n_ctx][hd / 2] each
 void rope_tables(int n_ctx, int hd, std::vector<float> &c, std::vector<float> &s) {
@@ -2139,19 +2187,33 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const float *__restrict__ 
 // from the sequential chain of k_attn_llm / the oracle (fp32 rounding only; MINIGPT4_PARITY uses k_attn_ref).
 typedef _Float16 aph8_t __attribute__((ext_vector_type(8)));
 constexpr int APH_LDT = 70;
-template <int HD, int QS>
+// SEG form (Engine::prefill_batch, trailing AttnSegArgs argument): the rows of several conversations packed in one chunk, one launch.  Grid (head, work item); item y
+// = (segment tiles[2 y], first query tiles[2 y + 1]), dealt longest-first over ALL segments by the host (attn_seg_tiles).  Segment i = segs[4 i ..]: slot, first packed
+// row, rows, position of its first row.  Each segment is tiled from its own row 0, so a tile sees exactly the queries and keys of the same tile of that segment's own
+// launch: the rows are bit-identical.  Only the tile setup differs; without the argument the kernels are the one-conversation forms.
+struct AttnSegArgs { const int *segs; const int *tiles; long long seq_stride; };
+template <int HD, int QS, typename... Seg>
 __global__ __launch_bounds__(256) void k_attn_prefill_h(const float *__restrict__ q, const __half *__restrict__ kc, const __half *__restrict__ vc, int E, int N, const int *__restrict__ n_past,
-                                                        const Tables tb, float *__restrict__ out, int LS) {
+                                                        const Tables tb, float *__restrict__ out, int LS, const Seg... seg) {
+    constexpr bool SEG = sizeof...(Seg) > 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_aph[];
     constexpr int C8 = HD / 8, QT = AP_QT * QS, KSQ = HD / 32, DT = HD / 16, PER = AP_KT * C8 / 256;
     static_assert(PER >= 1 && (DT % 4 == 0 || DT == 2), "tile geometry");
     float *S = reinterpret_cast<float *>(smem_aph);               // [QT][LS], LS = 4 mod 64
     __half *Kt = reinterpret_cast<__half *>(S + (size_t)QT * LS); // [64][HD], chunk c of row j at slot c ^ (j & (C8 - 1))
     __half *Vt = Kt + AP_KT * HD;                                 // [HD][APH_LDT]
-    // causal: the LAST query tile sees the most keys -- it is dispatched first (longest-first), so the short tiles fill the tail of the launch
-    const int h = blockIdx.x, q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // causal: the LAST query tile sees the most keys -- it is dispatched first (longest-first), so the short tiles fill the tail of the launch.  SEG: the work item
+    // (segment, first query) comes from the host's longest-first list instead
+    int q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, np_seg = 0;
+    if constexpr (SEG) {   // the segment's own tile: its rows, its conversation's cache, its first position
+        const AttnSegArgs sa = (seg, ...);
+        const int *t = sa.tiles + 2 * blockIdx.y, *g = sa.segs + 4 * t[0];
+        q0 = t[1]; N = g[2]; np_seg = g[3];
+        q += (size_t)g[1] * E; out += (size_t)g[1] * E; kc += (size_t)g[0] * sa.seq_stride; vc += (size_t)g[0] * sa.seq_stride;
+    }
+    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     MG4_TLP(0);
-    const int np = *n_past;
+    const int np = SEG ? np_seg : *n_past;
     const int T = np + min(q0 + QT - 1, N - 1) + 1;               // keys the last query of this tile sees
     const int nkt = (T + AP_KT - 1) / AP_KT;
     const float scale = 1.0f / sqrtf((float)HD);
@@ -2321,20 +2383,29 @@ __global__ __launch_bounds__(256) void k_attn_prefill_h(const float *__restrict_
 // Every value is formed by the same operations in the same order as in k_attn_prefill_h (scores: one MFMA chain per (query group, key tile) over ks; softmax: order-free
 // max / exact sum; P.V: tiles in key order), so the two kernels are bit-identical (MINIGPT4_ATTN_PREFILL_W8=0 selects the 4-wave form, A/B).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int HD>
+template <int HD, typename... Seg>
 __global__ __launch_bounds__(512) void k_attn_prefill_h8(const float *__restrict__ q, const __half *__restrict__ kc, const __half *__restrict__ vc, int E, int N, const int *__restrict__ n_past,
-                                                         const Tables tb, float *__restrict__ out, int LS, __half *__restrict__ out_h) {
+                                                         const Tables tb, float *__restrict__ out, int LS, __half *__restrict__ out_h, const Seg... seg) {
+    constexpr bool SEG = sizeof...(Seg) > 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_aph8[];
     constexpr int QS = 2, C8 = HD / 8, QT = AP_QT * QS, KSQ = HD / 32, DT = HD / 16, PER = AP_KT * C8 / 256;
     constexpr int KVB = (AP_KT * HD * 2 > HD * APH_LDT * 2 ? AP_KT * HD * 2 : HD * APH_LDT * 2);        // bytes of one K (or transposed V) tile buffer
     static_assert(PER >= 1 && (DT % 4 == 0 || DT == 2), "tile geometry");
     float *S = reinterpret_cast<float *>(smem_aph8);                                                 // [QT][LS]
     unsigned char *kvb = smem_aph8 + (size_t)QT * LS * 4;                                             // two tile buffers (K tiles, later V tiles)
-    const int h = blockIdx.x, q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, np_seg = 0;
+    if constexpr (SEG) {   // the segment's own tile: its rows, its conversation's cache, its first position
+        const AttnSegArgs sa = (seg, ...);
+        const int *t = sa.tiles + 2 * blockIdx.y, *g = sa.segs + 4 * t[0];
+        q0 = t[1]; N = g[2]; np_seg = g[3];
+        q += (size_t)g[1] * E; out += (size_t)g[1] * E; kc += (size_t)g[0] * sa.seq_stride; vc += (size_t)g[0] * sa.seq_stride;
+        if (out_h) out_h += (size_t)g[1] * E;
+    }
+    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = wave >= 4;
     const int lt = tid & 255, mw = wave & 3;                                                           // loader thread / MFMA wave index
     MG4_TLP(0);
-    const int np = *n_past;
+    const int np = SEG ? np_seg : *n_past;
     const int T = np + min(q0 + QT - 1, N - 1) + 1;
     const int nkt = (T + AP_KT - 1) / AP_KT;
     const float scale = 1.0f / sqrtf((float)HD);
@@ -2534,6 +2605,7 @@ static bool launch_attn_prefill_h8(const float *q, const __half *kc, const __hal
 }
 static int g_attn_prefill_f16 = 1;   // 1: prompt attention on the fp16 matrix cores (k_attn_prefill_h), 0: the exact-f32 MFMA kernel (k_attn_prefill); test-library setter only
 void set_attn_prefill_f16(int v) { g_attn_prefill_f16 = v != 0; }
+int attn_prefill_f16() { return g_attn_prefill_f16; }
 template <int HD, int QS>
 static bool launch_attn_prefill_h_qs(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s) {
     const int LS = ((t_max + AP_KT - 1) / AP_KT) * AP_KT + 4;
@@ -2544,12 +2616,17 @@ static bool launch_attn_prefill_h_qs(const float *q, const __half *kc, const __h
     hipLaunchKernelGGL((k_attn_prefill_h<HD, QS>), dim3((unsigned)n_head, (unsigned)((N + AP_QT * QS - 1) / (AP_QT * QS))), dim3(256), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS);
     return true;
 }
+static int g_attn_prefill_form = 0;  // test library: 1 / 2 / 3 = only k_attn_prefill_h8 / _h<HD, 2> / _h<HD, 1> is tried (no size rule); 0 = the launchers' own choice
+void set_attn_prefill_form(int v) { g_attn_prefill_form = v; }
+int attn_prefill_form() { return g_attn_prefill_form; }
 template <int HD>
 static bool launch_attn_prefill_hd(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s, __half *out_h, bool *wrote_h) {
     if (g_attn_prefill_f16) {   // 32 queries per staged K / V tile once that still gives every CU a workgroup
-        if (g_attn_prefill_w8 && n_head * ((N + 31) / 32) >= 256 && launch_attn_prefill_h8<HD>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s, out_h)) { if (wrote_h) *wrote_h = out_h != nullptr; return true; }
-        if (n_head * ((N + 31) / 32) >= 256 && launch_attn_prefill_h_qs<HD, 2>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s)) return true;
-        if (launch_attn_prefill_h_qs<HD, 1>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s)) return true;
+        const bool wide = n_head * ((N + 31) / 32) >= 256;
+        const int f = g_attn_prefill_form;
+        if ((f == 1 || (f == 0 && g_attn_prefill_w8 && wide)) && launch_attn_prefill_h8<HD>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s, out_h)) { if (wrote_h) *wrote_h = out_h != nullptr; return true; }
+        if ((f == 2 || (f == 0 && wide)) && launch_attn_prefill_h_qs<HD, 2>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s)) return true;
+        if ((f == 0 || f == 3) && launch_attn_prefill_h_qs<HD, 1>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s)) return true;
     }
     // Fallback: k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken (a) after set_attn_prefill_f16(0) (test library: the A/B switch of
     // the fp16 kernels), (b) when the fp16 kernels refuse because their LDS image (score rows + fp16 K tile + transposed V tile) exceeds the 160 KiB of a CU.  Both forms
@@ -2564,6 +2641,62 @@ static bool launch_attn_prefill_hd(const float *q, const __half *kc, const __hal
     if (lds > 160 * 1024 - 512) return false;
     hipLaunchKernelGGL((k_attn_prefill<HD, 1>), dim3((unsigned)n_head, (unsigned)((N + AP_QT - 1) / AP_QT)), dim3(256), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS);
     return true;
+}
+// Segmented prompt attention (Engine::prefill_batch): one launch over every segment of a packed chunk; the same forms and the same size rule as
+// launch_attn_prefill_hd, with the 32-query work items of all segments standing in for one conversation's tiles.
+int attn_seg_tiles(const int *segs, int n_seg, int qt, int *out) {
+    struct Item { int seg, q0, keys; };
+    std::vector<Item> v;
+    for (int i = 0; i < n_seg; i++)
+        for (int q0 = 0; q0 < segs[4 * i + 2]; q0 += qt) v.push_back({i, q0, segs[4 * i + 3] + std::min(q0 + qt, segs[4 * i + 2])});
+    // longest first over all segments (a lone segment: its last tile first, as the one-conversation launch deals them); ties keep the segment order
+    std::stable_sort(v.begin(), v.end(), [](const Item &a, const Item &b) { return a.keys > b.keys; });
+    for (size_t k = 0; k < v.size(); k++) { out[2 * k] = v[k].seg; out[2 * k + 1] = v[k].q0; }
+    return (int)v.size();
+}
+template <int HD>
+static bool launch_attn_prefill_seg_hd(const float *q, const __half *kc, const __half *vc, const AttnSegs &sg, int n_head, const Tables &tb, float *out, hipStream_t s, __half *out_h,
+                                       bool *wrote_h) {
+    if (!g_attn_prefill_f16) return false;           // the exact-f32 kernel: per-segment launches (the caller)
+    const int E = n_head * HD, f = g_attn_prefill_form;
+    const bool wide = n_head * sg.n_tiles[1] >= 256;
+    const int LS = ((sg.t_max + AP_KT - 1) / AP_KT) * AP_KT + 4;
+    if (f == 1 || (f == 0 && g_attn_prefill_w8 && wide)) {
+        const size_t lds = (size_t)AP_QT * 2 * LS * 4 + 2 * std::max((size_t)AP_KT * HD * 2, (size_t)HD * APH_LDT * 2);
+        if (lds <= 160 * 1024 - 512) {
+            static bool attr = false;
+            if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h8<HD, AttnSegArgs>)); attr = true; }
+            note_kernel("k_attn_prefill_h8<%d, SEG>", HD);
+            hipLaunchKernelGGL((k_attn_prefill_h8<HD, AttnSegArgs>), dim3((unsigned)n_head, (unsigned)sg.n_tiles[1]), dim3(512), lds, s, q, kc, vc, E, 0, (const int *)nullptr, tb, out, LS,
+                               out_h, AttnSegArgs{sg.segs, sg.tiles[1], (long long)sg.seq_stride});
+            if (wrote_h) *wrote_h = out_h != nullptr;
+            return true;
+        }
+    }
+    auto h_qs = [&](auto qs_tag) {
+        constexpr int QS = decltype(qs_tag)::value;
+        const size_t lds = (size_t)AP_QT * QS * LS * 4 + (size_t)AP_KT * HD * 2 + (size_t)HD * APH_LDT * 2;
+        if (lds > 160 * 1024 - 512) return false;
+        static bool attr = false;
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h<HD, QS, AttnSegArgs>)); attr = true; }
+        note_kernel("k_attn_prefill_h<%d, %d, SEG>", HD, QS);
+        hipLaunchKernelGGL((k_attn_prefill_h<HD, QS, AttnSegArgs>), dim3((unsigned)n_head, (unsigned)sg.n_tiles[QS - 1]), dim3(256), lds, s, q, kc, vc, E, 0, (const int *)nullptr, tb, out, LS,
+                           AttnSegArgs{sg.segs, sg.tiles[QS - 1], (long long)sg.seq_stride});
+        return true;
+    };
+    if ((f == 2 || (f == 0 && wide)) && h_qs(std::integral_constant<int, 2>{})) return true;
+    if ((f == 0 || f == 3) && h_qs(std::integral_constant<int, 1>{})) return true;
+    return false;
+}
+bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, hipStream_t s, __half *out_h,
+                             bool *wrote_h) {
+    if (wrote_h) *wrote_h = false;
+    switch (hd) {
+    case 32: return launch_attn_prefill_seg_hd<32>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h);
+    case 64: return launch_attn_prefill_seg_hd<64>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h);
+    case 128: return launch_attn_prefill_seg_hd<128>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h);
+    default: return false;
+    }
 }
 // N > 1 query rows at positions *n_past .. *n_past + N - 1 (launch_rope_kv has run); t_max >= *n_past + N (the host's view, sizes the LDS score rows).
 // false -> the score rows do not fit LDS (very long contexts): the caller runs launch_attn_llm instead.
@@ -2797,9 +2930,8 @@ __global__ void k_set_int(int *p, int v) { *p = v; }
 void launch_set_int(int *p, int v, hipStream_t s) { hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, p, v); }
 // Batched decode epilogue, one workgroup per row: greedy argmax of the row's logits (first maximum wins), stored with the logits' owner slot; the
 // conversation's position advances by one and the greedy token becomes its next input.
-__global__ __launch_bounds__(1024) void k_batch_finish(const float *__restrict__ logits, int n_vocab, const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax,
-                                                      int *__restrict__ feed, float *__restrict__ slot_logits) {
-    const int r = blockIdx.x, slot = row_slot[r];
+// Returns the greedy id in thread 0 (the other threads' value is meaningless).
+__device__ __forceinline__ int batch_finish_row(const float *__restrict__ logits, int n_vocab, int r, int slot, float *__restrict__ slot_logits) {
     const float *x = logits + (size_t)r * n_vocab;
     float *keep = slot_logits + (size_t)slot * n_vocab;                   // the conversation's own copy (sampling with temp > 0, minigpt4_amd_get_logits)
     float best = -INFINITY; int bi = 0x7FFFFFFF;
@@ -2815,14 +2947,39 @@ __global__ __launch_bounds__(1024) void k_batch_finish(const float *__restrict__
     argmax_wave(best, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++) argmax_combine(best, bi, sv[w], si[w]);
-        const int id = bi == 0x7FFFFFFF ? 0 : bi;
-        argmax[slot] = id; feed[slot] = id; n_past[slot] += 1;
-    }
+    if (threadIdx.x == 0) for (int w = 1; w < 16; w++) argmax_combine(best, bi, sv[w], si[w]);
+    return bi == 0x7FFFFFFF ? 0 : bi;
+}
+__global__ __launch_bounds__(1024) void k_batch_finish(const float *__restrict__ logits, int n_vocab, const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax,
+                                                      int *__restrict__ feed, float *__restrict__ slot_logits) {
+    const int r = blockIdx.x, slot = row_slot[r];
+    const int id = batch_finish_row(logits, n_vocab, r, slot, slot_logits);
+    if (threadIdx.x == 0) { argmax[slot] = id; feed[slot] = id; n_past[slot] += 1; }
 }
 void launch_batch_finish(const float *logits, int n_vocab, int B, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s) {
     hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)B), dim3(1024), 0, s, logits, n_vocab, row_slot, n_past, argmax, feed, slot_logits);
+}
+// Packed prompt chunk epilogue (Engine::prefill_batch): row r of `logits` is the last row of conversation fin[2 r]; its position becomes fin[2 r + 1] (set, not
+// advanced), its greedy id and feed token as k_batch_finish writes them.
+__global__ __launch_bounds__(1024) void k_seg_finish(const float *__restrict__ logits, int n_vocab, const int *__restrict__ fin, int *__restrict__ n_past, int *__restrict__ argmax,
+                                                    int *__restrict__ feed, float *__restrict__ slot_logits) {
+    const int r = blockIdx.x, slot = fin[2 * r];
+    const int id = batch_finish_row(logits, n_vocab, r, slot, slot_logits);
+    if (threadIdx.x == 0) { argmax[slot] = id; feed[slot] = id; n_past[slot] = fin[2 * r + 1]; }
+}
+void launch_seg_finish(const float *logits, int n_vocab, int B, const int *fin, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s) {
+    note_kernel("k_seg_finish");
+    hipLaunchKernelGGL(k_seg_finish, dim3((unsigned)B), dim3(1024), 0, s, logits, n_vocab, fin, n_past, argmax, feed, slot_logits);
+}
+// dst[r] = src[idx[r]] (rows of E floats)
+__global__ void k_gather_rows(const float *__restrict__ src, const int *__restrict__ idx, int E, float *__restrict__ dst) {
+    const float *a = src + (size_t)idx[blockIdx.x] * E;
+    float *b = dst + (size_t)blockIdx.x * E;
+    for (int i = threadIdx.x; i < E; i += blockDim.x) b[i] = a[i];
+}
+void launch_gather_rows(const float *src, const int *idx, int n, int E, float *dst, hipStream_t s) {
+    note_kernel("k_gather_rows");
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n), dim3(256), 0, s, src, idx, E, dst);
 }
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {

@@ -535,6 +535,115 @@ int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, i
         return 0;
     });
 }
+// ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
+// [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
+static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {
+    out.assign((size_t)n_seg * 4, 0); N = 0; t_max = 0;
+    for (int i = 0; i < n_seg; i++) {
+        const int slot = segs[3 * i], rows = segs[3 * i + 1], pos0 = segs[3 * i + 2];
+        if (slot < 0 || slot >= n_slots || rows < 1 || pos0 < 0 || pos0 + rows > n_ctx) return false;
+        out[4 * (size_t)i] = slot; out[4 * (size_t)i + 1] = N; out[4 * (size_t)i + 2] = rows; out[4 * (size_t)i + 3] = pos0;
+        N += rows; t_max = std::max(t_max, pos0 + rows);
+    }
+    return true;
+}
+int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slots, const uint16_t *kc, const uint16_t *vc, int n_seg, const int32_t *segs, const float *q,
+                                       int form, float *out_seg, float *out_ref, int *seg_launched, uint16_t *out_h_seg, uint16_t *out_h_ref, int *wrote_h) {
+    std::vector<int> st; int N = 0, t_max = 0;
+    if (!kc || !vc || !segs || !q || !out_seg || !out_ref || n_head < 1 || !attn_head_size_supported(hd) || n_slots < 1 || n_seg < 1 || form < 0 || form > 4 ||
+        !seg_table(n_ctx, n_slots, n_seg, segs, st, N, t_max) || (!out_h_seg) != (!out_h_ref) || (out_h_seg && !wrote_h)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    struct Restore { int form = attn_prefill_form(), f16 = attn_prefill_f16(); ~Restore() { set_attn_prefill_form(form); set_attn_prefill_f16(f16); } } restore;   // the caller's settings
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, cache = (size_t)n_slots * n_ctx * E, stride = (size_t)n_ctx * E;
+        std::vector<int> t16((size_t)2 * (N + n_seg)), t32((size_t)2 * (N + n_seg));
+        AttnSegs sg;
+        sg.n_tiles[0] = attn_seg_tiles(st.data(), n_seg, 16, t16.data()); sg.n_tiles[1] = attn_seg_tiles(st.data(), n_seg, 32, t32.data());
+        sg.t_max = t_max; sg.seq_stride = stride;
+        DevBuf dk(cache * 2), dv(cache * 2), dq((size_t)N * E * 4), ds(st.size() * 4), d16(t16.size() * 4), d32(t32.size() * 4), da((size_t)N * E * 4), db((size_t)N * E * 4), dtab(65536 * 2);
+        const bool want_h = out_h_seg != nullptr;                           // fp16 rows for an F16 wo (the out_h arm of the launchers)
+        DevBuf dha(want_h ? (size_t)N * E * 2 : 0), dhb(want_h ? (size_t)N * E * 2 : 0);
+        if (want_h) { HIP_CHECK(hipMemset(dha.p, 0, (size_t)N * E * 2)); HIP_CHECK(hipMemset(dhb.p, 0, (size_t)N * E * 2)); }
+        HIP_CHECK(hipMemcpy(dk.p, kc, cache * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, vc, cache * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dq.p, q, (size_t)N * E * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(ds.p, st.data(), st.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d16.p, t16.data(), t16.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(d32.p, t32.data(), t32.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(da.p, 0, (size_t)N * E * 4)); HIP_CHECK(hipMemset(db.p, 0, (size_t)N * E * 4));
+        { std::vector<__half> e(65536); for (int i = 0; i < 65536; i++) e[(size_t)i] = __float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)i)))); HIP_CHECK(hipMemcpy(dtab.p, e.data(), 131072, hipMemcpyHostToDevice)); }
+        Tables tb; tb.exp = dtab.as<__half>();
+        { int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if (__half2float(__float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)c))))) == 0.0f) break; nneg++; } tb.exp_neg_n = (nneg + 2047) / 2048 * 2048; }
+        sg.segs = ds.as<int>(); sg.tiles[0] = d16.as<int>(); sg.tiles[1] = d32.as<int>();
+        set_attn_prefill_f16(form != 4);
+        set_attn_prefill_form(form >= 1 && form <= 3 ? form : 0);
+        const float *dqp = dq.as<float>();
+        // one launch_attn_prefill per segment; *all_h: every segment stored fp16 rows
+        auto per_segment = [&](float *out, __half *out_h, bool *all_h) {
+            if (all_h) *all_h = true;
+            for (int i = 0; i < n_seg; i++) {
+                const int *g = st.data() + 4 * (size_t)i;
+                const size_t off = (size_t)g[1] * E, cs = (size_t)g[0] * stride;
+                bool w = false;
+                if (!launch_attn_prefill(dqp + off, dk.as<__half>() + cs, dv.as<__half>() + cs, g[2], n_head, hd, ds.as<int>() + 4 * i + 3, g[3] + g[2], tb, out + off, nullptr,
+                                         out_h ? out_h + off : nullptr, &w)) return false;
+                if (all_h) *all_h = *all_h && w;
+            }
+            return true;
+        };
+        bool seg_h = false, ref_h = false;
+        const bool one = launch_attn_prefill_seg(dqp, dk.as<__half>(), dv.as<__half>(), sg, n_head, hd, tb, da.as<float>(), nullptr, want_h ? dha.as<__half>() : nullptr, &seg_h);
+        if (!one && !per_segment(da.as<float>(), want_h ? dha.as<__half>() : nullptr, &seg_h)) return 4;
+        if (!per_segment(db.as<float>(), want_h ? dhb.as<__half>() : nullptr, &ref_h)) return 4;
+        HIP_CHECK(hipDeviceSynchronize());
+        if (seg_launched) *seg_launched = one ? 1 : 0;
+        HIP_CHECK(hipMemcpy(out_seg, da.p, (size_t)N * E * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(out_ref, db.p, (size_t)N * E * 4, hipMemcpyDeviceToHost));
+        if (want_h) {
+            wrote_h[0] = seg_h; wrote_h[1] = ref_h;
+            HIP_CHECK(hipMemcpy(out_h_seg, dha.p, (size_t)N * E * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(out_h_ref, dhb.p, (size_t)N * E * 2, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    });
+}
+int minigpt4_amd_test_rope_kv_seg(int n_head, int hd, int n_ctx, int n_slots, int n_seg, const int32_t *segs, const float *q, const float *k, const float *v, int ks,
+                                  float *q_seg, uint16_t *kc_seg, uint16_t *vc_seg, float *q_ref, uint16_t *kc_ref, uint16_t *vc_ref) {
+    std::vector<int> st; int N = 0, t_max = 0;
+    if (!segs || !q || !k || !v || !q_seg || !kc_seg || !vc_seg || !q_ref || !kc_ref || !vc_ref || n_head < 1 || hd < 2 || hd % 2 || n_slots < 1 || n_seg < 1 || ks < 1 || ks > 8 ||
+        !seg_table(n_ctx, n_slots, n_seg, segs, st, N, t_max)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, cache = (size_t)n_slots * n_ctx * E, stride = (size_t)n_ctx * E, NE = (size_t)N * E;
+        std::vector<float> c, sn;
+        rope_tables(n_ctx, hd, c, sn);
+        std::vector<int> rows((size_t)2 * N);
+        for (int i = 0; i < n_seg; i++) for (int r = 0; r < st[4 * (size_t)i + 2]; r++) { rows[2 * (size_t)(st[4 * (size_t)i + 1] + r)] = st[4 * (size_t)i]; rows[2 * (size_t)(st[4 * (size_t)i + 1] + r) + 1] = st[4 * (size_t)i + 3] + r; }
+        DevBuf dc(c.size() * 4), dsn(sn.size() * 4), ds(st.size() * 4), dr(rows.size() * 4), dslab(3 * (size_t)ks * NE * 4), dqa(NE * 4), dqb(NE * 4), dka(cache * 2), dva(cache * 2), dkb(cache * 2), dvb(cache * 2);
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, st.data(), st.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+        const float *src[3] = {q, k, v};
+        for (int a = 0; a < 3; a++) for (int z = 0; z < ks; z++) HIP_CHECK(hipMemcpy(dslab.as<float>() + ((size_t)a * ks + z) * NE, src[a], NE * 4, hipMemcpyHostToDevice));   // slab z of matrix a
+        for (DevBuf *b : {&dka, &dva, &dkb, &dvb}) HIP_CHECK(hipMemset(b->p, 0, cache * 2));
+        HIP_CHECK(hipMemcpy(dqa.p, q, NE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dqb.p, q, NE * 4, hipMemcpyHostToDevice));
+        float *sl = dslab.as<float>();
+        auto slabs = [&](size_t off, float *qout) {
+            SlabSrc S; S.ws = sl; S.ks = ks; S.stride = (long long)NE; S.n = 3; S.y[0] = qout;
+            for (int a = 0; a < 3; a++) { S.mbase[a] = sl + (size_t)a * ks * NE + off; S.mks[a] = ks; }
+            return S;
+        };
+        // the plain forms read the first slab of k / v (= k, v); q is rotated in place in its own copy
+        if (ks > 1) launch_rope_kv_seg_slabs(slabs(0, dqa.as<float>()), N, n_head, hd, dr.as<int>(), stride, dc.as<float>(), dsn.as<float>(), dka.as<__half>(), dva.as<__half>(), nullptr);
+        else launch_rope_kv_seg(dqa.as<float>(), sl + NE, sl + 2 * NE, N, n_head, hd, dr.as<int>(), stride, dc.as<float>(), dsn.as<float>(), dka.as<__half>(), dva.as<__half>(), nullptr);
+        for (int i = 0; i < n_seg; i++) {
+            const int *g = st.data() + 4 * (size_t)i;
+            const size_t off = (size_t)g[1] * E, cs = (size_t)g[0] * stride;
+            const int *np = ds.as<int>() + 4 * i + 3;
+            if (ks > 1) launch_rope_kv_slabs(slabs(off, dqb.as<float>() + off), g[2], n_head, hd, np, dc.as<float>(), dsn.as<float>(), dkb.as<__half>() + cs, dvb.as<__half>() + cs, nullptr);
+            else launch_rope_kv(dqb.as<float>() + off, sl + NE + off, sl + 2 * NE + off, g[2], n_head, hd, np, dc.as<float>(), dsn.as<float>(), dkb.as<__half>() + cs, dvb.as<__half>() + cs, nullptr);
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(q_seg, dqa.p, NE * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(q_ref, dqb.p, NE * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc_seg, dka.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc_seg, dva.p, cache * 2, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc_ref, dkb.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc_ref, dvb.p, cache * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // Micro-benchmark of the prompt-row attention (launch_attn_prefill): N query rows at positions n_past .. n_past + N - 1 of an fp16 K / V cache filled with synthetic rows
 int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int iters, float *us_per_launch) {
     if (const char *w8 = getenv("MINIGPT4_ATTN_PREFILL_W8")) set_attn_prefill_w8(atoi(w8));        // micro-benchmark only (no engine in this process)

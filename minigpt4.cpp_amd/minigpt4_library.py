@@ -198,6 +198,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_n_conversations.argtypes = [VOID_PTR]
         L.minigpt4_amd_end_chat_batch.argtypes = [VOID_PTR, INT_PTR, I32, P(ctypes.c_char_p), F32, I32, F32, F32, F32, I32, F32, F32]
         L.minigpt4_amd_eval_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR]
+        L.minigpt4_amd_prefill_batch.argtypes = [VOID_PTR, INT_PTR, I32]
         L.minigpt4_amd_batch_path.argtypes = [VOID_PTR, INT_PTR]
         L.minigpt4_amd_shift_context.argtypes = [VOID_PTR, I32, I32]
         L.minigpt4_amd_set_context_shift.argtypes = [VOID_PTR, I32]
@@ -217,6 +218,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_gemm_f16.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_gemm_f16_skinny.argtypes = L.minigpt4_amd_test_gemm_f16.argtypes
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
+        L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
         L.minigpt4_amd_vocab_load.argtypes = [CHAR_PTR]
         L.minigpt4_amd_vocab_load.restype = VOID_PTR
@@ -371,6 +374,13 @@ class MiniGPT4SharedLibrary:
             raise RuntimeError("end_chat_batch failed: " + self.library.minigpt4_amd_last_error().decode())
         return [(t or b"").decode("utf-8", errors="replace") for t in toks]
 
+    def amd_prefill_batch(self, ctx, slots: Sequence[int]):
+        """Evaluate the queued prompt rows of several conversations, packed into chunks of <= n_batch rows (one pass over the weights per chunk)."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        rc = self.library.minigpt4_amd_prefill_batch(ctx.ptr, sl.ctypes.data_as(INT_PTR), len(sl))
+        if rc:
+            raise RuntimeError("prefill_batch failed: " + self.library.minigpt4_amd_last_error().decode())
+
     def amd_eval_batch(self, ctx, slots: Sequence[int], tokens: Sequence[int]) -> List[int]:
         """One batched decode step with GIVEN next tokens (teacher forcing); returns every conversation's own greedy choice."""
         n = len(slots)
@@ -401,6 +411,42 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_kv_shift rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return k, v, float(ms.value)
+
+    def amd_test_attn_prefill_seg(self, kc: np.ndarray, vc: np.ndarray, n_head: int, segs, q: np.ndarray, form: int = 0, fp16_rows: bool = False):
+        """Segmented prompt attention (one launch) and one launch_attn_prefill per segment on fp16 caches [n_slots][n_ctx][E]; segs = [(slot, rows, pos0)], q = packed
+        [N][E] fp32.  form: 0 auto, 1 h8, 2 h QS 2, 3 h QS 1, 4 exact f32.  Returns (out_seg, out_ref, seg_launched); fp16_rows: the launchers may store fp16 rows instead
+        (the F16 wo's input), returns (out_seg, out_ref, seg_launched, h_seg, h_ref, (seg wrote fp16, every per-segment launch wrote fp16))."""
+        kc, vc = np.ascontiguousarray(kc, np.float16), np.ascontiguousarray(vc, np.float16)
+        assert kc.ndim == 3 and kc.shape == vc.shape
+        S, C, E = kc.shape
+        sg = np.ascontiguousarray(segs, np.int32).reshape(-1, 3)
+        q = np.ascontiguousarray(q, np.float32)
+        a, b, one = np.zeros_like(q), np.zeros_like(q), ctypes.c_int32()
+        ha, hb, wrote = (np.zeros(q.shape, np.uint16), np.zeros(q.shape, np.uint16), (ctypes.c_int32 * 2)()) if fp16_rows else (None, None, None)
+        hp = [x.ctypes.data_as(VOID_PTR) if x is not None else None for x in (ha, hb)]
+        rc = self.library.minigpt4_amd_test_attn_prefill_seg(n_head, E // n_head, C, S, kc.ctypes.data_as(VOID_PTR), vc.ctypes.data_as(VOID_PTR), len(sg), sg.ctypes.data_as(INT_PTR),
+                                                             q.ctypes.data_as(FLOAT_PTR), form, a.ctypes.data_as(FLOAT_PTR), b.ctypes.data_as(FLOAT_PTR), ctypes.byref(one),
+                                                             hp[0], hp[1], wrote)
+        if rc:
+            raise RuntimeError(f"test_attn_prefill_seg rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        if fp16_rows:
+            return a, b, bool(one.value), ha, hb, (bool(wrote[0]), bool(wrote[1]))
+        return a, b, bool(one.value)
+
+    def amd_test_rope_kv_seg(self, n_head: int, n_ctx: int, n_slots: int, segs, q: np.ndarray, k: np.ndarray, v: np.ndarray, ks: int = 1):
+        """RoPE + cache append of packed rows (k_rope_kv_seg, ks > 1: the slab form) and per segment (k_rope_kv / _slabs).  Returns ((q, kc, vc) seg, (q, kc, vc) ref);
+        caches [n_slots][n_ctx][E] fp16."""
+        q, k, v = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+        N, E = q.shape
+        sg = np.ascontiguousarray(segs, np.int32).reshape(-1, 3)
+        out = [np.zeros_like(q), np.zeros((n_slots, n_ctx, E), np.float16), np.zeros((n_slots, n_ctx, E), np.float16),
+               np.zeros_like(q), np.zeros((n_slots, n_ctx, E), np.float16), np.zeros((n_slots, n_ctx, E), np.float16)]
+        ptr = [o.ctypes.data_as(FLOAT_PTR) if o.dtype == np.float32 else o.ctypes.data_as(VOID_PTR) for o in out]
+        rc = self.library.minigpt4_amd_test_rope_kv_seg(n_head, E // n_head, n_ctx, n_slots, len(sg), sg.ctypes.data_as(INT_PTR), q.ctypes.data_as(FLOAT_PTR), k.ctypes.data_as(FLOAT_PTR),
+                                                        v.ctypes.data_as(FLOAT_PTR), ks, *ptr)
+        if rc:
+            raise RuntimeError(f"test_rope_kv_seg rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return tuple(out[:3]), tuple(out[3:])
 
     def amd_batch_path(self, ctx) -> dict:
         """Launch kinds of the batched step as last built (include/minigpt4_amd.h: minigpt4_amd_batch_path)."""

@@ -62,7 +62,8 @@ class ReplicaServer:
         pre = self.lib.minigpt4_preprocess_image(self.ctx, raw)
         return pre, [raw, pre]
 
-    def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False) -> List[str]:
+    def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
+            batched_prefill: bool = False) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         answers: List[str] = [""] * len(requests)
@@ -81,6 +82,8 @@ class ReplicaServer:
                     lib.minigpt4_reset_chat(ctx)
                     lib.minigpt4_system_prompt(ctx)
                     lib.minigpt4_begin_chat_image(ctx, embs.embeddings[slot], requests[i].prompt)
+                if batched_prefill:                           # the wave's prompts in one pass per chunk instead of one pass per conversation
+                    lib.amd_prefill_batch(ctx, list(range(len(wave))))
                 text = {slot: "" for slot in range(len(wave))}
                 shown = {slot: "" for slot in range(len(wave))}
                 left = {slot: requests[i].max_tokens for slot, i in enumerate(wave)}
