@@ -28,6 +28,10 @@ MINIGPT4_API int minigpt4_amd_test_mmq2(int ggml_type, const void *raw_w, int n_
  * epi = 1: y[g] = silu(W0[g] . a) * (W1[g] . a) (n1 == 2); epi = 2: every fp32 accumulation in the CPU oracle's order (k-quants; bit-identical to oracle/refcpu.c).  residual / y: (n1 + n2) * n_out floats.  Returns 4 when the shape is outside the kernel's range. */
 MINIGPT4_API int minigpt4_amd_test_matvec(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2,
                                           int prep, int fuse, int epi, const float *residual, float *y);
+/* the same with the SiLU arm chosen by the caller: silu_table = the table prep 3 / epi 1 gather from, or NULL = the computed arm (what the decode step's stand-alone
+ * silu * mul preparation launch gets in fast mode: prep 3 with fuse 0; the fused prologue and the pair epilogue always gather, so NULL with them is refused: 1) */
+MINIGPT4_API int minigpt4_amd_test_matvec_ex(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2,
+                                             int prep, int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y);
 /* The batched-decode mat-vec: N = 1..4 activation rows x[N][n_in] against n_mat (1..3) equally spaced matrices in one weight pass; y / residual: [n_mat][N][n_out].
  * Returns 4 when the shape / type is outside the kernel's range. */
 MINIGPT4_API int minigpt4_amd_test_matvec_rows(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, float *y);
@@ -38,6 +42,18 @@ MINIGPT4_API int minigpt4_amd_test_quantize(const float *x, const float *rms_w, 
 MINIGPT4_API int minigpt4_amd_test_gemm_f16(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C);
 /* the same through the skinny-M kernel of the Q-Former (k_gemm_f16_skinny: N % 16 == 0, K % 32 == 0; 4 otherwise) */
 MINIGPT4_API int minigpt4_amd_test_gemm_f16_skinny(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C);
+
+/* the same two with the arm chosen by the caller: gelu_table = the 65536 fp16 bit patterns the GELU epilogue gathers from, or NULL = the computed arm (Tables::gelu null, what the
+ * engine's fast mode passes); skinny != 0: the skinny-M kernel */
+MINIGPT4_API int minigpt4_amd_test_gemm_f16_ex(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, int skinny, const unsigned short *gelu_table, float *C);
+/* exp / SiLU / GELU exactly as the kernels' epilogues call them (csrc/activations.hpp), evaluated on all 65536 fp16 bit patterns -> out[65536] fp16 bit patterns.
+ * which: 0 GELU, 1 SiLU, 2 exp; table (65536 fp16 bit patterns) is gathered from, NULL selects the computed form */
+MINIGPT4_API int minigpt4_amd_test_activation(int which, const unsigned short *table, unsigned short *out);
+/* The ViT / Q-Former attention kernel (launch_attn_f32) on host rows q [batch * nq][heads * hd], k / v [batch * nk][heads * hd], hd 88 or 64, nk <= 320.  head_major != 0: the rows
+ * reach the kernel as [head][batch * rows][hd] with head strides (the ViT's layout); qt: query tiles per workgroup, 0 = the launcher's choice; exp_table: ggml's fp16 exp table or
+ * NULL = computed exponentials.  out [batch * nq][heads * hd] fp32, out_h (may be NULL) the same as fp16 bit patterns */
+MINIGPT4_API int minigpt4_amd_test_attn_f32(const float *q, const float *k, const float *v, int heads, int hd, int nq, int nk, int batch, float q_prescale, float score_div, int head_major,
+                                            int qt, const unsigned short *exp_table, float *out, unsigned short *out_h);
 
 /* Micro-benchmark of the image path's fp16 GEMM on synthetic operands (tools/timeline_gemm.py). flags: 1 GELU, 2 residual, 4 fp16 output too; variant 0 = the dispatcher
  * (launch_gemm_f16), 1 = the skinny-M kernel, 2 + (slices << 8) = split K + k_splitk_reduce_ln; n_sets weight matrices are cycled (no Infinity-Cache repeats) */
@@ -50,6 +66,8 @@ MINIGPT4_API int minigpt4_amd_bench_attn_f32_b(int heads, int hd, int nq, int nk
 MINIGPT4_API void minigpt4_amd_test_set_attn_qt(int qt);
 /* the F16 feed-forward pair launch: out_h[N][n_out] = fp16(silu_table(w1 x) * (w3 x)) (uint16 bit patterns), w = w1 then w3 as fp16 [n_out][n_in]; 4 = shape outside the path */
 MINIGPT4_API int minigpt4_amd_test_f16_silu_pair(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, unsigned short *out_h, float *out_f);
+/* the same with the SiLU arm chosen by the caller (silu_table or NULL = computed, as above) */
+MINIGPT4_API int minigpt4_amd_test_f16_silu_pair_ex(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, const unsigned short *silu_table, unsigned short *out_h, float *out_f);
 /* the context shift's kernel (launch_kv_shift) on host fp16 caches k / v = [n_layer][n_ctx][n_embd] (uint16 bit patterns, shifted in place): rows [n_keep + n_discard, n_rows)
  * move down by n_discard, keys re-rotated by -n_discard positions with the engine's RoPE table.  ms (may be NULL): hipEvent time of the launch.  1 = bad arguments */
 MINIGPT4_API int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, int n_rows, int n_keep, int n_discard, uint16_t *k, uint16_t *v, float *ms);

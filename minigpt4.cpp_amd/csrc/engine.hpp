@@ -202,10 +202,12 @@ private:
     __half *kc_ = nullptr, *vc_ = nullptr;
     float *cos_ = nullptr, *sin_ = nullptr;
     Tables tabs_;
-    // tabs_ = ggml's three fp16 tables (GELU, SiLU, exp) as the host libm evaluates them: what parity mode, every prompt pass and every GELU read.
-    // tabs_dec_ = what the DECODE step's attention and SiLU launches get, tabs_vis_ = what the ViT / Q-Former attention gets: copies of tabs_ whose exp (and, for the decode step, silu)
-    // pointers are NULL when MINIGPT4_COMPUTED_TABLES is on (the default) -- the kernels then compute the table VALUES (qtraits.hpp exp_h / silu_h: equal to the table's up to one fp16
-    // ulp in ~1 of 10^4 values) instead of gathering them from the 128 KB tables; tabs_vis_.gelu is NULL too (computed_gelu_): the vision GEMMs' GELU epilogues compute (gelu_v)
+    // tabs_ = ggml's three fp16 tables (GELU, SiLU, exp) as the host libm evaluates them: what parity mode, the quantised models' prompt passes, prompt-row attention, the decode
+    // mat-vec's fused SiLU prologue / pair epilogue and the stand-alone GELU epilogue launch read.
+    // tabs_dec_ = what the DECODE step's attention and its stand-alone SiLU preparation launch get (and, pair_silu_computed_, the F16 model's w1 | w3 pair launch, which serves prompt
+    // chunks from 512 rows up -- shorter chunks gather); tabs_vis_ = what the ViT / Q-Former attention and the vision GEMMs' GELU epilogues get: copies of tabs_ whose exp / silu resp.
+    // exp / gelu (computed_gelu_) pointers are NULL when MINIGPT4_COMPUTED_TABLES is on (the default) -- the kernels then compute the table VALUES (activations.hpp exp_h / silu_h /
+    // gelu_h; within one fp16 ulp of the table on every argument, recorded on an MI355X: 0 / 2 / 1 of 63 488 arguments different) instead of gathering them from the 128 KB tables
     Tables tabs_dec_, tabs_vis_;
     // activations
     float *x_ = nullptr, *q_ = nullptr, *k_ = nullptr, *v_ = nullptr, *att_ = nullptr, *h1_ = nullptr, *h3_ = nullptr, *logits_ = nullptr;

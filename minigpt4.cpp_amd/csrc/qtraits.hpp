@@ -3,21 +3,12 @@
 #pragma once
 #include "common.hpp"
 #include "devutil.hpp"
+#include "activations.hpp"
 
 namespace mg4 {
 
 __device__ __forceinline__ int dot4(int a, int b, int c) { return __builtin_amdgcn_sdot4(a, b, c, false); }
-__device__ __forceinline__ float h2f_bits(unsigned short h) { return __half2float(__ushort_as_half(h)); }
-__device__ __forceinline__ unsigned short f2h_bits(float f) { return __half_as_ushort(f2h_rn(f)); }
-__device__ __forceinline__ float f16r(float f) { return __half2float(f2h_rn(f)); }
-__device__ __forceinline__ float tab(const __half *t, float x) { return __half2float(t[f2h_bits(x)]); }
-// Fast mode (round 5, SURVEY.md 9.5: "in fast mode evaluate in fp32"): the VALUE of ggml's fp16 tables computed instead of gathered -- table[x] = fp16(f(fp16(x))) with f
-// evaluated in fp32 by the host libm; here f comes from the GPU's exp (v_exp_f32, ~1 ulp), so a result differs from the table's by one fp16 ulp only when f lands within
-// ~1e-7 of an fp16 rounding boundary (about one value in 10^4).  A null table pointer selects this form: the DEFAULT of fast mode for the decode step's attention / SiLU launches (Engine::tabs_dec_) and for the ViT / Q-Former
-// attention (Engine::tabs_vis_.exp; MINIGPT4_COMPUTED_TABLES=0 passes the tables again, kept under test) -- a stated deviation from ggml's table VALUES by at most one fp16 ulp,
-// inside the fast-mode bound.  Parity mode, every prompt pass and the GELU of the vision tower always read the tables.
-__device__ __forceinline__ float exp_h(const __half *t, float x) { if (t) return tab(t, x); return f16r(__expf(f16r(x))); }
-__device__ __forceinline__ float silu_h(const __half *t, float x) { if (t) return tab(t, x); const float xh = f16r(x); return f16r(xh / (1.0f + __expf(-xh))); }
+// h2f_bits / f2h_bits / f16r / tab and the table functions exp_h / silu_h / gelu_h (gathered or computed): activations.hpp
 
 __device__ __forceinline__ int4 ld16(const void *p) { return *reinterpret_cast<const int4 *>(p); }
 // weight-plane loads: streamed once per token by exactly one wave -> non-temporal (MG4_NT_WEIGHTS=0 builds the default-policy variant for A/B runs)

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "api_internal.hpp"
+#include "activations.hpp"
 #include "imageio.hpp"
 #include "quantize.hpp"
 #include "minigpt4_amd.h"
@@ -20,6 +21,28 @@ float probe_grid_barrier_us(int n_blocks, int iters, unsigned *errors_out);
 int parse_dist_env_for_test(int *world, int *rank, char *id_file, size_t cap, char *err, size_t err_cap);
 float probe_dma_GBps(int form, int policy, int waves, int fill, int depth, int deal, size_t total_bytes);
 void launch_fill_random(void *p, size_t bytes, unsigned seed, hipStream_t s);
+}
+
+// One thread per fp16 bit pattern: the table functions of activations.hpp exactly as the kernels' epilogues call them (t == null: the computed form), result as fp16 bits.
+// which: 0 GELU, 1 SiLU, 2 exp (the oracle's orc_table numbering)
+__global__ __launch_bounds__(256) void k_test_activation(int which, const __half *t, unsigned short *out) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= 65536u) return;
+    const float x = h2f_bits((unsigned short)i);
+    const float y = which == 0 ? gelu_h(t, x) : which == 1 ? silu_h(t, x) : exp_h(t, x);
+    out[i] = f2h_bits(y);
+}
+
+// ggml's fp16 tables as the host libm gives them (the hooks' original entry points gather from these; the _ex forms take the caller's table or none)
+static std::vector<unsigned short> host_gelu_table() {
+    std::vector<unsigned short> g(65536);
+    for (int i = 0; i < 65536; i++) { const float x = __half2float(__ushort_as_half((unsigned short)i)); g[(size_t)i] = __half_as_ushort(__float2half_rn(0.5f * x * (1.0f + tanhf(0.79788456080286535587989211986876f * x * (1.0f + 0.044715f * x * x))))); }
+    return g;
+}
+static std::vector<unsigned short> host_silu_table() {
+    std::vector<unsigned short> si(65536);
+    for (int i = 0; i < 65536; i++) { const float v = __half2float(__ushort_as_half((unsigned short)i)); si[(size_t)i] = __half_as_ushort(__float2half_rn(v / (1.0f + expf(-v)))); }
+    return si;
 }
 
 extern "C" {
@@ -128,8 +151,21 @@ int minigpt4_amd_test_mmq2(int ggml_type, const void *raw_w, int n_mat, int64_t 
 // The decode mat-vec launches exactly as Engine::forward issues them: n1 equally spaced matrices of type1 (+ optionally n2 of type2 in the same,
 // mixed-type launch), activation preparation either standalone (fuse = 0) or in the kernel prologue, optional residual, optional SiLU row-pair
 // epilogue.  prep: 1 = rms_norm(x) * x2, 2 = x, 3 = silu(x) * x2.  y: (n1 + n2) * n_out floats (epi = 1: n_out floats).
+static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
+                            int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y);
 int minigpt4_amd_test_matvec(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
                              int fuse, int epi, const float *residual, float *y) {
+    return test_matvec_impl(type1, raw1, n1, type2, raw2, n2, n_in, n_out, x, x2, prep, fuse, epi, residual, host_silu_table().data(), y);
+}
+// silu_table: the table of prep = 3 / epi = 1, or NULL: Tables::silu stays null -- the computed arm, as Engine::tabs_dec_ passes it to the decode step's launches
+int minigpt4_amd_test_matvec_ex(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
+                                int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y) {
+    // the mat-vec's fused SiLU prologue and its pair epilogue always gather (the engine hands them the tables): only the stand-alone preparation launch has a computed arm
+    if (!silu_table && ((fuse && prep == 3) || epi == 1)) { set_last_error("the fused SiLU prologue / pair epilogue of the decode mat-vec need a table"); return 1; }
+    return test_matvec_impl(type1, raw1, n1, type2, raw2, n2, n_in, n_out, x, x2, prep, fuse, epi, residual, silu_table, y);
+}
+static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
+                            int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y) {
     if (!raw1 || !x || !y || n_in <= 0 || n_out <= 0 || n1 < 1 || n1 > 3 || n2 < 0 || n2 > 1 || prep < 1 || prep > 3 || (prep != 2 && !x2)) return 1;
     if (!qweight_supported(type1) || n_in % gt_block(type1) || (n2 && (!raw2 || !qweight_supported(type2) || n_in % gt_block(type2)))) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
@@ -156,9 +192,7 @@ int minigpt4_amd_test_matvec(int type1, const void *raw1, int n1, int type2, con
         if (residual) HIP_CHECK(hipMemcpy(d_res.p, residual, (size_t)nt * R * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(d_y.p, 0xFF, (size_t)nt * R * 4));
         Tables tb;
-        { std::vector<__half> si(65536);
-          for (int i = 0; i < 65536; i++) { const float v = __half2float(__ushort_as_half((unsigned short)i)); si[(size_t)i] = __float2half_rn(v / (1.0f + expf(-v))); }
-          HIP_CHECK(hipMemcpy(d_tab.p, si.data(), 131072, hipMemcpyHostToDevice)); tb.silu = d_tab.as<__half>(); }
+        if (silu_table) { HIP_CHECK(hipMemcpy(d_tab.p, silu_table, 131072, hipMemcpyHostToDevice)); tb.silu = d_tab.as<__half>(); }
         ActQ A; alloc_act(A, keep, 1, (size_t)K);
         int mask = 0; for (int m = 0; m < nt; m++) mask |= act_mask_for(W[(size_t)m].type);
         if (!fuse) {
@@ -358,10 +392,12 @@ int minigpt4_amd_test_quantize(const float *x, const float *rms_w, int64_t N, in
     });
 }
 
-static int test_gemm_impl(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C, bool skinny);
-int minigpt4_amd_test_gemm_f16(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C) { return test_gemm_impl(A, W, bias, M, N, K, gelu, C, false); }
-int minigpt4_amd_test_gemm_f16_skinny(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C) { return test_gemm_impl(A, W, bias, M, N, K, gelu, C, true); }
-static int test_gemm_impl(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C, bool skinny) {
+// table: the GELU table the epilogue gathers from (65536 fp16 bit patterns, uploaded); NULL with gelu set: Tables::gelu stays null -- the computed arm, as Engine::tabs_vis_ passes it
+static int test_gemm_impl(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C, bool skinny, const unsigned short *table);
+int minigpt4_amd_test_gemm_f16(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C) { return test_gemm_impl(A, W, bias, M, N, K, gelu, C, false, gelu ? host_gelu_table().data() : nullptr); }
+int minigpt4_amd_test_gemm_f16_skinny(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C) { return test_gemm_impl(A, W, bias, M, N, K, gelu, C, true, gelu ? host_gelu_table().data() : nullptr); }
+int minigpt4_amd_test_gemm_f16_ex(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, int skinny, const unsigned short *gelu_table, float *C) { return test_gemm_impl(A, W, bias, M, N, K, gelu, C, skinny != 0, gelu_table); }
+static int test_gemm_impl(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C, bool skinny, const unsigned short *table) {
     if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || K % 16) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -369,9 +405,7 @@ static int test_gemm_impl(const float *A, const float *W, const float *bias, int
         HIP_CHECK(hipMemcpy(dA.p, A, (size_t)M * K * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dW.p, W, (size_t)N * K * 4, hipMemcpyHostToDevice));
         if (bias) HIP_CHECK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
         Tables tb;
-        if (gelu) { std::vector<__half> g(65536);
-            for (int i = 0; i < 65536; i++) { const float x = __half2float(__ushort_as_half((unsigned short)i)); g[(size_t)i] = __float2half_rn(0.5f * x * (1.0f + tanhf(0.79788456080286535587989211986876f * x * (1.0f + 0.044715f * x * x)))); }
-            HIP_CHECK(hipMemcpy(dtab.p, g.data(), 131072, hipMemcpyHostToDevice)); tb.gelu = dtab.as<__half>(); }
+        if (gelu && table) { HIP_CHECK(hipMemcpy(dtab.p, table, 131072, hipMemcpyHostToDevice)); tb.gelu = dtab.as<__half>(); }
         launch_f32_to_f16(dA.as<float>(), dAh.as<__half>(), (size_t)M * K, nullptr); launch_f32_to_f16(dW.as<float>(), dWh.as<__half>(), (size_t)N * K, nullptr);
         if (skinny) { if (!launch_gemm_f16_skinny(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, nullptr, gelu != 0, tb, dC.as<float>(), nullptr, N, nullptr)) return 4; }
         else launch_gemm_f16(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, nullptr, gelu != 0, tb, dC.as<float>(), nullptr, N, nullptr);
@@ -490,23 +524,77 @@ int minigpt4_amd_bench_attn_f32_b(int heads, int hd, int nq, int nk, int batch, 
 void minigpt4_amd_test_set_attn_qt(int qt) { set_attn_vit_qt(qt); }
 // The F16 feed-forward pair launch (launch_gemm_f16_silu_pair): x [N][n_in] fp32 (rounded to fp16 as the engine's row preparation does), w = w1 then w3, each [n_out][n_in]
 // fp16; out_h [N][n_out] = fp16(silu_table(w1 x) * (w3 x)) as uint16 bit patterns, out_f (optional) the fp32 product before the rounding
-int minigpt4_amd_test_f16_silu_pair(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, unsigned short *out_h, float *out_f) {
+static int test_f16_silu_pair_impl(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, const unsigned short *table, unsigned short *out_h, float *out_f);
+int minigpt4_amd_test_f16_silu_pair(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, unsigned short *out_h, float *out_f) { return test_f16_silu_pair_impl(x, w_f16, N, n_in, n_out, host_silu_table().data(), out_h, out_f); }
+// silu_table: the table the epilogue gathers from, or NULL: Tables::silu stays null -- the computed arm the engine's fast mode passes to this launch
+int minigpt4_amd_test_f16_silu_pair_ex(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, const unsigned short *silu_table, unsigned short *out_h, float *out_f) { return test_f16_silu_pair_impl(x, w_f16, N, n_in, n_out, silu_table, out_h, out_f); }
+static int test_f16_silu_pair_impl(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, const unsigned short *table, unsigned short *out_h, float *out_f) {
     if (!x || !w_f16 || !out_h || N <= 0 || n_in <= 0 || n_out <= 0) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
         const size_t nx = (size_t)(N * n_in), nw = (size_t)(n_in * n_out), no = (size_t)(N * n_out);
         DevBuf dx(nx * 4), dxh(nx * 2), dw(nw * 2 * 2), dh(no * 2), df(no * 4), dtab(65536 * 2);
         HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dw.p, w_f16, nw * 4, hipMemcpyHostToDevice));
-        { std::vector<__half> si(65536); for (int i = 0; i < 65536; i++) { const float v = __half2float(__ushort_as_half((unsigned short)i)); si[(size_t)i] = __float2half_rn(v / (1.0f + expf(-v))); }
-          HIP_CHECK(hipMemcpy(dtab.p, si.data(), 131072, hipMemcpyHostToDevice)); }
+        Tables tb;
+        if (table) { HIP_CHECK(hipMemcpy(dtab.p, table, 131072, hipMemcpyHostToDevice)); tb.silu = dtab.as<__half>(); }
         launch_f32_to_f16(dx.as<float>(), dxh.as<__half>(), nx, nullptr);
-        Tables tb; tb.silu = dtab.as<__half>();
         hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0));
         if (!launch_gemm_f16_silu_pair(dxh.as<__half>(), (int)n_in, dw.as<__half>(), dw.as<__half>() + nw, (int)N, (int)n_out, (int)n_in, tb, df.as<float>(), dh.as<__half>(), (int)n_out,
                                        prop.multiProcessorCount, nullptr)) return 4;
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out_h, dh.p, no * 2, hipMemcpyDeviceToHost));
         if (out_f) HIP_CHECK(hipMemcpy(out_f, df.p, no * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+// exp / SiLU / GELU (activations.hpp) over all 65 536 fp16 bit patterns: table != null gathers from it (uploaded), table == null computes -- the arm fast mode ships
+int minigpt4_amd_test_activation(int which, const unsigned short *table, unsigned short *out) {
+    if (which < 0 || which > 2 || !out) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        DevBuf dtab(65536 * 2), dout(65536 * 2);
+        if (table) HIP_CHECK(hipMemcpy(dtab.p, table, 131072, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xFF, 131072));
+        hipLaunchKernelGGL(k_test_activation, dim3(256), dim3(256), 0, nullptr, which, table ? dtab.as<__half>() : nullptr, dout.as<unsigned short>());
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dout.p, 131072, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+// The ViT / Q-Former attention (launch_attn_f32 -> k_attn_vit) on host rows q [batch * nq][heads * hd], k / v [batch * nk][heads * hd] (an image's rows back to back).
+// head_major: the rows are re-laid [head][batch * rows][hd] on the way to the device and the launch gets the head strides, as the ViT's qkv projection stores them; qt: query tiles
+// per workgroup (0 = the launcher's choice; back at 0 afterwards); exp_table: ggml's fp16 exp table (gathered) or NULL (computed exponentials).  out / out_h: [batch * nq][heads * hd] fp32 / fp16 bits.
+int minigpt4_amd_test_attn_f32(const float *q, const float *k, const float *v, int heads, int hd, int nq, int nk, int batch, float q_prescale, float score_div, int head_major, int qt,
+                               const unsigned short *exp_table, float *out, unsigned short *out_h) {
+    if (!q || !k || !v || !out || heads < 1 || (hd != 88 && hd != 64) || nq < 1 || nk < 1 || nk > 320 || batch < 1 || batch > 16 || qt < 0) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const int D = heads * hd, Rq = batch * nq, Rk = batch * nk;
+        const size_t nQ = (size_t)Rq * D, nK = (size_t)Rk * D;
+        auto lay = [&](const float *src, int R) {   // [R][heads][hd] -> [heads][R][hd]
+            std::vector<float> o((size_t)R * D);
+            if (!head_major) { std::memcpy(o.data(), src, o.size() * 4); return o; }
+            for (int r = 0; r < R; r++) for (int h = 0; h < heads; h++) std::memcpy(&o[((size_t)h * R + r) * hd], src + (size_t)r * D + (size_t)h * hd, (size_t)hd * 4);
+            return o;
+        };
+        DevBuf dq(nQ * 4), dk(nK * 4), dv(nK * 4), dout(nQ * 4), douth(nQ * 2), dtab(65536 * 2);
+        { const std::vector<float> hq = lay(q, Rq), hk = lay(k, Rk), hv = lay(v, Rk);
+          HIP_CHECK(hipMemcpy(dq.p, hq.data(), nQ * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dk.p, hk.data(), nK * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, hv.data(), nK * 4, hipMemcpyHostToDevice)); }
+        HIP_CHECK(hipMemset(dout.p, 0xFF, nQ * 4)); HIP_CHECK(hipMemset(douth.p, 0xFF, nQ * 2));
+        Tables tb;
+        if (exp_table) {   // as Engine::init sets the table up: the LDS part covers arguments -0 .. the last one whose entry is not zero, in whole 2048-entry pieces
+            HIP_CHECK(hipMemcpy(dtab.p, exp_table, 131072, hipMemcpyHostToDevice)); tb.exp = dtab.as<__half>();
+            int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if ((exp_table[c] & 0x7FFF) == 0) break; nneg++; }
+            tb.exp_neg_n = (nneg + 2047) / 2048 * 2048;
+        }
+        struct QtScope { QtScope(int t) { set_attn_vit_qt(t); } ~QtScope() { set_attn_vit_qt(0); } } scope(qt);
+        if (head_major) launch_attn_f32(dq.as<float>(), hd, dk.as<float>(), dv.as<float>(), hd, nq, nk, heads, hd, q_prescale, score_div, tb, dout.as<float>(), douth.as<__half>(), D, nullptr, batch, Rq * hd, Rk * hd);
+        else launch_attn_f32(dq.as<float>(), D, dk.as<float>(), dv.as<float>(), D, nq, nk, heads, hd, q_prescale, score_div, tb, dout.as<float>(), douth.as<__half>(), D, nullptr, batch);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dout.p, nQ * 4, hipMemcpyDeviceToHost));
+        if (out_h) HIP_CHECK(hipMemcpy(out_h, douth.p, nQ * 2, hipMemcpyDeviceToHost));
         return 0;
     });
 }

@@ -5,6 +5,7 @@
 //   * fp32 attention (ViT 16 x 88, BERT 12 x 64) staged through LDS; exact-sum softmax through the fp16 exp table.
 #include "kernels.hpp"
 #include "devutil.hpp"
+#include "activations.hpp"
 
 #include <algorithm>
 
@@ -15,24 +16,8 @@ typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef float float16_t __attribute__((ext_vector_type(16)));
 typedef unsigned v4u_g __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ unsigned short f2h_bits_v(float f) { return __half_as_ushort(f2h_rn(f)); }
-__device__ __forceinline__ float tab_v(const __half *t, float x) { return __half2float(t[f2h_bits_v(x)]); }
-// SiLU likewise (the F16 language model's w1 | w3 pair epilogue): table[x] = fp16(x / (1 + expf(-x))) on the fp16-rounded argument (qtraits.hpp silu_h)
-__device__ __forceinline__ float silu_v(const __half *t, float x) {
-    if (t) return tab_v(t, x);
-    const float xh = __half2float(f2h_rn(x));
-    return __half2float(f2h_rn(xh / (1.0f + __expf(-xh))));
-}
-// GELU through ggml's fp16 table, or (t == null: fast mode, round 6) the table's VALUE computed: table[x] = fp16(0.5 x (1 + tanhf(sqrt(2 / pi) x (1 + 0.044715 x^2)))) on the fp16-rounded
-// argument, with tanh(u) = 1 - 2 / (exp(2 u) + 1) on the device's exp -- the host table's entry except within ~1e-7 of an fp16 rounding boundary (as exp_h / silu_h, qtraits.hpp).
-// A GEMM tile's epilogue gathers 16-64 table entries per lane from a 128 KB table: at four images that is 7 us of the 39 us fc1 launch.
-__device__ __forceinline__ float gelu_v(const __half *t, float x) {
-    if (t) return tab_v(t, x);
-    const float xh = __half2float(f2h_rn(x));
-    const float u = 0.79788456080286535587989211986876f * xh * (1.0f + 0.044715f * xh * xh);
-    const float th = 1.0f - 2.0f / (__expf(2.0f * u) + 1.0f);
-    return __half2float(f2h_rn(0.5f * xh * (1.0f + th)));
-}
+// exp / SiLU / GELU through ggml's fp16 tables or (null table pointer: fast mode) the tables' VALUES computed: activations.hpp (exp_h, silu_h, gelu_h), one definition shared with the
+// language model's kernels.  Why GELU is computed: a GEMM tile's epilogue gathers 16-64 table entries per lane from a 128 KB table -- at four images 7 us of the 39 us fc1 launch.
 
 // In-kernel timeline of the image path's kernels (diagnostic builds only, as the mat-vec's: make EXTRA=-DMG4_TIMELINE OUT=../libminigpt4_tl.so OBJ=build_tl).  Thread 0 of
 // every workgroup stamps the 100 MHz constant clock into 32 slots; the last launch wins; read with minigpt4_amd_timeline_vision (tools/timeline_gemm.py).
@@ -221,7 +206,7 @@ __global__ __launch_bounds__(GB_M / (32 * TM) * (BN / (32 * TN)) * 64) void k_ge
             }
             if (GELU) {
 #pragma unroll
-                for (int r = 0; r < 16; r++) v[r] = gelu_v(tb.gelu, v[r]);
+                for (int r = 0; r < 16; r++) v[r] = gelu_h(tb.gelu, v[r]);
             }
             if (RES) {
                 float rr[16];
@@ -393,7 +378,7 @@ __global__ __launch_bounds__(BM / (32 * TM) * (BN / (32 * TN)) * 64) void k_gemm
         for (int a = 0; a < TM; a++) {
             float sv[16];
 #pragma unroll
-            for (int r = 0; r < 16; r++) sv[r] = silu_v(tb.silu, acc[a][0][r]);
+            for (int r = 0; r < 16; r++) sv[r] = silu_h(tb.silu, acc[a][0][r]);
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int row = m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
@@ -422,7 +407,7 @@ __global__ __launch_bounds__(BM / (32 * TM) * (BN / (32 * TN)) * 64) void k_gemm
             }
             if (GELU) {
 #pragma unroll
-                for (int r = 0; r < 16; r++) v[r] = gelu_v(tb.gelu, v[r]);
+                for (int r = 0; r < 16; r++) v[r] = gelu_h(tb.gelu, v[r]);
             }
             if (RES) {
                 float rr[16];
@@ -590,7 +575,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16_big(const __half *__restric
             }
             if (GELU) {
 #pragma unroll
-                for (int r = 0; r < 16; r++) v[r] = gelu_v(tb.gelu, v[r]);
+                for (int r = 0; r < 16; r++) v[r] = gelu_h(tb.gelu, v[r]);
             }
             if (RES) {
                 float rr[16];
@@ -770,7 +755,7 @@ __global__ __launch_bounds__(64 * SK_WAVES) void k_gemm_f16_skinny(const __half 
 #pragma unroll
         for (int w = 1; w < SK_WAVES; w++) v += red[w][mt][lane][r];
         if (bias) v = bv + v;
-        if (GELU) v = gelu_v(tb.gelu, v);
+        if (GELU) v = gelu_h(tb.gelu, v);
         if (RES) v = rr[r] + v;
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ob, (int)(o[r] * 4u), 0, 0);
         __builtin_amdgcn_raw_buffer_store_b16(__half_as_ushort(f2h_rn(v)), hb, (int)(o[r] * 2u), 0, 0);
@@ -1080,7 +1065,7 @@ __global__ __launch_bounds__(256) void k_attn_vref(const float *__restrict__ q, 
     __syncthreads();
     mx = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
     double sum = 0.0;
-    for (int j = tid; j < nk; j += 256) { const float e = tab_v(tb.exp, sc[j] - mx); sc[j] = e; sum += (double)e; }   // fp16 values: exact in any order
+    for (int j = tid; j < nk; j += 256) { const float e = tab(tb.exp, sc[j] - mx); sc[j] = e; sum += (double)e; }   // fp16 values: exact in any order
     sum = wave_sum_d(sum);
     if ((tid & 63) == 0) red_d[tid >> 6] = sum;
     __syncthreads();
@@ -1101,8 +1086,6 @@ void launch_attn_vref(const float *q, int ldq, const float *k, const float *v, i
 }
 
 typedef float float4_t __attribute__((ext_vector_type(4)));
-// the VALUE of ggml's fp16 exp table, computed: table[x] = fp16(expf(fp16(x))) (qtraits.hpp::exp_h: differs from the host libm's entry by one fp16 ulp in about 1 of 10^4 values)
-__device__ __forceinline__ float exp_c16(float x) { return __half2float(f2h_rn(__expf(__half2float(f2h_rn(x))))); }
 // ---------------------------------------------------------------------------------------------------------------------
 // k_attn_vit -- fp32 attention without K / V staging (round 2; replaces the LDS-staged k_attn_mfma for nk <= 64 * TPW keys).
 //   * workgroup = (head, 16 queries, image); its 4 waves split the KEYS (wave w owns key tiles w, w + 4, ...), so a ViT layer is 16 x 17 = 272 workgroups
@@ -1175,7 +1158,8 @@ __global__ __launch_bounds__(256) void k_attn_vit(const float *__restrict__ q, i
     float *part = reinterpret_cast<float *>(smem + 768);                    // [4][DT * 4][64]
     __half *etab = reinterpret_cast<__half *>(smem + 768 + 4 * DT * 4 * 64 * 4);
     const unsigned NT = (unsigned)tb.exp_neg_n;                             // multiple of 2048
-    // tb.exp == null (fast mode, round 5): the exponentials are computed -- fp16(__expf(fp16 argument)), the table's value up to its last fp16 bit -- and no table travels: the
+    // tb.exp == null (fast mode, round 5): the exponentials are computed -- exp_h, activations.hpp: fp16(__expf(fp16 argument)); on an MI355X the table's entry for every one of the
+    // 65 536 arguments (tests/golden/activation_deviation_observed.json), by contract within one fp16 ulp of it -- and no table travels: the
     // 40 KB LDS-DMA per workgroup was the first thing in every wave's memory queue (~1.6 us of a CU's DMA rate, two workgroups per CU on 16 of the ViT's CUs), in front of the
     // Q / K requests.  Parity mode (k_attn_vref) and the generic path keep the table.
     constexpr bool computed = COMPUTED;                                     // (the launcher instantiates by tb.exp == nullptr)
@@ -1242,13 +1226,13 @@ __global__ __launch_bounds__(256) void k_attn_vit(const float *__restrict__ q, i
 #pragma unroll
             for (int t = 0; t < TPW; t++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) { el[t][r] = exp_c16(sc[t][r] - mx); code[t][r] = 0u; }     // (-inf -> 0, 0 -> 1)
+                for (int r = 0; r < 4; r++) { el[t][r] = exp_h(nullptr, sc[t][r] - mx); code[t][r] = 0u; }     // (-inf -> 0, 0 -> 1)
         } else {
 #pragma unroll
         for (int t = 0; t < TPW; t++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                code[t][r] = f2h_bits_v(sc[t][r] - mx);
+                code[t][r] = f2h_bits(sc[t][r] - mx);
                 el[t][r] = __half2float(etab[min(code[t][r] ^ 0x8000u, NT - 1u)]);
             }
 #pragma unroll
@@ -1373,7 +1357,7 @@ __global__ __launch_bounds__(256) void k_lin_epilogue(const float *__restrict__ 
     if (i >= total) return;
     float v = y[i];
     if (bias) v = bias[i % (size_t)n] + v;
-    if (gelu) v = tab_v(tb.gelu, v);
+    if (gelu) v = tab(tb.gelu, v);
     if (residual) v = residual[i] + v;
     if (out) out[i] = v;
     if (out_h) out_h[i] = f2h_rn(v);

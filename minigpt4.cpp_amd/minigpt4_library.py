@@ -217,6 +217,12 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_quantize.argtypes = [FLOAT_PTR, FLOAT_PTR, ctypes.c_int64, ctypes.c_int64, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_test_gemm_f16.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_gemm_f16_skinny.argtypes = L.minigpt4_amd_test_gemm_f16.argtypes
+        L.minigpt4_amd_test_gemm_f16_ex.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_matvec_ex.argtypes = L.minigpt4_amd_test_matvec.argtypes[:-1] + [VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_f16_silu_pair.argtypes = [FLOAT_PTR, VOID_PTR, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_f16_silu_pair_ex.argtypes = [FLOAT_PTR, VOID_PTR, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_activation.argtypes = [I32, VOID_PTR, VOID_PTR]
+        L.minigpt4_amd_test_attn_f32.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, F32, F32, I32, I32, VOID_PTR, FLOAT_PTR, VOID_PTR]
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
@@ -534,8 +540,10 @@ class MiniGPT4SharedLibrary:
         return y
 
     def amd_test_matvec(self, type1: int, raw1: np.ndarray, n1: int, n_in: int, n_out: int, x: np.ndarray, x2: Optional[np.ndarray] = None, prep: int = 2,
-                        fuse: bool = False, epi: int = 0, residual: Optional[np.ndarray] = None, type2: int = 0, raw2: Optional[np.ndarray] = None) -> np.ndarray:
-        """Decode mat-vec launches exactly as the engine issues them (see include/minigpt4_amd.h)."""
+                        fuse: bool = False, epi: int = 0, residual: Optional[np.ndarray] = None, type2: int = 0, raw2: Optional[np.ndarray] = None,
+                        silu_table: Optional[np.ndarray] = None, computed: bool = False) -> np.ndarray:
+        """Decode mat-vec launches exactly as the engine issues them (see include/minigpt4_amd_test.h).  silu_table: the fp16 SiLU table (uint16[65536]) that prep 3 / epi 1
+        gather from; computed: no table, the kernels compute its values (the decode step's fast-mode arm); neither: the hook's own host-libm table."""
         x = np.ascontiguousarray(x, np.float32).reshape(n_in)
         x2c = None if x2 is None else np.ascontiguousarray(x2, np.float32).reshape(n_in)
         raw1 = np.ascontiguousarray(raw1)
@@ -543,9 +551,14 @@ class MiniGPT4SharedLibrary:
         raw2c = None if raw2 is None else np.ascontiguousarray(raw2)
         res = None if residual is None else np.ascontiguousarray(residual, np.float32).reshape(-1)
         y = np.empty(((1 if epi == 1 else n1 + n2), n_out), np.float32)      # epi 1: the SiLU pair epilogue writes one row; 2: the CPU oracle's fp32 order (k-quants)
-        rc = self.library.minigpt4_amd_test_matvec(type1, raw1.ctypes.data_as(VOID_PTR), n1, type2, None if raw2c is None else raw2c.ctypes.data_as(VOID_PTR), n2,
-                                                   n_in, n_out, x.ctypes.data_as(FLOAT_PTR), None if x2c is None else x2c.ctypes.data_as(FLOAT_PTR), prep, int(fuse), epi,
-                                                   None if res is None else res.ctypes.data_as(FLOAT_PTR), y.ctypes.data_as(FLOAT_PTR))
+        args = [type1, raw1.ctypes.data_as(VOID_PTR), n1, type2, None if raw2c is None else raw2c.ctypes.data_as(VOID_PTR), n2,
+                n_in, n_out, x.ctypes.data_as(FLOAT_PTR), None if x2c is None else x2c.ctypes.data_as(FLOAT_PTR), prep, int(fuse), epi,
+                None if res is None else res.ctypes.data_as(FLOAT_PTR)]
+        if computed or silu_table is not None:
+            tab = None if computed else self._table_arg(silu_table)
+            rc = self.library.minigpt4_amd_test_matvec_ex(*args, None if tab is None else tab.ctypes.data_as(VOID_PTR), y.ctypes.data_as(FLOAT_PTR))
+        else:
+            rc = self.library.minigpt4_amd_test_matvec(*args, y.ctypes.data_as(FLOAT_PTR))
         if rc:
             raise RuntimeError(f"test_matvec rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
         return y
@@ -603,15 +616,72 @@ class MiniGPT4SharedLibrary:
             raise RuntimeError(f"test_quantize rc={rc}")
         return q8k, dk, bs, q80, d0
 
-    def amd_test_gemm_f16(self, A: np.ndarray, W: np.ndarray, bias: Optional[np.ndarray] = None, gelu: bool = False, skinny: bool = False) -> np.ndarray:
+    @staticmethod
+    def _table_arg(table: np.ndarray) -> np.ndarray:
+        t = np.ascontiguousarray(table).view(np.uint16).reshape(-1)
+        if t.size != 65536:
+            raise ValueError("an fp16 table has 65536 entries")
+        return t
+
+    def amd_test_activation(self, which: int, table: Optional[np.ndarray] = None) -> np.ndarray:
+        """GELU (0) / SiLU (1) / exp (2) of csrc/activations.hpp on all 65536 fp16 bit patterns -> uint16[65536]; table: gathered from it, None: the computed form."""
+        out = np.zeros(65536, np.uint16)
+        tab = None if table is None else self._table_arg(table)
+        rc = self.library.minigpt4_amd_test_activation(which, None if tab is None else tab.ctypes.data_as(VOID_PTR), out.ctypes.data_as(VOID_PTR))
+        if rc:
+            raise RuntimeError(f"test_activation rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
+        return out
+
+    def amd_test_f16_silu_pair(self, x: np.ndarray, w: np.ndarray, silu_table: Optional[np.ndarray] = None, computed: bool = False):
+        """The F16 w1 | w3 pair launch: x [N][n_in] fp32, w [2 * n_out][n_in] fp16 (w1 then w3) -> (fp16 bits [N][n_out], fp32 [N][n_out]).  Table arms as amd_test_matvec."""
+        x = np.ascontiguousarray(x, np.float32)
+        w = np.ascontiguousarray(w, np.float16)
+        N, n_in = x.shape
+        n_out = w.shape[0] // 2
+        oh, of = np.zeros((N, n_out), np.uint16), np.zeros((N, n_out), np.float32)
+        if computed or silu_table is not None:
+            tab = None if computed else self._table_arg(silu_table)
+            rc = self.library.minigpt4_amd_test_f16_silu_pair_ex(x.ctypes.data_as(FLOAT_PTR), w.ctypes.data_as(VOID_PTR), N, n_in, n_out,
+                                                                 None if tab is None else tab.ctypes.data_as(VOID_PTR), oh.ctypes.data_as(VOID_PTR), of.ctypes.data_as(FLOAT_PTR))
+        else:
+            rc = self.library.minigpt4_amd_test_f16_silu_pair(x.ctypes.data_as(FLOAT_PTR), w.ctypes.data_as(VOID_PTR), N, n_in, n_out, oh.ctypes.data_as(VOID_PTR), of.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_f16_silu_pair rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
+        return oh, of
+
+    def amd_test_attn_f32(self, q: np.ndarray, k: np.ndarray, v: np.ndarray, heads: int, hd: int, nq: int, nk: int, batch: int = 1, q_prescale: float = 0.0,
+                          score_div: float = 0.0, head_major: bool = False, qt: int = 0, exp_table: Optional[np.ndarray] = None):
+        """The ViT / Q-Former attention kernel on q [batch * nq][heads * hd], k / v [batch * nk][heads * hd] -> (fp32 [batch * nq][heads * hd], the same as fp16 bits).
+        exp_table None: computed exponentials (fast mode's arm)."""
+        D = heads * hd
+        q = np.ascontiguousarray(q, np.float32).reshape(batch * nq, D)
+        k = np.ascontiguousarray(k, np.float32).reshape(batch * nk, D)
+        v = np.ascontiguousarray(v, np.float32).reshape(batch * nk, D)
+        out, out_h = np.zeros((batch * nq, D), np.float32), np.zeros((batch * nq, D), np.uint16)
+        tab = None if exp_table is None else self._table_arg(exp_table)
+        rc = self.library.minigpt4_amd_test_attn_f32(q.ctypes.data_as(FLOAT_PTR), k.ctypes.data_as(FLOAT_PTR), v.ctypes.data_as(FLOAT_PTR), heads, hd, nq, nk, batch,
+                                                     q_prescale, score_div, int(head_major), qt, None if tab is None else tab.ctypes.data_as(VOID_PTR),
+                                                     out.ctypes.data_as(FLOAT_PTR), out_h.ctypes.data_as(VOID_PTR))
+        if rc:
+            raise RuntimeError(f"test_attn_f32 rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
+        return out, out_h
+
+    def amd_test_gemm_f16(self, A: np.ndarray, W: np.ndarray, bias: Optional[np.ndarray] = None, gelu: bool = False, skinny: bool = False,
+                          gelu_table: Optional[np.ndarray] = None, computed: bool = False) -> np.ndarray:
+        """gelu_table: the fp16 GELU table (uint16[65536]) the epilogue gathers from; computed: no table, the epilogue computes (fast mode's arm); neither: the hook's host-libm table."""
         A = np.ascontiguousarray(A, np.float32)
         W = np.ascontiguousarray(W, np.float32)
         M, K = A.shape
         N = W.shape[0]
         C = np.empty((M, N), np.float32)
         b = None if bias is None else np.ascontiguousarray(bias, np.float32)
-        fn = self.library.minigpt4_amd_test_gemm_f16_skinny if skinny else self.library.minigpt4_amd_test_gemm_f16
-        rc = fn(A.ctypes.data_as(FLOAT_PTR), W.ctypes.data_as(FLOAT_PTR), None if b is None else b.ctypes.data_as(FLOAT_PTR), M, N, K, int(gelu), C.ctypes.data_as(FLOAT_PTR))
+        if computed or gelu_table is not None:
+            tab = None if computed else self._table_arg(gelu_table)
+            rc = self.library.minigpt4_amd_test_gemm_f16_ex(A.ctypes.data_as(FLOAT_PTR), W.ctypes.data_as(FLOAT_PTR), None if b is None else b.ctypes.data_as(FLOAT_PTR), M, N, K,
+                                                            int(gelu), int(skinny), None if tab is None else tab.ctypes.data_as(VOID_PTR), C.ctypes.data_as(FLOAT_PTR))
+        else:
+            fn = self.library.minigpt4_amd_test_gemm_f16_skinny if skinny else self.library.minigpt4_amd_test_gemm_f16
+            rc = fn(A.ctypes.data_as(FLOAT_PTR), W.ctypes.data_as(FLOAT_PTR), None if b is None else b.ctypes.data_as(FLOAT_PTR), M, N, K, int(gelu), C.ctypes.data_as(FLOAT_PTR))
         if rc:
             raise RuntimeError(f"test_gemm_f16 rc={rc}")
         return C
