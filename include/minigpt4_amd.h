@@ -95,6 +95,30 @@ MINIGPT4_API int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t ou
 MINIGPT4_API int minigpt4_amd_shift_context(struct MiniGPT4Context *ctx, int n_keep, int n_discard);
 MINIGPT4_API int minigpt4_amd_set_context_shift(struct MiniGPT4Context *ctx, int n_keep);
 
+/* ---- reuse of cached rows: conversation fork and a token-prefix cache -------------------------------------------------------------------------
+ * The K / V rows of a causal model depend only on the rows before them, so rows evaluated once can be copied instead of evaluated again (one copy launch for every
+ * layer, keys and values, all destinations).  Bit-exact in parity mode; otherwise the rows evaluated after a copied prefix run in a pass of a different size, which moves
+ * logits by as much as minigpt4_amd_prefill_batch does against one pass per conversation.
+ * minigpt4_amd_fork_conversation: conversation src_slot -> the n_dst DISTINCT other conversations dst_slots.  n_rows = -1: the whole state -- the source's queued rows
+ * are evaluated first, then its rows, last logits, greedy token and position are copied; every destination can be sampled at once and continues exactly like the source
+ * (k questions about one image: one image turn, fork, k question-only passes).  0 <= n_rows <= n_past(src): that prefix only; the destinations stand at n_past = n_rows
+ * WITHOUT current logits, like after minigpt4_reset_chat: add rows before sampling.  Whatever a destination held (rows, queued prompt) is dropped.  0, or 1 with the
+ * text "fork_conversation: ..." in minigpt4_amd_last_error and every conversation untouched (a slot out of range, a duplicate, a destination equal to the source,
+ * n_dst < 1, n_rows < -1 or > n_past(src)).
+ * minigpt4_amd_set_prefix_cache: the prefix cache of this context, off (0) by default.  max_rows > 0 (clamped to n_ctx) allocates ONE stored prefix of up to max_rows
+ * rows: 2 * n_layer * max_rows * n_embd * 2 bytes (13B, 256 rows: 210 MB).  A prompt pass that starts at position 0 (minigpt4_end_chat..., minigpt4_amd_get_logits,
+ * minigpt4_amd_prefill_batch -- there all matching conversations of the call share one copy launch) compares the leading TOKEN rows of its queue with the stored ids;
+ * a common prefix of at least 8 rows is copied instead of evaluated (never the queue's last row: one row is always evaluated, so that logits exist).  After such a
+ * pass, a leading token run of at least 8 rows that the store did not cover replaces the store (first max_rows rows; at most one capture per call).  So the constant
+ * system prompt + "Human: <Img>" of image turns (the run ends where the image rows begin) is captured once and served to every later request; a text-only chat, whose
+ * run is its whole queue, re-captures its own run each time (one copy).  The store is emptied by minigpt4_amd_set_conversations, by a minigpt4_amd_set_parity that
+ * changes the mode, and by calling this function again (same value: clear and zero the counters; 0: free it).  0 / 1 (no context, max_rows < 0, out of memory).
+ * minigpt4_amd_prefix_cache_info: out = {max_rows, stored_rows, hits, rows_reused_total, captures, rows_reused_by_last_pass (summed over the conversations of the last
+ * call that started a pass at position 0), copy launches made by hits (a batched call with 4 hits adds 1)}.  0 / 1. */
+MINIGPT4_API int minigpt4_amd_fork_conversation(struct MiniGPT4Context *ctx, int src_slot, const int32_t *dst_slots, int n_dst, int n_rows);
+MINIGPT4_API int minigpt4_amd_set_prefix_cache(struct MiniGPT4Context *ctx, int max_rows);
+MINIGPT4_API int minigpt4_amd_prefix_cache_info(struct MiniGPT4Context *ctx, int32_t out[7]);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

@@ -71,6 +71,13 @@ MINIGPT4_API int minigpt4_amd_test_f16_silu_pair_ex(const float *x, const void *
 /* the context shift's kernel (launch_kv_shift) on host fp16 caches k / v = [n_layer][n_ctx][n_embd] (uint16 bit patterns, shifted in place): rows [n_keep + n_discard, n_rows)
  * move down by n_discard, keys re-rotated by -n_discard positions with the engine's RoPE table.  ms (may be NULL): hipEvent time of the launch.  1 = bad arguments */
 MINIGPT4_API int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, int n_rows, int n_keep, int n_discard, uint16_t *k, uint16_t *v, float *ms);
+/* the prefix copy's kernel (launch_kv_copy) on host fp16 caches k / v = [n_slot][n_layer][rows][n_embd] (uint16 bit patterns, changed in place): rows [0, n_rows) of every
+ * layer of slot src go to the n_dst slots dst.  src_rows = 0: the source is that slot, as laid out; src_rows > 0: the source is a COMPACT copy [n_layer][src_rows][n_embd] of
+ * the slot's first src_rows rows (the prefix store's layout), built on the device before the launch.  ms (may be NULL): hipEvent time of the launch.  k == v == NULL: timing only -- the caches are
+ * device buffers of that shape (filled, never copied to or from the host), for shapes too large to move through the host (n_ctx = 2048 rows per layer).  1 = bad arguments
+ * (a slot out of range, src among dst, only one of k / v NULL), 3 = the launcher refused the shape (text in minigpt4_amd_last_error) */
+MINIGPT4_API int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int src, const int32_t *dst, int n_dst, int n_rows, int src_rows, uint16_t *k, uint16_t *v,
+                                           float *ms);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

@@ -282,6 +282,21 @@ int minigpt4_amd_set_context_shift(struct MiniGPT4Context *ctx, int n_keep) {
     if (!ctx) { set_last_error("set_context_shift: no context"); return 1; }
     return guarded(1, [&]() -> int { E_(ctx)->set_context_shift(n_keep); return 0; });
 }
+// ---- reuse of cached rows: conversation fork, prefix store -----------------------------------------------------------------------------
+int minigpt4_amd_fork_conversation(struct MiniGPT4Context *ctx, int src_slot, const int32_t *dst_slots, int n_dst, int n_rows) {
+    if (!ctx) { set_last_error("fork_conversation: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->fork(src_slot, dst_slots, n_dst, n_rows); });
+}
+int minigpt4_amd_set_prefix_cache(struct MiniGPT4Context *ctx, int max_rows) {
+    if (!ctx) { set_last_error("set_prefix_cache: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_prefix_cache(max_rows); });
+}
+int minigpt4_amd_prefix_cache_info(struct MiniGPT4Context *ctx, int32_t out[7]) {
+    if (!ctx || !out) { set_last_error(ctx ? "prefix_cache_info: no output array" : "prefix_cache_info: no context"); return 1; }
+    const Engine::PrefixInfo p = E_(ctx)->prefix_info();
+    out[0] = p.max_rows; out[1] = p.stored_rows; out[2] = p.hits; out[3] = p.rows_reused_total; out[4] = p.captures; out[5] = p.rows_last; out[6] = p.hit_launches;
+    return 0;
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

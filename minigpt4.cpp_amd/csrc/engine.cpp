@@ -92,6 +92,7 @@ Engine::~Engine() {
     if (stream_) HIP_IGNORE(hipStreamSynchronize(stream_));
     for (auto &e : site_events_) { HIP_IGNORE(hipEventDestroy(e.a)); HIP_IGNORE(hipEventDestroy(e.b)); }
     if (stage_) HIP_IGNORE(hipFree(stage_));
+    prefix_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -911,6 +912,7 @@ void Engine::set_parity(bool on) {
     for (Conversation &c : conv_) { if (c.graph) HIP_IGNORE(hipGraphExecDestroy(c.graph)); c.graph = nullptr; }   // captured with the other mode's launches
     for (hipGraphExec_t &g : batch_graph_) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; }
     parity_ = on;
+    prefix_empty();   // the store's rows were computed in the other mode
 }
 
 // Enqueue one forward pass for N rows already described by d_tokens_ (from_tokens) or x_ (embeddings), at position *d_npast_.
@@ -1233,8 +1235,20 @@ int Engine::flush() {
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.pend_tok.empty()) return 0;
     const int E = (int)llm_.n_embd;
+    // prefix store (engine.hpp): a pass that starts at position 0 takes the rows the store covers from it, and may leave its own leading token run there afterwards
+    size_t first = 0;
+    std::vector<int> cap_ids;
+    if (pfx_max_ > 0 && cv.n_committed == 0) {
+        const int run = token_run(cv), m = prefix_match(cv);
+        pfx_.rows_last = 0;
+        if (m >= PREFIX_MIN_ROWS) {
+            prefix_copy_in(&cur_, 1, m);
+            cv.n_committed = m; first = (size_t)m;                        // rows below m are token rows: no embedding row is skipped
+        }
+        if (run >= PREFIX_MIN_ROWS && m < std::min(run, pfx_max_)) cap_ids.assign(cv.pend_tok.begin(), cv.pend_tok.begin() + std::min(run, pfx_max_));
+    }
     size_t er = 0;
-    for (size_t i = 0; i < cv.pend_tok.size(); i += (size_t)max_chunk_) {
+    for (size_t i = first; i < cv.pend_tok.size(); i += (size_t)max_chunk_) {
         const int n = (int)std::min((size_t)max_chunk_, cv.pend_tok.size() - i);
         size_t ne = 0; for (int k = 0; k < n; k++) ne += cv.pend_tok[i + k] < 0;
         const int rc = eval_chunk(cv.pend_tok.data() + i, n, cv.pend_embd.data() + er * E);
@@ -1242,6 +1256,91 @@ int Engine::flush() {
         if (rc) { cv.pend_tok.clear(); cv.pend_embd.clear(); cv.n_past = cv.n_committed; return rc; }
     }
     cv.pend_tok.clear(); cv.pend_embd.clear();
+    if (first) { pfx_.hits++; pfx_.rows_reused_total += (int)first; pfx_.rows_last = (int)first; }   // counted, like the capture, only after a pass that succeeded
+    if (!cap_ids.empty()) prefix_capture(cur_, cap_ids);
+    return 0;
+}
+
+int Engine::set_prefix_cache(int max_rows) {
+    if (max_rows < 0) { set_last_error("set_prefix_cache: max_rows < 0"); return 1; }
+    max_rows = std::min(max_rows, n_ctx_);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    prefix_empty(); pfx_ = PrefixInfo{};
+    if (max_rows == pfx_max_) return 0;
+    prefix_free();
+    if (max_rows == 0) return 0;
+    const size_t bytes = layers_.size() * (size_t)max_rows * llm_.n_embd * sizeof(__half);
+    HIP_CHECK(hipMalloc((void **)&pfx_k_, bytes));
+    if (hipError_t e = hipMalloc((void **)&pfx_v_, bytes); e != hipSuccess) { HIP_IGNORE(hipFree(pfx_k_)); pfx_k_ = nullptr; HIP_CHECK(e); }
+    pfx_max_ = max_rows;
+    return 0;
+}
+void Engine::prefix_free() {
+    if (pfx_k_) HIP_IGNORE(hipFree(pfx_k_));
+    if (pfx_v_) HIP_IGNORE(hipFree(pfx_v_));
+    pfx_k_ = pfx_v_ = nullptr; pfx_max_ = 0; pfx_ids_.clear();
+}
+int Engine::prefix_match(const Conversation &cv) const {
+    if (pfx_max_ <= 0 || cv.n_committed != 0 || cv.pend_tok.empty()) return 0;
+    const int lim = std::min({token_run(cv), (int)pfx_ids_.size(), (int)cv.pend_tok.size() - 1});
+    int m = 0;
+    while (m < lim && cv.pend_tok[(size_t)m] == pfx_ids_[(size_t)m]) m++;
+    return m;
+}
+void Engine::prefix_copy_in(const int *slots, int n, int n_rows) {
+    const size_t seq = layers_.size() * (size_t)n_ctx_ * llm_.n_embd;
+    KvCopyDst d{};
+    for (int i = 0; i < n; i++) { d.k[i] = kc_ + (size_t)slots[i] * seq; d.v[i] = vc_ + (size_t)slots[i] * seq; }
+    launch_kv_copy(pfx_k_, pfx_v_, pfx_max_, d, n, n_ctx_, (int)layers_.size(), (int)llm_.n_embd, n_rows, stream_);
+    pfx_.hit_launches++;
+}
+void Engine::prefix_capture(int slot, const std::vector<int> &ids) {
+    const size_t seq = layers_.size() * (size_t)n_ctx_ * llm_.n_embd;
+    KvCopyDst d{};
+    d.k[0] = pfx_k_; d.v[0] = pfx_v_;
+    prefix_empty();                                                        // a launch that fails leaves the store empty, not half-written
+    launch_kv_copy(kc_ + (size_t)slot * seq, vc_ + (size_t)slot * seq, n_ctx_, d, 1, pfx_max_, (int)layers_.size(), (int)llm_.n_embd, (int)ids.size(), stream_);
+    pfx_ids_ = ids;
+    pfx_.captures++;
+}
+// The checks come before the flush, so a refused call evaluates nothing.  The copies run on stream_ behind the source's pass; a destination's captured decode step
+// replays at the new position (eval_chunk writes d_npast_ and re-evaluates the key-split choice), the batched step takes positions from the host's n_committed.
+int Engine::fork(int src, const int *dst, int n_dst, int n_rows) {
+    const int S = (int)conv_.size();
+    auto fail = [](const char *what) { set_last_error(std::string("fork_conversation: ") + what); return 1; };
+    if (src < 0 || src >= S) return fail("source conversation out of range");
+    if (!dst || n_dst < 1 || n_dst > S) return fail("need 1 <= n_dst <= the number of conversations");
+    bool seen[MAX_CONVERSATIONS] = {false};
+    for (int i = 0; i < n_dst; i++) {
+        if (dst[i] < 0 || dst[i] >= S) return fail("destination conversation out of range");
+        if (dst[i] == src) return fail("a destination equals the source");
+        if (seen[dst[i]]) return fail("duplicate destination");
+        seen[dst[i]] = true;
+    }
+    if (n_rows < -1 || n_rows > conv_[(size_t)src].n_past) return fail("need -1 <= n_rows <= n_past of the source");
+    if (weights_missing()) return fail(last_error().c_str());
+    const int keep = cur_;
+    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; } } restore{this, keep};
+    cur_ = src;
+    Conversation &sv = conv_[(size_t)src];
+    const bool whole = n_rows < 0;
+    if ((whole || n_rows > sv.n_committed) && flush()) return fail(("the source's queued rows could not be evaluated: " + last_error()).c_str());
+    const int rows = whole ? sv.n_committed : n_rows;
+    const size_t seq = layers_.size() * (size_t)n_ctx_ * llm_.n_embd, V = llm_.n_vocab;
+    KvCopyDst d{};
+    for (int i = 0; i < n_dst; i++) { d.k[i] = kc_ + (size_t)dst[i] * seq; d.v[i] = vc_ + (size_t)dst[i] * seq; }
+    launch_kv_copy(kc_ + (size_t)src * seq, vc_ + (size_t)src * seq, n_ctx_, d, n_dst, n_ctx_, (int)layers_.size(), (int)llm_.n_embd, rows, stream_);
+    for (int i = 0; i < n_dst; i++) {
+        Conversation &cv = conv_[(size_t)dst[i]];
+        cv.pend_tok.clear(); cv.pend_embd.clear();
+        cv.n_past = cv.n_committed = rows;
+        if (logits_host_slot_ == dst[i]) logits_host_slot_ = -1;
+        if (!whole) continue;
+        HIP_CHECK(hipMemcpyAsync(logits_ + (size_t)dst[i] * V, logits_ + (size_t)src * V, V * 4, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(d_argmax_ + dst[i], d_argmax_ + src, 4, hipMemcpyDeviceToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(d_feed_ + dst[i], d_feed_ + src, 4, hipMemcpyDeviceToDevice, stream_));
+    }
+    if (whole) HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));   // greedy sample_token reads this copy
     return 0;
 }
 
@@ -1434,6 +1533,7 @@ int Engine::set_conversations(int n) {
     release_buffers();
     conv_.assign((size_t)n, Conversation{});
     cur_ = 0;
+    prefix_empty();
     alloc_buffers();
     // the folded Q-Former constants live in the buffer arena alloc_buffers() has just re-taken (zeroed): evaluate them again, or every later encode
     // would run on all-zero layer-0 constants (round-5 advisor finding; tests/test_gpu_serve.py::test_encode_after_set_conversations_equals_fresh_context)
@@ -1529,7 +1629,9 @@ int Engine::prefill_batch(const int *slots, int n) {
     try {
         // oracle-order arithmetic (parity mode) and the parity trace exist for the single-conversation pass only: one flush per conversation, in slot order
         if (parity_ || trace_file_) {
-            for (int i = 0; i < n; i++) { cur_ = slots[i]; if (flush()) { drop_all(); return 1; } }
+            int reused = 0;                                                  // rows_last of the call = the sum over its conversations, as in the packed form
+            for (int i = 0; i < n; i++) { cur_ = slots[i]; pfx_.rows_last = 0; if (flush()) { drop_all(); return 1; } reused += pfx_.rows_last; }
+            if (pfx_max_ > 0) pfx_.rows_last = reused;
             return 0;
         }
         if (prefill_packed(slots, n)) { drop_all(); return 1; }
@@ -1538,10 +1640,30 @@ int Engine::prefill_batch(const int *slots, int n) {
 }
 int Engine::prefill_packed(const int *slots, int n) {
     const int E = (int)llm_.n_embd;
-    struct Src { int slot; size_t row, erow; };                              // next queued row / embedding row of a conversation
+    struct Src { int slot; size_t row, erow; int m; };                       // next queued row / embedding row of a conversation; rows taken from the prefix store
     std::vector<Src> src;
-    for (int i = 0; i < n; i++) if (!conv_[(size_t)slots[i]].pend_tok.empty()) src.push_back({slots[i], 0, 0});
+    for (int i = 0; i < n; i++) if (!conv_[(size_t)slots[i]].pend_tok.empty()) src.push_back({slots[i], 0, 0, 0});
     if (src.empty()) return 0;
+    // prefix store (engine.hpp): every conversation of the call that starts at position 0 and matches is served by ONE copy launch (n_rows = the longest match: rows
+    // above a shorter match are overwritten by the pass that follows on the stream); its segments then start at pos0 = m
+    std::vector<int> cap_ids; int cap_slot = -1, pfx_hits = 0, pfx_reused = 0;
+    if (pfx_max_ > 0) {
+        int hit[MAX_CONVERSATIONS], nh = 0, rows = 0, reused = 0; bool looked = false;
+        for (Src &c : src) {
+            const Conversation &cv = conv_[(size_t)c.slot];
+            if (cv.n_committed != 0) continue;
+            looked = true;
+            const int run = token_run(cv), m = prefix_match(cv);
+            if (m >= PREFIX_MIN_ROWS) { c.m = m; hit[nh++] = c.slot; rows = std::max(rows, m); reused += m; }
+            if (cap_slot < 0 && run >= PREFIX_MIN_ROWS && m < std::min(run, pfx_max_)) { cap_slot = c.slot; cap_ids.assign(cv.pend_tok.begin(), cv.pend_tok.begin() + std::min(run, pfx_max_)); }
+        }
+        if (nh) {
+            prefix_copy_in(hit, nh, rows);
+            for (Src &c : src) if (c.m) { conv_[(size_t)c.slot].n_committed = c.m; c.row = (size_t)c.m; }
+        }
+        if (looked) pfx_.rows_last = 0;
+        pfx_hits = nh; pfx_reused = reused;
+    }
     std::vector<int> tok;
     size_t k = 0;
     while (k < src.size()) {
@@ -1586,6 +1708,8 @@ int Engine::prefill_packed(const int *slots, int n) {
         for (int i = 0; i < sc.n_seg; i++) conv_[(size_t)sc.h_segs[4 * i]].n_committed += sc.h_segs[4 * i + 2];
     }
     for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.pend_tok.clear(); cv.pend_embd.clear(); }
+    if (pfx_hits) { pfx_.hits += pfx_hits; pfx_.rows_reused_total += pfx_reused; pfx_.rows_last = pfx_reused; }   // counted only after every chunk succeeded
+    if (cap_slot >= 0) prefix_capture(cap_slot, cap_ids);
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));   // greedy sample_token reads this copy
     return 0;
 }

@@ -109,6 +109,31 @@ public:
     const BatchPath &batch_path() const { return batch_path_; }
     static constexpr int MAX_CONVERSATIONS = 64;
 
+    // ---- reuse of cached rows.  The K / V rows of a causal model depend only on the rows before them, so a prefix evaluated once can be COPIED into another
+    // conversation instead of being evaluated again (launch_kv_copy: one launch for every layer, keys and values, every destination).  Exact in parity mode; in
+    // fast mode the rows after the prefix run at a different N (the K split of the prompt mat-muls depends on N): inside the bound the batched prefill is tested to.
+    // fork: conversation src -> n_dst other conversations.  n_rows = -1: the whole state -- the source's queue is evaluated first, then its n_committed rows, its
+    // logits row, greedy id and feed token are copied: every destination can be sampled at once and equals the source.  0 <= n_rows <= n_past(src): that prefix
+    // only (the queue is evaluated first when it reaches into it); the destinations end at n_past = n_committed = n_rows with no current logits, like after
+    // reset(): the caller adds rows before sampling.  A destination's queue is dropped, its captured graph kept (positions are read from d_npast_).  0, or 1 with
+    // last_error "fork_conversation: ..." and everything untouched (src / a destination out of range, duplicates, a destination equal to src, n_dst < 1,
+    // n_rows < -1 or > n_past(src)).
+    int fork(int src, const int *dst, int n_dst, int n_rows);
+    // prefix store (off by default): ONE stored prefix -- the token ids and K / V rows [layer][max_rows][E] of the leading token run of a pass that started at
+    // position 0.  Lookup (flush / prefill_batch, a conversation at n_committed == 0): m = the common prefix of its queue's leading token run with the stored ids,
+    // capped at queue length - 1 (one row is always evaluated, so that logits exist); m >= PREFIX_MIN_ROWS: the m rows are copied from the store and the pass starts
+    // at row m (a batched call serves all its hits with one launch).  Capture (after a successful pass from position 0, at most one per call, the first qualifying
+    // conversation in slot-list order): a leading run of >= PREFIX_MIN_ROWS token rows that the store did not cover (m < min(run, max_rows)) overwrites the store
+    // with its first min(run, max_rows) rows.  So a constant system prompt + "Human: <Img>" (the run ends at the image rows) is captured once and never rewritten,
+    // while a text-only chat, whose run is its whole queue and is therefore never covered, re-captures its own run every time (one cheap copy).
+    // set_prefix_cache: 0 = off, the store is freed; > 0 (clamped to n_ctx): (re)allocated when the size changes, emptied, counters zeroed.  set_conversations
+    // and a set_parity that changes the mode empty it (parity-mode rows must come from parity-mode passes).
+    static constexpr int PREFIX_MIN_ROWS = 8;          // policy: a bare BOS / a few common words are not worth a launch
+    int set_prefix_cache(int max_rows);
+    // hit_launches: k_kv_copy launches made by lookups (a batched call with 4 hits adds 1); rows_last: rows the last pass that consulted the store took from it
+    struct PrefixInfo { int max_rows = 0, stored_rows = 0, hits = 0, rows_reused_total = 0, captures = 0, rows_last = 0, hit_launches = 0; };
+    PrefixInfo prefix_info() const { PrefixInfo p = pfx_; p.max_rows = pfx_max_; p.stored_rows = (int)pfx_ids_.size(); return p; }
+
     // ---- measurement hooks (bench / tests)
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
     int decode_loop(int steps, int *tokens_out, float *ms_total);
@@ -179,6 +204,14 @@ private:
     std::vector<Conversation> conv_ = std::vector<Conversation>(1);
     int cur_ = 0;
     int shift_keep_ = -1;                  // set_context_shift
+    // prefix store: its own allocations (set_conversations re-takes buf_arena_, the store is only emptied then); pfx_ids_.size() = stored rows
+    __half *pfx_k_ = nullptr, *pfx_v_ = nullptr; int pfx_max_ = 0; std::vector<int> pfx_ids_; PrefixInfo pfx_;
+    void prefix_empty() { pfx_ids_.clear(); }
+    void prefix_free();
+    static int token_run(const Conversation &cv) { int r = 0; while (r < (int)cv.pend_tok.size() && cv.pend_tok[(size_t)r] >= 0) r++; return r; }
+    int prefix_match(const Conversation &cv) const;        // m of the lookup (0 when the store is off or the conversation is not at position 0)
+    void prefix_copy_in(const int *slots, int n, int n_rows);   // store -> the listed conversations' caches, one launch
+    void prefix_capture(int slot, const std::vector<int> &ids);   // that conversation's rows [0, ids.size()) -> store
     int make_room(int n);                  // the automatic shift for n more rows of the selected conversation: 0 = room made (or already there), 1 = not
     bool defer_ = true; int max_chunk_ = 512;
     void release_buffers();

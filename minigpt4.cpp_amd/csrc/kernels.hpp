@@ -130,6 +130,13 @@ void rope_tables(int n_ctx, int hd, std::vector<float> &cos_out, std::vector<flo
 // Launches nothing when no row moves.
 void launch_kv_shift(__half *kc_slot, __half *vc_slot, int n_layer, int n_ctx, int E, int hd, int n_keep, int n_discard, int n_rows, const float *cos_tab,
                      const float *sin_tab, hipStream_t s);
+// prefix copy (Engine::fork, the prefix store): rows [0, n_rows) of every layer, keys and values, from ONE source (src_k / src_v = [n_layer][src_rows][E] fp16) to n_dst
+// destinations (dst.k[d] / dst.v[d] = [n_layer][dst_rows][E]), bit for bit, in one launch; each 16-byte piece is loaded once and stored n_dst times.  Rows from n_rows on
+// are not touched.  n_rows == 0 launches nothing.  Throws HipError: E % 8, n_rows above src_rows or dst_rows, n_dst outside 1..KV_COPY_MAX_DST, a destination region
+// that overlaps the source's.
+constexpr int KV_COPY_MAX_DST = 64;                    // = Engine::MAX_CONVERSATIONS
+struct KvCopyDst { __half *k[KV_COPY_MAX_DST]; __half *v[KV_COPY_MAX_DST]; };   // passed by value to the kernel (llm_kernels.hip: why)
+void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, const KvCopyDst &dst, int n_dst, int dst_rows, int n_layer, int E, int n_rows, hipStream_t s);
 // out[t][h*hd+i] = softmax(K q / sqrt(hd)) V over keys 0..*n_past+t.  caches: [n_ctx][E] fp16.
 // fused (decode, N == 1): q,k,v are the raw projections; RoPE of q/k and the KV append happen inside the kernel.
 // !fused: launch_rope_kv must have run (q rotated in place, caches appended).

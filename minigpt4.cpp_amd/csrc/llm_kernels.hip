@@ -1665,6 +1665,75 @@ void launch_kv_shift(__half *kc_slot, __half *vc_slot, int n_layer, int n_ctx, i
 }
 
 // =====================================================================================================================
+// Prefix copy (Engine::fork, the prefix store): rows [0, n_rows) of every layer, keys and values, from ONE region with layer stride src_rows * E (a
+// conversation's caches or the compact store) to n_dst regions with layer stride dst_rows * E.  Per layer and tensor the rows of a prefix are one
+// contiguous run of n_rows * E halves, so the copy is 2 * n_layer runs cut into 16-byte pieces: lane t of workgroup b takes the pieces
+// (b * KV_COPY_PIECES + j) * KV_COPY_THREADS + t, j < KV_COPY_PIECES -- every load of a wave is one coalesced KiB, all KV_COPY_PIECES loads are issued before
+// the first store, and each piece is stored to every destination from the register it was loaded into (one-to-many: the source is read once).  The grid
+// follows the byte count (45 rows of a 13B layer are 460 KB per tensor: a grid over layers alone would leave most of the device idle).  Plain stores: the
+// written lines stay in the storing XCD's L2, and the next prompt pass reads exactly these rows.
+// Destinations travel BY VALUE in the kernel arguments (KvCopyDst, 2 x 64 pointers = 1 KiB of the 4 KiB segment) rather than in a device table like
+// d_seg_: a table would need a host-to-device copy and a wait for the previous use of its pinned staging before every launch, which costs more than the
+// copy of a 45-row prefix itself; the argument segment is written by the launch.  The lanes index it uniformly (scalar loads from the constant segment).
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 36 VGPRs, 30 SGPRs, no scratch, no LDS, occupancy 8 waves per SIMD.  The pieces are four named values,
+// not an array: as an array the compiler kept them in LDS (16 KB per workgroup) and the loads were no longer in flight together.
+// =====================================================================================================================
+constexpr int KV_COPY_PIECES = 4, KV_COPY_THREADS = 256;
+struct KvPiece { uint4 data; size_t off; int sel; };                       // off: destination offset in halves; sel: 0 = past the end (not stored), 1 = key, 2 = value
+__device__ __forceinline__ KvPiece kv_piece_load(const __half *src_k, const __half *src_v, unsigned i0, unsigned total, unsigned per, unsigned n_layer, unsigned src_rows,
+                                                 unsigned dst_rows, unsigned E) {
+    const unsigned i = i0 < total ? i0 : 0u;                               // past the end: piece 0 is loaded (in bounds, total >= 1) and not stored
+    const unsigned run = i / per, within = i - run * per;                  // run = tensor * n_layer + layer
+    const bool is_v = run >= n_layer;
+    const unsigned layer = is_v ? run - n_layer : run;
+    KvPiece p;
+    p.data = *reinterpret_cast<const uint4 *>((is_v ? src_v : src_k) + (size_t)layer * src_rows * E + (size_t)within * 8);
+    p.off = (size_t)layer * dst_rows * E + (size_t)within * 8;
+    p.sel = i0 < total ? (is_v ? 2 : 1) : 0;
+    return p;
+}
+__device__ __forceinline__ void kv_piece_store(const KvPiece &p, __half *dk, __half *dv) {
+    if (p.sel) *reinterpret_cast<uint4 *>((p.sel == 2 ? dv : dk) + p.off) = p.data;
+}
+// the source pointers are NOT __restrict__ on purpose: the loads then cannot be moved below (or repeated behind) the stores, so the four of a lane stay in flight together
+__global__ __launch_bounds__(KV_COPY_THREADS) void k_kv_copy(const __half *src_k, const __half *src_v, unsigned src_rows, const KvCopyDst dst, int n_dst, unsigned dst_rows,
+                                                           unsigned n_layer, unsigned E, unsigned n_rows) {
+    static_assert(KV_COPY_PIECES == 4, "the four pieces are named");
+    const unsigned per = n_rows * (E / 8);                                 // 16-byte pieces of one layer's run
+    const unsigned total = 2u * n_layer * per;                             // < 2^31 (launch_kv_copy)
+    const unsigned first = blockIdx.x * (KV_COPY_PIECES * KV_COPY_THREADS) + threadIdx.x;
+    const KvPiece p0 = kv_piece_load(src_k, src_v, first, total, per, n_layer, src_rows, dst_rows, E);
+    const KvPiece p1 = kv_piece_load(src_k, src_v, first + KV_COPY_THREADS, total, per, n_layer, src_rows, dst_rows, E);
+    const KvPiece p2 = kv_piece_load(src_k, src_v, first + 2 * KV_COPY_THREADS, total, per, n_layer, src_rows, dst_rows, E);
+    const KvPiece p3 = kv_piece_load(src_k, src_v, first + 3 * KV_COPY_THREADS, total, per, n_layer, src_rows, dst_rows, E);
+    for (int d = 0; d < n_dst; d++) {
+        __half *const dk = dst.k[d], *const dv = dst.v[d];
+        kv_piece_store(p0, dk, dv); kv_piece_store(p1, dk, dv); kv_piece_store(p2, dk, dv); kv_piece_store(p3, dk, dv);
+    }
+}
+void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, const KvCopyDst &dst, int n_dst, int dst_rows, int n_layer, int E, int n_rows, hipStream_t s) {
+    auto bad = [](const char *what) { throw HipError{hipErrorInvalidValue, what, __FILE__, __LINE__}; };
+    if (!src_k || !src_v || n_dst < 1 || n_dst > KV_COPY_MAX_DST || n_layer < 1 || E < 8 || E % 8 || src_rows < 1 || dst_rows < 1 || n_rows < 0) bad("launch_kv_copy: bad shape");
+    if (n_rows > src_rows || n_rows > dst_rows) bad("launch_kv_copy: n_rows exceeds a region's row count");
+    auto aligned = [](const __half *p) { return (uintptr_t)p % 16 == 0; };   // the 16-byte accesses (with E % 8 every layer and row offset keeps the alignment)
+    if (!aligned(src_k) || !aligned(src_v)) bad("launch_kv_copy: a region is not 16-byte aligned");
+    const size_t src_n = (size_t)n_layer * src_rows * E, dst_n = (size_t)n_layer * dst_rows * E;
+    auto overlap = [](const __half *a, size_t na, const __half *b, size_t nb) { const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b; return x < y + 2 * nb && y < x + 2 * na; };
+    for (int d = 0; d < n_dst; d++) {
+        if (!dst.k[d] || !dst.v[d]) bad("launch_kv_copy: bad shape");
+        if (!aligned(dst.k[d]) || !aligned(dst.v[d])) bad("launch_kv_copy: a region is not 16-byte aligned");
+        for (const __half *p : {dst.k[d], dst.v[d]}) if (overlap(p, dst_n, src_k, src_n) || overlap(p, dst_n, src_v, src_n)) bad("launch_kv_copy: a destination overlaps the source");
+    }
+    if (n_rows == 0) return;
+    const unsigned long long total = 2ull * n_layer * n_rows * (E / 8);
+    if (total >= (1ull << 31)) bad("launch_kv_copy: bad shape");
+    note_kernel("k_kv_copy");
+    const unsigned per_block = KV_COPY_PIECES * KV_COPY_THREADS;
+    hipLaunchKernelGGL(k_kv_copy, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(KV_COPY_THREADS), 0, s, src_k, src_v, (unsigned)src_rows, dst, n_dst, (unsigned)dst_rows,
+                       (unsigned)n_layer, (unsigned)E, (unsigned)n_rows);
+}
+
+// =====================================================================================================================
 // causal attention over the fp16 KV cache.  One 512-thread workgroup per (head, query token).
 //   FUSED (decode, N = 1): RoPE of q/k and the KV append happen in the prologue; the new key/value are also kept in LDS.
 //   scores : one lane per key, the whole head row in registers (HD/8 independent 16-byte loads), sequential fp32 fma over the

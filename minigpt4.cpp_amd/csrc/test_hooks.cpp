@@ -623,6 +623,37 @@ int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, i
         return 0;
     });
 }
+// The prefix copy's kernel (launch_kv_copy) on host caches [n_slot][n_layer][rows][n_embd] fp16: slot src (or a compact copy of its first src_rows rows) -> the slots dst.
+// k == v == NULL: timing only, on device buffers of that shape that never cross the host (the engine's real strides, n_ctx = 2048 rows per layer, are gigabytes per tensor)
+int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int src, const int32_t *dst, int n_dst, int n_rows, int src_rows, uint16_t *k, uint16_t *v, float *ms) {
+    if (!k != !v || !dst || n_slot < 1 || n_layer < 1 || rows < 1 || n_embd < 1 || src < 0 || src >= n_slot || n_dst < 1 || n_dst > KV_COPY_MAX_DST || src_rows < 0 || src_rows > rows) return 1;
+    for (int i = 0; i < n_dst; i++) if (dst[i] < 0 || dst[i] >= n_slot || dst[i] == src) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_embd, slot_n = (size_t)n_layer * rows * E, n = (size_t)n_slot * slot_n;
+        DevBuf dk(n * 2), dv(n * 2), ck(src_rows ? (size_t)n_layer * src_rows * E * 2 : 2), cv(src_rows ? (size_t)n_layer * src_rows * E * 2 : 2);
+        if (k) { HIP_CHECK(hipMemcpy(dk.p, k, n * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, n * 2, hipMemcpyHostToDevice)); }
+        else { HIP_CHECK(hipMemset(dk.p, 0x11, n * 2)); HIP_CHECK(hipMemset(dv.p, 0x22, n * 2)); }   // every page touched before the timed launch
+        const __half *sk = dk.as<__half>() + (size_t)src * slot_n, *sv = dv.as<__half>() + (size_t)src * slot_n;
+        if (src_rows) {   // [layer][rows][E] -> [layer][src_rows][E]
+            HIP_CHECK(hipMemcpy2D(ck.p, (size_t)src_rows * E * 2, sk, (size_t)rows * E * 2, (size_t)src_rows * E * 2, (size_t)n_layer, hipMemcpyDeviceToDevice));
+            HIP_CHECK(hipMemcpy2D(cv.p, (size_t)src_rows * E * 2, sv, (size_t)rows * E * 2, (size_t)src_rows * E * 2, (size_t)n_layer, hipMemcpyDeviceToDevice));
+            sk = ck.as<__half>(); sv = cv.as<__half>();
+        }
+        KvCopyDst d{};
+        for (int i = 0; i < n_dst; i++) { d.k[i] = dk.as<__half>() + (size_t)dst[i] * slot_n; d.v[i] = dv.as<__half>() + (size_t)dst[i] * slot_n; }
+        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+        HIP_CHECK(hipEventRecord(a, nullptr));
+        launch_kv_copy(sk, sv, src_rows ? src_rows : rows, d, n_dst, rows, n_layer, n_embd, n_rows, nullptr);
+        HIP_CHECK(hipEventRecord(b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
+        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        if (ms) *ms = t;
+        if (k) { HIP_CHECK(hipMemcpy(k, dk.p, n * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, n * 2, hipMemcpyDeviceToHost)); }
+        return 0;
+    });
+}
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
 static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {

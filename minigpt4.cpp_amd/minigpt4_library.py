@@ -202,6 +202,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_batch_path.argtypes = [VOID_PTR, INT_PTR]
         L.minigpt4_amd_shift_context.argtypes = [VOID_PTR, I32, I32]
         L.minigpt4_amd_set_context_shift.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_fork_conversation.argtypes = [VOID_PTR, I32, INT_PTR, I32, I32]
+        L.minigpt4_amd_set_prefix_cache.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_prefix_cache_info.argtypes = [VOID_PTR, INT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -224,6 +227,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_activation.argtypes = [I32, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_test_attn_f32.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, F32, F32, I32, I32, VOID_PTR, FLOAT_PTR, VOID_PTR]
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_kv_copy.argtypes = [I32, I32, I32, I32, I32, INT_PTR, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
@@ -405,6 +409,49 @@ class MiniGPT4SharedLibrary:
         """Automatic context shift of this context when an add would overflow, keeping the first n_keep rows; n_keep < 0 = off (the default)."""
         if self.library.minigpt4_amd_set_context_shift(ctx.ptr, int(n_keep)):
             raise RuntimeError("set_context_shift failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+
+    PREFIX_INFO_FIELDS = ("max_rows", "stored_rows", "hits", "rows_reused_total", "captures", "rows_reused_by_last_pass", "hit_launches")
+
+    def amd_fork_conversation(self, ctx, src: int, dsts: Sequence[int], n_rows: int = -1):
+        """Copy conversation `src` into the conversations `dsts` (one launch): n_rows = -1 the whole state (rows, logits, greedy token: sample at once), otherwise the
+        first n_rows rows only (no logits: add rows before sampling).  include/minigpt4_amd.h"""
+        d = np.ascontiguousarray(dsts, np.int32)
+        if self.library.minigpt4_amd_fork_conversation(ctx.ptr, int(src), d.ctypes.data_as(INT_PTR), len(d), int(n_rows)):
+            raise RuntimeError("fork_conversation failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+
+    def amd_set_prefix_cache(self, ctx, max_rows: int):
+        """Prefix cache of this context: 0 = off (the default); > 0 = one stored prefix of up to max_rows rows, emptied (and its counters zeroed) by every call."""
+        if self.library.minigpt4_amd_set_prefix_cache(ctx.ptr, int(max_rows)):
+            raise RuntimeError("set_prefix_cache failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+
+    def amd_prefix_cache_info(self, ctx) -> dict:
+        out = (ctypes.c_int32 * len(self.PREFIX_INFO_FIELDS))()
+        if self.library.minigpt4_amd_prefix_cache_info(ctx.ptr, out):
+            raise RuntimeError("prefix_cache_info failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return dict(zip(self.PREFIX_INFO_FIELDS, (int(x) for x in out)))
+
+    def amd_test_kv_copy(self, k: np.ndarray, v: np.ndarray, src: int, dsts: Sequence[int], n_rows: int, src_rows: int = 0):
+        """launch_kv_copy on fp16 caches [n_slot][n_layer][rows][n_embd]: rows [0, n_rows) of slot `src` (src_rows > 0: of a compact [n_layer][src_rows][n_embd] copy of its
+        first rows) to the slots `dsts`; returns (k, v, ms) -- changed copies and the launch's hipEvent time."""
+        k = np.ascontiguousarray(k, np.float16).copy()
+        v = np.ascontiguousarray(v, np.float16).copy()
+        assert k.ndim == 4 and k.shape == v.shape
+        d = np.ascontiguousarray(dsts, np.int32)
+        ms = ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_kv_copy(k.shape[0], k.shape[1], k.shape[2], k.shape[3], int(src), d.ctypes.data_as(INT_PTR), len(d), int(n_rows), int(src_rows),
+                                                    k.ctypes.data_as(VOID_PTR), v.ctypes.data_as(VOID_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_copy rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return k, v, float(ms.value)
+
+    def amd_test_kv_copy_ms(self, n_slot: int, n_layer: int, rows: int, n_embd: int, src: int, dsts: Sequence[int], n_rows: int, src_rows: int = 0) -> float:
+        """The same launch on device-only caches of the given shape (nothing crosses the host): its hipEvent time in ms."""
+        d = np.ascontiguousarray(dsts, np.int32)
+        ms = ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_kv_copy(n_slot, n_layer, rows, n_embd, int(src), d.ctypes.data_as(INT_PTR), len(d), int(n_rows), int(src_rows), None, None, ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_copy rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return float(ms.value)
 
     def amd_test_kv_shift(self, k: np.ndarray, v: np.ndarray, n_head: int, n_rows: int, n_keep: int, n_discard: int):
         """launch_kv_shift on fp16 caches [n_layer][n_ctx][n_embd]; returns (k, v, ms) -- shifted copies and the launch's hipEvent time."""

@@ -37,9 +37,11 @@ def plan_waves(n_requests: int, conversations: int) -> List[List[int]]:
 
 class ReplicaServer:
     def __init__(self, vision_path: str, llm_path: str, conversations: int = 4, n_ctx: int = 2048, n_batch: int = 512, seed: int = 1337,
-                 library: Optional[ML.MiniGPT4SharedLibrary] = None, verbosity: int = 0, rank: int = 0, world: int = 1, device=None):
+                 library: Optional[ML.MiniGPT4SharedLibrary] = None, verbosity: int = 0, rank: int = 0, world: int = 1, device=None, prefix_cache: int = 0):
         """world > 1 (inside an initialised `torch.distributed` job): the replica is loaded through `dist.load_replica` -- rank 0 reads the files, every other
-        rank loads headers only and receives both weight arenas by broadcast, so the weights cross the file system once per node."""
+        rank loads headers only and receives both weight arenas by broadcast, so the weights cross the file system once per node.
+        prefix_cache > 0: the engine's prefix cache with that many rows (`minigpt4_amd_set_prefix_cache`): the constant head of every request (system prompt +
+        "Human: <Img>") is evaluated by the first request and copied by the others, in the per-conversation and in the batched prefill alike."""
         self.lib = library or ML.load_library()
         self.load_stats = None
         if world > 1:
@@ -48,6 +50,8 @@ class ReplicaServer:
             self.ctx = self.lib.minigpt4_model_load(vision_path, llm_path, verbosity=verbosity, seed=seed, n_ctx=n_ctx, n_batch=n_batch)
         self.conversations = conversations
         self.lib.amd_set_conversations(self.ctx, conversations)
+        if prefix_cache:
+            self.lib.amd_set_prefix_cache(self.ctx, prefix_cache)
 
     def close(self):
         if self.ctx is not None:
@@ -124,7 +128,7 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     mine = D.shard_requests(len(requests), rank, world)
     server = ReplicaServer(vision_path, llm_path, conversations=conversations, rank=rank, world=world, device=kw.get("device"),
-                           **{k: v for k, v in kw.items() if k in ("n_ctx", "n_batch", "seed", "library", "verbosity")})
+                           **{k: v for k, v in kw.items() if k in ("n_ctx", "n_batch", "seed", "library", "verbosity", "prefix_cache")})
     try:
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos")})
     finally:

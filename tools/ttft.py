@@ -50,3 +50,16 @@ for turn in range(3):
     lib.minigpt4_free_embedding(emb)
     ttft = T["encode_image"] + T["system_prompt"] + T["begin_chat_image"] + T["end_chat_image #1"]     # the prompt rows are queued by the calls and evaluated in ONE pass when the first token is asked for
     print(f"turn {turn}: " + "  ".join(f"{k} {v:.2f}" for k, v in T.items()) + f"   | image -> first token {ttft:.2f} ms")
+# the same from a preprocessed array with the prefix cache on (minigpt4_amd_set_prefix_cache): turn 0 captures the system prompt + "Human: <Img>" rows, the later turns copy them
+lib.amd_set_prefix_cache(ctx, 256)
+for turn in range(3):
+    lib.minigpt4_reset_chat(ctx)
+    lib.library.minigpt4_amd_sync(ctx.ptr)
+    t = time.perf_counter()
+    emb = lib.minigpt4_encode_image(ctx, img)
+    lib.minigpt4_system_prompt(ctx)
+    lib.minigpt4_begin_chat_image(ctx, emb, "what is the text in the picture?")
+    lib.minigpt4_end_chat_image(ctx, temp=0.0)
+    ttft = 1e3 * (time.perf_counter() - t)
+    lib.minigpt4_free_embedding(emb)
+    print(f"prefix cache on, turn {turn}: image -> first token {ttft:.2f} ms   (rows reused by the prompt pass: {lib.amd_prefix_cache_info(ctx)['rows_reused_by_last_pass']})")
