@@ -119,6 +119,32 @@ MINIGPT4_API int minigpt4_amd_fork_conversation(struct MiniGPT4Context *ctx, int
 MINIGPT4_API int minigpt4_amd_set_prefix_cache(struct MiniGPT4Context *ctx, int max_rows);
 MINIGPT4_API int minigpt4_amd_prefix_cache_info(struct MiniGPT4Context *ctx, int32_t out[7]);
 
+/* ---- scoring: log-probabilities of GIVEN tokens (llama.cpp's logits_all / perplexity) ---------------------------------------------------------
+ * The prompt pass keeps one logits row per conversation; these two calls also report what the model thought of every row before it, from the same pass (the output
+ * matrix runs on the scored rows in tiles of 64, one more kernel turns each row into numbers) instead of one weight pass per token.
+ * minigpt4_amd_score_tokens, on the selected conversation: rows already queued are evaluated first, as their own pass (what minigpt4_amd_get_logits does); then `tokens`
+ * are appended and evaluated in chunks of n_batch.  Afterwards position, last logits, greedy token and feed token equal BIT FOR BIT what minigpt4_amd_eval_tokens +
+ * minigpt4_amd_get_logits of the same tokens leave: the conversation can be sampled and continued.  Outputs are indexed by the distribution a token is drawn from: entry
+ * i describes the distribution that predicts tokens[i] -- for i >= 1 the logits of row i - 1 of this call, for i == 0 the conversation's logits from before the call.
+ * logprob_out[i] = log softmax(logits_i)[tokens[i]] (natural logarithm), greedy_out[i] = the argmax of that distribution (first maximum), greedy_logprob_out[i] = its
+ * log-probability, logits_out[i] = the row itself.  The logits after tokens[n - 1] are not in logits_out: they are the conversation's current logits
+ * (minigpt4_amd_get_logits).  A conversation without current logits (nothing evaluated yet, after minigpt4_reset_chat, after a partial fork) gets logprob 0, greedy -1,
+ * greedy_logprob 0 and a zero logits row in entry 0 (llama.cpp's perplexity skips the first token too).  greedy_out, greedy_logprob_out and logits_out may be NULL.
+ * Perplexity of a sequence = exp(-mean(logprob_out[1 .. n - 1])).  0, or 1 with the text "score_tokens: ..." in minigpt4_amd_last_error and nothing of `tokens` added (no
+ * context, tokens or logprob_out NULL, n < 1, an id outside [0, n_vocab), rows that do not fit n_ctx under minigpt4_amd_eval_tokens' rule, automatic shift included).
+ * Score passes neither consult nor fill the prefix cache.
+ * minigpt4_amd_score_batch: the same for n_slots DISTINCT conversations -- tokens, counts (each >= 1) and the outputs concatenated in slot-list order.  Queued rows
+ * are evaluated first (as minigpt4_amd_prefill_batch(slots) does), then all conversations' tokens run packed, in as few passes as minigpt4_amd_prefill_batch takes; every
+ * conversation ends bit-identical to minigpt4_amd_prefill_batch of the same tokens.  After minigpt4_amd_fork_conversation this scores k candidate answers to one image
+ * and question for one image turn (multiple-choice evaluation: sum each candidate's entries).  Parity mode: one minigpt4_amd_score_tokens per conversation, in slot order.
+ * 0, or 1 with "score_batch: ..." and every conversation untouched (a bad slot list, a count < 1, a bad id, an overflow: all checked before anything runs).  A pass or an
+ * automatic shift that fails on the device afterwards returns 1 with the same prefix; what the call had evaluated or shifted by then stays, as after a failed
+ * minigpt4_amd_prefill_batch. */
+MINIGPT4_API int minigpt4_amd_score_tokens(struct MiniGPT4Context *ctx, const int32_t *tokens, int n, float *logprob_out, int32_t *greedy_out, float *greedy_logprob_out,
+                                           float *logits_out);
+MINIGPT4_API int minigpt4_amd_score_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n_slots, const int32_t *tokens, const int32_t *counts, float *logprob_out,
+                                          int32_t *greedy_out, float *greedy_logprob_out);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

@@ -78,6 +78,11 @@ MINIGPT4_API int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, 
  * (a slot out of range, src among dst, only one of k / v NULL), 3 = the launcher refused the shape (text in minigpt4_amd_last_error) */
 MINIGPT4_API int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int src, const int32_t *dst, int n_dst, int n_rows, int src_rows, uint16_t *k, uint16_t *v,
                                            float *ms);
+/* the scoring kernel (launch_logprob_rows) on host logits [rows][ld] fp32 (ld >= n_vocab; only the first n_vocab floats of a row are read): per row the log-softmax of
+ * targets[r] (-1: none, logprob 0), the first argmax and its log-softmax.  One launch; ms (may be NULL): its hipEvent time.  1 = bad arguments, before any device is
+ * touched (a NULL pointer, rows < 1, n_vocab < 1, ld < n_vocab, a target >= n_vocab or < -1) */
+MINIGPT4_API int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, int ld, const int32_t *targets, float *logprob_out, int32_t *greedy_out,
+                                                float *greedy_logprob_out, float *ms_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

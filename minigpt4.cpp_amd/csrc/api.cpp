@@ -297,6 +297,16 @@ int minigpt4_amd_prefix_cache_info(struct MiniGPT4Context *ctx, int32_t out[7]) 
     out[0] = p.max_rows; out[1] = p.stored_rows; out[2] = p.hits; out[3] = p.rows_reused_total; out[4] = p.captures; out[5] = p.rows_last; out[6] = p.hit_launches;
     return 0;
 }
+// ---- scoring: log-probabilities of given tokens ------------------------------------------------------------------------------------------
+int minigpt4_amd_score_tokens(struct MiniGPT4Context *ctx, const int32_t *tokens, int n, float *logprob_out, int32_t *greedy_out, float *greedy_logprob_out, float *logits_out) {
+    if (!ctx) { set_last_error("score_tokens: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->score_tokens(tokens, n, logprob_out, greedy_out, greedy_logprob_out, logits_out); });
+}
+int minigpt4_amd_score_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n_slots, const int32_t *tokens, const int32_t *counts, float *logprob_out, int32_t *greedy_out,
+                             float *greedy_logprob_out) {
+    if (!ctx) { set_last_error("score_batch: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->score_batch(slots, n_slots, tokens, counts, logprob_out, greedy_out, greedy_logprob_out); });
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

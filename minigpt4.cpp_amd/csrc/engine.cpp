@@ -93,6 +93,7 @@ Engine::~Engine() {
     for (auto &e : site_events_) { HIP_IGNORE(hipEventDestroy(e.a)); HIP_IGNORE(hipEventDestroy(e.b)); }
     if (stage_) HIP_IGNORE(hipFree(stage_));
     prefix_free();
+    score_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -892,6 +893,7 @@ void Engine::forward_ref(int N, bool from_tokens, hipStream_t s, bool feed) {
         if (!fused_set({&L.w2}, {x_}, x_, 0, nullptr, nullptr)) ref_set({&L.w2}, {x_}, x_);
         tr("x_ffn", (int)il, x_, (size_t)N * E);
     }
+    if (score_) score_rows(s);
     if (!(N == 1 && fused_set({&output_}, {logits}, nullptr, 1, x_, norm_))) {
         launch_rms_quant(x_ + (size_t)(N - 1) * E, norm_, 1, E, act_, act_mask_for(output_.type), s, true);
         const QWeight *Wo[1] = {&output_}; float *Yo[1] = {logits};
@@ -999,6 +1001,7 @@ void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
         mul_mat(L.w2, N, x_, E, x_, s, paired ? &p_h : &p_silu, fz(3), "w2", !dec);
     }
     flush_pending(s);
+    if (score_) score_rows(s);
     if (sg) {   // the last row of every conversation that ends in this chunk: one output pass over those rows, then each slot's logits / greedy id / position
         if (sg->n_end > 0) {
             launch_gather_rows(x_, sg->last, sg->n_end, E, att_, s);
@@ -1196,7 +1199,7 @@ int Engine::eval_chunk(const int *row_tok, int N, const float *embd) {
         // hundred keys on).  The choice is part of the captured graph, so a conversation that crosses the threshold gets its step re-captured (once).
         const bool split = attn_split_t_ > 0 && cv.n_committed + 1 > attn_split_t_;
         attn_split_now_ = split;
-        if (use_graph_ && !prof_on_ && !trace_file_) {
+        if (use_graph_ && !prof_on_ && !trace_file_ && !score_) {   // a scored row runs eagerly: the same launches as the captured step + the scoring ones
             if (cv.graph && cv.graph_split != split) { HIP_IGNORE(hipGraphExecDestroy(cv.graph)); cv.graph = nullptr; }
             cv.graph_split = split;
             if (!cv.graph) {
@@ -1223,7 +1226,7 @@ int Engine::eval_chunk(const int *row_tok, int N, const float *embd) {
         HIP_CHECK(hipStreamSynchronize(stream_));   // the (pageable) staging vectors may be reused right after this call
         forward(N, true, stream_);                   // k_get_rows skips rows whose id is negative
     }
-    cv.n_committed += N;
+    cv.n_committed += N; cv.has_logits = true;
     return 0;
 }
 
@@ -1334,6 +1337,7 @@ int Engine::fork(int src, const int *dst, int n_dst, int n_rows) {
         Conversation &cv = conv_[(size_t)dst[i]];
         cv.pend_tok.clear(); cv.pend_embd.clear();
         cv.n_past = cv.n_committed = rows;
+        cv.has_logits = whole && sv.has_logits;
         if (logits_host_slot_ == dst[i]) logits_host_slot_ = -1;
         if (!whole) continue;
         HIP_CHECK(hipMemcpyAsync(logits_ + (size_t)dst[i] * V, logits_ + (size_t)src * V, V * 4, hipMemcpyDeviceToDevice, stream_));
@@ -1386,7 +1390,7 @@ int Engine::shift_context(int n_keep, int n_discard) {
 }
 int Engine::make_room(int n) {
     Conversation &cv = conv_[(size_t)cur_];
-    if (shift_keep_ < 0 || n > n_ctx_ - shift_keep_) return 1;
+    if (!shift_allows(n)) return 1;
     if (cv.n_past + n <= n_ctx_) return 0;
     if (flush()) return 1;
     const int need = cv.n_past + n - n_ctx_;
@@ -1592,7 +1596,7 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     for (int r = 0; r < B; r++) {
         const int sl = h_bstage_[MAX_CONVERSATIONS + r];
         Conversation &cv = conv_[(size_t)sl];
-        cv.n_past += 1; cv.n_committed += 1;
+        cv.n_past += 1; cv.n_committed += 1; cv.has_logits = true;
         if (logits_host_slot_ == sl) logits_host_slot_ = -1;
     }
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
@@ -1638,7 +1642,7 @@ int Engine::prefill_batch(const int *slots, int n) {
     } catch (...) { drop_all(); throw; }
     return 0;
 }
-int Engine::prefill_packed(const int *slots, int n) {
+int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
     const int E = (int)llm_.n_embd;
     struct Src { int slot; size_t row, erow; int m; };                       // next queued row / embedding row of a conversation; rows taken from the prefix store
     std::vector<Src> src;
@@ -1647,7 +1651,7 @@ int Engine::prefill_packed(const int *slots, int n) {
     // prefix store (engine.hpp): every conversation of the call that starts at position 0 and matches is served by ONE copy launch (n_rows = the longest match: rows
     // above a shorter match are overwritten by the pass that follows on the stream); its segments then start at pos0 = m
     std::vector<int> cap_ids; int cap_slot = -1, pfx_hits = 0, pfx_reused = 0;
-    if (pfx_max_ > 0) {
+    if (pfx_max_ > 0 && !so) {   // a score pass neither consults nor captures the store: a copied row has no logits
         int hit[MAX_CONVERSATIONS], nh = 0, rows = 0, reused = 0; bool looked = false;
         for (Src &c : src) {
             const Conversation &cv = conv_[(size_t)c.slot];
@@ -1664,7 +1668,7 @@ int Engine::prefill_packed(const int *slots, int n) {
         if (looked) pfx_.rows_last = 0;
         pfx_hits = nh; pfx_reused = reused;
     }
-    std::vector<int> tok;
+    std::vector<int> tok, tgt, dest, h_gr; std::vector<float> h_lp, h_glp;   // score pass: per packed row, the id it predicts (-1: none) and the output entry that takes its result
     size_t k = 0;
     while (k < src.size()) {
         HIP_CHECK(hipStreamSynchronize(stream_));                            // h_seg_ may still feed the previous chunk's copy
@@ -1672,7 +1676,7 @@ int Engine::prefill_packed(const int *slots, int n) {
         int *const hs = h_seg_, *const fin = hs + SEG_FIN, *const last = hs + SEG_LAST, *const rows = hs + SEG_ROWS;
         int *const t16 = rows + 2 * (size_t)max_rows_, *const t32 = t16 + 2 * ((size_t)max_rows_ + MAX_CONVERSATIONS);
         int N = 0;
-        tok.clear();
+        tok.clear(); tgt.clear(); dest.clear();
         while (k < src.size() && N < max_chunk_) {
             Src &c = src[k];
             Conversation &cv = conv_[(size_t)c.slot];
@@ -1682,6 +1686,11 @@ int Engine::prefill_packed(const int *slots, int n) {
             sc.key_rows += (double)(pos0 + m);
             sc.att.t_max = std::max(sc.att.t_max, pos0 + m);
             for (int r = 0; r < m; r++) { rows[2 * (N + r)] = c.slot; rows[2 * (N + r) + 1] = pos0 + r; tok.push_back(cv.pend_tok[c.row + r]); }
+            if (so) for (int r = 0; r < m; r++) {   // the queue holds exactly the call's tokens: row j predicts token j + 1, the conversation's last row nothing
+                const size_t nx = c.row + (size_t)r + 1;
+                const bool has = nx < cv.pend_tok.size();
+                tgt.push_back(has ? cv.pend_tok[nx] : -1); dest.push_back(has ? so->off[c.slot] + (int)nx : -1);
+            }
             for (int r = 0; r < m;) {   // contiguous runs of embedding rows go straight into the residual stream at their packed rows
                 if (cv.pend_tok[c.row + r] >= 0) { r++; continue; }
                 int j = r; while (j < m && cv.pend_tok[c.row + j] < 0) j++;
@@ -1702,15 +1711,195 @@ int Engine::prefill_packed(const int *slots, int n) {
         HIP_CHECK(hipMemcpyAsync(d_seg_, h_seg_, seg_ints() * 4, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(d_tokens_, tok.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));                            // the (pageable) queues may be changed right after this call
+        ScoreReq rq;
+        if (so) {
+            rq.first = N; rq.end = 0;
+            for (int r = 0; r < N; r++) if (tgt[(size_t)r] >= 0) { rq.first = std::min(rq.first, r); rq.end = r + 1; }
+            if (rq.end > rq.first) {   // (a chunk without a target row runs exactly as prefill_batch runs it)
+                rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_;
+                HIP_CHECK(hipMemcpyAsync(score_tgt_, tgt.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
+                HIP_CHECK(hipStreamSynchronize(stream_));
+                score_ = &rq;
+            }
+        }
         seg_ = &sc;
+        struct Clear { Engine *e; ~Clear() { e->seg_ = nullptr; e->score_ = nullptr; } } clear{this};
         forward(N, true, stream_);                                           // k_get_rows skips rows whose id is negative
         seg_ = nullptr;
+        if (score_) {
+            score_ = nullptr;
+            const size_t nr = (size_t)(rq.end - rq.first);
+            h_lp.resize(nr); h_glp.resize(nr); h_gr.resize(nr);
+            HIP_CHECK(hipMemcpyAsync(h_lp.data(), score_lp_ + rq.first, nr * 4, hipMemcpyDeviceToHost, stream_));
+            HIP_CHECK(hipMemcpyAsync(h_glp.data(), score_glp_ + rq.first, nr * 4, hipMemcpyDeviceToHost, stream_));
+            HIP_CHECK(hipMemcpyAsync(h_gr.data(), score_greedy_ + rq.first, nr * 4, hipMemcpyDeviceToHost, stream_));
+            HIP_CHECK(hipStreamSynchronize(stream_));
+            for (int r = rq.first; r < rq.end; r++) {
+                const int d = dest[(size_t)r];
+                if (d < 0) continue;
+                so->logprob[d] = h_lp[(size_t)(r - rq.first)];
+                if (so->greedy) so->greedy[d] = h_gr[(size_t)(r - rq.first)];
+                if (so->greedy_logprob) so->greedy_logprob[d] = h_glp[(size_t)(r - rq.first)];
+            }
+        }
         for (int i = 0; i < sc.n_seg; i++) conv_[(size_t)sc.h_segs[4 * i]].n_committed += sc.h_segs[4 * i + 2];
     }
-    for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.pend_tok.clear(); cv.pend_embd.clear(); }
+    for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.pend_tok.clear(); cv.pend_embd.clear(); cv.has_logits = true; }
     if (pfx_hits) { pfx_.hits += pfx_hits; pfx_.rows_reused_total += pfx_reused; pfx_.rows_last = pfx_reused; }   // counted only after every chunk succeeded
     if (cap_slot >= 0) prefix_capture(cap_slot, cap_ids);
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));   // greedy sample_token reads this copy
+    return 0;
+}
+
+// ====================================================================================================================
+// scoring: log-probabilities of given tokens from the prompt pass (engine.hpp)
+// ====================================================================================================================
+void Engine::score_alloc() {
+    const int need = max_rows_ + MAX_CONVERSATIONS;
+    if (score_buf_ && score_cap_ >= need) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    score_free();
+    const size_t V = llm_.n_vocab;
+    try {
+        HIP_CHECK(hipMalloc((void **)&score_buf_, (size_t)SCORE_ROWS * V * 4));
+        HIP_CHECK(hipMalloc((void **)&score_tgt_, (size_t)need * 4)); HIP_CHECK(hipMalloc((void **)&score_greedy_, (size_t)need * 4));
+        HIP_CHECK(hipMalloc((void **)&score_lp_, (size_t)need * 4)); HIP_CHECK(hipMalloc((void **)&score_glp_, (size_t)need * 4));
+    } catch (...) { score_free(); throw; }
+    score_cap_ = need;
+}
+void Engine::score_free() {
+    for (void *p : {(void *)score_buf_, (void *)score_tgt_, (void *)score_greedy_, (void *)score_lp_, (void *)score_glp_}) if (p) HIP_IGNORE(hipFree(p));
+    score_buf_ = score_lp_ = score_glp_ = nullptr; score_tgt_ = score_greedy_ = nullptr; score_cap_ = 0;
+}
+// The scored rows of the pass that is being enqueued: x_ holds every row's residual once the layers are done.  Tiles of SCORE_ROWS rows: final norm + output matrix
+// into score_buf_ (parity mode: the oracle-order preparation and mat-mul, as forward_ref's prompt rows), k_logprob_rows, the optional copy of the tile to the host.
+void Engine::score_rows(hipStream_t s) {
+    const ScoreReq &rq = *score_;
+    const int E = (int)llm_.n_embd, V = (int)llm_.n_vocab;
+    for (int r0 = rq.first; r0 < rq.end; r0 += SCORE_ROWS) {
+        const int rows = std::min(SCORE_ROWS, rq.end - r0);
+        const float *xr = x_ + (size_t)r0 * E;
+        if (parity_) {
+            launch_rms_quant(xr, norm_, rows, E, act_, act_mask_for(output_.type), s, true);
+            const QWeight *Wo[1] = {&output_}; float *Yo[1] = {score_buf_};
+            if (!(rows >= 5 && launch_mmq2_set(Wo, Yo, nullptr, 1, act_, rows, V, s, nullptr, 1))) launch_mul_mat_ref(output_, act_, rows, score_buf_, V, nullptr, s);
+        } else {
+            const Prep p_rows{1, xr, norm_};
+            mul_mat(output_, rows, score_buf_, V, nullptr, s, &p_rows, false, "score");
+        }
+        launch_logprob_rows(score_buf_, V, V, rows, rq.targets + r0, rq.logprob + r0, rq.greedy + r0, rq.greedy_logprob + r0, s);
+        if (rq.h_logits) HIP_CHECK(hipMemcpyAsync(rq.h_logits + (size_t)(r0 - rq.first) * V, score_buf_, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
+    }
+}
+// Entry 0 of a conversation: one launch of the kernel on its logits_ row from before the call (result slot max_rows_ + idx); the no-logits values otherwise.
+// The copies land by the caller's next synchronisation.
+void Engine::score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out) {
+    const size_t V = llm_.n_vocab;
+    if (!conv_[(size_t)slot].has_logits) {
+        *logprob = 0.0f; if (greedy) *greedy = -1; if (greedy_logprob) *greedy_logprob = 0.0f;
+        if (logits_out) memset(logits_out, 0, V * 4);
+        return;
+    }
+    const int at = max_rows_ + idx;
+    const float *row = logits_ + (size_t)slot * V;
+    launch_set_int(score_tgt_ + at, target, stream_);
+    launch_logprob_rows(row, (int)V, (int)V, 1, score_tgt_ + at, score_lp_ + at, score_greedy_ + at, score_glp_ + at, stream_);
+    HIP_CHECK(hipMemcpyAsync(logprob, score_lp_ + at, 4, hipMemcpyDeviceToHost, stream_));
+    if (greedy) HIP_CHECK(hipMemcpyAsync(greedy, score_greedy_ + at, 4, hipMemcpyDeviceToHost, stream_));
+    if (greedy_logprob) HIP_CHECK(hipMemcpyAsync(greedy_logprob, score_glp_ + at, 4, hipMemcpyDeviceToHost, stream_));
+    if (logits_out) HIP_CHECK(hipMemcpyAsync(logits_out, row, V * 4, hipMemcpyDeviceToHost, stream_));
+}
+// The checks come before anything is evaluated or queued.  The chunks are flush()'s chunks without the prefix store; a chunk whose rows all predict a given token
+// (every chunk but the last) scores all its rows, the last chunk all but its last row -- which, when it is the chunk's only row, leaves the captured decode step.
+int Engine::score_tokens(const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out) {
+    auto fail = [](const std::string &what) { set_last_error("score_tokens: " + what); return 1; };
+    if (!tokens || !logprob) return fail("tokens and logprob_out are required");
+    if (n < 1) return fail("n < 1");
+    const int V = (int)llm_.n_vocab;
+    for (int i = 0; i < n; i++) if (tokens[i] < 0 || tokens[i] >= V) return fail("token id out of range");
+    if (weights_missing()) return fail(last_error());
+    Conversation &cv = conv_[(size_t)cur_];
+    if (cv.n_past + n > n_ctx_ && make_room(n)) return fail("context overflow: n_past + n_tokens > n_ctx");
+    if (flush()) return fail("the queued rows could not be evaluated: " + last_error());
+    score_alloc();
+    score_entry0(cur_, 0, tokens[0], logprob, greedy, greedy_logprob, logits_out);
+    struct Clear { Engine *e; ~Clear() { e->score_ = nullptr; } } clear{this};
+    std::vector<int> tgt;
+    try {
+        for (int i = 0; i < n; i += max_chunk_) {
+            const int N = std::min(max_chunk_, n - i), nt = std::min(N, n - 1 - i);   // rows i .. i + N - 1; row j predicts tokens[j + 1]
+            ScoreReq rq;
+            if (nt > 0) {
+                tgt.assign(tokens + i + 1, tokens + i + 1 + nt); tgt.resize((size_t)N, -1);
+                HIP_CHECK(hipMemcpyAsync(score_tgt_, tgt.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
+                HIP_CHECK(hipStreamSynchronize(stream_));
+                rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_; rq.first = 0; rq.end = nt;
+                rq.h_logits = logits_out ? logits_out + (size_t)(i + 1) * V : nullptr;
+                score_ = &rq;
+            }
+            const int rc = eval_chunk(tokens + i, N, nullptr);
+            score_ = nullptr;
+            if (rc) { cv.n_past = cv.n_committed; return fail("a pass failed: " + last_error()); }
+            cv.n_past = cv.n_committed;
+            if (nt > 0) {
+                HIP_CHECK(hipMemcpyAsync(logprob + i + 1, score_lp_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
+                if (greedy) HIP_CHECK(hipMemcpyAsync(greedy + i + 1, score_greedy_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
+                if (greedy_logprob) HIP_CHECK(hipMemcpyAsync(greedy_logprob + i + 1, score_glp_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    } catch (...) { cv.n_past = cv.n_committed; throw; }
+    return 0;
+}
+int Engine::score_batch(const int *slots, int n, const int *tokens, const int *counts, float *logprob, int *greedy, float *greedy_logprob) {
+    auto fail = [](const std::string &what) { set_last_error("score_batch: " + what); return 1; };
+    const int S = (int)conv_.size(), V = (int)llm_.n_vocab;
+    if (!slots || n < 1 || n > S) return fail("bad slot list");
+    bool seen[MAX_CONVERSATIONS] = {false};
+    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return fail("conversations must be distinct and in range"); seen[slots[i]] = true; }
+    if (!tokens || !counts || !logprob) return fail("tokens, counts and logprob_out are required");
+    size_t total = 0;
+    for (int i = 0; i < n; i++) { if (counts[i] < 1) return fail("every count must be >= 1"); total += (size_t)counts[i]; }
+    for (size_t i = 0; i < total; i++) if (tokens[i] < 0 || tokens[i] >= V) return fail("token id out of range");
+    // make_room's own rule, asked before anything is evaluated: past it, make_room below can only fail with the device (its shift arguments are in range by then)
+    for (int i = 0; i < n; i++)
+        if (conv_[(size_t)slots[i]].n_past + counts[i] > n_ctx_ && !shift_allows(counts[i])) return fail("context overflow: n_past + n_tokens > n_ctx");
+    if (weights_missing()) return fail(last_error());
+    const int keep = cur_;
+    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; e->seg_ = nullptr; e->score_ = nullptr; } } restore{this, keep};
+    if (parity_ || trace_file_) {   // as prefill_batch: the oracle-order pass is the single-conversation one
+        size_t off = 0;
+        for (int i = 0; i < n; i++) {
+            cur_ = slots[i];
+            // (the arguments were checked above: what can still fail is a pass on the device -- the conversations before this one keep what they evaluated, like
+            // prefill_batch's per-conversation flush)
+            if (score_tokens(tokens + off, counts[i], logprob + off, greedy ? greedy + off : nullptr, greedy_logprob ? greedy_logprob + off : nullptr, nullptr)) return fail(last_error());
+            off += (size_t)counts[i];
+        }
+        return 0;
+    }
+    if (prefill_batch(slots, n)) return fail("the queued rows could not be evaluated: " + last_error());
+    for (int i = 0; i < n; i++) { cur_ = slots[i]; if (conv_[(size_t)cur_].n_past + counts[i] > n_ctx_ && make_room(counts[i])) return fail("context overflow: the automatic shift failed"); }
+    score_alloc();
+    ScoreOut so; so.logprob = logprob; so.greedy = greedy; so.greedy_logprob = greedy_logprob;
+    size_t off = 0;
+    for (int i = 0; i < n; i++) {
+        so.off[slots[i]] = (int)off;
+        score_entry0(slots[i], i, tokens[off], logprob + off, greedy ? greedy + off : nullptr, greedy_logprob ? greedy_logprob + off : nullptr, nullptr);
+        off += (size_t)counts[i];
+    }
+    off = 0;
+    for (int i = 0; i < n; i++) {
+        Conversation &cv = conv_[(size_t)slots[i]];
+        cv.pend_tok.assign(tokens + off, tokens + off + counts[i]); cv.pend_embd.clear();
+        cv.n_past += counts[i];
+        off += (size_t)counts[i];
+    }
+    auto drop_all = [&] { for (int i = 0; i < n; i++) { Conversation &cv = conv_[(size_t)slots[i]]; cv.pend_tok.clear(); cv.pend_embd.clear(); cv.n_past = cv.n_committed; } };
+    try {
+        if (prefill_packed(slots, n, &so)) { drop_all(); return fail("a pass failed: " + last_error()); }
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    } catch (...) { drop_all(); throw; }
     return 0;
 }
 

@@ -62,7 +62,7 @@ public:
     int sample_token(const SampleParams &p);          // minigpt4.cpp:2425-2483
     const char *id_to_token(int id) const;            // minigpt4.cpp:2485-2497 (borrowed pointer)
     // minigpt4.cpp:2499-2502 (the selected conversation)
-    void reset() { Conversation &c = conv_[(size_t)cur_]; c.pend_tok.clear(); c.pend_embd.clear(); c.n_past = 0; c.n_committed = 0; }
+    void reset() { Conversation &c = conv_[(size_t)cur_]; c.pend_tok.clear(); c.pend_embd.clear(); c.n_past = 0; c.n_committed = 0; c.has_logits = false; }
     void sync();
     hipStream_t stream() const { return stream_; }
     // ---- context shift (llama.cpp's answer to a full context), selected conversation: pending rows are evaluated first, then rows
@@ -134,6 +134,23 @@ public:
     struct PrefixInfo { int max_rows = 0, stored_rows = 0, hits = 0, rows_reused_total = 0, captures = 0, rows_last = 0, hit_launches = 0; };
     PrefixInfo prefix_info() const { PrefixInfo p = pfx_; p.max_rows = pfx_max_; p.stored_rows = (int)pfx_ids_.size(); return p; }
 
+    // ---- scoring: the log-probabilities of GIVEN tokens (llama.cpp's logits_all / perplexity), from the prompt pass that evaluates them.  Entry i describes the
+    // distribution tokens[i] is drawn from: for i >= 1 the logits of row i - 1 of this call, for i == 0 the conversation's logits from before the call (none --
+    // nothing evaluated yet, after reset(), after a partial fork: logprob 0, greedy -1, greedy_logprob 0, a zero logits row).  logprob[i] = log softmax(row)[tokens[i]],
+    // greedy[i] = the row's first argmax, greedy_logprob[i] = its log-probability, logits_out[i] = the row.  The pass is the one add_tokens + flush runs -- same chunks,
+    // same launches, the last row's logits / greedy id / feed token from the same one-row output launch -- with the scored rows' output mat-mul (tiles of SCORE_ROWS
+    // rows into a buffer of the feature's own) and k_logprob_rows next to it, so the conversation ends bit-identical and can be sampled and continued.  The prefix
+    // store is neither consulted nor written.  0, or 1 with last_error "score_tokens: ..." and nothing of `tokens` added (null tokens / logprob, n < 1, an id outside
+    // [0, n_vocab) -- checked on the host: a target indexes a logits row on the device --, rows that do not fit n_ctx under add_tokens' rule).
+    static constexpr int SCORE_ROWS = 64;
+    int score_tokens(const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out);
+    // the same for n_slots distinct conversations, tokens / counts / outputs concatenated in slot-list order: queued rows first (prefill_batch), then every
+    // conversation's tokens packed into as few passes as prefill_batch takes; each conversation ends bit-identical to prefill_batch of the same tokens.  Parity mode:
+    // one score_tokens per conversation.  1 with last_error "score_batch: ..." and every conversation untouched on a bad slot list, a count < 1, a bad id, an overflow
+    // (all checked before anything runs).  A pass or an automatic shift that fails on the device afterwards also returns 1 with that prefix; conversations the call had
+    // already evaluated or shifted by then keep that state, as after a failed prefill_batch.
+    int score_batch(const int *slots, int n_slots, const int *tokens, const int *counts, float *logprob, int *greedy, float *greedy_logprob);
+
     // ---- measurement hooks (bench / tests)
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
     int decode_loop(int steps, int *tokens_out, float *ms_total);
@@ -163,7 +180,20 @@ private:
         double key_rows = 0;                           // cached rows the segments' attention reads (profile_sites)
     };
     const SegChunk *seg_ = nullptr;
-    int prefill_packed(const int *slots, int n);
+    // score request: while set, the pass (forward / forward_ref, plain or packed) also evaluates the output matrix on chunk rows [first, end) and runs k_logprob_rows
+    // on them.  targets / logprob / greedy / greedy_logprob: device arrays indexed by chunk row, target -1 = the row predicts nothing that was given; h_logits
+    // (plain pass only): host destination of row `first`'s logits, the following rows behind it
+    struct ScoreReq { const int *targets = nullptr; float *logprob = nullptr; int *greedy = nullptr; float *greedy_logprob = nullptr; int first = 0, end = 0; float *h_logits = nullptr; };
+    const ScoreReq *score_ = nullptr;
+    // the feature's own lazy allocation (first scoring call; freed with the context): [SCORE_ROWS][n_vocab] logits, and [score_cap_] targets / results -- one per chunk
+    // row, then one per conversation for entry 0
+    float *score_buf_ = nullptr, *score_lp_ = nullptr, *score_glp_ = nullptr; int *score_tgt_ = nullptr, *score_greedy_ = nullptr; int score_cap_ = 0;
+    void score_alloc();
+    void score_free();
+    void score_rows(hipStream_t s);
+    void score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out);
+    struct ScoreOut { int off[MAX_CONVERSATIONS]; float *logprob; int *greedy; float *greedy_logprob; };   // score_batch: [slot] -> the conversation's first output entry
+    int prefill_packed(const int *slots, int n, const ScoreOut *so = nullptr);
     void attn_segments(const SegChunk &sg, __half *kc, __half *vc, bool want_h, bool *att_in_xh, hipStream_t s);
     // d_seg_ / h_seg_ layout (ints): segments [0, 256), finish rows [256, 384), last rows [384, 448), row table [448, + 2 max_rows_), then the 16- and 32-query work
     // lists, 2 (max_rows_ + 64) each
@@ -200,6 +230,7 @@ private:
         std::vector<int> pend_tok; std::vector<float> pend_embd;
         hipGraphExec_t graph = nullptr;   // decode step captured with this conversation's cache / position / token addresses
         bool graph_split = false;         // ... with the key-split attention launches (long context) or the one-workgroup-per-head kernel
+        bool has_logits = false;          // its logits_ row holds the logits after its last evaluated row (not: nothing evaluated yet, after reset(), after a partial fork)
     };
     std::vector<Conversation> conv_ = std::vector<Conversation>(1);
     int cur_ = 0;
@@ -212,6 +243,7 @@ private:
     int prefix_match(const Conversation &cv) const;        // m of the lookup (0 when the store is off or the conversation is not at position 0)
     void prefix_copy_in(const int *slots, int n, int n_rows);   // store -> the listed conversations' caches, one launch
     void prefix_capture(int slot, const std::vector<int> &ids);   // that conversation's rows [0, ids.size()) -> store
+    bool shift_allows(int n) const { return shift_keep_ >= 0 && n <= n_ctx_ - shift_keep_; }   // the policy is on and n more rows fit behind the kept ones
     int make_room(int n);                  // the automatic shift for n more rows of the selected conversation: 0 = room made (or already there), 1 = not
     bool defer_ = true; int max_chunk_ = 512;
     void release_buffers();

@@ -173,6 +173,9 @@ bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half 
 // row r: logits row r belongs to conversation fin[2 r]: slot_logits / argmax / feed as launch_batch_finish, n_past[slot] = fin[2 r + 1]
 void launch_seg_finish(const float *logits, int n_vocab, int B, const int *fin, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s);
 void launch_gather_rows(const float *src, const int *idx, int n, int E, float *dst, hipStream_t s);   // dst[r] = src[idx[r]], rows of E floats
+// scoring, one workgroup per row r of `logits` (row stride ld >= n_vocab floats, any alignment): greedy[r] = first argmax, greedy_logprob[r] = its log-softmax,
+// logprob[r] = log softmax(row)[targets[r]] (natural logarithm; the maximum is subtracted before exp), or 0 when targets[r] == -1
+void launch_logprob_rows(const float *logits, int ld, int n_vocab, int rows, const int *targets, float *logprob, int *greedy, float *greedy_logprob, hipStream_t s);
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)

@@ -3050,6 +3050,50 @@ void launch_gather_rows(const float *src, const int *idx, int n, int E, float *d
     note_kernel("k_gather_rows");
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n), dim3(256), 0, s, src, idx, E, dst);
 }
+// Scoring (Engine::score_tokens): one workgroup per logits row.  Sweep 1: the row's maximum and its first index; sweep 2: sum of exp(x - max) (the row was just
+// written, both sweeps hit L2).  logprob = (x[target] - max) - log(sum): the maximum's own term is exp(0) = 1, so sum >= 1 and no single exp is ever passed to log.
+// Rows start at logits + r * ld with any ld >= n_vocab (32001 floats: not 16-byte aligned from row 1 on), so each row takes its own scalar head up to the first
+// aligned address, 16-byte loads over the body and a scalar tail; every element carries its index and argmax_combine prefers the lower one, whatever order a thread meets them in.
+__global__ __launch_bounds__(256) void k_logprob_rows(const float *__restrict__ logits, int ld, int n_vocab, const int *__restrict__ targets, float *__restrict__ logprob,
+                                                      int *__restrict__ greedy, float *__restrict__ greedy_logprob) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const float *x = logits + (size_t)r * ld;
+    const int head = min(n_vocab, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2);
+    const int n4 = (n_vocab - head) >> 2, tail0 = head + 4 * n4;
+    const float4 *x4 = reinterpret_cast<const float4 *>(x + head);
+    float best = -INFINITY; int bi = 0x7FFFFFFF;
+    if (tid < head) argmax_combine(best, bi, x[tid], tid);
+    for (int i = tid; i < n4; i += 256) {
+        const float4 v = x4[i]; const int b = head + 4 * i;
+        argmax_combine(best, bi, v.x, b); argmax_combine(best, bi, v.y, b + 1); argmax_combine(best, bi, v.z, b + 2); argmax_combine(best, bi, v.w, b + 3);
+    }
+    if (tail0 + tid < n_vocab) argmax_combine(best, bi, x[tail0 + tid], tail0 + tid);
+    __shared__ float sv[4]; __shared__ int si[4]; __shared__ float ss[4];
+    argmax_wave(best, bi);
+    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+    __syncthreads();
+    best = sv[0]; bi = si[0];
+    for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]);   // every thread: the row's maximum, uniformly
+    float sum = 0.0f;
+    if (tid < head) sum += expf(x[tid] - best);
+    for (int i = tid; i < n4; i += 256) { const float4 v = x4[i]; sum += expf(v.x - best); sum += expf(v.y - best); sum += expf(v.z - best); sum += expf(v.w - best); }
+    if (tail0 + tid < n_vocab) sum += expf(x[tail0 + tid] - best);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((tid & 63) == 0) ss[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        const float lse = logf((ss[0] + ss[1]) + (ss[2] + ss[3]));
+        const int t = targets[r];
+        greedy[r] = bi == 0x7FFFFFFF ? 0 : bi;
+        greedy_logprob[r] = -lse;
+        logprob[r] = t >= 0 && t < n_vocab ? (x[t] - best) - lse : 0.0f;
+    }
+}
+void launch_logprob_rows(const float *logits, int ld, int n_vocab, int rows, const int *targets, float *logprob, int *greedy, float *greedy_logprob, hipStream_t s) {
+    note_kernel("k_logprob_rows");
+    hipLaunchKernelGGL(k_logprob_rows, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, n_vocab, targets, logprob, greedy, greedy_logprob);
+}
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {
     const int r = threadIdx.x;

@@ -654,6 +654,29 @@ int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int
         return 0;
     });
 }
+// The scoring kernel (launch_logprob_rows) on host logits [rows][ld]: one launch, hipEvent-timed.  Every target is checked here: it indexes a row on the device.
+int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, int ld, const int32_t *targets, float *logprob_out, int32_t *greedy_out, float *greedy_logprob_out,
+                                   float *ms_out) {
+    if (!logits || !targets || !logprob_out || !greedy_out || !greedy_logprob_out || rows < 1 || n_vocab < 1 || ld < n_vocab) return 1;
+    for (int r = 0; r < rows; r++) if (targets[r] < -1 || targets[r] >= n_vocab) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)rows * ld, R = (size_t)rows;
+        DevBuf dl(n * 4), dt(R * 4), dp(R * 4), dg(R * 4), dq(R * 4);
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, targets, R * 4, hipMemcpyHostToDevice));
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;   // destroyed on every path
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        launch_logprob_rows(dl.as<float>(), ld, n_vocab, rows, dt.as<int>(), dp.as<float>(), dg.as<int>(), dq.as<float>(), nullptr);
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        HIP_CHECK(hipMemcpy(logprob_out, dp.p, R * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(greedy_out, dg.p, R * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(greedy_logprob_out, dq.p, R * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
 static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {

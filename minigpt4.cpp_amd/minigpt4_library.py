@@ -205,6 +205,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_fork_conversation.argtypes = [VOID_PTR, I32, INT_PTR, I32, I32]
         L.minigpt4_amd_set_prefix_cache.argtypes = [VOID_PTR, I32]
         L.minigpt4_amd_prefix_cache_info.argtypes = [VOID_PTR, INT_PTR]
+        L.minigpt4_amd_score_tokens.argtypes = [VOID_PTR, INT_PTR, I32, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_score_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -228,6 +230,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_attn_f32.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, F32, F32, I32, I32, VOID_PTR, FLOAT_PTR, VOID_PTR]
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_kv_copy.argtypes = [I32, I32, I32, I32, I32, INT_PTR, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
@@ -429,6 +432,55 @@ class MiniGPT4SharedLibrary:
         if self.library.minigpt4_amd_prefix_cache_info(ctx.ptr, out):
             raise RuntimeError("prefix_cache_info failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return dict(zip(self.PREFIX_INFO_FIELDS, (int(x) for x in out)))
+
+    def amd_score_tokens(self, ctx, tokens: Sequence[int], want_logits: bool = False) -> dict:
+        """Append `tokens` to the selected conversation and evaluate them like amd_eval_tokens + amd_logits (same state afterwards), reporting per token the
+        log-probability the model gave it.  Entry i describes the distribution tokens[i] is drawn from (entry 0: the conversation's logits from before the call; none:
+        logprob 0, greedy -1).  dict(logprob [n] f32, greedy [n] i32, greedy_logprob [n] f32[, logits [n][n_vocab] f32]).  include/minigpt4_amd.h"""
+        t = np.ascontiguousarray(tokens, np.int32)
+        n = len(t)
+        lp, gr, glp = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        lg = np.zeros((n, self.library.minigpt4_amd_n_vocab(ctx.ptr)), np.float32) if want_logits else None
+        if self.library.minigpt4_amd_score_tokens(ctx.ptr, t.ctypes.data_as(INT_PTR), n, lp.ctypes.data_as(FLOAT_PTR), gr.ctypes.data_as(INT_PTR), glp.ctypes.data_as(FLOAT_PTR),
+                                                  lg.ctypes.data_as(FLOAT_PTR) if want_logits else None):
+            raise RuntimeError("score_tokens failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        out = dict(logprob=lp, greedy=gr, greedy_logprob=glp)
+        if want_logits:
+            out["logits"] = lg
+        return out
+
+    def amd_score_batch(self, ctx, slots: Sequence[int], token_lists: Sequence[Sequence[int]]) -> List[dict]:
+        """amd_score_tokens for several distinct conversations in packed passes (as amd_prefill_batch evaluates them): one dict(logprob, greedy, greedy_logprob) per
+        conversation, in slot-list order.  include/minigpt4_amd.h"""
+        sl = np.ascontiguousarray(slots, np.int32)
+        lists = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_lists]
+        cnt = np.ascontiguousarray([len(t) for t in lists], np.int32)
+        tk = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32)
+        n = max(int(tk.size), 1)
+        lp, gr, glp = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        if len(lists) != len(sl):
+            raise RuntimeError("score_batch failed: score_batch: one token list per slot is required")
+        if self.library.minigpt4_amd_score_batch(ctx.ptr, sl.ctypes.data_as(INT_PTR), len(sl), tk.ctypes.data_as(INT_PTR), cnt.ctypes.data_as(INT_PTR),
+                                                 lp.ctypes.data_as(FLOAT_PTR), gr.ctypes.data_as(INT_PTR), glp.ctypes.data_as(FLOAT_PTR)):
+            raise RuntimeError("score_batch failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        ends = np.cumsum(cnt)
+        return [dict(logprob=lp[e - c:e].copy(), greedy=gr[e - c:e].copy(), greedy_logprob=glp[e - c:e].copy()) for e, c in zip(ends, cnt)]
+
+    def amd_test_logprob_rows(self, logits: np.ndarray, targets: Sequence[int], n_vocab: Optional[int] = None):
+        """launch_logprob_rows on host logits [rows][ld] (n_vocab <= ld columns are read): returns (logprob, greedy, greedy_logprob, ms) -- per row the log-softmax of
+        targets[r] (-1: none), the first argmax, its log-softmax, and the launch's hipEvent time."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        rows, ld = lg.shape
+        nv = ld if n_vocab is None else int(n_vocab)
+        tg = np.ascontiguousarray(targets, np.int32)
+        assert tg.shape == (rows,)
+        lp, gr, glp, ms = np.zeros(rows, np.float32), np.zeros(rows, np.int32), np.zeros(rows, np.float32), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_logprob_rows(lg.ctypes.data_as(FLOAT_PTR), rows, nv, ld, tg.ctypes.data_as(INT_PTR), lp.ctypes.data_as(FLOAT_PTR),
+                                                         gr.ctypes.data_as(INT_PTR), glp.ctypes.data_as(FLOAT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_logprob_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return lp, gr, glp, float(ms.value)
 
     def amd_test_kv_copy(self, k: np.ndarray, v: np.ndarray, src: int, dsts: Sequence[int], n_rows: int, src_rows: int = 0):
         """launch_kv_copy on fp16 caches [n_slot][n_layer][rows][n_embd]: rows [0, n_rows) of slot `src` (src_rows > 0: of a compact [n_layer][src_rows][n_embd] copy of its
