@@ -145,6 +145,37 @@ MINIGPT4_API int minigpt4_amd_score_tokens(struct MiniGPT4Context *ctx, const in
 MINIGPT4_API int minigpt4_amd_score_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n_slots, const int32_t *tokens, const int32_t *counts, float *logprob_out,
                                           int32_t *greedy_out, float *greedy_logprob_out);
 
+/* ---- top-N alternatives with log-probabilities (the `logprobs=N` of completion APIs, llama.cpp server's n_probs) ------------------------------------------------------
+ * One kernel (k_topn_rows, one workgroup per logits row, a constant number of sweeps whatever top_n and the data) selects on the device: a 32001-float row never travels
+ * to the host to be sorted.  ORDER: logit descending, equal logits (float equality: -0.0 and +0.0 tie) by ascending token id.  top_n is 1 .. 64 and <= n_vocab.  A
+ * log-probability is log softmax(raw logits) (natural logarithm), whatever sampling parameters are in use, and is bit for bit the value minigpt4_amd_score_tokens reports
+ * for the same token of the same row.  rank = the number of tokens that sort before a token in that order (0: it is the greedy token).  Every call returns 0, or 1 with
+ * a text in minigpt4_amd_last_error that begins with the call's short name ("top_logprobs: ...") -- and on a refusal of its arguments nothing has changed.
+ * minigpt4_amd_token_piece: the borrowed text of a token id, as minigpt4_end_chat returns it ("</s>" for id 2); NULL without a context or for an id outside [0, n_vocab).
+ * minigpt4_amd_top_logprobs: what each of n_slots DISTINCT conversations would say next, without advancing anything.  Queued rows are evaluated first, exactly as
+ * minigpt4_amd_prefill_batch(ctx, slots, n_slots) does; then one launch over the listed conversations' logits, one copy back, one synchronise.  top_ids_out /
+ * top_logprobs_out: [n_slots][top_n].  targets (may be NULL; an entry of -1 = none): logprob_out[i] / rank_out[i] (each may be NULL) describe targets[i] (none: 0 / -1).
+ * A conversation without current logits (nothing evaluated, after minigpt4_reset_chat, after a partial fork): ids -1, log-probabilities 0, rank -1.  Position, logits,
+ * greedy token, feed token, the sampler's generator and the mirostat state are untouched.  Refused: no context, a bad slot list, NULL top_ids_out / top_logprobs_out,
+ * top_n out of range, a target outside [-1, n_vocab).
+ * minigpt4_amd_end_chat_batch_top: minigpt4_amd_end_chat_batch that also reports, for EVERY listed conversation (one that is full, sampled but not advanced, included),
+ * the sampled id (ids_out[n]), its log-probability and rank (logprob_out[n], rank_out[n]) and the top_n alternatives of the distribution it was drawn from
+ * (top_ids_out / top_logprobs_out [n][top_n]).  Conversations, pieces and sampler draws are exactly minigpt4_amd_end_chat_batch's in the same state; the kernel runs
+ * between the sampling and the weight pass and its results are awaited while the pass runs.  All five outputs are required.
+ * minigpt4_amd_score_tokens_top: minigpt4_amd_score_tokens with rank_out[n] and the alternatives top_ids_out / top_logprobs_out [n][top_n] of every entry (same entry
+ * indexing; column 0 is score_tokens' greedy / greedy_logprob).  Entry 0 of a conversation without logits: logprob 0, rank -1, ids -1, log-probabilities 0.  logprob_out
+ * and the conversation afterwards are bit for bit what minigpt4_amd_score_tokens of the same tokens gives.  All four outputs are required.  The result arrays of the
+ * feature are allocated by the first of these calls: plain scoring and plain decoding pay nothing and launch nothing new.
+ * Not built: a packed minigpt4_amd_score_batch with alternatives; log-probabilities of tempered or filtered distributions; any use of the selection by the sampler. */
+MINIGPT4_API const char *minigpt4_amd_token_piece(struct MiniGPT4Context *ctx, int32_t id);
+MINIGPT4_API int minigpt4_amd_top_logprobs(struct MiniGPT4Context *ctx, const int32_t *slots, int n_slots, int top_n, const int32_t *targets, int32_t *top_ids_out,
+                                           float *top_logprobs_out, float *logprob_out, int32_t *rank_out);
+MINIGPT4_API int minigpt4_amd_end_chat_batch_top(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p, float tfs_z,
+                                                 float typical_p, int mirostat, float mirostat_tau, float mirostat_eta, int top_n, int32_t *ids_out, float *logprob_out,
+                                                 int32_t *rank_out, int32_t *top_ids_out, float *top_logprobs_out);
+MINIGPT4_API int minigpt4_amd_score_tokens_top(struct MiniGPT4Context *ctx, const int32_t *tokens, int n, int top_n, float *logprob_out, int32_t *rank_out, int32_t *top_ids_out,
+                                               float *top_logprobs_out);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

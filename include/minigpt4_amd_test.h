@@ -83,6 +83,14 @@ MINIGPT4_API int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, in
  * touched (a NULL pointer, rows < 1, n_vocab < 1, ld < n_vocab, a target >= n_vocab or < -1) */
 MINIGPT4_API int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, int ld, const int32_t *targets, float *logprob_out, int32_t *greedy_out,
                                                 float *greedy_logprob_out, float *ms_out);
+/* the top-N kernel (launch_topn_rows) on host logits [buf_rows][ld] fp32 (ld >= n_vocab; only the first n_vocab floats of a row are read).  `rows` rows are evaluated:
+ * row r is buffer row row_index[r] (duplicates allowed), or r when row_index is NULL.  Per row: ids_out / logprobs_out [rows][top_n] = the first top_n tokens in the
+ * order "logit descending, equal logits by ascending id" and their log-softmax (the bits minigpt4_amd_test_logprob_rows reports for them), rank_out = the number of tokens
+ * that sort before targets[r] (-1: no target, rank -1), target_logprob_out = the target's log-softmax (0 without one).  One launch; ms_out (may be NULL): its hipEvent
+ * time.  1 = bad arguments, before any device is touched (a NULL pointer other than row_index / ms_out, rows < 1, buf_rows < 1, n_vocab < 1, ld < n_vocab, top_n outside
+ * 1..64 or above n_vocab, a target >= n_vocab or < -1, a row_index entry outside [0, buf_rows), rows > buf_rows without row_index) */
+MINIGPT4_API int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *row_index, int rows, int top_n, const int32_t *targets,
+                                             int32_t *ids_out, float *logprobs_out, int32_t *rank_out, float *target_logprob_out, float *ms_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

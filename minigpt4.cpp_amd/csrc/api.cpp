@@ -307,6 +307,35 @@ int minigpt4_amd_score_batch(struct MiniGPT4Context *ctx, const int32_t *slots, 
     if (!ctx) { set_last_error("score_batch: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->score_batch(slots, n_slots, tokens, counts, logprob_out, greedy_out, greedy_logprob_out); });
 }
+// ---- top-N alternatives with log-probabilities ---------------------------------------------------------------------------------------------
+const char *minigpt4_amd_token_piece(struct MiniGPT4Context *ctx, int32_t id) {
+    if (!ctx || id < 0 || id >= E_(ctx)->n_vocab()) return nullptr;
+    return E_(ctx)->id_to_token(id);
+}
+int minigpt4_amd_top_logprobs(struct MiniGPT4Context *ctx, const int32_t *slots, int n_slots, int top_n, const int32_t *targets, int32_t *top_ids_out, float *top_logprobs_out,
+                              float *logprob_out, int32_t *rank_out) {
+    if (!ctx) { set_last_error("top_logprobs: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->top_logprobs(slots, n_slots, top_n, targets, top_ids_out, top_logprobs_out, logprob_out, rank_out); });
+}
+int minigpt4_amd_end_chat_batch_top(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p,
+                                    int mirostat, float mirostat_tau, float mirostat_eta, int top_n, int32_t *ids_out, float *logprob_out, int32_t *rank_out, int32_t *top_ids_out,
+                                    float *top_logprobs_out) {
+    if (!ctx) { set_last_error("end_chat_batch_top: no context"); return 1; }
+    if (!tokens) { set_last_error("end_chat_batch_top: tokens is required"); return 1; }
+    Engine *e = E_(ctx);
+    return guarded(1, [&]() -> int {
+        SampleParams p; p.temp = temp; p.top_k = top_k; p.top_p = top_p; p.tfs_z = tfs_z; p.typical_p = typical_p; p.mirostat = mirostat; p.mirostat_tau = mirostat_tau; p.mirostat_eta = mirostat_eta;
+        Engine::TopOut top; top.top_n = top_n; top.top_ids = top_ids_out; top.top_lp = top_logprobs_out; top.logprob = logprob_out; top.rank = rank_out;
+        if (int rc = e->decode_batch_top(slots, n, p, ids_out, top)) return rc;
+        for (int i = 0; i < n; i++) tokens[i] = e->id_to_token(ids_out[i]);
+        return 0;
+    });
+}
+int minigpt4_amd_score_tokens_top(struct MiniGPT4Context *ctx, const int32_t *tokens, int n, int top_n, float *logprob_out, int32_t *rank_out, int32_t *top_ids_out,
+                                  float *top_logprobs_out) {
+    if (!ctx) { set_last_error("score_tokens_top: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->score_tokens_top(tokens, n, top_n, logprob_out, rank_out, top_ids_out, top_logprobs_out); });
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

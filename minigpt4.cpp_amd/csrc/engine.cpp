@@ -94,6 +94,7 @@ Engine::~Engine() {
     if (stage_) HIP_IGNORE(hipFree(stage_));
     prefix_free();
     score_free();
+    topn_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -1550,7 +1551,7 @@ int Engine::select_conversation(int slot) {
     cur_ = slot;
     return 0;
 }
-int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced) {
+int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced, const TopOut *top) {
     if (!slots || !ids_out || n < 1 || n > (int)conv_.size()) { set_last_error("decode_batch: bad slot list"); return 1; }
     if (weights_missing()) return 1;
     bool seen[MAX_CONVERSATIONS] = {false};
@@ -1562,6 +1563,10 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     for (int i = 0; i < n; i++) { cur_ = slots[i]; ids_out[i] = sample_token(p); }
     // 2. one weight pass for the conversations that still have room
     HIP_CHECK(hipStreamSynchronize(stream_));                                // h_bstage_ may still feed the previous step's copies
+    // the report reads the rows the ids were drawn from: behind the sampling, ahead of the pass that overwrites them (one in-order stream); its copy back is queued here
+    // and awaited once the step is launched
+    if (top) topn_slots_launch(slots, n, top->top_n, ids_out);
+    auto report = [&] { if (top) topn_slots_collect(n, top->top_n, top->top_ids, top->top_lp, top->logprob, top->rank); };
     int B = 0;
     for (int i = 0; i < n; i++) {
         Conversation &cv = conv_[(size_t)slots[i]];
@@ -1569,12 +1574,13 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
         if (cv.n_past + 1 > n_ctx_ && make_room(1)) continue;               // context full (and no automatic shift): sampled, not advanced
         h_bstage_[B] = forced ? forced[i] : ids_out[i]; h_bstage_[MAX_CONVERSATIONS + B] = slots[i]; h_bstage_[2 * MAX_CONVERSATIONS + B] = cv.n_committed; B++;
     }
-    if (!B) return 0;
+    if (!B) { report(); return 0; }
     // oracle-order arithmetic exists for the single-conversation pass only: one pass per conversation (same results as the batched step is tested to
     // give)
     if (parity_) {
         for (int r = 0; r < B; r++) { cur_ = h_bstage_[MAX_CONVERSATIONS + r]; const int id = h_bstage_[r]; if (eval_chunk(&id, 1, nullptr)) return 1; conv_[(size_t)cur_].n_past += 1; }
         HIP_CHECK(hipStreamSynchronize(stream_));
+        report();
         return 0;
     }
     // rows (token, conversation, position) travel in one copy; the device positions are normally current (k_advance / k_batch_finish keep them), but
@@ -1600,6 +1606,7 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
         if (logits_host_slot_ == sl) logits_host_slot_ = -1;
     }
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+    report();
     return 0;
 }
 
@@ -1788,16 +1795,20 @@ void Engine::score_rows(hipStream_t s) {
             mul_mat(output_, rows, score_buf_, V, nullptr, s, &p_rows, false, "score");
         }
         launch_logprob_rows(score_buf_, V, V, rows, rq.targets + r0, rq.logprob + r0, rq.greedy + r0, rq.greedy_logprob + r0, s);
+        if (rq.top_n && !launch_topn_rows(score_buf_, V, V, rows, nullptr, rq.top_n, rq.targets + r0, topn_ids() + (size_t)r0 * rq.top_n, topn_lp() + (size_t)r0 * rq.top_n,
+                                          topn_rank() + r0, topn_tlp() + r0, s))
+            throw HipError{hipErrorInvalidValue, "top-N launch refused", __FILE__, __LINE__};
         if (rq.h_logits) HIP_CHECK(hipMemcpyAsync(rq.h_logits + (size_t)(r0 - rq.first) * V, score_buf_, (size_t)rows * V * 4, hipMemcpyDeviceToHost, s));
     }
 }
 // Entry 0 of a conversation: one launch of the kernel on its logits_ row from before the call (result slot max_rows_ + idx); the no-logits values otherwise.
 // The copies land by the caller's next synchronisation.
-void Engine::score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out) {
+void Engine::score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top) {
     const size_t V = llm_.n_vocab;
     if (!conv_[(size_t)slot].has_logits) {
         *logprob = 0.0f; if (greedy) *greedy = -1; if (greedy_logprob) *greedy_logprob = 0.0f;
         if (logits_out) memset(logits_out, 0, V * 4);
+        if (top) { *top->rank = -1; for (int j = 0; j < top->top_n; j++) { top->top_ids[j] = -1; top->top_lp[j] = 0.0f; } }
         return;
     }
     const int at = max_rows_ + idx;
@@ -1808,21 +1819,41 @@ void Engine::score_entry0(int slot, int idx, int target, float *logprob, int *gr
     if (greedy) HIP_CHECK(hipMemcpyAsync(greedy, score_greedy_ + at, 4, hipMemcpyDeviceToHost, stream_));
     if (greedy_logprob) HIP_CHECK(hipMemcpyAsync(greedy_logprob, score_glp_ + at, 4, hipMemcpyDeviceToHost, stream_));
     if (logits_out) HIP_CHECK(hipMemcpyAsync(logits_out, row, V * 4, hipMemcpyDeviceToHost, stream_));
+    if (top) {
+        const size_t o = (size_t)at * top->top_n, nb = (size_t)top->top_n * 4;
+        if (!launch_topn_rows(row, (int)V, (int)V, 1, nullptr, top->top_n, score_tgt_ + at, topn_ids() + o, topn_lp() + o, topn_rank() + at, topn_tlp() + at, stream_))
+            throw HipError{hipErrorInvalidValue, "top-N launch refused", __FILE__, __LINE__};
+        HIP_CHECK(hipMemcpyAsync(top->top_ids, topn_ids() + o, nb, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(top->top_lp, topn_lp() + o, nb, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(top->rank, topn_rank() + at, 4, hipMemcpyDeviceToHost, stream_));
+    }
 }
 // The checks come before anything is evaluated or queued.  The chunks are flush()'s chunks without the prefix store; a chunk whose rows all predict a given token
 // (every chunk but the last) scores all its rows, the last chunk all but its last row -- which, when it is the chunk's only row, leaves the captured decode step.
 int Engine::score_tokens(const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out) {
-    auto fail = [](const std::string &what) { set_last_error("score_tokens: " + what); return 1; };
+    return score_tokens_impl("score_tokens", tokens, n, logprob, greedy, greedy_logprob, logits_out, nullptr);
+}
+int Engine::score_tokens_top(const int *tokens, int n, int top_n, float *logprob, int *rank, int *top_ids, float *top_lp) {
+    TopOut top; top.top_n = top_n; top.top_ids = top_ids; top.top_lp = top_lp; top.rank = rank;
+    return score_tokens_impl("score_tokens_top", tokens, n, logprob, nullptr, nullptr, nullptr, &top);
+}
+// top: entry i's alternatives at top_ids / top_lp + i * top_n, its rank at rank + i
+int Engine::score_tokens_impl(const char *name, const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top) {
+    auto fail = [name](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
     if (!tokens || !logprob) return fail("tokens and logprob_out are required");
     if (n < 1) return fail("n < 1");
     const int V = (int)llm_.n_vocab;
+    if (top && (!top->rank || !top->top_ids || !top->top_lp)) return fail("rank_out, top_ids_out and top_logprobs_out are required");
+    if (top && (top->top_n < 1 || top->top_n > TOPN_MAX || top->top_n > V)) return fail("top_n outside 1 .. min(64, n_vocab)");
     for (int i = 0; i < n; i++) if (tokens[i] < 0 || tokens[i] >= V) return fail("token id out of range");
     if (weights_missing()) return fail(last_error());
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.n_past + n > n_ctx_ && make_room(n)) return fail("context overflow: n_past + n_tokens > n_ctx");
     if (flush()) return fail("the queued rows could not be evaluated: " + last_error());
     score_alloc();
-    score_entry0(cur_, 0, tokens[0], logprob, greedy, greedy_logprob, logits_out);
+    if (top) topn_alloc();
+    const int tn = top ? top->top_n : 0;
+    score_entry0(cur_, 0, tokens[0], logprob, greedy, greedy_logprob, logits_out, top);
     struct Clear { Engine *e; ~Clear() { e->score_ = nullptr; } } clear{this};
     std::vector<int> tgt;
     try {
@@ -1835,6 +1866,7 @@ int Engine::score_tokens(const int *tokens, int n, float *logprob, int *greedy, 
                 HIP_CHECK(hipStreamSynchronize(stream_));
                 rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_; rq.first = 0; rq.end = nt;
                 rq.h_logits = logits_out ? logits_out + (size_t)(i + 1) * V : nullptr;
+                rq.top_n = tn;
                 score_ = &rq;
             }
             const int rc = eval_chunk(tokens + i, N, nullptr);
@@ -1845,10 +1877,103 @@ int Engine::score_tokens(const int *tokens, int n, float *logprob, int *greedy, 
                 HIP_CHECK(hipMemcpyAsync(logprob + i + 1, score_lp_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
                 if (greedy) HIP_CHECK(hipMemcpyAsync(greedy + i + 1, score_greedy_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
                 if (greedy_logprob) HIP_CHECK(hipMemcpyAsync(greedy_logprob + i + 1, score_glp_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
+                if (top) {
+                    const size_t o = (size_t)(i + 1) * tn, nb = (size_t)nt * tn * 4;
+                    HIP_CHECK(hipMemcpyAsync(top->top_ids + o, topn_ids(), nb, hipMemcpyDeviceToHost, stream_));
+                    HIP_CHECK(hipMemcpyAsync(top->top_lp + o, topn_lp(), nb, hipMemcpyDeviceToHost, stream_));
+                    HIP_CHECK(hipMemcpyAsync(top->rank + i + 1, topn_rank(), (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
+                }
             }
         }
         HIP_CHECK(hipStreamSynchronize(stream_));
     } catch (...) { cv.n_past = cv.n_committed; throw; }
+    return 0;
+}
+// ====================================================================================================================
+// top-N alternatives (engine.hpp)
+// ====================================================================================================================
+void Engine::topn_alloc() {
+    score_alloc();
+    if (topn_d_ && topn_cap_ >= score_cap_) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    topn_free();
+    const size_t words = (size_t)score_cap_ * (2 * TOPN_MAX + 2);
+    try {
+        HIP_CHECK(hipMalloc((void **)&topn_d_, words * 4)); HIP_CHECK(hipHostMalloc((void **)&topn_h_, words * 4, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc((void **)&topn_in_, 2 * MAX_CONVERSATIONS * 4)); HIP_CHECK(hipHostMalloc((void **)&topn_hin_, 2 * MAX_CONVERSATIONS * 4, hipHostMallocDefault));
+        HIP_CHECK(hipEventCreateWithFlags(&topn_ev_, hipEventDisableTiming));
+    } catch (...) { topn_free(); throw; }
+    topn_cap_ = score_cap_;
+}
+void Engine::topn_free() {
+    if (topn_d_) HIP_IGNORE(hipFree(topn_d_));
+    if (topn_in_) HIP_IGNORE(hipFree(topn_in_));
+    if (topn_h_) HIP_IGNORE(hipHostFree(topn_h_));
+    if (topn_hin_) HIP_IGNORE(hipHostFree(topn_hin_));
+    if (topn_ev_) HIP_IGNORE(hipEventDestroy(topn_ev_));
+    topn_d_ = topn_h_ = topn_in_ = topn_hin_ = nullptr; topn_ev_ = nullptr; topn_cap_ = 0; topn_m_ = 0;
+}
+// One launch over the logits_ rows of the listed conversations that hold logits (targets: one per listed conversation, -1 = none), the packed results' copy to the
+// pinned mirror and the event behind it.  The caller has synchronised the stream since the previous slot call's collect (the pinned inputs are free).
+void Engine::topn_slots_launch(const int *slots, int n, int top_n, const int *targets) {
+    topn_alloc();
+    int m = 0;
+    for (int i = 0; i < n; i++) if (conv_[(size_t)slots[i]].has_logits) { topn_hin_[m] = slots[i]; topn_hin_[MAX_CONVERSATIONS + m] = targets ? targets[i] : -1; topn_map_[m] = i; m++; }
+    topn_m_ = m;
+    if (!m) return;
+    const int V = (int)llm_.n_vocab;
+    HIP_CHECK(hipMemcpyAsync(topn_in_, topn_hin_, 2 * MAX_CONVERSATIONS * 4, hipMemcpyHostToDevice, stream_));
+    int *ids = topn_d_; float *lp = reinterpret_cast<float *>(topn_d_ + (size_t)m * top_n); int *rk = topn_d_ + 2 * (size_t)m * top_n; float *tlp = reinterpret_cast<float *>(rk + m);
+    if (!launch_topn_rows(logits_, V, V, m, topn_in_, top_n, topn_in_ + MAX_CONVERSATIONS, ids, lp, rk, tlp, stream_)) throw HipError{hipErrorInvalidValue, "top-N launch refused", __FILE__, __LINE__};
+    HIP_CHECK(hipMemcpyAsync(topn_h_, topn_d_, (size_t)m * (2 * top_n + 2) * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipEventRecord(topn_ev_, stream_));
+}
+// Waits for that copy and hands the rows out in slot-list order; a conversation that held no logits: ids -1, log-probabilities 0, rank -1.
+void Engine::topn_slots_collect(int n, int top_n, int *top_ids, float *top_lp, float *logprob, int *rank) {
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < top_n; j++) { top_ids[(size_t)i * top_n + j] = -1; top_lp[(size_t)i * top_n + j] = 0.0f; }
+        if (logprob) logprob[i] = 0.0f;
+        if (rank) rank[i] = -1;
+    }
+    const int m = topn_m_;
+    topn_m_ = 0;
+    if (!m) return;
+    HIP_CHECK(hipEventSynchronize(topn_ev_));
+    const int *ids = topn_h_, *rk = topn_h_ + 2 * (size_t)m * top_n;
+    const float *lp = reinterpret_cast<const float *>(topn_h_ + (size_t)m * top_n), *tlp = reinterpret_cast<const float *>(rk + m);
+    for (int r = 0; r < m; r++) {
+        const int i = topn_map_[r];
+        memcpy(top_ids + (size_t)i * top_n, ids + (size_t)r * top_n, (size_t)top_n * 4); memcpy(top_lp + (size_t)i * top_n, lp + (size_t)r * top_n, (size_t)top_n * 4);
+        if (logprob) logprob[i] = tlp[r];
+        if (rank) rank[i] = rk[r];
+    }
+}
+int Engine::top_logprobs(const int *slots, int n, int top_n, const int *targets, int *top_ids, float *top_lp, float *logprob, int *rank) {
+    auto fail = [](const std::string &what) { set_last_error("top_logprobs: " + what); return 1; };
+    const int S = (int)conv_.size(), V = (int)llm_.n_vocab;
+    if (!slots || n < 1 || n > S) return fail("bad slot list");
+    bool seen[MAX_CONVERSATIONS] = {false};
+    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return fail("conversations must be distinct and in range"); seen[slots[i]] = true; }
+    if (!top_ids || !top_lp) return fail("top_ids_out and top_logprobs_out are required");
+    if (top_n < 1 || top_n > TOPN_MAX || top_n > V) return fail("top_n outside 1 .. min(64, n_vocab)");
+    if (targets) for (int i = 0; i < n; i++) if (targets[i] < -1 || targets[i] >= V) return fail("target id out of range");
+    if (weights_missing()) return fail(last_error());
+    if (prefill_batch(slots, n)) return fail("the queued rows could not be evaluated: " + last_error());
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    topn_slots_launch(slots, n, top_n, targets);
+    topn_slots_collect(n, top_n, top_ids, top_lp, logprob, rank);
+    return 0;
+}
+int Engine::decode_batch_top(const int *slots, int n, const SampleParams &p, int *ids_out, const TopOut &top) {
+    auto fail = [](const std::string &what) { set_last_error("end_chat_batch_top: " + what); return 1; };
+    const int S = (int)conv_.size(), V = (int)llm_.n_vocab;
+    if (!slots || n < 1 || n > S) return fail("bad slot list");
+    bool seen[MAX_CONVERSATIONS] = {false};
+    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return fail("conversations must be distinct and in range"); seen[slots[i]] = true; }
+    if (!ids_out || !top.top_ids || !top.top_lp || !top.logprob || !top.rank) return fail("ids_out, logprob_out, rank_out, top_ids_out and top_logprobs_out are required");
+    if (top.top_n < 1 || top.top_n > TOPN_MAX || top.top_n > V) return fail("top_n outside 1 .. min(64, n_vocab)");
+    if (weights_missing()) return fail(last_error());
+    if (decode_batch(slots, n, p, ids_out, nullptr, &top)) return fail(last_error());
     return 0;
 }
 int Engine::score_batch(const int *slots, int n, const int *tokens, const int *counts, float *logprob, int *greedy, float *greedy_logprob) {

@@ -97,7 +97,9 @@ public:
     // the token sampled for slots[i]; a conversation whose context is full is sampled but not advanced (the reference discards the error too).
     // forced != null: the step evaluates forced[i] for slots[i] instead of the token it sampled (teacher forcing: tests / bench parity legs compare every step's logits with
     // an oracle conversation that is fed the same ids); ids_out still reports what the conversation's own logits chose
-    int decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced = nullptr);
+    // top (decode_batch_top below): also report the distribution every id was drawn from
+    struct TopOut { int top_n = 0; int *top_ids = nullptr; float *top_lp = nullptr, *logprob = nullptr; int *rank = nullptr; };
+    int decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced = nullptr, const TopOut *top = nullptr);
     // the queued prompt rows of `n` distinct conversations, packed into chunks of <= n_batch rows, one pass over the weights per chunk.  Afterwards each is
     // where its own flush() leaves it (n_committed == n_past, queue empty, last-row logits / greedy id / feed token in its slot); one with nothing queued is
     // skipped.  0, or 1 (bad slot list, failed pass: then every listed conversation drops its queue, n_past = n_committed, like a failed flush).  Parity
@@ -151,6 +153,22 @@ public:
     // already evaluated or shifted by then keep that state, as after a failed prefill_batch.
     int score_batch(const int *slots, int n_slots, const int *tokens, const int *counts, float *logprob, int *greedy, float *greedy_logprob);
 
+    // ---- top-N alternatives (k_topn_rows): the first top_n (1 .. TOPN_MAX, <= n_vocab) tokens of a distribution in the order "logit descending, equal logits by
+    // ascending id", their log-probabilities (log-softmax of the RAW logits, whatever the sampling parameters), and the rank of a given token in that order.  Every
+    // check comes before anything runs; a refusal returns 1 with last_error "<name>: ..." and changes nothing.
+    // what each listed DISTINCT conversation would say next: queued rows first (prefill_batch(slots, n)), then one launch over the listed rows of logits_, one copy
+    // back, one synchronise.  targets (may be null; -1 = none): logprob / rank (may be null) describe targets[i].  A conversation without current logits: ids -1,
+    // log-probabilities 0, rank -1.  Position, logits, greedy / feed token, the sampler's generator and mirostat state are untouched.
+    int top_logprobs(const int *slots, int n, int top_n, const int *targets, int *top_ids, float *top_lp, float *logprob, int *rank);
+    // decode_batch that also reports, per listed conversation (one sampled but not advanced included), the sampled id's log-probability and rank and the top_n
+    // alternatives of the distribution it was drawn from: the kernel runs on the n logits_ rows after the sampling and before the weight pass (one in-order stream),
+    // its copy back is queued before the step and awaited after the step is launched.  Conversations, ids and sampler draws are decode_batch's.
+    int decode_batch_top(const int *slots, int n, const SampleParams &p, int *ids_out, const TopOut &top);
+    // score_tokens with the rank of every given token and the alternatives of the distribution it is drawn from (entry indexing as score_tokens; entry 0 without
+    // logits: logprob 0, rank -1, ids -1, log-probabilities 0).  The same passes and the same k_logprob_rows launches as score_tokens -- logprob and the conversation
+    // afterwards are bit for bit its -- with k_topn_rows behind k_logprob_rows on every tile.
+    int score_tokens_top(const int *tokens, int n, int top_n, float *logprob, int *rank, int *top_ids, float *top_lp);
+
     // ---- measurement hooks (bench / tests)
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
     int decode_loop(int steps, int *tokens_out, float *ms_total);
@@ -183,7 +201,9 @@ private:
     // score request: while set, the pass (forward / forward_ref, plain or packed) also evaluates the output matrix on chunk rows [first, end) and runs k_logprob_rows
     // on them.  targets / logprob / greedy / greedy_logprob: device arrays indexed by chunk row, target -1 = the row predicts nothing that was given; h_logits
     // (plain pass only): host destination of row `first`'s logits, the following rows behind it
-    struct ScoreReq { const int *targets = nullptr; float *logprob = nullptr; int *greedy = nullptr; float *greedy_logprob = nullptr; int first = 0, end = 0; float *h_logits = nullptr; };
+    // top_n > 0: k_topn_rows behind k_logprob_rows on every tile, into the top-N result block's score layout (topn_ids() ...), indexed by chunk row
+    struct ScoreReq { const int *targets = nullptr; float *logprob = nullptr; int *greedy = nullptr; float *greedy_logprob = nullptr; int first = 0, end = 0; float *h_logits = nullptr;
+                      int top_n = 0; };
     const ScoreReq *score_ = nullptr;
     // the feature's own lazy allocation (first scoring call; freed with the context): [SCORE_ROWS][n_vocab] logits, and [score_cap_] targets / results -- one per chunk
     // row, then one per conversation for entry 0
@@ -191,7 +211,22 @@ private:
     void score_alloc();
     void score_free();
     void score_rows(hipStream_t s);
-    void score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out);
+    void score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top = nullptr);
+    int score_tokens_impl(const char *name, const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top);
+    // the top-N feature's own lazy allocation (first *_top / top_logprobs call; freed with the context): one device block of topn_cap_ * (2 TOPN_MAX + 2) words and its
+    // pinned mirror, the slot calls' inputs (row index, target per listed conversation) and the event their copy back is awaited on.  Score passes lay the block out
+    // as ids [cap][top_n] | log-probabilities at cap * TOPN_MAX | rank at 2 cap TOPN_MAX | target log-probability behind it; the slot calls pack m rows' ids,
+    // log-probabilities, ranks and target log-probabilities back to back from word 0, so that one copy fetches them
+    int *topn_d_ = nullptr, *topn_h_ = nullptr, *topn_in_ = nullptr, *topn_hin_ = nullptr; int topn_cap_ = 0; hipEvent_t topn_ev_ = nullptr;
+    int topn_map_[MAX_CONVERSATIONS], topn_m_ = 0;                        // the launched rows of the slot call in flight: [row] -> index in the slot list
+    int *topn_ids() const { return topn_d_; }
+    float *topn_lp() const { return reinterpret_cast<float *>(topn_d_ + (size_t)topn_cap_ * TOPN_MAX); }
+    int *topn_rank() const { return topn_d_ + 2 * (size_t)topn_cap_ * TOPN_MAX; }
+    float *topn_tlp() const { return reinterpret_cast<float *>(topn_rank() + topn_cap_); }
+    void topn_alloc();
+    void topn_free();
+    void topn_slots_launch(const int *slots, int n, int top_n, const int *targets);
+    void topn_slots_collect(int n, int top_n, int *top_ids, float *top_lp, float *logprob, int *rank);
     struct ScoreOut { int off[MAX_CONVERSATIONS]; float *logprob; int *greedy; float *greedy_logprob; };   // score_batch: [slot] -> the conversation's first output entry
     int prefill_packed(const int *slots, int n, const ScoreOut *so = nullptr);
     void attn_segments(const SegChunk &sg, __half *kc, __half *vc, bool want_h, bool *att_in_xh, hipStream_t s);

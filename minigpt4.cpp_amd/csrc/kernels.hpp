@@ -176,6 +176,14 @@ void launch_gather_rows(const float *src, const int *idx, int n, int E, float *d
 // scoring, one workgroup per row r of `logits` (row stride ld >= n_vocab floats, any alignment): greedy[r] = first argmax, greedy_logprob[r] = its log-softmax,
 // logprob[r] = log softmax(row)[targets[r]] (natural logarithm; the maximum is subtracted before exp), or 0 when targets[r] == -1
 void launch_logprob_rows(const float *logits, int ld, int n_vocab, int rows, const int *targets, float *logprob, int *greedy, float *greedy_logprob, hipStream_t s);
+// top-N alternatives, one workgroup per row r of `logits` (read at logits + (row_index ? row_index[r] : r) * ld; any 4-byte alignment, duplicates allowed):
+// ids[r][0, top_n) = the first top_n tokens in the order "logit descending, equal logits (float equality: -0 and +0 tie) by ascending id", logprobs[r][j] = the
+// log-softmax of ids[r][j] -- bit for bit what launch_logprob_rows reports for that token as the row's target --, rank[r] = how many tokens sort before targets[r]
+// (-1 without a target), target_logprob[r] = launch_logprob_rows' logprob (0 without a target).  Outputs are packed [rows][top_n].  The number of sweeps over a row
+// does not depend on top_n or on the data (llm_kernels.hip).  false + last_error: rows / n_vocab < 1, ld < n_vocab, top_n outside [1, min(TOPN_MAX, n_vocab)]
+constexpr int TOPN_MAX = 64;   // one wavefront of candidates above the threshold; covers the reference's default top-k of 40
+bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const int *row_index, int top_n, const int *targets, int *ids, float *logprobs, int *rank,
+                      float *target_logprob, hipStream_t s);
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)

@@ -3050,6 +3050,41 @@ void launch_gather_rows(const float *src, const int *idx, int n, int E, float *d
     note_kernel("k_gather_rows");
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n), dim3(256), 0, s, src, idx, E, dst);
 }
+// The row as its sweeps see it, shared by k_logprob_rows and k_topn_rows (which must report the same bits): scalar head [0, head), 16-byte body, scalar tail [tail0, n).
+struct RowSpan { const float *x; const float4 *x4; int head, n4, tail0, n; };
+__device__ __forceinline__ RowSpan row_span(const float *x, int n_vocab) {
+    RowSpan s; s.x = x; s.n = n_vocab;
+    s.head = min(n_vocab, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2);
+    s.n4 = (n_vocab - s.head) >> 2; s.tail0 = s.head + 4 * s.n4;
+    s.x4 = reinterpret_cast<const float4 *>(x + s.head);
+    return s;
+}
+// one sweep of a 256-thread workgroup: f(value, index) for every element, a thread's indices in ascending order
+template <typename F> __device__ __forceinline__ void row_sweep(const RowSpan &s, int tid, F f) {
+    if (tid < s.head) f(s.x[tid], tid);
+    for (int i = tid; i < s.n4; i += 256) { const float4 v = s.x4[i]; const int b = s.head + 4 * i; f(v.x, b); f(v.y, b + 1); f(v.z, b + 2); f(v.w, b + 3); }
+    if (s.tail0 + tid < s.n) f(s.x[s.tail0 + tid], s.tail0 + tid);
+}
+// the row's maximum and its first index, in every thread (sv, si: 4 entries of LDS)
+__device__ __forceinline__ void row_max_first(const RowSpan &s, int tid, float *sv, int *si, float &best, int &bi) {
+    best = -INFINITY; bi = 0x7FFFFFFF;
+    row_sweep(s, tid, [&](float v, int i) { argmax_combine(best, bi, v, i); });
+    argmax_wave(best, bi);
+    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+    __syncthreads();
+    best = sv[0]; bi = si[0];
+    for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]);   // every thread: the row's maximum, uniformly
+}
+// sum of exp(x - best) over the row, in every thread (ss: 4 entries of LDS): per-thread sums in sweep order, xor tree per wave, (w0 + w1) + (w2 + w3)
+__device__ __forceinline__ float row_sum_exp(const RowSpan &s, int tid, float best, float *ss) {
+    float sum = 0.0f;
+    row_sweep(s, tid, [&](float v, int) { sum += expf(v - best); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((tid & 63) == 0) ss[tid >> 6] = sum;
+    __syncthreads();
+    return (ss[0] + ss[1]) + (ss[2] + ss[3]);
+}
 // Scoring (Engine::score_tokens): one workgroup per logits row.  Sweep 1: the row's maximum and its first index; sweep 2: sum of exp(x - max) (the row was just
 // written, both sweeps hit L2).  logprob = (x[target] - max) - log(sum): the maximum's own term is exp(0) = 1, so sum >= 1 and no single exp is ever passed to log.
 // Rows start at logits + r * ld with any ld >= n_vocab (32001 floats: not 16-byte aligned from row 1 on), so each row takes its own scalar head up to the first
@@ -3058,32 +3093,13 @@ __global__ __launch_bounds__(256) void k_logprob_rows(const float *__restrict__ 
                                                       int *__restrict__ greedy, float *__restrict__ greedy_logprob) {
     const int r = blockIdx.x, tid = threadIdx.x;
     const float *x = logits + (size_t)r * ld;
-    const int head = min(n_vocab, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2);
-    const int n4 = (n_vocab - head) >> 2, tail0 = head + 4 * n4;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x + head);
-    float best = -INFINITY; int bi = 0x7FFFFFFF;
-    if (tid < head) argmax_combine(best, bi, x[tid], tid);
-    for (int i = tid; i < n4; i += 256) {
-        const float4 v = x4[i]; const int b = head + 4 * i;
-        argmax_combine(best, bi, v.x, b); argmax_combine(best, bi, v.y, b + 1); argmax_combine(best, bi, v.z, b + 2); argmax_combine(best, bi, v.w, b + 3);
-    }
-    if (tail0 + tid < n_vocab) argmax_combine(best, bi, x[tail0 + tid], tail0 + tid);
+    const RowSpan sp = row_span(x, n_vocab);
     __shared__ float sv[4]; __shared__ int si[4]; __shared__ float ss[4];
-    argmax_wave(best, bi);
-    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-    __syncthreads();
-    best = sv[0]; bi = si[0];
-    for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]);   // every thread: the row's maximum, uniformly
-    float sum = 0.0f;
-    if (tid < head) sum += expf(x[tid] - best);
-    for (int i = tid; i < n4; i += 256) { const float4 v = x4[i]; sum += expf(v.x - best); sum += expf(v.y - best); sum += expf(v.z - best); sum += expf(v.w - best); }
-    if (tail0 + tid < n_vocab) sum += expf(x[tail0 + tid] - best);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-    if ((tid & 63) == 0) ss[tid >> 6] = sum;
-    __syncthreads();
+    float best; int bi;
+    row_max_first(sp, tid, sv, si, best, bi);
+    const float sum = row_sum_exp(sp, tid, best, ss);
     if (tid == 0) {
-        const float lse = logf((ss[0] + ss[1]) + (ss[2] + ss[3]));
+        const float lse = logf(sum);
         const int t = targets[r];
         greedy[r] = bi == 0x7FFFFFFF ? 0 : bi;
         greedy_logprob[r] = -lse;
@@ -3093,6 +3109,147 @@ __global__ __launch_bounds__(256) void k_logprob_rows(const float *__restrict__ 
 void launch_logprob_rows(const float *logits, int ld, int n_vocab, int rows, const int *targets, float *logprob, int *greedy, float *greedy_logprob, hipStream_t s) {
     note_kernel("k_logprob_rows");
     hipLaunchKernelGGL(k_logprob_rows, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, n_vocab, targets, logprob, greedy, greedy_logprob);
+}
+// Top-N alternatives (Engine::top_logprobs, score_tokens_top, decode_batch's report): one workgroup per logits row, the first top_n tokens in the order "logit
+// descending, equal logits by ascending id" (sampler.cpp's sort_desc_by_logit), their log-softmax -- the bits k_logprob_rows reports: row_max_first / row_sum_exp
+// and the same (x - max) - log(sum) -- and the rank of targets[r] in that order.  The selection works on an order-preserving 32-bit key (-0 canonicalised, so -0 and
+// +0 tie) and never sorts the row.  SWEEPS over the row: 7 at the most, whatever top_n and whatever the data -- maximum, sum of exponentials, three histogram levels
+// (11 + 11 + 10 key bits in 8 KB of LDS) that find the exact key T of the top_n-th token, one collecting sweep (keys above T: fewer than top_n; keys equal to T:
+// the first 192 that arrive; the target's rank), and, only when more than 192 keys equal T, a scan in id order that takes the lowest ids among them and stops when
+// it has them (7-level or all-equal rows; at most one more sweep).  An all-equal row does not serialise on one LDS word: a histogram add peels the lanes that
+// share the first active lane's bin into one atomic, the tie list takes one atomic per wave.  The <= 256 candidates are then placed by counting predecessors.
+// Logits are finite (NaN / infinities: unspecified).  Nothing beyond n_vocab floats of a row is read.
+__device__ __forceinline__ unsigned topn_key(float v) {
+    const unsigned u = __float_as_uint(v == 0.0f ? 0.0f : v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);                       // ascending in the float's value
+}
+__device__ __forceinline__ void topn_hist_add(unsigned *hist, bool take, unsigned bin, int lane) {
+    if (take) {
+        const unsigned long long m = __ballot(1);
+        const int leader = __ffsll((long long)m) - 1;
+        const unsigned b0 = (unsigned)__shfl((int)bin, leader);
+        const unsigned long long same = __ballot(bin == b0);
+        if (bin != b0) atomicAdd(&hist[bin], 1u);
+        else if (lane == leader) atomicAdd(&hist[b0], (unsigned)__popcll(same));
+    }
+}
+__device__ __forceinline__ unsigned topn_wave_scan(unsigned v, int lane) {   // inclusive
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = (unsigned)__shfl_up((int)v, o); if (lane >= o) v += t; }
+    return v;
+}
+// hist[0, 256 per): the bin b, counted from the top, with above < k <= above + hist[b] (above = the count in the bins over b); uniform in every thread
+__device__ __forceinline__ void topn_select(const unsigned *hist, int per, unsigned k, int tid, unsigned *sw, unsigned *sres, unsigned &bin, unsigned &above) {
+    const int nb = per * 256, lane = tid & 63, top = nb - 1 - tid * per;      // this thread's bins: top, top - 1, ..., top - per + 1
+    unsigned own = 0;
+    for (int j = 0; j < per; j++) own += hist[top - j];
+    const unsigned inc = topn_wave_scan(own, lane);
+    if (lane == 63) sw[tid >> 6] = inc;
+    __syncthreads();
+    unsigned before = inc - own;
+    for (int w = 0; w < (tid >> 6); w++) before += sw[w];
+    if (before < k && k <= before + own) {                                    // exactly one thread (the bins hold at least k)
+        unsigned a = before;
+        for (int j = 0; j < per; j++) { const unsigned h = hist[top - j]; if (k <= a + h) { sres[0] = (unsigned)(top - j); sres[1] = a; break; } a += h; }
+    }
+    __syncthreads();
+    bin = sres[0]; above = sres[1];
+    __syncthreads();
+}
+__global__ __launch_bounds__(256) void k_topn_rows(const float *__restrict__ logits, int ld, int n_vocab, const int *__restrict__ row_index, int top_n,
+                                                   const int *__restrict__ targets, int *__restrict__ ids, float *__restrict__ logprobs, int *__restrict__ rank,
+                                                   float *__restrict__ target_logprob) {
+    constexpr int GT = TOPN_MAX, TIES = 256 - TOPN_MAX;                      // candidate list: keys above T in [0, GT), keys equal to T in [GT, 256)
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const float *x = logits + (size_t)(row_index ? row_index[r] : r) * ld;
+    const RowSpan sp = row_span(x, n_vocab);
+    __shared__ float sv[4]; __shared__ int si[4]; __shared__ float ss[4];
+    __shared__ unsigned hist[2048], sw[4], sres[2], ckey[256];
+    __shared__ int cid[256], cnt[3];                                          // cnt: keys above T, keys equal to T, the target's rank
+    if (tid < 3) cnt[tid] = 0;
+    float best; int bi;
+    row_max_first(sp, tid, sv, si, best, bi);
+    const float lse = logf(row_sum_exp(sp, tid, best, ss));
+    // the key of the top_n-th token: three levels, each a histogram of the keys that share the prefix found so far
+    unsigned b1, b2, b3, a1, a2, a3;
+    for (int i = tid; i < 2048; i += 256) hist[i] = 0;
+    __syncthreads();
+    row_sweep(sp, tid, [&](float v, int) { topn_hist_add(hist, true, topn_key(v) >> 21, lane); });
+    __syncthreads();
+    topn_select(hist, 8, (unsigned)top_n, tid, sw, sres, b1, a1);
+    for (int i = tid; i < 2048; i += 256) hist[i] = 0;
+    __syncthreads();
+    row_sweep(sp, tid, [&](float v, int) { const unsigned k = topn_key(v); topn_hist_add(hist, (k >> 21) == b1, (k >> 10) & 2047u, lane); });
+    __syncthreads();
+    topn_select(hist, 8, (unsigned)top_n - a1, tid, sw, sres, b2, a2);
+    const unsigned p2 = (b1 << 11) | b2;
+    for (int i = tid; i < 1024; i += 256) hist[i] = 0;
+    __syncthreads();
+    row_sweep(sp, tid, [&](float v, int) { const unsigned k = topn_key(v); topn_hist_add(hist, (k >> 10) == p2, k & 1023u, lane); });
+    __syncthreads();
+    topn_select(hist, 4, (unsigned)top_n - a1 - a2, tid, sw, sres, b3, a3);
+    const unsigned T = (p2 << 10) | b3;
+    const int n_gt = (int)(a1 + a2 + a3), need = top_n - n_gt;                // n_gt < top_n keys lie above T, at least `need` >= 1 equal it
+    // the collecting sweep
+    const int t = targets[r];
+    const bool has_t = t >= 0 && t < n_vocab;
+    const unsigned tkey = has_t ? topn_key(x[t]) : 0u;
+    int before_t = 0;
+    row_sweep(sp, tid, [&](float v, int i) {
+        const unsigned k = topn_key(v);
+        if (has_t) before_t += (k > tkey || (k == tkey && i < t)) ? 1 : 0;
+        if (k > T) {
+            const int p = atomicAdd(&cnt[0], 1);
+            if (p < GT) { ckey[p] = k; cid[p] = i; }
+        } else if (k == T) {
+            const unsigned long long m = __ballot(1);
+            const int leader = __ffsll((long long)m) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&cnt[1], (int)__popcll(m));
+            const int p = __shfl(base, leader) + (int)__popcll(m & ((1ull << lane) - 1ull));
+            if (p < TIES) { ckey[GT + p] = k; cid[GT + p] = i; }
+        }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) before_t += __shfl_xor(before_t, o);
+    if (lane == 0 && before_t) atomicAdd(&cnt[2], before_t);
+    __syncthreads();
+    int n_tie = cnt[1];
+    if (n_tie > TIES) {   // (uniform) too many keys equal T to have been listed: the lowest `need` ids among them, 1024 ids per step, in id order
+        int taken = 0;
+        for (int base = 0; base < n_vocab && taken < need; base += 1024) {
+            const int i0 = base + 4 * tid;
+            unsigned m4 = 0;
+            for (int j = 0; j < 4; j++) if (i0 + j < n_vocab && topn_key(x[i0 + j]) == T) m4 |= 1u << j;
+            const unsigned c = (unsigned)__popc(m4), inc = topn_wave_scan(c, lane);
+            if (lane == 63) sw[tid >> 6] = inc;
+            __syncthreads();
+            int at = taken + (int)(inc - c);
+            for (int w = 0; w < (tid >> 6); w++) at += (int)sw[w];
+            for (int j = 0; j < 4; j++) if ((m4 >> j) & 1u) { if (at < need) { ckey[GT + at] = T; cid[GT + at] = i0 + j; } at++; }
+            taken += (int)(sw[0] + sw[1] + sw[2] + sw[3]);
+            __syncthreads();
+        }
+        n_tie = need;
+    }
+    __syncthreads();
+    // placement: a key above T goes behind the keys above it (equal ones by id); a key equal to T behind all of those and the lower ids of its own kind
+    const bool is_gt = tid < n_gt, is_tie = tid >= GT && tid < GT + n_tie;
+    if (is_gt || is_tie) {
+        const unsigned mk = ckey[tid]; const int mi = cid[tid];
+        int pos = is_gt ? 0 : n_gt;
+        if (is_gt) { for (int c = 0; c < n_gt; c++) pos += (ckey[c] > mk || (ckey[c] == mk && cid[c] < mi)) ? 1 : 0; }
+        else for (int c = GT; c < GT + n_tie; c++) pos += cid[c] < mi ? 1 : 0;
+        if (pos < top_n) { ids[(size_t)r * top_n + pos] = mi; logprobs[(size_t)r * top_n + pos] = (x[mi] - best) - lse; }
+    }
+    if (tid == 0) { rank[r] = has_t ? cnt[2] : -1; target_logprob[r] = has_t ? (x[t] - best) - lse : 0.0f; }
+}
+bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const int *row_index, int top_n, const int *targets, int *ids, float *logprobs, int *rank,
+                      float *target_logprob, hipStream_t s) {
+    if (rows < 1 || n_vocab < 1 || ld < n_vocab || top_n < 1 || top_n > TOPN_MAX || top_n > n_vocab) { set_last_error("launch_topn_rows: shape out of range"); return false; }
+    note_kernel("k_topn_rows");
+    hipLaunchKernelGGL(k_topn_rows, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, n_vocab, row_index, top_n, targets, ids, logprobs, rank, target_logprob);
+    return true;
 }
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {

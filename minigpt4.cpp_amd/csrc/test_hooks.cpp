@@ -677,6 +677,36 @@ int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, i
         return 0;
     });
 }
+// The top-N kernel (launch_topn_rows) on host logits [buf_rows][ld]: one launch, hipEvent-timed.  Everything that indexes device memory is checked here.
+int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *row_index, int rows, int top_n, const int32_t *targets, int32_t *ids_out,
+                                float *logprobs_out, int32_t *rank_out, float *target_logprob_out, float *ms_out) {
+    if (!logits || !targets || !ids_out || !logprobs_out || !rank_out || !target_logprob_out || rows < 1 || buf_rows < 1 || n_vocab < 1 || ld < n_vocab) return 1;
+    if (top_n < 1 || top_n > TOPN_MAX || top_n > n_vocab) return 1;
+    if (!row_index && rows > buf_rows) return 1;
+    for (int r = 0; r < rows; r++) {
+        if (targets[r] < -1 || targets[r] >= n_vocab) return 1;
+        if (row_index && (row_index[r] < 0 || row_index[r] >= buf_rows)) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)buf_rows * ld, R = (size_t)rows, RN = R * (size_t)top_n;
+        DevBuf dl(n * 4), dt(R * 4), dx(R * 4), di(RN * 4), dp(RN * 4), dr(R * 4), dq(R * 4);
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, targets, R * 4, hipMemcpyHostToDevice));
+        if (row_index) HIP_CHECK(hipMemcpy(dx.p, row_index, R * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(di.p, 0xFF, RN * 4)); HIP_CHECK(hipMemset(dp.p, 0xFF, RN * 4));   // an entry the kernel leaves out shows as id -1 / NaN
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;   // destroyed on every path
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_topn_rows(dl.as<float>(), ld, n_vocab, rows, row_index ? dx.as<int>() : nullptr, top_n, dt.as<int>(), di.as<int>(), dp.as<float>(), dr.as<int>(), dq.as<float>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        HIP_CHECK(hipMemcpy(ids_out, di.p, RN * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(logprobs_out, dp.p, RN * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(rank_out, dr.p, R * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(target_logprob_out, dq.p, R * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
 static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {

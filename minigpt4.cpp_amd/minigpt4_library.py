@@ -207,6 +207,12 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_prefix_cache_info.argtypes = [VOID_PTR, INT_PTR]
         L.minigpt4_amd_score_tokens.argtypes = [VOID_PTR, INT_PTR, I32, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_score_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_token_piece.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_token_piece.restype = ctypes.c_char_p
+        L.minigpt4_amd_top_logprobs.argtypes = [VOID_PTR, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR, INT_PTR]
+        L.minigpt4_amd_end_chat_batch_top.argtypes = [VOID_PTR, INT_PTR, I32, P(ctypes.c_char_p), F32, I32, F32, F32, F32, I32, F32, F32, I32, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR,
+                                                      FLOAT_PTR]
+        L.minigpt4_amd_score_tokens_top.argtypes = [VOID_PTR, INT_PTR, I32, I32, FLOAT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -231,6 +237,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_kv_copy.argtypes = [I32, I32, I32, I32, I32, INT_PTR, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
@@ -433,12 +440,23 @@ class MiniGPT4SharedLibrary:
             raise RuntimeError("prefix_cache_info failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return dict(zip(self.PREFIX_INFO_FIELDS, (int(x) for x in out)))
 
-    def amd_score_tokens(self, ctx, tokens: Sequence[int], want_logits: bool = False) -> dict:
+    def amd_score_tokens(self, ctx, tokens: Sequence[int], want_logits: bool = False, top_n: int = 0) -> dict:
         """Append `tokens` to the selected conversation and evaluate them like amd_eval_tokens + amd_logits (same state afterwards), reporting per token the
         log-probability the model gave it.  Entry i describes the distribution tokens[i] is drawn from (entry 0: the conversation's logits from before the call; none:
-        logprob 0, greedy -1).  dict(logprob [n] f32, greedy [n] i32, greedy_logprob [n] f32[, logits [n][n_vocab] f32]).  include/minigpt4_amd.h"""
+        logprob 0, greedy -1).  dict(logprob [n] f32, greedy [n] i32, greedy_logprob [n] f32[, logits [n][n_vocab] f32]).  top_n > 0 (minigpt4_amd_score_tokens_top;
+        not together with want_logits) adds rank [n] i32 (how many tokens the model preferred to tokens[i]; -1 without a distribution), top_ids [n][top_n] i32 and
+        top_logprobs [n][top_n] f32 (logit descending, equal logits by ascending id); greedy / greedy_logprob are then column 0.  include/minigpt4_amd.h"""
         t = np.ascontiguousarray(tokens, np.int32)
         n = len(t)
+        if top_n:
+            if want_logits:
+                raise ValueError("amd_score_tokens: top_n > 0 and want_logits=True exclude each other")
+            lp, rk = np.zeros(n, np.float32), np.zeros(n, np.int32)
+            ti, tl = np.zeros((n, max(int(top_n), 1)), np.int32), np.zeros((n, max(int(top_n), 1)), np.float32)
+            if self.library.minigpt4_amd_score_tokens_top(ctx.ptr, t.ctypes.data_as(INT_PTR), n, int(top_n), lp.ctypes.data_as(FLOAT_PTR), rk.ctypes.data_as(INT_PTR),
+                                                          ti.ctypes.data_as(INT_PTR), tl.ctypes.data_as(FLOAT_PTR)):
+                raise RuntimeError("score_tokens_top failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+            return dict(logprob=lp, greedy=ti[:, 0].copy(), greedy_logprob=tl[:, 0].copy(), rank=rk, top_ids=ti, top_logprobs=tl)
         lp, gr, glp = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.float32)
         lg = np.zeros((n, self.library.minigpt4_amd_n_vocab(ctx.ptr)), np.float32) if want_logits else None
         if self.library.minigpt4_amd_score_tokens(ctx.ptr, t.ctypes.data_as(INT_PTR), n, lp.ctypes.data_as(FLOAT_PTR), gr.ctypes.data_as(INT_PTR), glp.ctypes.data_as(FLOAT_PTR),
@@ -448,6 +466,41 @@ class MiniGPT4SharedLibrary:
         if want_logits:
             out["logits"] = lg
         return out
+
+    def amd_token_piece(self, ctx, token_id: int) -> Optional[str]:
+        """The text of one token id, as minigpt4_end_chat returns it ("</s>" for id 2); None for an id outside the vocabulary."""
+        p = self.library.minigpt4_amd_token_piece(ctx.ptr, int(token_id))
+        return None if p is None else p.decode("utf-8", errors="replace")
+
+    def amd_top_logprobs(self, ctx, slots: Sequence[int], top_n: int = 5, targets: Optional[Sequence[int]] = None) -> dict:
+        """What each listed (distinct) conversation would say next, without advancing anything: queued rows are evaluated first (as amd_prefill_batch does), then
+        dict(top_ids [n][top_n] i32, top_logprobs [n][top_n] f32, logprob [n] f32, rank [n] i32) -- the last two describe targets[i] (None / -1: logprob 0, rank -1).
+        A conversation without current logits gets ids -1, log-probabilities 0, rank -1.  include/minigpt4_amd.h"""
+        sl = np.ascontiguousarray(slots, np.int32)
+        n, k = len(sl), max(int(top_n), 1)
+        tg = None if targets is None else np.ascontiguousarray(targets, np.int32)
+        if tg is not None and tg.shape != (n,):
+            raise RuntimeError("top_logprobs failed: top_logprobs: one target per slot is required")
+        ti, tl, lp, rk = np.zeros((max(n, 1), k), np.int32), np.zeros((max(n, 1), k), np.float32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
+        if self.library.minigpt4_amd_top_logprobs(ctx.ptr, sl.ctypes.data_as(INT_PTR), n, int(top_n), None if tg is None else tg.ctypes.data_as(INT_PTR),
+                                                  ti.ctypes.data_as(INT_PTR), tl.ctypes.data_as(FLOAT_PTR), lp.ctypes.data_as(FLOAT_PTR), rk.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("top_logprobs failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return dict(top_ids=ti[:n], top_logprobs=tl[:n], logprob=lp[:n], rank=rk[:n])
+
+    def amd_end_chat_batch_top(self, ctx, slots: Sequence[int], top_n: int = 5, temp=0.8, top_k=40, top_p=0.9, tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0,
+                               mirostat_eta=1.0) -> dict:
+        """amd_end_chat_batch that also reports what it drew from: dict(pieces [n] str, ids [n] i32, logprob [n] f32, rank [n] i32, top_ids [n][top_n] i32,
+        top_logprobs [n][top_n] f32).  Log-probabilities are those of the raw logits, whatever the sampling parameters.  include/minigpt4_amd.h"""
+        sl = np.ascontiguousarray(slots, np.int32)
+        n, k = len(sl), max(int(top_n), 1)
+        toks = (ctypes.c_char_p * max(n, 1))()
+        ids, lp, rk = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
+        ti, tl = np.zeros((max(n, 1), k), np.int32), np.zeros((max(n, 1), k), np.float32)
+        if self.library.minigpt4_amd_end_chat_batch_top(ctx.ptr, sl.ctypes.data_as(INT_PTR), n, toks, temp, top_k, top_p, tfs_z, typical_p, mirostat, mirostat_tau, mirostat_eta,
+                                                        int(top_n), ids.ctypes.data_as(INT_PTR), lp.ctypes.data_as(FLOAT_PTR), rk.ctypes.data_as(INT_PTR),
+                                                        ti.ctypes.data_as(INT_PTR), tl.ctypes.data_as(FLOAT_PTR)):
+            raise RuntimeError("end_chat_batch_top failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return dict(pieces=[(t or b"").decode("utf-8", errors="replace") for t in toks[:n]], ids=ids[:n], logprob=lp[:n], rank=rk[:n], top_ids=ti[:n], top_logprobs=tl[:n])
 
     def amd_score_batch(self, ctx, slots: Sequence[int], token_lists: Sequence[Sequence[int]]) -> List[dict]:
         """amd_score_tokens for several distinct conversations in packed passes (as amd_prefill_batch evaluates them): one dict(logprob, greedy, greedy_logprob) per
@@ -481,6 +534,28 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_logprob_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return lp, gr, glp, float(ms.value)
+
+    def amd_test_topn_rows(self, logits: np.ndarray, top_n: int, targets: Sequence[int], n_vocab: Optional[int] = None, row_index: Optional[Sequence[int]] = None):
+        """launch_topn_rows on host logits [buf_rows][ld] (n_vocab <= ld columns are read; row r = buffer row row_index[r], or r): returns (ids [rows][top_n],
+        logprobs [rows][top_n], rank [rows], target_logprob [rows], ms) -- logit descending, equal logits by ascending id; rank / target_logprob describe targets[r]
+        (-1: none)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        buf_rows, ld = lg.shape
+        nv = ld if n_vocab is None else int(n_vocab)
+        tg = np.ascontiguousarray(targets, np.int32)
+        ri = None if row_index is None else np.ascontiguousarray(row_index, np.int32)
+        rows = int(tg.shape[0])
+        assert tg.ndim == 1 and (ri is None or ri.shape == (rows,))
+        k = max(int(top_n), 1)
+        ids, lps = np.zeros((max(rows, 1), k), np.int32), np.zeros((max(rows, 1), k), np.float32)
+        rk, tlp, ms = np.zeros(max(rows, 1), np.int32), np.zeros(max(rows, 1), np.float32), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_topn_rows(lg.ctypes.data_as(FLOAT_PTR), buf_rows, nv, ld, None if ri is None else ri.ctypes.data_as(INT_PTR), rows, int(top_n),
+                                                      tg.ctypes.data_as(INT_PTR), ids.ctypes.data_as(INT_PTR), lps.ctypes.data_as(FLOAT_PTR), rk.ctypes.data_as(INT_PTR),
+                                                      tlp.ctypes.data_as(FLOAT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_topn_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return ids[:rows], lps[:rows], rk[:rows], tlp[:rows], float(ms.value)
 
     def amd_test_kv_copy(self, k: np.ndarray, v: np.ndarray, src: int, dsts: Sequence[int], n_rows: int, src_rows: int = 0):
         """launch_kv_copy on fp16 caches [n_slot][n_layer][rows][n_embd]: rows [0, n_rows) of slot `src` (src_rows > 0: of a compact [n_layer][src_rows][n_embd] copy of its

@@ -67,10 +67,14 @@ class ReplicaServer:
         return pre, [raw, pre]
 
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
-            batched_prefill: bool = False) -> List[str]:
+            batched_prefill: bool = False, logprobs: int = 0) -> List[str]:
+        """logprobs > 0: the decode loop uses `minigpt4_amd_end_chat_batch_top` (same pieces, same sampler draws) and `self.last_logprobs[i]` holds, per generated
+        token of request i (swallowed "##" pieces included), dict(id, piece, logprob, rank, top=[(piece, logprob), ...]) with `logprobs` alternatives -- the
+        log-probabilities of the raw logits, whatever temp / top_k / top_p.  The return value is the same."""
         import ctypes
         lib, ctx = self.lib, self.ctx
         answers: List[str] = [""] * len(requests)
+        self.last_logprobs = [[] for _ in requests] if logprobs > 0 else None
         for wave in plan_waves(len(requests), self.conversations):
             structs, owned = [], []
             for i in wave:
@@ -93,7 +97,15 @@ class ReplicaServer:
                 left = {slot: requests[i].max_tokens for slot, i in enumerate(wave)}
                 active = [slot for slot in range(len(wave)) if left[slot] > 0]
                 while active:
-                    pieces = lib.amd_end_chat_batch(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
+                    if logprobs > 0:
+                        step = lib.amd_end_chat_batch_top(ctx, active, top_n=logprobs, temp=temp, top_k=top_k, top_p=top_p)
+                        pieces = step["pieces"]
+                        for r, slot in enumerate(active):
+                            self.last_logprobs[wave[slot]].append(dict(
+                                id=int(step["ids"][r]), piece=pieces[r], logprob=float(step["logprob"][r]), rank=int(step["rank"][r]),
+                                top=[(lib.amd_token_piece(ctx, int(t)), float(v)) for t, v in zip(step["top_ids"][r], step["top_logprobs"][r])]))
+                    else:
+                        pieces = lib.amd_end_chat_batch(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
                     nxt = []
                     for slot, piece in zip(active, pieces):
                         left[slot] -= 1
@@ -130,7 +142,7 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     server = ReplicaServer(vision_path, llm_path, conversations=conversations, rank=rank, world=world, device=kw.get("device"),
                            **{k: v for k, v in kw.items() if k in ("n_ctx", "n_batch", "seed", "library", "verbosity", "prefix_cache")})
     try:
-        out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos")})
+        out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs")})
     finally:
         server.close()
     mapping = dict(zip(mine, out))
