@@ -709,11 +709,28 @@ void Engine::prep_rms(const float *x, const float *w, int N, int K, int mask, hi
     launch_rms_quant(x, w, N, K, act_, mask, s);
 }
 void Engine::flush_pending(hipStream_t s) { if (pend_.ks > 1) { launch_slab_flush(pend_, s); } pend_ = SlabSrc{}; }
+namespace {
+// how many matrices from W[from] on share its type and shape (one set launch serves such a run); same_shape: all n do
+int same_run(const QWeight *const *W, int n, int from) {
+    int run = 1;
+    while (from + run < n && W[from + run]->type == W[from]->type && W[from + run]->rows == W[from]->rows && W[from + run]->cols == W[from]->cols) run++;
+    return run;
+}
+bool same_shape(const QWeight *const *W, int n) { return same_run(W, n, 0) == n; }
+// up to three matrices, their outputs and the residual they share, as the set launchers take them
+struct WeightSet {
+    const QWeight *W[3]; float *Y[3]; const float *R[3]; int n = 0;
+    WeightSet(std::initializer_list<const QWeight *> Ws, std::initializer_list<float *> Ys, const float *res) {
+        for (const QWeight *w : Ws) W[n++] = w;
+        int i = 0; for (float *y : Ys) { Y[i] = y; R[i] = res; i++; }
+    }
+};
+}  // namespace
 bool Engine::mul_mat_set(const QWeight *const *W, float *const *y, const float *const *res, int n, int N, int ldy, hipStream_t s, const Prep *prep, bool fuse, bool silu_pair, const char *site, bool defer_ok, bool keep_pending) {
     struct ClearOverride { const __half *&p; ~ClearOverride() { p = nullptr; } } clear_override{xh_override_};   // valid for exactly one call
-    bool same = true;
+    const bool same = same_shape(W, n);
     int mask = 0;
-    for (int i = 0; i < n; i++) { mask |= act_mask_for(W[i]->type); if (i) same = same && W[i]->type == W[0]->type && W[i]->rows == W[0]->rows && W[i]->cols == W[0]->cols; }
+    for (int i = 0; i < n; i++) mask |= act_mask_for(W[i]->type);
     const bool v2 = N == 1 && use_v2_ && same;
     fuse = fuse && v2 && prep && matvec_prologue_supported(W[0]->type, W[0]->cols);
     silu_pair = silu_pair && v2 && n == 2 && !res && matvec_silu_pair_supported(W[0]->type, W[0]->cols) && (!fuse || prep->kind == 1);
@@ -805,12 +822,14 @@ bool Engine::mixed_qkv(const LayerW &L, hipStream_t s, bool fuse) {
 // k_attn_ref (sequential score / P.V chains), no fused prologues, no MFMA tiles.  Everything else (integer block dots, activation quantisation, fp16
 // tables, RoPE table) is shared with the fast path and exact there, so this pass is BIT-IDENTICAL to oracle/refcpu.c: logits and greedy ids
 // (tests/test_gpu_paritymode.py).  Slow by design (one wave per output).
-void Engine::forward_ref(int N, bool from_tokens, hipStream_t s, bool feed) {
+void Engine::forward_ref(const Pass &p, hipStream_t s) {
+    if (p.seg) throw HipError{hipErrorInvalidValue, "forward_ref: a packed chunk reached the parity pass (parity mode evaluates one conversation per pass)", __FILE__, __LINE__};
+    const int N = p.N;
     const int E = (int)llm_.n_embd, F = (int)llm_.n_ff(), H = (int)llm_.n_head, hd = E / H, V = (int)llm_.n_vocab;
     const size_t C = (size_t)n_ctx_, sl = (size_t)cur_;
     int *const d_npast = d_npast_ + sl, *const d_argmax = d_argmax_ + sl, *const d_feed = d_feed_ + sl;
     float *const logits = logits_ + sl * (size_t)V;
-    if (from_tokens) launch_get_rows(tok_type_, tok_raw_, E, feed ? d_feed : d_tokens_, N, x_, s);
+    launch_get_rows(tok_type_, tok_raw_, E, p.feed ? d_feed : d_tokens_, N, x_, s);
     // MINIGPT4_PARITY_TRACE=<file>: every intermediate as a record {char name[32]; int64 n; float[n]} -- the oracle writes the same sequence
     // (orc_set_trace), and tools/trace_diff.py reports the first record that differs.  Synchronises after every launch; never inside a graph capture.
     auto tr = [&](const char *what, int il, const float *p, size_t n) {
@@ -825,30 +844,17 @@ void Engine::forward_ref(int N, bool from_tokens, hipStream_t s, bool feed) {
     };
     tr("embd", -1, x_, (size_t)N * E);
     const int t_max = n_ctx_;                                              // sizes k_attn_ref's LDS rows; a captured decode step is replayed at later positions
-    // one row (decode): same-type matrices of a set in one launch of the prefetching row kernel; otherwise (prompt rows, other types) one generic
-    // launch per matrix
+    // one row (decode): same-type matrices of a set in one launch of the prefetching row kernel.  Prompt rows: the int8-MFMA kernels WITHOUT a K split
+    // add every output's per-block terms block after block -- the oracle's order (bit-identical: test_gpu_paritymode).  Whatever those refuse (other
+    // types, fewer than 5 prompt rows): the oracle-order row kernel, one generic launch per matrix
     auto ref_set = [&](std::initializer_list<const QWeight *> Ws, std::initializer_list<float *> Ys, const float *res) {
-        const QWeight *W[3]; float *Y[3]; const float *R[3]; int n = 0;
-        for (const QWeight *w : Ws) W[n++] = w;
-        n = 0; for (float *yv : Ys) { Y[n] = yv; R[n] = res; n++; }
-        int done = 0;
-        if (N == 1) {                                // split into runs of equal type / shape (wq | wk + a differently typed wv)
-            while (done < n) {
-                int run = 1; while (done + run < n && W[done + run]->type == W[done]->type && W[done + run]->rows == W[done]->rows && W[done + run]->cols == W[done]->cols) run++;
-                if (!launch_mul_mat_ref_set(W + done, Y + done, res ? R + done : nullptr, run, act_, s))
-                    for (int i = 0; i < run; i++) launch_mul_mat_ref(*W[done + i], act_, N, Y[done + i], W[done + i]->rows, res, s);
-                done += run;
-            }
-        } else {
-            // prompt rows: the int8-MFMA kernels WITHOUT a K split add every output's per-block terms block after block -- the oracle's order
-            // (bit-identical: test_gpu_paritymode); runs of equal type / shape in one launch each, anything they refuse on the oracle-order row
-            // kernels
-            while (done < n) {
-                int run = 1; while (done + run < n && W[done + run]->type == W[done]->type && W[done + run]->rows == W[done]->rows && W[done + run]->cols == W[done]->cols) run++;
-                if (!(N >= 5 && launch_mmq2_set(W + done, Y + done, res ? R + done : nullptr, run, act_, N, W[done]->rows, s, nullptr, 1)))
-                    for (int i = 0; i < run; i++) launch_mul_mat_ref(*W[done + i], act_, N, Y[done + i], W[done + i]->rows, res, s);
-                done += run;
-            }
+        const WeightSet m(Ws, Ys, res);
+        for (int done = 0, run; done < m.n; done += run) {   // split into runs of equal type / shape (wq | wk + a differently typed wv), one launch each
+            run = same_run(m.W, m.n, done);
+            const float *const *R = res ? m.R + done : nullptr;
+            const bool ok = N == 1 ? launch_mul_mat_ref_set(m.W + done, m.Y + done, R, run, act_, s)
+                                   : N >= 5 && launch_mmq2_set(m.W + done, m.Y + done, R, run, act_, N, m.W[done]->rows, s, nullptr, 1);
+            if (!ok) for (int i = 0; i < run; i++) launch_mul_mat_ref(*m.W[done + i], act_, N, m.Y[done + i], m.W[done + i]->rows, res, s);
         }
     };
     // One row without a trace (the decode step): the fast step's launch structure -- row preparation in the mat-vec prologues, wq | wk (| wv) and w1
@@ -857,15 +863,11 @@ void Engine::forward_ref(int N, bool from_tokens, hipStream_t s, bool feed) {
     const bool fused_row = N == 1 && !trace_file_;
     auto fused_set = [&](std::initializer_list<const QWeight *> Ws, std::initializer_list<float *> Ys, const float *res, int pro, const float *px, const float *pw) -> bool {
         if (!fused_row) return false;
-        const QWeight *W[3]; float *Y[3]; const float *R[3]; int n = 0;
-        for (const QWeight *w : Ws) W[n++] = w;
-        n = 0; for (float *yv : Ys) { Y[n] = yv; R[n] = res; n++; }
-        if (pro != 0 && !matvec_prologue_supported(W[0]->type, W[0]->cols)) return false;
-        bool same = true;
-        for (int i = 1; i < n; i++) same = same && W[i]->type == W[0]->type && W[i]->rows == W[0]->rows && W[i]->cols == W[0]->cols;
-        if (same) return launch_matvec_set(W, Y, res ? R : nullptr, n, act_, s, pro, px, pw, &tabs_, MATVEC_EPI_REF);
-        if (n == 3 && !res && W[1]->type == W[0]->type && W[1]->rows == W[0]->rows && W[1]->cols == W[0]->cols && W[2]->cols == W[0]->cols && (pro == 0 || pro == 1))
-            return launch_matvec_mixed(W, Y, 2, W + 2, Y + 2, 1, act_, s, pro, px, pw, MATVEC_EPI_REF);     // wq | wk + a differently typed wv
+        WeightSet m(Ws, Ys, res);
+        if (pro != 0 && !matvec_prologue_supported(m.W[0]->type, m.W[0]->cols)) return false;
+        if (same_shape(m.W, m.n)) return launch_matvec_set(m.W, m.Y, res ? m.R : nullptr, m.n, act_, s, pro, px, pw, &tabs_, MATVEC_EPI_REF);
+        if (m.n == 3 && !res && same_shape(m.W, 2) && m.W[2]->cols == m.W[0]->cols && (pro == 0 || pro == 1))
+            return launch_matvec_mixed(m.W, m.Y, 2, m.W + 2, m.Y + 2, 1, act_, s, pro, px, pw, MATVEC_EPI_REF);     // wq | wk + a differently typed wv
         return false;
     };
     for (size_t il = 0; il < layers_.size(); il++) {
@@ -894,7 +896,7 @@ void Engine::forward_ref(int N, bool from_tokens, hipStream_t s, bool feed) {
         if (!fused_set({&L.w2}, {x_}, x_, 0, nullptr, nullptr)) ref_set({&L.w2}, {x_}, x_);
         tr("x_ffn", (int)il, x_, (size_t)N * E);
     }
-    if (score_) score_rows(s);
+    if (p.score) score_rows(*p.score, s);
     if (!(N == 1 && fused_set({&output_}, {logits}, nullptr, 1, x_, norm_))) {
         launch_rms_quant(x_ + (size_t)(N - 1) * E, norm_, 1, E, act_, act_mask_for(output_.type), s, true);
         const QWeight *Wo[1] = {&output_}; float *Yo[1] = {logits};
@@ -918,21 +920,22 @@ void Engine::set_parity(bool on) {
     prefix_empty();   // the store's rows were computed in the other mode
 }
 
-// Enqueue one forward pass for N rows already described by d_tokens_ (from_tokens) or x_ (embeddings), at position *d_npast_.
-void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
+// Enqueue one forward pass for the p.N rows described by d_tokens_ (p.feed: the decode row, by d_feed_), at position *d_npast_.
+void Engine::forward(const Pass &p, hipStream_t s) {
     pend_ = SlabSrc{}; xh_override_ = nullptr;          // host-side state of a pass that threw half-way must not reach this one
-    if (parity_) { forward_ref(N, from_tokens, s, feed); return; }
+    if (parity_) { forward_ref(p, s); return; }
+    const int N = p.N;
     const int E = (int)llm_.n_embd, F = (int)llm_.n_ff(), H = (int)llm_.n_head, hd = E / H, V = (int)llm_.n_vocab;
     const size_t C = (size_t)n_ctx_, sl = (size_t)cur_;                     // everything below addresses the selected conversation's cache / scalars
     int *const d_npast = d_npast_ + sl, *const d_argmax = d_argmax_ + sl, *const d_feed = d_feed_ + sl;
     float *const logits = logits_ + sl * (size_t)V;
-    // seg_ (prefill_batch): the rows are the packed prompt rows of several conversations; only RoPE + cache append, the attention and the output rows change
-    const SegChunk *const sg = seg_;
+    // p.seg (prefill_batch): the rows are the packed prompt rows of several conversations; only RoPE + cache append, the attention and the output rows change
+    const SegChunk *const sg = p.seg;
     const size_t seq_stride = layers_.size() * C * (size_t)E;
     const bool dec = N == 1 && !sg;
     // feed: the row is the decode token kept in d_feed (greedy feedback / set by eval_chunk); otherwise the rows are described by d_tokens_ (id, or
     // -1 = an embedding row already sitting in x_) -- a chunk of exactly ONE embedding row must not pick up the stale decode token
-    if (from_tokens) { SiteScope sc(this, "embed", (double)gt_nbytes(tok_type_, (size_t)E) * N, s); launch_get_rows(tok_type_, tok_raw_, E, feed ? d_feed : d_tokens_, N, x_, s); }
+    { SiteScope sc(this, "embed", (double)gt_nbytes(tok_type_, (size_t)E) * N, s); launch_get_rows(tok_type_, tok_raw_, E, p.feed ? d_feed : d_tokens_, N, x_, s); }
     auto fz = [&](int bit) { return dec && (fuse_mask_ >> bit & 1); };
     for (size_t il = 0; il < layers_.size(); il++) {
         const LayerW &L = layers_[il];
@@ -954,7 +957,7 @@ void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
         bool att_in_xh = false;                                             // the attention kernel left fp16 rows in act_.xh
         std::optional<SiteScope> att_sc;
         if (prof_on_) att_sc.emplace(this, "attention", 4.0 * (double)E * (sg ? sg->key_rows : (double)(conv_[sl].n_committed + N)), s);
-        if (dec && attn_split_now_) launch_attn_llm_split(q_, k_, v_, kc, vc, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, attn_ws_, attn_splits_, s);
+        if (dec && p.split) launch_attn_llm_split(q_, k_, v_, kc, vc, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, attn_ws_, attn_splits_, s);
         else if (dec) launch_attn_llm(q_, k_, v_, kc, vc, 1, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, true, s);
         else {
             if (pend_.ks > 1 && pend_.n == 3 && pend_.y[0] == q_ && pend_.y[1] == k_ && pend_.y[2] == v_ && !pend_.res[0] && !pend_.res[1] && !pend_.res[2] && pend_.stride == (long long)N * E) {
@@ -1002,7 +1005,7 @@ void Engine::forward(int N, bool from_tokens, hipStream_t s, bool feed) {
         mul_mat(L.w2, N, x_, E, x_, s, paired ? &p_h : &p_silu, fz(3), "w2", !dec);
     }
     flush_pending(s);
-    if (score_) score_rows(s);
+    if (p.score) score_rows(*p.score, s);
     if (sg) {   // the last row of every conversation that ends in this chunk: one output pass over those rows, then each slot's logits / greedy id / position
         if (sg->n_end > 0) {
             launch_gather_rows(x_, sg->last, sg->n_end, E, att_, s);
@@ -1041,8 +1044,9 @@ void Engine::forward_batch(int B, hipStream_t s) {
     auto ri_serves = [&](std::initializer_list<const QWeight *> Ws) {
         if (!ri_ready_ || B < 3 || B > 4) return false;
         const QWeight *w0 = *Ws.begin();
+        if (!same_shape(Ws.begin(), (int)Ws.size())) return false;
         int groups = 0;
-        for (const QWeight *w : Ws) { if (!ri_of(w) || w->type != w0->type || w->rows != w0->rows || w->cols != w0->cols) return false; groups += w->rows / 64; }
+        for (const QWeight *w : Ws) { if (!ri_of(w)) return false; groups += w->rows / 64; }
         // w2 (13B: 80 row groups x 54 super-blocks): three or four workgroups share a row group, each a K range, last arriver adds the parts.  With
         // the first weight fetch ahead of the staging and batched staging loads the launch is 18.9 (Q5_K) / 20.8 us (Q6_K) against 22.8 / 22.4 for
         // the v_dot4 kernel at B = 4 (equal at B = 3): 1037 vs 1018 tok/s, alternating on one box (profiles/r05_batched_decode_inengine.log)
@@ -1050,11 +1054,10 @@ void Engine::forward_batch(int B, hipStream_t s) {
         return groups >= 128;
     };
     auto mm = [&](std::initializer_list<const QWeight *> Ws, std::initializer_list<float *> ys, const float *res0, int ld, const float *px = nullptr, const float *pw = nullptr) {
-        const int n = (int)Ws.size();
-        const QWeight *W[3]; float *y[3]; const float *r[3];
-        int i = 0; for (const QWeight *w : Ws) W[i++] = w;
-        i = 0; for (float *p : ys) { y[i] = p; r[i] = res0; i++; }
-        bool same = true; for (int k = 1; k < n; k++) same = same && W[k]->type == W[0]->type && W[k]->rows == W[0]->rows && W[k]->cols == W[0]->cols;
+        WeightSet m(Ws, ys, res0);
+        const int n = m.n;
+        const QWeight *const *W = m.W; float *const *y = m.Y; const float *const *r = m.R;
+        const bool same = same_shape(W, n);
         // wo at 3 / 4 rows (round 6, MINIGPT4_RI_WO): the attention rows are quantised as they are inside the MFMA launch (80 row groups: eight waves per workgroup split K, no
         // workgroup K split -- every workgroup stages the whole rows anyway)
         if (ri_wo_ && px && !pw && n == 1 && ri_ready_ && B >= 3 && B <= 4 && ri_of(W[0])) {
@@ -1101,8 +1104,7 @@ void Engine::forward_batch(int B, hipStream_t s) {
         if (ri_serves(Ws)) return !plain && ri_fuse_;
         if (batch_fuse_ == 0 || B > batch_rows_max_ || B > 4 || (batch_fuse_ < 0 && B > 2 && !plain)) return false;
         const QWeight *w0 = *Ws.begin();
-        for (const QWeight *w : Ws) if (w->type != w0->type || w->rows != w0->rows || w->cols != w0->cols) return false;
-        return matvec_rows_prologue_ok(w0->type, w0->cols);
+        return same_shape(Ws.begin(), (int)Ws.size()) && matvec_rows_prologue_ok(w0->type, w0->cols);
     };
     launch_get_rows(tok_type_, tok_raw_, E, d_btok_, B, x_, s);
     for (size_t il = 0; il < layers_.size(); il++) {
@@ -1177,6 +1179,29 @@ void Engine::forward_batch(int B, hipStream_t s) {
     launch_batch_finish(blogits_, V, B, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, s);
 }
 
+// What `enqueue` launches on stream_, captured and instantiated into `out` (null on entry).  A launcher that refuses a shape throws: the capture is ended all the same --
+// a stream left in capture mode fails every later call with a capture error instead of the real one -- and `out` stays null.
+template <class F> void Engine::capture_graph(hipGraphExec_t &out, F &&enqueue) {
+    hipGraph_t g = nullptr;
+    HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+    try { enqueue(); }
+    catch (...) { HIP_IGNORE(hipStreamEndCapture(stream_, &g)); if (g) HIP_IGNORE(hipGraphDestroy(g)); out = nullptr; throw; }
+    HIP_CHECK(hipStreamEndCapture(stream_, &g));
+    HIP_CHECK(hipGraphInstantiate(&out, g, nullptr, nullptr, 0));
+    HIP_CHECK(hipGraphDestroy(g));
+}
+size_t Engine::upload_embd_runs(const int *tok, int m, const float *embd, float *x_dst) {
+    const size_t E = llm_.n_embd;
+    size_t er = 0;
+    for (int i = 0; i < m;) {   // contiguous runs of embedding rows go straight into the residual stream
+        if (tok[i] >= 0) { i++; continue; }
+        int j = i; while (j < m && tok[j] < 0) j++;
+        HIP_CHECK(hipMemcpyAsync(x_dst + (size_t)i * E, embd + er * E, (size_t)(j - i) * E * 4, hipMemcpyHostToDevice, stream_));
+        er += (size_t)(j - i); i = j;
+    }
+    return er;
+}
+
 // Evaluate one chunk of N rows of the selected conversation at its position n_committed.  row_tok[i] >= 0: token id; -1: the next packed embedding
 // row of `embd`. LOAD_RECV: the arenas are allocated but hold nothing until the broadcast has landed and weights_received() ran -- every compute
 // entry point refuses until then (a caller that skipped the hand-over, or an inherited MINIGPT4_LOAD=recv, must get an error, not text generated from
@@ -1187,45 +1212,29 @@ bool Engine::weights_missing() const {
     MG4_ERR("%s", last_error().c_str());
     return true;
 }
-int Engine::eval_chunk(const int *row_tok, int N, const float *embd) {
+int Engine::eval_chunk(const int *row_tok, int N, const float *embd, const ScoreReq *score) {
     if (N <= 0) return 0;
     if (weights_missing()) return 1;
-    const int E = (int)llm_.n_embd;
     Conversation &cv = conv_[(size_t)cur_];
     if (logits_host_slot_ == cur_) logits_host_slot_ = -1;
     launch_set_int(d_npast_ + cur_, cv.n_committed, stream_);
     if (N == 1 && row_tok[0] >= 0) {
         launch_set_int(d_feed_ + cur_, row_tok[0], stream_);
-        // long contexts: the decode step's attention shares every head's keys between workgroups (two launches instead of one: pays from a few
-        // hundred keys on).  The choice is part of the captured graph, so a conversation that crosses the threshold gets its step re-captured (once).
-        const bool split = attn_split_t_ > 0 && cv.n_committed + 1 > attn_split_t_;
-        attn_split_now_ = split;
-        if (use_graph_ && !prof_on_ && !trace_file_ && !score_) {   // a scored row runs eagerly: the same launches as the captured step + the scoring ones
-            if (cv.graph && cv.graph_split != split) { HIP_IGNORE(hipGraphExecDestroy(cv.graph)); cv.graph = nullptr; }
-            cv.graph_split = split;
-            if (!cv.graph) {
-                hipGraph_t g = nullptr;
-                HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-                forward(1, true, stream_, true);
-                HIP_CHECK(hipStreamEndCapture(stream_, &g));
-                HIP_CHECK(hipGraphInstantiate(&cv.graph, g, nullptr, nullptr, 0));
-                HIP_CHECK(hipGraphDestroy(g));
-            }
+        const Pass p = decode_pass(cv, score);
+        if (use_graph_ && !prof_on_ && !trace_file_ && !score) {   // a scored row runs eagerly: the same launches as the captured step + the scoring ones
+            if (cv.graph && cv.graph_split != p.split) { HIP_IGNORE(hipGraphExecDestroy(cv.graph)); cv.graph = nullptr; }
+            cv.graph_split = p.split;
+            if (!cv.graph) capture_graph(cv.graph, [&] { forward(p, stream_); });
             HIP_CHECK(hipGraphLaunch(cv.graph, stream_));
         } else {
-            forward(1, true, stream_, true);
+            forward(p, stream_);
         }
     } else {
         HIP_CHECK(hipMemcpyAsync(d_tokens_, row_tok, (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-        size_t er = 0;
-        for (int i = 0; i < N;) {   // contiguous runs of embedding rows go straight into the residual stream
-            if (row_tok[i] >= 0) { i++; continue; }
-            int j = i; while (j < N && row_tok[j] < 0) j++;
-            HIP_CHECK(hipMemcpyAsync(x_ + (size_t)i * E, embd + er * E, (size_t)(j - i) * E * 4, hipMemcpyHostToDevice, stream_));
-            er += (size_t)(j - i); i = j;
-        }
+        upload_embd_runs(row_tok, N, embd, x_);
         HIP_CHECK(hipStreamSynchronize(stream_));   // the (pageable) staging vectors may be reused right after this call
-        forward(N, true, stream_);                   // k_get_rows skips rows whose id is negative
+        Pass p{N}; p.score = score;
+        forward(p, stream_);                        // k_get_rows skips rows whose id is negative
     }
     cv.n_committed += N; cv.has_logits = true;
     return 0;
@@ -1240,28 +1249,17 @@ int Engine::flush() {
     if (cv.pend_tok.empty()) return 0;
     const int E = (int)llm_.n_embd;
     // prefix store (engine.hpp): a pass that starts at position 0 takes the rows the store covers from it, and may leave its own leading token run there afterwards
-    size_t first = 0;
-    std::vector<int> cap_ids;
-    if (pfx_max_ > 0 && cv.n_committed == 0) {
-        const int run = token_run(cv), m = prefix_match(cv);
-        pfx_.rows_last = 0;
-        if (m >= PREFIX_MIN_ROWS) {
-            prefix_copy_in(&cur_, 1, m);
-            cv.n_committed = m; first = (size_t)m;                        // rows below m are token rows: no embedding row is skipped
-        }
-        if (run >= PREFIX_MIN_ROWS && m < std::min(run, pfx_max_)) cap_ids.assign(cv.pend_tok.begin(), cv.pend_tok.begin() + std::min(run, pfx_max_));
-    }
+    const PrefixPlan plan = prefix_lookup(&cur_, 1);
     size_t er = 0;
-    for (size_t i = first; i < cv.pend_tok.size(); i += (size_t)max_chunk_) {
+    for (size_t i = (size_t)plan.m[0]; i < cv.pend_tok.size(); i += (size_t)max_chunk_) {   // rows below m are token rows: no embedding row is skipped
         const int n = (int)std::min((size_t)max_chunk_, cv.pend_tok.size() - i);
         size_t ne = 0; for (int k = 0; k < n; k++) ne += cv.pend_tok[i + k] < 0;
         const int rc = eval_chunk(cv.pend_tok.data() + i, n, cv.pend_embd.data() + er * E);
         er += ne;
-        if (rc) { cv.pend_tok.clear(); cv.pend_embd.clear(); cv.n_past = cv.n_committed; return rc; }
+        if (rc) { cv.drop_queue(); return rc; }
     }
     cv.pend_tok.clear(); cv.pend_embd.clear();
-    if (first) { pfx_.hits++; pfx_.rows_reused_total += (int)first; pfx_.rows_last = (int)first; }   // counted, like the capture, only after a pass that succeeded
-    if (!cap_ids.empty()) prefix_capture(cur_, cap_ids);
+    prefix_commit(plan);
     return 0;
 }
 
@@ -1284,12 +1282,32 @@ void Engine::prefix_free() {
     if (pfx_v_) HIP_IGNORE(hipFree(pfx_v_));
     pfx_k_ = pfx_v_ = nullptr; pfx_max_ = 0; pfx_ids_.clear();
 }
-int Engine::prefix_match(const Conversation &cv) const {
-    if (pfx_max_ <= 0 || cv.n_committed != 0 || cv.pend_tok.empty()) return 0;
-    const int lim = std::min({token_run(cv), (int)pfx_ids_.size(), (int)cv.pend_tok.size() - 1});
-    int m = 0;
-    while (m < lim && cv.pend_tok[(size_t)m] == pfx_ids_[(size_t)m]) m++;
-    return m;
+// Every listed conversation that starts at position 0 with rows queued and matches is served by ONE copy launch (n_rows = the longest match: rows above a shorter match
+// are overwritten by the pass that follows on the stream); its pass then starts at row / position m
+Engine::PrefixPlan Engine::prefix_lookup(const int *slots, int n) {
+    PrefixPlan pl;
+    if (pfx_max_ <= 0) return pl;
+    for (int i = 0; i < n; i++) {
+        const Conversation &cv = conv_[(size_t)slots[i]];
+        if (cv.n_committed != 0 || cv.pend_tok.empty()) continue;
+        pl.looked = true;
+        const int run = token_run(cv), lim = std::min({run, (int)pfx_ids_.size(), (int)cv.pend_tok.size() - 1});
+        int m = 0;
+        while (m < lim && cv.pend_tok[(size_t)m] == pfx_ids_[(size_t)m]) m++;
+        if (m >= PREFIX_MIN_ROWS) { pl.m[i] = m; pl.hit[pl.n_hit++] = slots[i]; pl.rows = std::max(pl.rows, m); pl.reused += m; }
+        if (pl.cap_slot < 0 && run >= PREFIX_MIN_ROWS && m < std::min(run, pfx_max_)) { pl.cap_slot = slots[i]; pl.cap_ids.assign(cv.pend_tok.begin(), cv.pend_tok.begin() + std::min(run, pfx_max_)); }
+    }
+    if (pl.looked) pfx_.rows_last = 0;
+    if (pl.n_hit) {
+        prefix_copy_in(pl.hit, pl.n_hit, pl.rows);
+        for (int i = 0; i < n; i++) if (pl.m[i]) conv_[(size_t)slots[i]].n_committed = pl.m[i];
+    }
+    return pl;
+}
+// counted, like the capture, only after every chunk of the call succeeded
+void Engine::prefix_commit(const PrefixPlan &pl) {
+    if (pl.n_hit) { pfx_.hits += pl.n_hit; pfx_.rows_reused_total += pl.reused; pfx_.rows_last = pl.reused; }
+    if (pl.cap_slot >= 0) prefix_capture(pl.cap_slot, pl.cap_ids);
 }
 void Engine::prefix_copy_in(const int *slots, int n, int n_rows) {
     const size_t seq = layers_.size() * (size_t)n_ctx_ * llm_.n_embd;
@@ -1323,8 +1341,7 @@ int Engine::fork(int src, const int *dst, int n_dst, int n_rows) {
     }
     if (n_rows < -1 || n_rows > conv_[(size_t)src].n_past) return fail("need -1 <= n_rows <= n_past of the source");
     if (weights_missing()) return fail(last_error().c_str());
-    const int keep = cur_;
-    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; } } restore{this, keep};
+    const SelectScope restore(this);
     cur_ = src;
     Conversation &sv = conv_[(size_t)src];
     const bool whole = n_rows < 0;
@@ -1336,8 +1353,7 @@ int Engine::fork(int src, const int *dst, int n_dst, int n_rows) {
     launch_kv_copy(kc_ + (size_t)src * seq, vc_ + (size_t)src * seq, n_ctx_, d, n_dst, n_ctx_, (int)layers_.size(), (int)llm_.n_embd, rows, stream_);
     for (int i = 0; i < n_dst; i++) {
         Conversation &cv = conv_[(size_t)dst[i]];
-        cv.pend_tok.clear(); cv.pend_embd.clear();
-        cv.n_past = cv.n_committed = rows;
+        cv.n_committed = rows; cv.drop_queue();
         cv.has_logits = whole && sv.has_logits;
         if (logits_host_slot_ == dst[i]) logits_host_slot_ = -1;
         if (!whole) continue;
@@ -1423,6 +1439,7 @@ int Engine::decode_loop(int steps, int *tokens_out, float *ms_total) {
     if (steps <= 0 || cv.n_past + steps > n_ctx_) return 1;
     HIP_CHECK(hipStreamSynchronize(stream_));
     int first = h_argmax_[cur_];
+    const Pass step = decode_pass(cv);               // the eager step below is the one eval_chunk captures (or runs) here
     if (eval_chunk(&first, 1, nullptr)) return 1;   // builds the graph if needed, d_feed_[slot] <- greedy token afterwards (k_advance)
     cv.n_past += 1;
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1431,7 +1448,7 @@ int Engine::decode_loop(int steps, int *tokens_out, float *ms_total) {
     HIP_CHECK(hipEventRecord(a, stream_));
     for (int i = 1; i < steps; i++) {   // step i consumes the greedy token of step i-1, left in d_tokens_[0] by k_advance
         if (tokens_out) HIP_CHECK(hipMemcpyAsync(&tokens_out[i], d_feed_ + cur_, 4, hipMemcpyDeviceToHost, stream_));
-        if (cv.graph && use_graph_) HIP_CHECK(hipGraphLaunch(cv.graph, stream_)); else forward(1, true, stream_, true);
+        if (cv.graph && use_graph_) HIP_CHECK(hipGraphLaunch(cv.graph, stream_)); else forward(step, stream_);
     }
     HIP_CHECK(hipEventRecord(b, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1448,6 +1465,7 @@ int Engine::profile_sites(int steps, std::string &json) {
     Conversation &cv = conv_[(size_t)cur_];
     if (steps <= 0 || cv.n_past + steps > n_ctx_) return 1;
     HIP_CHECK(hipStreamSynchronize(stream_));
+    struct ProfOff { Engine *e; ~ProfOff() { e->prof_on_ = false; kernel_name_tracing(false); } } prof_off{this};   // on every exit: a failed or throwing step included
     prof_on_ = true; kernel_name_tracing(true);
     // Every step starts behind a gate kernel that holds the stream for ~8 ms: the host queues the step's ~250 launches and ~500 event records (6-7 us
     // of host time each, more than most of the kernels run) while the gate spins, and the GPU then drains them back to back -- the event pairs time
@@ -1458,14 +1476,13 @@ int Engine::profile_sites(int steps, std::string &json) {
     for (int i = 0; i < steps; i++) {
         launch_delay(8000, stream_);
         HIP_CHECK(hipEventRecord(a, stream_));
-        if (eval_chunk(&tok, 1, nullptr)) { prof_on_ = false; kernel_name_tracing(false); return 1; }
+        if (eval_chunk(&tok, 1, nullptr)) return 1;
         cv.n_past += 1;
         HIP_CHECK(hipEventRecord(b, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
         float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b)); tot += ms;
         tok = h_argmax_[cur_];
     }
-    prof_on_ = false; kernel_name_tracing(false);
     // us: dispatch begin..end (launch probes); mus: marker pairs
     struct Agg { std::string site, kernel; double us = 0, mus = 0, bytes = 0; long calls = 0; bool probed = true; };
     std::vector<Agg> agg;                                                    // first-seen order = launch order within the step
@@ -1551,14 +1568,20 @@ int Engine::select_conversation(int slot) {
     cur_ = slot;
     return 0;
 }
-int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced, const TopOut *top) {
-    if (!slots || !ids_out || n < 1 || n > (int)conv_.size()) { set_last_error("decode_batch: bad slot list"); return 1; }
-    if (weights_missing()) return 1;
+int Engine::check_slots(const int *slots, int n) const {
+    const int S = (int)conv_.size();
+    if (!slots || n < 1 || n > S) return 1;
     bool seen[MAX_CONVERSATIONS] = {false};
-    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= (int)conv_.size() || seen[slots[i]]) { set_last_error("decode_batch: conversations must be distinct and in range"); return 1; } seen[slots[i]] = true; }
+    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return 2; seen[slots[i]] = true; }
+    return 0;
+}
+int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *ids_out, const int *forced, const TopOut *top) {
+    const int bad = check_slots(slots, n);
+    if (bad == 1 || !ids_out) { set_last_error("decode_batch: bad slot list"); return 1; }
+    if (weights_missing()) return 1;
+    if (bad) { set_last_error("decode_batch: conversations must be distinct and in range"); return 1; }
     if (forced) for (int i = 0; i < n; i++) if (forced[i] < 0 || forced[i] >= (int)llm_.n_vocab) { set_last_error("decode_batch: forced token id out of range"); return 1; }
-    const int keep = cur_;
-    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; } } restore{this, keep};
+    const SelectScope restore(this);
     // 1. pending prompt rows of each conversation (its own prefill pass), then sample
     for (int i = 0; i < n; i++) { cur_ = slots[i]; ids_out[i] = sample_token(p); }
     // 2. one weight pass for the conversations that still have room
@@ -1589,14 +1612,7 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
     if (use_graph_) {   // the step for B rows as one hipGraph: the rows live in device memory, so the same graph serves every set of B conversations
         hipGraphExec_t &ge = batch_graph_[(size_t)B];
-        if (!ge) {
-            hipGraph_t g = nullptr;
-            HIP_CHECK(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-            forward_batch(B, stream_);
-            HIP_CHECK(hipStreamEndCapture(stream_, &g));
-            HIP_CHECK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-            HIP_CHECK(hipGraphDestroy(g));
-        }
+        if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_); });
         HIP_CHECK(hipGraphLaunch(ge, stream_));
     } else forward_batch(B, stream_);
     for (int r = 0; r < B; r++) {
@@ -1630,51 +1646,30 @@ void Engine::attn_segments(const SegChunk &sg, __half *kc, __half *vc, bool want
 // quantised per row), so the conversations' rows are packed like flush() packs one conversation's fragments; RoPE + cache append, the attention and the
 // output rows learn each row's conversation from the chunk's tables.  A conversation may continue in the next chunk at its advanced position.
 int Engine::prefill_batch(const int *slots, int n) {
-    if (!slots || n < 1 || n > (int)conv_.size()) { set_last_error("prefill_batch: bad slot list"); return 1; }
-    bool seen[MAX_CONVERSATIONS] = {false};
-    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= (int)conv_.size() || seen[slots[i]]) { set_last_error("prefill_batch: conversations must be distinct and in range"); return 1; } seen[slots[i]] = true; }
+    if (const int bad = check_slots(slots, n)) { set_last_error(bad == 1 ? "prefill_batch: bad slot list" : "prefill_batch: conversations must be distinct and in range"); return 1; }
     if (weights_missing()) return 1;
-    const int keep = cur_;
-    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; e->seg_ = nullptr; } } restore{this, keep};
-    auto drop_all = [&] { for (int i = 0; i < n; i++) { Conversation &cv = conv_[(size_t)slots[i]]; cv.pend_tok.clear(); cv.pend_embd.clear(); cv.n_past = cv.n_committed; } };
+    const SelectScope restore(this);
     try {
         // oracle-order arithmetic (parity mode) and the parity trace exist for the single-conversation pass only: one flush per conversation, in slot order
         if (parity_ || trace_file_) {
             int reused = 0;                                                  // rows_last of the call = the sum over its conversations, as in the packed form
-            for (int i = 0; i < n; i++) { cur_ = slots[i]; pfx_.rows_last = 0; if (flush()) { drop_all(); return 1; } reused += pfx_.rows_last; }
+            for (int i = 0; i < n; i++) { cur_ = slots[i]; pfx_.rows_last = 0; if (flush()) { drop_queues(slots, n); return 1; } reused += pfx_.rows_last; }
             if (pfx_max_ > 0) pfx_.rows_last = reused;
             return 0;
         }
-        if (prefill_packed(slots, n)) { drop_all(); return 1; }
-    } catch (...) { drop_all(); throw; }
+        if (prefill_packed(slots, n)) { drop_queues(slots, n); return 1; }
+    } catch (...) { drop_queues(slots, n); throw; }
     return 0;
 }
 int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
     const int E = (int)llm_.n_embd;
-    struct Src { int slot; size_t row, erow; int m; };                       // next queued row / embedding row of a conversation; rows taken from the prefix store
+    // prefix store (engine.hpp): a conversation the store serves starts at queue row m, its segments at pos0 = m.  A score pass neither consults nor captures the store: a
+    // copied row has no logits
+    const PrefixPlan plan = so ? PrefixPlan{} : prefix_lookup(slots, n);
+    struct Src { int slot; size_t row, erow; };                              // next queued row / embedding row of a conversation
     std::vector<Src> src;
-    for (int i = 0; i < n; i++) if (!conv_[(size_t)slots[i]].pend_tok.empty()) src.push_back({slots[i], 0, 0, 0});
+    for (int i = 0; i < n; i++) if (!conv_[(size_t)slots[i]].pend_tok.empty()) src.push_back({slots[i], (size_t)plan.m[i], 0});
     if (src.empty()) return 0;
-    // prefix store (engine.hpp): every conversation of the call that starts at position 0 and matches is served by ONE copy launch (n_rows = the longest match: rows
-    // above a shorter match are overwritten by the pass that follows on the stream); its segments then start at pos0 = m
-    std::vector<int> cap_ids; int cap_slot = -1, pfx_hits = 0, pfx_reused = 0;
-    if (pfx_max_ > 0 && !so) {   // a score pass neither consults nor captures the store: a copied row has no logits
-        int hit[MAX_CONVERSATIONS], nh = 0, rows = 0, reused = 0; bool looked = false;
-        for (Src &c : src) {
-            const Conversation &cv = conv_[(size_t)c.slot];
-            if (cv.n_committed != 0) continue;
-            looked = true;
-            const int run = token_run(cv), m = prefix_match(cv);
-            if (m >= PREFIX_MIN_ROWS) { c.m = m; hit[nh++] = c.slot; rows = std::max(rows, m); reused += m; }
-            if (cap_slot < 0 && run >= PREFIX_MIN_ROWS && m < std::min(run, pfx_max_)) { cap_slot = c.slot; cap_ids.assign(cv.pend_tok.begin(), cv.pend_tok.begin() + std::min(run, pfx_max_)); }
-        }
-        if (nh) {
-            prefix_copy_in(hit, nh, rows);
-            for (Src &c : src) if (c.m) { conv_[(size_t)c.slot].n_committed = c.m; c.row = (size_t)c.m; }
-        }
-        if (looked) pfx_.rows_last = 0;
-        pfx_hits = nh; pfx_reused = reused;
-    }
     std::vector<int> tok, tgt, dest, h_gr; std::vector<float> h_lp, h_glp;   // score pass: per packed row, the id it predicts (-1: none) and the output entry that takes its result
     size_t k = 0;
     while (k < src.size()) {
@@ -1698,12 +1693,7 @@ int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
                 const bool has = nx < cv.pend_tok.size();
                 tgt.push_back(has ? cv.pend_tok[nx] : -1); dest.push_back(has ? so->off[c.slot] + (int)nx : -1);
             }
-            for (int r = 0; r < m;) {   // contiguous runs of embedding rows go straight into the residual stream at their packed rows
-                if (cv.pend_tok[c.row + r] >= 0) { r++; continue; }
-                int j = r; while (j < m && cv.pend_tok[c.row + j] < 0) j++;
-                HIP_CHECK(hipMemcpyAsync(x_ + (size_t)(N + r) * E, cv.pend_embd.data() + c.erow * E, (size_t)(j - r) * E * 4, hipMemcpyHostToDevice, stream_));
-                c.erow += (size_t)(j - r); r = j;
-            }
+            c.erow += upload_embd_runs(cv.pend_tok.data() + c.row, m, cv.pend_embd.data() + c.erow * E, x_ + (size_t)N * E);   // at their packed rows
             c.row += (size_t)m;
             if (c.row == cv.pend_tok.size()) { fin[2 * sc.n_end] = c.slot; fin[2 * sc.n_end + 1] = pos0 + m; last[sc.n_end] = N + m - 1; sc.n_end++; k++; }
             if (logits_host_slot_ == c.slot) logits_host_slot_ = -1;
@@ -1718,23 +1708,11 @@ int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
         HIP_CHECK(hipMemcpyAsync(d_seg_, h_seg_, seg_ints() * 4, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(d_tokens_, tok.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));                            // the (pageable) queues may be changed right after this call
-        ScoreReq rq;
-        if (so) {
-            rq.first = N; rq.end = 0;
-            for (int r = 0; r < N; r++) if (tgt[(size_t)r] >= 0) { rq.first = std::min(rq.first, r); rq.end = r + 1; }
-            if (rq.end > rq.first) {   // (a chunk without a target row runs exactly as prefill_batch runs it)
-                rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_;
-                HIP_CHECK(hipMemcpyAsync(score_tgt_, tgt.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-                HIP_CHECK(hipStreamSynchronize(stream_));
-                score_ = &rq;
-            }
-        }
-        seg_ = &sc;
-        struct Clear { Engine *e; ~Clear() { e->seg_ = nullptr; e->score_ = nullptr; } } clear{this};
-        forward(N, true, stream_);                                           // k_get_rows skips rows whose id is negative
-        seg_ = nullptr;
-        if (score_) {
-            score_ = nullptr;
+        const ScoreReq rq = so ? score_request(tgt, 0, nullptr) : ScoreReq{};
+        Pass p{N}; p.seg = &sc;
+        if (rq.end > rq.first) p.score = &rq;                               // (a chunk without a target row runs exactly as prefill_batch runs it)
+        forward(p, stream_);                                                 // k_get_rows skips rows whose id is negative
+        if (p.score) {
             const size_t nr = (size_t)(rq.end - rq.first);
             h_lp.resize(nr); h_glp.resize(nr); h_gr.resize(nr);
             HIP_CHECK(hipMemcpyAsync(h_lp.data(), score_lp_ + rq.first, nr * 4, hipMemcpyDeviceToHost, stream_));
@@ -1751,9 +1729,8 @@ int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
         }
         for (int i = 0; i < sc.n_seg; i++) conv_[(size_t)sc.h_segs[4 * i]].n_committed += sc.h_segs[4 * i + 2];
     }
-    for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.pend_tok.clear(); cv.pend_embd.clear(); cv.has_logits = true; }
-    if (pfx_hits) { pfx_.hits += pfx_hits; pfx_.rows_reused_total += pfx_reused; pfx_.rows_last = pfx_reused; }   // counted only after every chunk succeeded
-    if (cap_slot >= 0) prefix_capture(cap_slot, cap_ids);
+    for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.drop_queue(); cv.has_logits = true; }
+    prefix_commit(plan);
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));   // greedy sample_token reads this copy
     return 0;
 }
@@ -1774,14 +1751,24 @@ void Engine::score_alloc() {
     } catch (...) { score_free(); throw; }
     score_cap_ = need;
 }
+Engine::ScoreReq Engine::score_request(const std::vector<int> &targets, int top_n, float *h_logits) {
+    ScoreReq rq;
+    rq.first = (int)targets.size();
+    for (int r = 0; r < (int)targets.size(); r++) if (targets[(size_t)r] >= 0) { rq.first = std::min(rq.first, r); rq.end = r + 1; }
+    if (rq.end <= rq.first) return rq;
+    HIP_CHECK(hipMemcpyAsync(score_tgt_, targets.data(), targets.size() * 4, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_;
+    rq.h_logits = h_logits; rq.top_n = top_n;
+    return rq;
+}
 void Engine::score_free() {
     for (void *p : {(void *)score_buf_, (void *)score_tgt_, (void *)score_greedy_, (void *)score_lp_, (void *)score_glp_}) if (p) HIP_IGNORE(hipFree(p));
     score_buf_ = score_lp_ = score_glp_ = nullptr; score_tgt_ = score_greedy_ = nullptr; score_cap_ = 0;
 }
 // The scored rows of the pass that is being enqueued: x_ holds every row's residual once the layers are done.  Tiles of SCORE_ROWS rows: final norm + output matrix
 // into score_buf_ (parity mode: the oracle-order preparation and mat-mul, as forward_ref's prompt rows), k_logprob_rows, the optional copy of the tile to the host.
-void Engine::score_rows(hipStream_t s) {
-    const ScoreReq &rq = *score_;
+void Engine::score_rows(const ScoreReq &rq, hipStream_t s) {
     const int E = (int)llm_.n_embd, V = (int)llm_.n_vocab;
     for (int r0 = rq.first; r0 < rq.end; r0 += SCORE_ROWS) {
         const int rows = std::min(SCORE_ROWS, rq.end - r0);
@@ -1854,25 +1841,15 @@ int Engine::score_tokens_impl(const char *name, const int *tokens, int n, float 
     if (top) topn_alloc();
     const int tn = top ? top->top_n : 0;
     score_entry0(cur_, 0, tokens[0], logprob, greedy, greedy_logprob, logits_out, top);
-    struct Clear { Engine *e; ~Clear() { e->score_ = nullptr; } } clear{this};
     std::vector<int> tgt;
     try {
         for (int i = 0; i < n; i += max_chunk_) {
             const int N = std::min(max_chunk_, n - i), nt = std::min(N, n - 1 - i);   // rows i .. i + N - 1; row j predicts tokens[j + 1]
-            ScoreReq rq;
-            if (nt > 0) {
-                tgt.assign(tokens + i + 1, tokens + i + 1 + nt); tgt.resize((size_t)N, -1);
-                HIP_CHECK(hipMemcpyAsync(score_tgt_, tgt.data(), (size_t)N * 4, hipMemcpyHostToDevice, stream_));
-                HIP_CHECK(hipStreamSynchronize(stream_));
-                rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_; rq.first = 0; rq.end = nt;
-                rq.h_logits = logits_out ? logits_out + (size_t)(i + 1) * V : nullptr;
-                rq.top_n = tn;
-                score_ = &rq;
-            }
-            const int rc = eval_chunk(tokens + i, N, nullptr);
-            score_ = nullptr;
-            if (rc) { cv.n_past = cv.n_committed; return fail("a pass failed: " + last_error()); }
-            cv.n_past = cv.n_committed;
+            tgt.assign(tokens + i + 1, tokens + i + 1 + nt); tgt.resize((size_t)N, -1);
+            const ScoreReq rq = score_request(tgt, tn, logits_out ? logits_out + (size_t)(i + 1) * V : nullptr);   // rows [0, nt); none when nt == 0
+            const int rc = eval_chunk(tokens + i, N, nullptr, rq.end > rq.first ? &rq : nullptr);
+            cv.drop_queue();                                                 // (nothing is queued: n_past = n_committed)
+            if (rc) return fail("a pass failed: " + last_error());
             if (nt > 0) {
                 HIP_CHECK(hipMemcpyAsync(logprob + i + 1, score_lp_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
                 if (greedy) HIP_CHECK(hipMemcpyAsync(greedy + i + 1, score_greedy_, (size_t)nt * 4, hipMemcpyDeviceToHost, stream_));
@@ -1886,7 +1863,7 @@ int Engine::score_tokens_impl(const char *name, const int *tokens, int n, float 
             }
         }
         HIP_CHECK(hipStreamSynchronize(stream_));
-    } catch (...) { cv.n_past = cv.n_committed; throw; }
+    } catch (...) { cv.drop_queue(); throw; }
     return 0;
 }
 // ====================================================================================================================
@@ -1950,10 +1927,8 @@ void Engine::topn_slots_collect(int n, int top_n, int *top_ids, float *top_lp, f
 }
 int Engine::top_logprobs(const int *slots, int n, int top_n, const int *targets, int *top_ids, float *top_lp, float *logprob, int *rank) {
     auto fail = [](const std::string &what) { set_last_error("top_logprobs: " + what); return 1; };
-    const int S = (int)conv_.size(), V = (int)llm_.n_vocab;
-    if (!slots || n < 1 || n > S) return fail("bad slot list");
-    bool seen[MAX_CONVERSATIONS] = {false};
-    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return fail("conversations must be distinct and in range"); seen[slots[i]] = true; }
+    const int V = (int)llm_.n_vocab;
+    if (const int bad = check_slots(slots, n)) return fail(bad == 1 ? "bad slot list" : "conversations must be distinct and in range");
     if (!top_ids || !top_lp) return fail("top_ids_out and top_logprobs_out are required");
     if (top_n < 1 || top_n > TOPN_MAX || top_n > V) return fail("top_n outside 1 .. min(64, n_vocab)");
     if (targets) for (int i = 0; i < n; i++) if (targets[i] < -1 || targets[i] >= V) return fail("target id out of range");
@@ -1966,10 +1941,8 @@ int Engine::top_logprobs(const int *slots, int n, int top_n, const int *targets,
 }
 int Engine::decode_batch_top(const int *slots, int n, const SampleParams &p, int *ids_out, const TopOut &top) {
     auto fail = [](const std::string &what) { set_last_error("end_chat_batch_top: " + what); return 1; };
-    const int S = (int)conv_.size(), V = (int)llm_.n_vocab;
-    if (!slots || n < 1 || n > S) return fail("bad slot list");
-    bool seen[MAX_CONVERSATIONS] = {false};
-    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return fail("conversations must be distinct and in range"); seen[slots[i]] = true; }
+    const int V = (int)llm_.n_vocab;
+    if (const int bad = check_slots(slots, n)) return fail(bad == 1 ? "bad slot list" : "conversations must be distinct and in range");
     if (!ids_out || !top.top_ids || !top.top_lp || !top.logprob || !top.rank) return fail("ids_out, logprob_out, rank_out, top_ids_out and top_logprobs_out are required");
     if (top.top_n < 1 || top.top_n > TOPN_MAX || top.top_n > V) return fail("top_n outside 1 .. min(64, n_vocab)");
     if (weights_missing()) return fail(last_error());
@@ -1978,10 +1951,8 @@ int Engine::decode_batch_top(const int *slots, int n, const SampleParams &p, int
 }
 int Engine::score_batch(const int *slots, int n, const int *tokens, const int *counts, float *logprob, int *greedy, float *greedy_logprob) {
     auto fail = [](const std::string &what) { set_last_error("score_batch: " + what); return 1; };
-    const int S = (int)conv_.size(), V = (int)llm_.n_vocab;
-    if (!slots || n < 1 || n > S) return fail("bad slot list");
-    bool seen[MAX_CONVERSATIONS] = {false};
-    for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= S || seen[slots[i]]) return fail("conversations must be distinct and in range"); seen[slots[i]] = true; }
+    const int V = (int)llm_.n_vocab;
+    if (const int bad = check_slots(slots, n)) return fail(bad == 1 ? "bad slot list" : "conversations must be distinct and in range");
     if (!tokens || !counts || !logprob) return fail("tokens, counts and logprob_out are required");
     size_t total = 0;
     for (int i = 0; i < n; i++) { if (counts[i] < 1) return fail("every count must be >= 1"); total += (size_t)counts[i]; }
@@ -1990,8 +1961,7 @@ int Engine::score_batch(const int *slots, int n, const int *tokens, const int *c
     for (int i = 0; i < n; i++)
         if (conv_[(size_t)slots[i]].n_past + counts[i] > n_ctx_ && !shift_allows(counts[i])) return fail("context overflow: n_past + n_tokens > n_ctx");
     if (weights_missing()) return fail(last_error());
-    const int keep = cur_;
-    struct Restore { Engine *e; int v; ~Restore() { e->cur_ = v; e->seg_ = nullptr; e->score_ = nullptr; } } restore{this, keep};
+    const SelectScope restore(this);
     if (parity_ || trace_file_) {   // as prefill_batch: the oracle-order pass is the single-conversation one
         size_t off = 0;
         for (int i = 0; i < n; i++) {
@@ -2020,11 +1990,10 @@ int Engine::score_batch(const int *slots, int n, const int *tokens, const int *c
         cv.n_past += counts[i];
         off += (size_t)counts[i];
     }
-    auto drop_all = [&] { for (int i = 0; i < n; i++) { Conversation &cv = conv_[(size_t)slots[i]]; cv.pend_tok.clear(); cv.pend_embd.clear(); cv.n_past = cv.n_committed; } };
     try {
-        if (prefill_packed(slots, n, &so)) { drop_all(); return fail("a pass failed: " + last_error()); }
+        if (prefill_packed(slots, n, &so)) { drop_queues(slots, n); return fail("a pass failed: " + last_error()); }
         HIP_CHECK(hipStreamSynchronize(stream_));
-    } catch (...) { drop_all(); throw; }
+    } catch (...) { drop_queues(slots, n); throw; }
     return 0;
 }
 

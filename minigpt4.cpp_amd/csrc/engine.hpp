@@ -62,7 +62,7 @@ public:
     int sample_token(const SampleParams &p);          // minigpt4.cpp:2425-2483
     const char *id_to_token(int id) const;            // minigpt4.cpp:2485-2497 (borrowed pointer)
     // minigpt4.cpp:2499-2502 (the selected conversation)
-    void reset() { Conversation &c = conv_[(size_t)cur_]; c.pend_tok.clear(); c.pend_embd.clear(); c.n_past = 0; c.n_committed = 0; c.has_logits = false; }
+    void reset() { Conversation &c = conv_[(size_t)cur_]; c.n_committed = 0; c.drop_queue(); c.has_logits = false; }
     void sync();
     hipStream_t stream() const { return stream_; }
     // ---- context shift (llama.cpp's answer to a full context), selected conversation: pending rows are evaluated first, then rows
@@ -185,11 +185,8 @@ private:
     int load_llm(const std::string &path);
     int load_vision(const std::string &path);
     void alloc_buffers();
-    int eval_chunk(const int *row_tok, int N, const float *embd);
-    void forward(int N, bool from_tokens, hipStream_t s, bool feed = false);   // feed: N == 1 and the token comes from d_feed_ (decode)
-    void forward_ref(int N, bool from_tokens, hipStream_t s, bool feed);   // parity mode: the oracle's accumulation order
     void forward_batch(int B, hipStream_t s);          // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]
-    // prefill_batch: one packed chunk as forward() sees it while seg_ is set (device tables in d_seg_, host copy of the segment table)
+    // prefill_batch: one packed chunk as forward() sees it through Pass::seg (device tables in d_seg_, host copy of the segment table)
     struct SegChunk {
         int n_seg = 0, n_end = 0;                      // segments; conversations whose queue ends in this chunk
         int h_segs[4 * MAX_CONVERSATIONS];            // [segment][slot, first packed row, rows, position of the first row]
@@ -197,20 +194,33 @@ private:
         const int *rows = nullptr, *fin = nullptr, *last = nullptr;   // device: [row][slot, position]; [ending][slot, end position]; [ending] last packed row
         double key_rows = 0;                           // cached rows the segments' attention reads (profile_sites)
     };
-    const SegChunk *seg_ = nullptr;
-    // score request: while set, the pass (forward / forward_ref, plain or packed) also evaluates the output matrix on chunk rows [first, end) and runs k_logprob_rows
+    // score request (Pass::score): the pass (forward / forward_ref, plain or packed) also evaluates the output matrix on chunk rows [first, end) and runs k_logprob_rows
     // on them.  targets / logprob / greedy / greedy_logprob: device arrays indexed by chunk row, target -1 = the row predicts nothing that was given; h_logits
     // (plain pass only): host destination of row `first`'s logits, the following rows behind it
     // top_n > 0: k_topn_rows behind k_logprob_rows on every tile, into the top-N result block's score layout (topn_ids() ...), indexed by chunk row
     struct ScoreReq { const int *targets = nullptr; float *logprob = nullptr; int *greedy = nullptr; float *greedy_logprob = nullptr; int first = 0, end = 0; float *h_logits = nullptr;
                       int top_n = 0; };
-    const ScoreReq *score_ = nullptr;
+    // Everything one prompt / decode pass depends on besides the selected conversation.  N rows described by d_tokens_ (id, or -1 = an embedding row already sitting in
+    // x_); feed: the decode row, its token taken from d_feed_; split: that row's attention on the key-split launches (decode_pass chooses; no other pass takes them); seg: the rows are a packed chunk of several
+    // conversations; score: also score chunk rows [first, end)
+    struct Pass { int N; bool feed = false; bool split = false; const SegChunk *seg = nullptr; const ScoreReq *score = nullptr; };
+    void forward(const Pass &p, hipStream_t s);
+    void forward_ref(const Pass &p, hipStream_t s);    // parity mode: the oracle's accumulation order (never a packed chunk)
+    int eval_chunk(const int *row_tok, int N, const float *embd, const ScoreReq *score = nullptr);
+    // the request for the chunk rows that have a target (>= 0) in `targets` (one entry per chunk row), uploaded to score_tgt_; end <= first: no row has one, no scoring
+    ScoreReq score_request(const std::vector<int> &targets, int top_n, float *h_logits);
+    size_t upload_embd_runs(const int *tok, int m, const float *embd, float *x_dst);   // the runs of embedding rows (id -1) among m rows -> their rows of x_dst; rows consumed
+    // begin capture, enqueue(), end capture, instantiate; when enqueue() throws the capture is ended (the stream must not stay in capture mode), `out` stays null
+    template <class F> void capture_graph(hipGraphExec_t &out, F &&enqueue);
+    struct SelectScope { Engine *e; int keep; explicit SelectScope(Engine *e_) : e(e_), keep(e_->cur_) {} ~SelectScope() { e->cur_ = keep; } };   // entry points that walk a slot list with cur_
+    int check_slots(const int *slots, int n) const;    // 0; 1: a bad list (null, n < 1, n > the conversations); 2: not distinct / out of range
+    void drop_queues(const int *slots, int n) { for (int i = 0; i < n; i++) conv_[(size_t)slots[i]].drop_queue(); }
     // the feature's own lazy allocation (first scoring call; freed with the context): [SCORE_ROWS][n_vocab] logits, and [score_cap_] targets / results -- one per chunk
     // row, then one per conversation for entry 0
     float *score_buf_ = nullptr, *score_lp_ = nullptr, *score_glp_ = nullptr; int *score_tgt_ = nullptr, *score_greedy_ = nullptr; int score_cap_ = 0;
     void score_alloc();
     void score_free();
-    void score_rows(hipStream_t s);
+    void score_rows(const ScoreReq &rq, hipStream_t s);
     void score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top = nullptr);
     int score_tokens_impl(const char *name, const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top);
     // the top-N feature's own lazy allocation (first *_top / top_logprobs call; freed with the context): one device block of topn_cap_ * (2 TOPN_MAX + 2) words and its
@@ -266,8 +276,12 @@ private:
         hipGraphExec_t graph = nullptr;   // decode step captured with this conversation's cache / position / token addresses
         bool graph_split = false;         // ... with the key-split attention launches (long context) or the one-workgroup-per-head kernel
         bool has_logits = false;          // its logits_ row holds the logits after its last evaluated row (not: nothing evaluated yet, after reset(), after a partial fork)
+        void drop_queue() { pend_tok.clear(); pend_embd.clear(); n_past = n_committed; }   // what a failed pass, fork and reset leave: nothing queued
     };
     std::vector<Conversation> conv_ = std::vector<Conversation>(1);
+    // The decode step of a conversation.  Long contexts: its attention shares every head's keys between workgroups (two launches instead of one: pays from a few hundred
+    // keys on).  The choice is part of the captured graph, so a conversation that crosses the threshold gets its step re-captured (once).
+    Pass decode_pass(const Conversation &cv, const ScoreReq *score = nullptr) const { Pass p{1, true, attn_split_t_ > 0 && cv.n_committed + 1 > attn_split_t_}; p.score = score; return p; }
     int cur_ = 0;
     int shift_keep_ = -1;                  // set_context_shift
     // prefix store: its own allocations (set_conversations re-takes buf_arena_, the store is only emptied then); pfx_ids_.size() = stored rows
@@ -275,7 +289,11 @@ private:
     void prefix_empty() { pfx_ids_.clear(); }
     void prefix_free();
     static int token_run(const Conversation &cv) { int r = 0; while (r < (int)cv.pend_tok.size() && cv.pend_tok[(size_t)r] >= 0) r++; return r; }
-    int prefix_match(const Conversation &cv) const;        // m of the lookup (0 when the store is off or the conversation is not at position 0)
+    // The store's part of one flush (n = 1) / packed prefill (n > 1).  prefix_lookup: m[i] = rows conversation slots[i] takes from the store (0: none, not at position 0,
+    // nothing queued, store off) -- copied in by one launch, n_committed = m[i]; prefix_commit, once every chunk succeeded: the counters, then the capture
+    struct PrefixPlan { int m[MAX_CONVERSATIONS] = {0}, hit[MAX_CONVERSATIONS], n_hit = 0, rows = 0, reused = 0; bool looked = false; int cap_slot = -1; std::vector<int> cap_ids; };
+    PrefixPlan prefix_lookup(const int *slots, int n);
+    void prefix_commit(const PrefixPlan &plan);
     void prefix_copy_in(const int *slots, int n, int n_rows);   // store -> the listed conversations' caches, one launch
     void prefix_capture(int slot, const std::vector<int> &ids);   // that conversation's rows [0, ids.size()) -> store
     bool shift_allows(int n) const { return shift_keep_ >= 0 && n <= n_ctx_ - shift_keep_; }   // the policy is on and n more rows fit behind the kept ones
@@ -323,7 +341,7 @@ private:
     bool use_graph_ = true, use_v2_ = true, attn_prefill_ = true, parity_ = false;
     FILE *trace_file_ = nullptr;       // MINIGPT4_PARITY_TRACE
     // key-split decode attention (llm_kernels.hip: k_attn_split_*)
-    void *attn_ws_ = nullptr; int attn_splits_ = 6; int attn_split_t_ = 768; bool attn_split_now_ = false; int attn_splits_forced_ = 0;
+    void *attn_ws_ = nullptr; int attn_splits_ = 6; int attn_split_t_ = 768; int attn_splits_forced_ = 0;
     int batch_rows_max_ = 4; int batch_fuse_ = -1; int n_cus_ = 256;
     // round 5: B = 2..4 rows per weight pass on the int8 matrix cores over a row-interleaved second image of the k-quant matrices (ri_kernels.hip);
     // built by set_conversations(n > 1) -- a context with one conversation never pays the memory.  MINIGPT4_RI=0: the v_dot4 multi-row mat-vec of
