@@ -176,6 +176,41 @@ MINIGPT4_API int minigpt4_amd_end_chat_batch_top(struct MiniGPT4Context *ctx, co
 MINIGPT4_API int minigpt4_amd_score_tokens_top(struct MiniGPT4Context *ctx, const int32_t *tokens, int n, int top_n, float *logprob_out, int32_t *rank_out, int32_t *top_ids_out,
                                                float *top_logprobs_out);
 
+/* ---- speculation: draft tokens verified in one weight pass; greedy lookup decoding (llama.cpp's lookup example, the `draft` family of its server) ------------------
+ * A decode step streams every weight for ONE row.  A caller who can guess the next few tokens -- from the prompt, from a smaller model in a second context, from a
+ * template -- lets the conversation put its next token AND the guesses through one pass (the batched step's mat-vec launches at 1 + n rows, an attention launch that is
+ * causal among the rows, an epilogue that decides on the device how many rows count) and keeps the guesses the pass's own logits confirm: under greedy decoding the
+ * tokens are exactly those plain decoding emits, 1 + m of them for one pass.  Each call returns 0, or 1 with "<short name>: ..." in minigpt4_amd_last_error; on a
+ * refusal of its arguments nothing has changed.
+ * minigpt4_amd_set_speculation: off (0) by default; max_draft 1 .. 7 allocates 1 + max_draft logits rows, a small result block and one captured pass per row count (at
+ * first use); 0 frees them.  Plain decoding, batched decoding and scoring pay nothing and launch nothing new either way.  At 3 and 4 rows the pass runs on the
+ * row-interleaved int8-MFMA image of the k-quant weights where the context already HAS it (minigpt4_amd_set_conversations(n > 1) builds it; it doubles those weights'
+ * memory): this call never builds it.  The setting survives minigpt4_amd_set_parity and minigpt4_amd_set_conversations; the captured passes are dropped there.
+ * minigpt4_amd_verify_draft, on the selected conversation: queued rows are evaluated first (as minigpt4_amd_get_logits does); the conversation must then have current
+ * logits.  g0 = its greedy token (what minigpt4_end_chat at temp 0 would emit).  ONE pass evaluates g0, draft[0 .. n_draft) at positions p, p + 1, ...; g[r + 1] = the
+ * first argmax of row r; m = the largest value with draft[i] == g[i + 1] for all i < m.  Afterwards ids_out[0 .. m] = g0, draft[0 .. m - 1], *n_out = 1 + m, the
+ * conversation stands at n_past = p + 1 + m with the logits, greedy token and feed token of row m, and can be sampled, scored, forked or shifted as after any
+ * evaluation.  (Cache rows above n_past hold the rejected rows: dead -- a fork copies n_past rows, the next evaluation overwrites them.)  row_greedy_out (may be NULL;
+ * 1 + n_draft entries) = g[1 ...] of every evaluated row, -1 for a row that was not evaluated.  n_draft = 0 is one greedy step.  A draft longer than the room left is
+ * cut to n_ctx - n_past - 1 rows; with no room for g0 the call follows minigpt4_amd_eval_tokens' rule: the automatic shift makes room, else 1 with "verify_draft:
+ * context full".  Refused: no context, speculation off, n_draft < 0 or > max_draft, draft NULL with n_draft > 0, ids_out / n_out NULL, an id outside [0, n_vocab), no
+ * current logits.  The sampler's generator, the mirostat state and the prefix cache are untouched.  Parity mode: one single-row oracle-order pass per row, stopping at
+ * the first mismatch -- bit-identical to plain greedy decoding, no speed-up (as minigpt4_amd_score_batch and the batched step fall back).  No key-split attention:
+ * the pass's attention is the one-workgroup-per-head form at any context length.
+ * minigpt4_amd_decode_lookup: the greedy generation loop with an n-gram drafter on the host.  History = corpus (may be empty) followed by what this call has emitted.
+ * Before each pass: the longest suffix of the history (ngram_max down to ngram_min tokens, ending in the token about to be evaluated) that occurs earlier, the most
+ * recent occurrence among equals; the draft = the tokens that followed it, cut at n_draft (1 .. max_draft), before any id 2 and at the tokens still wanted.  No match:
+ * the ordinary decode step of minigpt4_end_chat at temp 0 (its own graph, key-split attention at long contexts) -- text the drafter cannot guess costs what it costs
+ * today.  Ends after max_tokens, after emitting and evaluating </s>, or when the context is full and cannot shift.  tokens_out[max_tokens], *n_tokens;
+ * stats = {verify passes, plain steps, draft tokens sent, draft tokens accepted} (passes + steps + accepted == *n_tokens).
+ * WHICH n_draft: NOT MEASURED YET.  A pass of R = 1 + n_draft rows pays when the draft tokens it keeps per pass exceed pass_ms / plain_step_ms - 1; tools/lookup_decode.py
+ * prints that break-even per R (its table c) next to the pass and step times it follows from.  Until its log is recorded the only figure is the batched step's: four rows
+ * per pass cost 3.87 ms against 2.65 ms for one -- about 0.46 kept draft tokens of 3 to break even -- which is why the loop never drafts without a match. */
+MINIGPT4_API int minigpt4_amd_set_speculation(struct MiniGPT4Context *ctx, int max_draft);
+MINIGPT4_API int minigpt4_amd_verify_draft(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, int32_t *ids_out, int32_t *n_out, int32_t *row_greedy_out);
+MINIGPT4_API int minigpt4_amd_decode_lookup(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft,
+                                            int32_t *tokens_out, int32_t *n_tokens, int32_t stats[4]);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

@@ -138,7 +138,18 @@ MINIGPT4_API float minigpt4_amd_probe_dma(int form, int policy, int waves, int f
    6 v_bfe_u32, 7 v_cvt_f32_i32, 8 v_dot4_i32_i8, 9 v_mad_u64_u32, 10 v_lshrrev) at 1..4 waves per SIMD; < 0 without a GPU */
 MINIGPT4_API float minigpt4_amd_probe_valu(int op, int waves_per_simd, int iters);
 
+/* The verify pass's attention launch alone (csrc/llm_kernels.hip k_attn_llm_draft).  q, k, v [R][n_head * hd] fp32 raw projections; kc, vc [n_slot][n_ctx][n_head * hd]
+ * fp16 bit patterns, changed in place; the R rows belong to conversation `slot` at positions n_past .. n_past + R - 1; computed_exp != 0: the exponentials are computed
+ * (what the engine's decode step gets by default), 0: gathered from the fp16 table.  mode 0: one launch_attn_llm_draft; mode 1: R one-row launches of the batched decode
+ * attention kernel, the position advanced by one between them.  out [R][n_head * hd].  1 = refused before any device is touched (a NULL array, mode not 0 / 1, hd not
+ * 32 / 64 / 128, n_head < 1, slot outside [0, n_slot), R outside 1 .. 8, n_past < 0, n_past + R > n_ctx, n_ctx above the kernel's LDS rows), 2 = no device, 3 = HIP error */
+MINIGPT4_API int minigpt4_amd_test_attn_draft(int mode, int n_head, int hd, int n_ctx, int n_slot, int slot, int n_past, int R, int computed_exp, const float *q, const float *k,
+                                              const float *v, uint16_t *kc, uint16_t *vc, float *out);
+
 /* ---- host-only logic (no GPU needed) -------------------------------------------------------------------------------- */
+/* the n-gram drafter of minigpt4_amd_decode_lookup alone (csrc/draft.cpp): the draft for a history of n tokens, at most n_draft tokens into out; returns its length
+ * (0: no match), -1 for bad arguments (NULL history with n > 0, NULL out, n < 0, ngram_min < 1, ngram_max < ngram_min, n_draft < 0) */
+MINIGPT4_API int minigpt4_amd_test_ngram_draft(const int32_t *history, int n, int ngram_max, int ngram_min, int n_draft, int32_t *out);
 struct MiniGPT4Vocab;
 MINIGPT4_API struct MiniGPT4Vocab *minigpt4_amd_vocab_load(const char *llm_path);            /* parses hparams + vocab of a GGJT v3 file */
 MINIGPT4_API void minigpt4_amd_vocab_free(struct MiniGPT4Vocab *v);

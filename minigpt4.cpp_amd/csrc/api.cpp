@@ -336,6 +336,20 @@ int minigpt4_amd_score_tokens_top(struct MiniGPT4Context *ctx, const int32_t *to
     if (!ctx) { set_last_error("score_tokens_top: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->score_tokens_top(tokens, n, top_n, logprob_out, rank_out, top_ids_out, top_logprobs_out); });
 }
+// ---- speculation: draft tokens verified in one weight pass, greedy lookup decoding ------------------------------------------------------------
+int minigpt4_amd_set_speculation(struct MiniGPT4Context *ctx, int max_draft) {
+    if (!ctx) { set_last_error("set_speculation: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_speculation(max_draft); });
+}
+int minigpt4_amd_verify_draft(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, int32_t *ids_out, int32_t *n_out, int32_t *row_greedy_out) {
+    if (!ctx) { set_last_error("verify_draft: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->verify_draft(draft, n_draft, ids_out, n_out, row_greedy_out); });
+}
+int minigpt4_amd_decode_lookup(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int32_t *tokens_out,
+                               int32_t *n_tokens, int32_t stats[4]) {
+    if (!ctx) { set_last_error("decode_lookup: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->decode_lookup(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats); });
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

@@ -1,5 +1,6 @@
 #include "engine.hpp"
 #include "dist.hpp"
+#include "draft.hpp"
 #include "quantize.hpp"
 #include "imageio.hpp"
 
@@ -76,6 +77,7 @@ void preprocess_image_device(hipStream_t s, const uint8_t *rgb, int w, int h, fl
 void Engine::release_buffers() {
     for (Conversation &c : conv_) { if (c.graph) HIP_IGNORE(hipGraphExecDestroy(c.graph)); c.graph = nullptr; }
     for (hipGraphExec_t &g : batch_graph_) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; }
+    spec_drop_graphs();
     if (h_argmax_) HIP_IGNORE(hipHostFree(h_argmax_));
     if (h_bstage_) HIP_IGNORE(hipHostFree(h_bstage_));
     if (h_logits_) HIP_IGNORE(hipHostFree(h_logits_));
@@ -95,6 +97,7 @@ Engine::~Engine() {
     prefix_free();
     score_free();
     topn_free();
+    spec_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -916,6 +919,7 @@ void Engine::set_parity(bool on) {
     HIP_CHECK(hipStreamSynchronize(stream_));
     for (Conversation &c : conv_) { if (c.graph) HIP_IGNORE(hipGraphExecDestroy(c.graph)); c.graph = nullptr; }   // captured with the other mode's launches
     for (hipGraphExec_t &g : batch_graph_) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; }
+    spec_drop_graphs();
     parity_ = on;
     prefix_empty();   // the store's rows were computed in the other mode
 }
@@ -1027,7 +1031,9 @@ void Engine::forward(const Pass &p, hipStream_t s) {
 // One decode step for B conversations at once: row r carries token d_btok_[r] of conversation d_bslot_[r].  The weights are streamed once for the B
 // rows (k_mul_mat's 4-token tiles up to B = 4, the int8-MFMA kernels from B = 5); attention runs per row against its conversation's cache.  Same
 // arithmetic per row as forward(1): per-row activation quantisation, exact integer block dots, the same attention kernel body.
-void Engine::forward_batch(int B, hipStream_t s) {
+// verify (Engine::verify_draft): the B rows are ONE conversation's (d_bslot_[0]) at consecutive positions -- the same embedding rows and mat-vec branches; the attention
+// launch is launch_attn_llm_draft, the row logits go to spec_logits_ and the epilogue is launch_draft_finish.
+void Engine::forward_batch(int B, hipStream_t s, bool verify) {
     pend_ = SlabSrc{}; xh_override_ = nullptr;
     batch_path_ = BatchPath{}; batch_path_.rows = B;
     const int E = (int)llm_.n_embd, F = (int)llm_.n_ff(), H = (int)llm_.n_head, hd = E / H, V = (int)llm_.n_vocab;
@@ -1106,6 +1112,11 @@ void Engine::forward_batch(int B, hipStream_t s) {
         const QWeight *w0 = *Ws.begin();
         return same_shape(Ws.begin(), (int)Ws.size()) && matvec_rows_prologue_ok(w0->type, w0->cols);
     };
+    auto attn = [&](__half *kc, __half *vc) {
+        if (verify) launch_attn_llm_draft(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
+        else launch_attn_llm_batched(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
+    };
+    float *const row_logits = verify ? spec_logits_ : blogits_;
     launch_get_rows(tok_type_, tok_raw_, E, d_btok_, B, x_, s);
     for (size_t il = 0; il < layers_.size(); il++) {
         const LayerW &L = layers_[il];
@@ -1139,7 +1150,7 @@ void Engine::forward_batch(int B, hipStream_t s) {
                 else { mul_mat(L.wq, B, q_, E, nullptr, s, nullptr, false, "q"); mul_mat(L.wk, B, k_, E, nullptr, s, nullptr, false, "k"); mul_mat(L.wv, B, v_, E, nullptr, s, nullptr, false, "v"); }
             }
             flush_pending(s);
-            launch_attn_llm_batched(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
+            attn(kc, vc);
             mul_mat(L.wo, B, x_, E, x_, s, &p_att, false, "wo", true);
             if (L.w1.type == L.w3.type) { const QWeight *W2[2] = {&L.w1, &L.w3}; float *Y2[2] = {h1_, h3_}; mul_mat_set(W2, Y2, nullptr, 2, B, F, s, &p_ffn, false, false, "w1w3", true); }
             else { prep_rms(x_, L.ffn_norm, B, E, act_mask_for(L.w1.type) | act_mask_for(L.w3.type), s); mul_mat(L.w1, B, h1_, F, nullptr, s, nullptr, false, "w1"); mul_mat(L.w3, B, h3_, F, nullptr, s, nullptr, false, "w3"); }
@@ -1156,7 +1167,7 @@ void Engine::forward_batch(int B, hipStream_t s) {
             else if (L.wk.type == L.wq.type) { mm({&L.wq, &L.wk}, {q_, k_}, nullptr, E); mm({&L.wv}, {v_}, nullptr, E); }
             else { mm({&L.wq}, {q_}, nullptr, E); mm({&L.wk}, {k_}, nullptr, E); mm({&L.wv}, {v_}, nullptr, E); }
         }
-        launch_attn_llm_batched(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
+        attn(kc, vc);
         if (rows_pro({&L.wo}, true)) mm({&L.wo}, {x_}, x_, E, att_, nullptr);     // the attention output rows are quantised inside the wo launch
         else { launch_silu_mul_quant(att_, nullptr, B, E, act_, act_mask_for(L.wo.type), tabs_, s); mm({&L.wo}, {x_}, x_, E); }
         if (L.w1.type == L.w3.type && rows_pro({&L.w1, &L.w3})) mm({&L.w1, &L.w3}, {h1_, h3_}, nullptr, F, x_, L.ffn_norm);
@@ -1171,12 +1182,13 @@ void Engine::forward_batch(int B, hipStream_t s) {
         mm({&L.w2}, {x_}, x_, E);
     }
     // final norm inside the output matrix's MFMA launch
-    if (B <= batch_rows_max_ && ri_fuse_ && ri_serves({&output_})) mm({&output_}, {blogits_}, nullptr, V, x_, norm_);
+    if (B <= batch_rows_max_ && ri_fuse_ && ri_serves({&output_})) mm({&output_}, {row_logits}, nullptr, V, x_, norm_);
     else {
         prep_rms(x_, norm_, B, E, act_mask_for(output_.type), s);             // (also combines the last layer's w2 slabs when its combine was deferred)
-        mm({&output_}, {blogits_}, nullptr, V);
+        mm({&output_}, {row_logits}, nullptr, V);
     }
-    launch_batch_finish(blogits_, V, B, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, s);
+    if (verify) launch_draft_finish(spec_logits_, V, B, d_btok_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, spec_res_, s);
+    else launch_batch_finish(blogits_, V, B, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, s);
 }
 
 // What `enqueue` launches on stream_, captured and instantiated into `out` (null on entry).  A launcher that refuses a shape throws: the capture is ended all the same --
@@ -1624,6 +1636,117 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
     report();
     return 0;
+}
+
+// ---- speculation: draft tokens verified in one weight pass (engine.hpp) ----
+void Engine::spec_drop_graphs() { for (hipGraphExec_t &g : spec_graph_) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; } }
+void Engine::spec_free() {
+    spec_drop_graphs();
+    if (spec_logits_) HIP_IGNORE(hipFree(spec_logits_));
+    if (spec_res_) HIP_IGNORE(hipFree(spec_res_));
+    if (spec_hres_) HIP_IGNORE(hipHostFree(spec_hres_));
+    spec_logits_ = nullptr; spec_res_ = nullptr; spec_hres_ = nullptr; spec_max_ = 0;
+}
+int Engine::set_speculation(int max_draft) {
+    if (max_draft < 0 || max_draft > DRAFT_MAX) { set_last_error("set_speculation: max_draft must be 0 (off) ... " + std::to_string(DRAFT_MAX)); return 1; }
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    spec_free();
+    if (max_draft == 0) return 0;
+    try {
+        HIP_CHECK(hipMalloc((void **)&spec_logits_, (size_t)(max_draft + 1) * llm_.n_vocab * 4));
+        HIP_CHECK(hipMalloc((void **)&spec_res_, (1 + DRAFT_ROWS) * 4));
+        HIP_CHECK(hipHostMalloc((void **)&spec_hres_, (1 + DRAFT_ROWS) * 4, hipHostMallocDefault));
+    } catch (...) { spec_free(); throw; }
+    spec_graph_.assign((size_t)DRAFT_ROWS + 1, nullptr);
+    spec_max_ = max_draft;
+    return 0;
+}
+int Engine::verify_draft(const int *draft, int n_draft, int *ids_out, int *n_out, int *row_greedy, int *n_sent) {
+    auto refuse = [](const char *what) { set_last_error(std::string("verify_draft: ") + what); return 1; };
+    if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
+    if (n_draft < 0 || n_draft > spec_max_) return refuse("n_draft outside [0, max_draft]");
+    if (n_draft > 0 && !draft) return refuse("draft is NULL");
+    if (!ids_out || !n_out) return refuse("ids_out and n_out are required");
+    for (int i = 0; i < n_draft; i++) if (draft[i] < 0 || draft[i] >= (int)llm_.n_vocab) return refuse("draft token id out of range");
+    if (weights_missing()) return 1;
+    Conversation &cv = conv_[(size_t)cur_];
+    if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
+    if (flush()) { set_last_error("verify_draft: " + last_error()); return 1; }
+    if (!cv.has_logits) return refuse("the conversation has no current logits");
+    if (cv.n_past + 1 > n_ctx_ && make_room(1)) return refuse("context full");
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // h_argmax_ is current; h_bstage_ no longer feeds an earlier step's copy
+    const int g0 = h_argmax_[cur_], p = cv.n_committed;
+    const int R = 1 + std::min(n_draft, n_ctx_ - cv.n_past - 1);
+    if (n_sent) *n_sent = R - 1;
+    if (row_greedy) for (int r = 0; r < 1 + n_draft; r++) row_greedy[r] = -1;   // rows that were not evaluated (cut for room; parity mode: behind the first mismatch)
+    int m = 0;
+    if (parity_) {   // oracle-order arithmetic exists for the single-row pass only: one row at a time, stopping at the first mismatch -- plain greedy decoding
+        for (int r = 0; r < R; r++) {
+            const int id = r ? draft[r - 1] : g0;
+            if (eval_chunk(&id, 1, nullptr)) return 1;
+            cv.n_past += 1;
+            HIP_CHECK(hipStreamSynchronize(stream_));
+            const int g = h_argmax_[cur_];
+            if (row_greedy) row_greedy[r] = g;
+            if (r + 1 < R && draft[r] == g) m++; else break;
+        }
+    } else {
+        h_bstage_[0] = g0; for (int r = 1; r < R; r++) h_bstage_[r] = draft[r - 1];
+        h_bstage_[MAX_CONVERSATIONS] = cur_; h_bstage_[2 * MAX_CONVERSATIONS] = p;
+        HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
+        launch_draft_begin(d_npast_, d_bslot_, d_bpos_, stream_);
+        if (use_graph_) {   // one graph per row count: token ids, conversation and position live in device memory
+            hipGraphExec_t &ge = spec_graph_[(size_t)R];
+            if (!ge) capture_graph(ge, [&] { forward_batch(R, stream_, true); });
+            HIP_CHECK(hipGraphLaunch(ge, stream_));
+        } else forward_batch(R, stream_, true);
+        HIP_CHECK(hipMemcpyAsync(spec_hres_, spec_res_, (size_t)(1 + R) * 4, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));                            // the one wait of the call: m and the rows' greedy ids
+        m = spec_hres_[0];
+        if (m < 0 || m >= R) throw HipError{hipErrorUnknown, "verify_draft: the device reported an accepted count outside the pass", __FILE__, __LINE__};
+        if (row_greedy) for (int r = 0; r < R; r++) row_greedy[r] = spec_hres_[1 + r];
+        h_argmax_[cur_] = spec_hres_[1 + m];
+        cv.n_committed = p + 1 + m; cv.n_past = cv.n_committed; cv.has_logits = true;
+        if (logits_host_slot_ == cur_) logits_host_slot_ = -1;
+    }
+    ids_out[0] = g0; for (int i = 0; i < m; i++) ids_out[1 + i] = draft[i];
+    *n_out = 1 + m;
+    return 0;
+}
+int Engine::decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats) {
+    auto refuse = [](const char *what) { set_last_error(std::string("decode_lookup: ") + what); return 1; };
+    if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
+    if (n_corpus < 0 || (n_corpus > 0 && !corpus)) return refuse("bad corpus");
+    if (max_tokens < 1 || !tokens_out || !n_tokens || !stats) return refuse("max_tokens >= 1, tokens_out, n_tokens and stats are required");
+    if (ngram_min < 1 || ngram_max < ngram_min) return refuse("need 1 <= ngram_min <= ngram_max");
+    if (n_draft < 1 || n_draft > spec_max_) return refuse("n_draft outside [1, max_draft]");
+    for (int i = 0; i < n_corpus; i++) if (corpus[i] < 0 || corpus[i] >= (int)llm_.n_vocab) return refuse("corpus token id out of range");
+    if (weights_missing()) return 1;
+    Conversation &cv = conv_[(size_t)cur_];
+    if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
+    NgramDrafter drafter(ngram_max, ngram_min);
+    drafter.reset(corpus, n_corpus);
+    int n = 0, st[4] = {0, 0, 0, 0}, d[DRAFT_MAX], ids[DRAFT_ROWS];
+    *n_tokens = 0;
+    auto done = [&](int rc) { *n_tokens = n; for (int i = 0; i < 4; i++) stats[i] = st[i]; return rc; };
+    SampleParams greedy; greedy.temp = 0.0f;
+    while (n < max_tokens) {
+        const int g0 = sample_token(greedy);                                // evaluates what is queued; the token the next pass evaluates
+        if (cv.n_past + 1 > n_ctx_ && make_room(1)) break;                   // context full and no automatic shift
+        drafter.push(g0);
+        const int nd = g0 == 2 ? 0 : drafter.draft(std::min(n_draft, max_tokens - n - 1), d);
+        if (nd == 0) {                                                       // nothing to guess from: the ordinary decode step, at its ordinary cost
+            if (add_tokens({g0}, /*flush_now=*/true)) { set_last_error("decode_lookup: " + last_error()); return done(1); }
+            tokens_out[n++] = g0; st[1]++;
+        } else {
+            int got = 0, sent = 0;
+            if (verify_draft(d, nd, ids, &got, nullptr, &sent)) { set_last_error("decode_lookup: " + last_error()); return done(1); }
+            st[0]++; st[2] += sent; st[3] += got - 1;
+            for (int i = 0; i < got; i++) { tokens_out[n++] = ids[i]; if (i) drafter.push(ids[i]); }
+        }
+        if (g0 == 2) break;                                                  // </s> emitted and evaluated
+    }
+    return done(0);
 }
 
 // The segmented prompt attention of one packed chunk: one launch over every segment; when it declines (the exact-f32 kernel is selected, or the score

@@ -169,6 +169,23 @@ public:
     // afterwards are bit for bit its -- with k_topn_rows behind k_logprob_rows on every tile.
     int score_tokens_top(const int *tokens, int n, int top_n, float *logprob, int *rank, int *top_ids, float *top_lp);
 
+    // ---- speculation, greedy: one conversation puts several of its OWN rows through one weight pass.  verify_draft evaluates the rows g0, draft[0 .. n) (g0 = the
+    // selected conversation's greedy token) at consecutive positions in a verify pass of forward_batch (causal among the rows: launch_attn_llm_draft) and keeps the
+    // 1 + m rows whose tokens the pass's own logits chose: ids_out = g0, draft[0 .. m), *n_out = 1 + m, n_past = n_committed = p + 1 + m, logits / greedy / feed token
+    // those of row m.  Cache rows above n_past hold the rejected rows' keys and values: dead (fork copies n_committed rows, the next evaluation overwrites them).
+    // row_greedy (may be null, 1 + n_draft entries): the first argmax of every evaluated row, -1 for rows not evaluated (cut for room; parity mode: behind the first
+    // mismatch).  n_sent (may be null): draft rows evaluated.  Parity mode: one single-row oracle-order pass per row, stopping at the first mismatch.
+    // set_speculation allocates (1 + max_draft) logits rows, the result block and its pinned mirror, one graph slot per row count; 0 frees them.  It never builds the
+    // row-interleaved MFMA image: a context that has it (set_conversations(n > 1)) uses it at 3 and 4 rows.  The setting survives set_parity / set_conversations; the
+    // captured passes are dropped there with the batched ones.  1 + last_error "set_speculation: ..." / "verify_draft: ..." / "decode_lookup: ..." on a refusal.
+    static constexpr int DRAFT_MAX = DRAFT_ROWS - 1;
+    int set_speculation(int max_draft);
+    int verify_draft(const int *draft, int n_draft, int *ids_out, int *n_out, int *row_greedy, int *n_sent = nullptr);
+    // the greedy generation loop over an n-gram drafter (draft.hpp): history = corpus + what this call emitted; a pass with a draft where the history's suffix occurs
+    // earlier, the ordinary decode step (sample_token at temp 0 + add_tokens, its own graph, key-split attention included) where it does not.
+    // stats = {verify passes, plain steps, draft tokens sent, draft tokens accepted}
+    int decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats);
+
     // ---- measurement hooks (bench / tests)
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
     int decode_loop(int steps, int *tokens_out, float *ms_total);
@@ -185,7 +202,11 @@ private:
     int load_llm(const std::string &path);
     int load_vision(const std::string &path);
     void alloc_buffers();
-    void forward_batch(int B, hipStream_t s);          // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]
+    void forward_batch(int B, hipStream_t s, bool verify = false);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation
+    // speculation's own allocations (set_speculation; freed with the context): [1 + spec_max_][n_vocab] row logits, {m, greedy id per row} and its pinned mirror, [R] graphs
+    int spec_max_ = 0; float *spec_logits_ = nullptr; int *spec_res_ = nullptr, *spec_hres_ = nullptr; std::vector<hipGraphExec_t> spec_graph_;
+    void spec_drop_graphs();
+    void spec_free();
     // prefill_batch: one packed chunk as forward() sees it through Pass::seg (device tables in d_seg_, host copy of the segment table)
     struct SegChunk {
         int n_seg = 0, n_end = 0;                      // segments; conversations whose queue ends in this chunk

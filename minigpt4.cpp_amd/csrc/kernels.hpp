@@ -156,6 +156,16 @@ void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *k
 // per row r, slot = row_slot[r]: argmax[slot] = feed[slot] = argmax(logits[r]); slot_logits[slot] = logits[r]; n_past[slot] += 1
 void launch_batch_finish(const float *logits, int n_vocab, int B, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s);
 void launch_batch_begin(int *n_past, const int *row_slot, const int *row_pos, int B, hipStream_t s);   // n_past[row_slot[r]] = row_pos[r]
+// ---- verify pass: R <= DRAFT_ROWS rows of ONE conversation (row_slot[0]) at consecutive positions in one weight pass (Engine::verify_draft) ----
+constexpr int DRAFT_ROWS = 8;                          // the conversation's greedy token + at most 7 draft tokens
+// row t at position n_past[row_slot[0]] + t (all below n_ctx): RoPE + append of its own row, attention over the cache below the position, the pass's rows 0 .. t - 1
+// and itself.  out and the appended rows are bit for bit those of R one-row launch_attn_llm_batched calls with n_past advanced by one between them.  n_past is not written.
+void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int R, int n_head, int hd, const int *n_past, const int *row_slot,
+                           size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s);
+void launch_draft_begin(int *n_past, const int *row_slot, const int *row_pos, hipStream_t s);   // n_past[row_slot[0]] = row_pos[0]
+// res[1 + r] = first argmax of logits row r; m = leading draft tokens accepted (tok[i + 1] == res[1 + i], i < m); slot = row_slot[0]: slot_logits[slot] = logits[m],
+// argmax[slot] = feed[slot] = res[1 + m], n_past[slot] += 1 + m, res[0] = m.  res: 1 + DRAFT_ROWS ints
+void launch_draft_finish(const float *logits, int n_vocab, int R, const int *tok, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, int *res, hipStream_t s);
 // ---- prompt rows of several conversations packed in one chunk (Engine::prefill_batch) ----
 // rows: device [N][2] = (slot, absolute position) per packed row.  k_rope_kv's arithmetic; cache row = position in kcache / vcache + slot * seq_stride
 void launch_rope_kv_seg(float *q, const float *k, const float *v, int N, int n_head, int hd, const int *rows, size_t seq_stride, const float *cos_tab, const float *sin_tab,

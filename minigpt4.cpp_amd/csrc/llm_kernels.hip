@@ -1920,6 +1920,175 @@ void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *k
     default: throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
     }
 }
+// Verify pass (Engine::verify_draft): R <= DRAFT_ROWS rows of ONE conversation at the consecutive positions p0 + t, p0 = n_past[row_slot[0]], in one launch, grid
+// (head, row).  Row t's keys are the cached rows [0, p0), then this pass's rows 0 .. t - 1, then its own.  No workgroup waits for another: every workgroup rotates and
+// rounds the k / v of rows 0 .. t itself into LDS (at most 8 x HD values; cheaper than a dependency between workgroups) and appends only its own row to the cache.
+// CONTRACT: out and the appended rows are bit for bit those of R launches of k_attn_llm<HD, true, true> with one row each and n_past advancing by one between them.
+// The body is that kernel's with one difference: a key j in [p0, pos) is taken from LDS instead of the cache -- SELECTED into the same (partition j mod P, round j / P)
+// place of the same loops, so every fp32 chain keeps its order (as t < P, a partition holds at most one such key: one LDS read per thread, one select per round).
+template <int HD>
+__global__ __launch_bounds__(AT_THREADS) void k_attn_llm_draft(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
+                                                               __half *__restrict__ vc, int E, const int *__restrict__ n_past, int n_ctx, const float *__restrict__ cos_tab,
+                                                               const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot,
+                                                               size_t seq_stride) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int CH = HD / 8, P = AT_THREADS / CH, RM = DRAFT_ROWS;
+    static_assert(RM <= P && RM * (HD / 2) <= AT_THREADS, "one prologue thread per (row, rotated pair); at most one LDS key per partition");
+    const int h = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    const int slot = row_slot[0], p0 = n_past[slot];
+    const int pos = p0 + t, T = pos + 1, Tg = pos;
+    if (pos >= n_ctx) return;                                     // the host cuts a draft to the room left: never taken, and never a store outside the cache
+    kc += (size_t)slot * seq_stride; vc += (size_t)slot * seq_stride;
+    const int Tpad = (T + 7) & ~7;
+    float *sc = reinterpret_cast<float *>(smem);                  // [Tpad]
+    __half *ph = reinterpret_cast<__half *>(sc + Tpad);           // [Tpad]
+    __half *qh = ph + Tpad;                                       // [HD]
+    __half *knew = qh + HD, *vnew = knew + RM * HD;               // [RM][HD] each: rows 0 .. t of this pass
+    float *part = reinterpret_cast<float *>(vnew + RM * HD);      // [P][HD]
+    __shared__ float s_red[AT_THREADS / 64];
+    __shared__ double s_dred[AT_THREADS / 64];
+    const float scale = 1.0f / sqrtf((float)HD);
+    const size_t qo = (size_t)t * E + (size_t)h * HD;
+    if (tid < (t + 1) * (HD / 2)) {
+        const int r = tid / (HD / 2), i = tid % (HD / 2), pr = p0 + r;
+        const size_t ro = (size_t)r * E + (size_t)h * HD;
+        const float c = cos_tab[(size_t)pr * (HD / 2) + i], s = sin_tab[(size_t)pr * (HD / 2) + i];
+        const float k0 = kin[ro + 2 * i], k1 = kin[ro + 2 * i + 1];
+        const __half2 kr = __floats2half2_rn(k0 * c - k1 * s, k0 * s + k1 * c);
+        const __half2 vr = __floats2half2_rn(vin[ro + 2 * i], vin[ro + 2 * i + 1]);
+        *reinterpret_cast<__half2 *>(knew + r * HD + 2 * i) = kr; *reinterpret_cast<__half2 *>(vnew + r * HD + 2 * i) = vr;
+        if (r == t) {
+            const float q0 = q[qo + 2 * i], q1 = q[qo + 2 * i + 1];
+            *reinterpret_cast<__half2 *>(qh + 2 * i) = __floats2half2_rn(q0 * c - q1 * s, q0 * s + q1 * c);
+            const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
+            *reinterpret_cast<__half2 *>(kc + co) = kr; *reinterpret_cast<__half2 *>(vc + co) = vr;
+        }
+    }
+    __syncthreads();
+    unsigned qreg[HD / 2];
+#pragma unroll
+    for (int i = 0; i < HD / 8; i++) { const int4 v4 = *reinterpret_cast<const int4 *>(qh + 8 * i); qreg[4 * i] = (unsigned)v4.x; qreg[4 * i + 1] = (unsigned)v4.y; qreg[4 * i + 2] = (unsigned)v4.z; qreg[4 * i + 3] = (unsigned)v4.w; }
+    auto dot_row = [&](const __half *kr) {
+        int4 kk[HD / 8];
+#pragma unroll
+        for (int i = 0; i < HD / 8; i++) kk[i] = ld16(kr + 8 * i);
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < HD / 8; i++) {
+            const unsigned w[4] = {(unsigned)kk[i].x, (unsigned)kk[i].y, (unsigned)kk[i].z, (unsigned)kk[i].w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), h2f_bits(qreg[4 * i + e] & 0xFFFF), s); s = fmaf(h2f_bits(w[e] >> 16), h2f_bits(qreg[4 * i + e] >> 16), s); }
+        }
+        return s * scale;
+    };
+    const int c = tid % CH, p = tid / CH;
+    const __half *kb = kc + (size_t)h * HD + 8 * c, *vb = vc + (size_t)h * HD + 8 * c;
+    constexpr int NPRE = 16;
+    const int gmax = max(p0 - 1, 0);                              // the last row the cache is read at: rows from p0 on are written by this launch
+    int4 kpre[NPRE], vpre[NPRE];
+#pragma unroll
+    for (int i = 0; i < NPRE; i++) kpre[i] = ld16(kb + (size_t)min(p + i * P, gmax) * E);
+#pragma unroll
+    for (int i = 0; i < NPRE; i++) vpre[i] = ld16(vb + (size_t)min(p + i * P, gmax) * E);
+    // this partition's key among the pass's earlier rows, if any: row rl at position jl (jl mod P == p)
+    const int rl = (p - p0) & (P - 1);
+    const int jl = rl < t ? p0 + rl : -1;
+    const int4 kl = *reinterpret_cast<const int4 *>(knew + min(rl, RM - 1) * HD + 8 * c), vl = *reinterpret_cast<const int4 *>(vnew + min(rl, RM - 1) * HD + 8 * c);
+    float qd[8];
+    {
+        const int4 q4 = *reinterpret_cast<const int4 *>(qh + 8 * c);
+        const unsigned w[4] = {(unsigned)q4.x, (unsigned)q4.y, (unsigned)q4.z, (unsigned)q4.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++) { qd[2 * e] = h2f_bits(w[e] & 0xFFFF); qd[2 * e + 1] = h2f_bits(w[e] >> 16); }
+    }
+    auto dot16 = [&](const int4 &kk) {
+        const unsigned w[4] = {(unsigned)kk.x, (unsigned)kk.y, (unsigned)kk.z, (unsigned)kk.w};
+        float s = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), qd[2 * e], s); s = fmaf(h2f_bits(w[e] >> 16), qd[2 * e + 1], s); }
+        s += dpp_f<0xB1>(s); s += dpp_f<0x4E>(s);
+        if (CH >= 8) s += dpp_f<0x141>(s);
+        if (CH >= 16) s += dpp_f<0x140>(s);
+        return s * scale;
+    };
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; const float s = dot16(j == jl ? kl : kpre[i]); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
+    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {
+        int4 kk[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) kk[i] = ld16(kb + (size_t)min(j0 + i * P, gmax) * E);
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; const float s = dot16(j == jl ? kl : kk[i]); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
+    }
+    if (tid == AT_THREADS - 1) { const float s = dot_row(knew + t * HD); sc[pos] = s; mx = fmaxf(mx, s); }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
+    __syncthreads();
+    mx = s_red[0];
+#pragma unroll
+    for (int i = 1; i < AT_THREADS / 64; i++) mx = fmaxf(mx, s_red[i]);
+    double sum = 0.0;
+    for (int j = tid; j < T; j += AT_THREADS) { const float v = exp_h(tb.exp, sc[j] - mx); sc[j] = v; sum += (double)v; }
+    sum = wave_sum_d(sum);
+    if ((tid & 63) == 0) s_dred[tid >> 6] = sum;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int i = 0; i < AT_THREADS / 64; i++) tot += s_dred[i];
+    const float inv = (float)(1.0 / tot);
+    for (int j = tid; j < T; j += AT_THREADS) ph[j] = f2h_rn(sc[j] * inv);
+    __syncthreads();
+    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto pv_acc = [&](const int4 &vv, const int j) {
+        const float pj = __half2float(ph[j]);
+        const unsigned w[4] = {(unsigned)vv.x, (unsigned)vv.y, (unsigned)vv.z, (unsigned)vv.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++) { o[2 * e] = fmaf(h2f_bits(w[e] & 0xFFFF), pj, o[2 * e]); o[2 * e + 1] = fmaf(h2f_bits(w[e] >> 16), pj, o[2 * e + 1]); }
+    };
+#pragma unroll
+    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; if (j < Tg) pv_acc(j == jl ? vl : vpre[i], j); }
+    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {
+        int4 vv[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) vv[i] = ld16(vb + (size_t)min(j0 + i * P, gmax) * E);
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; if (j < Tg) pv_acc(j == jl ? vl : vv[i], j); }
+    }
+    if (p == P - 1) {
+        const float pj = __half2float(ph[pos]);
+#pragma unroll
+        for (int e = 0; e < 8; e++) o[e] = fmaf(__half2float(vnew[t * HD + 8 * c + e]), pj, o[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) part[p * HD + 8 * c + e] = o[e];
+    __syncthreads();
+    for (int i = tid; i < HD; i += AT_THREADS) { float s = 0.0f;
+#pragma unroll 8
+        for (int pp = 0; pp < P; pp++) s += part[pp * HD + i];
+        out[qo + i] = s; }
+}
+template <int HD>
+static void launch_attn_draft_hd(float *q, const float *k, const float *v, __half *kc, __half *vc, int R, int n_head, const int *n_past, const int *row_slot, size_t seq_stride,
+                                 int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+    const int Tpad = (n_ctx + 7) & ~7;
+    const size_t lds = (size_t)Tpad * 6 + (size_t)HD * 2 + (size_t)2 * DRAFT_ROWS * HD * 2 + (size_t)(AT_THREADS / (HD / 8)) * HD * 4 + 64;
+    static bool attr = false;
+    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_draft<HD>)); attr = true; }
+    note_kernel("k_attn_llm_draft<%d>", HD);
+    hipLaunchKernelGGL((k_attn_llm_draft<HD>), dim3((unsigned)n_head, (unsigned)R), dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, n_ctx, cos_tab, sin_tab, tb, out,
+                       row_slot, seq_stride);
+}
+void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int R, int n_head, int hd, const int *n_past, const int *row_slot,
+                           size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+    if (R < 1 || R > DRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_attn_llm_draft: row count out of range", __FILE__, __LINE__};
+    switch (hd) {
+    case 32: launch_attn_draft_hd<32>(q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
+    case 64: launch_attn_draft_hd<64>(q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
+    case 128: launch_attn_draft_hd<128>(q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
+    default: throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
+    }
+}
 // =====================================================================================================================
 // Key-split decode attention (long contexts): k_attn_llm above puts ONE workgroup on a head -- 40 workgroups on a 256-CU chip, 0.015 us per cached key, 35 us per layer
 // at 2048 keys.  Here S workgroups share a head's keys (n_head x S >= 240 workgroups) in two launches; nothing spins, so nothing can hang:
@@ -2999,7 +3168,8 @@ __global__ void k_set_int(int *p, int v) { *p = v; }
 void launch_set_int(int *p, int v, hipStream_t s) { hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, p, v); }
 // Batched decode epilogue, one workgroup per row: greedy argmax of the row's logits (first maximum wins), stored with the logits' owner slot; the
 // conversation's position advances by one and the greedy token becomes its next input.
-// Returns the greedy id in thread 0 (the other threads' value is meaningless).
+// Returns the greedy id in thread 0 (the other threads' value is meaningless).  KEEP = false: the sweep alone, no copy into the slot's row (k_draft_argmax).
+template <bool KEEP = true>
 __device__ __forceinline__ int batch_finish_row(const float *__restrict__ logits, int n_vocab, int r, int slot, float *__restrict__ slot_logits) {
     const float *x = logits + (size_t)r * n_vocab;
     float *keep = slot_logits + (size_t)slot * n_vocab;                   // the conversation's own copy (sampling with temp > 0, minigpt4_amd_get_logits)
@@ -3008,10 +3178,10 @@ __device__ __forceinline__ int batch_finish_row(const float *__restrict__ logits
     // argmax_combine prefers the lower index, so ties resolve to the first maximum as before
     const int n4 = (n_vocab & 3) == 0 ? n_vocab >> 2 : 0;
     for (int i = threadIdx.x; i < n4; i += 1024) {
-        const float4 v = reinterpret_cast<const float4 *>(x)[i]; reinterpret_cast<float4 *>(keep)[i] = v;
+        const float4 v = reinterpret_cast<const float4 *>(x)[i]; if (KEEP) reinterpret_cast<float4 *>(keep)[i] = v;
         if (v.x > best) { best = v.x; bi = 4 * i; } if (v.y > best) { best = v.y; bi = 4 * i + 1; } if (v.z > best) { best = v.z; bi = 4 * i + 2; } if (v.w > best) { best = v.w; bi = 4 * i + 3; }
     }
-    for (int i = 4 * n4 + threadIdx.x; i < n_vocab; i += 1024) { const float v = x[i]; keep[i] = v; if (v > best) { best = v; bi = i; } }
+    for (int i = 4 * n4 + threadIdx.x; i < n_vocab; i += 1024) { const float v = x[i]; if (KEEP) keep[i] = v; if (v > best) { best = v; bi = i; } }
     __shared__ float sv[16]; __shared__ int si[16];
     argmax_wave(best, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
@@ -3028,6 +3198,33 @@ __global__ __launch_bounds__(1024) void k_batch_finish(const float *__restrict__
 void launch_batch_finish(const float *logits, int n_vocab, int B, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s) {
     hipLaunchKernelGGL(k_batch_finish, dim3((unsigned)B), dim3(1024), 0, s, logits, n_vocab, row_slot, n_past, argmax, feed, slot_logits);
 }
+// Verify pass epilogue (Engine::verify_draft), two launches in stream order.  tok[0 .. R) are the pass's rows (tok[0] = the conversation's greedy token, tok[1 ..] the draft).
+// k_draft_argmax, one workgroup per row: res[1 + r] = the first argmax of logits row r (batch_finish_row's sweep without the copy).
+// k_draft_finish, one workgroup: m = the number of leading draft tokens the pass's own rows chose (tok[i + 1] == res[1 + i] for every i < m); row m becomes the
+// conversation's state -- its logits row, greedy and feed token res[1 + m], position p + 1 + m (n_past[slot] still holds p: the attention launches read it) -- and res[0] = m.
+__global__ __launch_bounds__(1024) void k_draft_argmax(const float *__restrict__ logits, int n_vocab, int *__restrict__ res) {
+    const int id = batch_finish_row<false>(logits, n_vocab, blockIdx.x, 0, nullptr);
+    if (threadIdx.x == 0) res[1 + blockIdx.x] = id;
+}
+__global__ __launch_bounds__(1024) void k_draft_finish(const float *__restrict__ logits, int n_vocab, int R, const int *__restrict__ tok, const int *__restrict__ row_slot, int *__restrict__ n_past,
+                                                      int *__restrict__ argmax, int *__restrict__ feed, float *__restrict__ slot_logits, int *__restrict__ res) {
+    int m = 0;
+    while (m < R - 1 && tok[m + 1] == res[1 + m]) m++;                    // every thread: R <= 8 words, all in cache
+    const int slot = row_slot[0];
+    const float *x = logits + (size_t)m * n_vocab;
+    float *keep = slot_logits + (size_t)slot * n_vocab;
+    for (int i = threadIdx.x; i < n_vocab; i += 1024) keep[i] = x[i];
+    if (threadIdx.x == 0) { const int id = res[1 + m]; argmax[slot] = id; feed[slot] = id; n_past[slot] += 1 + m; res[0] = m; }
+}
+void launch_draft_finish(const float *logits, int n_vocab, int R, const int *tok, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, int *res, hipStream_t s) {
+    if (R < 1 || R > DRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_draft_finish: row count out of range", __FILE__, __LINE__};
+    note_kernel("k_draft_argmax"); note_kernel("k_draft_finish");
+    hipLaunchKernelGGL(k_draft_argmax, dim3((unsigned)R), dim3(1024), 0, s, logits, n_vocab, res);
+    hipLaunchKernelGGL(k_draft_finish, dim3(1), dim3(1024), 0, s, logits, n_vocab, R, tok, row_slot, n_past, argmax, feed, slot_logits, res);
+}
+// verify pass prologue: the host's view of the conversation's position, once (every row of the pass derives its own from it)
+__global__ void k_draft_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos) { n_past[row_slot[0]] = row_pos[0]; }
+void launch_draft_begin(int *n_past, const int *row_slot, const int *row_pos, hipStream_t s) { hipLaunchKernelGGL(k_draft_begin, dim3(1), dim3(1), 0, s, n_past, row_slot, row_pos); }
 // Packed prompt chunk epilogue (Engine::prefill_batch): row r of `logits` is the last row of conversation fin[2 r]; its position becomes fin[2 r + 1] (set, not
 // advanced), its greedy id and feed token as k_batch_finish writes them.
 __global__ __launch_bounds__(1024) void k_seg_finish(const float *__restrict__ logits, int n_vocab, const int *__restrict__ fin, int *__restrict__ n_past, int *__restrict__ argmax,

@@ -7,6 +7,7 @@
 
 #include "api_internal.hpp"
 #include "activations.hpp"
+#include "draft.hpp"
 #include "imageio.hpp"
 #include "quantize.hpp"
 #include "minigpt4_amd.h"
@@ -773,6 +774,51 @@ int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slot
         }
         return 0;
     });
+}
+int minigpt4_amd_test_attn_draft(int mode, int n_head, int hd, int n_ctx, int n_slot, int slot, int n_past, int R, int computed_exp, const float *q, const float *k, const float *v,
+                                 uint16_t *kc, uint16_t *vc, float *out) {
+    if (!q || !k || !v || !kc || !vc || !out || (mode != 0 && mode != 1) || (hd != 32 && hd != 64 && hd != 128) || n_head < 1 || n_slot < 1 || slot < 0 || slot >= n_slot ||
+        R < 1 || R > DRAFT_ROWS || n_past < 0 || n_ctx < 1 || n_past > n_ctx - R || n_ctx > attn_max_ctx(hd)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, stride = (size_t)n_ctx * E, cache = (size_t)n_slot * stride, RE = (size_t)R * E;
+        std::vector<float> c, sn;
+        rope_tables(n_ctx, hd, c, sn);
+        std::vector<int> np((size_t)n_slot, 0); np[(size_t)slot] = n_past;
+        DevBuf dc(c.size() * 4), dsn(sn.size() * 4), dq(RE * 4), dk(RE * 4), dv(RE * 4), dkc(cache * 2), dvc(cache * 2), dout(RE * 4), dnp((size_t)n_slot * 4), dslot(4), dtab(65536 * 2);
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dq.p, q, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dk.p, k, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, RE * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dkc.p, kc, cache * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dvc.p, vc, cache * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dnp.p, np.data(), np.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dslot.p, &slot, 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0, RE * 4));
+        // the engine's tables (Engine::alloc_buffers): the host libm's fp16 exp table and its live negative part; the decode step's copy has no table when it computes
+        Tables tb;
+        { std::vector<__half> e(65536); int last = 0;
+          for (int i = 0; i < 65536; i++) e[(size_t)i] = __float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)i))));
+          for (int i = 0; i < 0x7C00; i++) if (__half2float(e[(size_t)(0x8000 + i)]) != 0.0f) last = i;
+          HIP_CHECK(hipMemcpy(dtab.p, e.data(), 131072, hipMemcpyHostToDevice));
+          tb.exp = computed_exp ? nullptr : dtab.as<__half>(); tb.exp_neg_n = (last + 1 + 2047) / 2048 * 2048; }
+        if (mode == 0) {
+            launch_attn_llm_draft(dq.as<float>(), dk.as<float>(), dv.as<float>(), dkc.as<__half>(), dvc.as<__half>(), R, n_head, hd, dnp.as<int>(), dslot.as<int>(), stride, n_ctx,
+                                  dc.as<float>(), dsn.as<float>(), tb, dout.as<float>(), nullptr);
+        } else {
+            for (int r = 0; r < R; r++) {
+                launch_set_int(dnp.as<int>() + slot, n_past + r, nullptr);
+                launch_attn_llm_batched(dq.as<float>() + (size_t)r * E, dk.as<float>() + (size_t)r * E, dv.as<float>() + (size_t)r * E, dkc.as<__half>(), dvc.as<__half>(), 1, n_head, hd,
+                                        dnp.as<int>(), dslot.as<int>(), stride, n_ctx, dc.as<float>(), dsn.as<float>(), tb, dout.as<float>() + (size_t)r * E, nullptr);
+            }
+        }
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dout.p, RE * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc, dkc.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+int minigpt4_amd_test_ngram_draft(const int32_t *history, int n, int ngram_max, int ngram_min, int n_draft, int32_t *out) {
+    if (n < 0 || (n > 0 && !history) || !out || ngram_min < 1 || ngram_max < ngram_min || n_draft < 0) return -1;
+    NgramDrafter d(ngram_max, ngram_min);
+    d.reset(history, n);
+    return d.draft(n_draft, out);
 }
 int minigpt4_amd_test_rope_kv_seg(int n_head, int hd, int n_ctx, int n_slots, int n_seg, const int32_t *segs, const float *q, const float *k, const float *v, int ks,
                                   float *q_seg, uint16_t *kc_seg, uint16_t *vc_seg, float *q_ref, uint16_t *kc_ref, uint16_t *vc_ref) {

@@ -213,6 +213,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_end_chat_batch_top.argtypes = [VOID_PTR, INT_PTR, I32, P(ctypes.c_char_p), F32, I32, F32, F32, F32, I32, F32, F32, I32, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR,
                                                       FLOAT_PTR]
         L.minigpt4_amd_score_tokens_top.argtypes = [VOID_PTR, INT_PTR, I32, I32, FLOAT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_set_speculation.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_verify_draft.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_decode_lookup.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, INT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -238,6 +241,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_kv_copy.argtypes = [I32, I32, I32, I32, I32, INT_PTR, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
@@ -467,6 +472,33 @@ class MiniGPT4SharedLibrary:
             out["logits"] = lg
         return out
 
+    def amd_set_speculation(self, ctx, max_draft: int) -> None:
+        """Draft verification for this context: max_draft 1 .. 7 allocates what amd_verify_draft / amd_decode_lookup need, 0 (the default) frees it.  include/minigpt4_amd.h"""
+        if self.library.minigpt4_amd_set_speculation(ctx.ptr, int(max_draft)):
+            raise RuntimeError("set_speculation failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+
+    def amd_verify_draft(self, ctx, draft: Sequence[int]) -> dict:
+        """One weight pass over the selected conversation's greedy token and the guessed tokens behind it; keeps the guesses the pass's own logits confirm.
+        dict(ids [1 + m] i32: the tokens plain greedy decoding would have emitted, row_greedy [1 + len(draft)] i32: the first argmax of every evaluated row, -1 for a
+        row not evaluated).  include/minigpt4_amd.h"""
+        d = np.ascontiguousarray(draft, np.int32)
+        n = len(d)
+        ids, rg, n_out = np.zeros(n + 1, np.int32), np.zeros(n + 1, np.int32), np.zeros(1, np.int32)
+        if self.library.minigpt4_amd_verify_draft(ctx.ptr, d.ctypes.data_as(INT_PTR) if n else None, n, ids.ctypes.data_as(INT_PTR), n_out.ctypes.data_as(INT_PTR),
+                                                  rg.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("verify_draft failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return dict(ids=ids[:int(n_out[0])].copy(), row_greedy=rg)
+
+    def amd_decode_lookup(self, ctx, corpus: Sequence[int], max_tokens: int, ngram_max: int = 3, ngram_min: int = 1, n_draft: int = 4) -> dict:
+        """Greedy generation of up to max_tokens tokens with drafts looked up in corpus + the tokens emitted so far (n-gram lookup decoding).
+        dict(tokens [n] i32, passes, steps, sent, accepted): verify passes, plain decode steps, draft tokens sent and accepted.  include/minigpt4_amd.h"""
+        c = np.ascontiguousarray(corpus, np.int32)
+        out, n, st = np.zeros(max(int(max_tokens), 1), np.int32), np.zeros(1, np.int32), np.zeros(4, np.int32)
+        if self.library.minigpt4_amd_decode_lookup(ctx.ptr, c.ctypes.data_as(INT_PTR) if len(c) else None, len(c), int(max_tokens), int(ngram_max), int(ngram_min), int(n_draft),
+                                                   out.ctypes.data_as(INT_PTR), n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("decode_lookup failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return dict(tokens=out[:int(n[0])].copy(), passes=int(st[0]), steps=int(st[1]), sent=int(st[2]), accepted=int(st[3]))
+
     def amd_token_piece(self, ctx, token_id: int) -> Optional[str]:
         """The text of one token id, as minigpt4_end_chat returns it ("</s>" for id 2); None for an id outside the vocabulary."""
         p = self.library.minigpt4_amd_token_piece(ctx.ptr, int(token_id))
@@ -627,6 +659,30 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_rope_kv_seg rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return tuple(out[:3]), tuple(out[3:])
+
+    def amd_test_attn_draft(self, mode: int, q: np.ndarray, k: np.ndarray, v: np.ndarray, kc: np.ndarray, vc: np.ndarray, n_head: int, slot: int, n_past: int,
+                            computed_exp: bool = True):
+        """The verify pass's attention (mode 0: one k_attn_llm_draft launch; mode 1: one launch of the batched decode kernel per row) for the rows q, k, v [R][E] of
+        conversation `slot` at positions n_past ..., on fp16 caches [n_slot][n_ctx][E] given as uint16 patterns.  Returns (out [R][E], kc, vc) -- copies."""
+        q, k, v = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+        kc, vc = np.array(kc, np.uint16, order="C"), np.array(vc, np.uint16, order="C")
+        R, E = q.shape
+        S, C, _ = kc.shape
+        out = np.zeros_like(q)
+        rc = self.library.minigpt4_amd_test_attn_draft(int(mode), n_head, E // n_head, C, S, slot, n_past, R, int(computed_exp), q.ctypes.data_as(FLOAT_PTR), k.ctypes.data_as(FLOAT_PTR),
+                                                       v.ctypes.data_as(FLOAT_PTR), kc.ctypes.data_as(VOID_PTR), vc.ctypes.data_as(VOID_PTR), out.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_attn_draft rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return out, kc, vc
+
+    def amd_test_ngram_draft(self, history: Sequence[int], ngram_max: int, ngram_min: int, n_draft: int) -> List[int]:
+        """The draft minigpt4_amd_decode_lookup's host drafter proposes for `history` (its last token = the one about to be evaluated)."""
+        h = np.ascontiguousarray(history, np.int32)
+        out = np.zeros(max(int(n_draft), 1), np.int32)
+        n = self.library.minigpt4_amd_test_ngram_draft(h.ctypes.data_as(INT_PTR) if len(h) else None, len(h), int(ngram_max), int(ngram_min), int(n_draft), out.ctypes.data_as(INT_PTR))
+        if n < 0:
+            raise ValueError("test_ngram_draft: bad arguments")
+        return [int(x) for x in out[:n]]
 
     def amd_batch_path(self, ctx) -> dict:
         """Launch kinds of the batched step as last built (include/minigpt4_amd.h: minigpt4_amd_batch_path)."""
