@@ -186,6 +186,8 @@ MINIGPT4_API int minigpt4_amd_score_tokens_top(struct MiniGPT4Context *ctx, cons
  * first use); 0 frees them.  Plain decoding, batched decoding and scoring pay nothing and launch nothing new either way.  At 3 and 4 rows the pass runs on the
  * row-interleaved int8-MFMA image of the k-quant weights where the context already HAS it (minigpt4_amd_set_conversations(n > 1) builds it; it doubles those weights'
  * memory): this call never builds it.  The setting survives minigpt4_amd_set_parity and minigpt4_amd_set_conversations; the captured passes are dropped there.
+ * Refused (1, "set_speculation: ...", nothing allocated, the setting stays off): max_draft > 0 on a context whose n_ctx exceeds what the verify pass's attention kernel
+ * holds in LDS -- it keeps 8 new key / value rows there where the decode step keeps one: 23 792 rows at head size 128 (the load admits 24 392), 24 160 at 64 (24 456), 24 336 at 32 (24 488).
  * minigpt4_amd_verify_draft, on the selected conversation: queued rows are evaluated first (as minigpt4_amd_get_logits does); the conversation must then have current
  * logits.  g0 = its greedy token (what minigpt4_end_chat at temp 0 would emit).  ONE pass evaluates g0, draft[0 .. n_draft) at positions p, p + 1, ...; g[r + 1] = the
  * first argmax of row r; m = the largest value with draft[i] == g[i + 1] for all i < m.  Afterwards ids_out[0 .. m] = g0, draft[0 .. m - 1], *n_out = 1 + m, the

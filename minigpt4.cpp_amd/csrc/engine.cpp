@@ -1649,6 +1649,11 @@ void Engine::spec_free() {
 }
 int Engine::set_speculation(int max_draft) {
     if (max_draft < 0 || max_draft > DRAFT_MAX) { set_last_error("set_speculation: max_draft must be 0 (off) ... " + std::to_string(DRAFT_MAX)); return 1; }
+    // the verify pass keeps DRAFT_ROWS new key / value rows next to the score rows in the attention kernel's LDS: a context the one-row form holds may not fit it
+    if (const int lim = attn_draft_max_ctx((int)(llm_.n_embd / llm_.n_head)); max_draft > 0 && n_ctx_ > lim) {
+        set_last_error("set_speculation: n_ctx " + std::to_string(n_ctx_) + " exceeds what the verify pass's attention kernel holds in LDS at this head size (" + std::to_string(lim) + ")");
+        return 1;
+    }
     HIP_CHECK(hipStreamSynchronize(stream_));
     spec_free();
     if (max_draft == 0) return 0;

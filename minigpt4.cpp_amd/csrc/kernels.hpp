@@ -160,6 +160,7 @@ void launch_batch_begin(int *n_past, const int *row_slot, const int *row_pos, in
 constexpr int DRAFT_ROWS = 8;                          // the conversation's greedy token + at most 7 draft tokens
 // row t at position n_past[row_slot[0]] + t (all below n_ctx): RoPE + append of its own row, attention over the cache below the position, the pass's rows 0 .. t - 1
 // and itself.  out and the appended rows are bit for bit those of R one-row launch_attn_llm_batched calls with n_past advanced by one between them.  n_past is not written.
+// n_ctx <= attn_draft_max_ctx(hd) (below).
 void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int R, int n_head, int hd, const int *n_past, const int *row_slot,
                            size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s);
 void launch_draft_begin(int *n_past, const int *row_slot, const int *row_pos, hipStream_t s);   // n_past[row_slot[0]] = row_pos[0]
@@ -211,6 +212,7 @@ bool attn_head_size_supported(int hd);
 void attn_ref_prepare();        // the oracle-order attention kernels' > 64 KiB LDS opt-in on the current device, checked (throws HipError); outside any stream capture
 int attn_ref_max_ctx(int hd);   // the same bound for the oracle-order kernel of parity mode (smaller: it also stages value rows in LDS)
 int attn_max_ctx(int hd);   // largest n_ctx whose score / probability rows fit the attention kernel's LDS
+int attn_draft_max_ctx(int hd);   // the same bound for the verify form (launch_attn_llm_draft), which keeps DRAFT_ROWS new key / value rows in LDS instead of one: smaller
 void launch_argmax(const float *logits, int n, int *out, void *scratch /*>= 512 bytes*/, hipStream_t s);
 void launch_add_inplace(float *x, const float *y, size_t n, hipStream_t s);
 void launch_set_int(int *p, int v, hipStream_t s);

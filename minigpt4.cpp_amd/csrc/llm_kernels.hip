@@ -1734,360 +1734,141 @@ void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, cons
 }
 
 // =====================================================================================================================
-// causal attention over the fp16 KV cache.  One 512-thread workgroup per (head, query token).
-//   FUSED (decode, N = 1): RoPE of q/k and the KV append happen in the prologue; the new key/value are also kept in LDS.
-//   scores : one lane per key, the whole head row in registers (HD/8 independent 16-byte loads), sequential fp32 fma over the
-//            head dim; q is rounded to fp16 first, like ggml's f16 x f32 mul_mat
+// Decode attention over the fp16 KV cache: ONE body, attn_llm_body.hpp, included in the kernels k_attn_llm<HD, FUSED, BATCHED> and k_attn_llm_draft<HD> (why included and
+// not called: the head of that file); FUSED, BATCHED and DRAFT are compile-time constants there.
+// One 512-thread workgroup per (head, query row).
+//   scores : 16 consecutive lanes share one cached key row (dot16), the new key by one lane over the whole head row (dot_row: sequential fp32 fma over the head dim);
+//            q is rounded to fp16 first, like ggml's f16 x f32 mul_mat
 //   softmax: max, exp through the fp16 table, exact double sum, probabilities rounded to fp16
-//   PV     : thread = (key partition, 8-dim chunk): 16-byte V loads, 4 in flight; partitions reduced through LDS
+//   PV     : thread = (key partition, 8-dim chunk): 16-byte V loads, NPRE in flight; partitions reduced through LDS
+// The forms:
+//   plain   (!FUSED; prompt rows beyond the prompt kernels' LDS): row t at position *n_past + t, launch_rope_kv has run; every key comes from the cache.
+//   FUSED   (decode, one row): RoPE of q / k and the KV append happen in the prologue; the new key / value are also kept in LDS and take the last place of the chains.
+//   BATCHED (decode of several conversations in one pass; implies FUSED): row t belongs to conversation row_slot[t], whose position is n_past[row_slot[t]] and whose
+//           caches start seq_stride * row_slot[t] elements behind kc / vc.
+//   DRAFT   (verify pass, Engine::verify_draft; implies BATCHED): R <= DRAFT_ROWS rows of ONE conversation at the consecutive positions p0 + t, p0 = n_past[row_slot[0]].
+//           Row t's keys are the cached rows [0, p0), then this pass's rows 0 .. t - 1, then its own.  No workgroup waits for another: every workgroup rotates and rounds
+//           the k / v of rows 0 .. t itself into LDS (at most 8 x HD values; cheaper than a dependency between workgroups) and appends only its own row to the cache.
+//           CONTRACT: out and the appended rows are bit for bit those of R launches of the BATCHED form with one row each and n_past advancing by one between them.
+// What DRAFT adds to the BATCHED form, and why every fp32 chain keeps its order -- each line below is under `DRAFT`, the rest of the body is shared text:
+//   - the position is p0 + t with p0 from row_slot[0]; a row at or past n_ctx returns (the host cuts a draft to the room left: never taken, never a store outside the cache);
+//   - the prologue (its own branch) has one thread per (row r <= t, rotated pair) instead of one per pair: rows before t only fill knew / vnew [r], row t is what the
+//     BATCHED form does;
+//   - the cache is read up to row p0 - 1 only (gmax): rows from p0 on are written by this launch's other workgroups;
+//   - a key j in [p0, pos) is taken from LDS (kl / vl) instead of the cache -- SELECTED into the same (partition j mod P, round j / P) place of the same loops, so the
+//     max, the score row, and each partition's P.V chain see the same values in the same order (as t < P, a partition holds at most one such key: one LDS read per thread,
+//     one select per round); the own key is knew / vnew [t] where the BATCHED form has knew / vnew [0].
 // =====================================================================================================================
 constexpr int AT_THREADS = 512;
-//   BATCHED (decode of several conversations in one pass; implies FUSED): row t belongs to conversation row_slot[t], whose position is
-//            n_past[row_slot[t]] and whose caches start seq_stride * row_slot[t] elements behind kc / vc.
+// ---- shared by the family (k_attn_llm*, k_attn_split_*, k_attn_ref<true>): operand order and rounding calls are part of the results ----
+// the pair (x0, x1) rotated by the angle of (c, s); each kernel rounds the result in its own spelling
+__device__ __forceinline__ float2 rope_rot(float x0, float x1, float c, float s) { return make_float2(x0 * c - x1 * s, x0 * s + x1 * c); }
+__device__ __forceinline__ __half2 rope_rot_h2(float x0, float x1, float c, float s) { const float2 r = rope_rot(x0, x1, c, s); return __floats2half2_rn(r.x, r.y); }
+__device__ __forceinline__ void st_h2(__half *p, __half2 v) { *reinterpret_cast<__half2 *>(p) = v; }
+// the eight halves of a 16-byte piece as floats, in element order
+__device__ __forceinline__ void unpack8(const int4 &v, float (&f)[8]) {
+    const unsigned w[4] = {(unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) { f[2 * e] = h2f_bits(w[e] & 0xFFFF); f[2 * e + 1] = h2f_bits(w[e] >> 16); }
+}
+// score of one key whose row is spread over CH consecutive lanes (lane c: dims 8 c .. 8 c + 7 in kk, the same dims of q in qd): all CH lanes return it
+template <int CH> __device__ __forceinline__ float dot16(const int4 &kk, const float (&qd)[8], float scale) {
+    float kf[8], s = 0.0f;
+    unpack8(kk, kf);
+#pragma unroll
+    for (int e = 0; e < 8; e++) s = fmaf(kf[e], qd[e], s);
+    s += dpp_f<0xB1>(s); s += dpp_f<0x4E>(s);                     // the CH = HD / 8 lanes of the key: 4 (HD 32), 8 (HD 64: half a DPP row) or 16 (HD 128: a DPP row)
+    if (CH >= 8) s += dpp_f<0x141>(s);
+    if (CH >= 16) s += dpp_f<0x140>(s);
+    return s * scale;
+}
+__device__ __forceinline__ void pv_acc(float (&o)[8], const int4 &vv, float pj) {   // o += pj * (the eight values of vv)
+    const unsigned w[4] = {(unsigned)vv.x, (unsigned)vv.y, (unsigned)vv.z, (unsigned)vv.w};
+#pragma unroll
+    for (int e = 0; e < 4; e++) { o[2 * e] = fmaf(h2f_bits(w[e] & 0xFFFF), pj, o[2 * e]); o[2 * e + 1] = fmaf(h2f_bits(w[e] >> 16), pj, o[2 * e + 1]); }
+}
+// Dynamic LDS of the body for contexts up to n_ctx with `rows` new rows kept in LDS (1, or DRAFT_ROWS for the DRAFT form) -- the ONLY place the layout's size is
+// written: sc [Tpad] fp32 | ph [Tpad] | qh [hd] | knew [rows][hd] | vnew [rows][hd] | part [P][hd] fp32 | 64 spare
+static size_t attn_lds_bytes(int n_ctx, int hd, int rows) {
+    const int Tpad = (n_ctx + 7) & ~7;
+    return (size_t)Tpad * 6 + (size_t)hd * 2 + (size_t)2 * rows * hd * 2 + (size_t)(AT_THREADS / (hd / 8)) * hd * 4 + 64;
+}
+static int attn_ctx_that_fits(int hd, int rows) { int n = 0; while (attn_lds_bytes(n + 8, hd, rows) + 256 /* static reduction arrays */ <= 160 * 1024) n += 8; return n; }
+int attn_max_ctx(int hd) { return attn_ctx_that_fits(hd, 1); }
+int attn_draft_max_ctx(int hd) { return attn_ctx_that_fits(hd, DRAFT_ROWS); }
+
 template <int HD, bool FUSED, bool BATCHED = false>
 __global__ __launch_bounds__(AT_THREADS) void k_attn_llm(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
                                                          __half *__restrict__ vc, int E, const int *__restrict__ n_past, const float *__restrict__ cos_tab,
                                                          const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot = nullptr,
                                                          size_t seq_stride = 0) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int CH = HD / 8, P = AT_THREADS / CH;
-    const int h = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    int pos_;
-    if (BATCHED) { const int slot = row_slot[t]; pos_ = n_past[slot]; kc += (size_t)slot * seq_stride; vc += (size_t)slot * seq_stride; }
-    else pos_ = *n_past + t;
-    const int pos = pos_, T = pos + 1;
-    const int Tg = FUSED ? pos : T;                               // keys read from the global cache
-    const int Tpad = (T + 7) & ~7;
-    float *sc = reinterpret_cast<float *>(smem);                  // [Tpad]
-    __half *ph = reinterpret_cast<__half *>(sc + Tpad);           // [Tpad]
-    __half *qh = ph + Tpad;                                       // [HD]
-    __half *knew = qh + HD, *vnew = knew + HD;                    // [HD] each
-    float *part = reinterpret_cast<float *>(vnew + HD);           // [P][HD]
-    __shared__ float s_red[AT_THREADS / 64];
-    __shared__ double s_dred[AT_THREADS / 64];
-    const float scale = 1.0f / sqrtf((float)HD);
-    const size_t qo = (size_t)t * E + (size_t)h * HD;
-    if (FUSED) {
-        if (tid < HD / 2) {
-            const int i = tid;
-            const float c = cos_tab[(size_t)pos * (HD / 2) + i], s = sin_tab[(size_t)pos * (HD / 2) + i];
-            const float q0 = q[qo + 2 * i], q1 = q[qo + 2 * i + 1], k0 = kin[qo + 2 * i], k1 = kin[qo + 2 * i + 1];
-            const __half2 qr = __floats2half2_rn(q0 * c - q1 * s, q0 * s + q1 * c), kr = __floats2half2_rn(k0 * c - k1 * s, k0 * s + k1 * c);
-            const __half2 vr = __floats2half2_rn(vin[qo + 2 * i], vin[qo + 2 * i + 1]);
-            *reinterpret_cast<__half2 *>(qh + 2 * i) = qr; *reinterpret_cast<__half2 *>(knew + 2 * i) = kr; *reinterpret_cast<__half2 *>(vnew + 2 * i) = vr;
-            const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
-            *reinterpret_cast<__half2 *>(kc + co) = kr; *reinterpret_cast<__half2 *>(vc + co) = vr;
-        }
-    } else {
-        for (int i = tid; i < HD; i += AT_THREADS) qh[i] = f2h_rn(q[qo + i]);
-    }
-    __syncthreads();
-    unsigned qreg[HD / 2];
-#pragma unroll
-    for (int i = 0; i < HD / 8; i++) { const int4 v4 = *reinterpret_cast<const int4 *>(qh + 8 * i); qreg[4 * i] = (unsigned)v4.x; qreg[4 * i + 1] = (unsigned)v4.y; qreg[4 * i + 2] = (unsigned)v4.z; qreg[4 * i + 3] = (unsigned)v4.w; }
-    auto dot_row = [&](const __half *kr) {
-        int4 kk[HD / 8];
-#pragma unroll
-        for (int i = 0; i < HD / 8; i++) kk[i] = ld16(kr + 8 * i);
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < HD / 8; i++) {
-            const unsigned w[4] = {(unsigned)kk[i].x, (unsigned)kk[i].y, (unsigned)kk[i].z, (unsigned)kk[i].w};
-#pragma unroll
-            for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), h2f_bits(qreg[4 * i + e] & 0xFFFF), s); s = fmaf(h2f_bits(w[e] >> 16), h2f_bits(qreg[4 * i + e] >> 16), s); }
-        }
-        return s * scale;
-    };
-    // (Measured and not adopted, profiles/r02m_bench_n1.json vs r02k: requesting these K / V rows at kernel entry, before the RoPE prologue and its barrier, with the exp
-    // table's live part in LDS and the KV append moved behind the last barrier -- 11.7 us per launch at a context of 430 against 10.9 us for this form; beside LDS-DMA
-    // hipcc waits vmcnt(0) for every ordinary load, so the prologue sat out the whole prefetch.)
-    // Scores of the cached keys: 16 consecutive lanes share one key row (lane c holds its dims 8 c .. 8 c + 7 -- one 256-byte row per 16 lanes, four whole rows per
-    // wave instruction; the round-1 form, a whole row per lane, asked the address path for 64 different cache lines per instruction and grew by ~0.025 us per key), the
-    // 8-dim partial dots are added across the 16 lanes with DPP.  Key and value rows of the same (lane, round) sit at the same offset of the two caches, and neither
-    // depends on this step's scores: both are requested here, NPRE rounds deep, so they arrive during the dot products / the softmax.
-    const int c = tid % CH, p = tid / CH;
-    const __half *kb = kc + (size_t)h * HD + 8 * c, *vb = vc + (size_t)h * HD + 8 * c;
-    constexpr int NPRE = 16;                        // x P = 32 key partitions: contexts up to 512 need no second round trip
-    int4 kpre[NPRE], vpre[NPRE];
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) kpre[i] = ld16(kb + (size_t)min(p + i * P, max(Tg - 1, 0)) * E);   // clamped: never branches, never out of the cache
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) vpre[i] = ld16(vb + (size_t)min(p + i * P, max(Tg - 1, 0)) * E);
-    float qd[8];
-    {
-        const int4 q4 = *reinterpret_cast<const int4 *>(qh + 8 * c);
-        const unsigned w[4] = {(unsigned)q4.x, (unsigned)q4.y, (unsigned)q4.z, (unsigned)q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) { qd[2 * e] = h2f_bits(w[e] & 0xFFFF); qd[2 * e + 1] = h2f_bits(w[e] >> 16); }
-    }
-    auto dot16 = [&](const int4 &kk) {              // all 16 lanes of the row return the key's score
-        const unsigned w[4] = {(unsigned)kk.x, (unsigned)kk.y, (unsigned)kk.z, (unsigned)kk.w};
-        float s = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), qd[2 * e], s); s = fmaf(h2f_bits(w[e] >> 16), qd[2 * e + 1], s); }
-        s += dpp_f<0xB1>(s); s += dpp_f<0x4E>(s);                 // the CH = HD / 8 lanes of the key: 4 (HD 32), 8 (HD 64: half a DPP row) or 16 (HD 128: a DPP row)
-        if (CH >= 8) s += dpp_f<0x141>(s);
-        if (CH >= 16) s += dpp_f<0x140>(s);
-        return s * scale;
-    };
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; const float s = dot16(kpre[i]); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
-    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {      // beyond the prefetch: 8 rows per round trip
-        int4 kk[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) kk[i] = ld16(kb + (size_t)min(j0 + i * P, Tg - 1) * E);
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; const float s = dot16(kk[i]); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
-    }
-    if (FUSED && tid == AT_THREADS - 1) { const float s = dot_row(knew); sc[pos] = s; mx = fmaxf(mx, s); }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-    __syncthreads();
-    mx = s_red[0];
-#pragma unroll
-    for (int i = 1; i < AT_THREADS / 64; i++) mx = fmaxf(mx, s_red[i]);
-    double sum = 0.0;
-    for (int j = tid; j < T; j += AT_THREADS) { const float v = exp_h(tb.exp, sc[j] - mx); sc[j] = v; sum += (double)v; }
-    sum = wave_sum_d(sum);
-    if ((tid & 63) == 0) s_dred[tid >> 6] = sum;
-    __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int i = 0; i < AT_THREADS / 64; i++) tot += s_dred[i];
-    const float inv = (float)(1.0 / tot);
-    for (int j = tid; j < T; j += AT_THREADS) ph[j] = f2h_rn(sc[j] * inv);
-    __syncthreads();
-    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto pv_acc = [&](const int4 &vv, const int j) {
-        const float pj = __half2float(ph[j]);
-        const unsigned w[4] = {(unsigned)vv.x, (unsigned)vv.y, (unsigned)vv.z, (unsigned)vv.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) { o[2 * e] = fmaf(h2f_bits(w[e] & 0xFFFF), pj, o[2 * e]); o[2 * e + 1] = fmaf(h2f_bits(w[e] >> 16), pj, o[2 * e + 1]); }
-    };
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; if (j < Tg) pv_acc(vpre[i], j); }
-    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {
-        int4 vv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) vv[i] = ld16(vb + (size_t)min(j0 + i * P, Tg - 1) * E);
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; if (j < Tg) pv_acc(vv[i], j); }
-    }
-    if (FUSED && p == P - 1) {
-        const float pj = __half2float(ph[pos]);
-#pragma unroll
-        for (int e = 0; e < 8; e++) o[e] = fmaf(__half2float(vnew[8 * c + e]), pj, o[e]);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) part[p * HD + 8 * c + e] = o[e];
-    __syncthreads();
-    for (int i = tid; i < HD; i += AT_THREADS) { float s = 0.0f;
-#pragma unroll 8
-        for (int pp = 0; pp < P; pp++) s += part[pp * HD + i];
-        out[qo + i] = s; }
+    constexpr bool DRAFT = false;
+    constexpr int n_ctx = 0;                                      // DRAFT only
+#include "attn_llm_body.hpp"
 }
-
-template <int HD>
-static void launch_attn_hd(float *q, const float *k, const float *v, __half *kc, __half *vc, int N, int n_head, const int *n_past, int n_ctx, const float *cos_tab,
-                           const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s) {
-    const int Tpad = (n_ctx + 7) & ~7;
-    const size_t lds = (size_t)Tpad * 6 + (size_t)HD * 6 + (size_t)(AT_THREADS / (HD / 8)) * HD * 4 + 64;
-    static bool attr = false;
-    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true>));
-                 HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, false>)); attr = true; }
-    note_kernel("k_attn_llm<%d, %s, false>", HD, fused ? "true" : "false");
-    if (fused) hipLaunchKernelGGL((k_attn_llm<HD, true>), dim3((unsigned)n_head, 1), dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, (const int *)nullptr, (size_t)0);
-    else hipLaunchKernelGGL((k_attn_llm<HD, false>), dim3((unsigned)n_head, (unsigned)N), dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, (const int *)nullptr, (size_t)0);
-}
-template <int HD>
-static void launch_attn_batched_hd(float *q, const float *k, const float *v, __half *kc, __half *vc, int B, int n_head, const int *n_past, const int *row_slot, size_t seq_stride,
-                                   int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
-    const int Tpad = (n_ctx + 7) & ~7;
-    const size_t lds = (size_t)Tpad * 6 + (size_t)HD * 6 + (size_t)(AT_THREADS / (HD / 8)) * HD * 4 + 64;
-    static bool attr = false;
-    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, true>)); attr = true; }
-    hipLaunchKernelGGL((k_attn_llm<HD, true, true>), dim3((unsigned)n_head, (unsigned)B), dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot,
-                       seq_stride);
-}
-// Decode attention for B rows of B different conversations (RoPE + KV append fused): row t uses position n_past[row_slot[t]] and the caches of that conversation.
-void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int B, int n_head, int hd, const int *n_past, const int *row_slot,
-                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
-    switch (hd) {
-    case 32: launch_attn_batched_hd<32>(q, k, v, kcache, vcache, B, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
-    case 64: launch_attn_batched_hd<64>(q, k, v, kcache, vcache, B, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
-    case 128: launch_attn_batched_hd<128>(q, k, v, kcache, vcache, B, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
-    default: throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
-    }
-}
-// Verify pass (Engine::verify_draft): R <= DRAFT_ROWS rows of ONE conversation at the consecutive positions p0 + t, p0 = n_past[row_slot[0]], in one launch, grid
-// (head, row).  Row t's keys are the cached rows [0, p0), then this pass's rows 0 .. t - 1, then its own.  No workgroup waits for another: every workgroup rotates and
-// rounds the k / v of rows 0 .. t itself into LDS (at most 8 x HD values; cheaper than a dependency between workgroups) and appends only its own row to the cache.
-// CONTRACT: out and the appended rows are bit for bit those of R launches of k_attn_llm<HD, true, true> with one row each and n_past advancing by one between them.
-// The body is that kernel's with one difference: a key j in [p0, pos) is taken from LDS instead of the cache -- SELECTED into the same (partition j mod P, round j / P)
-// place of the same loops, so every fp32 chain keeps its order (as t < P, a partition holds at most one such key: one LDS read per thread, one select per round).
 template <int HD>
 __global__ __launch_bounds__(AT_THREADS) void k_attn_llm_draft(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
                                                                __half *__restrict__ vc, int E, const int *__restrict__ n_past, int n_ctx, const float *__restrict__ cos_tab,
                                                                const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot,
                                                                size_t seq_stride) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int CH = HD / 8, P = AT_THREADS / CH, RM = DRAFT_ROWS;
-    static_assert(RM <= P && RM * (HD / 2) <= AT_THREADS, "one prologue thread per (row, rotated pair); at most one LDS key per partition");
-    const int h = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
-    const int slot = row_slot[0], p0 = n_past[slot];
-    const int pos = p0 + t, T = pos + 1, Tg = pos;
-    if (pos >= n_ctx) return;                                     // the host cuts a draft to the room left: never taken, and never a store outside the cache
-    kc += (size_t)slot * seq_stride; vc += (size_t)slot * seq_stride;
-    const int Tpad = (T + 7) & ~7;
-    float *sc = reinterpret_cast<float *>(smem);                  // [Tpad]
-    __half *ph = reinterpret_cast<__half *>(sc + Tpad);           // [Tpad]
-    __half *qh = ph + Tpad;                                       // [HD]
-    __half *knew = qh + HD, *vnew = knew + RM * HD;               // [RM][HD] each: rows 0 .. t of this pass
-    float *part = reinterpret_cast<float *>(vnew + RM * HD);      // [P][HD]
-    __shared__ float s_red[AT_THREADS / 64];
-    __shared__ double s_dred[AT_THREADS / 64];
-    const float scale = 1.0f / sqrtf((float)HD);
-    const size_t qo = (size_t)t * E + (size_t)h * HD;
-    if (tid < (t + 1) * (HD / 2)) {
-        const int r = tid / (HD / 2), i = tid % (HD / 2), pr = p0 + r;
-        const size_t ro = (size_t)r * E + (size_t)h * HD;
-        const float c = cos_tab[(size_t)pr * (HD / 2) + i], s = sin_tab[(size_t)pr * (HD / 2) + i];
-        const float k0 = kin[ro + 2 * i], k1 = kin[ro + 2 * i + 1];
-        const __half2 kr = __floats2half2_rn(k0 * c - k1 * s, k0 * s + k1 * c);
-        const __half2 vr = __floats2half2_rn(vin[ro + 2 * i], vin[ro + 2 * i + 1]);
-        *reinterpret_cast<__half2 *>(knew + r * HD + 2 * i) = kr; *reinterpret_cast<__half2 *>(vnew + r * HD + 2 * i) = vr;
-        if (r == t) {
-            const float q0 = q[qo + 2 * i], q1 = q[qo + 2 * i + 1];
-            *reinterpret_cast<__half2 *>(qh + 2 * i) = __floats2half2_rn(q0 * c - q1 * s, q0 * s + q1 * c);
-            const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
-            *reinterpret_cast<__half2 *>(kc + co) = kr; *reinterpret_cast<__half2 *>(vc + co) = vr;
-        }
-    }
-    __syncthreads();
-    unsigned qreg[HD / 2];
-#pragma unroll
-    for (int i = 0; i < HD / 8; i++) { const int4 v4 = *reinterpret_cast<const int4 *>(qh + 8 * i); qreg[4 * i] = (unsigned)v4.x; qreg[4 * i + 1] = (unsigned)v4.y; qreg[4 * i + 2] = (unsigned)v4.z; qreg[4 * i + 3] = (unsigned)v4.w; }
-    auto dot_row = [&](const __half *kr) {
-        int4 kk[HD / 8];
-#pragma unroll
-        for (int i = 0; i < HD / 8; i++) kk[i] = ld16(kr + 8 * i);
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < HD / 8; i++) {
-            const unsigned w[4] = {(unsigned)kk[i].x, (unsigned)kk[i].y, (unsigned)kk[i].z, (unsigned)kk[i].w};
-#pragma unroll
-            for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), h2f_bits(qreg[4 * i + e] & 0xFFFF), s); s = fmaf(h2f_bits(w[e] >> 16), h2f_bits(qreg[4 * i + e] >> 16), s); }
-        }
-        return s * scale;
-    };
-    const int c = tid % CH, p = tid / CH;
-    const __half *kb = kc + (size_t)h * HD + 8 * c, *vb = vc + (size_t)h * HD + 8 * c;
-    constexpr int NPRE = 16;
-    const int gmax = max(p0 - 1, 0);                              // the last row the cache is read at: rows from p0 on are written by this launch
-    int4 kpre[NPRE], vpre[NPRE];
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) kpre[i] = ld16(kb + (size_t)min(p + i * P, gmax) * E);
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) vpre[i] = ld16(vb + (size_t)min(p + i * P, gmax) * E);
-    // this partition's key among the pass's earlier rows, if any: row rl at position jl (jl mod P == p)
-    const int rl = (p - p0) & (P - 1);
-    const int jl = rl < t ? p0 + rl : -1;
-    const int4 kl = *reinterpret_cast<const int4 *>(knew + min(rl, RM - 1) * HD + 8 * c), vl = *reinterpret_cast<const int4 *>(vnew + min(rl, RM - 1) * HD + 8 * c);
-    float qd[8];
-    {
-        const int4 q4 = *reinterpret_cast<const int4 *>(qh + 8 * c);
-        const unsigned w[4] = {(unsigned)q4.x, (unsigned)q4.y, (unsigned)q4.z, (unsigned)q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) { qd[2 * e] = h2f_bits(w[e] & 0xFFFF); qd[2 * e + 1] = h2f_bits(w[e] >> 16); }
-    }
-    auto dot16 = [&](const int4 &kk) {
-        const unsigned w[4] = {(unsigned)kk.x, (unsigned)kk.y, (unsigned)kk.z, (unsigned)kk.w};
-        float s = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), qd[2 * e], s); s = fmaf(h2f_bits(w[e] >> 16), qd[2 * e + 1], s); }
-        s += dpp_f<0xB1>(s); s += dpp_f<0x4E>(s);
-        if (CH >= 8) s += dpp_f<0x141>(s);
-        if (CH >= 16) s += dpp_f<0x140>(s);
-        return s * scale;
-    };
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; const float s = dot16(j == jl ? kl : kpre[i]); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
-    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {
-        int4 kk[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) kk[i] = ld16(kb + (size_t)min(j0 + i * P, gmax) * E);
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; const float s = dot16(j == jl ? kl : kk[i]); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
-    }
-    if (tid == AT_THREADS - 1) { const float s = dot_row(knew + t * HD); sc[pos] = s; mx = fmaxf(mx, s); }
-    mx = wave_max(mx);
-    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
-    __syncthreads();
-    mx = s_red[0];
-#pragma unroll
-    for (int i = 1; i < AT_THREADS / 64; i++) mx = fmaxf(mx, s_red[i]);
-    double sum = 0.0;
-    for (int j = tid; j < T; j += AT_THREADS) { const float v = exp_h(tb.exp, sc[j] - mx); sc[j] = v; sum += (double)v; }
-    sum = wave_sum_d(sum);
-    if ((tid & 63) == 0) s_dred[tid >> 6] = sum;
-    __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int i = 0; i < AT_THREADS / 64; i++) tot += s_dred[i];
-    const float inv = (float)(1.0 / tot);
-    for (int j = tid; j < T; j += AT_THREADS) ph[j] = f2h_rn(sc[j] * inv);
-    __syncthreads();
-    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto pv_acc = [&](const int4 &vv, const int j) {
-        const float pj = __half2float(ph[j]);
-        const unsigned w[4] = {(unsigned)vv.x, (unsigned)vv.y, (unsigned)vv.z, (unsigned)vv.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) { o[2 * e] = fmaf(h2f_bits(w[e] & 0xFFFF), pj, o[2 * e]); o[2 * e + 1] = fmaf(h2f_bits(w[e] >> 16), pj, o[2 * e + 1]); }
-    };
-#pragma unroll
-    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; if (j < Tg) pv_acc(j == jl ? vl : vpre[i], j); }
-    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {
-        int4 vv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) vv[i] = ld16(vb + (size_t)min(j0 + i * P, gmax) * E);
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; if (j < Tg) pv_acc(j == jl ? vl : vv[i], j); }
-    }
-    if (p == P - 1) {
-        const float pj = __half2float(ph[pos]);
-#pragma unroll
-        for (int e = 0; e < 8; e++) o[e] = fmaf(__half2float(vnew[t * HD + 8 * c + e]), pj, o[e]);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) part[p * HD + 8 * c + e] = o[e];
-    __syncthreads();
-    for (int i = tid; i < HD; i += AT_THREADS) { float s = 0.0f;
-#pragma unroll 8
-        for (int pp = 0; pp < P; pp++) s += part[pp * HD + i];
-        out[qo + i] = s; }
+    constexpr bool FUSED = true, BATCHED = true, DRAFT = true;
+#include "attn_llm_body.hpp"
 }
-template <int HD>
-static void launch_attn_draft_hd(float *q, const float *k, const float *v, __half *kc, __half *vc, int R, int n_head, const int *n_past, const int *row_slot, size_t seq_stride,
-                                 int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
-    const int Tpad = (n_ctx + 7) & ~7;
-    const size_t lds = (size_t)Tpad * 6 + (size_t)HD * 2 + (size_t)2 * DRAFT_ROWS * HD * 2 + (size_t)(AT_THREADS / (HD / 8)) * HD * 4 + 64;
+
+// the supported head sizes as compile-time constants: f(std::integral_constant<int, HD>) for hd's HD; false (f not called) for an unsupported head size
+template <class F> static bool attn_for_head_size(int hd, F &&f) {
+    switch (hd) {
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
+    case 128: f(std::integral_constant<int, 128>{}); return true;
+    default: return false;
+    }
+}
+// the decode launchers' answer to an unsupported head size (the prompt launchers return false instead)
+template <class F> static void attn_for_head_size_or_throw(int hd, F &&f) {
+    if (!attn_for_head_size(hd, f)) throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
+}
+// The one launcher of the body's kernels: grid (head, row), the layout's LDS, the > 64 KiB opt-in at the first launch of a form (the plain and the one-row fused
+// form together, as they always were).
+template <int HD, bool BATCHED, bool DRAFT>
+static void launch_attn_body(bool fused, float *q, const float *k, const float *v, __half *kc, __half *vc, int rows, int n_head, const int *n_past, const int *row_slot,
+                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+    const size_t lds = attn_lds_bytes(n_ctx, HD, DRAFT ? DRAFT_ROWS : 1);
+    const dim3 grid((unsigned)n_head, (unsigned)rows);
     static bool attr = false;
-    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_draft<HD>)); attr = true; }
-    note_kernel("k_attn_llm_draft<%d>", HD);
-    hipLaunchKernelGGL((k_attn_llm_draft<HD>), dim3((unsigned)n_head, (unsigned)R), dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, n_ctx, cos_tab, sin_tab, tb, out,
-                       row_slot, seq_stride);
+    if constexpr (DRAFT) {
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_draft<HD>)); attr = true; }
+        note_kernel("k_attn_llm_draft<%d>", HD);
+        hipLaunchKernelGGL((k_attn_llm_draft<HD>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, n_ctx, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+    } else if constexpr (BATCHED) {
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, true>)); attr = true; }
+        hipLaunchKernelGGL((k_attn_llm<HD, true, true>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+    } else {
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true>));
+                     HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, false>)); attr = true; }
+        note_kernel("k_attn_llm<%d, %s, false>", HD, fused ? "true" : "false");
+        hipLaunchKernelGGL((fused ? k_attn_llm<HD, true> : k_attn_llm<HD, false>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out,
+                           row_slot, seq_stride);
+    }
 }
+// fused = true (N must be 1): q,k,v are the raw projections; RoPE + KV append happen inside.  fused = false: launch_rope_kv must have run.
+void launch_attn_llm(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int N, int n_head, int hd, const int *n_past, int n_ctx,
+                     const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s) {
+    attn_for_head_size_or_throw(hd, [&](auto tag) {
+        launch_attn_body<decltype(tag)::value, false, false>(fused, q, k, v, kcache, vcache, fused ? 1 : N, n_head, n_past, nullptr, 0, n_ctx, cos_tab, sin_tab, tb, out, s); });
+}
+// Decode attention for B rows of B different conversations (RoPE + KV append fused): row t uses position n_past[row_slot[t]] and the caches of that conversation.
+void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int B, int n_head, int hd, const int *n_past, const int *row_slot,
+                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+    attn_for_head_size_or_throw(hd, [&](auto tag) {
+        launch_attn_body<decltype(tag)::value, true, false>(true, q, k, v, kcache, vcache, B, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); });
+}
+// Verify pass: R <= DRAFT_ROWS rows of the conversation row_slot[0] (the DRAFT form above); n_ctx <= attn_draft_max_ctx(hd)
 void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int R, int n_head, int hd, const int *n_past, const int *row_slot,
                            size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
     if (R < 1 || R > DRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_attn_llm_draft: row count out of range", __FILE__, __LINE__};
-    switch (hd) {
-    case 32: launch_attn_draft_hd<32>(q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
-    case 64: launch_attn_draft_hd<64>(q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
-    case 128: launch_attn_draft_hd<128>(q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); break;
-    default: throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
-    }
+    attn_for_head_size_or_throw(hd, [&](auto tag) {
+        launch_attn_body<decltype(tag)::value, true, true>(true, q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); });
 }
 // =====================================================================================================================
 // Key-split decode attention (long contexts): k_attn_llm above puts ONE workgroup on a head -- 40 workgroups on a 256-CU chip, 0.015 us per cached key, 35 us per layer
@@ -2124,34 +1905,19 @@ __global__ __launch_bounds__(AS_THREADS) void k_attn_split_scores(const float *_
     if (tid < HD / 2) {
         const int i = tid;
         const float cs = cos_tab[(size_t)pos * (HD / 2) + i], sn = sin_tab[(size_t)pos * (HD / 2) + i];
-        const float q0 = q[qo + 2 * i], q1 = q[qo + 2 * i + 1], k0 = kin[qo + 2 * i], k1 = kin[qo + 2 * i + 1];
-        const __half2 qr = __halves2half2(f2h_rn(q0 * cs - q1 * sn), f2h_rn(q0 * sn + q1 * cs)), kr = __halves2half2(f2h_rn(k0 * cs - k1 * sn), f2h_rn(k0 * sn + k1 * cs));
-        *reinterpret_cast<__half2 *>(qh + 2 * i) = qr; *reinterpret_cast<__half2 *>(knew + 2 * i) = kr;
+        const float2 qf = rope_rot(q[qo + 2 * i], q[qo + 2 * i + 1], cs, sn), kf = rope_rot(kin[qo + 2 * i], kin[qo + 2 * i + 1], cs, sn);
+        const __half2 qr = __halves2half2(f2h_rn(qf.x), f2h_rn(qf.y)), kr = __halves2half2(f2h_rn(kf.x), f2h_rn(kf.y));
+        st_h2(qh + 2 * i, qr); st_h2(knew + 2 * i, kr);
         if (sp == 0) {
             const __half2 vr = __halves2half2(f2h_rn(vin[qo + 2 * i]), f2h_rn(vin[qo + 2 * i + 1]));
             const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
-            *reinterpret_cast<__half2 *>(kc + co) = kr; *reinterpret_cast<__half2 *>(vc + co) = vr;
-            *reinterpret_cast<__half2 *>(qrot + qo + 2 * i) = qr;   // (diagnostics / tests)
+            st_h2(kc + co, kr); st_h2(vc + co, vr);
+            st_h2(qrot + qo + 2 * i, qr);                           // (diagnostics / tests)
         }
     }
     __syncthreads();
     float qd[8];
-    {
-        const int4 q4 = *reinterpret_cast<const int4 *>(qh + 8 * c);
-        const unsigned w[4] = {(unsigned)q4.x, (unsigned)q4.y, (unsigned)q4.z, (unsigned)q4.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) { qd[2 * e] = h2f_bits(w[e] & 0xFFFF); qd[2 * e + 1] = h2f_bits(w[e] >> 16); }
-    }
-    auto dot16 = [&](const int4 &kv) {
-        const unsigned w[4] = {(unsigned)kv.x, (unsigned)kv.y, (unsigned)kv.z, (unsigned)kv.w};
-        float s = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), qd[2 * e], s); s = fmaf(h2f_bits(w[e] >> 16), qd[2 * e + 1], s); }
-        s += dpp_f<0xB1>(s); s += dpp_f<0x4E>(s);
-        if (CH >= 8) s += dpp_f<0x141>(s);
-        if (CH >= 16) s += dpp_f<0x140>(s);
-        return s * scale;
-    };
+    unpack8(*reinterpret_cast<const int4 *>(qh + 8 * c), qd);
     float *srow = scores + (size_t)h * ld_scores;
     for (int j0 = j_lo + p; j0 < j_hi; j0 += NR * P) {
         int4 nx[NR];
@@ -2159,7 +1925,7 @@ __global__ __launch_bounds__(AS_THREADS) void k_attn_split_scores(const float *_
 #pragma unroll
         for (int i = 0; i < NR; i++) nx[i] = ld16(kb + (size_t)min(j0 + (NR + i) * P, j_cl) * E);
 #pragma unroll
-        for (int i = 0; i < NR; i++) { const int j = j0 + i * P; const float s = dot16(kk[i]); if (j < j_hi && c == 0) srow[j] = s; }
+        for (int i = 0; i < NR; i++) { const int j = j0 + i * P; const float s = dot16<CH>(kk[i], qd, scale); if (j < j_hi && c == 0) srow[j] = s; }
         (void)more;
 #pragma unroll
         for (int i = 0; i < NR; i++) kk[i] = nx[i];
@@ -2218,12 +1984,7 @@ __global__ __launch_bounds__(AS_THREADS) void k_attn_split_pv(const float *__res
 #pragma unroll
         for (int i = 0; i < NR; i++) {
             const int j = j0 + i * P;
-            if (j < j_hi) {
-                const float pj = __half2float(f2h_rn(sc[j] * inv));
-                const unsigned w[4] = {(unsigned)vv[i].x, (unsigned)vv[i].y, (unsigned)vv[i].z, (unsigned)vv[i].w};
-#pragma unroll
-                for (int e = 0; e < 4; e++) { o[2 * e] = fmaf(h2f_bits(w[e] & 0xFFFF), pj, o[2 * e]); o[2 * e + 1] = fmaf(h2f_bits(w[e] >> 16), pj, o[2 * e + 1]); }
-            }
+            if (j < j_hi) pv_acc(o, vv[i], __half2float(f2h_rn(sc[j] * inv)));
         }
 #pragma unroll
         for (int i = 0; i < NR; i++) vv[i] = nx[i];
@@ -2277,12 +2038,7 @@ static void launch_attn_split_hd(float *q, const float *k, const float *v, __hal
 // decode (one row): RoPE + KV append + attention with the keys of every head shared by `splits` workgroups; `ws` >= attn_split_workspace_bytes(...), its last 1 KiB zeroed once
 void launch_attn_llm_split(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int n_head, int hd, const int *n_past, int n_ctx, const float *cos_tab,
                            const float *sin_tab, const Tables &tb, float *out, void *ws, int splits, hipStream_t s) {
-    switch (hd) {
-    case 32: launch_attn_split_hd<32>(q, k, v, kcache, vcache, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, ws, splits, s); break;
-    case 64: launch_attn_split_hd<64>(q, k, v, kcache, vcache, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, ws, splits, s); break;
-    case 128: launch_attn_split_hd<128>(q, k, v, kcache, vcache, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, ws, splits, s); break;
-    default: throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
-    }
+    attn_for_head_size_or_throw(hd, [&](auto tag) { launch_attn_split_hd<decltype(tag)::value>(q, k, v, kcache, vcache, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, ws, splits, s); });
 }
 
 // =====================================================================================================================
@@ -2929,38 +2685,20 @@ static bool launch_attn_prefill_seg_hd(const float *q, const __half *kc, const _
 bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, hipStream_t s, __half *out_h,
                              bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
-    switch (hd) {
-    case 32: return launch_attn_prefill_seg_hd<32>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h);
-    case 64: return launch_attn_prefill_seg_hd<64>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h);
-    case 128: return launch_attn_prefill_seg_hd<128>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h);
-    default: return false;
-    }
+    bool done = false;                                             // an unsupported head size: declined, like a shape that does not fit
+    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_seg_hd<decltype(tag)::value>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h); });
+    return done;
 }
 // N > 1 query rows at positions *n_past .. *n_past + N - 1 (launch_rope_kv has run); t_max >= *n_past + N (the host's view, sizes the LDS score rows).
 // false -> the score rows do not fit LDS (very long contexts): the caller runs launch_attn_llm instead.
 bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s,
                          __half *out_h, bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
-    switch (hd) {
-    case 32: return launch_attn_prefill_hd<32>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s, out_h, wrote_h);
-    case 64: return launch_attn_prefill_hd<64>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s, out_h, wrote_h);
-    case 128: return launch_attn_prefill_hd<128>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s, out_h, wrote_h);
-    default: return false;
-    }
+    bool done = false;
+    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_hd<decltype(tag)::value>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s, out_h, wrote_h); });
+    return done;
 }
 bool attn_head_size_supported(int hd) { return hd == 32 || hd == 64 || hd == 128; }
-static size_t attn_lds_bytes(int n_ctx, int hd) { const int Tpad = (n_ctx + 7) & ~7; return (size_t)Tpad * 6 + (size_t)hd * 6 + (size_t)(AT_THREADS / (hd / 8)) * hd * 4 + 64; }
-int attn_max_ctx(int hd) { int n = 0; while (attn_lds_bytes(n + 8, hd) + 256 /* static reduction arrays */ <= 160 * 1024) n += 8; return n; }
-// fused = true (N must be 1): q,k,v are the raw projections; RoPE + KV append happen inside.  fused = false: launch_rope_kv must have run.
-void launch_attn_llm(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int N, int n_head, int hd, const int *n_past, int n_ctx,
-                     const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s) {
-    switch (hd) {
-    case 32: launch_attn_hd<32>(q, k, v, kcache, vcache, N, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, fused, s); break;
-    case 64: launch_attn_hd<64>(q, k, v, kcache, vcache, N, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, fused, s); break;
-    case 128: launch_attn_hd<128>(q, k, v, kcache, vcache, N, n_head, n_past, n_ctx, cos_tab, sin_tab, tb, out, fused, s); break;
-    default: throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
-    }
-}
 
 // =====================================================================================================================
 // MINIGPT4_PARITY=1 attention: the oracle's loops (oracle/refcpu.c orc_llama_eval, = ggml's mul_mat(K, Q) / soft_max / mul_mat(V, P) on f16 operands) with every fp32
@@ -2988,14 +2726,12 @@ __global__ __launch_bounds__(256) void k_attn_ref(const float *__restrict__ q, c
             const int i = tid, pos = T - 1;
             const float c = cos_tab[(size_t)pos * (hd / 2) + i], s = sin_tab[(size_t)pos * (hd / 2) + i];
             const size_t o = (size_t)h * hd + 2 * i;
-            const float q0 = q[o], q1 = q[o + 1];
-            const float r0 = q0 * c - q1 * s, r1 = q0 * s + q1 * c;
-            qh[2 * i] = f2h_rn(r0); qh[2 * i + 1] = f2h_rn(r1);
-            const float k0 = kraw[o], k1 = kraw[o + 1];
+            const float2 qr = rope_rot(q[o], q[o + 1], c, s);
+            qh[2 * i] = f2h_rn(qr.x); qh[2 * i + 1] = f2h_rn(qr.y);
             const size_t co = (size_t)pos * E + (size_t)h * hd + 2 * i;
-            const __half2 kk = __floats2half2_rn(k0 * c - k1 * s, k0 * s + k1 * c), vv = __floats2half2_rn(vraw[o], vraw[o + 1]);
-            *reinterpret_cast<__half2 *>(kc + co) = kk; *reinterpret_cast<__half2 *>(vc + co) = vv;
-            *reinterpret_cast<__half2 *>(knew + 2 * i) = kk; *reinterpret_cast<__half2 *>(vnew + 2 * i) = vv;
+            const __half2 kk = rope_rot_h2(kraw[o], kraw[o + 1], c, s), vv = __floats2half2_rn(vraw[o], vraw[o + 1]);
+            st_h2(kc + co, kk); st_h2(vc + co, vv);
+            st_h2(knew + 2 * i, kk); st_h2(vnew + 2 * i, vv);
         }
     } else {
         for (int i = tid; i < hd; i += 256) qh[i] = __float2half_rn(q[(size_t)t * E + (size_t)h * hd + i]);

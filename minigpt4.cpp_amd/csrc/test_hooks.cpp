@@ -778,7 +778,7 @@ int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slot
 int minigpt4_amd_test_attn_draft(int mode, int n_head, int hd, int n_ctx, int n_slot, int slot, int n_past, int R, int computed_exp, const float *q, const float *k, const float *v,
                                  uint16_t *kc, uint16_t *vc, float *out) {
     if (!q || !k || !v || !kc || !vc || !out || (mode != 0 && mode != 1) || (hd != 32 && hd != 64 && hd != 128) || n_head < 1 || n_slot < 1 || slot < 0 || slot >= n_slot ||
-        R < 1 || R > DRAFT_ROWS || n_past < 0 || n_ctx < 1 || n_past > n_ctx - R || n_ctx > attn_max_ctx(hd)) return 1;
+        R < 1 || R > DRAFT_ROWS || n_past < 0 || n_ctx < 1 || n_past > n_ctx - R || n_ctx > attn_draft_max_ctx(hd)) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
         const size_t E = (size_t)n_head * hd, stride = (size_t)n_ctx * E, cache = (size_t)n_slot * stride, RE = (size_t)R * E;

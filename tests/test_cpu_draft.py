@@ -55,7 +55,18 @@ def test_null_context_is_refused_with_the_function_name(lib):
     assert L.minigpt4_amd_last_error().startswith(b"decode_lookup")
 
 
+def _verify_form_max_ctx(hd):
+    """The largest n_ctx (a multiple of 8) whose verify-pass attention launch fits a CU's LDS, from the layout alone: 160 KiB hold 256 bytes of static reduction arrays
+    and, dynamically, n_ctx fp32 scores + n_ctx fp16 probabilities (n_ctx padded to 8), the fp16 q row [hd], 8 new key rows and 8 new value rows in fp16 [8][hd] each
+    (the one-row forms keep one of each), the fp32 partial outputs [P][hd] of the P = 512 / (hd / 8) key partitions, and 64 spare bytes."""
+    fixed = 256 + hd * 2 + 2 * 8 * hd * 2 + (512 // (hd // 8)) * hd * 4 + 64
+    return (160 * 1024 - fixed) // (4 + 2) // 8 * 8
+
+
 def test_attention_hook_refuses_bad_arguments_without_a_device(lib):
+    """Every bad argument is refused (1) before a device is looked for (2 on a box without one).  The context bound is the verify form's own, derived in
+    _verify_form_max_ctx from the LDS layout: at head size 128 a context of 23 792 rows is accepted as far as the device check and 23 800 is refused, although the
+    one-row kernel (and with it the model load) admits 24 392; the same pair at the bound and 8 rows above it holds for head sizes 64 and 32."""
     T = lib.library.minigpt4_amd_test_attn_draft
     n_head, hd, n_ctx, n_slot = 2, 64, 16, 2
     E = n_head * hd
@@ -80,6 +91,13 @@ def test_attention_hook_refuses_bad_arguments_without_a_device(lib):
     assert call(n_past=14, R=3) == 1                          # the last row would sit at position n_ctx
     assert call(n_past=16, R=1) == 1
     assert call(n_ctx=1 << 24, n_past=0) == 1                 # more score rows than the kernel's LDS holds
+    assert _verify_form_max_ctx(128) == 23792
+    no_device = lib.amd_device_count() <= 0
+    for hd_ in (128, 64, 32):
+        fits = _verify_form_max_ctx(hd_)
+        if no_device:
+            assert call(hd=hd_, n_ctx=fits, n_past=0) == 2, (hd_, fits)       # accepted as far as the device check (the arrays are never touched)
+        assert call(hd=hd_, n_ctx=fits + 8, n_past=0) == 1, (hd_, fits)       # 8 rows more: the launch would not fit
 
 
 def ref_draft(h, ngram_max, ngram_min, n_draft):

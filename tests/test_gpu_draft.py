@@ -397,3 +397,30 @@ def test_decode_lookup_emits_the_greedy_text_whatever_the_corpus(gpu_lib, contex
             assert r["accepted"] > 0 and r["passes"] + r["steps"] < N_ORACLE, r
     with pytest.raises(RuntimeError, match="decode_lookup: n_draft"):
         gpu_lib.amd_decode_lookup(ctx, [], 4, n_draft=8)
+
+
+def test_speculation_is_refused_where_the_verify_attention_does_not_fit(gpu_lib, tiny_files):
+    """The verify pass keeps 8 new key / value rows in the attention kernel's LDS where the decode step keeps one, so it ends at a smaller context than the load admits.
+    Head size 64 (the tiny files): 160 KiB = 256 B static + 6 B per context row + q [64] + 2 x [8][64] fp16 + partial outputs [64][64] fp32 + 64 spare -> 24 160 rows.
+    At that n_ctx a full 8-row pass launches (its LDS is sized by n_ctx) and keeps the oracle's tokens; 8 rows more, set_speculation refuses and the setting stays off."""
+    vp, llm = tiny_files
+    lp = llm("q4_0", "none", conditioned=True)
+    G, _, _ = oracle(lp)
+    fits = (160 * 1024 - (256 + 64 * 2 + 2 * 8 * 64 * 2 + 64 * 64 * 4 + 64)) // 6 // 8 * 8
+    assert fits == 24160
+    for n_ctx in (fits + 8, fits):
+        ctx = gpu_lib.minigpt4_model_load(vp, lp, verbosity=0, n_ctx=n_ctx, n_batch=32)
+        try:
+            if n_ctx > fits:
+                with pytest.raises(RuntimeError, match="set_speculation: n_ctx"):
+                    gpu_lib.amd_set_speculation(ctx, 7)
+                begin(gpu_lib, ctx)
+                with pytest.raises(RuntimeError, match="speculation is off"):
+                    gpu_lib.amd_verify_draft(ctx, [G[1]])
+                gpu_lib.amd_set_speculation(ctx, 0)                # switching off is never refused
+            else:
+                gpu_lib.amd_set_speculation(ctx, 7)
+                begin(gpu_lib, ctx)
+                assert list(gpu_lib.amd_verify_draft(ctx, list(G[1:8]))["ids"]) == list(G[:8])
+        finally:
+            gpu_lib.minigpt4_free(ctx)
