@@ -213,6 +213,50 @@ MINIGPT4_API int minigpt4_amd_verify_draft(struct MiniGPT4Context *ctx, const in
 MINIGPT4_API int minigpt4_amd_decode_lookup(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft,
                                             int32_t *tokens_out, int32_t *n_tokens, int32_t stats[4]);
 
+/* ---- repetition, frequency and presence penalties; logit bias (llama.cpp master-31cfbb1: llama_sample_repetition_penalty, llama_sample_frequency_and_presence_penalties,
+ * applied in the order of llama.cpp's main) ------------------------------------------------------------------------------------------------------------------------------
+ * The reference accepts repeat_last_n, repeat_penalty, alpha_presence, alpha_frequency and penalize_nl in minigpt4_end_chat(_image) and ignores them.  So does this library
+ * BY DEFAULT (bit-compatibility); the mode below is an opt-in.
+ * NEUTRAL VALUES ARE repeat_penalty 1.0, alpha_presence 0.0, alpha_frequency 0.0.  THE REFERENCE BINDING'S DEFAULTS FOR THE TWO ALPHAS ARE 1.0: a caller who switches the
+ * mode on and keeps those defaults gets a frequency penalty of 1 per occurrence plus a presence penalty of 1 on every token of the window.
+ * HISTORY.  Every conversation keeps a row-aligned token history: entry r is the token id of cache row r, or -1 for a row that came in as an embedding (the 32 image rows,
+ * minigpt4_amd_eval_embd).  Prompt passes, batched steps (forced ids included), scoring, draft verification (kept rows only), forks (whole or prefix copy), prefix-cache hits
+ * all keep it in step; minigpt4_reset_chat and minigpt4_amd_set_conversations clear it (set_conversations also resets parameters and bias); a context shift REMOVES the
+ * shifted rows from it.  minigpt4_amd_decode_loop and minigpt4_amd_profile_sites feed tokens back on the device and are measurement entry points: their rows enter as -1.
+ * Rows that are queued but not evaluated count, because sampling evaluates them first.
+ * WINDOW.  The last min(len(history), W) entries, W = n_ctx if repeat_last_n < 0, else repeat_last_n, clamped to 1024.  A -1 entry takes a place in the window and
+ * penalises nothing.  count[id] = occurrences of id in the window.
+ * ARITHMETIC on a copy of the logits row l, every operation rounded to fp32 on its own (no fused multiply-add):
+ *   1. l[id] += bias[id] for each bias pair;   2. nl = l[13] (13 = llama_token_nl(); skipped when n_vocab <= 13);
+ *   3. window non-empty and repeat_penalty != 1: for every id with count > 0, l = (l <= 0) ? l * repeat_penalty : l / repeat_penalty;
+ *   4. window non-empty and not both alphas 0: for every id with count > 0, t = float(count) * alpha_frequency; t = t + alpha_presence; l = l - t;
+ *   5. !penalize_nl: l[13] = nl (the value AFTER the bias).
+ * With temp <= 0 the pick is the FIRST maximum of the result (lowest id among equal values, -0.0 == +0.0), found by one kernel launch (k_pen_pick) over all listed
+ * conversations of the call -- no logits row travels to the host; with temp > 0 the result feeds the sampling chain (top-k, mirostat, ... see penalised logits, as in
+ * llama.cpp).  Host and device share one definition of the arithmetic and agree bit for bit; parity mode changes nothing here: the transformation is exact and the same.
+ * The logits themselves are never modified: minigpt4_amd_get_logits, the scoring calls, minigpt4_amd_top_logprobs and the report of minigpt4_amd_end_chat_batch_top keep
+ * describing the RAW distribution (a log-probability is that of the raw logits, as promised above).
+ * minigpt4_amd_verify_draft, minigpt4_amd_decode_lookup and minigpt4_amd_decode_loop decide on raw logits and ignore penalties and bias; their tokens still enter the history.
+ * A conversation whose transformation is the identity (neutral parameters or an empty window, and no bias) takes exactly the path it takes with the mode off: no launch,
+ * no copy, no allocation.  The feature's buffers are allocated by its first launch.
+ * minigpt4_amd_set_penalties: on = 0 (default; also MINIGPT4_PENALTIES=1 in the environment at load switches it on, for the reference's unmodified binding and web UI): the
+ * five arguments are ignored.  on = 1: minigpt4_end_chat(_image) first stores its five arguments as the selected conversation's parameters (arguments that
+ * minigpt4_amd_conversation_penalties would refuse are not stored; minigpt4_amd_last_error says so), then samples with them.  Returns 0, or 1 without a context.
+ * minigpt4_amd_conversation_penalties: stores a conversation's parameters (default: 64, 1.0, 0.0, 0.0, 1); they take effect only while the mode is on.
+ * minigpt4_amd_end_chat_batch, minigpt4_amd_end_chat_batch_top and minigpt4_amd_sample have no penalty arguments and use each conversation's stored parameters.  Refused
+ * (1, "conversation_penalties: ...", nothing changed): a slot out of range, repeat_penalty <= 0 or not finite, an alpha that is not finite.
+ * minigpt4_amd_set_logit_bias: the selected conversation's bias, at most 256 (id, bias) pairs, n = 0 clears it; active WHATEVER the mode; -INFINITY bans a token.  It
+ * survives minigpt4_reset_chat.  Refused (1, "set_logit_bias: ...", nothing changed): NaN or +INFINITY, an id outside [0, n_vocab), a duplicate id, n < 0 or > 256.
+ * minigpt4_amd_token_history: evaluates the selected conversation's queued rows, writes the first min(count, cap) entries of its history to out (may be NULL) and returns
+ * the count (-1: no context, or the pass failed).
+ * minigpt4_amd_penalty_info: out = {mode, k_pen_pick launches so far, rows penalised on the host so far, table entries uploaded by the last launch}. */
+MINIGPT4_API int minigpt4_amd_set_penalties(struct MiniGPT4Context *ctx, int on);
+MINIGPT4_API int minigpt4_amd_conversation_penalties(struct MiniGPT4Context *ctx, int slot, int32_t repeat_last_n, float repeat_penalty, float alpha_presence,
+                                                     float alpha_frequency, int penalize_nl);
+MINIGPT4_API int minigpt4_amd_set_logit_bias(struct MiniGPT4Context *ctx, const int32_t *ids, const float *bias, int n);
+MINIGPT4_API int minigpt4_amd_token_history(struct MiniGPT4Context *ctx, int32_t *out, int cap);
+MINIGPT4_API int minigpt4_amd_penalty_info(struct MiniGPT4Context *ctx, int32_t out[4]);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

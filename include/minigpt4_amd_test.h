@@ -91,6 +91,20 @@ MINIGPT4_API int minigpt4_amd_test_logprob_rows(const float *logits, int rows, i
  * 1..64 or above n_vocab, a target >= n_vocab or < -1, a row_index entry outside [0, buf_rows), rows > buf_rows without row_index) */
 MINIGPT4_API int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *row_index, int rows, int top_n, const int32_t *targets,
                                              int32_t *ids_out, float *logprobs_out, int32_t *rank_out, float *target_logprob_out, float *ms_out);
+/* Penalties and logit bias (minigpt4_amd.h).  A table is [n][4] int32 words per entry: id, count, the bias's fp32 bit pattern, has_bias (0 / 1).
+ * minigpt4_amd_test_penalise_host, no GPU: builds the table for `history` (row-aligned ids, -1 = embedding row) and the bias pairs (distinct ids in [0, n_vocab), at most
+ * 256) with the engine's builder, applies it to row[n_vocab] in place with the host function, and writes the table to table_out (may be NULL; table_cap entries at
+ * most) and the builder's flags (1 = repetition step runs, 2 = frequency / presence step runs, 4 = the newline id is exempt) to flags_out (may be NULL).  Returns the
+ * number of table entries, or -1 on bad arguments.
+ * minigpt4_amd_test_pen_pick: the kernel (launch_pen_pick, one launch, one workgroup per row) on host logits [buf_rows][ld] fp32 (only the first n_vocab floats of a row
+ * are read).  rows = [n_rows][8] words: buffer row, first table entry, entries, flags, repeat_penalty / alpha_frequency / alpha_presence bit patterns, 0.  picked_out[n_rows]
+ * = the first maximum of each transformed row, adjusted_out[n_table] (may be NULL) = the transformed value of every table entry.  1 = bad arguments, before any device is
+ * touched (a NULL pointer, shapes < 1, ld < n_vocab, a row / table range / id out of range, duplicate ids within one row's table); 2 = no device; 3 = device error */
+MINIGPT4_API int minigpt4_amd_test_penalise_host(float *row, int n_vocab, const int32_t *history, int n_history, int n_ctx, int32_t repeat_last_n, float repeat_penalty,
+                                                 float alpha_presence, float alpha_frequency, int penalize_nl, const int32_t *bias_ids, const float *bias, int n_bias,
+                                                 int32_t *table_out, int table_cap, int32_t *flags_out);
+MINIGPT4_API int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
+                                            int32_t *picked_out, float *adjusted_out, float *ms_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

@@ -110,11 +110,14 @@ int minigpt4_begin_chat_image(struct MiniGPT4Context *ctx, struct MiniGPT4Embedd
     });
 }
 
-int minigpt4_end_chat_image(struct MiniGPT4Context *ctx, const char **token, size_t, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p, int32_t /*repeat_last_n*/,
-                            float /*repeat_penalty*/, float /*alpha_presence*/, float /*alpha_frequency*/, int mirostat, float mirostat_tau, float mirostat_eta, int /*penalize_nl*/) {
+int minigpt4_end_chat_image(struct MiniGPT4Context *ctx, const char **token, size_t, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p, int32_t repeat_last_n,
+                            float repeat_penalty, float alpha_presence, float alpha_frequency, int mirostat, float mirostat_tau, float mirostat_eta, int penalize_nl) {
     if (!ctx || !token) return E_None;
     Engine *e = E_(ctx);
     guarded(0, [&]() -> int {
+        // the five penalty arguments: ignored, like the reference (minigpt4.cpp:2425-2483), unless minigpt4_amd_set_penalties / MINIGPT4_PENALTIES switched them on; values
+        // minigpt4_amd_conversation_penalties would refuse leave the stored parameters as they were (last_error says so; the call itself reports nothing, as ever)
+        if (e->penalties()) (void)e->set_conversation_penalties(e->current_conversation(), PenParams{repeat_last_n, repeat_penalty, alpha_presence, alpha_frequency, penalize_nl});
         SampleParams p; p.temp = temp; p.top_k = top_k; p.top_p = top_p; p.tfs_z = tfs_z; p.typical_p = typical_p; p.mirostat = mirostat; p.mirostat_tau = mirostat_tau; p.mirostat_eta = mirostat_eta;
         const int id = e->sample_token(p);
         *token = e->id_to_token(id);
@@ -335,6 +338,32 @@ int minigpt4_amd_score_tokens_top(struct MiniGPT4Context *ctx, const int32_t *to
                                   float *top_logprobs_out) {
     if (!ctx) { set_last_error("score_tokens_top: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->score_tokens_top(tokens, n, top_n, logprob_out, rank_out, top_ids_out, top_logprobs_out); });
+}
+// ---- repetition / frequency / presence penalties, logit bias ----
+int minigpt4_amd_set_penalties(struct MiniGPT4Context *ctx, int on) {
+    if (!ctx) { set_last_error("set_penalties: no context"); return 1; }
+    E_(ctx)->set_penalties(on != 0);
+    return 0;
+}
+int minigpt4_amd_conversation_penalties(struct MiniGPT4Context *ctx, int slot, int32_t repeat_last_n, float repeat_penalty, float alpha_presence, float alpha_frequency, int penalize_nl) {
+    if (!ctx) { set_last_error("conversation_penalties: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_conversation_penalties(slot, PenParams{repeat_last_n, repeat_penalty, alpha_presence, alpha_frequency, penalize_nl}); });
+}
+int minigpt4_amd_set_logit_bias(struct MiniGPT4Context *ctx, const int32_t *ids, const float *bias, int n) {
+    if (!ctx) { set_last_error("set_logit_bias: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_logit_bias(ids, bias, n); });
+}
+int minigpt4_amd_token_history(struct MiniGPT4Context *ctx, int32_t *out, int cap) {
+    if (!ctx) { set_last_error("token_history: no context"); return -1; }
+    int count = -1;
+    guarded(1, [&]() -> int { count = E_(ctx)->token_history(out, out ? cap : 0); return count < 0; });
+    return count;
+}
+int minigpt4_amd_penalty_info(struct MiniGPT4Context *ctx, int32_t out[4]) {
+    if (!ctx || !out) { set_last_error(ctx ? "penalty_info: no output array" : "penalty_info: no context"); return 1; }
+    const Engine::PenInfo p = E_(ctx)->penalty_info();
+    out[0] = p.mode; out[1] = p.launches; out[2] = p.host_rows; out[3] = p.last_entries;
+    return 0;
 }
 // ---- speculation: draft tokens verified in one weight pass, greedy lookup decoding ------------------------------------------------------------
 int minigpt4_amd_set_speculation(struct MiniGPT4Context *ctx, int max_draft) {

@@ -97,6 +97,7 @@ Engine::~Engine() {
     prefix_free();
     score_free();
     topn_free();
+    pen_free();
     spec_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
@@ -183,6 +184,7 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     if (const char *tf = getenv("MINIGPT4_PARITY_TRACE")) { if (*tf) trace_file_ = fopen(tf, "wb"); }
     // oracle-order fp32 accumulation (forward_ref): bit-identical to the CPU oracle, slow
     parity_ = trace_file_ || (getenv("MINIGPT4_PARITY") && atoi(getenv("MINIGPT4_PARITY")));
+    pen_mode_ = getenv("MINIGPT4_PENALTIES") && atoi(getenv("MINIGPT4_PENALTIES"));   // the reference's unmodified binding / web UI: its penalty arguments are honoured
     if (const char *lm = getenv("MINIGPT4_LOAD")) load_mode_ = !strcmp(lm, "recv") ? LOAD_RECV : LOAD_FULL;
     // the exchange decides who reads the files: MINIGPT4_LOAD=recv on rank 0 would broadcast empty arenas
     if (dist.active()) load_mode_ = dist.rank != 0 ? LOAD_RECV : LOAD_FULL;
@@ -1249,6 +1251,7 @@ int Engine::eval_chunk(const int *row_tok, int N, const float *embd, const Score
         forward(p, stream_);                        // k_get_rows skips rows whose id is negative
     }
     cv.n_committed += N; cv.has_logits = true;
+    cv.hist.insert(cv.hist.end(), row_tok, row_tok + N);
     return 0;
 }
 
@@ -1312,7 +1315,7 @@ Engine::PrefixPlan Engine::prefix_lookup(const int *slots, int n) {
     if (pl.looked) pfx_.rows_last = 0;
     if (pl.n_hit) {
         prefix_copy_in(pl.hit, pl.n_hit, pl.rows);
-        for (int i = 0; i < n; i++) if (pl.m[i]) conv_[(size_t)slots[i]].n_committed = pl.m[i];
+        for (int i = 0; i < n; i++) if (pl.m[i]) { Conversation &cv = conv_[(size_t)slots[i]]; cv.n_committed = pl.m[i]; cv.hist.assign(cv.pend_tok.begin(), cv.pend_tok.begin() + pl.m[i]); }   // token rows: their ids are the queue's
     }
     return pl;
 }
@@ -1366,6 +1369,7 @@ int Engine::fork(int src, const int *dst, int n_dst, int n_rows) {
     for (int i = 0; i < n_dst; i++) {
         Conversation &cv = conv_[(size_t)dst[i]];
         cv.n_committed = rows; cv.drop_queue();
+        cv.hist.assign(sv.hist.begin(), sv.hist.begin() + rows);
         cv.has_logits = whole && sv.has_logits;
         if (logits_host_slot_ == dst[i]) logits_host_slot_ = -1;
         if (!whole) continue;
@@ -1415,6 +1419,7 @@ int Engine::shift_context(int n_keep, int n_discard) {
     launch_kv_shift(kc_ + (size_t)cur_ * L * C * E, vc_ + (size_t)cur_ * L * C * E, (int)L, n_ctx_, (int)E, (int)(E / llm_.n_head), n_keep, n_discard, cv.n_committed,
                     cos_, sin_, stream_);
     cv.n_committed -= n_discard; cv.n_past -= n_discard;
+    cv.hist.erase(cv.hist.begin() + n_keep, cv.hist.begin() + n_keep + n_discard);
     return 0;
 }
 int Engine::make_room(int n) {
@@ -1434,10 +1439,26 @@ const float *Engine::logits_host() {
     }
     return h_logits_;
 }
-int Engine::sample_token(const SampleParams &p) {
+int Engine::greedy_raw() {
     if (flush()) throw HipError{hipErrorUnknown, "deferred evaluation failed", __FILE__, __LINE__};
-    if (p.temp <= 0) { HIP_CHECK(hipStreamSynchronize(stream_)); return h_argmax_[cur_]; }   // greedy: argmax computed on the device
-    return sampler_.sample(logits_host(), (int)llm_.n_vocab, p);
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    return h_argmax_[cur_];                                                  // greedy: argmax computed on the device
+}
+int Engine::sample_token(const SampleParams &p) {
+    if (p.temp <= 0) { int id = greedy_raw(); pen_pick(&cur_, 1, &id); return id; }
+    if (flush()) throw HipError{hipErrorUnknown, "deferred evaluation failed", __FILE__, __LINE__};
+    const Conversation &cv = conv_[(size_t)cur_];
+    const float *raw = logits_host();
+    if (pen_mode_ || !cv.bias_id.empty()) {   // the chain sees penalised logits, as in llama.cpp; h_logits_ (minigpt4_amd_get_logits) stays raw
+        const int V = (int)llm_.n_vocab;
+        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
+        pen_row_.assign(raw, raw + V);
+        if (penalise_row(pen_row_.data(), V, cv.hist.data(), cv.hist.size(), pp, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size())) {
+            pen_info_.host_rows++;
+            return sampler_.sample(pen_row_.data(), V, p);
+        }
+    }
+    return sampler_.sample(raw, (int)llm_.n_vocab, p);
 }
 const char *Engine::id_to_token(int id) const {
     if (id == 2) return "</s>";   // llama_token_eos()
@@ -1468,6 +1489,7 @@ int Engine::decode_loop(int steps, int *tokens_out, float *ms_total) {
     if (ms_total) *ms_total = ms;
     HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
     cv.n_past += steps - 1; cv.n_committed += steps - 1;
+    cv.hist.back() = -1; cv.hist.insert(cv.hist.end(), (size_t)(steps - 1), -1);   // a measurement entry point: its rows' ids are not recorded
     if (logits_host_slot_ == cur_) logits_host_slot_ = -1;
     return 0;
 }
@@ -1489,7 +1511,7 @@ int Engine::profile_sites(int steps, std::string &json) {
         launch_delay(8000, stream_);
         HIP_CHECK(hipEventRecord(a, stream_));
         if (eval_chunk(&tok, 1, nullptr)) return 1;
-        cv.n_past += 1;
+        cv.n_past += 1; cv.hist.back() = -1;                                 // as decode_loop
         HIP_CHECK(hipEventRecord(b, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
         float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b)); tot += ms;
@@ -1595,7 +1617,9 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     if (forced) for (int i = 0; i < n; i++) if (forced[i] < 0 || forced[i] >= (int)llm_.n_vocab) { set_last_error("decode_batch: forced token id out of range"); return 1; }
     const SelectScope restore(this);
     // 1. pending prompt rows of each conversation (its own prefill pass), then sample
-    for (int i = 0; i < n; i++) { cur_ = slots[i]; ids_out[i] = sample_token(p); }
+    // (greedy with penalties or a bias: the raw ids first, then ONE launch over the listed conversations replaces those the transformation can change)
+    for (int i = 0; i < n; i++) { cur_ = slots[i]; ids_out[i] = p.temp <= 0 ? greedy_raw() : sample_token(p); }
+    if (p.temp <= 0) pen_pick(slots, n, ids_out);
     // 2. one weight pass for the conversations that still have room
     HIP_CHECK(hipStreamSynchronize(stream_));                                // h_bstage_ may still feed the previous step's copies
     // the report reads the rows the ids were drawn from: behind the sampling, ahead of the pass that overwrites them (one in-order stream); its copy back is queued here
@@ -1631,11 +1655,95 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
         const int sl = h_bstage_[MAX_CONVERSATIONS + r];
         Conversation &cv = conv_[(size_t)sl];
         cv.n_past += 1; cv.n_committed += 1; cv.has_logits = true;
+        cv.hist.push_back(h_bstage_[r]);
         if (logits_host_slot_ == sl) logits_host_slot_ = -1;
     }
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
     report();
     return 0;
+}
+
+// ---- penalties and logit bias (engine.hpp, penalty.hpp) ----
+void Engine::pen_alloc() {
+    if (pen_d_) return;
+    const size_t bytes = (size_t)MAX_CONVERSATIONS * (sizeof(PenRow) + (size_t)PEN_TABLE_MAX * sizeof(PenEntry));
+    try {
+        HIP_CHECK(hipMalloc((void **)&pen_d_, bytes)); HIP_CHECK(hipHostMalloc((void **)&pen_h_, bytes, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc((void **)&pen_out_d_, MAX_CONVERSATIONS * 4)); HIP_CHECK(hipHostMalloc((void **)&pen_out_h_, MAX_CONVERSATIONS * 4, hipHostMallocDefault));
+    } catch (...) { pen_free(); throw; }
+}
+void Engine::pen_free() {
+    if (pen_d_) HIP_IGNORE(hipFree(pen_d_));
+    if (pen_out_d_) HIP_IGNORE(hipFree(pen_out_d_));
+    if (pen_h_) HIP_IGNORE(hipHostFree(pen_h_));
+    if (pen_out_h_) HIP_IGNORE(hipHostFree(pen_out_h_));
+    pen_d_ = pen_h_ = nullptr; pen_out_d_ = pen_out_h_ = nullptr;
+}
+int Engine::pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const {
+    return pen_build_table(cv.hist.data(), cv.hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, (int)llm_.n_vocab, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size(), tab);
+}
+// The caller has evaluated every listed conversation's queue and synchronised (greedy_raw): hist is the whole history, the pinned staging is free.
+void Engine::pen_pick(const int *slots, int n, int *ids) {
+    bool any = pen_mode_;
+    for (int i = 0; i < n && !any; i++) any = !conv_[(size_t)slots[i]].bias_id.empty();
+    if (!any) return;                                                        // mode off, no bias: today's path
+    std::vector<PenEntry> tab;
+    int m = 0, map[MAX_CONVERSATIONS]; size_t off = 0;
+    PenRow *rows = nullptr; PenEntry *ent = nullptr;
+    for (int i = 0; i < n; i++) {
+        const Conversation &cv = conv_[(size_t)slots[i]];
+        if (!cv.has_logits) continue;
+        const int flags = pen_table(cv, tab);
+        if (!flags && tab.empty()) continue;                                 // the identity: the raw greedy id stands
+        if (!rows) { pen_alloc(); rows = reinterpret_cast<PenRow *>(pen_h_); ent = reinterpret_cast<PenEntry *>(pen_h_ + MAX_CONVERSATIONS * sizeof(PenRow)); }
+        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
+        rows[m] = PenRow{slots[i], (int)off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0};
+        std::copy(tab.begin(), tab.end(), ent + off);
+        off += tab.size(); map[m++] = i;
+    }
+    if (!m) return;
+    const size_t head = MAX_CONVERSATIONS * sizeof(PenRow);
+    HIP_CHECK(hipMemcpyAsync(pen_d_, pen_h_, head + off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
+    const int V = (int)llm_.n_vocab;
+    if (!launch_pen_pick(logits_, V, V, m, reinterpret_cast<const PenRow *>(pen_d_), reinterpret_cast<const PenEntry *>(pen_d_ + head), pen_out_d_, nullptr, stream_))
+        throw HipError{hipErrorInvalidValue, "penalised pick launch refused", __FILE__, __LINE__};
+    HIP_CHECK(hipMemcpyAsync(pen_out_h_, pen_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int r = 0; r < m; r++) {
+        if (pen_out_h_[r] < 0 || pen_out_h_[r] >= V) throw HipError{hipErrorUnknown, "the penalised pick reported an id outside the vocabulary", __FILE__, __LINE__};
+        ids[map[r]] = pen_out_h_[r];
+    }
+    pen_info_.launches++; pen_info_.last_entries = (int)off;
+}
+int Engine::set_conversation_penalties(int slot, const PenParams &p) {
+    auto refuse = [](const char *what) { set_last_error(std::string("conversation_penalties: ") + what); return 1; };
+    if (slot < 0 || slot >= (int)conv_.size()) return refuse("conversation index out of range");
+    if (!std::isfinite(p.repeat_penalty) || p.repeat_penalty <= 0.0f) return refuse("repeat_penalty must be finite and > 0");
+    if (!std::isfinite(p.alpha_presence) || !std::isfinite(p.alpha_frequency)) return refuse("alpha_presence and alpha_frequency must be finite");
+    conv_[(size_t)slot].pen = p;
+    return 0;
+}
+int Engine::set_logit_bias(const int *ids, const float *bias, int n) {
+    auto refuse = [](const char *what) { set_last_error(std::string("set_logit_bias: ") + what); return 1; };
+    if (n < 0 || n > PEN_BIAS_MAX) return refuse("n outside [0, 256]");
+    if (n > 0 && (!ids || !bias)) return refuse("ids and bias are required");
+    const int V = (int)llm_.n_vocab;
+    std::vector<int> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= V) return refuse("token id out of range");
+        if (bias[i] != bias[i] || bias[i] == INFINITY) return refuse("a bias must not be NaN or +infinity");
+        if (i && sorted[(size_t)i] == sorted[(size_t)i - 1]) return refuse("duplicate token id");
+    }
+    Conversation &cv = conv_[(size_t)cur_];
+    cv.bias_id.assign(ids, ids + n); cv.bias_val.assign(bias, bias + n);
+    return 0;
+}
+int Engine::token_history(int *out, int cap) {
+    if (flush()) return -1;
+    const Conversation &cv = conv_[(size_t)cur_];
+    if (out) for (int i = 0; i < cap && i < (int)cv.hist.size(); i++) out[i] = cv.hist[(size_t)i];
+    return (int)cv.hist.size();
 }
 
 // ---- speculation: draft tokens verified in one weight pass (engine.hpp) ----
@@ -1712,6 +1820,7 @@ int Engine::verify_draft(const int *draft, int n_draft, int *ids_out, int *n_out
         if (row_greedy) for (int r = 0; r < R; r++) row_greedy[r] = spec_hres_[1 + r];
         h_argmax_[cur_] = spec_hres_[1 + m];
         cv.n_committed = p + 1 + m; cv.n_past = cv.n_committed; cv.has_logits = true;
+        cv.hist.push_back(g0); cv.hist.insert(cv.hist.end(), draft, draft + m);   // the kept rows only
         if (logits_host_slot_ == cur_) logits_host_slot_ = -1;
     }
     ids_out[0] = g0; for (int i = 0; i < m; i++) ids_out[1 + i] = draft[i];
@@ -1734,9 +1843,8 @@ int Engine::decode_lookup(const int *corpus, int n_corpus, int max_tokens, int n
     int n = 0, st[4] = {0, 0, 0, 0}, d[DRAFT_MAX], ids[DRAFT_ROWS];
     *n_tokens = 0;
     auto done = [&](int rc) { *n_tokens = n; for (int i = 0; i < 4; i++) stats[i] = st[i]; return rc; };
-    SampleParams greedy; greedy.temp = 0.0f;
     while (n < max_tokens) {
-        const int g0 = sample_token(greedy);                                // evaluates what is queued; the token the next pass evaluates
+        const int g0 = greedy_raw();                                        // evaluates what is queued; the token the next pass evaluates (raw logits: no penalties here)
         if (cv.n_past + 1 > n_ctx_ && make_room(1)) break;                   // context full and no automatic shift
         drafter.push(g0);
         const int nd = g0 == 2 ? 0 : drafter.draft(std::min(n_draft, max_tokens - n - 1), d);
@@ -1855,7 +1963,11 @@ int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
                 if (so->greedy_logprob) so->greedy_logprob[d] = h_glp[(size_t)(r - rq.first)];
             }
         }
-        for (int i = 0; i < sc.n_seg; i++) conv_[(size_t)sc.h_segs[4 * i]].n_committed += sc.h_segs[4 * i + 2];
+        for (int i = 0; i < sc.n_seg; i++) {
+            const int *g = sc.h_segs + 4 * i;
+            Conversation &cv = conv_[(size_t)g[0]];
+            cv.n_committed += g[2]; cv.hist.insert(cv.hist.end(), tok.begin() + g[1], tok.begin() + g[1] + g[2]);
+        }
     }
     for (const Src &c : src) { Conversation &cv = conv_[(size_t)c.slot]; cv.drop_queue(); cv.has_logits = true; }
     prefix_commit(plan);

@@ -62,7 +62,7 @@ public:
     int sample_token(const SampleParams &p);          // minigpt4.cpp:2425-2483
     const char *id_to_token(int id) const;            // minigpt4.cpp:2485-2497 (borrowed pointer)
     // minigpt4.cpp:2499-2502 (the selected conversation)
-    void reset() { Conversation &c = conv_[(size_t)cur_]; c.n_committed = 0; c.drop_queue(); c.has_logits = false; }
+    void reset() { Conversation &c = conv_[(size_t)cur_]; c.n_committed = 0; c.hist.clear(); c.drop_queue(); c.has_logits = false; }
     void sync();
     hipStream_t stream() const { return stream_; }
     // ---- context shift (llama.cpp's answer to a full context), selected conversation: pending rows are evaluated first, then rows
@@ -186,7 +186,22 @@ public:
     // stats = {verify passes, plain steps, draft tokens sent, draft tokens accepted}
     int decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats);
 
-    // ---- measurement hooks (bench / tests)
+    // ---- repetition / frequency / presence penalties and a logit bias (penalty.hpp: llama.cpp's arithmetic, one definition for host and device).  Off by default
+    // (the reference ignores the arguments); minigpt4_amd.h states the rules.  Every conversation keeps a ROW-ALIGNED token history -- entry r = the token id of cache
+    // row r, -1 for an embedding row -- that every path which advances or moves rows keeps in step (invariant: hist.size() == n_committed; the queued rows follow it
+    // in pend_tok), its five parameters (neutral by default; they count only while the mode is on) and its bias (counts whatever the mode).  sample_token and
+    // decode_batch apply them: temp <= 0 through ONE k_pen_pick launch over the listed conversations whose transformation is not the identity (tables built on the
+    // host, one upload, one small copy back, one synchronise; logits_, d_argmax_, d_feed_ and the graphs untouched), temp > 0 on a host copy of the row before the
+    // chain.  verify_draft, decode_lookup and decode_loop decide on raw logits.  The buffers are allocated at the first launch.
+    void set_penalties(bool on) { pen_mode_ = on; }
+    bool penalties() const { return pen_mode_; }
+    int set_conversation_penalties(int slot, const PenParams &p);          // 0, or 1 + last_error "conversation_penalties: ...", nothing changed
+    int set_logit_bias(const int *ids, const float *bias, int n);          // selected conversation; 0, or 1 + last_error "set_logit_bias: ...", nothing changed
+    int token_history(int *out, int cap);                                  // selected conversation, queued rows evaluated first; the count (-1: that pass failed)
+    struct PenInfo { int mode = 0, launches = 0, host_rows = 0, last_entries = 0; };
+    PenInfo penalty_info() const { PenInfo i = pen_info_; i.mode = pen_mode_; return i; }
+
+    // ---- measurement hooks (bench / tests): both feed tokens back on the device, so the rows they add enter the token history as -1
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
     int decode_loop(int steps, int *tokens_out, float *ms_total);
     // Per-launch-site table of the decode step: `steps` eager decode steps issuing EXACTLY the launch set the captured hipGraph replays, a hipEvent
@@ -205,6 +220,16 @@ private:
     void forward_batch(int B, hipStream_t s, bool verify = false);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation
     // speculation's own allocations (set_speculation; freed with the context): [1 + spec_max_][n_vocab] row logits, {m, greedy id per row} and its pinned mirror, [R] graphs
     int spec_max_ = 0; float *spec_logits_ = nullptr; int *spec_res_ = nullptr, *spec_hres_ = nullptr; std::vector<hipGraphExec_t> spec_graph_;
+    // penalties: [MAX_CONVERSATIONS] PenRow then the tables, device and pinned (one upload per launch); the picked ids and their pinned mirror
+    bool pen_mode_ = false; PenInfo pen_info_;
+    uint8_t *pen_d_ = nullptr, *pen_h_ = nullptr; int *pen_out_d_ = nullptr, *pen_out_h_ = nullptr;
+    std::vector<float> pen_row_;                                           // the host path's scratch copy of the row (h_logits_ stays raw)
+    void pen_alloc();
+    void pen_free();
+    struct Conversation;
+    int pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const;   // the conversation's table for its history as a sample sees it; the flags
+    void pen_pick(const int *slots, int n, int *ids);                      // ids[i] <- the penalised pick of every listed conversation whose transformation is not the identity
+    int greedy_raw();                                                      // sample_token at temp 0 without penalties or bias
     void spec_drop_graphs();
     void spec_free();
     // prefill_batch: one packed chunk as forward() sees it through Pass::seg (device tables in d_seg_, host copy of the segment table)
@@ -296,6 +321,8 @@ private:
         std::vector<int> pend_tok; std::vector<float> pend_embd;
         hipGraphExec_t graph = nullptr;   // decode step captured with this conversation's cache / position / token addresses
         bool graph_split = false;         // ... with the key-split attention launches (long context) or the one-workgroup-per-head kernel
+        std::vector<int> hist;            // token id of every evaluated row, -1 = embedding row / fed back on the device (size n_committed)
+        PenParams pen; std::vector<int> bias_id; std::vector<float> bias_val;   // penalties (while the mode is on), logit bias (always)
         bool has_logits = false;          // its logits_ row holds the logits after its last evaluated row (not: nothing evaluated yet, after reset(), after a partial fork)
         void drop_queue() { pend_tok.clear(); pend_embd.clear(); n_past = n_committed; }   // what a failed pass, fork and reset leave: nothing queued
     };

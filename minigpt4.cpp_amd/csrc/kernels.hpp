@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "penalty.hpp"
 
 namespace mg4 {
 
@@ -195,6 +196,11 @@ void launch_logprob_rows(const float *logits, int ld, int n_vocab, int rows, con
 constexpr int TOPN_MAX = 64;   // one wavefront of candidates above the threshold; covers the reference's default top-k of 40
 bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const int *row_index, int top_n, const int *targets, int *ids, float *logprobs, int *rank,
                       float *target_logprob, hipStream_t s);
+// penalised greedy pick, one workgroup per entry of `rows` (device; penalty.hpp): picked[r] = the first maximum of logits row rows[r].row (at logits + row * ld, any
+// 4-byte alignment) after the bias / repetition / frequency / presence transformation its table entries table[rows[r].off .. + rows[r].n) describe (distinct ids);
+// the logits are not written.  adjusted (may be null): [table entry] the transformed value.  false + last_error: n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose
+// bitmap does not fit LDS
+bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const PenRow *rows, const PenEntry *table, int *picked, float *adjusted, hipStream_t s);
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)

@@ -3184,6 +3184,48 @@ bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const 
     hipLaunchKernelGGL(k_topn_rows, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, n_vocab, row_index, top_n, targets, ids, logprobs, rank, target_logprob);
     return true;
 }
+// Penalised greedy pick (Engine::pen_pick), one workgroup of 256 per listed conversation, one launch for all of them.  rows[r] names the logits row, the conversation's
+// table (penalty.hpp: the distinct ids its repetition / frequency / presence penalties and its logit bias touch) and the factors.  Thread i computes the adjusted value of
+// table entry i with pen_value -- the function the host path applies, so both give the same bits -- and marks the id in a bitmap in LDS; the sweep over the row (row_span:
+// scalar head, 16-byte body, scalar tail) skips the marked ids; "larger value, then smaller id" over both sets is the first maximum of the transformed row.  The row is
+// read in place and never written: whoever reads logits_ afterwards (minigpt4_amd_get_logits, scoring, top-N) sees raw logits.  picked[r] = the id; adjusted (may be
+// null): the value of every table entry, at the entry's index (test hook).  An entry whose id lies outside [0, n_vocab) is ignored (the host never builds one).
+// LDS, all dynamic: (n_vocab + 31) / 32 bitmap words rounded up to 4, then 4 floats and 4 ints of reduction scratch.
+__global__ __launch_bounds__(256) void k_pen_pick(const float *__restrict__ logits, int ld, int n_vocab, const PenRow *__restrict__ rows, const PenEntry *__restrict__ table,
+                                                  int *__restrict__ picked, float *__restrict__ adjusted) {
+    extern __shared__ __attribute__((aligned(16))) unsigned pen_lds[];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const PenRow pr = rows[r];
+    const int words = ((n_vocab + 31) / 32 + 3) & ~3;
+    unsigned *bits = pen_lds;
+    float *sv = reinterpret_cast<float *>(pen_lds + words); int *si = reinterpret_cast<int *>(pen_lds + words + 4);
+    const float *x = logits + (size_t)pr.row * ld;
+    for (int i = tid; i < words; i += 256) bits[i] = 0u;
+    __syncthreads();
+    float best = -INFINITY; int bi = 0x7FFFFFFF;
+    for (int i = tid; i < pr.n; i += 256) {
+        const PenEntry e = table[(size_t)pr.off + i];
+        if (e.id < 0 || e.id >= n_vocab) continue;
+        const float v = pen_value(x[e.id], e.id, e.count, e.has_bias, e.bias, pr.flags, pr.repeat_penalty, pr.alpha_frequency, pr.alpha_presence);
+        atomicOr(&bits[e.id >> 5], 1u << (e.id & 31));
+        if (adjusted) adjusted[(size_t)pr.off + i] = v;
+        argmax_combine(best, bi, v, e.id);
+    }
+    __syncthreads();
+    const RowSpan sp = row_span(x, n_vocab);
+    row_sweep(sp, tid, [&](float v, int i) { if (!((bits[i >> 5] >> (i & 31)) & 1u)) argmax_combine(best, bi, v, i); });
+    argmax_wave(best, bi);
+    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) { for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]); picked[r] = bi == 0x7FFFFFFF ? 0 : bi; }
+}
+bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const PenRow *rows, const PenEntry *table, int *picked, float *adjusted, hipStream_t s) {
+    const size_t lds = ((size_t)(((n_vocab + 31) / 32 + 3) & ~3) + 8) * 4;
+    if (n_rows < 1 || n_vocab < 1 || ld < n_vocab || lds > 64 * 1024) { set_last_error("launch_pen_pick: shape out of range"); return false; }
+    note_kernel("k_pen_pick");
+    hipLaunchKernelGGL(k_pen_pick, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, picked, adjusted);
+    return true;
+}
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {
     const int r = threadIdx.x;

@@ -8,6 +8,14 @@
 
 namespace mg4 {
 
+bool penalise_row(float *l, int n_vocab, const int *hist, size_t len, const PenParams &p, int n_ctx, const int *bias_id, const float *bias_val, int n_bias) {
+    std::vector<PenEntry> tab;
+    const int flags = pen_build_table(hist, len, p, n_ctx, n_vocab, bias_id, bias_val, n_bias, tab);
+    if (!flags && tab.empty()) return false;
+    pen_apply_row(l, n_vocab, tab, flags, p);
+    return true;
+}
+
 void Sampler::seed(int s) {
     if (s < 0) s = (int)time(nullptr);   // llama.cpp: seed < 0 -> time(NULL)
     rng.seed((uint32_t)s);

@@ -5,6 +5,8 @@
 #include <random>
 #include <vector>
 
+#include "penalty.hpp"
+
 namespace mg4 {
 
 struct TokenData { int id; float logit; float p; };
@@ -14,6 +16,10 @@ struct SampleParams {
     float temp = 0.8f; int32_t top_k = 40; float top_p = 0.9f; float tfs_z = 1.0f; float typical_p = 1.0f;
     int mirostat = 0; float mirostat_tau = 5.0f; float mirostat_eta = 1.0f;
 };
+
+// Steps 1-5 of penalty.hpp on a row of n_vocab logits, in place, for a row-aligned history (token id, -1 = embedding row) and a bias list: what the chain sees when the
+// penalties are on (llama.cpp applies them to the candidates before top-k, mirostat and the rest).  false: the transformation is the identity, the row is untouched.
+bool penalise_row(float *l, int n_vocab, const int *hist, size_t len, const PenParams &p, int n_ctx, const int *bias_id, const float *bias_val, int n_bias);
 
 struct Sampler {
     std::mt19937 rng;

@@ -708,6 +708,57 @@ int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, 
         return 0;
     });
 }
+// ---- penalties and logit bias (penalty.hpp) ----
+int minigpt4_amd_test_penalise_host(float *row, int n_vocab, const int32_t *history, int n_history, int n_ctx, int32_t repeat_last_n, float repeat_penalty, float alpha_presence,
+                                    float alpha_frequency, int penalize_nl, const int32_t *bias_ids, const float *bias, int n_bias, int32_t *table_out, int table_cap, int32_t *flags_out) {
+    if (!row || n_vocab < 1 || n_history < 0 || (n_history > 0 && !history) || n_bias < 0 || n_bias > PEN_BIAS_MAX || (n_bias > 0 && (!bias_ids || !bias))) return -1;
+    for (int i = 0; i < n_bias; i++) {
+        if (bias_ids[i] < 0 || bias_ids[i] >= n_vocab) return -1;
+        for (int j = 0; j < i; j++) if (bias_ids[j] == bias_ids[i]) return -1;
+    }
+    try {
+        const PenParams p{repeat_last_n, repeat_penalty, alpha_presence, alpha_frequency, penalize_nl};
+        std::vector<PenEntry> tab;
+        const int flags = pen_build_table(history, (size_t)n_history, p, n_ctx, n_vocab, bias_ids, bias, n_bias, tab);
+        pen_apply_row(row, n_vocab, tab, flags, p);
+        static_assert(sizeof(PenEntry) == 16, "the hooks hand tables out as 4 words per entry");
+        if (table_out) memcpy(table_out, tab.data(), std::min(tab.size(), (size_t)std::max(table_cap, 0)) * sizeof(PenEntry));
+        if (flags_out) *flags_out = flags;
+        return (int)tab.size();
+    } catch (...) { return -1; }
+}
+int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table, int32_t *picked_out,
+                               float *adjusted_out, float *ms_out) {
+    static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16, "the hook's word layout");
+    if (!logits || !rows || !picked_out || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n_rows < 1 || n_table < 0 || (n_table > 0 && !table)) return 1;
+    for (int r = 0; r < n_rows; r++) {   // everything that indexes device memory
+        const int32_t *w = rows + 8 * (size_t)r;
+        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table) return 1;
+        std::vector<int> ids;
+        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)buf_rows * ld, R = (size_t)n_rows, T = (size_t)std::max(n_table, 1);
+        DevBuf dl(n * 4), dr(R * sizeof(PenRow)), dt(T * sizeof(PenEntry)), dp(R * 4), da(T * 4);
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, rows, R * sizeof(PenRow), hipMemcpyHostToDevice));
+        if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dp.p, 0xFF, R * 4)); HIP_CHECK(hipMemset(da.p, 0xFF, T * 4));   // what the kernel leaves out shows as id -1 / NaN
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_pen_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<PenRow>(), dt.as<PenEntry>(), dp.as<int>(), da.as<float>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        HIP_CHECK(hipMemcpy(picked_out, dp.p, R * 4, hipMemcpyDeviceToHost));
+        if (adjusted_out && n_table > 0) HIP_CHECK(hipMemcpy(adjusted_out, da.p, (size_t)n_table * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
 static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {

@@ -216,6 +216,11 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_set_speculation.argtypes = [VOID_PTR, I32]
         L.minigpt4_amd_verify_draft.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, INT_PTR]
         L.minigpt4_amd_decode_lookup.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_set_penalties.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_conversation_penalties.argtypes = [VOID_PTR, I32, I32, F32, F32, F32, I32]
+        L.minigpt4_amd_set_logit_bias.argtypes = [VOID_PTR, INT_PTR, FLOAT_PTR, I32]
+        L.minigpt4_amd_token_history.argtypes = [VOID_PTR, INT_PTR, I32]
+        L.minigpt4_amd_penalty_info.argtypes = [VOID_PTR, INT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -241,6 +246,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_kv_copy.argtypes = [I32, I32, I32, I32, I32, INT_PTR, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_penalise_host.argtypes = [FLOAT_PTR, I32, INT_PTR, I32, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, INT_PTR, I32, INT_PTR]
+        L.minigpt4_amd_test_pen_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
@@ -498,6 +505,82 @@ class MiniGPT4SharedLibrary:
                                                    out.ctypes.data_as(INT_PTR), n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR)):
             raise RuntimeError("decode_lookup failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return dict(tokens=out[:int(n[0])].copy(), passes=int(st[0]), steps=int(st[1]), sent=int(st[2]), accepted=int(st[3]))
+
+    # ---- repetition / frequency / presence penalties, logit bias (include/minigpt4_amd.h)
+    def _err(self) -> str:
+        return (self.library.minigpt4_amd_last_error() or b"").decode("utf-8", errors="replace")
+
+    def amd_set_penalties(self, ctx, on: bool) -> None:
+        """Off (the default, the reference's behaviour): minigpt4_end_chat(_image) ignores its five penalty arguments.  On: it stores them as the selected
+        conversation's parameters and samples with them; the batched calls and amd_sample use each conversation's stored parameters.  NEUTRAL values are
+        repeat_penalty 1.0, alpha_presence 0.0, alpha_frequency 0.0 -- the wrappers' defaults for the alphas (the reference binding's) are 1.0."""
+        if self.library.minigpt4_amd_set_penalties(ctx.ptr, int(bool(on))):
+            raise RuntimeError("set_penalties failed: " + self._err())
+
+    def amd_conversation_penalties(self, ctx, slot: int, repeat_last_n: int = 64, repeat_penalty: float = 1.0, alpha_presence: float = 0.0,
+                                   alpha_frequency: float = 0.0, penalize_nl: int = 1) -> None:
+        """A conversation's penalty parameters (the defaults are the neutral ones); they take effect only while amd_set_penalties is on."""
+        if self.library.minigpt4_amd_conversation_penalties(ctx.ptr, int(slot), int(repeat_last_n), float(repeat_penalty), float(alpha_presence), float(alpha_frequency),
+                                                            int(penalize_nl)):
+            raise RuntimeError("conversation_penalties failed: " + self._err())
+
+    def amd_set_logit_bias(self, ctx, bias) -> None:
+        """The selected conversation's logit bias: a dict {id: bias} or a sequence of (id, bias) pairs, at most 256; empty / None clears it.  Active whatever the
+        penalties mode; -inf bans a token."""
+        pairs = list(bias.items()) if isinstance(bias, dict) else list(bias or [])
+        ids = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        val = np.ascontiguousarray([p[1] for p in pairs], np.float32)
+        if self.library.minigpt4_amd_set_logit_bias(ctx.ptr, ids.ctypes.data_as(INT_PTR) if len(pairs) else None, val.ctypes.data_as(FLOAT_PTR) if len(pairs) else None,
+                                                    len(pairs)):
+            raise RuntimeError("set_logit_bias failed: " + self._err())
+
+    def amd_token_history(self, ctx) -> np.ndarray:
+        """The selected conversation's row-aligned token history (queued rows are evaluated first): the token id of every cache row, -1 for an embedding row."""
+        n = self.library.minigpt4_amd_token_history(ctx.ptr, None, 0)
+        if n < 0:
+            raise RuntimeError("token_history failed: " + self._err())
+        out = np.zeros(max(n, 1), np.int32)
+        self.library.minigpt4_amd_token_history(ctx.ptr, out.ctypes.data_as(INT_PTR), n)
+        return out[:n]
+
+    def amd_penalty_info(self, ctx) -> dict:
+        """dict(mode, launches: k_pen_pick launches so far, host_rows: rows penalised on the host so far, last_entries: table entries the last launch uploaded)."""
+        o = np.zeros(4, np.int32)
+        if self.library.minigpt4_amd_penalty_info(ctx.ptr, o.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("penalty_info failed: " + self._err())
+        return dict(mode=int(o[0]), launches=int(o[1]), host_rows=int(o[2]), last_entries=int(o[3]))
+
+    def amd_test_penalise_host(self, row: np.ndarray, history: Sequence[int], n_ctx: int, repeat_last_n: int = 64, repeat_penalty: float = 1.0,
+                               alpha_presence: float = 0.0, alpha_frequency: float = 0.0, penalize_nl: int = 1, bias=None):
+        """The host function on one row (no GPU): returns (row', table [n][4] i32 = id, count, bias bits, has_bias, flags)."""
+        r = np.ascontiguousarray(row, np.float32).copy()
+        h = np.ascontiguousarray(history, np.int32)
+        pairs = list(bias.items()) if isinstance(bias, dict) else list(bias or [])
+        ids = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        val = np.ascontiguousarray([p[1] for p in pairs], np.float32)
+        tab, fl = np.zeros((1281, 4), np.int32), np.zeros(1, np.int32)
+        n = self.library.minigpt4_amd_test_penalise_host(r.ctypes.data_as(FLOAT_PTR), len(r), h.ctypes.data_as(INT_PTR) if len(h) else None, len(h), int(n_ctx),
+                                                         int(repeat_last_n), float(repeat_penalty), float(alpha_presence), float(alpha_frequency), int(penalize_nl),
+                                                         ids.ctypes.data_as(INT_PTR) if len(pairs) else None, val.ctypes.data_as(FLOAT_PTR) if len(pairs) else None,
+                                                         len(pairs), tab.ctypes.data_as(INT_PTR), len(tab), fl.ctypes.data_as(INT_PTR))
+        if n < 0:
+            raise RuntimeError("test_penalise_host: bad arguments")
+        return r, tab[:n].copy(), int(fl[0])
+
+    def amd_test_pen_pick(self, logits: np.ndarray, n_vocab: int, rows: np.ndarray, table: np.ndarray):
+        """launch_pen_pick on host logits [buf_rows][ld] (n_vocab <= ld columns are read).  rows [n][8] i32 words (buffer row, first entry, entries, flags, the bit
+        patterns of repeat_penalty / alpha_frequency / alpha_presence, 0), table [m][4] i32 words: returns (picked [n] i32, adjusted [m] f32, ms)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        rw = np.ascontiguousarray(rows, np.int32).reshape(-1, 8)
+        tb = np.ascontiguousarray(table, np.int32).reshape(-1, 4)
+        picked, adj, ms = np.zeros(len(rw), np.int32), np.zeros(max(len(tb), 1), np.float32), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_pen_pick(lg.ctypes.data_as(FLOAT_PTR), lg.shape[0], int(n_vocab), lg.shape[1], rw.ctypes.data_as(INT_PTR), len(rw),
+                                                     tb.ctypes.data_as(INT_PTR) if len(tb) else None, len(tb), picked.ctypes.data_as(INT_PTR), adj.ctypes.data_as(FLOAT_PTR),
+                                                     ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_pen_pick rc={rc}: " + self._err())
+        return picked, adj[:len(tb)], float(ms.value)
 
     def amd_token_piece(self, ctx, token_id: int) -> Optional[str]:
         """The text of one token id, as minigpt4_end_chat returns it ("</s>" for id 2); None for an id outside the vocabulary."""

@@ -67,13 +67,36 @@ class ReplicaServer:
         return pre, [raw, pre]
 
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
-            batched_prefill: bool = False, logprobs: int = 0) -> List[str]:
-        """logprobs > 0: the decode loop uses `minigpt4_amd_end_chat_batch_top` (same pieces, same sampler draws) and `self.last_logprobs[i]` holds, per generated
+            batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
+            frequency_penalty: float = 0.0, logit_bias=None) -> List[str]:
+        """repeat_penalty / repeat_last_n / presence_penalty / frequency_penalty / logit_bias ({id: bias} or (id, bias) pairs): llama.cpp's penalties and a logit
+        bias for every request of the call (include/minigpt4_amd.h), applied per conversation before the decode loop and taken back when the call returns.  The
+        defaults are neutral: the call then touches none of it.
+        logprobs > 0: the decode loop uses `minigpt4_amd_end_chat_batch_top` (same pieces, same sampler draws) and `self.last_logprobs[i]` holds, per generated
         token of request i (swallowed "##" pieces included), dict(id, piece, logprob, rank, top=[(piece, logprob), ...]) with `logprobs` alternatives -- the
         log-probabilities of the raw logits, whatever temp / top_k / top_p.  The return value is the same."""
-        import ctypes
         lib, ctx = self.lib, self.ctx
         answers: List[str] = [""] * len(requests)
+        penalised = repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
+        mode_before = lib.amd_penalty_info(ctx)["mode"] if penalised else 0
+        try:
+            return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
+                             dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty))
+        finally:
+            if penalised or logit_bias:
+                for slot in range(self.conversations):
+                    lib.amd_select_conversation(ctx, slot)
+                    lib.amd_conversation_penalties(ctx, slot)
+                    lib.amd_set_logit_bias(ctx, None)
+                lib.amd_select_conversation(ctx, 0)
+            if penalised:
+                lib.amd_set_penalties(ctx, bool(mode_before))
+
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen) -> List[str]:
+        import ctypes
+        lib, ctx = self.lib, self.ctx
+        if penalised:
+            lib.amd_set_penalties(ctx, True)
         self.last_logprobs = [[] for _ in requests] if logprobs > 0 else None
         for wave in plan_waves(len(requests), self.conversations):
             structs, owned = [], []
@@ -90,6 +113,10 @@ class ReplicaServer:
                     lib.minigpt4_reset_chat(ctx)
                     lib.minigpt4_system_prompt(ctx)
                     lib.minigpt4_begin_chat_image(ctx, embs.embeddings[slot], requests[i].prompt)
+                    if penalised:
+                        lib.amd_conversation_penalties(ctx, slot, **pen)
+                    if logit_bias:
+                        lib.amd_set_logit_bias(ctx, logit_bias)
                 if batched_prefill:                           # the wave's prompts in one pass per chunk instead of one pass per conversation
                     lib.amd_prefill_batch(ctx, list(range(len(wave))))
                 text = {slot: "" for slot in range(len(wave))}
@@ -142,7 +169,8 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     server = ReplicaServer(vision_path, llm_path, conversations=conversations, rank=rank, world=world, device=kw.get("device"),
                            **{k: v for k, v in kw.items() if k in ("n_ctx", "n_batch", "seed", "library", "verbosity", "prefix_cache")})
     try:
-        out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs")})
+        out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
+                                                                                                "presence_penalty", "frequency_penalty", "logit_bias")})
     finally:
         server.close()
     mapping = dict(zip(mine, out))
