@@ -2174,470 +2174,387 @@ __global__ __launch_bounds__(256) void k_attn_prefill(const float *__restrict__ 
             }
         }
 }
-// The same on the fp16 matrix cores (round 3): every operand of both products IS an fp16 value in the reference (K / V cache rows, q rounded to fp16 by ggml's f16 x f32
-// mul_mat, probabilities rounded to fp16 before P.V), so v_mfma_f32_16x16x32_f16 multiplies them exactly and accumulates in fp32 -- 16x the rate of the f32 MFMA above and
-// no fp16 -> fp32 staging pass.  K tiles go to LDS as they are (16-byte chunks XOR-swizzled by the key index: conflict-free fragment reads); V tiles are written
-// TRANSPOSED ([dim][key], 70-half rows) so that a lane's 8 consecutive keys of one dim are contiguous.  Softmax as above.  fp32 accumulation order inside the MFMA differs
-// from the sequential chain of k_attn_llm / the oracle (fp32 rounding only; MINIGPT4_PARITY uses k_attn_ref).
+// =====================================================================================================================
+// Prompt attention on the fp16 matrix cores: k_attn_prefill_h<HD, QS> (4 waves, 16 QS queries) and k_attn_prefill_h8<HD> (8 waves, 32 queries).
+// The family computes what k_attn_prefill computes, for a workgroup's (head, query tile): every operand of both products IS an fp16 value in the reference (K / V cache
+// rows, q rounded to fp16 by ggml's f16 x f32 mul_mat, probabilities rounded to fp16 before P.V), so v_mfma_f32_16x16x32_f16 multiplies them exactly and accumulates in
+// fp32.  scores = q K^T / sqrt(hd) into LDS rows S[query][key]; softmax per query over its own causal range (max, fp16-table exp, exact double sum, p = fp16(e / sum));
+// out = P V with the key tiles in index order.  fp32 accumulation order inside the MFMA differs from the sequential chain of k_attn_llm / the oracle (fp32 rounding only;
+// MINIGPT4_PARITY uses k_attn_ref).
+// Every stage is written ONCE, as one of the APH_ macros below; a kernel is only its schedule (loops, barriers, register double buffers, wave roles, MG4_TLP stamps).
+// The forms therefore give the same bits: one MFMA chain per (query group, key tile), an order-free max and sum, P.V tiles in key order -- whichever waves run them
+// (tests/test_gpu_prefill_batch.py compares them).
+// Why text and not __device__ functions: a function is simplified on its own before it is inlined, and the index arithmetic then keeps another form.  With only the
+// softmax row behind a forceinline function (the tile as a struct or as scalars; the thread index passed raw or split by the caller) the 4-wave kernels came out up to 22
+// instructions away from the ISA that was validated and measured; with every stage behind one, all eighteen instantiations differed.  As macros they are instruction
+// for instruction what they were (tools/isa_diff.py) -- what attn_llm_body.hpp found for the decode family.  Even moving APH_TILE below the thread indices renames registers.
+// A stage names its threads by its arguments -- st: staging thread 0 .. 255 (tid; the 8-wave form's loader thread lt), mw: MFMA wave 0 .. 3 (wave; mw) -- and is handed
+// the LDS buffer it reads or writes.  In scope where one is used: the kernel's parameters, HD, QS, SEG, the names APH_GEOMETRY and APH_TILE_KEYS declare, h, tid, lane, and
+// out_h (a parameter of the 8-wave form; the 4-wave form declares a null local, which the compiler drops with the arms that test it).
+// =====================================================================================================================
 typedef _Float16 aph8_t __attribute__((ext_vector_type(8)));
-constexpr int APH_LDT = 70;
+constexpr int APH_LDT = 70;                                       // halfs per row of a transposed V tile [dim][key]: a lane's 8 consecutive keys of one dim are contiguous
 // SEG form (Engine::prefill_batch, trailing AttnSegArgs argument): the rows of several conversations packed in one chunk, one launch.  Grid (head, work item); item y
 // = (segment tiles[2 y], first query tiles[2 y + 1]), dealt longest-first over ALL segments by the host (attn_seg_tiles).  Segment i = segs[4 i ..]: slot, first packed
 // row, rows, position of its first row.  Each segment is tiled from its own row 0, so a tile sees exactly the queries and keys of the same tile of that segment's own
-// launch: the rows are bit-identical.  Only the tile setup differs; without the argument the kernels are the one-conversation forms.
+// launch: the rows are bit-identical.  Only APH_TILE differs; without the argument the kernels are the one-conversation forms.
 struct AttnSegArgs { const int *segs; const int *tiles; long long seq_stride; };
+#define APH_GEOMETRY                                                                                                                                                    \
+    constexpr bool SEG = sizeof...(Seg) > 0;                                                                                                                            \
+    constexpr int C8 = HD / 8, QT = AP_QT * QS, KSQ = HD / 32, DT = HD / 16, PER = AP_KT * C8 / 256, DPW = (DT + 3) / 4;                                                \
+    static_assert(PER >= 1 && (DT % 4 == 0 || DT == 2), "tile geometry")
+// tile set-up.  Causal: the LAST query tile sees the most keys -- it is dispatched first (longest-first), so the short tiles fill the tail of the launch.  SEG: the work
+// item (segment, first query) comes from the host's longest-first list instead: the segment's rows, its conversation's cache, its first position
+#define APH_TILE                                                                                                                                                        \
+    int q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, np_seg = 0;                                                                                                        \
+    if constexpr (SEG) {                                                                                                                                                \
+        const AttnSegArgs sa = (seg, ...);                                                                                                                              \
+        const int *t = sa.tiles + 2 * blockIdx.y, *g = sa.segs + 4 * t[0];                                                                                              \
+        q0 = t[1]; N = g[2]; np_seg = g[3];                                                                                                                             \
+        q += (size_t)g[1] * E; out += (size_t)g[1] * E; kc += (size_t)g[0] * sa.seq_stride; vc += (size_t)g[0] * sa.seq_stride;                                         \
+        if (out_h) out_h += (size_t)g[1] * E;                                                                                                                           \
+    }
+// np: first position; T: keys the last query of this tile sees; nkt: key tiles
+#define APH_TILE_KEYS                                                                                                                                                   \
+    const int np = SEG ? np_seg : *n_past;                                                                                                                              \
+    const int T = np + min(q0 + QT - 1, N - 1) + 1;                                                                                                                     \
+    const int nkt = (T + AP_KT - 1) / AP_KT;                                                                                                                            \
+    const float scale = 1.0f / sqrtf((float)HD);                                                                                                                        \
+    const int l15 = lane & 15, l4 = lane >> 4
+// Q fragments (A operands) into qf[QS][KSQ]: query l15 of each group of 16, dims 32 ks + 8 l4 .. + 7, rounded to fp16
+#define APH_Q_FRAGS                                                                                                                                                     \
+    _Pragma("unroll") for (int qs = 0; qs < QS; qs++) {                                                                                                                 \
+        const float *qp = q + (size_t)min(q0 + 16 * qs + l15, N - 1) * E + (size_t)h * HD + 8 * l4;                                                                     \
+        _Pragma("unroll") for (int ks = 0; ks < KSQ; ks++) {                                                                                                            \
+            const float4 a = *reinterpret_cast<const float4 *>(qp + 32 * ks), b = *reinterpret_cast<const float4 *>(qp + 32 * ks + 4);                                  \
+            const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};                                                                                                \
+            _Pragma("unroll") for (int e = 0; e < 8; e++) qf[qs][ks][e] = (_Float16)__half2float(f2h_rn(v[e]));                                                         \
+        }                                                                                                                                                               \
+    }
+// key tile `tile` of the cache `base` (kc or vc), global -> registers X[PER] (rows past the last key repeat it)
+#define APH_KV_LOAD(X, base, tile, st)                                                                                                                                  \
+    _Pragma("unroll") for (int u = 0; u < PER; u++) { const int e = (st) + 256 * u, j = e / C8, c = e - j * C8;                                                         \
+        X[u] = ld16(base + (size_t)min((tile) * AP_KT + j, T - 1) * E + (size_t)h * HD + 8 * c); }
+// K tile, registers X -> Kt [64][HD] as it is: 16-byte chunk c of key j at slot c ^ (j & (C8 - 1)) (conflict-free fragment reads in APH_SCORES)
+#define APH_K_WRITE(Kt, X, st)                                                                                                                                          \
+    _Pragma("unroll") for (int u = 0; u < PER; u++) { const int e = (st) + 256 * u, j = e / C8, c = e - j * C8;                                                         \
+        *reinterpret_cast<int4 *>(Kt + j * HD + ((c ^ (j & (C8 - 1))) << 3)) = X[u]; }
+// scores of (MFMA wave mw, key tile kt) out of Kt: keys kt 64 + 16 mw .. + 15 against the QS query groups, one MFMA chain over the head dim each, * scale, into S
+#define APH_SCORES(Kt, kt, mw)                                                                                                                                          \
+    const int key0 = (kt) * AP_KT + 16 * (mw);                                                                                                                          \
+    if (key0 < T) {                                                                                                                                                     \
+        const int row = 16 * (mw) + l15;                                                                                                                                \
+        pf4_t acc[QS];                                                                                                                                                  \
+        _Pragma("unroll") for (int qs = 0; qs < QS; qs++) acc[qs] = pf4_t{0.0f, 0.0f, 0.0f, 0.0f};                                                                      \
+        _Pragma("unroll") for (int ks = 0; ks < KSQ; ks++) {                                                                                                            \
+            const aph8_t kf = *reinterpret_cast<const aph8_t *>(Kt + row * HD + (((4 * ks + l4) ^ (row & (C8 - 1))) << 3));                                             \
+            _Pragma("unroll") for (int qs = 0; qs < QS; qs++) acc[qs] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[qs][ks], kf, acc[qs], 0, 0, 0);                       \
+        }                                                                                                                                                               \
+        _Pragma("unroll") for (int qs = 0; qs < QS; qs++)                                                                                                               \
+            _Pragma("unroll") for (int r = 0; r < 4; r++) S[(size_t)(16 * qs + l4 * 4 + r) * LS + key0 + l15] = acc[qs][r] * scale;                                     \
+    }
+// softmax of the tile's query row ROW by 16 lanes; lane `sub` owns the keys 64 s + 4 sub .. + 3 (16-byte LDS accesses); the row sees keys 0 .. np + q0 + ROW.  Same
+// values as k_attn_prefill's loop (max, fp16-table exp, exact double sum -- order-free --, p = fp16(e * (1 / sum))) with 16 table gathers in flight per round.
+// "a block past the end repeats the last one": its values are dropped by the `j0 + 64 * u < nb` test, which is uniform over the 16 lanes of a row.
+// (The table stays in global memory: an LDS copy -- 39 KB by LDS-DMA per workgroup -- left this phase at 8.0 us against 7.7 and cost the 142-row launch its co-resident
+//  workgroups, 11.3 -> 15.1 us: the phase is bound by its ~30 vector instructions per element, not by the gathers.)
+#define APH_SOFTMAX_ROW(ROW)                                                                                                                                            \
+    const int row = (ROW), sub = tid & 15;                                                                                                                              \
+    const int Tq = min(np + q0 + row + 1, T), nb = nkt * AP_KT;                                                                                                         \
+    float *sr = S + (size_t)row * LS;                                                                                                                                   \
+    float mx = -INFINITY;                                                                                                                                               \
+    for (int j = 4 * sub; j < nb; j += 64) {                                                                                                                            \
+        const float4 v = *reinterpret_cast<const float4 *>(sr + j);                                                                                                     \
+        mx = fmaxf(mx, j < Tq ? v.x : -INFINITY); mx = fmaxf(mx, j + 1 < Tq ? v.y : -INFINITY); mx = fmaxf(mx, j + 2 < Tq ? v.z : -INFINITY); mx = fmaxf(mx, j + 3 < Tq ? v.w : -INFINITY); \
+    }                                                                                                                                                                   \
+    mx = fmaxf(mx, __shfl_xor(mx, 1)); mx = fmaxf(mx, __shfl_xor(mx, 2)); mx = fmaxf(mx, __shfl_xor(mx, 4)); mx = fmaxf(mx, __shfl_xor(mx, 8));                         \
+    double sum = 0.0;                                                                                                                                                   \
+    for (int j0 = 0; j0 < nb; j0 += 256) {                                                                                                                              \
+        float x[16]; unsigned short t[16];                                                                                                                              \
+        _Pragma("unroll") for (int u = 0; u < 4; u++) {                                                                                                                 \
+            const int jj = min(j0 + 64 * u, nb - 64) + 4 * sub;          /* a block past the end repeats the last one */                                                \
+            const float4 v = *reinterpret_cast<const float4 *>(sr + jj);                                                                                                \
+            x[4 * u] = v.x; x[4 * u + 1] = v.y; x[4 * u + 2] = v.z; x[4 * u + 3] = v.w;                                                                                 \
+        }                                                                                                                                                               \
+        _Pragma("unroll") for (int e = 0; e < 16; e++) {                                                                                                                \
+            const int jj = j0 + 64 * (e >> 2) + 4 * sub + (e & 3);                                                                                                      \
+            t[e] = reinterpret_cast<const unsigned short *>(tb.exp)[f2h_bits(jj < Tq ? x[e] - mx : 0.0f)];                                                              \
+        }                                                                                                                                                               \
+        _Pragma("unroll") for (int u = 0; u < 4; u++) {                                                                                                                 \
+            const int jj = j0 + 64 * u + 4 * sub;                                                                                                                       \
+            if (j0 + 64 * u < nb) {                                                                                                                                     \
+                float4 ev;                                                                                                                                              \
+                ev.x = jj < Tq ? h2f_bits(t[4 * u]) : 0.0f; ev.y = jj + 1 < Tq ? h2f_bits(t[4 * u + 1]) : 0.0f; ev.z = jj + 2 < Tq ? h2f_bits(t[4 * u + 2]) : 0.0f; ev.w = jj + 3 < Tq ? h2f_bits(t[4 * u + 3]) : 0.0f; \
+                sum += (double)ev.x; sum += (double)ev.y; sum += (double)ev.z; sum += (double)ev.w;                                                                     \
+                *reinterpret_cast<float4 *>(sr + jj) = ev;                                                                                                              \
+            }                                                                                                                                                           \
+        }                                                                                                                                                               \
+    }                                                                                                                                                                   \
+    sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);                                                         \
+    const float inv = (float)(1.0 / sum);                                                                                                                               \
+    for (int j = 4 * sub; j < nb; j += 64) {                             /* keys past the row's limit already hold 0 */                                                 \
+        float4 v = *reinterpret_cast<float4 *>(sr + j);                                                                                                                 \
+        v.x = f16r(v.x * inv); v.y = f16r(v.y * inv); v.z = f16r(v.z * inv); v.w = f16r(v.w * inv);                                                                     \
+        *reinterpret_cast<float4 *>(sr + j) = v;                                                                                                                        \
+    }
+// V tile kt, registers X -> Vt TRANSPOSED [HD][APH_LDT]; keys past the last one are written as 0
+#define APH_V_WRITE(Vt, X, kt, st)                                                                                                                                      \
+    _Pragma("unroll") for (int u = 0; u < PER; u++) {                                                                                                                   \
+        const int e = (st) + 256 * u, j = e / C8, c = e - j * C8;                                                                                                       \
+        const bool live = (kt) * AP_KT + j < T;                                                                                                                         \
+        const unsigned w[4] = {(unsigned)X[u].x, (unsigned)X[u].y, (unsigned)X[u].z, (unsigned)X[u].w};                                                                 \
+        unsigned short *d = reinterpret_cast<unsigned short *>(Vt) + (8 * c) * APH_LDT + j;                                                                             \
+        _Pragma("unroll") for (int i = 0; i < 4; i++) { d[(2 * i) * APH_LDT] = live ? (unsigned short)(w[i] & 0xFFFF) : (unsigned short)0; d[(2 * i + 1) * APH_LDT] = live ? (unsigned short)(w[i] >> 16) : (unsigned short)0; } \
+    }
+// P.V of key tile kt out of Vt: MFMA wave mw owns the dim tiles mw, mw + 4, ..; the accumulators oacc[QS][DPW] persist across the key tiles.  (Vt rows are 140 bytes:
+// 4-byte aligned loads)
+#define APH_PV(Vt, kt, mw)                                                                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < DPW; i++) {                                                                                                                   \
+        const int dt = (mw) + 4 * i;                                                                                                                                    \
+        if (dt < DT) {                                                                                                                                                  \
+            _Pragma("unroll") for (int k2 = 0; k2 < AP_KT / 32; k2++) {                                                                                                 \
+                const unsigned *vp = reinterpret_cast<const unsigned *>(Vt + (16 * dt + l15) * APH_LDT + 32 * k2 + 8 * l4);                                             \
+                union { unsigned u[4]; aph8_t v; } vb;                                                                                                                  \
+                _Pragma("unroll") for (int e = 0; e < 4; e++) vb.u[e] = vp[e];                                                                                          \
+                _Pragma("unroll") for (int qs = 0; qs < QS; qs++) {                                                                                                     \
+                    const float *pp = S + (size_t)(16 * qs + l15) * LS + (kt) * AP_KT + 32 * k2 + 8 * l4;                                                               \
+                    const float4 a = *reinterpret_cast<const float4 *>(pp), b = *reinterpret_cast<const float4 *>(pp + 4);                                              \
+                    aph8_t pf;                                                                                                                                          \
+                    pf[0] = (_Float16)a.x; pf[1] = (_Float16)a.y; pf[2] = (_Float16)a.z; pf[3] = (_Float16)a.w; pf[4] = (_Float16)b.x; pf[5] = (_Float16)b.y; pf[6] = (_Float16)b.z; pf[7] = (_Float16)b.w; \
+                    oacc[qs][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pf, vb.v, oacc[qs][i], 0, 0, 0);                                                               \
+                }                                                                                                                                                       \
+            }                                                                                                                                                           \
+        }                                                                                                                                                               \
+    }
+#define APH_ZERO_OACC                                                                                                                                                   \
+    pf4_t oacc[QS][DPW];                                                                                                                                                \
+    _Pragma("unroll") for (int qs = 0; qs < QS; qs++)                                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < DPW; i++) oacc[qs][i] = pf4_t{0.0f, 0.0f, 0.0f, 0.0f}
+// store of MFMA wave mw.  out_h given (8-wave form): the rows as the consumer wants them (an F16 wo multiplies the fp16-rounded attention output: the conversion launch
+// is saved), pairs of dims from neighbouring lanes as 4-byte stores; else the f32 rows
+#define APH_STORE(mw)                                                                                                                                                   \
+    _Pragma("unroll") for (int qs = 0; qs < QS; qs++)                                                                                                                   \
+        _Pragma("unroll") for (int i = 0; i < DPW; i++) {                                                                                                               \
+            const int dt = (mw) + 4 * i;                                                                                                                                \
+            if (dt < DT) {                                                                                                                                              \
+                _Pragma("unroll") for (int r = 0; r < 4; r++) {                                                                                                         \
+                    const int qrow = q0 + 16 * qs + l4 * 4 + r;                                                                                                         \
+                    if (out_h) {                                                                                                                                        \
+                        const float o0 = oacc[qs][i][r], o1 = __shfl_xor(o0, 1);                                                                                        \
+                        if (qrow < N && !(l15 & 1)) *reinterpret_cast<__half2 *>(out_h + (size_t)qrow * E + (size_t)h * HD + dt * 16 + l15) = __halves2half2(f2h_rn(o0), f2h_rn(o1)); \
+                    } else if (qrow < N) out[(size_t)qrow * E + (size_t)h * HD + dt * 16 + l15] = oacc[qs][i][r];                                                       \
+                }                                                                                                                                                       \
+            }                                                                                                                                                           \
+        }
+// ---- the 4-wave schedule: every wave stages and multiplies.  Per key tile [barrier, LDS write of the staged tile, global loads of tile kt + 1 (register double buffer:
+// one exposed memory round trip per phase instead of one per tile), barrier, MFMAs]; the softmax takes 16 rows at a time.
 template <int HD, int QS, typename... Seg>
 __global__ __launch_bounds__(256) void k_attn_prefill_h(const float *__restrict__ q, const __half *__restrict__ kc, const __half *__restrict__ vc, int E, int N, const int *__restrict__ n_past,
                                                         const Tables tb, float *__restrict__ out, int LS, const Seg... seg) {
-    constexpr bool SEG = sizeof...(Seg) > 0;
+    APH_GEOMETRY;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_aph[];
-    constexpr int C8 = HD / 8, QT = AP_QT * QS, KSQ = HD / 32, DT = HD / 16, PER = AP_KT * C8 / 256;
-    static_assert(PER >= 1 && (DT % 4 == 0 || DT == 2), "tile geometry");
     float *S = reinterpret_cast<float *>(smem_aph);               // [QT][LS], LS = 4 mod 64
-    __half *Kt = reinterpret_cast<__half *>(S + (size_t)QT * LS); // [64][HD], chunk c of row j at slot c ^ (j & (C8 - 1))
+    __half *Kt = reinterpret_cast<__half *>(S + (size_t)QT * LS); // [64][HD]
     __half *Vt = Kt + AP_KT * HD;                                 // [HD][APH_LDT]
-    // causal: the LAST query tile sees the most keys -- it is dispatched first (longest-first), so the short tiles fill the tail of the launch.  SEG: the work item
-    // (segment, first query) comes from the host's longest-first list instead
-    int q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, np_seg = 0;
-    if constexpr (SEG) {   // the segment's own tile: its rows, its conversation's cache, its first position
-        const AttnSegArgs sa = (seg, ...);
-        const int *t = sa.tiles + 2 * blockIdx.y, *g = sa.segs + 4 * t[0];
-        q0 = t[1]; N = g[2]; np_seg = g[3];
-        q += (size_t)g[1] * E; out += (size_t)g[1] * E; kc += (size_t)g[0] * sa.seq_stride; vc += (size_t)g[0] * sa.seq_stride;
-    }
+    __half *out_h = nullptr;                                      // no fp16 store arm: the compiler drops it
+    APH_TILE
     const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     MG4_TLP(0);
-    const int np = SEG ? np_seg : *n_past;
-    const int T = np + min(q0 + QT - 1, N - 1) + 1;               // keys the last query of this tile sees
-    const int nkt = (T + AP_KT - 1) / AP_KT;
-    const float scale = 1.0f / sqrtf((float)HD);
-    const int l15 = lane & 15, l4 = lane >> 4;
-    aph8_t qf[QS][KSQ];                                           // A fragments: query l15, dims 32 ks + 8 l4 .. + 7, rounded to fp16
-#pragma unroll
-    for (int qs = 0; qs < QS; qs++) {
-        const float *qp = q + (size_t)min(q0 + 16 * qs + l15, N - 1) * E + (size_t)h * HD + 8 * l4;
-#pragma unroll
-        for (int ks = 0; ks < KSQ; ks++) {
-            const float4 a = *reinterpret_cast<const float4 *>(qp + 32 * ks), b = *reinterpret_cast<const float4 *>(qp + 32 * ks + 4);
-            const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int e = 0; e < 8; e++) qf[qs][ks][e] = (_Float16)__half2float(f2h_rn(v[e]));
-        }
-    }
-    // the global loads of tile kt + 1 are issued before the MFMAs of tile kt (register double buffer): one exposed memory round trip per phase instead of one per tile
+    APH_TILE_KEYS;
+    aph8_t qf[QS][KSQ];
+    APH_Q_FRAGS
     int4 xk[PER];
-#pragma unroll
-    for (int u = 0; u < PER; u++) { const int e = tid + 256 * u, j = e / C8, c = e - j * C8; xk[u] = ld16(kc + (size_t)min(j, T - 1) * E + (size_t)h * HD + 8 * c); }
+    APH_KV_LOAD(xk, kc, 0, tid)
     for (int kt = 0; kt < nkt; kt++) {
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < PER; u++) { const int e = tid + 256 * u, j = e / C8, c = e - j * C8; *reinterpret_cast<int4 *>(Kt + j * HD + ((c ^ (j & (C8 - 1))) << 3)) = xk[u]; }
-#pragma unroll
-        for (int u = 0; u < PER; u++) { const int e = tid + 256 * u, j = e / C8, c = e - j * C8; xk[u] = ld16(kc + (size_t)min((kt + 1) * AP_KT + j, T - 1) * E + (size_t)h * HD + 8 * c); }
+        APH_K_WRITE(Kt, xk, tid)
+        APH_KV_LOAD(xk, kc, kt + 1, tid)
         __syncthreads();
-        const int key0 = kt * AP_KT + 16 * wave;
-        if (key0 < T) {
-            const int row = 16 * wave + l15;
-            pf4_t acc[QS];
-#pragma unroll
-            for (int qs = 0; qs < QS; qs++) acc[qs] = pf4_t{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int ks = 0; ks < KSQ; ks++) {
-                const aph8_t kf = *reinterpret_cast<const aph8_t *>(Kt + row * HD + (((4 * ks + l4) ^ (row & (C8 - 1))) << 3));
-#pragma unroll
-                for (int qs = 0; qs < QS; qs++) acc[qs] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[qs][ks], kf, acc[qs], 0, 0, 0);
-            }
-#pragma unroll
-            for (int qs = 0; qs < QS; qs++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) S[(size_t)(16 * qs + l4 * 4 + r) * LS + key0 + l15] = acc[qs][r] * scale;
-        }
+        APH_SCORES(Kt, kt, wave)
     }
     __syncthreads();
     MG4_TLP(1);
 #pragma unroll
-    for (int qs = 0; qs < QS; qs++) {
-        // softmax: 16 lanes per query row, lane `sub` owns the keys 64 s + 4 sub .. + 3 (16-byte LDS accesses); row r sees keys 0 .. np + q0 + r.  Same values as
-        // k_attn_prefill's loop (max, fp16-table exp, exact double sum -- order-free --, p = fp16(e * (1 / sum))); what changed in round 3 is the shape: the timeline
-        // had this phase at 15 of a workgroup's 35 us -- 16 dependent rounds of 4 table gathers per row pass -- now 16 gathers are in flight per round.
-        const int row = 16 * qs + (tid >> 4), sub = tid & 15;
-        const int Tq = min(np + q0 + row + 1, T), nb = nkt * AP_KT;
-        float *sr = S + (size_t)row * LS;
-        float mx = -INFINITY;
-        for (int j = 4 * sub; j < nb; j += 64) {
-            const float4 v = *reinterpret_cast<const float4 *>(sr + j);
-            mx = fmaxf(mx, j < Tq ? v.x : -INFINITY); mx = fmaxf(mx, j + 1 < Tq ? v.y : -INFINITY); mx = fmaxf(mx, j + 2 < Tq ? v.z : -INFINITY); mx = fmaxf(mx, j + 3 < Tq ? v.w : -INFINITY);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 1)); mx = fmaxf(mx, __shfl_xor(mx, 2)); mx = fmaxf(mx, __shfl_xor(mx, 4)); mx = fmaxf(mx, __shfl_xor(mx, 8));
-        double sum = 0.0;
-        for (int j0 = 0; j0 < nb; j0 += 256) {
-            float x[16]; unsigned short t[16];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int jj = min(j0 + 64 * u, nb - 64) + 4 * sub;          // a block past the end repeats the last one (its values are dropped below)
-                const float4 v = *reinterpret_cast<const float4 *>(sr + jj);
-                x[4 * u] = v.x; x[4 * u + 1] = v.y; x[4 * u + 2] = v.z; x[4 * u + 3] = v.w;
-            }
-            // (the table stays in global memory: an LDS copy -- 39 KB by LDS-DMA per workgroup -- left this phase at 8.0 us against 7.7 and cost the 142-row launch its
-            //  co-resident workgroups, 11.3 -> 15.1 us: the phase is bound by its ~30 vector instructions per element, not by the gathers)
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const int jj = j0 + 64 * (e >> 2) + 4 * sub + (e & 3);
-                t[e] = reinterpret_cast<const unsigned short *>(tb.exp)[f2h_bits(jj < Tq ? x[e] - mx : 0.0f)];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int jj = j0 + 64 * u + 4 * sub;
-                if (j0 + 64 * u < nb) {                                       // uniform over the 16 lanes of a row
-                    float4 ev;
-                    ev.x = jj < Tq ? h2f_bits(t[4 * u]) : 0.0f; ev.y = jj + 1 < Tq ? h2f_bits(t[4 * u + 1]) : 0.0f; ev.z = jj + 2 < Tq ? h2f_bits(t[4 * u + 2]) : 0.0f; ev.w = jj + 3 < Tq ? h2f_bits(t[4 * u + 3]) : 0.0f;
-                    sum += (double)ev.x; sum += (double)ev.y; sum += (double)ev.z; sum += (double)ev.w;
-                    *reinterpret_cast<float4 *>(sr + jj) = ev;
-                }
-            }
-        }
-        sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);
-        const float inv = (float)(1.0 / sum);
-        for (int j = 4 * sub; j < nb; j += 64) {                             // keys past the row's limit already hold 0
-            float4 v = *reinterpret_cast<const float4 *>(sr + j);
-            v.x = f16r(v.x * inv); v.y = f16r(v.y * inv); v.z = f16r(v.z * inv); v.w = f16r(v.w * inv);
-            *reinterpret_cast<float4 *>(sr + j) = v;
-        }
-    }
+    for (int qs = 0; qs < QS; qs++) { APH_SOFTMAX_ROW(16 * qs + (tid >> 4)) }
     MG4_TLP(2);
-    constexpr int DPW = (DT + 3) / 4;
-    pf4_t oacc[QS][DPW];
-#pragma unroll
-    for (int qs = 0; qs < QS; qs++)
-#pragma unroll
-        for (int i = 0; i < DPW; i++) oacc[qs][i] = pf4_t{0.0f, 0.0f, 0.0f, 0.0f};
+    APH_ZERO_OACC;
     int4 xv[PER];
-#pragma unroll
-    for (int u = 0; u < PER; u++) { const int e = tid + 256 * u, j = e / C8, c = e - j * C8; xv[u] = ld16(vc + (size_t)min(j, T - 1) * E + (size_t)h * HD + 8 * c); }
+    APH_KV_LOAD(xv, vc, 0, tid)
     for (int kt = 0; kt < nkt; kt++) {
         __syncthreads();
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            const int e = tid + 256 * u, j = e / C8, c = e - j * C8;
-            const bool live = kt * AP_KT + j < T;
-            const unsigned w[4] = {(unsigned)xv[u].x, (unsigned)xv[u].y, (unsigned)xv[u].z, (unsigned)xv[u].w};
-            unsigned short *d = reinterpret_cast<unsigned short *>(Vt) + (8 * c) * APH_LDT + j;
-#pragma unroll
-            for (int i = 0; i < 4; i++) { d[(2 * i) * APH_LDT] = live ? (unsigned short)(w[i] & 0xFFFF) : (unsigned short)0; d[(2 * i + 1) * APH_LDT] = live ? (unsigned short)(w[i] >> 16) : (unsigned short)0; }
-        }
-#pragma unroll
-        for (int u = 0; u < PER; u++) { const int e = tid + 256 * u, j = e / C8, c = e - j * C8; xv[u] = ld16(vc + (size_t)min((kt + 1) * AP_KT + j, T - 1) * E + (size_t)h * HD + 8 * c); }
+        APH_V_WRITE(Vt, xv, kt, tid)
+        APH_KV_LOAD(xv, vc, kt + 1, tid)
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < DPW; i++) {
-            const int dt = wave + 4 * i;
-            if (dt < DT) {
-#pragma unroll
-                for (int k2 = 0; k2 < AP_KT / 32; k2++) {
-                    const unsigned *vp = reinterpret_cast<const unsigned *>(Vt + (16 * dt + l15) * APH_LDT + 32 * k2 + 8 * l4);   // 4-byte aligned: 140-byte rows
-                    union { unsigned u[4]; aph8_t v; } vb;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) vb.u[e] = vp[e];
-#pragma unroll
-                    for (int qs = 0; qs < QS; qs++) {
-                        const float *pp = S + (size_t)(16 * qs + l15) * LS + kt * AP_KT + 32 * k2 + 8 * l4;
-                        const float4 a = *reinterpret_cast<const float4 *>(pp), b = *reinterpret_cast<const float4 *>(pp + 4);
-                        aph8_t pf;
-                        pf[0] = (_Float16)a.x; pf[1] = (_Float16)a.y; pf[2] = (_Float16)a.z; pf[3] = (_Float16)a.w; pf[4] = (_Float16)b.x; pf[5] = (_Float16)b.y; pf[6] = (_Float16)b.z; pf[7] = (_Float16)b.w;
-                        oacc[qs][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pf, vb.v, oacc[qs][i], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        APH_PV(Vt, kt, wave)
     }
     MG4_TLP(3);
-#pragma unroll
-    for (int qs = 0; qs < QS; qs++)
-#pragma unroll
-        for (int i = 0; i < DPW; i++) {
-            const int dt = wave + 4 * i;
-            if (dt < DT) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int qrow = q0 + 16 * qs + l4 * 4 + r;
-                    if (qrow < N) out[(size_t)qrow * E + (size_t)h * HD + dt * 16 + l15] = oacc[qs][i][r];
-                }
-            }
-        }
+    APH_STORE(wave)
 #ifdef MG4_TIMELINE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     MG4_TLP(4);
 #endif
 }
-// ---------------------------------------------------------------------------------------------------------------------
-// k_attn_prefill_h8 (round 3): the same arithmetic as k_attn_prefill_h in a 512-thread workgroup whose waves have ROLES.  The timeline of the 4-wave form had a 512-key
-// workgroup at 6.2 us of scores + 7.7 us of softmax + 12.7 us of P.V, each key tile paying [barrier, LDS write of the staged tile, barrier, MFMAs] in sequence on the same
-// four waves.  Here waves 4..7 are LOADERS (global -> registers two tiles ahead -> LDS tile kt, transposing V) while waves 0..3 multiply tile kt - 1 out of the OTHER LDS
-// buffer: one barrier per tile and the staging runs beside the MFMAs; the softmax uses all 512 threads (32 rows x 16 lanes at once).  QS = 2 only (32 queries).
-// Every value is formed by the same operations in the same order as in k_attn_prefill_h (scores: one MFMA chain per (query group, key tile) over ks; softmax: order-free
-// max / exact sum; P.V: tiles in key order), so the two kernels are bit-identical (MINIGPT4_ATTN_PREFILL_W8=0 selects the 4-wave form, A/B).
-// ---------------------------------------------------------------------------------------------------------------------
+// ---- the 8-wave schedule (32 queries): a 512-thread workgroup whose waves have ROLES.  The timeline of the 4-wave form had a 512-key workgroup at 6.2 us of scores +
+// 7.7 us of softmax + 12.7 us of P.V, each key tile paying its barriers, LDS write and MFMAs in sequence on the same four waves.  Here waves 4..7 are LOADERS (global ->
+// registers two tiles ahead -> LDS tile kt) while waves 0..3 multiply tile kt - 1 out of the OTHER LDS buffer: one barrier per tile and the staging runs beside the MFMAs;
+// the softmax uses all 512 threads (32 rows x 16 lanes at once), and the first two V tiles are requested before it.  It also has the fp16 store arm (out_h).
+// MINIGPT4_ATTN_PREFILL_W8=0 selects the 4-wave form (A/B).
 template <int HD, typename... Seg>
 __global__ __launch_bounds__(512) void k_attn_prefill_h8(const float *__restrict__ q, const __half *__restrict__ kc, const __half *__restrict__ vc, int E, int N, const int *__restrict__ n_past,
                                                          const Tables tb, float *__restrict__ out, int LS, __half *__restrict__ out_h, const Seg... seg) {
-    constexpr bool SEG = sizeof...(Seg) > 0;
+    constexpr int QS = 2;
+    APH_GEOMETRY;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_aph8[];
-    constexpr int QS = 2, C8 = HD / 8, QT = AP_QT * QS, KSQ = HD / 32, DT = HD / 16, PER = AP_KT * C8 / 256;
     constexpr int KVB = (AP_KT * HD * 2 > HD * APH_LDT * 2 ? AP_KT * HD * 2 : HD * APH_LDT * 2);        // bytes of one K (or transposed V) tile buffer
-    static_assert(PER >= 1 && (DT % 4 == 0 || DT == 2), "tile geometry");
     float *S = reinterpret_cast<float *>(smem_aph8);                                                 // [QT][LS]
     unsigned char *kvb = smem_aph8 + (size_t)QT * LS * 4;                                             // two tile buffers (K tiles, later V tiles)
-    int q0 = (int)(gridDim.y - 1 - blockIdx.y) * QT, np_seg = 0;
-    if constexpr (SEG) {   // the segment's own tile: its rows, its conversation's cache, its first position
-        const AttnSegArgs sa = (seg, ...);
-        const int *t = sa.tiles + 2 * blockIdx.y, *g = sa.segs + 4 * t[0];
-        q0 = t[1]; N = g[2]; np_seg = g[3];
-        q += (size_t)g[1] * E; out += (size_t)g[1] * E; kc += (size_t)g[0] * sa.seq_stride; vc += (size_t)g[0] * sa.seq_stride;
-        if (out_h) out_h += (size_t)g[1] * E;
-    }
+    APH_TILE
     const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = wave >= 4;
     const int lt = tid & 255, mw = wave & 3;                                                           // loader thread / MFMA wave index
     MG4_TLP(0);
-    const int np = SEG ? np_seg : *n_past;
-    const int T = np + min(q0 + QT - 1, N - 1) + 1;
-    const int nkt = (T + AP_KT - 1) / AP_KT;
-    const float scale = 1.0f / sqrtf((float)HD);
-    const int l15 = lane & 15, l4 = lane >> 4;
+    APH_TILE_KEYS;
     aph8_t qf[QS][KSQ];
-    if (!loader) {
-#pragma unroll
-        for (int qs = 0; qs < QS; qs++) {
-            const float *qp = q + (size_t)min(q0 + 16 * qs + l15, N - 1) * E + (size_t)h * HD + 8 * l4;
-#pragma unroll
-            for (int ks = 0; ks < KSQ; ks++) {
-                const float4 a = *reinterpret_cast<const float4 *>(qp + 32 * ks), b = *reinterpret_cast<const float4 *>(qp + 32 * ks + 4);
-                const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-                for (int e = 0; e < 8; e++) qf[qs][ks][e] = (_Float16)__half2float(f2h_rn(v[e]));
-            }
-        }
-    }
+    if (!loader) { APH_Q_FRAGS }
     // ---- scores: iteration kt stages tile kt (loaders) and multiplies tile kt - 1 (MFMA waves)
     int4 xa[PER], xb[PER];                                                                            // loaders: tiles kt and kt + 1 in flight
-#define MG4_KV_LOAD(X, base, tile)                                                                          \
-    _Pragma("unroll") for (int u = 0; u < PER; u++) { const int e = lt + 256 * u, j = e / C8, c = e - j * C8;   \
-        X[u] = ld16(base + (size_t)min((tile) * AP_KT + j, T - 1) * E + (size_t)h * HD + 8 * c); }
-    if (loader) { MG4_KV_LOAD(xa, kc, 0) MG4_KV_LOAD(xb, kc, 1) }
-    auto k_write = [&](const int4 (&X)[PER], int buf) {
-        __half *Kt = reinterpret_cast<__half *>(kvb + (size_t)buf * KVB);
-#pragma unroll
-        for (int u = 0; u < PER; u++) { const int e = lt + 256 * u, j = e / C8, c = e - j * C8; *reinterpret_cast<int4 *>(Kt + j * HD + ((c ^ (j & (C8 - 1))) << 3)) = X[u]; }
-    };
-    auto k_mul = [&](int kt, int buf) {
-        const __half *Kt = reinterpret_cast<const __half *>(kvb + (size_t)buf * KVB);
-        const int key0 = kt * AP_KT + 16 * mw;
-        if (key0 < T) {
-            const int row = 16 * mw + l15;
-            pf4_t acc[QS];
-#pragma unroll
-            for (int qs = 0; qs < QS; qs++) acc[qs] = pf4_t{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int ks = 0; ks < KSQ; ks++) {
-                const aph8_t kf = *reinterpret_cast<const aph8_t *>(Kt + row * HD + (((4 * ks + l4) ^ (row & (C8 - 1))) << 3));
-#pragma unroll
-                for (int qs = 0; qs < QS; qs++) acc[qs] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qf[qs][ks], kf, acc[qs], 0, 0, 0);
-            }
-#pragma unroll
-            for (int qs = 0; qs < QS; qs++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) S[(size_t)(16 * qs + l4 * 4 + r) * LS + key0 + l15] = acc[qs][r] * scale;
-        }
-    };
+    if (loader) { APH_KV_LOAD(xa, kc, 0, lt) APH_KV_LOAD(xb, kc, 1, lt) }
+    auto k_write = [&](const int4 (&X)[PER], int buf) { __half *Kt = reinterpret_cast<__half *>(kvb + (size_t)buf * KVB); APH_K_WRITE(Kt, X, lt) };
+    auto k_mul = [&](int kt, int buf) { const __half *Kt = reinterpret_cast<const __half *>(kvb + (size_t)buf * KVB); APH_SCORES(Kt, kt, mw) };
     for (int kt = 0; kt <= nkt; kt += 2) {
-        if (loader) { if (kt < nkt) { k_write(xa, 0); MG4_KV_LOAD(xa, kc, kt + 2) } }
+        if (loader) { if (kt < nkt) { k_write(xa, 0); APH_KV_LOAD(xa, kc, kt + 2, lt) } }
         else if (kt >= 1) k_mul(kt - 1, 1);
         __syncthreads();
         if (kt + 1 > nkt) break;
-        if (loader) { if (kt + 1 < nkt) { k_write(xb, 1); MG4_KV_LOAD(xb, kc, kt + 3) } }
+        if (loader) { if (kt + 1 < nkt) { k_write(xb, 1); APH_KV_LOAD(xb, kc, kt + 3, lt) } }
         else k_mul(kt, 0);
         __syncthreads();
     }
     MG4_TLP(1);
-    // the first two V tiles are requested now: they arrive while the softmax runs
-    if (loader) { MG4_KV_LOAD(xa, vc, 0) MG4_KV_LOAD(xb, vc, 1) }
-    {   // softmax: 32 rows x 16 lanes at once (k_attn_prefill_h's code with qs = tid >> 8)
-        const int row = tid >> 4, sub = tid & 15;
-        const int Tq = min(np + q0 + row + 1, T), nb = nkt * AP_KT;
-        float *sr = S + (size_t)row * LS;
-        float mx = -INFINITY;
-        for (int j = 4 * sub; j < nb; j += 64) {
-            const float4 v = *reinterpret_cast<const float4 *>(sr + j);
-            mx = fmaxf(mx, j < Tq ? v.x : -INFINITY); mx = fmaxf(mx, j + 1 < Tq ? v.y : -INFINITY); mx = fmaxf(mx, j + 2 < Tq ? v.z : -INFINITY); mx = fmaxf(mx, j + 3 < Tq ? v.w : -INFINITY);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 1)); mx = fmaxf(mx, __shfl_xor(mx, 2)); mx = fmaxf(mx, __shfl_xor(mx, 4)); mx = fmaxf(mx, __shfl_xor(mx, 8));
-        double sum = 0.0;
-        for (int j0 = 0; j0 < nb; j0 += 256) {
-            float x[16]; unsigned short t[16];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int jj = min(j0 + 64 * u, nb - 64) + 4 * sub;
-                const float4 v = *reinterpret_cast<const float4 *>(sr + jj);
-                x[4 * u] = v.x; x[4 * u + 1] = v.y; x[4 * u + 2] = v.z; x[4 * u + 3] = v.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 16; e++) {
-                const int jj = j0 + 64 * (e >> 2) + 4 * sub + (e & 3);
-                t[e] = reinterpret_cast<const unsigned short *>(tb.exp)[f2h_bits(jj < Tq ? x[e] - mx : 0.0f)];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int jj = j0 + 64 * u + 4 * sub;
-                if (j0 + 64 * u < nb) {
-                    float4 ev;
-                    ev.x = jj < Tq ? h2f_bits(t[4 * u]) : 0.0f; ev.y = jj + 1 < Tq ? h2f_bits(t[4 * u + 1]) : 0.0f; ev.z = jj + 2 < Tq ? h2f_bits(t[4 * u + 2]) : 0.0f; ev.w = jj + 3 < Tq ? h2f_bits(t[4 * u + 3]) : 0.0f;
-                    sum += (double)ev.x; sum += (double)ev.y; sum += (double)ev.z; sum += (double)ev.w;
-                    *reinterpret_cast<float4 *>(sr + jj) = ev;
-                }
-            }
-        }
-        sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4); sum += __shfl_xor(sum, 8);
-        const float inv = (float)(1.0 / sum);
-        for (int j = 4 * sub; j < nb; j += 64) {
-            float4 v = *reinterpret_cast<const float4 *>(sr + j);
-            v.x = f16r(v.x * inv); v.y = f16r(v.y * inv); v.z = f16r(v.z * inv); v.w = f16r(v.w * inv);
-            *reinterpret_cast<float4 *>(sr + j) = v;
-        }
-    }
+    if (loader) { APH_KV_LOAD(xa, vc, 0, lt) APH_KV_LOAD(xb, vc, 1, lt) }                             // the first two V tiles arrive while the softmax runs
+    { APH_SOFTMAX_ROW(tid >> 4) }
     MG4_TLP(2);
-    // ---- P.V: the same two-role loop over the V tiles (written transposed: [dim][key])
-    constexpr int DPW = (DT + 3) / 4;
-    pf4_t oacc[QS][DPW];
-#pragma unroll
-    for (int qs = 0; qs < QS; qs++)
-#pragma unroll
-        for (int i = 0; i < DPW; i++) oacc[qs][i] = pf4_t{0.0f, 0.0f, 0.0f, 0.0f};
-    auto v_write = [&](const int4 (&X)[PER], int kt, int buf) {
-        __half *Vt = reinterpret_cast<__half *>(kvb + (size_t)buf * KVB);
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            const int e = lt + 256 * u, j = e / C8, c = e - j * C8;
-            const bool live = kt * AP_KT + j < T;
-            const unsigned w[4] = {(unsigned)X[u].x, (unsigned)X[u].y, (unsigned)X[u].z, (unsigned)X[u].w};
-            unsigned short *d = reinterpret_cast<unsigned short *>(Vt) + (8 * c) * APH_LDT + j;
-#pragma unroll
-            for (int i = 0; i < 4; i++) { d[(2 * i) * APH_LDT] = live ? (unsigned short)(w[i] & 0xFFFF) : (unsigned short)0; d[(2 * i + 1) * APH_LDT] = live ? (unsigned short)(w[i] >> 16) : (unsigned short)0; }
-        }
-    };
-    auto v_mul = [&](int kt, int buf) {
-        const __half *Vt = reinterpret_cast<const __half *>(kvb + (size_t)buf * KVB);
-#pragma unroll
-        for (int i = 0; i < DPW; i++) {
-            const int dt = mw + 4 * i;
-            if (dt < DT) {
-#pragma unroll
-                for (int k2 = 0; k2 < AP_KT / 32; k2++) {
-                    const unsigned *vp = reinterpret_cast<const unsigned *>(Vt + (16 * dt + l15) * APH_LDT + 32 * k2 + 8 * l4);
-                    union { unsigned u[4]; aph8_t v; } vb;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) vb.u[e] = vp[e];
-#pragma unroll
-                    for (int qs = 0; qs < QS; qs++) {
-                        const float *pp = S + (size_t)(16 * qs + l15) * LS + kt * AP_KT + 32 * k2 + 8 * l4;
-                        const float4 a = *reinterpret_cast<const float4 *>(pp), b = *reinterpret_cast<const float4 *>(pp + 4);
-                        aph8_t pf;
-                        pf[0] = (_Float16)a.x; pf[1] = (_Float16)a.y; pf[2] = (_Float16)a.z; pf[3] = (_Float16)a.w; pf[4] = (_Float16)b.x; pf[5] = (_Float16)b.y; pf[6] = (_Float16)b.z; pf[7] = (_Float16)b.w;
-                        oacc[qs][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pf, vb.v, oacc[qs][i], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    };
+    // ---- P.V: the same two-role loop over the V tiles
+    APH_ZERO_OACC;
+    auto v_write = [&](const int4 (&X)[PER], int kt, int buf) { __half *Vt = reinterpret_cast<__half *>(kvb + (size_t)buf * KVB); APH_V_WRITE(Vt, X, kt, lt) };
+    auto v_mul = [&](int kt, int buf) { const __half *Vt = reinterpret_cast<const __half *>(kvb + (size_t)buf * KVB); APH_PV(Vt, kt, mw) };
     __syncthreads();                                                     // normalised probabilities visible; the K buffers are free
     for (int kt = 0; kt <= nkt; kt += 2) {
-        if (loader) { if (kt < nkt) { v_write(xa, kt, 0); MG4_KV_LOAD(xa, vc, kt + 2) } }
+        if (loader) { if (kt < nkt) { v_write(xa, kt, 0); APH_KV_LOAD(xa, vc, kt + 2, lt) } }
         else if (kt >= 1) v_mul(kt - 1, 1);
         __syncthreads();
         if (kt + 1 > nkt) break;
-        if (loader) { if (kt + 1 < nkt) { v_write(xb, kt + 1, 1); MG4_KV_LOAD(xb, vc, kt + 3) } }
+        if (loader) { if (kt + 1 < nkt) { v_write(xb, kt + 1, 1); APH_KV_LOAD(xb, vc, kt + 3, lt) } }
         else v_mul(kt, 0);
         __syncthreads();
     }
-#undef MG4_KV_LOAD
     MG4_TLP(3);
-    if (!loader) {
-#pragma unroll
-        for (int qs = 0; qs < QS; qs++)
-#pragma unroll
-            for (int i = 0; i < DPW; i++) {
-                const int dt = mw + 4 * i;
-                if (dt < DT) {
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int qrow = q0 + 16 * qs + l4 * 4 + r;
-                        // out_h: the rows as the consumer wants them (an F16 wo multiplies the fp16-rounded attention output: the conversion launch is saved)
-                        if (out_h) {   // pairs of dims from neighbouring lanes: 4-byte stores
-                            const float o0 = oacc[qs][i][r], o1 = __shfl_xor(o0, 1);
-                            if (qrow < N && !(l15 & 1)) *reinterpret_cast<__half2 *>(out_h + (size_t)qrow * E + (size_t)h * HD + dt * 16 + l15) = __halves2half2(f2h_rn(o0), f2h_rn(o1));
-                        } else if (qrow < N) out[(size_t)qrow * E + (size_t)h * HD + dt * 16 + l15] = oacc[qs][i][r];
-                    }
-                }
-            }
-    }
+    if (!loader) { APH_STORE(mw) }
 #ifdef MG4_TIMELINE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     MG4_TLP(4);
 #endif
 }
+#undef APH_GEOMETRY
+#undef APH_TILE
+#undef APH_TILE_KEYS
+#undef APH_Q_FRAGS
+#undef APH_KV_LOAD
+#undef APH_K_WRITE
+#undef APH_SCORES
+#undef APH_SOFTMAX_ROW
+#undef APH_V_WRITE
+#undef APH_PV
+#undef APH_ZERO_OACC
+#undef APH_STORE
+// ---- launchers.  Forms: 1 = k_attn_prefill_h8, 2 = k_attn_prefill_h<HD, 2>, 3 = k_attn_prefill_h<HD, 1>, 4 = the exact-f32 k_attn_prefill<HD, 1>
 static int g_attn_prefill_w8 = 1;    // 1: the 8-wave loader / MFMA form for 32-query tiles; MINIGPT4_ATTN_PREFILL_W8, read by Engine::init
 void set_attn_prefill_w8(int v) { g_attn_prefill_w8 = v != 0; }
-template <int HD>
-static bool launch_attn_prefill_h8(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s, __half *out_h) {
-    const int LS = ((t_max + AP_KT - 1) / AP_KT) * AP_KT + 4;
-    static bool attr = false;
-    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h8<HD>)); attr = true; }
-    const size_t kvbytes = std::max((size_t)AP_KT * HD * 2, (size_t)HD * APH_LDT * 2);
-    const size_t lds = (size_t)AP_QT * 2 * LS * 4 + 2 * kvbytes;
-    if (lds > 160 * 1024 - 512) return false;
-    hipLaunchKernelGGL((k_attn_prefill_h8<HD>), dim3((unsigned)n_head, (unsigned)((N + AP_QT * 2 - 1) / (AP_QT * 2))), dim3(512), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS, out_h);
-    return true;
-}
 static int g_attn_prefill_f16 = 1;   // 1: prompt attention on the fp16 matrix cores (k_attn_prefill_h), 0: the exact-f32 MFMA kernel (k_attn_prefill); test-library setter only
 void set_attn_prefill_f16(int v) { g_attn_prefill_f16 = v != 0; }
 int attn_prefill_f16() { return g_attn_prefill_f16; }
-template <int HD, int QS>
-static bool launch_attn_prefill_h_qs(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s) {
-    const int LS = ((t_max + AP_KT - 1) / AP_KT) * AP_KT + 4;
-    static bool attr = false;
-    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h<HD, QS>)); attr = true; }
-    const size_t lds = (size_t)AP_QT * QS * LS * 4 + (size_t)AP_KT * HD * 2 + (size_t)HD * APH_LDT * 2;
-    if (lds > 160 * 1024 - 512) return false;
-    hipLaunchKernelGGL((k_attn_prefill_h<HD, QS>), dim3((unsigned)n_head, (unsigned)((N + AP_QT * QS - 1) / (AP_QT * QS))), dim3(256), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS);
-    return true;
-}
 static int g_attn_prefill_form = 0;  // test library: 1 / 2 / 3 = only k_attn_prefill_h8 / _h<HD, 2> / _h<HD, 1> is tried (no size rule); 0 = the launchers' own choice
 void set_attn_prefill_form(int v) { g_attn_prefill_form = v; }
 int attn_prefill_form() { return g_attn_prefill_form; }
-template <int HD>
-static bool launch_attn_prefill_hd(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s, __half *out_h, bool *wrote_h) {
-    if (g_attn_prefill_f16) {   // 32 queries per staged K / V tile once that still gives every CU a workgroup
-        const bool wide = n_head * ((N + 31) / 32) >= 256;
-        const int f = g_attn_prefill_form;
-        if ((f == 1 || (f == 0 && g_attn_prefill_w8 && wide)) && launch_attn_prefill_h8<HD>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s, out_h)) { if (wrote_h) *wrote_h = out_h != nullptr; return true; }
-        if ((f == 2 || (f == 0 && wide)) && launch_attn_prefill_h_qs<HD, 2>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s)) return true;
-        if ((f == 0 || f == 3) && launch_attn_prefill_h_qs<HD, 1>(q, kc, vc, N, n_head, n_past, t_max, tb, out, s)) return true;
+// the LDS image of a form for score rows of t_max keys: *LS = floats per score row; returns its bytes, 0 when it exceeds the 160 KiB of a CU (the form refuses).
+// Forms 1 .. 3: score rows + fp16 K tile + transposed V tile (form 1: two buffers that hold either); form 4: score rows + one f32 tile.
+static size_t attn_prefill_lds(int form, int hd, int t_max, int *LS) {
+    *LS = ((t_max + AP_KT - 1) / AP_KT) * AP_KT + (form == 4 ? 1 : 4);
+    const size_t rows = (size_t)AP_QT * (form <= 2 ? 2 : 1) * *LS * 4, kt = (size_t)AP_KT * hd * 2, vt = (size_t)hd * APH_LDT * 2;
+    const size_t lds = rows + (form == 1 ? 2 * std::max(kt, vt) : form == 4 ? (size_t)AP_KT * (hd + 1) * 4 : kt + vt);
+    return lds > 160 * 1024 - 512 ? 0 : lds;
+}
+// the fp16 forms in the order they are tried.  wide: 32 queries per staged K / V tile still give every CU a workgroup
+static int attn_prefill_forms(bool wide, int (&forms)[3]) {
+    const int f = g_attn_prefill_form;
+    int n = 0;
+    if (f == 1 || (f == 0 && g_attn_prefill_w8 && wide)) forms[n++] = 1;
+    if (f == 2 || (f == 0 && wide)) forms[n++] = 2;
+    if (f == 0 || f == 3) forms[n++] = 3;
+    return n;
+}
+// one fp16 form over `tiles` query tiles: of one conversation (N rows at *n_past), or with a trailing AttnSegArgs of the segments of a packed chunk (N = 0, no n_past).
+// false: its LDS image does not fit
+template <int HD, int FORM, typename... Seg>
+static bool launch_attn_prefill_form(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, int tiles, const Tables &tb, float *out, hipStream_t s,
+                                     __half *out_h, const Seg... seg) {
+    int LS;
+    const size_t lds = attn_prefill_lds(FORM, HD, t_max, &LS);
+    if (!lds) return false;
+    const dim3 grid((unsigned)n_head, (unsigned)tiles);
+    static bool attr = false;
+    if constexpr (FORM == 1) {
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h8<HD, Seg...>)); attr = true; }
+        if constexpr (sizeof...(Seg) > 0) note_kernel("k_attn_prefill_h8<%d, SEG>", HD);
+        hipLaunchKernelGGL((k_attn_prefill_h8<HD, Seg...>), grid, dim3(512), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS, out_h, seg...);
+    } else {
+        constexpr int QS = FORM == 2 ? 2 : 1;
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h<HD, QS, Seg...>)); attr = true; }
+        if constexpr (sizeof...(Seg) > 0) note_kernel("k_attn_prefill_h<%d, %d, SEG>", HD, QS);
+        hipLaunchKernelGGL((k_attn_prefill_h<HD, QS, Seg...>), grid, dim3(256), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS, seg...);
     }
-    // Fallback: k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken (a) after set_attn_prefill_f16(0) (test library: the A/B switch of
-    // the fp16 kernels), (b) when the fp16 kernels refuse because their LDS image (score rows + fp16 K tile + transposed V tile) exceeds the 160 KiB of a CU.  Both forms
-    // hold 16 score rows of the whole context: at head size 128 both end at 1984 keys; beyond, this returns false and Engine::forward runs the rows through the decode
-    // attention kernel (k_attn_llm, one query row per workgroup), which has no such limit.
-    const int LS = ((t_max + AP_KT - 1) / AP_KT) * AP_KT + 1;
+    return true;
+}
+// the first fp16 form of attn_prefill_forms that fits; sg: the segments of a packed chunk, nullptr: one conversation.  *wrote_h: the 8-wave form ran and stored fp16 rows
+template <int HD>
+static bool launch_attn_prefill_f16(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const AttnSegs *sg, const Tables &tb, float *out,
+                                    hipStream_t s, __half *out_h, bool *wrote_h) {
+    auto tiles = [&](int qs) { return sg ? sg->n_tiles[qs - 1] : (N + AP_QT * qs - 1) / (AP_QT * qs); };
+    auto launch = [&](auto form) {
+        constexpr int FORM = decltype(form)::value, QS = FORM == 3 ? 1 : 2;
+        __half *oh = FORM == 1 ? out_h : nullptr;                      // only the 8-wave form has the fp16 store arm
+        if (sg) return launch_attn_prefill_form<HD, FORM>(q, kc, vc, 0, n_head, nullptr, t_max, tiles(QS), tb, out, s, oh, AttnSegArgs{sg->segs, sg->tiles[QS - 1], (long long)sg->seq_stride});
+        return launch_attn_prefill_form<HD, FORM>(q, kc, vc, N, n_head, n_past, t_max, tiles(QS), tb, out, s, oh);
+    };
+    int forms[3];
+    const int n = attn_prefill_forms(n_head * tiles(2) >= 256, forms);
+    for (int i = 0; i < n; i++) {
+        const int f = forms[i];
+        if (f == 1 ? launch(std::integral_constant<int, 1>{}) : f == 2 ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 3>{})) {
+            if (f == 1 && wrote_h) *wrote_h = out_h != nullptr;
+            return true;
+        }
+    }
+    return false;
+}
+// Fallback: k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken (a) after set_attn_prefill_f16(0) (test library: the A/B switch of
+// the fp16 kernels), (b) when the fp16 kernels refuse because their LDS image exceeds the 160 KiB of a CU.  Both forms hold 16 score rows of the whole context: at head
+// size 128 both end at 1984 keys; beyond, this returns false and Engine::forward runs the rows through the decode attention kernel (k_attn_llm, one query row per
+// workgroup), which has no such limit.
+// (QS = 2 -- 32 queries per staged key / value tile from 256 prompt rows on -- is bit-identical and was measured 2 % SLOWER at 512 rows: 13B Q5_K_M 31.7 vs 31.0 ms,
+// 13B f16 27.9 vs 27.2 ms, profiles/r02r_prefill_ksplit_fill_sweep.log; half the workgroups, each twice as long: not instantiated.)
+template <int HD>
+static bool launch_attn_prefill_f32(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s) {
+    int LS;
+    const size_t lds = attn_prefill_lds(4, HD, t_max, &LS);
+    if (!lds) return false;
     static bool attr = false;
     if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill<HD, 1>)); attr = true; }
-    // (QS = 2 -- 32 queries per staged key / value tile from 256 prompt rows on -- is bit-identical and was measured 2 % SLOWER at 512 rows: 13B Q5_K_M 31.7 vs 31.0 ms,
-    // 13B f16 27.9 vs 27.2 ms, profiles/r02r_prefill_ksplit_fill_sweep.log; half the workgroups, each twice as long: not instantiated.)
-    const size_t lds = ((size_t)AP_QT * LS + (size_t)AP_KT * (HD + 1)) * 4;
-    if (lds > 160 * 1024 - 512) return false;
     hipLaunchKernelGGL((k_attn_prefill<HD, 1>), dim3((unsigned)n_head, (unsigned)((N + AP_QT - 1) / AP_QT)), dim3(256), lds, s, q, kc, vc, n_head * HD, N, n_past, tb, out, LS);
     return true;
 }
-// Segmented prompt attention (Engine::prefill_batch): one launch over every segment of a packed chunk; the same forms and the same size rule as
-// launch_attn_prefill_hd, with the 32-query work items of all segments standing in for one conversation's tiles.
+// Segmented prompt attention (Engine::prefill_batch): one launch over every segment of a packed chunk; the same forms and the same size rule as launch_attn_prefill,
+// with the 32-query work items of all segments standing in for one conversation's tiles.
 int attn_seg_tiles(const int *segs, int n_seg, int qt, int *out) {
     struct Item { int seg, q0, keys; };
     std::vector<Item> v;
@@ -2648,45 +2565,12 @@ int attn_seg_tiles(const int *segs, int n_seg, int qt, int *out) {
     for (size_t k = 0; k < v.size(); k++) { out[2 * k] = v[k].seg; out[2 * k + 1] = v[k].q0; }
     return (int)v.size();
 }
-template <int HD>
-static bool launch_attn_prefill_seg_hd(const float *q, const __half *kc, const __half *vc, const AttnSegs &sg, int n_head, const Tables &tb, float *out, hipStream_t s, __half *out_h,
-                                       bool *wrote_h) {
-    if (!g_attn_prefill_f16) return false;           // the exact-f32 kernel: per-segment launches (the caller)
-    const int E = n_head * HD, f = g_attn_prefill_form;
-    const bool wide = n_head * sg.n_tiles[1] >= 256;
-    const int LS = ((sg.t_max + AP_KT - 1) / AP_KT) * AP_KT + 4;
-    if (f == 1 || (f == 0 && g_attn_prefill_w8 && wide)) {
-        const size_t lds = (size_t)AP_QT * 2 * LS * 4 + 2 * std::max((size_t)AP_KT * HD * 2, (size_t)HD * APH_LDT * 2);
-        if (lds <= 160 * 1024 - 512) {
-            static bool attr = false;
-            if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h8<HD, AttnSegArgs>)); attr = true; }
-            note_kernel("k_attn_prefill_h8<%d, SEG>", HD);
-            hipLaunchKernelGGL((k_attn_prefill_h8<HD, AttnSegArgs>), dim3((unsigned)n_head, (unsigned)sg.n_tiles[1]), dim3(512), lds, s, q, kc, vc, E, 0, (const int *)nullptr, tb, out, LS,
-                               out_h, AttnSegArgs{sg.segs, sg.tiles[1], (long long)sg.seq_stride});
-            if (wrote_h) *wrote_h = out_h != nullptr;
-            return true;
-        }
-    }
-    auto h_qs = [&](auto qs_tag) {
-        constexpr int QS = decltype(qs_tag)::value;
-        const size_t lds = (size_t)AP_QT * QS * LS * 4 + (size_t)AP_KT * HD * 2 + (size_t)HD * APH_LDT * 2;
-        if (lds > 160 * 1024 - 512) return false;
-        static bool attr = false;
-        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_prefill_h<HD, QS, AttnSegArgs>)); attr = true; }
-        note_kernel("k_attn_prefill_h<%d, %d, SEG>", HD, QS);
-        hipLaunchKernelGGL((k_attn_prefill_h<HD, QS, AttnSegArgs>), dim3((unsigned)n_head, (unsigned)sg.n_tiles[QS - 1]), dim3(256), lds, s, q, kc, vc, E, 0, (const int *)nullptr, tb, out, LS,
-                           AttnSegArgs{sg.segs, sg.tiles[QS - 1], (long long)sg.seq_stride});
-        return true;
-    };
-    if ((f == 2 || (f == 0 && wide)) && h_qs(std::integral_constant<int, 2>{})) return true;
-    if ((f == 0 || f == 3) && h_qs(std::integral_constant<int, 1>{})) return true;
-    return false;
-}
 bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, hipStream_t s, __half *out_h,
                              bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
     bool done = false;                                             // an unsupported head size: declined, like a shape that does not fit
-    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_seg_hd<decltype(tag)::value>(q, kcache, vcache, sg, n_head, tb, out, s, out_h, wrote_h); });
+    if (!g_attn_prefill_f16) return false;                         // the exact-f32 kernel: per-segment launches (the caller)
+    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_f16<decltype(tag)::value>(q, kcache, vcache, 0, n_head, nullptr, sg.t_max, &sg, tb, out, s, out_h, wrote_h); });
     return done;
 }
 // N > 1 query rows at positions *n_past .. *n_past + N - 1 (launch_rope_kv has run); t_max >= *n_past + N (the host's view, sizes the LDS score rows).
@@ -2695,7 +2579,11 @@ bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vca
                          __half *out_h, bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
     bool done = false;
-    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_hd<decltype(tag)::value>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s, out_h, wrote_h); });
+    attn_for_head_size(hd, [&](auto tag) {
+        constexpr int HD = decltype(tag)::value;
+        done = (g_attn_prefill_f16 && launch_attn_prefill_f16<HD>(q, kcache, vcache, N, n_head, n_past, t_max, nullptr, tb, out, s, out_h, wrote_h)) ||
+               launch_attn_prefill_f32<HD>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s);
+    });
     return done;
 }
 bool attn_head_size_supported(int hd) { return hd == 32 || hd == 64 || hd == 128; }

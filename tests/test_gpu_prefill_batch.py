@@ -64,6 +64,25 @@ def test_segmented_attention_fp16_rows_for_f16_wo(gpu_lib, case, E, H):
     assert np.array_equal(ha, hb)
 
 
+@pytest.mark.parametrize("E,H", [(256, 2), (128, 2), (64, 2)])          # hd 128 / 64 / 32
+def test_prompt_attention_forms_are_bit_identical_to_each_other(gpu_lib, E, H):
+    """The 8-wave form (1), the 4-wave form with 32 queries (2) and with 16 queries (3) are schedules over the same stages: for one input they return the same bits,
+    launched per segment and segmented.  The segments take 1, 2, 3 and 4 key tiles (both exits of the 8-wave form's two-tile loop), row counts that are no multiple
+    of 16 or 32, first positions that are no multiple of 64, and one row."""
+    segs = [(0, 1, 0), (1, 17, 40), (2, 33, 60), (0, 5, 150), (1, 40, 200)]
+    rng = np.random.default_rng(E + H)
+    kc, vc = _caches(rng, 3, 256, E)
+    q = rng.standard_normal((sum(r for _, r, _ in segs), E), dtype=np.float32)
+    res = {form: gpu_lib.amd_test_attn_prefill_seg(kc, vc, H, segs, q, form) for form in (1, 2, 3)}
+    assert all(one for _, _, one in res.values())
+    want = res[1][1]
+    assert np.isfinite(want).all() and np.abs(want).max() > 0
+    for form in (2, 3):
+        assert np.array_equal(res[form][1], want), form
+    for form in (1, 2, 3):
+        assert np.array_equal(res[form][0], want), form
+
+
 @pytest.mark.parametrize("E,H", [(5120, 40), (256, 4), (256, 8)])
 @pytest.mark.parametrize("ks", [1, 3])
 def test_segmented_rope_append_is_bit_identical_to_per_segment_launches(gpu_lib, E, H, ks):
