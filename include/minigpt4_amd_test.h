@@ -46,6 +46,32 @@ MINIGPT4_API int minigpt4_amd_test_gemm_f16_skinny(const float *A, const float *
 /* the same two with the arm chosen by the caller: gelu_table = the 65536 fp16 bit patterns the GELU epilogue gathers from, or NULL = the computed arm (Tables::gelu null, what the
  * engine's fast mode passes); skinny != 0: the skinny-M kernel */
 MINIGPT4_API int minigpt4_amd_test_gemm_f16_ex(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, int skinny, const unsigned short *gelu_table, float *C);
+/* ---- the image encoder's kernels between its GEMMs, one launch each (tests/test_gpu_vision_kernels.py).  Common form: 1 = bad arguments, before any device is touched;
+ * 2 = no device; 3 = HIP error or a launcher's host-side throw (a row longer than 2048, more than 12 slabs, D % hd != 0); 4 = the launcher returned false.  Every output
+ * buffer is prefilled with 0xFF bytes and has ONE GUARD ROW past `rows`, copied back with the rows; nothing is copied back unless the call returns 0. */
+/* launch_layernorm (k_layernorm<3|6|8>): x [rows][n], w [n], b [n] or NULL; sequential_sums != 0: parity mode's one-thread sums.  out [rows + 1][n] fp32 and / or
+ * out_h [rows + 1][n] fp16 bit patterns (either may be NULL, not both) */
+MINIGPT4_API int minigpt4_amd_test_layernorm(const float *x, const float *w, const float *b, int rows, int n, int sequential_sums, float *out, unsigned short *out_h);
+/* launch_splitk_reduce_ln (k_splitk_reduce_ln<2|4|8|12, 3|6|8>): slabs = n_slabs x slab_stride floats, row r of slab z at z * slab_stride + r * n (slab_stride >= rows * n; the
+ * caller fills the padding); bias [n] / residual [rows][n] or NULL; in_place != 0: ONE device buffer serves as residual and x_out (needs both), as the ViT blocks call it;
+ * ln_w NULL: no LayerNorm (then ln_b / ln_out / ln_out_h must be NULL too).  x_out / ln_out [rows + 1][n] fp32, ln_out_h [rows + 1][n] fp16 bit patterns */
+MINIGPT4_API int minigpt4_amd_test_splitk_reduce_ln(const float *slabs, int n_slabs, int64_t slab_stride, const float *bias, const float *residual, int in_place, int rows, int n,
+                                                    const float *ln_w, const float *ln_b, float *x_out, float *ln_out, unsigned short *ln_out_h);
+/* The split-K forms of the fp16 GEMM: slab z = the raw fp32 partial product over slice z's k columns.  A [M][K], W [N][K] fp32, rounded to fp16 on the device.
+ * skinny == 0: slices = gemm_split_slices(K, slices_wanted) as the engine computes it, then launch_gemm_f16_splitk (k_gemm_f16 64x64 tiles; from 384 / 640 rows the 128x128 /
+ * 256x128 k_gemm_dma ring tiles); skinny != 0: launch_gemm_f16_skinny_splitk with slices_wanted as given (4, nothing launched, when it refuses).  slabs_out: room for
+ * slices_wanted slabs of [M][N]; the first *slices_used_out are written.  minigpt4_amd_test_set_splitk_xcd / _set_gemm_arm apply */
+MINIGPT4_API int minigpt4_amd_test_gemm_f16_splitk(const float *A, const float *W, int M, int N, int K, int slices_wanted, int skinny, float *slabs_out, int *slices_used_out);
+/* launch_gemm_f16_head_major with N = 3 * D (the ViT's qkv projection).  out = 3 * D guard floats, then [3][D / hd][M][hd], then 3 * D guard floats: (M + 2) * 3 * D floats */
+MINIGPT4_API int minigpt4_amd_test_gemm_f16_head_major(const float *A, const float *W, const float *bias, int M, int D, int hd, int K, float *out);
+/* launch_im2col: image [batch][3][224][224] fp32 -> patches [batch * 256 + 1][ldp] fp16 bit patterns (ldp >= 588; batch <= 16) */
+MINIGPT4_API int minigpt4_amd_test_im2col(const float *image, int batch, int ldp, unsigned short *patches);
+/* launch_assemble_embeddings: cls [D], pe [batch * 256][D], pos [257][D] -> x [batch * 257 + 1][D] */
+MINIGPT4_API int minigpt4_amd_test_assemble(const float *cls, const float *pe, const float *pos, int batch, int D, float *x);
+/* launch_lin_epilogue: out = [residual +] gelu?(bias + y); y / residual [rows][n], bias [n]; gelu_table (65536 fp16 bit patterns) non-NULL = with the GELU step, gathered
+ * from it (this launch always gathers).  out [rows + 1][n] fp32 and / or out_h [rows + 1][n] fp16 bit patterns */
+MINIGPT4_API int minigpt4_amd_test_lin_epilogue(const float *y, const float *bias, const float *residual, const unsigned short *gelu_table, int rows, int n, float *out,
+                                                unsigned short *out_h);
 /* exp / SiLU / GELU exactly as the kernels' epilogues call them (csrc/activations.hpp), evaluated on all 65536 fp16 bit patterns -> out[65536] fp16 bit patterns.
  * which: 0 GELU, 1 SiLU, 2 exp; table (65536 fp16 bit patterns) is gathered from, NULL selects the computed form */
 MINIGPT4_API int minigpt4_amd_test_activation(int which, const unsigned short *table, unsigned short *out);

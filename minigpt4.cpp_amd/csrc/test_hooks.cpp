@@ -416,6 +416,162 @@ static int test_gemm_impl(const float *A, const float *W, const float *bias, int
     });
 }
 
+// ---- the image encoder's kernels BETWEEN its GEMMs, one launch each (tests/test_gpu_vision_kernels.py).  Common form: arguments checked before a device is touched (1);
+// every output buffer is prefilled with 0xFF bytes and carries one guard row past `rows`, copied back with the rows; a launcher's host-side throw arrives as 3 through guarded().
+static constexpr int VK_MAX_ROWS = 4096, VK_MAX_N = 1 << 16;     // sanity caps of the hooks' allocations, far above every launcher's own limit
+static void upload_f32(DevBuf &d, const float *src, size_t n) { HIP_CHECK(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice)); }
+
+// launch_layernorm: x [rows][n], w [n], b [n] or NULL -> out [rows + 1][n] fp32 and / or out_h [rows + 1][n] fp16 bits (either may be NULL, not both)
+int minigpt4_amd_test_layernorm(const float *x, const float *w, const float *b, int rows, int n, int sequential_sums, float *out, unsigned short *out_h) {
+    if (!x || !w || (!out && !out_h) || rows < 1 || rows > VK_MAX_ROWS || n < 1 || n > VK_MAX_N) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t rn = (size_t)rows * n, gn = rn + (size_t)n;
+        DevBuf dx(rn * 4), dw((size_t)n * 4), db((size_t)n * 4), dout(gn * 4), douth(gn * 2);
+        upload_f32(dx, x, rn); upload_f32(dw, w, (size_t)n);
+        if (b) upload_f32(db, b, (size_t)n);
+        HIP_CHECK(hipMemset(dout.p, 0xFF, gn * 4)); HIP_CHECK(hipMemset(douth.p, 0xFF, gn * 2));
+        launch_layernorm(dx.as<float>(), dw.as<float>(), b ? db.as<float>() : nullptr, rows, n, out ? dout.as<float>() : nullptr, out_h ? douth.as<__half>() : nullptr, nullptr, sequential_sums != 0);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        if (out) HIP_CHECK(hipMemcpy(out, dout.p, gn * 4, hipMemcpyDeviceToHost));
+        if (out_h) HIP_CHECK(hipMemcpy(out_h, douth.p, gn * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// launch_splitk_reduce_ln: slabs = n_slabs x slab_stride floats (slab z's row r at z * slab_stride + r * n; slab_stride >= rows * n, the caller fills the padding);
+// in_place: ONE device buffer is both `residual` and `x_out` (the ViT blocks' call).  x_out / ln_out [rows + 1][n] fp32, ln_out_h [rows + 1][n] fp16 bits
+int minigpt4_amd_test_splitk_reduce_ln(const float *slabs, int n_slabs, int64_t slab_stride, const float *bias, const float *residual, int in_place, int rows, int n, const float *ln_w,
+                                       const float *ln_b, float *x_out, float *ln_out, unsigned short *ln_out_h) {
+    if (!slabs || n_slabs < 1 || n_slabs > 64 || rows < 1 || rows > VK_MAX_ROWS || n < 1 || n > VK_MAX_N || slab_stride < (int64_t)rows * n || slab_stride > ((int64_t)1 << 28)) return 1;
+    if ((!x_out && !ln_out && !ln_out_h) || (!ln_w && (ln_b || ln_out || ln_out_h)) || (ln_w && !ln_out && !ln_out_h) || (in_place && (!residual || !x_out))) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t rn = (size_t)rows * n, gn = rn + (size_t)n, sn = (size_t)n_slabs * (size_t)slab_stride;
+        DevBuf ds(sn * 4), dbias((size_t)n * 4), dres(rn * 4), dw((size_t)n * 4), db((size_t)n * 4), dx(gn * 4), dln(gn * 4), dlnh(gn * 2);
+        upload_f32(ds, slabs, sn);
+        if (bias) upload_f32(dbias, bias, (size_t)n);
+        if (ln_w) upload_f32(dw, ln_w, (size_t)n);
+        if (ln_b) upload_f32(db, ln_b, (size_t)n);
+        HIP_CHECK(hipMemset(dx.p, 0xFF, gn * 4)); HIP_CHECK(hipMemset(dln.p, 0xFF, gn * 4)); HIP_CHECK(hipMemset(dlnh.p, 0xFF, gn * 2));
+        if (residual) upload_f32(in_place ? dx : dres, residual, rn);
+        const float *res = residual ? (in_place ? dx.as<float>() : dres.as<float>()) : nullptr;
+        launch_splitk_reduce_ln(ds.as<float>(), n_slabs, (size_t)slab_stride, bias ? dbias.as<float>() : nullptr, res, rows, n, x_out ? dx.as<float>() : nullptr, ln_w ? dw.as<float>() : nullptr,
+                                ln_b ? db.as<float>() : nullptr, ln_out ? dln.as<float>() : nullptr, ln_out_h ? dlnh.as<__half>() : nullptr, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        if (x_out) HIP_CHECK(hipMemcpy(x_out, dx.p, gn * 4, hipMemcpyDeviceToHost));
+        if (ln_out) HIP_CHECK(hipMemcpy(ln_out, dln.p, gn * 4, hipMemcpyDeviceToHost));
+        if (ln_out_h) HIP_CHECK(hipMemcpy(ln_out_h, dlnh.p, gn * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// The split-K forms of the fp16 GEMM: raw fp32 partial sums, slab z = A[:, cols of slice z] . W[:, the same]^T.  Operands as test_gemm_impl (fp32 on the host, rounded to fp16
+// on the device).  skinny == 0: slices = gemm_split_slices(K, slices_wanted) as Engine::encode computes it, then launch_gemm_f16_splitk (64x64 tiles, or the ring tiles from
+// 384 rows on); skinny != 0: launch_gemm_f16_skinny_splitk with slices_wanted as given -- 4, nothing launched, when it refuses.  slabs_out: room for slices_wanted slabs
+// [M][N]; the first *slices_used_out are written, and only on success
+int minigpt4_amd_test_gemm_f16_splitk(const float *A, const float *W, int M, int N, int K, int slices_wanted, int skinny, float *slabs_out, int *slices_used_out) {
+    if (!A || !W || !slabs_out || !slices_used_out || M <= 0 || M > VK_MAX_ROWS || N <= 0 || N > VK_MAX_N || K <= 0 || K > VK_MAX_N || K % 16 || slices_wanted < 1 || slices_wanted > 64) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const int slices = skinny ? slices_wanted : gemm_split_slices(K, slices_wanted);
+        const size_t mn = (size_t)M * N, sn = (size_t)slices * mn + (size_t)N;           // + one guard row (never copied back: the descriptors' bounds end at the slab)
+        DevBuf dA((size_t)M * K * 4), dW((size_t)N * K * 4), dAh((size_t)M * K * 2), dWh((size_t)N * K * 2), dS(sn * 4);
+        upload_f32(dA, A, (size_t)M * K); upload_f32(dW, W, (size_t)N * K);
+        HIP_CHECK(hipMemset(dS.p, 0xFF, sn * 4));
+        launch_f32_to_f16(dA.as<float>(), dAh.as<__half>(), (size_t)M * K, nullptr); launch_f32_to_f16(dW.as<float>(), dWh.as<__half>(), (size_t)N * K, nullptr);
+        if (skinny) { if (!launch_gemm_f16_skinny_splitk(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, slices, dS.as<float>(), mn, N, nullptr)) { HIP_CHECK(hipDeviceSynchronize()); set_last_error("launch_gemm_f16_skinny_splitk refused"); return 4; } }
+        else launch_gemm_f16_splitk(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, slices, dS.as<float>(), mn, N, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(slabs_out, dS.p, (size_t)slices * mn * 4, hipMemcpyDeviceToHost));
+        *slices_used_out = slices;
+        return 0;
+    });
+}
+
+// launch_gemm_f16_head_major with N = 3 * D: out = [3 * D floats of guard][3][D / hd][M][hd][3 * D floats of guard], all of it copied back (the launcher's throw for
+// D % hd != 0 arrives as 3)
+int minigpt4_amd_test_gemm_f16_head_major(const float *A, const float *W, const float *bias, int M, int D, int hd, int K, float *out) {
+    if (!A || !W || !out || M <= 0 || M > VK_MAX_ROWS || D <= 0 || 3 * (int64_t)D > VK_MAX_N || hd <= 0 || K <= 0 || K > VK_MAX_N || K % 16) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const int N = 3 * D;
+        const size_t mn = (size_t)M * N, gn = mn + 2 * (size_t)N;
+        DevBuf dA((size_t)M * K * 4), dW((size_t)N * K * 4), dAh((size_t)M * K * 2), dWh((size_t)N * K * 2), dC(gn * 4), db((size_t)N * 4);
+        upload_f32(dA, A, (size_t)M * K); upload_f32(dW, W, (size_t)N * K);
+        if (bias) upload_f32(db, bias, (size_t)N);
+        HIP_CHECK(hipMemset(dC.p, 0xFF, gn * 4));
+        launch_f32_to_f16(dA.as<float>(), dAh.as<__half>(), (size_t)M * K, nullptr); launch_f32_to_f16(dW.as<float>(), dWh.as<__half>(), (size_t)N * K, nullptr);
+        Tables tb;
+        launch_gemm_f16_head_major(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, tb, dC.as<float>() + N, D, hd, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dC.p, gn * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// launch_im2col: image [batch][3][224][224] fp32 -> patches [batch * 256 + 1][ldp] fp16 bits
+int minigpt4_amd_test_im2col(const float *image, int batch, int ldp, unsigned short *patches) {
+    if (!image || !patches || batch < 1 || batch > 16 || ldp < 588 || ldp > 4096) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t ni = (size_t)batch * 3 * 224 * 224, np = ((size_t)batch * 256 + 1) * ldp;
+        DevBuf di(ni * 4), dp(np * 2);
+        upload_f32(di, image, ni);
+        HIP_CHECK(hipMemset(dp.p, 0xFF, np * 2));
+        launch_im2col(di.as<float>(), dp.as<__half>(), ldp, nullptr, batch);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(patches, dp.p, np * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// launch_assemble_embeddings: cls [D], pe [batch * 256][D], pos [257][D] -> x [batch * 257 + 1][D]
+int minigpt4_amd_test_assemble(const float *cls, const float *pe, const float *pos, int batch, int D, float *x) {
+    if (!cls || !pe || !pos || !x || batch < 1 || batch > 16 || D < 1 || D > VK_MAX_N) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t npe = (size_t)batch * 256 * D, npos = (size_t)257 * D, nx = ((size_t)batch * 257 + 1) * D;
+        DevBuf dc((size_t)D * 4), dpe(npe * 4), dpos(npos * 4), dx(nx * 4);
+        upload_f32(dc, cls, (size_t)D); upload_f32(dpe, pe, npe); upload_f32(dpos, pos, npos);
+        HIP_CHECK(hipMemset(dx.p, 0xFF, nx * 4));
+        launch_assemble_embeddings(dc.as<float>(), dpe.as<float>(), dpos.as<float>(), D, dx.as<float>(), nullptr, batch);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(x, dx.p, nx * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// launch_lin_epilogue: y / residual [rows][n], bias [n]; gelu_table (65536 fp16 bit patterns) non-NULL = the GELU step, gathered from it (this launch has no computed arm:
+// the engine always hands it the tables).  out [rows + 1][n] fp32 and / or out_h [rows + 1][n] fp16 bits
+int minigpt4_amd_test_lin_epilogue(const float *y, const float *bias, const float *residual, const unsigned short *gelu_table, int rows, int n, float *out, unsigned short *out_h) {
+    if (!y || (!out && !out_h) || rows < 1 || rows > VK_MAX_ROWS || n < 1 || n > VK_MAX_N) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t rn = (size_t)rows * n, gn = rn + (size_t)n;
+        DevBuf dy(rn * 4), dbias((size_t)n * 4), dres(rn * 4), dtab(65536 * 2), dout(gn * 4), douth(gn * 2);
+        upload_f32(dy, y, rn);
+        if (bias) upload_f32(dbias, bias, (size_t)n);
+        if (residual) upload_f32(dres, residual, rn);
+        Tables tb;
+        if (gelu_table) { HIP_CHECK(hipMemcpy(dtab.p, gelu_table, 131072, hipMemcpyHostToDevice)); tb.gelu = dtab.as<__half>(); }
+        HIP_CHECK(hipMemset(dout.p, 0xFF, gn * 4)); HIP_CHECK(hipMemset(douth.p, 0xFF, gn * 2));
+        launch_lin_epilogue(dy.as<float>(), bias ? dbias.as<float>() : nullptr, residual ? dres.as<float>() : nullptr, gelu_table != nullptr, tb, rows, n, out ? dout.as<float>() : nullptr,
+                            out_h ? douth.as<__half>() : nullptr, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        if (out) HIP_CHECK(hipMemcpy(out, dout.p, gn * 4, hipMemcpyDeviceToHost));
+        if (out_h) HIP_CHECK(hipMemcpy(out_h, douth.p, gn * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
 // Micro-benchmark of the fp16 GEMM of the image path on synthetic operands (tools/timeline_gemm.py): `iters` launches of C[M][N] = A[M][K] . W[N][K]^T, cycling through
 // `n_sets` weight matrices so that the Infinity Cache cannot serve repeats (as in the encoder, where every block has its own weights).  flags: 1 = GELU epilogue,
 // 2 = residual epilogue, 4 = fp16 output as well.  variant 0 = launch_gemm_f16 (the dispatcher: 128x128 tiles from M = 512, 64x64 below), 1 = the skinny-M kernel,

@@ -240,6 +240,17 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_matvec_ex.argtypes = L.minigpt4_amd_test_matvec.argtypes[:-1] + [VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_f16_silu_pair.argtypes = [FLOAT_PTR, VOID_PTR, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_f16_silu_pair_ex.argtypes = [FLOAT_PTR, VOID_PTR, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_layernorm.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, FLOAT_PTR, VOID_PTR]
+        L.minigpt4_amd_test_splitk_reduce_ln.argtypes = [FLOAT_PTR, I32, ctypes.c_int64, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR]
+        L.minigpt4_amd_test_gemm_f16_splitk.argtypes = [FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, FLOAT_PTR, INT_PTR]
+        L.minigpt4_amd_test_gemm_f16_head_major.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, FLOAT_PTR]
+        L.minigpt4_amd_test_im2col.argtypes = [FLOAT_PTR, I32, I32, VOID_PTR]
+        L.minigpt4_amd_test_assemble.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, FLOAT_PTR]
+        L.minigpt4_amd_test_lin_epilogue.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, I32, I32, FLOAT_PTR, VOID_PTR]
+        L.minigpt4_amd_test_set_gemm_arm.argtypes = [I32, I32]
+        L.minigpt4_amd_test_set_gemm_arm.restype = None
+        L.minigpt4_amd_test_set_splitk_xcd.argtypes = [I32]
+        L.minigpt4_amd_test_set_splitk_xcd.restype = None
         L.minigpt4_amd_test_activation.argtypes = [I32, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_test_attn_f32.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, F32, F32, I32, I32, VOID_PTR, FLOAT_PTR, VOID_PTR]
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
@@ -998,6 +1009,104 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_gemm_f16 rc={rc}")
         return C
+
+    # ---- the image encoder's kernels between its GEMMs (include/minigpt4_amd_test.h).  These wrappers RETURN the hook's code first instead of raising (the tests assert the
+    # refusals too); every output array is created filled with HOOK_FILL bytes, so an output the hook did not copy back is recognisable, and keeps the hook's guard row.
+    HOOK_FILL = 0xA5
+
+    @classmethod
+    def _hook_out(cls, shape, dtype) -> np.ndarray:
+        a = np.empty(shape, dtype)
+        a.view(np.uint8).fill(cls.HOOK_FILL)
+        return a
+
+    @staticmethod
+    def _f32p(a: Optional[np.ndarray]):
+        return None if a is None else a.ctypes.data_as(FLOAT_PTR)
+
+    @staticmethod
+    def _vp(a: Optional[np.ndarray]):
+        return None if a is None else a.ctypes.data_as(VOID_PTR)
+
+    @staticmethod
+    def _f32(a, shape=None) -> Optional[np.ndarray]:
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.float32)
+        return a if shape is None else a.reshape(shape)
+
+    def amd_test_layernorm(self, x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray] = None, sequential: bool = False, want_out: bool = True, want_out_h: bool = True):
+        """One launch_layernorm on x [rows][n] -> (rc, out fp32 [rows + 1][n] or None, out_h uint16 [rows + 1][n] or None); the last row is the hook's guard row."""
+        x = self._f32(x)
+        rows, n = x.shape
+        w, b = self._f32(w, (n,)), self._f32(b, (n,))
+        out = self._hook_out((rows + 1, n), np.float32) if want_out else None
+        out_h = self._hook_out((rows + 1, n), np.uint16) if want_out_h else None
+        rc = self.library.minigpt4_amd_test_layernorm(self._f32p(x), self._f32p(w), self._f32p(b), rows, n, int(sequential), self._f32p(out), self._vp(out_h))
+        return rc, out, out_h
+
+    def amd_test_splitk_reduce_ln(self, slabs: np.ndarray, rows: int, n: int, bias: Optional[np.ndarray] = None, residual: Optional[np.ndarray] = None, in_place: bool = False,
+                                  ln_w: Optional[np.ndarray] = None, ln_b: Optional[np.ndarray] = None, want_x: bool = True, want_ln: bool = True, want_ln_h: bool = True):
+        """One launch_splitk_reduce_ln.  slabs [n_slabs][slab_stride] fp32 (slab_stride >= rows * n, padding included) -> (rc, x_out, ln_out, ln_out_h), each [rows + 1][n]
+        (guard row last) or None; without ln_w only x_out is produced."""
+        slabs = self._f32(slabs)
+        n_slabs, stride = slabs.shape
+        bias, residual, ln_w, ln_b = self._f32(bias, (n,)), self._f32(residual, (rows, n)), self._f32(ln_w, (n,)), self._f32(ln_b, (n,))
+        x_out = self._hook_out((rows + 1, n), np.float32) if want_x else None
+        ln_out = self._hook_out((rows + 1, n), np.float32) if want_ln and ln_w is not None else None
+        ln_out_h = self._hook_out((rows + 1, n), np.uint16) if want_ln_h and ln_w is not None else None
+        rc = self.library.minigpt4_amd_test_splitk_reduce_ln(self._f32p(slabs), n_slabs, stride, self._f32p(bias), self._f32p(residual), int(in_place), rows, n, self._f32p(ln_w),
+                                                             self._f32p(ln_b), self._f32p(x_out), self._f32p(ln_out), self._vp(ln_out_h))
+        return rc, x_out, ln_out, ln_out_h
+
+    def amd_test_gemm_f16_splitk(self, A: np.ndarray, W: np.ndarray, slices: int, skinny: bool = False):
+        """The split-K GEMM forms -> (rc, slabs fp32 [slices wanted][M][N], slices used); rc 0: slabs[:used] are the raw partial products, otherwise nothing was written."""
+        A, W = self._f32(A), self._f32(W)
+        (M, K), N = A.shape, W.shape[0]
+        slabs = self._hook_out((max(1, slices), M, N), np.float32)
+        used = ctypes.c_int32(-1)
+        rc = self.library.minigpt4_amd_test_gemm_f16_splitk(self._f32p(A), self._f32p(W), M, N, K, slices, int(skinny), self._f32p(slabs), ctypes.byref(used))
+        return rc, slabs, used.value
+
+    def amd_test_gemm_f16_head_major(self, A: np.ndarray, W: np.ndarray, bias: Optional[np.ndarray], D: int, hd: int):
+        """launch_gemm_f16_head_major, W [3 * D][K] -> (rc, fp32 [(M + 2) * 3 * D]: 3 * D guard floats, [3][D / hd][M][hd], 3 * D guard floats)."""
+        A, W = self._f32(A), self._f32(W)
+        M, K = A.shape
+        assert W.shape == (3 * D, K)
+        bias = self._f32(bias, (3 * D,))
+        out = self._hook_out(((M + 2) * 3 * D,), np.float32)
+        rc = self.library.minigpt4_amd_test_gemm_f16_head_major(self._f32p(A), self._f32p(W), self._f32p(bias), M, D, hd, K, self._f32p(out))
+        return rc, out
+
+    def amd_test_im2col(self, image: np.ndarray, ldp: int = 592):
+        """launch_im2col on image [B][3][224][224] -> (rc, uint16 [B * 256 + 1][ldp] fp16 bit patterns, guard row last)."""
+        image = self._f32(image)
+        B = image.shape[0]
+        assert image.shape == (B, 3, 224, 224)
+        out = self._hook_out((B * 256 + 1, ldp), np.uint16)
+        return self.library.minigpt4_amd_test_im2col(self._f32p(image), B, ldp, self._vp(out)), out
+
+    def amd_test_assemble(self, cls_token: np.ndarray, pe: np.ndarray, pos: np.ndarray):
+        """launch_assemble_embeddings: cls [D], pe [B * 256][D], pos [257][D] -> (rc, fp32 [B * 257 + 1][D], guard row last)."""
+        pe = self._f32(pe)
+        D = pe.shape[1]
+        B = pe.shape[0] // 256
+        assert pe.shape[0] == B * 256
+        cls_token, pos = self._f32(cls_token, (D,)), self._f32(pos, (257, D))
+        out = self._hook_out((B * 257 + 1, D), np.float32)
+        return self.library.minigpt4_amd_test_assemble(self._f32p(cls_token), self._f32p(pe), self._f32p(pos), B, D, self._f32p(out)), out
+
+    def amd_test_lin_epilogue(self, y: np.ndarray, bias: Optional[np.ndarray] = None, residual: Optional[np.ndarray] = None, gelu_table: Optional[np.ndarray] = None,
+                              want_out: bool = True, want_out_h: bool = True):
+        """launch_lin_epilogue on y [rows][n] -> (rc, out fp32 [rows + 1][n] or None, out_h uint16 [rows + 1][n] or None); gelu_table given = with the GELU step."""
+        y = self._f32(y)
+        rows, n = y.shape
+        bias, residual = self._f32(bias, (n,)), self._f32(residual, (rows, n))
+        tab = None if gelu_table is None else self._table_arg(gelu_table)
+        out = self._hook_out((rows + 1, n), np.float32) if want_out else None
+        out_h = self._hook_out((rows + 1, n), np.uint16) if want_out_h else None
+        rc = self.library.minigpt4_amd_test_lin_epilogue(self._f32p(y), self._f32p(bias), self._f32p(residual), self._vp(tab), rows, n, self._f32p(out), self._vp(out_h))
+        return rc, out, out_h
 
     def amd_sample_logits(self, logits: np.ndarray, seed: int, temp=0.8, top_k=40, top_p=0.9, tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0,
                           mirostat_eta=1.0) -> int:
