@@ -166,7 +166,8 @@ MINIGPT4_API int minigpt4_amd_score_batch(struct MiniGPT4Context *ctx, const int
  * indexing; column 0 is score_tokens' greedy / greedy_logprob).  Entry 0 of a conversation without logits: logprob 0, rank -1, ids -1, log-probabilities 0.  logprob_out
  * and the conversation afterwards are bit for bit what minigpt4_amd_score_tokens of the same tokens gives.  All four outputs are required.  The result arrays of the
  * feature are allocated by the first of these calls: plain scoring and plain decoding pay nothing and launch nothing new.
- * Not built: a packed minigpt4_amd_score_batch with alternatives; log-probabilities of tempered or filtered distributions; any use of the selection by the sampler. */
+ * Not built: a packed minigpt4_amd_score_batch with alternatives; log-probabilities of tempered or filtered distributions; any use of the selection by the sampler
+ * (minigpt4_amd_beam_search below is the one consumer of the selection on the device). */
 MINIGPT4_API const char *minigpt4_amd_token_piece(struct MiniGPT4Context *ctx, int32_t id);
 MINIGPT4_API int minigpt4_amd_top_logprobs(struct MiniGPT4Context *ctx, const int32_t *slots, int n_slots, int top_n, const int32_t *targets, int32_t *top_ids_out,
                                            float *top_logprobs_out, float *logprob_out, int32_t *rank_out);
@@ -256,6 +257,41 @@ MINIGPT4_API int minigpt4_amd_conversation_penalties(struct MiniGPT4Context *ctx
 MINIGPT4_API int minigpt4_amd_set_logit_bias(struct MiniGPT4Context *ctx, const int32_t *ids, const float *bias, int n);
 MINIGPT4_API int minigpt4_amd_token_history(struct MiniGPT4Context *ctx, int32_t *out, int cap);
 MINIGPT4_API int minigpt4_amd_penalty_info(struct MiniGPT4Context *ctx, int32_t out[4]);
+
+/* ---- beam search over forked conversations, selected on the device (the "beam search numbers" of MiniGPT-4's demo, llama.cpp's llama_beam_search) ----------------------
+ * Every other generation entry point follows ONE hypothesis per conversation.  This call keeps n_beams of them, each in a conversation of its own, and puts all of them
+ * through ONE weight pass per step (the batched step of minigpt4_amd_eval_batch at n_beams rows -- the same launches, no new mat-vec or attention code).  Between the logits
+ * of one step and the pass of the next there is no host round trip: k_topn_rows lists every beam's best tokens, k_beam_select picks the n_beams best (beam, token) pairs and
+ * writes the next pass's row tokens, k_kv_permute makes beam i continue from its parent's cache rows (any map -- swaps, cycles, all-to-one -- in one launch); the host reads
+ * a 44-word result block per step through pinned memory while the pass runs.
+ * slots: n_beams DISTINCT conversations, 2 <= n_beams <= 8; slots[0] is the SOURCE, the others are scratch.  The source's queued rows are evaluated first (as
+ * minigpt4_amd_get_logits does); it must then have current logits.  Its logits row is saved and its state forked to the other slots.
+ * THE RULE, W = n_beams, C = 2 W, EOS = id 2 ("</s>"), fp32 throughout.  A live beam i carries the cumulative score s[i]; step t (t = 0, 1, ...: t tokens emitted so far)
+ * takes each beam's C best tokens in k_topn_rows' order (logit descending, equal logits by ascending id) with their log-probabilities lp[i][c] (log softmax of the RAW
+ * logits, bit for bit minigpt4_amd_top_logprobs' values).  Candidate (i, c) scores s[i] + lp[i][c] (one add, no fused multiply-add).  The W C candidates are ranked by score
+ * descending; equal scores (float equality: -0 and +0 tie) by ascending beam, then ascending c.  The ranking is walked from the top: an EOS candidate at a rank below W
+ * FINISHES a hypothesis -- tokens = the beam's tokens + EOS, final score = score / powf((float)(t + 1), length_penalty) --, an EOS candidate at rank W or above is skipped,
+ * any other candidate becomes the next live beam, in walk order, until W are filled (a beam lists EOS at most once, so C = 2 W always fills them).  In step 0 only beam 0
+ * is live (the others score -INFINITY and their candidates are ignored): its C best tokens fill all W beams.  The search ENDS after the step that brings the finished list
+ * to at least W hypotheses (the list keeps the W best under the order below and drops the rest), or after max_tokens steps; then the live beams join the list UNFINISHED:
+ * score / powf((float)steps, length_penalty) with the steps that ran (max_tokens, or the room), no EOS appended.  RESULT ORDER: final score descending; equal scores: finished before unfinished, then earlier creation
+ * first (walk order, step after step; the unfinished ones in beam order).  length_penalty 0 compares raw sums, 1 the mean log-probability.
+ * Outputs: *n_out = min(n_best, hypotheses) rows; tokens_out is [n_best][max_tokens + 1] (-1 behind a row's length), lengths_out / scores_out [n_best].  stats = {weight
+ * passes (= steps: the step that ends the search still runs its pass), k_kv_permute launches whose map was not the identity, cache rows moved (rows x conversations that
+ * took another beam's rows; the launch covers only the rows that can differ between the beams: from the last step whose beams all had one parent on), hypotheses finished
+ * by EOS}.
+ * AFTERWARDS slots[0] is bit for bit what it was -- position, logits, greedy token, feed token, token history -- and the other slots stand as
+ * minigpt4_amd_fork_conversation(n_rows = that position) leaves them; continue the chat with minigpt4_amd_eval_tokens(best hypothesis).  Cache rows above the position are
+ * dead, as after minigpt4_amd_verify_draft.  The search needs max_tokens rows of room in every slot: with less, max_tokens is cut to the room; with none the call returns 1
+ * with "beam_search: context full".  It never shifts a context.  Decisions are on raw logits: penalties and logit bias are ignored (as in minigpt4_amd_verify_draft); the
+ * sampler's generator, the mirostat state and the prefix cache are untouched and no token-history entry survives the call.
+ * Parity mode: the same rule and kernels decide; one oracle-order single-row pass per beam and step evaluates (the fall-back of minigpt4_amd_eval_batch).
+ * Returns 0, or 1 with "beam_search: ..." in minigpt4_amd_last_error and nothing changed: no context, a bad slot list, n_beams outside 2 .. 8, n_best outside 1 .. n_beams,
+ * max_tokens < 1, a length_penalty that is not finite, a NULL output, no current logits, n_vocab <= 2 * n_beams.  The buffers of the feature are allocated by the first
+ * call and freed with the context and by minigpt4_amd_set_conversations: a context that never calls it allocates nothing new and launches nothing new.
+ * Not built: sampling or diverse beam search, penalties inside the search, more than 8 beams, a device-resident loop without the per-step read-back. */
+MINIGPT4_API int minigpt4_amd_beam_search(struct MiniGPT4Context *ctx, const int32_t *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int32_t *tokens_out,
+                                          int32_t *lengths_out, float *scores_out, int32_t *n_out, int32_t stats[4]);
 
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */

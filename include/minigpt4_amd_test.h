@@ -117,6 +117,27 @@ MINIGPT4_API int minigpt4_amd_test_logprob_rows(const float *logits, int rows, i
  * 1..64 or above n_vocab, a target >= n_vocab or < -1, a row_index entry outside [0, buf_rows), rows > buf_rows without row_index) */
 MINIGPT4_API int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *row_index, int rows, int top_n, const int32_t *targets,
                                              int32_t *ids_out, float *logprobs_out, int32_t *rank_out, float *target_logprob_out, float *ms_out);
+/* Beam search (minigpt4_amd.h states the rule).  A step's decision is 44 int32 words: parent[8], tok[8], score[8] (fp32 bit patterns), n_live, n_fin, fin_beam[8],
+ * fin_score[8] (raw scores, fp32 bit patterns), two words of padding.  Candidates are [n_beams][2 n_beams], row i = what beam i lists, in k_topn_rows' order.
+ * minigpt4_amd_test_beam_select_host, no GPU: a whole search over GIVEN candidates -- ids / logprobs [n_steps][n_beams][2 n_beams], row (t, i) = what beam i lists in step t --
+ * through the rule's host function and the engine's book-keeping, the source at `position`.  scores0 / live0: the first step's beam scores and live mask (scores0 NULL: the
+ * search's own first step -- beam 0 at score 0, the others dead).  It ends like the engine's search: when the finished list reaches n_beams, or after n_steps.  steps_out (may
+ * be NULL): [steps run][44].  tokens_out [n_best][n_steps + 1] (-1 behind a row's length), lengths_out / scores_out [n_best], *n_out rows, stats[4] as minigpt4_amd_beam_search.
+ * 1 = bad arguments (a NULL pointer other than scores0 / steps_out, n_beams outside 2 .. 8, n_steps < 1, n_best outside 1 .. n_beams, a length_penalty that is not finite, no live
+ * beam, a step that cannot fill n_beams live beams).
+ * minigpt4_amd_test_beam_select: the kernel (launch_beam_select, one launch) on one step's candidates; scores[n_beams] is replaced by the next step's, step_out[44] the result
+ * block, row_tok_out[n_beams] the row tokens it wrote for the weight pass.  1 = bad arguments, 2 = no device, 3 = device error.
+ * minigpt4_amd_test_kv_permute: the beam reordering kernel (launch_kv_permute, one launch) on host fp16 caches k / v = [n_slot][n_layer][n_ctx][n_embd] (uint16 bit patterns,
+ * changed in place): rows [r0, r1) of every layer of the listed conversation slots[i] become what slots[parent[i]] held, i < n.  ms (may be NULL): hipEvent time of the launch.
+ * k == v == NULL: timing only, on device buffers of that shape.  1 = bad arguments (n outside 2 .. 8, a slot out of range or listed twice, a parent outside [0, n), rows outside
+ * the cache, only one of k / v NULL), 2 = no device, 3 = the launcher refused the shape (text in minigpt4_amd_last_error) */
+MINIGPT4_API int minigpt4_amd_test_beam_select_host(int n_beams, int n_steps, const int32_t *ids, const float *logprobs, const float *scores0, uint32_t live0, int eos, int position,
+                                                    float length_penalty, int n_best, int32_t *steps_out, int32_t *tokens_out, int32_t *lengths_out, float *scores_out,
+                                                    int32_t *n_out, int32_t *stats);
+MINIGPT4_API int minigpt4_amd_test_beam_select(int n_beams, const int32_t *ids, const float *logprobs, float *scores, uint32_t live, int eos, int n_vocab, int32_t *step_out,
+                                               int32_t *row_tok_out);
+MINIGPT4_API int minigpt4_amd_test_kv_permute(int n_slot, int n_layer, int n_ctx, int n_embd, const int32_t *slots, int n, const int32_t *parent, int r0, int r1, uint16_t *k,
+                                              uint16_t *v, float *ms);
 /* Penalties and logit bias (minigpt4_amd.h).  A table is [n][4] int32 words per entry: id, count, the bias's fp32 bit pattern, has_bias (0 / 1).
  * minigpt4_amd_test_penalise_host, no GPU: builds the table for `history` (row-aligned ids, -1 = embedding row) and the bias pairs (distinct ids in [0, n_vocab), at most
  * 256) with the engine's builder, applies it to row[n_vocab] in place with the host function, and writes the table to table_out (may be NULL; table_cap entries at

@@ -379,6 +379,12 @@ int minigpt4_amd_decode_lookup(struct MiniGPT4Context *ctx, const int32_t *corpu
     if (!ctx) { set_last_error("decode_lookup: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->decode_lookup(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats); });
 }
+// ---- beam search over forked conversations ------------------------------------------------------------------------------------------------------
+int minigpt4_amd_beam_search(struct MiniGPT4Context *ctx, const int32_t *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int32_t *tokens_out,
+                             int32_t *lengths_out, float *scores_out, int32_t *n_out, int32_t stats[4]) {
+    if (!ctx) { set_last_error("beam_search: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->beam_search(slots, n_beams, max_tokens, length_penalty, n_best, tokens_out, lengths_out, scores_out, n_out, stats); });
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

@@ -1,6 +1,7 @@
 #include "engine.hpp"
 #include "dist.hpp"
 #include "draft.hpp"
+#include "beam_host.hpp"
 #include "quantize.hpp"
 #include "imageio.hpp"
 
@@ -99,6 +100,7 @@ Engine::~Engine() {
     topn_free();
     pen_free();
     spec_free();
+    beam_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -1587,6 +1589,7 @@ int Engine::set_conversations(int n) {
     if (n < 1 || n > MAX_CONVERSATIONS) { set_last_error("conversation count out of range"); return 1; }
     HIP_CHECK(hipStreamSynchronize(stream_));
     release_buffers();
+    beam_free();
     conv_.assign((size_t)n, Conversation{});
     cur_ = 0;
     prefix_empty();
@@ -1660,6 +1663,120 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     }
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
     report();
+    return 0;
+}
+
+// ====================================================================================================================
+// beam search (engine.hpp, beam.hpp)
+// ====================================================================================================================
+void Engine::beam_alloc() {
+    if (beam_d_) return;
+    try {
+        HIP_CHECK(hipMalloc((void **)&beam_d_, BEAM_WORDS * 4)); HIP_CHECK(hipHostMalloc((void **)&beam_h_, BEAM_WORDS * 4, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc((void **)&beam_save_, ((size_t)llm_.n_vocab + 2) * 4));
+        HIP_CHECK(hipEventCreateWithFlags(&beam_ev_, hipEventDisableTiming));
+    } catch (...) { beam_free(); throw; }
+}
+void Engine::beam_free() {
+    if (beam_d_) HIP_IGNORE(hipFree(beam_d_));
+    if (beam_h_) HIP_IGNORE(hipHostFree(beam_h_));
+    if (beam_save_) HIP_IGNORE(hipFree(beam_save_));
+    if (beam_ev_) HIP_IGNORE(hipEventDestroy(beam_ev_));
+    beam_d_ = beam_h_ = nullptr; beam_save_ = nullptr; beam_ev_ = nullptr;
+}
+int Engine::beam_search(const int *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int *tokens_out, int *lengths_out, float *scores_out, int *n_out, int *stats) {
+    auto refuse = [](const std::string &what) { set_last_error("beam_search: " + what); return 1; };
+    const int W = n_beams, V = (int)llm_.n_vocab;
+    if (W < 2 || W > BEAM_MAX) return refuse("n_beams outside 2 .. 8");
+    if (const int bad = check_slots(slots, W)) return refuse(bad == 1 ? "bad slot list" : "conversations must be distinct and in range");
+    if (n_best < 1 || n_best > W) return refuse("n_best outside 1 .. n_beams");
+    if (max_tokens < 1) return refuse("max_tokens must be at least 1");
+    if (!std::isfinite(length_penalty)) return refuse("length_penalty must be finite");
+    if (!tokens_out || !lengths_out || !scores_out || !n_out || !stats) return refuse("tokens_out, lengths_out, scores_out, n_out and stats are required");
+    if (V <= 2 * W) return refuse("the vocabulary must hold more than 2 * n_beams tokens");
+    if (weights_missing()) return refuse(last_error());
+    const int src = slots[0], C = 2 * W, stride_out = max_tokens + 1;
+    Conversation &sv = conv_[(size_t)src];
+    if (sv.pend_tok.empty() && !sv.has_logits) return refuse("the source conversation has no current logits");
+    if (n_ctx_ - sv.n_past < 1) return refuse("context full");
+    const SelectScope restore(this);
+    cur_ = src;
+    if (flush()) return refuse("the source's queued rows could not be evaluated: " + last_error());
+    if (!sv.has_logits) return refuse("the source conversation has no current logits");
+    const int steps_max = std::min(max_tokens, n_ctx_ - sv.n_past), p = sv.n_committed;
+    beam_alloc();
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // h_argmax_ is current; h_bstage_ and beam_h_ feed no earlier copy
+    const int src_greedy = h_argmax_[src];
+    // the source's logits row, greedy and feed token: the passes overwrite them
+    HIP_CHECK(hipMemcpyAsync(beam_save_, logits_ + (size_t)src * V, (size_t)V * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(beam_save_ + V, d_argmax_ + src, 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(beam_save_ + V + 1, d_feed_ + src, 4, hipMemcpyDeviceToDevice, stream_));
+    if (fork(src, slots + 1, W - 1, -1)) return refuse(last_error());
+    // inputs of every step: the listed rows of logits_, no targets, the initial scores (only beam 0 counts in the first step); the pass's rows: conversations and positions
+    KvPermuteSlots ps{};
+    for (int i = 0; i < BEAM_MAX; i++) {
+        beam_h_[i] = i < W ? slots[i] : 0; beam_h_[8 + i] = -1; ps.s[i] = i < W ? slots[i] : 0;
+        reinterpret_cast<float *>(beam_h_)[BEAM_S + i] = i == 0 ? 0.0f : -INFINITY;
+    }
+    HIP_CHECK(hipMemcpyAsync(beam_d_, beam_h_, 16 * 4, hipMemcpyHostToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(beam_d_ + BEAM_S, beam_h_ + BEAM_S, 8 * 4, hipMemcpyHostToDevice, stream_));
+    if (!parity_) {
+        for (int i = 0; i < W; i++) { h_bstage_[i] = 0; h_bstage_[MAX_CONVERSATIONS + i] = slots[i]; h_bstage_[2 * MAX_CONVERSATIONS + i] = p; }
+        HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
+        launch_batch_begin(d_npast_, d_bslot_, d_bpos_, W, stream_);
+    }
+    int *const d_ids = beam_d_ + BEAM_IDS, *const d_rank = beam_d_ + BEAM_RANK;
+    float *const d_lp = reinterpret_cast<float *>(beam_d_ + BEAM_LP), *const d_tlp = reinterpret_cast<float *>(beam_d_ + BEAM_TLP), *const d_s = reinterpret_cast<float *>(beam_d_ + BEAM_S);
+    BeamStep *const d_res = reinterpret_cast<BeamStep *>(beam_d_ + BEAM_RES);
+    const BeamStep &hr = *reinterpret_cast<const BeamStep *>(beam_h_ + BEAM_RES);
+    const size_t seq = layers_.size() * (size_t)n_ctx_ * llm_.n_embd;
+    BeamBook book(W, p, length_penalty);
+    for (int t = 0; t < steps_max && !book.full; t++) {
+        const int pos = p + t;                                               // every listed conversation's position before this step's pass
+        if (!launch_topn_rows(logits_, V, V, W, beam_d_, C, beam_d_ + 8, d_ids, d_lp, d_rank, d_tlp, stream_)) return refuse(last_error());
+        if (!launch_beam_select(d_ids, d_lp, d_s, t == 0 ? 1u : (1u << W) - 1u, W, C, BEAM_EOS, V, d_res, parity_ ? d_rank : d_btok_, stream_)) return refuse(last_error());
+        HIP_CHECK(hipMemcpyAsync(beam_h_ + BEAM_RES, d_res, sizeof(BeamStep), hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipEventRecord(beam_ev_, stream_));
+        launch_kv_permute(kc_, vc_, seq, (int)conv_.size(), ps, W, d_res->parent, (int)layers_.size(), n_ctx_, (int)llm_.n_embd, book.common, pos, stream_);
+        if (!parity_) {
+            if (use_graph_) {
+                hipGraphExec_t &ge = batch_graph_[(size_t)W];
+                if (!ge) capture_graph(ge, [&] { forward_batch(W, stream_); });
+                HIP_CHECK(hipGraphLaunch(ge, stream_));
+            } else forward_batch(W, stream_);
+        }
+        HIP_CHECK(hipEventSynchronize(beam_ev_));                            // the result block; the pass is still running
+        bool sane = hr.n_live == W && hr.n_fin >= 0 && hr.n_fin <= W;         // the block indexes the host's ancestry
+        for (int i = 0; i < W && sane; i++) sane = hr.parent[i] >= 0 && hr.parent[i] < W && hr.tok[i] >= 0 && hr.tok[i] < V && (i >= hr.n_fin || (hr.fin_beam[i] >= 0 && hr.fin_beam[i] < W));
+        if (!sane) throw HipError{hipErrorUnknown, "beam_search: the device reported a step outside the rule", __FILE__, __LINE__};
+        if (parity_) {   // oracle-order arithmetic exists for the single-row pass only: one pass per beam, in slot-list order
+            for (int i = 0; i < W; i++) {
+                Conversation &cv = conv_[(size_t)slots[i]];
+                cur_ = slots[i]; cv.n_committed = pos; cv.n_past = pos; cv.hist.resize((size_t)p);
+                const int id = hr.tok[i];
+                if (eval_chunk(&id, 1, nullptr)) return refuse(last_error());
+            }
+            cur_ = src;
+        }
+        book.step(hr);
+    }
+    book.finish();
+    // the source as it was; the others as fork(n_rows = p) leaves them
+    HIP_CHECK(hipMemcpyAsync(logits_ + (size_t)src * V, beam_save_, (size_t)V * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(d_argmax_ + src, beam_save_ + V, 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(d_feed_ + src, beam_save_ + V + 1, 4, hipMemcpyDeviceToDevice, stream_));
+    for (int i = 0; i < W; i++) {
+        Conversation &cv = conv_[(size_t)slots[i]];
+        cv.n_committed = p; cv.n_past = p; cv.hist.resize((size_t)p);
+        if (i) cv.has_logits = false;
+        launch_set_int(d_npast_ + slots[i], p, stream_);
+        if (logits_host_slot_ == slots[i]) logits_host_slot_ = -1;
+    }
+    HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    h_argmax_[src] = src_greedy;
+    *n_out = book.write(n_best, stride_out, tokens_out, lengths_out, scores_out);
+    for (int i = 0; i < 4; i++) stats[i] = book.stats[i];
     return 0;
 }
 

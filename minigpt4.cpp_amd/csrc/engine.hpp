@@ -186,6 +186,18 @@ public:
     // stats = {verify passes, plain steps, draft tokens sent, draft tokens accepted}
     int decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats);
 
+    // ---- beam search over forked conversations (beam.hpp: the step's rule; minigpt4_amd.h: the whole rule).  slots[0] is the source, the other n_beams - 1 listed
+    // conversations are scratch.  The source's queue is evaluated, its logits row / greedy / feed token saved, its state forked to the others; then every step queues, on one
+    // in-order stream and without a host round trip between them, k_topn_rows (top_n = C = 2 n_beams) over the listed logits_ rows, k_beam_select (the W best (beam, token)
+    // pairs; it writes the row tokens into d_btok_), the copy of its result block to pinned memory, k_kv_permute (beam i continues from beam parent[i]'s cache rows; over
+    // rows [common, position), common = the leading rows known to be equal in all W conversations) and forward_batch at W rows -- the batched step's own pass and graph.  The
+    // host awaits the result block while the pass runs and keeps the token ancestry and the finished list.  Afterwards the source is bit for bit what it was (rows below its
+    // position are never written; its logits row, greedy and feed token are restored) and the others stand as fork(n_rows = that position) leaves them.  Decisions are on
+    // raw logits; sampler, mirostat state, prefix store and every token history are untouched.  Parity mode: the same kernels decide, one oracle-order single-row pass per
+    // beam and step evaluates.  stats = {weight passes, k_kv_permute launches whose map was not the identity, cache rows moved (summed over conversations), hypotheses
+    // finished by EOS}.  tokens_out: [n_best][max_tokens + 1].  1 + last_error "beam_search: ..." and nothing changed on a refusal.  Buffers: first call; freed with the
+    // context and by set_conversations.
+    int beam_search(const int *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int *tokens_out, int *lengths_out, float *scores_out, int *n_out, int *stats);
     // ---- repetition / frequency / presence penalties and a logit bias (penalty.hpp: llama.cpp's arithmetic, one definition for host and device).  Off by default
     // (the reference ignores the arguments); minigpt4_amd.h states the rules.  Every conversation keeps a ROW-ALIGNED token history -- entry r = the token id of cache
     // row r, -1 for an embedding row -- that every path which advances or moves rows keeps in step (invariant: hist.size() == n_committed; the queued rows follow it
@@ -226,6 +238,13 @@ private:
     std::vector<float> pen_row_;                                           // the host path's scratch copy of the row (h_logits_ stays raw)
     void pen_alloc();
     void pen_free();
+    // beam search's own lazy allocation: device words [slots 8 | targets 8 | ids 128 | logprobs 128 | rank 8 | target logprob 8 | scores 8 | BeamStep], its pinned mirror
+    // (staging of the uploads, the landing place of the result block), the saved logits row + greedy / feed token of the source, the event the result block is awaited on
+    int *beam_d_ = nullptr, *beam_h_ = nullptr; float *beam_save_ = nullptr; hipEvent_t beam_ev_ = nullptr;
+    static constexpr int BEAM_IDS = 16, BEAM_LP = BEAM_IDS + BEAM_MAX * BEAM_CAND_MAX, BEAM_RANK = BEAM_LP + BEAM_MAX * BEAM_CAND_MAX, BEAM_TLP = BEAM_RANK + 8, BEAM_S = BEAM_TLP + 8,
+                         BEAM_RES = BEAM_S + 8, BEAM_WORDS = BEAM_RES + (int)(sizeof(BeamStep) / 4);
+    void beam_alloc();
+    void beam_free();
     struct Conversation;
     int pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const;   // the conversation's table for its history as a sample sees it; the flags
     void pen_pick(const int *slots, int n, int *ids);                      // ids[i] <- the penalised pick of every listed conversation whose transformation is not the identity

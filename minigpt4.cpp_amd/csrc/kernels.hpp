@@ -4,6 +4,7 @@
 
 #include "common.hpp"
 #include "penalty.hpp"
+#include "beam.hpp"
 
 namespace mg4 {
 
@@ -138,6 +139,15 @@ void launch_kv_shift(__half *kc_slot, __half *vc_slot, int n_layer, int n_ctx, i
 constexpr int KV_COPY_MAX_DST = 64;                    // = Engine::MAX_CONVERSATIONS
 struct KvCopyDst { __half *k[KV_COPY_MAX_DST]; __half *v[KV_COPY_MAX_DST]; };   // passed by value to the kernel (llm_kernels.hip: why)
 void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, const KvCopyDst &dst, int n_dst, int dst_rows, int n_layer, int E, int n_rows, hipStream_t s);
+// beam reordering (Engine::beam_search): rows [r0, r1) of every layer, keys and values, among W conversations of ONE cache pair (kc / vc = [slot][n_layer][n_ctx][E] fp16,
+// conversation x at kc + x * seq_stride): conversation slots.s[i] receives what conversation slots.s[parent[i]] held, for ANY map parent[0 .. W) -- swaps, cycles,
+// all-to-one -- in one launch; parent is read on the device (k_beam_select's output; an entry outside [0, W) counts as i).  An identity map returns at once; rows outside
+// [r0, r1) and conversations not listed are not touched.  r0 == r1 launches nothing.  Throws HipError: W outside 2 .. KV_PERMUTE_MAX, E % 8, a region that is not 16-byte
+// aligned, r0 < 0, r1 < r0, r1 > n_ctx, a slot outside [0, n_slots), duplicate slots, 2^31 or more 16-byte pieces.
+constexpr int KV_PERMUTE_MAX = 8;                      // = BEAM_MAX
+struct KvPermuteSlots { int s[KV_PERMUTE_MAX]; };      // passed by value to the kernel, as KvCopyDst is
+void launch_kv_permute(__half *kc, __half *vc, size_t seq_stride, int n_slots, const KvPermuteSlots &slots, int W, const int *parent, int n_layer, int n_ctx, int E, int r0, int r1,
+                       hipStream_t s);
 // out[t][h*hd+i] = softmax(K q / sqrt(hd)) V over keys 0..*n_past+t.  caches: [n_ctx][E] fp16.
 // fused (decode, N == 1): q,k,v are the raw projections; RoPE of q/k and the KV append happen inside the kernel.
 // !fused: launch_rope_kv must have run (q rotated in place, caches appended).
@@ -196,6 +206,11 @@ void launch_logprob_rows(const float *logits, int ld, int n_vocab, int rows, con
 constexpr int TOPN_MAX = 64;   // one wavefront of candidates above the threshold; covers the reference's default top-k of 40
 bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const int *row_index, int top_n, const int *targets, int *ids, float *logprobs, int *rank,
                       float *target_logprob, hipStream_t s);
+// one beam-search step's decision (beam.hpp: the rule), one workgroup: ids / logprobs = [W][C] as launch_topn_rows just wrote them (top_n = C), scores[W] the beams'
+// cumulative scores, live bit i = beam i takes part.  Writes *res (the step's parents, tokens, scores and the hypotheses EOS finished), scores[i] = res->score[i] for the
+// next step and row_tok[i] = res->tok[i] -- where the batched step reads its row tokens (an id outside [0, n_vocab) is written as 0: it indexes the embedding matrix).
+// false + last_error: W outside 2 .. BEAM_MAX, C outside 1 .. BEAM_CAND_MAX, no live beam
+bool launch_beam_select(const int *ids, const float *logprobs, float *scores, unsigned live, int W, int C, int eos, int n_vocab, BeamStep *res, int *row_tok, hipStream_t s);
 // penalised greedy pick, one workgroup per entry of `rows` (device; penalty.hpp): picked[r] = the first maximum of logits row rows[r].row (at logits + row * ld, any
 // 4-byte alignment) after the bias / repetition / frequency / presence transformation its table entries table[rows[r].off .. + rows[r].n) describe (distinct ids);
 // the logits are not written.  adjusted (may be null): [table entry] the transformed value.  false + last_error: n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose

@@ -1734,6 +1734,70 @@ void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, cons
 }
 
 // =====================================================================================================================
+// Beam reordering (Engine::beam_search): conversation slots.s[i] receives rows [r0, r0 + n_rows) of conversation slots.s[parent[i]], every layer, keys and values, for ANY
+// map parent -- a swap, a cycle, all-to-one -- in ONE launch, which k_kv_copy (one source, destinations that may not overlap it) cannot express.  Per layer and tensor the
+// rows are one contiguous run of n_rows * E halves, cut into 16-byte pieces as in k_kv_copy; ONE thread owns ONE piece position (tensor, layer, row, column piece) in all W
+// conversations: it loads the W pieces its conversations are to receive -- piece i from conversation parent[i] -- and only then stores them, skipping i where parent[i] == i.
+// No other thread touches any of these 2 W addresses, so no ordering between threads or workgroups is needed whatever the map.  The pointers are not __restrict__ (as in
+// k_kv_copy): the loads cannot sink below the stores.  parent comes from device memory (k_beam_select wrote it in this stream); every lane reads the same W words, so the
+// identity test and the source choice are uniform (scalar), and an identity map ends every workgroup before it touches the caches.  The slot list travels by value in the
+// argument segment (KvPermuteSlots), like KvCopyDst.  The grid follows the piece count.
+// The W pieces are NAMED values (PERM_LOAD / PERM_STORE below, `if constexpr` on W), not an indexed array: k_kv_copy's array ended up in LDS.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage), W = 2 | 3 | 4 | 5 | 6 | 7 | 8: 14 | 18 | 22 | 26 | 30 | 34 | 38 VGPRs (4 per piece), 26 | 30 | 34 | 38 | 38 | 46 | 46 SGPRs,
+// no scratch, no LDS, occupancy 8 waves per SIMD.
+// =====================================================================================================================
+constexpr int KV_PERMUTE_THREADS = 256;
+__device__ __forceinline__ int kv_permute_slot(const KvPermuteSlots &sl, int j) {   // sl.s[j] for a uniform j without indexing the argument struct
+    int v = sl.s[0];
+    v = j == 1 ? sl.s[1] : v; v = j == 2 ? sl.s[2] : v; v = j == 3 ? sl.s[3] : v; v = j == 4 ? sl.s[4] : v; v = j == 5 ? sl.s[5] : v; v = j == 6 ? sl.s[6] : v; v = j == 7 ? sl.s[7] : v;
+    return v;
+}
+template <int W>
+__global__ __launch_bounds__(KV_PERMUTE_THREADS) void k_kv_permute(__half *kc, __half *vc, size_t seq_stride, const KvPermuteSlots slots, const int *parent, unsigned n_layer,
+                                                                  unsigned n_ctx, unsigned E, unsigned r0, unsigned n_rows) {
+    static_assert(W >= 2 && W <= KV_PERMUTE_MAX, "beams per search");
+    int par[W]; bool identity = true;                                      // uniform: W scalar loads (fully unrolled, constant indices: registers)
+#pragma unroll
+    for (int i = 0; i < W; i++) { const int p = parent[i]; par[i] = p < 0 || p >= W ? i : p; identity = identity && par[i] == i; }
+    if (identity) return;
+    const unsigned per = n_rows * (E / 8);                                 // 16-byte pieces of one layer's run
+    const unsigned total = 2u * n_layer * per;                             // < 2^31 (launch_kv_permute)
+    const unsigned idx = blockIdx.x * KV_PERMUTE_THREADS + threadIdx.x;
+    if (idx >= total) return;
+    const unsigned run = idx / per, within = idx - run * per;              // run = tensor * n_layer + layer
+    const bool is_v = run >= n_layer;
+    const unsigned layer = is_v ? run - n_layer : run;
+    __half *const base = (is_v ? vc : kc) + ((size_t)layer * n_ctx + r0) * E + (size_t)within * 8;
+#define PERM_LOAD(I) uint4 v##I = make_uint4(0u, 0u, 0u, 0u); if constexpr (W > I) { if (par[I] != I) v##I = *reinterpret_cast<const uint4 *>(base + (size_t)kv_permute_slot(slots, par[I]) * seq_stride); }
+#define PERM_STORE(I) if constexpr (W > I) { if (par[I] != I) *reinterpret_cast<uint4 *>(base + (size_t)slots.s[I] * seq_stride) = v##I; }
+    PERM_LOAD(0) PERM_LOAD(1) PERM_LOAD(2) PERM_LOAD(3) PERM_LOAD(4) PERM_LOAD(5) PERM_LOAD(6) PERM_LOAD(7)
+    PERM_STORE(0) PERM_STORE(1) PERM_STORE(2) PERM_STORE(3) PERM_STORE(4) PERM_STORE(5) PERM_STORE(6) PERM_STORE(7)
+#undef PERM_LOAD
+#undef PERM_STORE
+}
+void launch_kv_permute(__half *kc, __half *vc, size_t seq_stride, int n_slots, const KvPermuteSlots &slots, int W, const int *parent, int n_layer, int n_ctx, int E, int r0, int r1,
+                       hipStream_t s) {
+    auto bad = [](const char *what) { throw HipError{hipErrorInvalidValue, what, __FILE__, __LINE__}; };
+    if (!kc || !vc || !parent || n_slots < 1 || n_layer < 1 || n_ctx < 1 || E < 8 || E % 8) bad("launch_kv_permute: bad shape");
+    if (W < 2 || W > KV_PERMUTE_MAX || W > n_slots) bad("launch_kv_permute: W outside 2 .. 8");
+    if (r0 < 0 || r1 < r0 || r1 > n_ctx) bad("launch_kv_permute: rows outside the cache");
+    if ((uintptr_t)kc % 16 || (uintptr_t)vc % 16 || seq_stride % 8) bad("launch_kv_permute: a region is not 16-byte aligned");
+    if (seq_stride < (size_t)n_layer * n_ctx * E) bad("launch_kv_permute: conversations overlap");
+    for (int i = 0; i < W; i++) {
+        if (slots.s[i] < 0 || slots.s[i] >= n_slots) bad("launch_kv_permute: slot out of range");
+        for (int j = 0; j < i; j++) if (slots.s[j] == slots.s[i]) bad("launch_kv_permute: duplicate slot");
+    }
+    if (r1 == r0) return;
+    const unsigned long long total = 2ull * n_layer * (unsigned long long)(r1 - r0) * (E / 8);
+    if (total >= (1ull << 31)) bad("launch_kv_permute: bad shape");
+    note_kernel("k_kv_permute<%d>", W);
+    const dim3 grid((unsigned)((total + KV_PERMUTE_THREADS - 1) / KV_PERMUTE_THREADS)), block(KV_PERMUTE_THREADS);
+#define PERM_CASE(W_) case W_: hipLaunchKernelGGL((k_kv_permute<W_>), grid, block, 0, s, kc, vc, seq_stride, slots, parent, (unsigned)n_layer, (unsigned)n_ctx, (unsigned)E, (unsigned)r0, (unsigned)(r1 - r0)); break
+    switch (W) { PERM_CASE(2); PERM_CASE(3); PERM_CASE(4); PERM_CASE(5); PERM_CASE(6); PERM_CASE(7); PERM_CASE(8); }
+#undef PERM_CASE
+}
+
+// =====================================================================================================================
 // Decode attention over the fp16 KV cache: ONE body, attn_llm_body.hpp, included in the kernels k_attn_llm<HD, FUSED, BATCHED> and k_attn_llm_draft<HD> (why included and
 // not called: the head of that file); FUSED, BATCHED and DRAFT are compile-time constants there.
 // One 512-thread workgroup per (head, query row).
@@ -3070,6 +3134,36 @@ bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const 
     if (rows < 1 || n_vocab < 1 || ld < n_vocab || top_n < 1 || top_n > TOPN_MAX || top_n > n_vocab) { set_last_error("launch_topn_rows: shape out of range"); return false; }
     note_kernel("k_topn_rows");
     hipLaunchKernelGGL(k_topn_rows, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, n_vocab, row_index, top_n, targets, ids, logprobs, rank, target_logprob);
+    return true;
+}
+// One beam-search step's decision (Engine::beam_search; beam.hpp holds the rule and its arithmetic, shared with the host), ONE workgroup of BEAM_MAX * BEAM_CAND_MAX = 128
+// threads, one launch per step.  Thread j owns candidate j = beam * C + c of the [W][C] ids / log-probabilities k_topn_rows just wrote: its score is one fp32 add, its rank
+// the number of live candidates that sort before it (beam_rank_of -- the counting placement of k_topn_rows; no sort, no atomics), order[rank] = j.  Thread 0 then walks the
+// ranking (beam_walk) and writes the result block, the next step's scores and the row tokens of the weight pass that follows in the stream -- no host round trip between
+// the logits of step t and the pass of step t + 1; the host reads *res through pinned memory while that pass runs.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 22 VGPRs, 93 SGPRs, no scratch, 1712 bytes of LDS, occupancy 8 waves per SIMD.
+__global__ __launch_bounds__(BEAM_MAX * BEAM_CAND_MAX) void k_beam_select(const int *__restrict__ ids, const float *__restrict__ logprobs, float *scores, unsigned live, int W, int C,
+                                                                         int eos, int n_vocab, BeamStep *__restrict__ res, int *__restrict__ row_tok) {
+    constexpr int N = BEAM_MAX * BEAM_CAND_MAX;
+    __shared__ float cand[N]; __shared__ int cid[N], order[N]; __shared__ BeamStep st;
+    const int j = threadIdx.x, n = W * C;
+    const bool mine = j < n && ((live >> (j / C)) & 1u);
+    order[j] = -1;
+    if (j < n) { cand[j] = beam_score(scores[j / C], logprobs[j]); cid[j] = ids[j]; }
+    __syncthreads();
+    if (mine) order[beam_rank_of(j, cand, W, C, live)] = j;
+    __syncthreads();
+    if (j == 0) beam_walk(order, __popc(live & ((1u << W) - 1u)) * C, cid, cand, W, C, eos, st);
+    __syncthreads();
+    if (j < (int)(sizeof(BeamStep) / 4)) reinterpret_cast<int *>(res)[j] = reinterpret_cast<const int *>(&st)[j];
+    if (j < W) { scores[j] = st.score[j]; const int t = st.tok[j]; row_tok[j] = t >= 0 && t < n_vocab ? t : 0; }
+}
+bool launch_beam_select(const int *ids, const float *logprobs, float *scores, unsigned live, int W, int C, int eos, int n_vocab, BeamStep *res, int *row_tok, hipStream_t s) {
+    if (!ids || !logprobs || !scores || !res || !row_tok || W < 2 || W > BEAM_MAX || C < 1 || C > BEAM_CAND_MAX || n_vocab < 1 || !(live & ((1u << W) - 1u))) {
+        set_last_error("launch_beam_select: shape out of range"); return false;
+    }
+    note_kernel("k_beam_select");
+    hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(BEAM_MAX * BEAM_CAND_MAX), 0, s, ids, logprobs, scores, live, W, C, eos, n_vocab, res, row_tok);
     return true;
 }
 // Penalised greedy pick (Engine::pen_pick), one workgroup of 256 per listed conversation, one launch for all of them.  rows[r] names the logits row, the conversation's

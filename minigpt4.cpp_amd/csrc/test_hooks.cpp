@@ -8,6 +8,7 @@
 #include "api_internal.hpp"
 #include "activations.hpp"
 #include "draft.hpp"
+#include "beam_host.hpp"
 #include "imageio.hpp"
 #include "quantize.hpp"
 #include "minigpt4_amd.h"
@@ -861,6 +862,83 @@ int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, 
         if (ms_out) *ms_out = t;
         HIP_CHECK(hipMemcpy(ids_out, di.p, RN * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(logprobs_out, dp.p, RN * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(rank_out, dr.p, R * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(target_logprob_out, dq.p, R * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+// ---- beam search (beam.hpp, beam_host.hpp) ----
+static bool beam_hook_args_ok(int W, int n_steps, const int32_t *ids, const float *lp) { return W >= 2 && W <= BEAM_MAX && n_steps >= 1 && ids && lp; }
+// The rule on the CPU: n_steps steps whose candidates are GIVEN -- ids / logprobs [n_steps][W][2 W], row (t, i) = what beam i lists in step t, in k_topn_rows' order -- through
+// beam_select_host and the engine's book-keeping (BeamBook) at source position `position`.  scores0 / live0: the first step's beam scores and live mask (NULL: the search's own
+// first step, only beam 0 live).  steps_out (may be NULL): [steps run][44] words, every step's BeamStep.
+int minigpt4_amd_test_beam_select_host(int n_beams, int n_steps, const int32_t *ids, const float *logprobs, const float *scores0, uint32_t live0, int eos, int position,
+                                       float length_penalty, int n_best, int32_t *steps_out, int32_t *tokens_out, int32_t *lengths_out, float *scores_out, int32_t *n_out,
+                                       int32_t *stats) {
+    const int W = n_beams, C = 2 * W;
+    if (!beam_hook_args_ok(W, n_steps, ids, logprobs) || n_best < 1 || n_best > W || !tokens_out || !lengths_out || !scores_out || !n_out || !stats || position < 0) return 1;
+    if (scores0 && !(live0 & ((1u << W) - 1u))) return 1;
+    if (!std::isfinite(length_penalty)) return 1;
+    BeamBook book(W, position, length_penalty);
+    float s[BEAM_MAX];
+    for (int i = 0; i < BEAM_MAX; i++) s[i] = scores0 && i < W ? scores0[i] : (i == 0 ? 0.0f : -INFINITY);
+    for (int t = 0; t < n_steps && !book.full; t++) {
+        BeamStep r;
+        beam_select_host(W, C, s, t == 0 ? (scores0 ? live0 : 1u) : (1u << W) - 1u, ids + (size_t)t * W * C, logprobs + (size_t)t * W * C, eos, r);
+        if (steps_out) memcpy(steps_out + (size_t)t * (sizeof(BeamStep) / 4), &r, sizeof(BeamStep));
+        if (r.n_live != W) return 1;                                          // fewer than W tokens other than EOS among the live candidates: not a step of the search
+        for (int i = 0; i < W; i++) s[i] = r.score[i];
+        book.step(r);
+    }
+    book.finish();
+    *n_out = book.write(n_best, n_steps + 1, tokens_out, lengths_out, scores_out);
+    for (int i = 0; i < 4; i++) stats[i] = book.stats[i];
+    return 0;
+}
+// k_beam_select, one launch: ids / logprobs [W][2 W], scores [W] (updated in place like the device copy), the result block and the row tokens it wrote
+int minigpt4_amd_test_beam_select(int n_beams, const int32_t *ids, const float *logprobs, float *scores, uint32_t live, int eos, int n_vocab, int32_t *step_out, int32_t *row_tok_out) {
+    const int W = n_beams, C = 2 * W;
+    if (!beam_hook_args_ok(W, 1, ids, logprobs) || !scores || !step_out || !row_tok_out || n_vocab < 1 || !(live & ((1u << W) - 1u))) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)W * C;
+        DevBuf di(n * 4), dl(n * 4), ds(BEAM_MAX * 4), dr(sizeof(BeamStep)), dt(BEAM_MAX * 4);
+        HIP_CHECK(hipMemcpy(di.p, ids, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dl.p, logprobs, n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(ds.p, scores, (size_t)W * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dr.p, 0xFF, sizeof(BeamStep))); HIP_CHECK(hipMemset(dt.p, 0xFF, BEAM_MAX * 4));
+        if (!launch_beam_select(di.as<int>(), dl.as<float>(), ds.as<float>(), live, W, C, eos, n_vocab, static_cast<BeamStep *>(dr.p), dt.as<int>(), nullptr)) return 3;
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(step_out, dr.p, sizeof(BeamStep), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(row_tok_out, dt.p, (size_t)W * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(scores, ds.p, (size_t)W * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+// k_kv_permute on host caches k / v = [n_slot][n_layer][n_ctx][n_embd] fp16 (changed in place): listed slot i receives rows [r0, r1) of listed slot parent[i].
+// k == v == NULL: timing only, on device buffers of that shape
+int minigpt4_amd_test_kv_permute(int n_slot, int n_layer, int n_ctx, int n_embd, const int32_t *slots, int n, const int32_t *parent, int r0, int r1, uint16_t *k, uint16_t *v,
+                                 float *ms) {
+    if (!k != !v || !slots || !parent || n_slot < 1 || n_layer < 1 || n_ctx < 1 || n_embd < 1 || n < 2 || n > KV_PERMUTE_MAX || n > n_slot) return 1;
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= n_slot || parent[i] < 0 || parent[i] >= n) return 1;
+        for (int j = 0; j < i; j++) if (slots[j] == slots[i]) return 1;
+    }
+    if (r0 < 0 || r1 < r0 || r1 > n_ctx) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t slot_n = (size_t)n_layer * n_ctx * n_embd, total = (size_t)n_slot * slot_n;
+        DevBuf dk(total * 2), dv(total * 2), dp(KV_PERMUTE_MAX * 4);
+        if (k) { HIP_CHECK(hipMemcpy(dk.p, k, total * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, total * 2, hipMemcpyHostToDevice)); }
+        else { HIP_CHECK(hipMemset(dk.p, 0x11, total * 2)); HIP_CHECK(hipMemset(dv.p, 0x22, total * 2)); }
+        HIP_CHECK(hipMemcpy(dp.p, parent, (size_t)n * 4, hipMemcpyHostToDevice));
+        KvPermuteSlots ps{};
+        for (int i = 0; i < n; i++) ps.s[i] = slots[i];
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        launch_kv_permute(dk.as<__half>(), dv.as<__half>(), slot_n, n_slot, ps, n, dp.as<int>(), n_layer, n_ctx, n_embd, r0, r1, nullptr);
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms) *ms = t;
+        if (k) { HIP_CHECK(hipMemcpy(k, dk.p, total * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, total * 2, hipMemcpyDeviceToHost)); }
         return 0;
     });
 }

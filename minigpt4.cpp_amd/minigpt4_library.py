@@ -221,6 +221,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_set_logit_bias.argtypes = [VOID_PTR, INT_PTR, FLOAT_PTR, I32]
         L.minigpt4_amd_token_history.argtypes = [VOID_PTR, INT_PTR, I32]
         L.minigpt4_amd_penalty_info.argtypes = [VOID_PTR, INT_PTR]
+        L.minigpt4_amd_beam_search.argtypes = [VOID_PTR, INT_PTR, I32, I32, F32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -258,6 +259,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_penalise_host.argtypes = [FLOAT_PTR, I32, INT_PTR, I32, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, INT_PTR, I32, INT_PTR]
+        L.minigpt4_amd_test_beam_select_host.argtypes = [I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, ctypes.c_uint32, I32, I32, F32, I32, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_test_beam_select.argtypes = [I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, ctypes.c_uint32, I32, I32, INT_PTR, INT_PTR]
+        L.minigpt4_amd_test_kv_permute.argtypes = [I32, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_pen_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
@@ -516,6 +520,90 @@ class MiniGPT4SharedLibrary:
                                                    out.ctypes.data_as(INT_PTR), n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR)):
             raise RuntimeError("decode_lookup failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return dict(tokens=out[:int(n[0])].copy(), passes=int(st[0]), steps=int(st[1]), sent=int(st[2]), accepted=int(st[3]))
+
+    # ---- beam search (include/minigpt4_amd.h)
+    def amd_beam_search(self, ctx, slots: Sequence[int], max_tokens: int, length_penalty: float = 1.0, n_best: Optional[int] = None, with_stats: bool = False):
+        """Beam search with len(slots) beams: slots[0] is the source conversation (left exactly as it was), the others are scratch.  Returns the hypotheses, best first, as a
+        list of (ids i32 array, score); a finished hypothesis ends in id 2.  with_stats: (that list, dict(passes, permutes, rows_moved, finished)).  Continue the chat with
+        amd_eval_tokens(ctx, best ids).  include/minigpt4_amd.h states the rule."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        W = len(sl)
+        nb = W if n_best is None else int(n_best)
+        if W < 2 or W > 8:
+            raise ValueError("beam_search: 2 .. 8 beams (slots)")
+        if nb < 1 or nb > W:
+            raise ValueError("beam_search: n_best outside 1 .. len(slots)")
+        if int(max_tokens) < 1:
+            raise ValueError("beam_search: max_tokens must be at least 1")
+        if not np.isfinite(length_penalty):
+            raise ValueError("beam_search: length_penalty must be finite")
+        stride = int(max_tokens) + 1
+        tok, ln, sc = np.full((nb, stride), -1, np.int32), np.zeros(nb, np.int32), np.zeros(nb, np.float32)
+        n, st = np.zeros(1, np.int32), np.zeros(4, np.int32)
+        if self.library.minigpt4_amd_beam_search(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), W, int(max_tokens), float(length_penalty), nb,
+                                                 tok.ctypes.data_as(INT_PTR), ln.ctypes.data_as(INT_PTR), sc.ctypes.data_as(FLOAT_PTR), n.ctypes.data_as(INT_PTR),
+                                                 st.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("beam_search failed: " + self._err())
+        hyps = [(tok[i, :int(ln[i])].copy(), float(sc[i])) for i in range(int(n[0]))]
+        if with_stats:
+            return hyps, dict(passes=int(st[0]), permutes=int(st[1]), rows_moved=int(st[2]), finished=int(st[3]))
+        return hyps
+
+    def amd_test_beam_select_host(self, ids: np.ndarray, logprobs: np.ndarray, length_penalty: float = 1.0, n_best: Optional[int] = None, position: int = 0,
+                                  scores0: Optional[Sequence[float]] = None, live0: int = 0, eos: int = 2) -> dict:
+        """The search rule on the CPU over GIVEN candidates ids / logprobs [n_steps][W][2 W] (include/minigpt4_amd_test.h).  dict(steps [steps run][44] i32 words,
+        hyps [(ids, score f32)], stats [4])."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        lp = np.ascontiguousarray(logprobs, np.float32)
+        T, W, C = ids.shape
+        if lp.shape != ids.shape or C != 2 * W:
+            raise ValueError("test_beam_select_host: ids / logprobs must both be [n_steps][W][2 W]")
+        nb = W if n_best is None else int(n_best)
+        steps = np.zeros((T, 44), np.int32)
+        tok, ln, sc = np.full((max(nb, 1), T + 1), -1, np.int32), np.zeros(max(nb, 1), np.int32), np.zeros(max(nb, 1), np.float32)
+        n, st = np.zeros(1, np.int32), np.zeros(4, np.int32)
+        s0 = None if scores0 is None else np.ascontiguousarray(scores0, np.float32)
+        rc = self.library.minigpt4_amd_test_beam_select_host(W, T, ids.ctypes.data_as(INT_PTR), lp.ctypes.data_as(FLOAT_PTR), None if s0 is None else s0.ctypes.data_as(FLOAT_PTR),
+                                                             int(live0), int(eos), int(position), float(length_penalty), nb, steps.ctypes.data_as(INT_PTR),
+                                                             tok.ctypes.data_as(INT_PTR), ln.ctypes.data_as(INT_PTR), sc.ctypes.data_as(FLOAT_PTR), n.ctypes.data_as(INT_PTR),
+                                                             st.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError(f"test_beam_select_host rc={rc}")
+        return dict(steps=steps[:int(st[0])].copy(), hyps=[(tok[i, :int(ln[i])].copy(), np.float32(sc[i])) for i in range(int(n[0]))], stats=st)
+
+    def amd_test_beam_select(self, ids: np.ndarray, logprobs: np.ndarray, scores: Sequence[float], live: int, n_vocab: int, eos: int = 2) -> dict:
+        """k_beam_select on one step's candidates ids / logprobs [W][2 W]: dict(step [44] i32 words, row_tok [W], scores [W] f32: the next step's)."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        lp = np.ascontiguousarray(logprobs, np.float32)
+        W = ids.shape[0]
+        s = np.ascontiguousarray(scores, np.float32).copy()
+        step, rt = np.zeros(44, np.int32), np.zeros(W, np.int32)
+        rc = self.library.minigpt4_amd_test_beam_select(W, ids.ctypes.data_as(INT_PTR), lp.ctypes.data_as(FLOAT_PTR), s.ctypes.data_as(FLOAT_PTR), int(live), int(eos), int(n_vocab),
+                                                        step.ctypes.data_as(INT_PTR), rt.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError(f"test_beam_select rc={rc}: " + self._err())
+        return dict(step=step, row_tok=rt, scores=s)
+
+    def amd_test_kv_permute(self, k: np.ndarray, v: np.ndarray, slots: Sequence[int], parent: Sequence[int], r0: int, r1: int):
+        """k_kv_permute on fp16 caches k / v = [n_slot][n_layer][n_ctx][n_embd] (uint16 bit patterns): returns the caches after listed slot i took rows [r0, r1) of listed
+        slot parent[i]."""
+        k, v = np.ascontiguousarray(k, np.uint16).copy(), np.ascontiguousarray(v, np.uint16).copy()
+        sl, pa = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(parent, np.int32)
+        rc = self.library.minigpt4_amd_test_kv_permute(k.shape[0], k.shape[1], k.shape[2], k.shape[3], sl.ctypes.data_as(INT_PTR), len(sl), pa.ctypes.data_as(INT_PTR), int(r0),
+                                                       int(r1), k.ctypes.data_as(VOID_PTR), v.ctypes.data_as(VOID_PTR), None)
+        if rc:
+            raise RuntimeError(f"test_kv_permute rc={rc}: " + self._err())
+        return k, v
+
+    def amd_test_kv_permute_ms(self, n_slot: int, n_layer: int, n_ctx: int, n_embd: int, slots: Sequence[int], parent: Sequence[int], r0: int, r1: int) -> float:
+        """hipEvent time of one k_kv_permute launch on device caches of that shape."""
+        sl, pa = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(parent, np.int32)
+        ms = ctypes.c_float(0)
+        rc = self.library.minigpt4_amd_test_kv_permute(n_slot, n_layer, n_ctx, n_embd, sl.ctypes.data_as(INT_PTR), len(sl), pa.ctypes.data_as(INT_PTR), int(r0), int(r1), None, None,
+                                                       ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_permute rc={rc}: " + self._err())
+        return float(ms.value)
 
     # ---- repetition / frequency / presence penalties, logit bias (include/minigpt4_amd.h)
     def _err(self) -> str:

@@ -68,20 +68,29 @@ class ReplicaServer:
 
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
             batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
-            frequency_penalty: float = 0.0, logit_bias=None) -> List[str]:
-        """repeat_penalty / repeat_last_n / presence_penalty / frequency_penalty / logit_bias ({id: bias} or (id, bias) pairs): llama.cpp's penalties and a logit
+            frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0) -> List[str]:
+        """num_beams > 1: beam search (`minigpt4_amd_beam_search`) instead of the decode loop -- every request takes num_beams conversations (its own and num_beams - 1 of
+        scratch), so a wave holds conversations // num_beams requests; the answer is the best hypothesis (final score = sum of log-probabilities / length ** length_penalty),
+        cut by the same "###" rule.  The search decides on raw logits: temp / top_k / top_p, penalties and logit bias do not enter it; logprobs is not available with it.
+        num_beams = 1 (the default) is exactly the decode loop below.
+        repeat_penalty / repeat_last_n / presence_penalty / frequency_penalty / logit_bias ({id: bias} or (id, bias) pairs): llama.cpp's penalties and a logit
         bias for every request of the call (include/minigpt4_amd.h), applied per conversation before the decode loop and taken back when the call returns.  The
         defaults are neutral: the call then touches none of it.
         logprobs > 0: the decode loop uses `minigpt4_amd_end_chat_batch_top` (same pieces, same sampler draws) and `self.last_logprobs[i]` holds, per generated
         token of request i (swallowed "##" pieces included), dict(id, piece, logprob, rank, top=[(piece, logprob), ...]) with `logprobs` alternatives -- the
         log-probabilities of the raw logits, whatever temp / top_k / top_p.  The return value is the same."""
         lib, ctx = self.lib, self.ctx
+        if num_beams < 1 or num_beams > 8 or num_beams > self.conversations:
+            raise ValueError("num_beams must be 1 .. min(8, conversations)")
+        if num_beams > 1 and logprobs > 0:
+            raise ValueError("logprobs is not available with num_beams > 1")
         answers: List[str] = [""] * len(requests)
         penalised = repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
         mode_before = lib.amd_penalty_info(ctx)["mode"] if penalised else 0
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
-                             dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty))
+                             dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
+                             num_beams, length_penalty)
         finally:
             if penalised or logit_bias:
                 for slot in range(self.conversations):
@@ -92,13 +101,36 @@ class ReplicaServer:
             if penalised:
                 lib.amd_set_penalties(ctx, bool(mode_before))
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen) -> List[str]:
+    def _beam_answer(self, slots, max_tokens, length_penalty, ignore_eos) -> str:
+        """The best hypothesis of a beam search from conversation slots[0], as the decode loop would have shown its pieces."""
+        lib, ctx = self.lib, self.ctx
+        if max_tokens <= 0:
+            return ""
+        ids, _ = lib.amd_beam_search(ctx, slots, max_tokens, length_penalty, n_best=1)[0]
+        text = shown = ""
+        for t in ids:
+            if int(t) == 2:                                       # the hypothesis finished: </s> is not part of the answer
+                break
+            piece = lib.amd_token_piece(ctx, int(t))
+            text += piece
+            if ignore_eos:
+                shown += piece
+            elif lib.minigpt4_contains_eos_token(piece):
+                pass
+            elif lib.minigpt4_is_eos(text):
+                break
+            else:
+                shown += piece
+        return shown
+
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         if penalised:
             lib.amd_set_penalties(ctx, True)
         self.last_logprobs = [[] for _ in requests] if logprobs > 0 else None
-        for wave in plan_waves(len(requests), self.conversations):
+        per = num_beams                                           # conversations per request: its own, then the search's scratch
+        for wave in plan_waves(len(requests), self.conversations // per):
             structs, owned = [], []
             for i in wave:
                 st, own = self._to_struct(requests[i].image)
@@ -108,17 +140,22 @@ class ReplicaServer:
             batch, embs = ML.MiniGPT4Images(arr, len(wave)), ML.MiniGPT4Embeddings()
             lib.panic_if_error(lib.library.minigpt4_amd_encode_images(ctx.ptr, ctypes.byref(batch), ctypes.byref(embs), 0))
             try:
-                for slot, i in enumerate(wave):
+                for j, i in enumerate(wave):
+                    slot = j * per
                     lib.amd_select_conversation(ctx, slot)
                     lib.minigpt4_reset_chat(ctx)
                     lib.minigpt4_system_prompt(ctx)
-                    lib.minigpt4_begin_chat_image(ctx, embs.embeddings[slot], requests[i].prompt)
+                    lib.minigpt4_begin_chat_image(ctx, embs.embeddings[j], requests[i].prompt)
                     if penalised:
                         lib.amd_conversation_penalties(ctx, slot, **pen)
                     if logit_bias:
                         lib.amd_set_logit_bias(ctx, logit_bias)
                 if batched_prefill:                           # the wave's prompts in one pass per chunk instead of one pass per conversation
-                    lib.amd_prefill_batch(ctx, list(range(len(wave))))
+                    lib.amd_prefill_batch(ctx, [j * per for j in range(len(wave))])
+                if per > 1:
+                    for j, i in enumerate(wave):
+                        answers[i] = self._beam_answer(list(range(j * per, (j + 1) * per)), requests[i].max_tokens, length_penalty, ignore_eos)
+                    continue
                 text = {slot: "" for slot in range(len(wave))}
                 shown = {slot: "" for slot in range(len(wave))}
                 left = {slot: requests[i].max_tokens for slot, i in enumerate(wave)}
@@ -170,7 +207,8 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
                            **{k: v for k, v in kw.items() if k in ("n_ctx", "n_batch", "seed", "library", "verbosity", "prefix_cache")})
     try:
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
-                                                                                                "presence_penalty", "frequency_penalty", "logit_bias")})
+                                                                                                "presence_penalty", "frequency_penalty", "logit_bias", "num_beams",
+                                                                                                "length_penalty")})
     finally:
         server.close()
     mapping = dict(zip(mine, out))
