@@ -206,6 +206,15 @@ MINIGPT4_API float minigpt4_amd_probe_valu(int op, int waves_per_simd, int iters
  * 32 / 64 / 128, n_head < 1, slot outside [0, n_slot), R outside 1 .. 8, n_past < 0, n_past + R > n_ctx, n_ctx above the kernel's LDS rows), 2 = no device, 3 = HIP error */
 MINIGPT4_API int minigpt4_amd_test_attn_draft(int mode, int n_head, int hd, int n_ctx, int n_slot, int slot, int n_past, int R, int computed_exp, const float *q, const float *k,
                                               const float *v, uint16_t *kc, uint16_t *vc, float *out);
+/* One launch of the decode attention body with `vs` workgroups per (head, row), each computing hd / vs of the head's output dims (csrc/llm_kernels.hip: VS; vs 1 is the
+ * plain launch).  form 0: the one-row fused kernel (rows = 1, n_slot = 1, position n_past[0]); 1: the batched kernel, row r belongs to conversation row_slot[r] (all
+ * different) at position n_past[row_slot[r]]; 2: the verify kernel, `rows` rows of conversation row_slot[0] at positions n_past[row_slot[0]] + r.  q, k, v [rows][n_head * hd]
+ * fp32 raw projections; kc, vc [n_slot][n_ctx][n_head * hd] fp16 bit patterns, changed in place; row_slot [rows], n_past [n_slot]; computed_exp as above.
+ * out [rows][n_head * hd].  1 = refused before any device is touched (a NULL array, form not 0 .. 2, hd not 32 / 64 / 128, vs not 1 / 2 / 4, n_head < 1, a slot outside
+ * [0, n_slot) or used twice, rows outside 1 .. 8 for form 2 or not 1 for form 0, a position that leaves the cache, n_ctx above the kernel's LDS rows), 2 = no device,
+ * 3 = HIP error */
+MINIGPT4_API int minigpt4_amd_test_attn_vsplit(int form, int vs, int n_head, int hd, int n_ctx, int n_slot, int rows, const int32_t *row_slot, const int32_t *n_past,
+                                               int computed_exp, const float *q, const float *k, const float *v, uint16_t *kc, uint16_t *vc, float *out);
 
 /* ---- host-only logic (no GPU needed) -------------------------------------------------------------------------------- */
 /* the n-gram drafter of minigpt4_amd_decode_lookup alone (csrc/draft.cpp): the draft for a history of n tokens, at most n_draft tokens into out; returns its length

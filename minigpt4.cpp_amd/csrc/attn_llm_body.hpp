@@ -1,15 +1,21 @@
-// NOT a header: the statements of the decode attention body, included INSIDE the two kernels k_attn_llm<HD, FUSED, BATCHED> and k_attn_llm_draft<HD> of llm_kernels.hip
-// (description, forms and the list of DRAFT's lines: there, above the kernels).  In scope at the point of inclusion: the kernels' parameters (q, kin, vin, kc, vc, E,
-// n_past, n_ctx, cos_tab, sin_tab, tb, out, row_slot, seq_stride) and the constants HD, FUSED, BATCHED, DRAFT.
+// NOT a header: the statements of the decode attention body, included INSIDE the two kernels k_attn_llm<HD, FUSED, BATCHED, VS> and k_attn_llm_draft<HD, VS> of
+// llm_kernels.hip (description, forms, the list of DRAFT's lines and of VS's: there, above the kernels).  In scope at the point of inclusion: the kernels' parameters (q,
+// kin, vin, kc, vc, E, n_past, n_ctx, cos_tab, sin_tab, tb, out, row_slot, seq_stride) and the constants HD, FUSED, BATCHED, DRAFT, VS.
 // Why text and not a function template: with the body behind a __device__ function (forceinline or not; __restrict__ or plain parameters; Tables by value, by reference
 // or only its exp pointer; indices and position read in the kernel and passed in) hipcc allocates the six fused k_attn_llm one VGPR and 1 ... 9 instructions differently
 // from the ISA that was validated and measured -- the optimised IR then differs in one eliminated smin and in inbounds flags of the last reduction; why, not known.
-// Included, all twelve instantiations are instruction for instruction what they were (tools/isa_diff.py).
+// Included, all twelve instantiations are instruction for instruction what they were (tools/isa_diff.py) -- and stayed so as the VS = 1 forms when VS was added
+// (every VS line below is a compile-time `VS == 1 ? the former expression : ...`; tools/isa_diff.py --rename maps the old symbols onto <..., VS = 1>).
     static_assert((FUSED || !BATCHED) && (BATCHED || !DRAFT), "BATCHED implies FUSED, DRAFT implies BATCHED");
+    static_assert(VS == 1 || (FUSED && (VS == 2 || VS == 4) && (HD / 8) % VS == 0), "the value-column split: fused forms, 2 or 4 workgroups per (head, row)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int CH = HD / 8, P = AT_THREADS / CH, RM = DRAFT ? DRAFT_ROWS : 1;
     static_assert(!DRAFT || (RM <= P && RM * (HD / 2) <= AT_THREADS), "one prologue thread per (row, rotated pair); at most one LDS key per partition");
     const int h = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    // VS > 1: workgroup blockIdx.z of the VS that share this (head, row) -- all of them do everything up to ph[], then each its own HD / VS output dims.  Its P.V threads are
+    // the first AT_THREADS / VS (whole waves): chunk cv of the workgroup's CH / VS, partition pv of the same P.  VS == 1: (cv, pv) = (c, p), every thread.
+    constexpr int CHV = (HD / 8) / VS;
+    const bool vact = VS == 1 || tid < AT_THREADS / VS;
     int pos_, p0_ = 0;
     if (BATCHED) {
         const int slot = row_slot[DRAFT ? 0 : t];
@@ -41,7 +47,7 @@
                 if (r == t) {
                     st_h2(qh + 2 * i, rope_rot_h2(q[qo + 2 * i], q[qo + 2 * i + 1], c, s));
                     const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
-                    st_h2(kc + co, kr); st_h2(vc + co, vr);
+                    if (VS == 1 || blockIdx.z == 0) { st_h2(kc + co, kr); st_h2(vc + co, vr); }
                 }
             }
         } else if (tid < HD / 2) {                                // one thread per rotated pair of the row
@@ -51,7 +57,7 @@
             const __half2 vr = __floats2half2_rn(vin[qo + 2 * i], vin[qo + 2 * i + 1]);
             st_h2(qh + 2 * i, qr); st_h2(knew + 2 * i, kr); st_h2(vnew + 2 * i, vr);
             const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
-            st_h2(kc + co, kr); st_h2(vc + co, vr);
+            if (VS == 1 || blockIdx.z == 0) { st_h2(kc + co, kr); st_h2(vc + co, vr); }   // the append: one workgroup of the VS (the others read rows below pos only)
         }
     } else {
         for (int i = tid; i < HD; i += AT_THREADS) qh[i] = f2h_rn(q[qo + i]);
@@ -81,22 +87,25 @@
     // 8-dim partial dots are added across the 16 lanes with DPP.  Key and value rows of the same (lane, round) sit at the same offset of the two caches, and neither
     // depends on this step's scores: both are requested here, NPRE rounds deep, so they arrive during the dot products / the softmax.
     const int c = tid % CH, p = tid / CH;
-    const __half *kb = kc + (size_t)h * HD + 8 * c, *vb = vc + (size_t)h * HD + 8 * c;
+    const int cv = VS == 1 ? c : (int)blockIdx.z * CHV + tid % CHV, pv = VS == 1 ? p : tid / CHV;
+    const __half *kb = kc + (size_t)h * HD + 8 * c, *vb = vc + (size_t)h * HD + 8 * cv;
     constexpr int NPRE = 16;                        // x P = 32 key partitions: contexts up to 512 need no second round trip
     // loads are clamped to the last row the cache is read at: never a branch, never outside the cache.  DRAFT: rows from p0 on are written by this launch
     const int gmax = DRAFT ? max(p0 - 1, 0) : 0;                  // DRAFT: the last row the cache is read at
     int4 kpre[NPRE], vpre[NPRE];
 #pragma unroll
     for (int i = 0; i < NPRE; i++) kpre[i] = ld16(kb + (size_t)min(p + i * P, DRAFT ? gmax : max(Tg - 1, 0)) * E);
+    if (vact) {
 #pragma unroll
-    for (int i = 0; i < NPRE; i++) vpre[i] = ld16(vb + (size_t)min(p + i * P, DRAFT ? gmax : max(Tg - 1, 0)) * E);
+        for (int i = 0; i < NPRE; i++) vpre[i] = ld16(vb + (size_t)min(pv + i * P, DRAFT ? gmax : max(Tg - 1, 0)) * E);
+    }
     // DRAFT: this partition's key among the pass's earlier rows, if any: row rl at position jl (jl mod P == p)
-    int jl = -1;
+    int jl = -1, jlv = -1;                                        // jlv: the same for the P.V roles (VS == 1: jl)
     int4 kl = make_int4(0, 0, 0, 0), vl = kl;
     if (DRAFT) {
-        const int rl = (p - p0) & (P - 1);
-        jl = rl < t ? p0 + rl : -1;
-        kl = *reinterpret_cast<const int4 *>(knew + min(rl, RM - 1) * HD + 8 * c); vl = *reinterpret_cast<const int4 *>(vnew + min(rl, RM - 1) * HD + 8 * c);
+        const int rl = (p - p0) & (P - 1), rlv = (pv - p0) & (P - 1);
+        jl = rl < t ? p0 + rl : -1; jlv = rlv < t ? p0 + rlv : -1;
+        kl = *reinterpret_cast<const int4 *>(knew + min(rl, RM - 1) * HD + 8 * c); vl = *reinterpret_cast<const int4 *>(vnew + min(rlv, RM - 1) * HD + 8 * cv);
     }
     float qd[8];
     unpack8(*reinterpret_cast<const int4 *>(qh + 8 * c), qd);
@@ -132,24 +141,27 @@
     // pv_acc goes through this lambda, as the kernels always had one here: with the helper called directly from the loops hipcc schedules all twelve k_attn_llm /
     // k_attn_llm_draft instantiations differently (3 ... 5 instructions more, same registers; cause not known) -- they would no longer be the validated ISA.
     auto pv_key = [&](const int4 &vv, const int j) { pv_acc(o, vv, __half2float(ph[j])); };
+    if (vact) {                                                   // VS > 1: the other waves skip (wave-uniform; no barrier inside)
 #pragma unroll
-    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; if (j < Tg) pv_key(DRAFT && j == jl ? vl : vpre[i], j); }
-    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {
-        int4 vv[8];
+        for (int i = 0; i < NPRE; i++) { const int j = pv + i * P; if (j < Tg) pv_key(DRAFT && j == jlv ? vl : vpre[i], j); }
+        for (int j0 = pv + NPRE * P; j0 < Tg; j0 += 8 * P) {
+            int4 vv[8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) vv[i] = ld16(vb + (size_t)min(j0 + i * P, DRAFT ? gmax : Tg - 1) * E);
+            for (int i = 0; i < 8; i++) vv[i] = ld16(vb + (size_t)min(j0 + i * P, DRAFT ? gmax : Tg - 1) * E);
 #pragma unroll
-        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; if (j < Tg) pv_key(DRAFT && j == jl ? vl : vv[i], j); }
+            for (int i = 0; i < 8; i++) { const int j = j0 + i * P; if (j < Tg) pv_key(DRAFT && j == jlv ? vl : vv[i], j); }
+        }
+        if (FUSED && pv == P - 1) {
+            const float pj = __half2float(ph[pos]);
+#pragma unroll
+            for (int e = 0; e < 8; e++) o[e] = fmaf(__half2float(vnew[(DRAFT ? t : 0) * HD + 8 * cv + e]), pj, o[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) part[pv * HD + 8 * cv + e] = o[e];
     }
-    if (FUSED && p == P - 1) {
-        const float pj = __half2float(ph[pos]);
-#pragma unroll
-        for (int e = 0; e < 8; e++) o[e] = fmaf(__half2float(vnew[(DRAFT ? t : 0) * HD + 8 * c + e]), pj, o[e]);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) part[p * HD + 8 * c + e] = o[e];
     __syncthreads();
-    for (int i = tid; i < HD; i += AT_THREADS) { float s = 0.0f;
+    // the partitions in order 0 .. P - 1, as ever; VS > 1: this workgroup's HD / VS dims
+    for (int i = (VS == 1 ? 0 : (int)blockIdx.z * (HD / VS)) + tid; i < (VS == 1 ? HD : ((int)blockIdx.z + 1) * (HD / VS)); i += AT_THREADS) { float s = 0.0f;
 #pragma unroll 8
         for (int pp = 0; pp < P; pp++) s += part[pp * HD + i];
         out[qo + i] = s; }

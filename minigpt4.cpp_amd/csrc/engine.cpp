@@ -148,6 +148,9 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     // 0: wq|wk and wv of a mixed-type layer as two launches (batched step)
     batch_mix_ = !(getenv("MINIGPT4_BATCH_MIX") && atoi(getenv("MINIGPT4_BATCH_MIX")) == 0);
     if (const char *e = getenv("MINIGPT4_ATTN_SPLIT_T")) attn_split_t_ = atoi(e);   // cached keys from which the decode step uses the key-split attention (0 = never)
+    // workgroups per head of the one-row decode attention, each with its own share of the value columns (llm_kernels.hip: VS): 0 = choose (Engine::forward: 4 while
+    // 4 x heads fit the CUs -- 376.2-376.4 against 370.5-371.0 tok/s at 40 heads, profiles/r12_decode_attention_vsplit.log), 1 / 2 / 4 = force
+    if (const char *e = getenv("MINIGPT4_ATTN_VS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) attn_vs_ = v; }
     n_cus_ = prop.multiProcessorCount;
     // 1: Q4_K / Q5_K prompt rows on the fp16-MFMA form with scaled operands (k_mmqh_q45k: measured SLOWER,
     // profiles/r05_prefill_fp16_scaled_operands.md; A/B)
@@ -966,7 +969,8 @@ void Engine::forward(const Pass &p, hipStream_t s) {
         std::optional<SiteScope> att_sc;
         if (prof_on_) att_sc.emplace(this, "attention", 4.0 * (double)E * (sg ? sg->key_rows : (double)(conv_[sl].n_committed + N)), s);
         if (dec && p.split) launch_attn_llm_split(q_, k_, v_, kc, vc, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, attn_ws_, attn_splits_, s);
-        else if (dec) launch_attn_llm(q_, k_, v_, kc, vc, 1, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, true, s);
+        else if (dec) launch_attn_llm(q_, k_, v_, kc, vc, 1, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, true, s,
+                                      attn_vs_ ? attn_vs_ : 4 * H <= n_cus_ ? 4 : 2 * H <= n_cus_ ? 2 : 1);   // a workgroup can need a whole CU's LDS: never more of them than CUs
         else {
             if (pend_.ks > 1 && pend_.n == 3 && pend_.y[0] == q_ && pend_.y[1] == k_ && pend_.y[2] == v_ && !pend_.res[0] && !pend_.res[1] && !pend_.res[2] && pend_.stride == (long long)N * E) {
                 if (sg) launch_rope_kv_seg_slabs(pend_, N, H, hd, sg->rows, seq_stride, cos_, sin_, kc, vc, s);

@@ -409,6 +409,8 @@ private:
     FILE *trace_file_ = nullptr;       // MINIGPT4_PARITY_TRACE
     // key-split decode attention (llm_kernels.hip: k_attn_split_*)
     void *attn_ws_ = nullptr; int attn_splits_ = 6; int attn_split_t_ = 768; int attn_splits_forced_ = 0;
+    // value-column split of the one-row decode attention (k_attn_llm's VS; MINIGPT4_ATTN_VS; 0 = chosen at the launch).  The batched and the verify pass stay at 1
+    int attn_vs_ = 0;
     int batch_rows_max_ = 4; int batch_fuse_ = -1; int n_cus_ = 256;
     // round 5: B = 2..4 rows per weight pass on the int8 matrix cores over a row-interleaved second image of the k-quant matrices (ri_kernels.hip);
     // built by set_conversations(n > 1) -- a context with one conversation never pays the memory.  MINIGPT4_RI=0: the v_dot4 multi-row mat-vec of

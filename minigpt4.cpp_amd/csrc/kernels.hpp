@@ -151,8 +151,11 @@ void launch_kv_permute(__half *kc, __half *vc, size_t seq_stride, int n_slots, c
 // out[t][h*hd+i] = softmax(K q / sqrt(hd)) V over keys 0..*n_past+t.  caches: [n_ctx][E] fp16.
 // fused (decode, N == 1): q,k,v are the raw projections; RoPE of q/k and the KV append happen inside the kernel.
 // !fused: launch_rope_kv must have run (q rotated in place, caches appended).
+// vs (this launcher, the batched and the verify one): 1, or 2 / 4 = that many workgroups per (head, row), each with its own hd / vs output dims (fused forms only; same
+// bits out; attn_vsplit_ok says what is instantiated, the launchers throw for the rest).
+bool attn_vsplit_ok(int hd, int vs);
 void launch_attn_llm(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int N, int n_head, int hd, const int *n_past, int n_ctx,
-                     const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s);
+                     const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s, int vs = 1);
 // key-split decode attention for long contexts (one row; RoPE + KV append fused): every head's keys are shared by `splits` workgroups in two launches (scores; softmax + P.V
 // + deterministic combine by the last-arriving workgroup of the head).  ws: attn_split_workspace_bytes() bytes of device memory whose LAST 1 KiB + n_head words (the arrival
 // counters) were zeroed once; the kernels leave them zero.
@@ -163,7 +166,7 @@ void launch_attn_llm_split(float *q, const float *k, const float *v, __half *kca
 // decode of B different conversations in one pass (RoPE + KV append fused): row t -> conversation row_slot[t] at position n_past[row_slot[t]], caches at
 // kcache / vcache + row_slot[t] * seq_stride elements.
 void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int B, int n_head, int hd, const int *n_past, const int *row_slot,
-                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s);
+                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s, int vs = 1);
 // per row r, slot = row_slot[r]: argmax[slot] = feed[slot] = argmax(logits[r]); slot_logits[slot] = logits[r]; n_past[slot] += 1
 void launch_batch_finish(const float *logits, int n_vocab, int B, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s);
 void launch_batch_begin(int *n_past, const int *row_slot, const int *row_pos, int B, hipStream_t s);   // n_past[row_slot[r]] = row_pos[r]
@@ -173,7 +176,7 @@ constexpr int DRAFT_ROWS = 8;                          // the conversation's gre
 // and itself.  out and the appended rows are bit for bit those of R one-row launch_attn_llm_batched calls with n_past advanced by one between them.  n_past is not written.
 // n_ctx <= attn_draft_max_ctx(hd) (below).
 void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int R, int n_head, int hd, const int *n_past, const int *row_slot,
-                           size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s);
+                           size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s, int vs = 1);
 void launch_draft_begin(int *n_past, const int *row_slot, const int *row_pos, hipStream_t s);   // n_past[row_slot[0]] = row_pos[0]
 // res[1 + r] = first argmax of logits row r; m = leading draft tokens accepted (tok[i + 1] == res[1 + i], i < m); slot = row_slot[0]: slot_logits[slot] = logits[m],
 // argmax[slot] = feed[slot] = res[1 + m], n_past[slot] += 1 + m, res[0] = m.  res: 1 + DRAFT_ROWS ints

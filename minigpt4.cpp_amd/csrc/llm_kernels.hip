@@ -1798,9 +1798,9 @@ void launch_kv_permute(__half *kc, __half *vc, size_t seq_stride, int n_slots, c
 }
 
 // =====================================================================================================================
-// Decode attention over the fp16 KV cache: ONE body, attn_llm_body.hpp, included in the kernels k_attn_llm<HD, FUSED, BATCHED> and k_attn_llm_draft<HD> (why included and
-// not called: the head of that file); FUSED, BATCHED and DRAFT are compile-time constants there.
-// One 512-thread workgroup per (head, query row).
+// Decode attention over the fp16 KV cache: ONE body, attn_llm_body.hpp, included in the kernels k_attn_llm<HD, FUSED, BATCHED, VS> and k_attn_llm_draft<HD, VS> (why
+// included and not called: the head of that file); FUSED, BATCHED, DRAFT and VS are compile-time constants there.
+// One 512-thread workgroup per (head, query row) -- VS of them with the value-column split below.
 //   scores : 16 consecutive lanes share one cached key row (dot16), the new key by one lane over the whole head row (dot_row: sequential fp32 fma over the head dim);
 //            q is rounded to fp16 first, like ggml's f16 x f32 mul_mat
 //   softmax: max, exp through the fp16 table, exact double sum, probabilities rounded to fp16
@@ -1822,6 +1822,11 @@ void launch_kv_permute(__half *kc, __half *vc, size_t seq_stride, int n_slots, c
 //   - a key j in [p0, pos) is taken from LDS (kl / vl) instead of the cache -- SELECTED into the same (partition j mod P, round j / P) place of the same loops, so the
 //     max, the score row, and each partition's P.V chain see the same values in the same order (as t < P, a partition holds at most one such key: one LDS read per thread,
 //     one select per round); the own key is knew / vnew [t] where the BATCHED form has knew / vnew [0].
+// VS in {2, 4} (fused forms only; grid z): the value-column split.  Output dim d of a head is sum_j p_j V[j][d] -- different d never meet -- so VS workgroups share a
+// (head, row) with NO hand-off: each computes the whole score row, max, softmax and ph[] (K is read VS times; the splits of a head sit on one XCD's L2) and then the P.V
+// chains, the part[] rows and the final sums of ITS HD / VS dims only, on its first AT_THREADS / VS threads = (chunk cv of CH / VS, the same P partitions); the other
+// waves skip the V loads and the P.V loops.  Only split 0 appends to the cache; the others read it below pos (DRAFT: below p0), so there is no race.  Every fp32 chain is
+// the one of VS == 1 (same keys, same order, same operands): out and the caches are bit-identical.  Per CU the V bytes and P.V instructions fall to 1 / VS.
 // =====================================================================================================================
 constexpr int AT_THREADS = 512;
 // ---- shared by the family (k_attn_llm*, k_attn_split_*, k_attn_ref<true>): operand order and rounding calls are part of the results ----
@@ -1861,7 +1866,7 @@ static int attn_ctx_that_fits(int hd, int rows) { int n = 0; while (attn_lds_byt
 int attn_max_ctx(int hd) { return attn_ctx_that_fits(hd, 1); }
 int attn_draft_max_ctx(int hd) { return attn_ctx_that_fits(hd, DRAFT_ROWS); }
 
-template <int HD, bool FUSED, bool BATCHED = false>
+template <int HD, bool FUSED, bool BATCHED = false, int VS = 1>
 __global__ __launch_bounds__(AT_THREADS) void k_attn_llm(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
                                                          __half *__restrict__ vc, int E, const int *__restrict__ n_past, const float *__restrict__ cos_tab,
                                                          const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot = nullptr,
@@ -1870,7 +1875,7 @@ __global__ __launch_bounds__(AT_THREADS) void k_attn_llm(float *__restrict__ q, 
     constexpr int n_ctx = 0;                                      // DRAFT only
 #include "attn_llm_body.hpp"
 }
-template <int HD>
+template <int HD, int VS = 1>
 __global__ __launch_bounds__(AT_THREADS) void k_attn_llm_draft(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
                                                                __half *__restrict__ vc, int E, const int *__restrict__ n_past, int n_ctx, const float *__restrict__ cos_tab,
                                                                const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot,
@@ -1892,47 +1897,64 @@ template <class F> static bool attn_for_head_size(int hd, F &&f) {
 template <class F> static void attn_for_head_size_or_throw(int hd, F &&f) {
     if (!attn_for_head_size(hd, f)) throw HipError{hipErrorInvalidValue, "unsupported head size", __FILE__, __LINE__};
 }
-// The one launcher of the body's kernels: grid (head, row), the layout's LDS, the > 64 KiB opt-in at the first launch of a form (the plain and the one-row fused
-// form together, as they always were).
-template <int HD, bool BATCHED, bool DRAFT>
-static void launch_attn_body(bool fused, float *q, const float *k, const float *v, __half *kc, __half *vc, int rows, int n_head, const int *n_past, const int *row_slot,
-                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+// The one launcher of the body's kernels: grid (head, row, value-column split), the layout's LDS, the > 64 KiB opt-in at the first launch of every instantiation (the
+// plain and the one-row fused form together, as they always were).  z is the split: with 40 or 32 heads the workgroups h + n_head (t + rows z) of a head's splits land on
+// the same XCD and share its L2 for the K rows they all read.
+template <int HD, bool BATCHED, bool DRAFT, int VS>
+static void launch_attn_body_vs(bool fused, float *q, const float *k, const float *v, __half *kc, __half *vc, int rows, int n_head, const int *n_past, const int *row_slot,
+                                size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
     const size_t lds = attn_lds_bytes(n_ctx, HD, DRAFT ? DRAFT_ROWS : 1);
-    const dim3 grid((unsigned)n_head, (unsigned)rows);
+    const dim3 grid((unsigned)n_head, (unsigned)rows, (unsigned)VS);
     static bool attr = false;
     if constexpr (DRAFT) {
-        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_draft<HD>)); attr = true; }
-        note_kernel("k_attn_llm_draft<%d>", HD);
-        hipLaunchKernelGGL((k_attn_llm_draft<HD>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, n_ctx, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_draft<HD, VS>)); attr = true; }
+        if (VS == 1) note_kernel("k_attn_llm_draft<%d>", HD); else note_kernel("k_attn_llm_draft<%d, %d>", HD, VS);
+        hipLaunchKernelGGL((k_attn_llm_draft<HD, VS>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, n_ctx, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
     } else if constexpr (BATCHED) {
-        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, true>)); attr = true; }
-        hipLaunchKernelGGL((k_attn_llm<HD, true, true>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
-    } else {
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, true, VS>)); attr = true; }
+        hipLaunchKernelGGL((k_attn_llm<HD, true, true, VS>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+    } else if constexpr (VS == 1) {
         if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true>));
                      HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, false>)); attr = true; }
         note_kernel("k_attn_llm<%d, %s, false>", HD, fused ? "true" : "false");
         hipLaunchKernelGGL((fused ? k_attn_llm<HD, true> : k_attn_llm<HD, false>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out,
                            row_slot, seq_stride);
+    } else {
+        if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, false, VS>)); attr = true; }
+        note_kernel("k_attn_llm<%d, true, false, %d>", HD, VS);
+        hipLaunchKernelGGL((k_attn_llm<HD, true, false, VS>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
     }
+}
+// vs: 1, or 2 / 4 for the fused forms where the head's HD / 8 chunks divide (every supported head size does); anything else is refused
+bool attn_vsplit_ok(int hd, int vs) { return vs == 1 || ((vs == 2 || vs == 4) && (hd == 32 || hd == 64 || hd == 128)); }
+template <int HD, bool BATCHED, bool DRAFT>
+static void launch_attn_body(bool fused, float *q, const float *k, const float *v, __half *kc, __half *vc, int rows, int n_head, const int *n_past, const int *row_slot,
+                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, int vs, hipStream_t s) {
+    if (!attn_vsplit_ok(HD, vs) || (vs != 1 && !fused)) throw HipError{hipErrorInvalidValue, "decode attention: unsupported value-column split", __FILE__, __LINE__};
+#define ATTN_VS_ARGS fused, q, k, v, kc, vc, rows, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s
+    if (vs == 4) launch_attn_body_vs<HD, BATCHED, DRAFT, 4>(ATTN_VS_ARGS);
+    else if (vs == 2) launch_attn_body_vs<HD, BATCHED, DRAFT, 2>(ATTN_VS_ARGS);
+    else launch_attn_body_vs<HD, BATCHED, DRAFT, 1>(ATTN_VS_ARGS);
+#undef ATTN_VS_ARGS
 }
 // fused = true (N must be 1): q,k,v are the raw projections; RoPE + KV append happen inside.  fused = false: launch_rope_kv must have run.
 void launch_attn_llm(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int N, int n_head, int hd, const int *n_past, int n_ctx,
-                     const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s) {
+                     const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, bool fused, hipStream_t s, int vs) {
     attn_for_head_size_or_throw(hd, [&](auto tag) {
-        launch_attn_body<decltype(tag)::value, false, false>(fused, q, k, v, kcache, vcache, fused ? 1 : N, n_head, n_past, nullptr, 0, n_ctx, cos_tab, sin_tab, tb, out, s); });
+        launch_attn_body<decltype(tag)::value, false, false>(fused, q, k, v, kcache, vcache, fused ? 1 : N, n_head, n_past, nullptr, 0, n_ctx, cos_tab, sin_tab, tb, out, vs, s); });
 }
 // Decode attention for B rows of B different conversations (RoPE + KV append fused): row t uses position n_past[row_slot[t]] and the caches of that conversation.
 void launch_attn_llm_batched(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int B, int n_head, int hd, const int *n_past, const int *row_slot,
-                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+                             size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s, int vs) {
     attn_for_head_size_or_throw(hd, [&](auto tag) {
-        launch_attn_body<decltype(tag)::value, true, false>(true, q, k, v, kcache, vcache, B, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); });
+        launch_attn_body<decltype(tag)::value, true, false>(true, q, k, v, kcache, vcache, B, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, vs, s); });
 }
 // Verify pass: R <= DRAFT_ROWS rows of the conversation row_slot[0] (the DRAFT form above); n_ctx <= attn_draft_max_ctx(hd)
 void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int R, int n_head, int hd, const int *n_past, const int *row_slot,
-                           size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+                           size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s, int vs) {
     if (R < 1 || R > DRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_attn_llm_draft: row count out of range", __FILE__, __LINE__};
     attn_for_head_size_or_throw(hd, [&](auto tag) {
-        launch_attn_body<decltype(tag)::value, true, true>(true, q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s); });
+        launch_attn_body<decltype(tag)::value, true, true>(true, q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, vs, s); });
 }
 // =====================================================================================================================
 // Key-split decode attention (long contexts): k_attn_llm above puts ONE workgroup on a head -- 40 workgroups on a 256-CU chip, 0.015 us per cached key, 35 us per layer

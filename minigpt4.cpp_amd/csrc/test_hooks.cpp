@@ -1099,6 +1099,52 @@ int minigpt4_amd_test_attn_draft(int mode, int n_head, int hd, int n_ctx, int n_
         return 0;
     });
 }
+int minigpt4_amd_test_attn_vsplit(int form, int vs, int n_head, int hd, int n_ctx, int n_slot, int rows, const int32_t *row_slot, const int32_t *n_past, int computed_exp,
+                                  const float *q, const float *k, const float *v, uint16_t *kc, uint16_t *vc, float *out) {
+    if (!q || !k || !v || !kc || !vc || !out || !row_slot || !n_past || form < 0 || form > 2 || (hd != 32 && hd != 64 && hd != 128) || !attn_vsplit_ok(hd, vs) || n_head < 1 ||
+        n_slot < 1 || rows < 1 || n_ctx < 1 || n_ctx > (form == 2 ? attn_draft_max_ctx(hd) : attn_max_ctx(hd)) || (form == 0 && (rows != 1 || n_slot != 1)) ||
+        (form == 2 && rows > DRAFT_ROWS)) return 1;
+    // form 1: every row its own conversation; form 2: all rows in row_slot[0] at consecutive positions; every position written must lie inside the cache
+    for (int r = 0; r < (form == 2 ? 1 : rows); r++) {
+        if (row_slot[r] < 0 || row_slot[r] >= n_slot) return 1;
+        for (int r2 = 0; r2 < r; r2++) if (row_slot[r2] == row_slot[r]) return 1;
+        const int np = n_past[row_slot[r]];
+        if (np < 0 || np > n_ctx - (form == 2 ? rows : 1)) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, stride = (size_t)n_ctx * E, cache = (size_t)n_slot * stride, RE = (size_t)rows * E;
+        std::vector<float> c, sn;
+        rope_tables(n_ctx, hd, c, sn);
+        DevBuf dc(c.size() * 4), dsn(sn.size() * 4), dq(RE * 4), dk(RE * 4), dv(RE * 4), dkc(cache * 2), dvc(cache * 2), dout(RE * 4), dnp((size_t)n_slot * 4), dslot((size_t)rows * 4),
+            dtab(65536 * 2);
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dq.p, q, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dk.p, k, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, RE * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dkc.p, kc, cache * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dvc.p, vc, cache * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dnp.p, n_past, (size_t)n_slot * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dslot.p, row_slot, (size_t)rows * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0, RE * 4));
+        Tables tb;                                                // as in minigpt4_amd_test_attn_draft
+        { std::vector<__half> e(65536); int last = 0;
+          for (int i = 0; i < 65536; i++) e[(size_t)i] = __float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)i))));
+          for (int i = 0; i < 0x7C00; i++) if (__half2float(e[(size_t)(0x8000 + i)]) != 0.0f) last = i;
+          HIP_CHECK(hipMemcpy(dtab.p, e.data(), 131072, hipMemcpyHostToDevice));
+          tb.exp = computed_exp ? nullptr : dtab.as<__half>(); tb.exp_neg_n = (last + 1 + 2047) / 2048 * 2048; }
+        if (form == 0)
+            launch_attn_llm(dq.as<float>(), dk.as<float>(), dv.as<float>(), dkc.as<__half>(), dvc.as<__half>(), 1, n_head, hd, dnp.as<int>(), n_ctx, dc.as<float>(), dsn.as<float>(), tb,
+                            dout.as<float>(), true, nullptr, vs);
+        else if (form == 1)
+            launch_attn_llm_batched(dq.as<float>(), dk.as<float>(), dv.as<float>(), dkc.as<__half>(), dvc.as<__half>(), rows, n_head, hd, dnp.as<int>(), dslot.as<int>(), stride, n_ctx,
+                                    dc.as<float>(), dsn.as<float>(), tb, dout.as<float>(), nullptr, vs);
+        else
+            launch_attn_llm_draft(dq.as<float>(), dk.as<float>(), dv.as<float>(), dkc.as<__half>(), dvc.as<__half>(), rows, n_head, hd, dnp.as<int>(), dslot.as<int>(), stride, n_ctx,
+                                  dc.as<float>(), dsn.as<float>(), tb, dout.as<float>(), nullptr, vs);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dout.p, RE * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc, dkc.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 int minigpt4_amd_test_ngram_draft(const int32_t *history, int n, int ngram_max, int ngram_min, int n_draft, int32_t *out) {
     if (n < 0 || (n > 0 && !history) || !out || ngram_min < 1 || ngram_max < ngram_min || n_draft < 0) return -1;
     NgramDrafter d(ngram_max, ngram_min);

@@ -264,6 +264,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_kv_permute.argtypes = [I32, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_pen_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
@@ -855,6 +856,26 @@ class MiniGPT4SharedLibrary:
                                                        v.ctypes.data_as(FLOAT_PTR), kc.ctypes.data_as(VOID_PTR), vc.ctypes.data_as(VOID_PTR), out.ctypes.data_as(FLOAT_PTR))
         if rc:
             raise RuntimeError(f"test_attn_draft rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return out, kc, vc
+
+    def amd_test_attn_vsplit(self, form: int, vs: int, q: np.ndarray, k: np.ndarray, v: np.ndarray, kc: np.ndarray, vc: np.ndarray, n_head: int, row_slot: Sequence[int],
+                             n_past: Sequence[int], computed_exp: bool = True):
+        """One launch of the decode attention with `vs` workgroups per (head, row), each on its own share of the value columns (vs 1: the plain launch).  form 0: the
+        one-row fused kernel, 1: the batched kernel (row r = conversation row_slot[r]), 2: the verify kernel (all rows in row_slot[0], consecutive positions).  q, k, v
+        [rows][E]; fp16 caches [n_slot][n_ctx][E] as uint16 patterns; n_past [n_slot].  Returns (out [rows][E], kc, vc) -- copies."""
+        q, k, v = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+        kc, vc = np.array(kc, np.uint16, order="C"), np.array(vc, np.uint16, order="C")
+        R, E = q.shape
+        S, C, _ = kc.shape
+        rs, npast = np.ascontiguousarray(row_slot, np.int32), np.ascontiguousarray(n_past, np.int32)
+        if len(rs) != R or len(npast) != S:
+            raise ValueError("test_attn_vsplit: one slot per row and one position per slot")
+        out = np.zeros_like(q)
+        rc = self.library.minigpt4_amd_test_attn_vsplit(int(form), int(vs), n_head, E // n_head, C, S, R, rs.ctypes.data_as(INT_PTR), npast.ctypes.data_as(INT_PTR), int(computed_exp),
+                                                        q.ctypes.data_as(FLOAT_PTR), k.ctypes.data_as(FLOAT_PTR), v.ctypes.data_as(FLOAT_PTR), kc.ctypes.data_as(VOID_PTR),
+                                                        vc.ctypes.data_as(VOID_PTR), out.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_attn_vsplit rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return out, kc, vc
 
     def amd_test_ngram_draft(self, history: Sequence[int], ngram_max: int, ngram_min: int, n_draft: int) -> List[int]:
