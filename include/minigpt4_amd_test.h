@@ -32,6 +32,12 @@ MINIGPT4_API int minigpt4_amd_test_matvec(int type1, const void *raw1, int n1, i
  * silu * mul preparation launch gets in fast mode: prep 3 with fuse 0; the fused prologue and the pair epilogue always gather, so NULL with them is refused: 1) */
 MINIGPT4_API int minigpt4_amd_test_matvec_ex(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2,
                                              int prep, int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y);
+/* ONE launch of the decode mat-vec with the row preparation in its prologue (arguments as minigpt4_amd_test_matvec with fuse = 1), with or without the issue barrier: a
+ * data-free barrier between the prologue's row loads and its first weight requests (built for the k-quants at K <= 6144; elsewhere the plain form runs).  y: the outputs
+ * followed by `guard` floats that the launch must leave at their 0xFF fill.  Outputs do not depend on issue_barrier, bit for bit. */
+MINIGPT4_API int minigpt4_amd_test_matvec_issue(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2,
+                                                int prep, int epi, const float *residual, int issue_barrier, int guard, float *y);
+MINIGPT4_API int minigpt4_amd_test_matvec_waves(void);   /* waves of a prologue launch that fills the device (wave w owns row groups w, w + waves, ...) */
 /* The batched-decode mat-vec: N = 1..4 activation rows x[N][n_in] against n_mat (1..3) equally spaced matrices in one weight pass; y / residual: [n_mat][N][n_out].
  * Returns 4 when the shape / type is outside the kernel's range. */
 MINIGPT4_API int minigpt4_amd_test_matvec_rows(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, float *y);

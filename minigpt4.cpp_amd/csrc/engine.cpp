@@ -151,6 +151,7 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     // workgroups per head of the one-row decode attention, each with its own share of the value columns (llm_kernels.hip: VS): 0 = choose (Engine::forward: 4 while
     // 4 x heads fit the CUs -- 376.2-376.4 against 370.5-371.0 tok/s at 40 heads, profiles/r12_decode_attention_vsplit.log), 1 / 2 / 4 = force
     if (const char *e = getenv("MINIGPT4_ATTN_VS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) attn_vs_ = v; }
+    if (const char *e = getenv("MINIGPT4_MV_IB")) { const int v = atoi(e); if (v == 0 || v == 1) for (bool &b : mv_issue_bar_) b = v != 0; }   // unset: the per-site defaults
     n_cus_ = prop.multiProcessorCount;
     // 1: Q4_K / Q5_K prompt rows on the fp16-MFMA form with scaled operands (k_mmqh_q45k: measured SLOWER,
     // profiles/r05_prefill_fp16_scaled_operands.md; A/B)
@@ -736,7 +737,7 @@ struct WeightSet {
     }
 };
 }  // namespace
-bool Engine::mul_mat_set(const QWeight *const *W, float *const *y, const float *const *res, int n, int N, int ldy, hipStream_t s, const Prep *prep, bool fuse, bool silu_pair, const char *site, bool defer_ok, bool keep_pending) {
+bool Engine::mul_mat_set(const QWeight *const *W, float *const *y, const float *const *res, int n, int N, int ldy, hipStream_t s, const Prep *prep, bool fuse, bool silu_pair, const char *site, bool defer_ok, bool keep_pending, bool issue_bar) {
     struct ClearOverride { const __half *&p; ~ClearOverride() { p = nullptr; } } clear_override{xh_override_};   // valid for exactly one call
     const bool same = same_shape(W, n);
     int mask = 0;
@@ -782,11 +783,11 @@ bool Engine::mul_mat_set(const QWeight *const *W, float *const *y, const float *
     }
     if (!done && staged_elsewhere && xh_override_) throw HipError{hipErrorInvalidValue, "F16 set launch refused rows that only exist in fp16 (no generic path may read act_ here)", __FILE__, __LINE__};
     if (!done && silu_pair) {   // the pair epilogue needs the two matrices equally spaced; launch_matvec_set refuses otherwise and the plain launch below runs
-        done = fuse ? launch_matvec_set(W, y, res, n, act_, s, prep->kind, prep->x, prep->w, &tabs_, 1) : launch_matvec_set(W, y, res, n, act_, s, 0, nullptr, nullptr, &tabs_, 1);
+        done = fuse ? launch_matvec_set(W, y, res, n, act_, s, prep->kind, prep->x, prep->w, &tabs_, 1, issue_bar) : launch_matvec_set(W, y, res, n, act_, s, 0, nullptr, nullptr, &tabs_, 1);
         silu_pair = done;
     }
     if (!done) {
-        if (fuse) done = launch_matvec_set(W, y, res, n, act_, s, prep->kind, prep->x, prep->w, &tabs_);
+        if (fuse) done = launch_matvec_set(W, y, res, n, act_, s, prep->kind, prep->x, prep->w, &tabs_, 0, issue_bar);
         else if (v2) done = launch_matvec_set(W, y, res, n, act_, s);
     }
     if (!done) {
@@ -804,9 +805,9 @@ bool Engine::mul_mat_set(const QWeight *const *W, float *const *y, const float *
     }
     return silu_pair;
 }
-void Engine::mul_mat(const QWeight &W, int N, float *y, int ldy, const float *residual, hipStream_t s, const Prep *prep, bool fuse, const char *site, bool defer_ok, bool keep_pending) {
+void Engine::mul_mat(const QWeight &W, int N, float *y, int ldy, const float *residual, hipStream_t s, const Prep *prep, bool fuse, const char *site, bool defer_ok, bool keep_pending, bool issue_bar) {
     const QWeight *Wp[1] = {&W}; float *Yp[1] = {y}; const float *Rp[1] = {residual};
-    mul_mat_set(Wp, Yp, Rp, 1, N, ldy, s, prep, fuse, false, site, defer_ok, keep_pending);
+    mul_mat_set(Wp, Yp, Rp, 1, N, ldy, s, prep, fuse, false, site, defer_ok, keep_pending, issue_bar);
 }
 
 // wq|wk and a differently typed wv (k-quant "more bits" layers) in one launch; returns false when the shapes / types are outside the mixed kernel's
@@ -817,7 +818,7 @@ bool Engine::mixed_qkv(const LayerW &L, hipStream_t s, bool fuse) {
     const QWeight *W1[2] = {&L.wq, &L.wk}, *W2[1] = {&L.wv}; float *Y1[2] = {q_, k_}, *Y2[1] = {v_};
     if (act_mask_for(L.wq.type) != ACT_Q8K || act_mask_for(L.wv.type) != ACT_Q8K) return false;
     SiteScope sc(this, "qkv", (double)(L.wq.bytes + L.wk.bytes + L.wv.bytes), s);   // only once the launch is certain: a refused shape must not record an empty site
-    if (fuse && matvec_prologue_supported(L.wq.type, E)) { if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, s, 1, x_, L.attn_norm)) return true; }
+    if (fuse && matvec_prologue_supported(L.wq.type, E)) { if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, s, 1, x_, L.attn_norm, 0, mv_issue_bar_[MV_QKV_MIXED])) return true; }
     // standalone preparation, then the mixed launch; if that is refused the caller's per-type launches find the row already prepared
     launch_rms_quant(x_, L.attn_norm, 1, E, act_, ACT_Q8K, s);
     if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, s)) return true;
@@ -956,7 +957,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
         {
             const QWeight *W3[3] = {&L.wq, &L.wk, &L.wv}; float *Y3[3] = {q_, k_, v_};
             // a K-split combine is left to launch_rope_kv_slabs
-            if (L.wv.type == L.wq.type) mul_mat_set(W3, Y3, nullptr, 3, N, E, s, &p_attn, fz(0), false, "qkv", !dec);
+            if (L.wv.type == L.wq.type) mul_mat_set(W3, Y3, nullptr, 3, N, E, s, &p_attn, fz(0), false, "qkv", !dec, false, mv_issue_bar_[MV_QKV]);
             else if (fz(6) && L.wk.type == L.wq.type && mixed_qkv(L, s, fz(0))) {}
             else if (act_mask_for(L.wv.type) == act_mask_for(L.wq.type) && !fz(0)) {   // one standalone preparation serves both launches
                 prep_rms(x_, L.attn_norm, N, E, act_mask_for(L.wq.type), s);
@@ -989,7 +990,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
                 launch_attn_llm(q_, k_, v_, kc, vc, N, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_, att_, false, s);
         }
         att_sc.reset();
-        mul_mat(L.wo, N, x_, E, x_, s, att_in_xh ? nullptr : &p_att, fz(1), "wo", !dec);             // combine left to the ffn norm's preparation
+        mul_mat(L.wo, N, x_, E, x_, s, att_in_xh ? nullptr : &p_att, fz(1), "wo", !dec, false, mv_issue_bar_[MV_WO]);             // combine left to the ffn norm's preparation
         bool paired = false;   // h1_ already holds silu(w1 x) * (w3 x)
         // F16 weights at prompt sizes: w1 | w3 in one launch whose epilogue stores fp16(silu(w1 x) * (w3 x)) -- the rows w2 multiplies -- into h1_'s
         // memory (round 3)
@@ -1007,7 +1008,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
             continue;
         }
         // combine left to silu * mul
-        if (L.w1.type == L.w3.type) { const QWeight *W2[2] = {&L.w1, &L.w3}; float *Y2[2] = {h1_, h3_}; paired = mul_mat_set(W2, Y2, nullptr, 2, N, F, s, &p_ffn, fz(2), fz(5), "w1w3", !dec); }
+        if (L.w1.type == L.w3.type) { const QWeight *W2[2] = {&L.w1, &L.w3}; float *Y2[2] = {h1_, h3_}; paired = mul_mat_set(W2, Y2, nullptr, 2, N, F, s, &p_ffn, fz(2), fz(5), "w1w3", !dec, false, mv_issue_bar_[MV_W1W3]); }
         else if (act_mask_for(L.w1.type) == act_mask_for(L.w3.type) && !fz(2)) {
             prep_rms(x_, L.ffn_norm, N, E, act_mask_for(L.w1.type), s);
             mul_mat(L.w1, N, h1_, F, nullptr, s, nullptr, false, "w1"); mul_mat(L.w3, N, h3_, F, nullptr, s, nullptr, false, "w3");
@@ -1030,7 +1031,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
     }
     // only the last token's logits are kept (llama.cpp logits_all = false)
     const Prep p_out{1, x_ + (size_t)(N - 1) * E, norm_};
-    mul_mat(output_, 1, logits, V, nullptr, s, &p_out, fz(4), "output");
+    mul_mat(output_, 1, logits, V, nullptr, s, &p_out, fz(4), "output", false, false, mv_issue_bar_[MV_OUTPUT]);
     { SiteScope sc(this, "argmax", (double)V * 4, s); launch_argmax(logits, V, d_argmax, d_scratch_, s); }
     { SiteScope sc(this, "advance", 0.0, s); launch_advance(d_npast, N, d_feed, d_argmax, s); }
     HIP_CHECK(hipMemcpyAsync(h_argmax_ + sl, d_argmax, 4, hipMemcpyDeviceToHost, s));

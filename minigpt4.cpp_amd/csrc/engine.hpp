@@ -311,8 +311,8 @@ private:
     size_t seg_ints() const { return (size_t)SEG_ROWS + 2 * (size_t)max_rows_ + 4 * ((size_t)max_rows_ + MAX_CONVERSATIONS); }
     int *d_seg_ = nullptr, *h_seg_ = nullptr;
     struct Prep { int kind; const float *x; const float *w; };   // 1: rms_norm(x)*w, 2: x, 3: silu(x)*w -- then quantised for the consumer's type
-    void mul_mat(const QWeight &W, int N, float *y, int ldy, const float *residual, hipStream_t s, const Prep *prep, bool fuse, const char *site = "matmul", bool defer_ok = false, bool keep_pending = false);
-    bool mul_mat_set(const QWeight *const *W, float *const *y, const float *const *res, int n, int N, int ldy, hipStream_t s, const Prep *prep, bool fuse, bool silu_pair = false, const char *site = "matmul", bool defer_ok = false, bool keep_pending = false);
+    void mul_mat(const QWeight &W, int N, float *y, int ldy, const float *residual, hipStream_t s, const Prep *prep, bool fuse, const char *site = "matmul", bool defer_ok = false, bool keep_pending = false, bool issue_bar = false);
+    bool mul_mat_set(const QWeight *const *W, float *const *y, const float *const *res, int n, int N, int ldy, hipStream_t s, const Prep *prep, bool fuse, bool silu_pair = false, const char *site = "matmul", bool defer_ok = false, bool keep_pending = false, bool issue_bar = false);
     // prompt passes: the combine of a K-split mat-mul is left to the kernel that consumes the result (rope + cache append, the next norm +
     // quantisation, silu * mul); pend_ describes the slabs until then, flush_pending runs the combine as its own launch when the next consumer is not
     // one of those.  MINIGPT4_DEFER_COMBINE=0: always flush (A/B)
@@ -411,6 +411,11 @@ private:
     void *attn_ws_ = nullptr; int attn_splits_ = 6; int attn_split_t_ = 768; int attn_splits_forced_ = 0;
     // value-column split of the one-row decode attention (k_attn_llm's VS; MINIGPT4_ATTN_VS; 0 = chosen at the launch).  The batched and the verify pass stay at 1
     int attn_vs_ = 0;
+    // issue barrier of the decode step's prologue mat-vec launches (kernels.hpp: issue_bar), one default per launch site: on where it won on the 13B Q5_K_M step (per
+    // launch 17.64 -> 17.13 us qkv and w1|w3, 14.03 -> 13.60 mixed qkv, 24.88 -> 24.77 output), off for wo (6.99 -> 7.13 us: its two or three row groups per wave leave
+    // nothing to reorder); profiles/r13_matvec_prefetch_depth.log.  MINIGPT4_MV_IB = 0 / 1 forces it off / on at every site
+    enum MvSite { MV_QKV = 0, MV_QKV_MIXED, MV_WO, MV_W1W3, MV_OUTPUT, MV_SITES };
+    bool mv_issue_bar_[MV_SITES] = {true, true, false, true, true};
     int batch_rows_max_ = 4; int batch_fuse_ = -1; int n_cus_ = 256;
     // round 5: B = 2..4 rows per weight pass on the int8 matrix cores over a row-interleaved second image of the k-quant matrices (ri_kernels.hip);
     // built by set_conversations(n > 1) -- a context with one conversation never pays the memory.  MINIGPT4_RI=0: the v_dot4 multi-row mat-vec of

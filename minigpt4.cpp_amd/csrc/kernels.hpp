@@ -76,9 +76,12 @@ bool launch_gemm_f16_set(const __half *A, int lda, const __half *const *W, int n
 // decode (N = 1) persistent-wave mat-vec over 1..3 same-type, same-shape matrices (wq|wk|wv, w1|w3); false -> caller falls back to launch_mul_mat
 // pro: 0 = activations come from `A` (prepared by launch_rms_quant / launch_silu_mul_quant); 1 = rms_norm(px) * pw, 2 = px, 3 = silu(px) * pw are
 // prepared and quantised inside the kernel prologue (one launch less per use).
+// issue_bar (pro != 0): a data-free barrier between the prologue's row loads and its first weight requests, so that the row loads of all waves of a CU are issued first
+// (built for the k-quants at K <= 6144; elsewhere the plain form runs).  Outputs do not depend on it, bit for bit.
 bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, hipStream_t s, int pro = 0, const float *px = nullptr,
-                       const float *pw = nullptr, const Tables *tb = nullptr, int epi = 0);   // epi 1: y[0][g] = silu(W0[g].x) * (W1[g].x) (n == 2); MATVEC_EPI_REF: the CPU oracle's fp32 order (k-quants; pro 0..2)
+                       const float *pw = nullptr, const Tables *tb = nullptr, int epi = 0, bool issue_bar = false);   // epi 1: y[0][g] = silu(W0[g].x) * (W1[g].x) (n == 2); MATVEC_EPI_REF: the CPU oracle's fp32 order (k-quants; pro 0..2)
 constexpr int MATVEC_EPI_REF = 2;
+int matvec_prologue_waves();   // waves of a prologue launch with at least as many row groups: wave w owns groups w, w + waves, ...
 bool matvec_silu_pair_supported(int type, int cols);
 // batched decode: N = 1..4 activation rows (prepared in `A`) against 1..3 same-type, same-shape, equally spaced matrices, weights streamed once;
 // y[m][t * ldy + r] (+ residual[m][t * ldy + r]).  false -> outside the kernel's range, use launch_mul_mat.
@@ -103,7 +106,7 @@ void set_ri_cus(int cus);
 int ri_ksplit(int total_groups, int K, const RiWorkspace &ws);   // workgroups per row group the launch would use with this workspace (1 = no K split)
 // two k-quant types (Q4_K|Q5_K + Q6_K) with the same K in one launch; pro: 0 or 1 (rms_norm prologue)
 bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, hipStream_t s, int pro = 0,
-                         const float *px = nullptr, const float *pw = nullptr, int epi = 0);
+                         const float *px = nullptr, const float *pw = nullptr, int epi = 0, bool issue_bar = false);
 // the same for N = 1..4 rows of the batched step (K <= 6144); px != null: rows rms-normed with pw and quantised inside the launch
 bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, int N, int ldy, hipStream_t s,
                               const float *px = nullptr, const float *pw = nullptr, int ldx = 0);

@@ -518,9 +518,14 @@ __device__ unsigned long long g_tla[2048 * 8];
 #endif
 // (Round 5 measured "pair packing" -- two consecutive K = 5120 rows as ONE run of 320 units over 5 lane-walks instead of 2 x 3 with 17 % of the lanes masked -- and lost:
 // 356 vs 374 tok/s on the 13B file, profiles/r05_experiments_not_adopted.md; removed again.)
-template <int T, int NU, int R, int PRO, int EPI>
+// IB (prologue forms): a raw s_barrier (no wait on data) between the row loads and the first weight requests, so that the row loads of ALL waves of the workgroup are ahead
+// of any weight request in the CU's vector-memory queue -- without it the row loads of the late waves queue behind the weight tiles of the early ones, and the row-wide
+// barriers wait for the slowest wave (row ready 3.6 -> 3.3 us, profiles/r13_matvec_prefetch_depth.log).  Requesting MORE row groups before the preparation (round 2's
+// PRIME2, measured again in round 13 as depths 2 / 3) loses: a wave issues in order, so it reaches its row only after the CU has taken all those requests.
+template <int T, int NU, int R, int PRO, int EPI, bool IB = false>
 __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, const ProArgs &pa, const int n_groups, const int n_waves, const int wave) {
     static_assert(EPI != EPI_SILU_PAIR || R == 2, "the SiLU pair epilogue works on row pairs");
+    static_assert(PRO != PRO_NONE || !IB, "the issue barrier belongs to the prologue forms");
     // groups of this wave: g = g_first, g_first + g_step, ... < g_last
     const int g_first = wave, g_last = n_groups, g_step = n_waves;
     MG4_TL(0); MG4_TL_ALL(7);
@@ -595,6 +600,11 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
         if (PRO == PRO_SILU) {
 #pragma unroll
             for (int r = 0; r < RND; r++) { xv[r].x = tab(pa.tb.silu, xv[r].x); xv[r].y = tab(pa.tb.silu, xv[r].y); xv[r].z = tab(pa.tb.silu, xv[r].z); xv[r].w = tab(pa.tb.silu, xv[r].w); }
+        }
+        if (IB) {   // orders ISSUE only: nothing is waited for
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
         }
         fetch(g_first, cur);
         MG4_TL(1);
@@ -697,19 +707,19 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
     MG4_TL(5); MG4_TL_ALL(6);
 #endif
 }
-template <int T, int NU, int R, int PRO, int EPI>
+template <int T, int NU, int R, int PRO, int EPI, bool IB = false>
 __global__ __launch_bounds__(PRO == PRO_NONE ? 256 : mv_fat_max_threads<NU>()) void k_matvec_v2(const MatSet ms, const ActQ A, const ProArgs pa, const int n_groups, const int n_waves) {
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));   // wave-uniform: scalar loop control
-    matvec_run<T, NU, R, PRO, EPI>(ms, A, pa, n_groups, n_waves, wave);
+    matvec_run<T, NU, R, PRO, EPI, IB>(ms, A, pa, n_groups, n_waves, wave);
 }
 // Two weight types in one launch (llama.cpp's k-quant mixes give wv more bits than wq|wk): waves [0, n_waves1) stream set 1, the rest set 2.  Both
 // sets share K and the prepared activation row (both types read the Q8_K image); every wave passes the same number of workgroup barriers.
-template <int T1, int T2, int NU, int PRO, int EPI = EPI_STORE>
+template <int T1, int T2, int NU, int PRO, int EPI = EPI_STORE, bool IB = false>
 __global__ __launch_bounds__(PRO == PRO_NONE ? 256 : mv_fat_max_threads<NU>()) void k_matvec_mix(const MatSet ms1, const MatSet ms2, const ActQ A, const ProArgs pa, const int n_groups1,
                                                                                                  const int n_waves1, const int n_groups2, const int n_waves2) {
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (wave < n_waves1) matvec_run<T1, NU, 1, PRO, EPI>(ms1, A, pa, n_groups1, n_waves1, wave);
-    else matvec_run<T2, NU, 1, PRO, EPI>(ms2, A, pa, n_groups2, n_waves2, wave - n_waves1);
+    if (wave < n_waves1) matvec_run<T1, NU, 1, PRO, EPI, IB>(ms1, A, pa, n_groups1, n_waves1, wave);
+    else matvec_run<T2, NU, 1, PRO, EPI, IB>(ms2, A, pa, n_groups2, n_waves2, wave - n_waves1);
 }
 static int g_mv_cus = 256;
 static int g_mv_force_waves = 0;    // MINIGPT4_MV_WAVES: waves per CU of the prologue-free launches (0 = choose)
@@ -719,13 +729,26 @@ static int g_mv_force_fat = 0;      // MINIGPT4_FAT_LB: threads of the fat workg
 // end than 512-thread ones; 1024-thread ones 5 % slower; 5 / 7 waves per CU for the K = 13824 mat-vec 4 % / 1 % slower than 8).
 static int pick_waves_per_cu(int /*groups*/, int max_wpc) { return std::min(g_mv_force_waves ? g_mv_force_waves : 8, max_wpc); }
 static int pick_fat_threads(int /*groups*/, int max_threads) { return g_mv_force_fat ? std::max(MV_FAT_MIN, std::min(g_mv_force_fat / 64 * 64, max_threads)) : MV_FAT_MIN; }
+int matvec_prologue_waves() { return g_mv_cus * (pick_fat_threads(0, MV_FAT_MIN) / 64); }
 static size_t mv_prologue_lds(int K) { return 128 + (size_t)2 * K + (size_t)(K / 256 + 1) * 4 + (size_t)4 * (K / 32) * 4 + (size_t)(K / 16) * 2 + 64; }
 template <int NU> constexpr int mv_max_wpc() { return NU <= 3 ? 16 : NU == 4 ? 12 : 8; }      // register budget of the two-stage pipeline
+// The issue-barrier forms are built for the k-quants at NU <= 3 (K <= 6144: every prologue launch of the 7B / 13B decode step) outside parity mode; elsewhere the launch runs
+// the plain form.
+template <int T, int NU, int EPI> constexpr bool mv_issue_bar_built() { return (T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K) && NU <= 3 && EPI != EPI_REF; }
+template <int T, int NU, int R, int PRO, int EPI>
+static void launch_v2_pro(bool issue_bar, dim3 grid, dim3 block, size_t lds, hipStream_t s, const MatSet &ms, const ActQ &A, const ProArgs &pa, int n_groups, int n_waves) {
+    const bool bar = issue_bar && mv_issue_bar_built<T, NU, EPI>();
+    note_kernel("k_matvec_v2<%d, %d, %d, %d, %d, %s>", T, NU, R, PRO, EPI, bar ? "true" : "false");
+    if constexpr (mv_issue_bar_built<T, NU, EPI>()) {
+        if (bar) { hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI, true>), grid, block, lds, s, ms, A, pa, n_groups, n_waves); return; }
+    }
+    hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI>), grid, block, lds, s, ms, A, pa, n_groups, n_waves);
+}
 template <int T, int NU, int R, int EPI>
-static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, hipStream_t s) {
+static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
     const int total_rows = ms.n * ms.rows_each;
     const int n_groups = EPI == EPI_SILU_PAIR ? ms.rows_each : (total_rows + R - 1) / R;
-    note_kernel("k_matvec_v2<%d, %d, %d, %d, %d>", T, NU, R, EPI == EPI_SILU_PAIR && pro != PRO_NONE ? (int)PRO_RMS : pro, (int)EPI);
+    if (pro == PRO_NONE) note_kernel("k_matvec_v2<%d, %d, %d, 0, %d, false>", T, NU, R, (int)EPI);
     if (pro == PRO_NONE) {
         // EPI_REF: the block chain is a dependent sequence per wave (DPP move + fma per block): as many waves per SIMD as the registers admit, not the stream-optimal 8 per CU
         int n_waves = std::min(n_groups, g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(n_groups, mv_max_wpc<NU>())));
@@ -740,11 +763,11 @@ static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs 
     const int K = ms.w0.cols;
     const size_t lds = mv_prologue_lds(K);
     if constexpr (EPI == EPI_SILU_PAIR) {   // w1|w3 follow the ffn norm: only that prologue is instantiated for the pair epilogue
-        hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO_RMS, EPI>), grid, block, lds, s, ms, A, pa, n_groups, n_waves);
+        launch_v2_pro<T, NU, R, PRO_RMS, EPI>(issue_bar, grid, block, lds, s, ms, A, pa, n_groups, n_waves);
     } else switch (pro) {
-    case PRO_RMS: hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO_RMS, EPI>), grid, block, lds, s, ms, A, pa, n_groups, n_waves); break;
-    case PRO_PLAIN: hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO_PLAIN, EPI>), grid, block, lds, s, ms, A, pa, n_groups, n_waves); break;
-    default: if constexpr (EPI == EPI_STORE) hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO_SILU, EPI>), grid, block, lds, s, ms, A, pa, n_groups, n_waves); break;
+    case PRO_RMS: launch_v2_pro<T, NU, R, PRO_RMS, EPI>(issue_bar, grid, block, lds, s, ms, A, pa, n_groups, n_waves); break;
+    case PRO_PLAIN: launch_v2_pro<T, NU, R, PRO_PLAIN, EPI>(issue_bar, grid, block, lds, s, ms, A, pa, n_groups, n_waves); break;
+    default: { if constexpr (EPI == EPI_STORE) launch_v2_pro<T, NU, R, PRO_SILU, EPI>(issue_bar, grid, block, lds, s, ms, A, pa, n_groups, n_waves); } break;
     }
 }
 #ifndef MG4_R_NU3
@@ -756,59 +779,59 @@ static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs 
 // Q8_0 / F16 (16-byte units of 16 / 8 weights): a row needs more units per lane than the 32-weight types, and only a few unit counts are instantiated -- a row takes the
 // smallest one that covers it (the surplus units are masked like any ragged tail).  Q8_0: K <= 1024 | 4096 | 5120 | 11264; F16: K <= 512 | 1024 | 4096 | 5120.
 template <int T>
-static bool launch_v2_narrow(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, hipStream_t s) {
+static bool launch_v2_narrow(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, bool issue_bar, hipStream_t s) {
     if (epi != EPI_STORE) return false;
     const int nu = (ms.w0.cols / TrMV<T>::EPU + 63) / 64;
     if constexpr (T == GT_Q8_0) {
-        if (nu <= 1) launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, s);
-        else if (nu <= 4) launch_v2_t<T, 4, 1, EPI_STORE>(ms, A, pro, pa, s);
-        else if (nu <= 5) launch_v2_t<T, 5, 1, EPI_STORE>(ms, A, pro, pa, s);
-        else if (nu <= 11) launch_v2_t<T, 11, 1, EPI_STORE>(ms, A, pro, pa, s);
+        if (nu <= 1) launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
+        else if (nu <= 4) launch_v2_t<T, 4, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
+        else if (nu <= 5) launch_v2_t<T, 5, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
+        else if (nu <= 11) launch_v2_t<T, 11, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
         else return false;
     } else {
-        if (nu <= 1) launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, s);
-        else if (nu <= 2) launch_v2_t<T, 2, 1, EPI_STORE>(ms, A, pro, pa, s);
-        else if (nu <= 8) launch_v2_t<T, 8, 1, EPI_STORE>(ms, A, pro, pa, s);
-        else if (nu <= 10) launch_v2_t<T, 10, 1, EPI_STORE>(ms, A, pro, pa, s);
+        if (nu <= 1) launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
+        else if (nu <= 2) launch_v2_t<T, 2, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
+        else if (nu <= 8) launch_v2_t<T, 8, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
+        else if (nu <= 10) launch_v2_t<T, 10, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
         else return false;
     }
     return true;
 }
 template <int T>
-static bool launch_v2_type(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, hipStream_t s) {
+static bool launch_v2_type(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, bool issue_bar, hipStream_t s) {
     const int U = ms.w0.cols / Tr<T>::EPU;
     const int nu = (U + 63) / 64;
     bool ok = true;
     if (epi == EPI_SILU_PAIR) {
         if (ms.n != 2 || (pro != PRO_NONE && pro != PRO_RMS)) ok = false;
         else switch (nu) {
-        case 1: launch_v2_t<T, 1, 2, EPI_SILU_PAIR>(ms, A, pro, pa, s); break;
-        case 2: launch_v2_t<T, 2, 2, EPI_SILU_PAIR>(ms, A, pro, pa, s); break;
-        case 3: launch_v2_t<T, 3, 2, EPI_SILU_PAIR>(ms, A, pro, pa, s); break;
+        case 1: launch_v2_t<T, 1, 2, EPI_SILU_PAIR>(ms, A, pro, pa, issue_bar, s); break;
+        case 2: launch_v2_t<T, 2, 2, EPI_SILU_PAIR>(ms, A, pro, pa, issue_bar, s); break;
+        case 3: launch_v2_t<T, 3, 2, EPI_SILU_PAIR>(ms, A, pro, pa, issue_bar, s); break;
         default: ok = false;
         }
     } else if (epi == EPI_REF) {   // parity mode: the k-quants of the headline files (other types: k_mul_mat_ref_row); no SiLU prologue (the row comes from k_silu_mul_quant)
         if constexpr (T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K) {
             if (pro == PRO_SILU) return false;
             switch (nu) {
-            case 1: launch_v2_t<T, 1, 1, EPI_REF>(ms, A, pro, pa, s); break;
-            case 2: launch_v2_t<T, 2, 1, EPI_REF>(ms, A, pro, pa, s); break;
-            case 3: launch_v2_t<T, 3, 1, EPI_REF>(ms, A, pro, pa, s); break;
-            case 4: launch_v2_t<T, 4, 1, EPI_REF>(ms, A, pro, pa, s); break;
-            case 5: launch_v2_t<T, 5, 1, EPI_REF>(ms, A, pro, pa, s); break;
-            case 6: launch_v2_t<T, 6, 1, EPI_REF>(ms, A, pro, pa, s); break;
-            case 7: launch_v2_t<T, 7, 1, EPI_REF>(ms, A, pro, pa, s); break;
+            case 1: launch_v2_t<T, 1, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
+            case 2: launch_v2_t<T, 2, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
+            case 3: launch_v2_t<T, 3, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
+            case 4: launch_v2_t<T, 4, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
+            case 5: launch_v2_t<T, 5, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
+            case 6: launch_v2_t<T, 6, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
+            case 7: launch_v2_t<T, 7, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
             default: ok = false;
             }
         } else ok = false;
     } else switch (nu) {
-    case 1: launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, s); break;
-    case 2: launch_v2_t<T, 2, MG4_R_NU2, EPI_STORE>(ms, A, pro, pa, s); break;
-    case 3: launch_v2_t<T, 3, MG4_R_NU3, EPI_STORE>(ms, A, pro, pa, s); break;
-    case 4: launch_v2_t<T, 4, 1, EPI_STORE>(ms, A, pro, pa, s); break;
-    case 5: launch_v2_t<T, 5, 1, EPI_STORE>(ms, A, pro, pa, s); break;
-    case 6: launch_v2_t<T, 6, 1, EPI_STORE>(ms, A, pro, pa, s); break;
-    case 7: launch_v2_t<T, 7, 1, EPI_STORE>(ms, A, pro, pa, s); break;
+    case 1: launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
+    case 2: launch_v2_t<T, 2, MG4_R_NU2, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
+    case 3: launch_v2_t<T, 3, MG4_R_NU3, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
+    case 4: launch_v2_t<T, 4, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
+    case 5: launch_v2_t<T, 5, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
+    case 6: launch_v2_t<T, 6, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
+    case 7: launch_v2_t<T, 7, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
     default: ok = false;
     }
     return ok;
@@ -850,7 +873,7 @@ static bool fill_matset(MatSet &ms, const QWeight *const *W, float *const *y, co
     return true;
 }
 template <int T1, int T2, int NU, int EPI = EPI_STORE>
-static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int pro, const ProArgs &pa, hipStream_t s) {
+static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
     const int ng1 = m1.n * m1.rows_each, ng2 = m2.n * m2.rows_each;
     // split the workgroups so that the busiest wave of either set finishes earliest: cost = rows per wave x bytes per row
     const double bpr1 = bytes1 / ng1, bpr2 = bytes2 / ng2;
@@ -865,26 +888,31 @@ static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, doub
             if (c < best_cost) { best_cost = c; best_t = t; best_b1 = b1; best_total = total; }
         }
     }
-    note_kernel("k_matvec_mix<%d, %d, %d, %d, %d>", T1, T2, NU, pro == PRO_NONE ? 0 : 1, (int)EPI);
+    constexpr bool BUILT = mv_issue_bar_built<T1, NU, EPI>() && mv_issue_bar_built<T2, NU, EPI>();
+    const bool bar = pro != PRO_NONE && issue_bar && BUILT;
+    note_kernel("k_matvec_mix<%d, %d, %d, %d, %d, %s>", T1, T2, NU, pro == PRO_NONE ? 0 : 1, (int)EPI, bar ? "true" : "false");
     const int wpb = best_t / 64, nw1 = best_b1 * wpb, nw2 = (best_total - best_b1) * wpb;
     const dim3 grid((unsigned)best_total), block((unsigned)best_t);
-    if (pro == PRO_NONE) hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_NONE, EPI>), grid, block, 0, s, m1, m2, A, pa, ng1, nw1, ng2, nw2);
-    else hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI>), grid, block, mv_prologue_lds(m1.w0.cols), s, m1, m2, A, pa, ng1, nw1, ng2, nw2);
+    if (pro == PRO_NONE) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_NONE, EPI>), grid, block, 0, s, m1, m2, A, pa, ng1, nw1, ng2, nw2); return; }
+    if constexpr (BUILT) {
+        if (bar) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI, true>), grid, block, mv_prologue_lds(m1.w0.cols), s, m1, m2, A, pa, ng1, nw1, ng2, nw2); return; }
+    }
+    hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI>), grid, block, mv_prologue_lds(m1.w0.cols), s, m1, m2, A, pa, ng1, nw1, ng2, nw2);
 }
 template <int T1, int T2, int EPI = EPI_STORE>
-static bool launch_mix_nu(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int pro, const ProArgs &pa, hipStream_t s) {
+static bool launch_mix_nu(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
     const int nu = (m1.w0.cols / 32 + 63) / 64;
     switch (nu) {
-    case 1: launch_mix_t<T1, T2, 1, EPI>(m1, m2, b1, b2, A, pro, pa, s); return true;
-    case 2: launch_mix_t<T1, T2, 2, EPI>(m1, m2, b1, b2, A, pro, pa, s); return true;
-    case 3: launch_mix_t<T1, T2, 3, EPI>(m1, m2, b1, b2, A, pro, pa, s); return true;
-    case 4: launch_mix_t<T1, T2, 4, EPI>(m1, m2, b1, b2, A, pro, pa, s); return true;
+    case 1: launch_mix_t<T1, T2, 1, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
+    case 2: launch_mix_t<T1, T2, 2, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
+    case 3: launch_mix_t<T1, T2, 3, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
+    case 4: launch_mix_t<T1, T2, 4, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
     default: return false;
     }
 }
 // Decode mat-vec over two sets of different k-quant types with the same K (wq|wk + wv of a "more bits" layer) in ONE launch.  pro: PRO_NONE or PRO_RMS.
 bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, hipStream_t s, int pro,
-                         const float *px, const float *pw, int epi) {
+                         const float *px, const float *pw, int epi, bool issue_bar) {
     if (pro != PRO_NONE && pro != PRO_RMS) return false;
     if (W1[0]->cols != W2[0]->cols || W1[0]->cols % 256) return false;
     MatSet m1, m2;
@@ -895,12 +923,12 @@ bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, con
     for (int i = 0; i < n2; i++) b2 += (double)W2[i]->bytes;
     const int t1 = W1[0]->type, t2 = W2[0]->type;
     if (epi == EPI_REF) {
-        if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q5_K, GT_Q6_K, EPI_REF>(m1, m2, b1, b2, A, pro, pa, s);
-        if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q4_K, GT_Q6_K, EPI_REF>(m1, m2, b1, b2, A, pro, pa, s);
+        if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q5_K, GT_Q6_K, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
+        if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q4_K, GT_Q6_K, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
         return false;
     }
-    if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q5_K, GT_Q6_K>(m1, m2, b1, b2, A, pro, pa, s);
-    if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q4_K, GT_Q6_K>(m1, m2, b1, b2, A, pro, pa, s);
+    if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q5_K, GT_Q6_K>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
+    if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q4_K, GT_Q6_K>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
     return false;
 }
 bool matvec_prologue_supported(int type, int cols) {
@@ -912,20 +940,20 @@ bool matvec_prologue_supported(int type, int cols) {
 void set_matvec_tuning(int waves_per_cu, int fat_threads, int cus) { g_mv_force_waves = std::max(0, waves_per_cu); g_mv_force_fat = std::max(0, fat_threads); if (cus > 0) { g_mv_cus = cus; g_ref_cus = cus; } }
 // Decode (N = 1) mat-vec over 1..3 same-type, same-shape, equally spaced matrices.  Returns false when the set is outside the v2 kernel's range.
 bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, hipStream_t s, int pro, const float *px, const float *pw,
-                       const Tables *tb, int epi) {
+                       const Tables *tb, int epi, bool issue_bar) {
     ProArgs pa{}; pa.x = px; pa.w = pw; if (tb) pa.tb = *tb;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
     switch (W[0]->type) {
-    case GT_Q4_0: return launch_v2_type<GT_Q4_0>(ms, A, pro, pa, epi, s);
-    case GT_Q4_1: return launch_v2_type<GT_Q4_1>(ms, A, pro, pa, epi, s);
-    case GT_Q5_0: return launch_v2_type<GT_Q5_0>(ms, A, pro, pa, epi, s);
-    case GT_Q5_1: return launch_v2_type<GT_Q5_1>(ms, A, pro, pa, epi, s);
-    case GT_Q4_K: return launch_v2_type<GT_Q4_K>(ms, A, pro, pa, epi, s);
-    case GT_Q5_K: return launch_v2_type<GT_Q5_K>(ms, A, pro, pa, epi, s);
-    case GT_Q6_K: return launch_v2_type<GT_Q6_K>(ms, A, pro, pa, epi, s);
-    case GT_Q8_0: return launch_v2_narrow<GT_Q8_0>(ms, A, pro, pa, epi, s);
-    case GT_F16: return launch_v2_narrow<GT_F16>(ms, A, pro, pa, epi, s);
+    case GT_Q4_0: return launch_v2_type<GT_Q4_0>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q4_1: return launch_v2_type<GT_Q4_1>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q5_0: return launch_v2_type<GT_Q5_0>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q5_1: return launch_v2_type<GT_Q5_1>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q4_K: return launch_v2_type<GT_Q4_K>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q5_K: return launch_v2_type<GT_Q5_K>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q6_K: return launch_v2_type<GT_Q6_K>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_Q8_0: return launch_v2_narrow<GT_Q8_0>(ms, A, pro, pa, epi, issue_bar, s);
+    case GT_F16: return launch_v2_narrow<GT_F16>(ms, A, pro, pa, epi, issue_bar, s);
     default: return false;   // F32 rows, and Q8_0 / F16 rows wider than launch_v2_narrow's instantiations: served by k_mul_mat
     }
 }

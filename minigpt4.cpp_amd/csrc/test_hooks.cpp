@@ -154,7 +154,7 @@ int minigpt4_amd_test_mmq2(int ggml_type, const void *raw_w, int n_mat, int64_t 
 // mixed-type launch), activation preparation either standalone (fuse = 0) or in the kernel prologue, optional residual, optional SiLU row-pair
 // epilogue.  prep: 1 = rms_norm(x) * x2, 2 = x, 3 = silu(x) * x2.  y: (n1 + n2) * n_out floats (epi = 1: n_out floats).
 static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
-                            int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y);
+                            int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y, bool issue_bar = false, int guard = 0);
 int minigpt4_amd_test_matvec(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
                              int fuse, int epi, const float *residual, float *y) {
     return test_matvec_impl(type1, raw1, n1, type2, raw2, n2, n_in, n_out, x, x2, prep, fuse, epi, residual, host_silu_table().data(), y);
@@ -166,8 +166,16 @@ int minigpt4_amd_test_matvec_ex(int type1, const void *raw1, int n1, int type2, 
     if (!silu_table && ((fuse && prep == 3) || epi == 1)) { set_last_error("the fused SiLU prologue / pair epilogue of the decode mat-vec need a table"); return 1; }
     return test_matvec_impl(type1, raw1, n1, type2, raw2, n2, n_in, n_out, x, x2, prep, fuse, epi, residual, silu_table, y);
 }
+// ONE prologue launch (the preparation fused, as the decode step issues it) with or without the issue barrier.  y: the outputs followed by `guard` floats behind them,
+// which the launch must leave at the 0xFF bytes they were filled with.
+int minigpt4_amd_test_matvec_issue(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
+                                   int epi, const float *residual, int issue_barrier, int guard, float *y) {
+    if (guard < 0 || guard > (1 << 20)) return 1;
+    return test_matvec_impl(type1, raw1, n1, type2, raw2, n2, n_in, n_out, x, x2, prep, 1, epi, residual, host_silu_table().data(), y, issue_barrier != 0, guard);
+}
+int minigpt4_amd_test_matvec_waves(void) { return matvec_prologue_waves(); }
 static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
-                            int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y) {
+                            int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y, bool issue_bar, int guard) {
     if (!raw1 || !x || !y || n_in <= 0 || n_out <= 0 || n1 < 1 || n1 > 3 || n2 < 0 || n2 > 1 || prep < 1 || prep > 3 || (prep != 2 && !x2)) return 1;
     if (!qweight_supported(type1) || n_in % gt_block(type1) || (n2 && (!raw2 || !qweight_supported(type2) || n_in % gt_block(type2)))) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
@@ -188,11 +196,11 @@ static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, cons
         };
         upload(type1, raw1, n1, W.data());
         if (n2) upload(type2, raw2, n2, W.data() + n1);
-        DevBuf d_x((size_t)K * 4), d_x2((size_t)K * 4), d_y((size_t)nt * R * 4), d_res((size_t)nt * R * 4), d_tab(65536 * 2);
+        DevBuf d_x((size_t)K * 4), d_x2((size_t)K * 4), d_y(((size_t)nt * R + (size_t)guard) * 4), d_res((size_t)nt * R * 4), d_tab(65536 * 2);
         HIP_CHECK(hipMemcpy(d_x.p, x, (size_t)K * 4, hipMemcpyHostToDevice));
         if (x2) HIP_CHECK(hipMemcpy(d_x2.p, x2, (size_t)K * 4, hipMemcpyHostToDevice));
         if (residual) HIP_CHECK(hipMemcpy(d_res.p, residual, (size_t)nt * R * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemset(d_y.p, 0xFF, (size_t)nt * R * 4));
+        HIP_CHECK(hipMemset(d_y.p, 0xFF, ((size_t)nt * R + (size_t)guard) * 4));
         Tables tb;
         if (silu_table) { HIP_CHECK(hipMemcpy(d_tab.p, silu_table, 131072, hipMemcpyHostToDevice)); tb.silu = d_tab.as<__half>(); }
         ActQ A; alloc_act(A, keep, 1, (size_t)K);
@@ -204,11 +212,11 @@ static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, cons
         const QWeight *Wp[4]; float *Yp[4]; const float *Rp[4];
         for (int m = 0; m < nt; m++) { Wp[m] = &W[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * R; Rp[m] = d_res.as<float>() + (size_t)m * R; }
         bool ok;
-        if (n2) ok = launch_matvec_mixed(Wp, Yp, n1, Wp + n1, Yp + n1, n2, A, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), epi);
-        else ok = launch_matvec_set(Wp, Yp, residual ? Rp : nullptr, n1, A, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), &tb, epi);
+        if (n2) ok = launch_matvec_mixed(Wp, Yp, n1, Wp + n1, Yp + n1, n2, A, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), epi, issue_bar);
+        else ok = launch_matvec_set(Wp, Yp, residual ? Rp : nullptr, n1, A, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), &tb, epi, issue_bar);
         if (!ok) { set_last_error("shape / type outside the decode mat-vec kernel's range"); return 4; }
         HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(y, d_y.p, (size_t)(epi == 1 ? 1 : nt) * R * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(y, d_y.p, ((size_t)(epi == 1 ? 1 : nt) * R + (size_t)guard) * 4, hipMemcpyDeviceToHost));
         return 0;
     });
 }
@@ -1259,13 +1267,15 @@ int minigpt4_amd_bench_matvec(int ggml_type, int rows, int cols, int n_mat, int 
         DevBuf dx((size_t)NR * cols * 4), dy((size_t)rows * 4 * 3 * NR);
         { std::vector<float> hx((size_t)NR * cols); for (size_t i = 0; i < hx.size(); i++) hx[i] = (float)((int)(i * 37 % 201) - 100) / 64.0f; HIP_CHECK(hipMemcpy(dx.p, hx.data(), hx.size() * 4, hipMemcpyHostToDevice)); }
         launch_rms_quant(dx.as<float>(), nullptr, NR, cols, A, act_mask_for(ggml_type), nullptr);
+        const bool issue_bar = getenv("MG4_MV_IB") && atoi(getenv("MG4_MV_IB")) != 0;   // issue barrier of the prologue variants (2, 7)
         auto run = [&](int set) {
             const QWeight *Wp[3]; float *Yp[3];
             for (int m = 0; m < n_mat; m++) { Wp[m] = &W[(size_t)set * n_mat + m]; Yp[m] = dy.as<float>() + (size_t)m * rows * NR; }
+            if (variant == 7 && launch_matvec_set(Wp, Yp, Yp, n_mat, A, nullptr, 2, dx.as<float>(), nullptr, nullptr, 0, issue_bar)) return;   // plain prologue + residual in place, as the decode's wo launch
             if (variant == 1 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, nullptr)) return;
             if ((variant == 3 || variant == 4 || (variant > 10 && variant <= 14)) && launch_matvec_rows(Wp, Yp, nullptr, n_mat, A, NR, rows, nullptr)) return;
             if ((variant == 5 || variant == 6 || (variant > 20 && variant <= 24)) && launch_matvec_rows(Wp, Yp, nullptr, n_mat, A, NR, rows, nullptr, dx.as<float>(), dx.as<float>(), cols)) return;
-            if (variant == 2 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, nullptr, 1, dx.as<float>(), dx.as<float>())) return;   // rms-norm prologue, as the decode's qkv / w1|w3 launches
+            if (variant == 2 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, nullptr, 1, dx.as<float>(), dx.as<float>(), nullptr, 0, issue_bar)) return;   // rms-norm prologue, as the decode's qkv / w1|w3 launches
             for (int m = 0; m < n_mat; m++) launch_mul_mat(*Wp[m], A, 1, Yp[m], rows, nullptr, nullptr);
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) run(i);

@@ -234,6 +234,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_mmq2.argtypes = [I32, VOID_PTR, I32, ctypes.c_int64, ctypes.c_int64, FLOAT_PTR, ctypes.c_int64, FLOAT_PTR, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_matvec.argtypes = [I32, VOID_PTR, I32, I32, VOID_PTR, I32, ctypes.c_int64, ctypes.c_int64, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_matvec_rows.argtypes = [I32, VOID_PTR, I32, ctypes.c_int64, ctypes.c_int64, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_matvec_issue.argtypes = L.minigpt4_amd_test_matvec.argtypes[:11] + [I32, FLOAT_PTR, I32, I32, FLOAT_PTR]
+        L.minigpt4_amd_test_matvec_waves.argtypes = []
         L.minigpt4_amd_test_quantize.argtypes = [FLOAT_PTR, FLOAT_PTR, ctypes.c_int64, ctypes.c_int64, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_test_gemm_f16.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_gemm_f16_skinny.argtypes = L.minigpt4_amd_test_gemm_f16.argtypes
@@ -995,6 +997,29 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_matvec rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
         return y
+
+    def amd_test_matvec_issue(self, type1: int, raw1: np.ndarray, n1: int, n_in: int, n_out: int, x: np.ndarray, x2: Optional[np.ndarray] = None, prep: int = 1, epi: int = 0,
+                              residual: Optional[np.ndarray] = None, type2: int = 0, raw2: Optional[np.ndarray] = None, issue_barrier: bool = False, guard: int = 0):
+        """ONE prologue launch of the decode mat-vec (preparation `prep` fused) with or without the issue barrier (csrc/llm_kernels.hip: IB).  Returns (y, guard):
+        y as amd_test_matvec, guard = the `guard` floats behind the outputs as uint32 bit patterns (0xFFFFFFFF where the launch left them alone)."""
+        x = np.ascontiguousarray(x, np.float32).reshape(n_in)
+        x2c = None if x2 is None else np.ascontiguousarray(x2, np.float32).reshape(n_in)
+        raw1 = np.ascontiguousarray(raw1)
+        n2 = 0 if raw2 is None else 1
+        raw2c = None if raw2 is None else np.ascontiguousarray(raw2)
+        res = None if residual is None else np.ascontiguousarray(residual, np.float32).reshape(-1)
+        rows = 1 if epi == 1 else n1 + n2
+        buf = np.empty(rows * n_out + guard, np.float32)
+        rc = self.library.minigpt4_amd_test_matvec_issue(type1, raw1.ctypes.data_as(VOID_PTR), n1, type2, None if raw2c is None else raw2c.ctypes.data_as(VOID_PTR), n2, n_in, n_out,
+                                                         x.ctypes.data_as(FLOAT_PTR), None if x2c is None else x2c.ctypes.data_as(FLOAT_PTR), prep, epi,
+                                                         None if res is None else res.ctypes.data_as(FLOAT_PTR), int(issue_barrier), int(guard), buf.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_matvec_issue rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
+        return buf[:rows * n_out].reshape(rows, n_out).copy(), buf[rows * n_out:].view(np.uint32).copy()
+
+    def amd_test_matvec_waves(self) -> int:
+        """Waves of a prologue mat-vec launch that fills the device: wave w owns row groups w, w + waves, ..."""
+        return int(self.library.minigpt4_amd_test_matvec_waves())
 
     def amd_test_matvec_rows(self, ggml_type: int, raw_w: np.ndarray, n_mat: int, n_in: int, n_out: int, x: np.ndarray, residual: Optional[np.ndarray] = None) -> np.ndarray:
         """The batched-decode mat-vec: x [N][n_in] (N <= 4) against n_mat matrices in one weight pass -> [n_mat][N][n_out]."""
