@@ -41,6 +41,13 @@ MINIGPT4_API int minigpt4_amd_test_matvec_waves(void);   /* waves of a prologue 
 /* The batched-decode mat-vec: N = 1..4 activation rows x[N][n_in] against n_mat (1..3) equally spaced matrices in one weight pass; y / residual: [n_mat][N][n_out].
  * Returns 4 when the shape / type is outside the kernel's range. */
 MINIGPT4_API int minigpt4_amd_test_matvec_rows(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, float *y);
+/* The same launch with the rows' preparation chosen: prepare = 0 -- a launch of its own in front (rms_w non-null: rms_norm(x_t) * rms_w there); prepare = 1 -- inside the
+   mat-vec launch (rms_w non-null: the norm form, NULL: the rows as they are).  Returns 4 when the kernel has no such form for the type / n_in. */
+MINIGPT4_API int minigpt4_amd_test_matvec_rows_prep(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual,
+                                                    const float *rms_w, int prepare, float *y);
+/* Host only: which in-launch preparations the decode mat-vec offers for (type, n_in).  bit 0: the single-row prologue (prep 1 / 2 / 3 of minigpt4_amd_test_matvec with
+   fuse = 1), bit 1: the SiLU row-pair epilogue, bit 2: the multi-row prologue (prepare = 1 above).  -1: bad arguments. */
+MINIGPT4_API int minigpt4_amd_test_matvec_predicates(int ggml_type, int64_t n_in);
 /* Activation quantisation (optionally after rms_norm with weight w): returns Q8_K and Q8_0 images of x[N][K].
  * q8k: int8[N*K], dk: float[N*K/256], bsums: int16[N*K/16], q80: int8[N*K], d0: float[N*K/32] (fp16-rounded). Any may be NULL. */
 MINIGPT4_API int minigpt4_amd_test_quantize(const float *x, const float *rms_w, int64_t N, int64_t K, int8_t *q8k, float *dk, int16_t *bsums, int8_t *q80, float *d0);

@@ -68,6 +68,7 @@ static inline void launch_k(void (*k)(KA...), dim3 g, dim3 b, size_t lds, hipStr
 
 }  // namespace mg4
 #include "qtraits.hpp"
+#include "row_prep.hpp"
 namespace mg4 {
 
 // =====================================================================================================================
@@ -233,6 +234,88 @@ static void launch_mul_mat_t(const QWeight &W, const ActQ &A, int N, float *y, i
     }
 }
 // =====================================================================================================================
+// What is instantiated.  A lane of a decode mat-vec owns NU units of a row (u = lane + 64 i), and every form of the kernel family is built for the unit counts stated
+// here and nowhere else: the launchers dispatch on these lists (mv_for_units), and the predicates the engine asks before it fuses a row preparation into a launch are
+// computed from them (below), so a shape a predicate accepts is a shape the launcher has.
+// =====================================================================================================================
+enum EpiKind : int { EPI_STORE = 0, EPI_SILU_PAIR = 1, EPI_REF = 2 };   // EPI_REF (MINIGPT4_PARITY): store, every fp32 accumulation in the CPU oracle's order (ref_chain; the rms sum = the oracle's value)
+#ifndef MG4_R_NU3
+#define MG4_R_NU3 1
+#endif
+#ifndef MG4_R_NU2
+#define MG4_R_NU2 1
+#endif
+template <int... NU> struct UnitList {};
+using Units1to7 = UnitList<1, 2, 3, 4, 5, 6, 7>;
+using Units1to3 = UnitList<1, 2, 3>;
+template <int T> constexpr bool tr_is_kquant() { return T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K; }
+template <int T> constexpr bool tr_is_q32() { return T == GT_Q4_0 || T == GT_Q4_1 || T == GT_Q5_0 || T == GT_Q5_1; }
+template <int T> constexpr bool tr_is_narrow() { return T == GT_Q8_0 || T == GT_F16; }   // 16-byte units of 16 / 8 weights: more units per row than the 32-weight types
+// k_matvec_v2<T, NU, R, PRO, EPI>.  Q8_0 / F16: only a few unit counts, a row takes the smallest one that covers it (the surplus units are masked like any ragged
+// tail) -- Q8_0: K <= 1024 | 4096 | 5120 | 11264; F16: K <= 512 | 1024 | 4096 | 5120.  Pair epilogue (w1|w3): K <= 6144.  EPI_REF: the k-quants of the headline files
+// (other types: k_mul_mat_ref_row).
+template <int T, int EPI> constexpr auto mv_units() {
+    if constexpr (T == GT_Q8_0) return std::conditional_t<EPI == EPI_STORE, UnitList<1, 4, 5, 11>, UnitList<>>{};
+    else if constexpr (T == GT_F16) return std::conditional_t<EPI == EPI_STORE, UnitList<1, 2, 8, 10>, UnitList<>>{};
+    else if constexpr (tr_is_kquant<T>()) return std::conditional_t<EPI == EPI_SILU_PAIR, Units1to3, Units1to7>{};
+    else if constexpr (tr_is_q32<T>()) return std::conditional_t<EPI == EPI_SILU_PAIR, Units1to3, std::conditional_t<EPI == EPI_STORE, Units1to7, UnitList<>>>{};
+    else return UnitList<>{};
+}
+template <int T, int NU, int EPI> constexpr int mv_rows_per_group() {   // R: rows a wave has in flight per stage
+    if (EPI == EPI_SILU_PAIR) return 2;
+    if (EPI == EPI_REF) return 1;
+    if (NU == 1) return 2;
+    return tr_is_narrow<T>() ? 1 : NU == 2 ? MG4_R_NU2 : NU == 3 ? MG4_R_NU3 : 1;
+}
+using MixUnits = UnitList<1, 2, 3, 4>;          // k_matvec_mix<T1, T2, NU, ..>
+// k_matvec_tn<T, NU, TN, PRO> (TN = 2..4 rows): every unit count without a preparation, K <= 6144 of Q4_0 and the k-quants with one; k_matvec_tn_mix: K <= 6144
+template <int T> constexpr auto mv_tn_units() { return std::conditional_t<tr_is_kquant<T>() || tr_is_q32<T>(), Units1to7, UnitList<>>{}; }
+template <int T> constexpr auto mv_tn_pro_units() { return std::conditional_t<T == GT_Q4_0 || tr_is_kquant<T>(), Units1to3, UnitList<>>{}; }
+using TnMixUnits = Units1to3;
+using RefRowUnits = UnitList<1, 2, 3, 4, 6, 7>;  // k_mul_mat_ref_row / k_mul_mat_ref_rows (the 7B / 13B widths)
+
+template <int... NU> constexpr bool units_have(UnitList<NU...>, int nu) { return ((nu == NU) || ...); }
+template <int... NU> constexpr int units_max(UnitList<NU...>) { int m = 0; ((m = NU > m ? NU : m), ...); return m; }
+// f(integral_constant<NU>) for the list's entry that equals nu (COVER: the first that covers it); false: no such entry, nothing was called
+template <bool COVER = false, int... NU, class F> static bool mv_for_units(UnitList<NU...>, int nu, F &&f) {
+    return (((COVER ? nu <= NU : nu == NU) ? (f(std::integral_constant<int, NU>{}), true) : false) || ...);
+}
+template <class F> static void mv_for_rows(int N, F &&f) {   // TN of N = 1..4 rows: the kernels are vector-issue bound, an unused row costs its share
+    if (N <= 2) f(std::integral_constant<int, 2>{}); else if (N == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 4>{});
+}
+// f(integral_constant<type>) -> bool for a repacked weight type; false: no such type
+template <class F> static bool for_weight_type(int type, F &&f) {
+    switch (type) {
+    case GT_Q4_0: return f(std::integral_constant<int, GT_Q4_0>{});
+    case GT_Q4_1: return f(std::integral_constant<int, GT_Q4_1>{});
+    case GT_Q5_0: return f(std::integral_constant<int, GT_Q5_0>{});
+    case GT_Q5_1: return f(std::integral_constant<int, GT_Q5_1>{});
+    case GT_Q8_0: return f(std::integral_constant<int, GT_Q8_0>{});
+    case GT_Q2_K: return f(std::integral_constant<int, GT_Q2_K>{});
+    case GT_Q4_K: return f(std::integral_constant<int, GT_Q4_K>{});
+    case GT_Q5_K: return f(std::integral_constant<int, GT_Q5_K>{});
+    case GT_Q6_K: return f(std::integral_constant<int, GT_Q6_K>{});
+    case GT_F16: return f(std::integral_constant<int, GT_F16>{});
+    case GT_F32: return f(std::integral_constant<int, GT_F32>{});
+    default: return false;
+    }
+}
+// the two-type launches: wq|wk + wv of llama.cpp's "more bits" k-quant mixes
+template <class F> static bool for_mixed_types(int t1, int t2, F &&f) {
+    if (t1 == GT_Q5_K && t2 == GT_Q6_K) return f(std::integral_constant<int, GT_Q5_K>{}, std::integral_constant<int, GT_Q6_K>{});
+    if (t1 == GT_Q4_K && t2 == GT_Q6_K) return f(std::integral_constant<int, GT_Q4_K>{}, std::integral_constant<int, GT_Q6_K>{});
+    return false;
+}
+// Largest K of a unit list for a type, 0: none.  A row is a whole number of the type's blocks (F16: of 16-byte units).
+template <class L> static bool mv_covers(L list, int type, int K) {
+    const int epu = type == GT_F16 ? 8 : type == GT_Q8_0 ? 16 : 32, block = type == GT_F16 ? 8 : gt_block(type);
+    return K > 0 && K % block == 0 && K <= units_max(list) * 64 * epu;
+}
+bool matvec_prologue_supported(int type, int cols) { return for_weight_type(type, [&](auto t) { return mv_covers(mv_units<decltype(t)::value, EPI_STORE>(), type, cols); }); }
+bool matvec_silu_pair_supported(int type, int cols) { return for_weight_type(type, [&](auto t) { return mv_covers(mv_units<decltype(t)::value, EPI_SILU_PAIR>(), type, cols); }); }
+bool matvec_rows_prologue_ok(int type, int K) { return for_weight_type(type, [&](auto t) { return mv_covers(mv_tn_pro_units<decltype(t)::value>(), type, K); }); }
+
+// =====================================================================================================================
 // MINIGPT4_PARITY=1 -- the oracle's fp32 ORDER (oracle/refcpu.c vec_dot_*: one sequential chain of fma's per output, block after block).  One wave per
 // (row, token): the lanes split the row's units exactly like k_mul_mat and use the same unit traits (same loads, same integer dot products), but the integer parts are
 // first combined per ggml block (8 units per k-quant super-block, 2 per Q8_0 block: exact), and the per-block fp32 terms are then added by every lane in block order.
@@ -361,31 +444,17 @@ template <int T> static bool launch_mul_mat_ref_row_t(const RefSet &S, const Act
     const int blocks = std::max(1, std::min((S.w[0].rows + 3) / 4, g_ref_cus * 4 / S.n));
     const dim3 grid((unsigned)blocks, (unsigned)S.n);
     note_kernel("k_mul_mat_ref_row<%d, %d>", T, nu);
-    switch (nu) {
-    case 1: hipLaunchKernelGGL((k_mul_mat_ref_row<T, 1>), grid, dim3(256), 0, s, S, A); return true;
-    case 2: hipLaunchKernelGGL((k_mul_mat_ref_row<T, 2>), grid, dim3(256), 0, s, S, A); return true;
-    case 3: hipLaunchKernelGGL((k_mul_mat_ref_row<T, 3>), grid, dim3(256), 0, s, S, A); return true;
-    case 4: hipLaunchKernelGGL((k_mul_mat_ref_row<T, 4>), grid, dim3(256), 0, s, S, A); return true;
-    case 6: hipLaunchKernelGGL((k_mul_mat_ref_row<T, 6>), grid, dim3(256), 0, s, S, A); return true;
-    case 7: hipLaunchKernelGGL((k_mul_mat_ref_row<T, 7>), grid, dim3(256), 0, s, S, A); return true;
-    default: return false;
-    }
+    return mv_for_units(RefRowUnits{}, nu, [&](auto n) { hipLaunchKernelGGL((k_mul_mat_ref_row<T, decltype(n)::value>), grid, dim3(256), 0, s, S, A); });
 }
 // One activation row against 1..3 equally shaped matrices of one type (parity mode's decode step); false -> shape outside this kernel, use launch_mul_mat_ref per matrix
 bool launch_mul_mat_ref_set(const QWeight *const *W, float *const *y, const float *const *res, int n, const ActQ &A, hipStream_t s) {
     if (n < 1 || n > 3) return false;
     RefSet S{}; S.n = n;
     for (int i = 0; i < n; i++) { if (W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false; S.w[i] = *W[i]; S.y[i] = y[i]; S.res[i] = res ? res[i] : nullptr; }
-    switch (W[0]->type) {
-    case GT_Q4_0: return launch_mul_mat_ref_row_t<GT_Q4_0>(S, A, s);
-    case GT_Q4_1: return launch_mul_mat_ref_row_t<GT_Q4_1>(S, A, s);
-    case GT_Q5_0: return launch_mul_mat_ref_row_t<GT_Q5_0>(S, A, s);
-    case GT_Q5_1: return launch_mul_mat_ref_row_t<GT_Q5_1>(S, A, s);
-    case GT_Q4_K: return launch_mul_mat_ref_row_t<GT_Q4_K>(S, A, s);
-    case GT_Q5_K: return launch_mul_mat_ref_row_t<GT_Q5_K>(S, A, s);
-    case GT_Q6_K: return launch_mul_mat_ref_row_t<GT_Q6_K>(S, A, s);
-    default: return false;                       // (Q8_0 / Q2_K / F16 / F32 rows have other unit widths: the generic kernel serves them)
-    }
+    return for_weight_type(W[0]->type, [&](auto t) {   // (Q8_0 / Q2_K / F16 / F32 rows have other unit widths: the generic kernel serves them)
+        constexpr int T = decltype(t)::value;
+        if constexpr (tr_is_q32<T>() || tr_is_kquant<T>()) return launch_mul_mat_ref_row_t<T>(S, A, s); else return false;
+    });
 }
 // Prompt rows in parity mode: one wave per WEIGHT row (persistent over rows wave, wave + n_waves, ...), the row's units in registers for all N activation rows -- the
 // generic kernel above re-reads the weights once per (output, activation row).  The chain per (row, activation row) is ref_chain's: bit-identical to k_mul_mat_ref.
@@ -425,45 +494,19 @@ template <int T> static bool launch_mul_mat_ref_rows_t(const QWeight &W, const A
     const int U = W.cols / Tr<T>::EPU, nu = (U + 63) / 64;
     const dim3 grid((unsigned)std::max(1, std::min((W.rows + 3) / 4, g_ref_cus * 4)));
     note_kernel("k_mul_mat_ref_rows<%d, %d>", T, nu);
-    switch (nu) {
-    case 1: hipLaunchKernelGGL((k_mul_mat_ref_rows<T, 1>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); return true;
-    case 2: hipLaunchKernelGGL((k_mul_mat_ref_rows<T, 2>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); return true;
-    case 3: hipLaunchKernelGGL((k_mul_mat_ref_rows<T, 3>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); return true;
-    case 4: hipLaunchKernelGGL((k_mul_mat_ref_rows<T, 4>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); return true;
-    case 6: hipLaunchKernelGGL((k_mul_mat_ref_rows<T, 6>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); return true;
-    case 7: hipLaunchKernelGGL((k_mul_mat_ref_rows<T, 7>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); return true;
-    default: return false;
-    }
+    return mv_for_units(RefRowUnits{}, nu, [&](auto n) { hipLaunchKernelGGL((k_mul_mat_ref_rows<T, decltype(n)::value>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); });
 }
 template <int T> static void launch_mul_mat_ref_t(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s) {
     note_kernel("k_mul_mat_ref<%d>", T);
     hipLaunchKernelGGL((k_mul_mat_ref<T>), dim3((unsigned)((W.rows + 3) / 4), (unsigned)N), dim3(256), 0, s, W, A, N, y, ldy, residual);
 }
 void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s) {
-    if (N > 1) {   // prompt rows: the weight row stays in registers for all N activation rows (k-quants; the other types and unit counts take the generic kernel)
-        bool done = false;
-        switch (W.type) {
-        case GT_Q4_K: done = launch_mul_mat_ref_rows_t<GT_Q4_K>(W, A, N, y, ldy, residual, s); break;
-        case GT_Q5_K: done = launch_mul_mat_ref_rows_t<GT_Q5_K>(W, A, N, y, ldy, residual, s); break;
-        case GT_Q6_K: done = launch_mul_mat_ref_rows_t<GT_Q6_K>(W, A, N, y, ldy, residual, s); break;
-        default: break;
-        }
-        if (done) return;
-    }
-    switch (W.type) {
-    case GT_Q4_0: launch_mul_mat_ref_t<GT_Q4_0>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q4_1: launch_mul_mat_ref_t<GT_Q4_1>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q5_0: launch_mul_mat_ref_t<GT_Q5_0>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q5_1: launch_mul_mat_ref_t<GT_Q5_1>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q8_0: launch_mul_mat_ref_t<GT_Q8_0>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q2_K: launch_mul_mat_ref_t<GT_Q2_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q4_K: launch_mul_mat_ref_t<GT_Q4_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q5_K: launch_mul_mat_ref_t<GT_Q5_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q6_K: launch_mul_mat_ref_t<GT_Q6_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_F16: launch_mul_mat_ref_t<GT_F16>(W, A, N, y, ldy, residual, s); break;
-    case GT_F32: launch_mul_mat_ref_t<GT_F32>(W, A, N, y, ldy, residual, s); break;
-    default: throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
-    }
+    // prompt rows: the weight row stays in registers for all N activation rows (k-quants; the other types and unit counts take the generic kernel)
+    if (N > 1 && for_weight_type(W.type, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            if constexpr (tr_is_kquant<T>()) return launch_mul_mat_ref_rows_t<T>(W, A, N, y, ldy, residual, s); else return false; })) return;
+    if (!for_weight_type(W.type, [&](auto t) { launch_mul_mat_ref_t<decltype(t)::value>(W, A, N, y, ldy, residual, s); return true; }))
+        throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
 }
 
 // =====================================================================================================================
@@ -475,9 +518,7 @@ void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ld
 // =====================================================================================================================
 // Activation preparation fused into the mat-vec prologue (decode): every workgroup redundantly prepares the (tiny, L2-resident) activation
 // row in LDS -- rms_norm * w | identity | silu(a) * b, then ggml's Q8_K / Q8_0 quantisation -- while its first weight loads are in flight.
-enum ProKind : int { PRO_NONE = 0, PRO_RMS = 1, PRO_PLAIN = 2, PRO_SILU = 3 };
 struct ProArgs { const float *x; const float *w; Tables tb; };   // RMS: x, norm weight; PLAIN: x; SILU: a = x, b = w
-__device__ __forceinline__ void quant_emit4(const float v[4], const bool in_range, const int idx, const size_t row, const int K, const ActQ &A, const int mask);
 
 struct MatSet {
     QWeight w0;            // matrix 0; matrix m has every plane shifted by m * dmat bytes
@@ -487,9 +528,24 @@ struct MatSet {
     int n;                 // matrices in the set
     int rows_each;         // rows of each matrix
 };
+// The weight-row fetch of a set, shared by the single-row and the multi-row kernel.  Text, not functions: behind a function boundary (also with rows_each passed in,
+// or with the selection handed back in a struct) every k_matvec_v2 / k_matvec_tn instantiation schedules its scalar address arithmetic differently.
+// MG4_MATSET_ROW: row `row` of the set's concatenated row space (wave-uniform, clamped by the caller) -> which matrix it belongs to (m1, m2), the row inside it (lr), and
+// the buffer descriptors of that weight row (B).  The matrix is selected on the operands themselves (a bool -> int conversion would be done on the vector ALU).
+// MG4_MATSET_RES: where that row's residual is read, right after the weight loads have been issued.  MG4_MATSET_M_LR: the same mapping where a result is stored.
+#define MG4_MATSET_ROW(X, ms, row, rows_each, U, B) \
+    const bool m1 = (row) >= (rows_each), m2 = (row) >= 2 * (rows_each); \
+    const int lr = (row) - (m2 ? 2 * (rows_each) : (m1 ? (rows_each) : 0)); \
+    const long long d = m2 ? 2 * (ms).dmat : (m1 ? (ms).dmat : 0ll); \
+    QWeight W = (ms).w0; \
+    W.qs += d; W.qh += d; W.sc += d; W.d += d; \
+    WBuf B; \
+    X::mkb(W, (size_t)lr * (U), B)
+#define MG4_MATSET_RES(res_base, res_stride) ((res_base) + (m2 ? 2 * (res_stride) : (m1 ? (res_stride) : 0ll)) + lr)
+#define MG4_MATSET_M_LR(row, rows_each) const int m = (row) >= 2 * (rows_each) ? 2 : ((row) >= (rows_each) ? 1 : 0), lr = (row) - m * (rows_each)
+// the residual is always loaded (from a valid address: the output when there is none) and dropped when there is none: no load of the pipeline is conditional
+__device__ __forceinline__ float load_res(const float *p) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mkbuf(reinterpret_cast<const uint8_t *>(p)), 0, 0, 0)); }
 
-// Workgroup size of the prologue variants: one fat workgroup per CU (as many waves as the register budget of NU admits), so that the redundant
-// row preparation is done once per CU instead of once per 4 waves.
 // Prologue variants run as ONE fat workgroup per CU of 8..12 waves (512..768 threads): the row preparation is repeated per workgroup, so fewer, fatter
 // workgroups repeat it less.  The kernel is compiled for the largest size its register budget admits and launched with the size whose
 // rows-per-wave division is the most even (see pick_fat_threads).
@@ -499,7 +555,6 @@ template <int NU> constexpr int mv_fat_max_threads() { return NU <= 4 ? 768 : 51
 // EPI_SILU_PAIR (w1|w3 of the feed-forward block; ms.n == 2, R == 2): group g = the row pair (w1[g], w3[g]); the wave writes
 // h[g] = silu_table(w1[g] . x) * (w3[g] . x) instead of the two dot products.  The table lookup of a group is consumed one group later, so
 // that it never stalls the weight stream.
-enum EpiKind : int { EPI_STORE = 0, EPI_SILU_PAIR = 1, EPI_REF = 2 };   // EPI_REF (MINIGPT4_PARITY): store, every fp32 accumulation in the CPU oracle's order (ref_chain; the rms sum = the oracle's value)
 // In-kernel timeline (diagnostic builds only: make EXTRA=-DMG4_TIMELINE OUT=../libminigpt4_tl.so OBJ=build_tl).  Thread 0 of every workgroup of a decode mat-vec
 // stamps the 100 MHz constant clock at: 0 entry, 1 first weight tiles requested, 2 activation row ready (prologue done), 3 first row group finished, 4 last row
 // group finished, 5 results stored.  The last launch wins; read with minigpt4_amd_timeline after a single-launch micro-benchmark (tools/timeline.py).
@@ -516,8 +571,6 @@ __device__ unsigned long long g_tla[2048 * 8];
 #define MG4_TL(i) do {} while (0)
 #define MG4_TL_ALL(i) do {} while (0)
 #endif
-// (Round 5 measured "pair packing" -- two consecutive K = 5120 rows as ONE run of 320 units over 5 lane-walks instead of 2 x 3 with 17 % of the lanes masked -- and lost:
-// 356 vs 374 tok/s on the 13B file, profiles/r05_experiments_not_adopted.md; removed again.)
 // IB (prologue forms): a raw s_barrier (no wait on data) between the row loads and the first weight requests, so that the row loads of ALL waves of the workgroup are ahead
 // of any weight request in the CU's vector-memory queue -- without it the row loads of the late waves queue behind the weight tiles of the early ones, and the row-wide
 // barriers wait for the slowest wave (row ready 3.6 -> 3.3 us, profiles/r13_matvec_prefetch_depth.log).  Requesting MORE row groups before the preparation (round 2's
@@ -544,19 +597,12 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
     auto fetch = [&](int g, Grp &G) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            // wave-uniform (scalar) row, clamped instead of branching; the matrix of the row is selected on the operands themselves (a
-            // bool -> int conversion would be done on the vector ALU)
+            // wave-uniform (scalar) row, clamped instead of branching
             const int row = EPI == EPI_SILU_PAIR ? min(g, rows_each - 1) + r * rows_each : min(g * R + r, total_rows - 1);
-            const bool m1 = row >= rows_each, m2 = row >= 2 * rows_each;
-            const int lr = row - (m2 ? 2 * rows_each : (m1 ? rows_each : 0));
-            const long long d = m2 ? 2 * ms.dmat : (m1 ? ms.dmat : 0ll);
-            QWeight W = ms.w0;
-            W.qs += d; W.qh += d; W.sc += d; W.d += d;
-            WBuf B;
-            X::mkb(W, (size_t)lr * U, B);
+            MG4_MATSET_ROW(X, ms, row, rows_each, U, B);
 #pragma unroll
             for (int i = 0; i < NU; i++) X::loadb(B, uc[i], G.w[r][i]);
-            G.res[r] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mkbuf(reinterpret_cast<const uint8_t *>(res_base + (m2 ? 2 * res_stride : (m1 ? res_stride : 0ll)) + lr)), 0, 0, 0));
+            G.res[r] = load_res(MG4_MATSET_RES(res_base, res_stride));
         }
     };
     Grp cur, nxt;
@@ -573,15 +619,7 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
         extern __shared__ __attribute__((aligned(16))) unsigned char smem_mv[];
         ActQ L;                                     // LDS image of the quantised row (only the planes this weight type reads are written)
         double *red = reinterpret_cast<double *>(smem_mv);               // [waves] partial sums (dynamic LDS: shared by both halves of k_matvec_mix)
-        unsigned char *p = smem_mv + 128;
-        L.q8k = reinterpret_cast<int8_t *>(p); p += (size_t)K;
-        L.q80 = reinterpret_cast<int8_t *>(p); p += (size_t)K;
-        L.dk = reinterpret_cast<float *>(p); p += (size_t)(K / 256 + 1) * 4;
-        L.d0 = reinterpret_cast<float *>(p); p += (size_t)(K / 32) * 4;
-        L.d1 = reinterpret_cast<float *>(p); p += (size_t)(K / 32) * 4;
-        L.s1 = reinterpret_cast<float *>(p); p += (size_t)(K / 32) * 4;
-        L.sum0 = reinterpret_cast<int *>(p); p += (size_t)(K / 32) * 4;
-        L.bsk = reinterpret_cast<int16_t *>(p); p += (size_t)(K / 16) * 2;
+        row_image(L, smem_mv + 128, K);
         L.xh = reinterpret_cast<__half *>(smem_mv + 128);                // F16 weights: the fp16 row takes the place of the two int8 images (2 K bytes)
         L.xf = nullptr;
         constexpr int RND = (NU * 64 * X::EPU / 4 + MV_FAT_MIN - 1) / MV_FAT_MIN;    // K <= NU * 64 * EPU elements, 4 per thread per round, >= MV_FAT_MIN threads
@@ -615,36 +653,23 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
             for (int r = 0; r < RND; r++) {
                 const float4 v = xv[r];
                 double q = 0.0;
-                q += (double)(v.x * v.x); q += (double)(v.y * v.y); q += (double)(v.z * v.z); q += (double)(v.w * v.w);
+                MG4_ROW_SUMSQ4(q, v);
                 sum += in[r] ? q : 0.0;
             }
-            sum = wave_sum_d(sum);
-            if (lane == 0) red[threadIdx.x >> 6] = sum;
+            row_partial(red, sum);
             __syncthreads();
             double tot = 0.0;
-            for (int w = 0; w < nthr / 64; w++) tot += red[w];
+            for (int w = 0; w < nthr / 64; w++) tot += red[w];   // row_total's loop as text: called as a function, these kernels (and only these) compile differently
             float mean;
-            if (EPI == EPI_REF) {   // the oracle's mean (one double accumulator in element order) from a parallel sum: k_rms_quant's interval argument
-                const double delta = (double)K * 4e-16;
-                const float lo = (float)(tot * (1.0 - delta) / (double)K), hi = (float)(tot * (1.0 + delta) / (double)K);
-                mean = lo;
-                if (lo != hi) {     // workgroup-uniform (~1e-4 of the rows): the literal loop
-                    __syncthreads();
-                    if (threadIdx.x == 0) { double sq = 0.0; for (int i = 0; i < K; i++) sq += (double)(pa.x[i] * pa.x[i]); red[0] = sq; }
-                    __syncthreads();
-                    mean = (float)(red[0] / (double)K);
-                }
-            } else mean = (float)(tot / (double)K);
-            scale = 1.0f / sqrtf(mean + 1e-6f);
+            if (EPI == EPI_REF) MG4_ROW_MEAN_ORACLE(mean, tot, K, pa.x, red); else mean = row_mean(tot, K);
+            scale = row_scale(mean);
         }
 #pragma unroll
         for (int r = 0; r < RND; r++) {
             const int i = (r * nthr + (int)threadIdx.x) * 4;
             float v[4];
-            if (PRO == PRO_RMS) { v[0] = (xv[r].x * scale) * yv[r].x; v[1] = (xv[r].y * scale) * yv[r].y; v[2] = (xv[r].z * scale) * yv[r].z; v[3] = (xv[r].w * scale) * yv[r].w; }
-            else if (PRO == PRO_SILU) { v[0] = xv[r].x * yv[r].x; v[1] = xv[r].y * yv[r].y; v[2] = xv[r].z * yv[r].z; v[3] = xv[r].w * yv[r].w; }
-            else { v[0] = xv[r].x; v[1] = xv[r].y; v[2] = xv[r].z; v[3] = xv[r].w; }
-            if (!in[r]) { v[0] = 0.0f; v[1] = 0.0f; v[2] = 0.0f; v[3] = 0.0f; }
+            row_value4<PRO>(v, xv[r], yv[r], scale);
+            row_zero_unless(v, in[r]);
             quant_emit4(v, in[r], i, 0, K, L, mask);
         }
         __syncthreads();
@@ -674,7 +699,7 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
             for (int r = 0; r < R; r++) {
                 const int row = g * R + r;
                 if (lane == 0 && row < total_rows) {
-                    const int m = row >= 2 * rows_each ? 2 : (row >= rows_each ? 1 : 0), lr = row - m * rows_each;
+                    MG4_MATSET_M_LR(row, rows_each);
                     const float val = has_res ? out[r] + G.res[r] : out[r];
                     ms.y0[(long long)m * ms.dy + lr] = val;
                 }
@@ -727,10 +752,10 @@ static int g_mv_force_fat = 0;      // MINIGPT4_FAT_LB: threads of the fat workg
 // Launch geometry (measured on the 13B decode, profiles/r01g_ab_geometry.log): 8 waves per CU everywhere.  More waves lose even where they divide
 // the rows more evenly (5120 rows: 2048 waves = 3 | 2 rows per wave, 2560 waves = 2 each, yet 640-thread workgroups are 6 % slower end to
 // end than 512-thread ones; 1024-thread ones 5 % slower; 5 / 7 waves per CU for the K = 13824 mat-vec 4 % / 1 % slower than 8).
-static int pick_waves_per_cu(int /*groups*/, int max_wpc) { return std::min(g_mv_force_waves ? g_mv_force_waves : 8, max_wpc); }
-static int pick_fat_threads(int /*groups*/, int max_threads) { return g_mv_force_fat ? std::max(MV_FAT_MIN, std::min(g_mv_force_fat / 64 * 64, max_threads)) : MV_FAT_MIN; }
-int matvec_prologue_waves() { return g_mv_cus * (pick_fat_threads(0, MV_FAT_MIN) / 64); }
-static size_t mv_prologue_lds(int K) { return 128 + (size_t)2 * K + (size_t)(K / 256 + 1) * 4 + (size_t)4 * (K / 32) * 4 + (size_t)(K / 16) * 2 + 64; }
+static int pick_waves_per_cu(int max_wpc) { return std::min(g_mv_force_waves ? g_mv_force_waves : 8, max_wpc); }
+static int pick_fat_threads(int max_threads) { return g_mv_force_fat ? std::max(MV_FAT_MIN, std::min(g_mv_force_fat / 64 * 64, max_threads)) : MV_FAT_MIN; }
+int matvec_prologue_waves() { return g_mv_cus * (pick_fat_threads(MV_FAT_MIN) / 64); }
+static size_t mv_prologue_lds(int K) { return 128 + row_image_bytes(K); }   // the per-wave partial sums, then the row
 template <int NU> constexpr int mv_max_wpc() { return NU <= 3 ? 16 : NU == 4 ? 12 : 8; }      // register budget of the two-stage pipeline
 // The issue-barrier forms are built for the k-quants at NU <= 3 (K <= 6144: every prologue launch of the 7B / 13B decode step) outside parity mode; elsewhere the launch runs
 // the plain form.
@@ -748,15 +773,15 @@ template <int T, int NU, int R, int EPI>
 static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
     const int total_rows = ms.n * ms.rows_each;
     const int n_groups = EPI == EPI_SILU_PAIR ? ms.rows_each : (total_rows + R - 1) / R;
-    if (pro == PRO_NONE) note_kernel("k_matvec_v2<%d, %d, %d, 0, %d, false>", T, NU, R, (int)EPI);
     if (pro == PRO_NONE) {
+        note_kernel("k_matvec_v2<%d, %d, %d, 0, %d, false>", T, NU, R, (int)EPI);
         // EPI_REF: the block chain is a dependent sequence per wave (DPP move + fma per block): as many waves per SIMD as the registers admit, not the stream-optimal 8 per CU
-        int n_waves = std::min(n_groups, g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(n_groups, mv_max_wpc<NU>())));
+        int n_waves = std::min(n_groups, g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(mv_max_wpc<NU>())));
         n_waves = (n_waves + 3) & ~3;
         hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO_NONE, EPI>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, ms, A, pa, n_groups, n_waves);
         return;
     }
-    const int LB = EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(n_groups, mv_fat_max_threads<NU>()), WPB = LB / 64;
+    const int LB = EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(mv_fat_max_threads<NU>()), WPB = LB / 64;
     const int n_blocks = std::min((n_groups + WPB - 1) / WPB, g_mv_cus);
     const int n_waves = n_blocks * WPB;
     const dim3 grid((unsigned)n_blocks), block((unsigned)LB);
@@ -770,71 +795,20 @@ static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs 
     default: { if constexpr (EPI == EPI_STORE) launch_v2_pro<T, NU, R, PRO_SILU, EPI>(issue_bar, grid, block, lds, s, ms, A, pa, n_groups, n_waves); } break;
     }
 }
-#ifndef MG4_R_NU3
-#define MG4_R_NU3 1
-#endif
-#ifndef MG4_R_NU2
-#define MG4_R_NU2 1
-#endif
-// Q8_0 / F16 (16-byte units of 16 / 8 weights): a row needs more units per lane than the 32-weight types, and only a few unit counts are instantiated -- a row takes the
-// smallest one that covers it (the surplus units are masked like any ragged tail).  Q8_0: K <= 1024 | 4096 | 5120 | 11264; F16: K <= 512 | 1024 | 4096 | 5120.
-template <int T>
-static bool launch_v2_narrow(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, bool issue_bar, hipStream_t s) {
-    if (epi != EPI_STORE) return false;
-    const int nu = (ms.w0.cols / TrMV<T>::EPU + 63) / 64;
-    if constexpr (T == GT_Q8_0) {
-        if (nu <= 1) launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else if (nu <= 4) launch_v2_t<T, 4, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else if (nu <= 5) launch_v2_t<T, 5, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else if (nu <= 11) launch_v2_t<T, 11, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else return false;
-    } else {
-        if (nu <= 1) launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else if (nu <= 2) launch_v2_t<T, 2, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else if (nu <= 8) launch_v2_t<T, 8, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else if (nu <= 10) launch_v2_t<T, 10, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s);
-        else return false;
-    }
-    return true;
-}
 template <int T>
 static bool launch_v2_type(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, bool issue_bar, hipStream_t s) {
-    const int U = ms.w0.cols / Tr<T>::EPU;
-    const int nu = (U + 63) / 64;
-    bool ok = true;
-    if (epi == EPI_SILU_PAIR) {
-        if (ms.n != 2 || (pro != PRO_NONE && pro != PRO_RMS)) ok = false;
-        else switch (nu) {
-        case 1: launch_v2_t<T, 1, 2, EPI_SILU_PAIR>(ms, A, pro, pa, issue_bar, s); break;
-        case 2: launch_v2_t<T, 2, 2, EPI_SILU_PAIR>(ms, A, pro, pa, issue_bar, s); break;
-        case 3: launch_v2_t<T, 3, 2, EPI_SILU_PAIR>(ms, A, pro, pa, issue_bar, s); break;
-        default: ok = false;
-        }
-    } else if (epi == EPI_REF) {   // parity mode: the k-quants of the headline files (other types: k_mul_mat_ref_row); no SiLU prologue (the row comes from k_silu_mul_quant)
-        if constexpr (T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K) {
-            if (pro == PRO_SILU) return false;
-            switch (nu) {
-            case 1: launch_v2_t<T, 1, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            case 2: launch_v2_t<T, 2, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            case 3: launch_v2_t<T, 3, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            case 4: launch_v2_t<T, 4, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            case 5: launch_v2_t<T, 5, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            case 6: launch_v2_t<T, 6, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            case 7: launch_v2_t<T, 7, 1, EPI_REF>(ms, A, pro, pa, issue_bar, s); break;
-            default: ok = false;
-            }
-        } else ok = false;
-    } else switch (nu) {
-    case 1: launch_v2_t<T, 1, 2, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    case 2: launch_v2_t<T, 2, MG4_R_NU2, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    case 3: launch_v2_t<T, 3, MG4_R_NU3, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    case 4: launch_v2_t<T, 4, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    case 5: launch_v2_t<T, 5, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    case 6: launch_v2_t<T, 6, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    case 7: launch_v2_t<T, 7, 1, EPI_STORE>(ms, A, pro, pa, issue_bar, s); break;
-    default: ok = false;
+    const int nu = (ms.w0.cols / TrMV<T>::EPU + 63) / 64;
+    auto launch = [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        return mv_for_units<tr_is_narrow<T>()>(mv_units<T, EPI>(), nu, [&](auto n) {
+            constexpr int NU = decltype(n)::value;
+            launch_v2_t<T, NU, mv_rows_per_group<T, NU, EPI>(), EPI>(ms, A, pro, pa, issue_bar, s); });
+    };
+    switch (epi) {
+    case EPI_SILU_PAIR: return ms.n == 2 && (pro == PRO_NONE || pro == PRO_RMS) && launch(std::integral_constant<int, EPI_SILU_PAIR>{});
+    case EPI_REF: return pro != PRO_SILU && launch(std::integral_constant<int, EPI_REF>{});   // parity mode has no SiLU prologue (the row comes from k_silu_mul_quant)
+    default: return launch(std::integral_constant<int, EPI_STORE>{});
     }
-    return ok;
 }
 // copies the timeline stamps of the last decode mat-vec launch (8 x u64 per workgroup); 0 when the library was built without MG4_TIMELINE
 int read_attn_timeline(unsigned long long *out, int max_workgroups) {
@@ -855,7 +829,6 @@ int read_matvec_timeline(unsigned long long *out, int max_workgroups) {
     (void)out; (void)max_workgroups; return 0;
 #endif
 }
-bool matvec_silu_pair_supported(int type, int cols) { return type != GT_Q8_0 && type != GT_F16 && matvec_prologue_supported(type, cols) && cols / 32 <= 3 * 64; }
 
 static bool fill_matset(MatSet &ms, const QWeight *const *W, float *const *y, const float *const *residual, int n) {
     ms = MatSet{};
@@ -872,27 +845,28 @@ static bool fill_matset(MatSet &ms, const QWeight *const *W, float *const *y, co
     }
     return true;
 }
+// Two sets in one launch of `total` workgroups of `wpb` waves: how many of them stream set 1, so that the busiest wave of either set finishes earliest
+// (cost = rows per wave x bytes per row)
+static int mv_split_blocks(int ng1, double bytes1, int ng2, double bytes2, int total, int wpb) {
+    const double bpr1 = bytes1 / ng1, bpr2 = bytes2 / ng2;
+    int best_b1 = 1; double best_cost = 1e300;
+    for (int b1 = 1; b1 < total; b1++) {
+        const int w1 = b1 * wpb, w2 = (total - b1) * wpb;
+        const double c = std::max((double)((ng1 + w1 - 1) / w1) * bpr1, (double)((ng2 + w2 - 1) / w2) * bpr2);
+        if (c < best_cost) { best_cost = c; best_b1 = b1; }
+    }
+    return best_b1;
+}
 template <int T1, int T2, int NU, int EPI = EPI_STORE>
 static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
     const int ng1 = m1.n * m1.rows_each, ng2 = m2.n * m2.rows_each;
-    // split the workgroups so that the busiest wave of either set finishes earliest: cost = rows per wave x bytes per row
-    const double bpr1 = bytes1 / ng1, bpr2 = bytes2 / ng2;
-    int best_t = 0, best_b1 = 0, best_total = 0; double best_cost = 1e300;
-    const int t_fix = pro == PRO_NONE ? 256 : (EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(ng1, mv_fat_max_threads<NU>()));
-    for (int t = t_fix; t <= t_fix; t += 64) {
-        const int wpb = t / 64;
-        const int total = pro == PRO_NONE ? g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(ng1 + ng2, mv_max_wpc<NU>())) / 4 : g_mv_cus;
-        for (int b1 = 1; b1 < total; b1++) {
-            const int w1 = b1 * wpb, w2 = (total - b1) * wpb;
-            const double c = std::max((double)((ng1 + w1 - 1) / w1) * bpr1, (double)((ng2 + w2 - 1) / w2) * bpr2);
-            if (c < best_cost) { best_cost = c; best_t = t; best_b1 = b1; best_total = total; }
-        }
-    }
+    const int threads = pro == PRO_NONE ? 256 : (EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(mv_fat_max_threads<NU>())), wpb = threads / 64;
+    const int total = pro == PRO_NONE ? g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(mv_max_wpc<NU>())) / 4 : g_mv_cus;
+    const int b1 = mv_split_blocks(ng1, bytes1, ng2, bytes2, total, wpb), nw1 = b1 * wpb, nw2 = (total - b1) * wpb;
     constexpr bool BUILT = mv_issue_bar_built<T1, NU, EPI>() && mv_issue_bar_built<T2, NU, EPI>();
     const bool bar = pro != PRO_NONE && issue_bar && BUILT;
     note_kernel("k_matvec_mix<%d, %d, %d, %d, %d, %s>", T1, T2, NU, pro == PRO_NONE ? 0 : 1, (int)EPI, bar ? "true" : "false");
-    const int wpb = best_t / 64, nw1 = best_b1 * wpb, nw2 = (best_total - best_b1) * wpb;
-    const dim3 grid((unsigned)best_total), block((unsigned)best_t);
+    const dim3 grid((unsigned)total), block((unsigned)threads);
     if (pro == PRO_NONE) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_NONE, EPI>), grid, block, 0, s, m1, m2, A, pa, ng1, nw1, ng2, nw2); return; }
     if constexpr (BUILT) {
         if (bar) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI, true>), grid, block, mv_prologue_lds(m1.w0.cols), s, m1, m2, A, pa, ng1, nw1, ng2, nw2); return; }
@@ -901,14 +875,7 @@ static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, doub
 }
 template <int T1, int T2, int EPI = EPI_STORE>
 static bool launch_mix_nu(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
-    const int nu = (m1.w0.cols / 32 + 63) / 64;
-    switch (nu) {
-    case 1: launch_mix_t<T1, T2, 1, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
-    case 2: launch_mix_t<T1, T2, 2, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
-    case 3: launch_mix_t<T1, T2, 3, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
-    case 4: launch_mix_t<T1, T2, 4, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); return true;
-    default: return false;
-    }
+    return mv_for_units(MixUnits{}, (m1.w0.cols / 32 + 63) / 64, [&](auto n) { launch_mix_t<T1, T2, decltype(n)::value, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); });
 }
 // Decode mat-vec over two sets of different k-quant types with the same K (wq|wk + wv of a "more bits" layer) in ONE launch.  pro: PRO_NONE or PRO_RMS.
 bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, hipStream_t s, int pro,
@@ -921,21 +888,9 @@ bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, con
     double b1 = 0, b2 = 0;
     for (int i = 0; i < n1; i++) b1 += (double)W1[i]->bytes;
     for (int i = 0; i < n2; i++) b2 += (double)W2[i]->bytes;
-    const int t1 = W1[0]->type, t2 = W2[0]->type;
-    if (epi == EPI_REF) {
-        if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q5_K, GT_Q6_K, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
-        if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q4_K, GT_Q6_K, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
-        return false;
-    }
-    if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q5_K, GT_Q6_K>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
-    if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_mix_nu<GT_Q4_K, GT_Q6_K>(m1, m2, b1, b2, A, pro, pa, issue_bar, s);
-    return false;
-}
-bool matvec_prologue_supported(int type, int cols) {
-    if (type == GT_Q8_0) return cols % 32 == 0 && cols <= 11 * 64 * 16;      // launch_v2_narrow's instantiations
-    if (type == GT_F16) return cols % 8 == 0 && cols <= 10 * 64 * 8;
-    switch (type) { case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: break; default: return false; }
-    return cols % 32 == 0 && cols / 32 <= 7 * 64 && ((type != GT_Q4_K && type != GT_Q5_K && type != GT_Q6_K) || cols % 256 == 0);
+    return for_mixed_types(W1[0]->type, W2[0]->type, [&](auto t1, auto t2) {
+        constexpr int T1 = decltype(t1)::value, T2 = decltype(t2)::value;
+        return epi == EPI_REF ? launch_mix_nu<T1, T2, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, s) : launch_mix_nu<T1, T2>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); });
 }
 void set_matvec_tuning(int waves_per_cu, int fat_threads, int cus) { g_mv_force_waves = std::max(0, waves_per_cu); g_mv_force_fat = std::max(0, fat_threads); if (cus > 0) { g_mv_cus = cus; g_ref_cus = cus; } }
 // Decode (N = 1) mat-vec over 1..3 same-type, same-shape, equally spaced matrices.  Returns false when the set is outside the v2 kernel's range.
@@ -944,18 +899,8 @@ bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *co
     ProArgs pa{}; pa.x = px; pa.w = pw; if (tb) pa.tb = *tb;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
-    switch (W[0]->type) {
-    case GT_Q4_0: return launch_v2_type<GT_Q4_0>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q4_1: return launch_v2_type<GT_Q4_1>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q5_0: return launch_v2_type<GT_Q5_0>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q5_1: return launch_v2_type<GT_Q5_1>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q4_K: return launch_v2_type<GT_Q4_K>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q5_K: return launch_v2_type<GT_Q5_K>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q6_K: return launch_v2_type<GT_Q6_K>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_Q8_0: return launch_v2_narrow<GT_Q8_0>(ms, A, pro, pa, epi, issue_bar, s);
-    case GT_F16: return launch_v2_narrow<GT_F16>(ms, A, pro, pa, epi, issue_bar, s);
-    default: return false;   // F32 rows, and Q8_0 / F16 rows wider than launch_v2_narrow's instantiations: served by k_mul_mat
-    }
+    // false: F32 / Q2_K rows, and rows wider than the type's unit counts (served by k_mul_mat)
+    return for_weight_type(W[0]->type, [&](auto t) { return launch_v2_type<decltype(t)::value>(ms, A, pro, pa, epi, issue_bar, s); });
 }
 
 
@@ -966,7 +911,6 @@ bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *co
 // and read from there inside the loop (registers could hold only K <= 6144 for four rows; LDS traffic is ~1/4 of its bandwidth at HBM speed).
 // Per row the arithmetic is exactly the single-row kernel's: the same unit dot products, the same per-lane fma order, the same wave reduction.
 // =====================================================================================================================
-template <int T> constexpr bool tr_is_kquant() { return T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K; }
 static size_t mv_tn_lds(int type, int K, int TN) {
     const bool kq = type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K;
     const size_t per_row = kq ? (size_t)K + (size_t)(K / 256) * 4 + (size_t)(K / 16) * 2 : (size_t)K + (size_t)(K / 32) * 16;
@@ -978,7 +922,7 @@ template <int NU, int TN> constexpr bool mv_tn_reg() { return NU <= 3 || (TN == 
 template <int NU> constexpr int mv_tn_threads() { return NU >= 7 ? 256 : 512; }   // widest K: one wave per SIMD (up to 512 VGPRs) -- two would spill Q5_K's weight stages; 4 waves x 7 units keep as many bytes in flight as 8 x 3
 // PRO = 1 (K <= 3 x 64 units only): the rows are prepared inside the launch -- rms_norm(x_t) * w and the quantisation of k_rms_quant, row by row with the single-row
 // prologue's arithmetic (matvec_run), into one LDS image per row -- so a batched decode step needs no standalone preparation launch in front of wq|wk|wv and w1|w3.
-static size_t mv_tn_image_bytes(int K) { return ((size_t)2 * K + (size_t)(K / 256 + 1) * 4 + (size_t)4 * (K / 32) * 4 + (size_t)(K / 16) * 2 + 64 + 15) & ~(size_t)15; }
+static size_t mv_tn_image_bytes(int K) { return (row_image_bytes(K) + 15) & ~(size_t)15; }
 extern __shared__ __attribute__((aligned(16))) unsigned char smem_tn[];
 // `wave` = this wave's index among the n_waves that share the set's rows (k_matvec_tn: all waves of the launch; k_matvec_tn_mix: the waves of one of its two sets)
 template <int T, int NU, int TN, int PRO>
@@ -997,18 +941,12 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
     const long long res_stride = has_res ? ms.dres : ms.dy;
     auto fetch = [&](int g, Grp &G) {           // every load unconditional (clamped indices): see matvec_run
         const int row = min(g, total_rows - 1);
-        const bool m1 = row >= rows_each, m2 = row >= 2 * rows_each;
-        const int lr = row - (m2 ? 2 * rows_each : (m1 ? rows_each : 0));
-        const long long d = m2 ? 2 * ms.dmat : (m1 ? ms.dmat : 0ll);
-        QWeight W = ms.w0;
-        W.qs += d; W.qh += d; W.sc += d; W.d += d;
-        WBuf B;
-        X::mkb(W, (size_t)lr * U, B);
+        MG4_MATSET_ROW(X, ms, row, rows_each, U, B);
 #pragma unroll
         for (int i = 0; i < NU; i++) X::loadb(B, uc[i], G.w[i]);
-        const float *rb = res_base + (m2 ? 2 * res_stride : (m1 ? res_stride : 0ll)) + lr;
+        const float *rb = MG4_MATSET_RES(res_base, res_stride);
 #pragma unroll
-        for (int t = 0; t < TN; t++) G.res[t] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(mkbuf(reinterpret_cast<const uint8_t *>(rb + (size_t)min(t, N - 1) * ldy)), 0, 0, 0));
+        for (int t = 0; t < TN; t++) G.res[t] = load_res(rb + (size_t)min(t, N - 1) * ldy);
     };
     Grp cur, nxt;
     MG4_TL(0); MG4_TL_ALL(7);
@@ -1043,11 +981,11 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
                 for (int r = 0; r < PRND; r++) {
                     const float4 v = pxv[t][r];
                     double q = 0.0;
-                    q += (double)(v.x * v.x); q += (double)(v.y * v.y); q += (double)(v.z * v.z); q += (double)(v.w * v.w);
+                    MG4_ROW_SUMSQ4(q, v);
                     sum += pin[r] ? q : 0.0;
                 }
                 sum = wave_sum_d(sum);
-                if (lane == 0) red[t * 8 + (threadIdx.x >> 6)] = sum;
+                if (lane == 0) red[t * 8 + (threadIdx.x >> 6)] = sum;   // row_partial as text: called as a function, these kernels (and only these) compile differently
             }
             __syncthreads();
         }
@@ -1055,29 +993,16 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
 #pragma unroll
         for (int t = 0; t < (PRO ? TN : 1); t++) {
             float scale = 1.0f;
-            if (PRO == 1) {
-                double tot = 0.0;
-                for (int w = 0; w < 8; w++) tot += red[t * 8 + w];
-                const float mean = (float)(tot / (double)K);
-                scale = 1.0f / sqrtf(mean + 1e-6f);
-            }
-            unsigned char *p = smem_tn + 512 + (size_t)t * image_bytes;
+            if (PRO == PRO_RMS) scale = row_scale(row_mean(row_total(red + t * 8, 8), K));
             ActQ L{};
-            L.q8k = reinterpret_cast<int8_t *>(p); p += (size_t)K;
-            L.q80 = reinterpret_cast<int8_t *>(p); p += (size_t)K;
-            L.dk = reinterpret_cast<float *>(p); p += (size_t)(K / 256 + 1) * 4;
-            L.d0 = reinterpret_cast<float *>(p); p += (size_t)(K / 32) * 4;
-            L.d1 = reinterpret_cast<float *>(p); p += (size_t)(K / 32) * 4;
-            L.s1 = reinterpret_cast<float *>(p); p += (size_t)(K / 32) * 4;
-            L.sum0 = reinterpret_cast<int *>(p); p += (size_t)(K / 32) * 4;
-            L.bsk = reinterpret_cast<int16_t *>(p);
+            row_image(L, smem_tn + 512 + (size_t)t * image_bytes, K);
             L.bsq = nullptr; L.xh = nullptr; L.xf = nullptr;
 #pragma unroll
             for (int r = 0; r < PRND; r++) {
                 const int i = (r * 512 + (int)threadIdx.x) * 4;
-                float v[4] = {pxv[t][r].x, pxv[t][r].y, pxv[t][r].z, pxv[t][r].w};                                     // PRO == 2: the rows as they are (attention output -> wo)
-                if (PRO == 1) { v[0] = (v[0] * scale) * pyv[r].x; v[1] = (v[1] * scale) * pyv[r].y; v[2] = (v[2] * scale) * pyv[r].z; v[3] = (v[3] * scale) * pyv[r].w; }
-                if (!pin[r]) { v[0] = 0.0f; v[1] = 0.0f; v[2] = 0.0f; v[3] = 0.0f; }
+                float v[4];
+                row_value4<PRO == PRO_RMS ? PRO_RMS : PRO_PLAIN>(v, pxv[t][r], pyv[r], scale);   // PRO_PLAIN: the rows as they are (attention output -> wo)
+                row_zero_unless(v, pin[r]);
                 quant_emit4(v, pin[r], i, 0, K, L, mask);
             }
             Li[t] = L;
@@ -1148,7 +1073,7 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
 #pragma unroll
         for (int t = 0; t < TN; t++) out[t] = wave_sum(out[t]);
         if (lane == 0 && g < total_rows) {
-            const int m = g >= 2 * rows_each ? 2 : (g >= rows_each ? 1 : 0), lr = g - m * rows_each;
+            MG4_MATSET_M_LR(g, rows_each);
             float *yo = ms.y0 + (long long)m * ms.dy + lr;
 #pragma unroll
             for (int t = 0; t < TN; t++) if (t < N) yo[(size_t)t * ldy] = has_res ? out[t] + G.res[t] : out[t];
@@ -1198,7 +1123,7 @@ static void launch_tn_n(const MatSet &ms, const ActQ &A, int N, int ldy, hipStre
     constexpr int WPB = mv_tn_threads<NU>() / 64;
     const int n_blocks = std::min((n_groups + WPB - 1) / WPB, g_mv_cus), n_waves = n_blocks * WPB;
     ProArgs pa{}; pa.x = px; pa.w = pw;
-    constexpr bool PRO_OK = NU <= 3 && (T == GT_Q4_0 || T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K);
+    constexpr bool PRO_OK = units_have(mv_tn_pro_units<T>(), NU);
     if constexpr (PRO_OK) {
         if (px) {
             const int img = (int)mv_tn_image_bytes(ms.w0.cols);
@@ -1217,49 +1142,20 @@ static void launch_tn_n(const MatSet &ms, const ActQ &A, int N, int ldy, hipStre
     if (!attr) { HIP_IGNORE(lds_optin_max(&k_matvec_tn<T, NU, TN, 0>)); attr = true; }
     hipLaunchKernelGGL((k_matvec_tn<T, NU, TN, 0>), dim3((unsigned)n_blocks), dim3((unsigned)mv_tn_threads<NU>()), lds, s, ms, A, N, ldy, n_groups, n_waves, pa, 0, 0);
 }
-template <int T, int NU>
-static void launch_tn_t(const MatSet &ms, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {   // 2-row instantiation: half the dot products (and LDS reads) of the 4-row one
-    if (N <= 2) launch_tn_n<T, NU, 2>(ms, A, N, ldy, s, px, pw, ldx);
-    else if (N == 3) launch_tn_n<T, NU, 3>(ms, A, N, ldy, s, px, pw, ldx);      // the kernels are vector-issue bound: a 4th, unused row costs a quarter more
-    else launch_tn_n<T, NU, 4>(ms, A, N, ldy, s, px, pw, ldx);
-}
 template <int T>
 static bool launch_tn_type(const MatSet &ms, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
-    const int nu = (ms.w0.cols / Tr<T>::EPU + 63) / 64;
-    switch (nu) {
-    case 1: launch_tn_t<T, 1>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    case 2: launch_tn_t<T, 2>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    case 3: launch_tn_t<T, 3>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    case 4: launch_tn_t<T, 4>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    case 5: launch_tn_t<T, 5>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    case 6: launch_tn_t<T, 6>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    case 7: launch_tn_t<T, 7>(ms, A, N, ldy, s, px, pw, ldx); return true;
-    default: return false;
-    }
+    return mv_for_units(mv_tn_units<T>(), (ms.w0.cols / Tr<T>::EPU + 63) / 64, [&](auto n) {
+        mv_for_rows(N, [&](auto tn) { launch_tn_n<T, decltype(n)::value, decltype(tn)::value>(ms, A, N, ldy, s, px, pw, ldx); }); });
 }
 // 2..4 activation rows against 1..3 same-type, same-shape, equally spaced matrices in ONE weight pass: y[m][t * ldy + r] = W_m[r] . act[t] (+ residual[m][t * ldy + r]).
 // false -> shape / type outside the kernel's range (the caller falls back to launch_mul_mat per matrix).
-bool matvec_rows_prologue_ok(int type, int K) {
-    if (type != GT_Q4_0 && type != GT_Q4_K && type != GT_Q5_K && type != GT_Q6_K) return false;
-    const int epu = type == GT_Q4_0 ? Tr<GT_Q4_0>::EPU : 32;
-    return matvec_prologue_supported(type, K) && K / epu <= 192 && K % 4 == 0;
-}
 bool launch_matvec_rows(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
     if (px && !matvec_rows_prologue_ok(W[0]->type, W[0]->cols)) return false;
     if (N < 1 || N > 4 || !matvec_prologue_supported(W[0]->type, W[0]->cols)) return false;
     if (mv_tn_lds(W[0]->type, W[0]->cols, 4) > 150 * 1024) return false;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
-    switch (W[0]->type) {
-    case GT_Q4_0: return launch_tn_type<GT_Q4_0>(ms, A, N, ldy, s, px, pw, ldx);
-    case GT_Q4_1: return launch_tn_type<GT_Q4_1>(ms, A, N, ldy, s, px, pw, ldx);
-    case GT_Q5_0: return launch_tn_type<GT_Q5_0>(ms, A, N, ldy, s, px, pw, ldx);
-    case GT_Q5_1: return launch_tn_type<GT_Q5_1>(ms, A, N, ldy, s, px, pw, ldx);
-    case GT_Q4_K: return launch_tn_type<GT_Q4_K>(ms, A, N, ldy, s, px, pw, ldx);
-    case GT_Q5_K: return launch_tn_type<GT_Q5_K>(ms, A, N, ldy, s, px, pw, ldx);
-    case GT_Q6_K: return launch_tn_type<GT_Q6_K>(ms, A, N, ldy, s, px, pw, ldx);
-    default: return false;
-    }
+    return for_weight_type(W[0]->type, [&](auto t) { return launch_tn_type<decltype(t)::value>(ms, A, N, ldy, s, px, pw, ldx); });
 }
 
 template <int T1, int T2, int NU, int TN>
@@ -1268,15 +1164,7 @@ static void launch_tn_mix_n(const MatSet &m1, const MatSet &m2, double bytes1, d
     const int ng1 = m1.n * m1.rows_each, ng2 = m2.n * m2.rows_each;
     constexpr int WPB = mv_tn_threads<NU>() / 64;
     const int total = g_mv_cus;
-    // split the workgroups so that the busiest wave of either set finishes earliest: cost = rows per wave x bytes per row (launch_mix_t)
-    const double bpr1 = bytes1 / ng1, bpr2 = bytes2 / ng2;
-    int best_b1 = 1; double best_cost = 1e300;
-    for (int b1 = 1; b1 < total; b1++) {
-        const int w1 = b1 * WPB, w2 = (total - b1) * WPB;
-        const double c = std::max((double)((ng1 + w1 - 1) / w1) * bpr1, (double)((ng2 + w2 - 1) / w2) * bpr2);
-        if (c < best_cost) { best_cost = c; best_b1 = b1; }
-    }
-    const int nw1 = best_b1 * WPB, nw2 = (total - best_b1) * WPB;
+    const int b1 = mv_split_blocks(ng1, bytes1, ng2, bytes2, total, WPB), nw1 = b1 * WPB, nw2 = (total - b1) * WPB;
     ProArgs pa{}; pa.x = px; pa.w = pw;
     const dim3 grid((unsigned)total), block((unsigned)mv_tn_threads<NU>());
     if (px) {
@@ -1292,19 +1180,8 @@ static void launch_tn_mix_n(const MatSet &m1, const MatSet &m2, double bytes1, d
 }
 template <int T1, int T2>
 static bool launch_tn_mix_type(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
-    const int nu = (m1.w0.cols / 32 + 63) / 64;
-    switch (nu * 3 + (N <= 2 ? 0 : N == 3 ? 1 : 2)) {
-    case 3: launch_tn_mix_n<T1, T2, 1, 2>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 4: launch_tn_mix_n<T1, T2, 1, 3>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 5: launch_tn_mix_n<T1, T2, 1, 4>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 6: launch_tn_mix_n<T1, T2, 2, 2>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 7: launch_tn_mix_n<T1, T2, 2, 3>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 8: launch_tn_mix_n<T1, T2, 2, 4>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 9: launch_tn_mix_n<T1, T2, 3, 2>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 10: launch_tn_mix_n<T1, T2, 3, 3>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    case 11: launch_tn_mix_n<T1, T2, 3, 4>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); return true;
-    default: return false;
-    }
+    return mv_for_units(TnMixUnits{}, (m1.w0.cols / 32 + 63) / 64, [&](auto n) {
+        mv_for_rows(N, [&](auto tn) { launch_tn_mix_n<T1, T2, decltype(n)::value, decltype(tn)::value>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); }); });
 }
 // Batched decode, N = 1..4 rows: two sets of different k-quant types with the same K (wq|wk + wv of a "more bits" layer) in ONE launch.  px != null: the rows are
 // prepared inside the launch (rms_norm(px_t) * pw, quantised), as in launch_matvec_rows.  false: outside the kernel's range, nothing was launched.
@@ -1317,10 +1194,8 @@ bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1
     double b1 = 0, b2 = 0;
     for (int i = 0; i < n1; i++) b1 += (double)W1[i]->bytes;
     for (int i = 0; i < n2; i++) b2 += (double)W2[i]->bytes;
-    const int t1 = W1[0]->type, t2 = W2[0]->type;
-    if (t1 == GT_Q5_K && t2 == GT_Q6_K) return launch_tn_mix_type<GT_Q5_K, GT_Q6_K>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx);
-    if (t1 == GT_Q4_K && t2 == GT_Q6_K) return launch_tn_mix_type<GT_Q4_K, GT_Q6_K>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx);
-    return false;
+    return for_mixed_types(W1[0]->type, W2[0]->type, [&](auto t1, auto t2) {
+        return launch_tn_mix_type<decltype(t1)::value, decltype(t2)::value>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); });
 }
 
 static int g_mmq_enabled = 2;   // 0: v_dot4 tiles only (tests / A-B), 2: the LDS-staged int8-MFMA kernels of mmq2_kernels.hip for N >= 5 rows
@@ -1339,20 +1214,8 @@ void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, c
     if (W.type == GT_F16 && N >= 16 && W.cols % 8 == 0) {
         if (g_f16_gemm) { launch_gemm_f16(A.xh, W.cols, reinterpret_cast<const __half *>(W.qs), W.cols, N, W.rows, W.cols, nullptr, residual, false, Tables{}, y, nullptr, ldy, s); return; }
     }
-    switch (W.type) {
-    case GT_Q4_0: launch_mul_mat_t<GT_Q4_0>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q4_1: launch_mul_mat_t<GT_Q4_1>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q5_0: launch_mul_mat_t<GT_Q5_0>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q5_1: launch_mul_mat_t<GT_Q5_1>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q8_0: launch_mul_mat_t<GT_Q8_0>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q2_K: launch_mul_mat_t<GT_Q2_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q4_K: launch_mul_mat_t<GT_Q4_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q5_K: launch_mul_mat_t<GT_Q5_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_Q6_K: launch_mul_mat_t<GT_Q6_K>(W, A, N, y, ldy, residual, s); break;
-    case GT_F16: launch_mul_mat_t<GT_F16>(W, A, N, y, ldy, residual, s); break;
-    case GT_F32: launch_mul_mat_t<GT_F32>(W, A, N, y, ldy, residual, s); break;
-    default: throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
-    }
+    if (!for_weight_type(W.type, [&](auto t) { launch_mul_mat_t<decltype(t)::value>(W, A, N, y, ldy, residual, s); return true; }))
+        throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
 }
 
 
@@ -1362,49 +1225,26 @@ __global__ __launch_bounds__(RQ_THREADS) void k_rms_quant(const float *__restric
     const float *xr = x + row * K;
     __shared__ double red[RQ_THREADS / 64];
     float scale = 1.0f;
-    if (w && seq) {   // MINIGPT4_PARITY: the value of ggml_compute_forward_rms_norm's loop -- ONE double accumulator, element order -- without running 5120 dependent double
-        // additions on one lane (20 us per norm, 1.6 ms of a 13B token).  Every addend is >= 0, so the sequential sum S and the parallel sum T below both lie within
-        // K * 2^-53 (relative) of the exact sum; mean = (float)(S / K) is monotone in S, so if the two ends of T (1 +- 4e-16 K) convert to the SAME float, that float is
-        // the oracle's mean, whatever S is.  Otherwise (a sum that close to a float rounding boundary: ~1e-4 of the rows) thread 0 runs the literal loop.
+    if (w && seq) {   // MINIGPT4_PARITY: the oracle's mean.  Two arms on purpose: with one arm and the choice at the mean, the plain path compiles to different code
         double sum = 0.0;
-        for (int i = threadIdx.x * 4; i < K; i += RQ_THREADS * 4) { const float4 v = *reinterpret_cast<const float4 *>(xr + i);
-            sum += (double)(v.x * v.x); sum += (double)(v.y * v.y); sum += (double)(v.z * v.z); sum += (double)(v.w * v.w); }
-        sum = wave_sum_d(sum);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+        for (int i = threadIdx.x * 4; i < K; i += RQ_THREADS * 4) { const float4 v = *reinterpret_cast<const float4 *>(xr + i); MG4_ROW_SUMSQ4(sum, v); }
+        row_partial(red, sum);
         __syncthreads();
-        double tot = 0.0;
-#pragma unroll
-        for (int i = 0; i < RQ_THREADS / 64; i++) tot += red[i];
-        const double delta = (double)K * 4e-16;          // two sums of K non-negative terms, each within K * 2^-53 of the exact one, and margin for the multiplications below
-        const float lo = (float)(tot * (1.0 - delta) / (double)K), hi = (float)(tot * (1.0 + delta) / (double)K);
-        float mean = lo;
-        if (lo != hi) {                                  // block-uniform: every thread computed the same tot
-            __syncthreads();
-            if (threadIdx.x == 0) { double sq = 0.0; for (int i = 0; i < K; i++) sq += (double)(xr[i] * xr[i]); red[0] = sq; }
-            __syncthreads();
-            mean = (float)(red[0] / (double)K);
-        }
-        scale = 1.0f / sqrtf(mean + 1e-6f);
+        scale = row_scale(row_mean_oracle(row_total(red, RQ_THREADS / 64), K, xr, red));
     } else if (w) {
         double sum = 0.0;
-        for (int i = threadIdx.x * 4; i < K; i += RQ_THREADS * 4) { const float4 v = *reinterpret_cast<const float4 *>(xr + i);
-            sum += (double)(v.x * v.x); sum += (double)(v.y * v.y); sum += (double)(v.z * v.z); sum += (double)(v.w * v.w); }
-        sum = wave_sum_d(sum);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+        for (int i = threadIdx.x * 4; i < K; i += RQ_THREADS * 4) { const float4 v = *reinterpret_cast<const float4 *>(xr + i); MG4_ROW_SUMSQ4(sum, v); }
+        row_partial(red, sum);
         __syncthreads();
-        double tot = 0.0;
-#pragma unroll
-        for (int i = 0; i < RQ_THREADS / 64; i++) tot += red[i];
-        const float mean = (float)(tot / (double)K);
-        scale = 1.0f / sqrtf(mean + 1e-6f);
+        scale = row_scale(row_mean(row_total(red, RQ_THREADS / 64), K));
     }
     for (int i0 = 0; i0 < K; i0 += RQ_THREADS * 4) {
         const int i = i0 + threadIdx.x * 4;
         const bool in = i < K;
         float v[4] = {0, 0, 0, 0};
         if (in) { const float4 xv = *reinterpret_cast<const float4 *>(xr + i);
-            if (w) { const float4 wv = *reinterpret_cast<const float4 *>(w + i); v[0] = (xv.x * scale) * wv.x; v[1] = (xv.y * scale) * wv.y; v[2] = (xv.z * scale) * wv.z; v[3] = (xv.w * scale) * wv.w; }
-            else { v[0] = xv.x; v[1] = xv.y; v[2] = xv.z; v[3] = xv.w; } }
+            if (w) row_value4<PRO_RMS>(v, xv, *reinterpret_cast<const float4 *>(w + i), scale);
+            else row_value4<PRO_PLAIN>(v, xv, xv, scale); }
         quant_emit4(v, in, i, row, K, A, mask);
     }
 }
@@ -1427,22 +1267,16 @@ __global__ __launch_bounds__(RQ_THREADS) void k_rms_quant_slabs(const float *__r
     for (int i = threadIdx.x * 4; i < K; i += RQ_THREADS * 4) {
         const float4 v = slab_sum4(slabs, ks, stride, res, row * K + i);
         *reinterpret_cast<float4 *>(xr + i) = v;                   // re-read below by the same thread
-        sum += (double)(v.x * v.x); sum += (double)(v.y * v.y); sum += (double)(v.z * v.z); sum += (double)(v.w * v.w);
+        MG4_ROW_SUMSQ4(sum, v);
     }
-    sum = wave_sum_d(sum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    row_partial(red, sum);
     __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int i = 0; i < RQ_THREADS / 64; i++) tot += red[i];
-    const float mean = (float)(tot / (double)K);
-    const float scale = 1.0f / sqrtf(mean + 1e-6f);
+    const float scale = row_scale(row_mean(row_total(red, RQ_THREADS / 64), K));
     for (int i0 = 0; i0 < K; i0 += RQ_THREADS * 4) {
         const int i = i0 + threadIdx.x * 4;
         const bool in = i < K;
         float v[4] = {0, 0, 0, 0};
-        if (in) { const float4 xv = *reinterpret_cast<const float4 *>(xr + i); const float4 wv = *reinterpret_cast<const float4 *>(w + i);
-            v[0] = (xv.x * scale) * wv.x; v[1] = (xv.y * scale) * wv.y; v[2] = (xv.z * scale) * wv.z; v[3] = (xv.w * scale) * wv.w; }
+        if (in) row_value4<PRO_RMS>(v, *reinterpret_cast<const float4 *>(xr + i), *reinterpret_cast<const float4 *>(w + i), scale);
         quant_emit4(v, in, i, row, K, A, mask);
     }
 }

@@ -21,7 +21,7 @@
 //   16-element sums.
 #include "kernels.hpp"
 #include "devutil.hpp"
-#include "qtraits.hpp"
+#include "row_prep.hpp"
 
 #include <algorithm>
 
@@ -277,23 +277,22 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_matvec_ri(const RiArgs a, const
                 if (norm) {
                     double sum = 0.0;
                     for (int i = threadIdx.x * 4; i < K; i += NT * 4) { const float4 v = *reinterpret_cast<const float4 *>(xr + i);
-                        double q = 0.0; q += (double)(v.x * v.x); q += (double)(v.y * v.y); q += (double)(v.z * v.z); q += (double)(v.w * v.w); sum += q; }
-                    sum = wave_sum_d(sum);
-                    if (lane == 0) redd[wv] = sum;
+                        double q = 0.0; MG4_ROW_SUMSQ4(q, v); sum += q; }
+                    row_partial(redd, sum);
                     __syncthreads();
-                    double tot = 0.0;
-                    for (int w = 0; w < WPB; w++) tot += redd[w];
+                    const double tot = row_total(redd, WPB);
                     __syncthreads();
-                    scale = 1.0f / sqrtf((float)(tot / (double)K) + 1e-6f);
+                    scale = row_scale(row_mean(tot, K));
                 }
                 for (int i0 = 0; i0 < K; i0 += NT * 4) {                      // whole waves per 256-block (K is a multiple of 256): the Q8_K emission is a wave-level operation
                     const int i = i0 + threadIdx.x * 4; const bool in = i < K; const int ic = in ? i : 0;
                     const float4 xv = *reinterpret_cast<const float4 *>(xr + ic);
                     float4 wv4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
                     if (norm) wv4 = *reinterpret_cast<const float4 *>(a.pw + ic);
-                    float v[4] = {xv.x, xv.y, xv.z, xv.w};
-                    if (norm) { v[0] = (xv.x * scale) * wv4.x; v[1] = (xv.y * scale) * wv4.y; v[2] = (xv.z * scale) * wv4.z; v[3] = (xv.w * scale) * wv4.w; }
-                    if (!in) { v[0] = 0.0f; v[1] = 0.0f; v[2] = 0.0f; v[3] = 0.0f; }
+                    float v[4];
+                    row_value4<PRO_PLAIN>(v, xv, wv4, scale);
+                    if (norm) row_value4<PRO_RMS>(v, xv, wv4, scale);
+                    row_zero_unless(v, in);
                     if (i0 + (int)(threadIdx.x & ~63) * 4 < K) quant_emit4(v, in, i, (size_t)t, K, L, ACT_Q8K);   // (wave-uniform condition: a wave entirely past the row skips)
                 }
             } else {

@@ -223,7 +223,20 @@ static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, cons
 
 // The batched-decode mat-vec (k_matvec_tn) as Engine::forward_batch issues it: N = 1..4 rows against n_mat equally spaced matrices (raw_w = their file bytes
 // back to back), optional residual.  x: [N][n_in]; y / residual: [n_mat][N][n_out].  Returns 4 when the shape is outside the kernel's range.
+// prepare = 0: the rows are quantised by a launch of their own (rms_w: normed with it there); 1: inside the mat-vec launch -- rms_norm(x_t) * rms_w, or x_t as it is.
+static int test_matvec_rows_impl(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, const float *rms_w, int prepare, float *y);
 int minigpt4_amd_test_matvec_rows(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, float *y) {
+    return test_matvec_rows_impl(ggml_type, raw_w, n_mat, n_in, n_out, x, N, residual, nullptr, 0, y);
+}
+int minigpt4_amd_test_matvec_rows_prep(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, const float *rms_w, int prepare, float *y) {
+    return test_matvec_rows_impl(ggml_type, raw_w, n_mat, n_in, n_out, x, N, residual, rms_w, prepare, y);
+}
+// bit 0: matvec_prologue_supported, bit 1: matvec_silu_pair_supported, bit 2: matvec_rows_prologue_ok -- what the engine asks before it fuses a preparation (host only)
+int minigpt4_amd_test_matvec_predicates(int ggml_type, int64_t n_in) {
+    if (n_in <= 0 || n_in > (1 << 30)) return -1;
+    return (matvec_prologue_supported(ggml_type, (int)n_in) ? 1 : 0) | (matvec_silu_pair_supported(ggml_type, (int)n_in) ? 2 : 0) | (matvec_rows_prologue_ok(ggml_type, (int)n_in) ? 4 : 0);
+}
+static int test_matvec_rows_impl(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, const float *rms_w, int prepare, float *y) {
     if (!raw_w || !x || !y || n_in <= 0 || n_out <= 0 || n_mat < 1 || n_mat > 3 || N < 1 || N > 4 || !qweight_supported(ggml_type) || n_in % gt_block(ggml_type)) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -241,10 +254,12 @@ int minigpt4_amd_test_matvec_rows(int ggml_type, const void *raw_w, int n_mat, i
         if (residual) HIP_CHECK(hipMemcpy(d_res.p, residual, (size_t)n_mat * N * R * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(d_y.p, 0xFF, (size_t)n_mat * N * R * 4));
         ActQ A; std::vector<std::unique_ptr<DevBuf>> keep; alloc_act(A, keep, (size_t)N, (size_t)K);
-        launch_rms_quant(d_x.as<float>(), nullptr, N, K, A, act_mask_for(ggml_type), nullptr);
+        DevBuf d_w((size_t)K * 4);
+        if (rms_w) HIP_CHECK(hipMemcpy(d_w.p, rms_w, (size_t)K * 4, hipMemcpyHostToDevice));
+        if (!prepare) launch_rms_quant(d_x.as<float>(), rms_w ? d_w.as<float>() : nullptr, N, K, A, act_mask_for(ggml_type), nullptr);
         const QWeight *Wp[3]; float *Yp[3]; const float *Rp[3];
         for (int m = 0; m < n_mat; m++) { Wp[m] = &W[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * N * R; Rp[m] = d_res.as<float>() + (size_t)m * N * R; }
-        if (!launch_matvec_rows(Wp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, nullptr)) { set_last_error("shape / type outside the multi-row mat-vec kernel's range"); return 4; }
+        if (!launch_matvec_rows(Wp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, nullptr, prepare ? d_x.as<float>() : nullptr, prepare && rms_w ? d_w.as<float>() : nullptr, K)) { set_last_error("shape / type outside the multi-row mat-vec kernel's range"); return 4; }
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, (size_t)n_mat * N * R * 4, hipMemcpyDeviceToHost));
         return 0;

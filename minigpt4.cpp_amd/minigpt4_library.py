@@ -1021,14 +1021,32 @@ class MiniGPT4SharedLibrary:
         """Waves of a prologue mat-vec launch that fills the device: wave w owns row groups w, w + waves, ..."""
         return int(self.library.minigpt4_amd_test_matvec_waves())
 
-    def amd_test_matvec_rows(self, ggml_type: int, raw_w: np.ndarray, n_mat: int, n_in: int, n_out: int, x: np.ndarray, residual: Optional[np.ndarray] = None) -> np.ndarray:
-        """The batched-decode mat-vec: x [N][n_in] (N <= 4) against n_mat matrices in one weight pass -> [n_mat][N][n_out]."""
+    def amd_test_matvec_predicates(self, ggml_type: int, n_in: int):
+        """(single-row prologue, SiLU pair epilogue, multi-row prologue): which in-launch preparations the decode mat-vec offers for (type, n_in).  Needs no GPU."""
+        f = self.library.minigpt4_amd_test_matvec_predicates
+        f.argtypes = [I32, ctypes.c_int64]
+        bits = int(f(ggml_type, n_in))
+        if bits < 0:
+            raise ValueError("amd_test_matvec_predicates: bad arguments")
+        return bool(bits & 1), bool(bits & 2), bool(bits & 4)
+
+    def amd_test_matvec_rows(self, ggml_type: int, raw_w: np.ndarray, n_mat: int, n_in: int, n_out: int, x: np.ndarray, residual: Optional[np.ndarray] = None,
+                             rms_w: Optional[np.ndarray] = None, prepare: bool = False) -> np.ndarray:
+        """The batched-decode mat-vec: x [N][n_in] (N <= 4) against n_mat matrices in one weight pass -> [n_mat][N][n_out].  prepare: the rows are prepared inside the
+        launch (rms_w: rms_norm(x_t) * rms_w, else as they are); otherwise by a launch of their own in front."""
         x = np.ascontiguousarray(x, np.float32).reshape(-1, n_in)
         raw_w = np.ascontiguousarray(raw_w)
         res = None if residual is None else np.ascontiguousarray(residual, np.float32)
         y = np.empty((n_mat, x.shape[0], n_out), np.float32)
-        rc = self.library.minigpt4_amd_test_matvec_rows(ggml_type, raw_w.ctypes.data_as(VOID_PTR), n_mat, n_in, n_out, x.ctypes.data_as(FLOAT_PTR), x.shape[0],
-                                                        None if res is None else res.ctypes.data_as(FLOAT_PTR), y.ctypes.data_as(FLOAT_PTR))
+        if rms_w is not None or prepare:
+            f = self.library.minigpt4_amd_test_matvec_rows_prep
+            f.argtypes = [I32, VOID_PTR, I32, ctypes.c_int64, ctypes.c_int64, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR]
+            w = None if rms_w is None else np.ascontiguousarray(rms_w, np.float32).reshape(n_in)
+            rc = f(ggml_type, raw_w.ctypes.data_as(VOID_PTR), n_mat, n_in, n_out, x.ctypes.data_as(FLOAT_PTR), x.shape[0], None if res is None else res.ctypes.data_as(FLOAT_PTR),
+                   None if w is None else w.ctypes.data_as(FLOAT_PTR), int(bool(prepare)), y.ctypes.data_as(FLOAT_PTR))
+        else:
+            rc = self.library.minigpt4_amd_test_matvec_rows(ggml_type, raw_w.ctypes.data_as(VOID_PTR), n_mat, n_in, n_out, x.ctypes.data_as(FLOAT_PTR), x.shape[0],
+                                                            None if res is None else res.ctypes.data_as(FLOAT_PTR), y.ctypes.data_as(FLOAT_PTR))
         if rc:
             raise RuntimeError(f"test_matvec_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
         return y
