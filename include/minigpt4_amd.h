@@ -293,6 +293,46 @@ MINIGPT4_API int minigpt4_amd_penalty_info(struct MiniGPT4Context *ctx, int32_t 
 MINIGPT4_API int minigpt4_amd_beam_search(struct MiniGPT4Context *ctx, const int32_t *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int32_t *tokens_out,
                                           int32_t *lengths_out, float *scores_out, int32_t *n_out, int32_t stats[4]);
 
+/* ---- guided decoding: two conversations' logits contrasted on the device (classifier-free guidance: llama.cpp's llama_sample_classifier_free_guidance behind
+ * --cfg-negative-prompt / --cfg-scale; for a vision-language model also image-contrastive decoding: the conversation that saw the image against the same question
+ * without it) ------------------------------------------------------------------------------------------------------------------------------------------------------
+ * Every other generation entry point decides a token from ONE conversation's logits.  Here a PAIR decides: a guided conversation pos = slots[i] and a guidance
+ * conversation neg = neg_slots[i], all 2 n of a call distinct conversations of one context, 1 <= n <= 32.  b and g are their current RAW logits rows, scale a finite
+ * float: 1 = no guidance, above 1 pushes away from neg, 0 and negative values are allowed.
+ * THE RULE, fp32 throughout:
+ *   1. lb[j] = (b[j] - max b) - log(sum exp(b - max b)), lg likewise from g: bit for bit the log-probabilities minigpt4_amd_top_logprobs reports for those rows.
+ *   2. d = lb[j] - lg[j];  t = scale * d;  m[j] = lg[j] + t -- each operation rounded to fp32 on its own, no fused multiply-add (llama.cpp's
+ *      l = guidance + scale * (base - guidance) on the two log-softmaxed rows).  Exactly: scale == 0 gives m == lg, and b, g being one row gives m == lb.
+ *   3. m is what everything downstream of the logits sees for pos, in the order of llama.cpp's main: guidance, then pos's logit bias and penalties (steps 1 - 5 above,
+ *      applied to m), then the pick.  neg's bias and penalties are ignored.
+ *   4. temp <= 0: the first maximum of the result (lowest id among equal values, -0.0 == +0.0).  temp > 0: the sampling chain on the result, one draw per pair, in list order.
+ *   5. BOTH conversations advance by the picked token in one weight pass -- the batched step's own launches and graph; the token enters both token histories.  Afterwards
+ *      each holds its own raw logits, greedy token and feed token, bit for bit as after minigpt4_amd_eval_batch with that token forced on both.
+ *   6. A pair advances both conversations or neither: if either has no room and the automatic shift (minigpt4_amd_set_context_shift) cannot make it, the pair is sampled, its
+ *      id reported, and neither advances.  With the shift on each conversation shifts by its own rule.
+ * Logits are finite (NaN and infinities in the raw rows: unspecified).  The raw rows are never modified: minigpt4_amd_get_logits, the scoring calls and
+ * minigpt4_amd_top_logprobs keep describing raw distributions; minigpt4_amd_verify_draft, minigpt4_amd_decode_lookup and minigpt4_amd_beam_search keep deciding on them.
+ * ON THE DEVICE: k_guide_rows (one 256-thread workgroup per pair, one launch per call) sweeps the two rows for their maxima and sums, mixes in one more sweep and carries
+ * the first maximum.  With temp <= 0 a pair whose pos has no bias and no active penalty never meets the host between the decision and the pass: the kernel writes the pick
+ * into the pass's row tokens, and the host reads the ids from pinned memory while the pass runs (it needs them for histories, pieces and ids_out only).  A pair with a bias or
+ * penalty runs k_pen_pick on its written m row; with temp > 0 the m rows of all pairs come to the host in one copy.  Parity mode: the same kernel decides, one oracle-order
+ * single-row pass per conversation evaluates (the fall-back of minigpt4_amd_eval_batch).
+ * Queued rows of all 2 n conversations are evaluated first (as minigpt4_amd_prefill_batch over them does); each must then have current logits.
+ * minigpt4_amd_end_chat_guided: one step.  tokens[i] = the borrowed piece of pair i's token (as minigpt4_amd_end_chat_batch returns it), ids_out (may be NULL) its id.
+ * minigpt4_amd_guided_logits: mixed_out (may be NULL) = [n][n_vocab] rows m BEFORE bias and penalties, pick_out (may be NULL) their first maxima.  It advances nothing:
+ * position, logits, greedy / feed token, the sampler's generator, mirostat state and histories are untouched; only queued rows are evaluated.
+ * minigpt4_amd_guidance_info: out = {k_guide_rows launches, pairs handed to the pass on the device, pairs picked through k_pen_pick, pairs sampled on the host} so far.
+ * Each returns 0, or 1 with "end_chat_guided: ..." / "guided_logits: ..." / "guidance_info: ..." in minigpt4_amd_last_error and nothing changed: no context, a NULL list,
+ * n < 1, 2 n above the number of conversations, a slot out of range or named twice, a scale that is not finite; after the queued rows: "... has no current logits" (after
+ * minigpt4_reset_chat, after a partial fork).  The buffers of the feature (32 mixed rows, the tables, an event) are allocated by the first call and freed with the context
+ * and by minigpt4_amd_set_conversations: a context that never calls it allocates nothing new and launches nothing new.
+ * Not built: a stored pairing that would make the reference's minigpt4_end_chat guided; guidance inside beam search or draft verification; a top-N report of the guided
+ * distribution; a smoothing factor; more than 32 pairs. */
+MINIGPT4_API int minigpt4_amd_end_chat_guided(struct MiniGPT4Context *ctx, const int32_t *slots, const int32_t *neg_slots, int n, float scale, const char **tokens, float temp,
+                                              int32_t top_k, float top_p, float tfs_z, float typical_p, int mirostat, float mirostat_tau, float mirostat_eta, int32_t *ids_out);
+MINIGPT4_API int minigpt4_amd_guided_logits(struct MiniGPT4Context *ctx, const int32_t *slots, const int32_t *neg_slots, int n, float scale, float *mixed_out, int32_t *pick_out);
+MINIGPT4_API int minigpt4_amd_guidance_info(struct MiniGPT4Context *ctx, int32_t out[4]);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

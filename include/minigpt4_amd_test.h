@@ -165,6 +165,14 @@ MINIGPT4_API int minigpt4_amd_test_penalise_host(float *row, int n_vocab, const 
                                                  int32_t *table_out, int table_cap, int32_t *flags_out);
 MINIGPT4_API int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
                                             int32_t *picked_out, float *adjusted_out, float *ms_out);
+/* Guided decoding (minigpt4_amd.h states the rule): the kernel (launch_guide_rows, one launch, one workgroup per pair) on host logits [buf_rows][ld] fp32 (only the first
+ * n_vocab floats of a row are read).  pairs = [n][2] buffer rows (guided row, guidance row; the two may be equal, a row may serve several pairs), scales[n], row_tok_index =
+ * [n][2] indices into a 64-entry row-token array, -1 = the pair writes none.  row_tok_io[64]: the array's contents before the launch, replaced by its contents afterwards.
+ * mixed_out (may be NULL): [n][n_vocab] guided rows; pick_out / pick_value_out [n]: each row's first maximum and its value.  ms_out (may be NULL): the launch's hipEvent
+ * time.  1 = bad arguments, before any device is looked for (a NULL pointer other than mixed_out / ms_out, buf_rows < 1, n_vocab < 1, ld < n_vocab, n outside 1 .. 32, a
+ * buffer row outside [0, buf_rows), a row-token index outside [-1, 64)); 2 = no device; 3 = device error */
+MINIGPT4_API int minigpt4_amd_test_guide_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *pairs, const float *scales, const int32_t *row_tok_index,
+                                              int n, float *mixed_out, int32_t *pick_out, float *pick_value_out, int32_t *row_tok_io, float *ms_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

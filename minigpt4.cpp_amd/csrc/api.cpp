@@ -385,6 +385,30 @@ int minigpt4_amd_beam_search(struct MiniGPT4Context *ctx, const int32_t *slots, 
     if (!ctx) { set_last_error("beam_search: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->beam_search(slots, n_beams, max_tokens, length_penalty, n_best, tokens_out, lengths_out, scores_out, n_out, stats); });
 }
+// ---- guided decoding: two conversations' logits contrasted on the device -------------------------------------------------------------------------
+int minigpt4_amd_end_chat_guided(struct MiniGPT4Context *ctx, const int32_t *slots, const int32_t *neg_slots, int n, float scale, const char **tokens, float temp, int32_t top_k,
+                                 float top_p, float tfs_z, float typical_p, int mirostat, float mirostat_tau, float mirostat_eta, int32_t *ids_out) {
+    if (!ctx) { set_last_error("end_chat_guided: no context"); return 1; }
+    if (!tokens) { set_last_error("end_chat_guided: tokens is required"); return 1; }
+    Engine *e = E_(ctx);
+    return guarded(1, [&]() -> int {
+        SampleParams p; p.temp = temp; p.top_k = top_k; p.top_p = top_p; p.tfs_z = tfs_z; p.typical_p = typical_p; p.mirostat = mirostat; p.mirostat_tau = mirostat_tau; p.mirostat_eta = mirostat_eta;
+        int ids[GUIDE_MAX] = {0};
+        if (int rc = e->decode_guided(slots, neg_slots, n, scale, p, ids)) return rc;   // it refuses an n outside 1 .. GUIDE_MAX before it writes an id
+        for (int i = 0; i < n; i++) { tokens[i] = e->id_to_token(ids[i]); if (ids_out) ids_out[i] = ids[i]; }
+        return 0;
+    });
+}
+int minigpt4_amd_guided_logits(struct MiniGPT4Context *ctx, const int32_t *slots, const int32_t *neg_slots, int n, float scale, float *mixed_out, int32_t *pick_out) {
+    if (!ctx) { set_last_error("guided_logits: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->guided_logits(slots, neg_slots, n, scale, mixed_out, pick_out); });
+}
+int minigpt4_amd_guidance_info(struct MiniGPT4Context *ctx, int32_t out[4]) {
+    if (!ctx || !out) { set_last_error(ctx ? "guidance_info: no output array" : "guidance_info: no context"); return 1; }
+    const Engine::GuideInfo g = E_(ctx)->guidance_info();
+    out[0] = g.launches; out[1] = g.handed; out[2] = g.pen_picked; out[3] = g.sampled;
+    return 0;
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

@@ -101,6 +101,7 @@ Engine::~Engine() {
     pen_free();
     spec_free();
     beam_free();
+    guide_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -1595,6 +1596,7 @@ int Engine::set_conversations(int n) {
     HIP_CHECK(hipStreamSynchronize(stream_));
     release_buffers();
     beam_free();
+    guide_free();
     conv_.assign((size_t)n, Conversation{});
     cur_ = 0;
     prefix_empty();
@@ -1782,6 +1784,195 @@ int Engine::beam_search(const int *slots, int n_beams, int max_tokens, float len
     h_argmax_[src] = src_greedy;
     *n_out = book.write(n_best, stride_out, tokens_out, lengths_out, scores_out);
     for (int i = 0; i < 4; i++) stats[i] = book.stats[i];
+    return 0;
+}
+
+// ====================================================================================================================
+// guided decoding (engine.hpp; minigpt4_amd.h: the rule)
+// ====================================================================================================================
+void Engine::guide_alloc() {
+    if (guide_d_) return;
+    try {
+        HIP_CHECK(hipMalloc((void **)&guide_mix_, (size_t)GUIDE_MAX * llm_.n_vocab * 4));
+        HIP_CHECK(hipMalloc((void **)&guide_d_, GUIDE_WORDS * 4)); HIP_CHECK(hipHostMalloc((void **)&guide_h_, GUIDE_WORDS * 4, hipHostMallocDefault));
+        HIP_CHECK(hipEventCreateWithFlags(&guide_ev_, hipEventDisableTiming));
+    } catch (...) { guide_free(); throw; }
+}
+void Engine::guide_free() {
+    if (guide_mix_) HIP_IGNORE(hipFree(guide_mix_));
+    if (guide_d_) HIP_IGNORE(hipFree(guide_d_));
+    if (guide_h_) HIP_IGNORE(hipHostFree(guide_h_));
+    if (guide_ev_) HIP_IGNORE(hipEventDestroy(guide_ev_));
+    guide_mix_ = nullptr; guide_d_ = guide_h_ = nullptr; guide_ev_ = nullptr;
+}
+int Engine::guide_prepare(const char *name, const int *pos, const int *neg, int n, float scale, int *all) {
+    auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
+    if (!pos || !neg) return refuse("slots and neg_slots are required");
+    if (n < 1 || n > GUIDE_MAX || 2 * n > (int)conv_.size()) return refuse("n pairs take 2 n conversations of the context, n >= 1");
+    for (int i = 0; i < n; i++) { all[2 * i] = pos[i]; all[2 * i + 1] = neg[i]; }
+    if (check_slots(all, 2 * n)) return refuse("the 2 n conversations must be distinct and in range");
+    if (!std::isfinite(scale)) return refuse("scale must be finite");
+    if (weights_missing()) return refuse(last_error());
+    auto no_logits = [&]() -> int {
+        for (int i = 0; i < 2 * n; i++) { const Conversation &cv = conv_[(size_t)all[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return all[i]; }
+        return -1;
+    };
+    int bad = no_logits();                                                    // nothing queued and nothing evaluated: known before anything runs
+    if (bad < 0) { if (prefill_batch(all, 2 * n)) return refuse("the queued rows could not be evaluated: " + last_error()); bad = no_logits(); }
+    if (bad >= 0) return refuse("conversation " + std::to_string(bad) + " has no current logits");
+    return 0;
+}
+int Engine::guided_logits(const int *pos, const int *neg, int n, float scale, float *mixed_out, int *pick_out) {
+    int all[MAX_CONVERSATIONS];
+    if (guide_prepare("guided_logits", pos, neg, n, scale, all)) return 1;
+    const int V = (int)llm_.n_vocab;
+    guide_alloc();
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // guide_h_ feeds no earlier copy
+    GuidePair *tab = reinterpret_cast<GuidePair *>(guide_h_);
+    for (int i = 0; i < n; i++) tab[i] = GuidePair{pos[i], neg[i], scale, -1, -1, {0, 0, 0}};
+    HIP_CHECK(hipMemcpyAsync(guide_d_, guide_h_, (size_t)n * sizeof(GuidePair), hipMemcpyHostToDevice, stream_));
+    if (!launch_guide_rows(logits_, V, V, n, reinterpret_cast<const GuidePair *>(guide_d_), mixed_out ? guide_mix_ : nullptr, guide_d_ + GUIDE_PICK,
+                           reinterpret_cast<float *>(guide_d_ + GUIDE_VAL), nullptr, stream_)) { set_last_error("guided_logits: " + last_error()); return 1; }
+    guide_info_.launches++;
+    HIP_CHECK(hipMemcpyAsync(guide_h_ + GUIDE_PICK, guide_d_ + GUIDE_PICK, (size_t)n * 4, hipMemcpyDeviceToHost, stream_));
+    if (mixed_out) HIP_CHECK(hipMemcpyAsync(mixed_out, guide_mix_, (size_t)n * V * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    if (pick_out) for (int i = 0; i < n; i++) pick_out[i] = guide_h_[GUIDE_PICK + i];
+    return 0;
+}
+int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, const SampleParams &p, int *ids_out) {
+    auto refuse = [](const std::string &what) { set_last_error("end_chat_guided: " + what); return 1; };
+    if (!ids_out) return refuse("ids_out is required");
+    int all[MAX_CONVERSATIONS];
+    if (guide_prepare("end_chat_guided", pos, neg, n, scale, all)) return 1;
+    const SelectScope restore(this);
+    const int V = (int)llm_.n_vocab;
+    const bool greedy = p.temp <= 0;
+    guide_alloc();
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_, guide_h_ and pen_h_ feed no earlier copy
+    // 1. how each pair's token is chosen (the kernel's pick stands / k_pen_pick on the mixed row / the host chain), from pos's history as a sample sees it: before any shift
+    enum { KERNEL = 0, PEN = 1, CHAIN = 2 };
+    int how[GUIDE_MAX], pen_map[GUIDE_MAX], m_pen = 0; size_t pen_off = 0;
+    std::vector<PenEntry> tab;
+    PenRow *prow = nullptr; PenEntry *pent = nullptr;
+    for (int i = 0; i < n; i++) {
+        how[i] = greedy ? KERNEL : CHAIN;
+        if (!greedy) continue;
+        const Conversation &cv = conv_[(size_t)pos[i]];
+        const int flags = pen_table(cv, tab);
+        if (!flags && tab.empty()) continue;                                 // the identity
+        if (!prow) { pen_alloc(); prow = reinterpret_cast<PenRow *>(pen_h_); pent = reinterpret_cast<PenEntry *>(pen_h_ + MAX_CONVERSATIONS * sizeof(PenRow)); }
+        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
+        prow[m_pen] = PenRow{i, (int)pen_off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0};   // row = the pair's row of guide_mix_
+        std::copy(tab.begin(), tab.end(), pent + pen_off);
+        pen_off += tab.size(); pen_map[m_pen++] = i; how[i] = PEN;
+    }
+    // 2. room: both conversations of a pair advance, or neither.  The chain penalises with the history from before a shift, as decode_batch's sampling does.  Whether a shift
+    // is allowed is arithmetic (shift_allows, the queue is empty, the weights are there), so a make_room that fails here is a failure on the device: thrown like any other,
+    // not a refusal -- the header's "nothing changed" covers the refusals.  Conversations of earlier pairs that this loop has already shifted STAY shifted in that case
+    bool adv[GUIDE_MAX];
+    std::vector<std::vector<int>> hist_before((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const bool full_p = conv_[(size_t)pos[i]].n_past + 1 > n_ctx_, full_n = conv_[(size_t)neg[i]].n_past + 1 > n_ctx_;
+        adv[i] = (!full_p && !full_n) || shift_allows(1);
+        if (!adv[i]) continue;
+        if (full_p && how[i] == CHAIN) hist_before[(size_t)i] = conv_[(size_t)pos[i]].hist;
+        for (int k = 0; k < 2; k++) {
+            if (!(k ? full_n : full_p)) continue;
+            cur_ = k ? neg[i] : pos[i];
+            if (make_room(1)) throw HipError{hipErrorUnknown, "end_chat_guided: the automatic shift failed", __FILE__, __LINE__};
+        }
+    }
+    // 3. the pass's rows: the pairs whose token the kernel hands over first, then those whose token the host writes (one contiguous tail of d_btok_)
+    GuidePair *gt = reinterpret_cast<GuidePair *>(guide_h_);
+    int B = 0, n_hand = 0, row_of[GUIDE_MAX];
+    auto stage_pair = [&](int i) {
+        row_of[i] = B;
+        for (int k = 0; k < 2; k++) { const int sl = k ? neg[i] : pos[i]; h_bstage_[B] = 0; h_bstage_[MAX_CONVERSATIONS + B] = sl; h_bstage_[2 * MAX_CONVERSATIONS + B] = conv_[(size_t)sl].n_committed; B++; }
+    };
+    for (int i = 0; i < n; i++) { gt[i] = GuidePair{pos[i], neg[i], scale, -1, -1, {0, 0, 0}}; row_of[i] = -1; }
+    if (!parity_) for (int i = 0; i < n; i++) if (adv[i] && how[i] == KERNEL) { stage_pair(i); gt[i].pos_tok = row_of[i]; gt[i].neg_tok = row_of[i] + 1; n_hand++; }
+    const int host_row0 = B;
+    for (int i = 0; i < n; i++) if (adv[i] && row_of[i] < 0) stage_pair(i);
+    const bool host_first = parity_ || m_pen > 0 || !greedy;                 // some id has to reach the host before the pass can be launched
+    const bool want_mixed = m_pen > 0 || !greedy;
+    HIP_CHECK(hipMemcpyAsync(guide_d_, guide_h_, (size_t)n * sizeof(GuidePair), hipMemcpyHostToDevice, stream_));
+    if (B && !parity_) {
+        HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
+        launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
+    }
+    // 4. the decision: one launch for all pairs; the picks' copy back is awaited after the pass is launched wherever the host does not need them sooner
+    if (!launch_guide_rows(logits_, V, V, n, reinterpret_cast<const GuidePair *>(guide_d_), want_mixed ? guide_mix_ : nullptr, guide_d_ + GUIDE_PICK,
+                           reinterpret_cast<float *>(guide_d_ + GUIDE_VAL), n_hand ? d_btok_ : nullptr, stream_)) return refuse(last_error());
+    guide_info_.launches++; guide_info_.handed += n_hand; guide_info_.pen_picked += m_pen; guide_info_.sampled += greedy ? 0 : n;
+    HIP_CHECK(hipMemcpyAsync(guide_h_ + GUIDE_PICK, guide_d_ + GUIDE_PICK, (size_t)n * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipEventRecord(guide_ev_, stream_));
+    // the kernel's picks from the pinned block; false: an id outside the vocabulary (the kernel writes none; a block that never arrived), entered as 0
+    auto take_picks = [&]() -> bool {
+        bool sane = true;
+        for (int i = 0; i < n; i++) {
+            if (how[i] != KERNEL) continue;
+            ids_out[i] = guide_h_[GUIDE_PICK + i];
+            if (ids_out[i] < 0 || ids_out[i] >= V) { sane = false; ids_out[i] = 0; }
+        }
+        return sane;
+    };
+    auto bad_pick = [] { return HipError{hipErrorUnknown, "end_chat_guided: the device reported an id outside the vocabulary", __FILE__, __LINE__}; };
+    if (host_first) {
+        if (m_pen) {
+            const size_t head = MAX_CONVERSATIONS * sizeof(PenRow);
+            HIP_CHECK(hipMemcpyAsync(pen_d_, pen_h_, head + pen_off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
+            if (!launch_pen_pick(guide_mix_, V, V, m_pen, reinterpret_cast<const PenRow *>(pen_d_), reinterpret_cast<const PenEntry *>(pen_d_ + head), pen_out_d_, nullptr, stream_))
+                return refuse(last_error());
+            HIP_CHECK(hipMemcpyAsync(pen_out_h_, pen_out_d_, (size_t)m_pen * 4, hipMemcpyDeviceToHost, stream_));
+            pen_info_.launches++; pen_info_.last_entries = (int)pen_off;
+        }
+        if (!greedy) { guide_rows_.resize((size_t)n * V); HIP_CHECK(hipMemcpyAsync(guide_rows_.data(), guide_mix_, (size_t)n * V * 4, hipMemcpyDeviceToHost, stream_)); }
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        if (!take_picks()) throw bad_pick();                                 // nothing has been launched for these picks yet
+        for (int r = 0; r < m_pen; r++) {
+            if (pen_out_h_[r] < 0 || pen_out_h_[r] >= V) throw HipError{hipErrorUnknown, "the penalised pick reported an id outside the vocabulary", __FILE__, __LINE__};
+            ids_out[pen_map[r]] = pen_out_h_[r];
+        }
+        if (!greedy) for (int i = 0; i < n; i++) {                           // one draw per pair, in list order
+            const Conversation &cv = conv_[(size_t)pos[i]];
+            const std::vector<int> &h = hist_before[(size_t)i].empty() ? cv.hist : hist_before[(size_t)i];
+            float *row = guide_rows_.data() + (size_t)i * V;
+            if ((pen_mode_ || !cv.bias_id.empty()) &&
+                penalise_row(row, V, h.data(), h.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size())) pen_info_.host_rows++;
+            ids_out[i] = sampler_.sample(row, V, p);
+        }
+        for (int i = 0; i < n; i++) if (row_of[i] >= host_row0) h_bstage_[row_of[i]] = h_bstage_[row_of[i] + 1] = ids_out[i];
+    }
+    if (!B) { if (!host_first) { HIP_CHECK(hipEventSynchronize(guide_ev_)); if (!take_picks()) throw bad_pick(); } return 0; }
+    // 5. the weight pass: the batched step's own (parity mode: one oracle-order single-row pass per conversation, decode_batch's fallback)
+    if (parity_) {
+        for (int r = 0; r < B; r++) { cur_ = h_bstage_[MAX_CONVERSATIONS + r]; const int id = h_bstage_[r]; if (eval_chunk(&id, 1, nullptr)) return 1; conv_[(size_t)cur_].n_past += 1; }
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        return 0;
+    }
+    // the tail the host chose (it synchronised to choose: the slab's copy has drained, h_bstage_ is free again)
+    if (B > host_row0) HIP_CHECK(hipMemcpyAsync(d_btok_ + host_row0, h_bstage_ + host_row0, (size_t)(B - host_row0) * 4, hipMemcpyHostToDevice, stream_));
+    if (use_graph_) {
+        hipGraphExec_t &ge = batch_graph_[(size_t)B];
+        if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_); });
+        HIP_CHECK(hipGraphLaunch(ge, stream_));
+    } else forward_batch(B, stream_);
+    // the pass is still running.  It has advanced the device state whatever the block says: the host's book-keeping follows it before a bad block is reported
+    bool sane = true;
+    if (!host_first) { HIP_CHECK(hipEventSynchronize(guide_ev_)); sane = take_picks(); }
+    for (int i = 0; i < n; i++) {
+        if (!adv[i]) continue;
+        for (int k = 0; k < 2; k++) {
+            const int sl = k ? neg[i] : pos[i];
+            Conversation &cv = conv_[(size_t)sl];
+            cv.n_past += 1; cv.n_committed += 1; cv.has_logits = true;
+            cv.hist.push_back(ids_out[i]);
+            if (logits_host_slot_ == sl) logits_host_slot_ = -1;
+        }
+    }
+    HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+    if (!sane) throw bad_pick();
     return 0;
 }
 

@@ -198,6 +198,19 @@ public:
     // finished by EOS}.  tokens_out: [n_best][max_tokens + 1].  1 + last_error "beam_search: ..." and nothing changed on a refusal.  Buffers: first call; freed with the
     // context and by set_conversations.
     int beam_search(const int *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int *tokens_out, int *lengths_out, float *scores_out, int *n_out, int *stats);
+    // ---- guided decoding (classifier-free guidance; minigpt4_amd.h: the rule).  Pair i = the guided conversation pos[i] and the guidance conversation neg[i], all 2 n distinct.
+    // Queued rows of all 2 n are evaluated first (prefill_batch over them); then k_guide_rows (one launch) mixes each pair's two logits_ rows and picks.  decode_guided
+    // advances BOTH conversations of a pair by the pick through the batched step's own pass and graph (or neither: no room in one of them and no automatic shift).  temp <= 0:
+    // a pair whose pos has no bias / penalty takes the pick from the kernel straight into d_btok_ -- the host awaits the ids on an event once the pass is launched --, a pair
+    // with one runs k_pen_pick on its mixed row (pos's table) and its id travels through the host.  temp > 0: the mixed rows come to the host in one copy, then penalise_row
+    // and the chain, one draw per pair in list order.  Parity mode: the same kernel decides, one oracle-order single-row pass per conversation evaluates.  guided_logits reports
+    // the mixed rows (before bias and penalties) and their first maxima and advances nothing.  1 + last_error "end_chat_guided: ..." / "guided_logits: ..." and nothing
+    // changed: a bad list, n < 1, 2 n > the conversations, a slot out of range or repeated, a scale that is not finite; after the queued rows: a conversation without current
+    // logits.  Buffers: first call; freed with the context and by set_conversations.
+    int decode_guided(const int *pos, const int *neg, int n, float scale, const SampleParams &p, int *ids_out);
+    int guided_logits(const int *pos, const int *neg, int n, float scale, float *mixed_out, int *pick_out);
+    struct GuideInfo { int launches = 0, handed = 0, pen_picked = 0, sampled = 0; };   // k_guide_rows launches; pairs handed to the pass on the device / through k_pen_pick / the host chain
+    GuideInfo guidance_info() const { return guide_info_; }
     // ---- repetition / frequency / presence penalties and a logit bias (penalty.hpp: llama.cpp's arithmetic, one definition for host and device).  Off by default
     // (the reference ignores the arguments); minigpt4_amd.h states the rules.  Every conversation keeps a ROW-ALIGNED token history -- entry r = the token id of cache
     // row r, -1 for an embedding row -- that every path which advances or moves rows keeps in step (invariant: hist.size() == n_committed; the queued rows follow it
@@ -496,6 +509,14 @@ private:
     int encode_images_ref(const float *const *chw, int B, float *const *out);   // parity mode (engine_vision_generic.cpp)
     void build_vision_views();
     void glinear(const GLin &L, const float *x, int rows, const float *bias, bool gelu, const float *residual, float *out, hipStream_t s);
+    // (behind everything else: the members every other path reads lie where they lay before the feature)
+    // guided decoding's own lazy allocation: the mixed rows [GUIDE_MAX][n_vocab]; device words [pair table 8 x 32 | picks 32 | pick values 32] and the pinned mirror (staging of
+    // the table, landing place of the picks); the event the picks are awaited on; the host copy of the mixed rows (temp > 0, guided_logits)
+    float *guide_mix_ = nullptr; int *guide_d_ = nullptr, *guide_h_ = nullptr; hipEvent_t guide_ev_ = nullptr; std::vector<float> guide_rows_; GuideInfo guide_info_;
+    static constexpr int GUIDE_PICK = 8 * GUIDE_MAX, GUIDE_VAL = GUIDE_PICK + GUIDE_MAX, GUIDE_WORDS = GUIDE_VAL + GUIDE_MAX;
+    void guide_alloc();
+    void guide_free();
+    int guide_prepare(const char *name, const int *pos, const int *neg, int n, float scale, int *all);   // the checks, the queued rows; all[2 i] = pos[i], all[2 i + 1] = neg[i]
 };
 
 int device_count_noexcept();

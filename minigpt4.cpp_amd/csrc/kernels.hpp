@@ -222,6 +222,14 @@ bool launch_beam_select(const int *ids, const float *logprobs, float *scores, un
 // the logits are not written.  adjusted (may be null): [table entry] the transformed value.  false + last_error: n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose
 // bitmap does not fit LDS
 bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const PenRow *rows, const PenEntry *table, int *picked, float *adjusted, hipStream_t s);
+// guided decoding, one workgroup per entry of `pairs` (device), n_pairs <= GUIDE_MAX: b = logits row pos_row, g = row neg_row (at logits + row * ld, any 4-byte alignment;
+// the two may be one row, a row may serve several pairs), m[j] = lg[j] + scale * (lb[j] - lg[j]) with lb / lg the rows' log-softmax -- bit for bit launch_topn_rows'
+// log-probabilities -- and every operation rounded to fp32 on its own.  mixed (may be null): [n_pairs][n_vocab] = m; pick[p] = the first maximum of m, pick_val[p] = m[pick];
+// row_tok (may be null): row_tok[pos_tok] = row_tok[neg_tok] = pick for the indices that are >= 0 (the row tokens of the batched step that follows in the stream).  The
+// logits are not written.  false + last_error: n_pairs outside 1 .. GUIDE_MAX, n_vocab < 1, ld < n_vocab, a null table / pick / pick_val
+constexpr int GUIDE_MAX = 32;                          // pairs per launch = Engine::MAX_CONVERSATIONS / 2
+struct GuidePair { int pos_row, neg_row; float scale; int pos_tok, neg_tok, pad[3]; };   // 8 words
+bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, const GuidePair *pairs, float *mixed, int *pick, float *pick_val, int *row_tok, hipStream_t s);
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)

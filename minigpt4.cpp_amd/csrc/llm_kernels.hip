@@ -3092,6 +3092,53 @@ bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const
     hipLaunchKernelGGL(k_pen_pick, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, picked, adjusted);
     return true;
 }
+// Guided decoding (Engine::decode_guided / guided_logits; minigpt4_amd.h states the rule), one workgroup of 256 per pair, one launch for all pairs of a call.  A pair names
+// two logits rows, b (the guided conversation) and g (the guidance one), and a scale.  Sweeps: the maxima of the two rows and the two sums of exponentials through
+// row_max_first / row_sum_exp -- so lb = (b - max b) - log(sum) and lg are the bits k_logprob_rows / k_topn_rows report for the same row at the same address -- and ONE mixing
+// sweep: d = lb - lg, t = scale * d, m = lg + t, each rounded to fp32 on its own, carried into the first argmax by argmax_combine and stored to mixed[pair][n_vocab] only when
+// a buffer is given.  The mixing sweep walks b's span (scalar head, 16-byte body, scalar tail); the two rows rarely share an alignment (32 001-float rows), so g and the
+// output are addressed per element -- the rows were just written by the output mat-vec and sit in L2.  Every element's value depends on its own index only, whatever thread
+// meets it.  Exact consequences: scale == 0 gives m == lg, b == g gives m == lb (d = +0, and lb is never -0: the maximum's term is +0 - log(sum >= 1)).
+// pick[pair] = the first maximum of m (lowest id among equal values, -0 == +0), pick_val[pair] = m[pick]; row_tok (may be null): the pick goes straight into entries
+// pos_tok and neg_tok (those >= 0) -- the row tokens of the weight pass that follows in the stream, as k_beam_select writes them.  Logits are finite (NaN / infinities:
+// unspecified).  Nothing beyond n_vocab floats of a row is read; the rows are never written.  No atomics, no LDS beyond 32 words of reduction scratch.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 42 VGPRs, 66 SGPRs, no scratch, 128 bytes of LDS, occupancy 8 waves per SIMD.
+__global__ __launch_bounds__(256) void k_guide_rows(const float *__restrict__ logits, int ld, int n_vocab, const GuidePair *__restrict__ pairs, float *__restrict__ mixed,
+                                                    int *__restrict__ pick, float *__restrict__ pick_val, int *__restrict__ row_tok) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const GuidePair gp = pairs[r];
+    const float *b = logits + (size_t)gp.pos_row * ld, *g = logits + (size_t)gp.neg_row * ld;
+    const RowSpan sb = row_span(b, n_vocab), sg = row_span(g, n_vocab);
+    __shared__ float sv[3][4], ss[2][4]; __shared__ int si[3][4];              // one set per reduction: no word is written while another wave may still read it
+    float max_b, max_g; int at_b, at_g;
+    row_max_first(sb, tid, sv[0], si[0], max_b, at_b);
+    row_max_first(sg, tid, sv[1], si[1], max_g, at_g);
+    const float lse_b = logf(row_sum_exp(sb, tid, max_b, ss[0])), lse_g = logf(row_sum_exp(sg, tid, max_g, ss[1]));
+    float *out = mixed ? mixed + (size_t)r * n_vocab : nullptr;
+    const float scale = gp.scale;
+    float best = -INFINITY; int bi = 0x7FFFFFFF;
+    row_sweep(sb, tid, [&](float v, int i) {
+        const float lb = __fsub_rn(__fsub_rn(v, max_b), lse_b), lg = __fsub_rn(__fsub_rn(g[i], max_g), lse_g);
+        const float m = __fadd_rn(lg, __fmul_rn(scale, __fsub_rn(lb, lg)));
+        if (out) out[i] = m;
+        argmax_combine(best, bi, m, i);
+    });
+    argmax_wave(best, bi);
+    if ((tid & 63) == 0) { sv[2][tid >> 6] = best; si[2][tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[2][w], si[2][w]);
+        const int id = bi == 0x7FFFFFFF ? 0 : bi;
+        pick[r] = id; pick_val[r] = best;
+        if (row_tok) { if (gp.pos_tok >= 0) row_tok[gp.pos_tok] = id; if (gp.neg_tok >= 0) row_tok[gp.neg_tok] = id; }
+    }
+}
+bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, const GuidePair *pairs, float *mixed, int *pick, float *pick_val, int *row_tok, hipStream_t s) {
+    if (!logits || !pairs || !pick || !pick_val || n_pairs < 1 || n_pairs > GUIDE_MAX || n_vocab < 1 || ld < n_vocab) { set_last_error("launch_guide_rows: shape out of range"); return false; }
+    note_kernel("k_guide_rows");
+    hipLaunchKernelGGL(k_guide_rows, dim3((unsigned)n_pairs), dim3(256), 0, s, logits, ld, n_vocab, pairs, mixed, pick, pick_val, row_tok);
+    return true;
+}
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {
     const int r = threadIdx.x;

@@ -1016,6 +1016,37 @@ int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, i
         return 0;
     });
 }
+// ---- guided decoding (launch_guide_rows) ----
+// k_guide_rows, one launch, on host logits [buf_rows][ld]: pairs = [n][2] buffer rows (guided, guidance), scales[n], row_tok_index = [n][2] indices into a 64-entry row-token
+// array (-1: not written) that starts as row_tok_io and is returned there.  mixed_out (may be NULL): [n][n_vocab].  Everything that indexes device memory is checked here.
+int minigpt4_amd_test_guide_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *pairs, const float *scales, const int32_t *row_tok_index, int n,
+                                 float *mixed_out, int32_t *pick_out, float *pick_value_out, int32_t *row_tok_io, float *ms_out) {
+    if (!logits || !pairs || !scales || !row_tok_index || !pick_out || !pick_value_out || !row_tok_io || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n < 1 || n > GUIDE_MAX) return 1;
+    for (int i = 0; i < 2 * n; i++) if (pairs[i] < 0 || pairs[i] >= buf_rows || row_tok_index[i] < -1 || row_tok_index[i] >= 64) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        static_assert(sizeof(GuidePair) == 32, "the pair table is 8 words per pair");
+        const size_t total = (size_t)buf_rows * ld, P = (size_t)n, PV = P * (size_t)n_vocab;
+        std::vector<GuidePair> tab(P);
+        for (int i = 0; i < n; i++) tab[(size_t)i] = GuidePair{pairs[2 * i], pairs[2 * i + 1], scales[i], row_tok_index[2 * i], row_tok_index[2 * i + 1], {0, 0, 0}};
+        DevBuf dl(total * 4), dt(P * sizeof(GuidePair)), dm(PV * 4), dp(P * 4), dv(P * 4), dr(64 * 4);
+        HIP_CHECK(hipMemcpy(dl.p, logits, total * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, tab.data(), P * sizeof(GuidePair), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dr.p, row_tok_io, 64 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dm.p, 0xFF, PV * 4)); HIP_CHECK(hipMemset(dp.p, 0xFF, P * 4)); HIP_CHECK(hipMemset(dv.p, 0xFF, P * 4));   // what the kernel leaves out shows as NaN / id -1
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_guide_rows(dl.as<float>(), ld, n_vocab, n, dt.as<GuidePair>(), mixed_out ? dm.as<float>() : nullptr, dp.as<int>(), dv.as<float>(), dr.as<int>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        if (mixed_out) HIP_CHECK(hipMemcpy(mixed_out, dm.p, PV * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(pick_out, dp.p, P * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(pick_value_out, dv.p, P * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(row_tok_io, dr.p, 64 * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
 static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {

@@ -222,6 +222,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_token_history.argtypes = [VOID_PTR, INT_PTR, I32]
         L.minigpt4_amd_penalty_info.argtypes = [VOID_PTR, INT_PTR]
         L.minigpt4_amd_beam_search.argtypes = [VOID_PTR, INT_PTR, I32, I32, F32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_end_chat_guided.argtypes = [VOID_PTR, INT_PTR, INT_PTR, I32, F32, ctypes.POINTER(ctypes.c_char_p), F32, I32, F32, F32, F32, I32, F32, F32, INT_PTR]
+        L.minigpt4_amd_guided_logits.argtypes = [VOID_PTR, INT_PTR, INT_PTR, I32, F32, FLOAT_PTR, INT_PTR]
+        L.minigpt4_amd_guidance_info.argtypes = [VOID_PTR, INT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -265,6 +268,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_beam_select.argtypes = [I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, ctypes.c_uint32, I32, I32, INT_PTR, INT_PTR]
         L.minigpt4_amd_test_kv_permute.argtypes = [I32, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_pen_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_guide_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, I32, FLOAT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
@@ -551,6 +555,85 @@ class MiniGPT4SharedLibrary:
         if with_stats:
             return hyps, dict(passes=int(st[0]), permutes=int(st[1]), rows_moved=int(st[2]), finished=int(st[3]))
         return hyps
+
+    # ---- guided decoding (include/minigpt4_amd.h)
+    @staticmethod
+    def _guided_args(name: str, slots: Sequence[int], neg_slots: Sequence[int], scale: float):
+        """The two slot lists as int32 arrays; ValueError before the library is touched."""
+        sl, ng = np.ascontiguousarray(slots, np.int32).reshape(-1), np.ascontiguousarray(neg_slots, np.int32).reshape(-1)
+        if len(sl) != len(ng):
+            raise ValueError(f"{name}: slots and neg_slots must have the same length")
+        if len(sl) < 1 or len(sl) > 32:
+            raise ValueError(f"{name}: 1 .. 32 pairs")
+        both = np.concatenate([sl, ng])
+        if len(np.unique(both)) != len(both):
+            raise ValueError(f"{name}: a conversation may be named once, in one of the two lists")
+        if both.min() < 0:
+            raise ValueError(f"{name}: conversation index out of range")
+        if not np.isfinite(ctypes.c_float(float(scale)).value):     # as the fp32 the library takes
+            raise ValueError(f"{name}: scale must be finite")
+        return sl, ng
+
+    def amd_end_chat_guided(self, ctx, slots: Sequence[int], neg_slots: Sequence[int], scale: float, temp=0.8, top_k=40, top_p=0.9, tfs_z=1.0, typical_p=1.0, mirostat=0,
+                            mirostat_tau=5.0, mirostat_eta=1.0, with_ids: bool = False):
+        """One guided decode step: pair i decides ONE token from the logits of conversation slots[i] contrasted with those of neg_slots[i] (scale 1 = no guidance) and both
+        advance by it in one pass over the weights.  Returns one piece per pair; with_ids: (pieces, ids i32 array).  include/minigpt4_amd.h states the rule."""
+        sl, ng = self._guided_args("end_chat_guided", slots, neg_slots, scale)
+        toks, ids = (ctypes.c_char_p * len(sl))(), np.zeros(len(sl), np.int32)
+        rc = self.library.minigpt4_amd_end_chat_guided(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), ng.ctypes.data_as(INT_PTR), len(sl), float(scale), toks,
+                                                       temp, top_k, top_p, tfs_z, typical_p, mirostat, mirostat_tau, mirostat_eta, ids.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError("end_chat_guided failed: " + self._err())
+        pieces = [(t or b"").decode("utf-8", errors="replace") for t in toks]
+        return (pieces, ids) if with_ids else pieces
+
+    def amd_guided_logits(self, ctx, slots: Sequence[int], neg_slots: Sequence[int], scale: float, with_rows: bool = True) -> dict:
+        """The guided rows of the listed pairs BEFORE bias and penalties, and their first maxima; nothing advances.  dict(mixed f32 [n][n_vocab] (None without with_rows),
+        pick i32 [n])."""
+        sl, ng = self._guided_args("guided_logits", slots, neg_slots, scale)
+        n = len(sl)
+        pick = np.zeros(n, np.int32)
+        mixed = np.zeros((n, self.library.minigpt4_amd_n_vocab(ctx.ptr)), np.float32) if with_rows and ctx is not None else None
+        rc = self.library.minigpt4_amd_guided_logits(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), ng.ctypes.data_as(INT_PTR), n, float(scale),
+                                                     None if mixed is None else mixed.ctypes.data_as(FLOAT_PTR), pick.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError("guided_logits failed: " + self._err())
+        return dict(mixed=mixed, pick=pick)
+
+    def amd_guidance_info(self, ctx) -> dict:
+        """dict(launches: k_guide_rows launches so far, handed: pairs whose token went to the pass on the device, pen_picked: pairs picked through k_pen_pick, sampled: pairs
+        sampled on the host)."""
+        o = np.zeros(4, np.int32)
+        if self.library.minigpt4_amd_guidance_info(ctx.ptr if ctx is not None else None, o.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("guidance_info failed: " + self._err())
+        return dict(launches=int(o[0]), handed=int(o[1]), pen_picked=int(o[2]), sampled=int(o[3]))
+
+    def amd_test_guide_rows(self, logits: np.ndarray, pairs, scales: Sequence[float], n_vocab: Optional[int] = None, row_tok_index=None, row_tok: Optional[Sequence[int]] = None,
+                            with_rows: bool = True) -> dict:
+        """k_guide_rows, one launch, on logits [rows][ld] (include/minigpt4_amd_test.h): pairs [n][2] buffer rows (guided, guidance), scales [n], row_tok_index [n][2] indices
+        into a 64-entry row-token array (-1 / None: none), row_tok its contents before the launch (default: all -7).  dict(mixed [n][n_vocab] or None, pick, value, row_tok
+        [64], ms)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.ndim != 2:
+            raise ValueError("test_guide_rows: logits must be [rows][ld]")
+        nv = lg.shape[1] if n_vocab is None else int(n_vocab)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = len(pr)
+        sc = np.ascontiguousarray(scales, np.float32).reshape(-1)
+        ti = np.full((n, 2), -1, np.int32) if row_tok_index is None else np.ascontiguousarray(row_tok_index, np.int32).reshape(-1, 2)
+        if len(sc) != n or len(ti) != n:
+            raise ValueError("test_guide_rows: pairs, scales and row_tok_index must name the same number of pairs")
+        rt = np.full(64, -7, np.int32) if row_tok is None else np.ascontiguousarray(row_tok, np.int32).copy()
+        if rt.shape != (64,):
+            raise ValueError("test_guide_rows: row_tok must hold 64 entries")
+        mixed = np.zeros((n, max(nv, 1)), np.float32) if with_rows else None
+        pick, val, ms = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32), ctypes.c_float(0)
+        rc = self.library.minigpt4_amd_test_guide_rows(lg.ctypes.data_as(FLOAT_PTR), lg.shape[0], nv, lg.shape[1], pr.ctypes.data_as(INT_PTR), sc.ctypes.data_as(FLOAT_PTR),
+                                                       ti.ctypes.data_as(INT_PTR), n, None if mixed is None else mixed.ctypes.data_as(FLOAT_PTR), pick.ctypes.data_as(INT_PTR),
+                                                       val.ctypes.data_as(FLOAT_PTR), rt.ctypes.data_as(INT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_guide_rows rc={rc}: " + self._err())
+        return dict(mixed=mixed, pick=pick[:n], value=val[:n], row_tok=rt, ms=float(ms.value))
 
     def amd_test_beam_select_host(self, ids: np.ndarray, logprobs: np.ndarray, length_penalty: float = 1.0, n_best: Optional[int] = None, position: int = 0,
                                   scores0: Optional[Sequence[float]] = None, live0: int = 0, eos: int = 2) -> dict:

@@ -68,8 +68,14 @@ class ReplicaServer:
 
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
             batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
-            frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0) -> List[str]:
-        """num_beams > 1: beam search (`minigpt4_amd_beam_search`) instead of the decode loop -- every request takes num_beams conversations (its own and num_beams - 1 of
+            frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
+            negative_prompt: Optional[str] = None) -> List[str]:
+        """guidance_scale != 1: guided decoding (classifier-free guidance, `minigpt4_amd_end_chat_guided`) -- every request takes two conversations, so a wave holds
+        conversations // 2 requests: its own, and a guidance conversation that gets the system prompt and `minigpt4_begin_chat` of the request's prompt WITHOUT the image
+        (negative_prompt given: of that text instead); with batched_prefill both kinds go into the one `minigpt4_amd_prefill_batch`.  Every step decides one token per
+        request from the two conversations' logits (scale > 1 pushes away from the guidance conversation) and advances both; penalties and logit bias act on the guided
+        row, the stop rule is the decode loop's.  Not available with logprobs > 0 or num_beams > 1.  guidance_scale = 1 (the default) is exactly the decode loop below.
+        num_beams > 1: beam search (`minigpt4_amd_beam_search`) instead of the decode loop -- every request takes num_beams conversations (its own and num_beams - 1 of
         scratch), so a wave holds conversations // num_beams requests; the answer is the best hypothesis (final score = sum of log-probabilities / length ** length_penalty),
         cut by the same "###" rule.  The search decides on raw logits: temp / top_k / top_p, penalties and logit bias do not enter it; logprobs is not available with it.
         num_beams = 1 (the default) is exactly the decode loop below.
@@ -84,13 +90,20 @@ class ReplicaServer:
             raise ValueError("num_beams must be 1 .. min(8, conversations)")
         if num_beams > 1 and logprobs > 0:
             raise ValueError("logprobs is not available with num_beams > 1")
+        guided = guidance_scale != 1.0
+        if guided and not np.isfinite(guidance_scale):
+            raise ValueError("guidance_scale must be finite")
+        if guided and (logprobs > 0 or num_beams > 1):
+            raise ValueError("guidance_scale != 1 is not available with logprobs > 0 or num_beams > 1")
+        if guided and self.conversations < 2:
+            raise ValueError("guidance_scale != 1 takes two conversations per request")
         answers: List[str] = [""] * len(requests)
         penalised = repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
         mode_before = lib.amd_penalty_info(ctx)["mode"] if penalised else 0
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
-                             num_beams, length_penalty)
+                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt)
         finally:
             if penalised or logit_bias:
                 for slot in range(self.conversations):
@@ -123,13 +136,13 @@ class ReplicaServer:
                 shown += piece
         return shown
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0) -> List[str]:
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         if penalised:
             lib.amd_set_penalties(ctx, True)
         self.last_logprobs = [[] for _ in requests] if logprobs > 0 else None
-        per = num_beams                                           # conversations per request: its own, then the search's scratch
+        per = 2 if guidance is not None else num_beams            # conversations per request: its own, then the guidance conversation / the search's scratch
         for wave in plan_waves(len(requests), self.conversations // per):
             structs, owned = [], []
             for i in wave:
@@ -150,9 +163,14 @@ class ReplicaServer:
                         lib.amd_conversation_penalties(ctx, slot, **pen)
                     if logit_bias:
                         lib.amd_set_logit_bias(ctx, logit_bias)
+                    if guidance is not None:                  # the guidance conversation: the same question (or the negative prompt) asked without the image
+                        lib.amd_select_conversation(ctx, slot + 1)
+                        lib.minigpt4_reset_chat(ctx)
+                        lib.minigpt4_system_prompt(ctx)
+                        lib.minigpt4_begin_chat(ctx, requests[i].prompt if negative_prompt is None else negative_prompt)
                 if batched_prefill:                           # the wave's prompts in one pass per chunk instead of one pass per conversation
-                    lib.amd_prefill_batch(ctx, [j * per for j in range(len(wave))])
-                if per > 1:
+                    lib.amd_prefill_batch(ctx, [j * per + k for j in range(len(wave)) for k in range(2 if guidance is not None else 1)])
+                if num_beams > 1:
                     for j, i in enumerate(wave):
                         answers[i] = self._beam_answer(list(range(j * per, (j + 1) * per)), requests[i].max_tokens, length_penalty, ignore_eos)
                     continue
@@ -168,6 +186,8 @@ class ReplicaServer:
                             self.last_logprobs[wave[slot]].append(dict(
                                 id=int(step["ids"][r]), piece=pieces[r], logprob=float(step["logprob"][r]), rank=int(step["rank"][r]),
                                 top=[(lib.amd_token_piece(ctx, int(t)), float(v)) for t, v in zip(step["top_ids"][r], step["top_logprobs"][r])]))
+                    elif guidance is not None:
+                        pieces = lib.amd_end_chat_guided(ctx, [2 * slot for slot in active], [2 * slot + 1 for slot in active], guidance, temp=temp, top_k=top_k, top_p=top_p)
                     else:
                         pieces = lib.amd_end_chat_batch(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
                     nxt = []
@@ -208,7 +228,7 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     try:
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
                                                                                                 "presence_penalty", "frequency_penalty", "logit_bias", "num_beams",
-                                                                                                "length_penalty")})
+                                                                                                "length_penalty", "guidance_scale", "negative_prompt")})
     finally:
         server.close()
     mapping = dict(zip(mine, out))
