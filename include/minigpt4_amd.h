@@ -333,6 +333,50 @@ MINIGPT4_API int minigpt4_amd_end_chat_guided(struct MiniGPT4Context *ctx, const
 MINIGPT4_API int minigpt4_amd_guided_logits(struct MiniGPT4Context *ctx, const int32_t *slots, const int32_t *neg_slots, int n, float scale, float *mixed_out, int32_t *pick_out);
 MINIGPT4_API int minigpt4_amd_guidance_info(struct MiniGPT4Context *ctx, int32_t out[4]);
 
+/* ---- constrained decoding: a regular expression per conversation, enforced on the device ------------------------------------------------------------
+ * The text a constrained conversation generates -- the bytes of its picked tokens, concatenated -- is kept inside a pattern, and "</s>" is allowed exactly where the text so
+ * far matches the WHOLE pattern.  The pattern is compiled once to a byte-level DFA of at most 1024 states (0 = dead, 1 = start); one kernel then builds, for every state,
+ * the bitmap of token ids that may follow (k_constrain_index), and a greedy step costs one small launch that takes the first maximum of the transformed logits row over
+ * the allowed ids (k_constrain_pick).
+ * Pattern syntax (bytes, UTF-8): a literal byte;  .  (any byte except 0x0A);  [...] and [^...] with ranges, a ']' in first place a literal, escapes allowed inside, a byte
+ * >= 0x80 inside refused (write \xHH);  ( ) and (?: ), both without capture;  |  with empty alternatives;  * + ? {m} {m,} {m,n} with 0 <= m <= n <= 255 (they stack: a**);
+ * \d \w \s \D \W \S (ASCII; the negations range over all 256 bytes), \n \t \r \f \v \0 \xHH, \ + ASCII punctuation = that byte.  A multi-byte UTF-8 character outside a
+ * class is its byte sequence and a quantifier behind it applies to the whole character; '.' and negated classes match ONE BYTE.  Refused, with the byte offset: anchors,
+ * lazy and possessive quantifiers, back-references, look-around and every other (? group, \ + any other letter or digit, a bare quantifier, groups nested deeper than
+ * 250.  Also refused: a pattern longer than 4096 bytes, "too many states" (more than 16 384 positions after the counted repeats are expanded, more than 8192 subsets,
+ * more than 1024 states of the minimal automaton), "matches nothing".
+ * Constraints belong to the CONTEXT, at most 8 at a time (handles 1 .. 8); they depend on the vocabulary only and survive minigpt4_amd_set_conversations and parity switches.
+ * minigpt4_amd_constraint_compile: n_bytes = -1 takes strlen(pattern).  Compiles, uploads, builds the index and synchronises.
+ * minigpt4_amd_constraint_free: refused while a conversation uses the handle.
+ * minigpt4_amd_set_constraint: handle 0 clears; the conversation's state always goes to the start.  The assignment survives minigpt4_reset_chat (which returns the state to
+ * the start), like the logit bias; minigpt4_amd_set_conversations clears it; a fork touches neither handle nor state of any conversation.
+ * minigpt4_amd_constraint_advance: walks the state over n token ids on the host, for callers who feed tokens themselves; id 2 ("</s>") leaves the state where it is; a
+ * token that leads to the dead state refuses the whole call and changes nothing.
+ * minigpt4_amd_constraint_info: out = {handle, state, 1 if the state accepts, states of the automaton, k_constrain_pick launches, rows masked on the host for the sampling
+ * chain, picks that found no allowed id, k_constrain_index launches}; the last four count over the context.
+ * minigpt4_amd_constraint_mask: out[n_words] <- the device index row of (handle, state): bit i of word i / 32 = token i is allowed.  n_words must be at least
+ * (n_vocab + 31) / 32 rounded up to a multiple of 4.  Bits: an id >= 3 whose piece is not empty and whose bytes do not lead to the dead state; id 2 iff the state accepts;
+ * never ids 0 and 1.
+ * Where it acts: minigpt4_end_chat(_image), minigpt4_amd_sample, minigpt4_amd_end_chat_batch and _end_chat_batch_top, in llama.cpp's order: logit bias, penalties,
+ * constraint, then the pick or the chain.  temp <= 0: ONE k_constrain_pick launch over the constrained conversations of the call -- it applies their penalty tables itself,
+ * so k_pen_pick skips them --, 4 bytes per conversation come back.  The pick is the FIRST maximum over the allowed ids (lowest id among equal values, -0 == +0); a state
+ * without an allowed id picks "</s>" and counts as stuck (a vocabulary with all 256 byte tokens never gets there).  temp > 0: the state's index row comes to the host and
+ * every other id of the chain's copy of the row becomes -infinity.  The state belongs to the sampler, like the generator: every constrained pick -- minigpt4_amd_sample's
+ * included -- advances it by the picked token, whether or not the conversation then has room to advance.  Parity mode changes nothing: the decision is exact either way.
+ * What stays raw: minigpt4_amd_get_logits, scoring, minigpt4_amd_top_logprobs and the _top report describe raw logits; minigpt4_amd_eval_batch neither consults nor
+ * advances a constraint.  A conversation without a constraint takes exactly the path it took before: no launch, no copy, no allocation (the vocabulary on the device, the
+ * staging and the indices are allocated by the first compile and freed with the context).
+ * Each call returns 0, or 1 with "<short name>: ..." in minigpt4_amd_last_error and nothing changed.
+ * Not built: minigpt4_amd_end_chat_guided, minigpt4_amd_verify_draft, minigpt4_amd_decode_lookup, minigpt4_amd_beam_search and minigpt4_amd_decode_loop neither consult
+ * nor advance a constraint; context-free grammars and JSON-schema translation; character-level '.' and negated classes; handing the constrained pick to the weight pass
+ * without the host visit. */
+MINIGPT4_API int minigpt4_amd_constraint_compile(struct MiniGPT4Context *ctx, const char *pattern, int n_bytes, int32_t *handle);
+MINIGPT4_API int minigpt4_amd_constraint_free(struct MiniGPT4Context *ctx, int32_t handle);
+MINIGPT4_API int minigpt4_amd_set_constraint(struct MiniGPT4Context *ctx, int slot, int32_t handle);
+MINIGPT4_API int minigpt4_amd_constraint_advance(struct MiniGPT4Context *ctx, int slot, const int32_t *tokens, int n);
+MINIGPT4_API int minigpt4_amd_constraint_info(struct MiniGPT4Context *ctx, int slot, int32_t out[8]);
+MINIGPT4_API int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32_t handle, int state, uint32_t *out, int n_words);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

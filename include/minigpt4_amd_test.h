@@ -173,6 +173,23 @@ MINIGPT4_API int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, i
  * buffer row outside [0, buf_rows), a row-token index outside [-1, 64)); 2 = no device; 3 = device error */
 MINIGPT4_API int minigpt4_amd_test_guide_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *pairs, const float *scales, const int32_t *row_tok_index,
                                               int n, float *mixed_out, int32_t *pick_out, float *pick_value_out, int32_t *row_tok_io, float *ms_out);
+/* Constrained decoding (minigpt4_amd.h states the pattern language and the rules).
+ * minigpt4_amd_test_constraint_compile, no GPU: the compiler alone.  n_bytes = -1: strlen.  trans_out (may be NULL) receives [n_states][256] entries when cap_states >=
+ * n_states, accept_out (may be NULL) the accepting bitmap, 32 words; *n_states_out = the automaton's states (0 = dead, 1 = start).  0; 1 = refused, the compiler's text in
+ * err (may be NULL; err_cap bytes); -1 = bad arguments.
+ * minigpt4_amd_test_constrain_index: k_constrain_index alone (one launch, one workgroup per state) on a GIVEN vocabulary -- vocab = the pieces' bytes back to back, off
+ * [n_vocab + 1] where each begins -- and a given table trans [n_states][256] / accepting bitmap accept [(n_states + 31) / 32]; index_out [n_states][W], W = (n_vocab + 31)
+ * / 32 rounded up to 4.  1 = bad arguments, before any device is touched (a NULL array, n_vocab < 1, n_states outside 2 .. 1024, offsets that do not start at 0 or
+ * decrease, a table entry >= n_states); 2 = no device; 3 = device error.
+ * minigpt4_amd_test_constrain_pick: k_constrain_pick alone (one launch, one workgroup per row) on host logits [buf_rows][ld].  rows / table as for
+ * minigpt4_amd_test_pen_pick (entries 0 for a row without penalties); bitmaps = [n_bitmaps][W] allowed-id bitmaps, bitmap_of_row[n_rows] names each row's.  out[n_rows] =
+ * the picked id, with bit 30 set when the row had no allowed id (the id is then 2).  1 = bad arguments as for _test_pen_pick, or a bitmap index out of range. */
+MINIGPT4_API int minigpt4_amd_test_constraint_compile(const char *pattern, int n_bytes, uint16_t *trans_out, uint32_t *accept_out, int cap_states, int32_t *n_states_out,
+                                                      char *err, size_t err_cap);
+MINIGPT4_API int minigpt4_amd_test_constrain_index(const uint8_t *vocab, const int32_t *off, int n_vocab, const uint16_t *trans, const uint32_t *accept, int n_states,
+                                                   uint32_t *index_out, float *ms_out);
+MINIGPT4_API int minigpt4_amd_test_constrain_pick(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
+                                                  const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, int32_t *out, float *ms_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

@@ -409,6 +409,31 @@ int minigpt4_amd_guidance_info(struct MiniGPT4Context *ctx, int32_t out[4]) {
     out[0] = g.launches; out[1] = g.handed; out[2] = g.pen_picked; out[3] = g.sampled;
     return 0;
 }
+// ---- constrained decoding: a regular expression per conversation ----------------------------------------------------------------------------------
+int minigpt4_amd_constraint_compile(struct MiniGPT4Context *ctx, const char *pattern, int n_bytes, int32_t *handle) {
+    if (!ctx) { set_last_error("constraint_compile: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->constraint_compile(reinterpret_cast<const unsigned char *>(pattern), n_bytes, handle); });
+}
+int minigpt4_amd_constraint_free(struct MiniGPT4Context *ctx, int32_t handle) {
+    if (!ctx) { set_last_error("constraint_free: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->constraint_free(handle); });
+}
+int minigpt4_amd_set_constraint(struct MiniGPT4Context *ctx, int slot, int32_t handle) {
+    if (!ctx) { set_last_error("set_constraint: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_constraint(slot, handle); });
+}
+int minigpt4_amd_constraint_advance(struct MiniGPT4Context *ctx, int slot, const int32_t *tokens, int n) {
+    if (!ctx) { set_last_error("constraint_advance: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->constraint_advance(slot, tokens, n); });
+}
+int minigpt4_amd_constraint_info(struct MiniGPT4Context *ctx, int slot, int32_t out[8]) {
+    if (!ctx) { set_last_error("constraint_info: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->constraint_info(slot, out); });
+}
+int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32_t handle, int state, uint32_t *out, int n_words) {
+    if (!ctx) { set_last_error("constraint_mask: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->constraint_mask(handle, state, out, n_words); });
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

@@ -102,6 +102,7 @@ Engine::~Engine() {
     spec_free();
     beam_free();
     guide_free();
+    con_free();
     release_buffers();
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
@@ -1453,10 +1454,25 @@ int Engine::greedy_raw() {
     return h_argmax_[cur_];                                                  // greedy: argmax computed on the device
 }
 int Engine::sample_token(const SampleParams &p) {
-    if (p.temp <= 0) { int id = greedy_raw(); pen_pick(&cur_, 1, &id); return id; }
+    if (p.temp <= 0) { int id = greedy_raw(); pen_pick(&cur_, 1, &id); con_pick(&cur_, 1, &id); return id; }
     if (flush()) throw HipError{hipErrorUnknown, "deferred evaluation failed", __FILE__, __LINE__};
     const Conversation &cv = conv_[(size_t)cur_];
     const float *raw = logits_host();
+    if (con_handle_[cur_] && cv.has_logits) {   // bias, penalties, then the constraint: the ids outside the state's allowed set leave the chain's copy of the row
+        const int V = (int)llm_.n_vocab;
+        pen_row_.assign(raw, raw + V);
+        if ((pen_mode_ || !cv.bias_id.empty()) &&
+            penalise_row(pen_row_.data(), V, cv.hist.data(), cv.hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size()))
+            pen_info_.host_rows++;
+        const unsigned *allowed = con_fetch_row(con_handle_[cur_], con_state_[cur_]);
+        bool any = false;
+        for (int i = 0; i < V; i++) { if ((allowed[i >> 5] >> (i & 31)) & 1u) any = true; else pen_row_[(size_t)i] = -INFINITY; }
+        con_info_.host_rows++;
+        if (!any) { con_info_.stuck++; return CONSTRAINT_EOS; }             // as k_constrain_pick: nothing allowed picks EOS
+        const int id = sampler_.sample(pen_row_.data(), V, p);
+        con_walk(cur_, id);
+        return id;
+    }
     if (pen_mode_ || !cv.bias_id.empty()) {   // the chain sees penalised logits, as in llama.cpp; h_logits_ (minigpt4_amd_get_logits) stays raw
         const int V = (int)llm_.n_vocab;
         const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
@@ -1598,6 +1614,7 @@ int Engine::set_conversations(int n) {
     beam_free();
     guide_free();
     conv_.assign((size_t)n, Conversation{});
+    std::fill(con_handle_, con_handle_ + MAX_CONVERSATIONS, 0); std::fill(con_state_, con_state_ + MAX_CONVERSATIONS, 0); con_assigned_ = 0;   // the compiled constraints stay
     cur_ = 0;
     prefix_empty();
     alloc_buffers();
@@ -1629,7 +1646,8 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
     // 1. pending prompt rows of each conversation (its own prefill pass), then sample
     // (greedy with penalties or a bias: the raw ids first, then ONE launch over the listed conversations replaces those the transformation can change)
     for (int i = 0; i < n; i++) { cur_ = slots[i]; ids_out[i] = p.temp <= 0 ? greedy_raw() : sample_token(p); }
-    if (p.temp <= 0) pen_pick(slots, n, ids_out);
+    // (forced tokens -- minigpt4_amd_eval_batch -- neither consult nor advance a constraint)
+    if (p.temp <= 0) { pen_pick(slots, n, ids_out, !forced); if (!forced) con_pick(slots, n, ids_out); }
     // 2. one weight pass for the conversations that still have room
     HIP_CHECK(hipStreamSynchronize(stream_));                                // h_bstage_ may still feed the previous step's copies
     // the report reads the rows the ids were drawn from: behind the sampling, ahead of the pass that overwrites them (one in-order stream); its copy back is queued here
@@ -1996,7 +2014,7 @@ int Engine::pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const 
     return pen_build_table(cv.hist.data(), cv.hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, (int)llm_.n_vocab, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size(), tab);
 }
 // The caller has evaluated every listed conversation's queue and synchronised (greedy_raw): hist is the whole history, the pinned staging is free.
-void Engine::pen_pick(const int *slots, int n, int *ids) {
+void Engine::pen_pick(const int *slots, int n, int *ids, bool skip_constrained) {
     bool any = pen_mode_;
     for (int i = 0; i < n && !any; i++) any = !conv_[(size_t)slots[i]].bias_id.empty();
     if (!any) return;                                                        // mode off, no bias: today's path
@@ -2005,7 +2023,7 @@ void Engine::pen_pick(const int *slots, int n, int *ids) {
     PenRow *rows = nullptr; PenEntry *ent = nullptr;
     for (int i = 0; i < n; i++) {
         const Conversation &cv = conv_[(size_t)slots[i]];
-        if (!cv.has_logits) continue;
+        if (!cv.has_logits || (skip_constrained && con_handle_[slots[i]])) continue;   // (a constrained conversation: k_constrain_pick applies its table)
         const int flags = pen_table(cv, tab);
         if (!flags && tab.empty()) continue;                                 // the identity: the raw greedy id stands
         if (!rows) { pen_alloc(); rows = reinterpret_cast<PenRow *>(pen_h_); ent = reinterpret_cast<PenEntry *>(pen_h_ + MAX_CONVERSATIONS * sizeof(PenRow)); }
@@ -2051,6 +2069,158 @@ int Engine::set_logit_bias(const int *ids, const float *bias, int n) {
     Conversation &cv = conv_[(size_t)cur_];
     cv.bias_id.assign(ids, ids + n); cv.bias_val.assign(bias, bias + n);
     return 0;
+}
+
+// ---- constrained decoding (engine.hpp, constraint.hpp) ----
+void Engine::con_alloc() {
+    if (con_vocab_) return;
+    const size_t V = llm_.n_vocab;
+    std::vector<int> off(V + 1, 0);
+    for (size_t i = 0; i < V; i++) off[i + 1] = off[i] + (int)(i < llm_.pieces.size() ? llm_.pieces[i].size() : 0);
+    std::vector<unsigned char> blob((size_t)off[V] + 1, 0);
+    for (size_t i = 0; i < V && i < llm_.pieces.size(); i++) std::copy(llm_.pieces[i].begin(), llm_.pieces[i].end(), blob.begin() + off[i]);
+    const size_t stage = (size_t)MAX_CONVERSATIONS * (sizeof(ConRow) + (size_t)PEN_TABLE_MAX * sizeof(PenEntry));
+    try {
+        HIP_CHECK(hipMalloc((void **)&con_vocab_, blob.size())); HIP_CHECK(hipMalloc((void **)&con_off_, (V + 1) * 4));
+        HIP_CHECK(hipMalloc((void **)&con_d_, stage)); HIP_CHECK(hipHostMalloc((void **)&con_h_, stage, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc((void **)&con_out_d_, MAX_CONVERSATIONS * 4)); HIP_CHECK(hipHostMalloc((void **)&con_out_h_, MAX_CONVERSATIONS * 4, hipHostMallocDefault));
+        HIP_CHECK(hipHostMalloc((void **)&con_row_h_, (size_t)constraint_words((int)V) * 4, hipHostMallocDefault));
+        HIP_CHECK(hipMemcpy(con_vocab_, blob.data(), blob.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(con_off_, off.data(), (V + 1) * 4, hipMemcpyHostToDevice));
+    } catch (...) { con_free(); throw; }
+}
+void Engine::con_free() {
+    for (Constraint &c : con_) { if (c.dev) HIP_IGNORE(hipFree(c.dev)); c = Constraint{}; }
+    if (con_vocab_) HIP_IGNORE(hipFree(con_vocab_));
+    if (con_off_) HIP_IGNORE(hipFree(con_off_));
+    if (con_d_) HIP_IGNORE(hipFree(con_d_));
+    if (con_out_d_) HIP_IGNORE(hipFree(con_out_d_));
+    if (con_h_) HIP_IGNORE(hipHostFree(con_h_));
+    if (con_out_h_) HIP_IGNORE(hipHostFree(con_out_h_));
+    if (con_row_h_) HIP_IGNORE(hipHostFree(con_row_h_));
+    con_vocab_ = nullptr; con_off_ = nullptr; con_d_ = con_h_ = nullptr; con_out_d_ = con_out_h_ = nullptr; con_row_h_ = nullptr;
+}
+int Engine::constraint_compile(const unsigned char *pattern, long long n_bytes, int *handle) {
+    auto refuse = [](const std::string &what) { set_last_error("constraint_compile: " + what); return 1; };
+    if (!handle) return refuse("handle is required");
+    if (!pattern) return refuse("pattern is required");
+    if (weights_missing()) return refuse(last_error());
+    int h = 0;
+    while (h < CONSTRAINT_SLOTS && con_[h].used) h++;
+    if (h == CONSTRAINT_SLOTS) return refuse("all 8 constraints of this context are in use");
+    ConstraintDfa dfa; std::string err;
+    if (!mg4::constraint_compile(pattern, n_bytes < 0 ? strlen(reinterpret_cast<const char *>(pattern)) : (size_t)n_bytes, dfa, err)) return refuse(err);
+    con_alloc();
+    const int V = (int)llm_.n_vocab, W = constraint_words(V);
+    const size_t S = (size_t)dfa.n_states, t_bytes = S * 256 * 2, a_bytes = (dfa.accept.size() * 4 + 15) & ~(size_t)15, i_bytes = S * (size_t)W * 4;
+    uint8_t *dev = nullptr;
+    HIP_CHECK(hipMalloc((void **)&dev, t_bytes + a_bytes + i_bytes));
+    try {
+        HIP_CHECK(hipMemcpyAsync(dev, dfa.trans.data(), t_bytes, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(dev + t_bytes, dfa.accept.data(), dfa.accept.size() * 4, hipMemcpyHostToDevice, stream_));
+        unsigned *index = reinterpret_cast<unsigned *>(dev + t_bytes + a_bytes);
+        if (!launch_constrain_index(con_vocab_, con_off_, V, reinterpret_cast<const uint16_t *>(dev), reinterpret_cast<const unsigned *>(dev + t_bytes), dfa.n_states, index, stream_))
+            throw HipError{hipErrorInvalidValue, "constraint index launch refused", __FILE__, __LINE__};
+        HIP_CHECK(hipStreamSynchronize(stream_));                            // the host vectors above go out of scope; the index is complete when the call returns
+        con_[h].used = true; con_[h].dfa = std::move(dfa); con_[h].dev = dev; con_[h].index = index;
+    } catch (...) { HIP_IGNORE(hipStreamSynchronize(stream_)); HIP_IGNORE(hipFree(dev)); throw; }
+    con_info_.index_launches++;
+    *handle = h + 1;
+    return 0;
+}
+int Engine::constraint_free(int handle) {
+    auto refuse = [](const char *what) { set_last_error(std::string("constraint_free: ") + what); return 1; };
+    if (handle < 1 || handle > CONSTRAINT_SLOTS || !con_[handle - 1].used) return refuse("no such constraint");
+    for (size_t i = 0; i < conv_.size(); i++) if (con_handle_[i] == handle) return refuse("a conversation uses this constraint");
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    HIP_IGNORE(hipFree(con_[handle - 1].dev));
+    con_[handle - 1] = Constraint{};
+    return 0;
+}
+int Engine::set_constraint(int slot, int handle) {
+    auto refuse = [](const char *what) { set_last_error(std::string("set_constraint: ") + what); return 1; };
+    if (slot < 0 || slot >= (int)conv_.size()) return refuse("conversation index out of range");
+    if (handle < 0 || handle > CONSTRAINT_SLOTS || (handle && !con_[handle - 1].used)) return refuse("no such constraint");
+    con_assigned_ += (handle != 0) - (con_handle_[slot] != 0);
+    con_handle_[slot] = handle; con_state_[slot] = handle ? CONSTRAINT_START : 0;
+    return 0;
+}
+void Engine::con_walk(int slot, int id) {
+    if (id == CONSTRAINT_EOS || id < 0 || id >= (int)llm_.pieces.size()) return;
+    const std::string &piece = llm_.pieces[(size_t)id];
+    con_state_[slot] = constraint_walk(con_[con_handle_[slot] - 1].dfa.trans.data(), con_state_[slot], reinterpret_cast<const unsigned char *>(piece.data()), (int)piece.size());
+}
+int Engine::constraint_advance(int slot, const int *tokens, int n) {
+    auto refuse = [](const std::string &what) { set_last_error("constraint_advance: " + what); return 1; };
+    if (slot < 0 || slot >= (int)conv_.size()) return refuse("conversation index out of range");
+    if (!con_handle_[slot]) return refuse("the conversation has no constraint");
+    if (n < 0 || (n > 0 && !tokens)) return refuse("tokens is required");
+    const uint16_t *trans = con_[con_handle_[slot] - 1].dfa.trans.data();
+    int state = con_state_[slot];
+    for (int i = 0; i < n; i++) {
+        if (tokens[i] < 0 || tokens[i] >= (int)llm_.n_vocab) return refuse("token id out of range");
+        if (tokens[i] == CONSTRAINT_EOS) continue;
+        const std::string &piece = tokens[i] < (int)llm_.pieces.size() ? llm_.pieces[(size_t)tokens[i]] : std::string();
+        state = constraint_walk(trans, state, reinterpret_cast<const unsigned char *>(piece.data()), (int)piece.size());
+        if (state == CONSTRAINT_DEAD) return refuse("token " + std::to_string(i) + " leaves the pattern");
+    }
+    con_state_[slot] = state;
+    return 0;
+}
+int Engine::constraint_info(int slot, int out[8]) const {
+    if (!out || slot < 0 || slot >= (int)conv_.size()) { set_last_error(out ? "constraint_info: conversation index out of range" : "constraint_info: no output array"); return 1; }
+    const int h = con_handle_[slot];
+    out[0] = h; out[1] = con_state_[slot]; out[2] = h ? (int)con_[h - 1].dfa.accepting(con_state_[slot]) : 0; out[3] = h ? con_[h - 1].dfa.n_states : 0;
+    out[4] = con_info_.launches; out[5] = con_info_.host_rows; out[6] = con_info_.stuck; out[7] = con_info_.index_launches;
+    return 0;
+}
+const unsigned *Engine::con_fetch_row(int handle, int state) {
+    const int W = constraint_words((int)llm_.n_vocab);
+    HIP_CHECK(hipMemcpyAsync(con_row_h_, con_[handle - 1].index + (size_t)state * W, (size_t)W * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    return con_row_h_;
+}
+int Engine::constraint_mask(int handle, int state, uint32_t *out, int n_words) {
+    auto refuse = [](const char *what) { set_last_error(std::string("constraint_mask: ") + what); return 1; };
+    if (handle < 1 || handle > CONSTRAINT_SLOTS || !con_[handle - 1].used) return refuse("no such constraint");
+    if (state < 0 || state >= con_[handle - 1].dfa.n_states) return refuse("state out of range");
+    const int W = constraint_words((int)llm_.n_vocab);
+    if (!out || n_words < W) return refuse("the buffer must hold (n_vocab + 31) / 32 words rounded up to 4");
+    memcpy(out, con_fetch_row(handle, state), (size_t)W * 4);
+    return 0;
+}
+// The caller has evaluated every listed conversation's queue and synchronised (greedy_raw): hist is the whole history, the pinned staging is free.
+void Engine::con_pick(const int *slots, int n, int *ids) {
+    if (!con_assigned_) return;                                              // no conversation of this context holds a constraint: today's path
+    std::vector<PenEntry> tab;
+    int m = 0, map[MAX_CONVERSATIONS]; size_t off = 0;
+    ConRow *rows = reinterpret_cast<ConRow *>(con_h_); PenEntry *ent = reinterpret_cast<PenEntry *>(con_h_ + MAX_CONVERSATIONS * sizeof(ConRow));
+    const int V = (int)llm_.n_vocab, W = constraint_words(V);
+    for (int i = 0; i < n; i++) {
+        const int slot = slots[i], h = con_handle_[slot];
+        const Conversation &cv = conv_[(size_t)slot];
+        if (!h || !cv.has_logits) continue;
+        int flags = 0; tab.clear();
+        if (pen_mode_ || !cv.bias_id.empty()) flags = pen_table(cv, tab);
+        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
+        rows[m] = ConRow{PenRow{slot, (int)off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0}, con_[h - 1].index + (size_t)con_state_[slot] * W, 0ull};
+        std::copy(tab.begin(), tab.end(), ent + off);
+        off += tab.size(); map[m++] = i;
+    }
+    if (!m) return;
+    const size_t head = MAX_CONVERSATIONS * sizeof(ConRow);
+    HIP_CHECK(hipMemcpyAsync(con_d_, con_h_, head + off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
+    if (!launch_constrain_pick(logits_, V, V, m, reinterpret_cast<const ConRow *>(con_d_), reinterpret_cast<const PenEntry *>(con_d_ + head), con_out_d_, stream_))
+        throw HipError{hipErrorInvalidValue, "constrained pick launch refused", __FILE__, __LINE__};
+    HIP_CHECK(hipMemcpyAsync(con_out_h_, con_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (int r = 0; r < m; r++) {
+        const int id = con_out_h_[r] & ~CONSTRAIN_STUCK;
+        if (id < 0 || id >= V) throw HipError{hipErrorUnknown, "the constrained pick reported an id outside the vocabulary", __FILE__, __LINE__};
+        if (con_out_h_[r] & CONSTRAIN_STUCK) con_info_.stuck++;
+        ids[map[r]] = id;
+        con_walk(slots[map[r]], id);
+    }
+    con_info_.launches++;
 }
 int Engine::token_history(int *out, int cap) {
     if (flush()) return -1;

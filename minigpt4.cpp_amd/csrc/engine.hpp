@@ -62,7 +62,7 @@ public:
     int sample_token(const SampleParams &p);          // minigpt4.cpp:2425-2483
     const char *id_to_token(int id) const;            // minigpt4.cpp:2485-2497 (borrowed pointer)
     // minigpt4.cpp:2499-2502 (the selected conversation)
-    void reset() { Conversation &c = conv_[(size_t)cur_]; c.n_committed = 0; c.hist.clear(); c.drop_queue(); c.has_logits = false; }
+    void reset() { Conversation &c = conv_[(size_t)cur_]; c.n_committed = 0; c.hist.clear(); c.drop_queue(); c.has_logits = false; con_state_[cur_] = con_handle_[cur_] ? CONSTRAINT_START : 0; }
     void sync();
     hipStream_t stream() const { return stream_; }
     // ---- context shift (llama.cpp's answer to a full context), selected conversation: pending rows are evaluated first, then rows
@@ -225,6 +225,22 @@ public:
     int token_history(int *out, int cap);                                  // selected conversation, queued rows evaluated first; the count (-1: that pass failed)
     struct PenInfo { int mode = 0, launches = 0, host_rows = 0, last_entries = 0; };
     PenInfo penalty_info() const { PenInfo i = pen_info_; i.mode = pen_mode_; return i; }
+    // ---- constrained decoding (constraint.hpp: the pattern language and the DFA; minigpt4_amd.h: the rules).  A compiled constraint belongs to the CONTEXT (handles 1 ..
+    // CONSTRAINT_SLOTS; it depends on the vocabulary only, so it survives set_conversations and parity switches): its DFA on the host, and on the device its table and the
+    // index k_constrain_index builds once -- the allowed-token bitmap of every state.  A conversation holds a handle (0: none) and a DFA state.  sample_token and
+    // decode_batch apply it behind bias and penalties: temp <= 0 through ONE k_constrain_pick launch over the constrained conversations of the call (pen_pick skips them: the
+    // kernel applies their tables itself; 4 m bytes come back, one synchronise), temp > 0 by fetching the state's index row and setting every other id of the penalised
+    // host copy to -infinity before the chain.  Every constrained pick advances the state by the picked token on the host (EOS leaves it), whether or not the conversation
+    // then advances: the state belongs to the sampler, like the generator.  reset() returns it to the start; fork touches neither handle nor state; decode_batch with forced
+    // tokens, verify_draft, decode_lookup, decode_loop, beam_search and decode_guided neither consult nor advance it.  The vocabulary blob, the staging and the indices are
+    // allocated by the first compile and freed with the context.  Each call: 0, or 1 + last_error "<name>: ..." and nothing changed.
+    static constexpr int CONSTRAINT_SLOTS = 8;
+    int constraint_compile(const unsigned char *pattern, long long n_bytes, int *handle);   // n_bytes < 0: strlen
+    int constraint_free(int handle);                                       // refused while a conversation holds it
+    int set_constraint(int slot, int handle);                              // 0 clears; the state goes to the start
+    int constraint_advance(int slot, const int *tokens, int n);            // host walk; a token that leads to state 0 refuses the whole call
+    int constraint_info(int slot, int out[8]) const;                       // {handle, state, accepting, n_states, pick launches, host rows, stuck picks, index launches}
+    int constraint_mask(int handle, int state, uint32_t *out, int n_words);   // the device index row of (handle, state)
 
     // ---- measurement hooks (bench / tests): both feed tokens back on the device, so the rows they add enter the token history as -1
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
@@ -260,7 +276,8 @@ private:
     void beam_free();
     struct Conversation;
     int pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const;   // the conversation's table for its history as a sample sees it; the flags
-    void pen_pick(const int *slots, int n, int *ids);                      // ids[i] <- the penalised pick of every listed conversation whose transformation is not the identity
+    // ids[i] <- the penalised pick of every listed conversation whose transformation is not the identity (skip_constrained: and that holds no constraint -- con_pick serves it)
+    void pen_pick(const int *slots, int n, int *ids, bool skip_constrained = true);
     int greedy_raw();                                                      // sample_token at temp 0 without penalties or bias
     void spec_drop_graphs();
     void spec_free();
@@ -517,6 +534,20 @@ private:
     void guide_alloc();
     void guide_free();
     int guide_prepare(const char *name, const int *pos, const int *neg, int n, float scale, int *all);   // the checks, the queued rows; all[2 i] = pos[i], all[2 i + 1] = neg[i]
+    // constrained decoding.  Per compiled constraint: the host DFA, the device table | accepting bitmap | index (one allocation).  Per conversation (arrays here, not in
+    // Conversation: that struct keeps its layout): handle and state.  Lazy, first compile: the vocabulary blob + offsets; the pick's staging ([MAX_CONVERSATIONS] ConRow, then
+    // the penalty tables: device and pinned), its output words and their pinned mirror, the pinned landing place of one index row (temp > 0, constraint_mask)
+    struct Constraint { bool used = false; ConstraintDfa dfa; uint8_t *dev = nullptr; const unsigned *index = nullptr; };
+    Constraint con_[CONSTRAINT_SLOTS];
+    int con_handle_[MAX_CONVERSATIONS] = {0}, con_state_[MAX_CONVERSATIONS] = {0}, con_assigned_ = 0;
+    struct ConInfo { int launches = 0, host_rows = 0, stuck = 0, index_launches = 0; } con_info_;
+    unsigned char *con_vocab_ = nullptr; int *con_off_ = nullptr;
+    uint8_t *con_d_ = nullptr, *con_h_ = nullptr; int *con_out_d_ = nullptr, *con_out_h_ = nullptr; unsigned *con_row_h_ = nullptr;
+    void con_alloc();
+    void con_free();
+    void con_walk(int slot, int id);                                       // the state after the picked token (EOS and ids outside the vocabulary leave it)
+    void con_pick(const int *slots, int n, int *ids);                      // ids[i] <- the constrained pick of every listed conversation that holds a constraint
+    const unsigned *con_fetch_row(int handle, int state);                  // index[state] of that constraint in con_row_h_, synchronised
 };
 
 int device_count_noexcept();

@@ -5,6 +5,7 @@
 #include "common.hpp"
 #include "penalty.hpp"
 #include "beam.hpp"
+#include "constraint.hpp"
 
 namespace mg4 {
 
@@ -222,6 +223,16 @@ bool launch_beam_select(const int *ids, const float *logprobs, float *scores, un
 // the logits are not written.  adjusted (may be null): [table entry] the transformed value.  false + last_error: n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose
 // bitmap does not fit LDS
 bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const PenRow *rows, const PenEntry *table, int *picked, float *adjusted, hipStream_t s);
+// constrained decoding (constraint.hpp).  launch_constrain_index: index[n_states][constraint_words(n_vocab)] = the allowed-token bitmap of every DFA state, one workgroup per
+// state; vocab / off[n_vocab + 1] = the pieces' bytes back to back and where each begins (device), trans[n_states][256] with entries < n_states, accept = the accepting
+// bitmap.  false + last_error: a null array, n_vocab < 1, n_states outside 2 .. CONSTRAINT_MAX_STATES.
+// launch_constrain_pick: out[r] = the first maximum, over the ids set in rows[r].allowed (constraint_words(n_vocab) words, device), of logits row rows[r].pen.row after the
+// transformation rows[r].pen / table describe as for launch_pen_pick (pen.n == 0: none); no id set: CONSTRAINT_EOS | CONSTRAIN_STUCK.  The logits are not written.
+// false + last_error: a null array, n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose two bitmaps do not fit LDS.
+constexpr int CONSTRAIN_STUCK = 1 << 30;               // flag in a pick's output word: the row had no allowed id
+struct ConRow { PenRow pen; const unsigned *allowed; unsigned long long pad; };   // 12 words
+bool launch_constrain_index(const unsigned char *vocab, const int *off, int n_vocab, const uint16_t *trans, const unsigned *accept, int n_states, unsigned *index, hipStream_t s);
+bool launch_constrain_pick(const float *logits, int ld, int n_vocab, int n_rows, const ConRow *rows, const PenEntry *table, int *out, hipStream_t s);
 // guided decoding, one workgroup per entry of `pairs` (device), n_pairs <= GUIDE_MAX: b = logits row pos_row, g = row neg_row (at logits + row * ld, any 4-byte alignment;
 // the two may be one row, a row may serve several pairs), m[j] = lg[j] + scale * (lb[j] - lg[j]) with lb / lg the rows' log-softmax -- bit for bit launch_topn_rows'
 // log-probabilities -- and every operation rounded to fp32 on its own.  mixed (may be null): [n_pairs][n_vocab] = m; pick[p] = the first maximum of m, pick_val[p] = m[pick];

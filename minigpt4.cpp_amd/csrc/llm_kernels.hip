@@ -3092,6 +3092,75 @@ bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const
     hipLaunchKernelGGL(k_pen_pick, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, picked, adjusted);
     return true;
 }
+// Constrained decoding, the index (Engine::constraint_compile; constraint.hpp): index[s][W] = the bitmap of the token ids a conversation in DFA state s may emit, built once
+// per compiled pattern.  One workgroup of 256 per state, a lane walks one token's bytes (vocab[off[i] .. off[i + 1]), unsigned) from s through constraint_walk -- the
+// function the host walks picked tokens with --, a wave takes 64 consecutive ids and one lane stores its ballot as two words: no atomics, every word of the row written once.
+// Bit i: i >= 3, the piece is not empty and the walk does not end in state 0; i == 2 (EOS) iff s accepts; ids 0, 1, ids >= n_vocab and all of row 0: zero.
+// W = (n_vocab + 31) / 32 rounded up to 4, so 32 W is a multiple of 128 and every wave's 64 ids lie inside the row.  Reads: off[0 .. n_vocab], vocab below off[n_vocab],
+// trans below S * 256 (its entries are < S: the compiler's table; the test hook checks a given one).  No LDS.
+__global__ __launch_bounds__(256) void k_constrain_index(const unsigned char *__restrict__ vocab, const int *__restrict__ off, int n_vocab, const uint16_t *__restrict__ trans,
+                                                         const unsigned *__restrict__ accept, int W, unsigned *__restrict__ index) {
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const bool accepting = s != CONSTRAINT_DEAD && ((accept[s >> 5] >> (s & 31)) & 1u);
+    unsigned *row = index + (size_t)s * W;
+    for (int i0 = (tid >> 6) * 64; i0 < 32 * W; i0 += 256) {                 // wave-uniform bounds: all 64 lanes vote
+        const int i = i0 + (tid & 63);
+        bool ok = false;
+        if (s != CONSTRAINT_DEAD && i < n_vocab) {
+            if (i == CONSTRAINT_EOS) ok = accepting;
+            else if (i > CONSTRAINT_EOS) { const int a = off[i], n = off[i + 1] - a; ok = n > 0 && constraint_walk(trans, s, vocab + a, n) != CONSTRAINT_DEAD; }
+        }
+        const unsigned long long votes = __ballot(ok);
+        if ((tid & 63) == 0) { row[i0 >> 5] = (unsigned)votes; row[(i0 >> 5) + 1] = (unsigned)(votes >> 32); }
+    }
+}
+bool launch_constrain_index(const unsigned char *vocab, const int *off, int n_vocab, const uint16_t *trans, const unsigned *accept, int n_states, unsigned *index, hipStream_t s) {
+    if (!vocab || !off || !trans || !accept || !index || n_vocab < 1 || n_states < 2 || n_states > CONSTRAINT_MAX_STATES) { set_last_error("launch_constrain_index: shape out of range"); return false; }
+    note_kernel("k_constrain_index");
+    hipLaunchKernelGGL(k_constrain_index, dim3((unsigned)n_states), dim3(256), 0, s, vocab, off, n_vocab, trans, accept, constraint_words(n_vocab), index);
+    return true;
+}
+// Constrained greedy pick (Engine::con_pick), one workgroup of 256 per constrained conversation, one launch for all of them.  rows[r] names the logits row, the address
+// of index[state] (the allowed bitmap, constraint_words(n_vocab) words) and -- pen.n > 0 -- the conversation's penalty table and factors, exactly as k_pen_pick takes them.
+// The allowed bitmap is staged in LDS; thread i computes table entry i with pen_value and marks its id in a second bitmap, carrying the value only when the id is allowed;
+// the sweep (row_span / row_sweep) carries the allowed, unmarked ids.  out[r] = the FIRST maximum of the transformed row over the allowed ids (larger value, then lower id;
+// -0 == +0; an allowed id at -infinity can still win among -infinities; NaN never wins).  No allowed id: out[r] = CONSTRAINT_EOS | CONSTRAIN_STUCK.  The logits are read
+// in place and never written.  LDS, all dynamic: 2 * constraint_words(n_vocab) bitmap words, then 4 floats and 4 ints of reduction scratch (8 KB at 32 001 ids); the
+// launch refuses a vocabulary whose two bitmaps exceed 64 KB (n_vocab above 261 000).
+__global__ __launch_bounds__(256) void k_constrain_pick(const float *__restrict__ logits, int ld, int n_vocab, const ConRow *__restrict__ rows, const PenEntry *__restrict__ table,
+                                                        int *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned con_lds[];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const ConRow cr = rows[r];
+    const int words = constraint_words(n_vocab);
+    unsigned *allow = con_lds, *marked = con_lds + words;
+    float *sv = reinterpret_cast<float *>(con_lds + 2 * words); int *si = reinterpret_cast<int *>(con_lds + 2 * words + 4);
+    const float *x = logits + (size_t)cr.pen.row * ld;
+    for (int i = tid; i < words; i += 256) { allow[i] = cr.allowed[i]; marked[i] = 0u; }
+    __syncthreads();
+    float best = -INFINITY; int bi = 0x7FFFFFFF;
+    for (int i = tid; i < cr.pen.n; i += 256) {
+        const PenEntry e = table[(size_t)cr.pen.off + i];
+        if (e.id < 0 || e.id >= n_vocab) continue;
+        atomicOr(&marked[e.id >> 5], 1u << (e.id & 31));
+        if (!((allow[e.id >> 5] >> (e.id & 31)) & 1u)) continue;
+        argmax_combine(best, bi, pen_value(x[e.id], e.id, e.count, e.has_bias, e.bias, cr.pen.flags, cr.pen.repeat_penalty, cr.pen.alpha_frequency, cr.pen.alpha_presence), e.id);
+    }
+    __syncthreads();
+    const RowSpan sp = row_span(x, n_vocab);
+    row_sweep(sp, tid, [&](float v, int i) { if (((allow[i >> 5] & ~marked[i >> 5]) >> (i & 31)) & 1u) argmax_combine(best, bi, v, i); });
+    argmax_wave(best, bi);
+    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) { for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]); out[r] = bi == 0x7FFFFFFF ? (CONSTRAINT_EOS | CONSTRAIN_STUCK) : bi; }
+}
+bool launch_constrain_pick(const float *logits, int ld, int n_vocab, int n_rows, const ConRow *rows, const PenEntry *table, int *out, hipStream_t s) {
+    const size_t lds = ((size_t)2 * constraint_words(n_vocab) + 8) * 4;
+    if (!logits || !rows || !out || n_rows < 1 || n_vocab < 1 || ld < n_vocab || lds > 64 * 1024) { set_last_error("launch_constrain_pick: shape out of range"); return false; }
+    note_kernel("k_constrain_pick");
+    hipLaunchKernelGGL(k_constrain_pick, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, out);
+    return true;
+}
 // Guided decoding (Engine::decode_guided / guided_logits; minigpt4_amd.h states the rule), one workgroup of 256 per pair, one launch for all pairs of a call.  A pair names
 // two logits rows, b (the guided conversation) and g (the guidance one), and a scale.  Sweeps: the maxima of the two rows and the two sums of exponentials through
 // row_max_first / row_sum_exp -- so lb = (b - max b) - log(sum) and lg are the bits k_logprob_rows / k_topn_rows report for the same row at the same address -- and ONE mixing

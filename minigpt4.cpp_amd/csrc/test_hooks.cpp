@@ -1016,6 +1016,81 @@ int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, i
         return 0;
     });
 }
+// ---- constrained decoding (constraint.hpp, launch_constrain_index, launch_constrain_pick) ----
+int minigpt4_amd_test_constraint_compile(const char *pattern, int n_bytes, uint16_t *trans_out, uint32_t *accept_out, int cap_states, int32_t *n_states_out, char *err, size_t err_cap) {
+    if (!pattern || !n_states_out) return -1;
+    if (err && err_cap) err[0] = 0;
+    try {
+        ConstraintDfa dfa; std::string why;
+        if (!constraint_compile(reinterpret_cast<const unsigned char *>(pattern), n_bytes < 0 ? strlen(pattern) : (size_t)n_bytes, dfa, why)) {
+            if (err && err_cap) { strncpy(err, why.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+            return 1;
+        }
+        *n_states_out = dfa.n_states;
+        if (trans_out && cap_states >= dfa.n_states) memcpy(trans_out, dfa.trans.data(), dfa.trans.size() * 2);
+        if (accept_out) { memset(accept_out, 0, 32 * 4); memcpy(accept_out, dfa.accept.data(), dfa.accept.size() * 4); }
+        return 0;
+    } catch (...) { return -1; }
+}
+int minigpt4_amd_test_constrain_index(const uint8_t *vocab, const int32_t *off, int n_vocab, const uint16_t *trans, const uint32_t *accept, int n_states, uint32_t *index_out,
+                                      float *ms_out) {
+    if (!vocab || !off || !trans || !accept || !index_out || n_vocab < 1 || n_states < 2 || n_states > CONSTRAINT_MAX_STATES || off[0] != 0) return 1;
+    for (int i = 0; i < n_vocab; i++) if (off[i + 1] < off[i]) return 1;                       // everything that indexes device memory
+    for (size_t i = 0; i < (size_t)n_states * 256; i++) if (trans[i] >= n_states) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t nb = (size_t)off[n_vocab], S = (size_t)n_states, W = (size_t)constraint_words(n_vocab), A = (S + 31) / 32;
+        DevBuf dv(std::max<size_t>(nb, 1)), doff(((size_t)n_vocab + 1) * 4), dt(S * 512), da(A * 4), di(S * W * 4);
+        if (nb) HIP_CHECK(hipMemcpy(dv.p, vocab, nb, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(doff.p, off, ((size_t)n_vocab + 1) * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, trans, S * 512, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(da.p, accept, A * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(di.p, 0xA5, S * W * 4));                                           // a word the kernel leaves out shows
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_constrain_index(dv.as<unsigned char>(), doff.as<int>(), n_vocab, dt.as<uint16_t>(), da.as<unsigned>(), n_states, di.as<unsigned>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        HIP_CHECK(hipMemcpy(index_out, di.p, S * W * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+int minigpt4_amd_test_constrain_pick(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
+                                     const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, int32_t *out, float *ms_out) {
+    static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(ConRow) == 48, "the hook's word layout");
+    if (!logits || !rows || !out || !bitmaps || !bitmap_of_row || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n_rows < 1 || n_bitmaps < 1 || n_table < 0 || (n_table > 0 && !table)) return 1;
+    for (int r = 0; r < n_rows; r++) {   // everything that indexes device memory
+        const int32_t *w = rows + 8 * (size_t)r;
+        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table || bitmap_of_row[r] < 0 || bitmap_of_row[r] >= n_bitmaps) return 1;
+        std::vector<int> ids;
+        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)buf_rows * ld, R = (size_t)n_rows, T = (size_t)std::max(n_table, 1), W = (size_t)constraint_words(n_vocab);
+        DevBuf dl(n * 4), dr(R * sizeof(ConRow)), dt(T * sizeof(PenEntry)), dp(R * 4), db((size_t)n_bitmaps * W * 4);
+        std::vector<ConRow> tab(R);
+        for (size_t r = 0; r < R; r++) { memcpy(&tab[r].pen, rows + 8 * r, sizeof(PenRow)); tab[r].allowed = db.as<unsigned>() + (size_t)bitmap_of_row[r] * W; tab[r].pad = 0; }
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, tab.data(), R * sizeof(ConRow), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(db.p, bitmaps, (size_t)n_bitmaps * W * 4, hipMemcpyHostToDevice));
+        if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dp.p, 0xFF, R * 4));                                                // what the kernel leaves out shows as id -1
+        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_constrain_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<ConRow>(), dt.as<PenEntry>(), dp.as<int>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        HIP_CHECK(hipMemcpy(out, dp.p, R * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- guided decoding (launch_guide_rows) ----
 // k_guide_rows, one launch, on host logits [buf_rows][ld]: pairs = [n][2] buffer rows (guided, guidance), scales[n], row_tok_index = [n][2] indices into a 64-entry row-token
 // array (-1: not written) that starts as row_tok_io and is returned there.  mixed_out (may be NULL): [n][n_vocab].  Everything that indexes device memory is checked here.

@@ -67,6 +67,32 @@ CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
+_REGEX_SPECIAL = frozenset(b"\\.[](){}|*+?^$-")
+
+
+def regex_escape(text) -> str:
+    """`text` (str, or bytes of UTF-8) as a pattern of the constraint language that matches exactly it: the characters with a meaning there get a backslash, a control byte
+    becomes \\xHH; everything else, UTF-8 included, stands for itself.  Python's `re` reads the result the same way."""
+    data = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    out = bytearray()
+    for b in data:
+        if b in _REGEX_SPECIAL:
+            out += b"\\" + bytes([b])
+        elif b < 0x20 or b == 0x7F:
+            out += b"\\x%02X" % b
+        else:
+            out.append(b)
+    return out.decode("utf-8")
+
+
+def choice_pattern(options) -> str:
+    """The pattern that matches exactly one of `options` (str each): (?:a|b|c) with every option escaped."""
+    options = list(options)
+    if not options:
+        raise ValueError("choice_pattern: at least one option is required")
+    return "(?:" + "|".join(regex_escape(o) for o in options) + ")"
+
+
 def _test_hook_names() -> frozenset:
     """The names include/minigpt4_amd_test.h declares: the ONLY symbols that may be served by libminigpt4_test.so."""
     import re
@@ -225,6 +251,12 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_end_chat_guided.argtypes = [VOID_PTR, INT_PTR, INT_PTR, I32, F32, ctypes.POINTER(ctypes.c_char_p), F32, I32, F32, F32, F32, I32, F32, F32, INT_PTR]
         L.minigpt4_amd_guided_logits.argtypes = [VOID_PTR, INT_PTR, INT_PTR, I32, F32, FLOAT_PTR, INT_PTR]
         L.minigpt4_amd_guidance_info.argtypes = [VOID_PTR, INT_PTR]
+        L.minigpt4_amd_constraint_compile.argtypes = [VOID_PTR, CHAR_PTR, I32, INT_PTR]
+        L.minigpt4_amd_constraint_free.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_set_constraint.argtypes = [VOID_PTR, I32, I32]
+        L.minigpt4_amd_constraint_advance.argtypes = [VOID_PTR, I32, INT_PTR, I32]
+        L.minigpt4_amd_constraint_info.argtypes = [VOID_PTR, I32, INT_PTR]
+        L.minigpt4_amd_constraint_mask.argtypes = [VOID_PTR, I32, I32, P(ctypes.c_uint32), I32]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -269,6 +301,10 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_kv_permute.argtypes = [I32, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_pen_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_guide_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, I32, FLOAT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR]
+        U16P, U32P = P(ctypes.c_uint16), P(ctypes.c_uint32)
+        L.minigpt4_amd_test_constraint_compile.argtypes = [CHAR_PTR, I32, U16P, U32P, I32, INT_PTR, ctypes.c_char_p, SIZE_T]
+        L.minigpt4_amd_test_constrain_index.argtypes = [P(ctypes.c_uint8), INT_PTR, I32, U16P, U32P, I32, U32P, FLOAT_PTR]
+        L.minigpt4_amd_test_constrain_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, U32P, I32, INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
@@ -766,6 +802,101 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_pen_pick rc={rc}: " + self._err())
         return picked, adj[:len(tb)], float(ms.value)
+
+    # ---- constrained decoding: a regular expression per conversation (include/minigpt4_amd.h)
+    CONSTRAINT_INFO_FIELDS = ("handle", "state", "accepting", "n_states", "pick_launches", "host_rows", "stuck", "index_launches")
+
+    @staticmethod
+    def _pattern_bytes(pattern) -> bytes:
+        return pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+
+    def amd_constraint_compile(self, ctx, pattern) -> int:
+        """Compile a pattern (str: its UTF-8 bytes; or bytes) for this context: the DFA, its upload and the index of allowed tokens per state.  Returns the handle (1 .. 8).
+        RuntimeError carries the compiler's refusal ("... at byte N", "too many states ...", "matches nothing")."""
+        pat, h = self._pattern_bytes(pattern), I32(0)
+        if self.library.minigpt4_amd_constraint_compile(ctx.ptr, pat, len(pat), ctypes.byref(h)):
+            raise RuntimeError("constraint_compile failed: " + self._err())
+        return int(h.value)
+
+    def amd_constraint_free(self, ctx, handle: int) -> None:
+        if self.library.minigpt4_amd_constraint_free(ctx.ptr, int(handle)):
+            raise RuntimeError("constraint_free failed: " + self._err())
+
+    def amd_set_constraint(self, ctx, slot: int, handle: int) -> None:
+        """Conversation `slot` generates inside the compiled pattern `handle` from now on (0: no constraint); its state goes to the start."""
+        if self.library.minigpt4_amd_set_constraint(ctx.ptr, int(slot), int(handle)):
+            raise RuntimeError("set_constraint failed: " + self._err())
+
+    def amd_constraint_advance(self, ctx, slot: int, tokens: Sequence[int]) -> None:
+        """Walk the conversation's state over token ids the caller fed itself; a token that leaves the pattern refuses the whole call."""
+        tk = np.ascontiguousarray(tokens, np.int32)
+        if self.library.minigpt4_amd_constraint_advance(ctx.ptr, int(slot), tk.ctypes.data_as(INT_PTR) if len(tk) else None, len(tk)):
+            raise RuntimeError("constraint_advance failed: " + self._err())
+
+    def amd_constraint_info(self, ctx, slot: int = 0) -> dict:
+        """dict(handle, state, accepting, n_states of the conversation's constraint; pick_launches: k_constrain_pick launches, host_rows: rows masked for the host chain,
+        stuck: picks without an allowed id, index_launches: k_constrain_index launches -- of the context so far)."""
+        o = np.zeros(8, np.int32)
+        if self.library.minigpt4_amd_constraint_info(ctx.ptr, int(slot), o.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("constraint_info failed: " + self._err())
+        return dict(zip(self.CONSTRAINT_INFO_FIELDS, (int(v) for v in o)))
+
+    def amd_constraint_mask(self, ctx, handle: int, state: int, n_words: Optional[int] = None) -> np.ndarray:
+        """The device index row of (handle, state): uint32 words, bit i of word i // 32 = token i is allowed."""
+        nv = self.library.minigpt4_amd_n_vocab(ctx.ptr)
+        w = ((nv + 31) // 32 + 3) // 4 * 4 if n_words is None else int(n_words)
+        out = np.zeros(max(w, 1), np.uint32)
+        if self.library.minigpt4_amd_constraint_mask(ctx.ptr, int(handle), int(state), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), w):
+            raise RuntimeError("constraint_mask failed: " + self._err())
+        return out[:w]
+
+    def amd_test_constraint_compile(self, pattern):
+        """The compiler alone, no GPU (include/minigpt4_amd_test.h): (trans [S][256] uint16, accept [(S + 31) // 32] uint32, S).  ValueError carries a refusal's text."""
+        pat = self._pattern_bytes(pattern)
+        trans, acc, n, err = np.zeros((1024, 256), np.uint16), np.zeros(32, np.uint32), I32(0), ctypes.create_string_buffer(256)
+        rc = self.library.minigpt4_amd_test_constraint_compile(pat, len(pat), trans.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
+                                                               acc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), 1024, ctypes.byref(n), err, len(err))
+        if rc == 1:
+            raise ValueError(err.value.decode("utf-8", errors="replace"))
+        if rc:
+            raise RuntimeError(f"test_constraint_compile rc={rc}")
+        S = int(n.value)
+        return trans[:S].copy(), acc[:(S + 31) // 32].copy(), S
+
+    def amd_test_constrain_index(self, pieces: Sequence[bytes], trans: np.ndarray, accept: np.ndarray):
+        """k_constrain_index alone on a given vocabulary (a list of byte strings) and table: (index [S][W] uint32, ms)."""
+        off = np.zeros(len(pieces) + 1, np.int32)
+        off[1:] = np.cumsum([len(p) for p in pieces])
+        blob = np.frombuffer(b"".join(bytes(p) for p in pieces) + b"\0", np.uint8).copy()
+        tr = np.ascontiguousarray(trans, np.uint16)
+        ac = np.ascontiguousarray(accept, np.uint32)
+        S, V = len(tr), len(pieces)
+        out, ms = np.zeros((S, ((V + 31) // 32 + 3) // 4 * 4), np.uint32), ctypes.c_float()
+        U32P = ctypes.POINTER(ctypes.c_uint32)
+        rc = self.library.minigpt4_amd_test_constrain_index(blob.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), off.ctypes.data_as(INT_PTR), V,
+                                                            tr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), ac.ctypes.data_as(U32P), S, out.ctypes.data_as(U32P), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_constrain_index rc={rc}: " + self._err())
+        return out, float(ms.value)
+
+    def amd_test_constrain_pick(self, logits: np.ndarray, n_vocab: int, rows: np.ndarray, table: np.ndarray, bitmaps: np.ndarray, bitmap_of_row: Sequence[int]):
+        """k_constrain_pick alone on host logits [buf_rows][ld]; rows / table as amd_test_pen_pick, bitmaps [k][W] uint32, bitmap_of_row [n]: returns (ids [n], stuck [n]
+        bool, ms)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        rw = np.ascontiguousarray(rows, np.int32).reshape(-1, 8)
+        tb = np.ascontiguousarray(table, np.int32).reshape(-1, 4)
+        bm = np.ascontiguousarray(bitmaps, np.uint32)
+        assert bm.ndim == 2 and bm.shape[1] == ((int(n_vocab) + 31) // 32 + 3) // 4 * 4
+        br = np.ascontiguousarray(bitmap_of_row, np.int32)
+        assert len(br) == len(rw)
+        out, ms = np.zeros(len(rw), np.int32), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_constrain_pick(lg.ctypes.data_as(FLOAT_PTR), lg.shape[0], int(n_vocab), lg.shape[1], rw.ctypes.data_as(INT_PTR), len(rw),
+                                                           tb.ctypes.data_as(INT_PTR) if len(tb) else None, len(tb), bm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(bm),
+                                                           br.ctypes.data_as(INT_PTR), out.ctypes.data_as(INT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_constrain_pick rc={rc}: " + self._err())
+        return out & ~(1 << 30), (out & (1 << 30)) != 0, float(ms.value)
 
     def amd_token_piece(self, ctx, token_id: int) -> Optional[str]:
         """The text of one token id, as minigpt4_end_chat returns it ("</s>" for id 2); None for an id outside the vocabulary."""

@@ -69,8 +69,13 @@ class ReplicaServer:
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
             batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
             frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
-            negative_prompt: Optional[str] = None) -> List[str]:
-        """guidance_scale != 1: guided decoding (classifier-free guidance, `minigpt4_amd_end_chat_guided`) -- every request takes two conversations, so a wave holds
+            negative_prompt: Optional[str] = None, regex=None) -> List[str]:
+        """regex (str or bytes; include/minigpt4_amd.h states the pattern language): constrained decoding -- the pattern is compiled once for the call
+        (`minigpt4_amd_constraint_compile`), set on every request's conversation and cleared and freed when the call returns; every answer then matches the WHOLE pattern, or is
+        a prefix of a match when max_tokens ran out first.  The answer ends at "</s>", which the constraint allows exactly where the text matches; the "###" / "##" rules
+        of the decode loop are off (the pattern decides what the text may hold).  Works with temp > 0, logprobs, penalties and logit_bias; ValueError together with
+        num_beams > 1 or guidance_scale != 1 (those paths decide on their own rows).
+        guidance_scale != 1: guided decoding (classifier-free guidance, `minigpt4_amd_end_chat_guided`) -- every request takes two conversations, so a wave holds
         conversations // 2 requests: its own, and a guidance conversation that gets the system prompt and `minigpt4_begin_chat` of the request's prompt WITHOUT the image
         (negative_prompt given: of that text instead); with batched_prefill both kinds go into the one `minigpt4_amd_prefill_batch`.  Every step decides one token per
         request from the two conversations' logits (scale > 1 pushes away from the guidance conversation) and advances both; penalties and logit bias act on the guided
@@ -97,7 +102,10 @@ class ReplicaServer:
             raise ValueError("guidance_scale != 1 is not available with logprobs > 0 or num_beams > 1")
         if guided and self.conversations < 2:
             raise ValueError("guidance_scale != 1 takes two conversations per request")
+        if regex is not None and (num_beams > 1 or guided):
+            raise ValueError("regex is not available with num_beams > 1 or guidance_scale != 1")
         answers: List[str] = [""] * len(requests)
+        self._constraint = lib.amd_constraint_compile(ctx, regex) if regex is not None else 0   # a refused pattern raises before anything is touched
         penalised = repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
         mode_before = lib.amd_penalty_info(ctx)["mode"] if penalised else 0
         try:
@@ -105,6 +113,11 @@ class ReplicaServer:
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
                              num_beams, length_penalty, guidance_scale if guided else None, negative_prompt)
         finally:
+            if self._constraint:
+                for slot in range(self.conversations):
+                    lib.amd_set_constraint(ctx, slot, 0)
+                lib.amd_constraint_free(ctx, self._constraint)
+                self._constraint = 0
             if penalised or logit_bias:
                 for slot in range(self.conversations):
                     lib.amd_select_conversation(ctx, slot)
@@ -163,6 +176,8 @@ class ReplicaServer:
                         lib.amd_conversation_penalties(ctx, slot, **pen)
                     if logit_bias:
                         lib.amd_set_logit_bias(ctx, logit_bias)
+                    if self._constraint:
+                        lib.amd_set_constraint(ctx, slot, self._constraint)   # (also returns the state to the start)
                     if guidance is not None:                  # the guidance conversation: the same question (or the negative prompt) asked without the image
                         lib.amd_select_conversation(ctx, slot + 1)
                         lib.minigpt4_reset_chat(ctx)
@@ -195,7 +210,12 @@ class ReplicaServer:
                         left[slot] -= 1
                         text[slot] += piece
                         done = left[slot] <= 0
-                        if not ignore_eos:
+                        if self._constraint:                      # the pattern decides: the answer ends where the constraint let "</s>" through
+                            if piece == "</s>":
+                                done = True
+                            else:
+                                shown[slot] += piece
+                        elif not ignore_eos:
                             if lib.minigpt4_contains_eos_token(piece):
                                 pass                                  # swallowed, like the reference's `continue`
                             elif lib.minigpt4_is_eos(text[slot]):
@@ -228,7 +248,7 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     try:
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
                                                                                                 "presence_penalty", "frequency_penalty", "logit_bias", "num_beams",
-                                                                                                "length_penalty", "guidance_scale", "negative_prompt")})
+                                                                                                "length_penalty", "guidance_scale", "negative_prompt", "regex")})
     finally:
         server.close()
     mapping = dict(zip(mine, out))
