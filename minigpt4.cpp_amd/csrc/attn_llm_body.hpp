@@ -23,6 +23,7 @@
         if (DRAFT && pos_ >= n_ctx) return;
         kc += (size_t)slot * seq_stride; vc += (size_t)slot * seq_stride;
     } else pos_ = *n_past + t;
+    MG4_ATTN_PIN();                                               // every argument's load is issued by here, in the position's round trip (llm_kernels.hip, above the kernels)
     const int pos = pos_, p0 = p0_, T = pos + 1;                  // p0: DRAFT only
     const int Tg = FUSED ? pos : T;                               // keys that are not this row's own
     const int Tpad = (T + 7) & ~7;

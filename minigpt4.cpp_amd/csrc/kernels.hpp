@@ -118,6 +118,7 @@ const char *last_kernel_name();          // "" when nothing was launched since t
 void reset_kernel_name();
 size_t launch_probe_count();                       // launches noted (and probed with their own start / stop events) since tracing was switched on
 float launch_probe_us(size_t first, size_t last);  // sum of the dispatch durations of probes [first, last) in microseconds (stream synchronised); < 0: not available
+int read_matvec_timeline_rows(unsigned long long *out, int max_workgroups);   // the same builds: one stamp per workgroup, taken when a prologue launch has issued its row loads
 int read_matvec_timeline(unsigned long long *out, int max_workgroups);   // diagnostic builds (MG4_TIMELINE): stamps of the last decode mat-vec launch; 0 otherwise
 int read_attn_timeline(unsigned long long *out, int max_workgroups);     // prompt attention (8 x u64 per workgroup, up to 2048 workgroups)
 int read_vision_timeline(unsigned long long *out, int max_workgroups);   // the same for the image path's kernels (32 x u64 per workgroup)

@@ -561,6 +561,9 @@ template <int NU> constexpr int mv_fat_max_threads() { return NU <= 4 ? 768 : 51
 #ifdef MG4_TIMELINE
 __device__ unsigned long long g_tl[1024 * 8];
 #define MG4_TL(i) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_tl[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+// prologue forms: the row loads have been issued (before the issue barrier and the first weight requests, which stamp 1 follows); an array of its own, read separately
+__device__ unsigned long long g_tl_rows[1024];
+#define MG4_TL_ROWS() do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_tl_rows[blockIdx.x] = __builtin_amdgcn_s_memrealtime(); } while (0)
 // slots 6 / 7: the LATEST end / entry over all waves of the workgroup (the clock only grows, so atomicMax needs no reset between launches)
 #define MG4_TL_ALL(i) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 1024) atomicMax(&g_tl[blockIdx.x * 8 + (i)], (unsigned long long)__builtin_amdgcn_s_memrealtime()); } while (0)
 // the prompt attention's own slots (workgroup = blockIdx.x + gridDim.x * blockIdx.y): 0 entry, 1 scores done, 2 softmax done, 3 P.V done, 4 stored
@@ -569,14 +572,32 @@ __device__ unsigned long long g_tla[2048 * 8];
 #else
 #define MG4_TLP(i) do {} while (0)
 #define MG4_TL(i) do {} while (0)
+#define MG4_TL_ROWS() do {} while (0)
 #define MG4_TL_ALL(i) do {} while (0)
 #endif
 // IB (prologue forms): a raw s_barrier (no wait on data) between the row loads and the first weight requests, so that the row loads of ALL waves of the workgroup are ahead
 // of any weight request in the CU's vector-memory queue -- without it the row loads of the late waves queue behind the weight tiles of the early ones, and the row-wide
 // barriers wait for the slowest wave (row ready 3.6 -> 3.3 us, profiles/r13_matvec_prefetch_depth.log).  Requesting MORE row groups before the preparation (round 2's
 // PRIME2, measured again in round 13 as depths 2 / 3) loses: a wave issues in order, so it reaches its row only after the CU has taken all those requests.
+// Kernel arguments: a HEAD of plain pointers and ints in front of the structs.  A wave has its kernel arguments fetched by scalar loads from a cold scalar cache
+// before it can issue anything; every dependent batch of such loads is a memory round trip in which the wave has nothing in flight.  So (a) what the first vector-memory
+// requests need is a head of plain parameters -- with -amdgpu-kernarg-preload-count (csrc/Makefile: PRELOAD) the command processor has those in SGPRs when the wave
+// starts, a struct passed by value ends the preloadable sequence -- (b) nothing on that path is a hidden argument (blockDim.x is the explicit nthr), and (c) every field of
+// the structs behind the head that the kernel reads is requested in ONE batch (mv_pin_tail: an empty asm statement that consumes the values, so hipcc cannot sink their
+// loads behind the row loads or a branch): at entry when nothing is preloaded -- one round trip in all -- or, in a preload build, right after the row loads have been
+// issued from the preloaded head, so the batch is in flight with them.  The head's fields shadow their twins in the structs, which the kernels no longer read.
+#ifndef MG4_KERNARG_PRELOAD
+#define MG4_KERNARG_PRELOAD 0
+#endif
+constexpr bool MV_PIN_AT_ENTRY = MG4_KERNARG_PRELOAD == 0;
+template <int T, int PRO, int EPI>
+__device__ __forceinline__ void mv_pin_tail(const MatSet &ms, const ActQ &A, const Tables &tb) {
+    asm volatile("" ::"s"(ms.w0.qs), "s"(ms.w0.qh), "s"(ms.w0.sc), "s"(ms.w0.d), "s"(ms.dmat), "s"(ms.y0), "s"(ms.dy), "s"(ms.res0), "s"(ms.dres), "s"(ms.n), "s"(ms.rows_each));
+    if (PRO == PRO_SILU || EPI == EPI_SILU_PAIR) asm volatile("" ::"s"(tb.silu));
+    if (PRO == PRO_NONE && tr_is_kquant<T>()) asm volatile("" ::"s"(A.q8k), "s"(A.dk), "s"(A.bsk));
+}
 template <int T, int NU, int R, int PRO, int EPI, bool IB = false>
-__device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, const ProArgs &pa, const int n_groups, const int n_waves, const int wave) {
+__device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, const ProArgs &pa, const int n_groups, const int n_waves, const int wave, const int nthr) {
     static_assert(EPI != EPI_SILU_PAIR || R == 2, "the SiLU pair epilogue works on row pairs");
     static_assert(PRO != PRO_NONE || !IB, "the issue barrier belongs to the prologue forms");
     // groups of this wave: g = g_first, g_first + g_step, ... < g_last
@@ -623,7 +644,6 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
         L.xh = reinterpret_cast<__half *>(smem_mv + 128);                // F16 weights: the fp16 row takes the place of the two int8 images (2 K bytes)
         L.xf = nullptr;
         constexpr int RND = (NU * 64 * X::EPU / 4 + MV_FAT_MIN - 1) / MV_FAT_MIN;    // K <= NU * 64 * EPU elements, 4 per thread per round, >= MV_FAT_MIN threads
-        const int nthr = (int)blockDim.x;
         constexpr int mask = T == GT_F16 ? ACT_F16 : (T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K) ? ACT_Q8K : ACT_Q80;
         float4 xv[RND], yv[RND];
         bool in[RND];
@@ -639,6 +659,8 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
 #pragma unroll
             for (int r = 0; r < RND; r++) { xv[r].x = tab(pa.tb.silu, xv[r].x); xv[r].y = tab(pa.tb.silu, xv[r].y); xv[r].z = tab(pa.tb.silu, xv[r].z); xv[r].w = tab(pa.tb.silu, xv[r].w); }
         }
+        MG4_TL_ROWS();
+        if (!MV_PIN_AT_ENTRY) mv_pin_tail<T, PRO, EPI>(ms, A, pa.tb);   // the row loads above needed the preloaded head only; the rest has been on its way meanwhile
         if (IB) {   // orders ISSUE only: nothing is waited for
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -732,19 +754,41 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
     MG4_TL(5); MG4_TL_ALL(6);
 #endif
 }
+// Prologue forms.  Head (8 dwords): the row, the norm weight / second factor, K, the workgroup's thread count, the wave's share of the row groups.
 template <int T, int NU, int R, int PRO, int EPI, bool IB = false>
-__global__ __launch_bounds__(PRO == PRO_NONE ? 256 : mv_fat_max_threads<NU>()) void k_matvec_v2(const MatSet ms, const ActQ A, const ProArgs pa, const int n_groups, const int n_waves) {
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));   // wave-uniform: scalar loop control
-    matvec_run<T, NU, R, PRO, EPI, IB>(ms, A, pa, n_groups, n_waves, wave);
+__global__ __launch_bounds__(mv_fat_max_threads<NU>()) void k_matvec_v2(const float *x, const float *w, const int K, const int nthr, const int n_groups, const int n_waves,
+                                                                        const MatSet ms_, const ActQ A, const Tables tb) {
+    static_assert(PRO != PRO_NONE, "the prologue-free form is k_matvec_v2_free");
+    MatSet ms = ms_; ms.w0.cols = K;
+    ProArgs pa; pa.x = x; pa.w = w; pa.tb = tb;
+    if (MV_PIN_AT_ENTRY) mv_pin_tail<T, PRO, EPI>(ms, A, tb);
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (nthr >> 6) + (threadIdx.x >> 6));   // wave-uniform: scalar loop control
+    matvec_run<T, NU, R, PRO, EPI, IB>(ms, A, pa, n_groups, n_waves, wave, nthr);
+}
+// Prologue-free form (256 threads).  Head (14 dwords): matrix 0's planes, the Q8_K plane of the prepared row, K, rows per matrix, the wave's share of the row groups.
+template <int T, int NU, int R, int EPI>
+__global__ __launch_bounds__(256) void k_matvec_v2_free(const uint8_t *qs, const uint8_t *qh, const uint8_t *sc, const uint8_t *d, int8_t *q8k, const int K, const int rows_each,
+                                                        const int n_groups, const int n_waves, const MatSet ms_, const ActQ A_, const Tables tb) {
+    MatSet ms = ms_; ms.w0.qs = qs; ms.w0.qh = qh; ms.w0.sc = sc; ms.w0.d = d; ms.w0.cols = K; ms.rows_each = rows_each;
+    ActQ A = A_; A.q8k = q8k;
+    ProArgs pa{}; pa.tb = tb;
+    mv_pin_tail<T, PRO_NONE, EPI>(ms, A, tb);   // the first weight request needs dmat and n from behind the head: one batch, at entry, in either build
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    matvec_run<T, NU, R, PRO_NONE, EPI, false>(ms, A, pa, n_groups, n_waves, wave, 256);
 }
 // Two weight types in one launch (llama.cpp's k-quant mixes give wv more bits than wq|wk): waves [0, n_waves1) stream set 1, the rest set 2.  Both
 // sets share K and the prepared activation row (both types read the Q8_K image); every wave passes the same number of workgroup barriers.
+// Head (10 dwords): as the prologue forms', with both sets' shares (a prologue-free launch passes null rows).
 template <int T1, int T2, int NU, int PRO, int EPI = EPI_STORE, bool IB = false>
-__global__ __launch_bounds__(PRO == PRO_NONE ? 256 : mv_fat_max_threads<NU>()) void k_matvec_mix(const MatSet ms1, const MatSet ms2, const ActQ A, const ProArgs pa, const int n_groups1,
-                                                                                                 const int n_waves1, const int n_groups2, const int n_waves2) {
-    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-    if (wave < n_waves1) matvec_run<T1, NU, 1, PRO, EPI, IB>(ms1, A, pa, n_groups1, n_waves1, wave);
-    else matvec_run<T2, NU, 1, PRO, EPI, IB>(ms2, A, pa, n_groups2, n_waves2, wave - n_waves1);
+__global__ __launch_bounds__(PRO == PRO_NONE ? 256 : mv_fat_max_threads<NU>()) void k_matvec_mix(const float *x, const float *w, const int K, const int nthr, const int n_groups1,
+                                                                                                 const int n_waves1, const int n_groups2, const int n_waves2, const MatSet ms1_,
+                                                                                                 const MatSet ms2_, const ActQ A, const Tables tb) {
+    MatSet ms1 = ms1_, ms2 = ms2_; ms1.w0.cols = K; ms2.w0.cols = K;
+    ProArgs pa; pa.x = x; pa.w = w; pa.tb = tb;
+    if (MV_PIN_AT_ENTRY || PRO == PRO_NONE) { mv_pin_tail<T1, PRO, EPI>(ms1, A, tb); mv_pin_tail<T2, PRO, EPI>(ms2, A, tb); }   // in front of the branch: one batch for either side
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (nthr >> 6) + (threadIdx.x >> 6));
+    if (wave < n_waves1) matvec_run<T1, NU, 1, PRO, EPI, IB>(ms1, A, pa, n_groups1, n_waves1, wave, nthr);
+    else matvec_run<T2, NU, 1, PRO, EPI, IB>(ms2, A, pa, n_groups2, n_waves2, wave - n_waves1, nthr);
 }
 static int g_mv_cus = 256;
 static int g_mv_force_waves = 0;    // MINIGPT4_MV_WAVES: waves per CU of the prologue-free launches (0 = choose)
@@ -765,20 +809,21 @@ static void launch_v2_pro(bool issue_bar, dim3 grid, dim3 block, size_t lds, hip
     const bool bar = issue_bar && mv_issue_bar_built<T, NU, EPI>();
     note_kernel("k_matvec_v2<%d, %d, %d, %d, %d, %s>", T, NU, R, PRO, EPI, bar ? "true" : "false");
     if constexpr (mv_issue_bar_built<T, NU, EPI>()) {
-        if (bar) { hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI, true>), grid, block, lds, s, ms, A, pa, n_groups, n_waves); return; }
+        if (bar) { hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI, true>), grid, block, lds, s, pa.x, pa.w, ms.w0.cols, (int)block.x, n_groups, n_waves, ms, A, pa.tb); return; }
     }
-    hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI>), grid, block, lds, s, ms, A, pa, n_groups, n_waves);
+    hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI>), grid, block, lds, s, pa.x, pa.w, ms.w0.cols, (int)block.x, n_groups, n_waves, ms, A, pa.tb);
 }
 template <int T, int NU, int R, int EPI>
 static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
     const int total_rows = ms.n * ms.rows_each;
     const int n_groups = EPI == EPI_SILU_PAIR ? ms.rows_each : (total_rows + R - 1) / R;
     if (pro == PRO_NONE) {
-        note_kernel("k_matvec_v2<%d, %d, %d, 0, %d, false>", T, NU, R, (int)EPI);
+        note_kernel("k_matvec_v2_free<%d, %d, %d, %d>", T, NU, R, (int)EPI);
         // EPI_REF: the block chain is a dependent sequence per wave (DPP move + fma per block): as many waves per SIMD as the registers admit, not the stream-optimal 8 per CU
         int n_waves = std::min(n_groups, g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(mv_max_wpc<NU>())));
         n_waves = (n_waves + 3) & ~3;
-        hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO_NONE, EPI>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, ms, A, pa, n_groups, n_waves);
+        hipLaunchKernelGGL((k_matvec_v2_free<T, NU, R, EPI>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, ms.w0.qs, ms.w0.qh, ms.w0.sc, ms.w0.d, A.q8k, ms.w0.cols, ms.rows_each,
+                           n_groups, n_waves, ms, A, pa.tb);
         return;
     }
     const int LB = EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(mv_fat_max_threads<NU>()), WPB = LB / 64;
@@ -830,6 +875,16 @@ int read_matvec_timeline(unsigned long long *out, int max_workgroups) {
 #endif
 }
 
+int read_matvec_timeline_rows(unsigned long long *out, int max_workgroups) {   // one stamp per workgroup: the row loads of a prologue launch issued
+#ifdef MG4_TIMELINE
+    const int n = std::min(max_workgroups, 1024);
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tl_rows), (size_t)n * sizeof(unsigned long long)) != hipSuccess) return -1;
+    return n;
+#else
+    (void)out; (void)max_workgroups; return 0;
+#endif
+}
+
 static bool fill_matset(MatSet &ms, const QWeight *const *W, float *const *y, const float *const *residual, int n) {
     ms = MatSet{};
     ms.n = n; ms.rows_each = W[0]->rows; ms.w0 = *W[0]; ms.y0 = y[0]; ms.res0 = residual ? residual[0] : nullptr;
@@ -867,11 +922,11 @@ static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, doub
     const bool bar = pro != PRO_NONE && issue_bar && BUILT;
     note_kernel("k_matvec_mix<%d, %d, %d, %d, %d, %s>", T1, T2, NU, pro == PRO_NONE ? 0 : 1, (int)EPI, bar ? "true" : "false");
     const dim3 grid((unsigned)total), block((unsigned)threads);
-    if (pro == PRO_NONE) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_NONE, EPI>), grid, block, 0, s, m1, m2, A, pa, ng1, nw1, ng2, nw2); return; }
+    if (pro == PRO_NONE) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_NONE, EPI>), grid, block, 0, s, pa.x, pa.w, m1.w0.cols, threads, ng1, nw1, ng2, nw2, m1, m2, A, pa.tb); return; }
     if constexpr (BUILT) {
-        if (bar) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI, true>), grid, block, mv_prologue_lds(m1.w0.cols), s, m1, m2, A, pa, ng1, nw1, ng2, nw2); return; }
+        if (bar) { hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI, true>), grid, block, mv_prologue_lds(m1.w0.cols), s, pa.x, pa.w, m1.w0.cols, threads, ng1, nw1, ng2, nw2, m1, m2, A, pa.tb); return; }
     }
-    hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI>), grid, block, mv_prologue_lds(m1.w0.cols), s, m1, m2, A, pa, ng1, nw1, ng2, nw2);
+    hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI>), grid, block, mv_prologue_lds(m1.w0.cols), s, pa.x, pa.w, m1.w0.cols, threads, ng1, nw1, ng2, nw2, m1, m2, A, pa.tb);
 }
 template <int T1, int T2, int EPI = EPI_STORE>
 static bool launch_mix_nu(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
@@ -1290,6 +1345,8 @@ void launch_rms_quant(const float *x, const float *w, int N, int K, const ActQ &
 }
 
 __global__ __launch_bounds__(256) void k_silu_mul_quant(const float *__restrict__ a, const float *__restrict__ b, const int K, const ActQ A, const int mask, const Tables tb) {
+    // (a, b, K) is the preloaded head: the two row loads wait for nothing.  Without preload every argument is requested in one batch at entry ("Kernel arguments", above matvec_run)
+    if (MV_PIN_AT_ENTRY) asm volatile("" ::"s"(a), "s"(b), "s"(K), "s"(mask), "s"(tb.silu), "s"(A.q8k), "s"(A.dk), "s"(A.bsk), "s"(A.bsq), "s"(A.q80), "s"(A.d0), "s"(A.d1), "s"(A.s1), "s"(A.sum0));
     const size_t row = blockIdx.y;
     const int i = blockIdx.x * 1024 + threadIdx.x * 4;
     const bool in = i < K;
@@ -1351,16 +1408,18 @@ __device__ float dequant_elem(int type, const uint8_t *row, int e) {
     default: return 0.0f;
     }
 }
-__global__ void k_get_rows(int type, const uint8_t *__restrict__ table, int K, size_t row_bytes, const int *__restrict__ tokens, float *__restrict__ out) {
+constexpr int GR_THREADS = 256;
+__global__ __launch_bounds__(GR_THREADS) void k_get_rows(int type, const uint8_t *__restrict__ table, int K, size_t row_bytes, const int *__restrict__ tokens, float *__restrict__ out) {
+    if (MV_PIN_AT_ENTRY) asm volatile("" ::"s"(type), "s"(table), "s"(K), "s"(row_bytes), "s"(tokens), "s"(out));   // one batch; the token id itself lives in device memory
     const int t = blockIdx.x;
     if (tokens[t] < 0) return;                     // embedding row: already written by the host copy
     const uint8_t *row = table + (size_t)tokens[t] * row_bytes;
-    const int e = blockIdx.y * blockDim.x + threadIdx.x;
+    const int e = blockIdx.y * GR_THREADS + threadIdx.x;   // the workgroup size as a constant: blockDim.x is a hidden kernel argument, a scalar load of its own
     if (e < K) out[(size_t)t * K + e] = dequant_elem(type, row, e);
 }
 void launch_get_rows(int type, const uint8_t *raw_table, int K, const int *tokens, int N, float *out, hipStream_t s) {
     note_kernel("k_get_rows");
-    hipLaunchKernelGGL(k_get_rows, dim3((unsigned)N, (unsigned)((K + 255) / 256)), dim3(256), 0, s, type, raw_table, K, gt_nbytes(type, (size_t)K), tokens, out);
+    hipLaunchKernelGGL(k_get_rows, dim3((unsigned)N, (unsigned)((K + GR_THREADS - 1) / GR_THREADS)), dim3(GR_THREADS), 0, s, type, raw_table, K, gt_nbytes(type, (size_t)K), tokens, out);
 }
 
 // =====================================================================================================================
@@ -1728,23 +1787,29 @@ static int attn_ctx_that_fits(int hd, int rows) { int n = 0; while (attn_lds_byt
 int attn_max_ctx(int hd) { return attn_ctx_that_fits(hd, 1); }
 int attn_draft_max_ctx(int hd) { return attn_ctx_that_fits(hd, DRAFT_ROWS); }
 
+// Argument order (see "Kernel arguments" above matvec_run): what the prologue's first loads need -- the position's address, the three projections, the two RoPE tables
+// and E, 13 dwords -- stands in front, inside the preloaded head; the caches, the exp table and the output follow.  The position itself lives in device memory, so its load
+// stays: MG4_ATTN_PIN (in the body, right behind that load) consumes the position and every argument, so all of them are requested in the position's round trip and none
+// in a further one behind it.
+#define MG4_ATTN_PIN() asm volatile("" ::"s"(pos_), "s"(q), "s"(kin), "s"(vin), "s"(cos_tab), "s"(sin_tab), "s"(E), "s"(kc), "s"(vc), "s"(tb.exp), "s"(out))
 template <int HD, bool FUSED, bool BATCHED = false, int VS = 1>
-__global__ __launch_bounds__(AT_THREADS) void k_attn_llm(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
-                                                         __half *__restrict__ vc, int E, const int *__restrict__ n_past, const float *__restrict__ cos_tab,
-                                                         const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot = nullptr,
+__global__ __launch_bounds__(AT_THREADS) void k_attn_llm(const int *__restrict__ n_past, float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin,
+                                                         const float *__restrict__ cos_tab, const float *__restrict__ sin_tab, int E, __half *__restrict__ kc,
+                                                         __half *__restrict__ vc, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot = nullptr,
                                                          size_t seq_stride = 0) {
     constexpr bool DRAFT = false;
     constexpr int n_ctx = 0;                                      // DRAFT only
 #include "attn_llm_body.hpp"
 }
 template <int HD, int VS = 1>
-__global__ __launch_bounds__(AT_THREADS) void k_attn_llm_draft(float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin, __half *__restrict__ kc,
-                                                               __half *__restrict__ vc, int E, const int *__restrict__ n_past, int n_ctx, const float *__restrict__ cos_tab,
-                                                               const float *__restrict__ sin_tab, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot,
+__global__ __launch_bounds__(AT_THREADS) void k_attn_llm_draft(const int *__restrict__ n_past, float *__restrict__ q, const float *__restrict__ kin, const float *__restrict__ vin,
+                                                               const float *__restrict__ cos_tab, const float *__restrict__ sin_tab, int E, int n_ctx, __half *__restrict__ kc,
+                                                               __half *__restrict__ vc, const Tables tb, float *__restrict__ out, const int *__restrict__ row_slot,
                                                                size_t seq_stride) {
     constexpr bool FUSED = true, BATCHED = true, DRAFT = true;
 #include "attn_llm_body.hpp"
 }
+#undef MG4_ATTN_PIN
 
 // the supported head sizes as compile-time constants: f(std::integral_constant<int, HD>) for hd's HD; false (f not called) for an unsupported head size
 template <class F> static bool attn_for_head_size(int hd, F &&f) {
@@ -1771,20 +1836,20 @@ static void launch_attn_body_vs(bool fused, float *q, const float *k, const floa
     if constexpr (DRAFT) {
         if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_draft<HD, VS>)); attr = true; }
         if (VS == 1) note_kernel("k_attn_llm_draft<%d>", HD); else note_kernel("k_attn_llm_draft<%d, %d>", HD, VS);
-        hipLaunchKernelGGL((k_attn_llm_draft<HD, VS>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, n_ctx, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+        hipLaunchKernelGGL((k_attn_llm_draft<HD, VS>), grid, dim3(AT_THREADS), lds, s, n_past, q, k, v, cos_tab, sin_tab, n_head * HD, n_ctx, kc, vc, tb, out, row_slot, seq_stride);
     } else if constexpr (BATCHED) {
         if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, true, VS>)); attr = true; }
-        hipLaunchKernelGGL((k_attn_llm<HD, true, true, VS>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+        hipLaunchKernelGGL((k_attn_llm<HD, true, true, VS>), grid, dim3(AT_THREADS), lds, s, n_past, q, k, v, cos_tab, sin_tab, n_head * HD, kc, vc, tb, out, row_slot, seq_stride);
     } else if constexpr (VS == 1) {
         if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true>));
                      HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, false>)); attr = true; }
         note_kernel("k_attn_llm<%d, %s, false>", HD, fused ? "true" : "false");
-        hipLaunchKernelGGL((fused ? k_attn_llm<HD, true> : k_attn_llm<HD, false>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out,
+        hipLaunchKernelGGL((fused ? k_attn_llm<HD, true> : k_attn_llm<HD, false>), grid, dim3(AT_THREADS), lds, s, n_past, q, k, v, cos_tab, sin_tab, n_head * HD, kc, vc, tb, out,
                            row_slot, seq_stride);
     } else {
         if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm<HD, true, false, VS>)); attr = true; }
         note_kernel("k_attn_llm<%d, true, false, %d>", HD, VS);
-        hipLaunchKernelGGL((k_attn_llm<HD, true, false, VS>), grid, dim3(AT_THREADS), lds, s, q, k, v, kc, vc, n_head * HD, n_past, cos_tab, sin_tab, tb, out, row_slot, seq_stride);
+        hipLaunchKernelGGL((k_attn_llm<HD, true, false, VS>), grid, dim3(AT_THREADS), lds, s, n_past, q, k, v, cos_tab, sin_tab, n_head * HD, kc, vc, tb, out, row_slot, seq_stride);
     }
 }
 // vs: 1, or 2 / 4 for the fused forms where the head's HD / 8 chunks divide (every supported head size does); anything else is refused
@@ -2680,6 +2745,7 @@ __device__ __forceinline__ void argmax_wave(float &best, int &bi) {
     for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bi, o); argmax_combine(best, bi, ov, oi); }
 }
 __global__ __launch_bounds__(256) void k_argmax_part(const float *__restrict__ x, int n, float *__restrict__ pv, int *__restrict__ pi) {
+    if (MV_PIN_AT_ENTRY) asm volatile("" ::"s"(x), "s"(n), "s"(pv), "s"(pi));
     float best = -INFINITY; int bi = 0x7FFFFFFF;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += AM_BLOCKS * 256) { const float v = x[i]; if (v > best) { best = v; bi = i; } }
     __shared__ float sv[4]; __shared__ int si[4];
@@ -3215,7 +3281,10 @@ __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ 
 }
 void launch_batch_begin(int *n_past, const int *row_slot, const int *row_pos, int B, hipStream_t s) { hipLaunchKernelGGL(k_batch_begin, dim3(1), dim3(64), 0, s, n_past, row_slot, row_pos, B); }
 // end of a decode step: the KV position advances and the greedy token becomes the next input (the host may overwrite it)
-__global__ void k_advance(int *n_past, int n, int *tok0, const int *argmax) { *n_past += n; if (tok0) *tok0 = *argmax; }
+__global__ void k_advance(int *n_past, int n, int *tok0, const int *argmax) {
+    if (MV_PIN_AT_ENTRY) asm volatile("" ::"s"(n_past), "s"(n), "s"(tok0), "s"(argmax));
+    *n_past += n; if (tok0) *tok0 = *argmax;
+}
 void launch_advance(int *n_past, int n, int *tok0, const int *argmax, hipStream_t s) { note_kernel("k_advance"); hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, s, n_past, n, tok0, argmax); }
 // Profiling gate (Engine::profile_sites): one wave that keeps the stream busy for `us` microseconds (s_memrealtime: the constant 100 MHz clock) while the host
 // queues the step's launches behind it, so the per-site event pairs time the GPU and not the host's launch rate.  Bounded: at most 2^20 polls even if the clock stood still.

@@ -62,6 +62,7 @@ int minigpt4_amd_copy_arenas(struct MiniGPT4Context *dst, struct MiniGPT4Context
 
 // ---- single-kernel hooks ---------------------------------------------------------------------------------------------------
 
+int minigpt4_amd_timeline_rows(unsigned long long *out, int max_workgroups) { return (out && max_workgroups > 0) ? read_matvec_timeline_rows(out, max_workgroups) : -1; }
 int minigpt4_amd_timeline(unsigned long long *out, int max_workgroups) { return (out && max_workgroups > 0) ? read_matvec_timeline(out, max_workgroups) : -1; }
 
 int minigpt4_amd_convert_q3k_q6k(const void *src, void *dst, int64_t n_blocks) {

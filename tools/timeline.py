@@ -6,7 +6,7 @@
 variant 1 = activation row prepared by its own launch, 2 = rms-norm prologue inside the mat-vec (the decode's qkv / w1|w3 flavour), 3 = the batched decode's
 multi-row launch (k_matvec_tn, 4 prepared rows), 4 = the same with 2 rows, 5 / 6 = 2 / 4 rows prepared inside the launch (rms-norm prologue), 7 = plain prologue + residual
 in place (the decode's wo flavour).  MG4_MV_IB = 1: variants 2 and 7 with the issue barrier.  Thread 0 of every workgroup
-stamps the 100 MHz constant clock at entry / first weight request / row ready / first group done / last group done / results stored; printed per stage as the
+stamps the 100 MHz constant clock at entry / rows requested (prologue variants: its row loads issued, before the issue barrier) / first weight request / row ready / first group done / last group done / results stored; printed per stage as the
 min / median / max over workgroups, in microseconds after the EARLIEST workgroup's entry, next to the hipEvent time of the launch (which additionally holds the
 dispatch + end-of-kernel cost).  GPU only."""
 import ctypes
@@ -45,10 +45,20 @@ def main():
             print("  (library built without MG4_TIMELINE)" if n == 0 else "  timeline read failed")
             continue
         a = np.frombuffer(buf, np.uint64).reshape(1024, 8).astype(np.float64)
-        a = a[a[:, 0] > 0]                                   # workgroups that ran in the last launch (all slots are rewritten by every launch of <= 1024 workgroups)
-        a = a[a[:, 5] >= a[:, 0]]
-        a = a[a[:, 0] > a[:, 0].max() - 1e4]                # drop stale slots of an earlier, wider launch (older than 100 us)
+        rows = np.zeros(1024)
+        if hasattr(L, "minigpt4_amd_timeline_rows"):         # prologue forms: the row loads issued (in front of the issue barrier and the first weight request)
+            rbuf = (ctypes.c_ulonglong * 1024)()
+            L.minigpt4_amd_timeline_rows.argtypes = [ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
+            if L.minigpt4_amd_timeline_rows(rbuf, 1024) > 0:
+                rows = np.frombuffer(rbuf, np.uint64).astype(np.float64)
+        live = a[:, 0] > 0                                   # workgroups that ran in the last launch (all slots are rewritten by every launch of <= 1024 workgroups)
+        live &= a[:, 5] >= a[:, 0]
+        live &= a[:, 0] > a[live, 0].max() - 1e4             # drop stale slots of an earlier, wider launch (older than 100 us)
+        a, rows = a[live], rows[live]
         t0 = a[:, 0].min()
+        if variant in (2, 7) and (rows >= a[:, 0]).all():
+            v = (rows - t0) / 100.0
+            print(f"  {'rows requested':22s} min {v.min():6.2f}  median {np.median(v):6.2f}  max {v.max():6.2f} us   ({len(v)} workgroups)")
         for i, name in enumerate(STAGES):
             v = (a[:, i] - t0) / 100.0                       # 100 MHz -> us
             print(f"  {name:22s} min {v.min():6.2f}  median {np.median(v):6.2f}  max {v.max():6.2f} us   ({len(v)} workgroups)")
