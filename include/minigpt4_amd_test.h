@@ -253,6 +253,18 @@ MINIGPT4_API int minigpt4_amd_test_attn_draft(int mode, int n_head, int hd, int 
  * 3 = HIP error */
 MINIGPT4_API int minigpt4_amd_test_attn_vsplit(int form, int vs, int n_head, int hd, int n_ctx, int n_slot, int rows, const int32_t *row_slot, const int32_t *n_past,
                                                int computed_exp, const float *q, const float *k, const float *v, uint16_t *kc, uint16_t *vc, float *out);
+/* The two attention paths that are otherwise reached only through a loaded model, on ONE conversation's caches kc, vc [n_ctx][n_head * hd] (fp16 bit patterns, changed in
+ * place); q, k, v [rows][n_head * hd] fp32 raw projections; computed_exp as above.
+ * mode 0: the key-split decode attention (launch_attn_llm_split: k_attn_split_scores + k_attn_split_pv, `splits` in 2 .. 16 workgroups per head) for `rows` successive
+ * decode steps, step i on row i at position n_past + i, all on ONE workspace of attn_split_workspace_bytes bytes: filled with 0xFF bytes, its last 1 KiB + n_head words
+ * zeroed ONCE before the first step (what the launcher asks of its caller), nothing between the steps.  q_rot is not used (may be NULL).
+ * mode 1: the plain form of the decode attention (prompt rows beyond the prompt kernels' LDS rows): launch_rope_kv of the rows at positions n_past .. n_past + rows - 1,
+ * then launch_attn_llm(fused = false); `splits` is ignored; q_rot [rows][E] receives the rotated q.
+ * out [rows + 1][n_head * hd]: prefilled with 0xFF bytes, row `rows` is a guard row the launches must not touch.  1 = refused before any device is touched (a NULL array,
+ * mode not 0 / 1, hd not 32 / 64 / 128, n_head outside 1 .. 64, rows outside 1 .. 64, n_past < 0, n_past + rows > n_ctx, n_ctx above the kernel's LDS rows, mode 0 with splits
+ * outside 2 .. 16, mode 1 without q_rot), 2 = no device, 3 = HIP error */
+MINIGPT4_API int minigpt4_amd_test_attn_rows(int mode, int n_head, int hd, int n_ctx, int n_past, int rows, int splits, int computed_exp, const float *q, const float *k,
+                                             const float *v, uint16_t *kc, uint16_t *vc, float *q_rot, float *out);
 
 /* ---- host-only logic (no GPU needed) -------------------------------------------------------------------------------- */
 /* the n-gram drafter of minigpt4_amd_decode_lookup alone (csrc/draft.cpp): the draft for a history of n tokens, at most n_draft tokens into out; returns its length

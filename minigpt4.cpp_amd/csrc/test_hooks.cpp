@@ -1275,6 +1275,53 @@ int minigpt4_amd_test_attn_vsplit(int form, int vs, int n_head, int hd, int n_ct
         return 0;
     });
 }
+// The two attention paths no other hook reaches, on ONE conversation's caches kc / vc [n_ctx][n_head * hd] (fp16 bit patterns, changed in place); q, k, v [rows][E] fp32 raw
+// projections.  mode 0: `rows` successive decode steps through launch_attn_llm_split on ONE workspace -- filled with 0xFF bytes, then its last 1 KiB + n_head words zeroed,
+// once, before the first step -- step i at position n_past + i.  mode 1: launch_rope_kv of the rows at n_past .. n_past + rows - 1, then launch_attn_llm(fused = false);
+// q_rot [rows][E] receives the rotated q.  out [rows + 1][E]: prefilled with 0xFF bytes, the last row is a guard.
+int minigpt4_amd_test_attn_rows(int mode, int n_head, int hd, int n_ctx, int n_past, int rows, int splits, int computed_exp, const float *q, const float *k, const float *v,
+                                uint16_t *kc, uint16_t *vc, float *q_rot, float *out) {
+    if (!q || !k || !v || !kc || !vc || !out || (mode != 0 && mode != 1) || (hd != 32 && hd != 64 && hd != 128) || n_head < 1 || n_head > 64 || rows < 1 || rows > 64 || n_past < 0 ||
+        n_ctx < 1 || n_past > n_ctx - rows || n_ctx > attn_max_ctx(hd) || (mode == 0 && (splits < 2 || splits > 16)) || (mode == 1 && !q_rot)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, cache = (size_t)n_ctx * E, RE = (size_t)rows * E, GE = RE + E;
+        std::vector<float> c, sn;
+        rope_tables(n_ctx, hd, c, sn);
+        const size_t ws_bytes = mode == 0 ? attn_split_workspace_bytes(n_head, hd, n_ctx, splits) : 16, ws_zero = 1024 + (size_t)n_head * 4;
+        DevBuf dc(c.size() * 4), dsn(sn.size() * 4), dq(RE * 4), dk(RE * 4), dv(RE * 4), dkc(cache * 2), dvc(cache * 2), dout(GE * 4), dnp(4), dtab(65536 * 2), dws(ws_bytes);
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dq.p, q, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dk.p, k, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, RE * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dkc.p, kc, cache * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dvc.p, vc, cache * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dnp.p, &n_past, 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xFF, GE * 4));
+        Tables tb;                                                // as in minigpt4_amd_test_attn_draft
+        { std::vector<__half> e(65536); int last = 0;
+          for (int i = 0; i < 65536; i++) e[(size_t)i] = __float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)i))));
+          for (int i = 0; i < 0x7C00; i++) if (__half2float(e[(size_t)(0x8000 + i)]) != 0.0f) last = i;
+          HIP_CHECK(hipMemcpy(dtab.p, e.data(), 131072, hipMemcpyHostToDevice));
+          tb.exp = computed_exp ? nullptr : dtab.as<__half>(); tb.exp_neg_n = (last + 1 + 2047) / 2048 * 2048; }
+        if (mode == 0) {
+            HIP_CHECK(hipMemset(dws.p, 0xFF, ws_bytes));
+            HIP_CHECK(hipMemset(static_cast<unsigned char *>(dws.p) + (ws_bytes - ws_zero), 0, ws_zero));   // the arrival counters: once, never between the steps
+            for (int i = 0; i < rows; i++) {
+                if (i) launch_set_int(dnp.as<int>(), n_past + i, nullptr);
+                launch_attn_llm_split(dq.as<float>() + (size_t)i * E, dk.as<float>() + (size_t)i * E, dv.as<float>() + (size_t)i * E, dkc.as<__half>(), dvc.as<__half>(), n_head, hd,
+                                      dnp.as<int>(), n_ctx, dc.as<float>(), dsn.as<float>(), tb, dout.as<float>() + (size_t)i * E, dws.p, splits, nullptr);
+            }
+        } else {
+            launch_rope_kv(dq.as<float>(), dk.as<float>(), dv.as<float>(), rows, n_head, hd, dnp.as<int>(), dc.as<float>(), dsn.as<float>(), dkc.as<__half>(), dvc.as<__half>(), nullptr);
+            launch_attn_llm(dq.as<float>(), dk.as<float>(), dv.as<float>(), dkc.as<__half>(), dvc.as<__half>(), rows, n_head, hd, dnp.as<int>(), n_ctx, dc.as<float>(), dsn.as<float>(), tb,
+                            dout.as<float>(), false, nullptr);
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dout.p, GE * 4, hipMemcpyDeviceToHost));
+        if (q_rot) HIP_CHECK(hipMemcpy(q_rot, dq.p, RE * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc, dkc.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 int minigpt4_amd_test_ngram_draft(const int32_t *history, int n, int ngram_max, int ngram_min, int n_draft, int32_t *out) {
     if (n < 0 || (n > 0 && !history) || !out || ngram_min < 1 || ngram_max < ngram_min || n_draft < 0) return -1;
     NgramDrafter d(ngram_max, ngram_min);

@@ -308,6 +308,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
+        L.minigpt4_amd_test_attn_rows.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_last_error.restype = CHAR_PTR
@@ -1093,6 +1094,24 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_attn_vsplit rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return out, kc, vc
+
+    def amd_test_attn_rows(self, mode: int, q: np.ndarray, k: np.ndarray, v: np.ndarray, kc: np.ndarray, vc: np.ndarray, n_head: int, n_past: int, splits: int = 0,
+                           computed_exp: bool = True):
+        """mode 0: q.shape[0] successive decode steps of the key-split attention (`splits` workgroups per head) on one workspace; mode 1: launch_rope_kv + the plain form
+        of the decode attention for the rows at n_past ...  q, k, v [rows][E]; fp16 caches [n_ctx][E] as uint16 patterns.  Returns (out [rows + 1][E] -- the last row is
+        the hook's 0xFF guard row --, q_rot [rows][E] (mode 1, else None), kc, vc) -- copies."""
+        q, k, v = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+        kc, vc = np.array(kc, np.uint16, order="C"), np.array(vc, np.uint16, order="C")
+        R, E = q.shape
+        C, _ = kc.shape
+        out = np.zeros((R + 1, E), np.float32)
+        q_rot = np.zeros_like(q) if mode == 1 else None
+        rc = self.library.minigpt4_amd_test_attn_rows(int(mode), n_head, E // n_head, C, int(n_past), R, int(splits), int(computed_exp), q.ctypes.data_as(FLOAT_PTR),
+                                                      k.ctypes.data_as(FLOAT_PTR), v.ctypes.data_as(FLOAT_PTR), kc.ctypes.data_as(VOID_PTR), vc.ctypes.data_as(VOID_PTR),
+                                                      q_rot.ctypes.data_as(FLOAT_PTR) if q_rot is not None else None, out.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_attn_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return out, q_rot, kc, vc
 
     def amd_test_ngram_draft(self, history: Sequence[int], ngram_max: int, ngram_min: int, n_draft: int) -> List[int]:
         """The draft minigpt4_amd_decode_lookup's host drafter proposes for `history` (its last token = the one about to be evaluated)."""

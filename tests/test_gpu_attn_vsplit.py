@@ -10,7 +10,8 @@ pytestmark = pytest.mark.gpu
 
 N_HEAD, N_CTX = 3, 1024                                 # an odd head count catches head indexing
 # cached keys: only the own key / one cached key / the partition boundary P = 32 (hd 128) / the end of the NPRE x P = 512-key prefetch and the first steady round /
-# a ragged steady round.  hd 64 (P = 64) and hd 32 (P = 128) prefetch 1024 / 2048 keys: they take the steady loop at none of these, hd 128 at the last four.
+# a ragged steady round.  hd 64 (P = 64) and hd 32 (P = 128) prefetch 1024 / 2048 keys: they take the steady loop at none of these, hd 128 at the last four
+# (tests/test_gpu_attn_kernels.py takes every head size through its own steady loop, VS = 1, against a float64 reference: contexts of 1664 / 3200 rows).
 N_PAST = (0, 1, 31, 32, 33, 511, 512, 513, 777)
 HD_VS = [(128, 2), (128, 4), (64, 2), (64, 4), (32, 2), (32, 4)]   # hd 32, VS 4: one 8-dim chunk per workgroup
 _INPUTS, _REF = {}, {}
