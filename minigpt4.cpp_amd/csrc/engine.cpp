@@ -90,20 +90,18 @@ Engine::~Engine() {
     if (trace_file_) { fclose(trace_file_); trace_file_ = nullptr; }
     if (stream_hung_) {   // see engine.hpp: leak the device side, touch nothing that synchronises
         llm_arena_.abandon(); vis_arena_.abandon(); buf_arena_.abandon(); ri_arena_.abandon(); vgen_arena_.abandon();
+        // the owning members would free themselves right after this body: hipFree / hipHostFree wait for a stream that never drains.  Every handle of the class is
+        // listed here and nowhere else
+        abandon_all(pfx_k_, pfx_v_, score_buf_, score_lp_, score_glp_, score_tgt_, score_greedy_, topn_d_, topn_h_, topn_in_, topn_hin_, topn_ev_,
+                    pen_d_, pen_h_, pen_out_d_, pen_out_h_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
+                    guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_d_, con_h_, con_out_d_, con_out_h_, con_row_h_);
+        for (Constraint &c : con_) c.dev.abandon();
         return;
     }
     if (stream_) HIP_IGNORE(hipStreamSynchronize(stream_));
     for (auto &e : site_events_) { HIP_IGNORE(hipEventDestroy(e.a)); HIP_IGNORE(hipEventDestroy(e.b)); }
     if (stage_) HIP_IGNORE(hipFree(stage_));
-    prefix_free();
-    score_free();
-    topn_free();
-    pen_free();
-    spec_free();
-    beam_free();
-    guide_free();
-    con_free();
-    release_buffers();
+    release_buffers();                                                       // (the features' own buffers free themselves behind this body: the stream has drained)
     if (stream_) HIP_IGNORE(hipStreamDestroy(stream_));
 }
 void Engine::sync() { (void)flush(); HIP_CHECK(hipStreamSynchronize(stream_)); }
@@ -655,7 +653,7 @@ void Engine::alloc_buffers() {
     act_.xh = takeh(B * Kmax); act_.xf = takef(B * Kmax);
     static_assert(MAX_CONVERSATIONS * 4 <= 256, "per-conversation scalars live in 256-byte slabs");
     d_npast_ = reinterpret_cast<int *>(buf_arena_.take(256)); d_argmax_ = reinterpret_cast<int *>(buf_arena_.take(256)); d_feed_ = reinterpret_cast<int *>(buf_arena_.take(256));
-    d_btok_ = reinterpret_cast<int *>(buf_arena_.take(768)); d_bslot_ = d_btok_ + MAX_CONVERSATIONS; d_bpos_ = d_bslot_ + MAX_CONVERSATIONS;
+    d_btok_ = reinterpret_cast<int *>(buf_arena_.take(BSTAGE_BYTES)); d_bslot_ = d_btok_ + MAX_CONVERSATIONS; d_bpos_ = d_bslot_ + MAX_CONVERSATIONS;
     batch_graph_.assign((size_t)MAX_CONVERSATIONS + 1, nullptr);
     d_tokens_ = reinterpret_cast<int *>(buf_arena_.take(B * 4));
     d_scratch_ = buf_arena_.take(8192);
@@ -668,10 +666,10 @@ void Engine::alloc_buffers() {
         act_.ws = reinterpret_cast<float *>(buf_arena_.take(slab_floats * 4)); act_.ws_floats = slab_floats;
         set_mmq2_cus(prop.multiProcessorCount);
     }
-    HIP_CHECK(hipMemset(d_npast_, 0, 256)); HIP_CHECK(hipMemset(d_argmax_, 0, 256)); HIP_CHECK(hipMemset(d_feed_, 0, 256)); HIP_CHECK(hipMemset(d_btok_, 0, 768));
+    HIP_CHECK(hipMemset(d_npast_, 0, 256)); HIP_CHECK(hipMemset(d_argmax_, 0, 256)); HIP_CHECK(hipMemset(d_feed_, 0, 256)); HIP_CHECK(hipMemset(d_btok_, 0, BSTAGE_BYTES));
     HIP_CHECK(hipMemset(d_tokens_, 0, B * 4));
     HIP_CHECK(hipHostMalloc((void **)&h_argmax_, 256, hipHostMallocDefault));
-    HIP_CHECK(hipHostMalloc((void **)&h_bstage_, 768, hipHostMallocDefault));
+    HIP_CHECK(hipHostMalloc((void **)&h_bstage_, BSTAGE_BYTES, hipHostMallocDefault));
     HIP_CHECK(hipHostMalloc((void **)&h_logits_, V * 4, hipHostMallocDefault));
     memset(h_argmax_, 0, 256);
     // vision
@@ -1239,7 +1237,6 @@ int Engine::eval_chunk(const int *row_tok, int N, const float *embd, const Score
     if (N <= 0) return 0;
     if (weights_missing()) return 1;
     Conversation &cv = conv_[(size_t)cur_];
-    if (logits_host_slot_ == cur_) logits_host_slot_ = -1;
     launch_set_int(d_npast_ + cur_, cv.n_committed, stream_);
     if (N == 1 && row_tok[0] >= 0) {
         launch_set_int(d_feed_ + cur_, row_tok[0], stream_);
@@ -1259,9 +1256,15 @@ int Engine::eval_chunk(const int *row_tok, int N, const float *embd, const Score
         Pass p{N}; p.score = score;
         forward(p, stream_);                        // k_get_rows skips rows whose id is negative
     }
-    cv.n_committed += N; cv.has_logits = true;
-    cv.hist.insert(cv.hist.end(), row_tok, row_tok + N);
+    commit_rows(cur_, row_tok, N, /*past=*/false);                           // n_past counted the rows when they were queued (a caller that queued nothing adds them itself)
     return 0;
+}
+void Engine::commit_rows(int slot, const int *ids, int n, bool past) {
+    Conversation &cv = conv_[(size_t)slot];
+    cv.n_committed += n; if (past) cv.n_past += n;
+    cv.has_logits = true;
+    cv.hist.insert(cv.hist.end(), ids, ids + n);                             // invariant: hist.size() == n_committed
+    if (logits_host_slot_ == slot) logits_host_slot_ = -1;
 }
 
 // Deferred prefill batching.  The reference evaluates every prompt fragment separately (system prompt, "Human: <Img>", the 32 image rows,
@@ -1296,16 +1299,12 @@ int Engine::set_prefix_cache(int max_rows) {
     prefix_free();
     if (max_rows == 0) return 0;
     const size_t bytes = layers_.size() * (size_t)max_rows * llm_.n_embd * sizeof(__half);
-    HIP_CHECK(hipMalloc((void **)&pfx_k_, bytes));
-    if (hipError_t e = hipMalloc((void **)&pfx_v_, bytes); e != hipSuccess) { HIP_IGNORE(hipFree(pfx_k_)); pfx_k_ = nullptr; HIP_CHECK(e); }
+    DevPtr<__half> k(bytes), v(bytes);                                       // both or neither
+    pfx_k_ = std::move(k); pfx_v_ = std::move(v);
     pfx_max_ = max_rows;
     return 0;
 }
-void Engine::prefix_free() {
-    if (pfx_k_) HIP_IGNORE(hipFree(pfx_k_));
-    if (pfx_v_) HIP_IGNORE(hipFree(pfx_v_));
-    pfx_k_ = pfx_v_ = nullptr; pfx_max_ = 0; pfx_ids_.clear();
-}
+void Engine::prefix_free() { reset_all(pfx_k_, pfx_v_); pfx_max_ = 0; pfx_ids_.clear(); }
 // Every listed conversation that starts at position 0 with rows queued and matches is served by ONE copy launch (n_rows = the longest match: rows above a shorter match
 // are overwritten by the pass that follows on the stream); its pass then starts at row / position m
 Engine::PrefixPlan Engine::prefix_lookup(const int *slots, int n) {
@@ -1458,31 +1457,27 @@ int Engine::sample_token(const SampleParams &p) {
     if (flush()) throw HipError{hipErrorUnknown, "deferred evaluation failed", __FILE__, __LINE__};
     const Conversation &cv = conv_[(size_t)cur_];
     const float *raw = logits_host();
-    if (con_handle_[cur_] && cv.has_logits) {   // bias, penalties, then the constraint: the ids outside the state's allowed set leave the chain's copy of the row
-        const int V = (int)llm_.n_vocab;
-        pen_row_.assign(raw, raw + V);
-        if ((pen_mode_ || !cv.bias_id.empty()) &&
-            penalise_row(pen_row_.data(), V, cv.hist.data(), cv.hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size()))
-            pen_info_.host_rows++;
-        const unsigned *allowed = con_fetch_row(con_handle_[cur_], con_state_[cur_]);
-        bool any = false;
-        for (int i = 0; i < V; i++) { if ((allowed[i >> 5] >> (i & 31)) & 1u) any = true; else pen_row_[(size_t)i] = -INFINITY; }
-        con_info_.host_rows++;
-        if (!any) { con_info_.stuck++; return CONSTRAINT_EOS; }             // as k_constrain_pick: nothing allowed picks EOS
-        const int id = sampler_.sample(pen_row_.data(), V, p);
-        con_walk(cur_, id);
-        return id;
-    }
-    if (pen_mode_ || !cv.bias_id.empty()) {   // the chain sees penalised logits, as in llama.cpp; h_logits_ (minigpt4_amd_get_logits) stays raw
-        const int V = (int)llm_.n_vocab;
-        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
-        pen_row_.assign(raw, raw + V);
-        if (penalise_row(pen_row_.data(), V, cv.hist.data(), cv.hist.size(), pp, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size())) {
-            pen_info_.host_rows++;
-            return sampler_.sample(pen_row_.data(), V, p);
-        }
-    }
-    return sampler_.sample(raw, (int)llm_.n_vocab, p);
+    const int V = (int)llm_.n_vocab;
+    const bool constrained = con_handle_[cur_] && cv.has_logits;
+    if (!constrained && !pen_mode_ && cv.bias_id.empty()) return sampler_.sample(raw, V, p);
+    // the chain sees penalised logits, as in llama.cpp; h_logits_ (minigpt4_amd_get_logits) stays raw.  Bias, penalties, then the constraint
+    pen_row_.assign(raw, raw + V);
+    pen_host_row(cv, cv.hist, pen_row_.data());
+    if (!constrained) return sampler_.sample(pen_row_.data(), V, p);
+    // the ids outside the state's allowed set leave the chain's copy of the row
+    const unsigned *allowed = con_fetch_row(con_handle_[cur_], con_state_[cur_]);
+    bool any = false;
+    for (int i = 0; i < V; i++) { if ((allowed[i >> 5] >> (i & 31)) & 1u) any = true; else pen_row_[(size_t)i] = -INFINITY; }
+    con_info_.host_rows++;
+    if (!any) { con_info_.stuck++; return CONSTRAINT_EOS; }                 // as k_constrain_pick: nothing allowed picks EOS
+    const int id = sampler_.sample(pen_row_.data(), V, p);
+    con_walk(cur_, id);
+    return id;
+}
+void Engine::pen_host_row(const Conversation &cv, const std::vector<int> &hist, float *row) {
+    if (!pen_mode_ && cv.bias_id.empty()) return;
+    if (penalise_row(row, (int)llm_.n_vocab, hist.data(), hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size()))
+        pen_info_.host_rows++;
 }
 const char *Engine::id_to_token(int id) const {
     if (id == 2) return "</s>";   // llama_token_eos()
@@ -1659,35 +1654,39 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
         Conversation &cv = conv_[(size_t)slots[i]];
         cur_ = slots[i];
         if (cv.n_past + 1 > n_ctx_ && make_room(1)) continue;               // context full (and no automatic shift): sampled, not advanced
-        h_bstage_[B] = forced ? forced[i] : ids_out[i]; h_bstage_[MAX_CONVERSATIONS + B] = slots[i]; h_bstage_[2 * MAX_CONVERSATIONS + B] = cv.n_committed; B++;
+        stage_row(B++, forced ? forced[i] : ids_out[i], slots[i], cv.n_committed);
     }
     if (!B) { report(); return 0; }
-    // oracle-order arithmetic exists for the single-conversation pass only: one pass per conversation (same results as the batched step is tested to
-    // give)
     if (parity_) {
-        for (int r = 0; r < B; r++) { cur_ = h_bstage_[MAX_CONVERSATIONS + r]; const int id = h_bstage_[r]; if (eval_chunk(&id, 1, nullptr)) return 1; conv_[(size_t)cur_].n_past += 1; }
+        if (step_parity(B)) return 1;
         HIP_CHECK(hipStreamSynchronize(stream_));
         report();
         return 0;
     }
-    // rows (token, conversation, position) travel in one copy; the device positions are normally current (k_advance / k_batch_finish keep them), but
-    // a reset may have moved the host's view, so k_batch_begin writes them like eval_chunk does
-    HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
-    launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
-    if (use_graph_) {   // the step for B rows as one hipGraph: the rows live in device memory, so the same graph serves every set of B conversations
-        hipGraphExec_t &ge = batch_graph_[(size_t)B];
-        if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_); });
-        HIP_CHECK(hipGraphLaunch(ge, stream_));
-    } else forward_batch(B, stream_);
-    for (int r = 0; r < B; r++) {
-        const int sl = h_bstage_[MAX_CONVERSATIONS + r];
-        Conversation &cv = conv_[(size_t)sl];
-        cv.n_past += 1; cv.n_committed += 1; cv.has_logits = true;
-        cv.hist.push_back(h_bstage_[r]);
-        if (logits_host_slot_ == sl) logits_host_slot_ = -1;
-    }
+    step_begin(B);
+    step_launch(B);
+    for (int r = 0; r < B; r++) commit_rows(staged_slot(r), &staged_token(r), 1, /*past=*/true);
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
     report();
+    return 0;
+}
+// rows (token, conversation, position) travel in one copy; the device positions are normally current (k_advance / k_batch_finish keep them), but
+// a reset may have moved the host's view, so k_batch_begin writes them like eval_chunk does
+void Engine::step_begin(int B, bool verify) {
+    HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, BSTAGE_BYTES, hipMemcpyHostToDevice, stream_));
+    if (verify) launch_draft_begin(d_npast_, d_bslot_, d_bpos_, stream_); else launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
+}
+// the step as one hipGraph per row count: token ids, conversations and positions live in device memory, so the same graph serves every set of B conversations
+// and every entry point (verify: every R rows of any conversation)
+void Engine::step_launch(int B, bool verify) {
+    if (!use_graph_) { forward_batch(B, stream_, verify); return; }
+    hipGraphExec_t &ge = (verify ? spec_graph_ : batch_graph_)[(size_t)B];
+    if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_, verify); });
+    HIP_CHECK(hipGraphLaunch(ge, stream_));
+}
+// oracle-order arithmetic exists for the single-conversation pass only: one pass per staged row (same results as the batched step is tested to give)
+int Engine::step_parity(int B) {
+    for (int r = 0; r < B; r++) { cur_ = staged_slot(r); const int id = staged_token(r); if (eval_chunk(&id, 1, nullptr)) return 1; conv_[(size_t)cur_].n_past += 1; }
     return 0;
 }
 
@@ -1696,18 +1695,8 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
 // ====================================================================================================================
 void Engine::beam_alloc() {
     if (beam_d_) return;
-    try {
-        HIP_CHECK(hipMalloc((void **)&beam_d_, BEAM_WORDS * 4)); HIP_CHECK(hipHostMalloc((void **)&beam_h_, BEAM_WORDS * 4, hipHostMallocDefault));
-        HIP_CHECK(hipMalloc((void **)&beam_save_, ((size_t)llm_.n_vocab + 2) * 4));
-        HIP_CHECK(hipEventCreateWithFlags(&beam_ev_, hipEventDisableTiming));
-    } catch (...) { beam_free(); throw; }
-}
-void Engine::beam_free() {
-    if (beam_d_) HIP_IGNORE(hipFree(beam_d_));
-    if (beam_h_) HIP_IGNORE(hipHostFree(beam_h_));
-    if (beam_save_) HIP_IGNORE(hipFree(beam_save_));
-    if (beam_ev_) HIP_IGNORE(hipEventDestroy(beam_ev_));
-    beam_d_ = beam_h_ = nullptr; beam_save_ = nullptr; beam_ev_ = nullptr;
+    DevPtr<int> d(BEAM_WORDS * 4); PinPtr<int> h(BEAM_WORDS * 4); DevPtr<float> save(((size_t)llm_.n_vocab + 2) * 4); OwnedEvent ev(0);   // all four or none
+    beam_d_ = std::move(d); beam_h_ = std::move(h); beam_save_ = std::move(save); beam_ev_ = std::move(ev);
 }
 int Engine::beam_search(const int *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int *tokens_out, int *lengths_out, float *scores_out, int *n_out, int *stats) {
     auto refuse = [](const std::string &what) { set_last_error("beam_search: " + what); return 1; };
@@ -1741,14 +1730,13 @@ int Engine::beam_search(const int *slots, int n_beams, int max_tokens, float len
     KvPermuteSlots ps{};
     for (int i = 0; i < BEAM_MAX; i++) {
         beam_h_[i] = i < W ? slots[i] : 0; beam_h_[8 + i] = -1; ps.s[i] = i < W ? slots[i] : 0;
-        reinterpret_cast<float *>(beam_h_)[BEAM_S + i] = i == 0 ? 0.0f : -INFINITY;
+        beam_h_.as<float>()[BEAM_S + i] = i == 0 ? 0.0f : -INFINITY;
     }
     HIP_CHECK(hipMemcpyAsync(beam_d_, beam_h_, 16 * 4, hipMemcpyHostToDevice, stream_));
     HIP_CHECK(hipMemcpyAsync(beam_d_ + BEAM_S, beam_h_ + BEAM_S, 8 * 4, hipMemcpyHostToDevice, stream_));
     if (!parity_) {
-        for (int i = 0; i < W; i++) { h_bstage_[i] = 0; h_bstage_[MAX_CONVERSATIONS + i] = slots[i]; h_bstage_[2 * MAX_CONVERSATIONS + i] = p; }
-        HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
-        launch_batch_begin(d_npast_, d_bslot_, d_bpos_, W, stream_);
+        for (int i = 0; i < W; i++) stage_row(i, 0, slots[i], p);            // k_beam_select writes every step's tokens into d_btok_
+        step_begin(W);
     }
     int *const d_ids = beam_d_ + BEAM_IDS, *const d_rank = beam_d_ + BEAM_RANK;
     float *const d_lp = reinterpret_cast<float *>(beam_d_ + BEAM_LP), *const d_tlp = reinterpret_cast<float *>(beam_d_ + BEAM_TLP), *const d_s = reinterpret_cast<float *>(beam_d_ + BEAM_S);
@@ -1763,13 +1751,7 @@ int Engine::beam_search(const int *slots, int n_beams, int max_tokens, float len
         HIP_CHECK(hipMemcpyAsync(beam_h_ + BEAM_RES, d_res, sizeof(BeamStep), hipMemcpyDeviceToHost, stream_));
         HIP_CHECK(hipEventRecord(beam_ev_, stream_));
         launch_kv_permute(kc_, vc_, seq, (int)conv_.size(), ps, W, d_res->parent, (int)layers_.size(), n_ctx_, (int)llm_.n_embd, book.common, pos, stream_);
-        if (!parity_) {
-            if (use_graph_) {
-                hipGraphExec_t &ge = batch_graph_[(size_t)W];
-                if (!ge) capture_graph(ge, [&] { forward_batch(W, stream_); });
-                HIP_CHECK(hipGraphLaunch(ge, stream_));
-            } else forward_batch(W, stream_);
-        }
+        if (!parity_) step_launch(W);
         HIP_CHECK(hipEventSynchronize(beam_ev_));                            // the result block; the pass is still running
         bool sane = hr.n_live == W && hr.n_fin >= 0 && hr.n_fin <= W;         // the block indexes the host's ancestry
         for (int i = 0; i < W && sane; i++) sane = hr.parent[i] >= 0 && hr.parent[i] < W && hr.tok[i] >= 0 && hr.tok[i] < V && (i >= hr.n_fin || (hr.fin_beam[i] >= 0 && hr.fin_beam[i] < W));
@@ -1810,18 +1792,8 @@ int Engine::beam_search(const int *slots, int n_beams, int max_tokens, float len
 // ====================================================================================================================
 void Engine::guide_alloc() {
     if (guide_d_) return;
-    try {
-        HIP_CHECK(hipMalloc((void **)&guide_mix_, (size_t)GUIDE_MAX * llm_.n_vocab * 4));
-        HIP_CHECK(hipMalloc((void **)&guide_d_, GUIDE_WORDS * 4)); HIP_CHECK(hipHostMalloc((void **)&guide_h_, GUIDE_WORDS * 4, hipHostMallocDefault));
-        HIP_CHECK(hipEventCreateWithFlags(&guide_ev_, hipEventDisableTiming));
-    } catch (...) { guide_free(); throw; }
-}
-void Engine::guide_free() {
-    if (guide_mix_) HIP_IGNORE(hipFree(guide_mix_));
-    if (guide_d_) HIP_IGNORE(hipFree(guide_d_));
-    if (guide_h_) HIP_IGNORE(hipHostFree(guide_h_));
-    if (guide_ev_) HIP_IGNORE(hipEventDestroy(guide_ev_));
-    guide_mix_ = nullptr; guide_d_ = guide_h_ = nullptr; guide_ev_ = nullptr;
+    DevPtr<float> mix((size_t)GUIDE_MAX * llm_.n_vocab * 4); DevPtr<int> d(GUIDE_WORDS * 4); PinPtr<int> h(GUIDE_WORDS * 4); OwnedEvent ev(0);   // all four or none
+    guide_mix_ = std::move(mix); guide_d_ = std::move(d); guide_h_ = std::move(h); guide_ev_ = std::move(ev);
 }
 int Engine::guide_prepare(const char *name, const int *pos, const int *neg, int n, float scale, int *all) {
     auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
@@ -1846,10 +1818,10 @@ int Engine::guided_logits(const int *pos, const int *neg, int n, float scale, fl
     const int V = (int)llm_.n_vocab;
     guide_alloc();
     HIP_CHECK(hipStreamSynchronize(stream_));                                // guide_h_ feeds no earlier copy
-    GuidePair *tab = reinterpret_cast<GuidePair *>(guide_h_);
+    GuidePair *tab = guide_h_.as<GuidePair>();
     for (int i = 0; i < n; i++) tab[i] = GuidePair{pos[i], neg[i], scale, -1, -1, {0, 0, 0}};
     HIP_CHECK(hipMemcpyAsync(guide_d_, guide_h_, (size_t)n * sizeof(GuidePair), hipMemcpyHostToDevice, stream_));
-    if (!launch_guide_rows(logits_, V, V, n, reinterpret_cast<const GuidePair *>(guide_d_), mixed_out ? guide_mix_ : nullptr, guide_d_ + GUIDE_PICK,
+    if (!launch_guide_rows(logits_, V, V, n, guide_d_.as<const GuidePair>(), mixed_out ? guide_mix_ : nullptr, guide_d_ + GUIDE_PICK,
                            reinterpret_cast<float *>(guide_d_ + GUIDE_VAL), nullptr, stream_)) { set_last_error("guided_logits: " + last_error()); return 1; }
     guide_info_.launches++;
     HIP_CHECK(hipMemcpyAsync(guide_h_ + GUIDE_PICK, guide_d_ + GUIDE_PICK, (size_t)n * 4, hipMemcpyDeviceToHost, stream_));
@@ -1872,18 +1844,11 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
     enum { KERNEL = 0, PEN = 1, CHAIN = 2 };
     int how[GUIDE_MAX], pen_map[GUIDE_MAX], m_pen = 0; size_t pen_off = 0;
     std::vector<PenEntry> tab;
-    PenRow *prow = nullptr; PenEntry *pent = nullptr;
     for (int i = 0; i < n; i++) {
         how[i] = greedy ? KERNEL : CHAIN;
         if (!greedy) continue;
-        const Conversation &cv = conv_[(size_t)pos[i]];
-        const int flags = pen_table(cv, tab);
-        if (!flags && tab.empty()) continue;                                 // the identity
-        if (!prow) { pen_alloc(); prow = reinterpret_cast<PenRow *>(pen_h_); pent = reinterpret_cast<PenEntry *>(pen_h_ + MAX_CONVERSATIONS * sizeof(PenRow)); }
-        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
-        prow[m_pen] = PenRow{i, (int)pen_off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0};   // row = the pair's row of guide_mix_
-        std::copy(tab.begin(), tab.end(), pent + pen_off);
-        pen_off += tab.size(); pen_map[m_pen++] = i; how[i] = PEN;
+        if (!pen_stage_row(conv_[(size_t)pos[i]], /*row of guide_mix_=*/i, m_pen, pen_off, tab)) continue;   // the identity
+        pen_map[m_pen++] = i; how[i] = PEN;
     }
     // 2. room: both conversations of a pair advance, or neither.  The chain penalises with the history from before a shift, as decode_batch's sampling does.  Whether a shift
     // is allowed is arithmetic (shift_allows, the queue is empty, the weights are there), so a make_room that fails here is a failure on the device: thrown like any other,
@@ -1902,11 +1867,11 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
         }
     }
     // 3. the pass's rows: the pairs whose token the kernel hands over first, then those whose token the host writes (one contiguous tail of d_btok_)
-    GuidePair *gt = reinterpret_cast<GuidePair *>(guide_h_);
+    GuidePair *gt = guide_h_.as<GuidePair>();
     int B = 0, n_hand = 0, row_of[GUIDE_MAX];
     auto stage_pair = [&](int i) {
         row_of[i] = B;
-        for (int k = 0; k < 2; k++) { const int sl = k ? neg[i] : pos[i]; h_bstage_[B] = 0; h_bstage_[MAX_CONVERSATIONS + B] = sl; h_bstage_[2 * MAX_CONVERSATIONS + B] = conv_[(size_t)sl].n_committed; B++; }
+        for (int k = 0; k < 2; k++) { const int sl = k ? neg[i] : pos[i]; stage_row(B++, 0, sl, conv_[(size_t)sl].n_committed); }
     };
     for (int i = 0; i < n; i++) { gt[i] = GuidePair{pos[i], neg[i], scale, -1, -1, {0, 0, 0}}; row_of[i] = -1; }
     if (!parity_) for (int i = 0; i < n; i++) if (adv[i] && how[i] == KERNEL) { stage_pair(i); gt[i].pos_tok = row_of[i]; gt[i].neg_tok = row_of[i] + 1; n_hand++; }
@@ -1915,12 +1880,9 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
     const bool host_first = parity_ || m_pen > 0 || !greedy;                 // some id has to reach the host before the pass can be launched
     const bool want_mixed = m_pen > 0 || !greedy;
     HIP_CHECK(hipMemcpyAsync(guide_d_, guide_h_, (size_t)n * sizeof(GuidePair), hipMemcpyHostToDevice, stream_));
-    if (B && !parity_) {
-        HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
-        launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
-    }
+    if (B && !parity_) step_begin(B);
     // 4. the decision: one launch for all pairs; the picks' copy back is awaited after the pass is launched wherever the host does not need them sooner
-    if (!launch_guide_rows(logits_, V, V, n, reinterpret_cast<const GuidePair *>(guide_d_), want_mixed ? guide_mix_ : nullptr, guide_d_ + GUIDE_PICK,
+    if (!launch_guide_rows(logits_, V, V, n, guide_d_.as<const GuidePair>(), want_mixed ? guide_mix_ : nullptr, guide_d_ + GUIDE_PICK,
                            reinterpret_cast<float *>(guide_d_ + GUIDE_VAL), n_hand ? d_btok_ : nullptr, stream_)) return refuse(last_error());
     guide_info_.launches++; guide_info_.handed += n_hand; guide_info_.pen_picked += m_pen; guide_info_.sampled += greedy ? 0 : n;
     HIP_CHECK(hipMemcpyAsync(guide_h_ + GUIDE_PICK, guide_d_ + GUIDE_PICK, (size_t)n * 4, hipMemcpyDeviceToHost, stream_));
@@ -1938,56 +1900,37 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
     auto bad_pick = [] { return HipError{hipErrorUnknown, "end_chat_guided: the device reported an id outside the vocabulary", __FILE__, __LINE__}; };
     if (host_first) {
         if (m_pen) {
-            const size_t head = MAX_CONVERSATIONS * sizeof(PenRow);
-            HIP_CHECK(hipMemcpyAsync(pen_d_, pen_h_, head + pen_off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-            if (!launch_pen_pick(guide_mix_, V, V, m_pen, reinterpret_cast<const PenRow *>(pen_d_), reinterpret_cast<const PenEntry *>(pen_d_ + head), pen_out_d_, nullptr, stream_))
-                return refuse(last_error());
-            HIP_CHECK(hipMemcpyAsync(pen_out_h_, pen_out_d_, (size_t)m_pen * 4, hipMemcpyDeviceToHost, stream_));
+            if (!pen_launch(guide_mix_, m_pen, pen_off)) return refuse(last_error());
             pen_info_.launches++; pen_info_.last_entries = (int)pen_off;
         }
         if (!greedy) { guide_rows_.resize((size_t)n * V); HIP_CHECK(hipMemcpyAsync(guide_rows_.data(), guide_mix_, (size_t)n * V * 4, hipMemcpyDeviceToHost, stream_)); }
         HIP_CHECK(hipStreamSynchronize(stream_));
         if (!take_picks()) throw bad_pick();                                 // nothing has been launched for these picks yet
-        for (int r = 0; r < m_pen; r++) {
-            if (pen_out_h_[r] < 0 || pen_out_h_[r] >= V) throw HipError{hipErrorUnknown, "the penalised pick reported an id outside the vocabulary", __FILE__, __LINE__};
-            ids_out[pen_map[r]] = pen_out_h_[r];
-        }
+        pen_collect(m_pen, pen_map, ids_out);
         if (!greedy) for (int i = 0; i < n; i++) {                           // one draw per pair, in list order
             const Conversation &cv = conv_[(size_t)pos[i]];
-            const std::vector<int> &h = hist_before[(size_t)i].empty() ? cv.hist : hist_before[(size_t)i];
             float *row = guide_rows_.data() + (size_t)i * V;
-            if ((pen_mode_ || !cv.bias_id.empty()) &&
-                penalise_row(row, V, h.data(), h.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size())) pen_info_.host_rows++;
+            pen_host_row(cv, hist_before[(size_t)i].empty() ? cv.hist : hist_before[(size_t)i], row);
             ids_out[i] = sampler_.sample(row, V, p);
         }
-        for (int i = 0; i < n; i++) if (row_of[i] >= host_row0) h_bstage_[row_of[i]] = h_bstage_[row_of[i] + 1] = ids_out[i];
+        for (int i = 0; i < n; i++) if (row_of[i] >= host_row0) staged_token(row_of[i]) = staged_token(row_of[i] + 1) = ids_out[i];
     }
     if (!B) { if (!host_first) { HIP_CHECK(hipEventSynchronize(guide_ev_)); if (!take_picks()) throw bad_pick(); } return 0; }
     // 5. the weight pass: the batched step's own (parity mode: one oracle-order single-row pass per conversation, decode_batch's fallback)
     if (parity_) {
-        for (int r = 0; r < B; r++) { cur_ = h_bstage_[MAX_CONVERSATIONS + r]; const int id = h_bstage_[r]; if (eval_chunk(&id, 1, nullptr)) return 1; conv_[(size_t)cur_].n_past += 1; }
+        if (step_parity(B)) return 1;
         HIP_CHECK(hipStreamSynchronize(stream_));
         return 0;
     }
     // the tail the host chose (it synchronised to choose: the slab's copy has drained, h_bstage_ is free again)
-    if (B > host_row0) HIP_CHECK(hipMemcpyAsync(d_btok_ + host_row0, h_bstage_ + host_row0, (size_t)(B - host_row0) * 4, hipMemcpyHostToDevice, stream_));
-    if (use_graph_) {
-        hipGraphExec_t &ge = batch_graph_[(size_t)B];
-        if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_); });
-        HIP_CHECK(hipGraphLaunch(ge, stream_));
-    } else forward_batch(B, stream_);
+    if (B > host_row0) HIP_CHECK(hipMemcpyAsync(d_btok_ + host_row0, &staged_token(host_row0), (size_t)(B - host_row0) * 4, hipMemcpyHostToDevice, stream_));
+    step_launch(B);
     // the pass is still running.  It has advanced the device state whatever the block says: the host's book-keeping follows it before a bad block is reported
     bool sane = true;
     if (!host_first) { HIP_CHECK(hipEventSynchronize(guide_ev_)); sane = take_picks(); }
     for (int i = 0; i < n; i++) {
         if (!adv[i]) continue;
-        for (int k = 0; k < 2; k++) {
-            const int sl = k ? neg[i] : pos[i];
-            Conversation &cv = conv_[(size_t)sl];
-            cv.n_past += 1; cv.n_committed += 1; cv.has_logits = true;
-            cv.hist.push_back(ids_out[i]);
-            if (logits_host_slot_ == sl) logits_host_slot_ = -1;
-        }
+        for (int k = 0; k < 2; k++) commit_rows(k ? neg[i] : pos[i], &ids_out[i], 1, /*past=*/true);
     }
     HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
     if (!sane) throw bad_pick();
@@ -1997,21 +1940,40 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
 // ---- penalties and logit bias (engine.hpp, penalty.hpp) ----
 void Engine::pen_alloc() {
     if (pen_d_) return;
-    const size_t bytes = (size_t)MAX_CONVERSATIONS * (sizeof(PenRow) + (size_t)PEN_TABLE_MAX * sizeof(PenEntry));
-    try {
-        HIP_CHECK(hipMalloc((void **)&pen_d_, bytes)); HIP_CHECK(hipHostMalloc((void **)&pen_h_, bytes, hipHostMallocDefault));
-        HIP_CHECK(hipMalloc((void **)&pen_out_d_, MAX_CONVERSATIONS * 4)); HIP_CHECK(hipHostMalloc((void **)&pen_out_h_, MAX_CONVERSATIONS * 4, hipHostMallocDefault));
-    } catch (...) { pen_free(); throw; }
-}
-void Engine::pen_free() {
-    if (pen_d_) HIP_IGNORE(hipFree(pen_d_));
-    if (pen_out_d_) HIP_IGNORE(hipFree(pen_out_d_));
-    if (pen_h_) HIP_IGNORE(hipHostFree(pen_h_));
-    if (pen_out_h_) HIP_IGNORE(hipHostFree(pen_out_h_));
-    pen_d_ = pen_h_ = nullptr; pen_out_d_ = pen_out_h_ = nullptr;
+    const size_t bytes = PEN_HEAD + (size_t)MAX_CONVERSATIONS * PEN_TABLE_MAX * sizeof(PenEntry);
+    DevPtr<uint8_t> d(bytes); PinPtr<uint8_t> h(bytes); DevPtr<int> out_d(MAX_CONVERSATIONS * 4); PinPtr<int> out_h(MAX_CONVERSATIONS * 4);   // all four or none
+    pen_d_ = std::move(d); pen_h_ = std::move(h); pen_out_d_ = std::move(out_d); pen_out_h_ = std::move(out_h);
 }
 int Engine::pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const {
     return pen_build_table(cv.hist.data(), cv.hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, (int)llm_.n_vocab, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size(), tab);
+}
+bool Engine::pen_build_row(const Conversation &cv, int row, size_t off, PenRow *out, std::vector<PenEntry> &tab) const {
+    const int flags = pen_table(cv, tab);
+    const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
+    *out = PenRow{row, (int)off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0};
+    return flags || !tab.empty();
+}
+bool Engine::pen_stage_row(const Conversation &cv, int row, int m, size_t &off, std::vector<PenEntry> &tab) {
+    PenRow r;
+    if (!pen_build_row(cv, row, off, &r, tab)) return false;
+    pen_alloc();
+    pen_h_.as<PenRow>()[m] = r;
+    std::copy(tab.begin(), tab.end(), reinterpret_cast<PenEntry *>(pen_h_ + PEN_HEAD) + off);
+    off += tab.size();
+    return true;
+}
+bool Engine::pen_launch(const float *logits, int m, size_t n_ent) {
+    const int V = (int)llm_.n_vocab;
+    HIP_CHECK(hipMemcpyAsync(pen_d_, pen_h_, PEN_HEAD + n_ent * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
+    if (!launch_pen_pick(logits, V, V, m, pen_d_.as<const PenRow>(), reinterpret_cast<const PenEntry *>(pen_d_ + PEN_HEAD), pen_out_d_, nullptr, stream_)) return false;
+    HIP_CHECK(hipMemcpyAsync(pen_out_h_, pen_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
+    return true;
+}
+void Engine::pen_collect(int m, const int *map, int *ids) const {
+    for (int r = 0; r < m; r++) {
+        if (pen_out_h_[r] < 0 || pen_out_h_[r] >= (int)llm_.n_vocab) throw HipError{hipErrorUnknown, "the penalised pick reported an id outside the vocabulary", __FILE__, __LINE__};
+        ids[map[r]] = pen_out_h_[r];
+    }
 }
 // The caller has evaluated every listed conversation's queue and synchronised (greedy_raw): hist is the whole history, the pinned staging is free.
 void Engine::pen_pick(const int *slots, int n, int *ids, bool skip_constrained) {
@@ -2020,30 +1982,15 @@ void Engine::pen_pick(const int *slots, int n, int *ids, bool skip_constrained) 
     if (!any) return;                                                        // mode off, no bias: today's path
     std::vector<PenEntry> tab;
     int m = 0, map[MAX_CONVERSATIONS]; size_t off = 0;
-    PenRow *rows = nullptr; PenEntry *ent = nullptr;
     for (int i = 0; i < n; i++) {
         const Conversation &cv = conv_[(size_t)slots[i]];
         if (!cv.has_logits || (skip_constrained && con_handle_[slots[i]])) continue;   // (a constrained conversation: k_constrain_pick applies its table)
-        const int flags = pen_table(cv, tab);
-        if (!flags && tab.empty()) continue;                                 // the identity: the raw greedy id stands
-        if (!rows) { pen_alloc(); rows = reinterpret_cast<PenRow *>(pen_h_); ent = reinterpret_cast<PenEntry *>(pen_h_ + MAX_CONVERSATIONS * sizeof(PenRow)); }
-        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
-        rows[m] = PenRow{slots[i], (int)off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0};
-        std::copy(tab.begin(), tab.end(), ent + off);
-        off += tab.size(); map[m++] = i;
+        if (pen_stage_row(cv, slots[i], m, off, tab)) map[m++] = i;          // (the identity: the raw greedy id stands)
     }
     if (!m) return;
-    const size_t head = MAX_CONVERSATIONS * sizeof(PenRow);
-    HIP_CHECK(hipMemcpyAsync(pen_d_, pen_h_, head + off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-    const int V = (int)llm_.n_vocab;
-    if (!launch_pen_pick(logits_, V, V, m, reinterpret_cast<const PenRow *>(pen_d_), reinterpret_cast<const PenEntry *>(pen_d_ + head), pen_out_d_, nullptr, stream_))
-        throw HipError{hipErrorInvalidValue, "penalised pick launch refused", __FILE__, __LINE__};
-    HIP_CHECK(hipMemcpyAsync(pen_out_h_, pen_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
+    if (!pen_launch(logits_, m, off)) throw HipError{hipErrorInvalidValue, "penalised pick launch refused", __FILE__, __LINE__};
     HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int r = 0; r < m; r++) {
-        if (pen_out_h_[r] < 0 || pen_out_h_[r] >= V) throw HipError{hipErrorUnknown, "the penalised pick reported an id outside the vocabulary", __FILE__, __LINE__};
-        ids[map[r]] = pen_out_h_[r];
-    }
+    pen_collect(m, map, ids);
     pen_info_.launches++; pen_info_.last_entries = (int)off;
 }
 int Engine::set_conversation_penalties(int slot, const PenParams &p) {
@@ -2080,24 +2027,13 @@ void Engine::con_alloc() {
     std::vector<unsigned char> blob((size_t)off[V] + 1, 0);
     for (size_t i = 0; i < V && i < llm_.pieces.size(); i++) std::copy(llm_.pieces[i].begin(), llm_.pieces[i].end(), blob.begin() + off[i]);
     const size_t stage = (size_t)MAX_CONVERSATIONS * (sizeof(ConRow) + (size_t)PEN_TABLE_MAX * sizeof(PenEntry));
-    try {
-        HIP_CHECK(hipMalloc((void **)&con_vocab_, blob.size())); HIP_CHECK(hipMalloc((void **)&con_off_, (V + 1) * 4));
-        HIP_CHECK(hipMalloc((void **)&con_d_, stage)); HIP_CHECK(hipHostMalloc((void **)&con_h_, stage, hipHostMallocDefault));
-        HIP_CHECK(hipMalloc((void **)&con_out_d_, MAX_CONVERSATIONS * 4)); HIP_CHECK(hipHostMalloc((void **)&con_out_h_, MAX_CONVERSATIONS * 4, hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void **)&con_row_h_, (size_t)constraint_words((int)V) * 4, hipHostMallocDefault));
-        HIP_CHECK(hipMemcpy(con_vocab_, blob.data(), blob.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(con_off_, off.data(), (V + 1) * 4, hipMemcpyHostToDevice));
-    } catch (...) { con_free(); throw; }
-}
-void Engine::con_free() {
-    for (Constraint &c : con_) { if (c.dev) HIP_IGNORE(hipFree(c.dev)); c = Constraint{}; }
-    if (con_vocab_) HIP_IGNORE(hipFree(con_vocab_));
-    if (con_off_) HIP_IGNORE(hipFree(con_off_));
-    if (con_d_) HIP_IGNORE(hipFree(con_d_));
-    if (con_out_d_) HIP_IGNORE(hipFree(con_out_d_));
-    if (con_h_) HIP_IGNORE(hipHostFree(con_h_));
-    if (con_out_h_) HIP_IGNORE(hipHostFree(con_out_h_));
-    if (con_row_h_) HIP_IGNORE(hipHostFree(con_row_h_));
-    con_vocab_ = nullptr; con_off_ = nullptr; con_d_ = con_h_ = nullptr; con_out_d_ = con_out_h_ = nullptr; con_row_h_ = nullptr;
+    // all seven or none, the uploads included
+    DevPtr<unsigned char> vocab(blob.size()); DevPtr<int> offs((V + 1) * 4);
+    DevPtr<uint8_t> d(stage); PinPtr<uint8_t> h(stage); DevPtr<int> out_d(MAX_CONVERSATIONS * 4); PinPtr<int> out_h(MAX_CONVERSATIONS * 4);
+    PinPtr<unsigned> row_h((size_t)constraint_words((int)V) * 4);
+    HIP_CHECK(hipMemcpy(vocab, blob.data(), blob.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(offs, off.data(), (V + 1) * 4, hipMemcpyHostToDevice));
+    con_vocab_ = std::move(vocab); con_off_ = std::move(offs); con_d_ = std::move(d); con_h_ = std::move(h); con_out_d_ = std::move(out_d); con_out_h_ = std::move(out_h);
+    con_row_h_ = std::move(row_h);
 }
 int Engine::constraint_compile(const unsigned char *pattern, long long n_bytes, int *handle) {
     auto refuse = [](const std::string &what) { set_last_error("constraint_compile: " + what); return 1; };
@@ -2112,17 +2048,16 @@ int Engine::constraint_compile(const unsigned char *pattern, long long n_bytes, 
     con_alloc();
     const int V = (int)llm_.n_vocab, W = constraint_words(V);
     const size_t S = (size_t)dfa.n_states, t_bytes = S * 256 * 2, a_bytes = (dfa.accept.size() * 4 + 15) & ~(size_t)15, i_bytes = S * (size_t)W * 4;
-    uint8_t *dev = nullptr;
-    HIP_CHECK(hipMalloc((void **)&dev, t_bytes + a_bytes + i_bytes));
+    DevPtr<uint8_t> dev(t_bytes + a_bytes + i_bytes);
     try {
         HIP_CHECK(hipMemcpyAsync(dev, dfa.trans.data(), t_bytes, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipMemcpyAsync(dev + t_bytes, dfa.accept.data(), dfa.accept.size() * 4, hipMemcpyHostToDevice, stream_));
         unsigned *index = reinterpret_cast<unsigned *>(dev + t_bytes + a_bytes);
-        if (!launch_constrain_index(con_vocab_, con_off_, V, reinterpret_cast<const uint16_t *>(dev), reinterpret_cast<const unsigned *>(dev + t_bytes), dfa.n_states, index, stream_))
+        if (!launch_constrain_index(con_vocab_, con_off_, V, dev.as<const uint16_t>(), reinterpret_cast<const unsigned *>(dev + t_bytes), dfa.n_states, index, stream_))
             throw HipError{hipErrorInvalidValue, "constraint index launch refused", __FILE__, __LINE__};
         HIP_CHECK(hipStreamSynchronize(stream_));                            // the host vectors above go out of scope; the index is complete when the call returns
-        con_[h].used = true; con_[h].dfa = std::move(dfa); con_[h].dev = dev; con_[h].index = index;
-    } catch (...) { HIP_IGNORE(hipStreamSynchronize(stream_)); HIP_IGNORE(hipFree(dev)); throw; }
+        con_[h].used = true; con_[h].dfa = std::move(dfa); con_[h].dev = std::move(dev); con_[h].index = index;
+    } catch (...) { HIP_IGNORE(hipStreamSynchronize(stream_)); throw; }          // (dev is freed behind this: nothing queued reads it any more)
     con_info_.index_launches++;
     *handle = h + 1;
     return 0;
@@ -2132,7 +2067,6 @@ int Engine::constraint_free(int handle) {
     if (handle < 1 || handle > CONSTRAINT_SLOTS || !con_[handle - 1].used) return refuse("no such constraint");
     for (size_t i = 0; i < conv_.size(); i++) if (con_handle_[i] == handle) return refuse("a conversation uses this constraint");
     HIP_CHECK(hipStreamSynchronize(stream_));
-    HIP_IGNORE(hipFree(con_[handle - 1].dev));
     con_[handle - 1] = Constraint{};
     return 0;
 }
@@ -2193,23 +2127,21 @@ void Engine::con_pick(const int *slots, int n, int *ids) {
     if (!con_assigned_) return;                                              // no conversation of this context holds a constraint: today's path
     std::vector<PenEntry> tab;
     int m = 0, map[MAX_CONVERSATIONS]; size_t off = 0;
-    ConRow *rows = reinterpret_cast<ConRow *>(con_h_); PenEntry *ent = reinterpret_cast<PenEntry *>(con_h_ + MAX_CONVERSATIONS * sizeof(ConRow));
+    ConRow *rows = con_h_.as<ConRow>(); PenEntry *ent = reinterpret_cast<PenEntry *>(con_h_ + MAX_CONVERSATIONS * sizeof(ConRow));
     const int V = (int)llm_.n_vocab, W = constraint_words(V);
     for (int i = 0; i < n; i++) {
         const int slot = slots[i], h = con_handle_[slot];
         const Conversation &cv = conv_[(size_t)slot];
         if (!h || !cv.has_logits) continue;
-        int flags = 0; tab.clear();
-        if (pen_mode_ || !cv.bias_id.empty()) flags = pen_table(cv, tab);
-        const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
-        rows[m] = ConRow{PenRow{slot, (int)off, (int)tab.size(), flags, pp.repeat_penalty, pp.alpha_frequency, pp.alpha_presence, 0}, con_[h - 1].index + (size_t)con_state_[slot] * W, 0ull};
+        pen_build_row(cv, slot, off, &rows[m].pen, tab);                     // the identity included: the constraint applies whatever the table holds
+        rows[m].allowed = con_[h - 1].index + (size_t)con_state_[slot] * W; rows[m].pad = 0ull;
         std::copy(tab.begin(), tab.end(), ent + off);
         off += tab.size(); map[m++] = i;
     }
     if (!m) return;
     const size_t head = MAX_CONVERSATIONS * sizeof(ConRow);
     HIP_CHECK(hipMemcpyAsync(con_d_, con_h_, head + off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-    if (!launch_constrain_pick(logits_, V, V, m, reinterpret_cast<const ConRow *>(con_d_), reinterpret_cast<const PenEntry *>(con_d_ + head), con_out_d_, stream_))
+    if (!launch_constrain_pick(logits_, V, V, m, con_d_.as<const ConRow>(), reinterpret_cast<const PenEntry *>(con_d_ + head), con_out_d_, stream_))
         throw HipError{hipErrorInvalidValue, "constrained pick launch refused", __FILE__, __LINE__};
     HIP_CHECK(hipMemcpyAsync(con_out_h_, con_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
     HIP_CHECK(hipStreamSynchronize(stream_));
@@ -2231,13 +2163,7 @@ int Engine::token_history(int *out, int cap) {
 
 // ---- speculation: draft tokens verified in one weight pass (engine.hpp) ----
 void Engine::spec_drop_graphs() { for (hipGraphExec_t &g : spec_graph_) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; } }
-void Engine::spec_free() {
-    spec_drop_graphs();
-    if (spec_logits_) HIP_IGNORE(hipFree(spec_logits_));
-    if (spec_res_) HIP_IGNORE(hipFree(spec_res_));
-    if (spec_hres_) HIP_IGNORE(hipHostFree(spec_hres_));
-    spec_logits_ = nullptr; spec_res_ = nullptr; spec_hres_ = nullptr; spec_max_ = 0;
-}
+void Engine::spec_free() { spec_drop_graphs(); reset_all(spec_logits_, spec_res_, spec_hres_); spec_max_ = 0; }
 int Engine::set_speculation(int max_draft) {
     if (max_draft < 0 || max_draft > DRAFT_MAX) { set_last_error("set_speculation: max_draft must be 0 (off) ... " + std::to_string(DRAFT_MAX)); return 1; }
     // the verify pass keeps DRAFT_ROWS new key / value rows next to the score rows in the attention kernel's LDS: a context the one-row form holds may not fit it
@@ -2248,11 +2174,8 @@ int Engine::set_speculation(int max_draft) {
     HIP_CHECK(hipStreamSynchronize(stream_));
     spec_free();
     if (max_draft == 0) return 0;
-    try {
-        HIP_CHECK(hipMalloc((void **)&spec_logits_, (size_t)(max_draft + 1) * llm_.n_vocab * 4));
-        HIP_CHECK(hipMalloc((void **)&spec_res_, (1 + DRAFT_ROWS) * 4));
-        HIP_CHECK(hipHostMalloc((void **)&spec_hres_, (1 + DRAFT_ROWS) * 4, hipHostMallocDefault));
-    } catch (...) { spec_free(); throw; }
+    DevPtr<float> logits((size_t)(max_draft + 1) * llm_.n_vocab * 4); DevPtr<int> res((1 + DRAFT_ROWS) * 4); PinPtr<int> hres((1 + DRAFT_ROWS) * 4);   // all three or none
+    spec_logits_ = std::move(logits); spec_res_ = std::move(res); spec_hres_ = std::move(hres);
     spec_graph_.assign((size_t)DRAFT_ROWS + 1, nullptr);
     spec_max_ = max_draft;
     return 0;
@@ -2287,24 +2210,16 @@ int Engine::verify_draft(const int *draft, int n_draft, int *ids_out, int *n_out
             if (r + 1 < R && draft[r] == g) m++; else break;
         }
     } else {
-        h_bstage_[0] = g0; for (int r = 1; r < R; r++) h_bstage_[r] = draft[r - 1];
-        h_bstage_[MAX_CONVERSATIONS] = cur_; h_bstage_[2 * MAX_CONVERSATIONS] = p;
-        HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, 768, hipMemcpyHostToDevice, stream_));
-        launch_draft_begin(d_npast_, d_bslot_, d_bpos_, stream_);
-        if (use_graph_) {   // one graph per row count: token ids, conversation and position live in device memory
-            hipGraphExec_t &ge = spec_graph_[(size_t)R];
-            if (!ge) capture_graph(ge, [&] { forward_batch(R, stream_, true); });
-            HIP_CHECK(hipGraphLaunch(ge, stream_));
-        } else forward_batch(R, stream_, true);
+        stage_row(0, g0, cur_, p); for (int r = 1; r < R; r++) staged_token(r) = draft[r - 1];   // k_draft_begin spreads row 0's conversation and position
+        step_begin(R, /*verify=*/true);
+        step_launch(R, /*verify=*/true);
         HIP_CHECK(hipMemcpyAsync(spec_hres_, spec_res_, (size_t)(1 + R) * 4, hipMemcpyDeviceToHost, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));                            // the one wait of the call: m and the rows' greedy ids
         m = spec_hres_[0];
         if (m < 0 || m >= R) throw HipError{hipErrorUnknown, "verify_draft: the device reported an accepted count outside the pass", __FILE__, __LINE__};
         if (row_greedy) for (int r = 0; r < R; r++) row_greedy[r] = spec_hres_[1 + r];
         h_argmax_[cur_] = spec_hres_[1 + m];
-        cv.n_committed = p + 1 + m; cv.n_past = cv.n_committed; cv.has_logits = true;
-        cv.hist.push_back(g0); cv.hist.insert(cv.hist.end(), draft, draft + m);   // the kept rows only
-        if (logits_host_slot_ == cur_) logits_host_slot_ = -1;
+        commit_rows(cur_, &staged_token(0), 1 + m, /*past=*/true);              // the kept rows only: g0, draft[0 .. m) (the call has synchronised: the slab is whole)
     }
     ids_out[0] = g0; for (int i = 0; i < m; i++) ids_out[1 + i] = draft[i];
     *n_out = 1 + m;
@@ -2449,6 +2364,7 @@ int Engine::prefill_packed(const int *slots, int n, const ScoreOut *so) {
         for (int i = 0; i < sc.n_seg; i++) {
             const int *g = sc.h_segs + 4 * i;
             Conversation &cv = conv_[(size_t)g[0]];
+            // (not commit_rows: a segment that continues in the next chunk has no logits row yet -- has_logits waits for the last chunk, below)
             cv.n_committed += g[2]; cv.hist.insert(cv.hist.end(), tok.begin() + g[1], tok.begin() + g[1] + g[2]);
         }
     }
@@ -2465,13 +2381,9 @@ void Engine::score_alloc() {
     const int need = max_rows_ + MAX_CONVERSATIONS;
     if (score_buf_ && score_cap_ >= need) return;
     HIP_CHECK(hipStreamSynchronize(stream_));
-    score_free();
-    const size_t V = llm_.n_vocab;
-    try {
-        HIP_CHECK(hipMalloc((void **)&score_buf_, (size_t)SCORE_ROWS * V * 4));
-        HIP_CHECK(hipMalloc((void **)&score_tgt_, (size_t)need * 4)); HIP_CHECK(hipMalloc((void **)&score_greedy_, (size_t)need * 4));
-        HIP_CHECK(hipMalloc((void **)&score_lp_, (size_t)need * 4)); HIP_CHECK(hipMalloc((void **)&score_glp_, (size_t)need * 4));
-    } catch (...) { score_free(); throw; }
+    reset_all(score_buf_, score_tgt_, score_greedy_, score_lp_, score_glp_); score_cap_ = 0;
+    DevPtr<float> buf((size_t)SCORE_ROWS * llm_.n_vocab * 4), lp((size_t)need * 4), glp((size_t)need * 4); DevPtr<int> tgt((size_t)need * 4), greedy((size_t)need * 4);   // all five or none
+    score_buf_ = std::move(buf); score_tgt_ = std::move(tgt); score_greedy_ = std::move(greedy); score_lp_ = std::move(lp); score_glp_ = std::move(glp);
     score_cap_ = need;
 }
 Engine::ScoreReq Engine::score_request(const std::vector<int> &targets, int top_n, float *h_logits) {
@@ -2484,10 +2396,6 @@ Engine::ScoreReq Engine::score_request(const std::vector<int> &targets, int top_
     rq.targets = score_tgt_; rq.logprob = score_lp_; rq.greedy = score_greedy_; rq.greedy_logprob = score_glp_;
     rq.h_logits = h_logits; rq.top_n = top_n;
     return rq;
-}
-void Engine::score_free() {
-    for (void *p : {(void *)score_buf_, (void *)score_tgt_, (void *)score_greedy_, (void *)score_lp_, (void *)score_glp_}) if (p) HIP_IGNORE(hipFree(p));
-    score_buf_ = score_lp_ = score_glp_ = nullptr; score_tgt_ = score_greedy_ = nullptr; score_cap_ = 0;
 }
 // The scored rows of the pass that is being enqueued: x_ holds every row's residual once the layers are done.  Tiles of SCORE_ROWS rows: final norm + output matrix
 // into score_buf_ (parity mode: the oracle-order preparation and mat-mul, as forward_ref's prompt rows), k_logprob_rows, the optional copy of the tile to the host.
@@ -2596,22 +2504,11 @@ void Engine::topn_alloc() {
     score_alloc();
     if (topn_d_ && topn_cap_ >= score_cap_) return;
     HIP_CHECK(hipStreamSynchronize(stream_));
-    topn_free();
+    reset_all(topn_d_, topn_h_, topn_in_, topn_hin_, topn_ev_); topn_cap_ = 0; topn_m_ = 0;
     const size_t words = (size_t)score_cap_ * (2 * TOPN_MAX + 2);
-    try {
-        HIP_CHECK(hipMalloc((void **)&topn_d_, words * 4)); HIP_CHECK(hipHostMalloc((void **)&topn_h_, words * 4, hipHostMallocDefault));
-        HIP_CHECK(hipMalloc((void **)&topn_in_, 2 * MAX_CONVERSATIONS * 4)); HIP_CHECK(hipHostMalloc((void **)&topn_hin_, 2 * MAX_CONVERSATIONS * 4, hipHostMallocDefault));
-        HIP_CHECK(hipEventCreateWithFlags(&topn_ev_, hipEventDisableTiming));
-    } catch (...) { topn_free(); throw; }
+    DevPtr<int> d(words * 4), in(2 * MAX_CONVERSATIONS * 4); PinPtr<int> h(words * 4), hin(2 * MAX_CONVERSATIONS * 4); OwnedEvent ev(0);   // all five or none
+    topn_d_ = std::move(d); topn_h_ = std::move(h); topn_in_ = std::move(in); topn_hin_ = std::move(hin); topn_ev_ = std::move(ev);
     topn_cap_ = score_cap_;
-}
-void Engine::topn_free() {
-    if (topn_d_) HIP_IGNORE(hipFree(topn_d_));
-    if (topn_in_) HIP_IGNORE(hipFree(topn_in_));
-    if (topn_h_) HIP_IGNORE(hipHostFree(topn_h_));
-    if (topn_hin_) HIP_IGNORE(hipHostFree(topn_hin_));
-    if (topn_ev_) HIP_IGNORE(hipEventDestroy(topn_ev_));
-    topn_d_ = topn_h_ = topn_in_ = topn_hin_ = nullptr; topn_ev_ = nullptr; topn_cap_ = 0; topn_m_ = 0;
 }
 // One launch over the logits_ rows of the listed conversations that hold logits (targets: one per listed conversation, -1 = none), the packed results' copy to the
 // pinned mirror and the event behind it.  The caller has synchronised the stream since the previous slot call's collect (the pinned inputs are free).

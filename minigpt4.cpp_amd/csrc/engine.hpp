@@ -9,6 +9,7 @@
 #include "common.hpp"
 #include "formats.hpp"
 #include "kernels.hpp"
+#include "owned.hpp"
 #include "sampler.hpp"
 
 namespace mg4 {
@@ -213,8 +214,8 @@ public:
     GuideInfo guidance_info() const { return guide_info_; }
     // ---- repetition / frequency / presence penalties and a logit bias (penalty.hpp: llama.cpp's arithmetic, one definition for host and device).  Off by default
     // (the reference ignores the arguments); minigpt4_amd.h states the rules.  Every conversation keeps a ROW-ALIGNED token history -- entry r = the token id of cache
-    // row r, -1 for an embedding row -- that every path which advances or moves rows keeps in step (invariant: hist.size() == n_committed; the queued rows follow it
-    // in pend_tok), its five parameters (neutral by default; they count only while the mode is on) and its bias (counts whatever the mode).  sample_token and
+    // row r, -1 for an embedding row -- that every path which advances or moves rows keeps in step (commit_rows states the invariant; the queued rows
+    // follow in pend_tok), its five parameters (neutral by default; they count only while the mode is on) and its bias (counts whatever the mode).  sample_token and
     // decode_batch apply them: temp <= 0 through ONE k_pen_pick launch over the listed conversations whose transformation is not the identity (tables built on the
     // host, one upload, one small copy back, one synchronise; logits_, d_argmax_, d_feed_ and the graphs untouched), temp > 0 on a host copy of the row before the
     // chain.  verify_draft, decode_lookup and decode_loop decide on raw logits.  The buffers are allocated at the first launch.
@@ -260,22 +261,33 @@ private:
     void alloc_buffers();
     void forward_batch(int B, hipStream_t s, bool verify = false);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation
     // speculation's own allocations (set_speculation; freed with the context): [1 + spec_max_][n_vocab] row logits, {m, greedy id per row} and its pinned mirror, [R] graphs
-    int spec_max_ = 0; float *spec_logits_ = nullptr; int *spec_res_ = nullptr, *spec_hres_ = nullptr; std::vector<hipGraphExec_t> spec_graph_;
+    int spec_max_ = 0; DevPtr<float> spec_logits_; DevPtr<int> spec_res_; PinPtr<int> spec_hres_; std::vector<hipGraphExec_t> spec_graph_;
     // penalties: [MAX_CONVERSATIONS] PenRow then the tables, device and pinned (one upload per launch); the picked ids and their pinned mirror
     bool pen_mode_ = false; PenInfo pen_info_;
-    uint8_t *pen_d_ = nullptr, *pen_h_ = nullptr; int *pen_out_d_ = nullptr, *pen_out_h_ = nullptr;
+    DevPtr<uint8_t> pen_d_; PinPtr<uint8_t> pen_h_; DevPtr<int> pen_out_d_; PinPtr<int> pen_out_h_;
     std::vector<float> pen_row_;                                           // the host path's scratch copy of the row (h_logits_ stays raw)
     void pen_alloc();
-    void pen_free();
     // beam search's own lazy allocation: device words [slots 8 | targets 8 | ids 128 | logprobs 128 | rank 8 | target logprob 8 | scores 8 | BeamStep], its pinned mirror
     // (staging of the uploads, the landing place of the result block), the saved logits row + greedy / feed token of the source, the event the result block is awaited on
-    int *beam_d_ = nullptr, *beam_h_ = nullptr; float *beam_save_ = nullptr; hipEvent_t beam_ev_ = nullptr;
+    DevPtr<int> beam_d_; PinPtr<int> beam_h_; DevPtr<float> beam_save_; OwnedEvent beam_ev_;
     static constexpr int BEAM_IDS = 16, BEAM_LP = BEAM_IDS + BEAM_MAX * BEAM_CAND_MAX, BEAM_RANK = BEAM_LP + BEAM_MAX * BEAM_CAND_MAX, BEAM_TLP = BEAM_RANK + 8, BEAM_S = BEAM_TLP + 8,
                          BEAM_RES = BEAM_S + 8, BEAM_WORDS = BEAM_RES + (int)(sizeof(BeamStep) / 4);
     void beam_alloc();
-    void beam_free();
+    void beam_free() { reset_all(beam_d_, beam_h_, beam_save_, beam_ev_); }
     struct Conversation;
     int pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const;   // the conversation's table for its history as a sample sees it; the flags
+    // THE row builder of the device picks: cv's bias and penalties over its history as the PenRow of logits row `row` (-> *out, whose entries are to start at entry
+    // `off`) and its entries (-> tab).  false: the transformation is the identity (no flags, no entries); *out describes that too, for con_pick, which launches such rows
+    bool pen_build_row(const Conversation &cv, int row, size_t off, PenRow *out, std::vector<PenEntry> &tab) const;
+    // ... built into row m of the penalised pick's own pinned staging (allocated by the first row that is not the identity), entries at the running offset `off`
+    bool pen_stage_row(const Conversation &cv, int row, int m, size_t &off, std::vector<PenEntry> &tab);
+    static constexpr size_t PEN_HEAD = MAX_CONVERSATIONS * sizeof(PenRow);   // pen_h_ / pen_d_: [MAX_CONVERSATIONS] PenRow, the tables behind them
+    // m staged rows with n_ent entries: the upload, k_pen_pick over rows of `logits`, the ids' copy back queued.  false: the launch was refused (last_error).  Once
+    // the caller has synchronised, pen_collect checks the ids and scatters them: ids[map[r]] <- row r's pick
+    bool pen_launch(const float *logits, int m, size_t n_ent);
+    void pen_collect(int m, const int *map, int *ids) const;
+    // THE host chain's bias and penalties (temp > 0), in place on a copy of cv's logits row: bias, then penalties over `hist`; a constraint's mask comes after it
+    void pen_host_row(const Conversation &cv, const std::vector<int> &hist, float *row);
     // ids[i] <- the penalised pick of every listed conversation whose transformation is not the identity (skip_constrained: and that holds no constraint -- con_pick serves it)
     void pen_pick(const int *slots, int n, int *ids, bool skip_constrained = true);
     int greedy_raw();                                                      // sample_token at temp 0 without penalties or bias
@@ -312,9 +324,8 @@ private:
     void drop_queues(const int *slots, int n) { for (int i = 0; i < n; i++) conv_[(size_t)slots[i]].drop_queue(); }
     // the feature's own lazy allocation (first scoring call; freed with the context): [SCORE_ROWS][n_vocab] logits, and [score_cap_] targets / results -- one per chunk
     // row, then one per conversation for entry 0
-    float *score_buf_ = nullptr, *score_lp_ = nullptr, *score_glp_ = nullptr; int *score_tgt_ = nullptr, *score_greedy_ = nullptr; int score_cap_ = 0;
+    DevPtr<float> score_buf_, score_lp_, score_glp_; DevPtr<int> score_tgt_, score_greedy_; int score_cap_ = 0;
     void score_alloc();
-    void score_free();
     void score_rows(const ScoreReq &rq, hipStream_t s);
     void score_entry0(int slot, int idx, int target, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top = nullptr);
     int score_tokens_impl(const char *name, const int *tokens, int n, float *logprob, int *greedy, float *greedy_logprob, float *logits_out, const TopOut *top);
@@ -322,14 +333,13 @@ private:
     // pinned mirror, the slot calls' inputs (row index, target per listed conversation) and the event their copy back is awaited on.  Score passes lay the block out
     // as ids [cap][top_n] | log-probabilities at cap * TOPN_MAX | rank at 2 cap TOPN_MAX | target log-probability behind it; the slot calls pack m rows' ids,
     // log-probabilities, ranks and target log-probabilities back to back from word 0, so that one copy fetches them
-    int *topn_d_ = nullptr, *topn_h_ = nullptr, *topn_in_ = nullptr, *topn_hin_ = nullptr; int topn_cap_ = 0; hipEvent_t topn_ev_ = nullptr;
+    DevPtr<int> topn_d_; PinPtr<int> topn_h_; DevPtr<int> topn_in_; PinPtr<int> topn_hin_; int topn_cap_ = 0; OwnedEvent topn_ev_;
     int topn_map_[MAX_CONVERSATIONS], topn_m_ = 0;                        // the launched rows of the slot call in flight: [row] -> index in the slot list
     int *topn_ids() const { return topn_d_; }
     float *topn_lp() const { return reinterpret_cast<float *>(topn_d_ + (size_t)topn_cap_ * TOPN_MAX); }
     int *topn_rank() const { return topn_d_ + 2 * (size_t)topn_cap_ * TOPN_MAX; }
     float *topn_tlp() const { return reinterpret_cast<float *>(topn_rank() + topn_cap_); }
     void topn_alloc();
-    void topn_free();
     void topn_slots_launch(const int *slots, int n, int top_n, const int *targets);
     void topn_slots_collect(int n, int top_n, int *top_ids, float *top_lp, float *logprob, int *rank);
     struct ScoreOut { int off[MAX_CONVERSATIONS]; float *logprob; int *greedy; float *greedy_logprob; };   // score_batch: [slot] -> the conversation's first output entry
@@ -370,7 +380,7 @@ private:
         std::vector<int> pend_tok; std::vector<float> pend_embd;
         hipGraphExec_t graph = nullptr;   // decode step captured with this conversation's cache / position / token addresses
         bool graph_split = false;         // ... with the key-split attention launches (long context) or the one-workgroup-per-head kernel
-        std::vector<int> hist;            // token id of every evaluated row, -1 = embedding row / fed back on the device (size n_committed)
+        std::vector<int> hist;            // token id of every evaluated row, -1 = embedding row / fed back on the device (commit_rows)
         PenParams pen; std::vector<int> bias_id; std::vector<float> bias_val;   // penalties (while the mode is on), logit bias (always)
         bool has_logits = false;          // its logits_ row holds the logits after its last evaluated row (not: nothing evaluated yet, after reset(), after a partial fork)
         void drop_queue() { pend_tok.clear(); pend_embd.clear(); n_past = n_committed; }   // what a failed pass, fork and reset leave: nothing queued
@@ -382,7 +392,7 @@ private:
     int cur_ = 0;
     int shift_keep_ = -1;                  // set_context_shift
     // prefix store: its own allocations (set_conversations re-takes buf_arena_, the store is only emptied then); pfx_ids_.size() = stored rows
-    __half *pfx_k_ = nullptr, *pfx_v_ = nullptr; int pfx_max_ = 0; std::vector<int> pfx_ids_; PrefixInfo pfx_;
+    DevPtr<__half> pfx_k_, pfx_v_; int pfx_max_ = 0; std::vector<int> pfx_ids_; PrefixInfo pfx_;
     void prefix_empty() { pfx_ids_.clear(); }
     void prefix_free();
     static int token_run(const Conversation &cv) { int r = 0; while (r < (int)cv.pend_tok.size() && cv.pend_tok[(size_t)r] >= 0) r++; return r; }
@@ -430,10 +440,28 @@ private:
     // per conversation (indexed by slot): position, greedy token of the last evaluation, next input token; logits_ is [slots][n_vocab]
     int *d_npast_ = nullptr, *d_argmax_ = nullptr, *d_feed_ = nullptr;
     int *d_tokens_ = nullptr; void *d_scratch_ = nullptr;
-    // batched decode: row tokens / conversations / positions (one 768-byte slab), [rows][n_vocab] logits
+    // batched decode: row tokens / conversations / positions (one slab, BSTAGE_BYTES), [rows][n_vocab] logits
     int *d_btok_ = nullptr, *d_bslot_ = nullptr, *d_bpos_ = nullptr; float *blogits_ = nullptr;
-    // [B]: the batched step for B rows (rows are described in device memory, so one graph serves any slot set)
+    // [B]: the batched step for B rows.  The rows are described in device memory, so ONE graph serves every set of B conversations and every entry point that
+    // advances B rows (decode_batch, beam_search, decode_guided): all of them launch it through step_launch and nowhere else
     std::vector<hipGraphExec_t> batch_graph_;
+    // ---- the batched step, issued in one place.  The slab: [tokens | conversations | positions], MAX_CONVERSATIONS ints each (768 bytes), pinned in h_bstage_ and
+    // mirrored by d_btok_ | d_bslot_ | d_bpos_; only these members know the layout.  The caller has synchronised since the slab's last copy was queued.
+    static constexpr size_t BSTAGE_BYTES = 3 * (size_t)MAX_CONVERSATIONS * sizeof(int);
+    void stage_row(int r, int token, int slot, int position) { h_bstage_[r] = token; h_bstage_[MAX_CONVERSATIONS + r] = slot; h_bstage_[2 * MAX_CONVERSATIONS + r] = position; }
+    int &staged_token(int r) { return h_bstage_[r]; }
+    int staged_slot(int r) const { return h_bstage_[MAX_CONVERSATIONS + r]; }
+    // the slab's one copy, then k_batch_begin over B rows (verify: k_draft_begin -- R rows of the one conversation in row 0)
+    void step_begin(int B, bool verify = false);
+    // the weight pass over the staged rows: batch_graph_[B] (verify: spec_graph_[B]) replayed, captured first where it does not exist yet; without graphs, forward_batch
+    void step_launch(int B, bool verify = false);
+    // parity mode's stand-in for step_begin + step_launch: one oracle-order single-row pass per staged row, in row order; cur_ is left on the last row's conversation.
+    // 0, or eval_chunk's failure
+    int step_parity(int B);
+    // THE book-keeping after conversation `slot` had n more rows with these ids evaluated: the history grows by them (invariant: hist.size() == n_committed, the
+    // queued rows follow in pend_tok), its logits_ row is current, the host copy of that row is stale.  past: n_past follows too (a caller that had counted the rows
+    // into n_past when it queued them passes false)
+    void commit_rows(int slot, const int *ids, int n, bool past);
     int *h_argmax_ = nullptr, *h_bstage_ = nullptr; float *h_logits_ = nullptr; int logits_host_slot_ = -1;
     bool use_graph_ = true, use_v2_ = true, attn_prefill_ = true, parity_ = false;
     FILE *trace_file_ = nullptr;       // MINIGPT4_PARITY_TRACE
@@ -529,22 +557,21 @@ private:
     // (behind everything else: the members every other path reads lie where they lay before the feature)
     // guided decoding's own lazy allocation: the mixed rows [GUIDE_MAX][n_vocab]; device words [pair table 8 x 32 | picks 32 | pick values 32] and the pinned mirror (staging of
     // the table, landing place of the picks); the event the picks are awaited on; the host copy of the mixed rows (temp > 0, guided_logits)
-    float *guide_mix_ = nullptr; int *guide_d_ = nullptr, *guide_h_ = nullptr; hipEvent_t guide_ev_ = nullptr; std::vector<float> guide_rows_; GuideInfo guide_info_;
+    DevPtr<float> guide_mix_; DevPtr<int> guide_d_; PinPtr<int> guide_h_; OwnedEvent guide_ev_; std::vector<float> guide_rows_; GuideInfo guide_info_;
     static constexpr int GUIDE_PICK = 8 * GUIDE_MAX, GUIDE_VAL = GUIDE_PICK + GUIDE_MAX, GUIDE_WORDS = GUIDE_VAL + GUIDE_MAX;
     void guide_alloc();
-    void guide_free();
+    void guide_free() { reset_all(guide_mix_, guide_d_, guide_h_, guide_ev_); }
     int guide_prepare(const char *name, const int *pos, const int *neg, int n, float scale, int *all);   // the checks, the queued rows; all[2 i] = pos[i], all[2 i + 1] = neg[i]
     // constrained decoding.  Per compiled constraint: the host DFA, the device table | accepting bitmap | index (one allocation).  Per conversation (arrays here, not in
     // Conversation: that struct keeps its layout): handle and state.  Lazy, first compile: the vocabulary blob + offsets; the pick's staging ([MAX_CONVERSATIONS] ConRow, then
     // the penalty tables: device and pinned), its output words and their pinned mirror, the pinned landing place of one index row (temp > 0, constraint_mask)
-    struct Constraint { bool used = false; ConstraintDfa dfa; uint8_t *dev = nullptr; const unsigned *index = nullptr; };
+    struct Constraint { bool used = false; ConstraintDfa dfa; DevPtr<uint8_t> dev; const unsigned *index = nullptr; };
     Constraint con_[CONSTRAINT_SLOTS];
     int con_handle_[MAX_CONVERSATIONS] = {0}, con_state_[MAX_CONVERSATIONS] = {0}, con_assigned_ = 0;
     struct ConInfo { int launches = 0, host_rows = 0, stuck = 0, index_launches = 0; } con_info_;
-    unsigned char *con_vocab_ = nullptr; int *con_off_ = nullptr;
-    uint8_t *con_d_ = nullptr, *con_h_ = nullptr; int *con_out_d_ = nullptr, *con_out_h_ = nullptr; unsigned *con_row_h_ = nullptr;
+    DevPtr<unsigned char> con_vocab_; DevPtr<int> con_off_;
+    DevPtr<uint8_t> con_d_; PinPtr<uint8_t> con_h_; DevPtr<int> con_out_d_; PinPtr<int> con_out_h_; PinPtr<unsigned> con_row_h_;
     void con_alloc();
-    void con_free();
     void con_walk(int slot, int id);                                       // the state after the picked token (EOS and ids outside the vocabulary leave it)
     void con_pick(const int *slots, int n, int *ids);                      // ids[i] <- the constrained pick of every listed conversation that holds a constraint
     const unsigned *con_fetch_row(int handle, int state);                  // index[state] of that constraint in con_row_h_, synchronised

@@ -46,6 +46,8 @@ static std::vector<unsigned short> host_silu_table() {
     for (int i = 0; i < 65536; i++) { const float v = __half2float(__ushort_as_half((unsigned short)i)); si[(size_t)i] = __half_as_ushort(__float2half_rn(v / (1.0f + expf(-v)))); }
     return si;
 }
+// the timed hooks' event pair (hipEventCreate on a and b; timing enabled), destroyed on every path
+struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } };
 
 extern "C" {
 
@@ -846,7 +848,7 @@ int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, i
         const size_t n = (size_t)rows * ld, R = (size_t)rows;
         DevBuf dl(n * 4), dt(R * 4), dp(R * 4), dg(R * 4), dq(R * 4);
         HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, targets, R * 4, hipMemcpyHostToDevice));
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;   // destroyed on every path
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         launch_logprob_rows(dl.as<float>(), ld, n_vocab, rows, dt.as<int>(), dp.as<float>(), dg.as<int>(), dq.as<float>(), nullptr);
@@ -876,7 +878,7 @@ int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, 
         HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, targets, R * 4, hipMemcpyHostToDevice));
         if (row_index) HIP_CHECK(hipMemcpy(dx.p, row_index, R * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(di.p, 0xFF, RN * 4)); HIP_CHECK(hipMemset(dp.p, 0xFF, RN * 4));   // an entry the kernel leaves out shows as id -1 / NaN
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;   // destroyed on every path
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         if (!launch_topn_rows(dl.as<float>(), ld, n_vocab, rows, row_index ? dx.as<int>() : nullptr, top_n, dt.as<int>(), di.as<int>(), dp.as<float>(), dr.as<int>(), dq.as<float>(), nullptr)) return 3;
@@ -954,7 +956,7 @@ int minigpt4_amd_test_kv_permute(int n_slot, int n_layer, int n_ctx, int n_embd,
         HIP_CHECK(hipMemcpy(dp.p, parent, (size_t)n * 4, hipMemcpyHostToDevice));
         KvPermuteSlots ps{};
         for (int i = 0; i < n; i++) ps.s[i] = slots[i];
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         launch_kv_permute(dk.as<__half>(), dv.as<__half>(), slot_n, n_slot, ps, n, dp.as<int>(), n_layer, n_ctx, n_embd, r0, r1, nullptr);
@@ -1004,7 +1006,7 @@ int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, i
         HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, rows, R * sizeof(PenRow), hipMemcpyHostToDevice));
         if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dp.p, 0xFF, R * 4)); HIP_CHECK(hipMemset(da.p, 0xFF, T * 4));   // what the kernel leaves out shows as id -1 / NaN
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         if (!launch_pen_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<PenRow>(), dt.as<PenEntry>(), dp.as<int>(), da.as<float>(), nullptr)) return 3;
@@ -1046,7 +1048,7 @@ int minigpt4_amd_test_constrain_index(const uint8_t *vocab, const int32_t *off, 
         HIP_CHECK(hipMemcpy(doff.p, off, ((size_t)n_vocab + 1) * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, trans, S * 512, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(da.p, accept, A * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(di.p, 0xA5, S * W * 4));                                           // a word the kernel leaves out shows
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         if (!launch_constrain_index(dv.as<unsigned char>(), doff.as<int>(), n_vocab, dt.as<uint16_t>(), da.as<unsigned>(), n_states, di.as<unsigned>(), nullptr)) return 3;
@@ -1080,7 +1082,7 @@ int minigpt4_amd_test_constrain_pick(const float *logits, int buf_rows, int n_vo
         HIP_CHECK(hipMemcpy(db.p, bitmaps, (size_t)n_bitmaps * W * 4, hipMemcpyHostToDevice));
         if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dp.p, 0xFF, R * 4));                                                // what the kernel leaves out shows as id -1
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         if (!launch_constrain_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<ConRow>(), dt.as<PenEntry>(), dp.as<int>(), nullptr)) return 3;
@@ -1109,7 +1111,7 @@ int minigpt4_amd_test_guide_rows(const float *logits, int buf_rows, int n_vocab,
         HIP_CHECK(hipMemcpy(dl.p, logits, total * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, tab.data(), P * sizeof(GuidePair), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dr.p, row_tok_io, 64 * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dm.p, 0xFF, PV * 4)); HIP_CHECK(hipMemset(dp.p, 0xFF, P * 4)); HIP_CHECK(hipMemset(dv.p, 0xFF, P * 4));   // what the kernel leaves out shows as NaN / id -1
-        struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } } ev;
+        Events ev;
         HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         HIP_CHECK(hipEventRecord(ev.a, nullptr));
         if (!launch_guide_rows(dl.as<float>(), ld, n_vocab, n, dt.as<GuidePair>(), mixed_out ? dm.as<float>() : nullptr, dp.as<int>(), dv.as<float>(), dr.as<int>(), nullptr)) return 3;
