@@ -377,6 +377,53 @@ MINIGPT4_API int minigpt4_amd_constraint_advance(struct MiniGPT4Context *ctx, in
 MINIGPT4_API int minigpt4_amd_constraint_info(struct MiniGPT4Context *ctx, int slot, int32_t out[8]);
 MINIGPT4_API int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32_t handle, int state, uint32_t *out, int n_words);
 
+/* ---- snapshots: save and restore a conversation --------------------------------------------------------------------------------------------------------
+ * A conversation leaves its slot, its context or its process as one blob (llama.cpp's llama_copy_state_data / session files / slot save and restore) and comes back bit
+ * for bit: a restored conversation continues with the logits and tokens of the uninterrupted one.  The cache rows travel through k_kv_pack / k_kv_unpack -- rows
+ * [r0, r0 + n) of every layer, keys and values, to / from one contiguous block per launch, with the block's checksum (the wrapping 64-bit sum of its 32-bit words)
+ * computed in the same sweep.
+ * FORMAT, version 1.  Little-endian; a blob may start at any address.
+ *   header, 64 bytes:  0 magic "MG4S" | 4 u32 version = 1 | 8 u64 total bytes | 16 u32 n_layer | 20 u32 n_embd | 24 u32 n_head | 28 u32 n_vocab | 32 u64 LLM arena hash
+ *     (what minigpt4_amd_arena_plan reports) | 40 u32 n_rows | 44 u32 block_rows | 48 u32 flags (bit 0: has a logits row, bit 1: saved in parity mode) | 52 i32 greedy
+ *     token | 56 i32 feed token | 60 u32 n_bias
+ *   sections, back to back from byte 64:
+ *     token history   n_rows x i32, the token id of every cache row, -1 for an embedding row
+ *     logits row      n_vocab x f32, present only with flag bit 0
+ *     penalties       i32 repeat_last_n, f32 repeat_penalty, f32 alpha_presence, f32 alpha_frequency, i32 penalize_nl
+ *     logit bias      n_bias x (i32 id, f32 bias), n_bias <= 256
+ *     zero padding to a multiple of 8, then the block table: one u64 checksum per block, ceil(n_rows / block_rows) of them
+ *     zero padding to a multiple of 16, then the KV blocks, one per block_rows rows, the last one short: [tensor K, V][layer][row][n_embd] fp16, i.e.
+ *     4 * n_layer * n_embd bytes per row
+ *   block_rows = max(1, block_bytes / bytes per row); block_bytes is 32 MiB unless MINIGPT4_STATE_BLOCK_BYTES (read by minigpt4_model_load) says otherwise.  A loader
+ *   takes block_rows from the blob, whatever its own setting.
+ * NOT in a snapshot: the sampler's generator and the mirostat state (they belong to the context); the constraint handle and state (handles are per context: a load
+ *   keeps the slot's handle and returns its state to the start, like minigpt4_reset_chat); queued rows (a save evaluates them first); the prefix store.
+ * minigpt4_amd_state_size: the bytes a save of `slot` would take now, queued rows counted; 0 for a slot out of range.
+ * minigpt4_amd_state_save: *written (may be NULL) = the size.  cap too small (or buf NULL): 1, *written = the size needed, nothing written, nothing evaluated.
+ * minigpt4_amd_state_load: the header and every host section are checked BEFORE anything on the device or in the conversation changes: magic, version, total bytes ==
+ *   n, section sizes, the model fingerprint (n_layer, n_embd, n_head, n_vocab, arena hash), n_rows <= n_ctx, every history id in [-1, n_vocab), the penalty and bias
+ *   values the setters would accept.  Then whatever the slot held, queued rows included, is dropped, the blocks are uploaded and unpacked, and position, logits row,
+ *   greedy and feed token, history, penalties and bias are installed: minigpt4_end_chat, the batched step, scoring, fork, shift and minigpt4_amd_verify_draft continue
+ *   from there.  The target slot may be any slot of any context loaded from the same language-model file (n_ctx may differ as long as the rows fit).
+ *   A block whose checksum differs from the table ends the call with 1 and "state_load: block c checksum"; the conversation is then left as minigpt4_reset_chat
+ *   leaves it.  This is the ONE failure that is not "nothing changed": its rows were already overwritten.
+ * minigpt4_amd_state_save_file / _load_file: the same through a file; save writes path + ".tmp" and renames it.
+ * minigpt4_amd_state_peek: needs no context and no GPU.  Runs every check that needs no context and reports out = {version, total bytes, n_layer, n_embd, n_head,
+ *   n_vocab, arena hash, n_rows, block_rows, flags, greedy token, feed token}.
+ * minigpt4_amd_state_info: out = {saves, loads, rows saved, rows loaded, k_kv_pack launches, k_kv_unpack launches, checksum failures, bytes of staging held}.  The
+ *   staging -- two device and two pinned blocks, the checksum words, a copy stream -- is allocated by the first save or load, survives
+ *   minigpt4_amd_set_conversations and is freed with the context; a context that never calls these entry points allocates and launches nothing new.
+ * Each call returns 0, or 1 with "<short name>: ..." in minigpt4_amd_last_error.
+ * Not built: incremental snapshots (the kernels take a row range, so only new rows could be appended later), compression or a narrower cache type, constraint state,
+ * snapshots across different weight files. */
+MINIGPT4_API size_t minigpt4_amd_state_size(struct MiniGPT4Context *ctx, int slot);
+MINIGPT4_API int minigpt4_amd_state_save(struct MiniGPT4Context *ctx, int slot, void *buf, size_t cap, size_t *written);
+MINIGPT4_API int minigpt4_amd_state_load(struct MiniGPT4Context *ctx, int slot, const void *buf, size_t n);
+MINIGPT4_API int minigpt4_amd_state_save_file(struct MiniGPT4Context *ctx, int slot, const char *path);
+MINIGPT4_API int minigpt4_amd_state_load_file(struct MiniGPT4Context *ctx, int slot, const char *path);
+MINIGPT4_API int minigpt4_amd_state_peek(const void *buf, size_t n, int64_t out[12]);
+MINIGPT4_API int minigpt4_amd_state_info(struct MiniGPT4Context *ctx, int64_t out[8]);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

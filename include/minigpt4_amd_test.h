@@ -117,6 +117,17 @@ MINIGPT4_API int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, 
  * (a slot out of range, src among dst, only one of k / v NULL), 3 = the launcher refused the shape (text in minigpt4_amd_last_error) */
 MINIGPT4_API int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int src, const int32_t *dst, int n_dst, int n_rows, int src_rows, uint16_t *k, uint16_t *v,
                                            float *ms);
+/* the snapshot kernels alone (launch_kv_pack / launch_kv_unpack) on host fp16 caches k / v = [n_layer][n_ctx][n_embd] of ONE conversation (uint16 bit patterns) and a host
+ * block [tensor K, V][n_layer][n][n_embd].  pack: block_out <- rows [r0, r0 + n), *sum_out <- the checksum the launch accumulated (the wrapping 64-bit sum of the block's
+ * 32-bit words).  unpack: the block is scattered into rows [r0, r0 + n) of k / v IN PLACE, *sum_out <- the checksum of what the launch read.  ms (may be NULL): hipEvent
+ * time of the launcher's work in the stream: the 8-byte hipMemsetAsync that zeroes the checksum word, then the kernel.  k == v == block == NULL: timing only -- device buffers of that shape, filled, never copied to or from the host.  1 = bad arguments (only some of the
+ * arrays NULL, n < 0, n > n_ctx), 3 = the launcher refused the shape (n_embd % 8, r0 < 0, r0 + n > n_ctx; text in
+ * minigpt4_amd_last_error) */
+/* k_checksum alone (device_checksum: the sum of the 32-bit words of [device_ptr, device_ptr + bytes), bytes rounded down to 4, mod 2^64) over any range the device can
+ * read, pinned host memory included.  ms (may be NULL): hipEvent time around the call.  1 = bad arguments (NULL, a pointer that is not 4-byte aligned) */
+MINIGPT4_API int minigpt4_amd_test_checksum(const void *device_ptr, size_t bytes, uint64_t *sum_out, float *ms);
+MINIGPT4_API int minigpt4_amd_test_kv_pack(int n_layer, int n_ctx, int n_embd, int r0, int n, const uint16_t *k, const uint16_t *v, uint16_t *block_out, uint64_t *sum_out, float *ms);
+MINIGPT4_API int minigpt4_amd_test_kv_unpack(int n_layer, int n_ctx, int n_embd, int r0, int n, const uint16_t *block, uint16_t *k, uint16_t *v, uint64_t *sum_out, float *ms);
 /* the scoring kernel (launch_logprob_rows) on host logits [rows][ld] fp32 (ld >= n_vocab; only the first n_vocab floats of a row are read): per row the log-softmax of
  * targets[r] (-1: none, logprob 0), the first argmax and its log-softmax.  One launch; ms (may be NULL): its hipEvent time.  1 = bad arguments, before any device is
  * touched (a NULL pointer, rows < 1, n_vocab < 1, ld < n_vocab, a target >= n_vocab or < -1) */

@@ -434,6 +434,66 @@ int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32_t handle, in
     if (!ctx) { set_last_error("constraint_mask: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->constraint_mask(handle, state, out, n_words); });
 }
+// ---- snapshots: save and restore a conversation ----------------------------------------------------------------------------------------------------
+size_t minigpt4_amd_state_size(struct MiniGPT4Context *ctx, int slot) {
+    if (!ctx) { set_last_error("state_size: no context"); return 0; }
+    size_t n = 0;
+    guarded(1, [&]() -> int { n = E_(ctx)->state_size(slot); return n == 0; });
+    return n;
+}
+int minigpt4_amd_state_save(struct MiniGPT4Context *ctx, int slot, void *buf, size_t cap, size_t *written) {
+    if (written) *written = 0;
+    if (!ctx) { set_last_error("state_save: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->state_save(slot, buf, cap, written); });
+}
+int minigpt4_amd_state_load(struct MiniGPT4Context *ctx, int slot, const void *buf, size_t n) {
+    if (!ctx) { set_last_error("state_load: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->state_load(slot, buf, n); });
+}
+int minigpt4_amd_state_save_file(struct MiniGPT4Context *ctx, int slot, const char *path) {
+    if (!ctx || !path) { set_last_error(ctx ? "state_save_file: no path" : "state_save_file: no context"); return 1; }
+    return guarded(1, [&]() -> int {
+        const size_t need = E_(ctx)->state_size(slot);
+        if (!need) { set_last_error("state_save_file: " + last_error()); return 1; }
+        std::vector<uint8_t> blob(need);
+        size_t written = 0;
+        if (E_(ctx)->state_save(slot, blob.data(), blob.size(), &written)) { set_last_error("state_save_file: " + last_error()); return 1; }
+        const std::string tmp = std::string(path) + ".tmp";
+        FILE *f = fopen(tmp.c_str(), "wb");
+        if (!f) { set_last_error("state_save_file: cannot open " + tmp); return 1; }
+        const bool ok = fwrite(blob.data(), 1, written, f) == written;
+        if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path) != 0) { remove(tmp.c_str()); set_last_error("state_save_file: cannot write " + std::string(path)); return 1; }
+        return 0;
+    });
+}
+int minigpt4_amd_state_load_file(struct MiniGPT4Context *ctx, int slot, const char *path) {
+    if (!ctx || !path) { set_last_error(ctx ? "state_load_file: no path" : "state_load_file: no context"); return 1; }
+    return guarded(1, [&]() -> int {
+        FILE *f = fopen(path, "rb");
+        if (!f) { set_last_error("state_load_file: cannot open " + std::string(path)); return 1; }
+        std::vector<uint8_t> blob;
+        struct stat st;
+        if (fstat(fileno(f), &st) == 0 && st.st_size > 0) blob.resize((size_t)st.st_size);
+        const size_t got = blob.empty() ? 0 : fread(blob.data(), 1, blob.size(), f);
+        fclose(f);
+        if (got != blob.size()) { set_last_error("state_load_file: cannot read " + std::string(path)); return 1; }
+        if (E_(ctx)->state_load(slot, blob.data(), blob.size())) { set_last_error("state_load_file: " + last_error()); return 1; }
+        return 0;
+    });
+}
+int minigpt4_amd_state_peek(const void *buf, size_t n, int64_t out[12]) {
+    if (!out) { set_last_error("state_peek: no output array"); return 1; }
+    char why[256];
+    if (mg4_state_parse(buf, n, out, why, sizeof(why))) { set_last_error(std::string("state_peek: ") + why); return 1; }
+    return 0;
+}
+int minigpt4_amd_state_info(struct MiniGPT4Context *ctx, int64_t out[8]) {
+    if (!ctx || !out) { set_last_error(ctx ? "state_info: no output array" : "state_info: no context"); return 1; }
+    const Engine::StateInfo s = E_(ctx)->state_info();
+    out[0] = s.saves; out[1] = s.loads; out[2] = s.rows_saved; out[3] = s.rows_loaded; out[4] = s.pack_launches; out[5] = s.unpack_launches; out[6] = s.checksum_failures;
+    out[7] = s.staging_bytes;
+    return 0;
+}
 int minigpt4_amd_batch_path(struct MiniGPT4Context *ctx, int32_t out[8]) {
     if (!ctx || !out) return 1;
     const Engine::BatchPath &b = E_(ctx)->batch_path();

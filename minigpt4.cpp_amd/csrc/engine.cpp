@@ -94,7 +94,9 @@ Engine::~Engine() {
         // listed here and nowhere else
         abandon_all(pfx_k_, pfx_v_, score_buf_, score_lp_, score_glp_, score_tgt_, score_greedy_, topn_d_, topn_h_, topn_in_, topn_hin_, topn_ev_,
                     pen_d_, pen_h_, pen_out_d_, pen_out_h_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
-                    guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_d_, con_h_, con_out_d_, con_out_h_, con_row_h_);
+                    guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_d_, con_h_, con_out_d_, con_out_h_, con_row_h_,
+                    state_d_[0], state_d_[1], state_h_[0], state_h_[1], state_sum_d_, state_sum_h_, state_cs_, state_ev_kernel_[0], state_ev_kernel_[1], state_ev_copy_[0],
+                    state_ev_copy_[1]);
         for (Constraint &c : con_) c.dev.abandon();
         return;
     }
@@ -190,6 +192,7 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     if (const char *tf = getenv("MINIGPT4_PARITY_TRACE")) { if (*tf) trace_file_ = fopen(tf, "wb"); }
     // oracle-order fp32 accumulation (forward_ref): bit-identical to the CPU oracle, slow
     parity_ = trace_file_ || (getenv("MINIGPT4_PARITY") && atoi(getenv("MINIGPT4_PARITY")));
+    if (const char *e = getenv("MINIGPT4_STATE_BLOCK_BYTES")) { const long long v = atoll(e); if (v > 0) state_block_bytes_ = (size_t)v; }   // bytes of one snapshot block (default 32 MiB; tests force several blocks on tiny models)
     pen_mode_ = getenv("MINIGPT4_PENALTIES") && atoi(getenv("MINIGPT4_PENALTIES"));   // the reference's unmodified binding / web UI: its penalty arguments are honoured
     if (const char *lm = getenv("MINIGPT4_LOAD")) load_mode_ = !strcmp(lm, "recv") ? LOAD_RECV : LOAD_FULL;
     // the exchange decides who reads the files: MINIGPT4_LOAD=recv on rank 0 would broadcast empty arenas
@@ -2159,6 +2162,168 @@ int Engine::token_history(int *out, int cap) {
     const Conversation &cv = conv_[(size_t)cur_];
     if (out) for (int i = 0; i < cap && i < (int)cv.hist.size(); i++) out[i] = cv.hist[(size_t)i];
     return (int)cv.hist.size();
+}
+
+// ---- snapshots (engine.hpp, state.hpp) ----
+void Engine::state_alloc(size_t block_bytes) {
+    const size_t words = (size_t)n_ctx_ + 1;                                 // a block holds at least one row: at most n_ctx checksums, then the greedy | feed word
+    if (state_cap_ >= block_bytes && state_sum_words_ >= words && state_cs_) return;
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // nothing queued may still use what is replaced
+    const size_t cap = std::max(block_bytes, state_cap_), nw = std::max(words, state_sum_words_);
+    DevPtr<__half> d0(cap), d1(cap); PinPtr<uint8_t> h0(cap), h1(cap);       // all or nothing: locals first
+    DevPtr<unsigned long long> sd(nw * 8); PinPtr<unsigned long long> sh(nw * 8);
+    if (!state_cs_) {
+        OwnedStream cs(0); OwnedEvent k0(0), k1(0), c0(0), c1(0);
+        state_cs_ = std::move(cs); state_ev_kernel_[0] = std::move(k0); state_ev_kernel_[1] = std::move(k1); state_ev_copy_[0] = std::move(c0); state_ev_copy_[1] = std::move(c1);
+    }
+    state_d_[0] = std::move(d0); state_d_[1] = std::move(d1); state_h_[0] = std::move(h0); state_h_[1] = std::move(h1); state_sum_d_ = std::move(sd); state_sum_h_ = std::move(sh);
+    state_cap_ = cap; state_sum_words_ = nw;
+    state_info_.staging_bytes = (long long)(4 * cap + 16 * nw);
+}
+int Engine::state_header(int slot, StateHeader &h, StateLayout &l) const {
+    const Conversation &cv = conv_[(size_t)slot];
+    h = StateHeader{};
+    h.n_layer = (uint32_t)layers_.size(); h.n_embd = (uint32_t)llm_.n_embd; h.n_head = (uint32_t)llm_.n_head; h.n_vocab = (uint32_t)llm_.n_vocab;
+    h.arena_hash = llm_arena_.layout_hash;
+    h.n_rows = (uint32_t)cv.n_past;
+    h.block_rows = state_block_rows(state_block_bytes_, state_row_bytes(h.n_layer, h.n_embd));
+    h.flags = ((cv.has_logits || !cv.pend_tok.empty()) ? STATE_HAS_LOGITS : 0u) | (parity_ ? STATE_PARITY : 0u);   // queued rows: their pass leaves logits
+    h.n_bias = (uint32_t)cv.bias_id.size();
+    std::string why;
+    if (!state_layout(h, l, why)) { set_last_error("state_save: " + why); return 1; }
+    h.total_bytes = l.total;
+    return 0;
+}
+size_t Engine::state_size(int slot) {
+    if (slot < 0 || slot >= (int)conv_.size()) { set_last_error("state_size: conversation index out of range"); return 0; }
+    StateHeader h; StateLayout l;
+    return state_header(slot, h, l) ? 0 : l.total;
+}
+int Engine::state_save(int slot, void *buf, size_t cap, size_t *written) {
+    auto fail = [](const std::string &what) { set_last_error("state_save: " + what); return 1; };
+    if (written) *written = 0;
+    if (slot < 0 || slot >= (int)conv_.size()) return fail("conversation index out of range");
+    StateHeader h; StateLayout l;
+    if (state_header(slot, h, l)) return 1;
+    if (written) *written = l.total;
+    if (!buf || cap < l.total) return fail("the buffer holds " + std::to_string(buf ? cap : 0) + " bytes, the snapshot takes " + std::to_string(l.total));
+    if (weights_missing()) return fail(last_error());
+    const SelectScope restore(this);
+    cur_ = slot;
+    if (flush()) { if (written) *written = 0; return fail("the queued rows could not be evaluated: " + last_error()); }
+    const Conversation &cv = conv_[(size_t)slot];                            // n_committed == n_past == h.n_rows, has_logits as the header says
+    const int L = (int)h.n_layer, E = (int)h.n_embd, V = (int)h.n_vocab;
+    const size_t seq = (size_t)L * n_ctx_ * E;
+    state_alloc((size_t)std::min(h.block_rows, std::max(h.n_rows, 1u)) * l.row_bytes);
+    uint8_t *out = static_cast<uint8_t *>(buf);
+    for (uint32_t r = 0; r < h.n_rows; r++) state_put32(out + l.hist + (size_t)4 * r, (uint32_t)cv.hist[r]);
+    if (h.flags & STATE_HAS_LOGITS) memcpy(out + l.logits, logits_host(), (size_t)V * 4);   // (little-endian hosts only, like the model files)
+    uint8_t *pp = out + l.pen;
+    state_put32(pp, (uint32_t)cv.pen.repeat_last_n); memcpy(pp + 4, &cv.pen.repeat_penalty, 4); memcpy(pp + 8, &cv.pen.alpha_presence, 4); memcpy(pp + 12, &cv.pen.alpha_frequency, 4);
+    state_put32(pp + 16, (uint32_t)cv.pen.penalize_nl);
+    for (uint32_t b = 0; b < h.n_bias; b++) { state_put32(out + l.bias + (size_t)8 * b, (uint32_t)cv.bias_id[b]); memcpy(out + l.bias + (size_t)8 * b + 4, &cv.bias_val[b], 4); }
+    memset(out + l.bias + (size_t)8 * h.n_bias, 0, l.table - (l.bias + (size_t)8 * h.n_bias));
+    memset(out + l.table + (size_t)8 * l.n_blocks, 0, l.kv - (l.table + (size_t)8 * l.n_blocks));
+    // the blocks: pack c + 1 on stream_ while block c's copy (copy stream) and the memcpy below run.  Staging block i is reused by block c + 2: its pack is issued after the
+    // host has waited for block c's copy, so neither the device block nor the pinned one is overwritten early
+    auto issue = [&](uint32_t c) {
+        const int i = (int)(c & 1), r0 = (int)(c * h.block_rows), n = (int)state_rows_of_block(h, c);
+        launch_kv_pack(kc_ + (size_t)slot * seq, vc_ + (size_t)slot * seq, n_ctx_, L, E, r0, n, state_d_[i], state_sum_d_ + c, stream_);
+        state_info_.pack_launches++;
+        HIP_CHECK(hipEventRecord(state_ev_kernel_[i], stream_));
+        HIP_CHECK(hipStreamWaitEvent(state_cs_, state_ev_kernel_[i], 0));
+        HIP_CHECK(hipMemcpyAsync(state_h_[i], state_d_[i], (size_t)n * l.row_bytes, hipMemcpyDeviceToHost, state_cs_));
+        HIP_CHECK(hipEventRecord(state_ev_copy_[i], state_cs_));
+    };
+    if (l.n_blocks) issue(0);
+    size_t off = l.kv;
+    for (uint32_t c = 0; c < l.n_blocks; c++) {
+        if (c + 1 < l.n_blocks) issue(c + 1);
+        HIP_CHECK(hipEventSynchronize(state_ev_copy_[c & 1]));
+        const size_t bytes = (size_t)state_rows_of_block(h, c) * l.row_bytes;
+        memcpy(out + off, state_h_[c & 1], bytes);
+        off += bytes;
+    }
+    // the block table last, with the greedy and the feed token in the word behind the checksums
+    int *tok = reinterpret_cast<int *>(state_sum_h_ + l.n_blocks);
+    if (l.n_blocks) HIP_CHECK(hipMemcpyAsync(state_sum_h_, state_sum_d_, (size_t)8 * l.n_blocks, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(tok, d_argmax_ + slot, 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipMemcpyAsync(tok + 1, d_feed_ + slot, 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    for (uint32_t c = 0; c < l.n_blocks; c++) state_put64(out + l.table + (size_t)8 * c, state_sum_h_[c]);
+    auto in_vocab = [&](int t) { return t >= 0 && t < V ? t : 0; };          // (a conversation that never had logits: whatever the words hold is not a token)
+    h.greedy = (h.flags & STATE_HAS_LOGITS) ? in_vocab(tok[0]) : 0; h.feed = h.n_rows ? in_vocab(tok[1]) : 0;
+    state_write_header(out, h);
+    state_info_.saves++; state_info_.rows_saved += h.n_rows;
+    return 0;
+}
+int Engine::state_load(int slot, const void *buf, size_t n) {
+    auto fail = [](const std::string &what) { set_last_error("state_load: " + what); return 1; };
+    if (slot < 0 || slot >= (int)conv_.size()) return fail("conversation index out of range");
+    StateHeader h; StateLayout l; std::string why;
+    if (!state_parse(buf, n, h, l, why)) return fail(why);
+    if (h.n_layer != layers_.size() || h.n_embd != (uint32_t)llm_.n_embd || h.n_head != (uint32_t)llm_.n_head || h.n_vocab != (uint32_t)llm_.n_vocab)
+        return fail("the snapshot's model shape (n_layer " + std::to_string(h.n_layer) + ", n_embd " + std::to_string(h.n_embd) + ", n_head " + std::to_string(h.n_head) + ", n_vocab " +
+                    std::to_string(h.n_vocab) + ") is not this context's");
+    if (h.arena_hash != llm_arena_.layout_hash) return fail("the snapshot's LLM arena hash is not this context's (another weight file)");
+    if (h.n_rows > (uint32_t)n_ctx_) return fail("n_rows " + std::to_string(h.n_rows) + " exceeds n_ctx " + std::to_string(n_ctx_));
+    const size_t block_bytes = (size_t)std::min(h.block_rows, std::max(h.n_rows, 1u)) * l.row_bytes;
+    if (block_bytes / 16 >= ((size_t)1 << 31)) return fail("a block of " + std::to_string(h.block_rows) + " rows is 2^31 or more 16-byte pieces");
+    if (weights_missing()) return fail(last_error());
+    state_alloc(block_bytes);                                                // throws before anything changed
+    const uint8_t *in = static_cast<const uint8_t *>(buf);
+    const int L = (int)h.n_layer, E = (int)h.n_embd, V = (int)h.n_vocab;
+    const size_t seq = (size_t)L * n_ctx_ * E;
+    // from here on the slot's former content is gone: what reset() does, then the queue
+    const SelectScope restore(this);
+    cur_ = slot;
+    reset();
+    Conversation &cv = conv_[(size_t)slot];
+    if (logits_host_slot_ == slot) logits_host_slot_ = -1;
+    // host memcpy of block c into pinned block i (free once block c - 2's upload is done), upload on the copy stream (device block i is free once block c - 2's
+    // unpack is done), unpack on stream_ behind the upload
+    size_t off = l.kv;
+    for (uint32_t c = 0; c < l.n_blocks; c++) {
+        const int i = (int)(c & 1), r0 = (int)(c * h.block_rows), nr = (int)state_rows_of_block(h, c);
+        const size_t bytes = (size_t)nr * l.row_bytes;
+        if (c >= 2) HIP_CHECK(hipEventSynchronize(state_ev_copy_[i]));
+        memcpy(state_h_[i], in + off, bytes);
+        off += bytes;
+        if (c >= 2) HIP_CHECK(hipStreamWaitEvent(state_cs_, state_ev_kernel_[i], 0));
+        HIP_CHECK(hipMemcpyAsync(state_d_[i], state_h_[i], bytes, hipMemcpyHostToDevice, state_cs_));
+        HIP_CHECK(hipEventRecord(state_ev_copy_[i], state_cs_));
+        HIP_CHECK(hipStreamWaitEvent(stream_, state_ev_copy_[i], 0));
+        launch_kv_unpack(state_d_[i], kc_ + (size_t)slot * seq, vc_ + (size_t)slot * seq, n_ctx_, L, E, r0, nr, state_sum_d_ + c, stream_);
+        state_info_.unpack_launches++;
+        HIP_CHECK(hipEventRecord(state_ev_kernel_[i], stream_));
+    }
+    if (l.n_blocks) HIP_CHECK(hipMemcpyAsync(state_sum_h_, state_sum_d_, (size_t)8 * l.n_blocks, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // (the copy stream's work lies before stream_'s last unpack)
+    for (uint32_t c = 0; c < l.n_blocks; c++)
+        if (state_sum_h_[c] != state_get64(in + l.table + (size_t)8 * c)) { state_info_.checksum_failures++; return fail("block " + std::to_string(c) + " checksum"); }
+    // everything a following sample, batched step, score, fork, shift or verify pass reads
+    const bool has_logits = (h.flags & STATE_HAS_LOGITS) != 0;
+    if (has_logits) {
+        memcpy(h_logits_, in + l.logits, (size_t)V * 4);                     // through the pinned row: the caller's buffer need not outlive the call
+        HIP_CHECK(hipMemcpyAsync(logits_ + (size_t)slot * V, h_logits_, (size_t)V * 4, hipMemcpyHostToDevice, stream_));
+    }
+    launch_set_int(d_npast_ + slot, (int)h.n_rows, stream_);
+    launch_set_int(d_argmax_ + slot, h.greedy, stream_);
+    launch_set_int(d_feed_ + slot, h.feed, stream_);
+    HIP_CHECK(hipMemcpyAsync(h_argmax_ + slot, d_argmax_ + slot, 4, hipMemcpyDeviceToHost, stream_));   // greedy sample_token reads this copy
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    logits_host_slot_ = has_logits ? slot : logits_host_slot_;               // h_logits_ holds exactly this row
+    cv.n_committed = cv.n_past = (int)h.n_rows;
+    cv.hist.resize(h.n_rows);
+    for (uint32_t r = 0; r < h.n_rows; r++) cv.hist[r] = (int)state_get32(in + l.hist + (size_t)4 * r);
+    cv.has_logits = has_logits;
+    const uint8_t *pp = in + l.pen;
+    cv.pen.repeat_last_n = (int)state_get32(pp); memcpy(&cv.pen.repeat_penalty, pp + 4, 4); memcpy(&cv.pen.alpha_presence, pp + 8, 4); memcpy(&cv.pen.alpha_frequency, pp + 12, 4);
+    cv.pen.penalize_nl = (int)state_get32(pp + 16);
+    cv.bias_id.resize(h.n_bias); cv.bias_val.resize(h.n_bias);
+    for (uint32_t b = 0; b < h.n_bias; b++) { cv.bias_id[b] = (int)state_get32(in + l.bias + (size_t)8 * b); memcpy(&cv.bias_val[b], in + l.bias + (size_t)8 * b + 4, 4); }
+    state_info_.loads++; state_info_.rows_loaded += h.n_rows;
+    return 0;
 }
 
 // ---- speculation: draft tokens verified in one weight pass (engine.hpp) ----

@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "owned.hpp"
 #include "sampler.hpp"
+#include "state.hpp"
 
 namespace mg4 {
 
@@ -242,6 +243,26 @@ public:
     int constraint_advance(int slot, const int *tokens, int n);            // host walk; a token that leads to state 0 refuses the whole call
     int constraint_info(int slot, int out[8]) const;                       // {handle, state, accepting, n_states, pick launches, host rows, stuck picks, index launches}
     int constraint_mask(int handle, int state, uint32_t *out, int n_words);   // the device index row of (handle, state)
+
+    // ---- snapshots (state.hpp: the format; minigpt4_amd.h: the rules).  A conversation leaves its slot, its context or its process as one checksummed blob and comes back
+    // bit for bit: cache rows [0, n_rows), token history, logits row, greedy / feed token, penalty parameters and logit bias.  Not in a snapshot: the sampler's generator and
+    // mirostat state (context-level), the constraint handle and state (handles are per context), queued rows (a save evaluates them first), the prefix store.
+    // The cache travels in blocks of block_rows rows through two device and two pinned staging blocks (allocated by the first save / load, grown when a snapshot's own
+    // block size asks for more, freed with the context; they survive set_conversations) and a copy stream of the feature's own: save packs block c + 1 (k_kv_pack, stream_)
+    // while block c's device-to-host copy (copy stream) and the host memcpy into the caller's buffer run; load mirrors it (host memcpy, upload, k_kv_unpack).  Every launch
+    // leaves its block's checksum in a device word; one small copy fetches them all.  Save writes them into the block table last; load compares them with the table.
+    // state_size: the bytes a save of `slot` would take now, queued rows counted (0 + last_error: slot out of range).
+    // state_save: 0, or 1 + last_error "state_save: ..." with nothing written and nothing evaluated for a slot out of range or cap < the size (*written = the size needed).
+    // state_load: header and every host section are parsed and checked first (fingerprint = n_layer, n_embd, n_head, n_vocab, LLM arena layout hash; n_rows <= n_ctx; ids in
+    // range; section sizes) -- a refusal there returns 1 + "state_load: ..." with nothing changed.  Then whatever the slot held, queued rows included, is dropped, the blocks
+    // are unpacked and position, device position word, logits row, greedy / feed token, history, penalties and bias installed; the slot's captured decode step stays (the
+    // addresses are unchanged, eval_chunk re-captures when the key-split choice differs).  A block whose checksum differs from the table: 1 + "state_load: block c
+    // checksum", the conversation left as reset() leaves it -- the one failure that is not "nothing changed".
+    size_t state_size(int slot);
+    int state_save(int slot, void *buf, size_t cap, size_t *written);
+    int state_load(int slot, const void *buf, size_t n);
+    struct StateInfo { long long saves = 0, loads = 0, rows_saved = 0, rows_loaded = 0, pack_launches = 0, unpack_launches = 0, checksum_failures = 0, staging_bytes = 0; };
+    StateInfo state_info() const { return state_info_; }
 
     // ---- measurement hooks (bench / tests): both feed tokens back on the device, so the rows they add enter the token history as -1
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
@@ -575,6 +596,15 @@ private:
     void con_walk(int slot, int id);                                       // the state after the picked token (EOS and ids outside the vocabulary leave it)
     void con_pick(const int *slots, int n, int *ids);                      // ids[i] <- the constrained pick of every listed conversation that holds a constraint
     const unsigned *con_fetch_row(int handle, int state);                  // index[state] of that constraint in con_row_h_, synchronised
+    // snapshots' own lazy allocation (first state_save / state_load; freed with the context, kept by set_conversations): two device and two pinned staging blocks of
+    // state_cap_ bytes each; one checksum word per block of a snapshot (at most n_ctx blocks) + one word for the greedy | feed token, device and pinned; the copy stream;
+    // per staging block the event behind its kernel (stream_) and behind its copy (copy stream).  state_block_bytes_: MINIGPT4_STATE_BLOCK_BYTES (read by init)
+    DevPtr<__half> state_d_[2]; PinPtr<uint8_t> state_h_[2]; DevPtr<unsigned long long> state_sum_d_; PinPtr<unsigned long long> state_sum_h_;
+    OwnedStream state_cs_; OwnedEvent state_ev_kernel_[2], state_ev_copy_[2];
+    size_t state_cap_ = 0, state_sum_words_ = 0, state_block_bytes_ = STATE_BLOCK_BYTES_DEFAULT;
+    StateInfo state_info_;
+    void state_alloc(size_t block_bytes);              // staging for blocks of that size (all or nothing; grows, never shrinks)
+    int state_header(int slot, StateHeader &h, StateLayout &l) const;   // what a save of `slot` would write now (n_rows = n_past); 0, or 1: the layout refused
 };
 
 int device_count_noexcept();

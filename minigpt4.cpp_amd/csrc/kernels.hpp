@@ -144,6 +144,13 @@ void launch_kv_shift(__half *kc_slot, __half *vc_slot, int n_layer, int n_ctx, i
 constexpr int KV_COPY_MAX_DST = 64;                    // = Engine::MAX_CONVERSATIONS
 struct KvCopyDst { __half *k[KV_COPY_MAX_DST]; __half *v[KV_COPY_MAX_DST]; };   // passed by value to the kernel (llm_kernels.hip: why)
 void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, const KvCopyDst &dst, int n_dst, int dst_rows, int n_layer, int E, int n_rows, hipStream_t s);
+// snapshot blocks (Engine::state_save / state_load): rows [r0, r0 + n) of every layer, keys and values, of ONE conversation (kc_slot / vc_slot = [n_layer][n_ctx][E] fp16)
+// to / from one contiguous block [tensor K, V][layer][row][E] of 4 * n_layer * n * E bytes, bit for bit, in one launch.  *sum (device, 8-byte aligned; zeroed by the launcher
+// in the stream) receives the block's checksum -- device_checksum's definition: the sum of its 32-bit words mod 2^64 --: of what pack wrote, of what unpack read.  Rows
+// outside the range are not touched.  n == 0 launches nothing and leaves *sum 0.  Throws HipError: E % 8, a pointer that is not 16-byte aligned, r0 < 0, r0 + n > n_ctx,
+// 2^31 or more 16-byte pieces.
+void launch_kv_pack(const __half *kc_slot, const __half *vc_slot, int n_ctx, int n_layer, int E, int r0, int n, __half *block, unsigned long long *sum, hipStream_t s);
+void launch_kv_unpack(const __half *block, __half *kc_slot, __half *vc_slot, int n_ctx, int n_layer, int E, int r0, int n, unsigned long long *sum, hipStream_t s);
 // beam reordering (Engine::beam_search): rows [r0, r1) of every layer, keys and values, among W conversations of ONE cache pair (kc / vc = [slot][n_layer][n_ctx][E] fp16,
 // conversation x at kc + x * seq_stride): conversation slots.s[i] receives what conversation slots.s[parent[i]] held, for ANY map parent[0 .. W) -- swaps, cycles,
 // all-to-one -- in one launch; parent is read on the device (k_beam_select's output; an entry outside [0, W) counts as i).  An identity map returns at once; rows outside

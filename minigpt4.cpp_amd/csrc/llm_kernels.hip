@@ -1655,6 +1655,102 @@ void launch_kv_copy(const __half *src_k, const __half *src_v, int src_rows, cons
 }
 
 // =====================================================================================================================
+// Snapshot pack / unpack (Engine::state_save / state_load): rows [r0, r0 + n) of ONE conversation's regions (kc / vc = [n_layer][n_ctx][E] fp16) <-> one contiguous
+// block laid out [tensor K, V][layer][row][E], which k_kv_copy cannot express (it starts at row 0 and has no integrity check).  Per layer and tensor the rows are one
+// contiguous run of n * E halves cut into 16-byte pieces, as in k_kv_copy; the block is the 2 * n_layer runs back to back, so piece i of the launch IS piece i of the block
+// and only the cache side is strided (layer stride n_ctx * E).  Lane t of workgroup b takes the pieces (b * KV_COPY_PIECES + j) * KV_COPY_THREADS + t: every load and store
+// of a wave is one coalesced KiB on both sides, the four loads of a lane are issued before its first store (pointers not __restrict__, as in k_kv_copy).
+// The same sweep sums the block: the wrapping 64-bit sum of its 32-bit words (k_checksum's definition), taken from the registers the pieces were loaded into -- PACK sums
+// what it stores into the block, UNPACK what it read from the block, so the two agree exactly when the block arrived unchanged.  Integer addition is order-free: the value
+// does not depend on the grid.  Reduction: wave (shuffles), workgroup (one 8-byte LDS word per wave), then ONE 64-bit vector atomic add per workgroup into *sum, which the launcher
+// zeroes in the stream before the launch (a 32 MiB block: 2048 adds).
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage), k_kv_pack | k_kv_unpack: 34 | 40 VGPRs, 28 | 28 SGPRs, no scratch, 32 bytes of LDS, occupancy 8 waves per SIMD.  The
+// pieces are four named values, not an array: k_kv_copy's array ended up in LDS (16 KB per workgroup) and its loads were no longer in flight together.
+// =====================================================================================================================
+struct KvBlockPiece { uint4 data; size_t cache_off; unsigned idx; int sel; };   // cache_off: halves into the tensor's region; idx: piece of the block; sel as KvPiece
+template <bool PACK>
+__device__ __forceinline__ KvBlockPiece kv_block_load(const __half *kc, const __half *vc, const __half *blk, unsigned i0, unsigned total, unsigned per, unsigned n_layer,
+                                                      unsigned n_ctx, unsigned E, unsigned r0) {
+    const unsigned i = i0 < total ? i0 : 0u;                               // past the end: piece 0 is loaded (in bounds, total >= 1), neither stored nor summed
+    const unsigned run = i / per, within = i - run * per;                  // run = tensor * n_layer + layer
+    const bool is_v = run >= n_layer;
+    const unsigned layer = is_v ? run - n_layer : run;
+    KvBlockPiece p;
+    p.cache_off = ((size_t)layer * n_ctx + r0) * E + (size_t)within * 8;
+    p.idx = i;
+    p.sel = i0 < total ? (is_v ? 2 : 1) : 0;
+    p.data = *reinterpret_cast<const uint4 *>(PACK ? (is_v ? vc : kc) + p.cache_off : blk + (size_t)i * 8);
+    return p;
+}
+template <bool PACK>
+__device__ __forceinline__ unsigned long long kv_block_store(const KvBlockPiece &p, __half *kc, __half *vc, __half *blk) {
+    if (!p.sel) return 0ull;
+    *reinterpret_cast<uint4 *>(PACK ? blk + (size_t)p.idx * 8 : (p.sel == 2 ? vc : kc) + p.cache_off) = p.data;
+    return (unsigned long long)p.data.x + p.data.y + p.data.z + p.data.w;
+}
+// PACK: kc / vc are read, blk is written; UNPACK: the reverse.  Not __restrict__ on purpose (above)
+template <bool PACK>
+__device__ __forceinline__ void kv_block_body(__half *kc, __half *vc, __half *blk, unsigned n_ctx, unsigned n_layer, unsigned E, unsigned r0, unsigned n, unsigned long long *sum) {
+    static_assert(KV_COPY_PIECES == 4, "the four pieces are named");
+    constexpr int WAVES = KV_COPY_THREADS / 64;
+    __shared__ unsigned long long wave_sum[WAVES];
+    const unsigned per = n * (E / 8);                                      // 16-byte pieces of one layer's run
+    const unsigned total = 2u * n_layer * per;                             // < 2^31 (kv_block_check)
+    const unsigned first = blockIdx.x * (KV_COPY_PIECES * KV_COPY_THREADS) + threadIdx.x;
+    const KvBlockPiece p0 = kv_block_load<PACK>(kc, vc, blk, first, total, per, n_layer, n_ctx, E, r0);
+    const KvBlockPiece p1 = kv_block_load<PACK>(kc, vc, blk, first + KV_COPY_THREADS, total, per, n_layer, n_ctx, E, r0);
+    const KvBlockPiece p2 = kv_block_load<PACK>(kc, vc, blk, first + 2 * KV_COPY_THREADS, total, per, n_layer, n_ctx, E, r0);
+    const KvBlockPiece p3 = kv_block_load<PACK>(kc, vc, blk, first + 3 * KV_COPY_THREADS, total, per, n_layer, n_ctx, E, r0);
+    unsigned long long s = kv_block_store<PACK>(p0, kc, vc, blk);
+    s += kv_block_store<PACK>(p1, kc, vc, blk); s += kv_block_store<PACK>(p2, kc, vc, blk); s += kv_block_store<PACK>(p3, kc, vc, blk);
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; w++) t += wave_sum[w];
+        atomicAdd(sum, t);                                                 // integer sum: order does not matter
+    }
+}
+__global__ __launch_bounds__(KV_COPY_THREADS) void k_kv_pack(const __half *kc, const __half *vc, __half *blk, unsigned n_ctx, unsigned n_layer, unsigned E, unsigned r0, unsigned n,
+                                                           unsigned long long *sum) {
+    kv_block_body<true>(const_cast<__half *>(kc), const_cast<__half *>(vc), blk, n_ctx, n_layer, E, r0, n, sum);
+}
+__global__ __launch_bounds__(KV_COPY_THREADS) void k_kv_unpack(const __half *blk, __half *kc, __half *vc, unsigned n_ctx, unsigned n_layer, unsigned E, unsigned r0, unsigned n,
+                                                             unsigned long long *sum) {
+    kv_block_body<false>(kc, vc, const_cast<__half *>(blk), n_ctx, n_layer, E, r0, n, sum);
+}
+static unsigned kv_block_check(const char *name, const void *kc, const void *vc, const void *blk, const void *sum, int n_ctx, int n_layer, int E, int r0, int n) {
+    static thread_local char msg[96];
+    auto bad = [&](const char *what) { snprintf(msg, sizeof(msg), "%s: %s", name, what); throw HipError{hipErrorInvalidValue, msg, __FILE__, __LINE__}; };
+    if (!kc || !vc || !blk || !sum || n_layer < 1 || n_ctx < 1 || E < 8 || E % 8 || r0 < 0 || n < 0) bad("bad shape");
+    if ((long long)r0 + n > n_ctx) bad("rows outside the cache");
+    if ((uintptr_t)kc % 16 || (uintptr_t)vc % 16 || (uintptr_t)blk % 16 || (uintptr_t)sum % 8) bad("a region is not 16-byte aligned");
+    const unsigned long long total = 2ull * n_layer * (unsigned long long)n * (E / 8);
+    if (total >= (1ull << 31)) bad("2^31 or more pieces");
+    return (unsigned)total;
+}
+void launch_kv_pack(const __half *kc_slot, const __half *vc_slot, int n_ctx, int n_layer, int E, int r0, int n, __half *block, unsigned long long *sum, hipStream_t s) {
+    const unsigned total = kv_block_check("launch_kv_pack", kc_slot, vc_slot, block, sum, n_ctx, n_layer, E, r0, n);
+    HIP_CHECK(hipMemsetAsync(sum, 0, 8, s));
+    if (total == 0) return;
+    note_kernel("k_kv_pack");
+    const unsigned per_block = KV_COPY_PIECES * KV_COPY_THREADS;
+    hipLaunchKernelGGL(k_kv_pack, dim3((total + per_block - 1) / per_block), dim3(KV_COPY_THREADS), 0, s, kc_slot, vc_slot, block, (unsigned)n_ctx, (unsigned)n_layer, (unsigned)E,
+                       (unsigned)r0, (unsigned)n, sum);
+}
+void launch_kv_unpack(const __half *block, __half *kc_slot, __half *vc_slot, int n_ctx, int n_layer, int E, int r0, int n, unsigned long long *sum, hipStream_t s) {
+    const unsigned total = kv_block_check("launch_kv_unpack", kc_slot, vc_slot, block, sum, n_ctx, n_layer, E, r0, n);
+    HIP_CHECK(hipMemsetAsync(sum, 0, 8, s));
+    if (total == 0) return;
+    note_kernel("k_kv_unpack");
+    const unsigned per_block = KV_COPY_PIECES * KV_COPY_THREADS;
+    hipLaunchKernelGGL(k_kv_unpack, dim3((total + per_block - 1) / per_block), dim3(KV_COPY_THREADS), 0, s, block, kc_slot, vc_slot, (unsigned)n_ctx, (unsigned)n_layer, (unsigned)E,
+                       (unsigned)r0, (unsigned)n, sum);
+}
+
+// =====================================================================================================================
 // Beam reordering (Engine::beam_search): conversation slots.s[i] receives rows [r0, r0 + n_rows) of conversation slots.s[parent[i]], every layer, keys and values, for ANY
 // map parent -- a swap, a cycle, all-to-one -- in ONE launch, which k_kv_copy (one source, destinations that may not overlap it) cannot express.  Per layer and tensor the
 // rows are one contiguous run of n_rows * E halves, cut into 16-byte pieces as in k_kv_copy; ONE thread owns ONE piece position (tensor, layer, row, column piece) in all W

@@ -40,6 +40,11 @@ struct WaitEvent {   // hipEventDisableTiming: something to wait on, never to me
     static void *acquire(size_t) { hipEvent_t e = nullptr; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; }
     static void release(void *e) noexcept { HIP_IGNORE(hipEventDestroy(static_cast<hipEvent_t>(e))); }
 };
+struct SideStream {   // a non-blocking stream next to the context's own (copies that overlap its kernels); ordered against it with events only
+    static void *acquire(size_t) { hipStream_t s = nullptr; HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return s; }
+    static void release(void *s) noexcept { HIP_IGNORE(hipStreamDestroy(static_cast<hipStream_t>(s))); }
+};
+using OwnedStream = Owned<std::remove_pointer_t<hipStream_t>, SideStream>;  // converts to hipStream_t; OwnedStream(0) creates it
 template <typename T> using DevPtr = Owned<T, DeviceMem>;
 template <typename T> using PinPtr = Owned<T, PinnedMem>;
 using OwnedEvent = Owned<std::remove_pointer_t<hipEvent_t>, WaitEvent>;     // converts to hipEvent_t; OwnedEvent(0) creates it

@@ -838,6 +838,72 @@ int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int
         return 0;
     });
 }
+// device_checksum (k_checksum: the sum of the 32-bit words mod 2^64) over a caller-given device-accessible range -- tools/state_swap.py's baseline runs it over the pinned
+// block its runtime copies filled.  ms: hipEvent time around the call (the launch, and the 8-byte allocation, memset and copy back that device_checksum makes)
+int minigpt4_amd_test_checksum(const void *device_ptr, size_t bytes, uint64_t *sum_out, float *ms) {
+    if (!device_ptr || !sum_out || (uintptr_t)device_ptr % 4) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+        struct Ev { hipEvent_t a, b; ~Ev() { HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b)); } } ev{a, b};
+        HIP_CHECK(hipEventRecord(a, nullptr));
+        *sum_out = device_checksum(device_ptr, bytes, nullptr);
+        HIP_CHECK(hipEventRecord(b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
+        if (ms) *ms = t;
+        return 0;
+    });
+}
+// The snapshot kernels alone (launch_kv_pack / launch_kv_unpack) on host caches [n_layer][n_ctx][n_embd] fp16 of ONE conversation and a host block [2][n_layer][n][n_embd].
+// The row range is NOT checked here: the launcher's refusal is what the tests look at (rc 3).  k == v == block == NULL: timing only, on device buffers of that shape that
+// never cross the host (the engine's real strides are gigabytes per tensor)
+int minigpt4_amd_test_kv_pack(int n_layer, int n_ctx, int n_embd, int r0, int n, const uint16_t *k, const uint16_t *v, uint16_t *block_out, uint64_t *sum_out, float *ms) {
+    if (!k != !v || !k != !block_out || !sum_out || n_layer < 1 || n_ctx < 1 || n_embd < 1 || n < 0 || n > n_ctx) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t cache = (size_t)n_layer * n_ctx * n_embd * 2, blk = (size_t)2 * n_layer * n * n_embd * 2;
+        DevBuf dk(cache), dv(cache), db(blk), ds(8);
+        if (k) { HIP_CHECK(hipMemcpy(dk.p, k, cache, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, cache, hipMemcpyHostToDevice)); }
+        else { HIP_CHECK(hipMemset(dk.p, 0x11, cache)); HIP_CHECK(hipMemset(dv.p, 0x22, cache)); }   // every page touched before the timed launch
+        HIP_CHECK(hipMemset(db.p, 0, blk ? blk : 1)); HIP_CHECK(hipMemset(ds.p, 0xFF, 8));   // the launcher zeroes the word
+        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+        struct Ev { hipEvent_t a, b; ~Ev() { HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b)); } } ev{a, b};
+        HIP_CHECK(hipEventRecord(a, nullptr));
+        launch_kv_pack(dk.as<__half>(), dv.as<__half>(), n_ctx, n_layer, n_embd, r0, n, db.as<__half>(), ds.as<unsigned long long>(), nullptr);
+        HIP_CHECK(hipEventRecord(b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
+        if (ms) *ms = t;
+        if (blk && block_out) HIP_CHECK(hipMemcpy(block_out, db.p, blk, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(sum_out, ds.p, 8, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+int minigpt4_amd_test_kv_unpack(int n_layer, int n_ctx, int n_embd, int r0, int n, const uint16_t *block, uint16_t *k, uint16_t *v, uint64_t *sum_out, float *ms) {
+    if (!k != !v || !k != !block || !sum_out || n_layer < 1 || n_ctx < 1 || n_embd < 1 || n < 0 || n > n_ctx) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t cache = (size_t)n_layer * n_ctx * n_embd * 2, blk = (size_t)2 * n_layer * n * n_embd * 2;
+        DevBuf dk(cache), dv(cache), db(blk), ds(8);
+        if (k) { HIP_CHECK(hipMemcpy(dk.p, k, cache, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, cache, hipMemcpyHostToDevice)); }
+        else { HIP_CHECK(hipMemset(dk.p, 0x11, cache)); HIP_CHECK(hipMemset(dv.p, 0x22, cache)); }
+        if (blk && block) HIP_CHECK(hipMemcpy(db.p, block, blk, hipMemcpyHostToDevice));
+        else if (blk) HIP_CHECK(hipMemset(db.p, 0x33, blk));
+        HIP_CHECK(hipMemset(ds.p, 0xFF, 8));
+        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
+        struct Ev { hipEvent_t a, b; ~Ev() { HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b)); } } ev{a, b};
+        HIP_CHECK(hipEventRecord(a, nullptr));
+        launch_kv_unpack(db.as<__half>(), dk.as<__half>(), dv.as<__half>(), n_ctx, n_layer, n_embd, r0, n, ds.as<unsigned long long>(), nullptr);
+        HIP_CHECK(hipEventRecord(b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
+        if (ms) *ms = t;
+        if (k) { HIP_CHECK(hipMemcpy(k, dk.p, cache, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, cache, hipMemcpyDeviceToHost)); }
+        HIP_CHECK(hipMemcpy(sum_out, ds.p, 8, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // The scoring kernel (launch_logprob_rows) on host logits [rows][ld]: one launch, hipEvent-timed.  Every target is checked here: it indexes a row on the device.
 int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, int ld, const int32_t *targets, float *logprob_out, int32_t *greedy_out, float *greedy_logprob_out,
                                    float *ms_out) {

@@ -257,6 +257,15 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_constraint_advance.argtypes = [VOID_PTR, I32, INT_PTR, I32]
         L.minigpt4_amd_constraint_info.argtypes = [VOID_PTR, I32, INT_PTR]
         L.minigpt4_amd_constraint_mask.argtypes = [VOID_PTR, I32, I32, P(ctypes.c_uint32), I32]
+        I64P = P(ctypes.c_int64)
+        L.minigpt4_amd_state_size.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_state_size.restype = SIZE_T
+        L.minigpt4_amd_state_save.argtypes = [VOID_PTR, I32, VOID_PTR, SIZE_T, P(ctypes.c_size_t)]
+        L.minigpt4_amd_state_load.argtypes = [VOID_PTR, I32, VOID_PTR, SIZE_T]
+        L.minigpt4_amd_state_save_file.argtypes = [VOID_PTR, I32, CHAR_PTR]
+        L.minigpt4_amd_state_load_file.argtypes = [VOID_PTR, I32, CHAR_PTR]
+        L.minigpt4_amd_state_peek.argtypes = [VOID_PTR, SIZE_T, I64P]
+        L.minigpt4_amd_state_info.argtypes = [VOID_PTR, I64P]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -293,6 +302,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_attn_f32.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, F32, F32, I32, I32, VOID_PTR, FLOAT_PTR, VOID_PTR]
         L.minigpt4_amd_test_kv_shift.argtypes = [I32, I32, I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_kv_copy.argtypes = [I32, I32, I32, I32, I32, INT_PTR, I32, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_checksum.argtypes = [VOID_PTR, SIZE_T, U64P, FLOAT_PTR]
+        L.minigpt4_amd_test_kv_pack.argtypes = [I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, VOID_PTR, U64P, FLOAT_PTR]
+        L.minigpt4_amd_test_kv_unpack.argtypes = [I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, VOID_PTR, U64P, FLOAT_PTR]
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_penalise_host.argtypes = [FLOAT_PTR, I32, INT_PTR, I32, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, INT_PTR, I32, INT_PTR]
@@ -756,6 +768,59 @@ class MiniGPT4SharedLibrary:
                                                     len(pairs)):
             raise RuntimeError("set_logit_bias failed: " + self._err())
 
+    # ---- snapshots (include/minigpt4_amd.h: the format and the rules)
+    STATE_PEEK_FIELDS = ("version", "total_bytes", "n_layer", "n_embd", "n_head", "n_vocab", "arena_hash", "n_rows", "block_rows", "flags", "greedy", "feed")
+    STATE_INFO_FIELDS = ("saves", "loads", "rows_saved", "rows_loaded", "pack_launches", "unpack_launches", "checksum_failures", "staging_bytes")
+
+    def amd_state_size(self, ctx, slot: int) -> int:
+        """The bytes amd_state_save(ctx, slot) would return now, queued rows counted."""
+        n = int(self.library.minigpt4_amd_state_size(ctx.ptr, int(slot)))
+        if n == 0:
+            raise RuntimeError("state_size failed: " + self._err())
+        return n
+
+    def amd_state_save(self, ctx, slot: int, cap: Optional[int] = None) -> bytes:
+        """Conversation `slot` as one checksummed blob (queued rows are evaluated first).  cap: the buffer size to offer (default: what amd_state_size says); too small
+        raises with the size needed in the text and in the exception's `needed` attribute."""
+        n = self.amd_state_size(ctx, slot) if cap is None else int(cap)
+        buf = (ctypes.c_uint8 * max(n, 1))()
+        written = ctypes.c_size_t()
+        if self.library.minigpt4_amd_state_save(ctx.ptr, int(slot), buf, n, ctypes.byref(written)):
+            e = RuntimeError("state_save failed: " + self._err())
+            e.needed = int(written.value)
+            raise e
+        return bytes(memoryview(buf)[:written.value])
+
+    def amd_state_load(self, ctx, slot: int, blob) -> None:
+        """Restore conversation `slot` from a blob of amd_state_save (any slot of any context of the same language-model file)."""
+        data = bytes(blob)
+        if self.library.minigpt4_amd_state_load(ctx.ptr, int(slot), ctypes.c_char_p(data) if data else None, len(data)):
+            raise RuntimeError("state_load failed: " + self._err())
+
+    def amd_state_save_file(self, ctx, slot: int, path: str) -> None:
+        if self.library.minigpt4_amd_state_save_file(ctx.ptr, int(slot), os.fsencode(path)):
+            raise RuntimeError("state_save_file failed: " + self._err())
+
+    def amd_state_load_file(self, ctx, slot: int, path: str) -> None:
+        if self.library.minigpt4_amd_state_load_file(ctx.ptr, int(slot), os.fsencode(path)):
+            raise RuntimeError("state_load_file failed: " + self._err())
+
+    def amd_state_peek(self, blob) -> dict:
+        """The header fields of a snapshot after every check that needs no context (no GPU either)."""
+        data = bytes(blob)
+        out = (ctypes.c_int64 * len(self.STATE_PEEK_FIELDS))()
+        if self.library.minigpt4_amd_state_peek(ctypes.c_char_p(data) if data else None, len(data), out):
+            raise RuntimeError("state_peek failed: " + self._err())
+        d = dict(zip(self.STATE_PEEK_FIELDS, (int(x) for x in out)))
+        d["arena_hash"] &= (1 << 64) - 1
+        return d
+
+    def amd_state_info(self, ctx) -> dict:
+        out = (ctypes.c_int64 * len(self.STATE_INFO_FIELDS))()
+        if self.library.minigpt4_amd_state_info(ctx.ptr, out):
+            raise RuntimeError("state_info failed: " + self._err())
+        return dict(zip(self.STATE_INFO_FIELDS, (int(x) for x in out)))
+
     def amd_token_history(self, ctx) -> np.ndarray:
         """The selected conversation's row-aligned token history (queued rows are evaluated first): the token id of every cache row, -1 for an embedding row."""
         n = self.library.minigpt4_amd_token_history(ctx.ptr, None, 0)
@@ -1002,6 +1067,50 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_kv_copy rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return k, v, float(ms.value)
+
+    def amd_test_kv_pack(self, k: np.ndarray, v: np.ndarray, r0: int, n: int):
+        """launch_kv_pack alone on uint16 caches [n_layer][n_ctx][n_embd] of one conversation: (block [2][n_layer][n][n_embd] uint16, checksum, ms)."""
+        k = np.ascontiguousarray(k, np.uint16)
+        v = np.ascontiguousarray(v, np.uint16)
+        assert k.ndim == 3 and k.shape == v.shape
+        blk = np.zeros((2, k.shape[0], max(int(n), 0), k.shape[2]), np.uint16)
+        s, ms = ctypes.c_uint64(), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_kv_pack(k.shape[0], k.shape[1], k.shape[2], int(r0), int(n), k.ctypes.data_as(VOID_PTR), v.ctypes.data_as(VOID_PTR),
+                                                    blk.ctypes.data_as(VOID_PTR), ctypes.byref(s), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_pack rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return blk, int(s.value), float(ms.value)
+
+    def amd_test_checksum(self, device_ptr: int, n_bytes: int):
+        """k_checksum over a device-accessible range (an address, e.g. of a hipMalloc / hipHostMalloc block): (sum of its 32-bit words mod 2^64, hipEvent ms)."""
+        s, ms = ctypes.c_uint64(), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_checksum(ctypes.c_void_p(device_ptr), int(n_bytes), ctypes.byref(s), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_checksum rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return int(s.value), float(ms.value)
+
+    def amd_test_kv_block_ms(self, n_layer: int, n_ctx: int, n_embd: int, r0: int, n: int, unpack: bool = False) -> float:
+        """launch_kv_pack (unpack: launch_kv_unpack) on device-only buffers of the given shape (nothing crosses the host): its hipEvent time in ms."""
+        s, ms = ctypes.c_uint64(), ctypes.c_float()
+        fn = self.library.minigpt4_amd_test_kv_unpack if unpack else self.library.minigpt4_amd_test_kv_pack
+        rc = fn(int(n_layer), int(n_ctx), int(n_embd), int(r0), int(n), None, None, None, ctypes.byref(s), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_block rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return float(ms.value)
+
+    def amd_test_kv_unpack(self, block: np.ndarray, k: np.ndarray, v: np.ndarray, r0: int):
+        """launch_kv_unpack alone: block [2][n_layer][n][n_embd] uint16 into rows [r0, r0 + n) of copies of the uint16 caches [n_layer][n_ctx][n_embd]:
+        (k, v, checksum of what the launch read, ms)."""
+        block = np.ascontiguousarray(block, np.uint16)
+        k = np.ascontiguousarray(k, np.uint16).copy()
+        v = np.ascontiguousarray(v, np.uint16).copy()
+        assert k.ndim == 3 and k.shape == v.shape and block.ndim == 4 and block.shape[:2] == (2, k.shape[0]) and block.shape[3] == k.shape[2]
+        s, ms = ctypes.c_uint64(), ctypes.c_float()
+        rc = self.library.minigpt4_amd_test_kv_unpack(k.shape[0], k.shape[1], k.shape[2], int(r0), block.shape[2], block.ctypes.data_as(VOID_PTR), k.ctypes.data_as(VOID_PTR),
+                                                      v.ctypes.data_as(VOID_PTR), ctypes.byref(s), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_kv_unpack rc={rc}: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
+        return k, v, int(s.value), float(ms.value)
 
     def amd_test_kv_copy_ms(self, n_slot: int, n_layer: int, rows: int, n_embd: int, src: int, dsts: Sequence[int], n_rows: int, src_rows: int = 0) -> float:
         """The same launch on device-only caches of the given shape (nothing crosses the host): its hipEvent time in ms."""

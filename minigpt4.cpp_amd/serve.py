@@ -9,6 +9,11 @@ A request = (image, prompt) owns its embedding, KV cache and position (SURVEY.md
   * per conversation the reference's stop rule applies: a piece equal to "##" is swallowed, the answer ends when the accumulated text ends with "###"
     (`minigpt4_contains_eos_token` / `minigpt4_is_eos`, reference `generate`), or after `max_tokens`.
 
+Sessions: a conversation can outlive its wave.  `suspend(slot)` takes a conversation out of its slot as one checksummed blob (`minigpt4_amd_state_save`) and
+`resume(slot, blob)` puts it into any slot (`minigpt4_amd_state_load`); `run(..., sessions=[...])` uses the pair to serve follow-up turns of more sessions than there
+are slots: after a wave every request that names a session is parked, and a later request of that session (image None) is resumed and asked with
+`minigpt4_begin_chat` instead of paying the image turn and all earlier turns again.
+
 Across GPUs requests shard round-robin (`dist.shard_requests`); ranks exchange nothing per token and the answers are gathered at the end.
 """
 from __future__ import annotations
@@ -25,7 +30,7 @@ from . import minigpt4_library as ML
 
 @dataclass
 class Request:
-    image: Union[str, bytes, np.ndarray]      # file path, encoded image bytes (PNG / JPEG / ...), or a preprocessed f32 [3][224][224] array
+    image: Union[str, bytes, np.ndarray, None]   # file path, encoded image bytes (PNG / JPEG / ...), or a preprocessed f32 [3][224][224] array; None: a follow-up turn of a session
     prompt: str
     max_tokens: int = 64
 
@@ -52,6 +57,24 @@ class ReplicaServer:
         self.lib.amd_set_conversations(self.ctx, conversations)
         if prefix_cache:
             self.lib.amd_set_prefix_cache(self.ctx, prefix_cache)
+        self._parked = {}                      # session id -> snapshot of the idle session
+
+    def suspend(self, slot: int) -> bytes:
+        """Conversation `slot` as a snapshot (queued rows are evaluated first); the slot is reset and free for another conversation."""
+        blob = self.lib.amd_state_save(self.ctx, slot)
+        self.lib.amd_select_conversation(self.ctx, slot)
+        self.lib.minigpt4_reset_chat(self.ctx)
+        return blob
+
+    def resume(self, slot: int, blob: bytes) -> None:
+        """Put a suspended conversation into `slot` (whatever it held is dropped): it continues bit for bit where `suspend` took it."""
+        self.lib.amd_state_load(self.ctx, slot, blob)
+
+    def parked_sessions(self) -> List:
+        return list(self._parked)
+
+    def drop_session(self, session) -> None:
+        self._parked.pop(session, None)
 
     def close(self):
         if self.ctx is not None:
@@ -69,8 +92,12 @@ class ReplicaServer:
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
             batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
             frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
-            negative_prompt: Optional[str] = None, regex=None) -> List[str]:
-        """regex (str or bytes; include/minigpt4_amd.h states the pattern language): constrained decoding -- the pattern is compiled once for the call
+            negative_prompt: Optional[str] = None, regex=None, sessions: Optional[Sequence] = None) -> List[str]:
+        """sessions (one hashable id or None per request; the decode loop only -- ValueError with num_beams > 1 or guidance_scale != 1): a request that names a session is
+        parked when its wave ends (`suspend`), so the server holds any number of idle sessions next to its `conversations` slots.  A request whose session is parked
+        is a FOLLOW-UP turn: its image must be None, the session is resumed into the wave's slot and the prompt asked with `minigpt4_begin_chat`; the image turn and
+        every earlier turn are not evaluated again.  A session may appear once per call.  `drop_session` forgets one.
+        regex (str or bytes; include/minigpt4_amd.h states the pattern language): constrained decoding -- the pattern is compiled once for the call
         (`minigpt4_amd_constraint_compile`), set on every request's conversation and cleared and freed when the call returns; every answer then matches the WHOLE pattern, or is
         a prefix of a match when max_tokens ran out first.  The answer ends at "</s>", which the constraint allows exactly where the text matches; the "###" / "##" rules
         of the decode loop are off (the pattern decides what the text may hold).  Works with temp > 0, logprobs, penalties and logit_bias; ValueError together with
@@ -104,6 +131,17 @@ class ReplicaServer:
             raise ValueError("guidance_scale != 1 takes two conversations per request")
         if regex is not None and (num_beams > 1 or guided):
             raise ValueError("regex is not available with num_beams > 1 or guidance_scale != 1")
+        if sessions is not None:
+            if num_beams > 1 or guided:
+                raise ValueError("sessions is not available with num_beams > 1 or guidance_scale != 1")
+            named = [s_ for s_ in sessions if s_ is not None]
+            if len(sessions) != len(requests) or len(set(named)) != len(named):
+                raise ValueError("sessions: one id (or None) per request, each session at most once per call")
+            for r, s_ in zip(requests, sessions):
+                if (r.image is None) != (s_ is not None and s_ in self._parked):
+                    raise ValueError("sessions: a request without an image must name a parked session, a request with one must not")
+        elif any(r.image is None for r in requests):
+            raise ValueError("a request without an image needs sessions=")
         answers: List[str] = [""] * len(requests)
         self._constraint = lib.amd_constraint_compile(ctx, regex) if regex is not None else 0   # a refused pattern raises before anything is touched
         penalised = repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
@@ -111,7 +149,7 @@ class ReplicaServer:
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
-                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt)
+                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions)
         finally:
             if self._constraint:
                 for slot in range(self.conversations):
@@ -149,7 +187,7 @@ class ReplicaServer:
                 shown += piece
         return shown
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None) -> List[str]:
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         if penalised:
@@ -157,21 +195,29 @@ class ReplicaServer:
         self.last_logprobs = [[] for _ in requests] if logprobs > 0 else None
         per = 2 if guidance is not None else num_beams            # conversations per request: its own, then the guidance conversation / the search's scratch
         for wave in plan_waves(len(requests), self.conversations // per):
-            structs, owned = [], []
+            structs, owned, emb_of = [], [], {}
             for i in wave:
+                if requests[i].image is None:                 # a follow-up turn: its image rows are in the parked snapshot
+                    continue
                 st, own = self._to_struct(requests[i].image)
+                emb_of[i] = len(structs)
                 structs.append(st)
                 owned += own
-            arr = (ML.MiniGPT4Image * len(wave))(*structs)
-            batch, embs = ML.MiniGPT4Images(arr, len(wave)), ML.MiniGPT4Embeddings()
-            lib.panic_if_error(lib.library.minigpt4_amd_encode_images(ctx.ptr, ctypes.byref(batch), ctypes.byref(embs), 0))
+            arr = (ML.MiniGPT4Image * max(len(structs), 1))(*structs)
+            batch, embs = ML.MiniGPT4Images(arr, len(structs)), ML.MiniGPT4Embeddings()
+            if structs:
+                lib.panic_if_error(lib.library.minigpt4_amd_encode_images(ctx.ptr, ctypes.byref(batch), ctypes.byref(embs), 0))
             try:
                 for j, i in enumerate(wave):
                     slot = j * per
                     lib.amd_select_conversation(ctx, slot)
-                    lib.minigpt4_reset_chat(ctx)
-                    lib.minigpt4_system_prompt(ctx)
-                    lib.minigpt4_begin_chat_image(ctx, embs.embeddings[j], requests[i].prompt)
+                    if requests[i].image is None:
+                        self.resume(slot, self._parked[sessions[i]])   # the parked blob stays until the wave has parked the session again: a failure in between loses nothing
+                        lib.minigpt4_begin_chat(ctx, requests[i].prompt)
+                    else:
+                        lib.minigpt4_reset_chat(ctx)
+                        lib.minigpt4_system_prompt(ctx)
+                        lib.minigpt4_begin_chat_image(ctx, embs.embeddings[emb_of[i]], requests[i].prompt)
                     if penalised:
                         lib.amd_conversation_penalties(ctx, slot, **pen)
                     if logit_bias:
@@ -229,8 +275,11 @@ class ReplicaServer:
                     active = nxt
                 for slot, i in enumerate(wave):
                     answers[i] = shown[slot]
+                    if sessions is not None and sessions[i] is not None:
+                        self._parked[sessions[i]] = self.suspend(slot)
             finally:
-                lib.library.minigpt4_amd_free_embeddings(ctypes.byref(embs))
+                if structs:
+                    lib.library.minigpt4_amd_free_embeddings(ctypes.byref(embs))
                 for im in owned:
                     lib.minigpt4_free_image(im)
         lib.amd_select_conversation(ctx, 0)
