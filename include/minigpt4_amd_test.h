@@ -45,12 +45,22 @@ MINIGPT4_API int minigpt4_amd_test_matvec_rows(int ggml_type, const void *raw_w,
    mat-vec launch (rms_w non-null: the norm form, NULL: the rows as they are).  Returns 4 when the kernel has no such form for the type / n_in. */
 MINIGPT4_API int minigpt4_amd_test_matvec_rows_prep(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual,
                                                     const float *rms_w, int prepare, float *y);
+/* The two-type launch of the batched decode (k_matvec_tn_mix; a "more bits" layer's wq | wk + wv): n_a equally shaped matrices of type_a (Q4_K / Q5_K) + n_b of type_b
+ * (Q6_K), n_a + n_b <= 3, against N = 1..4 rows prepared by a launch of their own.  y: [n_a + n_b][N][n_out] and ONE GUARD ROW of n_out floats behind them, prefilled
+ * with 0xFF bytes.  1 = bad arguments, 4 = the launcher refuses the types / shape (n_in above 6144) */
+MINIGPT4_API int minigpt4_amd_test_matvec_rows_mixed(int type_a, const void *raw_a, int n_a, int type_b, const void *raw_b, int n_b, int64_t n_in, int64_t n_out, const float *x,
+                                                     int N, float *y);
 /* Host only: which in-launch preparations the decode mat-vec offers for (type, n_in).  bit 0: the single-row prologue (prep 1 / 2 / 3 of minigpt4_amd_test_matvec with
    fuse = 1), bit 1: the SiLU row-pair epilogue, bit 2: the multi-row prologue (prepare = 1 above).  -1: bad arguments. */
 MINIGPT4_API int minigpt4_amd_test_matvec_predicates(int ggml_type, int64_t n_in);
 /* Activation quantisation (optionally after rms_norm with weight w): returns Q8_K and Q8_0 images of x[N][K].
  * q8k: int8[N*K], dk: float[N*K/256], bsums: int16[N*K/16], q80: int8[N*K], d0: float[N*K/32] (fp16-rounded). Any may be NULL. */
 MINIGPT4_API int minigpt4_amd_test_quantize(const float *x, const float *rms_w, int64_t N, int64_t K, int8_t *q8k, float *dk, int16_t *bsums, int8_t *q80, float *d0);
+/* The embedding gather alone (k_get_rows: the per-element decoder of every weight type), ONE launch_get_rows.  raw_table: n_rows rows of K weights as a model file stores
+ * them (Q3_K rows are re-encoded as Q6_K first, as the engine's load path does); tokens[N] in [-1, n_rows).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard
+ * row; a token of -1 leaves its row at the fill.  1 = bad arguments, before any device is touched (a NULL pointer, a token outside [-1, n_rows), a K that is not a whole
+ * number of blocks, an unknown type); 2 = no device; 3 = HIP error */
+MINIGPT4_API int minigpt4_amd_test_get_rows(int ggml_type, const void *raw_table, int n_rows, int64_t K, const int32_t *tokens, int N, float *out);
 /* C[M][N] = A[M][K] . W[N][K]^T on the MFMA f16 path (inputs given as fp32, rounded to fp16 on the device) + optional bias/GELU */
 MINIGPT4_API int minigpt4_amd_test_gemm_f16(const float *A, const float *W, const float *bias, int M, int N, int K, int gelu, float *C);
 /* the same through the skinny-M kernel of the Q-Former (k_gemm_f16_skinny: N % 16 == 0, K % 32 == 0; 4 otherwise) */

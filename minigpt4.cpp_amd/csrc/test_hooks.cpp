@@ -269,6 +269,46 @@ static int test_matvec_rows_impl(int ggml_type, const void *raw_w, int n_mat, in
     });
 }
 
+// The batched decode's two-type launch (k_matvec_tn_mix) as Engine::forward_batch issues it for a "more bits" layer: n_a equally spaced matrices of type_a (Q4_K / Q5_K) +
+// n_b of type_b (Q6_K), same shape, against N = 1..4 rows prepared by a launch of their own.  y: [n_a + n_b][N][n_out] followed by ONE GUARD ROW of n_out floats, the whole
+// buffer prefilled with 0xFF bytes.  4: the launcher refuses the types / shape.
+int minigpt4_amd_test_matvec_rows_mixed(int type_a, const void *raw_a, int n_a, int type_b, const void *raw_b, int n_b, int64_t n_in, int64_t n_out, const float *x, int N, float *y) {
+    if (!raw_a || !raw_b || !x || !y || n_in <= 0 || n_out <= 0 || n_a < 1 || n_b < 1 || n_a + n_b > 3 || N < 1 || N > 4 || !qweight_supported(type_a) || !qweight_supported(type_b)) return 1;
+    if (n_in % gt_block(type_a) || n_in % gt_block(type_b)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const int K = (int)n_in, R = (int)n_out, n = n_a + n_b;
+        std::vector<std::unique_ptr<DevBuf>> keep;
+        std::vector<QWeight> W((size_t)n);
+        auto upload = [&](int type, const void *raw, int cnt, QWeight *dst) {
+            QWeight plan; const size_t need = plan_qweight(type, R, K, plan, nullptr), raw_bytes = gt_nbytes(type, (size_t)R * K);
+            keep.emplace_back(new DevBuf(need * (size_t)cnt)); uint8_t *base = (uint8_t *)keep.back()->p;   // one allocation: equal spacing
+            DevBuf d_raw(raw_bytes);
+            for (int m = 0; m < cnt; m++) {
+                plan_qweight(type, R, K, dst[m], base + (size_t)m * need);
+                HIP_CHECK(hipMemcpy(d_raw.p, (const uint8_t *)raw + (size_t)m * raw_bytes, raw_bytes, hipMemcpyHostToDevice));
+                if (type == GT_F16 || type == GT_F32) HIP_CHECK(hipMemcpy(base + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), dst[m], nullptr);
+                HIP_CHECK(hipDeviceSynchronize());
+            }
+        };
+        upload(type_a, raw_a, n_a, W.data());
+        upload(type_b, raw_b, n_b, W.data() + n_a);
+        const size_t yn = ((size_t)n * N + 1) * R;
+        DevBuf d_x((size_t)N * K * 4), d_y(yn * 4);
+        HIP_CHECK(hipMemcpy(d_x.p, x, (size_t)N * K * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(d_y.p, 0xFF, yn * 4));
+        ActQ A; alloc_act(A, keep, (size_t)N, (size_t)K);
+        launch_rms_quant(d_x.as<float>(), nullptr, N, K, A, act_mask_for(type_a) | act_mask_for(type_b), nullptr);
+        const QWeight *Wp[3]; float *Yp[3];
+        for (int m = 0; m < n; m++) { Wp[m] = &W[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * N * R; }
+        if (!launch_matvec_rows_mixed(Wp, Yp, n_a, Wp + n_a, Yp + n_a, n_b, A, N, R, nullptr, nullptr, nullptr, K)) { set_last_error("types / shape outside the two-type multi-row mat-vec kernel's range"); return 4; }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(y, d_y.p, yn * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
 // The batched decode's MFMA launch (ri_kernels.hip): n_mat equally shaped k-quant matrices (rows of raw_w back to back) as ordinary planes -> row-interleaved image -> N = 1..4
 // prepared rows; y [n_mat][N][n_out].  4: the kernel refuses the shape / type.
 int minigpt4_amd_test_matvec_ri(int ggml_type, const void *raw_w, int n_mat, int64_t n_in, int64_t n_out, const float *x, int N, const float *residual, const float *rms_w, float *y) {
@@ -416,6 +456,34 @@ int minigpt4_amd_test_quantize(const float *x, const float *rms_w, int64_t N, in
         if (bsums) HIP_CHECK(hipMemcpy(bsums, A.bsk, (size_t)(N * K / 16) * 2, hipMemcpyDeviceToHost));
         if (q80) HIP_CHECK(hipMemcpy(q80, A.q80, (size_t)(N * K), hipMemcpyDeviceToHost));
         if (d0) HIP_CHECK(hipMemcpy(d0, A.d0, (size_t)(N * K / 32) * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// The embedding gather (k_get_rows / dequant_elem) alone: one launch_get_rows over a raw table [n_rows][K] exactly as a model file stores it (Q3_K: re-encoded as Q6_K first,
+// as the engine's load path does).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard row; a token of -1 leaves its row at the fill.
+int minigpt4_amd_test_get_rows(int ggml_type, const void *raw_table, int n_rows, int64_t K, const int32_t *tokens, int N, float *out) {
+    if (!raw_table || !tokens || !out || n_rows < 1 || n_rows > (1 << 20) || K < 1 || K > (1 << 20) || N < 1 || N > (1 << 16)) return 1;
+    if (ggml_type != GT_Q3_K && !qweight_supported(ggml_type)) return 1;
+    if (K % gt_block(ggml_type)) return 1;
+    for (int t = 0; t < N; t++) if (tokens[t] < -1 || tokens[t] >= n_rows) return 1;
+    if (ggml_type == GT_Q3_K) {
+        const size_t nb = (size_t)(K / 256) * (size_t)n_rows;
+        std::vector<uint8_t> q6(nb * 210);
+        q3k_to_q6k(static_cast<const uint8_t *>(raw_table), q6.data(), nb);
+        return minigpt4_amd_test_get_rows(GT_Q6_K, q6.data(), n_rows, K, tokens, N, out);
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t raw_bytes = gt_nbytes(ggml_type, (size_t)K) * (size_t)n_rows, on = ((size_t)N + 1) * (size_t)K;
+        DevBuf d_raw(raw_bytes), d_tok((size_t)N * 4), d_out(on * 4);
+        HIP_CHECK(hipMemcpy(d_raw.p, raw_table, raw_bytes, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(d_tok.p, tokens, (size_t)N * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(d_out.p, 0xFF, on * 4));
+        launch_get_rows(ggml_type, d_raw.as<uint8_t>(), (int)K, d_tok.as<int>(), N, d_out.as<float>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, d_out.p, on * 4, hipMemcpyDeviceToHost));
         return 0;
     });
 }

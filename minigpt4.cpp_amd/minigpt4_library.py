@@ -1393,6 +1393,20 @@ class MiniGPT4SharedLibrary:
             raise RuntimeError(f"test_matvec_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
         return y
 
+    def amd_test_matvec_rows_mixed(self, type_a: int, raw_a: np.ndarray, n_a: int, type_b: int, raw_b: np.ndarray, n_b: int, n_in: int, n_out: int, x: np.ndarray):
+        """The batched decode's two-type launch (k_matvec_tn_mix): x [N][n_in] (N <= 4) -> (y [n_a + n_b][N][n_out], guard: the n_out floats behind them as uint32 bit
+        patterns, 0xFFFFFFFF where the launch left them alone)."""
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, n_in)
+        raw_a, raw_b = np.ascontiguousarray(raw_a), np.ascontiguousarray(raw_b)
+        n, N = n_a + n_b, x.shape[0]
+        buf = np.empty((n * N + 1, n_out), np.float32)
+        f = self.library.minigpt4_amd_test_matvec_rows_mixed
+        f.argtypes = [I32, VOID_PTR, I32, I32, VOID_PTR, I32, ctypes.c_int64, ctypes.c_int64, FLOAT_PTR, I32, FLOAT_PTR]
+        rc = f(type_a, raw_a.ctypes.data_as(VOID_PTR), n_a, type_b, raw_b.ctypes.data_as(VOID_PTR), n_b, n_in, n_out, x.ctypes.data_as(FLOAT_PTR), N, buf.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_matvec_rows_mixed rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
+        return buf[:n * N].reshape(n, N, n_out).copy(), buf[n * N].view(np.uint32).copy()
+
     def amd_test_matvec_ri(self, ggml_type: int, raw_w: np.ndarray, n_mat: int, n_in: int, n_out: int, x: np.ndarray, residual: Optional[np.ndarray] = None,
                            rms_w: Optional[np.ndarray] = None) -> np.ndarray:
         """The batched decode's MFMA launch over the row-interleaved image (csrc/ri_kernels.hip): x [N][n_in] (N <= 4) -> [n_mat][N][n_out]."""
@@ -1433,6 +1447,21 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_quantize rc={rc}")
         return q8k, dk, bs, q80, d0
+
+    def amd_test_get_rows(self, ggml_type: int, raw_table: np.ndarray, n_rows: int, K: int, tokens) -> np.ndarray:
+        """The embedding gather alone (one launch_get_rows over a raw table [n_rows][K]): returns [N + 1][K] fp32 -- row N is the guard row, a row whose token is -1 and
+        the guard row keep their 0xFF fill.  ValueError for arguments the hook refuses before it touches a device."""
+        raw = np.ascontiguousarray(raw_table)
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        out = np.zeros((tok.size + 1, K), np.float32)
+        f = self.library.minigpt4_amd_test_get_rows
+        f.argtypes = [I32, VOID_PTR, I32, ctypes.c_int64, VOID_PTR, I32, FLOAT_PTR]
+        rc = f(ggml_type, raw.ctypes.data_as(VOID_PTR), n_rows, K, tok.ctypes.data_as(VOID_PTR), tok.size, out.ctypes.data_as(FLOAT_PTR))
+        if rc == 1:
+            raise ValueError("amd_test_get_rows: bad arguments")
+        if rc:
+            raise RuntimeError(f"test_get_rows rc={rc}: " + self.library.minigpt4_amd_last_error().decode())
+        return out
 
     @staticmethod
     def _table_arg(table: np.ndarray) -> np.ndarray:
