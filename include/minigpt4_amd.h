@@ -377,6 +377,54 @@ MINIGPT4_API int minigpt4_amd_constraint_advance(struct MiniGPT4Context *ctx, in
 MINIGPT4_API int minigpt4_amd_constraint_info(struct MiniGPT4Context *ctx, int slot, int32_t out[8]);
 MINIGPT4_API int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32_t handle, int state, uint32_t *out, int n_words);
 
+/* ---- sampled batched steps decided on the device, one seed per conversation ------------------------------------------------------------------------------
+ * minigpt4_amd_end_chat_batch with temp > 0 samples on the host: one logits row, one synchronise and one sort per listed conversation, all draws from the context's one
+ * generator in list order -- so the text a conversation receives depends on who shares its step.  Here ONE launch (k_sample_rows, one 256-thread workgroup per listed
+ * conversation) decides the whole step, and every conversation draws from a stream of its own.
+ * GENERATOR: Philox4x32-10 (Random123; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85).  Every conversation has a 64-bit seed and a 64-bit
+ * count of draws: key = (seed low word, seed high word), counter = (draws low, draws high, 0, 0), the draw uses output word 0.  After minigpt4_model_load and after
+ * minigpt4_amd_set_conversations conversation s has seed = (uint32_t)load seed | (uint64_t)s << 32 and draws = 0.  minigpt4_reset_chat, forks, shifts and snapshot loads
+ * touch neither: the pair belongs to the sampler, as the host generator does (the snapshot format does not carry it: set it again with minigpt4_amd_conversation_seed).
+ * THE ROW the rule sees is the conversation's raw logits row after the transformations above, in their order: logit bias and penalties (steps 1 - 5), then the
+ * conversation's constraint -- only ids allowed in its state take part.  The raw row is never written.
+ * CANDIDATES: the first n_c = min(top_k, participating ids) of them in minigpt4_amd_top_logprobs' order (value descending, equal values -- float equality, -0.0 == +0.0 --
+ * by ascending id), values v_0 >= v_1 >= ...  No participating id: the pick is "</s>" (id 2), flagged stuck, as the greedy constrained pick; a draw is still counted.
+ * THE RULE, fp32 throughout, each operation rounded on its own, no fused multiply-add, sums in candidate order -- llama.cpp's top-k -> top-p -> temperature -> softmax
+ * -> draw, the chain of minigpt4_end_chat with tail-free and typical sampling neutral:
+ *   1. top_p < 1: a_j = expf(v_j - v_0), A = sum a_j, q_j = a_j / A, c += q_j; kept = the first j + 1 with c >= top_p, n_c if there is none.  top_p == 1: kept = n_c.
+ *   2. w_j = v_j / temp for j < kept.
+ *   3. b_j = expf(w_j - w_0), S_j the running sum, S = S_{kept - 1}; the reported probability is p_j = b_j / S.
+ *   4. u = (float)(word >> 8) * 2^-24, t = u * S, pick = the first j with S_j > t; kept - 1 if there is none (u * S can round up to S).
+ *   5. draws += 1, exactly once per decision, also when the conversation then has no room to advance.
+ * minigpt4_amd_end_chat_batch_sampled: one minigpt4_amd_end_chat_batch step decided this way.  Queued rows of the listed conversations are evaluated first; each must then
+ * have current logits.  Then one descriptor upload, the one launch -- it writes each pick straight into the row tokens of the weight pass --, one small copy of the picks
+ * to pinned memory, and the batched step's own pass; the host reads the picks while the pass runs, for histories, constraint states, pieces and ids_out.  No logits row
+ * travels to the host and the host does not synchronise between the decision and the pass.  A conversation that is full and cannot shift is sampled and reported but not
+ * advanced.  Afterwards every conversation that advanced holds its raw logits, greedy and feed token bit for bit as after minigpt4_amd_eval_batch with the picked tokens
+ * forced.  tokens[i] = the borrowed piece of slots[i]'s token, ids_out (may be NULL) its id.  Parity mode: the same kernel decides, one oracle-order single-row pass per
+ * conversation evaluates.
+ * minigpt4_amd_sampled_candidates: the distribution the next such step would draw from: ids_out [n][64] (-1 behind n_cand), probs_out [n][64] = p_j (0 behind kept),
+ * n_cand_out [n], kept_out [n]; each may be NULL.  Only queued rows are evaluated; nothing advances and no draw is counted.
+ * minigpt4_amd_conversation_seed: sets both fields of one conversation; setting draws lets a caller resume a stream where it stopped.
+ * minigpt4_amd_sampling_info: out = {seed, draws, k_sample_rows launches, picks handed to a pass on the device, picks flagged stuck, rows sampled this way}; the last four
+ * count over the context.
+ * Each returns 0, or 1 with "end_chat_batch_sampled: ..." / "sampled_candidates: ..." / "conversation_seed: ..." / "sampling_info: ..." in minigpt4_amd_last_error and
+ * nothing changed: no context, a NULL or empty list, more entries than conversations, a slot out of range or named twice, temp not finite or <= 0, top_k outside
+ * 1 .. min(64, n_vocab), top_p outside (0, 1] (NaN included), tokens NULL; after the queued rows: "... has no current logits".  A pick outside the vocabulary read back
+ * from the device is an error after the fact, reported as minigpt4_amd_end_chat_guided reports it.
+ * What stays as it was: minigpt4_amd_end_chat_batch and _end_chat_batch_top, minigpt4_end_chat(_image), minigpt4_amd_sample and minigpt4_amd_end_chat_guided keep the host
+ * chain and the context's generator; their draws neither read nor move a conversation's (seed, draws).  The buffers of the feature (descriptors, result block, pinned
+ * mirror, an event) are allocated by the first call and freed with the context and by minigpt4_amd_set_conversations: a context that never calls these functions
+ * allocates nothing new and launches nothing new.
+ * Not built: tail-free, typical and mirostat sampling; top_k = 0 or above 64; a top-N report of the sampled step; guided sampling on the device; a mode that redirects the
+ * reference's minigpt4_end_chat here. */
+MINIGPT4_API int minigpt4_amd_end_chat_batch_sampled(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p,
+                                                     int32_t *ids_out);
+MINIGPT4_API int minigpt4_amd_sampled_candidates(struct MiniGPT4Context *ctx, const int32_t *slots, int n, float temp, int32_t top_k, float top_p, int32_t *ids_out,
+                                                 float *probs_out, int32_t *n_cand_out, int32_t *kept_out);
+MINIGPT4_API int minigpt4_amd_conversation_seed(struct MiniGPT4Context *ctx, int slot, uint64_t seed, uint64_t draws);
+MINIGPT4_API int minigpt4_amd_sampling_info(struct MiniGPT4Context *ctx, int slot, uint64_t out[6]);
+
 /* ---- snapshots: save and restore a conversation --------------------------------------------------------------------------------------------------------
  * A conversation leaves its slot, its context or its process as one blob (llama.cpp's llama_copy_state_data / session files / slot save and restore) and comes back bit
  * for bit: a restored conversation continues with the logits and tokens of the uninterrupted one.  The cache rows travel through k_kv_pack / k_kv_unpack -- rows

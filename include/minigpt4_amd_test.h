@@ -211,6 +211,23 @@ MINIGPT4_API int minigpt4_amd_test_constrain_index(const uint8_t *vocab, const i
                                                    uint32_t *index_out, float *ms_out);
 MINIGPT4_API int minigpt4_amd_test_constrain_pick(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
                                                   const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, int32_t *out, float *ms_out);
+/* Device-side sampling (minigpt4_amd.h states the rule).
+ * minigpt4_amd_test_philox, no GPU: Philox4x32-10 of counter[4] under key[2] -> out[4].  1 = a NULL pointer.
+ * minigpt4_amd_test_sample_rule, no GPU: the rule's steps 1 to 4 on values[n_cand] (the candidates in order, 1 .. 64) with the given output word: returns the index of the
+ * picked candidate, p_out[n_cand] = the probabilities (0 from kept on), *kept_out = kept.  -1 = bad arguments (a NULL pointer, n_cand outside 1 .. 64, temp not finite
+ * or <= 0, top_p not > 0).
+ * minigpt4_amd_test_sample_rows: k_sample_rows alone (one launch, one workgroup per row) on host logits [buf_rows][ld].  rows / table as for minigpt4_amd_test_pen_pick
+ * (several rows may name one buffer row); bitmaps = [n_bitmaps][W] allowed-id bitmaps (may be NULL with n_bitmaps 0), bitmap_of_row[n_rows] names each row's, -1 = none;
+ * temp_top_p = [n_rows][2]; top_k[n_rows]; seed_draws = [n_rows][2] 64-bit words; tok_index[n_rows] = an index into a 64-entry row-token array, -1 = the row writes none;
+ * row_tok_io[64]: the array before the launch, replaced by its contents afterwards.  out = [n_rows][133] words: pick, stuck, the Philox word, n_cand, kept, 64 candidate
+ * ids (-1 behind n_cand), 64 fp32 probabilities (0 behind kept).  ms_out (may be NULL): the launch's hipEvent time.  1 = bad arguments, before any device is looked for (as
+ * for _test_pen_pick; a bitmap index outside [-1, n_bitmaps), a row-token index outside [-1, 64), top_k outside 1 .. min(64, n_vocab), temp not finite or <= 0, top_p
+ * outside (0, 1]); 2 = no device; 3 = device error */
+MINIGPT4_API int minigpt4_amd_test_philox(const uint32_t *counter, const uint32_t *key, uint32_t *out);
+MINIGPT4_API int minigpt4_amd_test_sample_rule(const float *values, int n_cand, float temp, float top_p, uint32_t word, float *p_out, int32_t *kept_out);
+MINIGPT4_API int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
+                                               const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k,
+                                               const uint64_t *seed_draws, const int32_t *tok_index, int32_t *row_tok_io, int32_t *out, float *ms_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

@@ -434,6 +434,32 @@ int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32_t handle, in
     if (!ctx) { set_last_error("constraint_mask: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->constraint_mask(handle, state, out, n_words); });
 }
+// ---- sampled batched steps decided on the device, one seed per conversation ---------------------------------------------------------------------------------------
+int minigpt4_amd_end_chat_batch_sampled(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p, int32_t *ids_out) {
+    if (!ctx) { set_last_error("end_chat_batch_sampled: no context"); return 1; }
+    if (!tokens) { set_last_error("end_chat_batch_sampled: tokens is required"); return 1; }
+    Engine *e = E_(ctx);
+    return guarded(1, [&]() -> int {
+        int ids[Engine::MAX_CONVERSATIONS] = {0};
+        if (n > Engine::MAX_CONVERSATIONS) { set_last_error("end_chat_batch_sampled: bad slot list"); return 1; }
+        if (int rc = e->decode_batch_sampled(slots, n, temp, top_k, top_p, ids)) return rc;   // it refuses an n outside 1 .. the conversations before it writes an id
+        for (int i = 0; i < n; i++) { tokens[i] = e->id_to_token(ids[i]); if (ids_out) ids_out[i] = ids[i]; }
+        return 0;
+    });
+}
+int minigpt4_amd_sampled_candidates(struct MiniGPT4Context *ctx, const int32_t *slots, int n, float temp, int32_t top_k, float top_p, int32_t *ids_out, float *probs_out,
+                                    int32_t *n_cand_out, int32_t *kept_out) {
+    if (!ctx) { set_last_error("sampled_candidates: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->sampled_candidates(slots, n, temp, top_k, top_p, ids_out, probs_out, n_cand_out, kept_out); });
+}
+int minigpt4_amd_conversation_seed(struct MiniGPT4Context *ctx, int slot, uint64_t seed, uint64_t draws) {
+    if (!ctx) { set_last_error("conversation_seed: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_conversation_seed(slot, seed, draws); });
+}
+int minigpt4_amd_sampling_info(struct MiniGPT4Context *ctx, int slot, uint64_t out[6]) {
+    if (!ctx) { set_last_error("sampling_info: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->sampling_info(slot, out); });
+}
 // ---- snapshots: save and restore a conversation ----------------------------------------------------------------------------------------------------
 size_t minigpt4_amd_state_size(struct MiniGPT4Context *ctx, int slot) {
     if (!ctx) { set_last_error("state_size: no context"); return 0; }

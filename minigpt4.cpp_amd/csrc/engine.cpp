@@ -96,7 +96,7 @@ Engine::~Engine() {
                     pen_d_, pen_h_, pen_out_d_, pen_out_h_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
                     guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_d_, con_h_, con_out_d_, con_out_h_, con_row_h_,
                     state_d_[0], state_d_[1], state_h_[0], state_h_[1], state_sum_d_, state_sum_h_, state_cs_, state_ev_kernel_[0], state_ev_kernel_[1], state_ev_copy_[0],
-                    state_ev_copy_[1]);
+                    state_ev_copy_[1], smp_d_, smp_h_, smp_out_d_, smp_out_h_, smp_ev_);
         for (Constraint &c : con_) c.dev.abandon();
         return;
     }
@@ -189,6 +189,7 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     set_matvec_tuning(0, 0, prop.multiProcessorCount);
     if (const char *ns = getenv("MINIGPT4_CONVERSATIONS")) conv_.assign((size_t)std::max(1, std::min(MAX_CONVERSATIONS, atoi(ns))), Conversation{});
     sampler_.seed(seed);
+    smp_load_seed_ = (uint32_t)seed; smp_reseed();
     if (const char *tf = getenv("MINIGPT4_PARITY_TRACE")) { if (*tf) trace_file_ = fopen(tf, "wb"); }
     // oracle-order fp32 accumulation (forward_ref): bit-identical to the CPU oracle, slow
     parity_ = trace_file_ || (getenv("MINIGPT4_PARITY") && atoi(getenv("MINIGPT4_PARITY")));
@@ -1611,6 +1612,7 @@ int Engine::set_conversations(int n) {
     release_buffers();
     beam_free();
     guide_free();
+    smp_free(); smp_reseed();
     conv_.assign((size_t)n, Conversation{});
     std::fill(con_handle_, con_handle_ + MAX_CONVERSATIONS, 0); std::fill(con_state_, con_state_ + MAX_CONVERSATIONS, 0); con_assigned_ = 0;   // the compiled constraints stay
     cur_ = 0;
@@ -2156,6 +2158,148 @@ void Engine::con_pick(const int *slots, int n, int *ids) {
         con_walk(slots[map[r]], id);
     }
     con_info_.launches++;
+}
+// ---- sampled batched steps decided on the device (engine.hpp, sampling.hpp) ----
+void Engine::smp_alloc() {
+    if (smp_d_) return;
+    const size_t stage = SMP_HEAD + (size_t)MAX_CONVERSATIONS * PEN_TABLE_MAX * sizeof(PenEntry), res = (size_t)MAX_CONVERSATIONS * sizeof(SampleOut);
+    DevPtr<uint8_t> d(stage); PinPtr<uint8_t> h(stage); DevPtr<SampleOut> out_d(res); PinPtr<SampleOut> out_h(res); OwnedEvent ev(0);   // all five or none
+    smp_d_ = std::move(d); smp_h_ = std::move(h); smp_out_d_ = std::move(out_d); smp_out_h_ = std::move(out_h); smp_ev_ = std::move(ev);
+}
+int Engine::set_conversation_seed(int slot, uint64_t seed, uint64_t draws) {
+    if (slot < 0 || slot >= (int)conv_.size()) { set_last_error("conversation_seed: conversation index out of range"); return 1; }
+    smp_seed_[slot] = seed; smp_draws_[slot] = draws;
+    return 0;
+}
+int Engine::sampling_info(int slot, uint64_t out[6]) const {
+    if (!out || slot < 0 || slot >= (int)conv_.size()) { set_last_error(out ? "sampling_info: conversation index out of range" : "sampling_info: no output array"); return 1; }
+    out[0] = smp_seed_[slot]; out[1] = smp_draws_[slot]; out[2] = smp_info_.launches; out[3] = smp_info_.handed; out[4] = smp_info_.stuck; out[5] = smp_info_.rows;
+    return 0;
+}
+int Engine::smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p) {
+    auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
+    const int bad = check_slots(slots, n);
+    if (bad == 1) return refuse("bad slot list");
+    if (bad) return refuse("conversations must be distinct and in range");
+    if (!std::isfinite(temp) || !(temp > 0.0f)) return refuse("temp must be finite and > 0");
+    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, (int)llm_.n_vocab)) return refuse("top_k outside 1 .. min(64, n_vocab)");
+    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return refuse("top_p outside (0, 1]");
+    if (weights_missing()) return refuse(last_error());
+    auto no_logits = [&]() -> int {
+        for (int i = 0; i < n; i++) { const Conversation &cv = conv_[(size_t)slots[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return slots[i]; }
+        return -1;
+    };
+    int none = no_logits();                                                   // nothing queued and nothing evaluated: known before anything runs
+    if (none < 0) {
+        const SelectScope restore(this);
+        for (int i = 0; i < n; i++) { cur_ = slots[i]; if (flush()) return refuse("the queued rows could not be evaluated: " + last_error()); }   // as decode_batch: one pass each
+        none = no_logits();
+    }
+    if (none >= 0) return refuse("conversation " + std::to_string(none) + " has no current logits");
+    return 0;
+}
+size_t Engine::smp_stage(const int *slots, int n, float temp, int top_k, float top_p) {
+    smp_alloc();
+    SampleRow *rows = smp_h_.as<SampleRow>(); PenEntry *ent = reinterpret_cast<PenEntry *>(smp_h_ + SMP_HEAD);
+    const int W = constraint_words((int)llm_.n_vocab);
+    std::vector<PenEntry> tab;
+    size_t off = 0;
+    for (int i = 0; i < n; i++) {
+        const int slot = slots[i], h = con_handle_[slot];
+        pen_build_row(conv_[(size_t)slot], slot, off, &rows[i].pen, tab);    // the identity included: n = 0, no flags
+        rows[i].allowed = h ? con_[h - 1].index + (size_t)con_state_[slot] * W : nullptr;
+        rows[i].temp = temp; rows[i].top_p = top_p; rows[i].top_k = top_k; rows[i].tok_index = -1;
+        rows[i].seed = smp_seed_[slot]; rows[i].draws = smp_draws_[slot];
+        std::copy(tab.begin(), tab.end(), ent + off);
+        off += tab.size();
+    }
+    return off;
+}
+bool Engine::smp_launch(int n, size_t n_ent, bool hand) {
+    const int V = (int)llm_.n_vocab;
+    HIP_CHECK(hipMemcpyAsync(smp_d_, smp_h_, SMP_HEAD + n_ent * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
+    if (!launch_sample_rows(logits_, V, V, n, smp_d_.as<const SampleRow>(), reinterpret_cast<const PenEntry *>(smp_d_ + SMP_HEAD), smp_out_d_, hand ? d_btok_ : nullptr, stream_)) return false;
+    HIP_CHECK(hipMemcpyAsync(smp_out_h_, smp_out_d_, (size_t)n * sizeof(SampleOut), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipEventRecord(smp_ev_, stream_));
+    smp_info_.launches++;
+    return true;
+}
+int Engine::sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out) {
+    if (smp_prepare("sampled_candidates", slots, n, temp, top_k, top_p)) return 1;
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; smp_h_ feeds no earlier copy
+    const size_t n_ent = smp_stage(slots, n, temp, top_k, top_p);
+    if (!smp_launch(n, n_ent, /*hand=*/false)) { set_last_error("sampled_candidates: " + last_error()); return 1; }
+    HIP_CHECK(hipEventSynchronize(smp_ev_));
+    for (int i = 0; i < n; i++) {
+        const SampleOut &o = smp_out_h_[i];
+        if (ids_out) memcpy(ids_out + (size_t)i * SAMPLE_MAX, o.ids, sizeof(o.ids));
+        if (probs_out) memcpy(probs_out + (size_t)i * SAMPLE_MAX, o.p, sizeof(o.p));
+        if (n_cand_out) n_cand_out[i] = o.n_cand;
+        if (kept_out) kept_out[i] = o.kept;
+    }
+    return 0;
+}
+int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out) {
+    auto refuse = [](const std::string &what) { set_last_error("end_chat_batch_sampled: " + what); return 1; };
+    if (!ids_out) return refuse("ids_out is required");
+    if (smp_prepare("end_chat_batch_sampled", slots, n, temp, top_k, top_p)) return 1;
+    const SelectScope restore(this);
+    const int V = (int)llm_.n_vocab;
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_ and smp_h_ feed no earlier copy
+    // 1. the descriptors, from each history as a sample sees it: before any shift
+    const size_t n_ent = smp_stage(slots, n, temp, top_k, top_p);
+    SampleRow *rows = smp_h_.as<SampleRow>();
+    // 2. room, and the pass's rows: a conversation that is full and cannot shift is sampled and reported, not advanced
+    int B = 0, row_of[MAX_CONVERSATIONS];
+    for (int i = 0; i < n; i++) {
+        Conversation &cv = conv_[(size_t)slots[i]];
+        cur_ = slots[i]; row_of[i] = -1;
+        if (cv.n_past + 1 > n_ctx_ && make_room(1)) continue;
+        row_of[i] = B; stage_row(B++, 0, slots[i], cv.n_committed);
+        if (!parity_) rows[i].tok_index = row_of[i];
+    }
+    const bool hand = B > 0 && !parity_;
+    if (hand) step_begin(B);
+    // 3. the decision: one launch for all listed conversations; the picks of those that advance go straight into the pass's row tokens
+    if (!smp_launch(n, n_ent, hand)) return refuse(last_error());
+    smp_info_.rows += (uint64_t)n; smp_info_.handed += hand ? (uint64_t)B : 0;
+    // the block from pinned memory; false: an id outside the vocabulary (the kernel writes none; a block that never arrived), entered as 0
+    auto take_picks = [&]() -> bool {
+        bool sane = true;
+        for (int i = 0; i < n; i++) {
+            ids_out[i] = smp_out_h_[i].pick;
+            if (ids_out[i] < 0 || ids_out[i] >= V) { sane = false; ids_out[i] = 0; }
+        }
+        return sane;
+    };
+    // the sampler's own state follows every decision, whether or not the conversation advances
+    auto sampler_state = [&] {
+        for (int i = 0; i < n; i++) {
+            smp_draws_[slots[i]] += 1;
+            if (smp_out_h_[i].stuck == 1) smp_info_.stuck++;
+            if (con_handle_[slots[i]]) con_walk(slots[i], ids_out[i]);
+        }
+    };
+    auto bad_pick = [] { return HipError{hipErrorUnknown, "end_chat_batch_sampled: the device reported an id outside the vocabulary", __FILE__, __LINE__}; };
+    if (!hand) {                                                             // parity mode, or nobody advances: the picks first
+        HIP_CHECK(hipEventSynchronize(smp_ev_));
+        if (!take_picks()) throw bad_pick();                                 // nothing has been launched for these picks yet
+        sampler_state();
+        if (!B) return 0;
+        for (int i = 0; i < n; i++) if (row_of[i] >= 0) staged_token(row_of[i]) = ids_out[i];
+        if (step_parity(B)) return 1;
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        return 0;
+    }
+    // 4. the weight pass: the batched step's own.  It advances the device state whatever the block says: the host's book-keeping follows it before a bad block is reported
+    step_launch(B);
+    HIP_CHECK(hipEventSynchronize(smp_ev_));
+    const bool sane = take_picks();
+    sampler_state();
+    for (int i = 0; i < n; i++) if (row_of[i] >= 0) commit_rows(slots[i], &ids_out[i], 1, /*past=*/true);
+    HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+    if (!sane) throw bad_pick();
+    return 0;
 }
 int Engine::token_history(int *out, int cap) {
     if (flush()) return -1;

@@ -244,6 +244,22 @@ public:
     int constraint_info(int slot, int out[8]) const;                       // {handle, state, accepting, n_states, pick launches, host rows, stuck picks, index launches}
     int constraint_mask(int handle, int state, uint32_t *out, int n_words);   // the device index row of (handle, state)
 
+    // ---- sampled batched steps decided on the device (sampling.hpp: the generator and the rule; minigpt4_amd.h: the whole rule).  Every conversation holds a 64-bit seed and
+    // a 64-bit count of draws (after init and set_conversations: seed = (uint32)load seed | slot << 32, draws = 0; reset, fork, shift and snapshot loads touch neither: the pair
+    // belongs to the sampler, as the host generator does).  decode_batch_sampled is one decode_batch step whose tokens k_sample_rows decides: queued rows of the listed
+    // conversations first (one flush each, as decode_batch), then one descriptor upload (SampleRow per conversation + the penalty tables pen_build_row builds), ONE launch
+    // over the listed logits_ rows -- a pick goes straight into d_btok_ for every conversation that advances --, one copy of the result block to pinned memory + an event,
+    // the batched step's own pass (step_begin / step_launch).  The host awaits the event while the pass runs, then does the book-keeping: histories, con_walk, draws += 1 per
+    // listed conversation (a full one that cannot shift included: sampled, reported, not advanced).  No logits row travels to the host; no synchronise between decision and
+    // pass.  Parity mode: the same kernel decides, the picks are awaited first, step_parity evaluates.  sampled_candidates reports the distribution the next step would draw
+    // from (ids [n][64] with -1 behind n_cand, probabilities with 0 behind it) and moves nothing.  1 + last_error "end_chat_batch_sampled: ..." / "sampled_candidates: ..." /
+    // "conversation_seed: ..." / "sampling_info: ..." and nothing changed on a refusal (a bad slot list, temp not finite or <= 0, top_k outside 1 .. min(64, n_vocab), top_p
+    // outside (0, 1]; after the queued rows: a conversation without current logits).  The host chain and its mt19937 are untouched by all of this.  Buffers: first call;
+    // freed with the context and by set_conversations.
+    int decode_batch_sampled(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out);
+    int sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out);
+    int set_conversation_seed(int slot, uint64_t seed, uint64_t draws);
+    int sampling_info(int slot, uint64_t out[6]) const;                    // {seed, draws, k_sample_rows launches, picks handed to a pass on the device, stuck picks, rows sampled}
     // ---- snapshots (state.hpp: the format; minigpt4_amd.h: the rules).  A conversation leaves its slot, its context or its process as one checksummed blob and comes back
     // bit for bit: cache rows [0, n_rows), token history, logits row, greedy / feed token, penalty parameters and logit bias.  Not in a snapshot: the sampler's generator and
     // mirostat state (context-level), the constraint handle and state (handles are per context), queued rows (a save evaluates them first), the prefix store.
@@ -605,6 +621,23 @@ private:
     StateInfo state_info_;
     void state_alloc(size_t block_bytes);              // staging for blocks of that size (all or nothing; grows, never shrinks)
     int state_header(int slot, StateHeader &h, StateLayout &l) const;   // what a save of `slot` would write now (n_rows = n_past); 0, or 1: the layout refused
+    // device-side sampling.  Per conversation (arrays here, not in Conversation: that struct keeps its layout): seed and draws.  Lazy, first call: the staging
+    // ([MAX_CONVERSATIONS] SampleRow, then the penalty tables: device and pinned), the result block ([MAX_CONVERSATIONS] SampleOut) and its pinned mirror, the event the
+    // block is awaited on
+    uint64_t smp_seed_[MAX_CONVERSATIONS] = {0}, smp_draws_[MAX_CONVERSATIONS] = {0}; uint32_t smp_load_seed_ = 0;
+    struct SmpInfo { uint64_t launches = 0, handed = 0, stuck = 0, rows = 0; } smp_info_;
+    DevPtr<uint8_t> smp_d_; PinPtr<uint8_t> smp_h_; DevPtr<SampleOut> smp_out_d_; PinPtr<SampleOut> smp_out_h_; OwnedEvent smp_ev_;
+    static constexpr size_t SMP_HEAD = MAX_CONVERSATIONS * sizeof(SampleRow);
+    void smp_alloc();
+    void smp_free() { reset_all(smp_d_, smp_h_, smp_out_d_, smp_out_h_, smp_ev_); }
+    void smp_reseed() { for (int s = 0; s < MAX_CONVERSATIONS; s++) { smp_seed_[s] = (uint64_t)smp_load_seed_ | (uint64_t)s << 32; smp_draws_[s] = 0; } }
+    // the checks and the queued rows of both entry points; 0, or 1 with last_error "<name>: ..."
+    int smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p);
+    // the listed conversations' descriptors into the pinned staging (row-token index -1), from each history as a sample sees it; the table entries staged
+    size_t smp_stage(const int *slots, int n, float temp, int top_k, float top_p);
+    // n staged descriptors with n_ent entries: the upload, the launch (hand: picks go to d_btok_ at the descriptors' row-token indices), the result block's copy back and
+    // the event queued.  false: the launch was refused (last_error)
+    bool smp_launch(int n, size_t n_ent, bool hand);
 };
 
 int device_count_noexcept();

@@ -6,6 +6,7 @@
 #include "penalty.hpp"
 #include "beam.hpp"
 #include "constraint.hpp"
+#include "sampling.hpp"
 
 namespace mg4 {
 
@@ -249,6 +250,14 @@ bool launch_constrain_pick(const float *logits, int ld, int n_vocab, int n_rows,
 constexpr int GUIDE_MAX = 32;                          // pairs per launch = Engine::MAX_CONVERSATIONS / 2
 struct GuidePair { int pos_row, neg_row; float scale; int pos_tok, neg_tok, pad[3]; };   // 8 words
 bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, const GuidePair *pairs, float *mixed, int *pick, float *pick_val, int *row_tok, hipStream_t s);
+// sampled decode step (sampling.hpp: the generator and the rule), one workgroup per entry of `rows` (device): the first min(top_k, participating ids) ids of logits row
+// rows[r].pen.row after the transformation rows[r].pen / table describe (as for launch_pen_pick) among the ids set in rows[r].allowed (as for launch_constrain_pick; null:
+// every id), in launch_topn_rows' order; top-p, temperature and softmax over them; one draw with word 0 of Philox4x32-10(seed, draws).  out[r] = pick, stuck flag, word,
+// n_cand, kept, ids, probabilities; row_tok (may be null): row_tok[rows[r].tok_index] = pick where the index is >= 0.  The logits are not written.  top_k is clamped to
+// 1 .. SAMPLE_MAX; temp > 0 and 0 < top_p are the caller's to check.  false + last_error: a null array, n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose two bitmaps
+// and the kernel's 12 KB do not fit 64 KB of LDS.
+struct SampleRow { PenRow pen; const unsigned *allowed; float temp, top_p; int top_k, tok_index; unsigned long long seed, draws; };   // 18 words
+bool launch_sample_rows(const float *logits, int ld, int n_vocab, int n_rows, const SampleRow *rows, const PenEntry *table, SampleOut *out, int *row_tok, hipStream_t s);
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)

@@ -3370,6 +3370,159 @@ bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, co
     hipLaunchKernelGGL(k_guide_rows, dim3((unsigned)n_pairs), dim3(256), 0, s, logits, ld, n_vocab, pairs, mixed, pick, pick_val, row_tok);
     return true;
 }
+// Sampled decode step (Engine::decode_batch_sampled / sampled_candidates; sampling.hpp holds the generator and the rule's arithmetic, shared with the host), one workgroup
+// of 256 per listed conversation, one launch for all of them.  rows[r] names the logits row, the conversation's penalty table and factors (as k_pen_pick takes them), the
+// allowed bitmap of its constraint state (as k_constrain_pick takes it; null: every id), temp / top_k / top_p, the generator's (seed, draws) and the entry of the weight
+// pass's row tokens that takes the pick (-1: none).  The row the rule sees -- bias and penalties, then the constraint -- is never materialised: table ids are marked in an
+// LDS bitmap and skipped by the row sweeps (row_span / row_sweep), a loop over the table feeds their pen_value results into the same histograms and lists, an id whose
+// allowed bit is clear is skipped everywhere.  The selection is k_topn_rows': the same order-preserving key (topn_key), the same three histogram levels (11 + 11 + 10 bits)
+// for the key T of the k-th participating id (k = min(top_k, participating ids)), the same collecting sweep (keys above T: fewer than k; keys equal to T: the first 192
+// that arrive), the same id-order scan when more than 192 keys equal T (a marked id's value is looked up in the table there), the same counting placement.  Thread 0 then
+// runs sample_rule over the <= 64 candidates in LDS and draws with word 0 of Philox4x32-10(seed, draws).  out[r]: pick, stuck flag, the word, n_cand, kept, the candidate
+// ids (-1 behind n_cand) and probabilities (0 behind kept); the pick also goes into row_tok[tok_index] when that index is >= 0 (k_guide_rows' hand-over).  No id
+// participates: pick = CONSTRAINT_EOS, stuck = 1, n_cand = kept = 0.  Table ids outside [0, n_vocab) are ignored; the ids of one table are distinct.  Logits are finite
+// (-infinity through a bias is ordered like any value; NaN: unspecified).  The logits are read in place and never written; nothing beyond n_vocab floats of a row is read.
+// No spinning, no flags between workgroups, no global atomics; every loop is bounded by n_vocab or by the table length.
+// LDS: 12 KB static (8 KB histogram, 3 KB candidate lists, the ordered candidates) + dynamic 2 * constraint_words(n_vocab) bitmap words (8 KB at 32 001 ids).
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 51 VGPRs, 89 SGPRs, no scratch, 12080 bytes of static LDS, occupancy 8 waves per SIMD.
+__global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ logits, int ld, int n_vocab, const SampleRow *__restrict__ rows, const PenEntry *__restrict__ table,
+                                                     SampleOut *__restrict__ out, int *__restrict__ row_tok) {
+    constexpr int GT = SAMPLE_MAX, TIES = 256 - SAMPLE_MAX;
+    extern __shared__ __attribute__((aligned(16))) unsigned smp_lds[];
+    __shared__ unsigned hist[2048], sw[4], sres[2], ckey[256];
+    __shared__ int cid[256], cnt[2], s_id[SAMPLE_MAX], s_res[2];
+    __shared__ float cval[256], s_val[SAMPLE_MAX], s_p[SAMPLE_MAX];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const SampleRow sr = rows[r];
+    const PenRow pr = sr.pen;
+    const int words = constraint_words(n_vocab);
+    unsigned *allow = smp_lds, *marked = smp_lds + words;
+    const float *x = logits + (size_t)pr.row * ld;
+    for (int i = tid; i < words; i += 256) { allow[i] = sr.allowed ? sr.allowed[i] : 0xFFFFFFFFu; marked[i] = 0u; }
+    if (tid < 2) cnt[tid] = 0;
+    for (int i = tid; i < 2048; i += 256) hist[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < pr.n; i += 256) { const int id = table[(size_t)pr.off + i].id; if (id >= 0 && id < n_vocab) atomicOr(&marked[id >> 5], 1u << (id & 31)); }
+    __syncthreads();
+    const RowSpan sp = row_span(x, n_vocab);
+    auto entry_value = [&](const PenEntry &e) { return pen_value(x[e.id], e.id, e.count, e.has_bias, e.bias, pr.flags, pr.repeat_penalty, pr.alpha_frequency, pr.alpha_presence); };
+    // f(value, id) for every participating id of the transformed row: the unmarked allowed ids from the row, the allowed table ids through pen_value
+    auto each = [&](auto f) {
+        row_sweep(sp, tid, [&](float v, int i) { if (((allow[i >> 5] & ~marked[i >> 5]) >> (i & 31)) & 1u) f(v, i); });
+        for (int i = tid; i < pr.n; i += 256) {
+            const PenEntry e = table[(size_t)pr.off + i];
+            if (e.id < 0 || e.id >= n_vocab || !((allow[e.id >> 5] >> (e.id & 31)) & 1u)) continue;
+            f(entry_value(e), e.id);
+        }
+    };
+    // level 1, and the number of participating ids
+    unsigned mine = 0;
+    each([&](float v, int) { mine++; topn_hist_add(hist, true, topn_key(v) >> 21, lane); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += (unsigned)__shfl_xor((int)mine, o);
+    if (lane == 0) sw[tid >> 6] = mine;
+    __syncthreads();
+    const unsigned total = sw[0] + sw[1] + sw[2] + sw[3];
+    const uint32_t word = sample_word(sr.seed, sr.draws);
+    __syncthreads();                                                          // sw is written again by topn_select
+    if (total == 0) {                                                         // (uniform) nothing takes part: k_constrain_pick's answer
+        if (tid < SAMPLE_MAX) { out[r].ids[tid] = -1; out[r].p[tid] = 0.0f; }
+        if (tid == 0) {
+            out[r].pick = CONSTRAINT_EOS; out[r].stuck = 1; out[r].word = word; out[r].n_cand = 0; out[r].kept = 0;
+            if (row_tok && sr.tok_index >= 0) row_tok[sr.tok_index] = CONSTRAINT_EOS < n_vocab ? CONSTRAINT_EOS : 0;
+        }
+        return;
+    }
+    const int k = (int)min((unsigned)max(min(sr.top_k, SAMPLE_MAX), 1), total);
+    unsigned b1, b2, b3, a1, a2, a3;
+    topn_select(hist, 8, (unsigned)k, tid, sw, sres, b1, a1);
+    for (int i = tid; i < 2048; i += 256) hist[i] = 0;
+    __syncthreads();
+    each([&](float v, int) { const unsigned key = topn_key(v); topn_hist_add(hist, (key >> 21) == b1, (key >> 10) & 2047u, lane); });
+    __syncthreads();
+    topn_select(hist, 8, (unsigned)k - a1, tid, sw, sres, b2, a2);
+    const unsigned p2 = (b1 << 11) | b2;
+    for (int i = tid; i < 1024; i += 256) hist[i] = 0;
+    __syncthreads();
+    each([&](float v, int) { const unsigned key = topn_key(v); topn_hist_add(hist, (key >> 10) == p2, key & 1023u, lane); });
+    __syncthreads();
+    topn_select(hist, 4, (unsigned)k - a1 - a2, tid, sw, sres, b3, a3);
+    const unsigned T = (p2 << 10) | b3;
+    const int n_gt = (int)(a1 + a2 + a3), need = k - n_gt;                    // n_gt < k keys lie above T, at least `need` >= 1 equal it
+    // the collecting sweep
+    each([&](float v, int i) {
+        const unsigned key = topn_key(v);
+        if (key > T) {
+            const int p = atomicAdd(&cnt[0], 1);
+            if (p < GT) { ckey[p] = key; cid[p] = i; cval[p] = v; }
+        } else if (key == T) {
+            const unsigned long long m = __ballot(1);
+            const int leader = __ffsll((long long)m) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&cnt[1], (int)__popcll(m));
+            const int p = __shfl(base, leader) + (int)__popcll(m & ((1ull << lane) - 1ull));
+            if (p < TIES) { ckey[GT + p] = key; cid[GT + p] = i; cval[GT + p] = v; }
+        }
+    });
+    __syncthreads();
+    int n_tie = cnt[1];
+    if (n_tie > TIES) {   // (uniform) too many keys equal T to have been listed: the lowest `need` ids among them, 1024 ids per step, in id order
+        int taken = 0;
+        for (int base = 0; base < n_vocab && taken < need; base += 1024) {
+            const int i0 = base + 4 * tid;
+            unsigned m4 = 0; float v4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int i = i0 + j;
+                if (i >= n_vocab || !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
+                float v = x[i];
+                if ((marked[i >> 5] >> (i & 31)) & 1u)                        // a table id: its entry's value (the ids of a table are distinct)
+                    for (int e = 0; e < pr.n; e++) { const PenEntry pe = table[(size_t)pr.off + e]; if (pe.id == i) { v = entry_value(pe); break; } }
+                if (topn_key(v) == T) { m4 |= 1u << j; v4[j] = v; }
+            }
+            const unsigned c = (unsigned)__popc(m4), inc = topn_wave_scan(c, lane);
+            if (lane == 63) sw[tid >> 6] = inc;
+            __syncthreads();
+            int at = taken + (int)(inc - c);
+            for (int w = 0; w < (tid >> 6); w++) at += (int)sw[w];
+#pragma unroll
+            for (int j = 0; j < 4; j++) if ((m4 >> j) & 1u) { if (at < need) { ckey[GT + at] = T; cid[GT + at] = i0 + j; cval[GT + at] = v4[j]; } at++; }
+            taken += (int)(sw[0] + sw[1] + sw[2] + sw[3]);
+            __syncthreads();
+        }
+        n_tie = need;
+    }
+    __syncthreads();
+    // placement: a key above T goes behind the keys above it (equal ones by id); a key equal to T behind all of those and the lower ids of its own kind
+    const bool is_gt = tid < n_gt, is_tie = tid >= GT && tid < GT + n_tie;
+    if (is_gt || is_tie) {
+        const unsigned mk = ckey[tid]; const int mi = cid[tid];
+        int pos = is_gt ? 0 : n_gt;
+        if (is_gt) { for (int c = 0; c < n_gt; c++) pos += (ckey[c] > mk || (ckey[c] == mk && cid[c] < mi)) ? 1 : 0; }
+        else for (int c = GT; c < GT + n_tie; c++) pos += cid[c] < mi ? 1 : 0;
+        if (pos < k) { s_id[pos] = mi; s_val[pos] = cval[tid]; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int kept;
+        const int j = sample_rule(s_val, k, sr.temp, sr.top_p, word, s_p, &kept);
+        s_res[0] = s_id[j]; s_res[1] = kept;
+    }
+    __syncthreads();
+    if (tid < SAMPLE_MAX) { out[r].ids[tid] = tid < k ? s_id[tid] : -1; out[r].p[tid] = tid < k ? s_p[tid] : 0.0f; }
+    if (tid == 0) {
+        const int id = s_res[0];
+        out[r].pick = id; out[r].stuck = 0; out[r].word = word; out[r].n_cand = k; out[r].kept = s_res[1];
+        if (row_tok && sr.tok_index >= 0) row_tok[sr.tok_index] = id;
+    }
+}
+bool launch_sample_rows(const float *logits, int ld, int n_vocab, int n_rows, const SampleRow *rows, const PenEntry *table, SampleOut *out, int *row_tok, hipStream_t s) {
+    const size_t lds = (size_t)2 * constraint_words(n_vocab) * 4;
+    if (!logits || !rows || !out || n_rows < 1 || n_vocab < 1 || ld < n_vocab || lds + 12 * 1024 + 256 > 64 * 1024) { set_last_error("launch_sample_rows: shape out of range"); return false; }
+    note_kernel("k_sample_rows");
+    hipLaunchKernelGGL(k_sample_rows, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, out, row_tok);
+    return true;
+}
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {
     const int r = threadIdx.x;

@@ -1259,6 +1259,66 @@ int minigpt4_amd_test_guide_rows(const float *logits, int buf_rows, int n_vocab,
         return 0;
     });
 }
+// ---- device-side sampling (sampling.hpp, launch_sample_rows) ----
+int minigpt4_amd_test_philox(const uint32_t *counter, const uint32_t *key, uint32_t *out) {
+    if (!counter || !key || !out) return 1;
+    philox4x32_10(counter, key, out);
+    return 0;
+}
+int minigpt4_amd_test_sample_rule(const float *values, int n_cand, float temp, float top_p, uint32_t word, float *p_out, int32_t *kept_out) {
+    if (!values || !p_out || !kept_out || n_cand < 1 || n_cand > SAMPLE_MAX || !(temp > 0.0f) || !std::isfinite(temp) || !(top_p > 0.0f)) return -1;
+    int kept = 0;
+    const int pick = sample_rule(values, n_cand, temp, top_p, word, p_out, &kept);
+    *kept_out = kept;
+    return pick;
+}
+// k_sample_rows, one launch, on host logits [buf_rows][ld].  Everything that indexes device memory is checked here.
+int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table, const uint32_t *bitmaps,
+                                  int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k, const uint64_t *seed_draws, const int32_t *tok_index,
+                                  int32_t *row_tok_io, int32_t *out, float *ms_out) {
+    static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(SampleRow) == 72 && sizeof(SampleOut) == (5 + 2 * SAMPLE_MAX) * 4, "the hook's word layout");
+    if (!logits || !rows || !bitmap_of_row || !temp_top_p || !top_k || !seed_draws || !tok_index || !row_tok_io || !out || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n_rows < 1 ||
+        n_table < 0 || (n_table > 0 && !table) || n_bitmaps < 0 || (n_bitmaps > 0 && !bitmaps)) return 1;
+    for (int r = 0; r < n_rows; r++) {   // everything that indexes device memory, and the parameters the engine checks
+        const int32_t *w = rows + 8 * (size_t)r;
+        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table || bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps ||
+            tok_index[r] < -1 || tok_index[r] >= 64 || top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
+        const float temp = temp_top_p[2 * (size_t)r], top_p = temp_top_p[2 * (size_t)r + 1];
+        if (!std::isfinite(temp) || !(temp > 0.0f) || !(top_p > 0.0f) || !(top_p <= 1.0f)) return 1;
+        std::vector<int> ids;
+        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)buf_rows * ld, R = (size_t)n_rows, T = (size_t)std::max(n_table, 1), W = (size_t)constraint_words(n_vocab), NB = (size_t)std::max(n_bitmaps, 1);
+        DevBuf dl(n * 4), dr(R * sizeof(SampleRow)), dt(T * sizeof(PenEntry)), dout(R * sizeof(SampleOut)), db(NB * W * 4), dtok(64 * 4);
+        std::vector<SampleRow> tab(R);
+        for (size_t r = 0; r < R; r++) {
+            memcpy(&tab[r].pen, rows + 8 * r, sizeof(PenRow));
+            tab[r].allowed = bitmap_of_row[r] < 0 ? nullptr : db.as<unsigned>() + (size_t)bitmap_of_row[r] * W;
+            tab[r].temp = temp_top_p[2 * r]; tab[r].top_p = temp_top_p[2 * r + 1]; tab[r].top_k = top_k[r]; tab[r].tok_index = tok_index[r];
+            tab[r].seed = seed_draws[2 * r]; tab[r].draws = seed_draws[2 * r + 1];
+        }
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, tab.data(), R * sizeof(SampleRow), hipMemcpyHostToDevice));
+        if (n_bitmaps > 0) HIP_CHECK(hipMemcpy(db.p, bitmaps, (size_t)n_bitmaps * W * 4, hipMemcpyHostToDevice));
+        if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dtok.p, row_tok_io, 64 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xFF, R * sizeof(SampleOut)));                              // what the kernel leaves out shows as -1 / NaN
+        Events ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_sample_rows(dl.as<float>(), ld, n_vocab, n_rows, dr.as<SampleRow>(), dt.as<PenEntry>(), dout.as<SampleOut>(), dtok.as<int>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;
+        HIP_CHECK(hipMemcpy(out, dout.p, R * sizeof(SampleOut), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(row_tok_io, dtok.p, 64 * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches
 static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, std::vector<int> &out, int &N, int &t_max) {

@@ -257,6 +257,10 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_constraint_advance.argtypes = [VOID_PTR, I32, INT_PTR, I32]
         L.minigpt4_amd_constraint_info.argtypes = [VOID_PTR, I32, INT_PTR]
         L.minigpt4_amd_constraint_mask.argtypes = [VOID_PTR, I32, I32, P(ctypes.c_uint32), I32]
+        L.minigpt4_amd_end_chat_batch_sampled.argtypes = [VOID_PTR, INT_PTR, I32, P(ctypes.c_char_p), F32, I32, F32, INT_PTR]
+        L.minigpt4_amd_sampled_candidates.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_conversation_seed.argtypes = [VOID_PTR, I32, ctypes.c_uint64, ctypes.c_uint64]
+        L.minigpt4_amd_sampling_info.argtypes = [VOID_PTR, I32, U64P]
         I64P = P(ctypes.c_int64)
         L.minigpt4_amd_state_size.argtypes = [VOID_PTR, I32]
         L.minigpt4_amd_state_size.restype = SIZE_T
@@ -317,6 +321,10 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_constraint_compile.argtypes = [CHAR_PTR, I32, U16P, U32P, I32, INT_PTR, ctypes.c_char_p, SIZE_T]
         L.minigpt4_amd_test_constrain_index.argtypes = [P(ctypes.c_uint8), INT_PTR, I32, U16P, U32P, I32, U32P, FLOAT_PTR]
         L.minigpt4_amd_test_constrain_pick.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, U32P, I32, INT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_philox.argtypes = [U32P, U32P, U32P]
+        L.minigpt4_amd_test_sample_rule.argtypes = [FLOAT_PTR, I32, F32, F32, ctypes.c_uint32, FLOAT_PTR, INT_PTR]
+        L.minigpt4_amd_test_sample_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, U32P, I32, INT_PTR, FLOAT_PTR, INT_PTR, U64P, INT_PTR, INT_PTR, INT_PTR,
+                                                    FLOAT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
@@ -963,6 +971,119 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_constrain_pick rc={rc}: " + self._err())
         return out & ~(1 << 30), (out & (1 << 30)) != 0, float(ms.value)
+
+    # ---- sampled batched steps decided on the device (include/minigpt4_amd.h)
+    SAMPLE_MAX = 64
+
+    @staticmethod
+    def _sampled_args(name: str, slots: Sequence[int], temp, top_k, top_p) -> np.ndarray:
+        """The slot list as an int32 array; ValueError before the library is touched."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        if len(sl) < 1 or len(sl) > 64:
+            raise ValueError(f"{name}: 1 .. 64 conversations")
+        if len(np.unique(sl)) != len(sl) or sl.min() < 0:
+            raise ValueError(f"{name}: conversations must be distinct and in range")
+        t, p = ctypes.c_float(float(temp)).value, ctypes.c_float(float(top_p)).value      # as the fp32 the library takes
+        if not (np.isfinite(t) and t > 0):
+            raise ValueError(f"{name}: temp must be finite and > 0")
+        if int(top_k) != top_k or not 1 <= int(top_k) <= 64:
+            raise ValueError(f"{name}: top_k outside 1 .. 64")
+        if not (0 < p <= 1):
+            raise ValueError(f"{name}: top_p outside (0, 1]")
+        return sl
+
+    def amd_end_chat_batch_sampled(self, ctx, slots: Sequence[int], temp=0.8, top_k=40, top_p=0.9, with_ids: bool = False):
+        """One minigpt4_amd_end_chat_batch step whose tokens are sampled ON THE DEVICE, every conversation from its own (seed, draws) stream, and handed to the weight pass
+        without a host visit.  Returns one piece per conversation; with_ids: (pieces, ids i32 array).  include/minigpt4_amd.h states the rule."""
+        sl = self._sampled_args("end_chat_batch_sampled", slots, temp, top_k, top_p)
+        toks, ids = (ctypes.c_char_p * len(sl))(), np.zeros(len(sl), np.int32)
+        rc = self.library.minigpt4_amd_end_chat_batch_sampled(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), len(sl), toks, float(temp), int(top_k), float(top_p),
+                                                              ids.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError("end_chat_batch_sampled failed: " + self._err())
+        pieces = [(t or b"").decode("utf-8", errors="replace") for t in toks]
+        return (pieces, ids) if with_ids else pieces
+
+    def amd_sampled_candidates(self, ctx, slots: Sequence[int], temp=0.8, top_k=40, top_p=0.9) -> dict:
+        """The distribution the next sampled step would draw from; nothing advances, no draw is counted.  dict(ids i32 [n][64] (-1 behind n_cand), probs f32 [n][64] (0 behind
+        kept), n_cand i32 [n], kept i32 [n])."""
+        sl = self._sampled_args("sampled_candidates", slots, temp, top_k, top_p)
+        n = len(sl)
+        ids, probs, nc, kept = np.zeros((n, 64), np.int32), np.zeros((n, 64), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        rc = self.library.minigpt4_amd_sampled_candidates(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), n, float(temp), int(top_k), float(top_p),
+                                                          ids.ctypes.data_as(INT_PTR), probs.ctypes.data_as(FLOAT_PTR), nc.ctypes.data_as(INT_PTR), kept.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError("sampled_candidates failed: " + self._err())
+        return dict(ids=ids, probs=probs, n_cand=nc, kept=kept)
+
+    def amd_conversation_seed(self, ctx, slot: int, seed: int, draws: int = 0) -> None:
+        """Set a conversation's 64-bit seed and its count of draws (the next draw's Philox counter)."""
+        if not (0 <= int(seed) < 1 << 64 and 0 <= int(draws) < 1 << 64):
+            raise ValueError("conversation_seed: seed and draws are unsigned 64-bit integers")
+        if self.library.minigpt4_amd_conversation_seed(ctx.ptr if ctx is not None else None, int(slot), int(seed), int(draws)):
+            raise RuntimeError("conversation_seed failed: " + self._err())
+
+    def amd_sampling_info(self, ctx, slot: int = 0) -> dict:
+        """dict(seed, draws of the conversation; launches: k_sample_rows launches, handed: picks handed to a pass on the device, stuck: picks without a participating id,
+        rows: rows sampled on the device -- of the context so far)."""
+        o = np.zeros(6, np.uint64)
+        if self.library.minigpt4_amd_sampling_info(ctx.ptr if ctx is not None else None, int(slot), o.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))):
+            raise RuntimeError("sampling_info failed: " + self._err())
+        return dict(zip(("seed", "draws", "launches", "handed", "stuck", "rows"), (int(v) for v in o)))
+
+    def amd_test_philox(self, counter: Sequence[int], key: Sequence[int]) -> np.ndarray:
+        """Philox4x32-10 of counter[4] under key[2] (host hook, no GPU): uint32 [4]."""
+        c, k, o = np.ascontiguousarray(counter, np.uint32), np.ascontiguousarray(key, np.uint32), np.zeros(4, np.uint32)
+        if c.shape != (4,) or k.shape != (2,):
+            raise ValueError("test_philox: counter[4], key[2]")
+        U32P = ctypes.POINTER(ctypes.c_uint32)
+        if self.library.minigpt4_amd_test_philox(c.ctypes.data_as(U32P), k.ctypes.data_as(U32P), o.ctypes.data_as(U32P)):
+            raise RuntimeError("test_philox failed")
+        return o
+
+    def amd_test_sample_rule(self, values, temp: float, top_p: float, word: int) -> dict:
+        """The rule's steps 1 to 4 on the candidate values (in order) with the given Philox word (host hook, no GPU): dict(pick index, kept, p f32 [n])."""
+        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        p, kept = np.zeros(max(len(v), 1), np.float32), I32(0)
+        pick = self.library.minigpt4_amd_test_sample_rule(v.ctypes.data_as(FLOAT_PTR), len(v), float(temp), float(top_p), int(word) & 0xFFFFFFFF, p.ctypes.data_as(FLOAT_PTR),
+                                                          ctypes.byref(kept))
+        if pick < 0:
+            raise ValueError("test_sample_rule: bad arguments")
+        return dict(pick=int(pick), kept=int(kept.value), p=p[:len(v)])
+
+    def amd_test_sample_rows(self, logits: np.ndarray, n_vocab: int, rows: np.ndarray, table: np.ndarray, params, top_k, seed_draws, bitmaps=None, bitmap_of_row=None,
+                             tok_index=None, row_tok: Optional[Sequence[int]] = None) -> dict:
+        """k_sample_rows alone on host logits [buf_rows][ld] (include/minigpt4_amd_test.h): rows / table as amd_test_pen_pick, params [n][2] (temp, top_p), top_k [n],
+        seed_draws [n][2] uint64, bitmaps [k][W] uint32 + bitmap_of_row [n] (-1 / None: no constraint), tok_index [n] into a 64-entry row-token array (-1 / None: none),
+        row_tok its contents before the launch (default: all -7).  dict(pick, stuck, word, n_cand, kept [n]; ids [n][64]; p [n][64]; row_tok [64]; ms)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        rw = np.ascontiguousarray(rows, np.int32).reshape(-1, 8)
+        n = len(rw)
+        tb = np.ascontiguousarray(table, np.int32).reshape(-1, 4)
+        pr = np.ascontiguousarray(params, np.float32).reshape(-1, 2)
+        tk = np.ascontiguousarray(top_k, np.int32).reshape(-1)
+        sd = np.ascontiguousarray(seed_draws, np.uint64).reshape(-1, 2)
+        W = ((int(n_vocab) + 31) // 32 + 3) // 4 * 4
+        bm = np.zeros((0, W), np.uint32) if bitmaps is None else np.ascontiguousarray(bitmaps, np.uint32)
+        assert bm.ndim == 2 and bm.shape[1] == W
+        br = np.full(n, -1, np.int32) if bitmap_of_row is None else np.ascontiguousarray(bitmap_of_row, np.int32).reshape(-1)
+        ti = np.full(n, -1, np.int32) if tok_index is None else np.ascontiguousarray(tok_index, np.int32).reshape(-1)
+        assert len(pr) == n and len(tk) == n and len(sd) == n and len(br) == n and len(ti) == n
+        rt = np.full(64, -7, np.int32) if row_tok is None else np.ascontiguousarray(row_tok, np.int32).copy()
+        assert rt.shape == (64,)
+        out, ms = np.zeros((max(n, 1), 5 + 128), np.int32), ctypes.c_float()
+        U32P = ctypes.POINTER(ctypes.c_uint32)
+        rc = self.library.minigpt4_amd_test_sample_rows(lg.ctypes.data_as(FLOAT_PTR), lg.shape[0], int(n_vocab), lg.shape[1], rw.ctypes.data_as(INT_PTR), n,
+                                                        tb.ctypes.data_as(INT_PTR) if len(tb) else None, len(tb), bm.ctypes.data_as(U32P) if len(bm) else None, len(bm),
+                                                        br.ctypes.data_as(INT_PTR), pr.ctypes.data_as(FLOAT_PTR), tk.ctypes.data_as(INT_PTR),
+                                                        sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ti.ctypes.data_as(INT_PTR), rt.ctypes.data_as(INT_PTR),
+                                                        out.ctypes.data_as(INT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_sample_rows rc={rc}: " + self._err())
+        out = out[:n]
+        return dict(pick=out[:, 0].copy(), stuck=out[:, 1].copy(), word=out[:, 2].copy().view(np.uint32), n_cand=out[:, 3].copy(), kept=out[:, 4].copy(),
+                    ids=out[:, 5:69].copy(), p=np.ascontiguousarray(out[:, 69:133]).view(np.float32), row_tok=rt, ms=float(ms.value))
 
     def amd_token_piece(self, ctx, token_id: int) -> Optional[str]:
         """The text of one token id, as minigpt4_end_chat returns it ("</s>" for id 2); None for an id outside the vocabulary."""

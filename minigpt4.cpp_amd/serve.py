@@ -92,8 +92,14 @@ class ReplicaServer:
     def run(self, requests: Sequence[Request], temp: float = 0.0, top_k: int = 40, top_p: float = 0.9, ignore_eos: bool = False,
             batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
             frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
-            negative_prompt: Optional[str] = None, regex=None, sessions: Optional[Sequence] = None) -> List[str]:
-        """sessions (one hashable id or None per request; the decode loop only -- ValueError with num_beams > 1 or guidance_scale != 1): a request that names a session is
+            negative_prompt: Optional[str] = None, regex=None, sessions: Optional[Sequence] = None, device_sampling: bool = False,
+            seeds: Optional[Sequence[int]] = None) -> List[str]:
+        """device_sampling (the decode loop only, temp > 0): every step is ONE `minigpt4_amd_end_chat_batch_sampled` -- the tokens are sampled on the device (top-k <= 64,
+        top-p, temperature; include/minigpt4_amd.h states the rule) and handed to the weight pass without a host visit, and every request draws from a stream of its own:
+        seeds (one 64-bit integer per request; None: the request's index) is set with `minigpt4_amd_conversation_seed(slot, seed, 0)` when the request takes its slot, so
+        a request's text does not depend on which other requests share its wave or on its slot.  Works with regex, penalties and logit_bias; ValueError together with
+        num_beams > 1, guidance_scale != 1 or logprobs > 0, with temp <= 0, and for seeds without device_sampling or of another length than requests.
+        sessions (one hashable id or None per request; the decode loop only -- ValueError with num_beams > 1 or guidance_scale != 1): a request that names a session is
         parked when its wave ends (`suspend`), so the server holds any number of idle sessions next to its `conversations` slots.  A request whose session is parked
         is a FOLLOW-UP turn: its image must be None, the session is resumed into the wave's slot and the prompt asked with `minigpt4_begin_chat`; the image turn and
         every earlier turn are not evaluated again.  A session may appear once per call.  `drop_session` forgets one.
@@ -131,6 +137,18 @@ class ReplicaServer:
             raise ValueError("guidance_scale != 1 takes two conversations per request")
         if regex is not None and (num_beams > 1 or guided):
             raise ValueError("regex is not available with num_beams > 1 or guidance_scale != 1")
+        if device_sampling:
+            if num_beams > 1 or guided or logprobs > 0:
+                raise ValueError("device_sampling is not available with num_beams > 1, guidance_scale != 1 or logprobs > 0")
+            if not (np.isfinite(temp) and temp > 0):
+                raise ValueError("device_sampling needs temp > 0")
+            if top_k < 1 or top_k > 64 or not (0 < top_p <= 1):
+                raise ValueError("device_sampling needs top_k in 1 .. 64 and top_p in (0, 1]")
+            if seeds is not None and len(seeds) != len(requests):
+                raise ValueError("seeds: one integer per request")
+            seeds = [int(s_) & 0xFFFFFFFFFFFFFFFF for s_ in (range(len(requests)) if seeds is None else seeds)]
+        elif seeds is not None:
+            raise ValueError("seeds needs device_sampling=True")
         if sessions is not None:
             if num_beams > 1 or guided:
                 raise ValueError("sessions is not available with num_beams > 1 or guidance_scale != 1")
@@ -149,7 +167,7 @@ class ReplicaServer:
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
-                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions)
+                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None)
         finally:
             if self._constraint:
                 for slot in range(self.conversations):
@@ -187,7 +205,7 @@ class ReplicaServer:
                 shown += piece
         return shown
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None) -> List[str]:
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         if penalised:
@@ -224,6 +242,8 @@ class ReplicaServer:
                         lib.amd_set_logit_bias(ctx, logit_bias)
                     if self._constraint:
                         lib.amd_set_constraint(ctx, slot, self._constraint)   # (also returns the state to the start)
+                    if seeds is not None:
+                        lib.amd_conversation_seed(ctx, slot, seeds[i], 0)     # the request's own stream, from its first draw
                     if guidance is not None:                  # the guidance conversation: the same question (or the negative prompt) asked without the image
                         lib.amd_select_conversation(ctx, slot + 1)
                         lib.minigpt4_reset_chat(ctx)
@@ -249,6 +269,8 @@ class ReplicaServer:
                                 top=[(lib.amd_token_piece(ctx, int(t)), float(v)) for t, v in zip(step["top_ids"][r], step["top_logprobs"][r])]))
                     elif guidance is not None:
                         pieces = lib.amd_end_chat_guided(ctx, [2 * slot for slot in active], [2 * slot + 1 for slot in active], guidance, temp=temp, top_k=top_k, top_p=top_p)
+                    elif seeds is not None:
+                        pieces = lib.amd_end_chat_batch_sampled(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
                     else:
                         pieces = lib.amd_end_chat_batch(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
                     nxt = []
@@ -292,12 +314,15 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     (file load on rank 0, arena broadcast to the others); pass `device=torch.device("cuda", local_rank)` on GPUs."""
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     mine = D.shard_requests(len(requests), rank, world)
+    if kw.get("seeds") is not None and len(kw["seeds"]) != len(requests):
+        raise ValueError("seeds: one integer per request")
     server = ReplicaServer(vision_path, llm_path, conversations=conversations, rank=rank, world=world, device=kw.get("device"),
                            **{k: v for k, v in kw.items() if k in ("n_ctx", "n_batch", "seed", "library", "verbosity", "prefix_cache")})
     try:
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
                                                                                                 "presence_penalty", "frequency_penalty", "logit_bias", "num_beams",
-                                                                                                "length_penalty", "guidance_scale", "negative_prompt", "regex")})
+                                                                                                "length_penalty", "guidance_scale", "negative_prompt", "regex", "device_sampling")},
+                         **({"seeds": [(kw["seeds"][i] if kw.get("seeds") is not None else i) for i in mine]} if kw.get("device_sampling") or kw.get("seeds") is not None else {}))   # a request's seed follows it to its rank
     finally:
         server.close()
     mapping = dict(zip(mine, out))
