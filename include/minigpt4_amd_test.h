@@ -56,6 +56,41 @@ MINIGPT4_API int minigpt4_amd_test_matvec_predicates(int ggml_type, int64_t n_in
 /* Activation quantisation (optionally after rms_norm with weight w): returns Q8_K and Q8_0 images of x[N][K].
  * q8k: int8[N*K], dk: float[N*K/256], bsums: int16[N*K/16], q80: int8[N*K], d0: float[N*K/32] (fp16-rounded). Any may be NULL. */
 MINIGPT4_API int minigpt4_amd_test_quantize(const float *x, const float *rms_w, int64_t N, int64_t K, int8_t *q8k, float *dk, int16_t *bsums, int8_t *q80, float *d0);
+/* ---- the activation-preparation kernels and the consumers of a deferred split-K combine, one launch each (tests/test_gpu_act_prepare.py).  Common form: 1 = bad arguments,
+ * before any device is looked for; 2 = no device; 3 = HIP error.  An ActQ's thirteen planes, a row of each in elements: q8k int8 [K], dk float [K / 256], bsk int16 [K / 16],
+ * bsq int8 [K / 256 * 16], bs16 fp16 bits [K / 256 * 16], q16 fp16 bits [K], q80 int8 [K], d0 / d1 / s1 float [K / 32], sum0 int32 [K / 32], xh fp16 bits [K], xf float [K].
+ * Every plane is device memory of N + 1 such rows prefilled with 0xFF bytes -- row N is a guard row -- and every non-NULL out pointer receives all N + 1 rows, so a plane
+ * that `mask` does not select comes back as the fill.  mask: any OR of ACT_Q8K 1, ACT_Q80 2, ACT_F16 4, ACT_F32 8.  planes: which optional planes the ActQ carries --
+ * 1 bsq, 2 bs16 (needs bsq), 4 q16; the others are always there. */
+/* ONE launch_rms_quant (launcher 0: second = the norm weight [K], NULL = the rows as they are) or launch_silu_mul_quant (launcher 1: second = b [N][K], NULL = the rows as
+ * they are; silu_table = the 65536 fp16 bit patterns gathered from, NULL = the computed arm) on x [N][K].  sequential_sum: launcher 0's one-thread sum of squares.
+ * Refused: NULL x, N < 1, K < 4, K % 4, K % 256 with ACT_Q8K, K % 32 with ACT_Q80, a mask outside 1 .. 15, planes outside 0 .. 7 or bs16 without bsq, launcher not 0 / 1 */
+MINIGPT4_API int minigpt4_amd_test_prepare(int launcher, const float *x, const float *second, int64_t N, int64_t K, int mask, int planes, int sequential_sum,
+                                           const unsigned short *silu_table, int8_t *q8k, float *dk, int16_t *bsk, int8_t *bsq, unsigned short *bs16, unsigned short *q16,
+                                           int8_t *q80, float *d0, float *d1, float *s1, int32_t *sum0, unsigned short *xh, float *xf);
+/* ONE launch_rms_quant_slabs (launcher 0: a SlabSrc of n = 1, slabs [ks][stride]; residual [N][K] or NULL; in_place != 0: the residual lives in the x_out buffer, as x_ does in
+ * the engine; w [K] the norm weight; x_out [N + 1][K] = residual + slabs comes back with its guard row) or launch_silu_mul_quant_slabs (launcher 1: n = 2, slabs [2][ks][stride],
+ * a = matrix 0's sum, b = matrix 1's; always gathers from silu_table; residual, w and x_out must be NULL).  Element (row, i) of a slab is at row * K + i; the caller fills
+ * the padding behind N * K.  Refused: as above, and ks outside 2 .. 16, stride < N * K, stride % 4, launcher 0 without w or x_out, in_place without residual, launcher 1
+ * without silu_table */
+MINIGPT4_API int minigpt4_amd_test_prepare_slabs(int launcher, const float *slabs, int ks, int64_t stride, const float *residual, int in_place, const float *w, int64_t N, int64_t K,
+                                                 int mask, int planes, const unsigned short *silu_table, float *x_out, int8_t *q8k, float *dk, int16_t *bsk, int8_t *bsq,
+                                                 unsigned short *bs16, unsigned short *q16, int8_t *q80, float *d0, float *d1, float *s1, int32_t *sum0, unsigned short *xh,
+                                                 float *xf);
+/* ONE launch_slab_flush on a SlabSrc of n = 1 .. 3 matrices built from host data.  mks [n] = the matrices' slab counts; slabs = every matrix's slabs back to back
+ * (matrix i: mks[i] x stride floats), a matrix with mks[i] == 1 contributes none.  mixed == 0 (k_mmq2_reduce_set): every count equal and >= 2.  mixed != 0 (one
+ * launch_slab_reduce per split matrix; SlabSrc::ks = mks[0] >= 2): mks[i] == 1 means matrix i is already in place -- its contents are taken from row i of y and must come back
+ * bit for bit.  residual [n][stride], row i added to matrix i when bit i of residual_mask is set (NULL with mask 0).  y [n + 1][stride]: in / out, device rows prefilled with
+ * 0xFF bytes, row n is a guard row.  Refused: a NULL array, n outside 1 .. 3, a count outside 1 .. 16, stride < 4, stride % 4, residual_mask outside the n bits or without
+ * residual */
+MINIGPT4_API int minigpt4_amd_test_slab_flush(int n, int mixed, const int32_t *mks, const float *slabs, int64_t stride, const float *residual, int residual_mask, float *y);
+/* ONE launch_rope_kv_slabs on N rows of ONE conversation at positions pos0 .. pos0 + N - 1, with a slab count per matrix: mks [3] for q | k | v, slabs laid out as for
+ * minigpt4_amd_test_slab_flush with E = n_head * hd, element (row, i) at row * E + i.  mks[2] == 1: v is already in place -- v_in_place [N][E] is its buffer (SlabSrc::mbase[2] =
+ * y[2]) and the slabs hold none for it; otherwise v_in_place must be NULL.  q_out [N + 1][E]: the rotated q, 0xFF-prefilled with a guard row; kc / vc [n_ctx][E] fp16 bit
+ * patterns, zero where nothing was appended (what one side of minigpt4_amd_test_rope_kv_seg returns for one segment of slot 0).  Refused: a NULL array, n_head < 1, hd < 2 or
+ * odd, N < 1, pos0 < 0, pos0 + N > n_ctx, a count outside 2 .. 16 for q | k or 1 .. 16 for v, stride < N * E, stride % 4, v_in_place given or missing against mks[2] */
+MINIGPT4_API int minigpt4_amd_test_rope_kv_slabs(int n_head, int hd, int n_ctx, int N, int pos0, const int32_t *mks, const float *slabs, int64_t stride, const float *v_in_place,
+                                                 float *q_out, uint16_t *kc, uint16_t *vc);
 /* The embedding gather alone (k_get_rows: the per-element decoder of every weight type), ONE launch_get_rows.  raw_table: n_rows rows of K weights as a model file stores
  * them (Q3_K rows are re-encoded as Q6_K first, as the engine's load path does); tokens[N] in [-1, n_rows).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard
  * row; a token of -1 leaves its row at the fill.  1 = bad arguments, before any device is touched (a NULL pointer, a token outside [-1, n_rows), a K that is not a whole

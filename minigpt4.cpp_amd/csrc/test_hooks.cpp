@@ -460,6 +460,159 @@ int minigpt4_amd_test_quantize(const float *x, const float *rms_w, int64_t N, in
     });
 }
 
+}  // extern "C"
+
+// ---- the activation-preparation kernels and the consumers of a deferred split-K combine, one launch each (tests/test_gpu_act_prepare.py) ----
+namespace {
+constexpr int AP_PLANES = 13, AP_MAX_N = 4096, AP_MAX_K = 1 << 16, AP_MAX_KS = 16;
+// An ActQ whose thirteen planes are N + 1 rows of device memory each, prefilled with 0xFF bytes (row N: the guard row).  planes: 1 bsq, 2 bs16, 4 q16 exist.
+struct GuardedAct {
+    ActQ A; std::vector<std::unique_ptr<DevBuf>> keep; size_t bytes[AP_PLANES]; void *dev[AP_PLANES];
+    GuardedAct(size_t N, size_t K, int planes) {
+        const size_t row[AP_PLANES] = {K, K / 256 * 4, K / 16 * 2, K / 256 * 16, K / 256 * 32, K * 2, K, K / 32 * 4, K / 32 * 4, K / 32 * 4, K / 32 * 4, K * 2, K * 4};
+        for (int i = 0; i < AP_PLANES; i++) {
+            bytes[i] = (N + 1) * row[i];
+            keep.emplace_back(new DevBuf(bytes[i] + 256)); dev[i] = keep.back()->p;
+            HIP_CHECK(hipMemset(dev[i], 0xFF, bytes[i] + 256));
+        }
+        A.q8k = (int8_t *)dev[0]; A.dk = (float *)dev[1]; A.bsk = (int16_t *)dev[2];
+        A.bsq = (planes & 1) ? (int8_t *)dev[3] : nullptr; A.bs16 = (planes & 2) ? (__half *)dev[4] : nullptr; A.q16 = (planes & 4) ? (__half *)dev[5] : nullptr;
+        A.q80 = (int8_t *)dev[6]; A.d0 = (float *)dev[7]; A.d1 = (float *)dev[8]; A.s1 = (float *)dev[9]; A.sum0 = (int *)dev[10]; A.xh = (__half *)dev[11]; A.xf = (float *)dev[12];
+    }
+    void copy_back(void *const out[AP_PLANES]) { for (int i = 0; i < AP_PLANES; i++) if (out[i] && bytes[i]) HIP_CHECK(hipMemcpy(out[i], dev[i], bytes[i], hipMemcpyDeviceToHost)); }
+};
+// what every kernel that ends in quant_emit4 needs of (N, K, mask): float4 loads, whole Q8_K / Q8_0 blocks
+bool prepare_shape_ok(int64_t N, int64_t K, int mask, int planes) {
+    if (N < 1 || N > AP_MAX_N || K < 4 || K > AP_MAX_K || K % 4 || mask < 1 || mask > 15 || planes < 0 || planes > 7 || ((planes & 2) && !(planes & 1))) return false;
+    return !((mask & ACT_Q8K) && K % 256) && !((mask & ACT_Q80) && K % 32);
+}
+void ap_upload(DevBuf &d, const float *src, size_t n) { HIP_CHECK(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice)); }
+// slab counts of a SlabSrc's matrices -> in which slab of the back-to-back host array each matrix begins, and how many slabs there are in all; a matrix with count 1 is
+// in place and has no slab, which only the matrices from first_in_place_ok on may be
+bool slab_layout(const int32_t *mks, int n, int first_in_place_ok, size_t begin[3], size_t &total) {
+    total = 0;
+    for (int i = 0; i < n; i++) {
+        if (mks[i] < 1 || mks[i] > AP_MAX_KS || (mks[i] == 1 && i < first_in_place_ok)) return false;
+        begin[i] = total;
+        if (mks[i] > 1) total += (size_t)mks[i];
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int minigpt4_amd_test_prepare(int launcher, const float *x, const float *second, int64_t N, int64_t K, int mask, int planes, int sequential_sum, const unsigned short *silu_table,
+                              int8_t *q8k, float *dk, int16_t *bsk, int8_t *bsq, unsigned short *bs16, unsigned short *q16, int8_t *q80, float *d0, float *d1, float *s1,
+                              int32_t *sum0, unsigned short *xh, float *xf) {
+    if (!x || (launcher != 0 && launcher != 1) || !prepare_shape_ok(N, K, mask, planes)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t nk = (size_t)(N * K), n2 = launcher == 0 ? (size_t)K : nk;
+        DevBuf dx(nk * 4), d2(n2 * 4), dtab(65536 * 2);
+        ap_upload(dx, x, nk);
+        if (second) ap_upload(d2, second, n2);
+        Tables tb;
+        if (silu_table) { HIP_CHECK(hipMemcpy(dtab.p, silu_table, 131072, hipMemcpyHostToDevice)); tb.silu = dtab.as<__half>(); }
+        GuardedAct G((size_t)N, (size_t)K, planes);
+        if (launcher == 0) launch_rms_quant(dx.as<float>(), second ? d2.as<float>() : nullptr, (int)N, (int)K, G.A, mask, nullptr, sequential_sum != 0);
+        else launch_silu_mul_quant(dx.as<float>(), second ? d2.as<float>() : nullptr, (int)N, (int)K, G.A, mask, tb, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        void *const out[AP_PLANES] = {q8k, dk, bsk, bsq, bs16, q16, q80, d0, d1, s1, sum0, xh, xf};
+        G.copy_back(out);
+        return 0;
+    });
+}
+
+int minigpt4_amd_test_prepare_slabs(int launcher, const float *slabs, int ks, int64_t stride, const float *residual, int in_place, const float *w, int64_t N, int64_t K, int mask,
+                                    int planes, const unsigned short *silu_table, float *x_out, int8_t *q8k, float *dk, int16_t *bsk, int8_t *bsq, unsigned short *bs16,
+                                    unsigned short *q16, int8_t *q80, float *d0, float *d1, float *s1, int32_t *sum0, unsigned short *xh, float *xf) {
+    if (!slabs || (launcher != 0 && launcher != 1) || !prepare_shape_ok(N, K, mask, planes) || ks < 2 || ks > AP_MAX_KS || stride < N * K || stride % 4 || stride > ((int64_t)1 << 26)) return 1;
+    if (launcher == 0 ? (!w || !x_out || (in_place && !residual)) : (!silu_table || residual || in_place || w || x_out)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t nk = (size_t)(N * K), gk = nk + (size_t)K, ns = (size_t)(launcher == 0 ? 1 : 2) * (size_t)ks * (size_t)stride;
+        DevBuf ds(ns * 4), dres(nk * 4), dw((size_t)K * 4), dxo(gk * 4), dtab(65536 * 2);
+        ap_upload(ds, slabs, ns);
+        HIP_CHECK(hipMemset(dxo.p, 0xFF, gk * 4));
+        if (residual) ap_upload(in_place ? dxo : dres, residual, nk);
+        if (w) ap_upload(dw, w, (size_t)K);
+        Tables tb;
+        if (silu_table) { HIP_CHECK(hipMemcpy(dtab.p, silu_table, 131072, hipMemcpyHostToDevice)); tb.silu = dtab.as<__half>(); }
+        GuardedAct G((size_t)N, (size_t)K, planes);
+        SlabSrc S; S.ws = ds.as<float>(); S.ks = ks; S.stride = (long long)stride; S.n = launcher == 0 ? 1 : 2;
+        for (int m = 0; m < S.n; m++) { S.mbase[m] = S.ws + (size_t)m * ks * (size_t)stride; S.mks[m] = ks; }
+        if (launcher == 0) {
+            S.y[0] = dxo.as<float>(); S.res[0] = residual ? (in_place ? dxo.as<float>() : dres.as<float>()) : nullptr;
+            launch_rms_quant_slabs(S, dw.as<float>(), (int)N, (int)K, G.A, mask, nullptr);
+        } else launch_silu_mul_quant_slabs(S, (int)N, (int)K, G.A, mask, tb, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        if (x_out) HIP_CHECK(hipMemcpy(x_out, dxo.p, gk * 4, hipMemcpyDeviceToHost));
+        void *const out[AP_PLANES] = {q8k, dk, bsk, bsq, bs16, q16, q80, d0, d1, s1, sum0, xh, xf};
+        G.copy_back(out);
+        return 0;
+    });
+}
+
+int minigpt4_amd_test_slab_flush(int n, int mixed, const int32_t *mks, const float *slabs, int64_t stride, const float *residual, int residual_mask, float *y) {
+    size_t begin[3] = {0, 0, 0}, total = 0;
+    if (!mks || !slabs || !y || n < 1 || n > 3 || stride < 4 || stride % 4 || stride > ((int64_t)1 << 26) || residual_mask < 0 || residual_mask >= (1 << n) || (residual_mask && !residual)) return 1;
+    if (!slab_layout(mks, n, mixed ? 1 : n, begin, total)) return 1;
+    if (!mixed) for (int i = 1; i < n; i++) if (mks[i] != mks[0]) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t st = (size_t)stride, ny = (size_t)(n + 1) * st;
+        DevBuf ds(total * st * 4), dres((size_t)n * st * 4), dy(ny * 4);
+        ap_upload(ds, slabs, total * st);
+        if (residual) ap_upload(dres, residual, (size_t)n * st);
+        HIP_CHECK(hipMemset(dy.p, 0xFF, ny * 4));
+        SlabSrc S; S.ws = ds.as<float>(); S.ks = mks[0]; S.stride = (long long)stride; S.n = n; S.mixed = mixed != 0;
+        for (int i = 0; i < n; i++) {
+            S.y[i] = dy.as<float>() + (size_t)i * st;
+            S.res[i] = (residual_mask >> i & 1) ? dres.as<float>() + (size_t)i * st : nullptr;
+            S.mks[i] = mks[i];
+            if (mks[i] == 1) { S.mbase[i] = S.y[i]; HIP_CHECK(hipMemcpy(S.y[i], y + (size_t)i * st, st * 4, hipMemcpyHostToDevice)); }   // already in place
+            else S.mbase[i] = S.ws + begin[i] * st;
+        }
+        launch_slab_flush(S, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+int minigpt4_amd_test_rope_kv_slabs(int n_head, int hd, int n_ctx, int N, int pos0, const int32_t *mks, const float *slabs, int64_t stride, const float *v_in_place, float *q_out,
+                                    uint16_t *kc, uint16_t *vc) {
+    size_t begin[3] = {0, 0, 0}, total = 0;
+    if (!mks || !slabs || !q_out || !kc || !vc || n_head < 1 || n_head > 256 || hd < 2 || hd > 256 || hd % 2 || N < 1 || N > AP_MAX_N || pos0 < 0 || n_ctx < 1 || n_ctx > (1 << 16) ||
+        (int64_t)pos0 + N > n_ctx || stride < (int64_t)N * n_head * hd || stride % 4 || stride > ((int64_t)1 << 26)) return 1;
+    if (!slab_layout(mks, 3, 2, begin, total) || (mks[2] == 1) != (v_in_place != nullptr)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, NE = (size_t)N * E, st = (size_t)stride, cache = (size_t)n_ctx * E;
+        std::vector<float> c, sn;
+        rope_tables(n_ctx, hd, c, sn);
+        DevBuf dc(c.size() * 4), dsn(sn.size() * 4), ds(total * st * 4), dv(NE * 4), dq((NE + E) * 4), dkc(cache * 2), dvc(cache * 2), dnp(4);
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+        ap_upload(ds, slabs, total * st);
+        if (v_in_place) ap_upload(dv, v_in_place, NE);
+        HIP_CHECK(hipMemcpy(dnp.p, &pos0, 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dq.p, 0xFF, (NE + E) * 4)); HIP_CHECK(hipMemset(dkc.p, 0, cache * 2)); HIP_CHECK(hipMemset(dvc.p, 0, cache * 2));
+        SlabSrc S; S.ws = ds.as<float>(); S.ks = mks[0]; S.stride = (long long)stride; S.n = 3; S.mixed = mks[2] != mks[0];
+        S.y[0] = dq.as<float>(); S.y[2] = dv.as<float>();
+        for (int i = 0; i < 3; i++) { S.mks[i] = mks[i]; S.mbase[i] = mks[i] == 1 ? dv.as<float>() : S.ws + begin[i] * st; }
+        launch_rope_kv_slabs(S, N, n_head, hd, dnp.as<int>(), dc.as<float>(), dsn.as<float>(), dkc.as<__half>(), dvc.as<__half>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(q_out, dq.p, (NE + E) * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc, dkc.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
 // The embedding gather (k_get_rows / dequant_elem) alone: one launch_get_rows over a raw table [n_rows][K] exactly as a model file stores it (Q3_K: re-encoded as Q6_K first,
 // as the engine's load path does).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard row; a token of -1 leaves its row at the fill.
 int minigpt4_amd_test_get_rows(int ggml_type, const void *raw_table, int n_rows, int64_t K, const int32_t *tokens, int N, float *out) {

@@ -285,6 +285,11 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_matvec_issue.argtypes = L.minigpt4_amd_test_matvec.argtypes[:11] + [I32, FLOAT_PTR, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_matvec_waves.argtypes = []
         L.minigpt4_amd_test_quantize.argtypes = [FLOAT_PTR, FLOAT_PTR, ctypes.c_int64, ctypes.c_int64, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR, VOID_PTR]
+        planes13 = [VOID_PTR] * 13
+        L.minigpt4_amd_test_prepare.argtypes = [I32, FLOAT_PTR, FLOAT_PTR, ctypes.c_int64, ctypes.c_int64, I32, I32, I32, VOID_PTR] + planes13
+        L.minigpt4_amd_test_prepare_slabs.argtypes = [I32, FLOAT_PTR, I32, ctypes.c_int64, FLOAT_PTR, I32, FLOAT_PTR, ctypes.c_int64, ctypes.c_int64, I32, I32, VOID_PTR, FLOAT_PTR] + planes13
+        L.minigpt4_amd_test_slab_flush.argtypes = [I32, I32, INT_PTR, FLOAT_PTR, ctypes.c_int64, FLOAT_PTR, I32, FLOAT_PTR]
+        L.minigpt4_amd_test_rope_kv_slabs.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, ctypes.c_int64, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
         L.minigpt4_amd_test_gemm_f16.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_gemm_f16_skinny.argtypes = L.minigpt4_amd_test_gemm_f16.argtypes
         L.minigpt4_amd_test_gemm_f16_ex.argtypes = [FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, I32, I32, I32, I32, VOID_PTR, FLOAT_PTR]
@@ -1751,6 +1756,75 @@ class MiniGPT4SharedLibrary:
         out_h = self._hook_out((rows + 1, n), np.uint16) if want_out_h else None
         rc = self.library.minigpt4_amd_test_lin_epilogue(self._f32p(y), self._f32p(bias), self._f32p(residual), self._vp(tab), rows, n, self._f32p(out), self._vp(out_h))
         return rc, out, out_h
+
+    # ---- the activation-preparation kernels and the consumers of a deferred split-K combine (include/minigpt4_amd_test.h).  Same form as the image encoder's hooks above: the
+    # hook's code comes back first, every output is created filled with HOOK_FILL bytes and keeps the hook's guard row.
+    ACT_Q8K, ACT_Q80, ACT_F16, ACT_F32 = 1, 2, 4, 8
+    PLANE_BSQ, PLANE_BS16, PLANE_Q16 = 1, 2, 4
+    ACT_PLANES = ("q8k", "dk", "bsk", "bsq", "bs16", "q16", "q80", "d0", "d1", "s1", "sum0", "xh", "xf")
+
+    @staticmethod
+    def act_plane_shapes(N: int, K: int) -> dict:
+        """name -> (shape of N + 1 rows, dtype) of an ActQ's thirteen planes as the hooks return them (fp16 planes as uint16 bit patterns)."""
+        return {"q8k": ((N + 1, K), np.int8), "dk": ((N + 1, K // 256), np.float32), "bsk": ((N + 1, K // 16), np.int16), "bsq": ((N + 1, K // 256, 16), np.int8),
+                "bs16": ((N + 1, K // 256, 16), np.uint16), "q16": ((N + 1, K), np.uint16), "q80": ((N + 1, K), np.int8), "d0": ((N + 1, K // 32), np.float32),
+                "d1": ((N + 1, K // 32), np.float32), "s1": ((N + 1, K // 32), np.float32), "sum0": ((N + 1, K // 32), np.int32), "xh": ((N + 1, K), np.uint16),
+                "xf": ((N + 1, K), np.float32)}
+
+    def _act_outs(self, N: int, K: int):
+        outs = {name: self._hook_out(shape, dtype) for name, (shape, dtype) in self.act_plane_shapes(N, K).items()}
+        return outs, [self._vp(outs[name]) for name in self.ACT_PLANES]
+
+    def amd_test_prepare(self, launcher: int, x: np.ndarray, second: Optional[np.ndarray] = None, mask: int = 1, planes: int = 0, sequential_sum: bool = False,
+                         silu_table: Optional[np.ndarray] = None):
+        """One launch_rms_quant (launcher 0, second = the norm weight [K]) or launch_silu_mul_quant (launcher 1, second = b [N][K]) on x [N][K] -> (rc, {plane: N + 1 rows})."""
+        x = self._f32(x)
+        N, K = x.shape
+        second = self._f32(second, (K,) if launcher == 0 else (N, K))
+        tab = None if silu_table is None else self._table_arg(silu_table)
+        outs, ptrs = self._act_outs(N, K)
+        rc = self.library.minigpt4_amd_test_prepare(launcher, self._f32p(x), self._f32p(second), N, K, mask, planes, int(sequential_sum), self._vp(tab), *ptrs)
+        return rc, outs
+
+    def amd_test_prepare_slabs(self, launcher: int, slabs: np.ndarray, N: int, K: int, residual: Optional[np.ndarray] = None, in_place: bool = False,
+                               w: Optional[np.ndarray] = None, mask: int = 1, planes: int = 0, silu_table: Optional[np.ndarray] = None):
+        """One launch_rms_quant_slabs (launcher 0: slabs [ks][stride]) or launch_silu_mul_quant_slabs (launcher 1: slabs [2][ks][stride]) -> (rc, x_out [N + 1][K] or None,
+        {plane: N + 1 rows})."""
+        slabs = self._f32(slabs)
+        ks, stride = slabs.shape[-2:]
+        assert slabs.shape == ((ks, stride) if launcher == 0 else (2, ks, stride))
+        residual, w = self._f32(residual, (N, K)), self._f32(w, (K,))
+        tab = None if silu_table is None else self._table_arg(silu_table)
+        x_out = self._hook_out((N + 1, K), np.float32) if launcher == 0 else None
+        outs, ptrs = self._act_outs(N, K)
+        rc = self.library.minigpt4_amd_test_prepare_slabs(launcher, self._f32p(slabs), ks, stride, self._f32p(residual), int(in_place), self._f32p(w), N, K, mask, planes,
+                                                          self._vp(tab), self._f32p(x_out), *ptrs)
+        return rc, x_out, outs
+
+    def amd_test_slab_flush(self, mks: Sequence[int], slabs: np.ndarray, stride: int, mixed: bool = False, residual: Optional[np.ndarray] = None, residual_mask: int = 0,
+                            in_place: Optional[dict] = None):
+        """One launch_slab_flush: slabs [sum of the counts above 1][stride], residual [n][stride]; in_place {matrix: its contents [stride]} for the matrices whose count is 1
+        -> (rc, y [n + 1][stride], guard row last)."""
+        m = np.ascontiguousarray(mks, np.int32)
+        n = m.size
+        slabs, residual = self._f32(slabs), self._f32(residual, (n, stride))
+        y = self._hook_out((n + 1, stride), np.float32)
+        for i, rows in (in_place or {}).items():
+            y[i] = rows
+        rc = self.library.minigpt4_amd_test_slab_flush(n, int(mixed), m.ctypes.data_as(INT_PTR), self._f32p(slabs), stride, self._f32p(residual), residual_mask, self._f32p(y))
+        return rc, y
+
+    def amd_test_rope_kv_slabs(self, n_head: int, hd: int, n_ctx: int, N: int, pos0: int, mks: Sequence[int], slabs: np.ndarray, stride: int,
+                               v_in_place: Optional[np.ndarray] = None):
+        """One launch_rope_kv_slabs with a slab count per matrix -> (rc, q [N + 1][E] with its guard row, kc [n_ctx][E] fp16, vc [n_ctx][E] fp16)."""
+        m = np.ascontiguousarray(mks, np.int32)
+        E = n_head * hd
+        slabs, v_in_place = self._f32(slabs), self._f32(v_in_place, (N, E))
+        q = self._hook_out((N + 1, E), np.float32)
+        kc, vc = self._hook_out((n_ctx, E), np.float16), self._hook_out((n_ctx, E), np.float16)
+        rc = self.library.minigpt4_amd_test_rope_kv_slabs(n_head, hd, n_ctx, N, pos0, m.ctypes.data_as(INT_PTR), self._f32p(slabs), stride, self._f32p(v_in_place), self._f32p(q),
+                                                          self._vp(kc), self._vp(vc))
+        return rc, q, kc, vc
 
     def amd_sample_logits(self, logits: np.ndarray, seed: int, temp=0.8, top_k=40, top_p=0.9, tfs_z=1.0, typical_p=1.0, mirostat=0, mirostat_tau=5.0,
                           mirostat_eta=1.0) -> int:
