@@ -425,6 +425,53 @@ MINIGPT4_API int minigpt4_amd_sampled_candidates(struct MiniGPT4Context *ctx, co
 MINIGPT4_API int minigpt4_amd_conversation_seed(struct MiniGPT4Context *ctx, int slot, uint64_t seed, uint64_t draws);
 MINIGPT4_API int minigpt4_amd_sampling_info(struct MiniGPT4Context *ctx, int slot, uint64_t out[6]);
 
+/* ---- speculation under sampling: drafts verified at temp > 0, lookup decoding with the reference's default sampler settings -----------------------------------
+ * minigpt4_amd_verify_draft and minigpt4_amd_decode_lookup decide greedily.  Here the 1 + n rows of the same verify pass are SAMPLED, each with the draw plain decoding
+ * would have used at its position.  A conversation's stream is counter-based (Philox, (seed, draws) above), so no rejection-sampling arithmetic is needed: a draft token
+ * is kept exactly when the sample of the row before it equals it.  For a deterministic draft that accepts with probability P(draft token), the best any scheme achieves,
+ * and the emitted tokens are the ones minigpt4_amd_end_chat_batch_sampled emits from the same state with the same (seed, draws) wherever the logits are the same: always in
+ * parity mode; in fast mode a pass of another shape can round a logit differently, which can move a draw across a boundary.
+ * THE RULE.  D(L, h, q, k) = the pick of the "sampled batched steps" rule above, unchanged: the raw row L after the conversation's logit bias and its penalties for the
+ * token history h; only the ids allowed in constraint state q take part; top_k <= 64, then top_p, temperature, softmax; one draw with word 0 of Philox(seed, counter k).
+ * Before the call the selected conversation has position p, raw logits L, history h, constraint state q and stream (seed, c).
+ *   x0 = D(L, h, q, c).
+ *   The pass evaluates rows t_0 = x0, t_{i + 1} = draft[i] at positions p, p + 1, ...; L_r = the logits of row r.
+ *   h_r = h followed by t_0 .. t_r;  q_r = q walked over t_0 .. t_r (id 2 leaves the state, as minigpt4_amd_constraint_advance does).
+ *   x_{r + 1} = D(L_r, h_r, q_r, c + 1 + r) for every evaluated row.
+ *   m = the largest value with draft[i] == x_{i + 1} for all i < m.
+ * AFTERWARDS ids_out[0 .. m] = t_0 .. t_m and *n_out = 1 + m; the conversation stands at p + 1 + m with the raw logits, greedy token and feed token of row m; its history
+ * is h_m, its constraint state q_m, and draws = c + 1 + m: draws advance by exactly the number of tokens emitted.  The sample of row m is reported as *next_out and its draw
+ * is NOT counted: the next decision of this conversation -- this call's x0, or minigpt4_amd_end_chat_batch_sampled -- recomputes the same token from the same row, state
+ * and counter.  A caller drafts behind next_out; n_draft = 0 is one plain sampled step that also tells what comes next.  The call does not treat x0 == 2 specially.
+ * minigpt4_amd_verify_draft_sampled: queued rows are evaluated first.  With the automatic shift on and no room for x0, x0's descriptor is built from the history before the
+ * shift (as minigpt4_amd_end_chat_batch_sampled does) and the rows' from the shifted history followed by t_0 .. t_r.  The draft is cut to the room left, then at the first
+ * token its constraint state does not allow (bit clear in the state's index row; id 2 is allowed exactly where the state accepts): a token that cannot be sampled cannot be
+ * accepted.  A row where no id takes part picks "</s>" and is flagged stuck.  row_sampled_out (may be NULL; 1 + n_draft entries) = x_{r + 1} of every evaluated row, -1 for
+ * a row that was not evaluated; row_logits_out (may be NULL; [1 + n_draft][n_vocab]) = the pass's raw rows, rows not evaluated are left alone.
+ * ON THE DEVICE: x0 is one k_sample_rows launch on the conversation's row; the host waits for that 4-byte pick (the greedy call synchronises at the same point) because the
+ * rows' histories and constraint states begin with it.  Then, behind one wait: the verify pass (captured per row count WITHOUT an epilogue -- the greedy passes keep
+ * theirs), one k_sample_rows launch over the pass's R rows with R descriptors and draws c + 1 + r, and k_draft_sample_finish (one workgroup: m, row m into the
+ * conversation's logits row with its first argmax from the same sweep, position, the result block).  Parity mode: one oracle-order single-row pass per row, each followed
+ * by the decision on the conversation's own row, stopping at the first mismatch -- the sequence of minigpt4_amd_end_chat_batch_sampled there, bit for bit.
+ * minigpt4_amd_decode_lookup_sampled: minigpt4_amd_decode_lookup's loop (the same drafter; history = corpus followed by the emitted tokens).  The first step runs with
+ * n_draft = 0 to learn next_out; afterwards the draft continues the history behind next_out, cut at n_draft, before any id 2 and at the tokens still wanted.  With no match
+ * the step is the n_draft = 0 pass again (one decision path, and it keeps announcing the next token).  Ends after max_tokens, after "</s>" has been emitted and
+ * evaluated, or on a full context that cannot shift.  stats has minigpt4_amd_decode_lookup's meaning (passes + steps + accepted == *n_tokens).
+ * minigpt4_amd_speculation_info: out = {sampled verify passes, rows evaluated, draft tokens sent, draft tokens accepted, sampling launches made by these calls, stuck picks,
+ * draft tokens cut by a constraint, 0}.  The counters of minigpt4_amd_sampling_info do not count these calls; the conversation's draws does move.
+ * Each returns 0, or 1 with "verify_draft_sampled: ..." / "decode_lookup_sampled: ..." / "speculation_info: ..." in minigpt4_amd_last_error and nothing changed, no draw
+ * counted: no context, speculation off, n_draft outside the range, a NULL pointer (draft with n_draft > 0, ids_out, n_out, next_out; tokens_out, n_tokens, stats), an id
+ * outside [0, n_vocab), no current logits, temp not finite or <= 0, top_k outside 1 .. min(64, n_vocab), top_p outside (0, 1], and "context full" when there is no room for
+ * x0 and the automatic shift is off -- checked before anything is decided.  The graphs are dropped where the greedy ones are; the result block is allocated by the first
+ * call: a context that never calls these functions allocates nothing new and launches nothing new.
+ * Not built: several conversations' drafts in one pass; tree drafts; a draft model; remembering next_out per conversation, which would save the x0 launch of the next call
+ * (every setter of bias, penalties, constraint, seed and logits would have to invalidate it); tail-free, typical and mirostat sampling; guidance. */
+MINIGPT4_API int minigpt4_amd_verify_draft_sampled(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, float temp, int32_t top_k, float top_p, int32_t *ids_out,
+                                                   int32_t *n_out, int32_t *next_out, int32_t *row_sampled_out, float *row_logits_out);
+MINIGPT4_API int minigpt4_amd_decode_lookup_sampled(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft,
+                                                    float temp, int32_t top_k, float top_p, int32_t *tokens_out, int32_t *n_tokens, int32_t stats[4]);
+MINIGPT4_API int minigpt4_amd_speculation_info(struct MiniGPT4Context *ctx, int64_t out[8]);
+
 /* ---- snapshots: save and restore a conversation --------------------------------------------------------------------------------------------------------
  * A conversation leaves its slot, its context or its process as one blob (llama.cpp's llama_copy_state_data / session files / slot save and restore) and comes back bit
  * for bit: a restored conversation continues with the logits and tokens of the uninterrupted one.  The cache rows travel through k_kv_pack / k_kv_unpack -- rows

@@ -263,6 +263,25 @@ MINIGPT4_API int minigpt4_amd_test_sample_rule(const float *values, int n_cand, 
 MINIGPT4_API int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
                                                const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k,
                                                const uint64_t *seed_draws, const int32_t *tok_index, int32_t *row_tok_io, int32_t *out, float *ms_out);
+/* Speculation under sampling (minigpt4_amd.h states the rule).
+ * minigpt4_amd_test_draft_sample: the sampled verify pass's epilogue alone -- k_sample_rows over the R rows (1 .. 8) of host logits [R][ld], then k_draft_sample_finish.
+ * rows / table / bitmaps / bitmap_of_row / temp_top_p / top_k / seed_draws as for minigpt4_amd_test_sample_rows, one descriptor per row, descriptor r naming buffer row r;
+ * row_tok[R] = the pass's row tokens (row_tok[0] is not compared); slot (0 or 1) = the conversation the pass belongs to; state_io = [2][3] (n_past, argmax, feed) of two
+ * slots and slot_logits_io = [2][n_vocab] their logits rows, both replaced by their contents afterwards.  res_out[17] = {m, 8 picks, 8 stuck flags} (-1 behind R);
+ * out = [R][133] words as for _test_sample_rows; ms_out (may be NULL): the hipEvent time of k_draft_sample_finish alone.  1 = bad arguments, before any device is looked
+ * for; 2 = no device; 3 = device error.
+ * minigpt4_amd_test_draft_tables, no GPU: the host staging of that pass (csrc/draft_host.hpp) for a history, x0 and a draft of at most 7 tokens (already cut for room).
+ * trans / accept / n_states / state / vocab / off[n_vocab + 1] describe the constraint and the pieces (trans NULL: no constraint).  *n_rows_out = R, *cut_out = draft
+ * tokens the constraint cut, rows_out = [R][8] words (PenRow: row, first entry, entries, flags, the three factors, 0), table_out = the R tables back to back
+ * ([*n_table_out][4]: id, count, bias bits, has_bias), states_out[R] = q_r.  1 = bad arguments; 4 = table_cap too small (*n_table_out says what is needed). */
+MINIGPT4_API int minigpt4_amd_test_draft_sample(const float *logits, int R, int n_vocab, int ld, const int32_t *rows, const int32_t *table, int n_table, const uint32_t *bitmaps,
+                                                int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k, const uint64_t *seed_draws,
+                                                const int32_t *row_tok, int slot, int32_t *state_io, float *slot_logits_io, int32_t *res_out, int32_t *out, float *ms_out);
+MINIGPT4_API int minigpt4_amd_test_draft_tables(const int32_t *hist, int n_hist, int32_t x0, const int32_t *draft, int n_draft, int32_t repeat_last_n, float repeat_penalty,
+                                                float alpha_presence, float alpha_frequency, int penalize_nl, const int32_t *bias_id, const float *bias_val, int n_bias, int n_ctx,
+                                                int n_vocab, const uint16_t *trans, const uint32_t *accept, int n_states, int state, const uint8_t *vocab, const int32_t *off,
+                                                int32_t *n_rows_out, int32_t *cut_out, int32_t *rows_out, int32_t *table_out, int table_cap, int32_t *n_table_out,
+                                                int32_t *states_out);
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,

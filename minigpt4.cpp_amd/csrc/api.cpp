@@ -379,6 +379,21 @@ int minigpt4_amd_decode_lookup(struct MiniGPT4Context *ctx, const int32_t *corpu
     if (!ctx) { set_last_error("decode_lookup: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->decode_lookup(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats); });
 }
+int minigpt4_amd_verify_draft_sampled(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, float temp, int32_t top_k, float top_p, int32_t *ids_out, int32_t *n_out,
+                                      int32_t *next_out, int32_t *row_sampled_out, float *row_logits_out) {
+    if (!ctx) { set_last_error("verify_draft_sampled: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->verify_draft_sampled(draft, n_draft, temp, top_k, top_p, ids_out, n_out, next_out, row_sampled_out, row_logits_out); });
+}
+int minigpt4_amd_decode_lookup_sampled(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp,
+                                       int32_t top_k, float top_p, int32_t *tokens_out, int32_t *n_tokens, int32_t stats[4]) {
+    if (!ctx) { set_last_error("decode_lookup_sampled: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->decode_lookup_sampled(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, temp, top_k, top_p, tokens_out, n_tokens, stats); });
+}
+int minigpt4_amd_speculation_info(struct MiniGPT4Context *ctx, int64_t out[8]) {
+    if (!ctx) { set_last_error("speculation_info: no context"); return 1; }
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counters travel as 64-bit words");
+    return guarded(1, [&] { return E_(ctx)->speculation_info(reinterpret_cast<long long *>(out)); });
+}
 // ---- beam search over forked conversations ------------------------------------------------------------------------------------------------------
 int minigpt4_amd_beam_search(struct MiniGPT4Context *ctx, const int32_t *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int32_t *tokens_out,
                              int32_t *lengths_out, float *scores_out, int32_t *n_out, int32_t stats[4]) {

@@ -1,6 +1,7 @@
 #include "engine.hpp"
 #include "dist.hpp"
 #include "draft.hpp"
+#include "draft_host.hpp"
 #include "beam_host.hpp"
 #include "quantize.hpp"
 #include "imageio.hpp"
@@ -96,7 +97,7 @@ Engine::~Engine() {
                     pen_d_, pen_h_, pen_out_d_, pen_out_h_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
                     guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_d_, con_h_, con_out_d_, con_out_h_, con_row_h_,
                     state_d_[0], state_d_[1], state_h_[0], state_h_[1], state_sum_d_, state_sum_h_, state_cs_, state_ev_kernel_[0], state_ev_kernel_[1], state_ev_copy_[0],
-                    state_ev_copy_[1], smp_d_, smp_h_, smp_out_d_, smp_out_h_, smp_ev_);
+                    state_ev_copy_[1], smp_d_, smp_h_, smp_out_d_, smp_out_h_, smp_ev_, sdr_res_, sdr_hres_);
         for (Constraint &c : con_) c.dev.abandon();
         return;
     }
@@ -1046,7 +1047,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
 // arithmetic per row as forward(1): per-row activation quantisation, exact integer block dots, the same attention kernel body.
 // verify (Engine::verify_draft): the B rows are ONE conversation's (d_bslot_[0]) at consecutive positions -- the same embedding rows and mat-vec branches; the attention
 // launch is launch_attn_llm_draft, the row logits go to spec_logits_ and the epilogue is launch_draft_finish.
-void Engine::forward_batch(int B, hipStream_t s, bool verify) {
+void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
     pend_ = SlabSrc{}; xh_override_ = nullptr;
     batch_path_ = BatchPath{}; batch_path_.rows = B;
     const int E = (int)llm_.n_embd, F = (int)llm_.n_ff(), H = (int)llm_.n_head, hd = E / H, V = (int)llm_.n_vocab;
@@ -1200,7 +1201,7 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify) {
         prep_rms(x_, norm_, B, E, act_mask_for(output_.type), s);             // (also combines the last layer's w2 slabs when its combine was deferred)
         mm({&output_}, {row_logits}, nullptr, V);
     }
-    if (verify) launch_draft_finish(spec_logits_, V, B, d_btok_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, spec_res_, s);
+    if (verify) { if (epilogue) launch_draft_finish(spec_logits_, V, B, d_btok_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, spec_res_, s); }   // (the sampled form launches its own behind the pass)
     else launch_batch_finish(blogits_, V, B, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, s);
 }
 
@@ -2224,6 +2225,11 @@ bool Engine::smp_launch(int n, size_t n_ent, bool hand) {
     smp_info_.launches++;
     return true;
 }
+bool Engine::smp_launch_on(const float *logits, int n, size_t n_ent) {
+    const int V = (int)llm_.n_vocab;
+    HIP_CHECK(hipMemcpyAsync(smp_d_, smp_h_, SMP_HEAD + n_ent * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
+    return launch_sample_rows(logits, V, V, n, smp_d_.as<const SampleRow>(), reinterpret_cast<const PenEntry *>(smp_d_ + SMP_HEAD), smp_out_d_, nullptr, stream_);
+}
 int Engine::sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out) {
     if (smp_prepare("sampled_candidates", slots, n, temp, top_k, top_p)) return 1;
     HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; smp_h_ feeds no earlier copy
@@ -2471,8 +2477,10 @@ int Engine::state_load(int slot, const void *buf, size_t n) {
 }
 
 // ---- speculation: draft tokens verified in one weight pass (engine.hpp) ----
-void Engine::spec_drop_graphs() { for (hipGraphExec_t &g : spec_graph_) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; } }
-void Engine::spec_free() { spec_drop_graphs(); reset_all(spec_logits_, spec_res_, spec_hres_); spec_max_ = 0; }
+void Engine::spec_drop_graphs() {
+    for (std::vector<hipGraphExec_t> *v : {&spec_graph_, &spec_sgraph_}) for (hipGraphExec_t &g : *v) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; }
+}
+void Engine::spec_free() { spec_drop_graphs(); reset_all(spec_logits_, spec_res_, spec_hres_, sdr_res_, sdr_hres_); spec_max_ = 0; }
 int Engine::set_speculation(int max_draft) {
     if (max_draft < 0 || max_draft > DRAFT_MAX) { set_last_error("set_speculation: max_draft must be 0 (off) ... " + std::to_string(DRAFT_MAX)); return 1; }
     // the verify pass keeps DRAFT_ROWS new key / value rows next to the score rows in the attention kernel's LDS: a context the one-row form holds may not fit it
@@ -2565,6 +2573,175 @@ int Engine::decode_lookup(const int *corpus, int n_corpus, int max_tokens, int n
             for (int i = 0; i < got; i++) { tokens_out[n++] = ids[i]; if (i) drafter.push(ids[i]); }
         }
         if (g0 == 2) break;                                                  // </s> emitted and evaluated
+    }
+    return done(0);
+}
+// ---- speculation under sampling (engine.hpp, draft_host.hpp) ----
+void Engine::sdr_alloc() {
+    if (spec_sgraph_.empty()) spec_sgraph_.assign((size_t)DRAFT_ROWS + 1, nullptr);
+    if (sdr_res_) return;
+    DevPtr<int> d(DRAFT_SAMPLE_RES * 4); PinPtr<int> h(DRAFT_SAMPLE_RES * 4);   // both or none
+    sdr_res_ = std::move(d); sdr_hres_ = std::move(h);
+}
+void Engine::spec_pass_launch(int R) {
+    if (!use_graph_) { forward_batch(R, stream_, /*verify=*/true, /*epilogue=*/false); return; }
+    hipGraphExec_t &ge = spec_sgraph_[(size_t)R];
+    if (!ge) capture_graph(ge, [&] { forward_batch(R, stream_, /*verify=*/true, /*epilogue=*/false); });
+    HIP_CHECK(hipGraphLaunch(ge, stream_));
+}
+int Engine::speculation_info(long long out[8]) const {
+    if (!out) { set_last_error("speculation_info: no output array"); return 1; }
+    const SpecInfo &i = spec_info_;
+    out[0] = i.passes; out[1] = i.rows; out[2] = i.sent; out[3] = i.accepted; out[4] = i.launches; out[5] = i.stuck; out[6] = i.cut; out[7] = 0;
+    return 0;
+}
+int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int top_k, float top_p, int *ids_out, int *n_out, int *next_out, int *row_sampled, float *row_logits,
+                                 const char *name, int *n_sent) {
+    auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
+    const int V = (int)llm_.n_vocab;
+    if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
+    if (n_draft < 0 || n_draft > spec_max_) return refuse("n_draft outside [0, max_draft]");
+    if (n_draft > 0 && !draft) return refuse("draft is NULL");
+    if (!ids_out || !n_out || !next_out) return refuse("ids_out, n_out and next_out are required");
+    for (int i = 0; i < n_draft; i++) if (draft[i] < 0 || draft[i] >= V) return refuse("draft token id out of range");
+    if (!std::isfinite(temp) || !(temp > 0.0f)) return refuse("temp must be finite and > 0");
+    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, V)) return refuse("top_k outside 1 .. min(64, n_vocab)");
+    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return refuse("top_p outside (0, 1]");
+    if (weights_missing()) return refuse(last_error());
+    Conversation &cv = conv_[(size_t)cur_];
+    if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
+    if (flush()) return refuse("the queued rows could not be evaluated: " + last_error());
+    if (!cv.has_logits) return refuse("the conversation has no current logits");
+    if (cv.n_past + 1 > n_ctx_ && !shift_allows(1)) return refuse("context full");   // before anything is decided: no draw is counted for a call that cannot emit
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the history is whole; h_bstage_ and smp_h_ feed no earlier copy
+    const int slot = cur_, handle = con_handle_[slot], W = constraint_words(V);
+    const uint64_t c0 = smp_draws_[slot];
+    sdr_alloc();
+    // 1. x0 = D(L, h, q, c): the sampled step's own descriptor (history before the shift) and launch, on the conversation's row; the host needs the pick for the rows' tables
+    const size_t n_ent0 = smp_stage(&slot, 1, temp, top_k, top_p);
+    if (cv.n_past + 1 > n_ctx_ && make_room(1)) return refuse("context full");
+    auto decide = [&](size_t n_ent, int *stuck) -> int {                     // the staged descriptor on logits_, the 8 bytes {pick, stuck} awaited
+        if (!smp_launch_on(logits_, 1, n_ent)) throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
+        HIP_CHECK(hipMemcpyAsync(smp_out_h_, smp_out_d_, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        spec_info_.launches++;
+        const int id = smp_out_h_[0].pick;
+        if (id < 0 || id >= V) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an id outside the vocabulary", __FILE__, __LINE__};
+        *stuck = smp_out_h_[0].stuck == 1;
+        return id;
+    };
+    int stuck0 = 0;
+    const int x0 = decide(n_ent0, &stuck0), p = cv.n_committed;
+    spec_info_.stuck += stuck0;
+    // 2. the rows: the draft cut to the room left, then at the first token its constraint state does not allow; one table and one state per row
+    const int room = std::min(n_draft, n_ctx_ - cv.n_past - 1);
+    const PenParams pp = pen_mode_ ? cv.pen : PenParams{};
+    auto piece = [&](int id, const unsigned char **b, int *n) {
+        if (id < 0 || id >= (int)llm_.pieces.size()) return false;
+        *b = reinterpret_cast<const unsigned char *>(llm_.pieces[(size_t)id].data()); *n = (int)llm_.pieces[(size_t)id].size();
+        return true;
+    };
+    DraftStage st;
+    draft_stage(cv.hist.data(), cv.hist.size(), x0, draft, room, pp, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size(), n_ctx_, V,
+                handle ? &con_[handle - 1].dfa : nullptr, con_state_[slot], piece, st);
+    const int R = st.n_rows;
+    if (n_sent) *n_sent = R - 1;
+    if (row_sampled) for (int r = 0; r < 1 + n_draft; r++) row_sampled[r] = -1;   // rows that were not evaluated (cut; parity mode: behind the first mismatch)
+    spec_info_.passes++; spec_info_.sent += R - 1; spec_info_.cut += st.cut;
+    int m = 0, next = -1;
+    if (parity_) {   // oracle-order arithmetic exists for the single-row pass only: evaluate a row, decide on the conversation's own row, stop at the first mismatch
+        smp_draws_[slot] = c0 + 1; if (handle) con_walk(slot, x0);
+        for (int r = 0; r < R; r++) {
+            const int id = r ? draft[r - 1] : x0;
+            if (eval_chunk(&id, 1, nullptr)) return 1;
+            cv.n_past += 1;
+            HIP_CHECK(hipStreamSynchronize(stream_));
+            spec_info_.rows++;
+            if (row_logits) { HIP_CHECK(hipMemcpyAsync(row_logits + (size_t)r * V, logits_ + (size_t)slot * V, (size_t)V * 4, hipMemcpyDeviceToHost, stream_)); HIP_CHECK(hipStreamSynchronize(stream_)); }
+            int stuck = 0;
+            const int x = decide(smp_stage(&slot, 1, temp, top_k, top_p), &stuck);   // history h_r, state q_r, draw c + 1 + r: all current
+            spec_info_.stuck += stuck;
+            if (row_sampled) row_sampled[r] = x;
+            next = x;
+            if (r + 1 < R && draft[r] == x) { m++; smp_draws_[slot] += 1; if (handle) con_walk(slot, x); } else break;
+        }
+    } else {
+        // 3. behind one wait: the slab, the pass without an epilogue, the R decisions with draws c + 1 + r, the epilogue, the result block
+        SampleRow *rows = smp_h_.as<SampleRow>();
+        for (int r = 0; r < R; r++) {
+            rows[r].pen = st.rows[(size_t)r];
+            rows[r].allowed = handle ? con_[handle - 1].index + (size_t)st.state[(size_t)r] * W : nullptr;
+            rows[r].temp = temp; rows[r].top_p = top_p; rows[r].top_k = top_k; rows[r].tok_index = -1;
+            rows[r].seed = smp_seed_[slot]; rows[r].draws = c0 + 1 + (uint64_t)r;
+        }
+        std::copy(st.entries.begin(), st.entries.end(), reinterpret_cast<PenEntry *>(smp_h_ + SMP_HEAD));
+        stage_row(0, x0, slot, p); for (int r = 1; r < R; r++) staged_token(r) = draft[r - 1];   // k_draft_begin spreads row 0's conversation and position
+        step_begin(R, /*verify=*/true);
+        spec_pass_launch(R);
+        if (!smp_launch_on(spec_logits_, R, st.entries.size())) throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
+        if (!launch_draft_sample_finish(spec_logits_, V, V, R, d_btok_, smp_out_d_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, sdr_res_, stream_))
+            throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
+        spec_info_.launches++; spec_info_.rows += R;
+        HIP_CHECK(hipMemcpyAsync(sdr_hres_, sdr_res_, DRAFT_SAMPLE_RES * 4, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+        if (row_logits) HIP_CHECK(hipMemcpyAsync(row_logits, spec_logits_, (size_t)R * V * 4, hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));                            // the one wait behind the pass: m, the rows' samples, their stuck flags
+        m = sdr_hres_[0];
+        // the device has advanced the conversation by 1 + m whatever the block says: the book-keeping follows it before a bad block is reported
+        const bool sane = m >= 0 && m < R;
+        if (!sane) m = 0;
+        commit_rows(slot, &staged_token(0), 1 + m, /*past=*/true);              // the kept rows only: x0, draft[0 .. m)
+        smp_draws_[slot] = c0 + 1 + (uint64_t)m;
+        if (handle) con_state_[slot] = st.state[(size_t)m];
+        if (!sane) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an accepted count outside the pass", __FILE__, __LINE__};
+        for (int r = 0; r < R; r++) { if (row_sampled) row_sampled[r] = sdr_hres_[1 + r]; spec_info_.stuck += sdr_hres_[1 + DRAFT_ROWS + r] == 1; }
+        next = sdr_hres_[1 + m];
+        if (next < 0 || next >= V) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an id outside the vocabulary", __FILE__, __LINE__};
+    }
+    spec_info_.accepted += m;
+    ids_out[0] = x0; for (int i = 0; i < m; i++) ids_out[1 + i] = draft[i];
+    *n_out = 1 + m; *next_out = next;
+    return 0;
+}
+int Engine::decode_lookup_sampled(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p, int *tokens_out,
+                                  int *n_tokens, int *stats) {
+    static const char *const name = "decode_lookup_sampled";
+    auto refuse = [](const char *what) { set_last_error(std::string(name) + ": " + what); return 1; };
+    if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
+    if (n_corpus < 0 || (n_corpus > 0 && !corpus)) return refuse("bad corpus");
+    if (max_tokens < 1 || !tokens_out || !n_tokens || !stats) return refuse("max_tokens >= 1, tokens_out, n_tokens and stats are required");
+    if (ngram_min < 1 || ngram_max < ngram_min) return refuse("need 1 <= ngram_min <= ngram_max");
+    if (n_draft < 1 || n_draft > spec_max_) return refuse("n_draft outside [1, max_draft]");
+    for (int i = 0; i < n_corpus; i++) if (corpus[i] < 0 || corpus[i] >= (int)llm_.n_vocab) return refuse("corpus token id out of range");
+    if (!std::isfinite(temp) || !(temp > 0.0f)) return refuse("temp must be finite and > 0");
+    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, (int)llm_.n_vocab)) return refuse("top_k outside 1 .. min(64, n_vocab)");
+    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return refuse("top_p outside (0, 1]");
+    if (weights_missing()) return 1;
+    Conversation &cv = conv_[(size_t)cur_];
+    if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
+    NgramDrafter drafter(ngram_max, ngram_min);
+    drafter.reset(corpus, n_corpus);
+    int n = 0, st[4] = {0, 0, 0, 0}, d[DRAFT_MAX], ids[DRAFT_ROWS], next = -1;
+    *n_tokens = 0;
+    auto done = [&](int rc) { *n_tokens = n; for (int i = 0; i < 4; i++) stats[i] = st[i]; return rc; };
+    while (n < max_tokens) {
+        if (cv.n_past + 1 > n_ctx_ && !shift_allows(1)) break;               // context full and no automatic shift (n_past counts the queued rows)
+        // the draft continues the history behind `next`, the token the coming pass evaluates first (unknown before the first pass: that one runs without a draft)
+        const int announced = next;
+        int nd = 0;
+        if (announced >= 0 && announced != 2) {
+            drafter.push(announced);
+            nd = drafter.draft(std::min(n_draft, max_tokens - n - 1), d);
+        }
+        int got = 0, sent = 0;
+        if (verify_draft_sampled(d, nd, temp, top_k, top_p, ids, &got, &next, nullptr, nullptr, name, &sent)) return done(1);
+        // x0 is the announced token wherever the logits are the same; in fast mode a pass of another shape may have rounded a logit differently and moved the draw across a
+        // boundary: the history takes what was emitted (the draft then missed: m = 0 or a lucky match, both within the rule)
+        if (announced < 0 || announced == 2) drafter.push(ids[0]);
+        else if (ids[0] != announced) { drafter.reset(corpus, n_corpus); for (int i = 0; i < n; i++) drafter.push(tokens_out[i]); drafter.push(ids[0]); }
+        if (nd) { st[0]++; st[2] += sent; st[3] += got - 1; } else st[1]++;
+        for (int i = 0; i < got; i++) { tokens_out[n++] = ids[i]; if (i) drafter.push(ids[i]); }
+        if (ids[0] == 2) break;                                              // </s> emitted and evaluated (a draft never holds it)
     }
     return done(0);
 }

@@ -187,6 +187,28 @@ public:
     // earlier, the ordinary decode step (sample_token at temp 0 + add_tokens, its own graph, key-split attention included) where it does not.
     // stats = {verify passes, plain steps, draft tokens sent, draft tokens accepted}
     int decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats);
+    // ---- speculation under sampling (temp > 0; minigpt4_amd.h: the rule; draft_host.hpp: the host staging).  The conversation's stream is counter-based, so every row of the
+    // pass is sampled with the draw plain decoding would use at its position and a draft token is kept exactly when the sample equals it: the emitted tokens are those of
+    // decode_batch_sampled from the same (seed, draws) wherever the logits are the same.  verify_draft_sampled: x0 = the decision of the existing launch_sample_rows on the
+    // conversation's logits_ row (descriptor from the history before an automatic shift); the host waits for that pick -- the greedy call synchronises at the same point --
+    // because the rows' histories and constraint states start with it; draft_stage builds the R descriptors (tables over the shifted history + t_0 .. t_r, states q_r, the
+    // constraint's cut); then, behind ONE wait: the slab's copy, the verify pass WITHOUT an epilogue (forward_batch(R, verify, epilogue = false), one captured graph per row
+    // count in spec_sgraph_ -- the greedy graphs in spec_graph_ end in launch_draft_finish and stay as they are), and behind it, launched eagerly, launch_sample_rows over
+    // spec_logits_ with draws c + 1 + r and launch_draft_sample_finish, the result block's copy.  The epilogue stays outside the graph because its descriptor upload has a
+    // length of its own every call and its buffers (the smp_* staging, freed by set_conversations) have another lifetime than the pass's.  Afterwards: n_past = p + 1 + m,
+    // history + t_0 .. t_m, constraint state q_m, draws = c + 1 + m (the sample of row m is reported as *next_out, its draw not counted: the next decision recomputes it).
+    // row_sampled (may be null, 1 + n_draft entries): x_{r + 1} of every evaluated row, -1 behind them; row_logits (may be null): the pass's raw rows [1 + n_draft][n_vocab],
+    // evaluated rows only.  Parity mode: one oracle-order single-row pass per row, each followed by the decision on the conversation's own row, stopping at the first
+    // mismatch -- decode_batch_sampled's own sequence.  The graphs are dropped with the greedy ones; the result block is allocated by the first call.  The counters of
+    // sampling_info do not count these launches; speculation_info does.  1 + last_error "<name>: ..." and nothing changed on a refusal.
+    int verify_draft_sampled(const int *draft, int n_draft, float temp, int top_k, float top_p, int *ids_out, int *n_out, int *next_out, int *row_sampled, float *row_logits,
+                             const char *name = "verify_draft_sampled", int *n_sent = nullptr);
+    // decode_lookup's loop under sampling: the drafter drafts behind next_out (the first step runs with n_draft = 0 to learn it); no match: the n_draft = 0 pass again -- a
+    // plain sampled step that also tells what comes next, so the loop needs no second decision path
+    int decode_lookup_sampled(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p, int *tokens_out,
+                              int *n_tokens, int *stats);
+    // {sampled verify passes, rows evaluated, draft tokens sent, draft tokens accepted, sampling launches made by these calls, stuck picks, draft tokens cut by a constraint, 0}
+    int speculation_info(long long out[8]) const;
 
     // ---- beam search over forked conversations (beam.hpp: the step's rule; minigpt4_amd.h: the whole rule).  slots[0] is the source, the other n_beams - 1 listed
     // conversations are scratch.  The source's queue is evaluated, its logits row / greedy / feed token saved, its state forked to the others; then every step queues, on one
@@ -296,7 +318,7 @@ private:
     int load_llm(const std::string &path);
     int load_vision(const std::string &path);
     void alloc_buffers();
-    void forward_batch(int B, hipStream_t s, bool verify = false);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation
+    void forward_batch(int B, hipStream_t s, bool verify = false, bool epilogue = true);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation (epilogue = false: without launch_draft_finish)
     // speculation's own allocations (set_speculation; freed with the context): [1 + spec_max_][n_vocab] row logits, {m, greedy id per row} and its pinned mirror, [R] graphs
     int spec_max_ = 0; DevPtr<float> spec_logits_; DevPtr<int> spec_res_; PinPtr<int> spec_hres_; std::vector<hipGraphExec_t> spec_graph_;
     // penalties: [MAX_CONVERSATIONS] PenRow then the tables, device and pinned (one upload per launch); the picked ids and their pinned mirror
@@ -638,6 +660,14 @@ private:
     // n staged descriptors with n_ent entries: the upload, the launch (hand: picks go to d_btok_ at the descriptors' row-token indices), the result block's copy back and
     // the event queued.  false: the launch was refused (last_error)
     bool smp_launch(int n, size_t n_ent, bool hand);
+    // the same upload and launch over rows of `logits`, nothing handed over, nothing counted, no copy back (verify_draft_sampled: its launches are speculation_info's)
+    bool smp_launch_on(const float *logits, int n, size_t n_ent);
+    // speculation under sampling.  Lazy, first call: one graph slot per row count (the verify pass without its epilogue), the result block {m, picks, stuck flags} and its
+    // pinned mirror.  Dropped / freed where the greedy form's are (spec_drop_graphs, spec_free)
+    std::vector<hipGraphExec_t> spec_sgraph_; DevPtr<int> sdr_res_; PinPtr<int> sdr_hres_;
+    struct SpecInfo { long long passes = 0, rows = 0, sent = 0, accepted = 0, launches = 0, stuck = 0, cut = 0; } spec_info_;
+    void sdr_alloc();
+    void spec_pass_launch(int R);                      // the verify pass over the staged rows without an epilogue: spec_sgraph_[R] replayed, captured first; without graphs, eager
 };
 
 int device_count_noexcept();

@@ -3523,6 +3523,49 @@ bool launch_sample_rows(const float *logits, int ld, int n_vocab, int n_rows, co
     hipLaunchKernelGGL(k_sample_rows, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, out, row_tok);
     return true;
 }
+// Verify pass epilogue under sampling (Engine::verify_draft_sampled), ONE workgroup of 1024, launched behind k_sample_rows over the pass's R rows: picks[r] is the decision of
+// row r (x_{r + 1} of the rule in minigpt4_amd.h), tok[0 .. R) the pass's rows (tok[0] = x0, tok[1 ..] the draft).  m = the number of leading draft tokens the rows' own
+// samples chose (tok[i + 1] == picks[i].pick for every i < m); row m becomes the conversation's state as k_draft_finish leaves it -- its logits row copied into the slot's
+// row with the first argmax found in the same sweep (batch_finish_row<true>'s sweep: every thread visits its indices in ascending order, `>` keeps the first of equal values,
+// -0.0 == +0.0; 16-byte loads when both strides allow them), greedy and feed token = that argmax, position p + 1 + m (n_past[slot] still holds p) -- and
+// res = {m, picks [DRAFT_ROWS], stuck flags [DRAFT_ROWS]} (entries from R on are left alone).  The logits rows lie ld floats apart; nothing beyond n_vocab floats of a row is
+// read.  No flags or counters between workgroups, no spinning, no atomics; every loop is bounded by n_vocab or by R.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 17 VGPRs, 41 SGPRs, no scratch, 128 bytes of static LDS, occupancy 8 waves per SIMD.
+__global__ __launch_bounds__(1024) void k_draft_sample_finish(const float *__restrict__ logits, int ld, int n_vocab, int R, const int *__restrict__ tok, const SampleOut *__restrict__ picks,
+                                                             const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax, int *__restrict__ feed,
+                                                             float *__restrict__ slot_logits, int *__restrict__ res) {
+    int m = 0;
+    while (m < R - 1 && tok[m + 1] == picks[m].pick) m++;                 // every thread: R <= 8 words, all in cache
+    const int slot = row_slot[0];
+    const float *x = logits + (size_t)m * ld;
+    float *keep = slot_logits + (size_t)slot * n_vocab;
+    float best = -INFINITY; int bi = 0x7FFFFFFF;
+    const int n4 = ((n_vocab | ld) & 3) == 0 ? n_vocab >> 2 : 0;
+    for (int i = threadIdx.x; i < n4; i += 1024) {
+        const float4 v = reinterpret_cast<const float4 *>(x)[i]; reinterpret_cast<float4 *>(keep)[i] = v;
+        if (v.x > best) { best = v.x; bi = 4 * i; } if (v.y > best) { best = v.y; bi = 4 * i + 1; } if (v.z > best) { best = v.z; bi = 4 * i + 2; } if (v.w > best) { best = v.w; bi = 4 * i + 3; }
+    }
+    for (int i = 4 * n4 + threadIdx.x; i < n_vocab; i += 1024) { const float v = x[i]; keep[i] = v; if (v > best) { best = v; bi = i; } }
+    __shared__ float sv[16]; __shared__ int si[16];
+    argmax_wave(best, bi);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x < R) { res[1 + threadIdx.x] = picks[threadIdx.x].pick; res[1 + DRAFT_ROWS + threadIdx.x] = picks[threadIdx.x].stuck; }
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 16; w++) argmax_combine(best, bi, sv[w], si[w]);
+        const int id = bi == 0x7FFFFFFF ? 0 : bi;
+        argmax[slot] = id; feed[slot] = id; n_past[slot] += 1 + m; res[0] = m;
+    }
+}
+bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R, const int *tok, const SampleOut *picks, const int *row_slot, int *n_past, int *argmax, int *feed,
+                                float *slot_logits, int *res, hipStream_t s) {
+    if (!logits || !tok || !picks || !row_slot || !n_past || !argmax || !feed || !slot_logits || !res || R < 1 || R > DRAFT_ROWS || n_vocab < 1 || ld < n_vocab) {
+        set_last_error("launch_draft_sample_finish: shape out of range"); return false;
+    }
+    note_kernel("k_draft_sample_finish");
+    hipLaunchKernelGGL(k_draft_sample_finish, dim3(1), dim3(1024), 0, s, logits, ld, n_vocab, R, tok, picks, row_slot, n_past, argmax, feed, slot_logits, res);
+    return true;
+}
 // batched decode prologue: the host's view of each row's position (a conversation may have been reset) -> n_past[slot]
 __global__ void k_batch_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int B) {
     const int r = threadIdx.x;

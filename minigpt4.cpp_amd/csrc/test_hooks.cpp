@@ -8,6 +8,7 @@
 #include "api_internal.hpp"
 #include "activations.hpp"
 #include "draft.hpp"
+#include "draft_host.hpp"
 #include "beam_host.hpp"
 #include "imageio.hpp"
 #include "quantize.hpp"
@@ -1471,6 +1472,91 @@ int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab
         HIP_CHECK(hipMemcpy(row_tok_io, dtok.p, 64 * 4, hipMemcpyDeviceToHost));
         return 0;
     });
+}
+// ---- speculation under sampling (draft_host.hpp, launch_draft_sample_finish) ----
+// The sampled verify pass's epilogue alone: k_sample_rows over the R rows of host logits [R][ld], then k_draft_sample_finish on a two-slot state.  Everything that indexes
+// device memory is checked here.
+int minigpt4_amd_test_draft_sample(const float *logits, int R, int n_vocab, int ld, const int32_t *rows, const int32_t *table, int n_table, const uint32_t *bitmaps, int n_bitmaps,
+                                   const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k, const uint64_t *seed_draws, const int32_t *row_tok, int slot,
+                                   int32_t *state_io, float *slot_logits_io, int32_t *res_out, int32_t *out, float *ms_out) {
+    static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(SampleRow) == 72 && sizeof(SampleOut) == (5 + 2 * SAMPLE_MAX) * 4, "the hook's word layout");
+    if (!logits || !rows || !bitmap_of_row || !temp_top_p || !top_k || !seed_draws || !row_tok || !state_io || !slot_logits_io || !res_out || !out || R < 1 || R > DRAFT_ROWS ||
+        n_vocab < 1 || ld < n_vocab || slot < 0 || slot > 1 || n_table < 0 || (n_table > 0 && !table) || n_bitmaps < 0 || (n_bitmaps > 0 && !bitmaps)) return 1;
+    for (int r = 0; r < R; r++) {
+        const int32_t *w = rows + 8 * (size_t)r;
+        if (w[0] != r || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table || bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps ||
+            top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
+        const float temp = temp_top_p[2 * (size_t)r], top_p = temp_top_p[2 * (size_t)r + 1];
+        if (!std::isfinite(temp) || !(temp > 0.0f) || !(top_p > 0.0f) || !(top_p <= 1.0f)) return 1;
+        std::vector<int> ids;
+        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)R * ld, T = (size_t)std::max(n_table, 1), W = (size_t)constraint_words(n_vocab), NB = (size_t)std::max(n_bitmaps, 1), V = (size_t)n_vocab;
+        DevBuf dl(n * 4), dr((size_t)R * sizeof(SampleRow)), dt(T * sizeof(PenEntry)), dout((size_t)R * sizeof(SampleOut)), db(NB * W * 4), dtok(DRAFT_ROWS * 4), dslot(4), dst(6 * 4),
+               dkeep(2 * V * 4), dres(DRAFT_SAMPLE_RES * 4);
+        std::vector<SampleRow> tab((size_t)R);
+        for (size_t r = 0; r < (size_t)R; r++) {
+            memcpy(&tab[r].pen, rows + 8 * r, sizeof(PenRow));
+            tab[r].allowed = bitmap_of_row[r] < 0 ? nullptr : db.as<unsigned>() + (size_t)bitmap_of_row[r] * W;
+            tab[r].temp = temp_top_p[2 * r]; tab[r].top_p = temp_top_p[2 * r + 1]; tab[r].top_k = top_k[r]; tab[r].tok_index = -1;
+            tab[r].seed = seed_draws[2 * r]; tab[r].draws = seed_draws[2 * r + 1];
+        }
+        int tok[DRAFT_ROWS]; for (int r = 0; r < DRAFT_ROWS; r++) tok[r] = r < R ? row_tok[r] : -1;
+        // the state as the engine keeps it: n_past[2] | argmax[2] | feed[2]; the caller's layout is per slot (n_past, argmax, feed)
+        int st[6]; for (int s = 0; s < 2; s++) for (int f = 0; f < 3; f++) st[2 * f + s] = state_io[3 * s + f];
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, tab.data(), (size_t)R * sizeof(SampleRow), hipMemcpyHostToDevice));
+        if (n_bitmaps > 0) HIP_CHECK(hipMemcpy(db.p, bitmaps, (size_t)n_bitmaps * W * 4, hipMemcpyHostToDevice));
+        if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dtok.p, tok, sizeof(tok), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dslot.p, &slot, 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dst.p, st, sizeof(st), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dkeep.p, slot_logits_io, 2 * V * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xFF, (size_t)R * sizeof(SampleOut))); HIP_CHECK(hipMemset(dres.p, 0xFF, DRAFT_SAMPLE_RES * 4));   // what the kernels leave out shows as -1
+        Events ev;
+        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+        if (!launch_sample_rows(dl.as<float>(), ld, n_vocab, R, dr.as<SampleRow>(), dt.as<PenEntry>(), dout.as<SampleOut>(), nullptr, nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.a, nullptr));
+        if (!launch_draft_sample_finish(dl.as<float>(), ld, n_vocab, R, dtok.as<int>(), dout.as<SampleOut>(), dslot.as<int>(), dst.as<int>(), dst.as<int>() + 2, dst.as<int>() + 4,
+                                        dkeep.as<float>(), dres.as<int>(), nullptr)) return 3;
+        HIP_CHECK(hipEventRecord(ev.b, nullptr));
+        HIP_CHECK(hipDeviceSynchronize());
+        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+        if (ms_out) *ms_out = t;                                                 // k_draft_sample_finish alone
+        HIP_CHECK(hipMemcpy(out, dout.p, (size_t)R * sizeof(SampleOut), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(res_out, dres.p, DRAFT_SAMPLE_RES * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(st, dst.p, sizeof(st), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(slot_logits_io, dkeep.p, 2 * V * 4, hipMemcpyDeviceToHost));
+        for (int s = 0; s < 2; s++) for (int f = 0; f < 3; f++) state_io[3 * s + f] = st[2 * f + s];
+        return 0;
+    });
+}
+// draft_stage alone, no GPU
+int minigpt4_amd_test_draft_tables(const int32_t *hist, int n_hist, int32_t x0, const int32_t *draft, int n_draft, int32_t repeat_last_n, float repeat_penalty, float alpha_presence,
+                                   float alpha_frequency, int penalize_nl, const int32_t *bias_id, const float *bias_val, int n_bias, int n_ctx, int n_vocab, const uint16_t *trans,
+                                   const uint32_t *accept, int n_states, int state, const uint8_t *vocab, const int32_t *off, int32_t *n_rows_out, int32_t *cut_out,
+                                   int32_t *rows_out, int32_t *table_out, int table_cap, int32_t *n_table_out, int32_t *states_out) {
+    if (n_hist < 0 || (n_hist > 0 && !hist) || n_draft < 0 || n_draft > DRAFT_ROWS - 1 || (n_draft > 0 && !draft) || n_bias < 0 || n_bias > PEN_BIAS_MAX ||
+        (n_bias > 0 && (!bias_id || !bias_val)) || n_ctx < 1 || n_vocab < 1 || x0 < 0 || x0 >= n_vocab || !n_rows_out || !cut_out || !rows_out || !table_out || table_cap < 0 ||
+        !n_table_out || !states_out) return 1;
+    for (int i = 0; i < n_draft; i++) if (draft[i] < 0 || draft[i] >= n_vocab) return 1;
+    for (int i = 0; i < n_bias; i++) if (bias_id[i] < 0 || bias_id[i] >= n_vocab) return 1;
+    ConstraintDfa dfa;
+    if (trans) {
+        if (!accept || !vocab || !off || n_states < 2 || n_states > CONSTRAINT_MAX_STATES || state < 0 || state >= n_states) return 1;
+        for (size_t i = 0; i < (size_t)n_states * 256; i++) if (trans[i] >= n_states) return 1;
+        for (int i = 0; i < n_vocab; i++) if (off[i] < 0 || off[i + 1] < off[i]) return 1;
+        dfa.n_states = n_states; dfa.trans.assign(trans, trans + (size_t)n_states * 256); dfa.accept.assign(accept, accept + ((size_t)n_states + 31) / 32);
+    }
+    auto piece = [&](int id, const unsigned char **b, int *n) { if (id < 0 || id >= n_vocab) return false; *b = vocab + off[id]; *n = off[id + 1] - off[id]; return true; };
+    const PenParams pp{repeat_last_n, repeat_penalty, alpha_presence, alpha_frequency, penalize_nl};
+    DraftStage st;
+    draft_stage(hist, (size_t)n_hist, x0, draft, n_draft, pp, bias_id, bias_val, n_bias, n_ctx, n_vocab, trans ? &dfa : nullptr, state, piece, st);
+    *n_rows_out = st.n_rows; *cut_out = st.cut; *n_table_out = (int)st.entries.size();
+    if ((int)st.entries.size() > table_cap) return 4;
+    memcpy(rows_out, st.rows.data(), st.rows.size() * sizeof(PenRow));
+    memcpy(table_out, st.entries.data(), st.entries.size() * sizeof(PenEntry));
+    for (int r = 0; r < st.n_rows; r++) states_out[r] = st.state[(size_t)r];
+    return 0;
 }
 // ---- packed prompt rows of several conversations (Engine::prefill_batch) ----
 // [n_seg][3] (slot, rows, pos0) -> the engine's device table [n_seg][4] (slot, first packed row, rows, pos0); false on a segment outside the caches

@@ -270,6 +270,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_state_load_file.argtypes = [VOID_PTR, I32, CHAR_PTR]
         L.minigpt4_amd_state_peek.argtypes = [VOID_PTR, SIZE_T, I64P]
         L.minigpt4_amd_state_info.argtypes = [VOID_PTR, I64P]
+        L.minigpt4_amd_verify_draft_sampled.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_decode_lookup_sampled.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, F32, I32, F32, INT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_speculation_info.argtypes = [VOID_PTR, I64P]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -330,6 +333,10 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_sample_rule.argtypes = [FLOAT_PTR, I32, F32, F32, ctypes.c_uint32, FLOAT_PTR, INT_PTR]
         L.minigpt4_amd_test_sample_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, U32P, I32, INT_PTR, FLOAT_PTR, INT_PTR, U64P, INT_PTR, INT_PTR, INT_PTR,
                                                     FLOAT_PTR]
+        L.minigpt4_amd_test_draft_sample.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, INT_PTR, I32, U32P, I32, INT_PTR, FLOAT_PTR, INT_PTR, U64P, INT_PTR, I32, INT_PTR, FLOAT_PTR,
+                                                     INT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_draft_tables.argtypes = [INT_PTR, I32, I32, INT_PTR, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, I32, I32, U16P, U32P, I32, I32, P(ctypes.c_uint8),
+                                                     INT_PTR, INT_PTR, INT_PTR, INT_PTR, INT_PTR, I32, INT_PTR, INT_PTR]
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
@@ -589,6 +596,124 @@ class MiniGPT4SharedLibrary:
                                                    out.ctypes.data_as(INT_PTR), n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR)):
             raise RuntimeError("decode_lookup failed: " + self.library.minigpt4_amd_last_error().decode("utf-8", errors="replace"))
         return dict(tokens=out[:int(n[0])].copy(), passes=int(st[0]), steps=int(st[1]), sent=int(st[2]), accepted=int(st[3]))
+
+    SPECULATION_INFO_FIELDS = ("passes", "rows", "sent", "accepted", "launches", "stuck", "cut")
+
+    def amd_verify_draft_sampled(self, ctx, draft: Sequence[int], temp=0.8, top_k=40, top_p=0.9, want_rows: bool = False, want_logits: bool = False) -> dict:
+        """amd_verify_draft under sampling: every row of the pass is sampled with the draw plain sampled decoding (amd_end_chat_batch_sampled) would use at its position; a
+        draft token is kept exactly when the sample of the row before it equals it.  dict(ids [1 + m] i32: the emitted tokens; next: the sample of row m, which the next
+        decision recomputes (draft behind it); want_rows: row_sampled [1 + len(draft)] i32, -1 for a row not evaluated; want_logits: row_logits [1 + len(draft)][n_vocab]
+        f32, NaN rows where not evaluated).  include/minigpt4_amd.h states the rule."""
+        d = np.ascontiguousarray(draft, np.int32).reshape(-1)
+        n = len(d)
+        ids, n_out, nxt = np.zeros(n + 1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        rs = np.zeros(n + 1, np.int32) if want_rows else None
+        rl = np.full((n + 1, int(self.library.minigpt4_amd_n_vocab(ctx.ptr))), np.nan, np.float32) if want_logits and ctx is not None else None
+        rc = self.library.minigpt4_amd_verify_draft_sampled(ctx.ptr if ctx is not None else None, d.ctypes.data_as(INT_PTR) if n else None, n, float(temp), int(top_k), float(top_p),
+                                                            ids.ctypes.data_as(INT_PTR), n_out.ctypes.data_as(INT_PTR), nxt.ctypes.data_as(INT_PTR),
+                                                            rs.ctypes.data_as(INT_PTR) if rs is not None else None, rl.ctypes.data_as(FLOAT_PTR) if rl is not None else None)
+        if rc:
+            raise RuntimeError("verify_draft_sampled failed: " + self._err())
+        out = dict(ids=ids[:int(n_out[0])].copy(), next=int(nxt[0]))
+        if rs is not None:
+            out["row_sampled"] = rs
+        if rl is not None:
+            out["row_logits"] = rl
+        return out
+
+    def amd_decode_lookup_sampled(self, ctx, corpus: Sequence[int], max_tokens: int, ngram_max: int = 3, ngram_min: int = 1, n_draft: int = 4, temp=0.8, top_k=40,
+                                  top_p=0.9) -> dict:
+        """amd_decode_lookup under sampling (amd_verify_draft_sampled per step; no match: its n_draft = 0 form).  dict(tokens [n] i32, passes, steps, sent, accepted)."""
+        c = np.ascontiguousarray(corpus, np.int32).reshape(-1)
+        out, n, st = np.zeros(max(int(max_tokens), 1), np.int32), np.zeros(1, np.int32), np.zeros(4, np.int32)
+        if self.library.minigpt4_amd_decode_lookup_sampled(ctx.ptr if ctx is not None else None, c.ctypes.data_as(INT_PTR) if len(c) else None, len(c), int(max_tokens),
+                                                           int(ngram_max), int(ngram_min), int(n_draft), float(temp), int(top_k), float(top_p), out.ctypes.data_as(INT_PTR),
+                                                           n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("decode_lookup_sampled failed: " + self._err())
+        return dict(tokens=out[:int(n[0])].copy(), passes=int(st[0]), steps=int(st[1]), sent=int(st[2]), accepted=int(st[3]))
+
+    def amd_speculation_info(self, ctx) -> dict:
+        """dict(passes: sampled verify passes, rows: rows they evaluated, sent / accepted: draft tokens, launches: sampling launches made by these calls, stuck: picks
+        without a participating id, cut: draft tokens cut by a constraint) -- of the context so far."""
+        out = (ctypes.c_int64 * 8)()
+        if self.library.minigpt4_amd_speculation_info(ctx.ptr if ctx is not None else None, out):
+            raise RuntimeError("speculation_info failed: " + self._err())
+        return dict(zip(self.SPECULATION_INFO_FIELDS, (int(x) for x in out)))
+
+    def amd_test_draft_sample(self, logits: np.ndarray, n_vocab: int, rows: np.ndarray, table: np.ndarray, params, top_k, seed_draws, row_tok: Sequence[int], slot: int,
+                              state: np.ndarray, slot_logits: np.ndarray, bitmaps=None, bitmap_of_row=None) -> dict:
+        """The sampled verify pass's epilogue alone (include/minigpt4_amd_test.h): k_sample_rows over the R rows of host logits [R][ld] (descriptors as
+        amd_test_sample_rows, descriptor r on row r), then k_draft_sample_finish with the pass's row tokens on a two-slot state [2][3] (n_past, argmax, feed) and the
+        slots' logits rows [2][n_vocab].  dict(m, picks [R], stuck [R], res [17]; pick, stuck, word, n_cand, kept, ids, p as amd_test_sample_rows; state [2][3],
+        slot_logits [2][n_vocab] afterwards; ms: k_draft_sample_finish alone)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        R = lg.shape[0]
+        rw = np.ascontiguousarray(rows, np.int32).reshape(-1, 8)
+        tb = np.ascontiguousarray(table, np.int32).reshape(-1, 4)
+        pr = np.ascontiguousarray(params, np.float32).reshape(-1, 2)
+        tk = np.ascontiguousarray(top_k, np.int32).reshape(-1)
+        sd = np.ascontiguousarray(seed_draws, np.uint64).reshape(-1, 2)
+        W = ((int(n_vocab) + 31) // 32 + 3) // 4 * 4
+        bm = np.zeros((0, W), np.uint32) if bitmaps is None else np.ascontiguousarray(bitmaps, np.uint32)
+        assert bm.ndim == 2 and bm.shape[1] == W
+        br = np.full(R, -1, np.int32) if bitmap_of_row is None else np.ascontiguousarray(bitmap_of_row, np.int32).reshape(-1)
+        rt = np.ascontiguousarray(row_tok, np.int32).reshape(-1)
+        st = np.ascontiguousarray(state, np.int32).copy()
+        keep = np.ascontiguousarray(slot_logits, np.float32).copy()
+        assert len(rw) == R and len(pr) == R and len(tk) == R and len(sd) == R and len(br) == R and len(rt) == R and st.shape == (2, 3) and keep.shape == (2, int(n_vocab))
+        out, res, ms = np.zeros((max(R, 1), 5 + 128), np.int32), np.zeros(17, np.int32), ctypes.c_float()
+        U32P = ctypes.POINTER(ctypes.c_uint32)
+        rc = self.library.minigpt4_amd_test_draft_sample(lg.ctypes.data_as(FLOAT_PTR), R, int(n_vocab), lg.shape[1], rw.ctypes.data_as(INT_PTR),
+                                                         tb.ctypes.data_as(INT_PTR) if len(tb) else None, len(tb), bm.ctypes.data_as(U32P) if len(bm) else None, len(bm),
+                                                         br.ctypes.data_as(INT_PTR), pr.ctypes.data_as(FLOAT_PTR), tk.ctypes.data_as(INT_PTR),
+                                                         sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), rt.ctypes.data_as(INT_PTR), int(slot), st.ctypes.data_as(INT_PTR),
+                                                         keep.ctypes.data_as(FLOAT_PTR), res.ctypes.data_as(INT_PTR), out.ctypes.data_as(INT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_draft_sample rc={rc}: " + self._err())
+        return dict(m=int(res[0]), picks=res[1:1 + R].copy(), stuck_flags=res[9:9 + R].copy(), res=res, pick=out[:, 0].copy(), stuck=out[:, 1].copy(),
+                    word=out[:, 2].copy().view(np.uint32), n_cand=out[:, 3].copy(), kept=out[:, 4].copy(), ids=out[:, 5:69].copy(),
+                    p=np.ascontiguousarray(out[:, 69:133]).view(np.float32), state=st, slot_logits=keep, ms=float(ms.value))
+
+    def amd_test_draft_tables(self, history: Sequence[int], x0: int, draft: Sequence[int], n_ctx: int, n_vocab: int, repeat_last_n: int = 64, repeat_penalty: float = 1.0,
+                              alpha_presence: float = 0.0, alpha_frequency: float = 0.0, penalize_nl: int = 1, bias=None, trans=None, accept=None, state: int = 0,
+                              pieces: Optional[Sequence[bytes]] = None) -> dict:
+        """The host staging of a sampled verify pass alone (no GPU; csrc/draft_host.hpp): dict(n_rows, cut, rows [R][8] i32 PenRow words, tables: a list of R arrays
+        [n][4] i32 (id, count, bias bits, has_bias), states [R]).  trans [S][256] u16 + accept bitmap + pieces (bytes per token id): the constraint; None: none."""
+        h = np.ascontiguousarray(history, np.int32).reshape(-1)
+        d = np.ascontiguousarray(draft, np.int32).reshape(-1)
+        pairs = list(bias.items()) if isinstance(bias, dict) else list(bias or [])
+        bi = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        bv = np.ascontiguousarray([p[1] for p in pairs], np.float32)
+        U8P, U16P, U32P = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint32)
+        tr = ac = vb = of = None
+        n_states = 0
+        if trans is not None:
+            tr = np.ascontiguousarray(trans, np.uint16).reshape(-1, 256)
+            n_states = len(tr)
+            ac = np.zeros((n_states + 31) // 32 + 1, np.uint32)
+            a = np.ascontiguousarray(accept, np.uint32).reshape(-1)
+            ac[:len(a)] = a
+            assert pieces is not None and len(pieces) == int(n_vocab)
+            of = np.zeros(int(n_vocab) + 1, np.int32)
+            of[1:] = np.cumsum([len(p) for p in pieces])
+            vb = np.frombuffer(b"".join(pieces) + b"\0", np.uint8).copy()
+        cap = 8 * 1281
+        n_rows, cut, n_tab = I32(0), I32(0), I32(0)
+        rows, tab, states = np.zeros((8, 8), np.int32), np.zeros((cap, 4), np.int32), np.zeros(8, np.int32)
+        rc = self.library.minigpt4_amd_test_draft_tables(h.ctypes.data_as(INT_PTR) if len(h) else None, len(h), int(x0), d.ctypes.data_as(INT_PTR) if len(d) else None, len(d),
+                                                         int(repeat_last_n), float(repeat_penalty), float(alpha_presence), float(alpha_frequency), int(penalize_nl),
+                                                         bi.ctypes.data_as(INT_PTR) if len(pairs) else None, bv.ctypes.data_as(FLOAT_PTR) if len(pairs) else None, len(pairs),
+                                                         int(n_ctx), int(n_vocab), tr.ctypes.data_as(U16P) if tr is not None else None,
+                                                         ac.ctypes.data_as(U32P) if ac is not None else None, n_states, int(state),
+                                                         vb.ctypes.data_as(U8P) if vb is not None else None, of.ctypes.data_as(INT_PTR) if of is not None else None,
+                                                         ctypes.byref(n_rows), ctypes.byref(cut), rows.ctypes.data_as(INT_PTR), tab.ctypes.data_as(INT_PTR), cap, ctypes.byref(n_tab),
+                                                         states.ctypes.data_as(INT_PTR))
+        if rc:
+            raise RuntimeError(f"test_draft_tables rc={rc}")
+        R = int(n_rows.value)
+        rows = rows[:R].copy()
+        return dict(n_rows=R, cut=int(cut.value), rows=rows, tables=[tab[rows[r, 1]:rows[r, 1] + rows[r, 2]].copy() for r in range(R)], states=states[:R].copy())
 
     # ---- beam search (include/minigpt4_amd.h)
     def amd_beam_search(self, ctx, slots: Sequence[int], max_tokens: int, length_penalty: float = 1.0, n_best: Optional[int] = None, with_stats: bool = False):
