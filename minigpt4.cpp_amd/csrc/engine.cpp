@@ -94,10 +94,10 @@ Engine::~Engine() {
         // the owning members would free themselves right after this body: hipFree / hipHostFree wait for a stream that never drains.  Every handle of the class is
         // listed here and nowhere else
         abandon_all(pfx_k_, pfx_v_, score_buf_, score_lp_, score_glp_, score_tgt_, score_greedy_, topn_d_, topn_h_, topn_in_, topn_hin_, topn_ev_,
-                    pen_d_, pen_h_, pen_out_d_, pen_out_h_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
-                    guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_d_, con_h_, con_out_d_, con_out_h_, con_row_h_,
+                    pen_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
+                    guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_stage_, con_row_h_,
                     state_d_[0], state_d_[1], state_h_[0], state_h_[1], state_sum_d_, state_sum_h_, state_cs_, state_ev_kernel_[0], state_ev_kernel_[1], state_ev_copy_[0],
-                    state_ev_copy_[1], smp_d_, smp_h_, smp_out_d_, smp_out_h_, smp_ev_, sdr_res_, sdr_hres_);
+                    state_ev_copy_[1], smp_, sdr_res_, sdr_hres_);
         for (Constraint &c : con_) c.dev.abandon();
         return;
     }
@@ -1683,11 +1683,11 @@ void Engine::step_begin(int B, bool verify) {
     if (verify) launch_draft_begin(d_npast_, d_bslot_, d_bpos_, stream_); else launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
 }
 // the step as one hipGraph per row count: token ids, conversations and positions live in device memory, so the same graph serves every set of B conversations
-// and every entry point (verify: every R rows of any conversation)
-void Engine::step_launch(int B, bool verify) {
-    if (!use_graph_) { forward_batch(B, stream_, verify); return; }
-    hipGraphExec_t &ge = (verify ? spec_graph_ : batch_graph_)[(size_t)B];
-    if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_, verify); });
+// and every entry point (verify: every R rows of any conversation; without its epilogue: the sampled verify pass, whose epilogue follows k_sample_rows)
+void Engine::step_launch(int B, bool verify, bool epilogue) {
+    if (!use_graph_) { forward_batch(B, stream_, verify, epilogue); return; }
+    hipGraphExec_t &ge = (!verify ? batch_graph_ : epilogue ? spec_graph_ : spec_sgraph_)[(size_t)B];
+    if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_, verify, epilogue); });
     HIP_CHECK(hipGraphLaunch(ge, stream_));
 }
 // oracle-order arithmetic exists for the single-conversation pass only: one pass per staged row (same results as the batched step is tested to give)
@@ -1809,14 +1809,23 @@ int Engine::guide_prepare(const char *name, const int *pos, const int *neg, int 
     if (check_slots(all, 2 * n)) return refuse("the 2 n conversations must be distinct and in range");
     if (!std::isfinite(scale)) return refuse("scale must be finite");
     if (weights_missing()) return refuse(last_error());
+    return logits_ready(refuse, all, 2 * n, [&] { return !prefill_batch(all, 2 * n); }) ? 0 : 1;   // one packed pass over all 2 n queues
+}
+template <typename Refuse, typename Evaluate> bool Engine::logits_ready(Refuse refuse, const int *slots, int n, Evaluate evaluate) {
     auto no_logits = [&]() -> int {
-        for (int i = 0; i < 2 * n; i++) { const Conversation &cv = conv_[(size_t)all[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return all[i]; }
+        for (int i = 0; i < n; i++) { const Conversation &cv = conv_[(size_t)slots[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return slots[i]; }
         return -1;
     };
     int bad = no_logits();                                                    // nothing queued and nothing evaluated: known before anything runs
-    if (bad < 0) { if (prefill_batch(all, 2 * n)) return refuse("the queued rows could not be evaluated: " + last_error()); bad = no_logits(); }
-    if (bad >= 0) return refuse("conversation " + std::to_string(bad) + " has no current logits");
-    return 0;
+    if (bad < 0) { if (!evaluate()) { refuse("the queued rows could not be evaluated: " + last_error()); return false; } bad = no_logits(); }
+    if (bad >= 0) { refuse("conversation " + std::to_string(bad) + " has no current logits"); return false; }
+    return true;
+}
+template <typename Refuse> bool Engine::sampling_params_ok(Refuse refuse, float temp, int top_k, float top_p) const {
+    if (!std::isfinite(temp) || !(temp > 0.0f)) { refuse("temp must be finite and > 0"); return false; }
+    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, (int)llm_.n_vocab)) { refuse("top_k outside 1 .. min(64, n_vocab)"); return false; }
+    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) { refuse("top_p outside (0, 1]"); return false; }
+    return true;
 }
 int Engine::guided_logits(const int *pos, const int *neg, int n, float scale, float *mixed_out, int *pick_out) {
     int all[MAX_CONVERSATIONS];
@@ -1845,7 +1854,7 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
     const int V = (int)llm_.n_vocab;
     const bool greedy = p.temp <= 0;
     guide_alloc();
-    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_, guide_h_ and pen_h_ feed no earlier copy
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_, guide_h_ and pen_ feed no earlier copy
     // 1. how each pair's token is chosen (the kernel's pick stands / k_pen_pick on the mixed row / the host chain), from pos's history as a sample sees it: before any shift
     enum { KERNEL = 0, PEN = 1, CHAIN = 2 };
     int how[GUIDE_MAX], pen_map[GUIDE_MAX], m_pen = 0; size_t pen_off = 0;
@@ -1899,11 +1908,11 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
         for (int i = 0; i < n; i++) {
             if (how[i] != KERNEL) continue;
             ids_out[i] = guide_h_[GUIDE_PICK + i];
-            if (ids_out[i] < 0 || ids_out[i] >= V) { sane = false; ids_out[i] = 0; }
+            if (!id_in_vocab(ids_out[i])) { sane = false; ids_out[i] = 0; }
         }
         return sane;
     };
-    auto bad_pick = [] { return HipError{hipErrorUnknown, "end_chat_guided: the device reported an id outside the vocabulary", __FILE__, __LINE__}; };
+    auto bad_pick = [] { return bad_id("end_chat_guided: the device reported an id outside the vocabulary"); };
     if (host_first) {
         if (m_pen) {
             if (!pen_launch(guide_mix_, m_pen, pen_off)) return refuse(last_error());
@@ -1944,12 +1953,6 @@ int Engine::decode_guided(const int *pos, const int *neg, int n, float scale, co
 }
 
 // ---- penalties and logit bias (engine.hpp, penalty.hpp) ----
-void Engine::pen_alloc() {
-    if (pen_d_) return;
-    const size_t bytes = PEN_HEAD + (size_t)MAX_CONVERSATIONS * PEN_TABLE_MAX * sizeof(PenEntry);
-    DevPtr<uint8_t> d(bytes); PinPtr<uint8_t> h(bytes); DevPtr<int> out_d(MAX_CONVERSATIONS * 4); PinPtr<int> out_h(MAX_CONVERSATIONS * 4);   // all four or none
-    pen_d_ = std::move(d); pen_h_ = std::move(h); pen_out_d_ = std::move(out_d); pen_out_h_ = std::move(out_h);
-}
 int Engine::pen_table(const Conversation &cv, std::vector<PenEntry> &tab) const {
     return pen_build_table(cv.hist.data(), cv.hist.size(), pen_mode_ ? cv.pen : PenParams{}, n_ctx_, (int)llm_.n_vocab, cv.bias_id.data(), cv.bias_val.data(), (int)cv.bias_id.size(), tab);
 }
@@ -1962,24 +1965,21 @@ bool Engine::pen_build_row(const Conversation &cv, int row, size_t off, PenRow *
 bool Engine::pen_stage_row(const Conversation &cv, int row, int m, size_t &off, std::vector<PenEntry> &tab) {
     PenRow r;
     if (!pen_build_row(cv, row, off, &r, tab)) return false;
-    pen_alloc();
-    pen_h_.as<PenRow>()[m] = r;
-    std::copy(tab.begin(), tab.end(), reinterpret_cast<PenEntry *>(pen_h_ + PEN_HEAD) + off);
+    pen_.alloc();
+    pen_.rows()[m] = r;
+    std::copy(tab.begin(), tab.end(), pen_.entries() + off);
     off += tab.size();
     return true;
 }
 bool Engine::pen_launch(const float *logits, int m, size_t n_ent) {
     const int V = (int)llm_.n_vocab;
-    HIP_CHECK(hipMemcpyAsync(pen_d_, pen_h_, PEN_HEAD + n_ent * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-    if (!launch_pen_pick(logits, V, V, m, pen_d_.as<const PenRow>(), reinterpret_cast<const PenEntry *>(pen_d_ + PEN_HEAD), pen_out_d_, nullptr, stream_)) return false;
-    HIP_CHECK(hipMemcpyAsync(pen_out_h_, pen_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
+    pen_.upload(n_ent, stream_);
+    if (!launch_pen_pick(logits, V, V, m, pen_.d_rows(), pen_.d_entries(), pen_.out_d(), nullptr, stream_)) return false;
+    pen_.fetch(m, sizeof(int), stream_);
     return true;
 }
 void Engine::pen_collect(int m, const int *map, int *ids) const {
-    for (int r = 0; r < m; r++) {
-        if (pen_out_h_[r] < 0 || pen_out_h_[r] >= (int)llm_.n_vocab) throw HipError{hipErrorUnknown, "the penalised pick reported an id outside the vocabulary", __FILE__, __LINE__};
-        ids[map[r]] = pen_out_h_[r];
-    }
+    for (int r = 0; r < m; r++) ids[map[r]] = device_id(pen_.out_h()[r], "the penalised pick reported an id outside the vocabulary");
 }
 // The caller has evaluated every listed conversation's queue and synchronised (greedy_raw): hist is the whole history, the pinned staging is free.
 void Engine::pen_pick(const int *slots, int n, int *ids, bool skip_constrained) {
@@ -2032,14 +2032,12 @@ void Engine::con_alloc() {
     for (size_t i = 0; i < V; i++) off[i + 1] = off[i] + (int)(i < llm_.pieces.size() ? llm_.pieces[i].size() : 0);
     std::vector<unsigned char> blob((size_t)off[V] + 1, 0);
     for (size_t i = 0; i < V && i < llm_.pieces.size(); i++) std::copy(llm_.pieces[i].begin(), llm_.pieces[i].end(), blob.begin() + off[i]);
-    const size_t stage = (size_t)MAX_CONVERSATIONS * (sizeof(ConRow) + (size_t)PEN_TABLE_MAX * sizeof(PenEntry));
-    // all seven or none, the uploads included
+    // all four or none, the uploads included
     DevPtr<unsigned char> vocab(blob.size()); DevPtr<int> offs((V + 1) * 4);
-    DevPtr<uint8_t> d(stage); PinPtr<uint8_t> h(stage); DevPtr<int> out_d(MAX_CONVERSATIONS * 4); PinPtr<int> out_h(MAX_CONVERSATIONS * 4);
+    Stage<ConRow, int> stage; stage.alloc();
     PinPtr<unsigned> row_h((size_t)constraint_words((int)V) * 4);
     HIP_CHECK(hipMemcpy(vocab, blob.data(), blob.size(), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(offs, off.data(), (V + 1) * 4, hipMemcpyHostToDevice));
-    con_vocab_ = std::move(vocab); con_off_ = std::move(offs); con_d_ = std::move(d); con_h_ = std::move(h); con_out_d_ = std::move(out_d); con_out_h_ = std::move(out_h);
-    con_row_h_ = std::move(row_h);
+    con_vocab_ = std::move(vocab); con_off_ = std::move(offs); con_stage_ = std::move(stage); con_row_h_ = std::move(row_h);
 }
 int Engine::constraint_compile(const unsigned char *pattern, long long n_bytes, int *handle) {
     auto refuse = [](const std::string &what) { set_last_error("constraint_compile: " + what); return 1; };
@@ -2133,7 +2131,7 @@ void Engine::con_pick(const int *slots, int n, int *ids) {
     if (!con_assigned_) return;                                              // no conversation of this context holds a constraint: today's path
     std::vector<PenEntry> tab;
     int m = 0, map[MAX_CONVERSATIONS]; size_t off = 0;
-    ConRow *rows = con_h_.as<ConRow>(); PenEntry *ent = reinterpret_cast<PenEntry *>(con_h_ + MAX_CONVERSATIONS * sizeof(ConRow));
+    ConRow *rows = con_stage_.rows(); PenEntry *ent = con_stage_.entries();
     const int V = (int)llm_.n_vocab, W = constraint_words(V);
     for (int i = 0; i < n; i++) {
         const int slot = slots[i], h = con_handle_[slot];
@@ -2145,28 +2143,20 @@ void Engine::con_pick(const int *slots, int n, int *ids) {
         off += tab.size(); map[m++] = i;
     }
     if (!m) return;
-    const size_t head = MAX_CONVERSATIONS * sizeof(ConRow);
-    HIP_CHECK(hipMemcpyAsync(con_d_, con_h_, head + off * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-    if (!launch_constrain_pick(logits_, V, V, m, con_d_.as<const ConRow>(), reinterpret_cast<const PenEntry *>(con_d_ + head), con_out_d_, stream_))
+    con_stage_.upload(off, stream_);
+    if (!launch_constrain_pick(logits_, V, V, m, con_stage_.d_rows(), con_stage_.d_entries(), con_stage_.out_d(), stream_))
         throw HipError{hipErrorInvalidValue, "constrained pick launch refused", __FILE__, __LINE__};
-    HIP_CHECK(hipMemcpyAsync(con_out_h_, con_out_d_, (size_t)m * 4, hipMemcpyDeviceToHost, stream_));
+    con_stage_.fetch(m, sizeof(int), stream_);
     HIP_CHECK(hipStreamSynchronize(stream_));
     for (int r = 0; r < m; r++) {
-        const int id = con_out_h_[r] & ~CONSTRAIN_STUCK;
-        if (id < 0 || id >= V) throw HipError{hipErrorUnknown, "the constrained pick reported an id outside the vocabulary", __FILE__, __LINE__};
-        if (con_out_h_[r] & CONSTRAIN_STUCK) con_info_.stuck++;
+        const int word = con_stage_.out_h()[r], id = device_id(word & ~CONSTRAIN_STUCK, "the constrained pick reported an id outside the vocabulary");
+        if (word & CONSTRAIN_STUCK) con_info_.stuck++;
         ids[map[r]] = id;
         con_walk(slots[map[r]], id);
     }
     con_info_.launches++;
 }
 // ---- sampled batched steps decided on the device (engine.hpp, sampling.hpp) ----
-void Engine::smp_alloc() {
-    if (smp_d_) return;
-    const size_t stage = SMP_HEAD + (size_t)MAX_CONVERSATIONS * PEN_TABLE_MAX * sizeof(PenEntry), res = (size_t)MAX_CONVERSATIONS * sizeof(SampleOut);
-    DevPtr<uint8_t> d(stage); PinPtr<uint8_t> h(stage); DevPtr<SampleOut> out_d(res); PinPtr<SampleOut> out_h(res); OwnedEvent ev(0);   // all five or none
-    smp_d_ = std::move(d); smp_h_ = std::move(h); smp_out_d_ = std::move(out_d); smp_out_h_ = std::move(out_h); smp_ev_ = std::move(ev);
-}
 int Engine::set_conversation_seed(int slot, uint64_t seed, uint64_t draws) {
     if (slot < 0 || slot >= (int)conv_.size()) { set_last_error("conversation_seed: conversation index out of range"); return 1; }
     smp_seed_[slot] = seed; smp_draws_[slot] = draws;
@@ -2182,62 +2172,53 @@ int Engine::smp_prepare(const char *name, const int *slots, int n, float temp, i
     const int bad = check_slots(slots, n);
     if (bad == 1) return refuse("bad slot list");
     if (bad) return refuse("conversations must be distinct and in range");
-    if (!std::isfinite(temp) || !(temp > 0.0f)) return refuse("temp must be finite and > 0");
-    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, (int)llm_.n_vocab)) return refuse("top_k outside 1 .. min(64, n_vocab)");
-    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return refuse("top_p outside (0, 1]");
+    if (!sampling_params_ok(refuse, temp, top_k, top_p)) return 1;
     if (weights_missing()) return refuse(last_error());
-    auto no_logits = [&]() -> int {
-        for (int i = 0; i < n; i++) { const Conversation &cv = conv_[(size_t)slots[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return slots[i]; }
-        return -1;
-    };
-    int none = no_logits();                                                   // nothing queued and nothing evaluated: known before anything runs
-    if (none < 0) {
+    auto flush_each = [&] {                                                   // as decode_batch: one pass each
         const SelectScope restore(this);
-        for (int i = 0; i < n; i++) { cur_ = slots[i]; if (flush()) return refuse("the queued rows could not be evaluated: " + last_error()); }   // as decode_batch: one pass each
-        none = no_logits();
-    }
-    if (none >= 0) return refuse("conversation " + std::to_string(none) + " has no current logits");
-    return 0;
+        for (int i = 0; i < n; i++) { cur_ = slots[i]; if (flush()) return false; }
+        return true;
+    };
+    return logits_ready(refuse, slots, n, flush_each) ? 0 : 1;
+}
+SampleRow Engine::smp_row(int slot, const PenRow &pen, int state, uint64_t draws, int tok_index, float temp, int top_k, float top_p) const {
+    const int h = con_handle_[slot];
+    const unsigned *allowed = h ? con_[h - 1].index + (size_t)state * constraint_words((int)llm_.n_vocab) : nullptr;
+    return SampleRow{pen, allowed, temp, top_p, top_k, tok_index, smp_seed_[slot], draws};
 }
 size_t Engine::smp_stage(const int *slots, int n, float temp, int top_k, float top_p) {
-    smp_alloc();
-    SampleRow *rows = smp_h_.as<SampleRow>(); PenEntry *ent = reinterpret_cast<PenEntry *>(smp_h_ + SMP_HEAD);
-    const int W = constraint_words((int)llm_.n_vocab);
+    smp_.alloc();
     std::vector<PenEntry> tab;
     size_t off = 0;
     for (int i = 0; i < n; i++) {
-        const int slot = slots[i], h = con_handle_[slot];
-        pen_build_row(conv_[(size_t)slot], slot, off, &rows[i].pen, tab);    // the identity included: n = 0, no flags
-        rows[i].allowed = h ? con_[h - 1].index + (size_t)con_state_[slot] * W : nullptr;
-        rows[i].temp = temp; rows[i].top_p = top_p; rows[i].top_k = top_k; rows[i].tok_index = -1;
-        rows[i].seed = smp_seed_[slot]; rows[i].draws = smp_draws_[slot];
-        std::copy(tab.begin(), tab.end(), ent + off);
+        const int slot = slots[i];
+        PenRow pen;
+        pen_build_row(conv_[(size_t)slot], slot, off, &pen, tab);            // the identity included: n = 0, no flags
+        smp_.rows()[i] = smp_row(slot, pen, con_state_[slot], smp_draws_[slot], -1, temp, top_k, top_p);
+        std::copy(tab.begin(), tab.end(), smp_.entries() + off);
         off += tab.size();
     }
     return off;
 }
-bool Engine::smp_launch(int n, size_t n_ent, bool hand) {
+bool Engine::smp_launch_on(const float *logits, int n, size_t n_ent, int *row_tok) {
     const int V = (int)llm_.n_vocab;
-    HIP_CHECK(hipMemcpyAsync(smp_d_, smp_h_, SMP_HEAD + n_ent * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-    if (!launch_sample_rows(logits_, V, V, n, smp_d_.as<const SampleRow>(), reinterpret_cast<const PenEntry *>(smp_d_ + SMP_HEAD), smp_out_d_, hand ? d_btok_ : nullptr, stream_)) return false;
-    HIP_CHECK(hipMemcpyAsync(smp_out_h_, smp_out_d_, (size_t)n * sizeof(SampleOut), hipMemcpyDeviceToHost, stream_));
-    HIP_CHECK(hipEventRecord(smp_ev_, stream_));
+    smp_.upload(n_ent, stream_);
+    return launch_sample_rows(logits, V, V, n, smp_.d_rows(), smp_.d_entries(), smp_.out_d(), row_tok, stream_);
+}
+bool Engine::smp_launch(int n, size_t n_ent, bool hand) {
+    if (!smp_launch_on(logits_, n, n_ent, hand ? d_btok_ : nullptr)) return false;
+    smp_.fetch(n, sizeof(SampleOut), stream_);
     smp_info_.launches++;
     return true;
 }
-bool Engine::smp_launch_on(const float *logits, int n, size_t n_ent) {
-    const int V = (int)llm_.n_vocab;
-    HIP_CHECK(hipMemcpyAsync(smp_d_, smp_h_, SMP_HEAD + n_ent * sizeof(PenEntry), hipMemcpyHostToDevice, stream_));
-    return launch_sample_rows(logits, V, V, n, smp_d_.as<const SampleRow>(), reinterpret_cast<const PenEntry *>(smp_d_ + SMP_HEAD), smp_out_d_, nullptr, stream_);
-}
 int Engine::sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out) {
     if (smp_prepare("sampled_candidates", slots, n, temp, top_k, top_p)) return 1;
-    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; smp_h_ feeds no earlier copy
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; smp_ feeds no earlier copy
     const size_t n_ent = smp_stage(slots, n, temp, top_k, top_p);
     if (!smp_launch(n, n_ent, /*hand=*/false)) { set_last_error("sampled_candidates: " + last_error()); return 1; }
-    HIP_CHECK(hipEventSynchronize(smp_ev_));
+    HIP_CHECK(hipEventSynchronize(smp_.event()));
     for (int i = 0; i < n; i++) {
-        const SampleOut &o = smp_out_h_[i];
+        const SampleOut &o = smp_.out_h()[i];
         if (ids_out) memcpy(ids_out + (size_t)i * SAMPLE_MAX, o.ids, sizeof(o.ids));
         if (probs_out) memcpy(probs_out + (size_t)i * SAMPLE_MAX, o.p, sizeof(o.p));
         if (n_cand_out) n_cand_out[i] = o.n_cand;
@@ -2250,11 +2231,10 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
     if (!ids_out) return refuse("ids_out is required");
     if (smp_prepare("end_chat_batch_sampled", slots, n, temp, top_k, top_p)) return 1;
     const SelectScope restore(this);
-    const int V = (int)llm_.n_vocab;
-    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_ and smp_h_ feed no earlier copy
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_ and smp_ feed no earlier copy
     // 1. the descriptors, from each history as a sample sees it: before any shift
     const size_t n_ent = smp_stage(slots, n, temp, top_k, top_p);
-    SampleRow *rows = smp_h_.as<SampleRow>();
+    SampleRow *rows = smp_.rows();
     // 2. room, and the pass's rows: a conversation that is full and cannot shift is sampled and reported, not advanced
     int B = 0, row_of[MAX_CONVERSATIONS];
     for (int i = 0; i < n; i++) {
@@ -2273,8 +2253,8 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
     auto take_picks = [&]() -> bool {
         bool sane = true;
         for (int i = 0; i < n; i++) {
-            ids_out[i] = smp_out_h_[i].pick;
-            if (ids_out[i] < 0 || ids_out[i] >= V) { sane = false; ids_out[i] = 0; }
+            ids_out[i] = smp_.out_h()[i].pick;
+            if (!id_in_vocab(ids_out[i])) { sane = false; ids_out[i] = 0; }
         }
         return sane;
     };
@@ -2282,13 +2262,13 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
     auto sampler_state = [&] {
         for (int i = 0; i < n; i++) {
             smp_draws_[slots[i]] += 1;
-            if (smp_out_h_[i].stuck == 1) smp_info_.stuck++;
+            if (smp_.out_h()[i].stuck == 1) smp_info_.stuck++;
             if (con_handle_[slots[i]]) con_walk(slots[i], ids_out[i]);
         }
     };
-    auto bad_pick = [] { return HipError{hipErrorUnknown, "end_chat_batch_sampled: the device reported an id outside the vocabulary", __FILE__, __LINE__}; };
+    auto bad_pick = [] { return bad_id("end_chat_batch_sampled: the device reported an id outside the vocabulary"); };
     if (!hand) {                                                             // parity mode, or nobody advances: the picks first
-        HIP_CHECK(hipEventSynchronize(smp_ev_));
+        HIP_CHECK(hipEventSynchronize(smp_.event()));
         if (!take_picks()) throw bad_pick();                                 // nothing has been launched for these picks yet
         sampler_state();
         if (!B) return 0;
@@ -2299,7 +2279,7 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
     }
     // 4. the weight pass: the batched step's own.  It advances the device state whatever the block says: the host's book-keeping follows it before a bad block is reported
     step_launch(B);
-    HIP_CHECK(hipEventSynchronize(smp_ev_));
+    HIP_CHECK(hipEventSynchronize(smp_.event()));
     const bool sane = take_picks();
     sampler_state();
     for (int i = 0; i < n; i++) if (row_of[i] >= 0) commit_rows(slots[i], &ids_out[i], 1, /*past=*/true);
@@ -2542,14 +2522,20 @@ int Engine::verify_draft(const int *draft, int n_draft, int *ids_out, int *n_out
     *n_out = 1 + m;
     return 0;
 }
-int Engine::decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats) {
-    auto refuse = [](const char *what) { set_last_error(std::string("decode_lookup: ") + what); return 1; };
+int Engine::lookup_check(const char *name, const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, const int *tokens_out, const int *n_tokens,
+                         const int *stats) const {
+    auto refuse = [&](const char *what) { set_last_error(std::string(name) + ": " + what); return 1; };
     if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
     if (n_corpus < 0 || (n_corpus > 0 && !corpus)) return refuse("bad corpus");
     if (max_tokens < 1 || !tokens_out || !n_tokens || !stats) return refuse("max_tokens >= 1, tokens_out, n_tokens and stats are required");
     if (ngram_min < 1 || ngram_max < ngram_min) return refuse("need 1 <= ngram_min <= ngram_max");
     if (n_draft < 1 || n_draft > spec_max_) return refuse("n_draft outside [1, max_draft]");
     for (int i = 0; i < n_corpus; i++) if (corpus[i] < 0 || corpus[i] >= (int)llm_.n_vocab) return refuse("corpus token id out of range");
+    return 0;
+}
+int Engine::decode_lookup(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out, int *n_tokens, int *stats) {
+    auto refuse = [](const char *what) { set_last_error(std::string("decode_lookup: ") + what); return 1; };
+    if (lookup_check("decode_lookup", corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats)) return 1;
     if (weights_missing()) return 1;
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
@@ -2583,12 +2569,6 @@ void Engine::sdr_alloc() {
     DevPtr<int> d(DRAFT_SAMPLE_RES * 4); PinPtr<int> h(DRAFT_SAMPLE_RES * 4);   // both or none
     sdr_res_ = std::move(d); sdr_hres_ = std::move(h);
 }
-void Engine::spec_pass_launch(int R) {
-    if (!use_graph_) { forward_batch(R, stream_, /*verify=*/true, /*epilogue=*/false); return; }
-    hipGraphExec_t &ge = spec_sgraph_[(size_t)R];
-    if (!ge) capture_graph(ge, [&] { forward_batch(R, stream_, /*verify=*/true, /*epilogue=*/false); });
-    HIP_CHECK(hipGraphLaunch(ge, stream_));
-}
 int Engine::speculation_info(long long out[8]) const {
     if (!out) { set_last_error("speculation_info: no output array"); return 1; }
     const SpecInfo &i = spec_info_;
@@ -2604,17 +2584,15 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
     if (n_draft > 0 && !draft) return refuse("draft is NULL");
     if (!ids_out || !n_out || !next_out) return refuse("ids_out, n_out and next_out are required");
     for (int i = 0; i < n_draft; i++) if (draft[i] < 0 || draft[i] >= V) return refuse("draft token id out of range");
-    if (!std::isfinite(temp) || !(temp > 0.0f)) return refuse("temp must be finite and > 0");
-    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, V)) return refuse("top_k outside 1 .. min(64, n_vocab)");
-    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return refuse("top_p outside (0, 1]");
+    if (!sampling_params_ok(refuse, temp, top_k, top_p)) return 1;
     if (weights_missing()) return refuse(last_error());
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
     if (flush()) return refuse("the queued rows could not be evaluated: " + last_error());
     if (!cv.has_logits) return refuse("the conversation has no current logits");
     if (cv.n_past + 1 > n_ctx_ && !shift_allows(1)) return refuse("context full");   // before anything is decided: no draw is counted for a call that cannot emit
-    HIP_CHECK(hipStreamSynchronize(stream_));                                // the history is whole; h_bstage_ and smp_h_ feed no earlier copy
-    const int slot = cur_, handle = con_handle_[slot], W = constraint_words(V);
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the history is whole; h_bstage_ and smp_ feed no earlier copy
+    const int slot = cur_, handle = con_handle_[slot];
     const uint64_t c0 = smp_draws_[slot];
     sdr_alloc();
     // 1. x0 = D(L, h, q, c): the sampled step's own descriptor (history before the shift) and launch, on the conversation's row; the host needs the pick for the rows' tables
@@ -2622,12 +2600,11 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
     if (cv.n_past + 1 > n_ctx_ && make_room(1)) return refuse("context full");
     auto decide = [&](size_t n_ent, int *stuck) -> int {                     // the staged descriptor on logits_, the 8 bytes {pick, stuck} awaited
         if (!smp_launch_on(logits_, 1, n_ent)) throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
-        HIP_CHECK(hipMemcpyAsync(smp_out_h_, smp_out_d_, 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        smp_.fetch(1, 2 * sizeof(int), stream_);
         HIP_CHECK(hipStreamSynchronize(stream_));
         spec_info_.launches++;
-        const int id = smp_out_h_[0].pick;
-        if (id < 0 || id >= V) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an id outside the vocabulary", __FILE__, __LINE__};
-        *stuck = smp_out_h_[0].stuck == 1;
+        const int id = device_id(smp_.out_h()[0].pick, "verify_draft_sampled: the device reported an id outside the vocabulary");
+        *stuck = smp_.out_h()[0].stuck == 1;
         return id;
     };
     int stuck0 = 0;
@@ -2667,19 +2644,13 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
         }
     } else {
         // 3. behind one wait: the slab, the pass without an epilogue, the R decisions with draws c + 1 + r, the epilogue, the result block
-        SampleRow *rows = smp_h_.as<SampleRow>();
-        for (int r = 0; r < R; r++) {
-            rows[r].pen = st.rows[(size_t)r];
-            rows[r].allowed = handle ? con_[handle - 1].index + (size_t)st.state[(size_t)r] * W : nullptr;
-            rows[r].temp = temp; rows[r].top_p = top_p; rows[r].top_k = top_k; rows[r].tok_index = -1;
-            rows[r].seed = smp_seed_[slot]; rows[r].draws = c0 + 1 + (uint64_t)r;
-        }
-        std::copy(st.entries.begin(), st.entries.end(), reinterpret_cast<PenEntry *>(smp_h_ + SMP_HEAD));
+        for (int r = 0; r < R; r++) smp_.rows()[r] = smp_row(slot, st.rows[(size_t)r], st.state[(size_t)r], c0 + 1 + (uint64_t)r, -1, temp, top_k, top_p);
+        std::copy(st.entries.begin(), st.entries.end(), smp_.entries());
         stage_row(0, x0, slot, p); for (int r = 1; r < R; r++) staged_token(r) = draft[r - 1];   // k_draft_begin spreads row 0's conversation and position
         step_begin(R, /*verify=*/true);
-        spec_pass_launch(R);
+        step_launch(R, /*verify=*/true, /*epilogue=*/false);
         if (!smp_launch_on(spec_logits_, R, st.entries.size())) throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
-        if (!launch_draft_sample_finish(spec_logits_, V, V, R, d_btok_, smp_out_d_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, sdr_res_, stream_))
+        if (!launch_draft_sample_finish(spec_logits_, V, V, R, d_btok_, smp_.out_d(), d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, sdr_res_, stream_))
             throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
         spec_info_.launches++; spec_info_.rows += R;
         HIP_CHECK(hipMemcpyAsync(sdr_hres_, sdr_res_, DRAFT_SAMPLE_RES * 4, hipMemcpyDeviceToHost, stream_));
@@ -2696,7 +2667,7 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
         if (!sane) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an accepted count outside the pass", __FILE__, __LINE__};
         for (int r = 0; r < R; r++) { if (row_sampled) row_sampled[r] = sdr_hres_[1 + r]; spec_info_.stuck += sdr_hres_[1 + DRAFT_ROWS + r] == 1; }
         next = sdr_hres_[1 + m];
-        if (next < 0 || next >= V) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an id outside the vocabulary", __FILE__, __LINE__};
+        device_id(next, "verify_draft_sampled: the device reported an id outside the vocabulary");
     }
     spec_info_.accepted += m;
     ids_out[0] = x0; for (int i = 0; i < m; i++) ids_out[1 + i] = draft[i];
@@ -2707,15 +2678,8 @@ int Engine::decode_lookup_sampled(const int *corpus, int n_corpus, int max_token
                                   int *n_tokens, int *stats) {
     static const char *const name = "decode_lookup_sampled";
     auto refuse = [](const char *what) { set_last_error(std::string(name) + ": " + what); return 1; };
-    if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
-    if (n_corpus < 0 || (n_corpus > 0 && !corpus)) return refuse("bad corpus");
-    if (max_tokens < 1 || !tokens_out || !n_tokens || !stats) return refuse("max_tokens >= 1, tokens_out, n_tokens and stats are required");
-    if (ngram_min < 1 || ngram_max < ngram_min) return refuse("need 1 <= ngram_min <= ngram_max");
-    if (n_draft < 1 || n_draft > spec_max_) return refuse("n_draft outside [1, max_draft]");
-    for (int i = 0; i < n_corpus; i++) if (corpus[i] < 0 || corpus[i] >= (int)llm_.n_vocab) return refuse("corpus token id out of range");
-    if (!std::isfinite(temp) || !(temp > 0.0f)) return refuse("temp must be finite and > 0");
-    if (top_k < 1 || top_k > std::min(SAMPLE_MAX, (int)llm_.n_vocab)) return refuse("top_k outside 1 .. min(64, n_vocab)");
-    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) return refuse("top_p outside (0, 1]");
+    if (lookup_check(name, corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats)) return 1;
+    if (!sampling_params_ok(refuse, temp, top_k, top_p)) return 1;
     if (weights_missing()) return 1;
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");

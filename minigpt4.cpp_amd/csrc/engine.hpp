@@ -10,6 +10,7 @@
 #include "formats.hpp"
 #include "kernels.hpp"
 #include "owned.hpp"
+#include "pick_stage.hpp"
 #include "sampler.hpp"
 #include "state.hpp"
 
@@ -240,8 +241,8 @@ public:
     // row r, -1 for an embedding row -- that every path which advances or moves rows keeps in step (commit_rows states the invariant; the queued rows
     // follow in pend_tok), its five parameters (neutral by default; they count only while the mode is on) and its bias (counts whatever the mode).  sample_token and
     // decode_batch apply them: temp <= 0 through ONE k_pen_pick launch over the listed conversations whose transformation is not the identity (tables built on the
-    // host, one upload, one small copy back, one synchronise; logits_, d_argmax_, d_feed_ and the graphs untouched), temp > 0 on a host copy of the row before the
-    // chain.  verify_draft, decode_lookup and decode_loop decide on raw logits.  The buffers are allocated at the first launch.
+    // host and staged as pick_stage.hpp describes: one upload, one small copy back, one synchronise; logits_, d_argmax_, d_feed_ and the graphs untouched), temp > 0 on
+    // a host copy of the row before the chain.  verify_draft, decode_lookup and decode_loop decide on raw logits.  The staging block is allocated at the first launch.
     void set_penalties(bool on) { pen_mode_ = on; }
     bool penalties() const { return pen_mode_; }
     int set_conversation_penalties(int slot, const PenParams &p);          // 0, or 1 + last_error "conversation_penalties: ...", nothing changed
@@ -253,11 +254,11 @@ public:
     // CONSTRAINT_SLOTS; it depends on the vocabulary only, so it survives set_conversations and parity switches): its DFA on the host, and on the device its table and the
     // index k_constrain_index builds once -- the allowed-token bitmap of every state.  A conversation holds a handle (0: none) and a DFA state.  sample_token and
     // decode_batch apply it behind bias and penalties: temp <= 0 through ONE k_constrain_pick launch over the constrained conversations of the call (pen_pick skips them: the
-    // kernel applies their tables itself; 4 m bytes come back, one synchronise), temp > 0 by fetching the state's index row and setting every other id of the penalised
+    // kernel applies their tables itself; staged as pick_stage.hpp describes, 4 m bytes come back, one synchronise), temp > 0 by fetching the state's index row and setting every other id of the penalised
     // host copy to -infinity before the chain.  Every constrained pick advances the state by the picked token on the host (EOS leaves it), whether or not the conversation
     // then advances: the state belongs to the sampler, like the generator.  reset() returns it to the start; fork touches neither handle nor state; decode_batch with forced
-    // tokens, verify_draft, decode_lookup, decode_loop, beam_search and decode_guided neither consult nor advance it.  The vocabulary blob, the staging and the indices are
-    // allocated by the first compile and freed with the context.  Each call: 0, or 1 + last_error "<name>: ..." and nothing changed.
+    // tokens, verify_draft, decode_lookup, decode_loop, beam_search and decode_guided neither consult nor advance it.  The vocabulary blob, the staging block and the
+    // indices are allocated by the first compile and freed with the context.  Each call: 0, or 1 + last_error "<name>: ..." and nothing changed.
     static constexpr int CONSTRAINT_SLOTS = 8;
     int constraint_compile(const unsigned char *pattern, long long n_bytes, int *handle);   // n_bytes < 0: strlen
     int constraint_free(int handle);                                       // refused while a conversation holds it
@@ -269,9 +270,9 @@ public:
     // ---- sampled batched steps decided on the device (sampling.hpp: the generator and the rule; minigpt4_amd.h: the whole rule).  Every conversation holds a 64-bit seed and
     // a 64-bit count of draws (after init and set_conversations: seed = (uint32)load seed | slot << 32, draws = 0; reset, fork, shift and snapshot loads touch neither: the pair
     // belongs to the sampler, as the host generator does).  decode_batch_sampled is one decode_batch step whose tokens k_sample_rows decides: queued rows of the listed
-    // conversations first (one flush each, as decode_batch), then one descriptor upload (SampleRow per conversation + the penalty tables pen_build_row builds), ONE launch
-    // over the listed logits_ rows -- a pick goes straight into d_btok_ for every conversation that advances --, one copy of the result block to pinned memory + an event,
-    // the batched step's own pass (step_begin / step_launch).  The host awaits the event while the pass runs, then does the book-keeping: histories, con_walk, draws += 1 per
+    // conversations first (one flush each, as decode_batch), then the staging block's one upload (pick_stage.hpp: a SampleRow per conversation + the penalty tables
+    // pen_build_row builds), ONE launch over the listed logits_ rows -- a pick goes straight into d_btok_ for every conversation that advances --, the block's fetch (the
+    // results to pinned memory + the event), the batched step's own pass (step_begin / step_launch).  The host awaits the event while the pass runs, then does the book-keeping: histories, con_walk, draws += 1 per
     // listed conversation (a full one that cannot shift included: sampled, reported, not advanced).  No logits row travels to the host; no synchronise between decision and
     // pass.  Parity mode: the same kernel decides, the picks are awaited first, step_parity evaluates.  sampled_candidates reports the distribution the next step would draw
     // from (ids [n][64] with -1 behind n_cand, probabilities with 0 behind it) and moves nothing.  1 + last_error "end_chat_batch_sampled: ..." / "sampled_candidates: ..." /
@@ -321,11 +322,11 @@ private:
     void forward_batch(int B, hipStream_t s, bool verify = false, bool epilogue = true);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation (epilogue = false: without launch_draft_finish)
     // speculation's own allocations (set_speculation; freed with the context): [1 + spec_max_][n_vocab] row logits, {m, greedy id per row} and its pinned mirror, [R] graphs
     int spec_max_ = 0; DevPtr<float> spec_logits_; DevPtr<int> spec_res_; PinPtr<int> spec_hres_; std::vector<hipGraphExec_t> spec_graph_;
-    // penalties: [MAX_CONVERSATIONS] PenRow then the tables, device and pinned (one upload per launch); the picked ids and their pinned mirror
+    // penalties: the penalised pick's staging block (pick_stage.hpp), allocated by the first row that is not the identity; its results are the picked ids
+    template <typename Row, typename Out> using Stage = PickStage<Row, Out, MAX_CONVERSATIONS>;
     bool pen_mode_ = false; PenInfo pen_info_;
-    DevPtr<uint8_t> pen_d_; PinPtr<uint8_t> pen_h_; DevPtr<int> pen_out_d_; PinPtr<int> pen_out_h_;
+    Stage<PenRow, int> pen_;
     std::vector<float> pen_row_;                                           // the host path's scratch copy of the row (h_logits_ stays raw)
-    void pen_alloc();
     // beam search's own lazy allocation: device words [slots 8 | targets 8 | ids 128 | logprobs 128 | rank 8 | target logprob 8 | scores 8 | BeamStep], its pinned mirror
     // (staging of the uploads, the landing place of the result block), the saved logits row + greedy / feed token of the source, the event the result block is awaited on
     DevPtr<int> beam_d_; PinPtr<int> beam_h_; DevPtr<float> beam_save_; OwnedEvent beam_ev_;
@@ -338,13 +339,25 @@ private:
     // THE row builder of the device picks: cv's bias and penalties over its history as the PenRow of logits row `row` (-> *out, whose entries are to start at entry
     // `off`) and its entries (-> tab).  false: the transformation is the identity (no flags, no entries); *out describes that too, for con_pick, which launches such rows
     bool pen_build_row(const Conversation &cv, int row, size_t off, PenRow *out, std::vector<PenEntry> &tab) const;
-    // ... built into row m of the penalised pick's own pinned staging (allocated by the first row that is not the identity), entries at the running offset `off`
+    // ... built into row m of pen_ (allocated here), entries at the running offset `off`
     bool pen_stage_row(const Conversation &cv, int row, int m, size_t &off, std::vector<PenEntry> &tab);
-    static constexpr size_t PEN_HEAD = MAX_CONVERSATIONS * sizeof(PenRow);   // pen_h_ / pen_d_: [MAX_CONVERSATIONS] PenRow, the tables behind them
     // m staged rows with n_ent entries: the upload, k_pen_pick over rows of `logits`, the ids' copy back queued.  false: the launch was refused (last_error).  Once
     // the caller has synchronised, pen_collect checks the ids and scatters them: ids[map[r]] <- row r's pick
     bool pen_launch(const float *logits, int m, size_t n_ent);
     void pen_collect(int m, const int *map, int *ids) const;
+    // THE check of a token id the device reported: the id, or HipError{hipErrorUnknown, what} for one outside the vocabulary.  A caller whose book-keeping has to follow the
+    // device before a bad block is reported asks id_in_vocab first and throws bad_id(what) when it is done
+    bool id_in_vocab(int id) const { return id >= 0 && id < (int)llm_.n_vocab; }
+    static HipError bad_id(const char *what) { return HipError{hipErrorUnknown, what, __FILE__, __LINE__}; }
+    int device_id(int id, const char *what) const { if (!id_in_vocab(id)) throw bad_id(what); return id; }
+    // THE checks of temp / top_k / top_p of every entry point that samples on the device; false: refuse(...) has set last_error
+    template <typename Refuse> bool sampling_params_ok(Refuse refuse, float temp, int top_k, float top_p) const;
+    // Every listed conversation has queued rows or current logits; evaluate() runs the queues (the caller's way: the passes it costs differ; false: it failed, last_error
+    // says why); then every one has current logits.  false: refuse(...) has set last_error -- before anything ran where a conversation has neither
+    template <typename Refuse, typename Evaluate> bool logits_ready(Refuse refuse, const int *slots, int n, Evaluate evaluate);
+    // the argument checks decode_lookup and decode_lookup_sampled share, in their order; 0, or 1 with last_error "<name>: ..."
+    int lookup_check(const char *name, const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, const int *tokens_out, const int *n_tokens,
+                     const int *stats) const;
     // THE host chain's bias and penalties (temp > 0), in place on a copy of cv's logits row: bias, then penalties over `hist`; a constraint's mask comes after it
     void pen_host_row(const Conversation &cv, const std::vector<int> &hist, float *row);
     // ids[i] <- the penalised pick of every listed conversation whose transformation is not the identity (skip_constrained: and that holds no constraint -- con_pick serves it)
@@ -512,8 +525,9 @@ private:
     int staged_slot(int r) const { return h_bstage_[MAX_CONVERSATIONS + r]; }
     // the slab's one copy, then k_batch_begin over B rows (verify: k_draft_begin -- R rows of the one conversation in row 0)
     void step_begin(int B, bool verify = false);
-    // the weight pass over the staged rows: batch_graph_[B] (verify: spec_graph_[B]) replayed, captured first where it does not exist yet; without graphs, forward_batch
-    void step_launch(int B, bool verify = false);
+    // the weight pass over the staged rows, forward_batch(B, stream_, verify, epilogue): batch_graph_[B] (verify: spec_graph_[B]; verify without its epilogue, the sampled
+    // verify pass: spec_sgraph_[B]) replayed, captured first where it does not exist yet; without graphs, eager
+    void step_launch(int B, bool verify = false, bool epilogue = true);
     // parity mode's stand-in for step_begin + step_launch: one oracle-order single-row pass per staged row, in row order; cur_ is left on the last row's conversation.
     // 0, or eval_chunk's failure
     int step_parity(int B);
@@ -622,14 +636,14 @@ private:
     void guide_free() { reset_all(guide_mix_, guide_d_, guide_h_, guide_ev_); }
     int guide_prepare(const char *name, const int *pos, const int *neg, int n, float scale, int *all);   // the checks, the queued rows; all[2 i] = pos[i], all[2 i + 1] = neg[i]
     // constrained decoding.  Per compiled constraint: the host DFA, the device table | accepting bitmap | index (one allocation).  Per conversation (arrays here, not in
-    // Conversation: that struct keeps its layout): handle and state.  Lazy, first compile: the vocabulary blob + offsets; the pick's staging ([MAX_CONVERSATIONS] ConRow, then
-    // the penalty tables: device and pinned), its output words and their pinned mirror, the pinned landing place of one index row (temp > 0, constraint_mask)
+    // Conversation: that struct keeps its layout): handle and state.  Lazy, first compile: the vocabulary blob + offsets; the pick's staging block (pick_stage.hpp; its
+    // results are the output words), the pinned landing place of one index row (temp > 0, constraint_mask)
     struct Constraint { bool used = false; ConstraintDfa dfa; DevPtr<uint8_t> dev; const unsigned *index = nullptr; };
     Constraint con_[CONSTRAINT_SLOTS];
     int con_handle_[MAX_CONVERSATIONS] = {0}, con_state_[MAX_CONVERSATIONS] = {0}, con_assigned_ = 0;
     struct ConInfo { int launches = 0, host_rows = 0, stuck = 0, index_launches = 0; } con_info_;
     DevPtr<unsigned char> con_vocab_; DevPtr<int> con_off_;
-    DevPtr<uint8_t> con_d_; PinPtr<uint8_t> con_h_; DevPtr<int> con_out_d_; PinPtr<int> con_out_h_; PinPtr<unsigned> con_row_h_;
+    Stage<ConRow, int> con_stage_; PinPtr<unsigned> con_row_h_;
     void con_alloc();
     void con_walk(int slot, int id);                                       // the state after the picked token (EOS and ids outside the vocabulary leave it)
     void con_pick(const int *slots, int n, int *ids);                      // ids[i] <- the constrained pick of every listed conversation that holds a constraint
@@ -643,31 +657,30 @@ private:
     StateInfo state_info_;
     void state_alloc(size_t block_bytes);              // staging for blocks of that size (all or nothing; grows, never shrinks)
     int state_header(int slot, StateHeader &h, StateLayout &l) const;   // what a save of `slot` would write now (n_rows = n_past); 0, or 1: the layout refused
-    // device-side sampling.  Per conversation (arrays here, not in Conversation: that struct keeps its layout): seed and draws.  Lazy, first call: the staging
-    // ([MAX_CONVERSATIONS] SampleRow, then the penalty tables: device and pinned), the result block ([MAX_CONVERSATIONS] SampleOut) and its pinned mirror, the event the
-    // block is awaited on
+    // device-side sampling.  Per conversation (arrays here, not in Conversation: that struct keeps its layout): seed and draws.  Lazy, first call: the staging block
+    // (pick_stage.hpp); its results are the SampleOut blocks, awaited on its event
     uint64_t smp_seed_[MAX_CONVERSATIONS] = {0}, smp_draws_[MAX_CONVERSATIONS] = {0}; uint32_t smp_load_seed_ = 0;
     struct SmpInfo { uint64_t launches = 0, handed = 0, stuck = 0, rows = 0; } smp_info_;
-    DevPtr<uint8_t> smp_d_; PinPtr<uint8_t> smp_h_; DevPtr<SampleOut> smp_out_d_; PinPtr<SampleOut> smp_out_h_; OwnedEvent smp_ev_;
-    static constexpr size_t SMP_HEAD = MAX_CONVERSATIONS * sizeof(SampleRow);
-    void smp_alloc();
-    void smp_free() { reset_all(smp_d_, smp_h_, smp_out_d_, smp_out_h_, smp_ev_); }
+    Stage<SampleRow, SampleOut> smp_;
+    void smp_free() { smp_.reset(); }
     void smp_reseed() { for (int s = 0; s < MAX_CONVERSATIONS; s++) { smp_seed_[s] = (uint64_t)smp_load_seed_ | (uint64_t)s << 32; smp_draws_[s] = 0; } }
     // the checks and the queued rows of both entry points; 0, or 1 with last_error "<name>: ..."
     int smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p);
-    // the listed conversations' descriptors into the pinned staging (row-token index -1), from each history as a sample sees it; the table entries staged
+    // THE descriptor of one decision of conversation `slot`: its seed, the table `pen` describes, the allowed bitmap of constraint state `state` (no constraint: every id),
+    // draw number `draws`; tok_index: the entry of d_btok_ that takes the pick (-1: none)
+    SampleRow smp_row(int slot, const PenRow &pen, int state, uint64_t draws, int tok_index, float temp, int top_k, float top_p) const;
+    // the listed conversations' descriptors into smp_ (allocated here; row-token index -1), from each history as a sample sees it; the table entries staged
     size_t smp_stage(const int *slots, int n, float temp, int top_k, float top_p);
-    // n staged descriptors with n_ent entries: the upload, the launch (hand: picks go to d_btok_ at the descriptors' row-token indices), the result block's copy back and
-    // the event queued.  false: the launch was refused (last_error)
+    // n staged descriptors with n_ent entries: the upload and the launch over rows of `logits` (row_tok: picks go there at the descriptors' row-token indices), nothing
+    // counted, no copy back (verify_draft_sampled: its launches are speculation_info's).  false: the launch was refused (last_error)
+    bool smp_launch_on(const float *logits, int n, size_t n_ent, int *row_tok = nullptr);
+    // ... over logits_ (hand: picks go to d_btok_), counted, the result block's copy back and the event queued
     bool smp_launch(int n, size_t n_ent, bool hand);
-    // the same upload and launch over rows of `logits`, nothing handed over, nothing counted, no copy back (verify_draft_sampled: its launches are speculation_info's)
-    bool smp_launch_on(const float *logits, int n, size_t n_ent);
     // speculation under sampling.  Lazy, first call: one graph slot per row count (the verify pass without its epilogue), the result block {m, picks, stuck flags} and its
     // pinned mirror.  Dropped / freed where the greedy form's are (spec_drop_graphs, spec_free)
     std::vector<hipGraphExec_t> spec_sgraph_; DevPtr<int> sdr_res_; PinPtr<int> sdr_hres_;
     struct SpecInfo { long long passes = 0, rows = 0, sent = 0, accepted = 0, launches = 0, stuck = 0, cut = 0; } spec_info_;
     void sdr_alloc();
-    void spec_pass_launch(int R);                      // the verify pass over the staged rows without an epilogue: spec_sgraph_[R] replayed, captured first; without graphs, eager
 };
 
 int device_count_noexcept();

@@ -227,16 +227,17 @@ bool launch_topn_rows(const float *logits, int ld, int n_vocab, int rows, const 
 // next step and row_tok[i] = res->tok[i] -- where the batched step reads its row tokens (an id outside [0, n_vocab) is written as 0: it indexes the embedding matrix).
 // false + last_error: W outside 2 .. BEAM_MAX, C outside 1 .. BEAM_CAND_MAX, no live beam
 bool launch_beam_select(const int *ids, const float *logprobs, float *scores, unsigned live, int W, int C, int eos, int n_vocab, BeamStep *res, int *row_tok, hipStream_t s);
-// penalised greedy pick, one workgroup per entry of `rows` (device; penalty.hpp): picked[r] = the first maximum of logits row rows[r].row (at logits + row * ld, any
-// 4-byte alignment) after the bias / repetition / frequency / presence transformation its table entries table[rows[r].off .. + rows[r].n) describe (distinct ids);
-// the logits are not written.  adjusted (may be null): [table entry] the transformed value.  false + last_error: n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose
+// ---- the device picks: launch_pen_pick, launch_constrain_pick, launch_sample_rows.  One workgroup per entry of `rows` (device).  THE TRANSFORMED ROW of an entry, walked
+// by all three the same way (pick_row.hpp): logits row pen.row (at logits + row * ld, any 4-byte alignment) after the bias / repetition / frequency / presence
+// transformation its table entries table[pen.off .. + pen.n) describe (penalty.hpp; distinct ids, one outside [0, n_vocab) is ignored; pen.n == 0: none), restricted to the
+// ids set in the entry's `allowed` bitmap where it has one (constraint_words(n_vocab) words, device; null: every id).  The logits are not written.
+// penalised greedy pick: picked[r] = the first maximum of the transformed row (0 for a row without a comparable value).  adjusted (may be null): [table entry] the transformed value.  false + last_error: n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose
 // bitmap does not fit LDS
 bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const PenRow *rows, const PenEntry *table, int *picked, float *adjusted, hipStream_t s);
 // constrained decoding (constraint.hpp).  launch_constrain_index: index[n_states][constraint_words(n_vocab)] = the allowed-token bitmap of every DFA state, one workgroup per
 // state; vocab / off[n_vocab + 1] = the pieces' bytes back to back and where each begins (device), trans[n_states][256] with entries < n_states, accept = the accepting
 // bitmap.  false + last_error: a null array, n_vocab < 1, n_states outside 2 .. CONSTRAINT_MAX_STATES.
-// launch_constrain_pick: out[r] = the first maximum, over the ids set in rows[r].allowed (constraint_words(n_vocab) words, device), of logits row rows[r].pen.row after the
-// transformation rows[r].pen / table describe as for launch_pen_pick (pen.n == 0: none); no id set: CONSTRAINT_EOS | CONSTRAIN_STUCK.  The logits are not written.
+// launch_constrain_pick: out[r] = the first maximum of the transformed row (above) under rows[r].allowed; no id set: CONSTRAINT_EOS | CONSTRAIN_STUCK.
 // false + last_error: a null array, n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose two bitmaps do not fit LDS.
 constexpr int CONSTRAIN_STUCK = 1 << 30;               // flag in a pick's output word: the row had no allowed id
 struct ConRow { PenRow pen; const unsigned *allowed; unsigned long long pad; };   // 12 words
@@ -250,10 +251,9 @@ bool launch_constrain_pick(const float *logits, int ld, int n_vocab, int n_rows,
 constexpr int GUIDE_MAX = 32;                          // pairs per launch = Engine::MAX_CONVERSATIONS / 2
 struct GuidePair { int pos_row, neg_row; float scale; int pos_tok, neg_tok, pad[3]; };   // 8 words
 bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, const GuidePair *pairs, float *mixed, int *pick, float *pick_val, int *row_tok, hipStream_t s);
-// sampled decode step (sampling.hpp: the generator and the rule), one workgroup per entry of `rows` (device): the first min(top_k, participating ids) ids of logits row
-// rows[r].pen.row after the transformation rows[r].pen / table describe (as for launch_pen_pick) among the ids set in rows[r].allowed (as for launch_constrain_pick; null:
-// every id), in launch_topn_rows' order; top-p, temperature and softmax over them; one draw with word 0 of Philox4x32-10(seed, draws).  out[r] = pick, stuck flag, word,
-// n_cand, kept, ids, probabilities; row_tok (may be null): row_tok[rows[r].tok_index] = pick where the index is >= 0.  The logits are not written.  top_k is clamped to
+// sampled decode step (sampling.hpp: the generator and the rule): the first min(top_k, participating ids) ids of the transformed row (above) under rows[r].allowed, in
+// launch_topn_rows' order; top-p, temperature and softmax over them; one draw with word 0 of Philox4x32-10(seed, draws).  out[r] = pick, stuck flag, word,
+// n_cand, kept, ids, probabilities; row_tok (may be null): row_tok[rows[r].tok_index] = pick where the index is >= 0.  top_k is clamped to
 // 1 .. SAMPLE_MAX; temp > 0 and 0 < top_p are the caller's to check.  false + last_error: a null array, n_rows / n_vocab < 1, ld < n_vocab, a vocabulary whose two bitmaps
 // and the kernel's 12 KB do not fit 64 KB of LDS.
 struct SampleRow { PenRow pen; const unsigned *allowed; float temp, top_p; int top_k, tok_index; unsigned long long seed, draws; };   // 18 words

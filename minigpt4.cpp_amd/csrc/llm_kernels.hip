@@ -3212,40 +3212,18 @@ bool launch_beam_select(const int *ids, const float *logprobs, float *scores, un
     hipLaunchKernelGGL(k_beam_select, dim3(1), dim3(BEAM_MAX * BEAM_CAND_MAX), 0, s, ids, logprobs, scores, live, W, C, eos, n_vocab, res, row_tok);
     return true;
 }
+#include "pick_row.hpp"
 // Penalised greedy pick (Engine::pen_pick), one workgroup of 256 per listed conversation, one launch for all of them.  rows[r] names the logits row, the conversation's
-// table (penalty.hpp: the distinct ids its repetition / frequency / presence penalties and its logit bias touch) and the factors.  Thread i computes the adjusted value of
-// table entry i with pen_value -- the function the host path applies, so both give the same bits -- and marks the id in a bitmap in LDS; the sweep over the row (row_span:
-// scalar head, 16-byte body, scalar tail) skips the marked ids; "larger value, then smaller id" over both sets is the first maximum of the transformed row.  The row is
-// read in place and never written: whoever reads logits_ afterwards (minigpt4_amd_get_logits, scoring, top-N) sees raw logits.  picked[r] = the id; adjusted (may be
-// null): the value of every table entry, at the entry's index (test hook).  An entry whose id lies outside [0, n_vocab) is ignored (the host never builds one).
+// table (penalty.hpp: the distinct ids its repetition / frequency / presence penalties and its logit bias touch) and the factors.  pick_row.hpp holds the walk (the table
+// ids marked in ONE bitmap in LDS, the sweep over the unmarked ids, the table loop through pen_value) and the greedy tail; "larger value, then smaller id" over both sets
+// is the first maximum of the transformed row.  The row is read in place and never written: whoever reads logits_ afterwards (minigpt4_amd_get_logits, scoring, top-N)
+// sees raw logits.  picked[r] = the id (0 for a row without a comparable value); adjusted (may be null): the value of every table entry, at the entry's index (test hook).
 // LDS, all dynamic: (n_vocab + 31) / 32 bitmap words rounded up to 4, then 4 floats and 4 ints of reduction scratch.
 __global__ __launch_bounds__(256) void k_pen_pick(const float *__restrict__ logits, int ld, int n_vocab, const PenRow *__restrict__ rows, const PenEntry *__restrict__ table,
                                                   int *__restrict__ picked, float *__restrict__ adjusted) {
     extern __shared__ __attribute__((aligned(16))) unsigned pen_lds[];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const PenRow pr = rows[r];
-    const int words = ((n_vocab + 31) / 32 + 3) & ~3;
-    unsigned *bits = pen_lds;
-    float *sv = reinterpret_cast<float *>(pen_lds + words); int *si = reinterpret_cast<int *>(pen_lds + words + 4);
-    const float *x = logits + (size_t)pr.row * ld;
-    for (int i = tid; i < words; i += 256) bits[i] = 0u;
-    __syncthreads();
-    float best = -INFINITY; int bi = 0x7FFFFFFF;
-    for (int i = tid; i < pr.n; i += 256) {
-        const PenEntry e = table[(size_t)pr.off + i];
-        if (e.id < 0 || e.id >= n_vocab) continue;
-        const float v = pen_value(x[e.id], e.id, e.count, e.has_bias, e.bias, pr.flags, pr.repeat_penalty, pr.alpha_frequency, pr.alpha_presence);
-        atomicOr(&bits[e.id >> 5], 1u << (e.id & 31));
-        if (adjusted) adjusted[(size_t)pr.off + i] = v;
-        argmax_combine(best, bi, v, e.id);
-    }
-    __syncthreads();
-    const RowSpan sp = row_span(x, n_vocab);
-    row_sweep(sp, tid, [&](float v, int i) { if (!((bits[i >> 5] >> (i & 31)) & 1u)) argmax_combine(best, bi, v, i); });
-    argmax_wave(best, bi);
-    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) { for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]); picked[r] = bi == 0x7FFFFFFF ? 0 : bi; }
+    const int id = pick_greedy<false>(logits, ld, n_vocab, rows[blockIdx.x], table, nullptr, adjusted, 0, pen_lds, threadIdx.x);
+    if (threadIdx.x == 0) picked[blockIdx.x] = id;
 }
 bool launch_pen_pick(const float *logits, int ld, int n_vocab, int n_rows, const PenRow *rows, const PenEntry *table, int *picked, float *adjusted, hipStream_t s) {
     const size_t lds = ((size_t)(((n_vocab + 31) / 32 + 3) & ~3) + 8) * 4;
@@ -3282,39 +3260,18 @@ bool launch_constrain_index(const unsigned char *vocab, const int *off, int n_vo
     hipLaunchKernelGGL(k_constrain_index, dim3((unsigned)n_states), dim3(256), 0, s, vocab, off, n_vocab, trans, accept, constraint_words(n_vocab), index);
     return true;
 }
-// Constrained greedy pick (Engine::con_pick), one workgroup of 256 per constrained conversation, one launch for all of them.  rows[r] names the logits row, the address
-// of index[state] (the allowed bitmap, constraint_words(n_vocab) words) and -- pen.n > 0 -- the conversation's penalty table and factors, exactly as k_pen_pick takes them.
-// The allowed bitmap is staged in LDS; thread i computes table entry i with pen_value and marks its id in a second bitmap, carrying the value only when the id is allowed;
-// the sweep (row_span / row_sweep) carries the allowed, unmarked ids.  out[r] = the FIRST maximum of the transformed row over the allowed ids (larger value, then lower id;
-// -0 == +0; an allowed id at -infinity can still win among -infinities; NaN never wins).  No allowed id: out[r] = CONSTRAINT_EOS | CONSTRAIN_STUCK.  The logits are read
-// in place and never written.  LDS, all dynamic: 2 * constraint_words(n_vocab) bitmap words, then 4 floats and 4 ints of reduction scratch (8 KB at 32 001 ids); the
-// launch refuses a vocabulary whose two bitmaps exceed 64 KB (n_vocab above 261 000).
+// Constrained greedy pick (Engine::con_pick), one workgroup of 256 per constrained conversation, one launch for all of them: k_pen_pick's body (pick_row.hpp) with the
+// allowed bitmap.  rows[r] names the logits row, the address of index[state] (constraint_words(n_vocab) words; null: every id) and -- pen.n > 0 -- the conversation's
+// penalty table and factors.  out[r] = the FIRST maximum of the transformed row over the allowed ids (larger value, then lower id; -0 == +0; an allowed id at -infinity can
+// still win among -infinities; NaN never wins).  No allowed id: out[r] = CONSTRAINT_EOS | CONSTRAIN_STUCK.  The logits are read in place and never written.  LDS, all
+// dynamic: 2 * constraint_words(n_vocab) bitmap words, then 4 floats and 4 ints of reduction scratch (8 KB at 32 001 ids); the launch refuses a vocabulary whose two
+// bitmaps exceed 64 KB (n_vocab above 261 000).
 __global__ __launch_bounds__(256) void k_constrain_pick(const float *__restrict__ logits, int ld, int n_vocab, const ConRow *__restrict__ rows, const PenEntry *__restrict__ table,
                                                         int *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned con_lds[];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const ConRow cr = rows[r];
-    const int words = constraint_words(n_vocab);
-    unsigned *allow = con_lds, *marked = con_lds + words;
-    float *sv = reinterpret_cast<float *>(con_lds + 2 * words); int *si = reinterpret_cast<int *>(con_lds + 2 * words + 4);
-    const float *x = logits + (size_t)cr.pen.row * ld;
-    for (int i = tid; i < words; i += 256) { allow[i] = cr.allowed[i]; marked[i] = 0u; }
-    __syncthreads();
-    float best = -INFINITY; int bi = 0x7FFFFFFF;
-    for (int i = tid; i < cr.pen.n; i += 256) {
-        const PenEntry e = table[(size_t)cr.pen.off + i];
-        if (e.id < 0 || e.id >= n_vocab) continue;
-        atomicOr(&marked[e.id >> 5], 1u << (e.id & 31));
-        if (!((allow[e.id >> 5] >> (e.id & 31)) & 1u)) continue;
-        argmax_combine(best, bi, pen_value(x[e.id], e.id, e.count, e.has_bias, e.bias, cr.pen.flags, cr.pen.repeat_penalty, cr.pen.alpha_frequency, cr.pen.alpha_presence), e.id);
-    }
-    __syncthreads();
-    const RowSpan sp = row_span(x, n_vocab);
-    row_sweep(sp, tid, [&](float v, int i) { if (((allow[i >> 5] & ~marked[i >> 5]) >> (i & 31)) & 1u) argmax_combine(best, bi, v, i); });
-    argmax_wave(best, bi);
-    if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bi; }
-    __syncthreads();
-    if (tid == 0) { for (int w = 1; w < 4; w++) argmax_combine(best, bi, sv[w], si[w]); out[r] = bi == 0x7FFFFFFF ? (CONSTRAINT_EOS | CONSTRAIN_STUCK) : bi; }
+    const ConRow cr = rows[blockIdx.x];
+    const int id = pick_greedy<true>(logits, ld, n_vocab, cr.pen, table, cr.allowed, nullptr, CONSTRAINT_EOS | CONSTRAIN_STUCK, con_lds, threadIdx.x);
+    if (threadIdx.x == 0) out[blockIdx.x] = id;
 }
 bool launch_constrain_pick(const float *logits, int ld, int n_vocab, int n_rows, const ConRow *rows, const PenEntry *table, int *out, hipStream_t s) {
     const size_t lds = ((size_t)2 * constraint_words(n_vocab) + 8) * 4;
@@ -3373,9 +3330,8 @@ bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, co
 // Sampled decode step (Engine::decode_batch_sampled / sampled_candidates; sampling.hpp holds the generator and the rule's arithmetic, shared with the host), one workgroup
 // of 256 per listed conversation, one launch for all of them.  rows[r] names the logits row, the conversation's penalty table and factors (as k_pen_pick takes them), the
 // allowed bitmap of its constraint state (as k_constrain_pick takes it; null: every id), temp / top_k / top_p, the generator's (seed, draws) and the entry of the weight
-// pass's row tokens that takes the pick (-1: none).  The row the rule sees -- bias and penalties, then the constraint -- is never materialised: table ids are marked in an
-// LDS bitmap and skipped by the row sweeps (row_span / row_sweep), a loop over the table feeds their pen_value results into the same histograms and lists, an id whose
-// allowed bit is clear is skipped everywhere.  The selection is k_topn_rows': the same order-preserving key (topn_key), the same three histogram levels (11 + 11 + 10 bits)
+// pass's row tokens that takes the pick (-1: none).  The row the rule sees -- bias and penalties, then the constraint -- is never materialised: pick_row.hpp's walk (the
+// greedy picks' own) feeds every participating id, from the row sweep or from the table, into the same histograms and lists.  The selection is k_topn_rows': the same order-preserving key (topn_key), the same three histogram levels (11 + 11 + 10 bits)
 // for the key T of the k-th participating id (k = min(top_k, participating ids)), the same collecting sweep (keys above T: fewer than k; keys equal to T: the first 192
 // that arrive), the same id-order scan when more than 192 keys equal T (a marked id's value is looked up in the table there), the same counting placement.  Thread 0 then
 // runs sample_rule over the <= 64 candidates in LDS and draws with word 0 of Philox4x32-10(seed, draws).  out[r]: pick, stuck flag, the word, n_cand, kept, the candidate
@@ -3384,7 +3340,7 @@ bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, co
 // (-infinity through a bias is ordered like any value; NaN: unspecified).  The logits are read in place and never written; nothing beyond n_vocab floats of a row is read.
 // No spinning, no flags between workgroups, no global atomics; every loop is bounded by n_vocab or by the table length.
 // LDS: 12 KB static (8 KB histogram, 3 KB candidate lists, the ordered candidates) + dynamic 2 * constraint_words(n_vocab) bitmap words (8 KB at 32 001 ids).
-// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 51 VGPRs, 89 SGPRs, no scratch, 12080 bytes of static LDS, occupancy 8 waves per SIMD.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 51 VGPRs, 90 SGPRs, no scratch, 12080 bytes of static LDS, occupancy 8 waves per SIMD.
 __global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ logits, int ld, int n_vocab, const SampleRow *__restrict__ rows, const PenEntry *__restrict__ table,
                                                      SampleOut *__restrict__ out, int *__restrict__ row_tok) {
     constexpr int GT = SAMPLE_MAX, TIES = 256 - SAMPLE_MAX;
@@ -3394,27 +3350,11 @@ __global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ l
     __shared__ float cval[256], s_val[SAMPLE_MAX], s_p[SAMPLE_MAX];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const SampleRow sr = rows[r];
-    const PenRow pr = sr.pen;
-    const int words = constraint_words(n_vocab);
-    unsigned *allow = smp_lds, *marked = smp_lds + words;
-    const float *x = logits + (size_t)pr.row * ld;
-    for (int i = tid; i < words; i += 256) { allow[i] = sr.allowed ? sr.allowed[i] : 0xFFFFFFFFu; marked[i] = 0u; }
     if (tid < 2) cnt[tid] = 0;
     for (int i = tid; i < 2048; i += 256) hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < pr.n; i += 256) { const int id = table[(size_t)pr.off + i].id; if (id >= 0 && id < n_vocab) atomicOr(&marked[id >> 5], 1u << (id & 31)); }
-    __syncthreads();
-    const RowSpan sp = row_span(x, n_vocab);
-    auto entry_value = [&](const PenEntry &e) { return pen_value(x[e.id], e.id, e.count, e.has_bias, e.bias, pr.flags, pr.repeat_penalty, pr.alpha_frequency, pr.alpha_presence); };
-    // f(value, id) for every participating id of the transformed row: the unmarked allowed ids from the row, the allowed table ids through pen_value
-    auto each = [&](auto f) {
-        row_sweep(sp, tid, [&](float v, int i) { if (((allow[i >> 5] & ~marked[i >> 5]) >> (i & 31)) & 1u) f(v, i); });
-        for (int i = tid; i < pr.n; i += 256) {
-            const PenEntry e = table[(size_t)pr.off + i];
-            if (e.id < 0 || e.id >= n_vocab || !((allow[e.id >> 5] >> (e.id & 31)) & 1u)) continue;
-            f(entry_value(e), e.id);
-        }
-    };
+    PickRow<true> row;                                                        // the transformed row's walk (pick_row.hpp); its barriers cover cnt and hist
+    row.stage(logits, ld, n_vocab, sr.pen, table, sr.allowed, smp_lds, tid);
+    auto each = [&](auto f) { row.each(tid, f); };
     // level 1, and the number of participating ids
     unsigned mine = 0;
     each([&](float v, int) { mine++; topn_hist_add(hist, true, topn_key(v) >> 21, lane); });
@@ -3474,10 +3414,8 @@ __global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ l
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int i = i0 + j;
-                if (i >= n_vocab || !((allow[i >> 5] >> (i & 31)) & 1u)) continue;
-                float v = x[i];
-                if ((marked[i >> 5] >> (i & 31)) & 1u)                        // a table id: its entry's value (the ids of a table are distinct)
-                    for (int e = 0; e < pr.n; e++) { const PenEntry pe = table[(size_t)pr.off + e]; if (pe.id == i) { v = entry_value(pe); break; } }
+                if (i >= n_vocab || !row.is_allowed(i)) continue;
+                const float v = row.value_of(i);                              // (a table id: its entry's value)
                 if (topn_key(v) == T) { m4 |= 1u << j; v4[j] = v; }
             }
             const unsigned c = (unsigned)__popc(m4), inc = topn_wave_scan(c, lane);

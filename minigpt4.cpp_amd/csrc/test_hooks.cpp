@@ -49,6 +49,32 @@ static std::vector<unsigned short> host_silu_table() {
 }
 // the timed hooks' event pair (hipEventCreate on a and b; timing enabled), destroyed on every path
 struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) HIP_IGNORE(hipEventDestroy(a)); if (b) HIP_IGNORE(hipEventDestroy(b)); } };
+// ONE timed region of the null stream: f() between two event records, the device awaited, the elapsed milliseconds -> *ms_out (may be null).  false: f() returned
+// false (a launcher that refused): nothing was awaited
+template <typename F> static bool timed(float *ms_out, F f) {
+    Events ev;
+    HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
+    HIP_CHECK(hipEventRecord(ev.a, nullptr));
+    if (!f()) return false;
+    HIP_CHECK(hipEventRecord(ev.b, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
+    float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
+    if (ms_out) *ms_out = t;
+    return true;
+}
+// Everything of a pick hook's descriptors that indexes device memory: rows = [n_rows] PenRow as 8 words, table = [n_table] PenEntry as 4 words.  Row index inside the
+// buffer, offset and count inside the table, at most PEN_TABLE_MAX entries, every id inside the vocabulary, the ids of one row distinct
+static bool pen_rows_ok(const int32_t *rows, int n_rows, const int32_t *table, int n_table, int buf_rows, int n_vocab) {
+    for (int r = 0; r < n_rows; r++) {
+        const int32_t *w = rows + 8 * (size_t)r;
+        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table) return false;
+        std::vector<int> ids;
+        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return false; ids.push_back(id); }
+        std::sort(ids.begin(), ids.end());
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return false;
+    }
+    return true;
+}
 
 extern "C" {
 
@@ -430,14 +456,9 @@ int minigpt4_amd_bench_matvec_ri(int ggml_type, int rows, int cols, int n_mat, i
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) run(i);
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; i++) run(i % n_sets);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(i % n_sets); return true; });
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
         return 0;
     });
 }
@@ -860,13 +881,8 @@ int minigpt4_amd_bench_gemm_f16(int M, int N, int K, int flags, int variant, int
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) if (!run(i)) return 4;
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; i++) run(i % n_sets);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(i % n_sets); return true; });
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         return 0;
     });
@@ -886,13 +902,8 @@ int minigpt4_amd_bench_attn_f32(int heads, int hd, int nq, int nk, int iters, fl
         auto run = [&]() { launch_attn_f32(dq.as<float>(), 3 * D, dq.as<float>() + D, dq.as<float>() + 2 * D, 3 * D, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, nullptr, 1); };
         for (int i = 0; i < 3; i++) run();
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; i++) run();
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(); return true; });
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         return 0;
     });
@@ -916,13 +927,8 @@ int minigpt4_amd_bench_attn_f32_b(int heads, int hd, int nq, int nk, int batch, 
             else launch_attn_f32(dq.as<float>(), 3 * D, dq.as<float>() + D, dq.as<float>() + 2 * D, 3 * D, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, nullptr, batch); };
         for (int i = 0; i < 3; i++) run();
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; i++) run();
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(); return true; });
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         return 0;
     });
@@ -1017,14 +1023,7 @@ int minigpt4_amd_test_kv_shift(int n_layer, int n_ctx, int n_embd, int n_head, i
         DevBuf dk(n * 2), dv(n * 2), dc(c.size() * 4), ds(s.size() * 4);
         HIP_CHECK(hipMemcpy(dk.p, k, n * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, n * 2, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(ds.p, s.data(), s.size() * 4, hipMemcpyHostToDevice));
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        launch_kv_shift(dk.as<__half>(), dv.as<__half>(), n_layer, n_ctx, n_embd, hd, n_keep, n_discard, n_rows, dc.as<float>(), ds.as<float>(), nullptr);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
-        if (ms) *ms = t;
+        timed(ms, [&] { launch_kv_shift(dk.as<__half>(), dv.as<__half>(), n_layer, n_ctx, n_embd, hd, n_keep, n_discard, n_rows, dc.as<float>(), ds.as<float>(), nullptr); return true; });
         HIP_CHECK(hipMemcpy(k, dk.p, n * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, n * 2, hipMemcpyDeviceToHost));
         return 0;
     });
@@ -1048,14 +1047,7 @@ int minigpt4_amd_test_kv_copy(int n_slot, int n_layer, int rows, int n_embd, int
         }
         KvCopyDst d{};
         for (int i = 0; i < n_dst; i++) { d.k[i] = dk.as<__half>() + (size_t)dst[i] * slot_n; d.v[i] = dv.as<__half>() + (size_t)dst[i] * slot_n; }
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        launch_kv_copy(sk, sv, src_rows ? src_rows : rows, d, n_dst, rows, n_layer, n_embd, n_rows, nullptr);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
-        if (ms) *ms = t;
+        timed(ms, [&] { launch_kv_copy(sk, sv, src_rows ? src_rows : rows, d, n_dst, rows, n_layer, n_embd, n_rows, nullptr); return true; });
         if (k) { HIP_CHECK(hipMemcpy(k, dk.p, n * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, n * 2, hipMemcpyDeviceToHost)); }
         return 0;
     });
@@ -1066,14 +1058,7 @@ int minigpt4_amd_test_checksum(const void *device_ptr, size_t bytes, uint64_t *s
     if (!device_ptr || !sum_out || (uintptr_t)device_ptr % 4) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        struct Ev { hipEvent_t a, b; ~Ev() { HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b)); } } ev{a, b};
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        *sum_out = device_checksum(device_ptr, bytes, nullptr);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
-        if (ms) *ms = t;
+        timed(ms, [&] { *sum_out = device_checksum(device_ptr, bytes, nullptr); return true; });
         return 0;
     });
 }
@@ -1089,14 +1074,7 @@ int minigpt4_amd_test_kv_pack(int n_layer, int n_ctx, int n_embd, int r0, int n,
         if (k) { HIP_CHECK(hipMemcpy(dk.p, k, cache, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, cache, hipMemcpyHostToDevice)); }
         else { HIP_CHECK(hipMemset(dk.p, 0x11, cache)); HIP_CHECK(hipMemset(dv.p, 0x22, cache)); }   // every page touched before the timed launch
         HIP_CHECK(hipMemset(db.p, 0, blk ? blk : 1)); HIP_CHECK(hipMemset(ds.p, 0xFF, 8));   // the launcher zeroes the word
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        struct Ev { hipEvent_t a, b; ~Ev() { HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b)); } } ev{a, b};
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        launch_kv_pack(dk.as<__half>(), dv.as<__half>(), n_ctx, n_layer, n_embd, r0, n, db.as<__half>(), ds.as<unsigned long long>(), nullptr);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
-        if (ms) *ms = t;
+        timed(ms, [&] { launch_kv_pack(dk.as<__half>(), dv.as<__half>(), n_ctx, n_layer, n_embd, r0, n, db.as<__half>(), ds.as<unsigned long long>(), nullptr); return true; });
         if (blk && block_out) HIP_CHECK(hipMemcpy(block_out, db.p, blk, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(sum_out, ds.p, 8, hipMemcpyDeviceToHost));
         return 0;
@@ -1113,14 +1091,7 @@ int minigpt4_amd_test_kv_unpack(int n_layer, int n_ctx, int n_embd, int r0, int 
         if (blk && block) HIP_CHECK(hipMemcpy(db.p, block, blk, hipMemcpyHostToDevice));
         else if (blk) HIP_CHECK(hipMemset(db.p, 0x33, blk));
         HIP_CHECK(hipMemset(ds.p, 0xFF, 8));
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        struct Ev { hipEvent_t a, b; ~Ev() { HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b)); } } ev{a, b};
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        launch_kv_unpack(db.as<__half>(), dk.as<__half>(), dv.as<__half>(), n_ctx, n_layer, n_embd, r0, n, ds.as<unsigned long long>(), nullptr);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, a, b));
-        if (ms) *ms = t;
+        timed(ms, [&] { launch_kv_unpack(db.as<__half>(), dk.as<__half>(), dv.as<__half>(), n_ctx, n_layer, n_embd, r0, n, ds.as<unsigned long long>(), nullptr); return true; });
         if (k) { HIP_CHECK(hipMemcpy(k, dk.p, cache, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, cache, hipMemcpyDeviceToHost)); }
         HIP_CHECK(hipMemcpy(sum_out, ds.p, 8, hipMemcpyDeviceToHost));
         return 0;
@@ -1136,14 +1107,7 @@ int minigpt4_amd_test_logprob_rows(const float *logits, int rows, int n_vocab, i
         const size_t n = (size_t)rows * ld, R = (size_t)rows;
         DevBuf dl(n * 4), dt(R * 4), dp(R * 4), dg(R * 4), dq(R * 4);
         HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, targets, R * 4, hipMemcpyHostToDevice));
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        launch_logprob_rows(dl.as<float>(), ld, n_vocab, rows, dt.as<int>(), dp.as<float>(), dg.as<int>(), dq.as<float>(), nullptr);
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        timed(ms_out, [&] { launch_logprob_rows(dl.as<float>(), ld, n_vocab, rows, dt.as<int>(), dp.as<float>(), dg.as<int>(), dq.as<float>(), nullptr); return true; });
         HIP_CHECK(hipMemcpy(logprob_out, dp.p, R * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(greedy_out, dg.p, R * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(greedy_logprob_out, dq.p, R * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -1166,14 +1130,7 @@ int minigpt4_amd_test_topn_rows(const float *logits, int buf_rows, int n_vocab, 
         HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, targets, R * 4, hipMemcpyHostToDevice));
         if (row_index) HIP_CHECK(hipMemcpy(dx.p, row_index, R * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(di.p, 0xFF, RN * 4)); HIP_CHECK(hipMemset(dp.p, 0xFF, RN * 4));   // an entry the kernel leaves out shows as id -1 / NaN
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_topn_rows(dl.as<float>(), ld, n_vocab, rows, row_index ? dx.as<int>() : nullptr, top_n, dt.as<int>(), di.as<int>(), dp.as<float>(), dr.as<int>(), dq.as<float>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        if (!timed(ms_out, [&] { return launch_topn_rows(dl.as<float>(), ld, n_vocab, rows, row_index ? dx.as<int>() : nullptr, top_n, dt.as<int>(), di.as<int>(), dp.as<float>(), dr.as<int>(), dq.as<float>(), nullptr); })) return 3;
         HIP_CHECK(hipMemcpy(ids_out, di.p, RN * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(logprobs_out, dp.p, RN * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(rank_out, dr.p, R * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(target_logprob_out, dq.p, R * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -1244,14 +1201,7 @@ int minigpt4_amd_test_kv_permute(int n_slot, int n_layer, int n_ctx, int n_embd,
         HIP_CHECK(hipMemcpy(dp.p, parent, (size_t)n * 4, hipMemcpyHostToDevice));
         KvPermuteSlots ps{};
         for (int i = 0; i < n; i++) ps.s[i] = slots[i];
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        launch_kv_permute(dk.as<__half>(), dv.as<__half>(), slot_n, n_slot, ps, n, dp.as<int>(), n_layer, n_ctx, n_embd, r0, r1, nullptr);
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms) *ms = t;
+        timed(ms, [&] { launch_kv_permute(dk.as<__half>(), dv.as<__half>(), slot_n, n_slot, ps, n, dp.as<int>(), n_layer, n_ctx, n_embd, r0, r1, nullptr); return true; });
         if (k) { HIP_CHECK(hipMemcpy(k, dk.p, total * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(v, dv.p, total * 2, hipMemcpyDeviceToHost)); }
         return 0;
     });
@@ -1279,14 +1229,7 @@ int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, i
                                float *adjusted_out, float *ms_out) {
     static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16, "the hook's word layout");
     if (!logits || !rows || !picked_out || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n_rows < 1 || n_table < 0 || (n_table > 0 && !table)) return 1;
-    for (int r = 0; r < n_rows; r++) {   // everything that indexes device memory
-        const int32_t *w = rows + 8 * (size_t)r;
-        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table) return 1;
-        std::vector<int> ids;
-        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
-    }
+    if (!pen_rows_ok(rows, n_rows, table, n_table, buf_rows, n_vocab)) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
         const size_t n = (size_t)buf_rows * ld, R = (size_t)n_rows, T = (size_t)std::max(n_table, 1);
@@ -1294,14 +1237,7 @@ int minigpt4_amd_test_pen_pick(const float *logits, int buf_rows, int n_vocab, i
         HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, rows, R * sizeof(PenRow), hipMemcpyHostToDevice));
         if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dp.p, 0xFF, R * 4)); HIP_CHECK(hipMemset(da.p, 0xFF, T * 4));   // what the kernel leaves out shows as id -1 / NaN
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_pen_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<PenRow>(), dt.as<PenEntry>(), dp.as<int>(), da.as<float>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        if (!timed(ms_out, [&] { return launch_pen_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<PenRow>(), dt.as<PenEntry>(), dp.as<int>(), da.as<float>(), nullptr); })) return 3;
         HIP_CHECK(hipMemcpy(picked_out, dp.p, R * 4, hipMemcpyDeviceToHost));
         if (adjusted_out && n_table > 0) HIP_CHECK(hipMemcpy(adjusted_out, da.p, (size_t)n_table * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -1336,14 +1272,7 @@ int minigpt4_amd_test_constrain_index(const uint8_t *vocab, const int32_t *off, 
         HIP_CHECK(hipMemcpy(doff.p, off, ((size_t)n_vocab + 1) * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, trans, S * 512, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(da.p, accept, A * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(di.p, 0xA5, S * W * 4));                                           // a word the kernel leaves out shows
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_constrain_index(dv.as<unsigned char>(), doff.as<int>(), n_vocab, dt.as<uint16_t>(), da.as<unsigned>(), n_states, di.as<unsigned>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        if (!timed(ms_out, [&] { return launch_constrain_index(dv.as<unsigned char>(), doff.as<int>(), n_vocab, dt.as<uint16_t>(), da.as<unsigned>(), n_states, di.as<unsigned>(), nullptr); })) return 3;
         HIP_CHECK(hipMemcpy(index_out, di.p, S * W * 4, hipMemcpyDeviceToHost));
         return 0;
     });
@@ -1352,14 +1281,8 @@ int minigpt4_amd_test_constrain_pick(const float *logits, int buf_rows, int n_vo
                                      const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, int32_t *out, float *ms_out) {
     static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(ConRow) == 48, "the hook's word layout");
     if (!logits || !rows || !out || !bitmaps || !bitmap_of_row || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n_rows < 1 || n_bitmaps < 1 || n_table < 0 || (n_table > 0 && !table)) return 1;
-    for (int r = 0; r < n_rows; r++) {   // everything that indexes device memory
-        const int32_t *w = rows + 8 * (size_t)r;
-        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table || bitmap_of_row[r] < 0 || bitmap_of_row[r] >= n_bitmaps) return 1;
-        std::vector<int> ids;
-        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
-    }
+    if (!pen_rows_ok(rows, n_rows, table, n_table, buf_rows, n_vocab)) return 1;
+    for (int r = 0; r < n_rows; r++) if (bitmap_of_row[r] < 0 || bitmap_of_row[r] >= n_bitmaps) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
         const size_t n = (size_t)buf_rows * ld, R = (size_t)n_rows, T = (size_t)std::max(n_table, 1), W = (size_t)constraint_words(n_vocab);
@@ -1370,14 +1293,7 @@ int minigpt4_amd_test_constrain_pick(const float *logits, int buf_rows, int n_vo
         HIP_CHECK(hipMemcpy(db.p, bitmaps, (size_t)n_bitmaps * W * 4, hipMemcpyHostToDevice));
         if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dp.p, 0xFF, R * 4));                                                // what the kernel leaves out shows as id -1
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_constrain_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<ConRow>(), dt.as<PenEntry>(), dp.as<int>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        if (!timed(ms_out, [&] { return launch_constrain_pick(dl.as<float>(), ld, n_vocab, n_rows, dr.as<ConRow>(), dt.as<PenEntry>(), dp.as<int>(), nullptr); })) return 3;
         HIP_CHECK(hipMemcpy(out, dp.p, R * 4, hipMemcpyDeviceToHost));
         return 0;
     });
@@ -1399,14 +1315,7 @@ int minigpt4_amd_test_guide_rows(const float *logits, int buf_rows, int n_vocab,
         HIP_CHECK(hipMemcpy(dl.p, logits, total * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dt.p, tab.data(), P * sizeof(GuidePair), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dr.p, row_tok_io, 64 * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dm.p, 0xFF, PV * 4)); HIP_CHECK(hipMemset(dp.p, 0xFF, P * 4)); HIP_CHECK(hipMemset(dv.p, 0xFF, P * 4));   // what the kernel leaves out shows as NaN / id -1
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_guide_rows(dl.as<float>(), ld, n_vocab, n, dt.as<GuidePair>(), mixed_out ? dm.as<float>() : nullptr, dp.as<int>(), dv.as<float>(), dr.as<int>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        if (!timed(ms_out, [&] { return launch_guide_rows(dl.as<float>(), ld, n_vocab, n, dt.as<GuidePair>(), mixed_out ? dm.as<float>() : nullptr, dp.as<int>(), dv.as<float>(), dr.as<int>(), nullptr); })) return 3;
         if (mixed_out) HIP_CHECK(hipMemcpy(mixed_out, dm.p, PV * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(pick_out, dp.p, P * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(pick_value_out, dv.p, P * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(row_tok_io, dr.p, 64 * 4, hipMemcpyDeviceToHost));
@@ -1433,16 +1342,11 @@ int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab
     static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(SampleRow) == 72 && sizeof(SampleOut) == (5 + 2 * SAMPLE_MAX) * 4, "the hook's word layout");
     if (!logits || !rows || !bitmap_of_row || !temp_top_p || !top_k || !seed_draws || !tok_index || !row_tok_io || !out || buf_rows < 1 || n_vocab < 1 || ld < n_vocab || n_rows < 1 ||
         n_table < 0 || (n_table > 0 && !table) || n_bitmaps < 0 || (n_bitmaps > 0 && !bitmaps)) return 1;
-    for (int r = 0; r < n_rows; r++) {   // everything that indexes device memory, and the parameters the engine checks
-        const int32_t *w = rows + 8 * (size_t)r;
-        if (w[0] < 0 || w[0] >= buf_rows || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table || bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps ||
-            tok_index[r] < -1 || tok_index[r] >= 64 || top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
+    if (!pen_rows_ok(rows, n_rows, table, n_table, buf_rows, n_vocab)) return 1;
+    for (int r = 0; r < n_rows; r++) {   // the other indices, and the parameters the engine checks
+        if (bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps || tok_index[r] < -1 || tok_index[r] >= 64 || top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
         const float temp = temp_top_p[2 * (size_t)r], top_p = temp_top_p[2 * (size_t)r + 1];
         if (!std::isfinite(temp) || !(temp > 0.0f) || !(top_p > 0.0f) || !(top_p <= 1.0f)) return 1;
-        std::vector<int> ids;
-        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
     }
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -1460,14 +1364,7 @@ int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab
         if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dtok.p, row_tok_io, 64 * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dout.p, 0xFF, R * sizeof(SampleOut)));                              // what the kernel leaves out shows as -1 / NaN
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_sample_rows(dl.as<float>(), ld, n_vocab, n_rows, dr.as<SampleRow>(), dt.as<PenEntry>(), dout.as<SampleOut>(), dtok.as<int>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;
+        if (!timed(ms_out, [&] { return launch_sample_rows(dl.as<float>(), ld, n_vocab, n_rows, dr.as<SampleRow>(), dt.as<PenEntry>(), dout.as<SampleOut>(), dtok.as<int>(), nullptr); })) return 3;
         HIP_CHECK(hipMemcpy(out, dout.p, R * sizeof(SampleOut), hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(row_tok_io, dtok.p, 64 * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -1482,16 +1379,11 @@ int minigpt4_amd_test_draft_sample(const float *logits, int R, int n_vocab, int 
     static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(SampleRow) == 72 && sizeof(SampleOut) == (5 + 2 * SAMPLE_MAX) * 4, "the hook's word layout");
     if (!logits || !rows || !bitmap_of_row || !temp_top_p || !top_k || !seed_draws || !row_tok || !state_io || !slot_logits_io || !res_out || !out || R < 1 || R > DRAFT_ROWS ||
         n_vocab < 1 || ld < n_vocab || slot < 0 || slot > 1 || n_table < 0 || (n_table > 0 && !table) || n_bitmaps < 0 || (n_bitmaps > 0 && !bitmaps)) return 1;
-    for (int r = 0; r < R; r++) {
-        const int32_t *w = rows + 8 * (size_t)r;
-        if (w[0] != r || w[1] < 0 || w[2] < 0 || w[2] > PEN_TABLE_MAX || (long long)w[1] + w[2] > n_table || bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps ||
-            top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
+    if (!pen_rows_ok(rows, R, table, n_table, /*buf_rows=*/R, n_vocab)) return 1;
+    for (int r = 0; r < R; r++) {   // row r decides on logits row r
+        if (rows[8 * (size_t)r] != r || bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps || top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
         const float temp = temp_top_p[2 * (size_t)r], top_p = temp_top_p[2 * (size_t)r + 1];
         if (!std::isfinite(temp) || !(temp > 0.0f) || !(top_p > 0.0f) || !(top_p <= 1.0f)) return 1;
-        std::vector<int> ids;
-        for (int i = 0; i < w[2]; i++) { const int id = table[4 * ((size_t)w[1] + i)]; if (id < 0 || id >= n_vocab) return 1; ids.push_back(id); }
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return 1;
     }
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -1514,16 +1406,11 @@ int minigpt4_amd_test_draft_sample(const float *logits, int R, int n_vocab, int 
         HIP_CHECK(hipMemcpy(dtok.p, tok, sizeof(tok), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dslot.p, &slot, 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dst.p, st, sizeof(st), hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dkeep.p, slot_logits_io, 2 * V * 4, hipMemcpyHostToDevice));
         HIP_CHECK(hipMemset(dout.p, 0xFF, (size_t)R * sizeof(SampleOut))); HIP_CHECK(hipMemset(dres.p, 0xFF, DRAFT_SAMPLE_RES * 4));   // what the kernels leave out shows as -1
-        Events ev;
-        HIP_CHECK(hipEventCreate(&ev.a)); HIP_CHECK(hipEventCreate(&ev.b));
         if (!launch_sample_rows(dl.as<float>(), ld, n_vocab, R, dr.as<SampleRow>(), dt.as<PenEntry>(), dout.as<SampleOut>(), nullptr, nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.a, nullptr));
-        if (!launch_draft_sample_finish(dl.as<float>(), ld, n_vocab, R, dtok.as<int>(), dout.as<SampleOut>(), dslot.as<int>(), dst.as<int>(), dst.as<int>() + 2, dst.as<int>() + 4,
-                                        dkeep.as<float>(), dres.as<int>(), nullptr)) return 3;
-        HIP_CHECK(hipEventRecord(ev.b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float t = 0; HIP_CHECK(hipEventElapsedTime(&t, ev.a, ev.b));
-        if (ms_out) *ms_out = t;                                                 // k_draft_sample_finish alone
+        if (!timed(ms_out, [&] {                                                 // k_draft_sample_finish alone
+                return launch_draft_sample_finish(dl.as<float>(), ld, n_vocab, R, dtok.as<int>(), dout.as<SampleOut>(), dslot.as<int>(), dst.as<int>(), dst.as<int>() + 2,
+                                                  dst.as<int>() + 4, dkeep.as<float>(), dres.as<int>(), nullptr);
+            })) return 3;
         HIP_CHECK(hipMemcpy(out, dout.p, (size_t)R * sizeof(SampleOut), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(res_out, dres.p, DRAFT_SAMPLE_RES * 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(st, dst.p, sizeof(st), hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(slot_logits_io, dkeep.p, 2 * V * 4, hipMemcpyDeviceToHost));
         for (int s = 0; s < 2; s++) for (int f = 0; f < 3; f++) state_io[3 * s + f] = st[2 * f + s];
@@ -1823,13 +1710,8 @@ int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int i
         auto run = [&]() { return launch_attn_prefill(dq.as<float>(), dk.as<__half>(), dv.as<__half>(), N, n_head, hd, dnp.as<int>(), T, tb, dout.as<float>(), nullptr); };
         for (int i = 0; i < 3; i++) if (!run()) return 4;
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; i++) run();
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(); return true; });
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         return 0;
     });
@@ -1884,13 +1766,8 @@ int minigpt4_amd_bench_matvec(int ggml_type, int rows, int cols, int n_mat, int 
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) run(i);
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t a, b; HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-        HIP_CHECK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; i++) run(i % n_sets);
-        HIP_CHECK(hipEventRecord(b, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-        HIP_IGNORE(hipEventDestroy(a)); HIP_IGNORE(hipEventDestroy(b));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(i % n_sets); return true; });
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         if (bytes_per_launch) *bytes_per_launch = (double)gt_nbytes(ggml_type, (size_t)rows * cols) * n_mat;
         return 0;
@@ -1944,13 +1821,8 @@ int minigpt4_amd_bench_mmq(int ggml_type, int rows, int cols, int n_mat, int N, 
         };
         run(); run();
         HIP_CHECK(hipDeviceSynchronize());
-        hipEvent_t ea, eb; HIP_CHECK(hipEventCreate(&ea)); HIP_CHECK(hipEventCreate(&eb));
-        HIP_CHECK(hipEventRecord(ea, nullptr));
-        for (int i = 0; i < iters; i++) run();
-        HIP_CHECK(hipEventRecord(eb, nullptr));
-        HIP_CHECK(hipDeviceSynchronize());
-        float ms = 0; HIP_CHECK(hipEventElapsedTime(&ms, ea, eb));
-        HIP_IGNORE(hipEventDestroy(ea)); HIP_IGNORE(hipEventDestroy(eb));
+        float ms = 0;
+        timed(&ms, [&] { for (int i = 0; i < iters; i++) run(); return true; });
         set_mmq_enabled(keep_gen);
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         return 0;
