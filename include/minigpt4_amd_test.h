@@ -287,7 +287,7 @@ MINIGPT4_API int minigpt4_amd_test_draft_tables(const int32_t *hist, int n_hist,
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,
  * 2 = k_attn_prefill_h QS 2, 3 = QS 1 (both sides), 4 = the exact-f32 kernel (both sides per segment).  *seg_launched = 1 when the one segmented launch ran.
  * out_h_seg / out_h_ref (both or neither; [N][E] fp16 bits): the launchers may store fp16 rows there instead (the F16 wo's input); wrote_h[0] / [1] = whether the
- * segmented side / every per-segment launch did.  The caller's form / f16 settings are restored.  1 = bad arguments */
+ * segmented side / every per-segment launch did.  The form applies to this call only.  1 = bad arguments */
 MINIGPT4_API int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slots, const uint16_t *kc, const uint16_t *vc, int n_seg, const int32_t *segs, const float *q,
                                                     int form, float *out_seg, float *out_ref, int *seg_launched, uint16_t *out_h_seg, uint16_t *out_h_ref, int *wrote_h);
 /* RoPE + cache append of packed rows (k_rope_kv_seg; ks > 1: its slab form k_rope_kv_seg_slabs over ks copies of q | k | v) against k_rope_kv (_slabs) per segment.  segs as
@@ -297,10 +297,18 @@ MINIGPT4_API int minigpt4_amd_test_rope_kv_seg(int n_head, int hd, int n_ctx, in
 /* Micro-benchmark of the prompt-row attention on a synthetic fp16 K / V cache (tools/timeline_attn_prefill.py); _timeline_attn: its stamps in a -DMG4_TIMELINE build */
 MINIGPT4_API int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int iters, float *us_per_launch);
 MINIGPT4_API int minigpt4_amd_timeline_attn(unsigned long long *out, int max_workgroups);
-/* force one tile shape (an "arm" of launch_gemm_f16_arm in vision_kernels.hip; 0 = the launcher's own choice) for every small-M GEMM / split-K GEMM of this process */
+/* force one tile shape (an "arm" of launch_gemm_f16_arm in vision_kernels.hip; 0 = the launcher's own choice) for every small-M GEMM / split-K GEMM
+ * launched by the single-kernel hooks of this library, until set again (a context has its own tuning and never reads this one) */
 MINIGPT4_API void minigpt4_amd_test_set_gemm_arm(int arm, int sk_arm);
 /* 0: split-K GEMM slices in grid.z (the rounds 3-5 workgroup -> XCD mapping); 1 (default): the [slice][tile] work list dealt to the XCDs in contiguous ranges */
 MINIGPT4_API void minigpt4_amd_test_set_splitk_xcd(int on);
+/* Launch tuning (csrc/kernels.hpp: struct LaunchTuning) as n <= MINIGPT4_AMD_TUNING_FIELDS ints in the order cus, mv_waves_per_cu, mmq, mmqh, mmq_ks, mmq3_waves,
+ * attn_prefill_w8, attn_prefill_f16, attn_prefill_form, gemm_arm, gemm_sk_arm, f16_ks, splitk_xcd, attn_vit_qt; both return the number of fields written (-1: bad arguments).
+ * _tuning_from_env: what a context loaded now on a device with `cus` compute units would get (the defaults + MINIGPT4_ATTN_PREFILL_W8 / _MMQH / _ATTN_QT / _SPLITK_XCD /
+ * _F16_KS; host only).  _context_tuning: what `ctx` got at its load */
+#define MINIGPT4_AMD_TUNING_FIELDS 14
+MINIGPT4_API int minigpt4_amd_test_tuning_from_env(int cus, int *out, int n);
+MINIGPT4_API int minigpt4_amd_test_context_tuning(struct MiniGPT4Context *ctx, int *out, int n);
 /* diagnostic builds (-DMG4_TIMELINE): the 32 clock stamps per workgroup of the last image-path GEMM launch; 0 = built without */
 MINIGPT4_API int minigpt4_amd_timeline_vision(unsigned long long *out, int max_workgroups);
 /* Micro-benchmark of the decode mat-vec kernels on synthetic weight planes (see bench_kernels.py). variant 0: one launch per matrix, 1: fused persistent-wave launch,

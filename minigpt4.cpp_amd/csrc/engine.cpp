@@ -112,6 +112,18 @@ void Engine::sync() { (void)flush(); HIP_CHECK(hipStreamSynchronize(stream_)); }
 // ====================================================================================================================
 // init / load
 // ====================================================================================================================
+// The launch tuning of a context: the defaults, the device's CU count and the five environment switches that choose among launch forms.  Read per context, at load --
+// a later context with the variable unset has the default again.
+LaunchTuning launch_tuning_from_env(int cus) {
+    LaunchTuning t;
+    t.cus = cus;
+    if (const char *e = getenv("MINIGPT4_ATTN_PREFILL_W8")) t.attn_prefill_w8 = atoi(e);   // 0: prompt attention without the 8-wave loader / MFMA form
+    if (const char *e = getenv("MINIGPT4_MMQH")) t.mmqh = atoi(e);                         // 1: Q4_K / Q5_K prompt rows on the fp16-MFMA form with scaled operands (measured SLOWER; A/B)
+    if (const char *e = getenv("MINIGPT4_ATTN_QT")) t.attn_vit_qt = atoi(e);               // query tiles per workgroup of the ViT / Q-Former attention (1 = the rounds 2-5 form; A/B, bit-identical)
+    if (const char *e = getenv("MINIGPT4_SPLITK_XCD")) t.splitk_xcd = atoi(e);             // 0: split-K GEMM slices in grid.z, every XCD walks every slice (rounds 3-5; A/B, bit-identical)
+    if (const char *e = getenv("MINIGPT4_F16_KS")) t.f16_ks = atoi(e);                     // forced K split of the F16 language model's single-matrix prompt launches (wo, w2; A/B)
+    return t.normalised();
+}
 int Engine::init(const std::string &vision_path, const std::string &llm_path, int seed, int n_ctx, int n_batch) {
     const int ndev = device_count_noexcept();
     if (ndev <= 0) { set_last_error("no HIP device visible: the MI355X engine has no CPU fallback"); MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
@@ -144,7 +156,6 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     // (include/minigpt4_amd_test.h).
     use_graph_ = !(getenv("MINIGPT4_NO_GRAPH") && atoi(getenv("MINIGPT4_NO_GRAPH")));
     max_chunk_ = max_rows_;
-    if (getenv("MINIGPT4_ATTN_PREFILL_W8")) set_attn_prefill_w8(atoi(getenv("MINIGPT4_ATTN_PREFILL_W8")));   // 0: prompt attention without the 8-wave loader / MFMA form
     if (const char *dc = getenv("MINIGPT4_DEFER_COMBINE")) defer_combine_ = atoi(dc) != 0;                    // 0: every K-split combine as its own launch
     // bit mask: 1 w1|w3 + silu*mul in one launch, 4 the attention kernel stores fp16 rows for wo
     if (const char *fp = getenv("MINIGPT4_F16_PAIR")) f16_pair_ = atoi(fp);
@@ -155,10 +166,7 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     // 4 x heads fit the CUs -- 376.2-376.4 against 370.5-371.0 tok/s at 40 heads, profiles/r12_decode_attention_vsplit.log), 1 / 2 / 4 = force
     if (const char *e = getenv("MINIGPT4_ATTN_VS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) attn_vs_ = v; }
     if (const char *e = getenv("MINIGPT4_MV_IB")) { const int v = atoi(e); if (v == 0 || v == 1) for (bool &b : mv_issue_bar_) b = v != 0; }   // unset: the per-site defaults
-    n_cus_ = prop.multiProcessorCount;
-    // 1: Q4_K / Q5_K prompt rows on the fp16-MFMA form with scaled operands (k_mmqh_q45k: measured SLOWER,
-    // profiles/r05_prefill_fp16_scaled_operands.md; A/B)
-    if (const char *e = getenv("MINIGPT4_MMQH")) set_mmqh(atoi(e));
+    tune_ = launch_tuning_from_env(prop.multiProcessorCount);   // the CU count and the five launch switches (MINIGPT4_ATTN_PREFILL_W8, _MMQH, _ATTN_QT, _SPLITK_XCD, _F16_KS)
     // 0: the decode step gathers exp / SiLU from ggml's fp16 tables like rounds 1-4 (A/B)
     if (const char *e = getenv("MINIGPT4_COMPUTED_TABLES")) computed_tables_ = atoi(e) != 0;
     // 1: the MFMA batched launches norm + quantise their rows themselves (measured SLOWER: 864 vs 987 tok/s at B = 4; A/B)
@@ -169,25 +177,18 @@ int Engine::init(const std::string &vision_path, const std::string &llm_path, in
     if (const char *e = getenv("MINIGPT4_RI_WO")) ri_wo_ = atoi(e) != 0;
     // 0: batched decode on the v_dot4 multi-row mat-vec (rounds 2-4), no row-interleaved image
     if (const char *e = getenv("MINIGPT4_RI")) use_ri_ = atoi(e) != 0;
-    set_ri_cus(prop.multiProcessorCount);
     // 0: the Q-Former's image-independent head is recomputed per encode (round-4 form, A/B)
     if (const char *e = getenv("MINIGPT4_QF_FOLD")) qf_fold_ = atoi(e) != 0;
-    // query tiles per workgroup of the ViT / Q-Former attention (k_attn_vit; unset / 0 = chosen per launch; 1 = the rounds 2-5 form; A/B, bit-identical)
-    if (const char *e = getenv("MINIGPT4_ATTN_QT")) set_attn_vit_qt(atoi(e));
-    // 0: split-K GEMM slices in grid.z, every XCD walks every slice (rounds 3-5; A/B, bit-identical)
-    if (const char *e = getenv("MINIGPT4_SPLITK_XCD")) set_gemm_splitk_xcd(atoi(e));
     // K slices of the ViT's attention projection (1 = whole K + standalone LayerNorm: the default since round 3; 2..: split-K + the reduce that also normalises; A/B)
     if (const char *e = getenv("MINIGPT4_SPLITK_PROJ")) splitk_proj_ = std::max(1, std::min(SPLITK_MAX, atoi(e)));
     if (const char *e = getenv("MINIGPT4_SPLITK_FC2")) splitk_fc2_ = std::max(1, std::min(SPLITK_MAX, atoi(e)));     // K slices of the ViT's fc2 (default 4; A/B)
     // decode step: which row preparations ride in their consumer's prologue (bit 0 qkv, 1 wo, 2 w1|w3, 3 w2 <- SiLU * mul + quantisation, 4 output, 5 pair, 6 mixed qkv; default 87; A/B)
     if (const char *e = getenv("MINIGPT4_FUSE")) fuse_mask_ = atoi(e);
-    if (const char *e = getenv("MINIGPT4_F16_KS")) set_gemm_tuning(-1, atoi(e));     // forced K split of the F16 language model's single-matrix prompt launches (wo, w2; 0 = choose; A/B)
     if (const char *e = getenv("MINIGPT4_PAIR_SILU_COMPUTED")) pair_silu_computed_ = atoi(e) != 0;   // 0: the F16 model's w1 | w3 pair epilogue gathers SiLU from the fp16 table (A/B)
     if (const char *e = getenv("MINIGPT4_COMPUTED_GELU")) computed_gelu_ = atoi(e) != 0;   // 0: the vision GEMMs' GELU epilogues gather from the fp16 table (A/B)
     if (const char *e = getenv("MINIGPT4_QKV_HEAD_MAJOR")) qkv_head_major_ = atoi(e) != 0;
     if (const char *e = getenv("MINIGPT4_QF_SPLITK")) qf_splitk_ = atoi(e) != 0;     // 0: the Q-Former's dense / output layers as whole-K launches + standalone LayerNorm (A/B)
     if (const char *e = getenv("MINIGPT4_KV_HOIST")) kv_hoist_ = atoi(e) != 0;     // 0: one K | V projection GEMM per cross-attention layer (round-4 form, A/B)
-    set_matvec_tuning(0, 0, prop.multiProcessorCount);
     if (const char *ns = getenv("MINIGPT4_CONVERSATIONS")) conv_.assign((size_t)std::max(1, std::min(MAX_CONVERSATIONS, atoi(ns))), Conversation{});
     sampler_.seed(seed);
     smp_load_seed_ = (uint32_t)seed; smp_reseed();
@@ -605,7 +606,7 @@ void Engine::alloc_buffers() {
     sz(S * L * C * E * 2); sz(S * L * C * E * 2); sz(2 * C * (hd / 2) * 4 * 2); sz(3 * 65536 * 2);
     sz(5 * B * E * 4); sz(2 * B * F * 4); sz(S * V * 4); sz(S * V * 4); sz(8 * 256 + 2 * B * 4);
     sz(2 * B * Kmax); sz(B * Kmax / 256 * 4 + 64); sz(B * Kmax / 16 * 2 + 64); sz(B * Kmax / 16 + 64); sz(B * Kmax * 2); sz(B * Kmax / 8 + 128); sz(4 * (B * Kmax / 32 * 4 + 64)); sz(B * Kmax * 2); sz(B * Kmax * 4);
-    sz(8192); sz((size_t)64 << 20); sz(attn_split_workspace_bytes((int)llm_.n_head, (int)hd, n_ctx_, std::max(attn_splits_forced_, attn_split_count((int)llm_.n_head, n_cus_))));
+    sz(8192); sz((size_t)64 << 20); sz(attn_split_workspace_bytes((int)llm_.n_head, (int)hd, n_ctx_, std::max(attn_splits_forced_, attn_split_count((int)llm_.n_head, tune_.cus))));
     const size_t VB = (size_t)VISION_BATCH_MAX;                            // images encoded in one pass (minigpt4_amd_encode_images)
     sz(VB * 3 * 224 * 224 * 4); sz(VB * 256 * 592 * 2); sz(VB * 256 * D * 4); sz(VB * 257 * D * 4); sz(VB * 257 * 3 * D * 4); sz(VB * 3 * 257 * D * 2); sz(VB * 257 * M * 2);
     sz(VB * (size_t)SPLITK_MAX * 257 * D * 4);
@@ -652,7 +653,7 @@ void Engine::alloc_buffers() {
     act_.dk = takef(B * Kmax / 256 + 16); act_.bsk = reinterpret_cast<int16_t *>(buf_arena_.take(B * Kmax / 16 * 2 + 64));
     act_.bsq = reinterpret_cast<int8_t *>(buf_arena_.take(B * Kmax / 16 + 64));
     // MINIGPT4_MMQH=1 only: fp16 images of the Q8_K rows for the fp16-MFMA prompt mat-mul (k_mmqh_q45k, not adopted)
-    if (mmqh_enabled()) { act_.q16 = takeh(B * Kmax); act_.bs16 = takeh(B * Kmax / 16 + 64); }
+    if (tune_.mmqh) { act_.q16 = takeh(B * Kmax); act_.bs16 = takeh(B * Kmax / 16 + 64); }
     act_.d0 = takef(B * Kmax / 32 + 16); act_.d1 = takef(B * Kmax / 32 + 16); act_.s1 = takef(B * Kmax / 32 + 16);
     act_.sum0 = reinterpret_cast<int *>(buf_arena_.take(B * Kmax / 32 * 4 + 64));
     act_.xh = takeh(B * Kmax); act_.xf = takef(B * Kmax);
@@ -662,14 +663,12 @@ void Engine::alloc_buffers() {
     batch_graph_.assign((size_t)MAX_CONVERSATIONS + 1, nullptr);
     d_tokens_ = reinterpret_cast<int *>(buf_arena_.take(B * 4));
     d_scratch_ = buf_arena_.take(8192);
-    attn_splits_ = attn_splits_forced_ > 0 ? attn_splits_forced_ : attn_split_count((int)llm_.n_head, n_cus_);
+    attn_splits_ = attn_splits_forced_ > 0 ? attn_splits_forced_ : attn_split_count((int)llm_.n_head, tune_.cus);
     attn_ws_ = buf_arena_.take(attn_split_workspace_bytes((int)llm_.n_head, (int)hd, n_ctx_, attn_splits_));
     HIP_CHECK(hipMemset(attn_ws_, 0, attn_split_workspace_bytes((int)llm_.n_head, (int)hd, n_ctx_, attn_splits_)));   // the arrival counters start (and are left) at zero
     {   // K-split partial sums of the prefill mat-mul (only prompts short enough to need the extra parallelism use them)
         const size_t slab_floats = (size_t)16 << 20;
-        hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, device_));
         act_.ws = reinterpret_cast<float *>(buf_arena_.take(slab_floats * 4)); act_.ws_floats = slab_floats;
-        set_mmq2_cus(prop.multiProcessorCount);
     }
     HIP_CHECK(hipMemset(d_npast_, 0, 256)); HIP_CHECK(hipMemset(d_argmax_, 0, 256)); HIP_CHECK(hipMemset(d_feed_, 0, 256)); HIP_CHECK(hipMemset(d_btok_, 0, BSTAGE_BYTES));
     HIP_CHECK(hipMemset(d_tokens_, 0, B * 4));
@@ -777,29 +776,29 @@ bool Engine::mul_mat_set(const QWeight *const *W, float *const *y, const float *
     SiteScope sc(this, site, wbytes, s);
     bool done = false;
     // prefill: one launch for the set, weights streamed once per <= 128 rows
-    if (N >= 5 && same && mmq_enabled() >= 2) done = launch_mmq2_set(W, y, res, n, act_here, N, ldy, s, defer_ok && defer_combine_ ? &pend_ : nullptr);
+    if (N >= 5 && same && tune_.mmq >= 2) done = launch_mmq2_set(W, y, res, n, act_here, N, ldy, tune_, s, defer_ok && defer_combine_ ? &pend_ : nullptr);
     // the rows were left in fp16 by an earlier launch, act_ holds OTHER rows
     const bool staged_elsewhere = !prep && (xh_override_ != nullptr || (same && W[0]->type == GT_F16 && N >= 512));
     // unquantised weights at prompt sizes: the set in one launch of the big MFMA GEMM, split K for wo / w2
     if (!done && same && W[0]->type == GT_F16 && N >= 512 && act_.xh) {
         const __half *Wh[3]; for (int i = 0; i < n; i++) Wh[i] = reinterpret_cast<const __half *>(W[i]->qs);
         const __half *Ain = !prep && xh_override_ ? xh_override_ : act_.xh;     // rows some launch left in fp16 elsewhere (the feed-forward pair's epilogue)
-        done = launch_gemm_f16_set(Ain, W[0]->cols, Wh, n, N, W[0]->rows, W[0]->cols, y, res, ldy, act_.ws, act_.ws_floats, n_cus_, s, defer_ok && defer_combine_ ? &pend_ : nullptr);
+        done = launch_gemm_f16_set(Ain, W[0]->cols, Wh, n, N, W[0]->rows, W[0]->cols, y, res, ldy, act_.ws, act_.ws_floats, tune_, s, defer_ok && defer_combine_ ? &pend_ : nullptr);
     }
     if (!done && staged_elsewhere && xh_override_) throw HipError{hipErrorInvalidValue, "F16 set launch refused rows that only exist in fp16 (no generic path may read act_ here)", __FILE__, __LINE__};
     if (!done && silu_pair) {   // the pair epilogue needs the two matrices equally spaced; launch_matvec_set refuses otherwise and the plain launch below runs
-        done = fuse ? launch_matvec_set(W, y, res, n, act_, s, prep->kind, prep->x, prep->w, &tabs_, 1, issue_bar) : launch_matvec_set(W, y, res, n, act_, s, 0, nullptr, nullptr, &tabs_, 1);
+        done = fuse ? launch_matvec_set(W, y, res, n, act_, tune_, s, prep->kind, prep->x, prep->w, &tabs_, 1, issue_bar) : launch_matvec_set(W, y, res, n, act_, tune_, s, 0, nullptr, nullptr, &tabs_, 1);
         silu_pair = done;
     }
     if (!done) {
-        if (fuse) done = launch_matvec_set(W, y, res, n, act_, s, prep->kind, prep->x, prep->w, &tabs_, 0, issue_bar);
-        else if (v2) done = launch_matvec_set(W, y, res, n, act_, s);
+        if (fuse) done = launch_matvec_set(W, y, res, n, act_, tune_, s, prep->kind, prep->x, prep->w, &tabs_, 0, issue_bar);
+        else if (v2) done = launch_matvec_set(W, y, res, n, act_, tune_, s);
     }
     if (!done) {
         if (fuse) throw HipError{hipErrorInvalidValue, "fused mat-vec prologue rejected a supported shape", __FILE__, __LINE__};
         for (int i = 0; i < n; i++) {
             const QWeight *Wp[1] = {W[i]}; float *Yp[1] = {y[i]}; const float *Rp[1] = {res ? res[i] : nullptr};
-            if (!(N == 1 && use_v2_ && launch_matvec_set(Wp, Yp, Rp, 1, act_, s))) launch_mul_mat(*W[i], act_, N, y[i], ldy, res ? res[i] : nullptr, s);
+            if (!(N == 1 && use_v2_ && launch_matvec_set(Wp, Yp, Rp, 1, act_, tune_, s))) launch_mul_mat(*W[i], act_, N, y[i], ldy, res ? res[i] : nullptr, tune_, s);
         }
     }
     if (kept.ks > 1) {   // q | k pending from the earlier launch + this launch's v (pending or already in place): one SlabSrc for launch_rope_kv_slabs / the flush
@@ -823,10 +822,10 @@ bool Engine::mixed_qkv(const LayerW &L, hipStream_t s, bool fuse) {
     const QWeight *W1[2] = {&L.wq, &L.wk}, *W2[1] = {&L.wv}; float *Y1[2] = {q_, k_}, *Y2[1] = {v_};
     if (act_mask_for(L.wq.type) != ACT_Q8K || act_mask_for(L.wv.type) != ACT_Q8K) return false;
     SiteScope sc(this, "qkv", (double)(L.wq.bytes + L.wk.bytes + L.wv.bytes), s);   // only once the launch is certain: a refused shape must not record an empty site
-    if (fuse && matvec_prologue_supported(L.wq.type, E)) { if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, s, 1, x_, L.attn_norm, 0, mv_issue_bar_[MV_QKV_MIXED])) return true; }
+    if (fuse && matvec_prologue_supported(L.wq.type, E)) { if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, tune_, s, 1, x_, L.attn_norm, 0, mv_issue_bar_[MV_QKV_MIXED])) return true; }
     // standalone preparation, then the mixed launch; if that is refused the caller's per-type launches find the row already prepared
     launch_rms_quant(x_, L.attn_norm, 1, E, act_, ACT_Q8K, s);
-    if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, s)) return true;
+    if (launch_matvec_mixed(W1, Y1, 2, W2, Y2, 1, act_, tune_, s)) return true;
     const bool keep = prof_on_; prof_on_ = false;                          // the enclosing site already covers these launches
     mul_mat_set(W1, Y1, nullptr, 2, 1, E, s, nullptr, false); mul_mat(L.wv, 1, v_, E, nullptr, s, nullptr, false);
     prof_on_ = keep;
@@ -868,9 +867,9 @@ void Engine::forward_ref(const Pass &p, hipStream_t s) {
         for (int done = 0, run; done < m.n; done += run) {   // split into runs of equal type / shape (wq | wk + a differently typed wv), one launch each
             run = same_run(m.W, m.n, done);
             const float *const *R = res ? m.R + done : nullptr;
-            const bool ok = N == 1 ? launch_mul_mat_ref_set(m.W + done, m.Y + done, R, run, act_, s)
-                                   : N >= 5 && launch_mmq2_set(m.W + done, m.Y + done, R, run, act_, N, m.W[done]->rows, s, nullptr, 1);
-            if (!ok) for (int i = 0; i < run; i++) launch_mul_mat_ref(*m.W[done + i], act_, N, m.Y[done + i], m.W[done + i]->rows, res, s);
+            const bool ok = N == 1 ? launch_mul_mat_ref_set(m.W + done, m.Y + done, R, run, act_, tune_, s)
+                                   : N >= 5 && launch_mmq2_set(m.W + done, m.Y + done, R, run, act_, N, m.W[done]->rows, tune_, s, nullptr, 1);
+            if (!ok) for (int i = 0; i < run; i++) launch_mul_mat_ref(*m.W[done + i], act_, N, m.Y[done + i], m.W[done + i]->rows, res, tune_, s);
         }
     };
     // One row without a trace (the decode step): the fast step's launch structure -- row preparation in the mat-vec prologues, wq | wk (| wv) and w1
@@ -881,9 +880,9 @@ void Engine::forward_ref(const Pass &p, hipStream_t s) {
         if (!fused_row) return false;
         WeightSet m(Ws, Ys, res);
         if (pro != 0 && !matvec_prologue_supported(m.W[0]->type, m.W[0]->cols)) return false;
-        if (same_shape(m.W, m.n)) return launch_matvec_set(m.W, m.Y, res ? m.R : nullptr, m.n, act_, s, pro, px, pw, &tabs_, MATVEC_EPI_REF);
+        if (same_shape(m.W, m.n)) return launch_matvec_set(m.W, m.Y, res ? m.R : nullptr, m.n, act_, tune_, s, pro, px, pw, &tabs_, MATVEC_EPI_REF);
         if (m.n == 3 && !res && same_shape(m.W, 2) && m.W[2]->cols == m.W[0]->cols && (pro == 0 || pro == 1))
-            return launch_matvec_mixed(m.W, m.Y, 2, m.W + 2, m.Y + 2, 1, act_, s, pro, px, pw, MATVEC_EPI_REF);     // wq | wk + a differently typed wv
+            return launch_matvec_mixed(m.W, m.Y, 2, m.W + 2, m.Y + 2, 1, act_, tune_, s, pro, px, pw, MATVEC_EPI_REF);     // wq | wk + a differently typed wv
         return false;
     };
     for (size_t il = 0; il < layers_.size(); il++) {
@@ -916,7 +915,7 @@ void Engine::forward_ref(const Pass &p, hipStream_t s) {
     if (!(N == 1 && fused_set({&output_}, {logits}, nullptr, 1, x_, norm_))) {
         launch_rms_quant(x_ + (size_t)(N - 1) * E, norm_, 1, E, act_, act_mask_for(output_.type), s, true);
         const QWeight *Wo[1] = {&output_}; float *Yo[1] = {logits};
-        if (!launch_mul_mat_ref_set(Wo, Yo, nullptr, 1, act_, s)) launch_mul_mat_ref(output_, act_, 1, logits, V, nullptr, s);
+        if (!launch_mul_mat_ref_set(Wo, Yo, nullptr, 1, act_, tune_, s)) launch_mul_mat_ref(output_, act_, 1, logits, V, nullptr, tune_, s);
     }
     launch_argmax(logits, V, d_argmax, d_scratch_, s);
     launch_advance(d_npast, N, d_feed, d_argmax, s);
@@ -976,7 +975,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
         if (prof_on_) att_sc.emplace(this, "attention", 4.0 * (double)E * (sg ? sg->key_rows : (double)(conv_[sl].n_committed + N)), s);
         if (dec && p.split) launch_attn_llm_split(q_, k_, v_, kc, vc, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, attn_ws_, attn_splits_, s);
         else if (dec) launch_attn_llm(q_, k_, v_, kc, vc, 1, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_dec_, att_, true, s,
-                                      attn_vs_ ? attn_vs_ : 4 * H <= n_cus_ ? 4 : 2 * H <= n_cus_ ? 2 : 1);   // a workgroup can need a whole CU's LDS: never more of them than CUs
+                                      attn_vs_ ? attn_vs_ : 4 * H <= tune_.cus ? 4 : 2 * H <= tune_.cus ? 2 : 1);   // a workgroup can need a whole CU's LDS: never more of them than CUs
         else {
             if (pend_.ks > 1 && pend_.n == 3 && pend_.y[0] == q_ && pend_.y[1] == k_ && pend_.y[2] == v_ && !pend_.res[0] && !pend_.res[1] && !pend_.res[2] && pend_.stride == (long long)N * E) {
                 if (sg) launch_rope_kv_seg_slabs(pend_, N, H, hd, sg->rows, seq_stride, cos_, sin_, kc, vc, s);
@@ -991,7 +990,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
             // launch
             const bool want_h = (f16_pair_ & 4) && L.wo.type == GT_F16 && N >= 512 && act_.xh && E % 128 == 0;
             if (sg) attn_segments(*sg, kc, vc, want_h, &att_in_xh, s);
-            else if (!(attn_prefill_ && launch_attn_prefill(q_, kc, vc, N, H, hd, d_npast, conv_[sl].n_committed + N, tabs_, att_, s, want_h ? act_.xh : nullptr, &att_in_xh)))
+            else if (!(attn_prefill_ && launch_attn_prefill(q_, kc, vc, N, H, hd, d_npast, conv_[sl].n_committed + N, tabs_, att_, tune_, s, want_h ? act_.xh : nullptr, &att_in_xh)))
                 launch_attn_llm(q_, k_, v_, kc, vc, N, H, hd, d_npast, n_ctx_, cos_, sin_, tabs_, att_, false, s);
         }
         att_sc.reset();
@@ -1005,7 +1004,7 @@ void Engine::forward(const Pass &p, hipStream_t s) {
             prep_rms(x_, L.ffn_norm, N, E, act_mask_for(GT_F16), s);
             SiteScope sc(this, "w1w3", (double)(L.w1.bytes + L.w3.bytes), s);
             pair16 = launch_gemm_f16_silu_pair(act_.xh, E, reinterpret_cast<const __half *>(L.w1.qs), reinterpret_cast<const __half *>(L.w3.qs), N, F, E, pair_silu_computed_ ? tabs_dec_ : tabs_, nullptr,
-                                               reinterpret_cast<__half *>(h1_), F, n_cus_, s);
+                                               reinterpret_cast<__half *>(h1_), F, tune_, s);
         }
         if (pair16) {
             xh_override_ = reinterpret_cast<const __half *>(h1_);
@@ -1070,7 +1069,7 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
         // w2 (13B: 80 row groups x 54 super-blocks): three or four workgroups share a row group, each a K range, last arriver adds the parts.  With
         // the first weight fetch ahead of the staging and batched staging loads the launch is 18.9 (Q5_K) / 20.8 us (Q6_K) against 22.8 / 22.4 for
         // the v_dot4 kernel at B = 4 (equal at B = 3): 1037 vs 1018 tok/s, alternating on one box (profiles/r05_batched_decode_inengine.log)
-        if (ri_w2_ && B == 4 && Ws.size() == 1 && w0->cols >= 8192 && ri_ksplit(groups, w0->cols, ri_ws_) > 1) return true;
+        if (ri_w2_ && B == 4 && Ws.size() == 1 && w0->cols >= 8192 && ri_ksplit(groups, w0->cols, ri_ws_, tune_) > 1) return true;
         return groups >= 128;
     };
     auto mm = [&](std::initializer_list<const QWeight *> Ws, std::initializer_list<float *> ys, const float *res0, int ld, const float *px = nullptr, const float *pw = nullptr) {
@@ -1082,12 +1081,12 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
         // workgroup K split -- every workgroup stages the whole rows anyway)
         if (ri_wo_ && px && !pw && n == 1 && ri_ready_ && B >= 3 && B <= 4 && ri_of(W[0])) {
             const RiPlanes *rp[1] = {ri_of(W[0])};
-            if (launch_matvec_ri(W, rp, y, res0 ? r : nullptr, 1, act_, B, ld, s, px, nullptr, W[0]->cols, RiWorkspace{})) { batch_path_.ri++; batch_path_.ri_plain++; return; }
+            if (launch_matvec_ri(W, rp, y, res0 ? r : nullptr, 1, act_, B, ld, tune_, s, px, nullptr, W[0]->cols, RiWorkspace{})) { batch_path_.ri++; batch_path_.ri_plain++; return; }
         }
         if (ri_serves(Ws) && (!px || pw)) {                 // prepared rows, or rows this launch rms-norms and quantises itself (px, pw)
             const RiPlanes *rp[3]; for (int k = 0; k < n; k++) rp[k] = ri_of(W[k]);
-            if (launch_matvec_ri(W, rp, y, res0 ? r : nullptr, n, act_, B, ld, s, px, pw, W[0]->cols, ri_ws_)) {
-                batch_path_.ri++; if (ri_ksplit(n * (W[0]->rows / 64), W[0]->cols, ri_ws_) > 1) batch_path_.ri_ksplit++;
+            if (launch_matvec_ri(W, rp, y, res0 ? r : nullptr, n, act_, B, ld, tune_, s, px, pw, W[0]->cols, ri_ws_)) {
+                batch_path_.ri++; if (ri_ksplit(n * (W[0]->rows / 64), W[0]->cols, ri_ws_, tune_) > 1) batch_path_.ri_ksplit++;
                 return;
             }
         }
@@ -1100,7 +1099,7 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
                 A.d0 += (size_t)t0 * (K / 32); A.d1 += (size_t)t0 * (K / 32); A.s1 += (size_t)t0 * (K / 32); A.sum0 += (size_t)t0 * (K / 32);
                 float *yo[3]; const float *ro[3];
                 for (int k = 0; k < n; k++) { yo[k] = y[k] + (size_t)t0 * ld; ro[k] = r[k] ? r[k] + (size_t)t0 * ld : nullptr; }
-                ok = launch_matvec_rows(W, yo, res0 ? ro : nullptr, n, A, std::min(4, B - t0), ld, s, px ? px + (size_t)t0 * K : nullptr, pw, K);
+                ok = launch_matvec_rows(W, yo, res0 ? ro : nullptr, n, A, std::min(4, B - t0), ld, tune_, s, px ? px + (size_t)t0 * K : nullptr, pw, K);
                 if (!ok && t0) throw HipError{hipErrorInvalidValue, "multi-row mat-vec refused a pass it had accepted", __FILE__, __LINE__};
             }
             if (ok) { batch_path_.dot4++; return; }
@@ -1112,7 +1111,7 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
             for (int k = 0; k < n; k++) mask |= act_mask_for(W[k]->type);
             if (pw) launch_rms_quant(px, pw, B, K, act_, mask, s); else launch_silu_mul_quant(px, nullptr, B, K, act_, mask, tabs_, s);
         }
-        for (int k = 0; k < n; k++) { launch_mul_mat(*W[k], act_, B, y[k], ld, r[k], s); batch_path_.mul_mat++; }
+        for (int k = 0; k < n; k++) { launch_mul_mat(*W[k], act_, B, y[k], ld, r[k], tune_, s); batch_path_.mul_mat++; }
     };
     // may the rows of this set be prepared inside its launch?  (same conditions mm() takes the multi-row kernel under)
     auto rows_pro = [&](std::initializer_list<const QWeight *> Ws, bool plain = false) {
@@ -1144,9 +1143,9 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
             // the set
             if (!pro && ri_ready_ && B >= 3 && ri_of(&L.wq) && ri_of(&L.wk) && ri_of(&L.wv) && (L.wq.rows + L.wk.rows + L.wv.rows) / 64 >= 128) {
                 const RiPlanes *r1[2] = {ri_of(&L.wq), ri_of(&L.wk)}, *r2[1] = {ri_of(&L.wv)};
-                if (launch_matvec_ri_mixed(W1, r1, y1, 2, W2, r2, y2, 1, act_, B, E, s)) { batch_path_.ri_mix++; return true; }
+                if (launch_matvec_ri_mixed(W1, r1, y1, 2, W2, r2, y2, 1, act_, B, E, tune_, s)) { batch_path_.ri_mix++; return true; }
             }
-            const bool ok = launch_matvec_rows_mixed(W1, y1, 2, W2, y2, 1, act_, B, E, s, pro ? x_ : nullptr, pro ? L.attn_norm : nullptr, E);
+            const bool ok = launch_matvec_rows_mixed(W1, y1, 2, W2, y2, 1, act_, B, E, tune_, s, pro ? x_ : nullptr, pro ? L.attn_norm : nullptr, E);
             if (ok) batch_path_.dot4_mix++;
             return ok;
         };
@@ -2714,14 +2713,14 @@ int Engine::decode_lookup_sampled(const int *corpus, int n_corpus, int max_token
 // rows do not fit LDS), one launch of the single-conversation kernels per segment, with its rows, its cache and its position.
 void Engine::attn_segments(const SegChunk &sg, __half *kc, __half *vc, bool want_h, bool *att_in_xh, hipStream_t s) {
     const int E = (int)llm_.n_embd, H = (int)llm_.n_head, hd = E / H;
-    if (attn_prefill_ && launch_attn_prefill_seg(q_, kc, vc, sg.att, H, hd, tabs_, att_, s, want_h ? act_.xh : nullptr, att_in_xh)) return;
+    if (attn_prefill_ && launch_attn_prefill_seg(q_, kc, vc, sg.att, H, hd, tabs_, att_, tune_, s, want_h ? act_.xh : nullptr, att_in_xh)) return;
     *att_in_xh = false;
     const size_t seq_stride = layers_.size() * (size_t)n_ctx_ * E;
     for (int i = 0; i < sg.n_seg; i++) {
         const int *g = sg.h_segs + 4 * i;
         const size_t off = (size_t)g[1] * E, cs = (size_t)g[0] * seq_stride;
         const int *np = sg.att.segs + 4 * i + 3;                            // the segment's first position, in device memory
-        if (!(attn_prefill_ && launch_attn_prefill(q_ + off, kc + cs, vc + cs, g[2], H, hd, np, g[3] + g[2], tabs_, att_ + off, s)))
+        if (!(attn_prefill_ && launch_attn_prefill(q_ + off, kc + cs, vc + cs, g[2], H, hd, np, g[3] + g[2], tabs_, att_ + off, tune_, s)))
             launch_attn_llm(q_ + off, k_ + off, v_ + off, kc + cs, vc + cs, g[2], H, hd, np, n_ctx_, cos_, sin_, tabs_, att_ + off, false, s);
     }
 }
@@ -2857,7 +2856,7 @@ void Engine::score_rows(const ScoreReq &rq, hipStream_t s) {
         if (parity_) {
             launch_rms_quant(xr, norm_, rows, E, act_, act_mask_for(output_.type), s, true);
             const QWeight *Wo[1] = {&output_}; float *Yo[1] = {score_buf_};
-            if (!(rows >= 5 && launch_mmq2_set(Wo, Yo, nullptr, 1, act_, rows, V, s, nullptr, 1))) launch_mul_mat_ref(output_, act_, rows, score_buf_, V, nullptr, s);
+            if (!(rows >= 5 && launch_mmq2_set(Wo, Yo, nullptr, 1, act_, rows, V, tune_, s, nullptr, 1))) launch_mul_mat_ref(output_, act_, rows, score_buf_, V, nullptr, tune_, s);
         } else {
             const Prep p_rows{1, xr, norm_};
             mul_mat(output_, rows, score_buf_, V, nullptr, s, &p_rows, false, "score");
@@ -3089,7 +3088,7 @@ int Engine::encode_images(const float *const *chw, int B, float *const *out) {
     HIP_CHECK(hipEventRecord(ea, s));
     // patch embedding: conv 14x14/14 as an f16 GEMM over im2col'd patches (ggml_conv_2d, minigpt4.cpp:1059) + bias
     launch_im2col(vi_img_, vi_patches_, 592, s, B);
-    launch_gemm_f16(vi_patches_, 592, v_patch_w_, 592, B * 256, D, 592, v_patch_b_, nullptr, false, tabs_, vi_pe_, nullptr, D, s);
+    launch_gemm_f16(vi_patches_, 592, v_patch_w_, 592, B * 256, D, 592, v_patch_b_, nullptr, false, tabs_, vi_pe_, nullptr, D, tune_, s);
     launch_assemble_embeddings(v_cls_, vi_pe_, v_pos_, D, vi_x_, s, B);
     const float scale = 1.0f / sqrtf(88.0f);
     // ViT blocks.  attn.proj and mlp.fc2 (N = D: fewer 64x64 tiles than CUs, and fc2 has the longest K) run split-K; their deterministic reduce
@@ -3103,25 +3102,25 @@ int Engine::encode_images(const float *const *chw, int B, float *const *out) {
         const float *nw = last ? v_lnv_w_ : vblocks_[ib + 1].n1w, *nb = last ? v_lnv_b_ : vblocks_[ib + 1].n1b;
         __half *nout = last ? vi_img_h_ : vi_ln_h_;
         if (qkv_head_major_) {   // q | k | v stored [3][head][R][88]: every head's rows contiguous for the attention kernel (round 6; MINIGPT4_QKV_HEAD_MAJOR=0: rows of 3 x D, A/B, bit-identical)
-            launch_gemm_f16_head_major(vi_ln_h_, D, b.qkv_w, D, R, 3 * D, D, b.qkv_b, tabs_, vi_qkv_, D, 88, s);
-            launch_attn_f32(vi_qkv_, 88, vi_qkv_ + (size_t)D * R, vi_qkv_ + (size_t)2 * D * R, 88, 257, 257, v_heads_, 88, scale, 0.0f, tabs_vis_, nullptr, vi_att_h_, D, s, B, R * 88, R * 88);
+            launch_gemm_f16_head_major(vi_ln_h_, D, b.qkv_w, D, R, 3 * D, D, b.qkv_b, tabs_, vi_qkv_, D, 88, tune_, s);
+            launch_attn_f32(vi_qkv_, 88, vi_qkv_ + (size_t)D * R, vi_qkv_ + (size_t)2 * D * R, 88, 257, 257, v_heads_, 88, scale, 0.0f, tabs_vis_, nullptr, vi_att_h_, D, tune_, s, B, R * 88, R * 88);
         } else {
-        launch_gemm_f16(vi_ln_h_, D, b.qkv_w, D, R, 3 * D, D, b.qkv_b, nullptr, false, tabs_, vi_qkv_, nullptr, 3 * D, s);
-        launch_attn_f32(vi_qkv_, 3 * D, vi_qkv_ + D, vi_qkv_ + 2 * D, 3 * D, 257, 257, v_heads_, 88, scale, 0.0f, tabs_vis_, nullptr, vi_att_h_, D, s, B);
+        launch_gemm_f16(vi_ln_h_, D, b.qkv_w, D, R, 3 * D, D, b.qkv_b, nullptr, false, tabs_, vi_qkv_, nullptr, 3 * D, tune_, s);
+        launch_attn_f32(vi_qkv_, 3 * D, vi_qkv_ + D, vi_qkv_ + 2 * D, 3 * D, 257, 257, v_heads_, 88, scale, 0.0f, tabs_vis_, nullptr, vi_att_h_, D, tune_, s, B);
         }
         if (sp > 1) {
-            launch_gemm_f16_splitk(vi_att_h_, D, b.proj_w, D, R, D, D, sp, vi_slab_, slab, D, s);
+            launch_gemm_f16_splitk(vi_att_h_, D, b.proj_w, D, R, D, D, sp, vi_slab_, slab, D, tune_, s);
             launch_splitk_reduce_ln(vi_slab_, sp, slab, b.proj_b, vi_x_, R, D, vi_x_, b.n2w, b.n2b, nullptr, vi_ln_h_, s);
         } else {
-            launch_gemm_f16(vi_att_h_, D, b.proj_w, D, R, D, D, b.proj_b, vi_x_, false, tabs_, vi_x_, nullptr, D, s);
+            launch_gemm_f16(vi_att_h_, D, b.proj_w, D, R, D, D, b.proj_b, vi_x_, false, tabs_, vi_x_, nullptr, D, tune_, s);
             launch_layernorm(vi_x_, b.n2w, b.n2b, R, D, nullptr, vi_ln_h_, s);
         }
-        launch_gemm_f16(vi_ln_h_, D, b.fc1_w, D, R, M, D, b.fc1_b, nullptr, true, tabs_vis_, nullptr, vi_mlp_h_, M, s);
+        launch_gemm_f16(vi_ln_h_, D, b.fc1_w, D, R, M, D, b.fc1_b, nullptr, true, tabs_vis_, nullptr, vi_mlp_h_, M, tune_, s);
         if (sf > 1) {
-            launch_gemm_f16_splitk(vi_mlp_h_, M, b.fc2_w, M, R, D, M, sf, vi_slab_, slab, D, s);
+            launch_gemm_f16_splitk(vi_mlp_h_, M, b.fc2_w, M, R, D, M, sf, vi_slab_, slab, D, tune_, s);
             launch_splitk_reduce_ln(vi_slab_, sf, slab, b.fc2_b, vi_x_, R, D, vi_x_, nw, nb, nullptr, nout, s);
         } else {
-            launch_gemm_f16(vi_mlp_h_, M, b.fc2_w, M, R, D, M, b.fc2_b, vi_x_, false, tabs_, vi_x_, nullptr, D, s);
+            launch_gemm_f16(vi_mlp_h_, M, b.fc2_w, M, R, D, M, b.fc2_b, vi_x_, false, tabs_, vi_x_, nullptr, D, tune_, s);
             launch_layernorm(vi_x_, nw, nb, R, D, nullptr, nout, s);
         }
     }
@@ -3129,7 +3128,7 @@ int Engine::encode_images(const float *const *chw, int B, float *const *out) {
     // Q-Former (masks are all-zero).  Its GEMMs have 32 rows per image: the skinny-M kernel (MINIGPT4_QF_SKINNY=0: the
     // 64x64-tile kernel, A/B)
     auto qgemm = [&](const __half *A, int lda, const __half *W, int ldw, int Mr, int N, int K, const float *bias, const float *residual, bool gelu, float *o, __half *oh, int ldo) {
-        if (!(qf_skinny_ && launch_gemm_f16_skinny(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, s))) launch_gemm_f16(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, s);
+        if (!(qf_skinny_ && launch_gemm_f16_skinny(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, s))) launch_gemm_f16(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, tune_, s);
     };
     // a 768-wide dense / output layer + residual + the LayerNorm behind it (NNSelfAttention's output block, NNBertEncoderLayer's query FFN output: minigpt4.cpp:1365-1400,
     // 1430-1461).  Round 6: K split over 2 (K = 768) or 4 (K = 3072) workgroups per tile with the LayerNorm in the slab reduce (qf_dense_ln below).
@@ -3141,7 +3140,7 @@ int Engine::encode_images(const float *const *chw, int B, float *const *out) {
     // 1536)
     const bool hoist = kv_hoist_ && v_ncross_ > 0 && v_kv_all_w_;
     const int ldkv = hoist ? v_ncross_ * 2 * H : 2 * H;
-    if (hoist) launch_gemm_f16(vi_img_h_, D, v_kv_all_w_, D, R, v_ncross_ * 2 * H, D, v_kv_all_b_, nullptr, false, tabs_, vi_kv_, nullptr, ldkv, s);
+    if (hoist) launch_gemm_f16(vi_img_h_, D, v_kv_all_w_, D, R, v_ncross_ * 2 * H, D, v_kv_all_b_, nullptr, false, tabs_, vi_kv_, nullptr, ldkv, tune_, s);
     const bool folded = qf_fold_ && qf_folded_;                            // layer 0's image-independent head was evaluated at load time (fold_qformer_constants)
     if (!folded) launch_layernorm(vi_qtok_rep_, v_qeln_w_, v_qeln_b_, RQ, H, vi_hs_, vi_hs_h_, s);
     for (size_t il = 0; il < qlayers_.size(); il++) {
@@ -3150,7 +3149,7 @@ int Engine::encode_images(const float *const *chw, int B, float *const *out) {
         const float *a1 = pre ? vi_c_a1_ : vi_a1_; const __half *a1_h = pre ? vi_c_a1_h_ : vi_a1_h_;
         if (!pre) {
             qgemm(vi_hs_h_, H, L.self.q_w, H, RQ, 3 * H, H, L.self.q_b, nullptr, false, vi_qq_, nullptr, 3 * H);
-            launch_attn_f32(vi_qq_, 3 * H, vi_qq_ + H, vi_qq_ + 2 * H, 3 * H, NQ, NQ, 12, 64, 0.0f, 8.0f, tabs_vis_, nullptr, vi_ctx_h_, H, s, B);
+            launch_attn_f32(vi_qq_, 3 * H, vi_qq_ + H, vi_qq_ + 2 * H, 3 * H, NQ, NQ, 12, 64, 0.0f, 8.0f, tabs_vis_, nullptr, vi_ctx_h_, H, tune_, s, B);
             dense_ln(vi_ctx_h_, H, L.self.dense_w, H, L.self.dense_b, vi_hs_, L.self.ln_w, L.self.ln_b, vi_a1_, vi_a1_h_);
         }
         const float *ao = a1; const __half *ao_h = a1_h;
@@ -3158,8 +3157,8 @@ int Engine::encode_images(const float *const *chw, int B, float *const *out) {
             const float *cq = pre ? vi_c_qq_ : vi_qq_;
             if (!pre) qgemm(vi_a1_h_, H, L.cross.q_w, H, RQ, H, H, L.cross.q_b, nullptr, false, vi_qq_, nullptr, H);
             const float *kv = hoist ? vi_kv_ + (size_t)L.cross_idx * 2 * H : vi_kv_;
-            if (!hoist) launch_gemm_f16(vi_img_h_, D, L.cross.kv_w, D, R, 2 * H, D, L.cross.kv_b, nullptr, false, tabs_, vi_kv_, nullptr, 2 * H, s);
-            launch_attn_f32(cq, H, kv, kv + H, ldkv, NQ, 257, 12, 64, 0.0f, 8.0f, tabs_vis_, nullptr, vi_ctx_h_, H, s, B);
+            if (!hoist) launch_gemm_f16(vi_img_h_, D, L.cross.kv_w, D, R, 2 * H, D, L.cross.kv_b, nullptr, false, tabs_, vi_kv_, nullptr, 2 * H, tune_, s);
+            launch_attn_f32(cq, H, kv, kv + H, ldkv, NQ, 257, 12, 64, 0.0f, 8.0f, tabs_vis_, nullptr, vi_ctx_h_, H, tune_, s, B);
             dense_ln(vi_ctx_h_, H, L.cross.dense_w, H, L.cross.dense_b, a1, L.cross.ln_w, L.cross.ln_b, vi_a2_, vi_a2_h_);
             ao = vi_a2_; ao_h = vi_a2_h_;
         }
@@ -3187,7 +3186,7 @@ void Engine::qf_dense_ln(const __half *A, int lda, const __half *W, int K, const
         launch_splitk_reduce_ln(vi_slab_, slices, (size_t)rows * H, bias, residual, rows, H, nullptr, ln_w, ln_b, out, out_h, s);
         return;
     }
-    if (!(qf_skinny_ && launch_gemm_f16_skinny(A, lda, W, K, rows, H, K, bias, residual, false, tabs_, vi_d_, nullptr, H, s))) launch_gemm_f16(A, lda, W, K, rows, H, K, bias, residual, false, tabs_, vi_d_, nullptr, H, s);
+    if (!(qf_skinny_ && launch_gemm_f16_skinny(A, lda, W, K, rows, H, K, bias, residual, false, tabs_, vi_d_, nullptr, H, s))) launch_gemm_f16(A, lda, W, K, rows, H, K, bias, residual, false, tabs_, vi_d_, nullptr, H, tune_, s);
     launch_layernorm(vi_d_, ln_w, ln_b, rows, H, out, out_h, s);
 }
 
@@ -3203,11 +3202,11 @@ void Engine::fold_qformer_constants() {
     const int H = 768, NQ = v_nq_;
     const QLayer &L = qlayers_[0];
     auto qgemm = [&](const __half *A, int lda, const __half *W, int ldw, int Mr, int N, int K, const float *bias, const float *residual, bool gelu, float *o, __half *oh, int ldo) {
-        if (!(qf_skinny_ && launch_gemm_f16_skinny(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, s))) launch_gemm_f16(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, s);
+        if (!(qf_skinny_ && launch_gemm_f16_skinny(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, s))) launch_gemm_f16(A, lda, W, ldw, Mr, N, K, bias, residual, gelu, tabs_vis_, o, oh, ldo, tune_, s);
     };
     launch_layernorm(vi_qtok_rep_, v_qeln_w_, v_qeln_b_, NQ, H, vi_hs_, vi_hs_h_, s);
     qgemm(vi_hs_h_, H, L.self.q_w, H, NQ, 3 * H, H, L.self.q_b, nullptr, false, vi_qq_, nullptr, 3 * H);
-    launch_attn_f32(vi_qq_, 3 * H, vi_qq_ + H, vi_qq_ + 2 * H, 3 * H, NQ, NQ, 12, 64, 0.0f, 8.0f, tabs_vis_, nullptr, vi_ctx_h_, H, s, 1);
+    launch_attn_f32(vi_qq_, 3 * H, vi_qq_ + H, vi_qq_ + 2 * H, 3 * H, NQ, NQ, 12, 64, 0.0f, 8.0f, tabs_vis_, nullptr, vi_ctx_h_, H, tune_, s, 1);
     qf_dense_ln(vi_ctx_h_, H, L.self.dense_w, H, L.self.dense_b, vi_hs_, L.self.ln_w, L.self.ln_b, vi_c_a1_, vi_c_a1_h_, NQ, s);   // the launches encode_images issues
     if (L.has_cross) qgemm(vi_c_a1_h_, H, L.cross.q_w, H, NQ, H, H, L.cross.q_b, nullptr, false, vi_c_qq_, nullptr, H);
     HIP_CHECK(hipStreamSynchronize(s));

@@ -81,6 +81,7 @@ public:
     int n_embd() const { return (int)llm_.n_embd; }
     int n_past() const { return conv_[(size_t)cur_].n_past; }
     int n_ctx() const { return n_ctx_; }
+    const LaunchTuning &launch_tuning() const { return tune_; }
     const float *logits_host();                       // syncs, copies the last logits to pinned memory
     const Tokenizer &tokenizer() const { return tok_; }
     size_t weight_bytes_per_token() const { return wbytes_token_; }
@@ -547,7 +548,8 @@ private:
     // nothing to reorder); profiles/r13_matvec_prefetch_depth.log.  MINIGPT4_MV_IB = 0 / 1 forces it off / on at every site
     enum MvSite { MV_QKV = 0, MV_QKV_MIXED, MV_WO, MV_W1W3, MV_OUTPUT, MV_SITES };
     bool mv_issue_bar_[MV_SITES] = {true, true, false, true, true};
-    int batch_rows_max_ = 4; int batch_fuse_ = -1; int n_cus_ = 256;
+    int batch_rows_max_ = 4; int batch_fuse_ = -1;
+    LaunchTuning tune_;   // CU count + launch switches of THIS context (launch_tuning_from_env in init); passed to every launcher that chooses a grid or a kernel form
     // round 5: B = 2..4 rows per weight pass on the int8 matrix cores over a row-interleaved second image of the k-quant matrices (ri_kernels.hip);
     // built by set_conversations(n > 1) -- a context with one conversation never pays the memory.  MINIGPT4_RI=0: the v_dot4 multi-row mat-vec of
     // rounds 2-4 (A/B)

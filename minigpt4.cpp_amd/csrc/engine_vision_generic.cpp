@@ -91,7 +91,7 @@ void Engine::alloc_vision_generic() {
 // y = [residual +] gelu?(bias + W . convert(x)) for `rows` fp32 rows (NNLinear::forward, minigpt4.cpp:1020-1030, with the weight type's mul_mat arithmetic)
 void Engine::glinear(const GLin &L, const float *x, int rows, const float *bias, bool gelu, const float *residual, float *out, hipStream_t s) {
     launch_rms_quant(x, nullptr, rows, L.w.cols, vact_, act_mask_for(L.w.type), s);
-    launch_mul_mat(L.w, vact_, rows, vg_tmp_, L.w.rows, nullptr, s);
+    launch_mul_mat(L.w, vact_, rows, vg_tmp_, L.w.rows, nullptr, tune_, s);
     launch_lin_epilogue(vg_tmp_, bias, residual, gelu, tabs_, rows, L.w.rows, out, nullptr, s);
 }
 
@@ -105,14 +105,14 @@ int Engine::encode_images_generic(const float *const *chw, int B, float *const *
     HIP_CHECK(hipEventRecord(ea, s));
     // patch embedding: always the F16 conv kernel (ggml_conv_2d computes in fp16, minigpt4.cpp:1059)
     launch_im2col(vi_img_, vi_patches_, 592, s, B);
-    launch_gemm_f16(vi_patches_, 592, v_patch_w_, 592, B * 256, D, 592, v_patch_b_, nullptr, false, tabs_, vi_pe_, nullptr, D, s);
+    launch_gemm_f16(vi_patches_, 592, v_patch_w_, 592, B * 256, D, 592, v_patch_b_, nullptr, false, tabs_, vi_pe_, nullptr, D, tune_, s);
     launch_assemble_embeddings(v_cls_, vi_pe_, v_pos_, D, vi_x_, s, B);
     const float scale = 1.0f / sqrtf(88.0f);
     for (size_t ib = 0; ib < vblocks_.size(); ib++) {
         const VBlock &b = vblocks_[ib]; const GBlock &g = gblocks_[ib];
         launch_layernorm(vi_x_, b.n1w, b.n1b, R, D, vg_ln_, nullptr, s);
         glinear(g.qkv, vg_ln_, R, b.qkv_b, false, nullptr, vi_qkv_, s);
-        launch_attn_f32(vi_qkv_, 3 * D, vi_qkv_ + D, vi_qkv_ + 2 * D, 3 * D, 257, 257, v_heads_, 88, scale, 0.0f, tabs_, vg_att_, nullptr, D, s, B);
+        launch_attn_f32(vi_qkv_, 3 * D, vi_qkv_ + D, vi_qkv_ + 2 * D, 3 * D, 257, 257, v_heads_, 88, scale, 0.0f, tabs_, vg_att_, nullptr, D, tune_, s, B);
         glinear(g.proj, vg_att_, R, b.proj_b, false, vi_x_, vi_x_, s);
         launch_layernorm(vi_x_, b.n2w, b.n2b, R, D, vg_ln_, nullptr, s);
         glinear(g.fc1, vg_ln_, R, b.fc1_b, true, nullptr, vg_mlp_, s);
@@ -128,12 +128,12 @@ int Engine::encode_images_generic(const float *const *chw, int B, float *const *
             launch_rms_quant(vi_hs_, nullptr, RQ, H, vact_, act_mask_for(G.self.q.w.type) | act_mask_for(G.self.k.w.type) | act_mask_for(G.self.v.w.type), s);
             const GLin *qkv[3] = {&G.self.q, &G.self.k, &G.self.v};
             for (int j = 0; j < 3; j++) {
-                launch_mul_mat(qkv[j]->w, vact_, RQ, vg_tmp_, H, nullptr, s);
+                launch_mul_mat(qkv[j]->w, vact_, RQ, vg_tmp_, H, nullptr, tune_, s);
                 launch_lin_epilogue(vg_tmp_, L.self.q_b + (size_t)j * H, nullptr, false, tabs_, RQ, H, vg_tmp_, nullptr, s);
                 HIP_CHECK(hipMemcpy2DAsync(vi_qq_ + (size_t)j * H, (size_t)3 * H * 4, vg_tmp_, (size_t)H * 4, (size_t)H * 4, (size_t)RQ, hipMemcpyDeviceToDevice, s));
             }
         }
-        launch_attn_f32(vi_qq_, 3 * H, vi_qq_ + H, vi_qq_ + 2 * H, 3 * H, NQ, NQ, 12, 64, 0.0f, 8.0f, tabs_, vg_ctx_, nullptr, H, s, B);
+        launch_attn_f32(vi_qq_, 3 * H, vi_qq_ + H, vi_qq_ + 2 * H, 3 * H, NQ, NQ, 12, 64, 0.0f, 8.0f, tabs_, vg_ctx_, nullptr, H, tune_, s, B);
         glinear(G.self.dense, vg_ctx_, RQ, L.self.dense_b, false, vi_hs_, vi_d_, s);
         launch_layernorm(vi_d_, L.self.ln_w, L.self.ln_b, RQ, H, vi_a1_, nullptr, s);
         const float *ao = vi_a1_;
@@ -142,11 +142,11 @@ int Engine::encode_images_generic(const float *const *chw, int B, float *const *
             launch_rms_quant(vg_img_, nullptr, R, D, vact_, act_mask_for(G.cross.k.w.type) | act_mask_for(G.cross.v.w.type), s);
             const GLin *kv[2] = {&G.cross.k, &G.cross.v};
             for (int j = 0; j < 2; j++) {
-                launch_mul_mat(kv[j]->w, vact_, R, vg_tmp_, H, nullptr, s);
+                launch_mul_mat(kv[j]->w, vact_, R, vg_tmp_, H, nullptr, tune_, s);
                 launch_lin_epilogue(vg_tmp_, L.cross.kv_b + (size_t)j * H, nullptr, false, tabs_, R, H, vg_tmp_, nullptr, s);
                 HIP_CHECK(hipMemcpy2DAsync(vi_kv_ + (size_t)j * H, (size_t)2 * H * 4, vg_tmp_, (size_t)H * 4, (size_t)H * 4, (size_t)R, hipMemcpyDeviceToDevice, s));
             }
-            launch_attn_f32(vi_qq_, H, vi_kv_, vi_kv_ + H, 2 * H, NQ, 257, 12, 64, 0.0f, 8.0f, tabs_, vg_ctx_, nullptr, H, s, B);
+            launch_attn_f32(vi_qq_, H, vi_kv_, vi_kv_ + H, 2 * H, NQ, 257, 12, 64, 0.0f, 8.0f, tabs_, vg_ctx_, nullptr, H, tune_, s, B);
             glinear(G.cross.dense, vg_ctx_, RQ, L.cross.dense_b, false, vi_a1_, vi_d_, s);
             launch_layernorm(vi_d_, L.cross.ln_w, L.cross.ln_b, RQ, H, vi_a2_, nullptr, s);
             ao = vi_a2_;
@@ -201,7 +201,7 @@ int Engine::encode_images_ref(const float *const *chw, int B, float *const *out)
     const int R = B * 257, RQ = B * NQ;
     auto rlinear = [&](const GLin &L, const float *x, int rows, const float *bias, bool gelu, const float *residual, float *o) {
         launch_rms_quant(x, nullptr, rows, L.w.cols, vact_, act_mask_for(L.w.type), s);
-        launch_mul_mat_ref(L.w, vact_, rows, vg_tmp_, L.w.rows, nullptr, s);
+        launch_mul_mat_ref(L.w, vact_, rows, vg_tmp_, L.w.rows, nullptr, tune_, s);
         launch_lin_epilogue(vg_tmp_, bias, residual, gelu, tabs_, rows, L.w.rows, o, nullptr, s);
     };
     hipEvent_t ea, eb; HIP_CHECK(hipEventCreate(&ea)); HIP_CHECK(hipEventCreate(&eb));
@@ -213,7 +213,7 @@ int Engine::encode_images_ref(const float *const *chw, int B, float *const *out)
     {
         QWeight Wp; Wp.type = GT_F16; Wp.rows = D; Wp.cols = 592; Wp.qs = reinterpret_cast<const uint8_t *>(v_patch_w_); Wp.bytes = (size_t)D * 592 * 2;
         ActQ Ap{}; Ap.xh = vi_patches_;
-        launch_mul_mat_ref(Wp, Ap, B * 256, vi_pe_, D, nullptr, s);
+        launch_mul_mat_ref(Wp, Ap, B * 256, vi_pe_, D, nullptr, tune_, s);
         launch_lin_epilogue(vi_pe_, v_patch_b_, nullptr, false, tabs_, B * 256, D, vi_pe_, nullptr, s);
     }
     launch_assemble_embeddings(v_cls_, vi_pe_, v_pos_, D, vi_x_, s, B);

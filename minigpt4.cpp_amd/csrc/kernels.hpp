@@ -16,6 +16,42 @@ struct Tables {               // fp16 lookup tables, 65536 entries each, indexed
                                // the part of the table k_attn_vit keeps in LDS (softmax arguments are <= 0)
 };
 
+// ---- launch tuning -----------------------------------------------------------------------------------------------------
+// Everything that decides a grid size, a kernel form or a K split besides the launch's own arguments.  A plain value: every context owns one (Engine::tune_, filled once
+// at load), the test library's single-kernel hooks own another, and every launcher that reads a field takes it in front of its stream -- no process-global tuning state, so
+// two contexts, or a context and a test hook, never change each other's launches.  What stays process-wide is measurement and logging only: the kernel-name tracing and
+// launch probes, the timeline stamps of the diagnostic builds, the log verbosity, the thread-local last error, the launchers' function-local "attribute already set"
+// flags and the CU count of probe_kernels.hip.
+struct LaunchTuning {
+    int cus = 256;               // compute units of the context's device (device properties)
+    int mv_waves_per_cu = 0;     // decode mat-vec, prologue-free launches: waves per CU (0 = choose: 8; the mat-vec micro-benchmark sweeps it)
+    int mmq = 2;                 // prompt rows (N >= 5): 2 = the LDS-staged int8-MFMA kernels of mmq2_kernels.hip, below 2 = v_dot4 tiles only (tests / A-B)
+    int mmqh = 0;                // 1: Q4_K / Q5_K prompt rows on the fp16 matrix cores with the sub-block scales folded into the weight operands (k_mmqh_q45k; measured
+                                 // slower, profiles/r05_prefill_fp16_scaled_operands.md; MINIGPT4_MMQH)
+    int mmq_ks = 0;              // forced K split of launch_mmq2_set / launch_mmq3_set (0 = the launcher's choice)
+    int mmq3_waves = 8;          // launch_mmq3_set: 8 = 128-row workgroups, one per CU; 4 = 64-row workgroups, two per CU (slower)
+    int attn_prefill_w8 = 1;     // fp16 prompt attention: the 8-wave loader / MFMA form where its size rule selects it (MINIGPT4_ATTN_PREFILL_W8)
+    int attn_prefill_f16 = 1;    // 1: prompt attention on the fp16 matrix cores, 0: the exact-f32 MFMA kernel
+    int attn_prefill_form = 0;   // force one fp16 prompt attention form (1 = h8, 2 = h QS 2, 3 = h QS 1; 0 = the size rule)
+    int gemm_arm = 0;            // force one tile shape for every small-M F16 GEMM (launch_gemm_f16_arm's arms); 0 = choose, -2 = the 64x64 launch always, -3 = round 2's
+                                 // kernels everywhere (64x64 tiles, 128x128 large-M kernel)
+    int gemm_sk_arm = 0;         // the same for the split-K GEMM (launch_gemm_f16_splitk_arm's arms); 0 = choose
+    int f16_ks = 0;              // forced K split of the F16 language model's single-matrix prompt launches (wo, w2; 0 = choose, at most 8; MINIGPT4_F16_KS)
+    int splitk_xcd = 1;          // 1: a split-K GEMM's work list [slice][tile] is dealt to the XCDs in contiguous ranges; 0: slices in grid.z (rounds 3-5; MINIGPT4_SPLITK_XCD)
+    int attn_vit_qt = 0;         // query tiles per workgroup of k_attn_vit (0 = the launcher's choice; MINIGPT4_ATTN_QT)
+    // the one place the fields' ranges are kept: the booleans 0 / 1, the forced counts >= 0, f16_ks <= 8, mmq3_waves 4 or 8, gemm_arm >= 0 or -2 or -3 (else the default)
+    LaunchTuning normalised() const {
+        LaunchTuning t = *this;
+        t.mv_waves_per_cu = mv_waves_per_cu > 0 ? mv_waves_per_cu : 0; t.mmqh = mmqh != 0; t.mmq_ks = mmq_ks > 0 ? mmq_ks : 0; t.mmq3_waves = mmq3_waves == 4 ? 4 : 8;
+        t.attn_prefill_w8 = attn_prefill_w8 != 0; t.attn_prefill_f16 = attn_prefill_f16 != 0; t.attn_prefill_form = attn_prefill_form >= 1 && attn_prefill_form <= 3 ? attn_prefill_form : 0;
+        t.gemm_arm = gemm_arm >= 0 || gemm_arm == -2 || gemm_arm == -3 ? gemm_arm : 0; t.gemm_sk_arm = gemm_sk_arm > 0 ? gemm_sk_arm : 0;
+        t.f16_ks = f16_ks < 0 ? 0 : f16_ks > 8 ? 8 : f16_ks; t.splitk_xcd = splitk_xcd != 0; t.attn_vit_qt = attn_vit_qt > 0 ? attn_vit_qt : 0;
+        return t;
+    }
+};
+// the tuning of a context on a device with `cus` compute units: the defaults + MINIGPT4_ATTN_PREFILL_W8, _MMQH, _ATTN_QT, _SPLITK_XCD, _F16_KS (engine.cpp; uses no device)
+LaunchTuning launch_tuning_from_env(int cus);
+
 // ---- load-time repack: raw ggml blocks (device copy of the file bytes) -> planes of a QWeight -------------------
 // `dst` planes must already point into the arena (see plan_qweight).  raw/dst may not alias.
 size_t plan_qweight(int type, int rows, int cols, QWeight &w, uint8_t *base);  // assigns plane pointers from `base`, returns bytes used
@@ -29,14 +65,12 @@ void launch_rms_quant(const float *x, const float *w, int N, int K, const ActQ &
 void launch_silu_mul_quant(const float *a, const float *b, int N, int K, const ActQ &A, int mask, const Tables &tb, hipStream_t s);
 
 // ---- quantised mat-mul: y[t][r] = W[r] . act[t]  (+ residual[t][r]) ------------------------------------------------
-void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s);
+void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s);
 
 // MINIGPT4_PARITY=1: the same unit traits, the per-block fp32 terms added in the CPU oracle's order (one sequential chain per output) -- bit-identical to oracle/refcpu.c, slow
-void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s);
-bool launch_mul_mat_ref_set(const QWeight *const *W, float *const *y, const float *const *res, int n, const ActQ &A, hipStream_t s);   // one row (decode) x 1..3 same-shape matrices: every unit of a row requested up front; false -> use launch_mul_mat_ref
+void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s);
+bool launch_mul_mat_ref_set(const QWeight *const *W, float *const *y, const float *const *res, int n, const ActQ &A, const LaunchTuning &tune, hipStream_t s);   // one row (decode) x 1..3 same-shape matrices: every unit of a row requested up front; false -> use launch_mul_mat_ref
 bool matvec_prologue_supported(int type, int cols);   // the fused row-preparation variants of the decode mat-vec
-void set_mmq_enabled(int v);
-int mmq_enabled();
 // second-generation prefill kernels (mmq2_kernels.hip): 1..3 same-type, same-shape k-quant matrices against N >= 1 prepared rows (A.bsq required), weights streamed once per
 // chunk of <= 128 tokens, activations staged through LDS, optional K split (partial sums in A.ws) combined in fixed order.  false -> outside the kernels' range, nothing launched.
 bool mmq2_supported(int type, int rows, int cols);
@@ -51,43 +85,34 @@ void launch_rms_quant_slabs(const SlabSrc &src, const float *w, int N, int K, co
 void launch_silu_mul_quant_slabs(const SlabSrc &src, int N, int K, const ActQ &A, int mask, const Tables &tb, hipStream_t s);   // n == 2: silu(a) * b, quantised
 void launch_rope_kv_slabs(const SlabSrc &src, int N, int n_head, int hd, const int *n_past, const float *cos_tab, const float *sin_tab, __half *kcache, __half *vcache, hipStream_t s);   // n == 3
 // defer != nullptr: with a K split the combine launch is skipped and *defer describes the slabs (ks > 1); otherwise *defer is cleared
-bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, SlabSrc *defer = nullptr,
+bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer = nullptr,
                      int force_ks = 0);   // force_ks == 1: no K split = the CPU oracle's fp32 order (parity mode's prompt rows)
-void set_mmq2_cus(int cus);
-void set_mmqh(int v);   // 1: Q4_K / Q5_K prompt rows on the fp16 matrix cores with the sub-block scales folded into the weight operands (k_mmqh_q45k; measured slower, profiles/r05_prefill_fp16_scaled_operands.md); 0 (default): the int8 kernels
-int mmqh_enabled();
 // (test library only: measured in round 4, not adopted) prompt mat-mul on load-time digit planes (mmq3_kernels.hip): Q4_K / Q5_K, sub-block scale x quant stored as 128 hi + lo (1.5 B per weight) in MFMA-fragment order
 bool mmq3_supported(int type, int rows, int cols);
 size_t mmq3_plane_bytes(int rows, int cols, size_t *hi_off = nullptr);
 void launch_mmq3_build(const QWeight &W, uint8_t *planes, hipStream_t s);
-bool launch_mmq3_set(const QWeight *const *W, const uint8_t *const *planes, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, SlabSrc *defer = nullptr);
+bool launch_mmq3_set(const QWeight *const *W, const uint8_t *const *planes, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer = nullptr);
 int probe_tn_mfma(int rows, int cols, int TN, int iters, int n_sets, int check, int cus, float *us_per_launch, float *rel_diff);   // (test library with `make test-extras` only) tn_mfma_probe.hip
-void set_mmq3_waves(int nw);                          // 8 (default): 128-row workgroups, one per CU; 4: 64-row workgroups, two per CU (slower)
-void set_mmq3_tuning(int cus, int ks);                // CU count (<= 0: leave), forced K split (0 = the launcher's choice, < 0: leave)
-void set_mmq2_tuning(int tt, int fill_pct, int ks);   // experiment knobs, 0 = the launcher's choice, < 0 = leave as it is (read from the environment once, by Engine::init)
-void set_gemm_splitk_xcd(int on);   // 1 (default): a split-K GEMM's work list [slice][tile] is dealt to the XCDs in contiguous ranges; 0: slices in grid.z (rounds 3-5, A/B)
-void set_gemm_tuning(int big_min_m, int f16_ks, int arm = -1, int sk_arm = -1);      // smallest M of the 128x128 GEMM (< 0: leave), forced K split of the F16 set launches (0 = choose)
-void set_f16_gemm(int v);                             // F16 language-model weights at >= 16 rows on the MFMA GEMM (default 1)
 void launch_slab_reduce(const float *slabs, int n_slabs, long long slab_stride, const float *residual, float *y, size_t n, hipStream_t s);   // y = (residual +) sum_z slab_z, fixed order
 // F16 weights at prompt sizes: 1..3 equally spaced [N][K] matrices x M fp16 rows in one launch of the 128x128 LDS-DMA GEMM (split K when the tiles do not fill the chip);
 // false -> outside this path, nothing launched
-bool launch_gemm_f16_silu_pair(const __half *A, int lda, const __half *W1, const __half *W3, int M, int N, int K, const Tables &tb, float *out, __half *out_h, int ldo, int cus, hipStream_t s);   // fp16(silu(A.W1^T) * (A.W3^T)) in one launch (F16 w1|w3 at prompt sizes)
+bool launch_gemm_f16_silu_pair(const __half *A, int lda, const __half *W1, const __half *W3, int M, int N, int K, const Tables &tb, float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s);   // fp16(silu(A.W1^T) * (A.W3^T)) in one launch (F16 w1|w3 at prompt sizes)
 bool launch_gemm_f16_set(const __half *A, int lda, const __half *const *W, int n, int M, int N, int K, float *const *y, const float *const *residual, int ldo, float *ws,
-                         size_t ws_floats, int cus, hipStream_t s, SlabSrc *defer = nullptr);
+                         size_t ws_floats, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer = nullptr);
 
 // decode (N = 1) persistent-wave mat-vec over 1..3 same-type, same-shape matrices (wq|wk|wv, w1|w3); false -> caller falls back to launch_mul_mat
 // pro: 0 = activations come from `A` (prepared by launch_rms_quant / launch_silu_mul_quant); 1 = rms_norm(px) * pw, 2 = px, 3 = silu(px) * pw are
 // prepared and quantised inside the kernel prologue (one launch less per use).
 // issue_bar (pro != 0): a data-free barrier between the prologue's row loads and its first weight requests, so that the row loads of all waves of a CU are issued first
 // (built for the k-quants at K <= 6144; elsewhere the plain form runs).  Outputs do not depend on it, bit for bit.
-bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, hipStream_t s, int pro = 0, const float *px = nullptr,
+bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, const LaunchTuning &tune, hipStream_t s, int pro = 0, const float *px = nullptr,
                        const float *pw = nullptr, const Tables *tb = nullptr, int epi = 0, bool issue_bar = false);   // epi 1: y[0][g] = silu(W0[g].x) * (W1[g].x) (n == 2); MATVEC_EPI_REF: the CPU oracle's fp32 order (k-quants; pro 0..2)
 constexpr int MATVEC_EPI_REF = 2;
-int matvec_prologue_waves();   // waves of a prologue launch with at least as many row groups: wave w owns groups w, w + waves, ...
+int matvec_prologue_waves(const LaunchTuning &tune);   // waves of a prologue launch with at least as many row groups: wave w owns groups w, w + waves, ...
 bool matvec_silu_pair_supported(int type, int cols);
 // batched decode: N = 1..4 activation rows (prepared in `A`) against 1..3 same-type, same-shape, equally spaced matrices, weights streamed once;
 // y[m][t * ldy + r] (+ residual[m][t * ldy + r]).  false -> outside the kernel's range, use launch_mul_mat.
-bool launch_matvec_rows(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, const float *px = nullptr,
+bool launch_matvec_rows(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px = nullptr,
                         const float *pw = nullptr, int ldx = 0);   // px != null: rows t of x (stride ldx) are prepared inside the launch (A unused): pw != null rms-normed with pw, pw == null taken as they are; then quantised
 bool matvec_rows_prologue_ok(int type, int K);
 // batched decode on v_mfma_i32_4x4x4_16B_i8 over the row-interleaved image (ri_kernels.hip, round 5): N = 1..4 PREPARED rows (Q8_K image incl. bsk / bsq) against 1..3 same-type,
@@ -99,20 +124,18 @@ void launch_ri_build(const QWeight &w, const RiPlanes &p, hipStream_t s);      /
 // leaves them zero); without it (all null) such sets run one workgroup per group.  Owned by the caller -- one per context (Engine::ri_ws_), passed with every launch: no
 // process-global state, so two contexts decoding on different threads / streams never share slabs or tickets (round-5 advisor).
 struct RiWorkspace { float *slabs = nullptr; size_t slab_floats = 0; unsigned *tickets = nullptr; int n_tickets = 0; };
-bool launch_matvec_ri(const QWeight *const *W, const RiPlanes *const *ri, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s,
-                      const float *px = nullptr, const float *pw = nullptr, int ldx = 0, const RiWorkspace &ws = RiWorkspace{});   // px != null: rows t of px (stride ldx) are rms-normed with pw and quantised inside the launch (A unused)
+bool launch_matvec_ri(const QWeight *const *W, const RiPlanes *const *ri, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune,
+                      hipStream_t s, const float *px = nullptr, const float *pw = nullptr, int ldx = 0, const RiWorkspace &ws = RiWorkspace{});   // px != null: rows t of px (stride ldx) are rms-normed with pw and quantised inside the launch (A unused)
 // a "more bits" layer's set in one launch: na matrices of Q4_K / Q5_K + nb of Q6_K (na + nb <= 3), same shape, prepared rows
 bool launch_matvec_ri_mixed(const QWeight *const *Wa, const RiPlanes *const *ria, float *const *ya, int na, const QWeight *const *Wb, const RiPlanes *const *rib, float *const *yb, int nb,
-                            const ActQ &A, int N, int ldy, hipStream_t s);
-void set_ri_cus(int cus);
-int ri_ksplit(int total_groups, int K, const RiWorkspace &ws);   // workgroups per row group the launch would use with this workspace (1 = no K split)
+                            const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s);
+int ri_ksplit(int total_groups, int K, const RiWorkspace &ws, const LaunchTuning &tune);   // workgroups per row group the launch would use with this workspace (1 = no K split)
 // two k-quant types (Q4_K|Q5_K + Q6_K) with the same K in one launch; pro: 0 or 1 (rms_norm prologue)
-bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, hipStream_t s, int pro = 0,
+bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, const LaunchTuning &tune, hipStream_t s, int pro = 0,
                          const float *px = nullptr, const float *pw = nullptr, int epi = 0, bool issue_bar = false);
 // the same for N = 1..4 rows of the batched step (K <= 6144); px != null: rows rms-normed with pw and quantised inside the launch
-bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, int N, int ldy, hipStream_t s,
+bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s,
                               const float *px = nullptr, const float *pw = nullptr, int ldx = 0);
-void set_matvec_tuning(int waves_per_cu, int fat_threads, int cus);   // 0 = choose per launch
 // measurement: while tracing is on, every launcher of llm_kernels.hip notes the kernel symbol it launched (as rocprofv3 prints it, without the argument list)
 void kernel_name_tracing(bool on);
 const char *last_kernel_name();          // "" when nothing was launched since the last reset
@@ -206,8 +229,8 @@ struct AttnSegs { const int *segs = nullptr; const int *tiles[2] = {nullptr, nul
 int attn_seg_tiles(const int *segs, int n_seg, int qt, int *out);   // host: out[2 k] = segment, out[2 k + 1] = first query, longest first; returns the count
 // one launch of the SEG form of k_attn_prefill_h8 / k_attn_prefill_h (same choice rule as launch_attn_prefill); each row bit-identical to its segment's own launch.
 // false -> declined (the exact-f32 kernel is selected, or the score rows do not fit LDS): the caller runs per-segment launches.  out_h as launch_attn_prefill
-bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, hipStream_t s,
-                             __half *out_h = nullptr, bool *wrote_h = nullptr);
+bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, const LaunchTuning &tune,
+                             hipStream_t s, __half *out_h = nullptr, bool *wrote_h = nullptr);
 // row r: logits row r belongs to conversation fin[2 r]: slot_logits / argmax / feed as launch_batch_finish, n_past[slot] = fin[2 r + 1]
 void launch_seg_finish(const float *logits, int n_vocab, int B, const int *fin, int *n_past, int *argmax, int *feed, float *slot_logits, hipStream_t s);
 void launch_gather_rows(const float *src, const int *idx, int n, int E, float *dst, hipStream_t s);   // dst[r] = src[idx[r]], rows of E floats
@@ -268,16 +291,11 @@ bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R,
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)
-bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s, __half *out_h = nullptr, bool *wrote_h = nullptr);
+bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, const LaunchTuning &tune, hipStream_t s, __half *out_h = nullptr, bool *wrote_h = nullptr);
 // MINIGPT4_PARITY=1: scores / softmax / P.V with every fp32 chain in the oracle's order (after launch_rope_kv); t_max >= *n_past + N
 void launch_attn_ref(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s);
 void launch_attn_ref_fused(const float *q, const float *k, const float *v, __half *kcache, __half *vcache, int n_head, int hd, const int *n_past, int t_max, const float *cos_tab, const float *sin_tab,
                            const Tables &tb, float *out, hipStream_t s);   // one query row: RoPE + cache append inside
-void set_attn_prefill_f16(int v);
-int attn_prefill_form();
-int attn_prefill_f16();
-void set_attn_prefill_form(int v);   // test library: force one fp16 prompt attention form (1 = h8, 2 = h QS 2, 3 = h QS 1; 0 = the size rule)
-void set_attn_prefill_w8(int v);    // 8-wave loader / MFMA form of the fp16 prompt attention (MINIGPT4_ATTN_PREFILL_W8)   // 1 (default): prompt attention on the fp16 matrix cores, 0: the exact-f32 MFMA kernel
 bool attn_head_size_supported(int hd);
 void attn_ref_prepare();        // the oracle-order attention kernels' > 64 KiB LDS opt-in on the current device, checked (throws HipError); outside any stream capture
 int attn_ref_max_ctx(int hd);   // the same bound for the oracle-order kernel of parity mode (smaller: it also stages value rows in LDS)
@@ -296,9 +314,9 @@ void launch_delay(int us, hipStream_t s);   // profiling gate: keeps the stream 
 // C[M][N] = A[M][K](f16) . W[N][K](f16)^T + bias ; optional fp16-table GELU ; optional residual add (C = residual + C).
 // Writes fp32 `out` (nullable) and/or fp16 `out_h` (nullable).  K must be a multiple of 16.
 void launch_gemm_f16(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual,
-                     bool gelu, const Tables &tb, float *out, __half *out_h, int ldo, hipStream_t s);
+                     bool gelu, const Tables &tb, float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s);
 // fp32 output stored [N / D][D / hd][M][hd] (the ViT's qkv projection for k_attn_vit's head strides; vision_kernels.hip: struct HeadMajor)
-void launch_gemm_f16_head_major(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const Tables &tb, float *out, int D, int hd, hipStream_t s);
+void launch_gemm_f16_head_major(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const Tables &tb, float *out, int D, int hd, const LaunchTuning &tune, hipStream_t s);
 // out = [residual +] gelu?(bias + y) over [rows][n] contiguous fp32 (y may alias out); writes fp32 (nullable) and / or fp16 (nullable)
 // the same product for FEW rows (the Q-Former's 32 queries per image): N / 16 workgroups, K split across the waves of a workgroup, no LDS staging.  false -> shape outside
 // the kernel's range (N % 16, K % 32), nothing launched
@@ -313,18 +331,17 @@ void launch_attn_vref(const float *q, int ldq, const float *k, const float *v, i
                       float *out, int ldo, hipStream_t s, int batch = 1);
 // split-K GEMM (raw fp32 partial sums into `slices` slabs) + the deterministic reduce fused with bias / residual / the following LayerNorm
 bool launch_gemm_f16_arm(int arm, const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual, bool gelu, const Tables &tb,
-                         float *out, __half *out_h, int ldo, hipStream_t s);   // micro-benchmark arms (other tile shapes of k_gemm_f16)
-bool launch_gemm_f16_splitk_arm(int arm, const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, hipStream_t s);
+                         float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s);   // micro-benchmark arms (other tile shapes of k_gemm_f16)
+bool launch_gemm_f16_splitk_arm(int arm, const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, const LaunchTuning &tune, hipStream_t s);
 int gemm_split_slices(int K, int want);   // slices actually used for a K (whole 128-wide k tiles per slice)
-void launch_gemm_f16_splitk(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, hipStream_t s);
+void launch_gemm_f16_splitk(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, const LaunchTuning &tune, hipStream_t s);
 void launch_splitk_reduce_ln(const float *slabs, int n_slabs, size_t slab_stride, const float *bias, const float *residual, int rows, int n, float *x_out, const float *ln_w,
                              const float *ln_b, float *ln_out, __half *ln_out_h, hipStream_t s);
 // f32 attention: q[nq][ldq], k/v[nk][ldk]; per head h the slice [h*hd, (h+1)*hd).  q_prescale != 0: q *= q_prescale first (ViT);
 // score_div != 0: scores /= score_div (BERT).  Output fp32 (nullable) / fp16 (nullable) [nq][ldo].
 // batch > 1: image z uses rows [z * nq, (z + 1) * nq) of q / out and rows [z * nk, (z + 1) * nk) of k / v.
-void set_attn_vit_qt(int qt);   // query tiles per workgroup of k_attn_vit (0 = the launcher's choice); experiments / A-B
 void launch_attn_f32(const float *q, int ldq, const float *k, const float *v, int ldk, int nq, int nk, int heads, int hd, float q_prescale,
-                     float score_div, const Tables &tb, float *out, __half *out_h, int ldo, hipStream_t s, int batch = 1, int head_stride_q = 0, int head_stride_kv = 0)   /* head strides in floats; 0 = hd (heads side by side in a row) */;
+                     float score_div, const Tables &tb, float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s, int batch = 1, int head_stride_q = 0, int head_stride_kv = 0)   /* head strides in floats; 0 = hd (heads side by side in a row) */;
 // image CHW f32 [3][224][224] -> fp16 patches [256][ldp] (k = c*196 + kh*14 + kw, zero padded to ldp)
 void launch_im2col(const float *image, __half *patches, int ldp, hipStream_t s, int batch = 1);   // batch images back to back -> [batch * 256][ldp]
 // x[0] = cls + pos[0]; x[1+p] = pe[p] + pos[1+p]

@@ -437,23 +437,22 @@ __global__ __launch_bounds__(256) void k_mul_mat_ref_row(const RefSet S, const A
         row += n_waves;
     }
 }
-static int g_ref_cus = 256;
-template <int T> static bool launch_mul_mat_ref_row_t(const RefSet &S, const ActQ &A, hipStream_t s) {
+template <int T> static bool launch_mul_mat_ref_row_t(const RefSet &S, const ActQ &A, const LaunchTuning &tune, hipStream_t s) {
     const int U = S.w[0].cols / Tr<T>::EPU, nu = (U + 63) / 64;
     // persistent waves: ~16 per CU over the whole set, each walking rows wave, wave + n_waves, ...
-    const int blocks = std::max(1, std::min((S.w[0].rows + 3) / 4, g_ref_cus * 4 / S.n));
+    const int blocks = std::max(1, std::min((S.w[0].rows + 3) / 4, tune.cus * 4 / S.n));
     const dim3 grid((unsigned)blocks, (unsigned)S.n);
     note_kernel("k_mul_mat_ref_row<%d, %d>", T, nu);
     return mv_for_units(RefRowUnits{}, nu, [&](auto n) { hipLaunchKernelGGL((k_mul_mat_ref_row<T, decltype(n)::value>), grid, dim3(256), 0, s, S, A); });
 }
 // One activation row against 1..3 equally shaped matrices of one type (parity mode's decode step); false -> shape outside this kernel, use launch_mul_mat_ref per matrix
-bool launch_mul_mat_ref_set(const QWeight *const *W, float *const *y, const float *const *res, int n, const ActQ &A, hipStream_t s) {
+bool launch_mul_mat_ref_set(const QWeight *const *W, float *const *y, const float *const *res, int n, const ActQ &A, const LaunchTuning &tune, hipStream_t s) {
     if (n < 1 || n > 3) return false;
     RefSet S{}; S.n = n;
     for (int i = 0; i < n; i++) { if (W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false; S.w[i] = *W[i]; S.y[i] = y[i]; S.res[i] = res ? res[i] : nullptr; }
     return for_weight_type(W[0]->type, [&](auto t) {   // (Q8_0 / Q2_K / F16 / F32 rows have other unit widths: the generic kernel serves them)
         constexpr int T = decltype(t)::value;
-        if constexpr (tr_is_q32<T>() || tr_is_kquant<T>()) return launch_mul_mat_ref_row_t<T>(S, A, s); else return false;
+        if constexpr (tr_is_q32<T>() || tr_is_kquant<T>()) return launch_mul_mat_ref_row_t<T>(S, A, tune, s); else return false;
     });
 }
 // Prompt rows in parity mode: one wave per WEIGHT row (persistent over rows wave, wave + n_waves, ...), the row's units in registers for all N activation rows -- the
@@ -490,9 +489,9 @@ __global__ __launch_bounds__(256) void k_mul_mat_ref_rows(const QWeight W, const
         }
     }
 }
-template <int T> static bool launch_mul_mat_ref_rows_t(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s) {
+template <int T> static bool launch_mul_mat_ref_rows_t(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s) {
     const int U = W.cols / Tr<T>::EPU, nu = (U + 63) / 64;
-    const dim3 grid((unsigned)std::max(1, std::min((W.rows + 3) / 4, g_ref_cus * 4)));
+    const dim3 grid((unsigned)std::max(1, std::min((W.rows + 3) / 4, tune.cus * 4)));
     note_kernel("k_mul_mat_ref_rows<%d, %d>", T, nu);
     return mv_for_units(RefRowUnits{}, nu, [&](auto n) { hipLaunchKernelGGL((k_mul_mat_ref_rows<T, decltype(n)::value>), grid, dim3(256), 0, s, W, A, N, y, ldy, residual); });
 }
@@ -500,11 +499,11 @@ template <int T> static void launch_mul_mat_ref_t(const QWeight &W, const ActQ &
     note_kernel("k_mul_mat_ref<%d>", T);
     hipLaunchKernelGGL((k_mul_mat_ref<T>), dim3((unsigned)((W.rows + 3) / 4), (unsigned)N), dim3(256), 0, s, W, A, N, y, ldy, residual);
 }
-void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s) {
+void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s) {
     // prompt rows: the weight row stays in registers for all N activation rows (k-quants; the other types and unit counts take the generic kernel)
     if (N > 1 && for_weight_type(W.type, [&](auto t) {
             constexpr int T = decltype(t)::value;
-            if constexpr (tr_is_kquant<T>()) return launch_mul_mat_ref_rows_t<T>(W, A, N, y, ldy, residual, s); else return false; })) return;
+            if constexpr (tr_is_kquant<T>()) return launch_mul_mat_ref_rows_t<T>(W, A, N, y, ldy, residual, tune, s); else return false; })) return;
     if (!for_weight_type(W.type, [&](auto t) { launch_mul_mat_ref_t<decltype(t)::value>(W, A, N, y, ldy, residual, s); return true; }))
         throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
 }
@@ -790,15 +789,12 @@ __global__ __launch_bounds__(PRO == PRO_NONE ? 256 : mv_fat_max_threads<NU>()) v
     if (wave < n_waves1) matvec_run<T1, NU, 1, PRO, EPI, IB>(ms1, A, pa, n_groups1, n_waves1, wave, nthr);
     else matvec_run<T2, NU, 1, PRO, EPI, IB>(ms2, A, pa, n_groups2, n_waves2, wave - n_waves1, nthr);
 }
-static int g_mv_cus = 256;
-static int g_mv_force_waves = 0;    // MINIGPT4_MV_WAVES: waves per CU of the prologue-free launches (0 = choose)
-static int g_mv_force_fat = 0;      // MINIGPT4_FAT_LB: threads of the fat workgroups (0 = choose)
 // Launch geometry (measured on the 13B decode, profiles/r01g_ab_geometry.log): 8 waves per CU everywhere.  More waves lose even where they divide
 // the rows more evenly (5120 rows: 2048 waves = 3 | 2 rows per wave, 2560 waves = 2 each, yet 640-thread workgroups are 6 % slower end to
-// end than 512-thread ones; 1024-thread ones 5 % slower; 5 / 7 waves per CU for the K = 13824 mat-vec 4 % / 1 % slower than 8).
-static int pick_waves_per_cu(int max_wpc) { return std::min(g_mv_force_waves ? g_mv_force_waves : 8, max_wpc); }
-static int pick_fat_threads(int max_threads) { return g_mv_force_fat ? std::max(MV_FAT_MIN, std::min(g_mv_force_fat / 64 * 64, max_threads)) : MV_FAT_MIN; }
-int matvec_prologue_waves() { return g_mv_cus * (pick_fat_threads(MV_FAT_MIN) / 64); }
+// end than 512-thread ones; 1024-thread ones 5 % slower; 5 / 7 waves per CU for the K = 13824 mat-vec 4 % / 1 % slower than 8).  The fat (prologue) workgroups have
+// MV_FAT_MIN threads outside parity mode.
+static int pick_waves_per_cu(const LaunchTuning &tune, int max_wpc) { return std::min(tune.mv_waves_per_cu ? tune.mv_waves_per_cu : 8, max_wpc); }
+int matvec_prologue_waves(const LaunchTuning &tune) { return tune.cus * (MV_FAT_MIN / 64); }
 static size_t mv_prologue_lds(int K) { return 128 + row_image_bytes(K); }   // the per-wave partial sums, then the row
 template <int NU> constexpr int mv_max_wpc() { return NU <= 3 ? 16 : NU == 4 ? 12 : 8; }      // register budget of the two-stage pipeline
 // The issue-barrier forms are built for the k-quants at NU <= 3 (K <= 6144: every prologue launch of the 7B / 13B decode step) outside parity mode; elsewhere the launch runs
@@ -814,20 +810,20 @@ static void launch_v2_pro(bool issue_bar, dim3 grid, dim3 block, size_t lds, hip
     hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI>), grid, block, lds, s, pa.x, pa.w, ms.w0.cols, (int)block.x, n_groups, n_waves, ms, A, pa.tb);
 }
 template <int T, int NU, int R, int EPI>
-static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
+static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, const LaunchTuning &tune, hipStream_t s) {
     const int total_rows = ms.n * ms.rows_each;
     const int n_groups = EPI == EPI_SILU_PAIR ? ms.rows_each : (total_rows + R - 1) / R;
     if (pro == PRO_NONE) {
         note_kernel("k_matvec_v2_free<%d, %d, %d, %d>", T, NU, R, (int)EPI);
         // EPI_REF: the block chain is a dependent sequence per wave (DPP move + fma per block): as many waves per SIMD as the registers admit, not the stream-optimal 8 per CU
-        int n_waves = std::min(n_groups, g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(mv_max_wpc<NU>())));
+        int n_waves = std::min(n_groups, tune.cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(tune, mv_max_wpc<NU>())));
         n_waves = (n_waves + 3) & ~3;
         hipLaunchKernelGGL((k_matvec_v2_free<T, NU, R, EPI>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, ms.w0.qs, ms.w0.qh, ms.w0.sc, ms.w0.d, A.q8k, ms.w0.cols, ms.rows_each,
                            n_groups, n_waves, ms, A, pa.tb);
         return;
     }
-    const int LB = EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(mv_fat_max_threads<NU>()), WPB = LB / 64;
-    const int n_blocks = std::min((n_groups + WPB - 1) / WPB, g_mv_cus);
+    const int LB = EPI == EPI_REF ? mv_fat_max_threads<NU>() : MV_FAT_MIN, WPB = LB / 64;
+    const int n_blocks = std::min((n_groups + WPB - 1) / WPB, tune.cus);
     const int n_waves = n_blocks * WPB;
     const dim3 grid((unsigned)n_blocks), block((unsigned)LB);
     const int K = ms.w0.cols;
@@ -841,13 +837,13 @@ static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs 
     }
 }
 template <int T>
-static bool launch_v2_type(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, bool issue_bar, hipStream_t s) {
+static bool launch_v2_type(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, int epi, bool issue_bar, const LaunchTuning &tune, hipStream_t s) {
     const int nu = (ms.w0.cols / TrMV<T>::EPU + 63) / 64;
     auto launch = [&](auto e) {
         constexpr int EPI = decltype(e)::value;
         return mv_for_units<tr_is_narrow<T>()>(mv_units<T, EPI>(), nu, [&](auto n) {
             constexpr int NU = decltype(n)::value;
-            launch_v2_t<T, NU, mv_rows_per_group<T, NU, EPI>(), EPI>(ms, A, pro, pa, issue_bar, s); });
+            launch_v2_t<T, NU, mv_rows_per_group<T, NU, EPI>(), EPI>(ms, A, pro, pa, issue_bar, tune, s); });
     };
     switch (epi) {
     case EPI_SILU_PAIR: return ms.n == 2 && (pro == PRO_NONE || pro == PRO_RMS) && launch(std::integral_constant<int, EPI_SILU_PAIR>{});
@@ -913,10 +909,10 @@ static int mv_split_blocks(int ng1, double bytes1, int ng2, double bytes2, int t
     return best_b1;
 }
 template <int T1, int T2, int NU, int EPI = EPI_STORE>
-static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
+static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, const LaunchTuning &tune, hipStream_t s) {
     const int ng1 = m1.n * m1.rows_each, ng2 = m2.n * m2.rows_each;
-    const int threads = pro == PRO_NONE ? 256 : (EPI == EPI_REF ? mv_fat_max_threads<NU>() : pick_fat_threads(mv_fat_max_threads<NU>())), wpb = threads / 64;
-    const int total = pro == PRO_NONE ? g_mv_cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(mv_max_wpc<NU>())) / 4 : g_mv_cus;
+    const int threads = pro == PRO_NONE ? 256 : (EPI == EPI_REF ? mv_fat_max_threads<NU>() : MV_FAT_MIN), wpb = threads / 64;
+    const int total = pro == PRO_NONE ? tune.cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(tune, mv_max_wpc<NU>())) / 4 : tune.cus;
     const int b1 = mv_split_blocks(ng1, bytes1, ng2, bytes2, total, wpb), nw1 = b1 * wpb, nw2 = (total - b1) * wpb;
     constexpr bool BUILT = mv_issue_bar_built<T1, NU, EPI>() && mv_issue_bar_built<T2, NU, EPI>();
     const bool bar = pro != PRO_NONE && issue_bar && BUILT;
@@ -929,11 +925,11 @@ static void launch_mix_t(const MatSet &m1, const MatSet &m2, double bytes1, doub
     hipLaunchKernelGGL((k_matvec_mix<T1, T2, NU, PRO_RMS, EPI>), grid, block, mv_prologue_lds(m1.w0.cols), s, pa.x, pa.w, m1.w0.cols, threads, ng1, nw1, ng2, nw2, m1, m2, A, pa.tb);
 }
 template <int T1, int T2, int EPI = EPI_STORE>
-static bool launch_mix_nu(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, hipStream_t s) {
-    return mv_for_units(MixUnits{}, (m1.w0.cols / 32 + 63) / 64, [&](auto n) { launch_mix_t<T1, T2, decltype(n)::value, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); });
+static bool launch_mix_nu(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, const LaunchTuning &tune, hipStream_t s) {
+    return mv_for_units(MixUnits{}, (m1.w0.cols / 32 + 63) / 64, [&](auto n) { launch_mix_t<T1, T2, decltype(n)::value, EPI>(m1, m2, b1, b2, A, pro, pa, issue_bar, tune, s); });
 }
 // Decode mat-vec over two sets of different k-quant types with the same K (wq|wk + wv of a "more bits" layer) in ONE launch.  pro: PRO_NONE or PRO_RMS.
-bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, hipStream_t s, int pro,
+bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, const LaunchTuning &tune, hipStream_t s, int pro,
                          const float *px, const float *pw, int epi, bool issue_bar) {
     if (pro != PRO_NONE && pro != PRO_RMS) return false;
     if (W1[0]->cols != W2[0]->cols || W1[0]->cols % 256) return false;
@@ -945,17 +941,16 @@ bool launch_matvec_mixed(const QWeight *const *W1, float *const *y1, int n1, con
     for (int i = 0; i < n2; i++) b2 += (double)W2[i]->bytes;
     return for_mixed_types(W1[0]->type, W2[0]->type, [&](auto t1, auto t2) {
         constexpr int T1 = decltype(t1)::value, T2 = decltype(t2)::value;
-        return epi == EPI_REF ? launch_mix_nu<T1, T2, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, s) : launch_mix_nu<T1, T2>(m1, m2, b1, b2, A, pro, pa, issue_bar, s); });
+        return epi == EPI_REF ? launch_mix_nu<T1, T2, EPI_REF>(m1, m2, b1, b2, A, pro, pa, issue_bar, tune, s) : launch_mix_nu<T1, T2>(m1, m2, b1, b2, A, pro, pa, issue_bar, tune, s); });
 }
-void set_matvec_tuning(int waves_per_cu, int fat_threads, int cus) { g_mv_force_waves = std::max(0, waves_per_cu); g_mv_force_fat = std::max(0, fat_threads); if (cus > 0) { g_mv_cus = cus; g_ref_cus = cus; } }
 // Decode (N = 1) mat-vec over 1..3 same-type, same-shape, equally spaced matrices.  Returns false when the set is outside the v2 kernel's range.
-bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, hipStream_t s, int pro, const float *px, const float *pw,
+bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, const LaunchTuning &tune, hipStream_t s, int pro, const float *px, const float *pw,
                        const Tables *tb, int epi, bool issue_bar) {
     ProArgs pa{}; pa.x = px; pa.w = pw; if (tb) pa.tb = *tb;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
     // false: F32 / Q2_K rows, and rows wider than the type's unit counts (served by k_mul_mat)
-    return for_weight_type(W[0]->type, [&](auto t) { return launch_v2_type<decltype(t)::value>(ms, A, pro, pa, epi, issue_bar, s); });
+    return for_weight_type(W[0]->type, [&](auto t) { return launch_v2_type<decltype(t)::value>(ms, A, pro, pa, epi, issue_bar, tune, s); });
 }
 
 
@@ -1173,10 +1168,10 @@ __global__ __launch_bounds__(mv_tn_threads<NU>()) void k_matvec_tn_mix(const Mat
     else matvec_tn_run<T2, NU, TN, PRO>(ms2, A, N, ldy, n_groups2, n_waves2, wave - n_waves1, pa, ldx, image_bytes);
 }
 template <int T, int NU, int TN>
-static void launch_tn_n(const MatSet &ms, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
+static void launch_tn_n(const MatSet &ms, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px, const float *pw, int ldx) {
     const int n_groups = ms.n * ms.rows_each;
     constexpr int WPB = mv_tn_threads<NU>() / 64;
-    const int n_blocks = std::min((n_groups + WPB - 1) / WPB, g_mv_cus), n_waves = n_blocks * WPB;
+    const int n_blocks = std::min((n_groups + WPB - 1) / WPB, tune.cus), n_waves = n_blocks * WPB;
     ProArgs pa{}; pa.x = px; pa.w = pw;
     constexpr bool PRO_OK = units_have(mv_tn_pro_units<T>(), NU);
     if constexpr (PRO_OK) {
@@ -1198,27 +1193,27 @@ static void launch_tn_n(const MatSet &ms, const ActQ &A, int N, int ldy, hipStre
     hipLaunchKernelGGL((k_matvec_tn<T, NU, TN, 0>), dim3((unsigned)n_blocks), dim3((unsigned)mv_tn_threads<NU>()), lds, s, ms, A, N, ldy, n_groups, n_waves, pa, 0, 0);
 }
 template <int T>
-static bool launch_tn_type(const MatSet &ms, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
+static bool launch_tn_type(const MatSet &ms, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px, const float *pw, int ldx) {
     return mv_for_units(mv_tn_units<T>(), (ms.w0.cols / Tr<T>::EPU + 63) / 64, [&](auto n) {
-        mv_for_rows(N, [&](auto tn) { launch_tn_n<T, decltype(n)::value, decltype(tn)::value>(ms, A, N, ldy, s, px, pw, ldx); }); });
+        mv_for_rows(N, [&](auto tn) { launch_tn_n<T, decltype(n)::value, decltype(tn)::value>(ms, A, N, ldy, tune, s, px, pw, ldx); }); });
 }
 // 2..4 activation rows against 1..3 same-type, same-shape, equally spaced matrices in ONE weight pass: y[m][t * ldy + r] = W_m[r] . act[t] (+ residual[m][t * ldy + r]).
 // false -> shape / type outside the kernel's range (the caller falls back to launch_mul_mat per matrix).
-bool launch_matvec_rows(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
+bool launch_matvec_rows(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px, const float *pw, int ldx) {
     if (px && !matvec_rows_prologue_ok(W[0]->type, W[0]->cols)) return false;
     if (N < 1 || N > 4 || !matvec_prologue_supported(W[0]->type, W[0]->cols)) return false;
     if (mv_tn_lds(W[0]->type, W[0]->cols, 4) > 150 * 1024) return false;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
-    return for_weight_type(W[0]->type, [&](auto t) { return launch_tn_type<decltype(t)::value>(ms, A, N, ldy, s, px, pw, ldx); });
+    return for_weight_type(W[0]->type, [&](auto t) { return launch_tn_type<decltype(t)::value>(ms, A, N, ldy, tune, s, px, pw, ldx); });
 }
 
 template <int T1, int T2, int NU, int TN>
-static void launch_tn_mix_n(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
+static void launch_tn_mix_n(const MatSet &m1, const MatSet &m2, double bytes1, double bytes2, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px, const float *pw, int ldx) {
     static_assert(NU <= 3, "register-resident rows, the prologue's range");
     const int ng1 = m1.n * m1.rows_each, ng2 = m2.n * m2.rows_each;
     constexpr int WPB = mv_tn_threads<NU>() / 64;
-    const int total = g_mv_cus;
+    const int total = tune.cus;
     const int b1 = mv_split_blocks(ng1, bytes1, ng2, bytes2, total, WPB), nw1 = b1 * WPB, nw2 = (total - b1) * WPB;
     ProArgs pa{}; pa.x = px; pa.w = pw;
     const dim3 grid((unsigned)total), block((unsigned)mv_tn_threads<NU>());
@@ -1234,13 +1229,13 @@ static void launch_tn_mix_n(const MatSet &m1, const MatSet &m2, double bytes1, d
     hipLaunchKernelGGL((k_matvec_tn_mix<T1, T2, NU, TN, 0>), grid, block, 0, s, m1, m2, A, N, ldy, ng1, nw1, ng2, nw2, pa, 0, 0);
 }
 template <int T1, int T2>
-static bool launch_tn_mix_type(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int N, int ldy, hipStream_t s, const float *px, const float *pw, int ldx) {
+static bool launch_tn_mix_type(const MatSet &m1, const MatSet &m2, double b1, double b2, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px, const float *pw, int ldx) {
     return mv_for_units(TnMixUnits{}, (m1.w0.cols / 32 + 63) / 64, [&](auto n) {
-        mv_for_rows(N, [&](auto tn) { launch_tn_mix_n<T1, T2, decltype(n)::value, decltype(tn)::value>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); }); });
+        mv_for_rows(N, [&](auto tn) { launch_tn_mix_n<T1, T2, decltype(n)::value, decltype(tn)::value>(m1, m2, b1, b2, A, N, ldy, tune, s, px, pw, ldx); }); });
 }
 // Batched decode, N = 1..4 rows: two sets of different k-quant types with the same K (wq|wk + wv of a "more bits" layer) in ONE launch.  px != null: the rows are
 // prepared inside the launch (rms_norm(px_t) * pw, quantised), as in launch_matvec_rows.  false: outside the kernel's range, nothing was launched.
-bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, int N, int ldy, hipStream_t s,
+bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1, const QWeight *const *W2, float *const *y2, int n2, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s,
                               const float *px, const float *pw, int ldx) {
     if (N < 1 || N > 4 || W1[0]->cols != W2[0]->cols || W1[0]->cols % 256 || W1[0]->cols / 32 > 3 * 64) return false;
     if (px && (!pw || !matvec_rows_prologue_ok(W1[0]->type, W1[0]->cols) || !matvec_rows_prologue_ok(W2[0]->type, W2[0]->cols))) return false;
@@ -1250,25 +1245,18 @@ bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1
     for (int i = 0; i < n1; i++) b1 += (double)W1[i]->bytes;
     for (int i = 0; i < n2; i++) b2 += (double)W2[i]->bytes;
     return for_mixed_types(W1[0]->type, W2[0]->type, [&](auto t1, auto t2) {
-        return launch_tn_mix_type<decltype(t1)::value, decltype(t2)::value>(m1, m2, b1, b2, A, N, ldy, s, px, pw, ldx); });
+        return launch_tn_mix_type<decltype(t1)::value, decltype(t2)::value>(m1, m2, b1, b2, A, N, ldy, tune, s, px, pw, ldx); });
 }
 
-static int g_mmq_enabled = 2;   // 0: v_dot4 tiles only (tests / A-B), 2: the LDS-staged int8-MFMA kernels of mmq2_kernels.hip for N >= 5 rows
-void set_mmq_enabled(int v) { g_mmq_enabled = v; }
-int mmq_enabled() { return g_mmq_enabled; }
 // Unquantised (F16) weights, prefill: ggml converts the activation rows to fp16 and accumulates exact fp16 products in fp32 (ggml_vec_dot_f16) -- which is
 // precisely the vision tower's MFMA GEMM (v_mfma_f32_32x32x16_f16, fp32 accumulators), so rows >= 16 go there: BASELINE.json configs[4]
-// (13B f16, 512-token prefill) is MFMA-bound instead of re-streaming 25 GB of weights once per 4 tokens.  MINIGPT4_F16_GEMM=0 keeps the v_dot path.
-static int g_f16_gemm = 1;
-void set_f16_gemm(int v) { g_f16_gemm = v != 0; }
-void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, hipStream_t s) {
-    if (g_mmq_enabled >= 2 && N >= 5 && (A.bsq || W.type == GT_Q4_0) && mmq2_supported(W.type, W.rows, W.cols)) {
+// (13B f16, 512-token prefill) is MFMA-bound instead of re-streaming 25 GB of weights once per 4 tokens.
+void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s) {
+    if (tune.mmq >= 2 && N >= 5 && (A.bsq || W.type == GT_Q4_0) && mmq2_supported(W.type, W.rows, W.cols)) {
         const QWeight *Wp[1] = {&W}; float *Yp[1] = {y}; const float *Rp[1] = {residual};
-        if (launch_mmq2_set(Wp, Yp, residual ? Rp : nullptr, 1, A, N, ldy, s)) return;
+        if (launch_mmq2_set(Wp, Yp, residual ? Rp : nullptr, 1, A, N, ldy, tune, s)) return;
     }
-    if (W.type == GT_F16 && N >= 16 && W.cols % 8 == 0) {
-        if (g_f16_gemm) { launch_gemm_f16(A.xh, W.cols, reinterpret_cast<const __half *>(W.qs), W.cols, N, W.rows, W.cols, nullptr, residual, false, Tables{}, y, nullptr, ldy, s); return; }
-    }
+    if (W.type == GT_F16 && N >= 16 && W.cols % 8 == 0) { launch_gemm_f16(A.xh, W.cols, reinterpret_cast<const __half *>(W.qs), W.cols, N, W.rows, W.cols, nullptr, residual, false, Tables{}, y, nullptr, ldy, tune, s); return; }
     if (!for_weight_type(W.type, [&](auto t) { launch_mul_mat_t<decltype(t)::value>(W, A, N, y, ldy, residual, s); return true; }))
         throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
 }
@@ -2577,14 +2565,7 @@ __global__ __launch_bounds__(512) void k_attn_prefill_h8(const float *__restrict
 #undef APH_ZERO_OACC
 #undef APH_STORE
 // ---- launchers.  Forms: 1 = k_attn_prefill_h8, 2 = k_attn_prefill_h<HD, 2>, 3 = k_attn_prefill_h<HD, 1>, 4 = the exact-f32 k_attn_prefill<HD, 1>
-static int g_attn_prefill_w8 = 1;    // 1: the 8-wave loader / MFMA form for 32-query tiles; MINIGPT4_ATTN_PREFILL_W8, read by Engine::init
-void set_attn_prefill_w8(int v) { g_attn_prefill_w8 = v != 0; }
-static int g_attn_prefill_f16 = 1;   // 1: prompt attention on the fp16 matrix cores (k_attn_prefill_h), 0: the exact-f32 MFMA kernel (k_attn_prefill); test-library setter only
-void set_attn_prefill_f16(int v) { g_attn_prefill_f16 = v != 0; }
-int attn_prefill_f16() { return g_attn_prefill_f16; }
-static int g_attn_prefill_form = 0;  // test library: 1 / 2 / 3 = only k_attn_prefill_h8 / _h<HD, 2> / _h<HD, 1> is tried (no size rule); 0 = the launchers' own choice
-void set_attn_prefill_form(int v) { g_attn_prefill_form = v; }
-int attn_prefill_form() { return g_attn_prefill_form; }
+// (LaunchTuning::attn_prefill_w8 / _f16 / _form choose among them)
 // the LDS image of a form for score rows of t_max keys: *LS = floats per score row; returns its bytes, 0 when it exceeds the 160 KiB of a CU (the form refuses).
 // Forms 1 .. 3: score rows + fp16 K tile + transposed V tile (form 1: two buffers that hold either); form 4: score rows + one f32 tile.
 static size_t attn_prefill_lds(int form, int hd, int t_max, int *LS) {
@@ -2594,10 +2575,10 @@ static size_t attn_prefill_lds(int form, int hd, int t_max, int *LS) {
     return lds > 160 * 1024 - 512 ? 0 : lds;
 }
 // the fp16 forms in the order they are tried.  wide: 32 queries per staged K / V tile still give every CU a workgroup
-static int attn_prefill_forms(bool wide, int (&forms)[3]) {
-    const int f = g_attn_prefill_form;
+static int attn_prefill_forms(const LaunchTuning &tune, bool wide, int (&forms)[3]) {
+    const int f = tune.attn_prefill_form;
     int n = 0;
-    if (f == 1 || (f == 0 && g_attn_prefill_w8 && wide)) forms[n++] = 1;
+    if (f == 1 || (f == 0 && tune.attn_prefill_w8 && wide)) forms[n++] = 1;
     if (f == 2 || (f == 0 && wide)) forms[n++] = 2;
     if (f == 0 || f == 3) forms[n++] = 3;
     return n;
@@ -2627,7 +2608,7 @@ static bool launch_attn_prefill_form(const float *q, const __half *kc, const __h
 // the first fp16 form of attn_prefill_forms that fits; sg: the segments of a packed chunk, nullptr: one conversation.  *wrote_h: the 8-wave form ran and stored fp16 rows
 template <int HD>
 static bool launch_attn_prefill_f16(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, int t_max, const AttnSegs *sg, const Tables &tb, float *out,
-                                    hipStream_t s, __half *out_h, bool *wrote_h) {
+                                    const LaunchTuning &tune, hipStream_t s, __half *out_h, bool *wrote_h) {
     auto tiles = [&](int qs) { return sg ? sg->n_tiles[qs - 1] : (N + AP_QT * qs - 1) / (AP_QT * qs); };
     auto launch = [&](auto form) {
         constexpr int FORM = decltype(form)::value, QS = FORM == 3 ? 1 : 2;
@@ -2636,7 +2617,7 @@ static bool launch_attn_prefill_f16(const float *q, const __half *kc, const __ha
         return launch_attn_prefill_form<HD, FORM>(q, kc, vc, N, n_head, n_past, t_max, tiles(QS), tb, out, s, oh);
     };
     int forms[3];
-    const int n = attn_prefill_forms(n_head * tiles(2) >= 256, forms);
+    const int n = attn_prefill_forms(tune, n_head * tiles(2) >= 256, forms);
     for (int i = 0; i < n; i++) {
         const int f = forms[i];
         if (f == 1 ? launch(std::integral_constant<int, 1>{}) : f == 2 ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 3>{})) {
@@ -2646,7 +2627,7 @@ static bool launch_attn_prefill_f16(const float *q, const __half *kc, const __ha
     }
     return false;
 }
-// Fallback: k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken (a) after set_attn_prefill_f16(0) (test library: the A/B switch of
+// Fallback: k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken (a) with LaunchTuning::attn_prefill_f16 == 0 (test library: the A/B switch of
 // the fp16 kernels), (b) when the fp16 kernels refuse because their LDS image exceeds the 160 KiB of a CU.  Both forms hold 16 score rows of the whole context: at head
 // size 128 both end at 1984 keys; beyond, this returns false and Engine::forward runs the rows through the decode attention kernel (k_attn_llm, one query row per
 // workgroup), which has no such limit.
@@ -2674,23 +2655,23 @@ int attn_seg_tiles(const int *segs, int n_seg, int qt, int *out) {
     for (size_t k = 0; k < v.size(); k++) { out[2 * k] = v[k].seg; out[2 * k + 1] = v[k].q0; }
     return (int)v.size();
 }
-bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, hipStream_t s, __half *out_h,
-                             bool *wrote_h) {
+bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half *vcache, const AttnSegs &sg, int n_head, int hd, const Tables &tb, float *out, const LaunchTuning &tune, hipStream_t s,
+                             __half *out_h, bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
     bool done = false;                                             // an unsupported head size: declined, like a shape that does not fit
-    if (!g_attn_prefill_f16) return false;                         // the exact-f32 kernel: per-segment launches (the caller)
-    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_f16<decltype(tag)::value>(q, kcache, vcache, 0, n_head, nullptr, sg.t_max, &sg, tb, out, s, out_h, wrote_h); });
+    if (!tune.attn_prefill_f16) return false;                        // the exact-f32 kernel: per-segment launches (the caller)
+    attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_f16<decltype(tag)::value>(q, kcache, vcache, 0, n_head, nullptr, sg.t_max, &sg, tb, out, tune, s, out_h, wrote_h); });
     return done;
 }
 // N > 1 query rows at positions *n_past .. *n_past + N - 1 (launch_rope_kv has run); t_max >= *n_past + N (the host's view, sizes the LDS score rows).
 // false -> the score rows do not fit LDS (very long contexts): the caller runs launch_attn_llm instead.
-bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, hipStream_t s,
-                         __half *out_h, bool *wrote_h) {
+bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, const LaunchTuning &tune,
+                         hipStream_t s, __half *out_h, bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
     bool done = false;
     attn_for_head_size(hd, [&](auto tag) {
         constexpr int HD = decltype(tag)::value;
-        done = (g_attn_prefill_f16 && launch_attn_prefill_f16<HD>(q, kcache, vcache, N, n_head, n_past, t_max, nullptr, tb, out, s, out_h, wrote_h)) ||
+        done = (tune.attn_prefill_f16 && launch_attn_prefill_f16<HD>(q, kcache, vcache, N, n_head, n_past, t_max, nullptr, tb, out, tune, s, out_h, wrote_h)) ||
                launch_attn_prefill_f32<HD>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s);
     });
     return done;

@@ -831,20 +831,12 @@ void launch_slab_reduce(const float *slabs, int n_slabs, long long slab_stride, 
 
 bool mmq2_supported(int type, int rows, int cols) { return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0) && cols % 256 == 0 && rows >= 32; }
 
-static int g_mmq2_cus = 256;
-void set_mmq2_cus(int cus) { if (cus > 0) g_mmq2_cus = cus; }
-// experiment knobs (MINIGPT4_MMQ2_TT / _FILL / _KS, read ONCE by Engine::init; the test hooks set the K split directly): 0 = the launcher's own choice
-static int g_mmq2_tt = 0, g_mmq2_fill = 0, g_mmq2_ks = 0;
-void set_mmq2_tuning(int tt, int fill_pct, int ks) { if (tt >= 0) g_mmq2_tt = tt; if (fill_pct >= 0) g_mmq2_fill = fill_pct ? std::max(50, fill_pct) : 0; if (ks >= 0) g_mmq2_ks = ks; }
-
 template <typename KernelT>
 static void mmq2_launch_kernel(KernelT kernel, bool &attr_done, dim3 grid, int threads, size_t lds, hipStream_t s, const Mmq2Args &a, const ActQ &A) {
     if (!attr_done) { HIP_IGNORE(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); attr_done = true; }
     hipLaunchKernelGGL(kernel, grid, dim3((unsigned)threads), lds, s, a, A);
 }
-static int g_mmqh = 0;   // measured in round 5 and NOT adopted (profiles/r05_prefill_fp16_scaled_operands.md): 10-17 % slower per launch than the int8 kernels -- both forms are bound by the CU's load path, and the fp16 activation image doubles the staged bytes
-void set_mmqh(int v) { g_mmqh = v != 0; }
-int mmqh_enabled() { return g_mmqh; }
+// fp16_form (LaunchTuning::mmqh): measured in round 5 and NOT adopted (profiles/r05_prefill_fp16_scaled_operands.md): 10-17 % slower per launch than the int8 kernels -- both forms are bound by the CU's load path, and the fp16 activation image doubles the staged bytes
 template <int TT>
 static void mmq2_launch_tt(int type, dim3 grid, size_t lds, hipStream_t s, const Mmq2Args &a, const ActQ &A, bool fp16_form = false) {
     static bool attr[6] = {false, false, false, false, false, false};
@@ -880,7 +872,7 @@ void launch_slab_flush(const SlabSrc &src, hipStream_t s) {
     for (int i = 0; i < src.n; i++) { rs.y[i] = src.y[i]; rs.res[i] = src.res[i]; }
     hipLaunchKernelGGL(k_mmq2_reduce_set, dim3((unsigned)((n4 + 255) / 256), (unsigned)src.n), dim3(256), 0, s, src.ws, src.ks, src.stride, rs, n4);
 }
-bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, SlabSrc *defer, int force_ks) {
+bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer, int force_ks) {
     if (defer) *defer = SlabSrc{};
     if (n < 1 || n > 3 || N < 1 || (W[0]->type == GT_Q4_0 ? !(A.q80 && A.d0) : !A.bsq)) return false;
     for (int i = 0; i < n; i++) if (!mmq2_supported(W[i]->type, W[i]->rows, W[i]->cols) || W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false;
@@ -888,8 +880,7 @@ bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *cons
     for (int i = 0; i < n; i++) { a.w[i] = *W[i]; a.y[i] = y[i]; a.res[i] = residual ? residual[i] : nullptr; }
     a.n_tiles = (N + 31) / 32;
     a.n_mat = n; a.groups_each = (W[0]->rows + 127) / 128; a.N = N; a.ldy = ldy;
-    int max_tt = W[0]->type == GT_Q6_K ? 2 : 3;          // token tiles per chunk the 256-register budget (two waves per SIMD) admits: Q6_K keeps four half-masked operand sets per pair
-    if (g_mmq2_tt > 0) max_tt = std::min(max_tt, g_mmq2_tt);   // experiments
+    const int max_tt = W[0]->type == GT_Q6_K ? 2 : 3;    // token tiles per chunk the 256-register budget (two waves per SIMD) admits: Q6_K keeps four half-masked operand sets per pair
     const int n_chunks = (a.n_tiles + max_tt - 1) / max_tt;
     a.tiles_per_chunk = (a.n_tiles + n_chunks - 1) / n_chunks;
     const int NSB = W[0]->cols / 256;
@@ -899,12 +890,11 @@ bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *cons
     const size_t out_floats = (size_t)N * ldy;
     // workgroups per CU (x 100) below which another K slice is added.  Measured on the 142-row image turn (profiles/r02r_prefill_ksplit_fill_sweep.log): 13B (5120-wide
     // matrices) 13.1 ms at 200, 11.7 at 150, 12.6 at 125 / 100 -- w1|w3's 432 workgroups are better left unsplit; 7B (4096 x 4096 wq / wo ...) 7.7 at 200, 8.2 at 150,
-    // 8.0 at 125: the narrower model wants the deeper split.  MINIGPT4_MMQ2_FILL overrides.
-    const int fill_env = g_mmq2_fill;
+    // 8.0 at 125: the narrower model wants the deeper split.
     // by the model's width (the smaller matrix dimension): rule = 0 / 1 lines of the sweep log are two other rules that lost (by weights per matrix; by workgroup count)
-    const int fill_pct = fill_env ? fill_env : (std::min(W[0]->rows, W[0]->cols) >= 5120 ? 150 : 200);
-    while (wgs * ks * 100 < fill_pct * g_mmq2_cus && NSB / (ks + 1) >= 4 && A.ws && (size_t)(ks + 1) * out_floats * n <= A.ws_floats) ks++;
-    if (g_mmq2_ks > 0) ks = std::max(1, std::min(g_mmq2_ks, std::min(NSB, A.ws ? (int)(A.ws_floats / std::max<size_t>(1, out_floats * n)) : 1)));
+    const int fill_pct = std::min(W[0]->rows, W[0]->cols) >= 5120 ? 150 : 200;
+    while (wgs * ks * 100 < fill_pct * tune.cus && NSB / (ks + 1) >= 4 && A.ws && (size_t)(ks + 1) * out_floats * n <= A.ws_floats) ks++;
+    if (tune.mmq_ks > 0) ks = std::max(1, std::min(tune.mmq_ks, std::min(NSB, A.ws ? (int)(A.ws_floats / std::max<size_t>(1, out_floats * n)) : 1)));
     if (force_ks == 1) ks = 1;   // parity mode: without a K split the kernels add a row's per-block terms block after block -- the CPU oracle's order, bit for bit
     a.sb_per_split = (NSB + ks - 1) / ks;
     ks = (NSB + a.sb_per_split - 1) / a.sb_per_split;
@@ -917,7 +907,7 @@ bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *cons
     const int type = W[0]->type;
     const bool q40 = type == GT_Q4_0;
     // fast mode, Q4_K / Q5_K: the fp16-MFMA form (k_mmqh_q45k) whenever the activation rows carry their fp16 image; force_ks == 1 (parity mode: the oracle's fp32 order) keeps the int8 kernels
-    const bool h16 = g_mmqh && force_ks != 1 && (type == GT_Q4_K || type == GT_Q5_K) && A.q16 && A.bs16;
+    const bool h16 = tune.mmqh && force_ks != 1 && (type == GT_Q4_K || type == GT_Q5_K) && A.q16 && A.bs16;
     switch (a.tiles_per_chunk) {
     case 1: mmq2_launch_tt<1>(type, grid, 2 * (q40 ? Mmq2Stage80<1>::BYTES : Mmq2Stage<1>::BYTES) + 16384, s, a, A, h16); break;
     case 2: mmq2_launch_tt<2>(type, grid, 2 * (q40 ? Mmq2Stage80<2>::BYTES : Mmq2Stage<2>::BYTES) + 16384, s, a, A, h16); break;

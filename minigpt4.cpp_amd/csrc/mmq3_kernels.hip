@@ -297,10 +297,6 @@ void launch_mmq3_build(const QWeight &W, uint8_t *planes, hipStream_t s) {
     else hipLaunchKernelGGL(k_mmq3_build<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, planes, planes + hi_off);
 }
 
-static int g_mmq3_cus = 256, g_mmq3_ks = 0, g_mmq3_nw = 8;
-void set_mmq3_tuning(int cus, int ks) { if (cus > 0) g_mmq3_cus = cus; if (ks >= 0) g_mmq3_ks = ks; }
-void set_mmq3_waves(int nw) { g_mmq3_nw = nw == 4 ? 4 : 8; }
-
 template <int NT, int NW>
 static void mmq3_launch_nt(dim3 grid, hipStream_t s, const Mmq3Args &a, const ActQ &A) {
     static bool attr = false;
@@ -320,7 +316,7 @@ static void mmq3_launch(int tiles, dim3 grid, hipStream_t s, const Mmq3Args &a, 
 
 // 1..3 same-type, same-shape Q4_K / Q5_K matrices with planes (planes[i]: launch_mmq3_build's output) against the N prepared rows in one launch.  Same contract as
 // launch_mmq2_set (K split into A.ws, combine deferred on request); false -> outside the kernel's range, nothing launched.
-bool launch_mmq3_set(const QWeight *const *W, const uint8_t *const *planes, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s, SlabSrc *defer) {
+bool launch_mmq3_set(const QWeight *const *W, const uint8_t *const *planes, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer) {
     if (defer) *defer = SlabSrc{};
     if (n < 1 || n > 3 || N < 1 || !A.bsq || !A.q8k || !A.dk) return false;
     for (int i = 0; i < n; i++) if (!planes[i] || !mmq3_supported(W[i]->type, W[i]->rows, W[i]->cols) || W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false;
@@ -329,14 +325,14 @@ bool launch_mmq3_set(const QWeight *const *W, const uint8_t *const *planes, floa
     for (int i = 0; i < n; i++) { a.w[i] = *W[i]; a.plo[i] = planes[i]; a.phi[i] = planes[i] + hi_off; a.y[i] = y[i]; a.res[i] = residual ? residual[i] : nullptr; }
     const int tiles = (N + 15) / 16, n_chunks = (tiles + 8) / 9;
     a.tiles_per_chunk = (tiles + n_chunks - 1) / n_chunks;
-    const int nw = g_mmq3_nw, rw = 16 * nw, slots = g_mmq3_cus * (nw == 8 ? 1 : 2);   // workgroups the chip holds at once
+    const int nw = tune.mmq3_waves, rw = 16 * nw, slots = tune.cus * (nw == 8 ? 1 : 2);   // workgroups the chip holds at once
     a.n_mat = n; a.groups_each = (W[0]->rows + rw - 1) / rw; a.N = N; a.ldy = ldy;
     const int NSB = W[0]->cols / 256, wgs = n * a.groups_each * n_chunks;
     const size_t out_floats = (size_t)N * ldy;
     // K split: split until the launch just fills the chip; at least 4 super-blocks (8 stages) per slice
     int ks = std::max(1, slots / wgs);
     while (ks > 1 && (NSB / ks < 4 || !A.ws || (size_t)ks * out_floats * n > A.ws_floats)) ks--;
-    if (g_mmq3_ks > 0) ks = std::max(1, std::min(g_mmq3_ks, std::min(NSB, A.ws ? (int)(A.ws_floats / std::max<size_t>(1, out_floats * n)) : 1)));
+    if (tune.mmq_ks > 0) ks = std::max(1, std::min(tune.mmq_ks, std::min(NSB, A.ws ? (int)(A.ws_floats / std::max<size_t>(1, out_floats * n)) : 1)));
     a.sb_per_split = (NSB + ks - 1) / ks;
     ks = (NSB + a.sb_per_split - 1) / a.sb_per_split;
     if (ks > 1) {

@@ -419,8 +419,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_matvec_ri_mix(const RiArgs a, c
     }
 }
 
-static int g_ri_cus = 256;
-void set_ri_cus(int cus) { if (cus > 0) g_ri_cus = cus; }
 static size_t ri_lds(int type, int K, int wpb, bool pro) { const int NSB = K / 256; return (size_t)4 * K + (size_t)4 * NSB * (type == GT_Q6_K ? 32 : 16) + (size_t)4 * NSB * 4 + (size_t)wpb * 4 * 64 * 4 + (pro ? (size_t)4 * (K / 16) * 2 : 0); }
 template <int T, int WPB, bool PRO>
 static void launch_ri_k(const RiArgs &a, const ActQ &A, unsigned blocks, size_t lds, hipStream_t s) {
@@ -429,30 +427,30 @@ static void launch_ri_k(const RiArgs &a, const ActQ &A, unsigned blocks, size_t 
     hipLaunchKernelGGL((k_matvec_ri<T, WPB, PRO>), dim3(blocks), dim3(64 * WPB), lds, s, a, A);
 }
 template <int T>
-static bool launch_ri_t(const RiArgs &a, const ActQ &A, hipStream_t s) {
+static bool launch_ri_t(const RiArgs &a, const ActQ &A, const LaunchTuning &tune, hipStream_t s) {
     const int total = a.n_mat * a.groups_each;
     // 4 waves per workgroup (each a K quarter), two workgroups per CU; matrices with fewer 64-row groups than CUs (wo, w2: 80 groups at the 13B
     // width) split K over 8 waves
-    const bool wide = total < g_ri_cus && a.ksplit <= 1, pro = a.px != nullptr;
+    const bool wide = total < tune.cus && a.ksplit <= 1, pro = a.px != nullptr;
     const size_t lds = ri_lds(T, a.K, wide ? 8 : 4, pro);
     if (lds > (wide ? 150u : 78u) * 1024u) return false;
-    if (wide) { const unsigned nb = (unsigned)std::min(total, g_ri_cus); if (pro) launch_ri_k<T, 8, true>(a, A, nb, lds, s); else launch_ri_k<T, 8, false>(a, A, nb, lds, s); }
-    else { const unsigned nb = (unsigned)std::min(total * std::max(1, a.ksplit), 2 * g_ri_cus); if (pro) launch_ri_k<T, 4, true>(a, A, nb, lds, s); else launch_ri_k<T, 4, false>(a, A, nb, lds, s); }
+    if (wide) { const unsigned nb = (unsigned)std::min(total, tune.cus); if (pro) launch_ri_k<T, 8, true>(a, A, nb, lds, s); else launch_ri_k<T, 8, false>(a, A, nb, lds, s); }
+    else { const unsigned nb = (unsigned)std::min(total * std::max(1, a.ksplit), 2 * tune.cus); if (pro) launch_ri_k<T, 4, true>(a, A, nb, lds, s); else launch_ri_k<T, 4, false>(a, A, nb, lds, s); }
     return true;
 }
 // y[m][t * ldy + r] = W_m[r] . act[t] (+ residual[m][t * ldy + r]) for N = 1..4 prepared rows (A: Q8_K image incl. bsq) against 1..3 same-type,
 // same-shape k-quant matrices that carry their row-interleaved image (ri[k]); false -> outside this kernel's range, nothing launched
 // K split over workgroups for a set with few row groups and a long K (ri_kernels.hip header): parts of >= 8 super-blocks (two per wave), at most 4,
 // only with a workspace
-int ri_ksplit(int total_groups, int K, const RiWorkspace &ws) {
+int ri_ksplit(int total_groups, int K, const RiWorkspace &ws, const LaunchTuning &tune) {
     const int NSB = K / 256;
-    if (!ws.slabs || !ws.tickets || total_groups >= g_ri_cus / 2 || total_groups > ws.n_tickets) return 1;
-    int S = std::min(4, std::min(NSB / 8, 2 * g_ri_cus / std::max(1, total_groups)));
+    if (!ws.slabs || !ws.tickets || total_groups >= tune.cus / 2 || total_groups > ws.n_tickets) return 1;
+    int S = std::min(4, std::min(NSB / 8, 2 * tune.cus / std::max(1, total_groups)));
     while (S > 1 && (size_t)total_groups * S * 256 > ws.slab_floats) S--;
     return std::max(1, S);
 }
-bool launch_matvec_ri(const QWeight *const *W, const RiPlanes *const *ri, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, hipStream_t s,
-                      const float *px, const float *pw, int ldx, const RiWorkspace &ws) {
+bool launch_matvec_ri(const QWeight *const *W, const RiPlanes *const *ri, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune,
+                      hipStream_t s, const float *px, const float *pw, int ldx, const RiWorkspace &ws) {
     if (n < 1 || n > 3 || N < 1 || N > 4) return false;
     if (px ? ldx < W[0]->cols : (!A.q8k || !A.dk || !A.bsk || !A.bsq)) return false;      // px with pw == null: rows quantised as they are (no norm)
     RiArgs a{};
@@ -463,11 +461,11 @@ bool launch_matvec_ri(const QWeight *const *W, const RiPlanes *const *ri, float 
     }
     if (!ri_supported(W[0]->type, W[0]->rows, W[0]->cols)) return false;
     a.n_mat = n; a.groups_each = W[0]->rows / 64; a.rows_each = W[0]->rows; a.K = W[0]->cols; a.N = N; a.ldy = ldy;
-    a.ksplit = ri_ksplit(n * a.groups_each, a.K, ws); a.slabs = ws.slabs; a.tickets = ws.tickets;
+    a.ksplit = ri_ksplit(n * a.groups_each, a.K, ws, tune); a.slabs = ws.slabs; a.tickets = ws.tickets;
     switch (W[0]->type) {
-    case GT_Q4_K: return launch_ri_t<GT_Q4_K>(a, A, s);
-    case GT_Q5_K: return launch_ri_t<GT_Q5_K>(a, A, s);
-    case GT_Q6_K: return launch_ri_t<GT_Q6_K>(a, A, s);
+    case GT_Q4_K: return launch_ri_t<GT_Q4_K>(a, A, tune, s);
+    case GT_Q5_K: return launch_ri_t<GT_Q5_K>(a, A, tune, s);
+    case GT_Q6_K: return launch_ri_t<GT_Q6_K>(a, A, tune, s);
     default: return false;
     }
 }
@@ -481,7 +479,7 @@ static void launch_ri_mix_k(const RiArgs &a, const ActQ &A, unsigned blocks, siz
 // wq | wk of one type (Q4_K / Q5_K) and wv of another (Q6_K), same shape, every one with its row-interleaved image: y_k[t * ldy + r] = W_k[r] .
 // act[t] in one launch
 bool launch_matvec_ri_mixed(const QWeight *const *Wa, const RiPlanes *const *ria, float *const *ya, int na, const QWeight *const *Wb, const RiPlanes *const *rib, float *const *yb, int nb,
-                            const ActQ &A, int N, int ldy, hipStream_t s) {
+                            const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s) {
     if (na < 1 || nb < 1 || na + nb > 3 || N < 1 || N > 4 || !A.q8k || !A.dk || !A.bsk || !A.bsq) return false;
     const int ta = Wa[0]->type, tb = Wb[0]->type;
     if (!((ta == GT_Q4_K || ta == GT_Q5_K) && tb == GT_Q6_K) || !ri_supported(ta, Wa[0]->rows, Wa[0]->cols)) return false;
@@ -493,11 +491,11 @@ bool launch_matvec_ri_mixed(const QWeight *const *Wa, const RiPlanes *const *ria
     }
     a.n_mat = na + nb; a.n_a = na; a.groups_each = Wa[0]->rows / 64; a.rows_each = Wa[0]->rows; a.K = Wa[0]->cols; a.N = N; a.ldy = ldy; a.ksplit = 1;
     const int total = a.n_mat * a.groups_each, NSB = a.K / 256;
-    const bool wide = total < g_ri_cus;
+    const bool wide = total < tune.cus;
     const int wpb = wide ? 8 : 4;
     const size_t lds = (size_t)4 * a.K + (size_t)4 * NSB * (16 + 32) + (size_t)4 * NSB * 4 + (size_t)wpb * 4 * 64 * 4;
     if (lds > (wide ? 150u : 78u) * 1024u) return false;
-    const unsigned nbk = (unsigned)std::min(total, wide ? g_ri_cus : 2 * g_ri_cus);
+    const unsigned nbk = (unsigned)std::min(total, wide ? tune.cus : 2 * tune.cus);
     if (ta == GT_Q4_K) { if (wide) launch_ri_mix_k<GT_Q4_K, GT_Q6_K, 8>(a, A, nbk, lds, s); else launch_ri_mix_k<GT_Q4_K, GT_Q6_K, 4>(a, A, nbk, lds, s); }
     else { if (wide) launch_ri_mix_k<GT_Q5_K, GT_Q6_K, 8>(a, A, nbk, lds, s); else launch_ri_mix_k<GT_Q5_K, GT_Q6_K, 4>(a, A, nbk, lds, s); }
     return true;

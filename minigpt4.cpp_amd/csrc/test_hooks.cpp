@@ -26,6 +26,11 @@ float probe_dma_GBps(int form, int policy, int waves, int fill, int depth, int d
 void launch_fill_random(void *p, size_t bytes, unsigned seed, hipStream_t s);
 }
 
+// The launch tuning of the single-kernel hooks.  It lives in this library only and no context ever reads it (a context has its own: Engine::tune_).  The sticky setters
+// Python calls (minigpt4_amd_test_set_gemm_arm / _set_splitk_xcd / _set_attn_qt) write it; a hook that varies a knob for ONE call works on hook_tuning()'s copy.
+static LaunchTuning g_tune;
+static LaunchTuning hook_tuning() { LaunchTuning t = g_tune; hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0)); t.cus = prop.multiProcessorCount; return t; }
+
 // One thread per fp16 bit pattern: the table functions of activations.hpp exactly as the kernels' epilogues call them (t == null: the computed form), result as fp16 bits.
 // which: 0 GELU, 1 SiLU, 2 exp (the oracle's orc_table numbering)
 __global__ __launch_bounds__(256) void k_test_activation(int which, const __half *t, unsigned short *out) {
@@ -122,8 +127,8 @@ static int test_mul_mat_impl(int ggml_type, const void *raw_w, int64_t n_in, int
         HIP_CHECK(hipMemcpy(d_x.p, x, (size_t)(N * n_in) * 4, hipMemcpyHostToDevice));
         ActQ A; std::vector<std::unique_ptr<DevBuf>> keep; alloc_act(A, keep, (size_t)N, (size_t)n_in);
         launch_rms_quant(d_x.as<float>(), nullptr, (int)N, (int)n_in, A, act_mask_for(ggml_type), nullptr);
-        if (ref) launch_mul_mat_ref(W, A, (int)N, d_y.as<float>(), (int)n_out, nullptr, nullptr);
-        else launch_mul_mat(W, A, (int)N, d_y.as<float>(), (int)n_out, nullptr, nullptr);
+        if (ref) launch_mul_mat_ref(W, A, (int)N, d_y.as<float>(), (int)n_out, nullptr, g_tune, nullptr);
+        else launch_mul_mat(W, A, (int)N, d_y.as<float>(), (int)n_out, nullptr, g_tune, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, (size_t)(N * n_out) * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -154,24 +159,22 @@ int minigpt4_amd_test_mmq2(int ggml_type, const void *raw_w, int n_mat, int64_t 
         for (int i = 0; i < n_mat; i++) { Wp[i] = &W[i]; Yp[i] = d_y.as<float>() + (size_t)i * out_each; Rp[i] = d_res.as<float>() + (size_t)i * out_each; }
         A.ws = d_ws.as<float>(); A.ws_floats = out_each * n_mat * 16;
         bool ok;
+        LaunchTuning tune = hook_tuning();
+        tune.f16_ks = tune.mmq_ks = ks; tune.mmqh = generation == 4;   // 4: k_mmqh_q45k (fp16-MFMA form, not adopted)
+        tune = tune.normalised();
         if (ggml_type == GT_F16) {   // the F16 language-model set path (big MFMA GEMM, several matrices per launch / split K)
             const __half *Wh[3]; for (int i = 0; i < n_mat; i++) Wh[i] = reinterpret_cast<const __half *>(W[i].qs);
-            struct KsScope { KsScope(int k) { set_gemm_tuning(-1, k); } ~KsScope() { set_gemm_tuning(-1, 0); } } scope(std::max(0, ks));   // restored on every exit path
-            ok = launch_gemm_f16_set(A.xh, (int)n_in, Wh, n_mat, (int)N, (int)n_out, (int)n_in, Yp, residual ? Rp : nullptr, (int)n_out, A.ws, A.ws_floats, 256, nullptr);
+            ok = launch_gemm_f16_set(A.xh, (int)n_in, Wh, n_mat, (int)N, (int)n_out, (int)n_in, Yp, residual ? Rp : nullptr, (int)n_out, A.ws, A.ws_floats, tune, nullptr);
         } else {
-            struct KsScope { KsScope(int k) { set_mmq2_tuning(-1, -1, k); set_mmq3_tuning(-1, k); } ~KsScope() { set_mmq2_tuning(-1, -1, 0); set_mmq3_tuning(-1, 0); } } scope(std::max(0, ks));
             if (generation == 3) {   // load-time digit planes (mmq3_kernels.hip)
                 if (!mmq3_supported(ggml_type, (int)n_out, (int)n_in)) return 4;
                 const size_t pb = mmq3_plane_bytes((int)n_out, (int)n_in);
                 DevBuf d_pl(pb * (size_t)n_mat);
                 const uint8_t *Pp[3];
                 for (int i = 0; i < n_mat; i++) { Pp[i] = d_pl.as<uint8_t>() + (size_t)i * pb; launch_mmq3_build(W[i], d_pl.as<uint8_t>() + (size_t)i * pb, nullptr); }
-                ok = launch_mmq3_set(Wp, Pp, Yp, residual ? Rp : nullptr, n_mat, A, (int)N, (int)n_out, nullptr);
+                ok = launch_mmq3_set(Wp, Pp, Yp, residual ? Rp : nullptr, n_mat, A, (int)N, (int)n_out, tune, nullptr);
                 HIP_CHECK(hipDeviceSynchronize());
-            } else {
-                struct HScope { int keep; HScope(int v) : keep(mmqh_enabled()) { set_mmqh(v); } ~HScope() { set_mmqh(keep); } } h_scope(generation == 4);   // 4: k_mmqh_q45k (fp16-MFMA form, not adopted)
-                ok = launch_mmq2_set(Wp, Yp, residual ? Rp : nullptr, n_mat, A, (int)N, (int)n_out, nullptr);
-            }
+            } else ok = launch_mmq2_set(Wp, Yp, residual ? Rp : nullptr, n_mat, A, (int)N, (int)n_out, tune, nullptr);
         }
         HIP_CHECK(hipDeviceSynchronize());
         if (!ok) return 4;
@@ -203,7 +206,7 @@ int minigpt4_amd_test_matvec_issue(int type1, const void *raw1, int n1, int type
     if (guard < 0 || guard > (1 << 20)) return 1;
     return test_matvec_impl(type1, raw1, n1, type2, raw2, n2, n_in, n_out, x, x2, prep, 1, epi, residual, host_silu_table().data(), y, issue_barrier != 0, guard);
 }
-int minigpt4_amd_test_matvec_waves(void) { return matvec_prologue_waves(); }
+int minigpt4_amd_test_matvec_waves(void) { return matvec_prologue_waves(g_tune); }
 static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, const void *raw2, int n2, int64_t n_in, int64_t n_out, const float *x, const float *x2, int prep,
                             int fuse, int epi, const float *residual, const unsigned short *silu_table, float *y, bool issue_bar, int guard) {
     if (!raw1 || !x || !y || n_in <= 0 || n_out <= 0 || n1 < 1 || n1 > 3 || n2 < 0 || n2 > 1 || prep < 1 || prep > 3 || (prep != 2 && !x2)) return 1;
@@ -242,8 +245,8 @@ static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, cons
         const QWeight *Wp[4]; float *Yp[4]; const float *Rp[4];
         for (int m = 0; m < nt; m++) { Wp[m] = &W[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * R; Rp[m] = d_res.as<float>() + (size_t)m * R; }
         bool ok;
-        if (n2) ok = launch_matvec_mixed(Wp, Yp, n1, Wp + n1, Yp + n1, n2, A, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), epi, issue_bar);
-        else ok = launch_matvec_set(Wp, Yp, residual ? Rp : nullptr, n1, A, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), &tb, epi, issue_bar);
+        if (n2) ok = launch_matvec_mixed(Wp, Yp, n1, Wp + n1, Yp + n1, n2, A, g_tune, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), epi, issue_bar);
+        else ok = launch_matvec_set(Wp, Yp, residual ? Rp : nullptr, n1, A, g_tune, nullptr, fuse ? prep : 0, d_x.as<float>(), d_x2.as<float>(), &tb, epi, issue_bar);
         if (!ok) { set_last_error("shape / type outside the decode mat-vec kernel's range"); return 4; }
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, ((size_t)(epi == 1 ? 1 : nt) * R + (size_t)guard) * 4, hipMemcpyDeviceToHost));
@@ -289,7 +292,7 @@ static int test_matvec_rows_impl(int ggml_type, const void *raw_w, int n_mat, in
         if (!prepare) launch_rms_quant(d_x.as<float>(), rms_w ? d_w.as<float>() : nullptr, N, K, A, act_mask_for(ggml_type), nullptr);
         const QWeight *Wp[3]; float *Yp[3]; const float *Rp[3];
         for (int m = 0; m < n_mat; m++) { Wp[m] = &W[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * N * R; Rp[m] = d_res.as<float>() + (size_t)m * N * R; }
-        if (!launch_matvec_rows(Wp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, nullptr, prepare ? d_x.as<float>() : nullptr, prepare && rms_w ? d_w.as<float>() : nullptr, K)) { set_last_error("shape / type outside the multi-row mat-vec kernel's range"); return 4; }
+        if (!launch_matvec_rows(Wp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, g_tune, nullptr, prepare ? d_x.as<float>() : nullptr, prepare && rms_w ? d_w.as<float>() : nullptr, K)) { set_last_error("shape / type outside the multi-row mat-vec kernel's range"); return 4; }
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, (size_t)n_mat * N * R * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -328,7 +331,7 @@ int minigpt4_amd_test_matvec_rows_mixed(int type_a, const void *raw_a, int n_a, 
         launch_rms_quant(d_x.as<float>(), nullptr, N, K, A, act_mask_for(type_a) | act_mask_for(type_b), nullptr);
         const QWeight *Wp[3]; float *Yp[3];
         for (int m = 0; m < n; m++) { Wp[m] = &W[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * N * R; }
-        if (!launch_matvec_rows_mixed(Wp, Yp, n_a, Wp + n_a, Yp + n_a, n_b, A, N, R, nullptr, nullptr, nullptr, K)) { set_last_error("types / shape outside the two-type multi-row mat-vec kernel's range"); return 4; }
+        if (!launch_matvec_rows_mixed(Wp, Yp, n_a, Wp + n_a, Yp + n_a, n_b, A, N, R, g_tune, nullptr, nullptr, nullptr, K)) { set_last_error("types / shape outside the two-type multi-row mat-vec kernel's range"); return 4; }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, yn * 4, hipMemcpyDeviceToHost));
@@ -365,13 +368,13 @@ int minigpt4_amd_test_matvec_ri(int ggml_type, const void *raw_w, int n_mat, int
         else launch_rms_quant(d_x.as<float>(), nullptr, N, K, A, ACT_Q8K, nullptr);                   // rms_w given: the launch norms + quantises the rows itself
         const QWeight *Wp[3]; const RiPlanes *Pp[3]; float *Yp[3]; const float *Rp[3];
         for (int m = 0; m < n_mat; m++) { Wp[m] = &W[(size_t)m]; Pp[m] = &P[(size_t)m]; Yp[m] = d_y.as<float>() + (size_t)m * N * R; Rp[m] = d_res.as<float>() + (size_t)m * N * R; }
-        hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0)); set_ri_cus(prop.multiProcessorCount);
+        const LaunchTuning tune = hook_tuning();
         DevBuf d_ws(((size_t)1 << 18) * 4 + 4096);                           // K-split workspace (few groups, long K): slabs + zeroed tickets
         HIP_CHECK(hipMemset(d_ws.p, 0, ((size_t)1 << 18) * 4 + 4096));
         const RiWorkspace ws{d_ws.as<float>(), (size_t)1 << 18, reinterpret_cast<unsigned *>(d_ws.as<float>() + ((size_t)1 << 18)), 1024};
-        if (!launch_matvec_ri(Wp, Pp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, nullptr, rms_w ? d_x.as<float>() : nullptr, rms_w ? d_w.as<float>() : nullptr, K, ws)) { set_last_error("launch_matvec_ri refused"); return 4; }
+        if (!launch_matvec_ri(Wp, Pp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, tune, nullptr, rms_w ? d_x.as<float>() : nullptr, rms_w ? d_w.as<float>() : nullptr, K, ws)) { set_last_error("launch_matvec_ri refused"); return 4; }
         HIP_CHECK(hipDeviceSynchronize());
-        if (!launch_matvec_ri(Wp, Pp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, nullptr, rms_w ? d_x.as<float>() : nullptr, rms_w ? d_w.as<float>() : nullptr, K, ws)) { set_last_error("launch_matvec_ri refused"); return 4; }   // twice: the tickets must be back at zero
+        if (!launch_matvec_ri(Wp, Pp, Yp, residual ? Rp : nullptr, n_mat, A, N, R, tune, nullptr, rms_w ? d_x.as<float>() : nullptr, rms_w ? d_w.as<float>() : nullptr, K, ws)) { set_last_error("launch_matvec_ri refused"); return 4; }   // twice: the tickets must be back at zero
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, (size_t)n_mat * N * R * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -412,8 +415,8 @@ int minigpt4_amd_test_matvec_ri_mixed(int type_a, const void *raw_a, int n_a, in
             float *yo = d_y.as<float>() + (size_t)m * N * R;
             if (m < n_a) { Wa[m] = &W[(size_t)m]; Pa[m] = &P[(size_t)m]; Ya[m] = yo; } else { Wb[m - n_a] = &W[(size_t)m]; Pb[m - n_a] = &P[(size_t)m]; Yb[m - n_a] = yo; }
         }
-        hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0)); set_ri_cus(prop.multiProcessorCount);
-        if (!launch_matvec_ri_mixed(Wa, Pa, Ya, n_a, Wb, Pb, Yb, n_b, A, N, R, nullptr)) { set_last_error("launch_matvec_ri_mixed refused"); return 4; }
+        const LaunchTuning tune = hook_tuning();
+        if (!launch_matvec_ri_mixed(Wa, Pa, Ya, n_a, Wb, Pb, Yb, n_b, A, N, R, tune, nullptr)) { set_last_error("launch_matvec_ri_mixed refused"); return 4; }
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(y, d_y.p, (size_t)n * N * R * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -425,7 +428,7 @@ int minigpt4_amd_bench_matvec_ri(int ggml_type, int rows, int cols, int n_mat, i
     if (!ri_supported(ggml_type, rows, cols) || n_mat < 1 || n_mat > 3 || N < 1 || N > 4 || iters < 1 || n_sets < 1) return 1;
     if (device_count_noexcept() <= 0) return 2;
     return guarded(3, [&]() -> int {
-        hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0)); set_ri_cus(prop.multiProcessorCount);
+        const LaunchTuning tune = hook_tuning();
         QWeight plan; const size_t need = plan_qweight(ggml_type, rows, cols, plan, nullptr);
         RiPlanes rplan; const size_t rneed = ri_plan(ggml_type, rows, cols, rplan, nullptr);
         std::vector<std::unique_ptr<DevBuf>> keep;
@@ -452,7 +455,7 @@ int minigpt4_amd_bench_matvec_ri(int ggml_type, int rows, int cols, int n_mat, i
         auto run = [&](int set) {
             const QWeight *Wp[3]; const RiPlanes *Pp[3]; float *Yp[3];
             for (int m = 0; m < n_mat; m++) { Wp[m] = &W[(size_t)set * n_mat + m]; Pp[m] = &P[(size_t)set * n_mat + m]; Yp[m] = dy.as<float>() + (size_t)m * rows * N; }
-            if (!launch_matvec_ri(Wp, Pp, Yp, nullptr, n_mat, A, N, rows, nullptr, nullptr, nullptr, 0, ws)) throw HipError{hipErrorInvalidValue, "launch_matvec_ri refused", __FILE__, __LINE__};
+            if (!launch_matvec_ri(Wp, Pp, Yp, nullptr, n_mat, A, N, rows, tune, nullptr, nullptr, nullptr, 0, ws)) throw HipError{hipErrorInvalidValue, "launch_matvec_ri refused", __FILE__, __LINE__};
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) run(i);
         HIP_CHECK(hipDeviceSynchronize());
@@ -679,7 +682,7 @@ static int test_gemm_impl(const float *A, const float *W, const float *bias, int
         if (gelu && table) { HIP_CHECK(hipMemcpy(dtab.p, table, 131072, hipMemcpyHostToDevice)); tb.gelu = dtab.as<__half>(); }
         launch_f32_to_f16(dA.as<float>(), dAh.as<__half>(), (size_t)M * K, nullptr); launch_f32_to_f16(dW.as<float>(), dWh.as<__half>(), (size_t)N * K, nullptr);
         if (skinny) { if (!launch_gemm_f16_skinny(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, nullptr, gelu != 0, tb, dC.as<float>(), nullptr, N, nullptr)) return 4; }
-        else launch_gemm_f16(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, nullptr, gelu != 0, tb, dC.as<float>(), nullptr, N, nullptr);
+        else launch_gemm_f16(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, nullptr, gelu != 0, tb, dC.as<float>(), nullptr, N, g_tune, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(C, dC.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
         return 0;
@@ -753,7 +756,7 @@ int minigpt4_amd_test_gemm_f16_splitk(const float *A, const float *W, int M, int
         HIP_CHECK(hipMemset(dS.p, 0xFF, sn * 4));
         launch_f32_to_f16(dA.as<float>(), dAh.as<__half>(), (size_t)M * K, nullptr); launch_f32_to_f16(dW.as<float>(), dWh.as<__half>(), (size_t)N * K, nullptr);
         if (skinny) { if (!launch_gemm_f16_skinny_splitk(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, slices, dS.as<float>(), mn, N, nullptr)) { HIP_CHECK(hipDeviceSynchronize()); set_last_error("launch_gemm_f16_skinny_splitk refused"); return 4; } }
-        else launch_gemm_f16_splitk(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, slices, dS.as<float>(), mn, N, nullptr);
+        else launch_gemm_f16_splitk(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, slices, dS.as<float>(), mn, N, g_tune, nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(slabs_out, dS.p, (size_t)slices * mn * 4, hipMemcpyDeviceToHost));
@@ -776,7 +779,7 @@ int minigpt4_amd_test_gemm_f16_head_major(const float *A, const float *W, const 
         HIP_CHECK(hipMemset(dC.p, 0xFF, gn * 4));
         launch_f32_to_f16(dA.as<float>(), dAh.as<__half>(), (size_t)M * K, nullptr); launch_f32_to_f16(dW.as<float>(), dWh.as<__half>(), (size_t)N * K, nullptr);
         Tables tb;
-        launch_gemm_f16_head_major(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, tb, dC.as<float>() + N, D, hd, nullptr);
+        launch_gemm_f16_head_major(dAh.as<__half>(), K, dWh.as<__half>(), K, M, N, K, bias ? db.as<float>() : nullptr, tb, dC.as<float>() + N, D, hd, g_tune, nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out, dC.p, gn * 4, hipMemcpyDeviceToHost));
@@ -863,8 +866,8 @@ int minigpt4_amd_bench_gemm_f16(int M, int N, int K, int flags, int variant, int
             if (variant == 1) return launch_gemm_f16_skinny(dA.as<__half>(), K, Wh, K, M, N, K, db.as<float>(), res ? dR.as<float>() : nullptr, gelu, tb, dC.as<float>(), (flags & 4) ? dCh.as<__half>() : nullptr, N, nullptr);
             if (variant == 2) {
                 int sl = gemm_split_slices(K, slices);
-                if (sk_arm) { sl = slices; if (!launch_gemm_f16_splitk_arm(sk_arm, dA.as<__half>(), K, Wh, K, M, N, K, sl, dslab.as<float>(), (size_t)M * N, N, nullptr)) return false; }
-                else launch_gemm_f16_splitk(dA.as<__half>(), K, Wh, K, M, N, K, sl, dslab.as<float>(), (size_t)M * N, N, nullptr);
+                if (sk_arm) { sl = slices; if (!launch_gemm_f16_splitk_arm(sk_arm, dA.as<__half>(), K, Wh, K, M, N, K, sl, dslab.as<float>(), (size_t)M * N, N, g_tune, nullptr)) return false; }
+                else launch_gemm_f16_splitk(dA.as<__half>(), K, Wh, K, M, N, K, sl, dslab.as<float>(), (size_t)M * N, N, g_tune, nullptr);
                 if (N > 2048) launch_slab_reduce(dslab.as<float>(), sl, (long long)M * N, dR.as<float>(), dC.as<float>(), (size_t)M * N, nullptr);   // the language model's combine
                 else launch_splitk_reduce_ln(dslab.as<float>(), sl, (size_t)M * N, db.as<float>(), dR.as<float>(), M, N, dC.as<float>(), dln.as<float>(), dln.as<float>(), nullptr, dCh.as<__half>(), nullptr);
                 return true;
@@ -873,10 +876,10 @@ int minigpt4_amd_bench_gemm_f16(int M, int N, int K, int flags, int variant, int
                 const int n = variant - 100;
                 const __half *Wp[3]; float *Yp[3]; const float *Rp[3];
                 for (int m = 0; m < n; m++) { Wp[m] = Wh + (size_t)m * (N / n) * K; Yp[m] = dC.as<float>() + (size_t)m * M * (N / n); Rp[m] = dR.as<float>() + (size_t)m * M * (N / n); }
-                return launch_gemm_f16_set(dA.as<__half>(), K, Wp, n, M, N / n, K, Yp, res ? Rp : nullptr, N / n, dslab.as<float>(), (size_t)8 * M * N, 256, nullptr);
+                return launch_gemm_f16_set(dA.as<__half>(), K, Wp, n, M, N / n, K, Yp, res ? Rp : nullptr, N / n, dslab.as<float>(), (size_t)8 * M * N, g_tune, nullptr);
             }
-            if (variant >= 3 && variant < 100) return launch_gemm_f16_arm(variant, dA.as<__half>(), K, Wh, K, M, N, K, db.as<float>(), res ? dR.as<float>() : nullptr, gelu, tb, dC.as<float>(), (flags & 4) ? dCh.as<__half>() : nullptr, N, nullptr);
-            launch_gemm_f16(dA.as<__half>(), K, Wh, K, M, N, K, db.as<float>(), res ? dR.as<float>() : nullptr, gelu, tb, dC.as<float>(), (flags & 4) ? dCh.as<__half>() : nullptr, N, nullptr);
+            if (variant >= 3 && variant < 100) return launch_gemm_f16_arm(variant, dA.as<__half>(), K, Wh, K, M, N, K, db.as<float>(), res ? dR.as<float>() : nullptr, gelu, tb, dC.as<float>(), (flags & 4) ? dCh.as<__half>() : nullptr, N, g_tune, nullptr);
+            launch_gemm_f16(dA.as<__half>(), K, Wh, K, M, N, K, db.as<float>(), res ? dR.as<float>() : nullptr, gelu, tb, dC.as<float>(), (flags & 4) ? dCh.as<__half>() : nullptr, N, g_tune, nullptr);
             return true;
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) if (!run(i)) return 4;
@@ -899,7 +902,7 @@ int minigpt4_amd_bench_attn_f32(int heads, int hd, int nq, int nk, int iters, fl
         Tables tb; tb.exp = dtab.as<__half>();
         { int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if (__half2float(__float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)c))))) == 0.0f) break; nneg++; } tb.exp_neg_n = (nneg + 2047) / 2048 * 2048; }
         const float scale = 1.0f / sqrtf((float)hd);
-        auto run = [&]() { launch_attn_f32(dq.as<float>(), 3 * D, dq.as<float>() + D, dq.as<float>() + 2 * D, 3 * D, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, nullptr, 1); };
+        auto run = [&]() { launch_attn_f32(dq.as<float>(), 3 * D, dq.as<float>() + D, dq.as<float>() + 2 * D, 3 * D, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, g_tune, nullptr, 1); };
         for (int i = 0; i < 3; i++) run();
         HIP_CHECK(hipDeviceSynchronize());
         float ms = 0;
@@ -918,13 +921,13 @@ int minigpt4_amd_bench_attn_f32_b(int heads, int hd, int nq, int nk, int batch, 
         { std::vector<float> h((size_t)batch * nq * 3 * D); for (size_t i = 0; i < h.size(); i++) h[i] = (float)((int)(i * 2654435761u % 2001u) - 1000) / 1000.0f; HIP_CHECK(hipMemcpy(dq.p, h.data(), h.size() * 4, hipMemcpyHostToDevice)); }
         Tables tb;                                                          // exp == null: computed exponentials
         const float scale = 1.0f / sqrtf((float)hd);
-        struct QtScope { QtScope(int q) { set_attn_vit_qt(q); } ~QtScope() { set_attn_vit_qt(0); } } scope(qt);
+        LaunchTuning tune = hook_tuning(); tune.attn_vit_qt = qt; tune = tune.normalised();
         // MG4_ATTN_HEAD_MAJOR=1 (experiment): q | k | v as [3][head][batch x rows][hd] instead of [rows][3 x heads x hd]
         const bool hm = getenv("MG4_ATTN_HEAD_MAJOR") && atoi(getenv("MG4_ATTN_HEAD_MAJOR"));
         const int R = batch * nq;
         auto run = [&]() {
-            if (hm) launch_attn_f32(dq.as<float>(), hd, dq.as<float>() + (size_t)D * R, dq.as<float>() + (size_t)2 * D * R, hd, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, nullptr, batch, R * hd, R * hd);
-            else launch_attn_f32(dq.as<float>(), 3 * D, dq.as<float>() + D, dq.as<float>() + 2 * D, 3 * D, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, nullptr, batch); };
+            if (hm) launch_attn_f32(dq.as<float>(), hd, dq.as<float>() + (size_t)D * R, dq.as<float>() + (size_t)2 * D * R, hd, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, tune, nullptr, batch, R * hd, R * hd);
+            else launch_attn_f32(dq.as<float>(), 3 * D, dq.as<float>() + D, dq.as<float>() + 2 * D, 3 * D, nq, nk, heads, hd, scale, 0.0f, tb, nullptr, douth.as<__half>(), D, tune, nullptr, batch); };
         for (int i = 0; i < 3; i++) run();
         HIP_CHECK(hipDeviceSynchronize());
         float ms = 0;
@@ -933,7 +936,7 @@ int minigpt4_amd_bench_attn_f32_b(int heads, int hd, int nq, int nk, int batch, 
         return 0;
     });
 }
-void minigpt4_amd_test_set_attn_qt(int qt) { set_attn_vit_qt(qt); }
+void minigpt4_amd_test_set_attn_qt(int qt) { g_tune.attn_vit_qt = qt; g_tune = g_tune.normalised(); }
 // The F16 feed-forward pair launch (launch_gemm_f16_silu_pair): x [N][n_in] fp32 (rounded to fp16 as the engine's row preparation does), w = w1 then w3, each [n_out][n_in]
 // fp16; out_h [N][n_out] = fp16(silu_table(w1 x) * (w3 x)) as uint16 bit patterns, out_f (optional) the fp32 product before the rounding
 static int test_f16_silu_pair_impl(const float *x, const void *w_f16, int64_t N, int64_t n_in, int64_t n_out, const unsigned short *table, unsigned short *out_h, float *out_f);
@@ -952,7 +955,7 @@ static int test_f16_silu_pair_impl(const float *x, const void *w_f16, int64_t N,
         launch_f32_to_f16(dx.as<float>(), dxh.as<__half>(), nx, nullptr);
         hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0));
         if (!launch_gemm_f16_silu_pair(dxh.as<__half>(), (int)n_in, dw.as<__half>(), dw.as<__half>() + nw, (int)N, (int)n_out, (int)n_in, tb, df.as<float>(), dh.as<__half>(), (int)n_out,
-                                       prop.multiProcessorCount, nullptr)) return 4;
+                                       g_tune, nullptr)) return 4;
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out_h, dh.p, no * 2, hipMemcpyDeviceToHost));
         if (out_f) HIP_CHECK(hipMemcpy(out_f, df.p, no * 4, hipMemcpyDeviceToHost));
@@ -1000,9 +1003,9 @@ int minigpt4_amd_test_attn_f32(const float *q, const float *k, const float *v, i
             int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if ((exp_table[c] & 0x7FFF) == 0) break; nneg++; }
             tb.exp_neg_n = (nneg + 2047) / 2048 * 2048;
         }
-        struct QtScope { QtScope(int t) { set_attn_vit_qt(t); } ~QtScope() { set_attn_vit_qt(0); } } scope(qt);
-        if (head_major) launch_attn_f32(dq.as<float>(), hd, dk.as<float>(), dv.as<float>(), hd, nq, nk, heads, hd, q_prescale, score_div, tb, dout.as<float>(), douth.as<__half>(), D, nullptr, batch, Rq * hd, Rk * hd);
-        else launch_attn_f32(dq.as<float>(), D, dk.as<float>(), dv.as<float>(), D, nq, nk, heads, hd, q_prescale, score_div, tb, dout.as<float>(), douth.as<__half>(), D, nullptr, batch);
+        LaunchTuning tune = hook_tuning(); tune.attn_vit_qt = qt; tune = tune.normalised();
+        if (head_major) launch_attn_f32(dq.as<float>(), hd, dk.as<float>(), dv.as<float>(), hd, nq, nk, heads, hd, q_prescale, score_div, tb, dout.as<float>(), douth.as<__half>(), D, tune, nullptr, batch, Rq * hd, Rk * hd);
+        else launch_attn_f32(dq.as<float>(), D, dk.as<float>(), dv.as<float>(), D, nq, nk, heads, hd, q_prescale, score_div, tb, dout.as<float>(), douth.as<__half>(), D, tune, nullptr, batch);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out, dout.p, nQ * 4, hipMemcpyDeviceToHost));
@@ -1463,7 +1466,6 @@ int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slot
     if (!kc || !vc || !segs || !q || !out_seg || !out_ref || n_head < 1 || !attn_head_size_supported(hd) || n_slots < 1 || n_seg < 1 || form < 0 || form > 4 ||
         !seg_table(n_ctx, n_slots, n_seg, segs, st, N, t_max) || (!out_h_seg) != (!out_h_ref) || (out_h_seg && !wrote_h)) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
-    struct Restore { int form = attn_prefill_form(), f16 = attn_prefill_f16(); ~Restore() { set_attn_prefill_form(form); set_attn_prefill_f16(f16); } } restore;   // the caller's settings
     return guarded(3, [&]() -> int {
         const size_t E = (size_t)n_head * hd, cache = (size_t)n_slots * n_ctx * E, stride = (size_t)n_ctx * E;
         std::vector<int> t16((size_t)2 * (N + n_seg)), t32((size_t)2 * (N + n_seg));
@@ -1482,8 +1484,9 @@ int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slot
         Tables tb; tb.exp = dtab.as<__half>();
         { int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if (__half2float(__float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)c))))) == 0.0f) break; nneg++; } tb.exp_neg_n = (nneg + 2047) / 2048 * 2048; }
         sg.segs = ds.as<int>(); sg.tiles[0] = d16.as<int>(); sg.tiles[1] = d32.as<int>();
-        set_attn_prefill_f16(form != 4);
-        set_attn_prefill_form(form >= 1 && form <= 3 ? form : 0);
+        LaunchTuning tune = hook_tuning();
+        tune.attn_prefill_f16 = form != 4; tune.attn_prefill_form = form;   // (normalised: a form outside 1 .. 3 is the size rule)
+        tune = tune.normalised();
         const float *dqp = dq.as<float>();
         // one launch_attn_prefill per segment; *all_h: every segment stored fp16 rows
         auto per_segment = [&](float *out, __half *out_h, bool *all_h) {
@@ -1492,14 +1495,14 @@ int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slot
                 const int *g = st.data() + 4 * (size_t)i;
                 const size_t off = (size_t)g[1] * E, cs = (size_t)g[0] * stride;
                 bool w = false;
-                if (!launch_attn_prefill(dqp + off, dk.as<__half>() + cs, dv.as<__half>() + cs, g[2], n_head, hd, ds.as<int>() + 4 * i + 3, g[3] + g[2], tb, out + off, nullptr,
+                if (!launch_attn_prefill(dqp + off, dk.as<__half>() + cs, dv.as<__half>() + cs, g[2], n_head, hd, ds.as<int>() + 4 * i + 3, g[3] + g[2], tb, out + off, tune, nullptr,
                                          out_h ? out_h + off : nullptr, &w)) return false;
                 if (all_h) *all_h = *all_h && w;
             }
             return true;
         };
         bool seg_h = false, ref_h = false;
-        const bool one = launch_attn_prefill_seg(dqp, dk.as<__half>(), dv.as<__half>(), sg, n_head, hd, tb, da.as<float>(), nullptr, want_h ? dha.as<__half>() : nullptr, &seg_h);
+        const bool one = launch_attn_prefill_seg(dqp, dk.as<__half>(), dv.as<__half>(), sg, n_head, hd, tb, da.as<float>(), tune, nullptr, want_h ? dha.as<__half>() : nullptr, &seg_h);
         if (!one && !per_segment(da.as<float>(), want_h ? dha.as<__half>() : nullptr, &seg_h)) return 4;
         if (!per_segment(db.as<float>(), want_h ? dhb.as<__half>() : nullptr, &ref_h)) return 4;
         HIP_CHECK(hipDeviceSynchronize());
@@ -1694,7 +1697,6 @@ int minigpt4_amd_test_rope_kv_seg(int n_head, int hd, int n_ctx, int n_slots, in
 }
 // Micro-benchmark of the prompt-row attention (launch_attn_prefill): N query rows at positions n_past .. n_past + N - 1 of an fp16 K / V cache filled with synthetic rows
 int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int iters, float *us_per_launch) {
-    if (const char *w8 = getenv("MINIGPT4_ATTN_PREFILL_W8")) set_attn_prefill_w8(atoi(w8));        // micro-benchmark only (no engine in this process)
     if (n_head < 1 || !attn_head_size_supported(hd) || N < 2 || n_past < 0 || iters < 1) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -1707,7 +1709,10 @@ int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int i
         HIP_CHECK(hipMemcpy(dnp.p, &n_past, 4, hipMemcpyHostToDevice));
         Tables tb; tb.exp = dtab.as<__half>();
         { int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if (__half2float(__float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)c))))) == 0.0f) break; nneg++; } tb.exp_neg_n = (nneg + 2047) / 2048 * 2048; }
-        auto run = [&]() { return launch_attn_prefill(dq.as<float>(), dk.as<__half>(), dv.as<__half>(), N, n_head, hd, dnp.as<int>(), T, tb, dout.as<float>(), nullptr); };
+        LaunchTuning tune = hook_tuning();
+        if (const char *w8 = getenv("MINIGPT4_ATTN_PREFILL_W8")) tune.attn_prefill_w8 = atoi(w8);      // micro-benchmark only (no engine in this process)
+        tune = tune.normalised();
+        auto run = [&]() { return launch_attn_prefill(dq.as<float>(), dk.as<__half>(), dv.as<__half>(), N, n_head, hd, dnp.as<int>(), T, tb, dout.as<float>(), tune, nullptr); };
         for (int i = 0; i < 3; i++) if (!run()) return 4;
         HIP_CHECK(hipDeviceSynchronize());
         float ms = 0;
@@ -1717,8 +1722,18 @@ int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int i
     });
 }
 int minigpt4_amd_timeline_attn(unsigned long long *out, int max_workgroups) { return (out && max_workgroups > 0) ? read_attn_timeline(out, max_workgroups) : -1; }
-void minigpt4_amd_test_set_gemm_arm(int arm, int sk_arm) { set_gemm_tuning(-1, 0, arm, sk_arm); }
-void minigpt4_amd_test_set_splitk_xcd(int on) { set_gemm_splitk_xcd(on); }
+void minigpt4_amd_test_set_gemm_arm(int arm, int sk_arm) { g_tune.gemm_arm = arm; g_tune.gemm_sk_arm = sk_arm; g_tune = g_tune.normalised(); }
+void minigpt4_amd_test_set_splitk_xcd(int on) { g_tune.splitk_xcd = on; g_tune = g_tune.normalised(); }
+static int tuning_fields(const LaunchTuning &t, int *out, int n) {
+    const int f[MINIGPT4_AMD_TUNING_FIELDS] = {t.cus, t.mv_waves_per_cu, t.mmq, t.mmqh, t.mmq_ks, t.mmq3_waves, t.attn_prefill_w8, t.attn_prefill_f16, t.attn_prefill_form, t.gemm_arm, t.gemm_sk_arm,
+                                               t.f16_ks, t.splitk_xcd, t.attn_vit_qt};
+    if (!out || n < 0) return -1;
+    n = std::min(n, MINIGPT4_AMD_TUNING_FIELDS);
+    std::copy(f, f + n, out);
+    return n;
+}
+int minigpt4_amd_test_tuning_from_env(int cus, int *out, int n) { return tuning_fields(launch_tuning_from_env(cus), out, n); }
+int minigpt4_amd_test_context_tuning(MiniGPT4Context *ctx, int *out, int n) { return ctx ? tuning_fields(E_(ctx)->launch_tuning(), out, n) : -1; }
 int minigpt4_amd_timeline_vision(unsigned long long *out, int max_workgroups) { return (out && max_workgroups > 0) ? read_vision_timeline(out, max_workgroups) : -1; }
 
 // Micro-benchmark of the decode mat-vec kernels on synthetic planes (random quant bytes, sane fp16 scales).  `n_sets` distinct weight sets
@@ -1727,8 +1742,7 @@ int minigpt4_amd_bench_matvec(int ggml_type, int rows, int cols, int n_mat, int 
     if (!qweight_supported(ggml_type) || rows <= 0 || cols <= 0 || cols % gt_block(ggml_type) || n_mat < 1 || n_mat > 3 || iters < 1 || n_sets < 1) return 1;
     if (device_count_noexcept() <= 0) return 2;
     return guarded(3, [&]() -> int {
-        hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0));
-        set_matvec_tuning(waves_per_cu, 0, prop.multiProcessorCount);
+        LaunchTuning tune = hook_tuning(); tune.mv_waves_per_cu = waves_per_cu; tune = tune.normalised();
         QWeight plan; const size_t need = plan_qweight(ggml_type, rows, cols, plan, nullptr);
         std::vector<std::unique_ptr<DevBuf>> keep;
         std::vector<QWeight> W((size_t)n_sets * n_mat);
@@ -1757,12 +1771,12 @@ int minigpt4_amd_bench_matvec(int ggml_type, int rows, int cols, int n_mat, int 
         auto run = [&](int set) {
             const QWeight *Wp[3]; float *Yp[3];
             for (int m = 0; m < n_mat; m++) { Wp[m] = &W[(size_t)set * n_mat + m]; Yp[m] = dy.as<float>() + (size_t)m * rows * NR; }
-            if (variant == 7 && launch_matvec_set(Wp, Yp, Yp, n_mat, A, nullptr, 2, dx.as<float>(), nullptr, nullptr, 0, issue_bar)) return;   // plain prologue + residual in place, as the decode's wo launch
-            if (variant == 1 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, nullptr)) return;
-            if ((variant == 3 || variant == 4 || (variant > 10 && variant <= 14)) && launch_matvec_rows(Wp, Yp, nullptr, n_mat, A, NR, rows, nullptr)) return;
-            if ((variant == 5 || variant == 6 || (variant > 20 && variant <= 24)) && launch_matvec_rows(Wp, Yp, nullptr, n_mat, A, NR, rows, nullptr, dx.as<float>(), dx.as<float>(), cols)) return;
-            if (variant == 2 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, nullptr, 1, dx.as<float>(), dx.as<float>(), nullptr, 0, issue_bar)) return;   // rms-norm prologue, as the decode's qkv / w1|w3 launches
-            for (int m = 0; m < n_mat; m++) launch_mul_mat(*Wp[m], A, 1, Yp[m], rows, nullptr, nullptr);
+            if (variant == 7 && launch_matvec_set(Wp, Yp, Yp, n_mat, A, tune, nullptr, 2, dx.as<float>(), nullptr, nullptr, 0, issue_bar)) return;   // plain prologue + residual in place, as the decode's wo launch
+            if (variant == 1 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, tune, nullptr)) return;
+            if ((variant == 3 || variant == 4 || (variant > 10 && variant <= 14)) && launch_matvec_rows(Wp, Yp, nullptr, n_mat, A, NR, rows, tune, nullptr)) return;
+            if ((variant == 5 || variant == 6 || (variant > 20 && variant <= 24)) && launch_matvec_rows(Wp, Yp, nullptr, n_mat, A, NR, rows, tune, nullptr, dx.as<float>(), dx.as<float>(), cols)) return;
+            if (variant == 2 && launch_matvec_set(Wp, Yp, nullptr, n_mat, A, tune, nullptr, 1, dx.as<float>(), dx.as<float>(), nullptr, 0, issue_bar)) return;   // rms-norm prologue, as the decode's qkv / w1|w3 launches
+            for (int m = 0; m < n_mat; m++) launch_mul_mat(*Wp[m], A, 1, Yp[m], rows, nullptr, tune, nullptr);
         };
         for (int i = 0; i < std::min(n_sets, 4); i++) run(i);
         HIP_CHECK(hipDeviceSynchronize());
@@ -1780,7 +1794,6 @@ int minigpt4_amd_bench_mmq(int ggml_type, int rows, int cols, int n_mat, int N, 
     if (!qweight_supported(ggml_type) || rows <= 0 || cols <= 0 || cols % gt_block(ggml_type) || n_mat < 1 || n_mat > 3 || iters < 1 || N < 1) return 1;
     if (device_count_noexcept() <= 0) return 2;
     return guarded(3, [&]() -> int {
-        hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0));
         QWeight plan; const size_t need = plan_qweight(ggml_type, rows, cols, plan, nullptr);
         std::vector<std::unique_ptr<DevBuf>> keep;
         QWeight W[3];
@@ -1799,31 +1812,27 @@ int minigpt4_amd_bench_mmq(int ggml_type, int rows, int cols, int n_mat, int N, 
         { std::vector<float> hx((size_t)N * cols); for (size_t i = 0; i < hx.size(); i++) hx[i] = (float)((int)(i * 37 % 201) - 100) / 64.0f; HIP_CHECK(hipMemcpy(dx.p, hx.data(), hx.size() * 4, hipMemcpyHostToDevice)); }
         launch_rms_quant(dx.as<float>(), nullptr, N, cols, A, act_mask_for(ggml_type), nullptr);
         A.ws = dws.as<float>(); A.ws_floats = out_each * n_mat * 16;
-        set_mmq2_cus(prop.multiProcessorCount);
-        struct KsScope { KsScope(int k) { set_mmq2_tuning(-1, -1, k); set_mmq3_tuning(-1, k); } ~KsScope() { set_mmq2_tuning(-1, -1, 0); set_mmq3_tuning(-1, 0); } } ks_scope(std::max(0, ks));
-        set_mmq3_tuning(prop.multiProcessorCount, -1);
-        { const char *e = getenv("MMQ3_NW"); set_mmq3_waves(e ? atoi(e) : 8); }
+        LaunchTuning tune = hook_tuning();
+        tune.mmq_ks = ks; tune.mmq = std::min(generation, 2); tune.mmqh = generation == 4;   // 4: the fp16-MFMA form of the Q4_K / Q5_K launches (k_mmqh_q45k), 2: the int8 kernels
+        if (const char *e = getenv("MMQ3_NW")) tune.mmq3_waves = atoi(e);
+        tune = tune.normalised();
         const uint8_t *Pp[3] = {nullptr, nullptr, nullptr};
         if (generation == 3) {
             if (!mmq3_supported(ggml_type, rows, cols)) return 4;
             const size_t pb = mmq3_plane_bytes(rows, cols);
             for (int i = 0; i < n_mat; i++) { keep.emplace_back(new DevBuf(pb)); Pp[i] = (const uint8_t *)keep.back()->p; launch_mmq3_build(W[i], (uint8_t *)keep.back()->p, nullptr); }
         }
-        const int keep_gen = mmq_enabled();
-        set_mmq_enabled(std::min(generation, 2));
-        struct HScope { int keep; HScope(int v) : keep(mmqh_enabled()) { set_mmqh(v); } ~HScope() { set_mmqh(keep); } } h_scope(generation == 4);   // 4: the fp16-MFMA form of the Q4_K / Q5_K launches (k_mmqh_q45k), 2: the int8 kernels
         const QWeight *Wp[3]; float *Yp[3];
         for (int m = 0; m < n_mat; m++) { Wp[m] = &W[m]; Yp[m] = dy.as<float>() + (size_t)m * out_each; }
         auto run = [&]() {
-            if (generation == 3) { if (!launch_mmq3_set(Wp, Pp, Yp, nullptr, n_mat, A, N, rows, nullptr)) throw HipError{hipErrorInvalidValue, "mmq3 refused the shape", __FILE__, __LINE__}; return; }
-            if (generation >= 2 && launch_mmq2_set(Wp, Yp, nullptr, n_mat, A, N, rows, nullptr)) return;
-            for (int m = 0; m < n_mat; m++) launch_mul_mat(*Wp[m], A, N, Yp[m], rows, nullptr, nullptr);
+            if (generation == 3) { if (!launch_mmq3_set(Wp, Pp, Yp, nullptr, n_mat, A, N, rows, tune, nullptr)) throw HipError{hipErrorInvalidValue, "mmq3 refused the shape", __FILE__, __LINE__}; return; }
+            if (generation >= 2 && launch_mmq2_set(Wp, Yp, nullptr, n_mat, A, N, rows, tune, nullptr)) return;
+            for (int m = 0; m < n_mat; m++) launch_mul_mat(*Wp[m], A, N, Yp[m], rows, nullptr, tune, nullptr);
         };
         run(); run();
         HIP_CHECK(hipDeviceSynchronize());
         float ms = 0;
         timed(&ms, [&] { for (int i = 0; i < iters; i++) run(); return true; });
-        set_mmq_enabled(keep_gen);
         if (us_per_launch) *us_per_launch = ms * 1e3f / (float)iters;
         return 0;
     });
@@ -1837,9 +1846,7 @@ namespace mg4 {
 bool mmq3_supported(int, int, int) { return false; }
 size_t mmq3_plane_bytes(int, int, size_t *) { return 0; }
 void launch_mmq3_build(const QWeight &, uint8_t *, hipStream_t) {}
-bool launch_mmq3_set(const QWeight *const *, const uint8_t *const *, float *const *, const float *const *, int, const ActQ &, int, int, hipStream_t, SlabSrc *) { return false; }
-void set_mmq3_waves(int) {}
-void set_mmq3_tuning(int, int) {}
+bool launch_mmq3_set(const QWeight *const *, const uint8_t *const *, float *const *, const float *const *, int, const ActQ &, int, int, const LaunchTuning &, hipStream_t, SlabSrc *) { return false; }
 int probe_tn_mfma(int, int, int, int, int, int, int, float *, float *) { return 5; }
 }
 }  // extern "C++"
@@ -1854,7 +1861,7 @@ int minigpt4_amd_probe_tn_mfma(int rows, int cols, int TN, int iters, int n_sets
 float minigpt4_amd_probe_valu(int op, int waves_per_simd, int iters) {
     if (device_count_noexcept() <= 0 || iters < 1) return -1.0f;
     float ns = -1.0f;
-    guarded(1, [&] { hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0)); set_matvec_tuning(0, 0, prop.multiProcessorCount); ns = probe_valu_ns(op, waves_per_simd, iters, prop.multiProcessorCount); return 0; });
+    guarded(1, [&] { hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, 0)); ns = probe_valu_ns(op, waves_per_simd, iters, prop.multiProcessorCount); return 0; });
     return ns;
 }
 int minigpt4_amd_dist_env(int *world, int *rank, char *id_file, size_t cap, char *err, size_t err_cap) { return parse_dist_env_for_test(world, rank, id_file, cap, err, err_cap); }

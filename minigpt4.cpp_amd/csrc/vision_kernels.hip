@@ -11,7 +11,6 @@
 
 namespace mg4 {
 
-static int g_gemm_arm = 0, g_gemm_sk_arm = 0;   // experiments: force one tile shape for every small-M GEMM / split-K GEMM (MINIGPT4_GEMM_ARM / _SK_ARM, read once by Engine::init); 0 = choose, -2 = the 64x64 launch always, -3 = round 2's kernels everywhere (64x64 tiles, 128x128 large-M kernel)
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 typedef float float16_t __attribute__((ext_vector_type(16)));
 typedef unsigned v4u_g __attribute__((ext_vector_type(4)));
@@ -56,10 +55,8 @@ __device__ __forceinline__ void gemm_out_map(const HeadMajor &hm, int col, int l
 // that share a weight tile sit on one XCD, every XCD gets the same number of workgroups +- 1, and -- round 6 -- an XCD walks ONE K slice (or two neighbouring ones), not
 // all of them.  Rounds 3-5 put the slices in grid.z with the tile list dealt to the XCDs per slice, so every XCD walked every K slice and therefore fetched ALL of A:
 // for the ViT's fc2 (K = 6144, 4 slices) 8 x 3.2 MB at one image and 8 x 12.6 MB (three times an L2) at four -- FETCH_SIZE 47 MB for 20 MB of operands at B = 1,
-// 180 MB for 30 MB at B = 4 (profiles/r06_encode_kernel_table_b1.txt / _b4.txt).  xs = 0 keeps that form (A/B: MINIGPT4_SPLITK_XCD=0).  Which workgroup multiplies a
+// 180 MB for 30 MB at B = 4 (profiles/r06_encode_kernel_table_b1.txt / _b4.txt).  xs = 0 keeps that form (A/B: LaunchTuning::splitk_xcd = 0).  Which workgroup multiplies a
 // (tile, slice) never changes what is computed (slab z = columns [z * k_per_slice, ...)), so results are bit-identical under both mappings.
-static int g_splitk_xcd = 1;                       // 0: split-K slices in grid.z as in rounds 3-5 (read once by Engine::init)
-void set_gemm_splitk_xcd(int on) { g_splitk_xcd = on != 0; }
 __device__ __forceinline__ bool gemm_tile_of_block(int tile_n, int xs, int &tile_id, int &z) {
     const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
     if (xs > 1) {
@@ -72,7 +69,7 @@ __device__ __forceinline__ bool gemm_tile_of_block(int tile_n, int xs, int &tile
     tile_id = xcd * chunk + slot;
     return slot < chunk && tile_id < tile_n;
 }
-static inline bool splitk_on_xcds(int slices) { return g_splitk_xcd && slices > 1; }
+static inline bool splitk_on_xcds(const LaunchTuning &tune, int slices) { return tune.splitk_xcd && slices > 1; }
 static inline unsigned gemm_grid_x(int tile_n, int slices, bool on_xcds) { return (unsigned)(((on_xcds ? slices : 1) * tile_n + 7) / 8 * 8); }
 // =====================================================================================================================
 // C[M][N] = A[M][K] . W[N][K]^T  (+bias, GELU, +residual).  64x64 tile per 256-thread workgroup, 4 waves of 32x32,
@@ -230,10 +227,10 @@ __global__ __launch_bounds__(GB_M / (32 * TM) * (BN / (32 * TN)) * 64) void k_ge
 }
 template <int BK, int BM, int BN, int TM = 1, int TN = 1>
 static void launch_gemm_t(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual, bool gelu, const Tables &tb,
-                          float *out, __half *out_h, int ldo, hipStream_t s, int slices = 1, size_t slab_stride = 0) {
+                          float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s, int slices = 1, size_t slab_stride = 0) {
     const int k_per_slice = slices > 1 ? ((K + BK - 1) / BK + slices - 1) / slices * BK : 0;
     const int ntx = (N + BN - 1) / BN, rt = (M + BM - 1) / BM;
-    const bool sx = splitk_on_xcds(slices);
+    const bool sx = splitk_on_xcds(tune, slices);
     const int xs = sx ? slices : 0;
     dim3 grid(gemm_grid_x(ntx * rt, slices, sx), 1, sx ? 1u : (unsigned)slices), block(BM / (32 * TM) * (BN / (32 * TN)) * 64);
     const size_t lds = (size_t)2 * (BM + BN) * (BK + 8) * 2;
@@ -431,13 +428,13 @@ __global__ __launch_bounds__(BM / (32 * TM) * (BN / (32 * TN)) * 64) void k_gemm
 }
 template <int BM, int BN, int TM, int TN, int KT, int S>
 static bool launch_gemm_dma_t(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual, bool gelu, const Tables &tb,
-                              float *out, __half *out_h, int ldo, hipStream_t s, int slices = 1, size_t slab_stride = 0, GemmSet gs = GemmSet{0, 0, 0, 0, 0, 0}) {
+                              float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s, int slices = 1, size_t slab_stride = 0, GemmSet gs = GemmSet{0, 0, 0, 0, 0, 0}) {
     constexpr int BKS = 64 * KT;
     if (K % BKS || lda % 8 || ldw % 8 || (reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) % 16 || (gs.n_per_mat > 0 && gs.n_per_mat % BN)) return false;
     gs.k_per_slice = slices > 1 ? (K / BKS + slices - 1) / slices * BKS : 0;
     gs.slab_stride = (long long)slab_stride;
     const int ntx = (N + BN - 1) / BN, rt = (M + BM - 1) / BM;
-    const bool sx = splitk_on_xcds(slices) && gs.n_per_mat == 0;
+    const bool sx = splitk_on_xcds(tune, slices) && gs.n_per_mat == 0;
     gs.xs = sx ? slices : 0;
     gs.hm = t_hm;
     dim3 grid(gemm_grid_x(ntx * rt, slices, sx), 1, sx ? 1u : (unsigned)slices), block(BM / (32 * TM) * (BN / (32 * TN)) * 64);
@@ -467,11 +464,11 @@ static bool launch_gemm_dma_pair_t(const __half *A, int lda, const __half *W1, l
 }
 // The feed-forward pair of an F16 language model at prompt sizes: out_h[M][ldo] = fp16(silu_table(A . W1^T) * (A . W3^T)), N columns (rows of W1 / W3), one launch; `out`
 // (optional) receives the fp32 product before the rounding.  false: shape outside this path.
-bool launch_gemm_f16_silu_pair(const __half *A, int lda, const __half *W1, const __half *W3, int M, int N, int K, const Tables &tb, float *out, __half *out_h, int ldo, int cus, hipStream_t s) {
-    if (M < 256 || g_gemm_arm == -3 || W3 <= W1) return false;       // (tb.silu == null: the epilogue computes the table's values)
+bool launch_gemm_f16_silu_pair(const __half *A, int lda, const __half *W1, const __half *W3, int M, int N, int K, const Tables &tb, float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s) {
+    if (M < 256 || tune.gemm_arm == -3 || W3 <= W1) return false;       // (tb.silu == null: the epilogue computes the table's values)
     const long long d = W3 - W1;
     const int wgs128 = (((M + 255) / 256) * ((N + 63) / 64) + 7) / 8 * 8;          // 256x128 tiles carry 64 pair columns
-    if ((wgs128 * 2 > cus * 3 || N % 64) && launch_gemm_dma_pair_t<256, 256, 4, 1, 2>(A, lda, W1, d, K, M, N, K, tb, out, out_h, ldo, s)) return true;
+    if ((wgs128 * 2 > tune.cus * 3 || N % 64) && launch_gemm_dma_pair_t<256, 256, 4, 1, 2>(A, lda, W1, d, K, M, N, K, tb, out, out_h, ldo, s)) return true;
     return launch_gemm_dma_pair_t<256, 128, 2, 1, 3>(A, lda, W1, d, K, M, N, K, tb, out, out_h, ldo, s);
 }
 // =====================================================================================================================
@@ -592,14 +589,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16_big(const __half *__restric
         }
     }
 }
-static int g_gemm_big_min_m = 512;   // smallest M that takes the 128x128 kernel (0 = never); MINIGPT4_GEMM_BIG_M, read once by Engine::init
-static int g_f16_ks = 0;             // forced K split of the F16 set launches (0 = choose); MINIGPT4_F16_KS, read once by Engine::init
-void set_gemm_tuning(int big_min_m, int f16_ks, int arm, int sk_arm) {
-    if (big_min_m >= 0) g_gemm_big_min_m = big_min_m;
-    g_f16_ks = std::max(0, std::min(f16_ks, 8));
-    if (arm >= 0 || arm == -2 || arm == -3) g_gemm_arm = arm;
-    if (sk_arm >= 0) g_gemm_sk_arm = sk_arm;
-}
+constexpr int GEMM_BIG_MIN_M = 512;   // smallest M that takes the 128x128 kernel
 static bool launch_gemm_big(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual, bool gelu, const Tables &tb,
                             float *out, __half *out_h, int ldo, hipStream_t s, const GemmSet gs_in = GemmSet{0, 0, 0, 0, 0}, int slices = 1) {
     GemmSet gs = gs_in; gs.hm = t_hm;
@@ -609,7 +599,7 @@ static bool launch_gemm_big(const __half *A, int lda, const __half *W, int ldw, 
         HIP_IGNORE(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_f16_big<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         HIP_IGNORE(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_f16_big<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
         HIP_IGNORE(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm_f16_big<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); }
-    if (g_gemm_big_min_m <= 0 || M < g_gemm_big_min_m || K % 64 || K < 64 || lda % 8 || ldw % 8 || (reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) % 16) return false;
+    if (M < GEMM_BIG_MIN_M || K % 64 || K < 64 || lda % 8 || ldw % 8 || (reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) % 16) return false;
     const int ntx = (N + 127) / 128, rt = (M + 127) / 128;
     const dim3 grid((unsigned)((ntx * rt + 7) / 8 * 8), (unsigned)slices), block(256);
     const size_t lds = 64 * 1024;
@@ -624,7 +614,7 @@ static bool launch_gemm_big(const __half *A, int lda, const __half *W, int ldw, 
 // ONE launch; y[m] are [M][ldo] fp32 (+ residual[m]).  With fewer column x row tiles than 2 per CU the K range is split (partial slabs in `ws`, combined in fixed
 // order by launch_slab_reduce).  false: shape outside this path (nothing launched) -- the caller multiplies matrix by matrix.
 bool launch_gemm_f16_set(const __half *A, int lda, const __half *const *W, int n, int M, int N, int K, float *const *y, const float *const *residual, int ldo, float *ws,
-                         size_t ws_floats, int cus, hipStream_t s, SlabSrc *defer) {
+                         size_t ws_floats, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer) {
     if (defer) *defer = SlabSrc{};
     if (n < 1 || n > 3 || N % 128 || K % 64) return false;
     const long long wstride = n > 1 ? W[1] - W[0] : 0, ystride = n > 1 ? y[1] - y[0] : 0;
@@ -635,31 +625,31 @@ bool launch_gemm_f16_set(const __half *A, int lda, const __half *const *W, int n
     const size_t out_floats = (size_t)M * ldo;
     // Round 3: 256x128 tiles of the LDS-DMA ring kernel (8 waves of 64x64, three stages, counted waits), with the K range split until the launch has about one
     // workgroup per CU -- 13B at 512 rows: wq|wk|wv 240 workgroups 104 -> 83 us, w1|w3 432 workgroups 199 -> 161 us, wo 80 x 3 slices 63 -> 45 us, w2 139 -> 85 us
-    // (profiles/r03b_gemm_f16_set_512rows.log).  MINIGPT4_GEMM_ARM=-3: the 128x128 kernel below (A/B).
-    if (g_gemm_arm != -3 && M >= 256) {
+    // (profiles/r03b_gemm_f16_set_512rows.log).  LaunchTuning::gemm_arm == -3: the 128x128 kernel below (A/B).
+    if (tune.gemm_arm != -3 && M >= 256) {
         const int wgs = (((M + 255) / 256) * (n * N / 128) + 7) / 8 * 8;   // the tiles are dealt to the 8 XCDs in equal shares
         int ks = 1;
         if (n == 1 && out_floats % 4 == 0)
-            while (wgs * (ks + 1) <= cus && (K / 64) / (ks + 1) >= 16 && ws && (size_t)(ks + 1) * out_floats <= ws_floats && ks < 4) ks++;
-        if (g_f16_ks > 0 && n == 1 && out_floats % 4 == 0 && ws && (size_t)g_f16_ks * out_floats <= ws_floats && (K / 64) / g_f16_ks >= 8) ks = g_f16_ks;   // experiments (MINIGPT4_F16_KS)
+            while (wgs * (ks + 1) <= tune.cus && (K / 64) / (ks + 1) >= 16 && ws && (size_t)(ks + 1) * out_floats <= ws_floats && ks < 4) ks++;
+        if (tune.f16_ks > 0 && n == 1 && out_floats % 4 == 0 && ws && (size_t)tune.f16_ks * out_floats <= ws_floats && (K / 64) / tune.f16_ks >= 8) ks = tune.f16_ks;   // experiments (MINIGPT4_F16_KS)
         const GemmSet gs{n > 1 ? N : 0, wstride, ystride, 0, 0};
         if (ks > 1) {
-            if (launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W[0], K, M, N, K, nullptr, nullptr, false, tb, ws, nullptr, ldo, s, ks, out_floats, gs)) {
+            if (launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W[0], K, M, N, K, nullptr, nullptr, false, tb, ws, nullptr, ldo, tune, s, ks, out_floats, gs)) {
                 if (defer) { defer->ws = ws; defer->ks = ks; defer->stride = (long long)out_floats; defer->n = 1; defer->y[0] = y[0]; defer->res[0] = residual ? residual[0] : nullptr; }   // combined by the consumer
                 else launch_slab_reduce(ws, ks, (long long)out_floats, residual ? residual[0] : nullptr, y[0], out_floats, s);
                 return true;
             }
         } else {
             // far more 256x128 tiles than CUs (w1|w3: 432): 256x256 tiles, 8 waves of 128x64, two stages (216 workgroups: 159 -> 146 us)
-            if (wgs * 2 > cus * 3 && N % 256 == 0 &&
-                launch_gemm_dma_t<256, 256, 4, 2, 1, 2>(A, lda, W[0], K, M, n * N, K, nullptr, residual ? residual[0] : nullptr, false, tb, y[0], nullptr, ldo, s, 1, 0, gs)) return true;
-            if (launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W[0], K, M, n * N, K, nullptr, residual ? residual[0] : nullptr, false, tb, y[0], nullptr, ldo, s, 1, 0, gs)) return true;
+            if (wgs * 2 > tune.cus * 3 && N % 256 == 0 &&
+                launch_gemm_dma_t<256, 256, 4, 2, 1, 2>(A, lda, W[0], K, M, n * N, K, nullptr, residual ? residual[0] : nullptr, false, tb, y[0], nullptr, ldo, tune, s, 1, 0, gs)) return true;
+            if (launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W[0], K, M, n * N, K, nullptr, residual ? residual[0] : nullptr, false, tb, y[0], nullptr, ldo, tune, s, 1, 0, gs)) return true;
         }
     }
     const int tiles = ((M + 127) / 128) * (n * N / 128);
     int ks = 1;
-    while (tiles * ks < 2 * cus && (K / 64) / (ks + 1) >= 16 && ws && (size_t)(ks + 1) * out_floats * n <= ws_floats && ks < 4) ks++;
-    if (g_f16_ks > 0) ks = g_f16_ks;
+    while (tiles * ks < 2 * tune.cus && (K / 64) / (ks + 1) >= 16 && ws && (size_t)(ks + 1) * out_floats * n <= ws_floats && ks < 4) ks++;
+    if (tune.f16_ks > 0) ks = tune.f16_ks;
     if (ks > 1 && (!ws || (size_t)ks * out_floats * n > ws_floats || n > 1 || out_floats % 4)) ks = 1;   // split launches are single-matrix (wo, w2): the sets have tiles enough
     GemmSet gs{n > 1 ? N : 0, wstride, ystride, 0, 0};
     if (ks > 1) {
@@ -793,10 +783,9 @@ bool launch_gemm_f16_skinny(const __half *A, int lda, const __half *W, int ldw, 
     return true;
 }
 void launch_gemm_f16(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual, bool gelu, const Tables &tb,
-                     float *out, __half *out_h, int ldo, hipStream_t s) {
-    static int cus = 0;
-    if (!cus) { hipDeviceProp_t prop; cus = hipGetDeviceProperties(&prop, 0) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; }
-    if (g_gemm_arm > 0 && launch_gemm_f16_arm(g_gemm_arm, A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s)) return;
+                     float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s) {
+    const int cus = tune.cus;
+    if (tune.gemm_arm > 0 && launch_gemm_f16_arm(tune.gemm_arm, A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s)) return;
     // Tile shape by workgroup count (round 3, tools/timeline_gemm.py): a launch lasts as long as ONE workgroup's chain (1.5 us to the first request, ~0.5 us per
     // 128 k, the epilogue) as long as every workgroup has a CU to itself -- a CU pulls only 50-75 GB/s through its load path whatever the kernel does, so the second
     // workgroup of a CU roughly doubles that CU's time (330 tiles of 64x64 on 256 CUs: 16 us; 198 tiles of 128x64: 12.8 us).  Hence: the shape with the MOST
@@ -806,61 +795,61 @@ void launch_gemm_f16(const __half *A, int lda, const __half *W, int ldw, int M, 
     struct Shape { int bm, bn, arm; };
     static const Shape shapes[5] = {{64, 32, 11}, {64, 64, 0}, {128, 64, 31}, {64, 128, 5}, {128, 128, 32}};   // arms of launch_gemm_f16_arm; 0 = the 64x64 launch below
     int pick = -1, pick_n = 0;
-    for (int i = 0; i < 5 && g_gemm_arm == 0; i++) {
+    for (int i = 0; i < 5 && tune.gemm_arm == 0; i++) {
         const int n = (((M + shapes[i].bm - 1) / shapes[i].bm) * ((N + shapes[i].bn - 1) / shapes[i].bn) + 7) / 8 * 8;
         if (pick < 0 || (n <= cus ? (pick_n > cus || n > pick_n) : (pick_n > cus && n < pick_n))) { pick = i; pick_n = n; }
     }
-    if ((pick < 0 || pick_n > cus) && launch_gemm_big(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s)) return;   // M >= 512 (MINIGPT4_GEMM_BIG_M)
+    if ((pick < 0 || pick_n > cus) && launch_gemm_big(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s)) return;   // M >= GEMM_BIG_MIN_M
     if (pick >= 0 && shapes[pick].arm) {
-        if (launch_gemm_f16_arm(shapes[pick].arm, A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s)) return;
-        if (shapes[pick].arm == 31 && launch_gemm_f16_arm(4, A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s)) return;   // K % 64: the register-staged 128x64
+        if (launch_gemm_f16_arm(shapes[pick].arm, A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s)) return;
+        if (shapes[pick].arm == 31 && launch_gemm_f16_arm(4, A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s)) return;   // K % 64: the register-staged 128x64
         if (shapes[pick].arm == 32 && launch_gemm_big(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s)) return;
     }
-    launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);
+    launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);
 }
 // The same GEMM with its fp32 output stored head-major (struct HeadMajor above): N = 3 x D columns -> out[3][D / hd][M][hd].  Every tile shape the dispatcher may pick maps its
 // stores the same way, so the choice still never changes a value or where it lands.
-void launch_gemm_f16_head_major(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const Tables &tb, float *out, int D, int hd, hipStream_t s) {
+void launch_gemm_f16_head_major(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const Tables &tb, float *out, int D, int hd, const LaunchTuning &tune, hipStream_t s) {
     if (D <= 0 || hd <= 0 || D % hd || N % D) throw HipError{hipErrorInvalidValue, "head-major GEMM output: N must be a multiple of D and D of hd", __FILE__, __LINE__};
     struct Scope { Scope(int rows, int D_, int hd_) { t_hm = HeadMajor{rows, D_, hd_}; } ~Scope() { t_hm = HeadMajor{0, 0, 0}; } } scope(M, D, hd);
-    launch_gemm_f16(A, lda, W, ldw, M, N, K, bias, nullptr, false, tb, out, nullptr, N, s);
+    launch_gemm_f16(A, lda, W, ldw, M, N, K, bias, nullptr, false, tb, out, nullptr, N, tune, s);
 }
 
 // tile-shape arms of k_gemm_f16 for the micro-benchmark (test library only calls this): 3 = BK 64, 4 = 128x64 tiles, 5 = 64x128 tiles, 6 = BK 256
 bool launch_gemm_f16_arm(int arm, const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, const float *bias, const float *residual, bool gelu, const Tables &tb,
-                         float *out, __half *out_h, int ldo, hipStream_t s) {
+                         float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s) {
     switch (arm) {
-    case 3: launch_gemm_t<64, 64, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;
-    case 4: launch_gemm_t<128, 128, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;          // 8 waves, one tile each
-    case 5: launch_gemm_t<128, 64, 128>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;
-    case 7: launch_gemm_t<128, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;    // 4 waves of 64x32
-    case 8: launch_gemm_t<64, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;
-    case 9: launch_gemm_t<128, 64, 128, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;    // 4 waves of 32x64
-    case 10: launch_gemm_t<64, 64, 128, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;
-    case 11: launch_gemm_t<128, 64, 32>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;          // 2 waves
-    case 12: launch_gemm_t<64, 64, 32>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;
-    case 13: launch_gemm_t<64, 128, 128, 2, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;   // 4 waves of 64x64
-    case 14: launch_gemm_t<128, 32, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;          // 2 waves, 32 rows
-    case 20: return launch_gemm_dma_t<64, 64, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);     // 64 KB: two workgroups per CU
-    case 21: return launch_gemm_dma_t<64, 64, 1, 1, 2, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);     // 96 KB
-    case 22: return launch_gemm_dma_t<64, 64, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);     // 128 KB
-    case 23: return launch_gemm_dma_t<128, 64, 2, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);    // 96 KB, 4 waves of 64x32
-    case 24: return launch_gemm_dma_t<128, 64, 2, 1, 2, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);    // 144 KB
-    case 25: return launch_gemm_dma_t<64, 128, 1, 2, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);    // 4 waves of 32x64
-    case 26: return launch_gemm_dma_t<64, 128, 1, 2, 2, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);
-    case 27: return launch_gemm_dma_t<64, 32, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);     // 2 waves, 48 KB
-    case 28: return launch_gemm_dma_t<64, 32, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);     // 2 waves, 96 KB
-    case 29: return launch_gemm_dma_t<32, 64, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);     // 2 waves, 32 rows
-    case 30: return launch_gemm_dma_t<128, 128, 2, 2, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);   // 4 waves of 64x64, 128 KB
-    case 31: return launch_gemm_dma_t<128, 64, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);    // 8 waves of 32x32
-    case 32: return launch_gemm_dma_t<128, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);   // the large-M tile with 3 / 2 stages
-    case 33: return launch_gemm_dma_t<128, 128, 2, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);
-    case 34: return launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);   // 8 waves of 64x64, 144 KB
-    case 35: return launch_gemm_dma_t<128, 256, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);
-    case 36: return launch_gemm_dma_t<256, 128, 2, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);   // 96 KB
-    case 38: return launch_gemm_dma_t<256, 256, 2, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);   // 16 waves of 64x64, 128 KB
-    case 39: return launch_gemm_dma_t<256, 256, 4, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s);   // 8 waves of 128x64
-    case 37: launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, s); return true;          // the 64x64 launch
+    case 3: launch_gemm_t<64, 64, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;
+    case 4: launch_gemm_t<128, 128, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;          // 8 waves, one tile each
+    case 5: launch_gemm_t<128, 64, 128>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;
+    case 7: launch_gemm_t<128, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;    // 4 waves of 64x32
+    case 8: launch_gemm_t<64, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;
+    case 9: launch_gemm_t<128, 64, 128, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;    // 4 waves of 32x64
+    case 10: launch_gemm_t<64, 64, 128, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;
+    case 11: launch_gemm_t<128, 64, 32>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;          // 2 waves
+    case 12: launch_gemm_t<64, 64, 32>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;
+    case 13: launch_gemm_t<64, 128, 128, 2, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;   // 4 waves of 64x64
+    case 14: launch_gemm_t<128, 32, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;          // 2 waves, 32 rows
+    case 20: return launch_gemm_dma_t<64, 64, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);     // 64 KB: two workgroups per CU
+    case 21: return launch_gemm_dma_t<64, 64, 1, 1, 2, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);     // 96 KB
+    case 22: return launch_gemm_dma_t<64, 64, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);     // 128 KB
+    case 23: return launch_gemm_dma_t<128, 64, 2, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);    // 96 KB, 4 waves of 64x32
+    case 24: return launch_gemm_dma_t<128, 64, 2, 1, 2, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);    // 144 KB
+    case 25: return launch_gemm_dma_t<64, 128, 1, 2, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);    // 4 waves of 32x64
+    case 26: return launch_gemm_dma_t<64, 128, 1, 2, 2, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);
+    case 27: return launch_gemm_dma_t<64, 32, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);     // 2 waves, 48 KB
+    case 28: return launch_gemm_dma_t<64, 32, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);     // 2 waves, 96 KB
+    case 29: return launch_gemm_dma_t<32, 64, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);     // 2 waves, 32 rows
+    case 30: return launch_gemm_dma_t<128, 128, 2, 2, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);   // 4 waves of 64x64, 128 KB
+    case 31: return launch_gemm_dma_t<128, 64, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);    // 8 waves of 32x32
+    case 32: return launch_gemm_dma_t<128, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);   // the large-M tile with 3 / 2 stages
+    case 33: return launch_gemm_dma_t<128, 128, 2, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);
+    case 34: return launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);   // 8 waves of 64x64, 144 KB
+    case 35: return launch_gemm_dma_t<128, 256, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);
+    case 36: return launch_gemm_dma_t<256, 128, 2, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);   // 96 KB
+    case 38: return launch_gemm_dma_t<256, 256, 2, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);   // 16 waves of 64x64, 128 KB
+    case 39: return launch_gemm_dma_t<256, 256, 4, 2, 1, 2>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s);   // 8 waves of 128x64
+    case 37: launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, bias, residual, gelu, tb, out, out_h, ldo, tune, s); return true;          // the 64x64 launch
     default: return false;
     }
 }
@@ -881,37 +870,37 @@ __device__ __forceinline__ double block_sum_d(double v, double *red) {
 // (The slice count must not depend on the number of rows: image b of a batch has to equal the same image encoded alone bit for bit, and the slices fix the order in
 // which an output element's k ranges are added.  4 images' fc2 would prefer 3 slices of 256x128 tiles -- 61 -> 48 us, profiles/r03b_gemm_batched_encode.log -- not taken.)
 int gemm_split_slices(int K, int want) { const int nk = (K + 127) / 128; int s = std::max(1, std::min(want, nk)); const int per = (nk + s - 1) / s; return (nk + per - 1) / per; }
-void launch_gemm_f16_splitk(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, hipStream_t s) {
+void launch_gemm_f16_splitk(const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, const LaunchTuning &tune, hipStream_t s) {
     Tables tb{};
-    if (g_gemm_sk_arm && launch_gemm_f16_splitk_arm(g_gemm_sk_arm, A, lda, W, ldw, M, N, K, slices, slabs, slab_stride, ldo, s)) return;
+    if (tune.gemm_sk_arm && launch_gemm_f16_splitk_arm(tune.gemm_sk_arm, A, lda, W, ldw, M, N, K, slices, slabs, slab_stride, ldo, tune, s)) return;
     // Several images per pass (round 6): the LDS-DMA ring tiles of the language model's prompt GEMMs -- 256x128 from three images on, 128x128 at two -- instead of 64x64
     // tiles: the ViT's fc2 at four images 43 -> 30 us (profiles/r06_gemm_batched_tile_sweep.log: with the reduce 55.5 -> 42.4 us at M = 1028, 46.2 -> 40.2 at 771,
     // 36.4 -> 30.2 at 514, 109.7 -> 75.4 at 2056).  Only when both forms cut K at the same columns (the 64x64 form counts slices in 128-wide k tiles, the ring in 64-wide
     // ones): the slice boundaries fix the order in which an output's k ranges are added, and image b of a batch must equal the same image encoded alone bit for bit.
     const int kps128 = slices > 1 ? ((K + 127) / 128 + slices - 1) / slices * 128 : 0, kps64 = slices > 1 && K % 64 == 0 ? (K / 64 + slices - 1) / slices * 64 : -1;
-    if (g_gemm_arm == 0 && kps128 == kps64) {
-        if (M >= 640 && launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride)) return;
-        if (M >= 384 && launch_gemm_dma_t<128, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride)) return;
+    if (tune.gemm_arm == 0 && kps128 == kps64) {
+        if (M >= 640 && launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride)) return;
+        if (M >= 384 && launch_gemm_dma_t<128, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride)) return;
     }
-    launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
+    launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
 }
-bool launch_gemm_f16_splitk_arm(int arm, const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, hipStream_t s) {
+bool launch_gemm_f16_splitk_arm(int arm, const __half *A, int lda, const __half *W, int ldw, int M, int N, int K, int slices, float *slabs, size_t slab_stride, int ldo, const LaunchTuning &tune, hipStream_t s) {
     Tables tb{};
     switch (arm) {   // micro-benchmark arms (slices counted in whole k tiles of the arm's BK by launch_gemm_t)
-    case 0: launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 3: launch_gemm_t<64, 64, 64>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 7: launch_gemm_t<128, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 8: launch_gemm_t<64, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 11: launch_gemm_t<128, 64, 32>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 12: launch_gemm_t<64, 64, 32>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 13: launch_gemm_t<64, 128, 128, 2, 2>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride); return true;
-    case 20: return launch_gemm_dma_t<64, 64, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
-    case 21: return launch_gemm_dma_t<64, 64, 1, 1, 2, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
-    case 23: return launch_gemm_dma_t<128, 64, 2, 1, 1, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
-    case 27: return launch_gemm_dma_t<64, 32, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
-    case 28: return launch_gemm_dma_t<64, 32, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
-    case 32: return launch_gemm_dma_t<128, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
-    case 34: return launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, s, slices, slab_stride);
+    case 0: launch_gemm_t<128, 64, 64>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 3: launch_gemm_t<64, 64, 64>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 7: launch_gemm_t<128, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 8: launch_gemm_t<64, 128, 64, 2, 1>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 11: launch_gemm_t<128, 64, 32>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 12: launch_gemm_t<64, 64, 32>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 13: launch_gemm_t<64, 128, 128, 2, 2>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride); return true;
+    case 20: return launch_gemm_dma_t<64, 64, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
+    case 21: return launch_gemm_dma_t<64, 64, 1, 1, 2, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
+    case 23: return launch_gemm_dma_t<128, 64, 2, 1, 1, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
+    case 27: return launch_gemm_dma_t<64, 32, 1, 1, 1, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
+    case 28: return launch_gemm_dma_t<64, 32, 1, 1, 2, 4>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
+    case 32: return launch_gemm_dma_t<128, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
+    case 34: return launch_gemm_dma_t<256, 128, 2, 2, 1, 3>(A, lda, W, ldw, M, N, K, nullptr, nullptr, false, tb, slabs, nullptr, ldo, tune, s, slices, slab_stride);
     default: return false;
     }
 }
@@ -1313,10 +1302,8 @@ __global__ __launch_bounds__(256) void k_attn_vit(const float *__restrict__ q, i
 }
 
 // ViT / BERT attention (fp32 scores and outputs on the exact-f32 matrix cores, k_attn_vit).  nk <= 320 keys (the reference's graphs have 257 or 32).
-static int g_attn_qt = 0;                          // forced query tiles per workgroup (0 = choose); experiments / A-B only (set_attn_vit_qt)
-void set_attn_vit_qt(int qt) { g_attn_qt = qt < 0 ? 0 : qt; }
 void launch_attn_f32(const float *q, int ldq, const float *k, const float *v, int ldk, int nq, int nk, int heads, int hd, float q_prescale, float score_div,
-                     const Tables &tb, float *out, __half *out_h, int ldo, hipStream_t s, int batch, int hsq, int hsk) {
+                     const Tables &tb, float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s, int batch, int hsq, int hsk) {
     if (hsq <= 0) hsq = hd;
     if (hsk <= 0) hsk = hd;
     static bool attr_set = false;
@@ -1333,10 +1320,10 @@ void launch_attn_f32(const float *q, int ldq, const float *k, const float *v, in
     // measured against the single-tile kernel inside the encoder (profiles/r06_attn_query_tiles.log): 2 images 5.51 vs 5.41 ms, 4 images 7.65 vs 7.70, 8 images 13.05 vs
     // 12.81, one image 4.03 (qt 2) vs 3.91 -- no gain: the K / V / next-Q registers it keeps live (256 + 84 AGPRs, one workgroup per CU) cost what the saved rounds bring.
     // What DID pay in that experiment: the exponential mode as a template parameter (190 -> 161 registers on the single-tile kernel: 4.00 -> 3.91 ms, 8.47 -> 8.05 with
-    // the fc2 ring tiles).  MINIGPT4_ATTN_QT forces a tile count (A/B, bit-identical: tests/test_gpu_parity.py).
+    // the fc2 ring tiles).  LaunchTuning::attn_vit_qt (MINIGPT4_ATTN_QT) forces a tile count (A/B, bit-identical: tests/test_gpu_parity.py).
     const int tiles = (nq + 15) / 16;
     int qt = 1;
-    if (g_attn_qt > 0) qt = std::min(g_attn_qt, tiles);
+    if (tune.attn_vit_qt > 0) qt = std::min(tune.attn_vit_qt, tiles);
     if (hd == 64 && nk <= 64) qt = 1;                                       // the Q-Former's self-attention (32 x 32): the short-key instantiation has no looping form
     const bool comp = tb.exp == nullptr;
     dim3 grid((unsigned)heads, (unsigned)((tiles + qt - 1) / qt), (unsigned)batch);

@@ -820,9 +820,7 @@ def test_round6_encoder_arms_are_bit_identical_at_full_size(gpu_lib, monkeypatch
     imgs = [G.synth_image(60 + i) for i in range(3)]
 
     def run(env):
-        for k in ("MINIGPT4_SPLITK_XCD", "MINIGPT4_ATTN_QT"):          # these two switches are process-wide: every arm sets both
-            monkeypatch.setenv(k, env.get(k, "1" if k == "MINIGPT4_SPLITK_XCD" else "0"))
-        for k in ("MINIGPT4_QF_FOLD", "MINIGPT4_KV_HOIST", "MINIGPT4_QF_SPLITK", "MINIGPT4_QKV_HEAD_MAJOR"):   # per context
+        for k in ("MINIGPT4_SPLITK_XCD", "MINIGPT4_ATTN_QT", "MINIGPT4_QF_FOLD", "MINIGPT4_KV_HOIST", "MINIGPT4_QF_SPLITK", "MINIGPT4_QKV_HEAD_MAJOR"):   # each read per context, at load: an arm sets only what it names
             if k in env:
                 monkeypatch.setenv(k, env[k])
             else:
