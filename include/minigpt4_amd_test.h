@@ -365,6 +365,38 @@ MINIGPT4_API int minigpt4_amd_test_attn_vsplit(int form, int vs, int n_head, int
  * outside 2 .. 16, mode 1 without q_rot), 2 = no device, 3 = HIP error */
 MINIGPT4_API int minigpt4_amd_test_attn_rows(int mode, int n_head, int hd, int n_ctx, int n_past, int rows, int splits, int computed_exp, const float *q, const float *k,
                                              const float *v, uint16_t *kc, uint16_t *vc, float *q_rot, float *out);
+/* ---- the greedy step epilogues alone (tests/test_gpu_step_epilogue.py): the kernels that end a decode step, a batched step, a packed prompt chunk and a greedy verify
+ * pass, one launcher call each.  THE RULE all of them follow ("first maximum wins"): the id is the lowest index i with row[i] equal to the maximum over the row's
+ * non-NaN entries, when that maximum is above -inf; otherwise (every entry NaN or -inf) it is 0.  A NaN is never chosen (`v > best` is false for it), -0.0 and +0.0
+ * are equal (the lower index wins), and the 0x7FFFFFFF "nothing seen" index turns into id 0.  tests/greedy_ref.py: first_max.
+ * Common form: 1 = bad arguments, before any device is looked for; 2 = no device; 3 = HIP error.  Every device output is prefilled with 0xFF bytes or holds what the
+ * caller gave; every state array carries one guard word (logits: one guard row) behind its last slot, given by the caller and returned with the rest. */
+/* ONE launch_argmax (k_argmax_part over 64 workgroups + k_argmax_final) on logits[n] with a 512-byte scratch, as the engine gives it.  *out = the id;
+ * partial_values_out / partial_ids_out [64] (either may be NULL) = what each workgroup of the first launch left in the scratch (fp32 values; 0x7FFFFFFF = saw nothing).
+ * Refused: NULL logits / out, n < 1, n > 2^24 */
+MINIGPT4_API int minigpt4_amd_test_argmax(const float *logits, int n, int32_t *out, float *partial_values_out, int32_t *partial_ids_out);
+/* form 0: ONE launch_batch_finish, row_slot_or_fin = row_slot[rows]; form 1: ONE launch_seg_finish, row_slot_or_fin = fin[rows][2] = (slot, new position).
+ * logits [rows][n_vocab]; n_past_io / argmax_io / feed_io [n_slot + 1] words and slot_logits_io [n_slot + 1][n_vocab] are uploaded, and returned after the launch (the
+ * last word / row is the guard).  Refused: a NULL array, form not 0 / 1, rows outside 1 .. 64, n_vocab outside 1 .. 2^20, n_slot outside rows .. 4096, a slot outside
+ * [0, n_slot) or named twice */
+MINIGPT4_API int minigpt4_amd_test_step_finish(int form, const float *logits, int rows, int n_vocab, int n_slot, const int32_t *row_slot_or_fin, int32_t *n_past_io,
+                                               int32_t *argmax_io, int32_t *feed_io, float *slot_logits_io);
+/* ONE launch_draft_finish (k_draft_argmax over the R rows, then k_draft_finish) on logits [R][n_vocab] with the pass's row tokens tok[R] (tok[0] is not compared) for
+ * conversation `slot`.  State arrays as above.  res_out [1 + 8 + 1] words: m, the rows' ids, the 0xFF fill behind R, and a guard word behind the launcher's nine.
+ * Refused: a NULL array, R outside 1 .. 8 (the launcher's own throw is never reached), n_vocab outside 1 .. 2^20, n_slot outside 1 .. 4096, slot outside [0, n_slot) */
+MINIGPT4_API int minigpt4_amd_test_draft_finish(const float *logits, int R, int n_vocab, const int32_t *tok, int n_slot, int slot, int32_t *n_past_io, int32_t *argmax_io,
+                                                int32_t *feed_io, float *slot_logits_io, int32_t *res_out);
+/* The one-thread / one-wave bookkeeping launches on state arrays as above (all three are uploaded and returned, whichever the launch can reach).
+ * form 0: ONE launch_advance(n_past + slot, n, with_tok0 ? feed + slot : NULL, argmax + slot), slot = row_slot[0]; row_pos is not used (may be NULL).
+ * form 1: ONE launch_batch_begin(n_past, row_slot, row_pos, B = n), B in 1 .. 64, the slots distinct.
+ * form 2: ONE launch_draft_begin(n_past, row_slot, row_pos): one slot, one position; n is not used.
+ * Refused: a NULL array (row_pos: forms 1 / 2), form not 0 .. 2, n_slot outside 1 .. 4096, a slot outside [0, n_slot) or named twice, form 1 with n outside 1 .. 64 or
+ * n > n_slot */
+MINIGPT4_API int minigpt4_amd_test_step_words(int form, int n_slot, int n, const int32_t *row_slot, const int32_t *row_pos, int with_tok0, int32_t *n_past_io,
+                                              int32_t *argmax_io, int32_t *feed_io);
+/* ONE launch_gather_rows: dst[r] = src[idx[r]], rows of E floats, src [n_src][E], idx [n].  dst_out [n + 1][E]: prefilled with 0xFF bytes, row n is a guard row.
+ * Refused: a NULL array, n_src / n outside 1 .. 65536, E outside 1 .. 2^20, an idx entry outside [0, n_src) */
+MINIGPT4_API int minigpt4_amd_test_gather_rows(const float *src, int n_src, const int32_t *idx, int n, int E, float *dst_out);
 
 /* ---- host-only logic (no GPU needed) -------------------------------------------------------------------------------- */
 /* the n-gram drafter of minigpt4_amd_decode_lookup alone (csrc/draft.cpp): the draft for a history of n tokens, at most n_draft tokens into out; returns its length

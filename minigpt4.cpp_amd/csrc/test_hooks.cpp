@@ -1653,6 +1653,140 @@ int minigpt4_amd_test_ngram_draft(const int32_t *history, int n, int ngram_max, 
     d.reset(history, n);
     return d.draft(n_draft, out);
 }
+// ---- the greedy step epilogues alone (llm_kernels.hip: launch_argmax / _advance, launch_batch_begin / _finish, launch_gather_rows / _seg_finish, launch_draft_begin / _finish) ----
+// THE RULE every one of them follows ("first maximum wins"): the id is the lowest index i with row[i] equal to the maximum over the row's non-NaN entries, when that
+// maximum is above -inf; otherwise (every entry NaN or -inf) it is 0.  The kernels reach it by a `v > best` sweep from best = -inf (false for a NaN, false for a second
+// equal value: each thread keeps the first of its own), argmax_combine's "greater, or equal with the lower index" between threads, waves and workgroups, and the
+// 0x7FFFFFFF "nothing seen" index that the last step turns into id 0.  tests/greedy_ref.py states the same rule in numpy.
+// Every hook: plain host arrays in, every state array [n_slot + 1] words / [n_slot + 1][n_vocab] floats with the caller's guard behind the last slot, uploaded, returned
+// after the launch.  Everything that indexes device memory is checked here, before a device is looked for.
+static constexpr int SE_MAX_SLOTS = 4096, SE_MAX_VOCAB = 1 << 20;             // sanity caps of the hooks' allocations
+static bool se_slots_ok(const int32_t *slots, int n, int stride, int n_slot) {   // n slots, `stride` words apart, each inside [0, n_slot) and named once
+    std::vector<char> seen((size_t)n_slot, 0);
+    for (int r = 0; r < n; r++) { const int s = slots[(size_t)r * stride]; if (s < 0 || s >= n_slot || seen[(size_t)s]) return false; seen[(size_t)s] = 1; }
+    return true;
+}
+namespace {
+// n_past | argmax | feed [n_slot + 1] each and the slots' logits rows [n_slot + 1][n_vocab] (n_vocab 0: none) on the device, from and back to the caller's arrays
+struct StepState {
+    size_t words, keep_bytes; DevBuf dn, da, df, dk;
+    StepState(int n_slot, int n_vocab) : words((size_t)n_slot + 1), keep_bytes(words * (size_t)n_vocab * 4), dn(words * 4), da(words * 4), df(words * 4), dk(std::max<size_t>(keep_bytes, 4)) {}
+    void upload(const int32_t *n_past, const int32_t *argmax, const int32_t *feed, const float *keep) {
+        HIP_CHECK(hipMemcpy(dn.p, n_past, words * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(da.p, argmax, words * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(df.p, feed, words * 4, hipMemcpyHostToDevice));
+        if (keep_bytes) HIP_CHECK(hipMemcpy(dk.p, keep, keep_bytes, hipMemcpyHostToDevice));
+    }
+    void download(int32_t *n_past, int32_t *argmax, int32_t *feed, float *keep) {
+        HIP_CHECK(hipMemcpy(n_past, dn.p, words * 4, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(argmax, da.p, words * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(feed, df.p, words * 4, hipMemcpyDeviceToHost));
+        if (keep_bytes) HIP_CHECK(hipMemcpy(keep, dk.p, keep_bytes, hipMemcpyDeviceToHost));
+    }
+};
+}
+// ONE launch_argmax on logits[n] with the engine's 512-byte scratch (64 partial values, then 64 partial ids), prefilled with 0xFF bytes; the partials come back
+int minigpt4_amd_test_argmax(const float *logits, int n, int32_t *out, float *partial_values_out, int32_t *partial_ids_out) {
+    if (!logits || !out || n < 1 || n > (1 << 24)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        DevBuf dl((size_t)n * 4), ds(512), dout(2 * 4);                        // dout: the id and a guard word
+        HIP_CHECK(hipMemcpy(dl.p, logits, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(ds.p, 0xFF, 512)); HIP_CHECK(hipMemset(dout.p, 0xFF, 8));
+        launch_argmax(dl.as<float>(), n, dout.as<int>(), ds.p, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        int32_t o[2]; HIP_CHECK(hipMemcpy(o, dout.p, 8, hipMemcpyDeviceToHost));
+        if (o[1] != -1) { set_last_error("launch_argmax wrote behind its output word"); return 3; }
+        *out = o[0];
+        if (partial_values_out) HIP_CHECK(hipMemcpy(partial_values_out, ds.p, 256, hipMemcpyDeviceToHost));
+        if (partial_ids_out) HIP_CHECK(hipMemcpy(partial_ids_out, static_cast<const char *>(ds.p) + 256, 256, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+// form 0: ONE launch_batch_finish with row_slot[rows]; form 1: ONE launch_seg_finish with fin[rows][2] = (slot, new position)
+int minigpt4_amd_test_step_finish(int form, const float *logits, int rows, int n_vocab, int n_slot, const int32_t *row_slot_or_fin, int32_t *n_past_io, int32_t *argmax_io,
+                                  int32_t *feed_io, float *slot_logits_io) {
+    if (!logits || !row_slot_or_fin || !n_past_io || !argmax_io || !feed_io || !slot_logits_io || (form != 0 && form != 1) || rows < 1 || rows > Engine::MAX_CONVERSATIONS ||
+        n_vocab < 1 || n_vocab > SE_MAX_VOCAB || n_slot < rows || n_slot > SE_MAX_SLOTS) return 1;
+    if (!se_slots_ok(row_slot_or_fin, rows, form == 0 ? 1 : 2, n_slot)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)rows * n_vocab, nd = (size_t)rows * (form == 0 ? 1 : 2);
+        DevBuf dl(n * 4), dd(nd * 4);
+        StepState st(n_slot, n_vocab);
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dd.p, row_slot_or_fin, nd * 4, hipMemcpyHostToDevice));
+        st.upload(n_past_io, argmax_io, feed_io, slot_logits_io);
+        if (form == 0) launch_batch_finish(dl.as<float>(), n_vocab, rows, dd.as<int>(), st.dn.as<int>(), st.da.as<int>(), st.df.as<int>(), st.dk.as<float>(), nullptr);
+        else launch_seg_finish(dl.as<float>(), n_vocab, rows, dd.as<int>(), st.dn.as<int>(), st.da.as<int>(), st.df.as<int>(), st.dk.as<float>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        st.download(n_past_io, argmax_io, feed_io, slot_logits_io);
+        return 0;
+    });
+}
+// ONE launch_draft_finish (both kernels).  res_out [1 + DRAFT_ROWS + 1]: the launcher's nine words prefilled with 0xFF bytes, and a guard word behind them
+int minigpt4_amd_test_draft_finish(const float *logits, int R, int n_vocab, const int32_t *tok, int n_slot, int slot, int32_t *n_past_io, int32_t *argmax_io, int32_t *feed_io,
+                                   float *slot_logits_io, int32_t *res_out) {
+    if (!logits || !tok || !n_past_io || !argmax_io || !feed_io || !slot_logits_io || !res_out || R < 1 || R > DRAFT_ROWS || n_vocab < 1 || n_vocab > SE_MAX_VOCAB || n_slot < 1 ||
+        n_slot > SE_MAX_SLOTS || slot < 0 || slot >= n_slot) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)R * n_vocab, NR = 1 + DRAFT_ROWS + 1;
+        DevBuf dl(n * 4), dtok(DRAFT_ROWS * 4), dslot(4), dres(NR * 4);
+        StepState st(n_slot, n_vocab);
+        int t[DRAFT_ROWS]; for (int r = 0; r < DRAFT_ROWS; r++) t[r] = r < R ? tok[r] : -1;
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dtok.p, t, sizeof(t), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dslot.p, &slot, 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemset(dres.p, 0xFF, NR * 4));
+        st.upload(n_past_io, argmax_io, feed_io, slot_logits_io);
+        launch_draft_finish(dl.as<float>(), n_vocab, R, dtok.as<int>(), dslot.as<int>(), st.dn.as<int>(), st.da.as<int>(), st.df.as<int>(), st.dk.as<float>(), dres.as<int>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        st.download(n_past_io, argmax_io, feed_io, slot_logits_io);
+        HIP_CHECK(hipMemcpy(res_out, dres.p, NR * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+// The bookkeeping launches.  form 0: launch_advance on slot row_slot[0]'s words; 1: launch_batch_begin over n rows; 2: launch_draft_begin
+int minigpt4_amd_test_step_words(int form, int n_slot, int n, const int32_t *row_slot, const int32_t *row_pos, int with_tok0, int32_t *n_past_io, int32_t *argmax_io,
+                                 int32_t *feed_io) {
+    if (!row_slot || !n_past_io || !argmax_io || !feed_io || form < 0 || form > 2 || n_slot < 1 || n_slot > SE_MAX_SLOTS) return 1;
+    if (form != 0 && !row_pos) return 1;
+    if (form == 1 && (n < 1 || n > Engine::MAX_CONVERSATIONS || n > n_slot)) return 1;
+    const int B = form == 1 ? n : 1;
+    if (!se_slots_ok(row_slot, B, 1, n_slot)) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        DevBuf ds((size_t)B * 4), dp((size_t)B * 4);
+        StepState st(n_slot, 0);
+        HIP_CHECK(hipMemcpy(ds.p, row_slot, (size_t)B * 4, hipMemcpyHostToDevice));
+        if (row_pos) HIP_CHECK(hipMemcpy(dp.p, row_pos, (size_t)B * 4, hipMemcpyHostToDevice));
+        st.upload(n_past_io, argmax_io, feed_io, nullptr);
+        const int slot = row_slot[0];
+        if (form == 0) launch_advance(st.dn.as<int>() + slot, n, with_tok0 ? st.df.as<int>() + slot : nullptr, st.da.as<int>() + slot, nullptr);
+        else if (form == 1) launch_batch_begin(st.dn.as<int>(), ds.as<int>(), dp.as<int>(), B, nullptr);
+        else launch_draft_begin(st.dn.as<int>(), ds.as<int>(), dp.as<int>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        st.download(n_past_io, argmax_io, feed_io, nullptr);
+        return 0;
+    });
+}
+// ONE launch_gather_rows: dst_out [n + 1][E], prefilled with 0xFF bytes, row n is a guard row
+int minigpt4_amd_test_gather_rows(const float *src, int n_src, const int32_t *idx, int n, int E, float *dst_out) {
+    if (!src || !idx || !dst_out || n_src < 1 || n_src > (1 << 16) || n < 1 || n > (1 << 16) || E < 1 || E > SE_MAX_VOCAB) return 1;
+    for (int r = 0; r < n; r++) if (idx[r] < 0 || idx[r] >= n_src) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t ns = (size_t)n_src * E, nd = ((size_t)n + 1) * E;
+        DevBuf dsrc(ns * 4), di((size_t)n * 4), dd(nd * 4);
+        HIP_CHECK(hipMemcpy(dsrc.p, src, ns * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(di.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dd.p, 0xFF, nd * 4));
+        launch_gather_rows(dsrc.as<float>(), di.as<int>(), n, E, dd.as<float>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(dst_out, dd.p, nd * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 int minigpt4_amd_test_rope_kv_seg(int n_head, int hd, int n_ctx, int n_slots, int n_seg, const int32_t *segs, const float *q, const float *k, const float *v, int ks,
                                   float *q_seg, uint16_t *kc_seg, uint16_t *vc_seg, float *q_ref, uint16_t *kc_ref, uint16_t *vc_ref) {
     std::vector<int> st; int N = 0, t_max = 0;

@@ -340,6 +340,11 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
+        L.minigpt4_amd_test_argmax.argtypes = [FLOAT_PTR, I32, INT_PTR, FLOAT_PTR, INT_PTR]
+        L.minigpt4_amd_test_step_finish.argtypes = [I32, FLOAT_PTR, I32, I32, I32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_draft_finish.argtypes = [FLOAT_PTR, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR]
+        L.minigpt4_amd_test_step_words.argtypes = [I32, I32, I32, INT_PTR, INT_PTR, I32, INT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_test_gather_rows.argtypes = [FLOAT_PTR, I32, INT_PTR, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_attn_rows.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_prefill_seg.argtypes = [I32, I32, I32, I32, VOID_PTR, VOID_PTR, I32, INT_PTR, FLOAT_PTR, I32, FLOAT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, INT_PTR]
         L.minigpt4_amd_test_rope_kv_seg.argtypes = [I32, I32, I32, I32, I32, INT_PTR, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, I32, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR]
@@ -674,6 +679,101 @@ class MiniGPT4SharedLibrary:
         return dict(m=int(res[0]), picks=res[1:1 + R].copy(), stuck_flags=res[9:9 + R].copy(), res=res, pick=out[:, 0].copy(), stuck=out[:, 1].copy(),
                     word=out[:, 2].copy().view(np.uint32), n_cand=out[:, 3].copy(), kept=out[:, 4].copy(), ids=out[:, 5:69].copy(),
                     p=np.ascontiguousarray(out[:, 69:133]).view(np.float32), state=st, slot_logits=keep, ms=float(ms.value))
+
+    # ---- the greedy step epilogues alone (include/minigpt4_amd_test.h states the rule: the first maximum over the non-NaN entries, 0 when there is none above -inf).
+    # State arrays are [n_slot + 1] words / [n_slot + 1][n_vocab] floats, the last word / row a guard; the wrappers copy them and return the copies after the launch.
+    # ValueError: arguments the hook refuses before it looks for a device.
+    def _step_rc(self, name: str, rc: int) -> None:
+        if rc == 1:
+            raise ValueError(f"amd_{name}: bad arguments")
+        if rc:
+            raise RuntimeError(f"{name} rc={rc}: " + self._err())
+
+    @staticmethod
+    def _step_state(n_past, argmax, feed, slot_logits=None, n_vocab: int = 0):
+        st = [np.ascontiguousarray(a, np.int32).reshape(-1).copy() for a in (n_past, argmax, feed)]
+        if not (len(st[0]) == len(st[1]) == len(st[2]) and len(st[0]) >= 2):
+            raise ValueError("state arrays: n_slot + 1 words each")
+        keep = None
+        if slot_logits is not None:
+            keep = np.ascontiguousarray(slot_logits, np.float32).copy()
+            if keep.shape != (len(st[0]), int(n_vocab)):
+                raise ValueError("slot_logits: [n_slot + 1][n_vocab]")
+        return st, keep
+
+    def amd_test_argmax(self, logits: np.ndarray, n: Optional[int] = None):
+        """ONE launch_argmax on logits[n]: (id, partial_values [64] f32, partial_ids [64] i32) -- the partials are what the 64 workgroups of the first launch left."""
+        lg = np.ascontiguousarray(logits, np.float32).reshape(-1)
+        n = lg.size if n is None else int(n)
+        if n > lg.size:
+            raise ValueError("amd_test_argmax: n beyond the row")
+        out, pv, pi = ctypes.c_int32(-2), np.zeros(64, np.float32), np.zeros(64, np.int32)
+        self._step_rc("test_argmax", self.library.minigpt4_amd_test_argmax(lg.ctypes.data_as(FLOAT_PTR) if lg.size else None, n, ctypes.byref(out), pv.ctypes.data_as(FLOAT_PTR),
+                                                                            pi.ctypes.data_as(INT_PTR)))
+        return int(out.value), pv, pi
+
+    def amd_test_step_finish(self, form: int, logits: np.ndarray, slots_or_fin, n_past, argmax, feed, slot_logits) -> dict:
+        """form 0: ONE launch_batch_finish, slots_or_fin = row_slot [rows]; form 1: ONE launch_seg_finish, slots_or_fin = fin [rows][2] (slot, new position), on logits
+        [rows][n_vocab].  dict(n_past, argmax, feed [n_slot + 1], slot_logits [n_slot + 1][n_vocab]) after the launch."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.ndim != 2:
+            raise ValueError("amd_test_step_finish: logits [rows][n_vocab]")
+        rows, nv = lg.shape
+        d = np.ascontiguousarray(slots_or_fin, np.int32).reshape(-1)
+        if d.size != rows * (2 if form == 1 else 1):
+            raise ValueError("amd_test_step_finish: one slot (form 1: one pair) per row")
+        st, keep = self._step_state(n_past, argmax, feed, slot_logits, nv)
+        self._step_rc("test_step_finish", self.library.minigpt4_amd_test_step_finish(int(form), lg.ctypes.data_as(FLOAT_PTR) if lg.size else None, rows, nv, len(st[0]) - 1,
+                                                                                      d.ctypes.data_as(INT_PTR) if d.size else None, st[0].ctypes.data_as(INT_PTR),
+                                                                                      st[1].ctypes.data_as(INT_PTR), st[2].ctypes.data_as(INT_PTR), keep.ctypes.data_as(FLOAT_PTR)))
+        return dict(n_past=st[0], argmax=st[1], feed=st[2], slot_logits=keep)
+
+    def amd_test_draft_finish(self, logits: np.ndarray, tok: Sequence[int], slot: int, n_past, argmax, feed, slot_logits, R: Optional[int] = None) -> dict:
+        """ONE launch_draft_finish on logits [R][n_vocab] with the pass's row tokens tok[R] for conversation `slot`.  dict(m, res [10]: m, 8 ids (0xFF fill behind R), a
+        guard word; n_past, argmax, feed, slot_logits after the launch).  R: the row count handed to the hook (default: the rows of `logits`)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.ndim != 2:
+            raise ValueError("amd_test_draft_finish: logits [R][n_vocab]")
+        R = lg.shape[0] if R is None else int(R)
+        tk = np.ascontiguousarray(tok, np.int32).reshape(-1)
+        if 1 <= R <= 8 and (lg.shape[0] != R or tk.size != R):
+            raise ValueError("amd_test_draft_finish: R rows and R tokens")
+        st, keep = self._step_state(n_past, argmax, feed, slot_logits, lg.shape[1])
+        res = np.zeros(10, np.int32)
+        self._step_rc("test_draft_finish", self.library.minigpt4_amd_test_draft_finish(lg.ctypes.data_as(FLOAT_PTR) if lg.size else None, R, lg.shape[1],
+                                                                                        tk.ctypes.data_as(INT_PTR) if tk.size else None, len(st[0]) - 1, int(slot),
+                                                                                        st[0].ctypes.data_as(INT_PTR), st[1].ctypes.data_as(INT_PTR), st[2].ctypes.data_as(INT_PTR),
+                                                                                        keep.ctypes.data_as(FLOAT_PTR), res.ctypes.data_as(INT_PTR)))
+        return dict(m=int(res[0]), res=res, n_past=st[0], argmax=st[1], feed=st[2], slot_logits=keep)
+
+    def amd_test_step_words(self, form: int, row_slot, n_past, argmax, feed, row_pos=None, n: Optional[int] = None, with_tok0: bool = True) -> dict:
+        """The bookkeeping launches on state words.  form 0: launch_advance by n on slot row_slot[0] (with_tok0: feed[slot] <- argmax[slot]); form 1: launch_batch_begin,
+        n_past[row_slot[r]] = row_pos[r] for r < n (default: every row given); form 2: launch_draft_begin, n_past[row_slot[0]] = row_pos[0].  dict(n_past, argmax, feed)."""
+        sl = np.ascontiguousarray(row_slot, np.int32).reshape(-1)
+        ps = None if row_pos is None else np.ascontiguousarray(row_pos, np.int32).reshape(-1)
+        if form == 1 and n is None:
+            n = sl.size
+        if ps is not None and ps.size != sl.size:
+            raise ValueError("amd_test_step_words: one position per slot")
+        if form == 1 and 1 <= n <= 64 and n > sl.size:
+            raise ValueError("amd_test_step_words: n beyond the rows given")
+        st, _ = self._step_state(n_past, argmax, feed)
+        self._step_rc("test_step_words", self.library.minigpt4_amd_test_step_words(int(form), len(st[0]) - 1, int(n or 0), sl.ctypes.data_as(INT_PTR) if sl.size else None,
+                                                                                    ps.ctypes.data_as(INT_PTR) if ps is not None and ps.size else None, int(bool(with_tok0)),
+                                                                                    st[0].ctypes.data_as(INT_PTR), st[1].ctypes.data_as(INT_PTR), st[2].ctypes.data_as(INT_PTR)))
+        return dict(n_past=st[0], argmax=st[1], feed=st[2])
+
+    def amd_test_gather_rows(self, src: np.ndarray, idx: Sequence[int]) -> np.ndarray:
+        """ONE launch_gather_rows: dst[r] = src[idx[r]] on src [n_src][E]; returns [n + 1][E] fp32 -- row n is the guard row and keeps its 0xFF fill."""
+        s = np.ascontiguousarray(src, np.float32)
+        if s.ndim != 2:
+            raise ValueError("amd_test_gather_rows: src [n_src][E]")
+        ix = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        out = np.zeros((ix.size + 1, s.shape[1]), np.float32)
+        self._step_rc("test_gather_rows", self.library.minigpt4_amd_test_gather_rows(s.ctypes.data_as(FLOAT_PTR) if s.size else None, s.shape[0],
+                                                                                      ix.ctypes.data_as(INT_PTR) if ix.size else None, ix.size, s.shape[1],
+                                                                                      out.ctypes.data_as(FLOAT_PTR)))
+        return out
 
     def amd_test_draft_tables(self, history: Sequence[int], x0: int, draft: Sequence[int], n_ctx: int, n_vocab: int, repeat_last_n: int = 64, repeat_penalty: float = 1.0,
                               alpha_presence: float = 0.0, alpha_frequency: float = 0.0, penalize_nl: int = 1, bias=None, trans=None, accept=None, state: int = 0,
