@@ -416,14 +416,67 @@ MINIGPT4_API int minigpt4_amd_constraint_mask(struct MiniGPT4Context *ctx, int32
  * chain and the context's generator; their draws neither read nor move a conversation's (seed, draws).  The buffers of the feature (descriptors, result block, pinned
  * mirror, an event) are allocated by the first call and freed with the context and by minigpt4_amd_set_conversations: a context that never calls these functions
  * allocates nothing new and launches nothing new.
- * Not built: tail-free, typical and mirostat sampling; top_k = 0 or above 64; a top-N report of the sampled step; guided sampling on the device; a mode that redirects the
- * reference's minigpt4_end_chat here. */
+ * Tail-free, typical and min-p filters and mirostat v2: the extended rule below (the _ex calls).
+ * Not built: mirostat v1; mirostat over the whole vocabulary; top_k = 0 or above 64; mu in snapshots; a top-N report of the sampled step; guided sampling on the device; a
+ * mode that redirects the reference's minigpt4_end_chat here. */
 MINIGPT4_API int minigpt4_amd_end_chat_batch_sampled(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p,
                                                      int32_t *ids_out);
 MINIGPT4_API int minigpt4_amd_sampled_candidates(struct MiniGPT4Context *ctx, const int32_t *slots, int n, float temp, int32_t top_k, float top_p, int32_t *ids_out,
                                                  float *probs_out, int32_t *n_cand_out, int32_t *kept_out);
 MINIGPT4_API int minigpt4_amd_conversation_seed(struct MiniGPT4Context *ctx, int slot, uint64_t seed, uint64_t draws);
 MINIGPT4_API int minigpt4_amd_sampling_info(struct MiniGPT4Context *ctx, int slot, uint64_t out[6]);
+
+/* ---- the extended rule: tail-free, typical and min-p filters, mirostat v2 with one mu per conversation ----------------------------------------------------------
+ * The sampled step above honours temp, top_k and top_p.  The calls below honour every sampling parameter of minigpt4_end_chat except mirostat v1, and min_p (not in the
+ * reference ABI; llama.cpp's later filter).  The generator, THE ROW and the CANDIDATES are the section's above, unchanged: n_c = min(top_k, participating ids) ids in that
+ * order, values v_0 >= v_1 >= ..., top_k in 1 .. 64.  ARITHMETIC: fp32, each operation rounded on its own, nothing fused, sums sequential in list order.
+ * THE LIVE LIST L is the ordered list of surviving candidate indices; it starts as all n_c candidates and always stays in value order.
+ * softmax(L): a_j = expf(v_j - v_first(L)), A = the sequential sum, q_j = a_j / A; each filter recomputes it on the current L, as llama.cpp's chain does.
+ * WITH mirostat == 0 the filters run in the order of the host chain, each keeping at least one candidate:
+ *   1. tail-free, when tfs_z < 1 and |L| > 2: q = softmax(L), d1_i = q_i - q_{i+1}, d2_i = |d1_i - d1_{i+1}| for i < |L| - 2, s = sum d2; s > 1e-6f: d2_i = d2_i / s, else
+ *      d2_i = 1.0f / (float)(|L| - 2); c += d2_i; at the first i >= 1 with c > tfs_z, L becomes its first i entries; none: L is unchanged.  (The host chain's tail_free.)
+ *   2. typical, when typical_p < 1: q = softmax(L), H = sum -q_j * logf(q_j) (a term with q_j == 0 contributes 0), sh_j = fabsf(-logf(q_j) - H) (+inf where q_j == 0);
+ *      L ordered by sh ascending, equal scores by list position; c += q in that order; kept through the first entry with c > typical_p, all if there is none.  The kept
+ *      entries RETURN TO VALUE ORDER.  (A deliberate deviation: llama.cpp at the reference's revision leaves the list in typicality order, so its later softmax subtracts
+ *      a value that need not be the maximum; the distribution is the same up to rounding.  Bit-equality with the host chain is not promised here, as it is not above.)
+ *   3. top-p, when top_p < 1: step 1 of the rule above, on L.
+ *   4. min-p, when min_p > 0: q = softmax(L); kept: the j with q_j >= min_p * q_first (one multiply) -- a prefix of L.
+ *   5. temperature, softmax, draw: steps 2 - 4 of the rule above on L.  w_j = v_j / temp, b_j = expf(w_j - w_first), S the running sum over L in order,
+ *      u = (float)(word >> 8) * 2^-24, t = u * S, the pick is the first entry with S_j > t, the last entry of L if there is none; p_j = b_j / S, 0 for a candidate not in L.
+ *   NEUTRAL VALUES: with tfs_z = 1, typical_p = 1, min_p = 0 the chain performs exactly the operations of the rule above, in the same order: the pick, the kept count and
+ *   every bit of every p_j are that rule's.
+ * WITH mirostat == 2: llama.cpp's llama_sample_token_mirostat_v2 BEHIND top-k; tfs_z, typical_p, top_p and min_p are ignored, as the host chain ignores them there.
+ *   w_j = v_j / temp, b_j = expf(w_j - w_0), Z = sum b_j, p_j = b_j / Z, s_j = -log2f(p_j); n = the first j with s_j > mu, n_c if there is none, 1 if that j is 0;
+ *   S = the running sum of b_j for j < n; the draw is step 5's over those n; observed = -log2f(b_pick / S), e = observed - tau, mu' = mu - eta * e (the multiply and the
+ *   subtract rounded separately).  Reported p_j = b_j / S for j < n, 0 behind.
+ *   NOT THE REFERENCE'S BEHAVIOUR: the host chain's mirostat runs over the whole vocabulary, this one over at most 64 candidates.
+ *   mu is a PER-CONVERSATION value: unset until the conversation's first mirostat decision, where it becomes 2 * tau.  Like (seed, draws) it belongs to the sampler:
+ *   minigpt4_reset_chat, forks, shifts and snapshot loads leave it alone, minigpt4_amd_set_conversations unsets it, and it moves on every decision, whether or not the
+ *   conversation then has room to advance.  The snapshot format stays version 1 and does not carry it.  (The host chain's mu is the context's: there, what a conversation
+ *   receives depends on who shares its step.)
+ * minigpt4_amd_end_chat_batch_sampled_ex: minigpt4_amd_end_chat_batch_sampled under this rule, step for step: one descriptor upload, one launch (kernel
+ * k_sample_rows_ex: k_sample_rows' selection, then the chain), the picks handed to the pass on the device; mu' is read from the same pinned block as the picks, while the
+ * pass runs.  draws += 1 per decision as above.
+ * minigpt4_amd_sampled_candidates_ex: what the next such step would draw from: ids_out [n][64], probs_out [n][64], n_cand_out [n], kept_mask_out [n] (bit j: candidate j
+ * is in L; under mirostat the low n bits); each may be NULL.  Nothing advances, no draw is counted, mu does not move.
+ * minigpt4_amd_conversation_mirostat: a finite value sets the conversation's mu, NaN unsets it.
+ * minigpt4_amd_mirostat_info: out = {set 0 / 1, mu (0 when unset), the last observed surprise, the tau it was measured against}.
+ * Each returns 0, or 1 with "end_chat_batch_sampled_ex: ..." / "sampled_candidates_ex: ..." / "conversation_mirostat: ..." / "mirostat_info: ..." in
+ * minigpt4_amd_last_error and nothing changed, before anything is decided: everything the plain calls refuse; tfs_z or typical_p outside (0, 1]; min_p outside [0, 1];
+ * mirostat not 0 or 2 (1: "... mirostat v1 is not built"); mirostat_tau not finite or <= 0; mirostat_eta not finite or < 0; NaN in any of them; an infinite mu.
+ * The buffers (a staging block of the extended descriptors and results) are allocated by the first _ex call and freed with the context and by
+ * minigpt4_amd_set_conversations: a context that never calls these functions allocates nothing new and launches nothing new.  The existing calls launch k_sample_rows, one
+ * instance of the source text both kernels share: its results are bit for bit what they were.  The counters of minigpt4_amd_sampling_info count the _ex calls too.
+ * Not built: mirostat v1; mirostat over the whole vocabulary; mirostat inside draft verification (minigpt4_amd_verify_draft_sampled_ex below takes the filters only: mu at
+ * row r would depend on row r - 1's pick); top_k = 0 or above 64; mu in snapshots; guided sampling on the device; a mode that redirects the reference's minigpt4_end_chat
+ * here. */
+MINIGPT4_API int minigpt4_amd_end_chat_batch_sampled_ex(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p,
+                                                        float tfs_z, float typical_p, float min_p, int mirostat, float mirostat_tau, float mirostat_eta, int32_t *ids_out);
+MINIGPT4_API int minigpt4_amd_sampled_candidates_ex(struct MiniGPT4Context *ctx, const int32_t *slots, int n, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p,
+                                                    float min_p, int mirostat, float mirostat_tau, float mirostat_eta, int32_t *ids_out, float *probs_out, int32_t *n_cand_out,
+                                                    uint64_t *kept_mask_out);
+MINIGPT4_API int minigpt4_amd_conversation_mirostat(struct MiniGPT4Context *ctx, int slot, float mu);
+MINIGPT4_API int minigpt4_amd_mirostat_info(struct MiniGPT4Context *ctx, int slot, float out[4]);
 
 /* ---- speculation under sampling: drafts verified at temp > 0, lookup decoding with the reference's default sampler settings -----------------------------------
  * minigpt4_amd_verify_draft and minigpt4_amd_decode_lookup decide greedily.  Here the 1 + n rows of the same verify pass are SAMPLED, each with the draw plain decoding
@@ -465,12 +518,25 @@ MINIGPT4_API int minigpt4_amd_sampling_info(struct MiniGPT4Context *ctx, int slo
  * x0 and the automatic shift is off -- checked before anything is decided.  The graphs are dropped where the greedy ones are; the result block is allocated by the first
  * call: a context that never calls these functions allocates nothing new and launches nothing new.
  * Not built: several conversations' drafts in one pass; tree drafts; a draft model; remembering next_out per conversation, which would save the x0 launch of the next call
- * (every setter of bias, penalties, constraint, seed and logits would have to invalidate it); tail-free, typical and mirostat sampling; guidance. */
+ * (every setter of bias, penalties, constraint, seed and logits would have to invalidate it); mirostat inside draft verification (mu at row r depends on row r - 1's
+ * pick); guidance.
+ * minigpt4_amd_verify_draft_sampled_ex / minigpt4_amd_decode_lookup_sampled_ex: the two calls with tfs_z, typical_p and min_p.  D(L, h, q, k) becomes the pick of the
+ * extended rule above (mirostat == 0: tail-free, typical, top-p, min-p, temperature, softmax, draw); nothing else in THE RULE changes, so the emitted tokens are those of
+ * minigpt4_amd_end_chat_batch_sampled_ex with the same parameters from the same (seed, draws) wherever the logits are the same.  On the device: k_sample_rows_ex and
+ * k_draft_sample_finish_ex (k_draft_sample_finish's text over the extended result blocks) in the places of the plain kernels; with neutral values the results are the plain
+ * calls'.  There are no mirostat arguments.  Refusals: the plain calls', under "verify_draft_sampled_ex: ..." / "decode_lookup_sampled_ex: ...", and tfs_z or typical_p
+ * outside (0, 1], min_p outside [0, 1] (NaN included).  minigpt4_amd_speculation_info counts these calls too. */
 MINIGPT4_API int minigpt4_amd_verify_draft_sampled(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, float temp, int32_t top_k, float top_p, int32_t *ids_out,
                                                    int32_t *n_out, int32_t *next_out, int32_t *row_sampled_out, float *row_logits_out);
 MINIGPT4_API int minigpt4_amd_decode_lookup_sampled(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft,
                                                     float temp, int32_t top_k, float top_p, int32_t *tokens_out, int32_t *n_tokens, int32_t stats[4]);
 MINIGPT4_API int minigpt4_amd_speculation_info(struct MiniGPT4Context *ctx, int64_t out[8]);
+MINIGPT4_API int minigpt4_amd_verify_draft_sampled_ex(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, float temp, int32_t top_k, float top_p, float tfs_z,
+                                                      float typical_p, float min_p, int32_t *ids_out, int32_t *n_out, int32_t *next_out, int32_t *row_sampled_out,
+                                                      float *row_logits_out);
+MINIGPT4_API int minigpt4_amd_decode_lookup_sampled_ex(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft,
+                                                       float temp, int32_t top_k, float top_p, float tfs_z, float typical_p, float min_p, int32_t *tokens_out, int32_t *n_tokens,
+                                                       int32_t stats[4]);
 
 /* ---- snapshots: save and restore a conversation --------------------------------------------------------------------------------------------------------
  * A conversation leaves its slot, its context or its process as one blob (llama.cpp's llama_copy_state_data / session files / slot save and restore) and comes back bit

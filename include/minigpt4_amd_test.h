@@ -263,6 +263,20 @@ MINIGPT4_API int minigpt4_amd_test_sample_rule(const float *values, int n_cand, 
 MINIGPT4_API int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
                                                const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k,
                                                const uint64_t *seed_draws, const int32_t *tok_index, int32_t *row_tok_io, int32_t *out, float *ms_out);
+/* The extended rule of device-side sampling (minigpt4_amd.h states it): tail-free, typical, top-p, min-p, temperature, softmax and the draw, or mirostat v2.
+ * minigpt4_amd_test_sample_chain, no GPU: the host side of the chain on values[n_cand] (the candidates in order, 1 .. 64) with the given output word and mu (NaN: unset):
+ * returns the index of the picked candidate, p_out[n_cand] = the probabilities (0 for a candidate outside the live list), *kept_out = the live list's length, *mask_out =
+ * bit j set when candidate j is in it, *mu_out = mu' (mirostat 0: mu as given), *observed_out = the observed surprise (mirostat 0: 0).  -1 = bad arguments (as
+ * _test_sample_rule; tfs_z or typical_p outside (0, 1], min_p outside [0, 1], mirostat not 0 or 2, tau not finite or <= 0, eta not finite or < 0, an infinite mu).
+ * minigpt4_amd_test_sample_rows_ex: k_sample_rows_ex alone; the arguments of _test_sample_rows, then chain = [n_rows][6] (tfs_z, typical_p, min_p, tau, eta, mu) and
+ * mirostat[n_rows].  out = [n_rows][137] words: the 133 of _test_sample_rows (kept = the live list's length), the mask's low and high word, mu', the observed surprise.
+ * Return codes as _test_sample_rows; 1 also for a chain parameter outside the ranges above. */
+MINIGPT4_API int minigpt4_amd_test_sample_chain(const float *values, int n_cand, float temp, float top_p, float tfs_z, float typical_p, float min_p, int mirostat, float tau,
+                                                float eta, float mu, uint32_t word, float *p_out, int32_t *kept_out, uint64_t *mask_out, float *mu_out, float *observed_out);
+MINIGPT4_API int minigpt4_amd_test_sample_rows_ex(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table,
+                                                  const uint32_t *bitmaps, int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k,
+                                                  const uint64_t *seed_draws, const int32_t *tok_index, const float *chain, const int32_t *mirostat, int32_t *row_tok_io,
+                                                  int32_t *out, float *ms_out);
 /* Speculation under sampling (minigpt4_amd.h states the rule).
  * minigpt4_amd_test_draft_sample: the sampled verify pass's epilogue alone -- k_sample_rows over the R rows (1 .. 8) of host logits [R][ld], then k_draft_sample_finish.
  * rows / table / bitmaps / bitmap_of_row / temp_top_p / top_k / seed_draws as for minigpt4_amd_test_sample_rows, one descriptor per row, descriptor r naming buffer row r;

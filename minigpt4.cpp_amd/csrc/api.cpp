@@ -389,6 +389,22 @@ int minigpt4_amd_decode_lookup_sampled(struct MiniGPT4Context *ctx, const int32_
     if (!ctx) { set_last_error("decode_lookup_sampled: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->decode_lookup_sampled(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, temp, top_k, top_p, tokens_out, n_tokens, stats); });
 }
+int minigpt4_amd_verify_draft_sampled_ex(struct MiniGPT4Context *ctx, const int32_t *draft, int n_draft, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p,
+                                         float min_p, int32_t *ids_out, int32_t *n_out, int32_t *next_out, int32_t *row_sampled_out, float *row_logits_out) {
+    if (!ctx) { set_last_error("verify_draft_sampled_ex: no context"); return 1; }
+    return guarded(1, [&] {
+        const ChainParams cp{tfs_z, typical_p, min_p, 0, 5.0f, 0.1f, NAN, 0};   // no mirostat here: mu at row r would depend on row r - 1's pick
+        return E_(ctx)->verify_draft_sampled_ex(draft, n_draft, temp, top_k, top_p, cp, ids_out, n_out, next_out, row_sampled_out, row_logits_out);
+    });
+}
+int minigpt4_amd_decode_lookup_sampled_ex(struct MiniGPT4Context *ctx, const int32_t *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp,
+                                          int32_t top_k, float top_p, float tfs_z, float typical_p, float min_p, int32_t *tokens_out, int32_t *n_tokens, int32_t stats[4]) {
+    if (!ctx) { set_last_error("decode_lookup_sampled_ex: no context"); return 1; }
+    return guarded(1, [&] {
+        const ChainParams cp{tfs_z, typical_p, min_p, 0, 5.0f, 0.1f, NAN, 0};
+        return E_(ctx)->decode_lookup_sampled_ex(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, temp, top_k, top_p, cp, tokens_out, n_tokens, stats);
+    });
+}
 int minigpt4_amd_speculation_info(struct MiniGPT4Context *ctx, int64_t out[8]) {
     if (!ctx) { set_last_error("speculation_info: no context"); return 1; }
     static_assert(sizeof(long long) == sizeof(int64_t), "the counters travel as 64-bit words");
@@ -474,6 +490,37 @@ int minigpt4_amd_conversation_seed(struct MiniGPT4Context *ctx, int slot, uint64
 int minigpt4_amd_sampling_info(struct MiniGPT4Context *ctx, int slot, uint64_t out[6]) {
     if (!ctx) { set_last_error("sampling_info: no context"); return 1; }
     return guarded(1, [&] { return E_(ctx)->sampling_info(slot, out); });
+}
+// ---- the same under the extended rule: tail-free, typical, min-p, per-conversation mirostat v2 ----
+int minigpt4_amd_end_chat_batch_sampled_ex(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const char **tokens, float temp, int32_t top_k, float top_p, float tfs_z,
+                                           float typical_p, float min_p, int mirostat, float mirostat_tau, float mirostat_eta, int32_t *ids_out) {
+    if (!ctx) { set_last_error("end_chat_batch_sampled_ex: no context"); return 1; }
+    if (!tokens) { set_last_error("end_chat_batch_sampled_ex: tokens is required"); return 1; }
+    Engine *e = E_(ctx);
+    return guarded(1, [&]() -> int {
+        int ids[Engine::MAX_CONVERSATIONS] = {0};
+        if (n > Engine::MAX_CONVERSATIONS) { set_last_error("end_chat_batch_sampled_ex: bad slot list"); return 1; }
+        const ChainParams cp{tfs_z, typical_p, min_p, mirostat, mirostat_tau, mirostat_eta, NAN, 0};   // mu: the engine enters each conversation's own
+        if (int rc = e->decode_batch_sampled_ex(slots, n, temp, top_k, top_p, cp, ids)) return rc;
+        for (int i = 0; i < n; i++) { tokens[i] = e->id_to_token(ids[i]); if (ids_out) ids_out[i] = ids[i]; }
+        return 0;
+    });
+}
+int minigpt4_amd_sampled_candidates_ex(struct MiniGPT4Context *ctx, const int32_t *slots, int n, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p, float min_p,
+                                       int mirostat, float mirostat_tau, float mirostat_eta, int32_t *ids_out, float *probs_out, int32_t *n_cand_out, uint64_t *kept_mask_out) {
+    if (!ctx) { set_last_error("sampled_candidates_ex: no context"); return 1; }
+    return guarded(1, [&] {
+        const ChainParams cp{tfs_z, typical_p, min_p, mirostat, mirostat_tau, mirostat_eta, NAN, 0};
+        return E_(ctx)->sampled_candidates_ex(slots, n, temp, top_k, top_p, cp, ids_out, probs_out, n_cand_out, kept_mask_out);
+    });
+}
+int minigpt4_amd_conversation_mirostat(struct MiniGPT4Context *ctx, int slot, float mu) {
+    if (!ctx) { set_last_error("conversation_mirostat: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_conversation_mirostat(slot, mu); });
+}
+int minigpt4_amd_mirostat_info(struct MiniGPT4Context *ctx, int slot, float out[4]) {
+    if (!ctx) { set_last_error("mirostat_info: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->mirostat_info(slot, out); });
 }
 // ---- snapshots: save and restore a conversation ----------------------------------------------------------------------------------------------------
 size_t minigpt4_amd_state_size(struct MiniGPT4Context *ctx, int slot) {

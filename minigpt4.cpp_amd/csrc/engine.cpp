@@ -97,7 +97,7 @@ Engine::~Engine() {
                     pen_, spec_logits_, spec_res_, spec_hres_, beam_d_, beam_h_, beam_save_, beam_ev_,
                     guide_mix_, guide_d_, guide_h_, guide_ev_, con_vocab_, con_off_, con_stage_, con_row_h_,
                     state_d_[0], state_d_[1], state_h_[0], state_h_[1], state_sum_d_, state_sum_h_, state_cs_, state_ev_kernel_[0], state_ev_kernel_[1], state_ev_copy_[0],
-                    state_ev_copy_[1], smp_, sdr_res_, sdr_hres_);
+                    state_ev_copy_[1], smp_, smpx_, sdr_res_, sdr_hres_);
         for (Constraint &c : con_) c.dev.abandon();
         return;
     }
@@ -2166,12 +2166,36 @@ int Engine::sampling_info(int slot, uint64_t out[6]) const {
     out[0] = smp_seed_[slot]; out[1] = smp_draws_[slot]; out[2] = smp_info_.launches; out[3] = smp_info_.handed; out[4] = smp_info_.stuck; out[5] = smp_info_.rows;
     return 0;
 }
-int Engine::smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p) {
+int Engine::set_conversation_mirostat(int slot, float mu) {
+    if (slot < 0 || slot >= (int)conv_.size()) { set_last_error("conversation_mirostat: conversation index out of range"); return 1; }
+    if (std::isinf(mu)) { set_last_error("conversation_mirostat: mu must be finite (NaN unsets it)"); return 1; }
+    smp_mu_[slot] = mu;
+    return 0;
+}
+int Engine::mirostat_info(int slot, float out[4]) const {
+    if (!out || slot < 0 || slot >= (int)conv_.size()) { set_last_error(out ? "mirostat_info: conversation index out of range" : "mirostat_info: no output array"); return 1; }
+    const bool set = !std::isnan(smp_mu_[slot]);
+    out[0] = set ? 1.0f : 0.0f; out[1] = set ? smp_mu_[slot] : 0.0f; out[2] = smp_observed_[slot]; out[3] = smp_tau_[slot];
+    return 0;
+}
+// the extended rule's own parameters, in the order the header lists them
+template <typename Refuse> static bool chain_params_ok(Refuse refuse, const ChainParams &cp) {
+    if (!(cp.tfs_z > 0.0f) || !(cp.tfs_z <= 1.0f)) { refuse("tfs_z outside (0, 1]"); return false; }
+    if (!(cp.typical_p > 0.0f) || !(cp.typical_p <= 1.0f)) { refuse("typical_p outside (0, 1]"); return false; }
+    if (!(cp.min_p >= 0.0f) || !(cp.min_p <= 1.0f)) { refuse("min_p outside [0, 1]"); return false; }
+    if (cp.mirostat == 1) { refuse("mirostat v1 is not built"); return false; }
+    if (cp.mirostat != 0 && cp.mirostat != 2) { refuse("mirostat must be 0 or 2"); return false; }
+    if (!std::isfinite(cp.tau) || !(cp.tau > 0.0f)) { refuse("mirostat_tau must be finite and > 0"); return false; }
+    if (!std::isfinite(cp.eta) || !(cp.eta >= 0.0f)) { refuse("mirostat_eta must be finite and >= 0"); return false; }
+    return true;
+}
+int Engine::smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp) {
     auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
     const int bad = check_slots(slots, n);
     if (bad == 1) return refuse("bad slot list");
     if (bad) return refuse("conversations must be distinct and in range");
     if (!sampling_params_ok(refuse, temp, top_k, top_p)) return 1;
+    if (cp && !chain_params_ok(refuse, *cp)) return 1;
     if (weights_missing()) return refuse(last_error());
     auto flush_each = [&] {                                                   // as decode_batch: one pass each
         const SelectScope restore(this);
@@ -2185,55 +2209,76 @@ SampleRow Engine::smp_row(int slot, const PenRow &pen, int state, uint64_t draws
     const unsigned *allowed = h ? con_[h - 1].index + (size_t)state * constraint_words((int)llm_.n_vocab) : nullptr;
     return SampleRow{pen, allowed, temp, top_p, top_k, tok_index, smp_seed_[slot], draws};
 }
-size_t Engine::smp_stage(const int *slots, int n, float temp, int top_k, float top_p) {
-    smp_.alloc();
+template <bool EX> size_t Engine::smp_stage(const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp) {
+    auto &blk = smp_block<EX>();
+    blk.alloc();
     std::vector<PenEntry> tab;
     size_t off = 0;
     for (int i = 0; i < n; i++) {
         const int slot = slots[i];
         PenRow pen;
         pen_build_row(conv_[(size_t)slot], slot, off, &pen, tab);            // the identity included: n = 0, no flags
-        smp_.rows()[i] = smp_row(slot, pen, con_state_[slot], smp_draws_[slot], -1, temp, top_k, top_p);
-        std::copy(tab.begin(), tab.end(), smp_.entries() + off);
+        smp_plain(blk.rows()[i]) = smp_row(slot, pen, con_state_[slot], smp_draws_[slot], -1, temp, top_k, top_p);
+        if constexpr (EX) { blk.rows()[i].chain = *cp; blk.rows()[i].chain.mu = smp_mu_[slot]; }
+        std::copy(tab.begin(), tab.end(), blk.entries() + off);
         off += tab.size();
     }
     return off;
 }
-bool Engine::smp_launch_on(const float *logits, int n, size_t n_ent, int *row_tok) {
+template <bool EX> bool Engine::smp_launch_on(const float *logits, int n, size_t n_ent, int *row_tok) {
     const int V = (int)llm_.n_vocab;
-    smp_.upload(n_ent, stream_);
-    return launch_sample_rows(logits, V, V, n, smp_.d_rows(), smp_.d_entries(), smp_.out_d(), row_tok, stream_);
+    auto &blk = smp_block<EX>();
+    blk.upload(n_ent, stream_);
+    if constexpr (EX) return launch_sample_rows_ex(logits, V, V, n, blk.d_rows(), blk.d_entries(), blk.out_d(), row_tok, stream_);
+    else return launch_sample_rows(logits, V, V, n, blk.d_rows(), blk.d_entries(), blk.out_d(), row_tok, stream_);
 }
-bool Engine::smp_launch(int n, size_t n_ent, bool hand) {
-    if (!smp_launch_on(logits_, n, n_ent, hand ? d_btok_ : nullptr)) return false;
-    smp_.fetch(n, sizeof(SampleOut), stream_);
+template <bool EX> bool Engine::smp_launch(int n, size_t n_ent, bool hand) {
+    if (!smp_launch_on<EX>(logits_, n, n_ent, hand ? d_btok_ : nullptr)) return false;
+    smp_block<EX>().fetch(n, EX ? sizeof(SampleOutEx) : sizeof(SampleOut), stream_);
     smp_info_.launches++;
     return true;
 }
-int Engine::sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out) {
-    if (smp_prepare("sampled_candidates", slots, n, temp, top_k, top_p)) return 1;
-    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; smp_ feeds no earlier copy
-    const size_t n_ent = smp_stage(slots, n, temp, top_k, top_p);
-    if (!smp_launch(n, n_ent, /*hand=*/false)) { set_last_error("sampled_candidates: " + last_error()); return 1; }
-    HIP_CHECK(hipEventSynchronize(smp_.event()));
+template <bool EX> int Engine::sampled_candidates_t(const char *name, const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp, int *ids_out,
+                                                    float *probs_out, int *n_cand_out, int *kept_out, uint64_t *kept_mask_out) {
+    if (smp_prepare(name, slots, n, temp, top_k, top_p, cp)) return 1;
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; the block feeds no earlier copy
+    auto &blk = smp_block<EX>();
+    const size_t n_ent = smp_stage<EX>(slots, n, temp, top_k, top_p, cp);
+    if (!smp_launch<EX>(n, n_ent, /*hand=*/false)) { set_last_error(std::string(name) + ": " + last_error()); return 1; }
+    HIP_CHECK(hipEventSynchronize(blk.event()));
     for (int i = 0; i < n; i++) {
-        const SampleOut &o = smp_.out_h()[i];
+        const SampleOut &o = smp_plain(blk.out_h()[i]);
         if (ids_out) memcpy(ids_out + (size_t)i * SAMPLE_MAX, o.ids, sizeof(o.ids));
         if (probs_out) memcpy(probs_out + (size_t)i * SAMPLE_MAX, o.p, sizeof(o.p));
         if (n_cand_out) n_cand_out[i] = o.n_cand;
         if (kept_out) kept_out[i] = o.kept;
+        if constexpr (EX) if (kept_mask_out) kept_mask_out[i] = (uint64_t)blk.out_h()[i].mask_lo | (uint64_t)blk.out_h()[i].mask_hi << 32;
     }
     return 0;
 }
+int Engine::sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out) {
+    return sampled_candidates_t<false>("sampled_candidates", slots, n, temp, top_k, top_p, nullptr, ids_out, probs_out, n_cand_out, kept_out, nullptr);
+}
+int Engine::sampled_candidates_ex(const int *slots, int n, float temp, int top_k, float top_p, const ChainParams &cp, int *ids_out, float *probs_out, int *n_cand_out,
+                                  uint64_t *kept_mask_out) {
+    return sampled_candidates_t<true>("sampled_candidates_ex", slots, n, temp, top_k, top_p, &cp, ids_out, probs_out, n_cand_out, nullptr, kept_mask_out);
+}
 int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out) {
-    auto refuse = [](const std::string &what) { set_last_error("end_chat_batch_sampled: " + what); return 1; };
+    return decode_batch_sampled_t<false>("end_chat_batch_sampled", slots, n, temp, top_k, top_p, nullptr, ids_out);
+}
+int Engine::decode_batch_sampled_ex(const int *slots, int n, float temp, int top_k, float top_p, const ChainParams &cp, int *ids_out) {
+    return decode_batch_sampled_t<true>("end_chat_batch_sampled_ex", slots, n, temp, top_k, top_p, &cp, ids_out);
+}
+template <bool EX> int Engine::decode_batch_sampled_t(const char *name, const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp, int *ids_out) {
+    auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
     if (!ids_out) return refuse("ids_out is required");
-    if (smp_prepare("end_chat_batch_sampled", slots, n, temp, top_k, top_p)) return 1;
+    if (smp_prepare(name, slots, n, temp, top_k, top_p, cp)) return 1;
     const SelectScope restore(this);
-    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_ and smp_ feed no earlier copy
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the histories are whole; h_bstage_ and the block feed no earlier copy
     // 1. the descriptors, from each history as a sample sees it: before any shift
-    const size_t n_ent = smp_stage(slots, n, temp, top_k, top_p);
-    SampleRow *rows = smp_.rows();
+    auto &blk = smp_block<EX>();
+    const size_t n_ent = smp_stage<EX>(slots, n, temp, top_k, top_p, cp);
+    auto *rows = blk.rows();
     // 2. room, and the pass's rows: a conversation that is full and cannot shift is sampled and reported, not advanced
     int B = 0, row_of[MAX_CONVERSATIONS];
     for (int i = 0; i < n; i++) {
@@ -2241,18 +2286,18 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
         cur_ = slots[i]; row_of[i] = -1;
         if (cv.n_past + 1 > n_ctx_ && make_room(1)) continue;
         row_of[i] = B; stage_row(B++, 0, slots[i], cv.n_committed);
-        if (!parity_) rows[i].tok_index = row_of[i];
+        if (!parity_) smp_plain(rows[i]).tok_index = row_of[i];
     }
     const bool hand = B > 0 && !parity_;
     if (hand) step_begin(B);
     // 3. the decision: one launch for all listed conversations; the picks of those that advance go straight into the pass's row tokens
-    if (!smp_launch(n, n_ent, hand)) return refuse(last_error());
+    if (!smp_launch<EX>(n, n_ent, hand)) return refuse(last_error());
     smp_info_.rows += (uint64_t)n; smp_info_.handed += hand ? (uint64_t)B : 0;
     // the block from pinned memory; false: an id outside the vocabulary (the kernel writes none; a block that never arrived), entered as 0
     auto take_picks = [&]() -> bool {
         bool sane = true;
         for (int i = 0; i < n; i++) {
-            ids_out[i] = smp_.out_h()[i].pick;
+            ids_out[i] = smp_plain(blk.out_h()[i]).pick;
             if (!id_in_vocab(ids_out[i])) { sane = false; ids_out[i] = 0; }
         }
         return sane;
@@ -2261,13 +2306,16 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
     auto sampler_state = [&] {
         for (int i = 0; i < n; i++) {
             smp_draws_[slots[i]] += 1;
-            if (smp_.out_h()[i].stuck == 1) smp_info_.stuck++;
+            if (smp_plain(blk.out_h()[i]).stuck == 1) smp_info_.stuck++;
+            if constexpr (EX) if (cp->mirostat == 2) { smp_mu_[slots[i]] = blk.out_h()[i].mu; smp_observed_[slots[i]] = blk.out_h()[i].observed; smp_tau_[slots[i]] = cp->tau; }
             if (con_handle_[slots[i]]) con_walk(slots[i], ids_out[i]);
         }
     };
-    auto bad_pick = [] { return bad_id("end_chat_batch_sampled: the device reported an id outside the vocabulary"); };
+    auto bad_pick = [] {
+        return bad_id(EX ? "end_chat_batch_sampled_ex: the device reported an id outside the vocabulary" : "end_chat_batch_sampled: the device reported an id outside the vocabulary");
+    };
     if (!hand) {                                                             // parity mode, or nobody advances: the picks first
-        HIP_CHECK(hipEventSynchronize(smp_.event()));
+        HIP_CHECK(hipEventSynchronize(blk.event()));
         if (!take_picks()) throw bad_pick();                                 // nothing has been launched for these picks yet
         sampler_state();
         if (!B) return 0;
@@ -2278,7 +2326,7 @@ int Engine::decode_batch_sampled(const int *slots, int n, float temp, int top_k,
     }
     // 4. the weight pass: the batched step's own.  It advances the device state whatever the block says: the host's book-keeping follows it before a bad block is reported
     step_launch(B);
-    HIP_CHECK(hipEventSynchronize(smp_.event()));
+    HIP_CHECK(hipEventSynchronize(blk.event()));
     const bool sane = take_picks();
     sampler_state();
     for (int i = 0; i < n; i++) if (row_of[i] >= 0) commit_rows(slots[i], &ids_out[i], 1, /*past=*/true);
@@ -2576,6 +2624,14 @@ int Engine::speculation_info(long long out[8]) const {
 }
 int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int top_k, float top_p, int *ids_out, int *n_out, int *next_out, int *row_sampled, float *row_logits,
                                  const char *name, int *n_sent) {
+    return verify_draft_sampled_t<false>(draft, n_draft, temp, top_k, top_p, nullptr, ids_out, n_out, next_out, row_sampled, row_logits, name, n_sent);
+}
+int Engine::verify_draft_sampled_ex(const int *draft, int n_draft, float temp, int top_k, float top_p, const ChainParams &cp, int *ids_out, int *n_out, int *next_out, int *row_sampled,
+                                    float *row_logits) {
+    return verify_draft_sampled_t<true>(draft, n_draft, temp, top_k, top_p, &cp, ids_out, n_out, next_out, row_sampled, row_logits, "verify_draft_sampled_ex", nullptr);
+}
+template <bool EX> int Engine::verify_draft_sampled_t(const int *draft, int n_draft, float temp, int top_k, float top_p, const ChainParams *cp, int *ids_out, int *n_out, int *next_out,
+                                                      int *row_sampled, float *row_logits, const char *name, int *n_sent) {
     auto refuse = [&](const std::string &what) { set_last_error(std::string(name) + ": " + what); return 1; };
     const int V = (int)llm_.n_vocab;
     if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
@@ -2584,6 +2640,7 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
     if (!ids_out || !n_out || !next_out) return refuse("ids_out, n_out and next_out are required");
     for (int i = 0; i < n_draft; i++) if (draft[i] < 0 || draft[i] >= V) return refuse("draft token id out of range");
     if (!sampling_params_ok(refuse, temp, top_k, top_p)) return 1;
+    if (cp && !chain_params_ok(refuse, *cp)) return 1;
     if (weights_missing()) return refuse(last_error());
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
@@ -2594,16 +2651,19 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
     const int slot = cur_, handle = con_handle_[slot];
     const uint64_t c0 = smp_draws_[slot];
     sdr_alloc();
+    auto &blk = smp_block<EX>();
+    constexpr const char *refused = EX ? "verify_draft_sampled_ex: a launch was refused (minigpt4_amd_last_error)" : "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)";
+    constexpr const char *bad_pick = EX ? "verify_draft_sampled_ex: the device reported an id outside the vocabulary" : "verify_draft_sampled: the device reported an id outside the vocabulary";
     // 1. x0 = D(L, h, q, c): the sampled step's own descriptor (history before the shift) and launch, on the conversation's row; the host needs the pick for the rows' tables
-    const size_t n_ent0 = smp_stage(&slot, 1, temp, top_k, top_p);
+    const size_t n_ent0 = smp_stage<EX>(&slot, 1, temp, top_k, top_p, cp);
     if (cv.n_past + 1 > n_ctx_ && make_room(1)) return refuse("context full");
     auto decide = [&](size_t n_ent, int *stuck) -> int {                     // the staged descriptor on logits_, the 8 bytes {pick, stuck} awaited
-        if (!smp_launch_on(logits_, 1, n_ent)) throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
-        smp_.fetch(1, 2 * sizeof(int), stream_);
+        if (!smp_launch_on<EX>(logits_, 1, n_ent)) throw HipError{hipErrorInvalidValue, refused, __FILE__, __LINE__};
+        blk.fetch(1, 2 * sizeof(int), stream_);
         HIP_CHECK(hipStreamSynchronize(stream_));
         spec_info_.launches++;
-        const int id = device_id(smp_.out_h()[0].pick, "verify_draft_sampled: the device reported an id outside the vocabulary");
-        *stuck = smp_.out_h()[0].stuck == 1;
+        const int id = device_id(smp_plain(blk.out_h()[0]).pick, bad_pick);
+        *stuck = smp_plain(blk.out_h()[0]).stuck == 1;
         return id;
     };
     int stuck0 = 0;
@@ -2635,7 +2695,7 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
             spec_info_.rows++;
             if (row_logits) { HIP_CHECK(hipMemcpyAsync(row_logits + (size_t)r * V, logits_ + (size_t)slot * V, (size_t)V * 4, hipMemcpyDeviceToHost, stream_)); HIP_CHECK(hipStreamSynchronize(stream_)); }
             int stuck = 0;
-            const int x = decide(smp_stage(&slot, 1, temp, top_k, top_p), &stuck);   // history h_r, state q_r, draw c + 1 + r: all current
+            const int x = decide(smp_stage<EX>(&slot, 1, temp, top_k, top_p, cp), &stuck);   // history h_r, state q_r, draw c + 1 + r: all current
             spec_info_.stuck += stuck;
             if (row_sampled) row_sampled[r] = x;
             next = x;
@@ -2643,14 +2703,17 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
         }
     } else {
         // 3. behind one wait: the slab, the pass without an epilogue, the R decisions with draws c + 1 + r, the epilogue, the result block
-        for (int r = 0; r < R; r++) smp_.rows()[r] = smp_row(slot, st.rows[(size_t)r], st.state[(size_t)r], c0 + 1 + (uint64_t)r, -1, temp, top_k, top_p);
-        std::copy(st.entries.begin(), st.entries.end(), smp_.entries());
+        for (int r = 0; r < R; r++) {
+            smp_plain(blk.rows()[r]) = smp_row(slot, st.rows[(size_t)r], st.state[(size_t)r], c0 + 1 + (uint64_t)r, -1, temp, top_k, top_p);
+            if constexpr (EX) blk.rows()[r].chain = *cp;
+        }
+        std::copy(st.entries.begin(), st.entries.end(), blk.entries());
         stage_row(0, x0, slot, p); for (int r = 1; r < R; r++) staged_token(r) = draft[r - 1];   // k_draft_begin spreads row 0's conversation and position
         step_begin(R, /*verify=*/true);
         step_launch(R, /*verify=*/true, /*epilogue=*/false);
-        if (!smp_launch_on(spec_logits_, R, st.entries.size())) throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
-        if (!launch_draft_sample_finish(spec_logits_, V, V, R, d_btok_, smp_.out_d(), d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, sdr_res_, stream_))
-            throw HipError{hipErrorInvalidValue, "verify_draft_sampled: a launch was refused (minigpt4_amd_last_error)", __FILE__, __LINE__};
+        if (!smp_launch_on<EX>(spec_logits_, R, st.entries.size())) throw HipError{hipErrorInvalidValue, refused, __FILE__, __LINE__};
+        if (!launch_draft_sample_finish(spec_logits_, V, V, R, d_btok_, blk.out_d(), d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, sdr_res_, stream_))
+            throw HipError{hipErrorInvalidValue, refused, __FILE__, __LINE__};
         spec_info_.launches++; spec_info_.rows += R;
         HIP_CHECK(hipMemcpyAsync(sdr_hres_, sdr_res_, DRAFT_SAMPLE_RES * 4, hipMemcpyDeviceToHost, stream_));
         HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
@@ -2663,10 +2726,10 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
         commit_rows(slot, &staged_token(0), 1 + m, /*past=*/true);              // the kept rows only: x0, draft[0 .. m)
         smp_draws_[slot] = c0 + 1 + (uint64_t)m;
         if (handle) con_state_[slot] = st.state[(size_t)m];
-        if (!sane) throw HipError{hipErrorUnknown, "verify_draft_sampled: the device reported an accepted count outside the pass", __FILE__, __LINE__};
+        if (!sane) throw HipError{hipErrorUnknown, EX ? "verify_draft_sampled_ex: the device reported an accepted count outside the pass" : "verify_draft_sampled: the device reported an accepted count outside the pass", __FILE__, __LINE__};
         for (int r = 0; r < R; r++) { if (row_sampled) row_sampled[r] = sdr_hres_[1 + r]; spec_info_.stuck += sdr_hres_[1 + DRAFT_ROWS + r] == 1; }
         next = sdr_hres_[1 + m];
-        device_id(next, "verify_draft_sampled: the device reported an id outside the vocabulary");
+        device_id(next, bad_pick);
     }
     spec_info_.accepted += m;
     ids_out[0] = x0; for (int i = 0; i < m; i++) ids_out[1 + i] = draft[i];
@@ -2675,10 +2738,19 @@ int Engine::verify_draft_sampled(const int *draft, int n_draft, float temp, int 
 }
 int Engine::decode_lookup_sampled(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p, int *tokens_out,
                                   int *n_tokens, int *stats) {
-    static const char *const name = "decode_lookup_sampled";
+    return decode_lookup_sampled_t<false>(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, temp, top_k, top_p, nullptr, tokens_out, n_tokens, stats);
+}
+int Engine::decode_lookup_sampled_ex(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p, const ChainParams &cp,
+                                     int *tokens_out, int *n_tokens, int *stats) {
+    return decode_lookup_sampled_t<true>(corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, temp, top_k, top_p, &cp, tokens_out, n_tokens, stats);
+}
+template <bool EX> int Engine::decode_lookup_sampled_t(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p,
+                                                       const ChainParams *cp, int *tokens_out, int *n_tokens, int *stats) {
+    static const char *const name = EX ? "decode_lookup_sampled_ex" : "decode_lookup_sampled";
     auto refuse = [](const char *what) { set_last_error(std::string(name) + ": " + what); return 1; };
     if (lookup_check(name, corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats)) return 1;
     if (!sampling_params_ok(refuse, temp, top_k, top_p)) return 1;
+    if (cp && !chain_params_ok(refuse, *cp)) return 1;
     if (weights_missing()) return 1;
     Conversation &cv = conv_[(size_t)cur_];
     if (cv.pend_tok.empty() && !cv.has_logits) return refuse("the conversation has no current logits");
@@ -2697,7 +2769,7 @@ int Engine::decode_lookup_sampled(const int *corpus, int n_corpus, int max_token
             nd = drafter.draft(std::min(n_draft, max_tokens - n - 1), d);
         }
         int got = 0, sent = 0;
-        if (verify_draft_sampled(d, nd, temp, top_k, top_p, ids, &got, &next, nullptr, nullptr, name, &sent)) return done(1);
+        if (verify_draft_sampled_t<EX>(d, nd, temp, top_k, top_p, cp, ids, &got, &next, nullptr, nullptr, name, &sent)) return done(1);
         // x0 is the announced token wherever the logits are the same; in fast mode a pass of another shape may have rounded a logit differently and moved the draw across a
         // boundary: the history takes what was emitted (the draft then missed: m = 0 or a lucky match, both within the rule)
         if (announced < 0 || announced == 2) drafter.push(ids[0]);

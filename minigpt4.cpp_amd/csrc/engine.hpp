@@ -209,6 +209,12 @@ public:
     // plain sampled step that also tells what comes next, so the loop needs no second decision path
     int decode_lookup_sampled(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p, int *tokens_out,
                               int *n_tokens, int *stats);
+    // the two calls with D(L, h, q, k) = the extended rule's chain (tfs_z, typical_p, min_p of cp; mirostat is not available here: mu at row r would depend on row
+    // r - 1's pick): the same bodies (verify_draft_sampled_t / decode_lookup_sampled_t), the extended staging block, k_sample_rows_ex and k_draft_sample_finish_ex
+    int verify_draft_sampled_ex(const int *draft, int n_draft, float temp, int top_k, float top_p, const ChainParams &cp, int *ids_out, int *n_out, int *next_out, int *row_sampled,
+                                float *row_logits);
+    int decode_lookup_sampled_ex(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p, const ChainParams &cp,
+                                 int *tokens_out, int *n_tokens, int *stats);
     // {sampled verify passes, rows evaluated, draft tokens sent, draft tokens accepted, sampling launches made by these calls, stuck picks, draft tokens cut by a constraint, 0}
     int speculation_info(long long out[8]) const;
 
@@ -284,6 +290,17 @@ public:
     int sampled_candidates(const int *slots, int n, float temp, int top_k, float top_p, int *ids_out, float *probs_out, int *n_cand_out, int *kept_out);
     int set_conversation_seed(int slot, uint64_t seed, uint64_t draws);
     int sampling_info(int slot, uint64_t out[6]) const;                    // {seed, draws, k_sample_rows launches, picks handed to a pass on the device, stuck picks, rows sampled}
+    // ---- the same two calls under the extended rule (sampling.hpp: sample_chain; minigpt4_amd.h states it): tail-free, typical, top-p, min-p, temperature, softmax and
+    // the draw over the live list, or mirostat v2 over the candidates.  The steps are decode_batch_sampled's own, one by one (one body: decode_batch_sampled_t), with a
+    // staging block of its own kind (SampleRowEx / SampleOutEx, allocated by the first _ex call, freed where smp_ is) and k_sample_rows_ex deciding; the counters of
+    // sampling_info count them.  Mirostat's mu is the conversation's, like (seed, draws): NaN = unset, 2 * tau at the first mirostat decision, moved by every
+    // decode_batch_sampled_ex decision with mirostat == 2 (the conversation advancing or not), read with the picks from the pinned block; reset, fork, shift and snapshot
+    // loads leave it alone, set_conversations unsets it, sampled_candidates_ex does not move it.  Refusals in addition to the plain calls': tfs_z or typical_p outside
+    // (0, 1], min_p outside [0, 1], mirostat not 0 or 2 (1: "mirostat v1 is not built"), tau not finite or <= 0, eta not finite or < 0.
+    int decode_batch_sampled_ex(const int *slots, int n, float temp, int top_k, float top_p, const ChainParams &cp, int *ids_out);
+    int sampled_candidates_ex(const int *slots, int n, float temp, int top_k, float top_p, const ChainParams &cp, int *ids_out, float *probs_out, int *n_cand_out, uint64_t *kept_mask_out);
+    int set_conversation_mirostat(int slot, float mu);                     // finite: mu; NaN: unset
+    int mirostat_info(int slot, float out[4]) const;                       // {set 0 / 1, mu, last observed surprise, last tau}
     // ---- snapshots (state.hpp: the format; minigpt4_amd.h: the rules).  A conversation leaves its slot, its context or its process as one checksummed blob and comes back
     // bit for bit: cache rows [0, n_rows), token history, logits row, greedy / feed token, penalty parameters and logit bias.  Not in a snapshot: the sampler's generator and
     // mirostat state (context-level), the constraint handle and state (handles are per context), queued rows (a save evaluates them first), the prefix store.
@@ -664,20 +681,39 @@ private:
     uint64_t smp_seed_[MAX_CONVERSATIONS] = {0}, smp_draws_[MAX_CONVERSATIONS] = {0}; uint32_t smp_load_seed_ = 0;
     struct SmpInfo { uint64_t launches = 0, handed = 0, stuck = 0, rows = 0; } smp_info_;
     Stage<SampleRow, SampleOut> smp_;
-    void smp_free() { smp_.reset(); }
-    void smp_reseed() { for (int s = 0; s < MAX_CONVERSATIONS; s++) { smp_seed_[s] = (uint64_t)smp_load_seed_ | (uint64_t)s << 32; smp_draws_[s] = 0; } }
-    // the checks and the queued rows of both entry points; 0, or 1 with last_error "<name>: ..."
-    int smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p);
+    // the extended rule: its staging block (first _ex call) and, per conversation, mirostat's mu (NaN: unset), the last observed surprise and the tau it was measured against
+    Stage<SampleRowEx, SampleOutEx> smpx_;
+    float smp_mu_[MAX_CONVERSATIONS], smp_observed_[MAX_CONVERSATIONS] = {0}, smp_tau_[MAX_CONVERSATIONS] = {0};
+    template <bool EX> auto &smp_block() { if constexpr (EX) return smpx_; else return smp_; }
+    static SampleRow &smp_plain(SampleRow &r) { return r; }
+    static SampleRow &smp_plain(SampleRowEx &r) { return r.base; }
+    static const SampleOut &smp_plain(const SampleOut &o) { return o; }
+    static const SampleOut &smp_plain(const SampleOutEx &o) { return o.base; }
+    void smp_free() { smp_.reset(); smpx_.reset(); }
+    void smp_reseed() {
+        for (int s = 0; s < MAX_CONVERSATIONS; s++) { smp_seed_[s] = (uint64_t)smp_load_seed_ | (uint64_t)s << 32; smp_draws_[s] = 0; smp_mu_[s] = NAN; smp_observed_[s] = smp_tau_[s] = 0.0f; }
+    }
+    // the checks and the queued rows of the entry points; 0, or 1 with last_error "<name>: ..."; cp (the _ex calls): its ranges, behind top_p's
+    int smp_prepare(const char *name, const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp = nullptr);
     // THE descriptor of one decision of conversation `slot`: its seed, the table `pen` describes, the allowed bitmap of constraint state `state` (no constraint: every id),
     // draw number `draws`; tok_index: the entry of d_btok_ that takes the pick (-1: none)
     SampleRow smp_row(int slot, const PenRow &pen, int state, uint64_t draws, int tok_index, float temp, int top_k, float top_p) const;
-    // the listed conversations' descriptors into smp_ (allocated here; row-token index -1), from each history as a sample sees it; the table entries staged
-    size_t smp_stage(const int *slots, int n, float temp, int top_k, float top_p);
+    // the listed conversations' descriptors into the block (allocated here; row-token index -1), from each history as a sample sees it; the table entries staged.
+    // EX: the block is smpx_, every descriptor carries *cp and its conversation's mu
+    template <bool EX = false> size_t smp_stage(const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp = nullptr);
     // n staged descriptors with n_ent entries: the upload and the launch over rows of `logits` (row_tok: picks go there at the descriptors' row-token indices), nothing
     // counted, no copy back (verify_draft_sampled: its launches are speculation_info's).  false: the launch was refused (last_error)
-    bool smp_launch_on(const float *logits, int n, size_t n_ent, int *row_tok = nullptr);
+    template <bool EX = false> bool smp_launch_on(const float *logits, int n, size_t n_ent, int *row_tok = nullptr);
     // ... over logits_ (hand: picks go to d_btok_), counted, the result block's copy back and the event queued
-    bool smp_launch(int n, size_t n_ent, bool hand);
+    template <bool EX = false> bool smp_launch(int n, size_t n_ent, bool hand);
+    // THE sampled step and THE report of what it would draw from, under the plain rule (EX false: cp unused) or the extended one
+    template <bool EX> int decode_batch_sampled_t(const char *name, const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp, int *ids_out);
+    template <bool EX> int verify_draft_sampled_t(const int *draft, int n_draft, float temp, int top_k, float top_p, const ChainParams *cp, int *ids_out, int *n_out, int *next_out,
+                                                  int *row_sampled, float *row_logits, const char *name, int *n_sent);
+    template <bool EX> int decode_lookup_sampled_t(const int *corpus, int n_corpus, int max_tokens, int ngram_max, int ngram_min, int n_draft, float temp, int top_k, float top_p,
+                                                   const ChainParams *cp, int *tokens_out, int *n_tokens, int *stats);
+    template <bool EX> int sampled_candidates_t(const char *name, const int *slots, int n, float temp, int top_k, float top_p, const ChainParams *cp, int *ids_out, float *probs_out,
+                                                int *n_cand_out, int *kept_out, uint64_t *kept_mask_out);
     // speculation under sampling.  Lazy, first call: one graph slot per row count (the verify pass without its epilogue), the result block {m, picks, stuck flags} and its
     // pinned mirror.  Dropped / freed where the greedy form's are (spec_drop_graphs, spec_free)
     std::vector<hipGraphExec_t> spec_sgraph_; DevPtr<int> sdr_res_; PinPtr<int> sdr_hres_;

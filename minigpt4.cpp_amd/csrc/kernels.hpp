@@ -281,12 +281,21 @@ bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, co
 // and the kernel's 12 KB do not fit 64 KB of LDS.
 struct SampleRow { PenRow pen; const unsigned *allowed; float temp, top_p; int top_k, tok_index; unsigned long long seed, draws; };   // 18 words
 bool launch_sample_rows(const float *logits, int ld, int n_vocab, int n_rows, const SampleRow *rows, const PenEntry *table, SampleOut *out, int *row_tok, hipStream_t s);
+// the same decision under the extended rule (sampling.hpp: sample_chain): the selection is launch_sample_rows', then tail-free, typical, top-p, min-p, temperature,
+// softmax and the draw over the live list -- or mirostat v2 over the candidates, from rows[r].chain.mu (NaN: 2 * tau).  out[r] = the plain result (kept = the
+// live list's length), then the 64-bit mask of the candidates left in it, mu' (mirostat 0: mu as given) and the observed surprise.  The chain's ranges (tfs_z and
+// typical_p in (0, 1], min_p in [0, 1], mirostat 0 or 2, tau > 0, eta >= 0) are the caller's to check.  Refusals as launch_sample_rows.
+struct SampleRowEx { SampleRow base; ChainParams chain; };   // 26 words
+bool launch_sample_rows_ex(const float *logits, int ld, int n_vocab, int n_rows, const SampleRowEx *rows, const PenEntry *table, SampleOutEx *out, int *row_tok, hipStream_t s);
 // verify pass epilogue under sampling, behind launch_sample_rows over the pass's R rows (picks[r] = the decision of logits row r, rows ld floats apart; tok[0 .. R) = the
 // pass's row tokens): m = the leading draft tokens the rows' own samples chose (tok[i + 1] == picks[i].pick); the logits of row m -> slot_logits[slot], slot = row_slot[0],
 // argmax[slot] = feed[slot] = the first maximum of that row, n_past[slot] += 1 + m; res = {m, picks [DRAFT_ROWS], stuck flags [DRAFT_ROWS]}, 1 + 2 DRAFT_ROWS ints.
 // false + last_error: a null array, R outside 1 .. DRAFT_ROWS, n_vocab < 1, ld < n_vocab.
 constexpr int DRAFT_SAMPLE_RES = 1 + 2 * DRAFT_ROWS;
 bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R, const int *tok, const SampleOut *picks, const int *row_slot, int *n_past, int *argmax, int *feed,
+                                float *slot_logits, int *res, hipStream_t s);
+// the same behind launch_sample_rows_ex (picks: its extended blocks)
+bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R, const int *tok, const SampleOutEx *picks, const int *row_slot, int *n_past, int *argmax, int *feed,
                                 float *slot_logits, int *res, hipStream_t s);
 // prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
 // sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)

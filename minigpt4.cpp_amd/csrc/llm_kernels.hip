@@ -3321,16 +3321,29 @@ bool launch_guide_rows(const float *logits, int ld, int n_vocab, int n_pairs, co
 // (-infinity through a bias is ordered like any value; NaN: unspecified).  The logits are read in place and never written; nothing beyond n_vocab floats of a row is read.
 // No spinning, no flags between workgroups, no global atomics; every loop is bounded by n_vocab or by the table length.
 // LDS: 12 KB static (8 KB histogram, 3 KB candidate lists, the ordered candidates) + dynamic 2 * constraint_words(n_vocab) bitmap words (8 KB at 32 001 ids).
-// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 51 VGPRs, 90 SGPRs, no scratch, 12080 bytes of static LDS, occupancy 8 waves per SIMD.
-__global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ logits, int ld, int n_vocab, const SampleRow *__restrict__ rows, const PenEntry *__restrict__ table,
-                                                     SampleOut *__restrict__ out, int *__restrict__ row_tok) {
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 51 VGPRs, 89 SGPRs, no scratch, 12080 bytes of static LDS, occupancy 8 waves per SIMD.
+// The extended rule (sample_chain) decides in k_sample_rows_ex: the same text up to the ordered candidates, then every thread enters sample_chain (its sequential sums are
+// thread 0's, the order typical sampling needs is placed one lane per candidate); its scratch is the candidate lists' LDS, dead by then.  rows[r] carries the chain's
+// parameters and the conversation's mu behind the plain descriptor, out[r] the mask of the candidates left in L, mu' and the observed surprise behind the plain result
+// (stuck: mask 0, mu as a mirostat decision finds it, observed 0).  The contract above holds for it word for word.
+// Resources of k_sample_rows_ex (gfx950, -Rpass-analysis=kernel-resource-usage): 54 VGPRs, 96 SGPRs, no scratch, 12096 bytes of static LDS, occupancy 8 waves per SIMD.
+inline __device__ const SampleRow &smp_base(const SampleRow &r) { return r; }
+inline __device__ const SampleRow &smp_base(const SampleRowEx &r) { return r.base; }
+inline __device__ SampleOut &smp_base(SampleOut &o) { return o; }
+inline __device__ SampleOut &smp_base(SampleOutEx &o) { return o.base; }
+template <typename Row, typename Out>
+__device__ __forceinline__ void sample_rows_body(const float *__restrict__ logits, int ld, int n_vocab, const Row *__restrict__ rows, const PenEntry *__restrict__ table,
+                                                 Out *__restrict__ out_x, int *__restrict__ row_tok) {
+    constexpr bool EX = std::is_same<Row, SampleRowEx>::value;
     constexpr int GT = SAMPLE_MAX, TIES = 256 - SAMPLE_MAX;
     extern __shared__ __attribute__((aligned(16))) unsigned smp_lds[];
     __shared__ unsigned hist[2048], sw[4], sres[2], ckey[256];
     __shared__ int cid[256], cnt[2], s_id[SAMPLE_MAX], s_res[2];
     __shared__ float cval[256], s_val[SAMPLE_MAX], s_p[SAMPLE_MAX];
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const SampleRow sr = rows[r];
+    const Row rx = rows[r];
+    const SampleRow &sr = smp_base(rx);
+    SampleOut &o = smp_base(out_x[r]);                                        // the plain result of row r
     if (tid < 2) cnt[tid] = 0;
     for (int i = tid; i < 2048; i += 256) hist[i] = 0;
     PickRow<true> row;                                                        // the transformed row's walk (pick_row.hpp); its barriers cover cnt and hist
@@ -3347,10 +3360,15 @@ __global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ l
     const uint32_t word = sample_word(sr.seed, sr.draws);
     __syncthreads();                                                          // sw is written again by topn_select
     if (total == 0) {                                                         // (uniform) nothing takes part: k_constrain_pick's answer
-        if (tid < SAMPLE_MAX) { out[r].ids[tid] = -1; out[r].p[tid] = 0.0f; }
+        if (tid < SAMPLE_MAX) { o.ids[tid] = -1; o.p[tid] = 0.0f; }
         if (tid == 0) {
-            out[r].pick = CONSTRAINT_EOS; out[r].stuck = 1; out[r].word = word; out[r].n_cand = 0; out[r].kept = 0;
+            o.pick = CONSTRAINT_EOS; o.stuck = 1; o.word = word; o.n_cand = 0; o.kept = 0;
             if (row_tok && sr.tok_index >= 0) row_tok[sr.tok_index] = CONSTRAINT_EOS < n_vocab ? CONSTRAINT_EOS : 0;
+            if constexpr (EX) {
+                const ChainParams &cp = rx.chain;
+                out_x[r].mask_lo = 0u; out_x[r].mask_hi = 0u; out_x[r].observed = 0.0f;
+                out_x[r].mu = cp.mirostat == 2 && cp.mu != cp.mu ? smp::mul(2.0f, cp.tau) : cp.mu;
+            }
         }
         return;
     }
@@ -3422,18 +3440,40 @@ __global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ l
         if (pos < k) { s_id[pos] = mi; s_val[pos] = cval[tid]; }
     }
     __syncthreads();
-    if (tid == 0) {
+    if constexpr (EX) {   // the candidate lists are dead: cval and cid become the chain's scratch (sa, sb | L, ord)
+        __shared__ ChainRes s_chain;
+        sample_chain(s_val, k, sr.temp, sr.top_p, rx.chain, word, tid, 256, s_p, cval, cval + SAMPLE_MAX, cid, cid + SAMPLE_MAX, &s_chain);
+        if (tid == 0) {
+            s_res[0] = s_id[s_chain.pick]; s_res[1] = s_chain.kept;
+            out_x[r].mask_lo = s_chain.mask_lo; out_x[r].mask_hi = s_chain.mask_hi; out_x[r].mu = s_chain.mu; out_x[r].observed = s_chain.observed;
+        }
+    } else if (tid == 0) {
         int kept;
         const int j = sample_rule(s_val, k, sr.temp, sr.top_p, word, s_p, &kept);
         s_res[0] = s_id[j]; s_res[1] = kept;
     }
     __syncthreads();
-    if (tid < SAMPLE_MAX) { out[r].ids[tid] = tid < k ? s_id[tid] : -1; out[r].p[tid] = tid < k ? s_p[tid] : 0.0f; }
+    if (tid < SAMPLE_MAX) { o.ids[tid] = tid < k ? s_id[tid] : -1; o.p[tid] = tid < k ? s_p[tid] : 0.0f; }
     if (tid == 0) {
         const int id = s_res[0];
-        out[r].pick = id; out[r].stuck = 0; out[r].word = word; out[r].n_cand = k; out[r].kept = s_res[1];
+        o.pick = id; o.stuck = 0; o.word = word; o.n_cand = k; o.kept = s_res[1];
         if (row_tok && sr.tok_index >= 0) row_tok[sr.tok_index] = id;
     }
+}
+__global__ __launch_bounds__(256) void k_sample_rows(const float *__restrict__ logits, int ld, int n_vocab, const SampleRow *__restrict__ rows, const PenEntry *__restrict__ table,
+                                                     SampleOut *__restrict__ out, int *__restrict__ row_tok) {
+    sample_rows_body(logits, ld, n_vocab, rows, table, out, row_tok);
+}
+__global__ __launch_bounds__(256) void k_sample_rows_ex(const float *__restrict__ logits, int ld, int n_vocab, const SampleRowEx *__restrict__ rows, const PenEntry *__restrict__ table,
+                                                        SampleOutEx *__restrict__ out, int *__restrict__ row_tok) {
+    sample_rows_body(logits, ld, n_vocab, rows, table, out, row_tok);
+}
+bool launch_sample_rows_ex(const float *logits, int ld, int n_vocab, int n_rows, const SampleRowEx *rows, const PenEntry *table, SampleOutEx *out, int *row_tok, hipStream_t s) {
+    const size_t lds = (size_t)2 * constraint_words(n_vocab) * 4;
+    if (!logits || !rows || !out || n_rows < 1 || n_vocab < 1 || ld < n_vocab || lds + 12 * 1024 + 256 > 64 * 1024) { set_last_error("launch_sample_rows_ex: shape out of range"); return false; }
+    note_kernel("k_sample_rows_ex");
+    hipLaunchKernelGGL(k_sample_rows_ex, dim3((unsigned)n_rows), dim3(256), lds, s, logits, ld, n_vocab, rows, table, out, row_tok);
+    return true;
 }
 bool launch_sample_rows(const float *logits, int ld, int n_vocab, int n_rows, const SampleRow *rows, const PenEntry *table, SampleOut *out, int *row_tok, hipStream_t s) {
     const size_t lds = (size_t)2 * constraint_words(n_vocab) * 4;
@@ -3450,11 +3490,16 @@ bool launch_sample_rows(const float *logits, int ld, int n_vocab, int n_rows, co
 // res = {m, picks [DRAFT_ROWS], stuck flags [DRAFT_ROWS]} (entries from R on are left alone).  The logits rows lie ld floats apart; nothing beyond n_vocab floats of a row is
 // read.  No flags or counters between workgroups, no spinning, no atomics; every loop is bounded by n_vocab or by R.
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 17 VGPRs, 41 SGPRs, no scratch, 128 bytes of static LDS, occupancy 8 waves per SIMD.
-__global__ __launch_bounds__(1024) void k_draft_sample_finish(const float *__restrict__ logits, int ld, int n_vocab, int R, const int *__restrict__ tok, const SampleOut *__restrict__ picks,
-                                                             const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax, int *__restrict__ feed,
-                                                             float *__restrict__ slot_logits, int *__restrict__ res) {
+// k_draft_sample_finish_ex: the same text over the extended decisions (k_sample_rows_ex's SampleOutEx blocks: the plain result leads each).
+// Resources of k_draft_sample_finish_ex (gfx950, -Rpass-analysis=kernel-resource-usage): 17 VGPRs, 41 SGPRs, no scratch, 128 bytes of static LDS, as the plain instance.
+inline __device__ const SampleOut &smp_base(const SampleOut &o) { return o; }
+inline __device__ const SampleOut &smp_base(const SampleOutEx &o) { return o.base; }
+template <typename Out>
+__device__ __forceinline__ void draft_sample_finish_body(const float *__restrict__ logits, int ld, int n_vocab, int R, const int *__restrict__ tok, const Out *__restrict__ picks,
+                                                         const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax, int *__restrict__ feed,
+                                                         float *__restrict__ slot_logits, int *__restrict__ res) {
     int m = 0;
-    while (m < R - 1 && tok[m + 1] == picks[m].pick) m++;                 // every thread: R <= 8 words, all in cache
+    while (m < R - 1 && tok[m + 1] == smp_base(picks[m]).pick) m++;       // every thread: R <= 8 words, all in cache
     const int slot = row_slot[0];
     const float *x = logits + (size_t)m * ld;
     float *keep = slot_logits + (size_t)slot * n_vocab;
@@ -3469,12 +3514,31 @@ __global__ __launch_bounds__(1024) void k_draft_sample_finish(const float *__res
     argmax_wave(best, bi);
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
-    if (threadIdx.x < R) { res[1 + threadIdx.x] = picks[threadIdx.x].pick; res[1 + DRAFT_ROWS + threadIdx.x] = picks[threadIdx.x].stuck; }
+    if (threadIdx.x < R) { res[1 + threadIdx.x] = smp_base(picks[threadIdx.x]).pick; res[1 + DRAFT_ROWS + threadIdx.x] = smp_base(picks[threadIdx.x]).stuck; }
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; w++) argmax_combine(best, bi, sv[w], si[w]);
         const int id = bi == 0x7FFFFFFF ? 0 : bi;
         argmax[slot] = id; feed[slot] = id; n_past[slot] += 1 + m; res[0] = m;
     }
+}
+__global__ __launch_bounds__(1024) void k_draft_sample_finish(const float *__restrict__ logits, int ld, int n_vocab, int R, const int *__restrict__ tok, const SampleOut *__restrict__ picks,
+                                                             const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax, int *__restrict__ feed,
+                                                             float *__restrict__ slot_logits, int *__restrict__ res) {
+    draft_sample_finish_body(logits, ld, n_vocab, R, tok, picks, row_slot, n_past, argmax, feed, slot_logits, res);
+}
+__global__ __launch_bounds__(1024) void k_draft_sample_finish_ex(const float *__restrict__ logits, int ld, int n_vocab, int R, const int *__restrict__ tok, const SampleOutEx *__restrict__ picks,
+                                                                const int *__restrict__ row_slot, int *__restrict__ n_past, int *__restrict__ argmax, int *__restrict__ feed,
+                                                                float *__restrict__ slot_logits, int *__restrict__ res) {
+    draft_sample_finish_body(logits, ld, n_vocab, R, tok, picks, row_slot, n_past, argmax, feed, slot_logits, res);
+}
+bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R, const int *tok, const SampleOutEx *picks, const int *row_slot, int *n_past, int *argmax, int *feed,
+                                float *slot_logits, int *res, hipStream_t s) {
+    if (!logits || !tok || !picks || !row_slot || !n_past || !argmax || !feed || !slot_logits || !res || R < 1 || R > DRAFT_ROWS || n_vocab < 1 || ld < n_vocab) {
+        set_last_error("launch_draft_sample_finish: shape out of range"); return false;
+    }
+    note_kernel("k_draft_sample_finish_ex");
+    hipLaunchKernelGGL(k_draft_sample_finish_ex, dim3(1), dim3(1024), 0, s, logits, ld, n_vocab, R, tok, picks, row_slot, n_past, argmax, feed, slot_logits, res);
+    return true;
 }
 bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R, const int *tok, const SampleOut *picks, const int *row_slot, int *n_past, int *argmax, int *feed,
                                 float *slot_logits, int *res, hipStream_t s) {

@@ -1373,6 +1373,61 @@ int minigpt4_amd_test_sample_rows(const float *logits, int buf_rows, int n_vocab
         return 0;
     });
 }
+// ---- the extended rule (sampling.hpp: sample_chain; launch_sample_rows_ex) ----
+// the ranges every caller of the chain checks (the engine's chain_params_ok states them with words)
+static bool chain_ok(float tfs_z, float typical_p, float min_p, int mirostat, float tau, float eta) {
+    return tfs_z > 0.0f && tfs_z <= 1.0f && typical_p > 0.0f && typical_p <= 1.0f && min_p >= 0.0f && min_p <= 1.0f && (mirostat == 0 || mirostat == 2) && std::isfinite(tau) &&
+           tau > 0.0f && std::isfinite(eta) && eta >= 0.0f;
+}
+int minigpt4_amd_test_sample_chain(const float *values, int n_cand, float temp, float top_p, float tfs_z, float typical_p, float min_p, int mirostat, float tau, float eta, float mu,
+                                   uint32_t word, float *p_out, int32_t *kept_out, uint64_t *mask_out, float *mu_out, float *observed_out) {
+    if (!values || !p_out || !kept_out || !mask_out || !mu_out || !observed_out || n_cand < 1 || n_cand > SAMPLE_MAX || !(temp > 0.0f) || !std::isfinite(temp) || !(top_p > 0.0f) ||
+        !chain_ok(tfs_z, typical_p, min_p, mirostat, tau, eta) || std::isinf(mu)) return -1;
+    float sa[SAMPLE_MAX], sb[SAMPLE_MAX]; int L[SAMPLE_MAX], ord[SAMPLE_MAX];
+    const ChainParams cp{tfs_z, typical_p, min_p, mirostat, tau, eta, mu, 0};
+    ChainRes res{};
+    sample_chain(values, n_cand, temp, top_p, cp, word, 0, 1, p_out, sa, sb, L, ord, &res);
+    *kept_out = res.kept; *mask_out = (uint64_t)res.mask_lo | (uint64_t)res.mask_hi << 32; *mu_out = res.mu; *observed_out = res.observed;
+    return res.pick;
+}
+// k_sample_rows_ex, one launch, on host logits [buf_rows][ld].  Everything that indexes device memory is checked here.
+int minigpt4_amd_test_sample_rows_ex(const float *logits, int buf_rows, int n_vocab, int ld, const int32_t *rows, int n_rows, const int32_t *table, int n_table, const uint32_t *bitmaps,
+                                     int n_bitmaps, const int32_t *bitmap_of_row, const float *temp_top_p, const int32_t *top_k, const uint64_t *seed_draws, const int32_t *tok_index,
+                                     const float *chain, const int32_t *mirostat, int32_t *row_tok_io, int32_t *out, float *ms_out) {
+    static_assert(sizeof(PenRow) == 32 && sizeof(PenEntry) == 16 && sizeof(SampleRowEx) == 104 && sizeof(SampleOutEx) == (9 + 2 * SAMPLE_MAX) * 4, "the hook's word layout");
+    if (!logits || !rows || !bitmap_of_row || !temp_top_p || !top_k || !seed_draws || !tok_index || !chain || !mirostat || !row_tok_io || !out || buf_rows < 1 || n_vocab < 1 ||
+        ld < n_vocab || n_rows < 1 || n_table < 0 || (n_table > 0 && !table) || n_bitmaps < 0 || (n_bitmaps > 0 && !bitmaps)) return 1;
+    if (!pen_rows_ok(rows, n_rows, table, n_table, buf_rows, n_vocab)) return 1;
+    for (int r = 0; r < n_rows; r++) {   // the other indices, and the parameters the engine checks
+        if (bitmap_of_row[r] < -1 || bitmap_of_row[r] >= n_bitmaps || tok_index[r] < -1 || tok_index[r] >= 64 || top_k[r] < 1 || top_k[r] > std::min(SAMPLE_MAX, n_vocab)) return 1;
+        const float temp = temp_top_p[2 * (size_t)r], top_p = temp_top_p[2 * (size_t)r + 1], *c = chain + 6 * (size_t)r;
+        if (!std::isfinite(temp) || !(temp > 0.0f) || !(top_p > 0.0f) || !(top_p <= 1.0f) || !chain_ok(c[0], c[1], c[2], mirostat[r], c[3], c[4]) || std::isinf(c[5])) return 1;
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)buf_rows * ld, R = (size_t)n_rows, T = (size_t)std::max(n_table, 1), W = (size_t)constraint_words(n_vocab), NB = (size_t)std::max(n_bitmaps, 1);
+        DevBuf dl(n * 4), dr(R * sizeof(SampleRowEx)), dt(T * sizeof(PenEntry)), dout(R * sizeof(SampleOutEx)), db(NB * W * 4), dtok(64 * 4);
+        std::vector<SampleRowEx> tab(R);
+        for (size_t r = 0; r < R; r++) {
+            SampleRow &b = tab[r].base;
+            memcpy(&b.pen, rows + 8 * r, sizeof(PenRow));
+            b.allowed = bitmap_of_row[r] < 0 ? nullptr : db.as<unsigned>() + (size_t)bitmap_of_row[r] * W;
+            b.temp = temp_top_p[2 * r]; b.top_p = temp_top_p[2 * r + 1]; b.top_k = top_k[r]; b.tok_index = tok_index[r];
+            b.seed = seed_draws[2 * r]; b.draws = seed_draws[2 * r + 1];
+            const float *c = chain + 6 * r;
+            tab[r].chain = ChainParams{c[0], c[1], c[2], mirostat[r], c[3], c[4], c[5], 0};
+        }
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dr.p, tab.data(), R * sizeof(SampleRowEx), hipMemcpyHostToDevice));
+        if (n_bitmaps > 0) HIP_CHECK(hipMemcpy(db.p, bitmaps, (size_t)n_bitmaps * W * 4, hipMemcpyHostToDevice));
+        if (n_table > 0) HIP_CHECK(hipMemcpy(dt.p, table, (size_t)n_table * sizeof(PenEntry), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dtok.p, row_tok_io, 64 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0xFF, R * sizeof(SampleOutEx)));                            // what the kernel leaves out shows as -1 / NaN
+        if (!timed(ms_out, [&] { return launch_sample_rows_ex(dl.as<float>(), ld, n_vocab, n_rows, dr.as<SampleRowEx>(), dt.as<PenEntry>(), dout.as<SampleOutEx>(), dtok.as<int>(), nullptr); })) return 3;
+        HIP_CHECK(hipMemcpy(out, dout.p, R * sizeof(SampleOutEx), hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(row_tok_io, dtok.p, 64 * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ---- speculation under sampling (draft_host.hpp, launch_draft_sample_finish) ----
 // The sampled verify pass's epilogue alone: k_sample_rows over the R rows of host logits [R][ld], then k_draft_sample_finish on a two-slot state.  Everything that indexes
 // device memory is checked here.

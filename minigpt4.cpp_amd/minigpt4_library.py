@@ -261,6 +261,10 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_sampled_candidates.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, INT_PTR, FLOAT_PTR, INT_PTR, INT_PTR]
         L.minigpt4_amd_conversation_seed.argtypes = [VOID_PTR, I32, ctypes.c_uint64, ctypes.c_uint64]
         L.minigpt4_amd_sampling_info.argtypes = [VOID_PTR, I32, U64P]
+        L.minigpt4_amd_end_chat_batch_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, P(ctypes.c_char_p), F32, I32, F32, F32, F32, F32, I32, F32, F32, INT_PTR]
+        L.minigpt4_amd_sampled_candidates_ex.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, F32, F32, F32, I32, F32, F32, INT_PTR, FLOAT_PTR, INT_PTR, U64P]
+        L.minigpt4_amd_conversation_mirostat.argtypes = [VOID_PTR, I32, F32]
+        L.minigpt4_amd_mirostat_info.argtypes = [VOID_PTR, I32, FLOAT_PTR]
         I64P = P(ctypes.c_int64)
         L.minigpt4_amd_state_size.argtypes = [VOID_PTR, I32]
         L.minigpt4_amd_state_size.restype = SIZE_T
@@ -273,6 +277,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_verify_draft_sampled.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_decode_lookup_sampled.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, F32, I32, F32, INT_PTR, INT_PTR, INT_PTR]
         L.minigpt4_amd_speculation_info.argtypes = [VOID_PTR, I64P]
+        L.minigpt4_amd_verify_draft_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, F32, F32, F32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_decode_lookup_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, F32, I32, F32, F32, F32, F32, INT_PTR, INT_PTR, INT_PTR]
 
     @staticmethod
     def _declare_test_hooks(L):
@@ -333,6 +339,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_sample_rule.argtypes = [FLOAT_PTR, I32, F32, F32, ctypes.c_uint32, FLOAT_PTR, INT_PTR]
         L.minigpt4_amd_test_sample_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, U32P, I32, INT_PTR, FLOAT_PTR, INT_PTR, U64P, INT_PTR, INT_PTR, INT_PTR,
                                                     FLOAT_PTR]
+        L.minigpt4_amd_test_sample_chain.argtypes = [FLOAT_PTR, I32, F32, F32, F32, F32, F32, I32, F32, F32, F32, ctypes.c_uint32, FLOAT_PTR, INT_PTR, U64P, FLOAT_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_sample_rows_ex.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, INT_PTR, I32, U32P, I32, INT_PTR, FLOAT_PTR, INT_PTR, U64P, INT_PTR, FLOAT_PTR, INT_PTR,
+                                                       INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_draft_sample.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, INT_PTR, I32, U32P, I32, INT_PTR, FLOAT_PTR, INT_PTR, U64P, INT_PTR, I32, INT_PTR, FLOAT_PTR,
                                                      INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_draft_tables.argtypes = [INT_PTR, I32, I32, INT_PTR, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, I32, I32, U16P, U32P, I32, I32, P(ctypes.c_uint8),
@@ -604,19 +613,26 @@ class MiniGPT4SharedLibrary:
 
     SPECULATION_INFO_FIELDS = ("passes", "rows", "sent", "accepted", "launches", "stuck", "cut")
 
-    def amd_verify_draft_sampled(self, ctx, draft: Sequence[int], temp=0.8, top_k=40, top_p=0.9, want_rows: bool = False, want_logits: bool = False) -> dict:
+    def amd_verify_draft_sampled(self, ctx, draft: Sequence[int], temp=0.8, top_k=40, top_p=0.9, want_rows: bool = False, want_logits: bool = False, tfs_z=1.0, typical_p=1.0,
+                                 min_p=0.0) -> dict:
         """amd_verify_draft under sampling: every row of the pass is sampled with the draw plain sampled decoding (amd_end_chat_batch_sampled) would use at its position; a
         draft token is kept exactly when the sample of the row before it equals it.  dict(ids [1 + m] i32: the emitted tokens; next: the sample of row m, which the next
         decision recomputes (draft behind it); want_rows: row_sampled [1 + len(draft)] i32, -1 for a row not evaluated; want_logits: row_logits [1 + len(draft)][n_vocab]
-        f32, NaN rows where not evaluated).  include/minigpt4_amd.h states the rule."""
+        f32, NaN rows where not evaluated).  include/minigpt4_amd.h states the rule.  A non-neutral tfs_z, typical_p or min_p sends the call to
+        minigpt4_amd_verify_draft_sampled_ex: every row is decided by the extended rule (no mirostat there)."""
+        ex = self._chain_args("verify_draft_sampled", tfs_z, typical_p, min_p, 0, 5.0, 0.1)
         d = np.ascontiguousarray(draft, np.int32).reshape(-1)
         n = len(d)
         ids, n_out, nxt = np.zeros(n + 1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
         rs = np.zeros(n + 1, np.int32) if want_rows else None
         rl = np.full((n + 1, int(self.library.minigpt4_amd_n_vocab(ctx.ptr))), np.nan, np.float32) if want_logits and ctx is not None else None
-        rc = self.library.minigpt4_amd_verify_draft_sampled(ctx.ptr if ctx is not None else None, d.ctypes.data_as(INT_PTR) if n else None, n, float(temp), int(top_k), float(top_p),
-                                                            ids.ctypes.data_as(INT_PTR), n_out.ctypes.data_as(INT_PTR), nxt.ctypes.data_as(INT_PTR),
-                                                            rs.ctypes.data_as(INT_PTR) if rs is not None else None, rl.ctypes.data_as(FLOAT_PTR) if rl is not None else None)
+        head = (ctx.ptr if ctx is not None else None, d.ctypes.data_as(INT_PTR) if n else None, n, float(temp), int(top_k), float(top_p))
+        tail = (ids.ctypes.data_as(INT_PTR), n_out.ctypes.data_as(INT_PTR), nxt.ctypes.data_as(INT_PTR), rs.ctypes.data_as(INT_PTR) if rs is not None else None,
+                rl.ctypes.data_as(FLOAT_PTR) if rl is not None else None)
+        if ex:
+            rc = self.library.minigpt4_amd_verify_draft_sampled_ex(*head, float(tfs_z), float(typical_p), float(min_p), *tail)
+        else:
+            rc = self.library.minigpt4_amd_verify_draft_sampled(*head, *tail)
         if rc:
             raise RuntimeError("verify_draft_sampled failed: " + self._err())
         out = dict(ids=ids[:int(n_out[0])].copy(), next=int(nxt[0]))
@@ -627,13 +643,20 @@ class MiniGPT4SharedLibrary:
         return out
 
     def amd_decode_lookup_sampled(self, ctx, corpus: Sequence[int], max_tokens: int, ngram_max: int = 3, ngram_min: int = 1, n_draft: int = 4, temp=0.8, top_k=40,
-                                  top_p=0.9) -> dict:
-        """amd_decode_lookup under sampling (amd_verify_draft_sampled per step; no match: its n_draft = 0 form).  dict(tokens [n] i32, passes, steps, sent, accepted)."""
+                                  top_p=0.9, tfs_z=1.0, typical_p=1.0, min_p=0.0) -> dict:
+        """amd_decode_lookup under sampling (amd_verify_draft_sampled per step; no match: its n_draft = 0 form).  dict(tokens [n] i32, passes, steps, sent, accepted).
+        A non-neutral tfs_z, typical_p or min_p: minigpt4_amd_decode_lookup_sampled_ex, the extended rule on every row."""
+        ex = self._chain_args("decode_lookup_sampled", tfs_z, typical_p, min_p, 0, 5.0, 0.1)
         c = np.ascontiguousarray(corpus, np.int32).reshape(-1)
         out, n, st = np.zeros(max(int(max_tokens), 1), np.int32), np.zeros(1, np.int32), np.zeros(4, np.int32)
-        if self.library.minigpt4_amd_decode_lookup_sampled(ctx.ptr if ctx is not None else None, c.ctypes.data_as(INT_PTR) if len(c) else None, len(c), int(max_tokens),
-                                                           int(ngram_max), int(ngram_min), int(n_draft), float(temp), int(top_k), float(top_p), out.ctypes.data_as(INT_PTR),
-                                                           n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR)):
+        head = (ctx.ptr if ctx is not None else None, c.ctypes.data_as(INT_PTR) if len(c) else None, len(c), int(max_tokens), int(ngram_max), int(ngram_min), int(n_draft),
+                float(temp), int(top_k), float(top_p))
+        tail = (out.ctypes.data_as(INT_PTR), n.ctypes.data_as(INT_PTR), st.ctypes.data_as(INT_PTR))
+        if ex:
+            rc = self.library.minigpt4_amd_decode_lookup_sampled_ex(*head, float(tfs_z), float(typical_p), float(min_p), *tail)
+        else:
+            rc = self.library.minigpt4_amd_decode_lookup_sampled(*head, *tail)
+        if rc:
             raise RuntimeError("decode_lookup_sampled failed: " + self._err())
         return dict(tokens=out[:int(n[0])].copy(), passes=int(st[0]), steps=int(st[1]), sent=int(st[2]), accepted=int(st[3]))
 
@@ -1222,29 +1245,87 @@ class MiniGPT4SharedLibrary:
             raise ValueError(f"{name}: top_p outside (0, 1]")
         return sl
 
-    def amd_end_chat_batch_sampled(self, ctx, slots: Sequence[int], temp=0.8, top_k=40, top_p=0.9, with_ids: bool = False):
+    @staticmethod
+    def _chain_args(name: str, tfs_z, typical_p, min_p, mirostat, mirostat_tau, mirostat_eta) -> bool:
+        """True when any parameter of the extended rule is not neutral (the call then goes to the _ex entry point); ValueError before the library is touched."""
+        f = lambda x: ctypes.c_float(float(x)).value                                      # as the fp32 the library takes
+        z, ty, mp, tau, eta = f(tfs_z), f(typical_p), f(min_p), f(mirostat_tau), f(mirostat_eta)
+        if not (0 < z <= 1):
+            raise ValueError(f"{name}: tfs_z outside (0, 1]")
+        if not (0 < ty <= 1):
+            raise ValueError(f"{name}: typical_p outside (0, 1]")
+        if not (0 <= mp <= 1):
+            raise ValueError(f"{name}: min_p outside [0, 1]")
+        if int(mirostat) != mirostat or int(mirostat) not in (0, 1, 2):
+            raise ValueError(f"{name}: mirostat must be 0 or 2")
+        if int(mirostat) == 1:
+            raise ValueError(f"{name}: mirostat v1 is not built")
+        if not (np.isfinite(tau) and tau > 0):
+            raise ValueError(f"{name}: mirostat_tau must be finite and > 0")
+        if not (np.isfinite(eta) and eta >= 0):
+            raise ValueError(f"{name}: mirostat_eta must be finite and >= 0")
+        return z < 1 or ty < 1 or mp > 0 or int(mirostat) != 0
+
+    def amd_end_chat_batch_sampled(self, ctx, slots: Sequence[int], temp=0.8, top_k=40, top_p=0.9, with_ids: bool = False, tfs_z=1.0, typical_p=1.0, min_p=0.0, mirostat=0,
+                                   mirostat_tau=5.0, mirostat_eta=0.1, _extended: Optional[bool] = None):
         """One minigpt4_amd_end_chat_batch step whose tokens are sampled ON THE DEVICE, every conversation from its own (seed, draws) stream, and handed to the weight pass
-        without a host visit.  Returns one piece per conversation; with_ids: (pieces, ids i32 array).  include/minigpt4_amd.h states the rule."""
+        without a host visit.  Returns one piece per conversation; with_ids: (pieces, ids i32 array).  include/minigpt4_amd.h states the rule.  A non-neutral tfs_z,
+        typical_p, min_p or mirostat sends the call to minigpt4_amd_end_chat_batch_sampled_ex, the extended rule; mirostat's mu is the conversation's.  _extended (a test and
+        measurement aid): True sends neutral values there too."""
         sl = self._sampled_args("end_chat_batch_sampled", slots, temp, top_k, top_p)
+        ex = self._chain_args("end_chat_batch_sampled", tfs_z, typical_p, min_p, mirostat, mirostat_tau, mirostat_eta)
         toks, ids = (ctypes.c_char_p * len(sl))(), np.zeros(len(sl), np.int32)
-        rc = self.library.minigpt4_amd_end_chat_batch_sampled(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), len(sl), toks, float(temp), int(top_k), float(top_p),
-                                                              ids.ctypes.data_as(INT_PTR))
+        cp = ctx.ptr if ctx is not None else None
+        if ex if _extended is None else _extended:
+            rc = self.library.minigpt4_amd_end_chat_batch_sampled_ex(cp, sl.ctypes.data_as(INT_PTR), len(sl), toks, float(temp), int(top_k), float(top_p), float(tfs_z),
+                                                                     float(typical_p), float(min_p), int(mirostat), float(mirostat_tau), float(mirostat_eta),
+                                                                     ids.ctypes.data_as(INT_PTR))
+        else:
+            rc = self.library.minigpt4_amd_end_chat_batch_sampled(cp, sl.ctypes.data_as(INT_PTR), len(sl), toks, float(temp), int(top_k), float(top_p), ids.ctypes.data_as(INT_PTR))
         if rc:
             raise RuntimeError("end_chat_batch_sampled failed: " + self._err())
         pieces = [(t or b"").decode("utf-8", errors="replace") for t in toks]
         return (pieces, ids) if with_ids else pieces
 
-    def amd_sampled_candidates(self, ctx, slots: Sequence[int], temp=0.8, top_k=40, top_p=0.9) -> dict:
+    def amd_sampled_candidates(self, ctx, slots: Sequence[int], temp=0.8, top_k=40, top_p=0.9, tfs_z=1.0, typical_p=1.0, min_p=0.0, mirostat=0, mirostat_tau=5.0,
+                               mirostat_eta=0.1, _extended: Optional[bool] = None) -> dict:
         """The distribution the next sampled step would draw from; nothing advances, no draw is counted.  dict(ids i32 [n][64] (-1 behind n_cand), probs f32 [n][64] (0 behind
-        kept), n_cand i32 [n], kept i32 [n])."""
+        kept), n_cand i32 [n], kept i32 [n]).  A non-neutral tfs_z, typical_p, min_p or mirostat (_extended=True, a test aid: neutral values too): minigpt4_amd_sampled_candidates_ex, probs 0 for a
+        candidate outside the live list, and kept_mask uint64 [n] (bit j: candidate j is in it; kept = its population count); mu does not move."""
         sl = self._sampled_args("sampled_candidates", slots, temp, top_k, top_p)
+        ex = self._chain_args("sampled_candidates", tfs_z, typical_p, min_p, mirostat, mirostat_tau, mirostat_eta)
         n = len(sl)
         ids, probs, nc, kept = np.zeros((n, 64), np.int32), np.zeros((n, 64), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
-        rc = self.library.minigpt4_amd_sampled_candidates(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR), n, float(temp), int(top_k), float(top_p),
+        cp = ctx.ptr if ctx is not None else None
+        if ex if _extended is None else _extended:
+            mask = np.zeros(n, np.uint64)
+            rc = self.library.minigpt4_amd_sampled_candidates_ex(cp, sl.ctypes.data_as(INT_PTR), n, float(temp), int(top_k), float(top_p), float(tfs_z), float(typical_p),
+                                                                 float(min_p), int(mirostat), float(mirostat_tau), float(mirostat_eta), ids.ctypes.data_as(INT_PTR),
+                                                                 probs.ctypes.data_as(FLOAT_PTR), nc.ctypes.data_as(INT_PTR), mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+            if rc:
+                raise RuntimeError("sampled_candidates failed: " + self._err())
+            kept = np.array([bin(int(m)).count("1") for m in mask], np.int32)
+            return dict(ids=ids, probs=probs, n_cand=nc, kept=kept, kept_mask=mask)
+        rc = self.library.minigpt4_amd_sampled_candidates(cp, sl.ctypes.data_as(INT_PTR), n, float(temp), int(top_k), float(top_p),
                                                           ids.ctypes.data_as(INT_PTR), probs.ctypes.data_as(FLOAT_PTR), nc.ctypes.data_as(INT_PTR), kept.ctypes.data_as(INT_PTR))
         if rc:
             raise RuntimeError("sampled_candidates failed: " + self._err())
         return dict(ids=ids, probs=probs, n_cand=nc, kept=kept)
+
+    def amd_conversation_mirostat(self, ctx, slot: int, mu: Optional[float]) -> None:
+        """Set a conversation's mirostat mu (a finite value), or unset it (None / NaN): the next mirostat decision then starts from 2 * tau."""
+        m = float("nan") if mu is None else ctypes.c_float(float(mu)).value
+        if np.isinf(m):
+            raise ValueError("conversation_mirostat: mu must be finite (None unsets it)")
+        if self.library.minigpt4_amd_conversation_mirostat(ctx.ptr if ctx is not None else None, int(slot), m):
+            raise RuntimeError("conversation_mirostat failed: " + self._err())
+
+    def amd_mirostat_info(self, ctx, slot: int = 0) -> dict:
+        """dict(set: bool, mu: f32 (None when unset), observed: the last observed surprise, tau: the tau it was measured against) of one conversation."""
+        o = np.zeros(4, np.float32)
+        if self.library.minigpt4_amd_mirostat_info(ctx.ptr if ctx is not None else None, int(slot), o.ctypes.data_as(FLOAT_PTR)):
+            raise RuntimeError("mirostat_info failed: " + self._err())
+        return dict(set=bool(o[0]), mu=o[1] if o[0] else None, observed=o[2], tau=o[3])
 
     def amd_conversation_seed(self, ctx, slot: int, seed: int, draws: int = 0) -> None:
         """Set a conversation's 64-bit seed and its count of draws (the next draw's Philox counter)."""
@@ -1314,6 +1395,56 @@ class MiniGPT4SharedLibrary:
         out = out[:n]
         return dict(pick=out[:, 0].copy(), stuck=out[:, 1].copy(), word=out[:, 2].copy().view(np.uint32), n_cand=out[:, 3].copy(), kept=out[:, 4].copy(),
                     ids=out[:, 5:69].copy(), p=np.ascontiguousarray(out[:, 69:133]).view(np.float32), row_tok=rt, ms=float(ms.value))
+
+    def amd_test_sample_chain(self, values, temp: float, top_p: float, word: int, tfs_z=1.0, typical_p=1.0, min_p=0.0, mirostat=0, mirostat_tau=5.0, mirostat_eta=0.1,
+                              mu=None) -> dict:
+        """The extended rule's host side on the candidate values (in order) with the given Philox word (host hook, no GPU); mu None: unset.  dict(pick index, kept = the
+        live list's length, p f32 [n], mask: bit j = candidate j is in the live list, mu: mu' (mirostat 0: as given), observed)."""
+        v = np.ascontiguousarray(values, np.float32).reshape(-1)
+        p, kept, mask, mu_o, obs = np.zeros(max(len(v), 1), np.float32), I32(0), ctypes.c_uint64(0), ctypes.c_float(), ctypes.c_float()
+        pick = self.library.minigpt4_amd_test_sample_chain(v.ctypes.data_as(FLOAT_PTR), len(v), float(temp), float(top_p), float(tfs_z), float(typical_p), float(min_p), int(mirostat),
+                                                           float(mirostat_tau), float(mirostat_eta), float("nan") if mu is None else float(mu), int(word) & 0xFFFFFFFF,
+                                                           p.ctypes.data_as(FLOAT_PTR), ctypes.byref(kept), ctypes.byref(mask), ctypes.byref(mu_o), ctypes.byref(obs))
+        if pick < 0:
+            raise ValueError("test_sample_chain: bad arguments")
+        return dict(pick=int(pick), kept=int(kept.value), p=p[:len(v)], mask=int(mask.value), mu=np.float32(mu_o.value), observed=np.float32(obs.value))
+
+    def amd_test_sample_rows_ex(self, logits: np.ndarray, n_vocab: int, rows: np.ndarray, table: np.ndarray, params, top_k, seed_draws, chain, bitmaps=None, bitmap_of_row=None,
+                                tok_index=None, row_tok: Optional[Sequence[int]] = None) -> dict:
+        """k_sample_rows_ex alone on host logits [buf_rows][ld] (include/minigpt4_amd_test.h): the arguments of amd_test_sample_rows and chain [n][7] = (tfs_z, typical_p,
+        min_p, mirostat, tau, eta, mu; mu NaN: unset).  The dict of amd_test_sample_rows (kept = the live list's length) and mask uint64 [n], mu f32 [n], observed f32 [n]."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2
+        rw = np.ascontiguousarray(rows, np.int32).reshape(-1, 8)
+        n = len(rw)
+        tb = np.ascontiguousarray(table, np.int32).reshape(-1, 4)
+        pr = np.ascontiguousarray(params, np.float32).reshape(-1, 2)
+        tk = np.ascontiguousarray(top_k, np.int32).reshape(-1)
+        sd = np.ascontiguousarray(seed_draws, np.uint64).reshape(-1, 2)
+        ch = np.asarray(chain, np.float64).reshape(-1, 7)
+        cf, mi = np.ascontiguousarray(ch[:, [0, 1, 2, 4, 5, 6]], np.float32), np.ascontiguousarray(ch[:, 3], np.int32)
+        W = ((int(n_vocab) + 31) // 32 + 3) // 4 * 4
+        bm = np.zeros((0, W), np.uint32) if bitmaps is None else np.ascontiguousarray(bitmaps, np.uint32)
+        assert bm.ndim == 2 and bm.shape[1] == W
+        br = np.full(n, -1, np.int32) if bitmap_of_row is None else np.ascontiguousarray(bitmap_of_row, np.int32).reshape(-1)
+        ti = np.full(n, -1, np.int32) if tok_index is None else np.ascontiguousarray(tok_index, np.int32).reshape(-1)
+        assert len(pr) == n and len(tk) == n and len(sd) == n and len(br) == n and len(ti) == n and len(cf) == n
+        rt = np.full(64, -7, np.int32) if row_tok is None else np.ascontiguousarray(row_tok, np.int32).copy()
+        assert rt.shape == (64,)
+        out, ms = np.zeros((max(n, 1), 9 + 128), np.int32), ctypes.c_float()
+        U32P = ctypes.POINTER(ctypes.c_uint32)
+        rc = self.library.minigpt4_amd_test_sample_rows_ex(lg.ctypes.data_as(FLOAT_PTR), lg.shape[0], int(n_vocab), lg.shape[1], rw.ctypes.data_as(INT_PTR), n,
+                                                           tb.ctypes.data_as(INT_PTR) if len(tb) else None, len(tb), bm.ctypes.data_as(U32P) if len(bm) else None, len(bm),
+                                                           br.ctypes.data_as(INT_PTR), pr.ctypes.data_as(FLOAT_PTR), tk.ctypes.data_as(INT_PTR),
+                                                           sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ti.ctypes.data_as(INT_PTR), cf.ctypes.data_as(FLOAT_PTR),
+                                                           mi.ctypes.data_as(INT_PTR), rt.ctypes.data_as(INT_PTR), out.ctypes.data_as(INT_PTR), ctypes.byref(ms))
+        if rc:
+            raise RuntimeError(f"test_sample_rows_ex rc={rc}: " + self._err())
+        out = out[:n]
+        mask = out[:, 133].copy().view(np.uint32).astype(np.uint64) | out[:, 134].copy().view(np.uint32).astype(np.uint64) << np.uint64(32)
+        return dict(pick=out[:, 0].copy(), stuck=out[:, 1].copy(), word=out[:, 2].copy().view(np.uint32), n_cand=out[:, 3].copy(), kept=out[:, 4].copy(),
+                    ids=out[:, 5:69].copy(), p=np.ascontiguousarray(out[:, 69:133]).view(np.float32), mask=mask, mu=out[:, 135].copy().view(np.float32),
+                    observed=out[:, 136].copy().view(np.float32), row_tok=rt, ms=float(ms.value))
 
     def amd_token_piece(self, ctx, token_id: int) -> Optional[str]:
         """The text of one token id, as minigpt4_end_chat returns it ("</s>" for id 2); None for an id outside the vocabulary."""

@@ -93,8 +93,13 @@ class ReplicaServer:
             batched_prefill: bool = False, logprobs: int = 0, repeat_penalty: float = 1.0, repeat_last_n: int = 64, presence_penalty: float = 0.0,
             frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
             negative_prompt: Optional[str] = None, regex=None, sessions: Optional[Sequence] = None, device_sampling: bool = False,
-            seeds: Optional[Sequence[int]] = None) -> List[str]:
-        """device_sampling (the decode loop only, temp > 0): every step is ONE `minigpt4_amd_end_chat_batch_sampled` -- the tokens are sampled on the device (top-k <= 64,
+            seeds: Optional[Sequence[int]] = None, tfs_z: float = 1.0, typical_p: float = 1.0, min_p: float = 0.0, mirostat: int = 0, mirostat_tau: float = 5.0,
+            mirostat_eta: float = 0.1) -> List[str]:
+        """tfs_z, typical_p, min_p, mirostat (0 or 2), mirostat_tau, mirostat_eta: the extended rule of device-side sampling (include/minigpt4_amd.h), honoured with
+        device_sampling=True -- every step is then ONE `minigpt4_amd_end_chat_batch_sampled_ex`, and a request's mirostat mu is its own: unset
+        (`minigpt4_amd_conversation_mirostat`) when the request takes its slot, so its text does not depend on its partners.  A non-neutral value without
+        device_sampling raises ValueError (the host chain's mirostat state is the context's).
+        device_sampling (the decode loop only, temp > 0): every step is ONE `minigpt4_amd_end_chat_batch_sampled` -- the tokens are sampled on the device (top-k <= 64,
         top-p, temperature; include/minigpt4_amd.h states the rule) and handed to the weight pass without a host visit, and every request draws from a stream of its own:
         seeds (one 64-bit integer per request; None: the request's index) is set with `minigpt4_amd_conversation_seed(slot, seed, 0)` when the request takes its slot, so
         a request's text does not depend on which other requests share its wave or on its slot.  Works with regex, penalties and logit_bias; ValueError together with
@@ -149,6 +154,11 @@ class ReplicaServer:
             seeds = [int(s_) & 0xFFFFFFFFFFFFFFFF for s_ in (range(len(requests)) if seeds is None else seeds)]
         elif seeds is not None:
             raise ValueError("seeds needs device_sampling=True")
+        chain = dict(tfs_z=tfs_z, typical_p=typical_p, min_p=min_p, mirostat=mirostat, mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta)
+        extended = lib._chain_args("device_sampling", **chain)               # ValueError "device_sampling: ..." for a value out of range
+        if extended and not device_sampling:
+            raise ValueError("tfs_z, typical_p, min_p and mirostat need device_sampling=True")
+        chain = chain if extended else None
         if sessions is not None:
             if num_beams > 1 or guided:
                 raise ValueError("sessions is not available with num_beams > 1 or guidance_scale != 1")
@@ -167,7 +177,7 @@ class ReplicaServer:
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
-                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None)
+                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None, chain)
         finally:
             if self._constraint:
                 for slot in range(self.conversations):
@@ -205,7 +215,7 @@ class ReplicaServer:
                 shown += piece
         return shown
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None) -> List[str]:
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None, chain=None) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         if penalised:
@@ -244,6 +254,8 @@ class ReplicaServer:
                         lib.amd_set_constraint(ctx, slot, self._constraint)   # (also returns the state to the start)
                     if seeds is not None:
                         lib.amd_conversation_seed(ctx, slot, seeds[i], 0)     # the request's own stream, from its first draw
+                        if chain is not None:
+                            lib.amd_conversation_mirostat(ctx, slot, None)    # and its own mu, unset
                     if guidance is not None:                  # the guidance conversation: the same question (or the negative prompt) asked without the image
                         lib.amd_select_conversation(ctx, slot + 1)
                         lib.minigpt4_reset_chat(ctx)
@@ -270,7 +282,7 @@ class ReplicaServer:
                     elif guidance is not None:
                         pieces = lib.amd_end_chat_guided(ctx, [2 * slot for slot in active], [2 * slot + 1 for slot in active], guidance, temp=temp, top_k=top_k, top_p=top_p)
                     elif seeds is not None:
-                        pieces = lib.amd_end_chat_batch_sampled(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
+                        pieces = lib.amd_end_chat_batch_sampled(ctx, active, temp=temp, top_k=top_k, top_p=top_p, **(chain or {}))
                     else:
                         pieces = lib.amd_end_chat_batch(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
                     nxt = []
@@ -321,7 +333,8 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
     try:
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
                                                                                                 "presence_penalty", "frequency_penalty", "logit_bias", "num_beams",
-                                                                                                "length_penalty", "guidance_scale", "negative_prompt", "regex", "device_sampling")},
+                                                                                                "length_penalty", "guidance_scale", "negative_prompt", "regex", "device_sampling",
+                                                                                                "tfs_z", "typical_p", "min_p", "mirostat", "mirostat_tau", "mirostat_eta")},
                          **({"seeds": [(kw["seeds"][i] if kw.get("seeds") is not None else i) for i in mine]} if kw.get("device_sampling") or kw.get("seeds") is not None else {}))   # a request's seed follows it to its rank
     finally:
         server.close()
