@@ -538,6 +538,48 @@ MINIGPT4_API int minigpt4_amd_decode_lookup_sampled_ex(struct MiniGPT4Context *c
                                                        float temp, int32_t top_k, float top_p, float tfs_z, float typical_p, float min_p, int32_t *tokens_out, int32_t *n_tokens,
                                                        int32_t stats[4]);
 
+/* ---- speculation for SEVERAL conversations: the drafts of n conversations verified in one weight pass (greedy) --------------------------------------------------
+ * minigpt4_amd_verify_draft puts 1 + n_draft rows of ONE conversation through a pass; the batched step (minigpt4_amd_end_chat_batch) puts ONE row of each of many through
+ * it.  Here conversation slots[i] brings its greedy token g0_i and counts[i] draft tokens: a group of 1 + counts[i] rows at consecutive positions.  The groups are packed
+ * into ONE pass of N = n + sum(counts) <= 64 rows -- the batched step's mat-vec launches at N rows (dot4 / row-interleaved MFMA up to 4 rows, the int8-MFMA set launches
+ * from 5), an attention launch that is causal inside each group and reads nothing of another conversation, an epilogue with one decision per conversation -- and every
+ * conversation keeps the guesses the pass's own logits confirm.  Needs minigpt4_amd_set_speculation(max_draft >= 1); the pass allocates N-row logits, a 128-word result
+ * block and one captured pass per TOTAL row count at first use (the grouping is data in device memory: one graph serves every grouping), freed and dropped where the
+ * single-conversation pass's are.  The plain step, the batched step and minigpt4_amd_verify_draft launch nothing new.
+ * THE RULE, per conversation i, is minigpt4_amd_verify_draft's: g0_i = the first maximum of its RAW logits -- penalties, a logit bias and constraints do NOT enter it, nor
+ * any row's decision; its tokens still enter the history --; g[r + 1] = the first argmax of its row r; m_i = the largest value with draft_i[j] == g[j + 1] for all j < m_i.
+ * Afterwards ids_out[i][0 .. m_i] = g0_i, draft_i[0 .. m_i - 1], n_out[i] = 1 + m_i, the conversation stands at n_past = p_i + 1 + m_i with the logits, greedy token and
+ * feed token of its row m_i.  Under greedy decoding every conversation's tokens are exactly those plain decoding emits.
+ * minigpt4_amd_verify_draft_batch: slots[n] distinct; drafts = the drafts concatenated in list order (as minigpt4_amd_score_batch takes its tokens), counts[n] each in
+ * [0, max_draft]; ids_out [n][8]; n_out [n]; row_greedy_out (may be NULL) [n][8] = g[1 ...] of every evaluated row, -1 behind them.  Queued prompt rows of every listed
+ * conversation are evaluated first (as minigpt4_amd_end_chat_batch does).  A draft longer than the room left is cut to n_ctx - n_past - 1 rows; a conversation with no
+ * room for g0 follows the batched step: the automatic shift makes room, else n_out[i] = 0 and the conversation is left out of the pass, untouched.  One wait per call.
+ * The sampler's generator, the mirostat state and the prefix cache are untouched.  Every count 0 (or cut to 0): the ordinary batched step -- its own graph, its own
+ * epilogue -- so a call without drafts costs what minigpt4_amd_eval_batch costs.  Parity mode: minigpt4_amd_verify_draft's one-row oracle-order loop per conversation,
+ * bit-identical to plain greedy decoding, no speed-up.  No key-split attention in the pass.
+ * Refused (1, "verify_draft_batch: ...", nothing changed -- except that "a conversation has no current logits" can also come AFTER the queued prompt rows of the
+ * conversations listed before it were evaluated, as in minigpt4_amd_end_chat_batch: their rows then stand evaluated, no token is emitted): no context, speculation off, slots NULL / n < 1 / n above the conversations, a duplicate or out-of-range slot,
+ * counts / ids_out / n_out NULL, a count outside [0, max_draft], drafts NULL with a count > 0, an id outside [0, n_vocab), a conversation without current logits, more
+ * than 64 rows in total (or more than the context's activation rows, max(n_batch, 32, conversations)).
+ * minigpt4_amd_decode_lookup_batch: minigpt4_amd_decode_lookup's loop over n conversations.  Each has its own drafter -- history = its corpus (corpus: the corpora
+ * concatenated, corpus_counts[i] tokens each, 0 allowed) followed by what IT has emitted --, its own max_tokens budget and its own end (</s> emitted and evaluated, or a
+ * full context that cannot shift); every iteration is one minigpt4_amd_verify_draft_batch over the conversations still running (drafts are shortened, in list order,
+ * where the pass's 64 rows would not hold them).  tokens_out [n][max_tokens], n_tokens [n], stats [n][4] = {passes in which the conversation sent a draft, passes in
+ * which it sent none, draft tokens sent, draft tokens accepted} (passes + steps + accepted == n_tokens[i]).  Refusals: minigpt4_amd_decode_lookup's and the slot
+ * list's, under "decode_lookup_batch: ...".
+ * minigpt4_amd_speculation_batch_info: out = {passes, rows evaluated, groups, draft tokens sent, draft tokens accepted, calls without a draft that took the plain
+ * batched step, draft tokens cut for room, 0} since the context was loaded; parity mode's one-row loops are not passes of this kind and count nothing but the cut.  minigpt4_amd_speculation_info does not count these calls.
+ * BREAK-EVEN: a pass of N rows for n conversations pays when the draft tokens kept per conversation per pass exceed pass_ms(N) / step_ms(n) - 1, step_ms(n) = the
+ * batched step at n rows.  WHICH n_draft: tools/lookup_batch_decode.py prints pass_ms, step_ms and that break-even per (n, rows per conversation).  Recorded
+ * (profiles/r19_lookup_batch.log, 13B Q5_K_M, about 150 cached keys, medians of 5): rows per conversation 2 / 4 / 8 need 0.18 / 0.66 / 0.78 kept draft tokens per
+ * conversation per pass at n = 2, 0.43 / 0.53 / 0.76 at n = 4, 0.10 / 0.25 / 0.80 at n = 8 -- the steps in pass_ms lie at 5 rows (the int8-MFMA set launches) and
+ * above 32.  Synthetic files: nothing is measured about how many draft tokens real text keeps. */
+MINIGPT4_API int minigpt4_amd_verify_draft_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const int32_t *drafts, const int32_t *counts, int32_t *ids_out,
+                                                 int32_t *n_out, int32_t *row_greedy_out);
+MINIGPT4_API int minigpt4_amd_decode_lookup_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const int32_t *corpus, const int32_t *corpus_counts, int max_tokens,
+                                                  int ngram_max, int ngram_min, int n_draft, int32_t *tokens_out, int32_t *n_tokens, int32_t *stats);
+MINIGPT4_API int minigpt4_amd_speculation_batch_info(struct MiniGPT4Context *ctx, int64_t out[8]);
+
 /* ---- snapshots: save and restore a conversation --------------------------------------------------------------------------------------------------------
  * A conversation leaves its slot, its context or its process as one blob (llama.cpp's llama_copy_state_data / session files / slot save and restore) and comes back bit
  * for bit: a restored conversation continues with the logits and tokens of the uninterrupted one.  The cache rows travel through k_kv_pack / k_kv_unpack -- rows

@@ -411,6 +411,22 @@ MINIGPT4_API int minigpt4_amd_test_step_words(int form, int n_slot, int n, const
 /* ONE launch_gather_rows: dst[r] = src[idx[r]], rows of E floats, src [n_src][E], idx [n].  dst_out [n + 1][E]: prefilled with 0xFF bytes, row n is a guard row.
  * Refused: a NULL array, n_src / n outside 1 .. 65536, E outside 1 .. 2^20, an idx entry outside [0, n_src) */
 MINIGPT4_API int minigpt4_amd_test_gather_rows(const float *src, int n_src, const int32_t *idx, int n, int E, float *dst_out);
+/* ---- the verify pass of several conversations (minigpt4_amd_verify_draft_batch), its launches alone ---- */
+/* The attention launch.  groups [n_groups][3] = (slot, p0, R): group g is R rows of conversation `slot` at positions p0 .. p0 + R - 1; the N = sum R <= 64 packed rows
+ * follow in list order.  q, k, v, out [N][n_head * hd]; kc / vc [n_slot][n_ctx][n_head * hd] fp16 bit patterns, changed in place; vs 1 / 2 / 4 = the value-column split.
+ * mode 0: launch_mdraft_begin on all-zero positions, then ONE launch_attn_llm_draft_batched.  mode 1: one launch_attn_llm_draft per group, in list order.
+ * Otherwise as minigpt4_amd_test_attn_draft.  Refused (1, before a device is looked for): a NULL array, mode not 0 / 1, hd not 32 / 64 / 128, vs not 1 / 2 / 4,
+ * n_head < 1, n_slot < 1, n_groups outside 1 .. 64, a slot outside [0, n_slot) or named twice, R outside 1 .. 8, p0 < 0 or p0 + R > n_ctx, more than 64 rows, n_ctx
+ * beyond the verify form's LDS bound. */
+MINIGPT4_API int minigpt4_amd_test_attn_draft_batch(int mode, int vs, int n_head, int hd, int n_ctx, int n_slot, int n_groups, const int32_t *groups, int computed_exp,
+                                                    const float *q, const float *k, const float *v, uint16_t *kc, uint16_t *vc, float *out);
+/* launch_mdraft_begin, then ONE launch_draft_finish_batch (k_draft_argmax over the N rows, then k_draft_finish_batch) on logits [N][n_vocab] with the pass's row tokens
+ * tok[N], conversations row_slot[N] and positions row_pos[N].  State arrays as minigpt4_amd_test_step_finish's.  res_out [64 + 64 + 1] words: m per packed row (a
+ * group's first row: its m; any other row: -1), the rows' greedy ids, 0xFF fill behind N in both halves, and a guard word.
+ * Refused: a NULL array, N outside 1 .. 64, n_vocab outside 1 .. 2^20, n_slot outside 1 .. 4096, a slot outside [0, n_slot), rows of one slot that are not adjacent, a
+ * group of more than 8 rows, positions that are negative or not consecutive inside a group. */
+MINIGPT4_API int minigpt4_amd_test_draft_finish_batch(const float *logits, int N, int n_vocab, const int32_t *tok, const int32_t *row_slot, const int32_t *row_pos, int n_slot,
+                                                      int32_t *n_past_io, int32_t *argmax_io, int32_t *feed_io, float *slot_logits_io, int32_t *res_out);
 
 /* ---- host-only logic (no GPU needed) -------------------------------------------------------------------------------- */
 /* the n-gram drafter of minigpt4_amd_decode_lookup alone (csrc/draft.cpp): the draft for a history of n tokens, at most n_draft tokens into out; returns its length

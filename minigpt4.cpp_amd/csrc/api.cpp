@@ -410,6 +410,20 @@ int minigpt4_amd_speculation_info(struct MiniGPT4Context *ctx, int64_t out[8]) {
     static_assert(sizeof(long long) == sizeof(int64_t), "the counters travel as 64-bit words");
     return guarded(1, [&] { return E_(ctx)->speculation_info(reinterpret_cast<long long *>(out)); });
 }
+int minigpt4_amd_verify_draft_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const int32_t *drafts, const int32_t *counts, int32_t *ids_out, int32_t *n_out,
+                                    int32_t *row_greedy_out) {
+    if (!ctx) { set_last_error("verify_draft_batch: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->verify_draft_batch(slots, n, drafts, counts, ids_out, n_out, row_greedy_out); });
+}
+int minigpt4_amd_decode_lookup_batch(struct MiniGPT4Context *ctx, const int32_t *slots, int n, const int32_t *corpus, const int32_t *corpus_counts, int max_tokens, int ngram_max,
+                                     int ngram_min, int n_draft, int32_t *tokens_out, int32_t *n_tokens, int32_t *stats) {
+    if (!ctx) { set_last_error("decode_lookup_batch: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->decode_lookup_batch(slots, n, corpus, corpus_counts, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats); });
+}
+int minigpt4_amd_speculation_batch_info(struct MiniGPT4Context *ctx, int64_t out[8]) {
+    if (!ctx) { set_last_error("speculation_batch_info: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->speculation_batch_info(reinterpret_cast<long long *>(out)); });
+}
 // ---- beam search over forked conversations ------------------------------------------------------------------------------------------------------
 int minigpt4_amd_beam_search(struct MiniGPT4Context *ctx, const int32_t *slots, int n_beams, int max_tokens, float length_penalty, int n_best, int32_t *tokens_out,
                              int32_t *lengths_out, float *scores_out, int32_t *n_out, int32_t stats[4]) {

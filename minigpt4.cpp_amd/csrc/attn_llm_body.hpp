@@ -6,6 +6,9 @@
 // from the ISA that was validated and measured -- the optimised IR then differs in one eliminated smin and in inbounds flags of the last reduction; why, not known.
 // Included, all twelve instantiations are instruction for instruction what they were (tools/isa_diff.py) -- and stayed so as the VS = 1 forms when VS was added
 // (every VS line below is a compile-time `VS == 1 ? the former expression : ...`; tools/isa_diff.py --rename maps the old symbols onto <..., VS = 1>).
+// A COPY of this file's DRAFT lines lives in llm_kernels.hip: k_attn_llm_mdraft<HD, VS>, the verify form for several conversations, with (t - r, r) where DRAFT has
+// (0, t).  It is a copy so that the instantiations of THIS text stay the validated ISA; its contract is bit-identity with the DRAFT form (tests/test_gpu_draft_batch.py),
+// so a change to a DRAFT line here -- operand order, rounding call, loop structure -- has to be made there too.
     static_assert((FUSED || !BATCHED) && (BATCHED || !DRAFT), "BATCHED implies FUSED, DRAFT implies BATCHED");
     static_assert(VS == 1 || (FUSED && (VS == 2 || VS == 4) && (HD / 8) % VS == 0), "the value-column split: fused forms, 2 or 4 workgroups per (head, row)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -1046,7 +1046,9 @@ void Engine::forward(const Pass &p, hipStream_t s) {
 // arithmetic per row as forward(1): per-row activation quantisation, exact integer block dots, the same attention kernel body.
 // verify (Engine::verify_draft): the B rows are ONE conversation's (d_bslot_[0]) at consecutive positions -- the same embedding rows and mat-vec branches; the attention
 // launch is launch_attn_llm_draft, the row logits go to spec_logits_ and the epilogue is launch_draft_finish.
-void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
+// multi (Engine::verify_draft_batch): the B rows are consecutive groups, one per conversation, described by d_bslot_ / d_bpos_ alone -- the same embedding rows and mat-vec
+// branches at B rows; the attention launch is launch_attn_llm_draft_batched, the row logits go to mspec_logits_ and the epilogue is launch_draft_finish_batch.
+void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue, bool multi) {
     pend_ = SlabSrc{}; xh_override_ = nullptr;
     batch_path_ = BatchPath{}; batch_path_.rows = B;
     const int E = (int)llm_.n_embd, F = (int)llm_.n_ff(), H = (int)llm_.n_head, hd = E / H, V = (int)llm_.n_vocab;
@@ -1126,10 +1128,11 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
         return same_shape(Ws.begin(), (int)Ws.size()) && matvec_rows_prologue_ok(w0->type, w0->cols);
     };
     auto attn = [&](__half *kc, __half *vc) {
-        if (verify) launch_attn_llm_draft(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
+        if (multi) launch_attn_llm_draft_batched(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, d_bpos_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
+        else if (verify) launch_attn_llm_draft(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
         else launch_attn_llm_batched(q_, k_, v_, kc, vc, B, H, hd, d_npast_, d_bslot_, seq_stride, n_ctx_, cos_, sin_, tabs_dec_, att_, s);
     };
-    float *const row_logits = verify ? spec_logits_ : blogits_;
+    float *const row_logits = multi ? mspec_logits_ : verify ? spec_logits_ : blogits_;
     launch_get_rows(tok_type_, tok_raw_, E, d_btok_, B, x_, s);
     for (size_t il = 0; il < layers_.size(); il++) {
         const LayerW &L = layers_[il];
@@ -1200,7 +1203,8 @@ void Engine::forward_batch(int B, hipStream_t s, bool verify, bool epilogue) {
         prep_rms(x_, norm_, B, E, act_mask_for(output_.type), s);             // (also combines the last layer's w2 slabs when its combine was deferred)
         mm({&output_}, {row_logits}, nullptr, V);
     }
-    if (verify) { if (epilogue) launch_draft_finish(spec_logits_, V, B, d_btok_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, spec_res_, s); }   // (the sampled form launches its own behind the pass)
+    if (multi) launch_draft_finish_batch(mspec_logits_, V, B, d_btok_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, mspec_res_, s);
+    else if (verify) { if (epilogue) launch_draft_finish(spec_logits_, V, B, d_btok_, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, spec_res_, s); }   // (the sampled form launches its own behind the pass)
     else launch_batch_finish(blogits_, V, B, d_bslot_, d_npast_, d_argmax_, d_feed_, logits_, s);
 }
 
@@ -1677,16 +1681,17 @@ int Engine::decode_batch(const int *slots, int n, const SampleParams &p, int *id
 }
 // rows (token, conversation, position) travel in one copy; the device positions are normally current (k_advance / k_batch_finish keep them), but
 // a reset may have moved the host's view, so k_batch_begin writes them like eval_chunk does
-void Engine::step_begin(int B, bool verify) {
+void Engine::step_begin(int B, bool verify, bool multi) {
     HIP_CHECK(hipMemcpyAsync(d_btok_, h_bstage_, BSTAGE_BYTES, hipMemcpyHostToDevice, stream_));
-    if (verify) launch_draft_begin(d_npast_, d_bslot_, d_bpos_, stream_); else launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
+    if (multi) launch_mdraft_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
+    else if (verify) launch_draft_begin(d_npast_, d_bslot_, d_bpos_, stream_); else launch_batch_begin(d_npast_, d_bslot_, d_bpos_, B, stream_);
 }
 // the step as one hipGraph per row count: token ids, conversations and positions live in device memory, so the same graph serves every set of B conversations
 // and every entry point (verify: every R rows of any conversation; without its epilogue: the sampled verify pass, whose epilogue follows k_sample_rows)
-void Engine::step_launch(int B, bool verify, bool epilogue) {
-    if (!use_graph_) { forward_batch(B, stream_, verify, epilogue); return; }
-    hipGraphExec_t &ge = (!verify ? batch_graph_ : epilogue ? spec_graph_ : spec_sgraph_)[(size_t)B];
-    if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_, verify, epilogue); });
+void Engine::step_launch(int B, bool verify, bool epilogue, bool multi) {
+    if (!use_graph_) { forward_batch(B, stream_, verify, epilogue, multi); return; }
+    hipGraphExec_t &ge = (multi ? mspec_graph_ : !verify ? batch_graph_ : epilogue ? spec_graph_ : spec_sgraph_)[(size_t)B];
+    if (!ge) capture_graph(ge, [&] { forward_batch(B, stream_, verify, epilogue, multi); });
     HIP_CHECK(hipGraphLaunch(ge, stream_));
 }
 // oracle-order arithmetic exists for the single-conversation pass only: one pass per staged row (same results as the batched step is tested to give)
@@ -2505,9 +2510,9 @@ int Engine::state_load(int slot, const void *buf, size_t n) {
 
 // ---- speculation: draft tokens verified in one weight pass (engine.hpp) ----
 void Engine::spec_drop_graphs() {
-    for (std::vector<hipGraphExec_t> *v : {&spec_graph_, &spec_sgraph_}) for (hipGraphExec_t &g : *v) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; }
+    for (std::vector<hipGraphExec_t> *v : {&spec_graph_, &spec_sgraph_, &mspec_graph_}) for (hipGraphExec_t &g : *v) { if (g) HIP_IGNORE(hipGraphExecDestroy(g)); g = nullptr; }
 }
-void Engine::spec_free() { spec_drop_graphs(); reset_all(spec_logits_, spec_res_, spec_hres_, sdr_res_, sdr_hres_); spec_max_ = 0; }
+void Engine::spec_free() { spec_drop_graphs(); reset_all(spec_logits_, spec_res_, spec_hres_, sdr_res_, sdr_hres_, mspec_logits_, mspec_res_, mspec_hres_); spec_max_ = 0; }
 int Engine::set_speculation(int max_draft) {
     if (max_draft < 0 || max_draft > DRAFT_MAX) { set_last_error("set_speculation: max_draft must be 0 (off) ... " + std::to_string(DRAFT_MAX)); return 1; }
     // the verify pass keeps DRAFT_ROWS new key / value rows next to the score rows in the attention kernel's LDS: a context the one-row form holds may not fit it
@@ -2608,6 +2613,151 @@ int Engine::decode_lookup(const int *corpus, int n_corpus, int max_tokens, int n
         if (g0 == 2) break;                                                  // </s> emitted and evaluated
     }
     return done(0);
+}
+// ---- speculation, greedy, several conversations in one weight pass (engine.hpp) ----
+void Engine::mspec_alloc() {
+    if (mspec_graph_.empty()) mspec_graph_.assign((size_t)ATTN_MDRAFT_ROWS + 1, nullptr);
+    if (mspec_logits_) return;
+    DevPtr<float> logits((size_t)ATTN_MDRAFT_ROWS * llm_.n_vocab * 4); DevPtr<int> res(2 * ATTN_MDRAFT_ROWS * 4); PinPtr<int> hres(2 * ATTN_MDRAFT_ROWS * 4);   // all three or none
+    mspec_logits_ = std::move(logits); mspec_res_ = std::move(res); mspec_hres_ = std::move(hres);
+}
+int Engine::speculation_batch_info(long long out[8]) const {
+    if (!out) { set_last_error("speculation_batch_info: no output array"); return 1; }
+    const SpecBatchInfo &i = mspec_info_;
+    out[0] = i.passes; out[1] = i.rows; out[2] = i.groups; out[3] = i.sent; out[4] = i.accepted; out[5] = i.plain; out[6] = i.cut; out[7] = 0;
+    return 0;
+}
+int Engine::verify_draft_batch(const int *slots, int n, const int *drafts, const int *counts, int *ids_out, int *n_out, int *row_greedy) {
+    auto refuse = [](const std::string &what) { set_last_error("verify_draft_batch: " + what); return 1; };
+    if (spec_max_ <= 0) return refuse("speculation is off (minigpt4_amd_set_speculation)");
+    if (const int bad = check_slots(slots, n)) return refuse(bad == 1 ? "bad slot list" : "conversations must be distinct and in range");
+    if (!counts || !ids_out || !n_out) return refuse("counts, ids_out and n_out are required");
+    int n_drafts = 0;
+    for (int i = 0; i < n; i++) { if (counts[i] < 0 || counts[i] > spec_max_) return refuse("a count outside [0, max_draft]"); n_drafts += counts[i]; }
+    if (n_drafts > 0 && !drafts) return refuse("drafts is NULL");
+    for (int i = 0; i < n_drafts; i++) if (drafts[i] < 0 || drafts[i] >= (int)llm_.n_vocab) return refuse("draft token id out of range");
+    const int row_cap = std::min(ATTN_MDRAFT_ROWS, max_rows_);
+    if (n + n_drafts > row_cap) return refuse("more rows in total (" + std::to_string(n + n_drafts) + ") than the pass holds (" + std::to_string(row_cap) + ")");
+    if (weights_missing()) return 1;
+    for (int i = 0; i < n; i++) { const Conversation &cv = conv_[(size_t)slots[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return refuse("a conversation has no current logits"); }
+    const SelectScope restore(this);
+    for (int i = 0; i < n; i++) {                                             // queued prompt rows of each conversation first, as decode_batch does
+        cur_ = slots[i];
+        if (flush()) return refuse(last_error());
+        if (!conv_[(size_t)cur_].has_logits) return refuse("a conversation has no current logits");
+    }
+    if (row_greedy) std::fill(row_greedy, row_greedy + (size_t)n * DRAFT_ROWS, -1);   // rows that were not evaluated
+    // the rows each conversation brings: 0 = no room (and no automatic shift), left out; a draft is cut to the room left
+    int R[MAX_CONVERSATIONS], off[MAX_CONVERSATIONS], N = 0, G = 0, cut = 0; bool any_draft = false;
+    for (int i = 0, o = 0; i < n; o += counts[i], i++) {
+        Conversation &cv = conv_[(size_t)slots[i]];
+        cur_ = slots[i]; off[i] = o; n_out[i] = 0;
+        if (cv.n_past + 1 > n_ctx_ && make_room(1)) { R[i] = 0; continue; }
+        R[i] = 1 + std::min(counts[i], n_ctx_ - cv.n_past - 1);
+        cut += counts[i] - (R[i] - 1); N += R[i]; G++; any_draft = any_draft || R[i] > 1;
+    }
+    mspec_info_.cut += cut;
+    if (!G) return 0;
+    if (parity_) {   // oracle-order arithmetic exists for the single-row pass only: verify_draft's one-row loop per conversation -- plain greedy decoding
+        for (int i = 0; i < n; i++) {
+            if (!R[i]) continue;
+            cur_ = slots[i];
+            int rg[DRAFT_ROWS];
+            if (verify_draft(drafts + off[i], counts[i], ids_out + (size_t)i * DRAFT_ROWS, &n_out[i], rg)) return refuse(last_error());
+            if (row_greedy) std::copy(rg, rg + 1 + counts[i], row_greedy + (size_t)i * DRAFT_ROWS);
+        }
+        return 0;
+    }
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // h_argmax_ is current; h_bstage_ no longer feeds an earlier step's copy
+    if (!any_draft) {                                                        // nothing to verify: the ordinary batched step, its own graph and k_batch_finish
+        int B = 0;
+        for (int i = 0; i < n; i++) if (R[i]) { ids_out[(size_t)i * DRAFT_ROWS] = h_argmax_[slots[i]]; stage_row(B++, h_argmax_[slots[i]], slots[i], conv_[(size_t)slots[i]].n_committed); }
+        step_begin(B);
+        step_launch(B);
+        for (int r = 0; r < B; r++) commit_rows(staged_slot(r), &staged_token(r), 1, /*past=*/true);
+        HIP_CHECK(hipMemcpyAsync(h_argmax_, d_argmax_, conv_.size() * 4, hipMemcpyDeviceToHost, stream_));
+        for (int i = 0; i < n; i++) if (R[i]) n_out[i] = 1;
+        if (row_greedy) {
+            HIP_CHECK(hipStreamSynchronize(stream_));
+            for (int i = 0; i < n; i++) if (R[i]) row_greedy[(size_t)i * DRAFT_ROWS] = h_argmax_[slots[i]];
+        }
+        mspec_info_.plain++;
+        return 0;
+    }
+    mspec_alloc();
+    int t0[MAX_CONVERSATIONS];
+    for (int i = 0, t = 0; i < n; i++) {
+        if (!R[i]) continue;
+        const int p = conv_[(size_t)slots[i]].n_committed;
+        t0[i] = t;
+        stage_row(t, h_argmax_[slots[i]], slots[i], p);
+        for (int r = 1; r < R[i]; r++) stage_row(t + r, drafts[off[i] + r - 1], slots[i], p + r);
+        t += R[i];
+    }
+    step_begin(N, /*verify=*/false, /*multi=*/true);
+    step_launch(N, /*verify=*/false, /*epilogue=*/true, /*multi=*/true);
+    HIP_CHECK(hipMemcpyAsync(mspec_hres_, mspec_res_, 2 * ATTN_MDRAFT_ROWS * 4, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));                                // the one wait of the pass: every group's m and the rows' greedy ids
+    const int *hm = mspec_hres_, *hg = hm + ATTN_MDRAFT_ROWS;
+    for (int i = 0; i < n; i++) if (R[i] && (hm[t0[i]] < 0 || hm[t0[i]] >= R[i]))
+        throw HipError{hipErrorUnknown, "verify_draft_batch: the device reported an accepted count outside a group", __FILE__, __LINE__};
+    long long acc = 0;
+    for (int i = 0; i < n; i++) {
+        if (!R[i]) continue;
+        const int m = hm[t0[i]], slot = slots[i];
+        if (row_greedy) for (int r = 0; r < R[i]; r++) row_greedy[(size_t)i * DRAFT_ROWS + r] = hg[t0[i] + r];
+        h_argmax_[slot] = hg[t0[i] + m];
+        commit_rows(slot, &staged_token(t0[i]), 1 + m, /*past=*/true);         // the kept rows only: g0, draft[0 .. m)
+        for (int r = 0; r <= m; r++) ids_out[(size_t)i * DRAFT_ROWS + r] = staged_token(t0[i] + r);
+        n_out[i] = 1 + m; acc += m;
+    }
+    mspec_info_.passes++; mspec_info_.rows += N; mspec_info_.groups += G; mspec_info_.sent += N - G; mspec_info_.accepted += acc;
+    return 0;
+}
+int Engine::decode_lookup_batch(const int *slots, int n, const int *corpus, const int *corpus_counts, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out,
+                                int *n_tokens, int *stats) {
+    auto refuse = [](const std::string &what) { set_last_error("decode_lookup_batch: " + what); return 1; };
+    if (const int bad = check_slots(slots, n)) return refuse(bad == 1 ? "bad slot list" : "conversations must be distinct and in range");
+    if (!corpus_counts) return refuse("corpus_counts is NULL");
+    int n_corpus = 0;
+    for (int i = 0; i < n; i++) { if (corpus_counts[i] < 0) return refuse("bad corpus"); n_corpus += corpus_counts[i]; }
+    if (lookup_check("decode_lookup_batch", corpus, n_corpus, max_tokens, ngram_max, ngram_min, n_draft, tokens_out, n_tokens, stats)) return 1;
+    if (weights_missing()) return 1;
+    for (int i = 0; i < n; i++) { const Conversation &cv = conv_[(size_t)slots[i]]; if (cv.pend_tok.empty() && !cv.has_logits) return refuse("a conversation has no current logits"); }
+    std::vector<NgramDrafter> drafter((size_t)n, NgramDrafter(ngram_max, ngram_min));
+    for (int i = 0, o = 0; i < n; o += corpus_counts[i], i++) drafter[(size_t)i].reset(corpus + o, corpus_counts[i]);
+    std::vector<char> running((size_t)n, 1);
+    std::fill(n_tokens, n_tokens + n, 0); std::fill(stats, stats + (size_t)4 * n, 0);
+    const SelectScope restore(this);
+    const int row_cap = std::min(ATTN_MDRAFT_ROWS, max_rows_);
+    int who[MAX_CONVERSATIONS], sl[MAX_CONVERSATIONS], cnt[MAX_CONVERSATIONS], g0s[MAX_CONVERSATIONS], got[MAX_CONVERSATIONS];
+    std::vector<int> d((size_t)n * DRAFT_MAX), ids((size_t)n * DRAFT_ROWS);
+    for (;;) {
+        int k = 0, nd_all = 0, live = 0;
+        for (int i = 0; i < n; i++) live += running[(size_t)i];
+        int spare = row_cap - live;                                          // draft rows the pass still holds beside one row per running conversation
+        for (int i = 0; i < n; i++) {
+            if (!running[(size_t)i]) continue;
+            Conversation &cv = conv_[(size_t)slots[i]];
+            cur_ = slots[i];
+            const int g0 = greedy_raw();                                     // evaluates what is queued; raw logits: no penalties here
+            if (cv.n_past + 1 > n_ctx_ && make_room(1)) { running[(size_t)i] = 0; continue; }   // context full and no automatic shift
+            drafter[(size_t)i].push(g0);
+            const int want = std::min(std::min(n_draft, max_tokens - n_tokens[i] - 1), std::min(n_ctx_ - cv.n_past - 1, spare));
+            const int nd = g0 == 2 || want <= 0 ? 0 : drafter[(size_t)i].draft(want, d.data() + nd_all);
+            who[k] = i; sl[k] = slots[i]; cnt[k] = nd; g0s[k] = g0; k++; nd_all += nd; spare -= nd;
+        }
+        if (!k) break;
+        if (verify_draft_batch(sl, k, d.data(), cnt, ids.data(), got, nullptr)) return refuse(last_error());
+        for (int j = 0; j < k; j++) {
+            const int i = who[j];
+            if (got[j] < 1) { running[(size_t)i] = 0; continue; }
+            stats[4 * i + (cnt[j] ? 0 : 1)]++; stats[4 * i + 2] += cnt[j]; stats[4 * i + 3] += got[j] - 1;
+            for (int r = 0; r < got[j]; r++) { const int id = ids[(size_t)j * DRAFT_ROWS + r]; tokens_out[(size_t)i * max_tokens + n_tokens[i]++] = id; if (r) drafter[(size_t)i].push(id); }
+            if (g0s[j] == 2 || n_tokens[i] >= max_tokens) running[(size_t)i] = 0;   // </s> emitted and evaluated, or the budget spent
+        }
+    }
+    return 0;
 }
 // ---- speculation under sampling (engine.hpp, draft_host.hpp) ----
 void Engine::sdr_alloc() {

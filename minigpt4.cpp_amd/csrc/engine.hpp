@@ -217,6 +217,29 @@ public:
                                  int *tokens_out, int *n_tokens, int *stats);
     // {sampled verify passes, rows evaluated, draft tokens sent, draft tokens accepted, sampling launches made by these calls, stuck picks, draft tokens cut by a constraint, 0}
     int speculation_info(long long out[8]) const;
+    // ---- speculation, greedy, SEVERAL conversations in one weight pass.  verify_draft_batch: conversation slots[i] brings its greedy token g0_i and counts[i] draft tokens
+    // (drafts: concatenated in list order), i.e. a group of 1 + counts[i] rows at consecutive positions; the groups are packed into one pass of N <= 64 rows
+    // (forward_batch's multi mode: the batched step's embedding rows and mat-vec branches at N rows, launch_attn_llm_draft_batched -- causal inside each group --,
+    // launch_draft_finish_batch -- one decision per conversation).  g0_i is the conversation's RAW greedy token, verify_draft's rule: penalties, a logit bias and
+    // constraints do not enter it, and a row's greedy id is the first maximum of its raw logits.  Per conversation afterwards exactly what verify_draft leaves: ids_out
+    // [i][DRAFT_ROWS] = g0_i, draft_i[0 .. m_i), n_out[i] = 1 + m_i, n_past = n_committed = p_i + 1 + m_i, logits / greedy / feed token those of row m_i; row_greedy (may be
+    // null) [i][DRAFT_ROWS]: the first argmax of every evaluated row, -1 behind them.  Queued prompt rows of every listed conversation are evaluated first, as decode_batch
+    // does.  A draft is cut to the room left; a conversation without room follows decode_batch: the automatic shift makes room, or n_out[i] = 0 and it is left out of
+    // the pass, untouched.  One wait per call; commit_rows takes the kept rows only; the sampler's generator, the mirostat state and the prefix store are not touched.
+    // (A conversation that still has no logits once its queue is evaluated is refused behind that evaluation: the conversations listed before it keep their evaluated rows.)
+    // Every count 0: the ordinary batched step (step_launch(B), its own graph, k_batch_finish) -- that case costs what decode_batch costs.  Parity mode: verify_draft's
+    // one-row oracle-order loop per conversation.  Refusals ("verify_draft_batch: ...", nothing changed): speculation off, a bad / duplicate / out-of-range slot list, a
+    // count outside [0, max_draft], a token id out of range, a conversation without current logits, more rows in total than the pass holds (64, and the context's
+    // activation rows).
+    int verify_draft_batch(const int *slots, int n, const int *drafts, const int *counts, int *ids_out, int *n_out, int *row_greedy);
+    // decode_lookup's loop over n conversations: each its own NgramDrafter (corpus: concatenated, corpus_counts[i] tokens each, + what it emitted), its own max_tokens
+    // budget and its own </s> / context-full end; every iteration is ONE verify_draft_batch over the conversations still running.  tokens_out [n][max_tokens],
+    // n_tokens [n], stats [n][4] = {passes in which the conversation sent a draft, passes without one, draft tokens sent, draft tokens accepted}
+    int decode_lookup_batch(const int *slots, int n, const int *corpus, const int *corpus_counts, int max_tokens, int ngram_max, int ngram_min, int n_draft, int *tokens_out,
+                            int *n_tokens, int *stats);
+    // {passes, rows, groups, draft tokens sent, accepted, all-zero calls that took the plain batched step, draft tokens cut for room, 0}; parity mode's one-row loops
+    // count nothing here but the cut
+    int speculation_batch_info(long long out[8]) const;
 
     // ---- beam search over forked conversations (beam.hpp: the step's rule; minigpt4_amd.h: the whole rule).  slots[0] is the source, the other n_beams - 1 listed
     // conversations are scratch.  The source's queue is evaluated, its logits row / greedy / feed token saved, its state forked to the others; then every step queues, on one
@@ -337,7 +360,7 @@ private:
     int load_llm(const std::string &path);
     int load_vision(const std::string &path);
     void alloc_buffers();
-    void forward_batch(int B, hipStream_t s, bool verify = false, bool epilogue = true);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation (epilogue = false: without launch_draft_finish)
+    void forward_batch(int B, hipStream_t s, bool verify = false, bool epilogue = true, bool multi = false);   // B decode rows of B conversations: tokens d_btok_[r], conversations d_bslot_[r]; verify: of ONE conversation (epilogue = false: without launch_draft_finish); multi: groups of rows of several conversations (verify_draft_batch)
     // speculation's own allocations (set_speculation; freed with the context): [1 + spec_max_][n_vocab] row logits, {m, greedy id per row} and its pinned mirror, [R] graphs
     int spec_max_ = 0; DevPtr<float> spec_logits_; DevPtr<int> spec_res_; PinPtr<int> spec_hres_; std::vector<hipGraphExec_t> spec_graph_;
     // penalties: the penalised pick's staging block (pick_stage.hpp), allocated by the first row that is not the identity; its results are the picked ids
@@ -542,10 +565,11 @@ private:
     int &staged_token(int r) { return h_bstage_[r]; }
     int staged_slot(int r) const { return h_bstage_[MAX_CONVERSATIONS + r]; }
     // the slab's one copy, then k_batch_begin over B rows (verify: k_draft_begin -- R rows of the one conversation in row 0)
-    void step_begin(int B, bool verify = false);
+    void step_begin(int B, bool verify = false, bool multi = false);
     // the weight pass over the staged rows, forward_batch(B, stream_, verify, epilogue): batch_graph_[B] (verify: spec_graph_[B]; verify without its epilogue, the sampled
     // verify pass: spec_sgraph_[B]) replayed, captured first where it does not exist yet; without graphs, eager
-    void step_launch(int B, bool verify = false, bool epilogue = true);
+    // multi (verify_draft_batch): mspec_graph_[B], B the TOTAL row count -- the grouping is data in d_bslot_ / d_bpos_, so one graph serves every grouping
+    void step_launch(int B, bool verify = false, bool epilogue = true, bool multi = false);
     // parity mode's stand-in for step_begin + step_launch: one oracle-order single-row pass per staged row, in row order; cur_ is left on the last row's conversation.
     // 0, or eval_chunk's failure
     int step_parity(int B);
@@ -717,6 +741,11 @@ private:
     // speculation under sampling.  Lazy, first call: one graph slot per row count (the verify pass without its epilogue), the result block {m, picks, stuck flags} and its
     // pinned mirror.  Dropped / freed where the greedy form's are (spec_drop_graphs, spec_free)
     std::vector<hipGraphExec_t> spec_sgraph_; DevPtr<int> sdr_res_; PinPtr<int> sdr_hres_;
+    // the verify pass of several conversations (verify_draft_batch): its own lazy allocation (first call; freed by spec_free) -- [ATTN_MDRAFT_ROWS][n_vocab] row logits, the
+    // result block m [ATTN_MDRAFT_ROWS] | row_greedy [ATTN_MDRAFT_ROWS] and its pinned mirror, one graph per total row count (dropped by spec_drop_graphs)
+    DevPtr<float> mspec_logits_; DevPtr<int> mspec_res_; PinPtr<int> mspec_hres_; std::vector<hipGraphExec_t> mspec_graph_;
+    void mspec_alloc();
+    struct SpecBatchInfo { long long passes = 0, rows = 0, groups = 0, sent = 0, accepted = 0, plain = 0, cut = 0; } mspec_info_;
     struct SpecInfo { long long passes = 0, rows = 0, sent = 0, accepted = 0, launches = 0, stuck = 0, cut = 0; } spec_info_;
     void sdr_alloc();
 };

@@ -217,6 +217,21 @@ void launch_draft_begin(int *n_past, const int *row_slot, const int *row_pos, hi
 // res[1 + r] = first argmax of logits row r; m = leading draft tokens accepted (tok[i + 1] == res[1 + i], i < m); slot = row_slot[0]: slot_logits[slot] = logits[m],
 // argmax[slot] = feed[slot] = res[1 + m], n_past[slot] += 1 + m, res[0] = m.  res: 1 + DRAFT_ROWS ints
 void launch_draft_finish(const float *logits, int n_vocab, int R, const int *tok, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, int *res, hipStream_t s);
+// ---- verify pass of SEVERAL conversations (Engine::verify_draft_batch): N <= ATTN_MDRAFT_ROWS packed rows in consecutive groups, group g = R_g <= DRAFT_ROWS rows of
+// conversation slot_g at positions p0_g + 0 .. R_g - 1, all slots distinct.  Nothing but row_slot [N] / row_pos [N] describes the grouping ----
+constexpr int ATTN_MDRAFT_ROWS = 64;                   // the staging slab's rows
+// n_past[slot_g] = p0_g (the position of each group's first row): ahead of the pass, where launch_draft_begin stands for one conversation
+void launch_mdraft_begin(int *n_past, const int *row_slot, const int *row_pos, int N, hipStream_t s);
+// row t (index r = row_pos[t] - n_past[row_slot[t]] in its group): RoPE + append of its own row, attention over its conversation's cache below p0, the group's rows
+// before it and itself.  out and the appended rows are bit for bit those of one launch_attn_llm_draft per group; other conversations' caches and rows outside
+// [p0_g, p0_g + R_g) are not written; a row at or past n_ctx stores nothing.  n_past is not written.  n_ctx <= attn_draft_max_ctx(hd).
+void launch_attn_llm_draft_batched(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int N, int n_head, int hd, const int *n_past, const int *row_slot,
+                                   const int *row_pos, size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s, int vs = 1);
+// res = m [ATTN_MDRAFT_ROWS] | row_greedy [ATTN_MDRAFT_ROWS].  row_greedy[t] = first argmax of logits row t; per group (first packed row t0, R rows, slot): m = leading
+// draft tokens accepted (tok[t0 + i + 1] == row_greedy[t0 + i], i < m), slot_logits[slot] = logits[t0 + m], argmax[slot] = feed[slot] = row_greedy[t0 + m],
+// n_past[slot] += 1 + m, m[t0] = m; m[t] = -1 for a row that is not a group's first.
+void launch_draft_finish_batch(const float *logits, int n_vocab, int N, const int *tok, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, int *res,
+                               hipStream_t s);
 // ---- prompt rows of several conversations packed in one chunk (Engine::prefill_batch) ----
 // rows: device [N][2] = (slot, absolute position) per packed row.  k_rope_kv's arithmetic; cache row = position in kcache / vcache + slot * seq_stride
 void launch_rope_kv_seg(float *q, const float *k, const float *v, int N, int n_head, int hd, const int *rows, size_t seq_stride, const float *cos_tab, const float *sin_tab,

@@ -1894,6 +1894,148 @@ __global__ __launch_bounds__(AT_THREADS) void k_attn_llm_draft(const int *__rest
 #include "attn_llm_body.hpp"
 }
 #undef MG4_ATTN_PIN
+// MDRAFT (verify pass of SEVERAL conversations, Engine::verify_draft_batch): the N <= 64 rows of the pass are consecutive groups, group g = R_g <= DRAFT_ROWS rows of
+// conversation slot_g at the positions p0_g + 0 .. R_g - 1, p0_g = n_past[slot_g] (k_mdraft_begin has written it), all slots distinct.  Row t knows its conversation
+// row_slot[t] and its position row_pos[t]: its index inside the group is r = row_pos[t] - p0 and the group's first packed row is t - r -- no table of groups.  Everything
+// else is the DRAFT form with (t - r, r) where DRAFT has (0, t): row t rotates and rounds the k / v of the packed rows t - r .. t into LDS, appends only its own, reads
+// the cache below p0 only and SELECTS a key in [p0, pos) from LDS into the same (partition j mod P, round j / P) place of the same loops; no workgroup waits for another.
+// CONTRACT: out and the appended rows are bit for bit those of one launch_attn_llm_draft per group.
+// Its own body text and not a further constant of attn_llm_body.hpp: the twelve k_attn_llm and the k_attn_llm_draft instantiations stay the validated ISA untouched
+// (tools/isa_diff.py).  The statements below are that file's DRAFT lines, in its order, with the same helpers: operand order and rounding calls are part of the results.
+// Arguments: the two row arrays and the positions' address lead (the position is two dependent loads away: row_slot[t], then n_past[slot]), the projections, the RoPE
+// tables and E follow inside the preloadable head; one empty asm consumes every argument in the first round trip, as MG4_ATTN_PIN does for the other forms.
+// A row whose (slot, position) does not describe a place inside a group (r outside [0, min(t, DRAFT_ROWS - 1)]) or that lies at or past n_ctx returns without a store.
+template <int HD, int VS = 1>
+__global__ __launch_bounds__(AT_THREADS) void k_attn_llm_mdraft(const int *__restrict__ row_slot, const int *__restrict__ row_pos, const int *__restrict__ n_past, float *__restrict__ q,
+                                                                const float *__restrict__ kin, const float *__restrict__ vin, const float *__restrict__ cos_tab,
+                                                                const float *__restrict__ sin_tab, int E, int n_ctx, __half *__restrict__ kc, __half *__restrict__ vc, const Tables tb,
+                                                                float *__restrict__ out, size_t seq_stride) {
+    static_assert(VS == 1 || ((VS == 2 || VS == 4) && (HD / 8) % VS == 0), "the value-column split: 2 or 4 workgroups per (head, row)");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int CH = HD / 8, P = AT_THREADS / CH, RM = DRAFT_ROWS;
+    static_assert(RM <= P && RM * (HD / 2) <= AT_THREADS, "one prologue thread per (row, rotated pair); at most one LDS key per partition");
+    const int h = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    constexpr int CHV = (HD / 8) / VS;
+    const bool vact = VS == 1 || tid < AT_THREADS / VS;
+    const int slot = row_slot[t], pos = row_pos[t];
+    asm volatile("" ::"s"(slot), "s"(pos), "s"(n_past), "s"(q), "s"(kin), "s"(vin), "s"(cos_tab), "s"(sin_tab), "s"(E), "s"(kc), "s"(vc), "s"(tb.exp), "s"(out));
+    const int p0 = n_past[slot], r = pos - p0, t0 = t - r;          // the group's first position, this row's index in the group, the group's first packed row
+    if (r < 0 || r >= RM || r > t || pos >= n_ctx) return;
+    kc += (size_t)slot * seq_stride; vc += (size_t)slot * seq_stride;
+    const int T = pos + 1, Tg = pos;                               // Tg: keys that are not this row's own
+    const int Tpad = (T + 7) & ~7;
+    float *sc = reinterpret_cast<float *>(smem);                  // [Tpad]                 (the carve-up attn_lds_bytes sizes)
+    __half *ph = reinterpret_cast<__half *>(sc + Tpad);           // [Tpad]
+    __half *qh = ph + Tpad;                                       // [HD]
+    __half *knew = qh + HD, *vnew = knew + RM * HD;               // [RM][HD] each: rows 0 .. r of the group
+    float *part = reinterpret_cast<float *>(vnew + RM * HD);      // [P][HD]
+    __shared__ float s_red[AT_THREADS / 64];
+    __shared__ double s_dred[AT_THREADS / 64];
+    const float scale = 1.0f / sqrtf((float)HD);
+    const size_t qo = (size_t)t * E + (size_t)h * HD;
+    if (tid < (r + 1) * (HD / 2)) {                               // one thread per (row rr <= r of the group, rotated pair): rows before r only fill knew / vnew [rr]
+        const int rr = tid / (HD / 2), i = tid % (HD / 2), pr = p0 + rr;
+        const size_t ro = (size_t)(t0 + rr) * E + (size_t)h * HD;
+        const float c = cos_tab[(size_t)pr * (HD / 2) + i], s = sin_tab[(size_t)pr * (HD / 2) + i];
+        const __half2 kr = rope_rot_h2(kin[ro + 2 * i], kin[ro + 2 * i + 1], c, s);
+        const __half2 vr = __floats2half2_rn(vin[ro + 2 * i], vin[ro + 2 * i + 1]);
+        st_h2(knew + rr * HD + 2 * i, kr); st_h2(vnew + rr * HD + 2 * i, vr);
+        if (rr == r) {
+            st_h2(qh + 2 * i, rope_rot_h2(q[qo + 2 * i], q[qo + 2 * i + 1], c, s));
+            const size_t co = (size_t)pos * E + (size_t)h * HD + 2 * i;
+            if (VS == 1 || blockIdx.z == 0) { st_h2(kc + co, kr); st_h2(vc + co, vr); }
+        }
+    }
+    __syncthreads();
+    unsigned qreg[HD / 2];
+#pragma unroll
+    for (int i = 0; i < HD / 8; i++) { const int4 v4 = *reinterpret_cast<const int4 *>(qh + 8 * i); qreg[4 * i] = (unsigned)v4.x; qreg[4 * i + 1] = (unsigned)v4.y; qreg[4 * i + 2] = (unsigned)v4.z; qreg[4 * i + 3] = (unsigned)v4.w; }
+    auto dot_row = [&](const __half *kr) {
+        int4 kk[HD / 8];
+#pragma unroll
+        for (int i = 0; i < HD / 8; i++) kk[i] = ld16(kr + 8 * i);
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < HD / 8; i++) {
+            const unsigned w[4] = {(unsigned)kk[i].x, (unsigned)kk[i].y, (unsigned)kk[i].z, (unsigned)kk[i].w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) { s = fmaf(h2f_bits(w[e] & 0xFFFF), h2f_bits(qreg[4 * i + e] & 0xFFFF), s); s = fmaf(h2f_bits(w[e] >> 16), h2f_bits(qreg[4 * i + e] >> 16), s); }
+        }
+        return s * scale;
+    };
+    const int c = tid % CH, p = tid / CH;
+    const int cv = VS == 1 ? c : (int)blockIdx.z * CHV + tid % CHV, pv = VS == 1 ? p : tid / CHV;
+    const __half *kb = kc + (size_t)h * HD + 8 * c, *vb = vc + (size_t)h * HD + 8 * cv;
+    constexpr int NPRE = 16;
+    const int gmax = max(p0 - 1, 0);                              // the last row the cache is read at: rows from p0 on are written by this launch (loads are clamped, never a branch)
+    int4 kpre[NPRE], vpre[NPRE];
+#pragma unroll
+    for (int i = 0; i < NPRE; i++) kpre[i] = ld16(kb + (size_t)min(p + i * P, gmax) * E);
+    if (vact) {
+#pragma unroll
+        for (int i = 0; i < NPRE; i++) vpre[i] = ld16(vb + (size_t)min(pv + i * P, gmax) * E);
+    }
+    // this partition's key among the group's earlier rows, if any: row rl at position jl (jl mod P == p)
+    const int rl = (p - p0) & (P - 1), rlv = (pv - p0) & (P - 1);
+    const int jl = rl < r ? p0 + rl : -1, jlv = rlv < r ? p0 + rlv : -1;
+    const int4 kl = *reinterpret_cast<const int4 *>(knew + min(rl, RM - 1) * HD + 8 * c), vl = *reinterpret_cast<const int4 *>(vnew + min(rlv, RM - 1) * HD + 8 * cv);
+    float qd[8];
+    unpack8(*reinterpret_cast<const int4 *>(qh + 8 * c), qd);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NPRE; i++) { const int j = p + i * P; const float s = dot16<CH>(j == jl ? kl : kpre[i], qd, scale); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
+    for (int j0 = p + NPRE * P; j0 < Tg; j0 += 8 * P) {          // beyond the prefetch: 8 rows per round trip
+        int4 kk[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) kk[i] = ld16(kb + (size_t)min(j0 + i * P, gmax) * E);
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const int j = j0 + i * P; const float s = dot16<CH>(j == jl ? kl : kk[i], qd, scale); if (j < Tg) { if (c == 0) sc[j] = s; mx = fmaxf(mx, s); } }
+    }
+    if (tid == AT_THREADS - 1) { const float s = dot_row(knew + r * HD); sc[pos] = s; mx = fmaxf(mx, s); }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) s_red[tid >> 6] = mx;
+    __syncthreads();
+    mx = s_red[0];
+#pragma unroll
+    for (int i = 1; i < AT_THREADS / 64; i++) mx = fmaxf(mx, s_red[i]);
+    double sum = 0.0;
+    for (int j = tid; j < T; j += AT_THREADS) { const float v = exp_h(tb.exp, sc[j] - mx); sc[j] = v; sum += (double)v; }
+    sum = wave_sum_d(sum);
+    if ((tid & 63) == 0) s_dred[tid >> 6] = sum;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int i = 0; i < AT_THREADS / 64; i++) tot += s_dred[i];
+    const float inv = (float)(1.0 / tot);
+    for (int j = tid; j < T; j += AT_THREADS) ph[j] = f2h_rn(sc[j] * inv);
+    __syncthreads();
+    float o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto pv_key = [&](const int4 &vv, const int j) { pv_acc(o, vv, __half2float(ph[j])); };
+    if (vact) {                                                   // VS > 1: the other waves skip (wave-uniform; no barrier inside)
+#pragma unroll
+        for (int i = 0; i < NPRE; i++) { const int j = pv + i * P; if (j < Tg) pv_key(j == jlv ? vl : vpre[i], j); }
+        for (int j0 = pv + NPRE * P; j0 < Tg; j0 += 8 * P) {
+            int4 vv[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) vv[i] = ld16(vb + (size_t)min(j0 + i * P, gmax) * E);
+#pragma unroll
+            for (int i = 0; i < 8; i++) { const int j = j0 + i * P; if (j < Tg) pv_key(j == jlv ? vl : vv[i], j); }
+        }
+        if (pv == P - 1) {
+            const float pj = __half2float(ph[pos]);
+#pragma unroll
+            for (int e = 0; e < 8; e++) o[e] = fmaf(__half2float(vnew[r * HD + 8 * cv + e]), pj, o[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) part[pv * HD + 8 * cv + e] = o[e];
+    }
+    __syncthreads();
+    // the partitions in order 0 .. P - 1, as ever; VS > 1: this workgroup's HD / VS dims
+    for (int i = (VS == 1 ? 0 : (int)blockIdx.z * (HD / VS)) + tid; i < (VS == 1 ? HD : ((int)blockIdx.z + 1) * (HD / VS)); i += AT_THREADS) { float s = 0.0f;
+#pragma unroll 8
+        for (int pp = 0; pp < P; pp++) s += part[pp * HD + i];
+        out[qo + i] = s; }
+}
 
 // the supported head sizes as compile-time constants: f(std::integral_constant<int, HD>) for hd's HD; false (f not called) for an unsupported head size
 template <class F> static bool attn_for_head_size(int hd, F &&f) {
@@ -1966,6 +2108,30 @@ void launch_attn_llm_draft(float *q, const float *k, const float *v, __half *kca
     if (R < 1 || R > DRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_attn_llm_draft: row count out of range", __FILE__, __LINE__};
     attn_for_head_size_or_throw(hd, [&](auto tag) {
         launch_attn_body<decltype(tag)::value, true, true>(true, q, k, v, kcache, vcache, R, n_head, n_past, row_slot, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, vs, s); });
+}
+// Verify pass of several conversations: N <= ATTN_MDRAFT_ROWS packed rows in groups (k_attn_llm_mdraft above); n_ctx <= attn_draft_max_ctx(hd)
+template <int HD, int VS>
+static void launch_attn_mdraft_vs(float *q, const float *k, const float *v, __half *kc, __half *vc, int N, int n_head, const int *n_past, const int *row_slot, const int *row_pos,
+                                  size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s) {
+    static bool attr = false;
+    if (!attr) { HIP_IGNORE(lds_optin_max(&k_attn_llm_mdraft<HD, VS>)); attr = true; }
+    if (VS == 1) note_kernel("k_attn_llm_mdraft<%d>", HD); else note_kernel("k_attn_llm_mdraft<%d, %d>", HD, VS);
+    hipLaunchKernelGGL((k_attn_llm_mdraft<HD, VS>), dim3((unsigned)n_head, (unsigned)N, (unsigned)VS), dim3(AT_THREADS), attn_lds_bytes(n_ctx, HD, DRAFT_ROWS), s, row_slot, row_pos, n_past, q,
+                       k, v, cos_tab, sin_tab, n_head * HD, n_ctx, kc, vc, tb, out, seq_stride);
+}
+void launch_attn_llm_draft_batched(float *q, const float *k, const float *v, __half *kcache, __half *vcache, int N, int n_head, int hd, const int *n_past, const int *row_slot,
+                                   const int *row_pos, size_t seq_stride, int n_ctx, const float *cos_tab, const float *sin_tab, const Tables &tb, float *out, hipStream_t s, int vs) {
+    if (N < 1 || N > ATTN_MDRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_attn_llm_draft_batched: row count out of range", __FILE__, __LINE__};
+    if (n_ctx < 1 || n_ctx > attn_draft_max_ctx(hd)) throw HipError{hipErrorInvalidValue, "launch_attn_llm_draft_batched: n_ctx beyond what the verify form holds in LDS", __FILE__, __LINE__};
+    attn_for_head_size_or_throw(hd, [&](auto tag) {
+        constexpr int HD = decltype(tag)::value;
+        if (!attn_vsplit_ok(HD, vs)) throw HipError{hipErrorInvalidValue, "decode attention: unsupported value-column split", __FILE__, __LINE__};
+#define ATTN_MD_ARGS q, k, v, kcache, vcache, N, n_head, n_past, row_slot, row_pos, seq_stride, n_ctx, cos_tab, sin_tab, tb, out, s
+        if (vs == 4) launch_attn_mdraft_vs<HD, 4>(ATTN_MD_ARGS);
+        else if (vs == 2) launch_attn_mdraft_vs<HD, 2>(ATTN_MD_ARGS);
+        else launch_attn_mdraft_vs<HD, 1>(ATTN_MD_ARGS);
+#undef ATTN_MD_ARGS
+    });
 }
 // =====================================================================================================================
 // Key-split decode attention (long contexts): k_attn_llm above puts ONE workgroup on a head -- 40 workgroups on a 256-CU chip, 0.015 us per cached key, 35 us per layer
@@ -2940,6 +3106,42 @@ void launch_draft_finish(const float *logits, int n_vocab, int R, const int *tok
 // verify pass prologue: the host's view of the conversation's position, once (every row of the pass derives its own from it)
 __global__ void k_draft_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos) { n_past[row_slot[0]] = row_pos[0]; }
 void launch_draft_begin(int *n_past, const int *row_slot, const int *row_pos, hipStream_t s) { hipLaunchKernelGGL(k_draft_begin, dim3(1), dim3(1), 0, s, n_past, row_slot, row_pos); }
+// Verify pass of several conversations (Engine::verify_draft_batch): N packed rows in consecutive groups, one group per conversation, all slots distinct -- so a group
+// starts at row 0 and wherever the slot differs from the row before, and nothing but row_slot / row_pos describes the grouping.
+// k_mdraft_begin (replaces k_draft_begin): n_past[slot] = the position of the group's first row.
+// Epilogue, two launches in stream order over the result block res = m [ATTN_MDRAFT_ROWS] | row_greedy [ATTN_MDRAFT_ROWS]:
+//   k_draft_argmax over the N rows, writing row_greedy (it is handed res + ATTN_MDRAFT_ROWS - 1: its entry 1 + t is row_greedy[t]);
+//   k_draft_finish_batch, one workgroup per packed row of which those on a group's first row t0 work: R = the group's rows, m = the number of leading draft tokens with
+//   tok[t0 + i + 1] == row_greedy[t0 + i]; logits row t0 + m becomes the conversation's, argmax = feed = row_greedy[t0 + m], n_past += 1 + m, m[t0] = m.  The others
+//   write m[t] = -1 and leave.  Conversations not in the pass are not touched.
+__global__ void k_mdraft_begin(int *__restrict__ n_past, const int *__restrict__ row_slot, const int *__restrict__ row_pos, int N) {
+    const int t = threadIdx.x;
+    if (t < N && (t == 0 || row_slot[t] != row_slot[t - 1])) n_past[row_slot[t]] = row_pos[t];
+}
+void launch_mdraft_begin(int *n_past, const int *row_slot, const int *row_pos, int N, hipStream_t s) {
+    if (N < 1 || N > ATTN_MDRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_mdraft_begin: row count out of range", __FILE__, __LINE__};
+    hipLaunchKernelGGL(k_mdraft_begin, dim3(1), dim3(ATTN_MDRAFT_ROWS), 0, s, n_past, row_slot, row_pos, N);
+}
+__global__ __launch_bounds__(1024) void k_draft_finish_batch(const float *__restrict__ logits, int n_vocab, int N, const int *__restrict__ tok, const int *__restrict__ row_slot,
+                                                            int *__restrict__ n_past, int *__restrict__ argmax, int *__restrict__ feed, float *__restrict__ slot_logits, int *__restrict__ res) {
+    const int t0 = blockIdx.x, slot = row_slot[t0];
+    if (t0 > 0 && row_slot[t0 - 1] == slot) { if (threadIdx.x == 0) res[t0] = -1; return; }   // not a group's first row (uniform over the workgroup)
+    int R = 1;
+    while (R < DRAFT_ROWS && t0 + R < N && row_slot[t0 + R] == slot) R++;
+    const int *g = res + ATTN_MDRAFT_ROWS + t0;                            // the group's greedy ids (k_draft_argmax, the launch before)
+    int m = 0;
+    while (m < R - 1 && tok[t0 + m + 1] == g[m]) m++;                      // every thread: R <= 8 words, all in cache
+    const float *x = logits + (size_t)(t0 + m) * n_vocab;
+    float *keep = slot_logits + (size_t)slot * n_vocab;
+    for (int i = threadIdx.x; i < n_vocab; i += 1024) keep[i] = x[i];
+    if (threadIdx.x == 0) { const int id = g[m]; argmax[slot] = id; feed[slot] = id; n_past[slot] += 1 + m; res[t0] = m; }
+}
+void launch_draft_finish_batch(const float *logits, int n_vocab, int N, const int *tok, const int *row_slot, int *n_past, int *argmax, int *feed, float *slot_logits, int *res, hipStream_t s) {
+    if (N < 1 || N > ATTN_MDRAFT_ROWS) throw HipError{hipErrorInvalidValue, "launch_draft_finish_batch: row count out of range", __FILE__, __LINE__};
+    note_kernel("k_draft_argmax"); note_kernel("k_draft_finish_batch");
+    hipLaunchKernelGGL(k_draft_argmax, dim3((unsigned)N), dim3(1024), 0, s, logits, n_vocab, res + ATTN_MDRAFT_ROWS - 1);
+    hipLaunchKernelGGL(k_draft_finish_batch, dim3((unsigned)N), dim3(1024), 0, s, logits, n_vocab, N, tok, row_slot, n_past, argmax, feed, slot_logits, res);
+}
 // Packed prompt chunk epilogue (Engine::prefill_batch): row r of `logits` is the last row of conversation fin[2 r]; its position becomes fin[2 r + 1] (set, not
 // advanced), its greedy id and feed token as k_batch_finish writes them.
 __global__ __launch_bounds__(1024) void k_seg_finish(const float *__restrict__ logits, int n_vocab, const int *__restrict__ fin, int *__restrict__ n_past, int *__restrict__ argmax,

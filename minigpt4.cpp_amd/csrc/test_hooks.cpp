@@ -1825,6 +1825,93 @@ int minigpt4_amd_test_step_words(int form, int n_slot, int n, const int32_t *row
         return 0;
     });
 }
+// ---- the verify pass of several conversations: its attention launch and its prologue + epilogue alone ----
+int minigpt4_amd_test_attn_draft_batch(int mode, int vs, int n_head, int hd, int n_ctx, int n_slot, int n_groups, const int32_t *groups, int computed_exp, const float *q,
+                                       const float *k, const float *v, uint16_t *kc, uint16_t *vc, float *out) {
+    if (!q || !k || !v || !kc || !vc || !out || !groups || (mode != 0 && mode != 1) || (hd != 32 && hd != 64 && hd != 128) || (vs != 1 && vs != 2 && vs != 4) || n_head < 1 ||
+        n_slot < 1 || n_slot > SE_MAX_SLOTS || n_groups < 1 || n_groups > ATTN_MDRAFT_ROWS || n_ctx < 1 || n_ctx > attn_draft_max_ctx(hd)) return 1;
+    if (!se_slots_ok(groups, n_groups, 3, n_slot)) return 1;
+    int N = 0;
+    for (int g = 0; g < n_groups; g++) {
+        const int p0 = groups[3 * g + 1], R = groups[3 * g + 2];
+        if (R < 1 || R > DRAFT_ROWS || p0 < 0 || p0 > n_ctx - R) return 1;
+        N += R;
+    }
+    if (N > ATTN_MDRAFT_ROWS) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t E = (size_t)n_head * hd, stride = (size_t)n_ctx * E, cache = (size_t)n_slot * stride, RE = (size_t)N * E;
+        std::vector<float> c, sn;
+        rope_tables(n_ctx, hd, c, sn);
+        std::vector<int> np((size_t)n_slot, 0), rs((size_t)N), rp((size_t)N), first((size_t)n_groups);
+        for (int g = 0, t = 0; g < n_groups; g++) {
+            first[(size_t)g] = t;
+            if (mode == 1) np[(size_t)groups[3 * g]] = groups[3 * g + 1];    // mode 0: k_mdraft_begin writes them
+            for (int r = 0; r < groups[3 * g + 2]; r++, t++) { rs[(size_t)t] = groups[3 * g]; rp[(size_t)t] = groups[3 * g + 1] + r; }
+        }
+        DevBuf dc(c.size() * 4), dsn(sn.size() * 4), dq(RE * 4), dk(RE * 4), dv(RE * 4), dkc(cache * 2), dvc(cache * 2), dout(RE * 4), dnp((size_t)n_slot * 4), dslot((size_t)N * 4),
+            dpos((size_t)N * 4), dtab(65536 * 2);
+        HIP_CHECK(hipMemcpy(dc.p, c.data(), c.size() * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dq.p, q, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dk.p, k, RE * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dv.p, v, RE * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dkc.p, kc, cache * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dvc.p, vc, cache * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dnp.p, np.data(), np.size() * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dslot.p, rs.data(), (size_t)N * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dpos.p, rp.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dout.p, 0, RE * 4));
+        Tables tb;                                                // as in minigpt4_amd_test_attn_draft
+        { std::vector<__half> e(65536); int last = 0;
+          for (int i = 0; i < 65536; i++) e[(size_t)i] = __float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)i))));
+          for (int i = 0; i < 0x7C00; i++) if (__half2float(e[(size_t)(0x8000 + i)]) != 0.0f) last = i;
+          HIP_CHECK(hipMemcpy(dtab.p, e.data(), 131072, hipMemcpyHostToDevice));
+          tb.exp = computed_exp ? nullptr : dtab.as<__half>(); tb.exp_neg_n = (last + 1 + 2047) / 2048 * 2048; }
+        if (mode == 0) {
+            launch_mdraft_begin(dnp.as<int>(), dslot.as<int>(), dpos.as<int>(), N, nullptr);
+            launch_attn_llm_draft_batched(dq.as<float>(), dk.as<float>(), dv.as<float>(), dkc.as<__half>(), dvc.as<__half>(), N, n_head, hd, dnp.as<int>(), dslot.as<int>(), dpos.as<int>(),
+                                          stride, n_ctx, dc.as<float>(), dsn.as<float>(), tb, dout.as<float>(), nullptr, vs);
+        } else {
+            for (int g = 0; g < n_groups; g++) {
+                const size_t o = (size_t)first[(size_t)g] * E;
+                launch_attn_llm_draft(dq.as<float>() + o, dk.as<float>() + o, dv.as<float>() + o, dkc.as<__half>(), dvc.as<__half>(), groups[3 * g + 2], n_head, hd, dnp.as<int>(),
+                                      dslot.as<int>() + first[(size_t)g], stride, n_ctx, dc.as<float>(), dsn.as<float>(), tb, dout.as<float>() + o, nullptr, vs);
+            }
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dout.p, RE * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(kc, dkc.p, cache * 2, hipMemcpyDeviceToHost)); HIP_CHECK(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+int minigpt4_amd_test_draft_finish_batch(const float *logits, int N, int n_vocab, const int32_t *tok, const int32_t *row_slot, const int32_t *row_pos, int n_slot, int32_t *n_past_io,
+                                         int32_t *argmax_io, int32_t *feed_io, float *slot_logits_io, int32_t *res_out) {
+    if (!logits || !tok || !row_slot || !row_pos || !n_past_io || !argmax_io || !feed_io || !slot_logits_io || !res_out || N < 1 || N > ATTN_MDRAFT_ROWS || n_vocab < 1 ||
+        n_vocab > SE_MAX_VOCAB || n_slot < 1 || n_slot > SE_MAX_SLOTS) return 1;
+    {   // consecutive groups: rows of one slot adjacent, at most DRAFT_ROWS of them, at consecutive positions
+        std::vector<char> seen((size_t)n_slot, 0);
+        for (int t = 0, run = 0; t < N; t++) {
+            const int s = row_slot[t];
+            if (s < 0 || s >= n_slot || row_pos[t] < 0) return 1;
+            if (t > 0 && row_slot[t - 1] == s) { if (++run > DRAFT_ROWS || row_pos[t] != row_pos[t - 1] + 1) return 1; }
+            else { if (seen[(size_t)s]) return 1; seen[(size_t)s] = 1; run = 1; }
+        }
+    }
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const size_t n = (size_t)N * n_vocab, NR = 2 * ATTN_MDRAFT_ROWS + 1;
+        DevBuf dl(n * 4), dtok((size_t)N * 4), dslot((size_t)N * 4), dpos((size_t)N * 4), dres(NR * 4);
+        StepState st(n_slot, n_vocab);
+        HIP_CHECK(hipMemcpy(dl.p, logits, n * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dtok.p, tok, (size_t)N * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dslot.p, row_slot, (size_t)N * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dpos.p, row_pos, (size_t)N * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dres.p, 0xFF, NR * 4));
+        st.upload(n_past_io, argmax_io, feed_io, slot_logits_io);
+        launch_mdraft_begin(st.dn.as<int>(), dslot.as<int>(), dpos.as<int>(), N, nullptr);
+        launch_draft_finish_batch(dl.as<float>(), n_vocab, N, dtok.as<int>(), dslot.as<int>(), st.dn.as<int>(), st.da.as<int>(), st.df.as<int>(), st.dk.as<float>(), dres.as<int>(), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        st.download(n_past_io, argmax_io, feed_io, slot_logits_io);
+        HIP_CHECK(hipMemcpy(res_out, dres.p, NR * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 // ONE launch_gather_rows: dst_out [n + 1][E], prefilled with 0xFF bytes, row n is a guard row
 int minigpt4_amd_test_gather_rows(const float *src, int n_src, const int32_t *idx, int n, int E, float *dst_out) {
     if (!src || !idx || !dst_out || n_src < 1 || n_src > (1 << 16) || n < 1 || n > (1 << 16) || E < 1 || E > SE_MAX_VOCAB) return 1;

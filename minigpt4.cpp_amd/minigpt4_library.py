@@ -277,6 +277,9 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_verify_draft_sampled.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_decode_lookup_sampled.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, F32, I32, F32, INT_PTR, INT_PTR, INT_PTR]
         L.minigpt4_amd_speculation_info.argtypes = [VOID_PTR, I64P]
+        L.minigpt4_amd_verify_draft_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_decode_lookup_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, I32, I32, I32, I32, INT_PTR, INT_PTR, INT_PTR]
+        L.minigpt4_amd_speculation_batch_info.argtypes = [VOID_PTR, I64P]
         L.minigpt4_amd_verify_draft_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, F32, F32, F32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_decode_lookup_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, F32, I32, F32, F32, F32, F32, INT_PTR, INT_PTR, INT_PTR]
 
@@ -349,6 +352,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_attn_draft.argtypes = [I32, I32, I32, I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_attn_vsplit.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_ngram_draft.argtypes = [INT_PTR, I32, I32, I32, I32, INT_PTR]
+        L.minigpt4_amd_test_attn_draft_batch.argtypes = [I32, I32, I32, I32, I32, I32, I32, INT_PTR, I32, FLOAT_PTR, FLOAT_PTR, FLOAT_PTR, VOID_PTR, VOID_PTR, FLOAT_PTR]
+        L.minigpt4_amd_test_draft_finish_batch.argtypes = [FLOAT_PTR, I32, I32, INT_PTR, INT_PTR, INT_PTR, I32, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR]
         L.minigpt4_amd_test_argmax.argtypes = [FLOAT_PTR, I32, INT_PTR, FLOAT_PTR, INT_PTR]
         L.minigpt4_amd_test_step_finish.argtypes = [I32, FLOAT_PTR, I32, I32, I32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_draft_finish.argtypes = [FLOAT_PTR, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR]
@@ -667,6 +672,88 @@ class MiniGPT4SharedLibrary:
         if self.library.minigpt4_amd_speculation_info(ctx.ptr if ctx is not None else None, out):
             raise RuntimeError("speculation_info failed: " + self._err())
         return dict(zip(self.SPECULATION_INFO_FIELDS, (int(x) for x in out)))
+
+    SPECULATION_BATCH_INFO_FIELDS = ("passes", "rows", "groups", "sent", "accepted", "plain_steps", "cut")
+
+    def amd_verify_draft_batch(self, ctx, slots: Sequence[int], drafts: Sequence[Sequence[int]]) -> dict:
+        """amd_verify_draft for several conversations in ONE weight pass: conversation slots[i] brings its raw greedy token and the guesses drafts[i] (may be empty).
+        dict(ids: list of [1 + m_i] i32 arrays -- the tokens plain greedy decoding would have emitted, empty for a conversation left out (context full);
+        row_greedy [n][8] i32: the first argmax of every evaluated row, -1 behind them).  include/minigpt4_amd.h states the rule."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(sl)
+        if len(drafts) != n:
+            raise ValueError("amd_verify_draft_batch: one draft (possibly empty) per conversation")
+        cnt = np.array([len(d) for d in drafts], np.int32)
+        flat = np.ascontiguousarray([t for d in drafts for t in d], np.int32).reshape(-1)
+        ids, n_out, rg = np.zeros((max(n, 1), 8), np.int32), np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 8), np.int32)
+        if self.library.minigpt4_amd_verify_draft_batch(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR) if n else None, n,
+                                                        flat.ctypes.data_as(INT_PTR) if flat.size else None, cnt.ctypes.data_as(INT_PTR) if n else None,
+                                                        ids.ctypes.data_as(INT_PTR), n_out.ctypes.data_as(INT_PTR), rg.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("verify_draft_batch failed: " + self._err())
+        return dict(ids=[ids[i, :int(n_out[i])].copy() for i in range(n)], row_greedy=rg[:n])
+
+    def amd_decode_lookup_batch(self, ctx, slots: Sequence[int], corpora: Sequence[Sequence[int]], max_tokens: int, ngram_max: int = 3, ngram_min: int = 1,
+                                n_draft: int = 4) -> list:
+        """amd_decode_lookup for several conversations: each its own corpus (may be empty), drafter, budget and end; every iteration is one amd_verify_draft_batch over the
+        conversations still running.  A list of dict(tokens [n_i] i32, passes, steps, sent, accepted), one per conversation."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = len(sl)
+        if len(corpora) != n:
+            raise ValueError("amd_decode_lookup_batch: one corpus (possibly empty) per conversation")
+        cnt = np.array([len(c) for c in corpora], np.int32)
+        flat = np.ascontiguousarray([t for c in corpora for t in c], np.int32).reshape(-1)
+        mt = max(int(max_tokens), 1)
+        out, nt, st = np.zeros((max(n, 1), mt), np.int32), np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 4), np.int32)
+        if self.library.minigpt4_amd_decode_lookup_batch(ctx.ptr if ctx is not None else None, sl.ctypes.data_as(INT_PTR) if n else None, n,
+                                                         flat.ctypes.data_as(INT_PTR) if flat.size else None, cnt.ctypes.data_as(INT_PTR) if n else None, int(max_tokens),
+                                                         int(ngram_max), int(ngram_min), int(n_draft), out.ctypes.data_as(INT_PTR), nt.ctypes.data_as(INT_PTR),
+                                                         st.ctypes.data_as(INT_PTR)):
+            raise RuntimeError("decode_lookup_batch failed: " + self._err())
+        return [dict(tokens=out[i, :int(nt[i])].copy(), passes=int(st[i, 0]), steps=int(st[i, 1]), sent=int(st[i, 2]), accepted=int(st[i, 3])) for i in range(n)]
+
+    def amd_speculation_batch_info(self, ctx) -> dict:
+        """dict(passes, rows, groups, sent, accepted: of the verify passes over several conversations; plain_steps: calls without a draft that took the plain batched step;
+        cut: draft tokens cut for room) -- of the context so far."""
+        out = (ctypes.c_int64 * 8)()
+        if self.library.minigpt4_amd_speculation_batch_info(ctx.ptr if ctx is not None else None, out):
+            raise RuntimeError("speculation_batch_info failed: " + self._err())
+        return dict(zip(self.SPECULATION_BATCH_INFO_FIELDS, (int(x) for x in out)))
+
+    def amd_test_attn_draft_batch(self, mode: int, q: np.ndarray, k: np.ndarray, v: np.ndarray, kc: np.ndarray, vc: np.ndarray, n_head: int, groups, computed_exp: bool = True,
+                                  vs: int = 1):
+        """The attention of the verify pass over several conversations (mode 0: launch_mdraft_begin + ONE launch_attn_llm_draft_batched; mode 1: one launch_attn_llm_draft
+        per group) for the packed rows q, k, v [N][E]; groups [n][3] = (slot, p0, R) in row order; fp16 caches [n_slot][n_ctx][E] as uint16 patterns.  Returns
+        (out [N][E], kc, vc) -- copies.  ValueError: arguments the hook refuses before it looks for a device."""
+        q, k, v = (np.ascontiguousarray(x, np.float32) for x in (q, k, v))
+        kc, vc = np.array(kc, np.uint16, order="C"), np.array(vc, np.uint16, order="C")
+        g = np.ascontiguousarray(groups, np.int32).reshape(-1, 3)
+        N, E = q.shape
+        S, C, _ = kc.shape
+        if int(g[:, 2].sum()) != N or k.shape != q.shape or v.shape != q.shape or vc.shape != kc.shape or kc.shape[2] != E:
+            raise ValueError("amd_test_attn_draft_batch: q, k, v [sum R][E], caches [n_slot][n_ctx][E]")
+        out = np.zeros_like(q)
+        self._step_rc("test_attn_draft_batch", self.library.minigpt4_amd_test_attn_draft_batch(
+            int(mode), int(vs), n_head, E // n_head, C, S, len(g), g.ctypes.data_as(INT_PTR), int(computed_exp), q.ctypes.data_as(FLOAT_PTR), k.ctypes.data_as(FLOAT_PTR),
+            v.ctypes.data_as(FLOAT_PTR), kc.ctypes.data_as(VOID_PTR), vc.ctypes.data_as(VOID_PTR), out.ctypes.data_as(FLOAT_PTR)))
+        return out, kc, vc
+
+    def amd_test_draft_finish_batch(self, logits: np.ndarray, tok: Sequence[int], row_slot: Sequence[int], row_pos: Sequence[int], n_past, argmax, feed, slot_logits) -> dict:
+        """launch_mdraft_begin + ONE launch_draft_finish_batch on logits [N][n_vocab] with the pass's row tokens, conversations and positions.  dict(m [N] i32: a group's
+        first row holds its m, every other row -1; row_greedy [N] i32; res [129]: the whole block and its guard word; n_past, argmax, feed, slot_logits after the launches)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.ndim != 2:
+            raise ValueError("amd_test_draft_finish_batch: logits [N][n_vocab]")
+        N = lg.shape[0]
+        tk, rs, rp = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (tok, row_slot, row_pos))
+        if not (tk.size == rs.size == rp.size == N):
+            raise ValueError("amd_test_draft_finish_batch: one token, slot and position per row")
+        st, keep = self._step_state(n_past, argmax, feed, slot_logits, lg.shape[1])
+        res = np.zeros(129, np.int32)
+        self._step_rc("test_draft_finish_batch", self.library.minigpt4_amd_test_draft_finish_batch(
+            lg.ctypes.data_as(FLOAT_PTR) if lg.size else None, N, lg.shape[1], tk.ctypes.data_as(INT_PTR) if N else None, rs.ctypes.data_as(INT_PTR) if N else None,
+            rp.ctypes.data_as(INT_PTR) if N else None, len(st[0]) - 1, st[0].ctypes.data_as(INT_PTR), st[1].ctypes.data_as(INT_PTR), st[2].ctypes.data_as(INT_PTR),
+            keep.ctypes.data_as(FLOAT_PTR), res.ctypes.data_as(INT_PTR)))
+        return dict(m=res[:N].copy(), row_greedy=res[64:64 + N].copy(), res=res, n_past=st[0], argmax=st[1], feed=st[2], slot_logits=keep)
 
     def amd_test_draft_sample(self, logits: np.ndarray, n_vocab: int, rows: np.ndarray, table: np.ndarray, params, top_k, seed_draws, row_tok: Sequence[int], slot: int,
                               state: np.ndarray, slot_logits: np.ndarray, bitmaps=None, bitmap_of_row=None) -> dict:

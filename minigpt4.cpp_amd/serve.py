@@ -40,6 +40,29 @@ def plan_waves(n_requests: int, conversations: int) -> List[List[int]]:
     return [list(range(i, min(n_requests, i + conversations))) for i in range(0, n_requests, conversations)]
 
 
+def ngram_draft(history: Sequence[int], ngram_max: int = 3, ngram_min: int = 1, n_draft: int = 4) -> List[int]:
+    """The n-gram drafter of lookup decoding (csrc/draft.hpp, `minigpt4_amd_decode_lookup`), in Python for the serving loop: the longest suffix of `history`
+    (ngram_max down to ngram_min tokens, ending in its last token) that also starts at an earlier index, its most recent occurrence; the tokens that followed it, cut at
+    n_draft, before the first id 2 (</s>) and at the end of the history.  [] = no match."""
+    if ngram_min < 1 or ngram_max < ngram_min or n_draft < 0:
+        raise ValueError("ngram_draft: need 1 <= ngram_min <= ngram_max and n_draft >= 0")
+    h = [int(t) for t in history]
+    n = len(h)
+    if n_draft < 1:
+        return []
+    for length in range(min(ngram_max, n - 1), ngram_min - 1, -1):
+        tail = h[n - length:]
+        for s in range(n - length - 1, -1, -1):
+            if h[s:s + length] == tail:
+                out = []
+                for t in h[s + length:]:
+                    if len(out) >= n_draft or t == 2:
+                        break
+                    out.append(t)
+                return out
+    return []
+
+
 class ReplicaServer:
     def __init__(self, vision_path: str, llm_path: str, conversations: int = 4, n_ctx: int = 2048, n_batch: int = 512, seed: int = 1337,
                  library: Optional[ML.MiniGPT4SharedLibrary] = None, verbosity: int = 0, rank: int = 0, world: int = 1, device=None, prefix_cache: int = 0):
@@ -58,6 +81,8 @@ class ReplicaServer:
         if prefix_cache:
             self.lib.amd_set_prefix_cache(self.ctx, prefix_cache)
         self._parked = {}                      # session id -> snapshot of the idle session
+        self._speculation = False              # run(lookup=...) switches draft verification on at its first use
+        self._row_cap = min(64, max(n_batch, 32, conversations))   # rows one verify pass holds: 64, and the context's activation rows (include/minigpt4_amd.h)
 
     def suspend(self, slot: int) -> bytes:
         """Conversation `slot` as a snapshot (queued rows are evaluated first); the slot is reset and free for another conversation."""
@@ -94,8 +119,17 @@ class ReplicaServer:
             frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
             negative_prompt: Optional[str] = None, regex=None, sessions: Optional[Sequence] = None, device_sampling: bool = False,
             seeds: Optional[Sequence[int]] = None, tfs_z: float = 1.0, typical_p: float = 1.0, min_p: float = 0.0, mirostat: int = 0, mirostat_tau: float = 5.0,
-            mirostat_eta: float = 0.1) -> List[str]:
-        """tfs_z, typical_p, min_p, mirostat (0 or 2), mirostat_tau, mirostat_eta: the extended rule of device-side sampling (include/minigpt4_amd.h), honoured with
+            mirostat_eta: float = 0.1, lookup: int = 0) -> List[str]:
+        """lookup = n_draft (1 .. 7; 0, the default, is exactly the decode loop below): greedy lookup decoding for the whole wave.  Every iteration of the decode loop is
+        ONE `minigpt4_amd_verify_draft_batch`: each unfinished request brings its next token and up to n_draft guesses behind it -- `ngram_draft` over the request's
+        tokenized prompt followed by the tokens it has emitted, cut at the tokens the request still wants -- through one weight pass and keeps the guesses the pass's own
+        logits confirm, so the answers are those of temp = 0 without lookup.  The kept tokens go through the same piece-by-piece stop rule; tokens kept behind the stop are
+        discarded.  A pass holds 64 rows (and no more than the context's activation rows, max(n_batch, 32, conversations)): drafts are shortened, in slot order,
+        where the wave's rows would not fit.  (A request's first iteration sends no guess: the pass itself tells which token comes next.)  One difference from the plain loop: on a full context
+        that cannot shift the request ENDS (the pass leaves it out), where the plain loop goes on emitting the token it cannot evaluate until max_tokens.  `minigpt4_amd_set_speculation(7)` is called at first
+        use.  The pass decides on raw logits at temp <= 0 only, so ValueError together with temp > 0, penalties, logit_bias, regex, logprobs, num_beams > 1,
+        guidance_scale != 1, device_sampling, and sessions (a parked snapshot would hold rows behind the stop).
+        tfs_z, typical_p, min_p, mirostat (0 or 2), mirostat_tau, mirostat_eta: the extended rule of device-side sampling (include/minigpt4_amd.h), honoured with
         device_sampling=True -- every step is then ONE `minigpt4_amd_end_chat_batch_sampled_ex`, and a request's mirostat mu is its own: unset
         (`minigpt4_amd_conversation_mirostat`) when the request takes its slot, so its text does not depend on its partners.  A non-neutral value without
         device_sampling raises ValueError (the host chain's mirostat state is the context's).
@@ -129,6 +163,14 @@ class ReplicaServer:
         token of request i (swallowed "##" pieces included), dict(id, piece, logprob, rank, top=[(piece, logprob), ...]) with `logprobs` alternatives -- the
         log-probabilities of the raw logits, whatever temp / top_k / top_p.  The return value is the same."""
         lib, ctx = self.lib, self.ctx
+        if lookup:
+            if isinstance(lookup, bool) or not isinstance(lookup, int) or not 1 <= lookup <= 7:
+                raise ValueError("lookup must be 0 (off) or 1 .. 7 draft tokens")
+            bad = [name for name, on in (("temp > 0", temp > 0), ("penalties", repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0),
+                                         ("logit_bias", bool(logit_bias)), ("regex", regex is not None), ("logprobs", logprobs > 0), ("num_beams > 1", num_beams > 1),
+                                         ("guidance_scale != 1", guidance_scale != 1.0), ("device_sampling", bool(device_sampling)), ("sessions", sessions is not None)) if on]
+            if bad:
+                raise ValueError("lookup decides greedily on raw logits: not available with " + ", ".join(bad))
         if num_beams < 1 or num_beams > 8 or num_beams > self.conversations:
             raise ValueError("num_beams must be 1 .. min(8, conversations)")
         if num_beams > 1 and logprobs > 0:
@@ -177,7 +219,7 @@ class ReplicaServer:
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
-                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None, chain)
+                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None, chain, lookup)
         finally:
             if self._constraint:
                 for slot in range(self.conversations):
@@ -215,9 +257,12 @@ class ReplicaServer:
                 shown += piece
         return shown
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None, chain=None) -> List[str]:
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None, chain=None, lookup=0) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
+        if lookup and not self._speculation:
+            lib.amd_set_speculation(ctx, 7)
+            self._speculation = True
         if penalised:
             lib.amd_set_penalties(ctx, True)
         self.last_logprobs = [[] for _ in requests] if logprobs > 0 else None
@@ -271,6 +316,50 @@ class ReplicaServer:
                 shown = {slot: "" for slot in range(len(wave))}
                 left = {slot: requests[i].max_tokens for slot, i in enumerate(wave)}
                 active = [slot for slot in range(len(wave)) if left[slot] > 0]
+
+                def take(slot, piece):                        # THE stop rule, one piece at a time, for both loops below: True = the request is done
+                    left[slot] -= 1
+                    text[slot] += piece
+                    done = left[slot] <= 0
+                    if self._constraint:                          # the pattern decides: the answer ends where the constraint let "</s>" through
+                        if piece == "</s>":
+                            done = True
+                        else:
+                            shown[slot] += piece
+                    elif not ignore_eos:
+                        if lib.minigpt4_contains_eos_token(piece):
+                            pass                                  # swallowed, like the reference's `continue`
+                        elif lib.minigpt4_is_eos(text[slot]):
+                            done = True
+                        else:
+                            shown[slot] += piece
+                    else:
+                        shown[slot] += piece
+                    return done
+                if lookup:                                    # the drafter's history per request: its prompt's tokens, then what it emits; the token that comes next
+                    corpus = {slot: lib.amd_tokenize(ctx, requests[i].prompt.encode("utf-8"), add_bos=False) for slot, i in enumerate(wave)}
+                    coming = {slot: None for slot in range(len(wave))}
+                while active and lookup:
+                    spare, drafts = getattr(self, "_row_cap", 64) - len(active), []   # draft rows the pass holds beside one row per request: later drafts are shortened
+                    for slot in active:
+                        d = [] if coming[slot] is None else ngram_draft(corpus[slot] + [coming[slot]], n_draft=min(lookup, left[slot] - 1, spare))
+                        spare -= len(d)
+                        drafts.append(d)
+                    step = lib.amd_verify_draft_batch(ctx, active, drafts)
+                    nxt = []
+                    for r, slot in enumerate(active):
+                        ids = [int(t) for t in step["ids"][r]]
+                        done = not ids                            # a full context that cannot shift: the request ends here
+                        if ids:
+                            coming[slot] = int(step["row_greedy"][r][len(ids) - 1])
+                        for t in ids:                             # piece by piece; what was kept behind the stop is discarded
+                            corpus[slot].append(t)
+                            done = take(slot, lib.amd_token_piece(ctx, t))
+                            if done:
+                                break
+                        if not done:
+                            nxt.append(slot)
+                    active = nxt
                 while active:
                     if logprobs > 0:
                         step = lib.amd_end_chat_batch_top(ctx, active, top_n=logprobs, temp=temp, top_k=top_k, top_p=top_p)
@@ -287,24 +376,7 @@ class ReplicaServer:
                         pieces = lib.amd_end_chat_batch(ctx, active, temp=temp, top_k=top_k, top_p=top_p)
                     nxt = []
                     for slot, piece in zip(active, pieces):
-                        left[slot] -= 1
-                        text[slot] += piece
-                        done = left[slot] <= 0
-                        if self._constraint:                      # the pattern decides: the answer ends where the constraint let "</s>" through
-                            if piece == "</s>":
-                                done = True
-                            else:
-                                shown[slot] += piece
-                        elif not ignore_eos:
-                            if lib.minigpt4_contains_eos_token(piece):
-                                pass                                  # swallowed, like the reference's `continue`
-                            elif lib.minigpt4_is_eos(text[slot]):
-                                done = True
-                            else:
-                                shown[slot] += piece
-                        else:
-                            shown[slot] += piece
-                        if not done:
+                        if not take(slot, piece):
                             nxt.append(slot)
                     active = nxt
                 for slot, i in enumerate(wave):
@@ -334,7 +406,7 @@ def serve(requests: Sequence[Request], vision_path: str, llm_path: str, conversa
         out = server.run([requests[i] for i in mine], **{k: v for k, v in kw.items() if k in ("temp", "top_k", "top_p", "ignore_eos", "logprobs", "repeat_penalty", "repeat_last_n",
                                                                                                 "presence_penalty", "frequency_penalty", "logit_bias", "num_beams",
                                                                                                 "length_penalty", "guidance_scale", "negative_prompt", "regex", "device_sampling",
-                                                                                                "tfs_z", "typical_p", "min_p", "mirostat", "mirostat_tau", "mirostat_eta")},
+                                                                                                "tfs_z", "typical_p", "min_p", "mirostat", "mirostat_tau", "mirostat_eta", "lookup")},
                          **({"seeds": [(kw["seeds"][i] if kw.get("seeds") is not None else i) for i in mine]} if kw.get("device_sampling") or kw.get("seeds") is not None else {}))   # a request's seed follows it to its rank
     finally:
         server.close()
