@@ -19,13 +19,14 @@ enum Err : int {
 
 // ggml_type numbering (LLM file); the vision file's MiniGPT4DataType is mapped onto it by the loader.
 enum GType : int { GT_F32 = 0, GT_F16 = 1, GT_Q4_0 = 2, GT_Q4_1 = 3, GT_Q5_0 = 6, GT_Q5_1 = 7, GT_Q8_0 = 8, GT_Q8_1 = 9, GT_Q2_K = 10,
-                   GT_Q3_K = 11, GT_Q4_K = 12, GT_Q5_K = 13, GT_Q6_K = 14, GT_Q8_K = 15, GT_I32 = 18, GT_I64 = 19 };
+                   GT_Q3_K = 11, GT_Q4_K = 12, GT_Q5_K = 13, GT_Q6_K = 14, GT_Q8_K = 15, GT_I32 = 18, GT_I64 = 19,
+                   GT_IQ4_NL = 20, GT_IQ4_XS = 23 };   // the non-linear 4-bit formats: a 16-entry int8 codebook instead of q - 8 (qtraits.hpp)
 
-inline int gt_block(int t) { switch (t) { case GT_F32: case GT_F16: case GT_I32: case GT_I64: return 1; case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_Q8_K: return 256; default: return 32; } }
+inline int gt_block(int t) { switch (t) { case GT_F32: case GT_F16: case GT_I32: case GT_I64: return 1; case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_Q8_K: case GT_IQ4_XS: return 256; default: return 32; } }
 inline int gt_bytes(int t) {
     switch (t) { case GT_F32: case GT_I32: return 4; case GT_F16: return 2; case GT_I64: return 8; case GT_Q4_0: return 18; case GT_Q4_1: return 20; case GT_Q5_0: return 22;
         case GT_Q5_1: return 24; case GT_Q8_0: return 34; case GT_Q8_1: return 40; case GT_Q2_K: return 84; case GT_Q3_K: return 110; case GT_Q4_K: return 144;
-        case GT_Q5_K: return 176; case GT_Q6_K: return 210; case GT_Q8_K: return 292; default: return 0; }
+        case GT_Q5_K: return 176; case GT_Q6_K: return 210; case GT_Q8_K: return 292; case GT_IQ4_NL: return 18; case GT_IQ4_XS: return 136; default: return 0; }
 }
 inline size_t gt_nbytes(int t, size_t n) { return n / (size_t)gt_block(t) * (size_t)gt_bytes(t); }
 const char *gt_name(int t);
@@ -62,6 +63,7 @@ template <typename K> inline hipError_t lds_optin_max(K kernel) {
 // A "unit" is 16 bytes of the main quant plane = what one lane fetches with one dwordx4 load:
 //   Q4_0/Q4_1/Q5_0/Q5_1 : 1 unit = 1 block (32 weights)        Q8_0 : 1 unit = half a block (16 weights)
 //   Q4_K/Q5_K/Q6_K      : 1 unit = 32 weights (8 units / super-block)
+//   IQ4_NL : 1 unit = 1 block (as Q4_0)                        IQ4_XS : 1 unit = 32 weights in element order (8 units / super-block)
 //   F16 : 8 weights, F32 : 4 weights
 struct QWeight {
     int type = -1;
@@ -69,7 +71,7 @@ struct QWeight {
     const uint8_t *qs = nullptr;     // main plane  [rows][units][16]
     const uint8_t *qh = nullptr;     // high-bit plane, pre-transposed for v_dot4: Q5_*: 4 B/unit, Q6_K: 8 B/unit
     const uint8_t *sc = nullptr;     // scale plane: Q4_0/Q5_0/Q8_0: f16 d per block; Q4_1/Q5_1: {d,m}; Q4_K/Q5_K: 16 B {d,dmin,scales12} per
-                                     //   super-block; Q6_K: 2 int8 per unit
+                                     //   super-block; Q6_K: 2 int8 per unit; IQ4_NL: f16 d per block; IQ4_XS: 16 B {d, -, ls_0..7 - 32 as int8} per super-block
     const uint8_t *d = nullptr;      // Q6_K: f16 d per super-block
     size_t bytes = 0;                // HBM bytes of all planes (== file bytes of the tensor)
 };
@@ -99,7 +101,7 @@ struct ActQ {
 };
 enum ActMask : int { ACT_Q8K = 1, ACT_Q80 = 2, ACT_F16 = 4, ACT_F32 = 8 };
 __host__ __device__ inline int act_mask_for(int wtype) {
-    switch (wtype) { case GT_Q4_0: case GT_Q5_0: case GT_Q8_0: case GT_Q4_1: case GT_Q5_1: return ACT_Q80; case GT_Q2_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: return ACT_Q8K;
+    switch (wtype) { case GT_Q4_0: case GT_Q5_0: case GT_Q8_0: case GT_Q4_1: case GT_Q5_1: case GT_IQ4_NL: return ACT_Q80; case GT_Q2_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_XS: return ACT_Q8K;
         case GT_F16: return ACT_F16; case GT_F32: return ACT_F32; default: return 0; }
 }
 

@@ -46,4 +46,18 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return r;
 }
 
+// IQ4_NL / IQ4_XS codebook: kvalues_iq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113} as four dwords (entry n = byte n & 3 of dword
+// n >> 2), looked up four nibbles at a time in registers by v_perm_b32 (selector byte 0..3 -> byte of the second operand, 4..7 -> of the first).
+constexpr unsigned IQ4_T0 = 0xBFAD9881u, IQ4_T1 = 0xF6EADDCFu, IQ4_T2 = 0x26190D01u, IQ4_T3 = 0x71594535u;
+__device__ __forceinline__ int iq4_kv(int n) { const unsigned t = n < 8 ? (n < 4 ? IQ4_T0 : IQ4_T1) : (n < 12 ? IQ4_T2 : IQ4_T3); return (int)(signed char)(t >> (8 * (n & 3))); }
+// four nibbles (one per byte, 0..15) -> their four int8 codebook values: both halves of the table are looked up with the low three bits, and bit 3 selects between them
+// through a byte mask that is itself a lookup (selector (n >> 1) & 7 is >= 4 exactly where n >= 8).  Seven vector operations per four weights: the prompt kernel's form,
+// where the unpack runs once per 256 weights and row tile.
+__device__ __forceinline__ int iq4_lut4(unsigned n) {
+    const unsigned s = n & 0x07070707u;
+    const unsigned lo = __builtin_amdgcn_perm(IQ4_T1, IQ4_T0, s), hi = __builtin_amdgcn_perm(IQ4_T3, IQ4_T2, s);
+    const unsigned m = __builtin_amdgcn_perm(0xFFFFFFFFu, 0u, (n >> 1) & 0x07070707u);
+    return (int)((hi & m) | (lo & ~m));
+}
+
 }  // namespace mg4

@@ -30,7 +30,8 @@ void log_msg(int level, const char *tag, const char *fmt, ...) {
 const char *gt_name(int t) {
     switch (t) { case GT_F32: return "f32"; case GT_F16: return "f16"; case GT_Q4_0: return "q4_0"; case GT_Q4_1: return "q4_1"; case GT_Q5_0: return "q5_0";
         case GT_Q5_1: return "q5_1"; case GT_Q8_0: return "q8_0"; case GT_Q8_1: return "q8_1"; case GT_Q2_K: return "q2_K"; case GT_Q3_K: return "q3_K";
-        case GT_Q4_K: return "q4_K"; case GT_Q5_K: return "q5_K"; case GT_Q6_K: return "q6_K"; case GT_Q8_K: return "q8_K"; case GT_I32: return "i32"; case GT_I64: return "i64"; default: return "?"; }
+        case GT_Q4_K: return "q4_K"; case GT_Q5_K: return "q5_K"; case GT_Q6_K: return "q6_K"; case GT_Q8_K: return "q8_K"; case GT_I32: return "i32"; case GT_I64: return "i64";
+        case GT_IQ4_NL: return "iq4_nl"; case GT_IQ4_XS: return "iq4_xs"; default: return "?"; }
 }
 
 // ---------------------------------------------------------------------------------------------------- mmap

@@ -93,13 +93,15 @@ size_t plan_qweight(int type, int rows, int cols, QWeight &w, uint8_t *base) {
     case GT_Q4_K: w.qs = take(n / 256 * 128); w.sc = take(n / 256 * 16); break;
     case GT_Q5_K: w.qs = take(n / 256 * 128); w.qh = take(n / 256 * 32); w.sc = take(n / 256 * 16); break;
     case GT_Q6_K: w.qs = take(n / 256 * 128); w.qh = take(n / 256 * 64); w.sc = take(n / 256 * 16); w.d = take(n / 256 * 2); break;
+    case GT_IQ4_NL: w.qs = take(n / 32 * 16); w.sc = take(n / 32 * 2); break;
+    case GT_IQ4_XS: w.qs = take(n / 256 * 128); w.sc = take(n / 256 * 16); break;   // quants in element order; {d, -, ls - 32 as int8 x 8} per super-block (qtraits.hpp: why not the stored 8 bytes)
     default: return 0;
     }
     w.bytes = gt_nbytes(type, n);
     return off;
 }
 bool qweight_supported(int type) {
-    switch (type) { case GT_F32: case GT_F16: case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q8_0: case GT_Q2_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: return true; default: return false; }
+    switch (type) { case GT_F32: case GT_F16: case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q8_0: case GT_Q2_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_NL: case GT_IQ4_XS: return true; default: return false; }
 }
 
 // high-bit transposition for 5-bit types: element e of 32 (lo: e<16 -> dword k=e/4, byte i=e%4, slot w=k; hi: e>=16 -> w=4+k)
@@ -115,7 +117,7 @@ __global__ void k_repack(const uint8_t *__restrict__ raw, QWeight w, size_t n_un
     if (g >= n_units) return;
     uint8_t *qs = const_cast<uint8_t *>(w.qs), *qh = const_cast<uint8_t *>(w.qh), *sc = const_cast<uint8_t *>(w.sc), *dd = const_cast<uint8_t *>(w.d);
     switch (w.type) {
-    case GT_Q4_0: { const uint8_t *b = raw + g * 18; sc[g * 2] = b[0]; sc[g * 2 + 1] = b[1]; for (int i = 0; i < 16; i++) qs[g * 16 + i] = b[2 + i]; break; }
+    case GT_Q4_0: case GT_IQ4_NL: { const uint8_t *b = raw + g * 18; sc[g * 2] = b[0]; sc[g * 2 + 1] = b[1]; for (int i = 0; i < 16; i++) qs[g * 16 + i] = b[2 + i]; break; }
     case GT_Q4_1: { const uint8_t *b = raw + g * 20; for (int i = 0; i < 4; i++) sc[g * 4 + i] = b[i]; for (int i = 0; i < 16; i++) qs[g * 16 + i] = b[4 + i]; break; }
     case GT_Q5_0: case GT_Q5_1: {
         const int hdr = w.type == GT_Q5_0 ? 2 : 4; const uint8_t *b = raw + g * (size_t)(hdr + 20);
@@ -158,6 +160,13 @@ __global__ void k_repack(const uint8_t *__restrict__ raw, QWeight w, size_t n_un
         reinterpret_cast<unsigned *>(qh + g * 8)[0] = Plo; reinterpret_cast<unsigned *>(qh + g * 8)[1] = Phi;
         sc[g * 2] = b[192 + 8 * n + 2 * c + h]; sc[g * 2 + 1] = b[192 + 8 * n + 4 + 2 * c + h];
         for (int i = 0; i < 16; i++) qs[g * 16 + i] = b[u * 16 + i];
+        break; }
+    case GT_IQ4_XS: {   // block_iq4_xs = d | scales_h | scales_l[4] | qs[128]; sub-block ib = qs[16 ib .. 16 ib + 15]
+        const size_t sb = g >> 3; const int ib = (int)(g & 7); const uint8_t *b = raw + sb * 136;
+        if (ib == 0) { sc[sb * 16] = b[0]; sc[sb * 16 + 1] = b[1]; for (int i = 2; i < 8; i++) sc[sb * 16 + i] = 0; }
+        const int sh = b[2] | (b[3] << 8), ls = ((b[4 + ib / 2] >> (4 * (ib & 1))) & 15) | (((sh >> (2 * ib)) & 3) << 4);
+        sc[sb * 16 + 8 + ib] = (uint8_t)(signed char)(ls - 32);
+        for (int i = 0; i < 16; i++) qs[g * 16 + i] = b[8 + ib * 16 + i];
         break; }
     case GT_F16: case GT_F32: { for (int i = 0; i < 16; i++) qs[g * 16 + i] = raw[g * 16 + i]; break; }
     default: break;
@@ -248,8 +257,8 @@ enum EpiKind : int { EPI_STORE = 0, EPI_SILU_PAIR = 1, EPI_REF = 2 };   // EPI_R
 template <int... NU> struct UnitList {};
 using Units1to7 = UnitList<1, 2, 3, 4, 5, 6, 7>;
 using Units1to3 = UnitList<1, 2, 3>;
-template <int T> constexpr bool tr_is_kquant() { return T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K; }
-template <int T> constexpr bool tr_is_q32() { return T == GT_Q4_0 || T == GT_Q4_1 || T == GT_Q5_0 || T == GT_Q5_1; }
+template <int T> constexpr bool tr_is_kquant() { return T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K || T == GT_IQ4_XS; }   // 8 units per 256-weight super-block, Q8_K rows
+template <int T> constexpr bool tr_is_q32() { return T == GT_Q4_0 || T == GT_Q4_1 || T == GT_Q5_0 || T == GT_Q5_1 || T == GT_IQ4_NL; }
 template <int T> constexpr bool tr_is_narrow() { return T == GT_Q8_0 || T == GT_F16; }   // 16-byte units of 16 / 8 weights: more units per row than the 32-weight types
 // k_matvec_v2<T, NU, R, PRO, EPI>.  Q8_0 / F16: only a few unit counts, a row takes the smallest one that covers it (the surplus units are masked like any ragged
 // tail) -- Q8_0: K <= 1024 | 4096 | 5120 | 11264; F16: K <= 512 | 1024 | 4096 | 5120.  Pair epilogue (w1|w3): K <= 6144.  EPI_REF: the k-quants of the headline files
@@ -270,7 +279,7 @@ template <int T, int NU, int EPI> constexpr int mv_rows_per_group() {   // R: ro
 using MixUnits = UnitList<1, 2, 3, 4>;          // k_matvec_mix<T1, T2, NU, ..>
 // k_matvec_tn<T, NU, TN, PRO> (TN = 2..4 rows): every unit count without a preparation, K <= 6144 of Q4_0 and the k-quants with one; k_matvec_tn_mix: K <= 6144
 template <int T> constexpr auto mv_tn_units() { return std::conditional_t<tr_is_kquant<T>() || tr_is_q32<T>(), Units1to7, UnitList<>>{}; }
-template <int T> constexpr auto mv_tn_pro_units() { return std::conditional_t<T == GT_Q4_0 || tr_is_kquant<T>(), Units1to3, UnitList<>>{}; }
+template <int T> constexpr auto mv_tn_pro_units() { return std::conditional_t<T == GT_Q4_0 || T == GT_IQ4_NL || tr_is_kquant<T>(), Units1to3, UnitList<>>{}; }
 using TnMixUnits = Units1to3;
 using RefRowUnits = UnitList<1, 2, 3, 4, 6, 7>;  // k_mul_mat_ref_row / k_mul_mat_ref_rows (the 7B / 13B widths)
 
@@ -295,6 +304,8 @@ template <class F> static bool for_weight_type(int type, F &&f) {
     case GT_Q4_K: return f(std::integral_constant<int, GT_Q4_K>{});
     case GT_Q5_K: return f(std::integral_constant<int, GT_Q5_K>{});
     case GT_Q6_K: return f(std::integral_constant<int, GT_Q6_K>{});
+    case GT_IQ4_NL: return f(std::integral_constant<int, GT_IQ4_NL>{});
+    case GT_IQ4_XS: return f(std::integral_constant<int, GT_IQ4_XS>{});
     case GT_F16: return f(std::integral_constant<int, GT_F16>{});
     case GT_F32: return f(std::integral_constant<int, GT_F32>{});
     default: return false;
@@ -643,7 +654,7 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
         L.xh = reinterpret_cast<__half *>(smem_mv + 128);                // F16 weights: the fp16 row takes the place of the two int8 images (2 K bytes)
         L.xf = nullptr;
         constexpr int RND = (NU * 64 * X::EPU / 4 + MV_FAT_MIN - 1) / MV_FAT_MIN;    // K <= NU * 64 * EPU elements, 4 per thread per round, >= MV_FAT_MIN threads
-        constexpr int mask = T == GT_F16 ? ACT_F16 : (T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K) ? ACT_Q8K : ACT_Q80;
+        constexpr int mask = T == GT_F16 ? ACT_F16 : tr_is_kquant<T>() ? ACT_Q8K : ACT_Q80;
         float4 xv[RND], yv[RND];
         bool in[RND];
 #pragma unroll
@@ -962,7 +973,7 @@ bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *co
 // Per row the arithmetic is exactly the single-row kernel's: the same unit dot products, the same per-lane fma order, the same wave reduction.
 // =====================================================================================================================
 static size_t mv_tn_lds(int type, int K, int TN) {
-    const bool kq = type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K;
+    const bool kq = act_mask_for(type) == ACT_Q8K;
     const size_t per_row = kq ? (size_t)K + (size_t)(K / 256) * 4 + (size_t)(K / 16) * 2 : (size_t)K + (size_t)(K / 32) * 16;
     return (size_t)TN * per_row + 64;
 }
@@ -1021,7 +1032,7 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
     constexpr bool REG = mv_tn_reg<NU, TN>();
     typename X::AU ar[REG ? TN : 1][REG ? NU : 1];
     if (REG && PRO) {
-        constexpr int mask = (T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K) ? ACT_Q8K : ACT_Q80;
+        constexpr int mask = tr_is_kquant<T>() ? ACT_Q8K : ACT_Q80;
         double *red = reinterpret_cast<double *>(smem_tn);               // [TN][8 waves]
         if (PRO == 1) {
 #pragma unroll
@@ -1252,7 +1263,7 @@ bool launch_matvec_rows_mixed(const QWeight *const *W1, float *const *y1, int n1
 // precisely the vision tower's MFMA GEMM (v_mfma_f32_32x32x16_f16, fp32 accumulators), so rows >= 16 go there: BASELINE.json configs[4]
 // (13B f16, 512-token prefill) is MFMA-bound instead of re-streaming 25 GB of weights once per 4 tokens.
 void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s) {
-    if (tune.mmq >= 2 && N >= 5 && (A.bsq || W.type == GT_Q4_0) && mmq2_supported(W.type, W.rows, W.cols)) {
+    if (tune.mmq >= 2 && N >= 5 && (A.bsq || act_mask_for(W.type) == ACT_Q80) && mmq2_supported(W.type, W.rows, W.cols)) {
         const QWeight *Wp[1] = {&W}; float *Yp[1] = {y}; const float *Rp[1] = {residual};
         if (launch_mmq2_set(Wp, Yp, residual ? Rp : nullptr, 1, A, N, ldy, tune, s)) return;
     }
@@ -1377,6 +1388,10 @@ __device__ float dequant_elem(int type, const uint8_t *row, int e) {
     case GT_F32: return reinterpret_cast<const float *>(row)[e];
     case GT_F16: return h2f_bits(reinterpret_cast<const unsigned short *>(row)[e]);
     case GT_Q4_0: { const uint8_t *b = row + (e >> 5) * 18; const int j = e & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); const int q = j < 16 ? (b[2 + j] & 15) : (b[2 + j - 16] >> 4); return (float)(q - 8) * d; }
+    case GT_IQ4_NL: { const uint8_t *b = row + (e >> 5) * 18; const int j = e & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); return d * (float)iq4_kv(j < 16 ? (b[2 + j] & 15) : (b[2 + j - 16] >> 4)); }
+    case GT_IQ4_XS: { const uint8_t *b = row + (e >> 8) * 136; const int i = e & 255, ib = i >> 5, j = i & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); const int sh = b[2] | (b[3] << 8);
+        const int ls = ((b[4 + ib / 2] >> (4 * (ib & 1))) & 15) | (((sh >> (2 * ib)) & 3) << 4); const uint8_t qb = b[8 + 16 * ib + (j & 15)];
+        return (d * (float)(ls - 32)) * (float)iq4_kv(j < 16 ? (qb & 15) : (qb >> 4)); }
     case GT_Q4_1: { const uint8_t *b = row + (e >> 5) * 20; const int j = e & 31; const float d = h2f_bits(b[0] | (b[1] << 8)), m = h2f_bits(b[2] | (b[3] << 8)); const int q = j < 16 ? (b[4 + j] & 15) : (b[4 + j - 16] >> 4); return (float)q * d + m; }
     case GT_Q5_0: { const uint8_t *b = row + (e >> 5) * 22; const int j = e & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); const unsigned qh = b[2] | (b[3] << 8) | (b[4] << 16) | ((unsigned)b[5] << 24);
         const int q = (j < 16 ? (b[6 + j] & 15) : (b[6 + j - 16] >> 4)) | (((qh >> j) & 1) << 4); return (float)(q - 16) * d; }

@@ -30,101 +30,9 @@
 // Measured and removed (profiles/r02g_prefill_generations_microbench.log): pre-scaled "prefill planes" -- sub-block scale x quant stored as two int8 digits,
 // 2 bytes per weight, so that the scales ride inside the MFMA accumulation (exact, bit-identical results, 41 % fewer VALU instructions) -- lost on Q4_K / Q5_K
 // (w1|w3 at 142 rows: 155 vs 100 us): 2.8 x the weight bytes per chunk of <= 96 tokens turned the kernel into a latency-bound HBM stream; it won only on Q6_K.
-#include "kernels.hpp"
-#include "devutil.hpp"
+#include "mmq2_common.hpp"
 
 namespace mg4 {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-namespace {
-__device__ __forceinline__ float h2f_b(unsigned short h) { return __half2float(__ushort_as_half(h)); }
-__device__ __forceinline__ v4i ldg16(const void *p) { return *reinterpret_cast<const v4i *>(p); }
-__device__ __forceinline__ v16i zero16() { v16i z; for (int i = 0; i < 16; i++) z[i] = 0; return z; }
-__device__ __forceinline__ int tok_of(int reg, int hh) { return (reg & 3) + 8 * (reg >> 2) + 4 * hh; }   // MFMA 32x32 C layout: row (= token) of accumulator register `reg`
-__device__ __forceinline__ long pack64(int lo, int hi) { return (long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo); }
-__device__ __forceinline__ int sext6(int x) { const int yv = x ^ 0x20202020; const int s = yv & 0x20202020; return yv | (s << 1) | (s << 2); }   // 4 x (6-bit q - 32) as int8
-
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *glb_ptr_t;
-__device__ __forceinline__ void dma16(const void *src, unsigned char *lds_wave_base) {   // LDS[lds_wave_base + lane * 16 .. +16) <- src (per lane)
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ void dma4(const void *src, unsigned char *lds_wave_base) {    // LDS[lds_wave_base + lane * 4 .. +4) <- src
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)src, (lds_ptr_t)lds_wave_base, 4, 0, 0);
-}
-}  // namespace
-
-// LDS image of one activation stage (TT token tiles of one super-block):
-//   q8 [TT * 32 tokens][16 chunks of 16 B], chunk c of token t stored at slot c ^ (t & 15)
-//   bs [TTP * 32][16 B]  digit-split per-32 sums (TTP = TT rounded up to 2: one DMA instruction covers 64 tokens)
-//   dk [TTP * 32] fp32   activation super-block scale
-template <int TT> struct Mmq2Stage {
-    static constexpr int TTP = (TT + 1) & ~1;
-    static constexpr int Q8 = TT * 32 * 256, BS = TTP * 32 * 16, DK = TTP * 32 * 4;
-    static constexpr int BYTES = Q8 + BS + DK;
-};
-
-struct Mmq2Args {
-    QWeight w[3];                 // 1..3 matrices of one type and one shape; row group g belongs to matrix g / groups_each
-    float *y[3];                  // outputs, [N][ldy] each (K split: slab z at y + z * slab_stride)
-    const float *res[3];          // optional residual inputs (only without a K split)
-    int n_mat, groups_each;       // row groups (of 128 rows) per matrix
-    int N, ldy;
-    int n_tiles, tiles_per_chunk; // token tiles of 32 in total / per grid.y chunk
-    int sb_per_split;             // super-blocks per grid.z slice
-    long long slab_stride;        // floats between K-split slabs
-};
-
-// Requests stage `sb` of this chunk into LDS buffer `st` (all WPB waves of the workgroup take part; every request is unconditional, indices clamped).  n_q8: q8 wave-instructions
-// (4 tokens each) that carry live tokens -- the single-wave form (batched decode: a few rows) skips the rest; their LDS rows keep stale bytes that only ever reach
-// accumulator registers of tokens >= N, which are never stored.
-template <int TT, int WPB>
-__device__ __forceinline__ void mmq2_stage_load(const ActQ &A, int K, int NSB, int N, int t0, int sb, unsigned char *st, int wv, int lane, int n_q8) {
-    using S = Mmq2Stage<TT>;
-    // q8: TT * 8 wave-instructions of 4 tokens x 16 chunks; wave wv issues instructions wv * (8 TT / WPB) .. + 8 TT / WPB - 1
-#pragma unroll
-    for (int k = 0; k < 8 * TT / WPB; k++) {
-        const int ii = wv * (8 * TT / WPB) + k;
-        const int tl = 4 * ii + (lane >> 4);                 // token within the chunk
-        const int c = (lane & 15) ^ (tl & 15);               // logical chunk that lands in slot (lane & 15)
-        const int tok = min(t0 + tl, N - 1);
-        if (WPB == 4 || ii < n_q8) dma16(A.q8k + (size_t)tok * K + (size_t)sb * 256 + c * 16, st + ii * 1024);
-    }
-    if (WPB == 1 || wv == 0) {
-#pragma unroll
-        for (int j = 0; j < S::TTP / 2; j++) { const int tok = min(t0 + 64 * j + lane, N - 1); dma16(A.bsq + ((size_t)tok * NSB + sb) * 16, st + S::Q8 + j * 1024); }
-    }
-    if (WPB == 1 || wv == 1) {
-#pragma unroll
-        for (int j = 0; j < S::TTP / 2; j++) { const int tok = min(t0 + 64 * j + lane, N - 1); dma4(A.dk + (size_t)tok * NSB + sb, st + S::Q8 + S::BS + j * 256); }
-    }
-}
-
-// Result store: lane = weight row, accumulator register = token -> 32 consecutive floats per (register, lane half).  The residual values of a token tile are
-// requested together (clamped addresses, no branch around a load) before any of them is used.
-template <int TT>
-__device__ __forceinline__ void mmq2_store(const float (&acc)[TT][16], const Mmq2Args &a, int m, int orow, int rows, int t0, int my_tiles, int hh) {
-    float *y = a.y[m] + (size_t)blockIdx.z * a.slab_stride;
-    const bool has_res = gridDim.z == 1 && a.res[m] != nullptr;
-    const float *rb = has_res ? a.res[m] : y;
-    const int rowc = min(orow, rows - 1);
-#pragma unroll
-    for (int tt = 0; tt < TT; tt++) {
-        if (tt < my_tiles) {
-            float rv[16];
-#pragma unroll
-            for (int r = 0; r < 16; r++) rv[r] = rb[(size_t)min(t0 + tt * 32 + tok_of(r, hh), a.N - 1) * a.ldy + rowc];
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int tok = t0 + tt * 32 + tok_of(r, hh);
-                if (tok < a.N && orow < rows) y[(size_t)tok * a.ldy + orow] = has_res ? acc[tt][r] + rv[r] : acc[tt][r];
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Q4_K / Q5_K.  Unit u of a super-block (16 bytes of the repacked main plane): low nibbles = elements 64 (u >> 1) + 16 (u & 1) + i of sub-block 2 (u >> 1),
@@ -444,38 +352,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_mmq2_q6k(const Mmq2Args a, cons
 // their scales by LDS-DMA; one K = 32 MFMA per block, nibbles sign-extended to q - 8 at unpack time (no per-32 sum correction), and per block
 // acc = fma(d_w * d_a, (float)isum, acc) exactly as the decode kernel (Tr<GT_Q4_0>::dot) and ggml's AVX2 path do it.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int TT> struct Mmq2Stage80 {
-    static constexpr int TTP = (TT + 1) & ~1;
-    static constexpr int Q8 = TT * 32 * 256, DS = 8 * TTP * 32 * 4;      // q8 as Mmq2Stage; scales [8 blocks][TTP * 32 tokens] fp32 (token-contiguous: 4 accumulator registers = 16 bytes)
-    static constexpr int BYTES = Q8 + DS;
-};
-template <int TT, int WPB>
-__device__ __forceinline__ void mmq2_stage_load80(const ActQ &A, int K, int N, int t0, int sb, unsigned char *st, int wv, int lane, const unsigned (&tokoff)[Mmq2Stage80<TT>::TTP / 2], int n_q8) {
-    using S = Mmq2Stage80<TT>;
-#pragma unroll
-    for (int k = 0; k < 8 * TT / WPB; k++) {
-        const int ii = wv * (8 * TT / WPB) + k;
-        const int tl = 4 * ii + (lane >> 4);
-        const int c = (lane & 15) ^ (tl & 15);
-        const int tok = min(t0 + tl, N - 1);
-        if (WPB == 4 || ii < n_q8) dma16(A.q80 + (size_t)tok * K + (size_t)sb * 256 + c * 16, st + ii * 1024);
-    }
-    // scales: instruction (b, j) = block b of the super-chunk, tokens 64 j + lane; wave wv takes blocks wv and wv + 4 (the single wave: all 8).  tokoff[j] (this lane's row
-    // offset into d0) is computed once by the caller: rebuilding 64-bit addresses per instruction is cheaper than the 16 hoisted pointer pairs hipcc otherwise keeps (and spills)
-    constexpr int HJ = S::TTP / 2;
-#pragma unroll
-    for (int j = 0; j < HJ; j++) {
-        if (WPB == 4) {
-            const float *pj = A.d0 + (size_t)tokoff[j] + (size_t)sb * 8 + wv;
-            dma4(pj, st + S::Q8 + (wv * S::TTP * 32 + 64 * j) * 4);
-            dma4(pj + 4, st + S::Q8 + ((wv + 4) * S::TTP * 32 + 64 * j) * 4);
-        } else {
-            const float *pj = A.d0 + (size_t)tokoff[j] + (size_t)sb * 8;
-#pragma unroll
-            for (int b = 0; b < 8; b++) dma4(pj + b, st + S::Q8 + (b * S::TTP * 32 + 64 * j) * 4);
-        }
-    }
-}
 template <int TT, int WPB = 4>
 __global__ __launch_bounds__(64 * WPB, 2) void k_mmq2_q40(const Mmq2Args a, const ActQ A) {
     using S = Mmq2Stage80<TT>;
@@ -829,7 +705,9 @@ void launch_slab_reduce(const float *slabs, int n_slabs, long long slab_stride, 
     hipLaunchKernelGGL(k_mmq2_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, slabs, n_slabs, slab_stride, residual, y, n4);
 }
 
-bool mmq2_supported(int type, int rows, int cols) { return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0) && cols % 256 == 0 && rows >= 32; }
+bool mmq2_supported(int type, int rows, int cols) {
+    return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0 || type == GT_IQ4_NL || type == GT_IQ4_XS) && cols % 256 == 0 && rows >= 32;
+}
 
 template <typename KernelT>
 static void mmq2_launch_kernel(KernelT kernel, bool &attr_done, dim3 grid, int threads, size_t lds, hipStream_t s, const Mmq2Args &a, const ActQ &A) {
@@ -874,7 +752,7 @@ void launch_slab_flush(const SlabSrc &src, hipStream_t s) {
 }
 bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer, int force_ks) {
     if (defer) *defer = SlabSrc{};
-    if (n < 1 || n > 3 || N < 1 || (W[0]->type == GT_Q4_0 ? !(A.q80 && A.d0) : !A.bsq)) return false;
+    if (n < 1 || n > 3 || N < 1 || (act_mask_for(W[0]->type) == ACT_Q80 ? !(A.q80 && A.d0) : !A.bsq)) return false;
     for (int i = 0; i < n; i++) if (!mmq2_supported(W[i]->type, W[i]->rows, W[i]->cols) || W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false;
     Mmq2Args a{};
     for (int i = 0; i < n; i++) { a.w[i] = *W[i]; a.y[i] = y[i]; a.res[i] = residual ? residual[i] : nullptr; }
@@ -908,7 +786,8 @@ bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *cons
     const bool q40 = type == GT_Q4_0;
     // fast mode, Q4_K / Q5_K: the fp16-MFMA form (k_mmqh_q45k) whenever the activation rows carry their fp16 image; force_ks == 1 (parity mode: the oracle's fp32 order) keeps the int8 kernels
     const bool h16 = tune.mmqh && force_ks != 1 && (type == GT_Q4_K || type == GT_Q5_K) && A.q16 && A.bs16;
-    switch (a.tiles_per_chunk) {
+    if (type == GT_IQ4_NL || type == GT_IQ4_XS) launch_mmq2_iq4(type, grid, s, a, A);   // mmq2_iq4.hip; the K split above and the combine below are type-agnostic
+    else switch (a.tiles_per_chunk) {
     case 1: mmq2_launch_tt<1>(type, grid, 2 * (q40 ? Mmq2Stage80<1>::BYTES : Mmq2Stage<1>::BYTES) + 16384, s, a, A, h16); break;
     case 2: mmq2_launch_tt<2>(type, grid, 2 * (q40 ? Mmq2Stage80<2>::BYTES : Mmq2Stage<2>::BYTES) + 16384, s, a, A, h16); break;
     case 3: mmq2_launch_tt<3>(type, grid, 2 * (q40 ? Mmq2Stage80<3>::BYTES : Mmq2Stage<3>::BYTES) + 16384, s, a, A, h16); break;

@@ -323,6 +323,62 @@ static __device__ __forceinline__ void loada(const ActQ &A, int t, int K, int u,
         acc = fmaf(h2f_bits(w.dh) * a.d, (float)(mul24((int)(signed char)(w.sc & 0xFF), s0) + mul24((int)(signed char)(w.sc >> 8), s1)), acc);
     }
 };
+// IQ4_NL / IQ4_XS ----------------------------------------------------------------------------------------------------------
+// A nibble indexes the 16-entry int8 codebook (devutil.hpp); the looked-up value is a ready v_dot4 operand: no offset term, no min term.  The mat-vec kernels are
+// vector-issue bound, so the lookup stays in registers and the select between the table's halves is folded into the dot product, which is linear in the weight:
+//   lo = v_perm(L1, L0, n)       n < 8: L[n]        n >= 8: selectors 8..11 read the SIGN of a table byte (all of L are negative: 0xFF), 12 gives 0x00, 13..15 0xFF
+//   hi = v_perm(H3, H2, n ^ 8)   n >= 8: H[n - 8]   n < 8: selectors 8..11 (all of H are positive: 0x00), 12 -> 0x00, 13..15 -> 0xFF
+// so sum kv[n_j] a_j = dot4(lo, a) + dot4(hi, a) once L and H carry the other side's constant: L[n] = kv[n] + 1 for n = 5, 6, 7 and H[n - 8] = kv[n] + 1 for every
+// n >= 8 but 12 (all still int8 and of the same sign).  Five vector operations per four weights (xor, two v_perm, two v_dot4) where Q4_0 has one and the plain
+// mask-and-select form (iq4_lut4) eight.
+constexpr unsigned IQ4_L0 = IQ4_T0, IQ4_L1 = 0xF7EBDECFu, IQ4_H2 = 0x271A0E02u, IQ4_H3 = 0x725A4635u;
+__device__ __forceinline__ int iq4_dot4(unsigned n, int a, int s) {
+    s = dot4((int)__builtin_amdgcn_perm(IQ4_L1, IQ4_L0, n), a, s);
+    return dot4((int)__builtin_amdgcn_perm(IQ4_H3, IQ4_H2, n ^ 0x08080808u), a, s);
+}
+// the unit's 32 products: low nibbles against a0 (elements 0..15), high nibbles against a1 (16..31)
+__device__ __forceinline__ int iq4_dot32(const int4 &q, const int4 &a0, const int4 &a1) {
+    int s = 0;
+    s = iq4_dot4((unsigned)q.x & 0x0F0F0F0Fu, a0.x, s); s = iq4_dot4((unsigned)q.y & 0x0F0F0F0Fu, a0.y, s); s = iq4_dot4((unsigned)q.z & 0x0F0F0F0Fu, a0.z, s); s = iq4_dot4((unsigned)q.w & 0x0F0F0F0Fu, a0.w, s);
+    s = iq4_dot4(((unsigned)q.x >> 4) & 0x0F0F0F0Fu, a1.x, s); s = iq4_dot4(((unsigned)q.y >> 4) & 0x0F0F0F0Fu, a1.y, s); s = iq4_dot4(((unsigned)q.z >> 4) & 0x0F0F0F0Fu, a1.z, s); s = iq4_dot4(((unsigned)q.w >> 4) & 0x0F0F0F0Fu, a1.w, s);
+    return s;
+}
+template <> struct Tr<GT_IQ4_NL> {   // planes and block layout of Q4_0; ggml's vec_dot_iq4_nl_q8_0: per block sumf += (d_w * d_a) * sum kv * a
+    static constexpr int EPU = 32;
+    using WU = Tr<GT_Q4_0>::WU;
+    struct AU { int4 a0, a1; float d; };
+    static __device__ __forceinline__ void loadw(const QWeight &W, size_t g0, int u, WU &w) { Tr<GT_Q4_0>::loadw(W, g0, u, w); }
+    static __device__ __forceinline__ void mkb(const QWeight &W, size_t g0, WBuf &B) { Tr<GT_Q4_0>::mkb(W, g0, B); }
+    static __device__ __forceinline__ void loadb(const WBuf &B, int u, WU &w) { Tr<GT_Q4_0>::loadb(B, u, w); }
+    static __device__ __forceinline__ void loada(const ActQ &A, int t, int K, int u, AU &a) {
+        const int8_t *p = A.q80 + (size_t)t * K + (size_t)u * 32; a.a0 = ld16(p); a.a1 = ld16(p + 16); a.d = A.d0[(size_t)t * (K / 32) + u]; }
+    static constexpr int GROUP = 1, TERMS = 1;
+    static __device__ __forceinline__ void ints(const WU &w, const AU &a, int &i0, int &i1) { i0 = iq4_dot32(w.q, a.a0, a.a1); i1 = 0; }
+    static __device__ __forceinline__ void terms(const WU &w, const AU &a, int i0, int, float &f0, float &v0, float &f1, float &v1) { f0 = h2f_bits(w.dh) * a.d; v0 = (float)i0; f1 = v1 = 0.0f; }
+    static __device__ __forceinline__ void dot(const WU &w, const AU &a, float &acc) { acc = fmaf(h2f_bits(w.dh) * a.d, (float)iq4_dot32(w.q, a.a0, a.a1), acc); }
+};
+// IQ4_XS.  Scale plane: one 16-byte record per super-block, {fp16 d, 6 unused bytes, the eight sub-block scales ls - 32 as int8}, instead of the file's 8 bytes
+// {d, scales_h, scales_l}: a lane owns ONE sub-block and reads its scale with one byte load (plus d), where the stored form costs it six shift / mask operations per
+// unit on the vector ALU that bounds these kernels; the prompt kernel reads the record whole.  0.03 bits per weight of extra traffic.  The quants stay in element
+// order (unit ib = elements 32 ib .. 32 ib + 31), so the activation unit is 32 consecutive Q8_K values.  ggml's vec_dot_iq4_xs_q8_K: per super-block
+// sumf += (d_w * d_a) * sum_ib (ls - 32) * sum kv * a;  |ls - 32| <= 32 and |sum kv * a| < 2^19, so mul24 is exact.
+template <> struct Tr<GT_IQ4_XS> {
+    static constexpr int EPU = 32;
+    struct WU { int4 q; unsigned short dh; signed char ls; };
+    struct AU { int4 lo, hi; float d; };
+    static __device__ __forceinline__ void loadw(const QWeight &W, size_t g0, int u, WU &w) {
+        w.q = ldw<int4>(W.qs + g0 * 16 + (unsigned)(u * 16)); const uint8_t *r = W.sc + (g0 >> 3) * 16 + (unsigned)((u >> 3) * 16);
+        w.dh = ldw<unsigned short>(r); w.ls = ldw<signed char>(r + 8 + (u & 7)); }
+    static __device__ __forceinline__ void mkb(const QWeight &W, size_t g0, WBuf &B) { B.qs = mkbuf(W.qs + g0 * 16); B.sc = mkbuf(W.sc + (g0 >> 3) * 16); }
+    static __device__ __forceinline__ void loadb(const WBuf &B, int u, WU &w) {
+        w.q = bld16(B.qs, u * 16); w.dh = bld2(B.sc, (u >> 3) * 16); w.ls = (signed char)__builtin_amdgcn_raw_buffer_load_b8(B.sc, (u >> 3) * 16 + 8 + (u & 7), 0, WAUX); }
+    static __device__ __forceinline__ void loada(const ActQ &A, int t, int K, int u, AU &a) {
+        const int8_t *p = A.q8k + (size_t)t * K + (size_t)u * 32; a.lo = ld16(p); a.hi = ld16(p + 16); a.d = A.dk[(size_t)t * (K / 256) + (u >> 3)]; }
+    static constexpr int GROUP = 8, TERMS = 1;
+    static __device__ __forceinline__ void ints(const WU &w, const AU &a, int &i0, int &i1) { i0 = mul24((int)w.ls, iq4_dot32(w.q, a.lo, a.hi)); i1 = 0; }
+    static __device__ __forceinline__ void terms(const WU &w, const AU &a, int i0, int, float &f0, float &v0, float &f1, float &v1) { f0 = h2f_bits(w.dh) * a.d; v0 = (float)i0; f1 = v1 = 0.0f; }
+    static __device__ __forceinline__ void dot(const WU &w, const AU &a, float &acc) { acc = fmaf(h2f_bits(w.dh) * a.d, (float)mul24((int)w.ls, iq4_dot32(w.q, a.lo, a.hi)), acc); }
+};
 template <> struct Tr<GT_F16> {
     static constexpr int EPU = 8;
     struct WU { int4 q; };

@@ -142,7 +142,7 @@ def llm_tensor_types(cfg: LLMConfig) -> Dict[str, int]:
         if not cfg.output_type and Q.BLOCK[otype][0] == 256:
             otype = Q.GGML_F16
         if not cfg.tok_type and Q.BLOCK[ttype][0] == 256:
-            ttype = Q.GGML_Q4_0
+            ttype = Q.GGML_IQ4_NL if ttype == Q.GGML_IQ4_XS else Q.GGML_Q4_0   # (llama.cpp gives an IQ4_XS file IQ4_NL where a row is no multiple of 256)
     for t in (otype, ttype, base):
         e, _ = Q.BLOCK[t]
         assert cfg.n_embd % e == 0 and cfg.n_ff % e == 0, "row length must be a multiple of the block size"
@@ -266,7 +266,7 @@ class _Pool:
 def write_llm_file(path: str, cfg: LLMConfig, seed: int = 1234, std: float = 0.02,
                    unique_layers: Optional[int] = None, vocab: Optional[List[Tuple[bytes, float]]] = None,
                    fast: bool = False, resid_scale: float = 1.0, rotate_layers: bool = False, tok_std: Optional[float] = None,
-                   output_tie: float = 0.0, qk_scale: float = 1.0) -> None:
+                   output_tie: float = 0.0, qk_scale: float = 1.0, d_bits: Optional[int] = None) -> None:
     """Write a GGJT-v3 file with Gaussian weights.  `unique_layers` < n_layer re-uses the quantised bytes
     of layer (i % unique_layers) for layer i (bench-size files: same byte volume, generation in seconds).
     `resid_scale` multiplies the two matrices that write into the residual stream (attention.wo, feed_forward.w2) -- the
@@ -280,7 +280,8 @@ def write_llm_file(path: str, cfg: LLMConfig, seed: int = 1234, std: float = 0.0
     r Gaussian -- the logit of the token u with p[u] == current token stands out of the Gaussian rest by a margin beta controls: DECISIVE greedy decisions (top-2 margin
     far above the comparison tolerance) on a walk through the permutation instead of near-ties between 32000 i.i.d. logits.
     `qk_scale` multiplies attention.wq and attention.wk: the attention scores grow by its square, so the softmax is sharp and WHICH keys sit at which positions decides the
-    logits (tests of the context shift, whose whole point is the positions of cached keys)."""
+    logits (tests of the context shift, whose whole point is the positions of cached keys).
+    `d_bits` (IQ4_NL / IQ4_XS tensors): significant bits kept of every block scale d; 5 makes quants.iq4_to_q8_0's image of the file exact."""
     rng = np.random.default_rng(seed)
     types, shapes = llm_tensor_types(cfg), llm_tensor_shapes(cfg)
     vocab = vocab if vocab is not None else synth_vocab(cfg.n_vocab)
@@ -322,7 +323,7 @@ def write_llm_file(path: str, cfg: LLMConfig, seed: int = 1234, std: float = 0.0
             x = x * np.float32(resid_scale)
         if qk_scale != 1.0 and (name.endswith("attention.wq.weight") or name.endswith("attention.wk.weight")):
             x = x * np.float32(qk_scale)
-        raw = Q.quantize(t, x)
+        raw = Q.quantize(t, x, d_bits=d_bits)
         if key is not None:
             cache[key] = raw
         return raw
@@ -409,6 +410,26 @@ def ggjt_to_gguf(src: str, dst: str, version: int = 3, alignment: int = 32, extr
             out.seek(base + o)
             out.write(bytes(raw))
         out.truncate(base + off)
+
+
+def write_q8_0_twin(src: str, dst: str) -> None:
+    """The GGJT file `src` with every IQ4_NL / IQ4_XS tensor re-encoded as Q8_0 (quants.iq4_to_q8_0), everything else unchanged.  The CPU oracle does not know the IQ4
+    formats; where the image is exact (IQ4_NL always, IQ4_XS written with d_bits=5) it evaluates the SAME weights from the twin."""
+    f = read_llm_file(src)
+    hp = f.hparams
+    with open(dst, "wb") as out:
+        out.write(struct.pack("<II", GGJT_MAGIC, GGJT_VERSION))
+        out.write(struct.pack("<7I", *(hp[k] for k in ("n_vocab", "n_embd", "n_mult", "n_head", "n_layer", "n_rot", "ftype"))))
+        for piece, score in f.vocab:
+            out.write(struct.pack("<I", len(piece)) + piece + struct.pack("<f", score))
+        for name, t in f.tensors.items():
+            raw, gt = f.raw(name), t.gtype
+            if gt in (Q.GGML_IQ4_NL, Q.GGML_IQ4_XS):
+                raw, gt = Q.iq4_to_q8_0(raw, gt, int(np.prod(t.ne))), Q.GGML_Q8_0
+            nm = name.encode()
+            out.write(struct.pack("<III", len(t.ne), len(nm), gt) + struct.pack(f"<{len(t.ne)}I", *t.ne) + nm)
+            out.write(b"\0" * (_align(out.tell(), 32) - out.tell()))
+            out.write(bytes(raw))
 
 
 @dataclass

@@ -24,6 +24,7 @@ GGML_Q5_0, GGML_Q5_1, GGML_Q8_0, GGML_Q8_1 = 6, 7, 8, 9
 GGML_Q2_K, GGML_Q3_K, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_Q8_K = 10, 11, 12, 13, 14, 15
 GGML_I32 = 18  # not stored in LLM files; used internally for the vision file's I32/L64 tensors
 GGML_I64 = 19
+GGML_IQ4_NL, GGML_IQ4_XS = 20, 23  # the non-linear 4-bit formats (LLM files only): a nibble indexes KVALUES_IQ4NL
 
 # MiniGPT4DataType numbering (vision file / C API)
 MG4_F16, MG4_F32, MG4_I32, MG4_L64 = 0, 1, 2, 3
@@ -42,6 +43,7 @@ TYPE_NAMES = {
     GGML_F32: "f32", GGML_F16: "f16", GGML_Q4_0: "q4_0", GGML_Q4_1: "q4_1", GGML_Q5_0: "q5_0",
     GGML_Q5_1: "q5_1", GGML_Q8_0: "q8_0", GGML_Q4_K: "q4_k", GGML_Q5_K: "q5_k", GGML_Q6_K: "q6_k",
     GGML_Q2_K: "q2_k", GGML_Q3_K: "q3_k", GGML_I32: "i32", GGML_I64: "i64",
+    GGML_IQ4_NL: "iq4_nl", GGML_IQ4_XS: "iq4_xs",
 }
 NAME_TO_TYPE = {v: k for k, v in TYPE_NAMES.items()}
 
@@ -52,6 +54,7 @@ BLOCK = {
     GGML_Q8_0: (32, 34), GGML_Q8_1: (32, 40),
     GGML_Q2_K: (256, 84), GGML_Q3_K: (256, 110), GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176),
     GGML_Q6_K: (256, 210), GGML_Q8_K: (256, 292),
+    GGML_IQ4_NL: (32, 18), GGML_IQ4_XS: (256, 136),
 }
 
 
@@ -488,10 +491,112 @@ def q3_k_to_q6_k(buf: np.ndarray, n: int) -> np.ndarray:
     return out.reshape(-1)
 
 
+# --------------------------------------------------------------------------- IQ4_NL / IQ4_XS (16-entry int8 codebook)
+KVALUES_IQ4NL = np.array([-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113], np.int8)
+
+
+def _round_bits(d: np.ndarray, bits) -> np.ndarray:
+    """d rounded to `bits` significant bits (None: unchanged), then to fp16."""
+    if bits is not None:
+        m, e = np.frexp(np.asarray(d, np.float64))
+        d = np.ldexp(np.rint(m * (1 << bits)) / (1 << bits), e)
+    return _f16(d)
+
+
+def _iq4_nearest(x: np.ndarray, dl: np.ndarray) -> np.ndarray:
+    """codebook index of the entry nearest to x / dl, per 32-wide row ([nb, 32], [nb]); dl == 0 -> the entry nearest to 0"""
+    inv = np.where(dl != 0, 1.0 / np.where(dl != 0, dl, 1), 0.0)
+    t = x.astype(np.float64) * inv[:, None]
+    return np.abs(t[:, :, None] - KVALUES_IQ4NL.astype(np.float64)[None, None, :]).argmin(2).astype(np.uint8)
+
+
+def _iq4_block_scale(x: np.ndarray) -> np.ndarray:
+    """per 32 weights: the largest magnitude, signed, against the codebook's -127"""
+    idx = np.argmax(np.abs(x), axis=1)
+    return x[np.arange(x.shape[0]), idx].astype(np.float64) / -127.0
+
+
+def quantize_iq4_nl(x: np.ndarray, d_bits=None) -> np.ndarray:
+    """block = fp16 d | 16 bytes (low nibbles = elements 0..15, high = 16..31), as Q4_0.  A plain quantiser: nearest codebook entry, no search over d."""
+    x = np.asarray(x, np.float32).reshape(-1, 32)
+    dh = _round_bits(_iq4_block_scale(x), d_bits)
+    q = _iq4_nearest(x, dh.astype(np.float64))
+    out = np.zeros((x.shape[0], 18), np.uint8)
+    out[:, 0:2] = dh.view(np.uint8).reshape(-1, 2)
+    out[:, 2:] = q[:, :16] | (q[:, 16:] << 4)
+    return out.reshape(-1)
+
+
+def dequantize_iq4_nl(buf: np.ndarray, n: int) -> np.ndarray:
+    b = np.frombuffer(buf, np.uint8, n // 32 * 18).reshape(-1, 18)
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float64)
+    qs = b[:, 2:]
+    return (KVALUES_IQ4NL[np.concatenate([qs & 15, qs >> 4], axis=1)].astype(np.float64) * d).reshape(-1)
+
+
+def quantize_iq4_xs(x: np.ndarray, d_bits=None) -> np.ndarray:
+    """super-block = fp16 d | u16 scales_h | scales_l[4] | qs[128]; sub-block ib: dl = d * (ls - 32), ls = 6 bits split over scales_l (low 4) and scales_h (high 2)"""
+    x = np.asarray(x, np.float32).reshape(-1, 256)
+    nb = x.shape[0]
+    scale = _iq4_block_scale(x.reshape(-1, 32)).reshape(nb, 8)
+    dh = _round_bits(np.abs(scale).max(1) / 32.0, d_bits)
+    d = dh.astype(np.float64).reshape(nb)
+    inv = np.where(d != 0, 1.0 / np.where(d != 0, d, 1), 0.0)
+    ls = np.clip(np.rint(scale * inv[:, None]) + 32, 0, 63).astype(np.uint32)
+    q = _iq4_nearest(x.reshape(-1, 32), (d[:, None] * (ls.astype(np.float64) - 32)).reshape(-1)).reshape(nb, 8, 32)
+    out = np.zeros((nb, 136), np.uint8)
+    out[:, 0:2] = dh.view(np.uint8).reshape(-1, 2)
+    sh = np.zeros(nb, np.uint32)
+    for ib in range(8):
+        sh |= (ls[:, ib] >> 4) << (2 * ib)
+        out[:, 4 + ib // 2] |= ((ls[:, ib] & 15) << (4 * (ib & 1))).astype(np.uint8)
+    out[:, 2] = sh & 0xFF
+    out[:, 3] = sh >> 8
+    out[:, 8:] = (q[:, :, :16] | (q[:, :, 16:] << 4)).reshape(nb, 128)
+    return out.reshape(-1)
+
+
+def _iq4_xs_fields(buf: np.ndarray, n: int):
+    """-> d [nb], ls - 32 [nb, 8], codebook values [nb, 8, 32] in element order"""
+    b = np.frombuffer(buf, np.uint8, n // 256 * 136).reshape(-1, 136)
+    d = b[:, 0:2].copy().view(np.float16).astype(np.float64).reshape(-1)
+    sh = b[:, 2].astype(np.int64) | (b[:, 3].astype(np.int64) << 8)
+    ib = np.arange(8)
+    ls = ((b[:, 4 + ib // 2] >> (4 * (ib & 1))) & 15).astype(np.int64) | (((sh[:, None] >> (2 * ib)) & 3) << 4)
+    qs = b[:, 8:].reshape(-1, 8, 16)
+    return d, ls - 32, KVALUES_IQ4NL[np.concatenate([qs & 15, qs >> 4], axis=2)]
+
+
+def dequantize_iq4_xs(buf: np.ndarray, n: int) -> np.ndarray:
+    d, ls, kv = _iq4_xs_fields(buf, n)
+    return ((d[:, None] * ls)[:, :, None] * kv.astype(np.float64)).reshape(-1)
+
+
+def iq4_to_q8_0(buf, gtype: int, n: int) -> np.ndarray:
+    """The Q8_0 image of IQ4 blocks: per 32 weights d' = d (IQ4_NL) or d * (ls - 32) (IQ4_XS) as fp16 and q' = the codebook values.  It decodes to the same values
+    exactly where d' is an fp16 number -- always for IQ4_NL; for IQ4_XS when d has at most five significant bits (quantize_iq4_xs(d_bits=5): 5 + 6 bits <= fp16's 11)."""
+    buf = np.frombuffer(buf, np.uint8)
+    if gtype == GGML_IQ4_NL:
+        b = buf[: n // 32 * 18].reshape(-1, 18)
+        dh = b[:, 0:2].copy().view(np.float16).reshape(-1)
+        kv = KVALUES_IQ4NL[np.concatenate([b[:, 2:] & 15, b[:, 2:] >> 4], axis=1)]
+    else:
+        assert gtype == GGML_IQ4_XS, gtype
+        d, ls, kv = _iq4_xs_fields(buf, n)
+        dh = (d[:, None] * ls).astype(np.float16).reshape(-1)
+        kv = kv.reshape(-1, 32)
+    out = np.zeros((n // 32, 34), np.uint8)
+    out[:, 0:2] = dh.view(np.uint8).reshape(-1, 2)
+    out[:, 2:] = kv.view(np.uint8)
+    return out.reshape(-1)
+
+
 # --------------------------------------------------------------------------- dispatch
-def quantize(gtype: int, x: np.ndarray) -> np.ndarray:
-    """float array -> raw bytes (uint8) in ggml block layout, row-major over the flattened array."""
+def quantize(gtype: int, x: np.ndarray, d_bits=None) -> np.ndarray:
+    """float array -> raw bytes (uint8) in ggml block layout, row-major over the flattened array.  d_bits (IQ4_NL / IQ4_XS only): significant bits kept of every d."""
     x = np.ascontiguousarray(x)
+    if gtype in (GGML_IQ4_NL, GGML_IQ4_XS):
+        return (quantize_iq4_nl if gtype == GGML_IQ4_NL else quantize_iq4_xs)(x, d_bits)
     if gtype == GGML_F32:
         return x.astype(np.float32).reshape(-1).view(np.uint8)
     if gtype == GGML_F16:
@@ -514,5 +619,6 @@ def dequantize(gtype: int, buf, n: int) -> np.ndarray:
         GGML_Q4_0: dequantize_q4_0, GGML_Q4_1: dequantize_q4_1, GGML_Q5_0: dequantize_q5_0,
         GGML_Q5_1: dequantize_q5_1, GGML_Q8_0: dequantize_q8_0, GGML_Q4_K: dequantize_q4_k,
         GGML_Q5_K: dequantize_q5_k, GGML_Q6_K: dequantize_q6_k, GGML_Q3_K: dequantize_q3_k, GGML_Q2_K: dequantize_q2_k,
+        GGML_IQ4_NL: dequantize_iq4_nl, GGML_IQ4_XS: dequantize_iq4_xs,
     }[gtype]
     return fn(np.frombuffer(buf, np.uint8), n)
