@@ -299,7 +299,8 @@ MINIGPT4_API int minigpt4_amd_test_draft_tables(const int32_t *hist, int n_hist,
 /* Packed prompt rows of several conversations (minigpt4_amd_prefill_batch).  Caches kc / vc = [n_slots][n_ctx][n_head * hd] fp16 bit patterns, one layer per slot;
  * segs = [n_seg][3] (slot, rows, position of the first row), the segments' rows packed in that order in q = [N][n_head * hd] fp32.  Runs the segmented attention
  * (launch_attn_prefill_seg, one launch) into out_seg and one launch_attn_prefill per segment into out_ref.  form: 0 = the launchers' own choice, 1 = k_attn_prefill_h8,
- * 2 = k_attn_prefill_h QS 2, 3 = QS 1 (both sides), 4 = the exact-f32 kernel (both sides per segment).  *seg_launched = 1 when the one segmented launch ran.
+ * 2 = k_attn_prefill_h QS 2, 3 = QS 1 (both sides), 4 = the exact-f32 kernel, 5 = the streaming k_attn_prefill_s (4 and 5: both sides per segment).  With form 0 a
+ * segment past the LDS-row forms' range (1984 keys at head size 128) is served by the streaming kernel.  *seg_launched = 1 when the one segmented launch ran.
  * out_h_seg / out_h_ref (both or neither; [N][E] fp16 bits): the launchers may store fp16 rows there instead (the F16 wo's input); wrote_h[0] / [1] = whether the
  * segmented side / every per-segment launch did.  The form applies to this call only.  1 = bad arguments */
 MINIGPT4_API int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slots, const uint16_t *kc, const uint16_t *vc, int n_seg, const int32_t *segs, const float *q,

@@ -32,7 +32,7 @@ struct LaunchTuning {
     int mmq3_waves = 8;          // launch_mmq3_set: 8 = 128-row workgroups, one per CU; 4 = 64-row workgroups, two per CU (slower)
     int attn_prefill_w8 = 1;     // fp16 prompt attention: the 8-wave loader / MFMA form where its size rule selects it (MINIGPT4_ATTN_PREFILL_W8)
     int attn_prefill_f16 = 1;    // 1: prompt attention on the fp16 matrix cores, 0: the exact-f32 MFMA kernel
-    int attn_prefill_form = 0;   // force one fp16 prompt attention form (1 = h8, 2 = h QS 2, 3 = h QS 1; 0 = the size rule)
+    int attn_prefill_form = 0;   // force one fp16 prompt attention form (1 = h8, 2 = h QS 2, 3 = h QS 1, 5 = the streaming k_attn_prefill_s; 0 = the size rule)
     int gemm_arm = 0;            // force one tile shape for every small-M F16 GEMM (launch_gemm_f16_arm's arms); 0 = choose, -2 = the 64x64 launch always, -3 = round 2's
                                  // kernels everywhere (64x64 tiles, 128x128 large-M kernel)
     int gemm_sk_arm = 0;         // the same for the split-K GEMM (launch_gemm_f16_splitk_arm's arms); 0 = choose
@@ -43,7 +43,7 @@ struct LaunchTuning {
     LaunchTuning normalised() const {
         LaunchTuning t = *this;
         t.mv_waves_per_cu = mv_waves_per_cu > 0 ? mv_waves_per_cu : 0; t.mmqh = mmqh != 0; t.mmq_ks = mmq_ks > 0 ? mmq_ks : 0; t.mmq3_waves = mmq3_waves == 4 ? 4 : 8;
-        t.attn_prefill_w8 = attn_prefill_w8 != 0; t.attn_prefill_f16 = attn_prefill_f16 != 0; t.attn_prefill_form = attn_prefill_form >= 1 && attn_prefill_form <= 3 ? attn_prefill_form : 0;
+        t.attn_prefill_w8 = attn_prefill_w8 != 0; t.attn_prefill_f16 = attn_prefill_f16 != 0; t.attn_prefill_form = (attn_prefill_form >= 1 && attn_prefill_form <= 3) || attn_prefill_form == 5 ? attn_prefill_form : 0;
         t.gemm_arm = gemm_arm >= 0 || gemm_arm == -2 || gemm_arm == -3 ? gemm_arm : 0; t.gemm_sk_arm = gemm_sk_arm > 0 ? gemm_sk_arm : 0;
         t.f16_ks = f16_ks < 0 ? 0 : f16_ks > 8 ? 8 : f16_ks; t.splitk_xcd = splitk_xcd != 0; t.attn_vit_qt = attn_vit_qt > 0 ? attn_vit_qt : 0;
         return t;
@@ -312,8 +312,9 @@ bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R,
 // the same behind launch_sample_rows_ex (picks: its extended blocks)
 bool launch_draft_sample_finish(const float *logits, int ld, int n_vocab, int R, const int *tok, const SampleOutEx *picks, const int *row_slot, int *n_past, int *argmax, int *feed,
                                 float *slot_logits, int *res, hipStream_t s);
-// prefill (N > 1 rows of one conversation, after launch_rope_kv): workgroup = (head, 16 queries), keys streamed through LDS in tiles, exact-f32 MFMA; t_max >= *n_past + N
-// sizes the LDS score rows; false -> does not fit (the caller uses launch_attn_llm)
+// prefill (N > 1 rows of one conversation, after launch_rope_kv): the fp16-MFMA forms with score rows in LDS (t_max >= *n_past + N sizes them), past their range the
+// streaming form (attn_stream.hip, no limit); tune.attn_prefill_f16 == 0: the exact-f32 MFMA kernel only.  false -> no form serves (the exact-f32 kernel past its LDS
+// rows, an unsupported head size): the caller uses launch_attn_llm
 // out_h (optional): a kernel that can do so stores the fp16-rounded rows THERE instead of fp32 rows in `out` and sets *wrote_h (the F16 wo's input rows)
 bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, const LaunchTuning &tune, hipStream_t s, __half *out_h = nullptr, bool *wrote_h = nullptr);
 // MINIGPT4_PARITY=1: scores / softmax / P.V with every fp32 chain in the oracle's order (after launch_rope_kv); t_max >= *n_past + N
@@ -321,6 +322,9 @@ void launch_attn_ref(const float *q, const __half *kcache, const __half *vcache,
 void launch_attn_ref_fused(const float *q, const float *k, const float *v, __half *kcache, __half *vcache, int n_head, int hd, const int *n_past, int t_max, const float *cos_tab, const float *sin_tab,
                            const Tables &tb, float *out, hipStream_t s);   // one query row: RoPE + cache append inside
 bool attn_head_size_supported(int hd);
+// k_attn_prefill_s<hd> (attn_stream.hip), launched by launch_attn_prefill: grid (n_head, ceil(N / 64)), 256 threads, no dynamic LDS; null: unsupported head size
+using AttnPrefillSKernel = void (*)(const float *q, const __half *kc, const __half *vc, int E, int N, const int *n_past, const Tables tb, float *out);
+AttnPrefillSKernel attn_prefill_s_kernel(int hd);
 void attn_ref_prepare();        // the oracle-order attention kernels' > 64 KiB LDS opt-in on the current device, checked (throws HipError); outside any stream capture
 int attn_ref_max_ctx(int hd);   // the same bound for the oracle-order kernel of parity mode (smaller: it also stages value rows in LDS)
 int attn_max_ctx(int hd);   // largest n_ctx whose score / probability rows fit the attention kernel's LDS

@@ -1826,7 +1826,8 @@ void launch_kv_permute(__half *kc, __half *vc, size_t seq_stride, int n_slots, c
 //   softmax: max, exp through the fp16 table, exact double sum, probabilities rounded to fp16
 //   PV     : thread = (key partition, 8-dim chunk): 16-byte V loads, NPRE in flight; partitions reduced through LDS
 // The forms:
-//   plain   (!FUSED; prompt rows beyond the prompt kernels' LDS): row t at position *n_past + t, launch_rope_kv has run; every key comes from the cache.
+//   plain   (!FUSED; prompt rows no prompt kernel serves: beyond the exact-f32 kernel's LDS rows with the fp16 kernels switched off, or an unsupported case -- with
+//           them on, the streaming k_attn_prefill_s takes every length): row t at position *n_past + t, launch_rope_kv has run; every key comes from the cache.
 //   FUSED   (decode, one row): RoPE of q / k and the KV append happen in the prologue; the new key / value are also kept in LDS and take the last place of the chains.
 //   BATCHED (decode of several conversations in one pass; implies FUSED): row t belongs to conversation row_slot[t], whose position is n_past[row_slot[t]] and whose
 //           caches start seq_stride * row_slot[t] elements behind kc / vc.
@@ -2808,10 +2809,10 @@ static bool launch_attn_prefill_f16(const float *q, const __half *kc, const __ha
     }
     return false;
 }
-// Fallback: k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken (a) with LaunchTuning::attn_prefill_f16 == 0 (test library: the A/B switch of
-// the fp16 kernels), (b) when the fp16 kernels refuse because their LDS image exceeds the 160 KiB of a CU.  Both forms hold 16 score rows of the whole context: at head
-// size 128 both end at 1984 keys; beyond, this returns false and Engine::forward runs the rows through the decode attention kernel (k_attn_llm, one query row per
-// workgroup), which has no such limit.
+// k_attn_prefill<HD, 1>, the round-2 kernel with fp32 score / value products.  Taken with LaunchTuning::attn_prefill_f16 == 0 only (test library: the A/B switch of
+// the fp16 kernels; form 4 of the test hook) -- with the fp16 kernels on, a chunk their LDS-row forms refuse goes to the streaming form, not here.  It holds 16 score
+// rows of the whole context like the 16-query fp16 form: at head size 128 both end at 1984 keys; beyond, this returns false and Engine::forward runs the rows through
+// the decode attention kernel (k_attn_llm, one query row per workgroup), which has no such limit.
 // (QS = 2 -- 32 queries per staged key / value tile from 256 prompt rows on -- is bit-identical and was measured 2 % SLOWER at 512 rows: 13B Q5_K_M 31.7 vs 31.0 ms,
 // 13B f16 27.9 vs 27.2 ms, profiles/r02r_prefill_ksplit_fill_sweep.log; half the workgroups, each twice as long: not instantiated.)
 template <int HD>
@@ -2844,15 +2845,25 @@ bool launch_attn_prefill_seg(const float *q, const __half *kcache, const __half 
     attn_for_head_size(hd, [&](auto tag) { done = launch_attn_prefill_f16<decltype(tag)::value>(q, kcache, vcache, 0, n_head, nullptr, sg.t_max, &sg, tb, out, tune, s, out_h, wrote_h); });
     return done;
 }
+// The streaming form k_attn_prefill_s<HD> (attn_stream.hip): no score rows in LDS, so no context limit.  Tried when every LDS-row fp16 form has refused (or with
+// LaunchTuning::attn_prefill_form == 5, where attn_prefill_forms lists none); writes f32 rows only (*wrote_h stays false).
+template <int HD>
+static bool launch_attn_prefill_s(const float *q, const __half *kc, const __half *vc, int N, int n_head, const int *n_past, const Tables &tb, float *out, hipStream_t s) {
+    note_kernel("k_attn_prefill_s<%d>", HD);
+    hipLaunchKernelGGL(attn_prefill_s_kernel(HD), dim3((unsigned)n_head, (unsigned)((N + 63) / 64)), dim3(256), 0, s, q, kc, vc, n_head * HD, N, n_past, tb, out);
+    return true;
+}
 // N > 1 query rows at positions *n_past .. *n_past + N - 1 (launch_rope_kv has run); t_max >= *n_past + N (the host's view, sizes the LDS score rows).
-// false -> the score rows do not fit LDS (very long contexts): the caller runs launch_attn_llm instead.
+// Fast mode: the first LDS-row fp16 form that fits, else the streaming form -- always served.  false -> only with attn_prefill_f16 == 0 (parity mode, the A/B switch)
+// when the exact-f32 kernel's score rows do not fit LDS: the caller runs launch_attn_llm instead.
 bool launch_attn_prefill(const float *q, const __half *kcache, const __half *vcache, int N, int n_head, int hd, const int *n_past, int t_max, const Tables &tb, float *out, const LaunchTuning &tune,
                          hipStream_t s, __half *out_h, bool *wrote_h) {
     if (wrote_h) *wrote_h = false;
     bool done = false;
     attn_for_head_size(hd, [&](auto tag) {
         constexpr int HD = decltype(tag)::value;
-        done = (tune.attn_prefill_f16 && launch_attn_prefill_f16<HD>(q, kcache, vcache, N, n_head, n_past, t_max, nullptr, tb, out, tune, s, out_h, wrote_h)) ||
+        done = (tune.attn_prefill_f16 && (launch_attn_prefill_f16<HD>(q, kcache, vcache, N, n_head, n_past, t_max, nullptr, tb, out, tune, s, out_h, wrote_h) ||
+                                          launch_attn_prefill_s<HD>(q, kcache, vcache, N, n_head, n_past, tb, out, s))) ||
                launch_attn_prefill_f32<HD>(q, kcache, vcache, N, n_head, n_past, t_max, tb, out, s);
     });
     return done;

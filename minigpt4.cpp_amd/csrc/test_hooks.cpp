@@ -1518,7 +1518,7 @@ static bool seg_table(int n_ctx, int n_slots, int n_seg, const int32_t *segs, st
 int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slots, const uint16_t *kc, const uint16_t *vc, int n_seg, const int32_t *segs, const float *q,
                                        int form, float *out_seg, float *out_ref, int *seg_launched, uint16_t *out_h_seg, uint16_t *out_h_ref, int *wrote_h) {
     std::vector<int> st; int N = 0, t_max = 0;
-    if (!kc || !vc || !segs || !q || !out_seg || !out_ref || n_head < 1 || !attn_head_size_supported(hd) || n_slots < 1 || n_seg < 1 || form < 0 || form > 4 ||
+    if (!kc || !vc || !segs || !q || !out_seg || !out_ref || n_head < 1 || !attn_head_size_supported(hd) || n_slots < 1 || n_seg < 1 || form < 0 || form > 5 ||
         !seg_table(n_ctx, n_slots, n_seg, segs, st, N, t_max) || (!out_h_seg) != (!out_h_ref) || (out_h_seg && !wrote_h)) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -1540,7 +1540,7 @@ int minigpt4_amd_test_attn_prefill_seg(int n_head, int hd, int n_ctx, int n_slot
         { int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if (__half2float(__float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)c))))) == 0.0f) break; nneg++; } tb.exp_neg_n = (nneg + 2047) / 2048 * 2048; }
         sg.segs = ds.as<int>(); sg.tiles[0] = d16.as<int>(); sg.tiles[1] = d32.as<int>();
         LaunchTuning tune = hook_tuning();
-        tune.attn_prefill_f16 = form != 4; tune.attn_prefill_form = form;   // (normalised: a form outside 1 .. 3 is the size rule)
+        tune.attn_prefill_f16 = form != 4; tune.attn_prefill_form = form;   // (normalised: 0 and 4 are the size rule; 5: the segmented launch declines, both sides run k_attn_prefill_s per segment)
         tune = tune.normalised();
         const float *dqp = dq.as<float>();
         // one launch_attn_prefill per segment; *all_h: every segment stored fp16 rows
@@ -1987,6 +1987,7 @@ int minigpt4_amd_bench_attn_prefill(int n_head, int hd, int N, int n_past, int i
         { int nneg = 0; for (int c = 0x8000; c < 0xFC00; c++) { if (__half2float(__float2half_rn(expf(__half2float(__ushort_as_half((unsigned short)c))))) == 0.0f) break; nneg++; } tb.exp_neg_n = (nneg + 2047) / 2048 * 2048; }
         LaunchTuning tune = hook_tuning();
         if (const char *w8 = getenv("MINIGPT4_ATTN_PREFILL_W8")) tune.attn_prefill_w8 = atoi(w8);      // micro-benchmark only (no engine in this process)
+        if (const char *f = getenv("MINIGPT4_ATTN_PREFILL_FORM")) tune.attn_prefill_form = atoi(f);    // likewise: one form forced (tools/long_prompt_bench.py)
         tune = tune.normalised();
         auto run = [&]() { return launch_attn_prefill(dq.as<float>(), dk.as<__half>(), dv.as<__half>(), N, n_head, hd, dnp.as<int>(), T, tb, dout.as<float>(), tune, nullptr); };
         for (int i = 0; i < 3; i++) if (!run()) return 4;

@@ -1704,7 +1704,7 @@ class MiniGPT4SharedLibrary:
 
     def amd_test_attn_prefill_seg(self, kc: np.ndarray, vc: np.ndarray, n_head: int, segs, q: np.ndarray, form: int = 0, fp16_rows: bool = False):
         """Segmented prompt attention (one launch) and one launch_attn_prefill per segment on fp16 caches [n_slots][n_ctx][E]; segs = [(slot, rows, pos0)], q = packed
-        [N][E] fp32.  form: 0 auto, 1 h8, 2 h QS 2, 3 h QS 1, 4 exact f32.  Returns (out_seg, out_ref, seg_launched); fp16_rows: the launchers may store fp16 rows instead
+        [N][E] fp32.  form: 0 auto, 1 h8, 2 h QS 2, 3 h QS 1, 4 exact f32, 5 streaming (k_attn_prefill_s).  Returns (out_seg, out_ref, seg_launched); fp16_rows: the launchers may store fp16 rows instead
         (the F16 wo's input), returns (out_seg, out_ref, seg_launched, h_seg, h_ref, (seg wrote fp16, every per-segment launch wrote fp16))."""
         kc, vc = np.ascontiguousarray(kc, np.float16), np.ascontiguousarray(vc, np.float16)
         assert kc.ndim == 3 and kc.shape == vc.shape
