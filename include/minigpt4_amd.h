@@ -627,6 +627,34 @@ MINIGPT4_API int minigpt4_amd_state_load_file(struct MiniGPT4Context *ctx, int s
 MINIGPT4_API int minigpt4_amd_state_peek(const void *buf, size_t n, int64_t out[12]);
 MINIGPT4_API int minigpt4_amd_state_info(struct MiniGPT4Context *ctx, int64_t out[8]);
 
+/* ---- run-time LoRA adapters: one per conversation in the same weight pass -----------------------------------------------------------------------
+ * y = W x + s * B (A x) with s = alpha / rank * scale, added by two small HIP kernels behind the base launches of attn_q / attn_k / attn_v, attn_output, ffn_gate /
+ * ffn_up and ffn_down, whatever the base weights' type: the quantised file stays as it is and conversations under different adapters, and under none, share every
+ * weight pass (batched steps, prefill batches, verify passes, guidance, beams).
+ * File: GGUF v2 / v3 as convert_lora_to_gguf.py writes it -- general.type = "adapter", adapter.type = "lora", adapter.lora.alpha (f32), tensors
+ * blk.N.<target>.weight.lora_a (ggml ne = (n_in, r)) and .lora_b (ne = (r, n_out)), F16 or F32; any subset of the seven targets and of the layers; one rank 1 .. 64 per
+ * file.  The device copy is fp16 (F32 tensors are ROUNDED at load), the rank zero-padded to a multiple of 16.
+ * minigpt4_amd_adapter_peek (host only, no context): out = {rank, alpha * 1000, lora tensors, target mask (bit 0 attn_q, 1 attn_k, 2 attn_v, 3 attn_output, 4 ffn_gate,
+ *   5 ffn_down, 6 ffn_up), layers, device bytes, refusal code, 1 if some tensor is F32}.  Refusal codes (last_error "adapter file: ..."): 0 none, 1 general.type /
+ *   adapter.type, 2 a lora_a without its lora_b (or the reverse), 3 shapes (not 2-D, widths that disagree among the file's tensors; at load: with the model),
+ *   4 rank above 64 or mixed ranks, 5 a quantised or BF16 tensor, 6 not a readable GGUF adapter.  Returns 0 whenever out was filled.
+ * minigpt4_amd_adapter_load: at most 8 adapters per context, handles 1 .. 8.  Loading and freeing drop the context's captured graphs.
+ * minigpt4_amd_adapter_free: refused while a conversation uses the adapter.
+ * minigpt4_amd_set_adapter: handle 0 detaches.  Refused unless the conversation is empty (n_past == 0, nothing queued): cached K / V rows are only valid under the
+ *   adapter that wrote them.  The assignment is read on the device, so captured graphs survive it; minigpt4_reset_chat keeps it, minigpt4_amd_set_conversations clears it.
+ * minigpt4_amd_adapter_info: out = {the slot's handle, its scale * 1e6, rank, target mask; of the context so far: adapters loaded, k_lora_down launches, k_lora_up
+ *   launches, device bytes of the loaded adapters}.  The two launch figures count what the host ENQUEUED: a decode step replayed from its captured graph adds
+ *   nothing, so they say that the kernels are in a pass, not how often they ran.
+ * Rules: minigpt4_amd_fork_conversation copies the source's assignment to the destinations.  A conversation with an adapter neither reads nor feeds the prefix cache.
+ * A snapshot does not record the adapter; minigpt4_amd_state_load keeps the slot's assignment.  Parity mode has no ggml order to reproduce: set_adapter is refused while
+ * parity is on and minigpt4_amd_set_parity(1) is refused while any conversation has an adapter.  With an adapter loaded the decode step takes the unpaired w1 / w3
+ * launches.  Each call: 0, or 1 with minigpt4_amd_last_error "<name>: ...". */
+MINIGPT4_API int minigpt4_amd_adapter_peek(const char *path, int64_t out[8]);
+MINIGPT4_API int minigpt4_amd_adapter_load(struct MiniGPT4Context *ctx, const char *path, int32_t *handle);
+MINIGPT4_API int minigpt4_amd_adapter_free(struct MiniGPT4Context *ctx, int32_t handle);
+MINIGPT4_API int minigpt4_amd_set_adapter(struct MiniGPT4Context *ctx, int slot, int32_t handle, float scale);
+MINIGPT4_API int minigpt4_amd_adapter_info(struct MiniGPT4Context *ctx, int slot, int64_t out[8]);
+
 /* ---- weight arenas (load-time broadcast rank0 -> others over RCCL) ---------------------------- */
 /* which: 0 = LLM arena, 1 = vision arena.  Returns the device pointer and size in bytes. */
 MINIGPT4_API int minigpt4_amd_weight_arena(struct MiniGPT4Context *ctx, int which, void **device_ptr, size_t *bytes);

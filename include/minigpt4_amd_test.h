@@ -457,6 +457,11 @@ MINIGPT4_API int minigpt4_amd_timeline(unsigned long long *out, int max_workgrou
 MINIGPT4_API int minigpt4_amd_timeline_rows(unsigned long long *out, int max_workgroups);
 /* load-time re-encoding of Q3_K super-blocks (110 B) as value-identical Q6_K super-blocks (210 B); host only.  0 / 1 */
 MINIGPT4_API int minigpt4_amd_convert_q3k_q6k(const void *src, void *dst, int64_t n_blocks);
+/* The LoRA kernels alone (k_lora_down + k_lora_up of lora.hip, one target): rows <= 64, row i uses adapter row_adapter[i] (-1: none) of n_adapters <= 2 with A [rank][n_in],
+ * B [n_out][rank] given as fp16 bits back to back and factors s[a].  mode 0: x as it is; 1: RMS norm of x with weight second [n_in]; 2: silu(x) * second [rows][n_in].
+ * form 0 = by rows, 1 = vector, 2 = MFMA.  out [rows][n_out] = s * B (A f(x)) alone.  0; 1 bad arguments; 2 no device; 3 a HIP error. */
+MINIGPT4_API int minigpt4_amd_test_lora(int rows, int n_in, int n_out, int mode, const float *x, const float *second, int n_adapters, int rank, const unsigned short *a16,
+                                        const unsigned short *b16, const float *s, const int32_t *row_adapter, int form, float *out);
 /* Host sampler with an explicit seed (fresh std::mt19937 per call). */
 MINIGPT4_API int minigpt4_amd_sample_logits(const float *logits, int n_vocab, int seed, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p,
                                             int mirostat, float mirostat_tau, float mirostat_eta);

@@ -454,6 +454,33 @@ int minigpt4_amd_guidance_info(struct MiniGPT4Context *ctx, int32_t out[4]) {
     out[0] = g.launches; out[1] = g.handed; out[2] = g.pen_picked; out[3] = g.sampled;
     return 0;
 }
+// ---- run-time LoRA adapters: one per conversation in the same weight pass ---------------------------------------------------------------------------
+int minigpt4_amd_adapter_peek(const char *path, int64_t out[8]) {
+    if (!path || !out) { set_last_error("adapter_peek: no path / output array"); return 1; }
+    return guarded(1, [&]() -> int {
+        AdapterFile f;
+        const int rc = f.load(path);
+        out[0] = f.rank; out[1] = llround((double)f.alpha * 1000.0); out[2] = f.n_tensors; out[3] = f.target_mask; out[4] = f.n_layers;
+        out[5] = rc == ADAPTER_OK ? (int64_t)f.device_bytes() : 0; out[6] = rc; out[7] = f.any_f32;
+        return 0;
+    });
+}
+int minigpt4_amd_adapter_load(struct MiniGPT4Context *ctx, const char *path, int32_t *handle) {
+    if (!ctx || !path || !handle) { set_last_error(!ctx ? "adapter_load: no context" : !path ? "adapter_load: no path" : "adapter_load: no handle pointer"); return 1; }   // before a slot is taken
+    return guarded(1, [&] { int h = 0; const int rc = E_(ctx)->adapter_load(path, &h); if (!rc) *handle = h; return rc; });
+}
+int minigpt4_amd_adapter_free(struct MiniGPT4Context *ctx, int32_t handle) {
+    if (!ctx) { set_last_error("adapter_free: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->adapter_free(handle); });
+}
+int minigpt4_amd_set_adapter(struct MiniGPT4Context *ctx, int slot, int32_t handle, float scale) {
+    if (!ctx) { set_last_error("set_adapter: no context"); return 1; }
+    return guarded(1, [&] { return E_(ctx)->set_adapter(slot, handle, scale); });
+}
+int minigpt4_amd_adapter_info(struct MiniGPT4Context *ctx, int slot, int64_t out[8]) {
+    if (!ctx) { set_last_error("adapter_info: no context"); return 1; }
+    return guarded(1, [&] { long long o[8]; const int rc = E_(ctx)->adapter_info(slot, out ? o : nullptr); if (!rc) for (int i = 0; i < 8; i++) out[i] = o[i]; return rc; });
+}
 // ---- constrained decoding: a regular expression per conversation ----------------------------------------------------------------------------------
 int minigpt4_amd_constraint_compile(struct MiniGPT4Context *ctx, const char *pattern, int n_bytes, int32_t *handle) {
     if (!ctx) { set_last_error("constraint_compile: no context"); return 1; }

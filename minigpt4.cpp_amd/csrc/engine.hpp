@@ -2,6 +2,7 @@
 // and the decode hipGraph.  Mirrors the call surface of the reference's `class MiniGPT4` (minigpt4.cpp:1740-2522):
 // init / encode_image / add_tokens / add_strings / add_embedding / sample_token / id_to_token / reset.
 #pragma once
+#include <array>
 #include <memory>
 #include <string>
 #include <vector>
@@ -344,6 +345,17 @@ public:
     struct StateInfo { long long saves = 0, loads = 0, rows_saved = 0, rows_loaded = 0, pack_launches = 0, unpack_launches = 0, checksum_failures = 0, staging_bytes = 0; };
     StateInfo state_info() const { return state_info_; }
 
+    // ---- run-time LoRA adapters (lora.hip: the kernels; minigpt4_amd.h: the rules).  An adapter belongs to the CONTEXT (handles 1 .. ADAPTER_SLOTS): its fp16 A / B
+    // images in one device allocation, per layer one A image for q|k|v and one for w1|w3 (the sites share their input).  A conversation holds a handle (0: none) and a
+    // factor of its own; the kernels read both from device words indexed by the row's slot, so captured graphs survive set_adapter.  With at least one adapter loaded,
+    // forward / forward_batch enqueue k_lora_down + k_lora_up behind each of the four site groups that some adapter touches (the base launch's deferred combine is
+    // flushed first), the paired w1|w3 forms are off (h1_ / h3_ must exist in fp32) and the F16 prompt pass keeps fp32 attention rows.  Loading and freeing an adapter
+    // drop the captured graphs.  A context without adapters launches exactly what it launched before the feature.  Each call: 0, or 1 + last_error "<name>: ...".
+    static constexpr int ADAPTER_SLOTS = LORA_MAX;
+    int adapter_load(const std::string &path, int *handle);
+    int adapter_free(int handle);                                          // refused while a conversation uses it
+    int set_adapter(int slot, int handle, float scale);                    // 0 detaches; refused unless the conversation is empty, and in parity mode
+    int adapter_info(int slot, long long out[8]) const;                    // {handle, scale * 1e6, rank, target mask, adapters loaded, down launches, up launches, device bytes}
     // ---- measurement hooks (bench / tests): both feed tokens back on the device, so the rows they add enter the token history as -1
     // K greedy decode steps fed back on the device (no host round trip); returns ms per step via hipEvents.
     int decode_loop(int steps, int *tokens_out, float *ms_total);
@@ -748,6 +760,21 @@ private:
     struct SpecBatchInfo { long long passes = 0, rows = 0, groups = 0, sent = 0, accepted = 0, plain = 0, cut = 0; } mspec_info_;
     struct SpecInfo { long long passes = 0, rows = 0, sent = 0, accepted = 0, launches = 0, stuck = 0, cut = 0; } spec_info_;
     void sdr_alloc();
+    // LoRA adapters.  Per adapter and layer the four site groups' pieces; lora_groups_ = the kernels' by-value tables over the loaded adapters, rebuilt by every load / free
+    struct LoraPart { const __half *A = nullptr; const __half *B[LORA_TARGETS] = {nullptr, nullptr, nullptr}; int rcat = 0; int aoff[LORA_TARGETS] = {-1, -1, -1}; };
+    struct Adapter { bool used = false; int rank = 0, rp = 0; float alpha = 0.0f; unsigned tmask = 0; size_t bytes = 0; DevPtr<__half> dev; std::vector<std::array<LoraPart, 4>> part; };
+    Adapter lora_[LORA_MAX];
+    int lora_n_ = 0, lora_hi_ = 0;                                         // adapters loaded; highest used index + 1 (the MFMA forms' grid.y)
+    int lora_handle_[MAX_CONVERSATIONS] = {0}; float lora_scale_[MAX_CONVERSATIONS] = {0};
+    DevPtr<int> d_lora_; DevPtr<float> lora_ws_; size_t lora_t_floats_ = 0;   // [adapter index per slot | factor per slot]; t slabs, the sums of squares behind them
+    std::vector<std::array<LoraGroup, 4>> lora_groups_; std::vector<std::array<bool, 4>> lora_has_;
+    long long lora_down_ = 0, lora_up_ = 0;
+    enum LoraSite { LS_QKV = 0, LS_WO, LS_W1W3, LS_W2 };
+    void lora_site(int site, size_t il, int N, const LoraRows &R, hipStream_t s);
+    LoraRows lora_rows(const int *row_slot, int stride, int slot0) const { return LoraRows{d_lora_, reinterpret_cast<const float *>(d_lora_ + MAX_CONVERSATIONS), row_slot, stride, slot0}; }
+    void lora_rebuild();
+    void lora_assign(int slot, int handle, float scale);                   // host + device words
+    void drop_graphs();                                                    // every captured pass of the context
 };
 
 int device_count_noexcept();

@@ -315,6 +315,115 @@ int LLMFile::load_gguf(bool vocab_only) {
     return E_None;
 }
 
+// ---------------------------------------------------------------------------------------------------- LoRA adapter (GGUF)
+// The container is the one load_gguf reads (same header, key / value and tensor-info encoding); an adapter has no vocabulary and no hyper-parameters, so only
+// general.type, adapter.type, adapter.lora.alpha and general.alignment are taken and every other key is skipped by its type.
+int AdapterFile::load(const std::string &path) {
+    auto fail = [&](int code, const std::string &m) { set_last_error("adapter file: " + m); return code; };
+    if (!mf.open(path)) return fail(ADAPTER_MALFORMED, "cannot open " + path);
+    Reader r(mf.data, mf.size);
+    if (r.u4() != 0x46554747u) return fail(ADAPTER_MALFORMED, "not a GGUF file");
+    const uint32_t ver = r.u4();
+    if (ver != 2 && ver != 3) return fail(ADAPTER_MALFORMED, "only GGUF versions 2 and 3 are supported");
+    auto u8 = [&]() -> uint64_t { uint64_t v = 0; if (r.need(8)) { memcpy(&v, r.p + r.pos, 8); r.pos += 8; } return v; };
+    auto gstr = [&]() -> std::string { const uint64_t n = u8(); if (!r.ok || n > (1u << 24)) { r.ok = false; return std::string(); } return r.str((size_t)n); };
+    const uint64_t n_t = u8(), n_kv = u8();
+    if (!r.ok || n_t > (r.size - r.pos) / 24 || n_kv > (r.size - r.pos) / 12) return fail(ADAPTER_MALFORMED, "absurd counts");
+    static const size_t scalar_size[13] = {1, 1, 2, 2, 4, 4, 4, 1, 0, 0, 8, 8, 8};
+    uint64_t alignment = 32;
+    std::string gtype, atype;
+    bool have_alpha = false;
+    std::function<bool(uint32_t, int)> skip = [&](uint32_t t, int depth) -> bool {   // one value of type t
+        if (t == 8) { gstr(); return r.ok; }
+        if (t == 9) {
+            const uint32_t et = r.u4(); const uint64_t cnt = u8();
+            if (!r.ok || depth >= 4 || cnt > (r.size - r.pos)) return false;
+            if (et != 8 && et != 9) { if (et > 12 || !scalar_size[et] || !r.need((size_t)cnt * scalar_size[et])) return false; r.pos += (size_t)cnt * scalar_size[et]; return true; }
+            for (uint64_t k = 0; k < cnt; k++) if (!skip(et, depth + 1)) return false;
+            return true;
+        }
+        if (t > 12 || !scalar_size[t] || !r.need(scalar_size[t])) return false;
+        r.pos += scalar_size[t];
+        return true;
+    };
+    for (uint64_t i = 0; i < n_kv && r.ok; i++) {
+        const std::string key = gstr();
+        const uint32_t vt = r.u4();
+        if (vt == 8 && (key == "general.type" || key == "adapter.type")) { (key == "general.type" ? gtype : atype) = gstr(); continue; }
+        if (vt == 6 && key == "adapter.lora.alpha") { alpha = r.f4(); have_alpha = true; continue; }
+        if (vt == 4 && key == "general.alignment") { alignment = r.u4(); continue; }
+        if (!skip(vt, 0)) return fail(ADAPTER_MALFORMED, "bad metadata value for " + key);
+    }
+    if (!r.ok) return fail(ADAPTER_MALFORMED, "truncated metadata");
+    if (gtype != "adapter") return fail(ADAPTER_BAD_TYPE, "general.type must be \"adapter\" (is \"" + gtype + "\")");
+    if (atype != "lora") return fail(ADAPTER_BAD_TYPE, "adapter.type must be \"lora\"");
+    if (!have_alpha || !std::isfinite(alpha)) return fail(ADAPTER_MALFORMED, "missing adapter.lora.alpha (f32)");
+    if (alignment == 0 || alignment > 4096 || (alignment & (alignment - 1))) return fail(ADAPTER_MALFORMED, "bad general.alignment");
+    struct Info { std::string name; TensorMeta t; uint64_t rel; };
+    std::vector<Info> infos((size_t)n_t);
+    for (auto &in : infos) {
+        in.name = gstr();
+        const uint32_t nd = r.u4();
+        if (!r.ok || nd < 1 || nd > 2) return fail(ADAPTER_MALFORMED, "tensor " + in.name + ": only 1-D / 2-D tensors are expected");
+        for (uint32_t d = 0; d < nd; d++) { const uint64_t v = u8(); if (v < 1 || v > (1u << 30)) return fail(ADAPTER_MALFORMED, "absurd tensor shape"); in.t.ne.push_back((int64_t)v); }
+        in.t.type = (int)r.u4();
+        in.rel = u8();
+        if (!r.ok) return fail(ADAPTER_MALFORMED, "truncated tensor table");
+    }
+    const size_t data0 = (r.pos + (size_t)alignment - 1) & ~((size_t)alignment - 1);
+    static const char *tname[AT_COUNT] = {"attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_down", "ffn_up"};
+    for (auto &in : infos) {
+        // blk.N.<target>.weight.lora_a | lora_b; anything else is not part of an adapter for this graph
+        int layer = -1, tgt = -1; bool is_b = false;
+        if (in.name.compare(0, 4, "blk.") == 0) {
+            const size_t dot = in.name.find('.', 4);
+            if (dot != std::string::npos && dot > 4 && dot - 4 <= 6 && in.name.find_first_not_of("0123456789", 4) == dot) {
+                const std::string rest = in.name.substr(dot + 1);
+                for (int k = 0; k < AT_COUNT; k++) {
+                    const std::string base = std::string(tname[k]) + ".weight.lora_";
+                    if (rest == base + "a" || rest == base + "b") { tgt = k; is_b = rest.back() == 'b'; layer = atoi(in.name.c_str() + 4); }
+                }
+            }
+        }
+        if (tgt < 0) continue;
+        if (in.t.type != GT_F16 && in.t.type != GT_F32) return fail(ADAPTER_BAD_TENSOR_TYPE, "tensor " + in.name + " is neither F16 nor F32 (quantised and BF16 adapters are not read)");
+        if (in.t.ne.size() != 2) return fail(ADAPTER_BAD_SHAPE, "tensor " + in.name + " is not 2-D");
+        TensorMeta t = in.t;
+        t.name = in.name; t.nbytes = gt_nbytes(t.type, (size_t)t.nelements());
+        if (in.rel % alignment || in.rel > mf.size || data0 > mf.size - in.rel || t.nbytes > mf.size - data0 - in.rel) return fail(ADAPTER_MALFORMED, "tensor " + in.name + " runs past EOF");
+        t.offset = data0 + (size_t)in.rel;
+        any_f32 = any_f32 || t.type == GT_F32;
+        const TensorMeta *kept = &(tensors[in.name] = t);
+        (is_b ? layers[layer][(size_t)tgt].b : layers[layer][(size_t)tgt].a) = kept;
+        n_tensors++;
+    }
+    if (layers.empty()) return fail(ADAPTER_MALFORMED, "no blk.N.<target>.weight.lora_a / lora_b tensors");
+    int64_t n_embd = 0, n_ff = 0;   // the widths the file's own tensors imply
+    auto agree = [](int64_t &w, int64_t v) { if (!w) w = v; return w == v; };
+    for (auto &lp : layers) for (int k = 0; k < AT_COUNT; k++) {
+        const Pair &p = lp.second[(size_t)k];
+        if (!p.a && !p.b) continue;
+        const std::string nm = "blk." + std::to_string(lp.first) + "." + tname[k];
+        if (!p.a || !p.b) return fail(ADAPTER_UNPAIRED, nm + ": lora_a and lora_b must come together");
+        const int64_t ra = p.a->ne[1], rb = p.b->ne[0];
+        if (ra != rb) return fail(ra > LORA_FILE_RANK_MAX || rb > LORA_FILE_RANK_MAX ? ADAPTER_BAD_RANK : ADAPTER_BAD_SHAPE, nm + ": lora_a has " + std::to_string(ra) + " rows, lora_b " + std::to_string(rb) + " columns");
+        if (ra > LORA_FILE_RANK_MAX) return fail(ADAPTER_BAD_RANK, nm + ": rank " + std::to_string(ra) + " exceeds 64");
+        if (rank && rank != (int)ra) return fail(ADAPTER_BAD_RANK, nm + ": rank " + std::to_string(ra) + " differs from the file's " + std::to_string(rank) + " (one rank per file)");
+        rank = (int)ra;
+        const bool in_ff = k == AT_DOWN, out_ff = k == AT_GATE || k == AT_UP;
+        if (!agree(in_ff ? n_ff : n_embd, p.a->ne[0]) || !agree(out_ff ? n_ff : n_embd, p.b->ne[1])) return fail(ADAPTER_BAD_SHAPE, nm + ": widths disagree with the file's other tensors");
+        target_mask |= 1u << k;
+    }
+    n_layers = (int)layers.size();
+    return ADAPTER_OK;
+}
+size_t AdapterFile::device_bytes() const {
+    size_t n = 0;
+    const size_t rp = (size_t)rank_padded();
+    for (auto &lp : layers) for (const Pair &p : lp.second) if (p.a) n += ((size_t)p.a->ne[0] + (size_t)p.b->ne[1]) * rp * 2;
+    return n;
+}
+
 // ---------------------------------------------------------------------------------------------------- tokenizer
 void Tokenizer::init(const LLMFile &f) {
     pieces = &f.pieces; scores = &f.scores;

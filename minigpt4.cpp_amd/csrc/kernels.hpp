@@ -39,6 +39,7 @@ struct LaunchTuning {
     int f16_ks = 0;              // forced K split of the F16 language model's single-matrix prompt launches (wo, w2; 0 = choose, at most 8; MINIGPT4_F16_KS)
     int splitk_xcd = 1;          // 1: a split-K GEMM's work list [slice][tile] is dealt to the XCDs in contiguous ranges; 0: slices in grid.z (rounds 3-5; MINIGPT4_SPLITK_XCD)
     int attn_vit_qt = 0;         // query tiles per workgroup of k_attn_vit (0 = the launcher's choice; MINIGPT4_ATTN_QT)
+    int lora_form = 0;           // force one form of the LoRA kernels (lora.hip): 1 = vector, 2 = MFMA; 0 = by rows (MFMA above 8)
     // the one place the fields' ranges are kept: the booleans 0 / 1, the forced counts >= 0, f16_ks <= 8, mmq3_waves 4 or 8, gemm_arm >= 0 or -2 or -3 (else the default)
     LaunchTuning normalised() const {
         LaunchTuning t = *this;
@@ -46,6 +47,7 @@ struct LaunchTuning {
         t.attn_prefill_w8 = attn_prefill_w8 != 0; t.attn_prefill_f16 = attn_prefill_f16 != 0; t.attn_prefill_form = (attn_prefill_form >= 1 && attn_prefill_form <= 3) || attn_prefill_form == 5 ? attn_prefill_form : 0;
         t.gemm_arm = gemm_arm >= 0 || gemm_arm == -2 || gemm_arm == -3 ? gemm_arm : 0; t.gemm_sk_arm = gemm_sk_arm > 0 ? gemm_sk_arm : 0;
         t.f16_ks = f16_ks < 0 ? 0 : f16_ks > 8 ? 8 : f16_ks; t.splitk_xcd = splitk_xcd != 0; t.attn_vit_qt = attn_vit_qt > 0 ? attn_vit_qt : 0;
+        t.lora_form = lora_form == 1 || lora_form == 2 ? lora_form : 0;
         return t;
     }
 };
@@ -146,6 +148,27 @@ int read_matvec_timeline_rows(unsigned long long *out, int max_workgroups);   //
 int read_matvec_timeline(unsigned long long *out, int max_workgroups);   // diagnostic builds (MG4_TIMELINE): stamps of the last decode mat-vec launch; 0 otherwise
 int read_attn_timeline(unsigned long long *out, int max_workgroups);     // prompt attention (8 x u64 per workgroup, up to 2048 workgroups)
 int read_vision_timeline(unsigned long long *out, int max_workgroups);   // the same for the image path's kernels (32 x u64 per workgroup)
+
+// ---- run-time LoRA adapters (lora.hip): y += s * B (A f(x)) on top of what the base launches wrote --------------------
+constexpr int LORA_MAX = 8, LORA_RANK_MAX = 64, LORA_TARGETS = 3, LORA_TCAT = LORA_TARGETS * LORA_RANK_MAX;   // adapters per context; rank; targets per site group; floats of a t row
+constexpr int LORA_SLAB_VEC = 512, LORA_SLAB_MFMA = 2048;   // K elements per slab of the down kernel's two forms (unmeasured choices)
+enum LoraMode : int { LORA_PLAIN = 0, LORA_RMS = 1, LORA_SILU = 2 };   // f(x): x | x * g, the row's 1 / rms applied by the up kernel | silu(x) * h3
+// One site group (q|k|v, wo, w1|w3, w2) of one layer over the loaded adapters; passed by value.  Adapter a: A[a] = [rcat[a]][n_in] fp16, the rows of target m from row
+// aoff[a][m] on (rp[a] rows: the rank zero-padded to a multiple of 16), B[a][m] = [n_out][rp[a]] fp16 (null: the adapter does not touch target m), alpha_r = alpha / rank
+struct LoraGroup { const __half *A[LORA_MAX]; const __half *B[LORA_MAX][LORA_TARGETS]; int rp[LORA_MAX], rcat[LORA_MAX], aoff[LORA_MAX][LORA_TARGETS]; float alpha_r[LORA_MAX]; };
+// the rows of a pass: row r belongs to conversation slot = row_slot ? row_slot[r * stride] : slot0; adapter[slot] = index into the group (-1: none), scale[slot] = the
+// conversation's own factor (device arrays)
+struct LoraRows { const int *adapter; const float *scale; const int *row_slot; int stride; int slot0; };
+struct LoraOut { float *y[LORA_TARGETS]; };   // [N][ldy] per target, null = not written
+int lora_form_for(const LaunchTuning &tune, int N);
+int lora_ks(int n_in, int form);
+size_t lora_ws_floats(int N, int n_in);   // floats of t + ssq that serve N rows of width n_in under either form: t = ws, ssq = ws + ks * N * LORA_TCAT
+// t[ks][N][LORA_TCAT], ssq[ks][N] (LORA_RMS only); y2 = g [n_in] (LORA_RMS) or h3 [N][n_in] (LORA_SILU).  Returns ks for launch_lora_up.  n_in % 8 == 0; x, y2, A 16-byte aligned.
+// Throw HipError for a shape outside the kernels' range
+int launch_lora_down(const LoraGroup &G, int n_adapters, const LoraRows &R, int N, int n_in, int mode, const float *x, const float *y2, float *t, float *ssq, const LaunchTuning &tune,
+                     hipStream_t s);
+void launch_lora_up(const LoraGroup &G, int n_adapters, const LoraRows &R, const LoraOut &Y, int N, int n_in, int mode, int n_out, int ldy, int ks, const float *t, const float *ssq,
+                    const LaunchTuning &tune, hipStream_t s);
 
 // ---- token embedding gather (raw ggml rows, dequantised to f32) -----------------------------------------------------
 void launch_get_rows(int type, const uint8_t *raw_table, int K, const int *tokens, int N, float *out, hipStream_t s);

@@ -2222,6 +2222,47 @@ int minigpt4_amd_llm_file_digest(const char *llm_path, uint64_t *digest, int wit
     *digest = h;
     return E_None;
 }
+// The LoRA kernels alone (launch_lora_down + launch_lora_up, lora.hip) on one target: row i is conversation i with adapter row_adapter[i] (-1: none) at scale 1.
+// a16 / b16: the adapters' A [rank][n_in] and B [n_out][rank] as fp16 bits, back to back; padded here to the device image's rank multiple of 16.  out = the delta alone.
+int minigpt4_amd_test_lora(int rows, int n_in, int n_out, int mode, const float *x, const float *second, int n_adapters, int rank, const unsigned short *a16, const unsigned short *b16,
+                           const float *s, const int32_t *row_adapter, int form, float *out) {
+    if (!x || !a16 || !b16 || !s || !row_adapter || !out || rows < 1 || rows > Engine::MAX_CONVERSATIONS || n_in < 8 || n_in % 8 || n_out < 1 || mode < LORA_PLAIN || mode > LORA_SILU ||
+        (mode != LORA_PLAIN && !second) || n_adapters < 1 || n_adapters > 2 || rank < 1 || rank > LORA_RANK_MAX || form < 0 || form > 2) return 1;
+    for (int r = 0; r < rows; r++) if (row_adapter[r] < -1 || row_adapter[r] >= n_adapters) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        const int rp = (rank + 15) / 16 * 16;
+        const size_t na = (size_t)rp * n_in, nb = (size_t)n_out * rp, nx = (size_t)rows * n_in, ny = (size_t)rows * n_out;
+        std::vector<unsigned short> ha(na * n_adapters, 0), hb(nb * n_adapters, 0);
+        for (int a = 0; a < n_adapters; a++) {
+            memcpy(&ha[a * na], a16 + (size_t)a * rank * n_in, (size_t)rank * n_in * 2);
+            for (int n = 0; n < n_out; n++) memcpy(&hb[a * nb + (size_t)n * rp], b16 + ((size_t)a * n_out + n) * rank, (size_t)rank * 2);
+        }
+        std::vector<int> slots(rows); std::vector<float> ones(rows, 1.0f);
+        for (int r = 0; r < rows; r++) slots[r] = r;
+        const size_t n2 = mode == LORA_RMS ? (size_t)n_in : nx, wsf = lora_ws_floats(rows, n_in);
+        DevBuf da(ha.size() * 2), db(hb.size() * 2), dx(nx * 4), d2(n2 * 4), dy(ny * 4), dws(wsf * 4), dad(rows * 4), dsc(rows * 4), dsl(rows * 4);
+        HIP_CHECK(hipMemcpy(da.p, ha.data(), ha.size() * 2, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(db.p, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
+        if (mode != LORA_PLAIN) HIP_CHECK(hipMemcpy(d2.p, second, n2 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dad.p, row_adapter, rows * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsc.p, ones.data(), rows * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dsl.p, slots.data(), rows * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(dy.p, 0, ny * 4));
+        LoraGroup G{};
+        for (int a = 0; a < n_adapters; a++) {
+            G.A[a] = da.as<__half>() + a * na; G.B[a][0] = db.as<__half>() + a * nb; G.rp[a] = G.rcat[a] = rp; G.aoff[a][0] = 0; G.aoff[a][1] = G.aoff[a][2] = -1; G.alpha_r[a] = s[a];
+        }
+        const LoraRows R{dad.as<int>(), dsc.as<float>(), dsl.as<int>(), 1, 0};
+        LoraOut Y{}; Y.y[0] = dy.as<float>();
+        LaunchTuning tune = hook_tuning(); tune.lora_form = form;
+        float *t = dws.as<float>();
+        const int ks = launch_lora_down(G, n_adapters, R, rows, n_in, mode, dx.as<float>(), d2.as<float>(), t, t + (size_t)lora_ks(n_in, 1) * rows * LORA_TCAT, tune, nullptr);
+        launch_lora_up(G, n_adapters, R, Y, rows, n_in, mode, n_out, n_out, ks, t, t + (size_t)lora_ks(n_in, 1) * rows * LORA_TCAT, tune, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 int64_t minigpt4_amd_quantize_chunk(int ggml_type, const float *x, void *dst, int64_t n) {
     if (!x || !dst || n <= 0) return 0;
     return (int64_t)quantize_chunk(ggml_type, x, static_cast<uint8_t *>(dst), (size_t)n);

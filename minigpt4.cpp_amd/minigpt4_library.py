@@ -280,6 +280,11 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_verify_draft_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, INT_PTR]
         L.minigpt4_amd_decode_lookup_batch.argtypes = [VOID_PTR, INT_PTR, I32, INT_PTR, INT_PTR, I32, I32, I32, I32, INT_PTR, INT_PTR, INT_PTR]
         L.minigpt4_amd_speculation_batch_info.argtypes = [VOID_PTR, I64P]
+        L.minigpt4_amd_adapter_peek.argtypes = [ctypes.c_char_p, I64P]
+        L.minigpt4_amd_adapter_load.argtypes = [VOID_PTR, ctypes.c_char_p, P(I32)]
+        L.minigpt4_amd_adapter_free.argtypes = [VOID_PTR, I32]
+        L.minigpt4_amd_set_adapter.argtypes = [VOID_PTR, I32, I32, F32]
+        L.minigpt4_amd_adapter_info.argtypes = [VOID_PTR, I32, I64P]
         L.minigpt4_amd_verify_draft_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, F32, I32, F32, F32, F32, F32, INT_PTR, INT_PTR, INT_PTR, INT_PTR, FLOAT_PTR]
         L.minigpt4_amd_decode_lookup_sampled_ex.argtypes = [VOID_PTR, INT_PTR, I32, I32, I32, I32, I32, F32, I32, F32, F32, F32, F32, INT_PTR, INT_PTR, INT_PTR]
 
@@ -326,6 +331,7 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_checksum.argtypes = [VOID_PTR, SIZE_T, U64P, FLOAT_PTR]
         L.minigpt4_amd_test_kv_pack.argtypes = [I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, VOID_PTR, U64P, FLOAT_PTR]
         L.minigpt4_amd_test_kv_unpack.argtypes = [I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, VOID_PTR, U64P, FLOAT_PTR]
+        L.minigpt4_amd_test_lora.argtypes = [I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR, INT_PTR, I32, FLOAT_PTR]
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_penalise_host.argtypes = [FLOAT_PTR, I32, INT_PTR, I32, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, INT_PTR, I32, INT_PTR]
@@ -1216,6 +1222,59 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_pen_pick rc={rc}: " + self._err())
         return picked, adj[:len(tb)], float(ms.value)
+
+    # ---- run-time LoRA adapters: one per conversation in the same weight pass (include/minigpt4_amd.h)
+    ADAPTER_TARGETS = ("attn_q", "attn_k", "attn_v", "attn_output", "ffn_gate", "ffn_down", "ffn_up")   # bit order of the target mask
+    ADAPTER_PEEK_FIELDS = ("rank", "alpha_milli", "n_tensors", "target_mask", "n_layers", "device_bytes", "refusal", "any_f32")
+    ADAPTER_INFO_FIELDS = ("handle", "scale_micro", "rank", "target_mask", "loaded", "down_launches", "up_launches", "device_bytes")
+
+    def amd_adapter_peek(self, path: str) -> dict:
+        """What a GGUF LoRA adapter file holds, without a context or a GPU; refusal != 0: why a load would refuse it (the text in last_error)."""
+        o = np.zeros(8, np.int64)
+        if self.library.minigpt4_amd_adapter_peek(os.fsencode(path), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))):
+            raise RuntimeError("adapter_peek failed: " + self._err())
+        return dict(zip(self.ADAPTER_PEEK_FIELDS, (int(v) for v in o)))
+
+    def amd_adapter_load(self, ctx, path: str) -> int:
+        """Upload an adapter file for this context; returns the handle (1 .. 8)."""
+        h = I32(0)
+        if self.library.minigpt4_amd_adapter_load(ctx.ptr, os.fsencode(path), ctypes.byref(h)):
+            raise RuntimeError("adapter_load failed: " + self._err())
+        return int(h.value)
+
+    def amd_adapter_free(self, ctx, handle: int) -> None:
+        if self.library.minigpt4_amd_adapter_free(ctx.ptr, int(handle)):
+            raise RuntimeError("adapter_free failed: " + self._err())
+
+    def amd_set_adapter(self, ctx, slot: int, handle: int, scale: float = 1.0) -> None:
+        """The EMPTY conversation `slot` runs under adapter `handle` (0: none) with s = alpha / rank * scale from now on."""
+        if self.library.minigpt4_amd_set_adapter(ctx.ptr, int(slot), int(handle), float(scale)):
+            raise RuntimeError("set_adapter failed: " + self._err())
+
+    def amd_adapter_info(self, ctx, slot: int = 0) -> dict:
+        o = np.zeros(8, np.int64)
+        if self.library.minigpt4_amd_adapter_info(ctx.ptr, int(slot), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))):
+            raise RuntimeError("adapter_info failed: " + self._err())
+        return dict(zip(self.ADAPTER_INFO_FIELDS, (int(v) for v in o)))
+
+    def test_lora(self, x, second, adapters, row_adapter, mode: int, form: int = 0) -> np.ndarray:
+        """(test library) The LoRA kernels alone: x [rows][n_in] f32; adapters = [(A [r][n_in] float16, B [n_out][r] float16, s), ...] (<= 2, one rank);
+        row_adapter [rows] (-1: none); mode 0 plain, 1 RMS norm with weight `second` [n_in], 2 silu(x) * second [rows][n_in]; form 0 by rows, 1 vector, 2 MFMA.
+        Returns the delta [rows][n_out] f32."""
+        x = np.ascontiguousarray(x, np.float32)
+        rows, n_in = x.shape
+        a16 = np.ascontiguousarray(np.stack([np.asarray(a[0], np.float16) for a in adapters]))
+        b16 = np.ascontiguousarray(np.stack([np.asarray(a[1], np.float16) for a in adapters]))
+        sc = np.ascontiguousarray([a[2] for a in adapters], np.float32)
+        ra = np.ascontiguousarray(row_adapter, np.int32)
+        sec = None if second is None else np.ascontiguousarray(second, np.float32)
+        out = np.empty((rows, b16.shape[1]), np.float32)
+        rc = self.library.minigpt4_amd_test_lora(rows, n_in, b16.shape[1], int(mode), x.ctypes.data_as(FLOAT_PTR), None if sec is None else sec.ctypes.data_as(FLOAT_PTR),
+                                                 len(adapters), a16.shape[1], a16.ctypes.data_as(VOID_PTR), b16.ctypes.data_as(VOID_PTR), sc.ctypes.data_as(FLOAT_PTR),
+                                                 ra.ctypes.data_as(INT_PTR), int(form), out.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_lora rc={rc}: " + self._err())
+        return out
 
     # ---- constrained decoding: a regular expression per conversation (include/minigpt4_amd.h)
     CONSTRAINT_INFO_FIELDS = ("handle", "state", "accepting", "n_states", "pick_launches", "host_rows", "stuck", "index_launches")

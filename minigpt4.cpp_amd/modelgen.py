@@ -17,7 +17,7 @@ import json
 import os
 import struct
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -426,6 +426,130 @@ def write_q8_0_twin(src: str, dst: str) -> None:
             raw, gt = f.raw(name), t.gtype
             if gt in (Q.GGML_IQ4_NL, Q.GGML_IQ4_XS):
                 raw, gt = Q.iq4_to_q8_0(raw, gt, int(np.prod(t.ne))), Q.GGML_Q8_0
+            nm = name.encode()
+            out.write(struct.pack("<III", len(t.ne), len(nm), gt) + struct.pack(f"<{len(t.ne)}I", *t.ne) + nm)
+            out.write(b"\0" * (_align(out.tell(), 32) - out.tell()))
+            out.write(bytes(raw))
+
+
+# ---- LoRA adapters (GGUF, the layout of llama.cpp's convert_lora_to_gguf.py) -------------------------------------------------------------------------
+LORA_TARGETS = {"attn_q": "attention.wq", "attn_k": "attention.wk", "attn_v": "attention.wv", "attn_output": "attention.wo", "ffn_gate": "feed_forward.w1",
+                "ffn_down": "feed_forward.w2", "ffn_up": "feed_forward.w3"}   # GGUF target -> the GGJT tensor it adapts; the engine's target mask has this bit order
+
+
+def write_lora_gguf(path: str, cfg: LLMConfig, rank: int, alpha: float, targets: Sequence[str], seed: int, std_a: float, std_b: float, layers: Optional[Sequence[int]] = None,
+                    gtype: int = Q.GGML_F16, general_type: str = "adapter", omit: Sequence[str] = (), rank_of: Optional[Dict[str, int]] = None,
+                    n_in_of: Optional[Dict[str, int]] = None) -> None:
+    """A Gaussian rank-`rank` adapter on `targets` (keys of LORA_TARGETS) of `layers` (default: all): blk.N.<target>.weight.lora_a with ggml ne = (n_in, r), .lora_b with
+    ne = (r, n_out), F16 or F32 (`gtype`; 30 writes BF16 bits, which the engine refuses).  The last four arguments write files the reader must refuse: another general.type,
+    tensor names left out, a rank or an input width of its own for one target."""
+    rng = np.random.default_rng(seed)
+    shapes = llm_tensor_shapes(cfg)
+
+    def gs(b: bytes) -> bytes:
+        return struct.pack("<Q", len(b)) + b
+
+    def kv(key: str, vt: int, payload: bytes) -> bytes:
+        return gs(key.encode()) + struct.pack("<I", vt) + payload
+
+    def enc(x: np.ndarray) -> bytes:
+        if gtype == Q.GGML_F32:
+            return x.astype(np.float32).tobytes()
+        if gtype == Q.GGML_F16:
+            return x.astype(np.float16).tobytes()
+        return (x.astype(np.float32).view(np.uint32) >> 16).astype(np.uint16).tobytes()   # BF16 (truncated)
+    meta = [kv("general.architecture", 8, gs(b"llama")), kv("general.type", 8, gs(general_type.encode())), kv("adapter.type", 8, gs(b"lora")),
+            kv("adapter.lora.alpha", 6, struct.pack("<f", alpha)), kv("general.alignment", 4, struct.pack("<I", 32))]
+    infos, blobs, off = [], [], 0
+    for il in (range(cfg.n_layer) if layers is None else layers):
+        for t in targets:
+            n_in, n_out = shapes[f"layers.{il}.{LORA_TARGETS[t]}.weight"]
+            r = (rank_of or {}).get(t, rank)
+            n_in = (n_in_of or {}).get(t, n_in)
+            a = rng.standard_normal((r, n_in)) * std_a
+            b = rng.standard_normal((n_out, r)) * std_b
+            for suffix, x, ne in (("lora_a", a, (n_in, r)), ("lora_b", b, (r, n_out))):
+                name = f"blk.{il}.{t}.weight.{suffix}"
+                if name in omit:
+                    continue
+                raw = enc(x)
+                infos.append(gs(name.encode()) + struct.pack("<I", 2) + struct.pack("<2Q", *ne) + struct.pack("<IQ", gtype, off))
+                blobs.append((off, raw))
+                off = _align(off + len(raw), 32)
+    head = struct.pack("<IIQQ", 0x46554747, 3, len(infos), len(meta)) + b"".join(meta) + b"".join(infos)
+    with open(path, "wb") as out:
+        out.write(head)
+        out.write(b"\0" * (_align(len(head), 32) - len(head)))
+        base = out.tell()
+        for o, raw in blobs:
+            out.seek(base + o)
+            out.write(raw)
+        out.truncate(base + off)
+
+
+def read_lora_gguf(path: str) -> Tuple[float, Dict[str, np.ndarray]]:
+    """(alpha, {tensor name: float64 array in torch layout [rows][cols]}) of a file write_lora_gguf wrote (its key types only: u32, f32, string)."""
+    mm = np.fromfile(path, dtype=np.uint8)
+    pos = 0
+
+    def take(fmt):
+        nonlocal pos
+        v = struct.unpack_from(fmt, mm, pos)
+        pos += struct.calcsize(fmt)
+        return v if len(v) > 1 else v[0]
+
+    def gstr():
+        nonlocal pos
+        n = take("<Q")
+        b = bytes(mm[pos:pos + n])
+        pos += n
+        return b
+    magic, _, n_t, n_kv = take("<IIQQ")
+    assert magic == 0x46554747
+    alpha, alignment = 0.0, 32
+    for _ in range(n_kv):
+        key, vt = gstr().decode(), take("<I")
+        val = gstr() if vt == 8 else take("<f") if vt == 6 else take("<I")
+        assert vt in (4, 6, 8), (key, vt)
+        if key == "adapter.lora.alpha":
+            alpha = float(val)
+        elif key == "general.alignment":
+            alignment = int(val)
+    infos = []
+    for _ in range(n_t):
+        name, nd = gstr().decode(), take("<I")
+        ne = [take("<Q") for _ in range(nd)]
+        gt, rel = take("<IQ")
+        infos.append((name, ne, gt, rel))
+    base = _align(pos, alignment)
+    out = {}
+    for name, ne, gt, rel in infos:
+        dt = {Q.GGML_F32: np.float32, Q.GGML_F16: np.float16}[gt]
+        n = int(np.prod(ne))
+        out[name] = np.frombuffer(mm[base + rel:base + rel + n * np.dtype(dt).itemsize].tobytes(), dt).astype(np.float64).reshape(ne[1], ne[0])
+    return alpha, out
+
+
+def write_merged_twin(src_llm: str, lora_path: str, dst: str, scale: float = 1.0) -> None:
+    """The GGJT file `src_llm` with the adapter merged in: every targeted tensor is dequantised, s * B . A (s = alpha / rank * scale; A and B rounded to fp16 first, the
+    device copy's precision) is added in float64 and the tensor is stored as F32; every other tensor byte for byte.  What the CPU oracle evaluates in place of base + adapter."""
+    f = read_llm_file(src_llm)
+    hp = f.hparams
+    alpha, lt = read_lora_gguf(lora_path)
+    rev = {v: k for k, v in LORA_TARGETS.items()}
+    with open(dst, "wb") as out:
+        out.write(struct.pack("<II", GGJT_MAGIC, GGJT_VERSION))
+        out.write(struct.pack("<7I", *(hp[k] for k in ("n_vocab", "n_embd", "n_mult", "n_head", "n_layer", "n_rot", "ftype"))))
+        for piece, score in f.vocab:
+            out.write(struct.pack("<I", len(piece)) + piece + struct.pack("<f", score))
+        for name, t in f.tensors.items():
+            raw, gt = f.raw(name), t.gtype
+            parts = name.split(".")
+            key = f"blk.{parts[1]}.{rev.get('.'.join(parts[2:4]), '')}.weight.lora_a" if parts[0] == "layers" and len(parts) == 5 else ""
+            if key in lt:
+                a, b = lt[key].astype(np.float16).astype(np.float64), lt[key[:-1] + "b"].astype(np.float16).astype(np.float64)
+                w = f.f64(name) + (alpha / a.shape[0] * scale) * (b @ a)
+                raw, gt = w.astype(np.float32).reshape(-1).view(np.uint8), Q.GGML_F32
             nm = name.encode()
             out.write(struct.pack("<III", len(t.ne), len(nm), gt) + struct.pack(f"<{len(t.ne)}I", *t.ne) + nm)
             out.write(b"\0" * (_align(out.tell(), 32) - out.tell()))

@@ -82,6 +82,7 @@ class ReplicaServer:
             self.lib.amd_set_prefix_cache(self.ctx, prefix_cache)
         self._parked = {}                      # session id -> snapshot of the idle session
         self._speculation = False              # run(lookup=...) switches draft verification on at its first use
+        self._adapters = {}                    # run(adapters=...): path -> handle of every LoRA adapter loaded so far
         self._row_cap = min(64, max(n_batch, 32, conversations))   # rows one verify pass holds: 64, and the context's activation rows (include/minigpt4_amd.h)
 
     def suspend(self, slot: int) -> bytes:
@@ -119,8 +120,12 @@ class ReplicaServer:
             frequency_penalty: float = 0.0, logit_bias=None, num_beams: int = 1, length_penalty: float = 1.0, guidance_scale: float = 1.0,
             negative_prompt: Optional[str] = None, regex=None, sessions: Optional[Sequence] = None, device_sampling: bool = False,
             seeds: Optional[Sequence[int]] = None, tfs_z: float = 1.0, typical_p: float = 1.0, min_p: float = 0.0, mirostat: int = 0, mirostat_tau: float = 5.0,
-            mirostat_eta: float = 0.1, lookup: int = 0) -> List[str]:
-        """lookup = n_draft (1 .. 7; 0, the default, is exactly the decode loop below): greedy lookup decoding for the whole wave.  Every iteration of the decode loop is
+            mirostat_eta: float = 0.1, lookup: int = 0, adapters: Optional[Sequence[Optional[str]]] = None, adapter_scale: float = 1.0) -> List[str]:
+        """adapters (one GGUF LoRA adapter path or None per request): the request's conversation runs under that adapter (`minigpt4_amd_set_adapter`, factor adapter_scale),
+        requests under different adapters and under none share the wave's weight passes.  A path is loaded once per server (`minigpt4_amd_adapter_load`; at most 8
+        different ones) and stays loaded.  With guidance the guidance conversation takes the request's adapter, with beams the scratch conversations inherit it from the
+        fork.  ValueError together with sessions (a snapshot does not record the adapter).
+        lookup = n_draft (1 .. 7; 0, the default, is exactly the decode loop below): greedy lookup decoding for the whole wave.  Every iteration of the decode loop is
         ONE `minigpt4_amd_verify_draft_batch`: each unfinished request brings its next token and up to n_draft guesses behind it -- `ngram_draft` over the request's
         tokenized prompt followed by the tokens it has emitted, cut at the tokens the request still wants -- through one weight pass and keeps the guesses the pass's own
         logits confirm, so the answers are those of temp = 0 without lookup.  The kept tokens go through the same piece-by-piece stop rule; tokens kept behind the stop are
@@ -212,6 +217,19 @@ class ReplicaServer:
                     raise ValueError("sessions: a request without an image must name a parked session, a request with one must not")
         elif any(r.image is None for r in requests):
             raise ValueError("a request without an image needs sessions=")
+        handles = None
+        if adapters is not None:
+            if len(adapters) != len(requests):
+                raise ValueError("adapters: one path (or None) per request")
+            if sessions is not None:
+                raise ValueError("adapters is not available with sessions")
+            if not np.isfinite(adapter_scale):
+                raise ValueError("adapter_scale must be finite")
+            for path in adapters:
+                if path is not None and path not in self._adapters:
+                    self._adapters[path] = lib.amd_adapter_load(ctx, path)   # a refused file raises before anything is touched
+        if self._adapters:                                                   # (a server that never loaded one makes no adapter call at all)
+            handles = [self._adapters[p] if p is not None else 0 for p in (adapters if adapters is not None else [None] * len(requests))]
         answers: List[str] = [""] * len(requests)
         self._constraint = lib.amd_constraint_compile(ctx, regex) if regex is not None else 0   # a refused pattern raises before anything is touched
         penalised = repeat_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
@@ -219,7 +237,8 @@ class ReplicaServer:
         try:
             return self._run(requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias,
                              dict(repeat_last_n=repeat_last_n, repeat_penalty=repeat_penalty, alpha_presence=presence_penalty, alpha_frequency=frequency_penalty),
-                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None, chain, lookup)
+                             num_beams, length_penalty, guidance_scale if guided else None, negative_prompt, sessions, seeds if device_sampling else None, chain, lookup,
+                             handles, adapter_scale)
         finally:
             if self._constraint:
                 for slot in range(self.conversations):
@@ -257,7 +276,7 @@ class ReplicaServer:
                 shown += piece
         return shown
 
-    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None, chain=None, lookup=0) -> List[str]:
+    def _run(self, requests, answers, temp, top_k, top_p, ignore_eos, batched_prefill, logprobs, penalised, logit_bias, pen, num_beams=1, length_penalty=1.0, guidance=None, negative_prompt=None, sessions=None, seeds=None, chain=None, lookup=0, handles=None, adapter_scale=1.0) -> List[str]:
         import ctypes
         lib, ctx = self.lib, self.ctx
         if lookup and not self._speculation:
@@ -285,10 +304,15 @@ class ReplicaServer:
                     slot = j * per
                     lib.amd_select_conversation(ctx, slot)
                     if requests[i].image is None:
+                        if handles is not None:               # a slot an earlier call left under an adapter: the parked rows were written without one
+                            lib.minigpt4_reset_chat(ctx)
+                            lib.amd_set_adapter(ctx, slot, 0)
                         self.resume(slot, self._parked[sessions[i]])   # the parked blob stays until the wave has parked the session again: a failure in between loses nothing
                         lib.minigpt4_begin_chat(ctx, requests[i].prompt)
                     else:
                         lib.minigpt4_reset_chat(ctx)
+                        if handles is not None:
+                            lib.amd_set_adapter(ctx, slot, handles[i], adapter_scale)   # the conversation is empty here
                         lib.minigpt4_system_prompt(ctx)
                         lib.minigpt4_begin_chat_image(ctx, embs.embeddings[emb_of[i]], requests[i].prompt)
                     if penalised:
@@ -304,6 +328,8 @@ class ReplicaServer:
                     if guidance is not None:                  # the guidance conversation: the same question (or the negative prompt) asked without the image
                         lib.amd_select_conversation(ctx, slot + 1)
                         lib.minigpt4_reset_chat(ctx)
+                        if handles is not None:
+                            lib.amd_set_adapter(ctx, slot + 1, handles[i], adapter_scale)
                         lib.minigpt4_system_prompt(ctx)
                         lib.minigpt4_begin_chat(ctx, requests[i].prompt if negative_prompt is None else negative_prompt)
                 if batched_prefill:                           # the wave's prompts in one pass per chunk instead of one pass per conversation
