@@ -462,6 +462,15 @@ MINIGPT4_API int minigpt4_amd_convert_q3k_q6k(const void *src, void *dst, int64_
  * form 0 = by rows, 1 = vector, 2 = MFMA.  out [rows][n_out] = s * B (A f(x)) alone.  0; 1 bad arguments; 2 no device; 3 a HIP error. */
 MINIGPT4_API int minigpt4_amd_test_lora(int rows, int n_in, int n_out, int mode, const float *x, const float *second, int n_adapters, int rank, const unsigned short *a16,
                                         const unsigned short *b16, const float *s, const int32_t *row_adapter, int form, float *out);
+/* One LoRA site group as the engine drives it (k_lora_down + k_lora_up once, either form), everything the caller's: rows <= 512; n_in a multiple of 8; ldy >= n_out;
+ * n_targets 1..3 that share x; n_adapters 1..8, adapter a of rank[a] (1..64), factor alpha_r[a] and target_mask[a] (bit m: it touches target m; 0: nothing here, but not
+ * all 0); a16 / b16: per adapter, per present target in target order, A [rank][n_in] / B [n_out][rank] as fp16 bits back to back (the hook pads and concatenates them
+ * by the loader's rule); n_slots <= 64 conversation slots with slot_adapter (-1: none) and slot_scale; row r belongs to slot row_slot[r * stride] (rows * stride entries,
+ * every one a valid slot, stride 1..8), or row_slot NULL: every row to slot0.  mode / second / form as above.  y [n_targets][rows][ldy]: uploaded as given, the terms are
+ * added, the whole buffer (padding columns too) comes back.  0; 1 bad arguments; 2 no device; 3 a HIP error. */
+MINIGPT4_API int minigpt4_amd_test_lora_group(int rows, int n_in, int n_out, int ldy, int mode, int form, const float *x, const float *second, int n_targets, int n_adapters,
+                                              const int32_t *rank, const float *alpha_r, const int32_t *target_mask, const unsigned short *a16, const unsigned short *b16,
+                                              int n_slots, const int32_t *slot_adapter, const float *slot_scale, const int32_t *row_slot, int stride, int slot0, float *y);
 /* Host sampler with an explicit seed (fresh std::mt19937 per call). */
 MINIGPT4_API int minigpt4_amd_sample_logits(const float *logits, int n_vocab, int seed, float temp, int32_t top_k, float top_p, float tfs_z, float typical_p,
                                             int mirostat, float mirostat_tau, float mirostat_eta);

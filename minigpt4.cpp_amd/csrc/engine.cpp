@@ -992,7 +992,7 @@ int Engine::adapter_load(const std::string &path, int *handle) {
             if (p.a->ne[0] != n_in || p.b->ne[1] != n_out) return refuse("shapes of layer " + std::to_string(lp.first) + " do not match the loaded model");
         }
     }
-    const int r = f.rank, rp = f.rank_padded();
+    const int r = f.rank, rp = lora_rank_padded(f.rank);                   // = f.rank_padded(), which sized device_bytes(): the image-size check below holds them together
     // host image: fp16, the rank zero-padded to rp; per layer and group the A rows of its present targets back to back, then their B matrices [n_out][rp]
     std::vector<__half> img(f.device_bytes() / 2, __float2half_rn(0.0f));
     std::vector<std::array<LoraPart, 4>> part(layers_.size());
@@ -1003,13 +1003,13 @@ int Engine::adapter_load(const std::string &path, int *handle) {
         LoraPart &P = part[(size_t)lp.first][(size_t)g];
         const size_t n_in = (size_t)(g == LS_W2 ? F : E), n_out = (size_t)(g == LS_W1W3 ? F : E);
         a_off[(size_t)lp.first][(size_t)g] = pos;
+        bool present[LORA_TARGETS];
+        for (int m = 0; m < LORA_TARGETS; m++) present[m] = group_targets[g][m] >= 0 && lp.second[(size_t)group_targets[g][m]].a;
+        P.rcat = lora_concat(present, rp, P.aoff);
         for (int m = 0; m < LORA_TARGETS; m++) {
-            const int k = group_targets[g][m];
-            if (k < 0 || !lp.second[(size_t)k].a) continue;
-            const TensorMeta *ta = lp.second[(size_t)k].a;                 // ne = (n_in, r): r rows of n_in
-            P.aoff[m] = P.rcat;
-            for (size_t j = 0; j < (size_t)r; j++) for (size_t c = 0; c < n_in; c++) img[pos + ((size_t)P.rcat + j) * n_in + c] = value(ta, j * n_in + c);
-            P.rcat += rp;
+            if (P.aoff[m] < 0) continue;
+            const TensorMeta *ta = lp.second[(size_t)group_targets[g][m]].a;   // ne = (n_in, r): r rows of n_in
+            for (size_t j = 0; j < (size_t)r; j++) for (size_t c = 0; c < n_in; c++) img[pos + ((size_t)P.aoff[m] + j) * n_in + c] = value(ta, j * n_in + c);
         }
         pos += (size_t)P.rcat * n_in;
         for (int m = 0; m < LORA_TARGETS; m++) {

@@ -156,6 +156,14 @@ enum LoraMode : int { LORA_PLAIN = 0, LORA_RMS = 1, LORA_SILU = 2 };   // f(x): 
 // One site group (q|k|v, wo, w1|w3, w2) of one layer over the loaded adapters; passed by value.  Adapter a: A[a] = [rcat[a]][n_in] fp16, the rows of target m from row
 // aoff[a][m] on (rp[a] rows: the rank zero-padded to a multiple of 16), B[a][m] = [n_out][rp[a]] fp16 (null: the adapter does not touch target m), alpha_r = alpha / rank
 struct LoraGroup { const __half *A[LORA_MAX]; const __half *B[LORA_MAX][LORA_TARGETS]; int rp[LORA_MAX], rcat[LORA_MAX], aoff[LORA_MAX][LORA_TARGETS]; float alpha_r[LORA_MAX]; };
+// The layout rule of one adapter's A image at one site group (the engine's loader and the kernel test hook both call it): rank r is padded to rp, the present targets'
+// rp rows follow one another in target order.  aoff[m] = first row of target m (-1: absent); returns rcat, the rows of the image.
+inline int lora_rank_padded(int r) { return (r + 15) / 16 * 16; }
+inline int lora_concat(const bool present[LORA_TARGETS], int rp, int aoff[LORA_TARGETS]) {
+    int rcat = 0;
+    for (int m = 0; m < LORA_TARGETS; m++) { aoff[m] = present[m] ? rcat : -1; if (present[m]) rcat += rp; }
+    return rcat;
+}
 // the rows of a pass: row r belongs to conversation slot = row_slot ? row_slot[r * stride] : slot0; adapter[slot] = index into the group (-1: none), scale[slot] = the
 // conversation's own factor (device arrays)
 struct LoraRows { const int *adapter; const float *scale; const int *row_slot; int stride; int slot0; };

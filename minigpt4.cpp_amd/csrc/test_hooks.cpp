@@ -2263,6 +2263,77 @@ int minigpt4_amd_test_lora(int rows, int n_in, int n_out, int mode, const float 
         return 0;
     });
 }
+// One site group as Engine::lora_site drives it (launch_lora_down + launch_lora_up once), every degree of freedom the caller's: up to three targets that share the input,
+// up to LORA_MAX adapters of their own rank / alpha_r / target mask (0: the adapter has nothing at this site, like an index the engine left unused), conversation slots
+// with their adapter and factor, rows mapped to slots by row_slot[row * stride] or all to slot0, y [n_targets][rows][ldy] uploaded as given and returned whole.
+// a16 / b16: per adapter, per present target in target order, A [rank][n_in] / B [n_out][rank] as fp16 bits back to back; the device image is laid out by
+// lora_rank_padded / lora_concat, the engine loader's rule.
+int minigpt4_amd_test_lora_group(int rows, int n_in, int n_out, int ldy, int mode, int form, const float *x, const float *second, int n_targets, int n_adapters, const int32_t *rank,
+                                 const float *alpha_r, const int32_t *target_mask, const unsigned short *a16, const unsigned short *b16, int n_slots, const int32_t *slot_adapter,
+                                 const float *slot_scale, const int32_t *row_slot, int stride, int slot0, float *y) {
+    if (!x || !rank || !alpha_r || !target_mask || !a16 || !b16 || !slot_adapter || !slot_scale || !y || rows < 1 || rows > 512 || n_in < 8 || n_in % 8 || n_out < 1 || ldy < n_out ||
+        mode < LORA_PLAIN || mode > LORA_SILU || (mode != LORA_PLAIN && !second) || form < 0 || form > 2 || n_targets < 1 || n_targets > LORA_TARGETS || n_adapters < 1 ||
+        n_adapters > LORA_MAX || n_slots < 1 || n_slots > Engine::MAX_CONVERSATIONS) return 1;
+    bool any = false;
+    for (int a = 0; a < n_adapters; a++) {
+        if (rank[a] < 1 || rank[a] > LORA_RANK_MAX || target_mask[a] < 0 || target_mask[a] >= (1 << n_targets) || !std::isfinite(alpha_r[a])) return 1;
+        any = any || target_mask[a] != 0;
+    }
+    if (!any) return 1;
+    for (int i = 0; i < n_slots; i++) if (slot_adapter[i] < -1 || slot_adapter[i] >= n_adapters || !std::isfinite(slot_scale[i])) return 1;
+    if (row_slot) {
+        if (stride < 1 || stride > 8) return 1;
+        for (size_t i = 0; i < (size_t)rows * stride; i++) if (row_slot[i] < 0 || row_slot[i] >= n_slots) return 1;   // the skipped entries too: a misread stays in range
+    } else if (slot0 < 0 || slot0 >= n_slots) return 1;
+    if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
+    return guarded(3, [&]() -> int {
+        // host image, as Engine::adapter_load builds it: per adapter the concatenated A rows, then the present targets' B matrices
+        int rp[LORA_MAX], rcat[LORA_MAX], aoff[LORA_MAX][LORA_TARGETS];
+        size_t a_at[LORA_MAX], b_at[LORA_MAX][LORA_TARGETS], pos = 0;
+        for (int a = 0; a < n_adapters; a++) {
+            bool present[LORA_TARGETS];
+            for (int m = 0; m < LORA_TARGETS; m++) present[m] = (target_mask[a] >> m) & 1;
+            rp[a] = lora_rank_padded(rank[a]);
+            rcat[a] = lora_concat(present, rp[a], aoff[a]);
+            a_at[a] = pos; pos += (size_t)rcat[a] * n_in;
+            for (int m = 0; m < LORA_TARGETS; m++) if (aoff[a][m] >= 0) { b_at[a][m] = pos; pos += (size_t)n_out * rp[a]; }
+        }
+        std::vector<unsigned short> img(pos, 0);
+        const unsigned short *pa = a16, *pb = b16;
+        for (int a = 0; a < n_adapters; a++) for (int m = 0; m < LORA_TARGETS; m++) {
+            if (aoff[a][m] < 0) continue;
+            const size_t r = (size_t)rank[a];
+            memcpy(&img[a_at[a] + (size_t)aoff[a][m] * n_in], pa, r * n_in * 2); pa += r * n_in;
+            for (size_t n = 0; n < (size_t)n_out; n++) memcpy(&img[b_at[a][m] + n * rp[a]], pb + n * r, r * 2);
+            pb += (size_t)n_out * r;
+        }
+        const size_t nx = (size_t)rows * n_in, n2 = mode == LORA_RMS ? (size_t)n_in : nx, ny = (size_t)n_targets * rows * ldy, wsf = lora_ws_floats(rows, n_in),
+                     nrs = row_slot ? (size_t)rows * stride : 1;
+        DevBuf dimg(img.size() * 2), dx(nx * 4), d2(n2 * 4), dy(ny * 4), dws(wsf * 4), dad((size_t)n_slots * 4), dsc((size_t)n_slots * 4), dsl(nrs * 4);
+        HIP_CHECK(hipMemcpy(dimg.p, img.data(), img.size() * 2, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dx.p, x, nx * 4, hipMemcpyHostToDevice));
+        if (mode != LORA_PLAIN) HIP_CHECK(hipMemcpy(d2.p, second, n2 * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dy.p, y, ny * 4, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dad.p, slot_adapter, (size_t)n_slots * 4, hipMemcpyHostToDevice)); HIP_CHECK(hipMemcpy(dsc.p, slot_scale, (size_t)n_slots * 4, hipMemcpyHostToDevice));
+        if (row_slot) HIP_CHECK(hipMemcpy(dsl.p, row_slot, nrs * 4, hipMemcpyHostToDevice));
+        LoraGroup G{};
+        for (int a = 0; a < n_adapters; a++) {
+            G.rp[a] = rp[a]; G.rcat[a] = rcat[a]; G.alpha_r[a] = alpha_r[a];
+            G.A[a] = rcat[a] ? dimg.as<__half>() + a_at[a] : nullptr;
+            for (int m = 0; m < LORA_TARGETS; m++) { G.aoff[a][m] = aoff[a][m]; G.B[a][m] = aoff[a][m] >= 0 ? dimg.as<__half>() + b_at[a][m] : nullptr; }
+        }
+        const LoraRows R{dad.as<int>(), dsc.as<float>(), row_slot ? dsl.as<int>() : nullptr, row_slot ? stride : 0, slot0};
+        LoraOut Y{};
+        for (int m = 0; m < n_targets; m++) Y.y[m] = dy.as<float>() + (size_t)m * rows * ldy;
+        LaunchTuning tune = hook_tuning(); tune.lora_form = form;
+        float *t = dws.as<float>(), *ssq = t + (size_t)lora_ks(n_in, 1) * rows * LORA_TCAT;
+        const int ks = launch_lora_down(G, n_adapters, R, rows, n_in, mode, dx.as<float>(), d2.as<float>(), t, ssq, tune, nullptr);
+        launch_lora_up(G, n_adapters, R, Y, rows, n_in, mode, n_out, ldy, ks, t, ssq, tune, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 int64_t minigpt4_amd_quantize_chunk(int ggml_type, const float *x, void *dst, int64_t n) {
     if (!x || !dst || n <= 0) return 0;
     return (int64_t)quantize_chunk(ggml_type, x, static_cast<uint8_t *>(dst), (size_t)n);

@@ -332,6 +332,8 @@ class MiniGPT4SharedLibrary:
         L.minigpt4_amd_test_kv_pack.argtypes = [I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, VOID_PTR, U64P, FLOAT_PTR]
         L.minigpt4_amd_test_kv_unpack.argtypes = [I32, I32, I32, I32, I32, VOID_PTR, VOID_PTR, VOID_PTR, U64P, FLOAT_PTR]
         L.minigpt4_amd_test_lora.argtypes = [I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, I32, I32, VOID_PTR, VOID_PTR, FLOAT_PTR, INT_PTR, I32, FLOAT_PTR]
+        L.minigpt4_amd_test_lora_group.argtypes = [I32, I32, I32, I32, I32, I32, FLOAT_PTR, FLOAT_PTR, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, VOID_PTR, VOID_PTR, I32, INT_PTR,
+                                                   FLOAT_PTR, INT_PTR, I32, I32, FLOAT_PTR]
         L.minigpt4_amd_test_logprob_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_topn_rows.argtypes = [FLOAT_PTR, I32, I32, I32, INT_PTR, I32, I32, INT_PTR, INT_PTR, FLOAT_PTR, INT_PTR, FLOAT_PTR, FLOAT_PTR]
         L.minigpt4_amd_test_penalise_host.argtypes = [FLOAT_PTR, I32, INT_PTR, I32, I32, I32, F32, F32, F32, I32, INT_PTR, FLOAT_PTR, I32, INT_PTR, I32, INT_PTR]
@@ -1275,6 +1277,30 @@ class MiniGPT4SharedLibrary:
         if rc:
             raise RuntimeError(f"test_lora rc={rc}: " + self._err())
         return out
+
+    def test_lora_group(self, x, second, n_out: int, adapters, slot_adapter, slot_scale, row_slot, stride: int, slot0: int, y, mode: int, form: int = 0) -> np.ndarray:
+        """(test library) One LoRA site group as the engine drives it: x [rows][n_in] f32; adapters = [dict(rank, alpha_r, mask, A={m: [rank][n_in] float16},
+        B={m: [n_out][rank] float16}), ...] with A / B for the targets m of `mask`; slot_adapter / slot_scale per conversation slot; row_slot [rows * stride] or None
+        (every row in slot0); y [n_targets][rows][ldy] f32, the outputs before the call.  Returns y after it, padding columns included."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.array(y, np.float32, order="C")
+        (rows, n_in), (n_targets, _, ldy) = x.shape, y.shape
+        present = [(a, m) for a in adapters for m in range(3) if a["mask"] >> m & 1]
+        a16, b16 = (np.concatenate([np.asarray(a[k][m], np.float16).ravel() for a, m in present]) if present else np.zeros(1, np.float16) for k in "AB")
+        rk, ar, mk = (np.ascontiguousarray([a[k] for a in adapters], t) for k, t in (("rank", np.int32), ("alpha_r", np.float32), ("mask", np.int32)))
+        sa, ss = np.ascontiguousarray(slot_adapter, np.int32), np.ascontiguousarray(slot_scale, np.float32)
+        rs = None if row_slot is None else np.ascontiguousarray(row_slot, np.int32)
+        sec = None if second is None else np.ascontiguousarray(second, np.float32)
+        if y.shape[1] != rows or len(sa) != len(ss) or (rs is not None and rs.size != rows * stride) or a16.size < sum(a["rank"] * n_in for a, _ in present) or \
+                b16.size < sum(a["rank"] * n_out for a, _ in present):
+            raise ValueError("test_lora_group: y, the slots, row_slot or A / B do not fit the shapes")
+        rc = self.library.minigpt4_amd_test_lora_group(rows, n_in, int(n_out), ldy, int(mode), int(form), x.ctypes.data_as(FLOAT_PTR), None if sec is None else sec.ctypes.data_as(FLOAT_PTR),
+                                                       n_targets, len(adapters), rk.ctypes.data_as(INT_PTR), ar.ctypes.data_as(FLOAT_PTR), mk.ctypes.data_as(INT_PTR),
+                                                       a16.ctypes.data_as(VOID_PTR), b16.ctypes.data_as(VOID_PTR), len(sa), sa.ctypes.data_as(INT_PTR), ss.ctypes.data_as(FLOAT_PTR),
+                                                       None if rs is None else rs.ctypes.data_as(INT_PTR), int(stride), int(slot0), y.ctypes.data_as(FLOAT_PTR))
+        if rc:
+            raise RuntimeError(f"test_lora_group rc={rc}: " + self._err())
+        return y
 
     # ---- constrained decoding: a regular expression per conversation (include/minigpt4_amd.h)
     CONSTRAINT_INFO_FIELDS = ("handle", "state", "accepting", "n_states", "pick_launches", "host_rows", "stuck", "index_launches")

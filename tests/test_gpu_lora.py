@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from lora_ref import lora_bound
+
 pytestmark = pytest.mark.gpu
 
 N_IN, TOL = 352, 1e-2
@@ -17,17 +19,6 @@ def _rel(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ 1. the kernels alone
-def lora_bound(form, n_in, r, terms):
-    """Bound on |kernel - float64| of one output y_n = s sum_j B[n][j] t_j, t_j = sum_k A[j][k] f_k, with terms = S_n = |s| sum_j |B[n][j]| sum_k |A[j][k] f_k| (the sum of
-    the absolute values of every product that enters y_n) and u = 2^-24:
-      vector: f(x) is formed in fp32 (at most x * g, or expf / add / divide / multiply: <= 8 u relative), the RMS factor from an fp32 sum of n_in squares, a divide, a
-              square root and a divide (<= (n_in + 8) u relative, applied to t with one more rounding), every t_j from an fp32 sum of n_in products in some order plus the
-              slab sums (<= (n_in + 8) u T_j), y_n from an fp32 sum of r products and the scale (<= (r + 8) u):  (2 n_in + r + 32) u S_n
-      MFMA:   additionally f(x) and t are rounded to fp16 before they enter the matrix cores, 2^-11 S_n each (second order: a factor 1 + 2^-10)."""
-    b = (2 * n_in + r + 32) * 2.0 ** -24 * terms
-    return b + (2 * 2.0 ** -11 * (1 + 2.0 ** -10) * terms if form == 2 else 0.0)
-
-
 def _f64(mode, x, second):
     x = x.astype(np.float64)
     if mode == 1:
@@ -44,7 +35,7 @@ def _f64(mode, x, second):
 @pytest.mark.parametrize("r", [8, 24, 64])
 @pytest.mark.parametrize("rows", [1, 3, 9, 33])
 def test_kernels_against_float64(gpu_lib, rows, r, n_out, mode, form, arrangement):
-    """Every output within lora_bound (above) of the float64 value; rows without an adapter exactly 0.  33 rows: two MFMA tiles, one ragged; r = 24: the padding to 32;
+    """Every output within lora_bound (tests/lora_ref.py) of the float64 value; rows without an adapter exactly 0.  33 rows: two MFMA tiles, one ragged; r = 24: the padding to 32;
     n_in = 352: not a multiple of the K steps; "mixed": rows alternate adapter 0, adapter 1, none inside one tile."""
     rng = np.random.default_rng(rows * 1000 + r * 10 + mode)
     x = rng.standard_normal((rows, N_IN)).astype(np.float32)
@@ -131,6 +122,37 @@ def test_whole_model_against_merged_twin(gpu_lib, files):
         assert max(errs) <= TOL, errs
         info = gpu_lib.amd_adapter_info(ctx, 0)
         assert (info["handle"], info["scale_micro"], info["rank"], info["target_mask"], info["loaded"]) == (h, 1000000, 8, 127, 1) and info["down_launches"] == info["up_launches"] > 0
+    finally:
+        gpu_lib.minigpt4_free(ctx)
+
+
+def test_whole_model_at_a_multi_slab_width(gpu_lib, tiny_files, tmpdir_models):
+    """n_embd 1024, one layer, 8 heads: n_ff = 2816, so the vector forms sum 2 (n_embd) and 6 (ffn_down) K slabs and the MFMA form 2 at ffn_down; one rank-64 adapter on all
+    seven targets (192 rows of A at q | k | v).  37 prompt tokens at n_batch 64 (two MFMA row tiles, the second with 5 rows), then 8 greedy steps on the vector forms:
+    logits within 1e-2 of the largest |logit| of the oracle on the merged twin.  Condition, on the oracle alone: base and twin differ by >= 0.1 of the largest |logit|."""
+    from minigpt4_cpp_amd import modelgen as G
+    vp, _ = tiny_files
+    cfg = G.tiny_llm(wtype="f32", n_embd=1024, n_layer=1, n_head=8, n_vocab=512)
+    assert cfg.n_ff == 2816
+    base, lp, twin = (os.path.join(tmpdir_models, n) for n in ("llm_f32_1024.bin", "lora_1024.gguf", "lora_1024_twin.bin"))
+    G.write_llm_file(base, cfg, seed=1, std=0.05, **G.TINY_CONDITIONED)
+    G.write_lora_gguf(lp, cfg, rank=64, alpha=64.0, targets=ALL7, seed=31, std_a=0.05, std_b=0.05)
+    G.write_merged_twin(base, lp, twin)
+    toks = TOKS[:10] + list(range(301, 328))
+    assert len(toks) == 37
+    ob, ot = _oracle(base), _oracle(twin)
+    for o in (ob, ot):
+        o.eval_tokens(toks)
+    assert _rel(ob.logits, ot.logits) >= 0.1, _rel(ob.logits, ot.logits)
+    ctx = gpu_lib.minigpt4_model_load(vp, base, verbosity=0, n_ctx=96, n_batch=64)
+    try:
+        gpu_lib.amd_set_adapter(ctx, 0, gpu_lib.amd_adapter_load(ctx, lp))
+        gpu_lib.amd_eval_tokens(ctx, toks)
+        errs, _, _ = _walk(gpu_lib, ctx, ot, 8, strict=False)
+        print("lora whole model, 1024 wide: logit errors", ["%.2e" % e for e in errs])
+        assert max(errs) <= TOL, errs
+        info = gpu_lib.amd_adapter_info(ctx, 0)
+        assert (info["rank"], info["target_mask"]) == (64, 127) and info["down_launches"] == info["up_launches"] >= 8   # four site groups: the prompt pass, the decode step
     finally:
         gpu_lib.minigpt4_free(ctx)
 
