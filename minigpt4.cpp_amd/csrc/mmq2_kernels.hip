@@ -14,6 +14,8 @@
 //     weight row and its sub-block scales are per-lane scalars;  the Q4_K / Q5_K min term sum_j m_j * bsum_j runs as two MFMAs on the digit split
 //     bsum = 128 hi + lo (exact) instead of round 1's eight MFMAs against a broadcast byte;
 //   * <= 256 VGPRs: two workgroups (8 waves) per CU, so one wave's scale arithmetic (VALU) overlaps another's MFMAs.
+// Members (mmq2_supported; all behind launch_mmq2_set): k_mmq2_q45k (Q4_K, Q5_K), k_mmq2_q6k (Q6_K), k_mmq2_q40 (Q4_0) and k_mmqh_q45k (fp16 form, off) in this file;
+// k_mmq2_iq4 (IQ4_NL, IQ4_XS) in mmq2_iq4.hip; k_mmq2_q32 (Q8_0, Q5_0, Q5_1, Q4_1) in mmq2_q32.hip.
 // Per (row tile, super-block, token tile): 8 + 2 MFMAs (Q4_K / Q5_K) or 16 (Q6_K) and ~300 VALU instructions per wave -- the kernel is VALU-bound by the integer
 // sub-block scale multiply-adds ggml's format requires (one per output element per 32 weights: 1 VALU operation per 32 MFMA multiply-accumulates on a chip whose matrix
 // pipe is 64 x wider than its vector pipe), not by the matrix cores (PMC, profiles/r02e_pmc_mmq2.txt: two waves per SIMD issue 84 % of the time, MFMA 9 % busy).
@@ -705,8 +707,9 @@ void launch_slab_reduce(const float *slabs, int n_slabs, long long slab_stride, 
     hipLaunchKernelGGL(k_mmq2_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, slabs, n_slabs, slab_stride, residual, y, n4);
 }
 
+static bool mmq2_is_q32(int type) { return type == GT_Q8_0 || type == GT_Q5_0 || type == GT_Q5_1 || type == GT_Q4_1; }   // the members of mmq2_q32.hip
 bool mmq2_supported(int type, int rows, int cols) {
-    return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0 || type == GT_IQ4_NL || type == GT_IQ4_XS) && cols % 256 == 0 && rows >= 32;
+    return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0 || type == GT_IQ4_NL || type == GT_IQ4_XS || mmq2_is_q32(type)) && cols % 256 == 0 && rows >= 32;
 }
 
 template <typename KernelT>
@@ -752,7 +755,8 @@ void launch_slab_flush(const SlabSrc &src, hipStream_t s) {
 }
 bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer, int force_ks) {
     if (defer) *defer = SlabSrc{};
-    if (n < 1 || n > 3 || N < 1 || (act_mask_for(W[0]->type) == ACT_Q80 ? !(A.q80 && A.d0) : !A.bsq)) return false;
+    const bool q81 = W[0]->type == GT_Q4_1 || W[0]->type == GT_Q5_1;   // Q8_1 rows: the values + d1 / s1 (the other Q8_0-row members: + d0)
+    if (n < 1 || n > 3 || N < 1 || (act_mask_for(W[0]->type) == ACT_Q80 ? !(A.q80 && (q81 ? A.d1 && A.s1 : A.d0 != nullptr)) : !A.bsq)) return false;
     for (int i = 0; i < n; i++) if (!mmq2_supported(W[i]->type, W[i]->rows, W[i]->cols) || W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false;
     Mmq2Args a{};
     for (int i = 0; i < n; i++) { a.w[i] = *W[i]; a.y[i] = y[i]; a.res[i] = residual ? residual[i] : nullptr; }
@@ -787,6 +791,7 @@ bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *cons
     // fast mode, Q4_K / Q5_K: the fp16-MFMA form (k_mmqh_q45k) whenever the activation rows carry their fp16 image; force_ks == 1 (parity mode: the oracle's fp32 order) keeps the int8 kernels
     const bool h16 = tune.mmqh && force_ks != 1 && (type == GT_Q4_K || type == GT_Q5_K) && A.q16 && A.bs16;
     if (type == GT_IQ4_NL || type == GT_IQ4_XS) launch_mmq2_iq4(type, grid, s, a, A);   // mmq2_iq4.hip; the K split above and the combine below are type-agnostic
+    else if (mmq2_is_q32(type)) launch_mmq2_q32(type, grid, s, a, A);                    // mmq2_q32.hip; sizes its own dynamic LDS (the _1 members' stage has a second scale plane)
     else switch (a.tiles_per_chunk) {
     case 1: mmq2_launch_tt<1>(type, grid, 2 * (q40 ? Mmq2Stage80<1>::BYTES : Mmq2Stage<1>::BYTES) + 16384, s, a, A, h16); break;
     case 2: mmq2_launch_tt<2>(type, grid, 2 * (q40 ? Mmq2Stage80<2>::BYTES : Mmq2Stage<2>::BYTES) + 16384, s, a, A, h16); break;
