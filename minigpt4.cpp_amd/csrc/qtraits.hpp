@@ -187,7 +187,7 @@ __device__ __forceinline__ void scale_min_pair(const int4 &h, int j, int &sc0, i
     const int sh = (j & 1) * 16;
     sc0 = (scw >> sh) & 0xFF; sc1 = (scw >> (sh + 8)) & 0xFF; m0 = (mw >> sh) & 0xFF; m1 = (mw >> (sh + 8)) & 0xFF;
 }
-template <> struct Tr<GT_Q2_K> {   // supported, not tuned: only the generic tile kernel k_mul_mat streams this type (no persistent-wave / MFMA path)
+template <> struct Tr<GT_Q2_K> {   // decode (1..4 rows): the generic tile kernel k_mul_mat only, no persistent-wave path; N >= 5 rows: k_mmq2_q2k (int8 MFMA, mmq2_q2k.hip)
     static constexpr int EPU = 32;
     struct WU { uint2 p; unsigned short sc; unsigned dm; };
     using AU = AK;

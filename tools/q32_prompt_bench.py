@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""What a prompt pass and a batched step cost on a 7B file whose 2-D weights are Q8_0, Q5_0, Q5_1 or Q4_1 (k_mmq2_q32, csrc/mmq2_q32.hip; before it: k_mul_mat<T, 2, 4>,
-one pass over the weights per four rows).  One JSON line per format: medians of --reps (>= 5) alternated runs with max - min behind them, every run printed.
+"""What a prompt pass and a batched step cost on a 7B file whose 2-D weights are Q8_0, Q5_0, Q5_1 or Q4_1 (k_mmq2_q32, csrc/mmq2_q32.hip) or Q2_K (--formats q2_k:
+k_mmq2_q2k, csrc/mmq2_q2k.hip); before those kernels: k_mul_mat<T, 2, 4>, one pass over the weights per four rows.
+One JSON line per format: medians of --reps (>= 5) alternated runs with max - min behind them, every run printed.
   p142 / p512   wall clock in ms of amd_eval_tokens + amd_logits around minigpt4_amd_sync for a 142-row (the image turn's size) and a 512-row prompt on an empty conversation
   b8            ms per step of 16 greedy amd_end_chat_batch steps of 8 conversations (short prompts evaluated beforehand)
 The files are synthetic (modelgen.headline_llm's conditioning, every 2-D tensor in the format); every run is a child process that loads the file, warms each measurement
 up once and measures it once.  With --parent-lib (a libminigpt4.so built from the parent commit) the runs alternate, parent first in each pair.
-    python tools/q32_prompt_bench.py [--formats q8_0,q5_0,q5_1,q4_1] [--reps 5] [--parent-lib PATH]        GPU only."""
+    python tools/q32_prompt_bench.py [--formats q8_0,q5_0,q5_1,q4_1 | q2_k] [--reps 5] [--parent-lib PATH]        GPU only."""
 import argparse
 import dataclasses
 import json
@@ -20,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import _pkg  # noqa: E402
 
-FTYPE = {"q8_0": 7, "q5_0": 8, "q5_1": 9, "q4_1": 3}
+FTYPE = {"q8_0": 7, "q5_0": 8, "q5_1": 9, "q4_1": 3, "q2_k": 10}
 MEASURES = ("p142", "p512", "b8")
 B, STEPS = 8, 16
 
