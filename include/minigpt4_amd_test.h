@@ -92,7 +92,7 @@ MINIGPT4_API int minigpt4_amd_test_slab_flush(int n, int mixed, const int32_t *m
 MINIGPT4_API int minigpt4_amd_test_rope_kv_slabs(int n_head, int hd, int n_ctx, int N, int pos0, const int32_t *mks, const float *slabs, int64_t stride, const float *v_in_place,
                                                  float *q_out, uint16_t *kc, uint16_t *vc);
 /* The embedding gather alone (k_get_rows: the per-element decoder of every weight type), ONE launch_get_rows.  raw_table: n_rows rows of K weights as a model file stores
- * them (Q3_K rows are re-encoded as Q6_K first, as the engine's load path does); tokens[N] in [-1, n_rows).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard
+ * them; tokens[N] in [-1, n_rows).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard
  * row; a token of -1 leaves its row at the fill.  1 = bad arguments, before any device is touched (a NULL pointer, a token outside [-1, n_rows), a K that is not a whole
  * number of blocks, an unknown type); 2 = no device; 3 = HIP error */
 MINIGPT4_API int minigpt4_amd_test_get_rows(int ggml_type, const void *raw_table, int n_rows, int64_t K, const int32_t *tokens, int N, float *out);
@@ -455,7 +455,7 @@ MINIGPT4_API int64_t minigpt4_amd_quantize_chunk(int ggml_type, const float *x, 
 MINIGPT4_API int minigpt4_amd_timeline(unsigned long long *out, int max_workgroups);
 /* The same builds: one further stamp per workgroup of that launch, taken when a prologue form has issued its row loads (in front of the first weight request). */
 MINIGPT4_API int minigpt4_amd_timeline_rows(unsigned long long *out, int max_workgroups);
-/* load-time re-encoding of Q3_K super-blocks (110 B) as value-identical Q6_K super-blocks (210 B); host only.  0 / 1 */
+/* re-encoding of Q3_K super-blocks (110 B) as value-identical Q6_K super-blocks (210 B), as the generic vision path does at load (the language model streams Q3_K natively); host only.  0 / 1 */
 MINIGPT4_API int minigpt4_amd_convert_q3k_q6k(const void *src, void *dst, int64_t n_blocks);
 /* The LoRA kernels alone (k_lora_down + k_lora_up of lora.hip, one target): rows <= 64, row i uses adapter row_adapter[i] (-1: none) of n_adapters <= 2 with A [rank][n_in],
  * B [n_out][rank] given as fp16 bits back to back and factors s[a].  mode 0: x as it is; 1: RMS norm of x with weight second [n_in]; 2: silu(x) * second [rows][n_in].

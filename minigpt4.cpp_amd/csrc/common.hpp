@@ -63,16 +63,17 @@ template <typename K> inline hipError_t lds_optin_max(K kernel) {
 // A "unit" is 16 bytes of the main quant plane = what one lane fetches with one dwordx4 load:
 //   Q4_0/Q4_1/Q5_0/Q5_1 : 1 unit = 1 block (32 weights)        Q8_0 : 1 unit = half a block (16 weights)
 //   Q4_K/Q5_K/Q6_K      : 1 unit = 32 weights (8 units / super-block)
+//   Q2_K/Q3_K           : 1 unit = 32 consecutive weights = two 16-weight sub-blocks, 8 bytes of the 2-bit plane (8 units / super-block)
 //   IQ4_NL : 1 unit = 1 block (as Q4_0)                        IQ4_XS : 1 unit = 32 weights in element order (8 units / super-block)
 //   F16 : 8 weights, F32 : 4 weights
 struct QWeight {
     int type = -1;
     int rows = 0, cols = 0;          // n_out, n_in
     const uint8_t *qs = nullptr;     // main plane  [rows][units][16]
-    const uint8_t *qh = nullptr;     // high-bit plane, pre-transposed for v_dot4: Q5_*: 4 B/unit, Q6_K: 8 B/unit
+    const uint8_t *qh = nullptr;     // high-bit plane, pre-transposed for v_dot4: Q5_*: 4 B/unit, Q6_K: 8 B/unit, Q3_K: 4 B/unit (the hmask bit)
     const uint8_t *sc = nullptr;     // scale plane: Q4_0/Q5_0/Q8_0: f16 d per block; Q4_1/Q5_1: {d,m}; Q4_K/Q5_K: 16 B {d,dmin,scales12} per
                                      //   super-block; Q6_K: 2 int8 per unit; IQ4_NL: f16 d per block; IQ4_XS: 16 B {d, -, ls_0..7 - 32 as int8} per super-block
-    const uint8_t *d = nullptr;      // Q6_K: f16 d per super-block
+    const uint8_t *d = nullptr;      // Q6_K, Q3_K: f16 d per super-block; Q2_K: {d, dmin}
     size_t bytes = 0;                // HBM bytes of all planes (== file bytes of the tensor)
 };
 
@@ -101,7 +102,7 @@ struct ActQ {
 };
 enum ActMask : int { ACT_Q8K = 1, ACT_Q80 = 2, ACT_F16 = 4, ACT_F32 = 8 };
 __host__ __device__ inline int act_mask_for(int wtype) {
-    switch (wtype) { case GT_Q4_0: case GT_Q5_0: case GT_Q8_0: case GT_Q4_1: case GT_Q5_1: case GT_IQ4_NL: return ACT_Q80; case GT_Q2_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_XS: return ACT_Q8K;
+    switch (wtype) { case GT_Q4_0: case GT_Q5_0: case GT_Q8_0: case GT_Q4_1: case GT_Q5_1: case GT_IQ4_NL: return ACT_Q80; case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_XS: return ACT_Q8K;
         case GT_F16: return ACT_F16; case GT_F32: return ACT_F32; default: return 0; }
 }
 

@@ -326,22 +326,11 @@ int Engine::plan_arenas(const std::string &vision_path, const std::string &llm_p
     return 0;
 }
 
-// Tensor types the kernels do not stream natively but that have an exact image in one they do: Q3_K -> Q6_K (quantize.hpp).  The conversion runs on
-// the host at load.
-static int effective_type(int t) { return t == GT_Q3_K ? GT_Q6_K : t; }
-static bool tensor_type_loadable(int t) { return qweight_supported(effective_type(t)); }
-// bytes of a tensor as the GPU holds it
-static size_t effective_nbytes(const TensorMeta &t) { return t.type == GT_Q3_K ? t.nbytes / 110 * 210 : t.nbytes; }
+// The generic vision path (engine_vision_generic.cpp, not a hot path) holds a Q3_K tensor as its value-identical Q6_K image (quantize.hpp), converted on the host at load:
+// bytes of a vision tensor as the GPU holds it.  The language model streams Q3_K natively (plan_qweight: 114 bytes per 256 weights).
+static size_t vision_nbytes(const TensorMeta &t) { return t.type == GT_Q3_K ? t.nbytes / 110 * 210 : t.nbytes; }
 
-void Engine::upload_qweight(const TensorMeta &t0, const uint8_t *file_base0, QWeight &w) {
-    TensorMeta t = t0;
-    const uint8_t *file_base = file_base0;
-    std::vector<uint8_t> conv;
-    if (t0.type == GT_Q3_K) {
-        conv.resize(moves_data() ? effective_nbytes(t0) : 0);
-        if (moves_data()) q3k_to_q6k(file_base0 + t0.offset, conv.data(), t0.nbytes / 110);
-        t.type = GT_Q6_K; t.nbytes = effective_nbytes(t0); t.offset = 0; file_base = conv.data();
-    }
+void Engine::upload_qweight(const TensorMeta &t, const uint8_t *file_base, QWeight &w) {
     const int cols = (int)t.ne[0], rows = (int)t.ne[1];
     QWeight plan;
     const size_t need = plan_qweight(t.type, rows, cols, plan, nullptr);
@@ -377,7 +366,7 @@ int Engine::load_llm(const std::string &path) {
         if (!t) { set_last_error("LLM file: missing tensor " + name); return nullptr; }
         if (t->ne[0] != ne0 || (ne1 ? (t->ne.size() != 2 || t->ne[1] != ne1) : t->ne.size() != 1)) { set_last_error("LLM file: bad shape for " + name); return nullptr; }
         if (ne1 == 0 && t->type != GT_F32) { set_last_error("LLM file: " + name + " must be f32"); return nullptr; }
-        if (ne1 && !tensor_type_loadable(t->type)) { set_last_error(std::string("LLM file: tensor type ") + gt_name(t->type) + " of " + name + " is not supported by the gfx950 kernels"); return nullptr; }
+        if (ne1 && !qweight_supported(t->type)) { set_last_error(std::string("LLM file: tensor type ") + gt_name(t->type) + " of " + name + " is not supported by the gfx950 kernels"); return nullptr; }
         return t;
     };
     // pass 1: validate + size the arena
@@ -396,14 +385,14 @@ int Engine::load_llm(const std::string &path) {
     for (auto &m : mats) {
         const TensorMeta *t = need(m.first, m.second.first, m.second.second);
         if (!t) { MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
-        total += plan_qweight(effective_type(t->type), (int)t->ne[1], (int)t->ne[0], tmp, nullptr) + 256;
-        if (t->type != GT_F16 && t->type != GT_F32) max_raw = std::max(max_raw, effective_nbytes(*t));
-        wbytes_token_ += effective_nbytes(*t);                             // what a decoded token streams from HBM
+        total += plan_qweight(t->type, (int)t->ne[1], (int)t->ne[0], tmp, nullptr) + 256;
+        if (t->type != GT_F16 && t->type != GT_F32) max_raw = std::max(max_raw, t->nbytes);
+        wbytes_token_ += t->nbytes;                             // what a decoded token streams from HBM
     }
     const TensorMeta *tt = llm_.find("tok_embeddings.weight");
-    if (!tt || tt->ne.size() != 2 || tt->ne[0] != E || tt->ne[1] != V || !tensor_type_loadable(tt->type)) { set_last_error("LLM file: bad tok_embeddings.weight"); MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
-    total += effective_nbytes(*tt) + 256;
-    wbytes_token_ += gt_nbytes(effective_type(tt->type), (size_t)E);
+    if (!tt || tt->ne.size() != 2 || tt->ne[0] != E || tt->ne[1] != V || !qweight_supported(tt->type)) { set_last_error("LLM file: bad tok_embeddings.weight"); MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
+    total += tt->nbytes + 256;
+    wbytes_token_ += gt_nbytes(tt->type, (size_t)E);
     for (int i = 0; i < L; i++) for (const char *n : {"attention_norm.weight", "ffn_norm.weight"}) if (!need("layers." + std::to_string(i) + "." + n, E, 0)) { MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
     if (!need("norm.weight", E, 0)) { MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
     total += (size_t)(2 * L + 1) * ((size_t)E * 4 + 256);
@@ -430,12 +419,8 @@ int Engine::load_llm(const std::string &path) {
     }
     const TensorMeta *nt = llm_.find("norm.weight");
     norm_ = upload_raw<float>(llm_arena_, fb + nt->offset, nt->nbytes);
-    if (tt->type == GT_Q3_K) {   // the embedding gather dequantises raw ggml rows: give it the (value-identical) Q6_K rows
-        std::vector<uint8_t> conv(moves_data() ? effective_nbytes(*tt) : 0);
-        if (moves_data()) q3k_to_q6k(fb + tt->offset, conv.data(), tt->nbytes / 110);
-        tok_raw_ = upload_raw<uint8_t>(llm_arena_, conv.data(), effective_nbytes(*tt));
-    } else tok_raw_ = upload_raw<uint8_t>(llm_arena_, fb + tt->offset, tt->nbytes);
-    tok_type_ = effective_type(tt->type);
+    tok_raw_ = upload_raw<uint8_t>(llm_arena_, fb + tt->offset, tt->nbytes);   // the embedding gather dequantises raw ggml rows (dequant_elem)
+    tok_type_ = tt->type;
     MG4_INFO("llm weights: %.1f MB in HBM, %.3f GB streamed per decoded token", llm_arena_.used / 1048576.0, wbytes_token_ / 1e9);
     return E_None;
 }
@@ -483,7 +468,7 @@ int Engine::load_vision(const std::string &path) {
         if (is_lin && tm.type != GT_F16) v_generic_ = true;
     }
     size_t total = 0;
-    for (auto &m : vis_.models) for (auto &t : m.second) total += effective_nbytes(t.second) + 512 + (v_generic_ ? 2048 : 0);
+    for (auto &m : vis_.models) for (auto &t : m.second) total += vision_nbytes(t.second) + 512 + (v_generic_ ? 2048 : 0);
     total += (size_t)v_D_ * 592 * 2 + (size_t)v_depth_ * 3 * v_D_ * 4 + (1 << 20);
     vis_arena_.alloc(total);
     const uint8_t *fb = vis_.mf.data;

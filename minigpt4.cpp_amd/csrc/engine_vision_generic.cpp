@@ -27,7 +27,7 @@ int Engine::load_vision_generic() {
         if (bad_code) return;
         const TensorMeta *t = vis_.find(model, name);
         if (!t || t->ne.size() != 2 || t->ne[0] != n_in || t->ne[1] != n_out) { bad = model + "." + name; bad_code = E_LoadModelFileHeader; return; }
-        const int wt = t->type == GT_Q3_K ? GT_Q6_K : t->type;                  // Q3_K: exact Q6_K image built on the host (quantize.hpp), like the LLM loader
+        const int wt = t->type == GT_Q3_K ? GT_Q6_K : t->type;                  // Q3_K: exact Q6_K image built on the host (quantize.hpp); the language model streams Q3_K natively
         if (!qweight_supported(wt) || n_in % gt_block(t->type)) {
             bad = model + "." + name + ": type " + gt_name(t->type) + " with " + std::to_string(n_in) + " columns is not supported by the gfx950 kernels"; bad_code = E_LoadModelMiniGPT4DataType; return; }
         QWeight plan;

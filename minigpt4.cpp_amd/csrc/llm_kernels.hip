@@ -90,6 +90,9 @@ size_t plan_qweight(int type, int rows, int cols, QWeight &w, uint8_t *base) {
     case GT_Q5_1: w.qs = take(n / 32 * 16); w.qh = take(n / 32 * 4); w.sc = take(n / 32 * 4); break;
     case GT_Q8_0: w.qs = take(n / 32 * 32); w.sc = take(n / 32 * 2); break;
     case GT_Q2_K: w.qs = take(n / 32 * 8); w.sc = take(n / 32 * 2); w.d = take(n / 256 * 4); break;   // unit = 32 consecutive weights = two 16-weight sub-blocks: 2-bit planes, {scale | min << 4} x 2, {d, dmin} per super-block
+    // Q3_K, 114 bytes per 256 weights: unit = 32 consecutive weights as for Q2_K -- the low 2 bits in Q2_K's arrangement, the hmask bit transposed like a 5-bit type's
+    // high bit (pack_hb1), the two sub-block scales as int8 = 6-bit code - 32 (the file's 12-byte packing is undone here, once), d per super-block
+    case GT_Q3_K: w.qs = take(n / 32 * 8); w.qh = take(n / 32 * 4); w.sc = take(n / 32 * 2); w.d = take(n / 256 * 2); break;
     case GT_Q4_K: w.qs = take(n / 256 * 128); w.sc = take(n / 256 * 16); break;
     case GT_Q5_K: w.qs = take(n / 256 * 128); w.qh = take(n / 256 * 32); w.sc = take(n / 256 * 16); break;
     case GT_Q6_K: w.qs = take(n / 256 * 128); w.qh = take(n / 256 * 64); w.sc = take(n / 256 * 16); w.d = take(n / 256 * 2); break;
@@ -101,7 +104,7 @@ size_t plan_qweight(int type, int rows, int cols, QWeight &w, uint8_t *base) {
     return off;
 }
 bool qweight_supported(int type) {
-    switch (type) { case GT_F32: case GT_F16: case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q8_0: case GT_Q2_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_NL: case GT_IQ4_XS: return true; default: return false; }
+    switch (type) { case GT_F32: case GT_F16: case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q8_0: case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_NL: case GT_IQ4_XS: return true; default: return false; }
 }
 
 // high-bit transposition for 5-bit types: element e of 32 (lo: e<16 -> dword k=e/4, byte i=e%4, slot w=k; hi: e>=16 -> w=4+k)
@@ -140,6 +143,20 @@ __global__ void k_repack(const uint8_t *__restrict__ raw, QWeight w, size_t n_un
             P0 |= (((unsigned)b[16 + 32 * n + e] >> (2 * j)) & 3u) << (8 * c + 2 * k); P1 |= (((unsigned)b[16 + 32 * n + 16 + e] >> (2 * j)) & 3u) << (8 * c + 2 * k); }
         reinterpret_cast<unsigned *>(qs + g * 8)[0] = P0; reinterpret_cast<unsigned *>(qs + g * 8)[1] = P1;
         sc[g * 2] = b[2 * i]; sc[g * 2 + 1] = b[2 * i + 1];
+        break; }
+    case GT_Q3_K: {   // block_q3_K = hmask[32] | qs[64] | scales[12] | d; element 128 n + 32 j + l = ((qs[32 n + l] >> 2 j) & 3) + 4 * (hmask[l] bit 4 n + j) - 4, scale 8 n + 2 j + l / 16
+        const size_t sb = g >> 3; const int i = (int)(g & 7), n = i >> 2, j = i & 3; const uint8_t *b = raw + sb * 110;
+        if (i == 0) { dd[sb * 2] = b[108]; dd[sb * 2 + 1] = b[109]; }
+        unsigned P0 = 0, P1 = 0;   // as Q2_K's
+        unsigned char lo[16], hi[16];
+        for (int e = 0; e < 16; e++) { const int k = e >> 2, c = e & 3;
+            P0 |= (((unsigned)b[32 + 32 * n + e] >> (2 * j)) & 3u) << (8 * c + 2 * k); P1 |= (((unsigned)b[32 + 32 * n + 16 + e] >> (2 * j)) & 3u) << (8 * c + 2 * k);
+            lo[e] = (b[e] >> (4 * n + j)) & 1; hi[e] = (b[16 + e] >> (4 * n + j)) & 1; }
+        reinterpret_cast<unsigned *>(qs + g * 8)[0] = P0; reinterpret_cast<unsigned *>(qs + g * 8)[1] = P1;
+        *reinterpret_cast<unsigned *>(qh + g * 4) = pack_hb1(lo, hi);
+        for (int h = 0; h < 2; h++) {   // scale s = 2 i + h of sixteen: low nibble in scales[s & 7] (the upper nibble from s = 8 on), high 2 bits in scales[8 + (s & 3)] at 2 (s >> 2)
+            const int s = 2 * i + h, lo4 = s < 8 ? (b[96 + s] & 15) : (b[96 + s - 8] >> 4), hi2 = (b[104 + (s & 3)] >> (2 * (s >> 2))) & 3;
+            sc[g * 2 + h] = (uint8_t)(signed char)((lo4 | (hi2 << 4)) - 32); }
         break; }
     case GT_Q4_K: { const size_t sb = g >> 3; const int u = (int)(g & 7); const uint8_t *b = raw + sb * 144;
         if (u == 0) for (int i = 0; i < 16; i++) sc[sb * 16 + i] = b[i];
@@ -258,6 +275,11 @@ template <int... NU> struct UnitList {};
 using Units1to7 = UnitList<1, 2, 3, 4, 5, 6, 7>;
 using Units1to3 = UnitList<1, 2, 3>;
 template <int T> constexpr bool tr_is_kquant() { return T == GT_Q4_K || T == GT_Q5_K || T == GT_Q6_K || T == GT_IQ4_XS; }   // 8 units per 256-weight super-block, Q8_K rows
+// Q3_K (8 units per super-block, Q8_K rows, like the k-quants above) is built for launches WITHOUT an in-launch row preparation only: its rows come from k_rms_quant /
+// k_silu_mul_quant in front of the mat-vec, which Engine::mul_mat_set does for every shape a predicate below refuses.  It therefore has entries of its own in the
+// prologue-free unit lists (mv_free_units, mv_tn_units, the oracle-order row kernels) and none in tr_is_kquant(), from which the three predicates are computed.
+// Preparation fused into a Q3_K launch is a follow-up; it has to change tests/test_cpu_matvec_dispatch.py, which lists q3_k among the types the predicates refuse.
+template <int T> constexpr bool tr_reads_q8k() { return tr_is_kquant<T>() || T == GT_Q3_K; }   // the activation unit is an AK of the Q8_K planes
 template <int T> constexpr bool tr_is_q32() { return T == GT_Q4_0 || T == GT_Q4_1 || T == GT_Q5_0 || T == GT_Q5_1 || T == GT_IQ4_NL; }
 template <int T> constexpr bool tr_is_narrow() { return T == GT_Q8_0 || T == GT_F16; }   // 16-byte units of 16 / 8 weights: more units per row than the 32-weight types
 // k_matvec_v2<T, NU, R, PRO, EPI>.  Q8_0 / F16: only a few unit counts, a row takes the smallest one that covers it (the surplus units are masked like any ragged
@@ -270,6 +292,11 @@ template <int T, int EPI> constexpr auto mv_units() {
     else if constexpr (tr_is_q32<T>()) return std::conditional_t<EPI == EPI_SILU_PAIR, Units1to3, std::conditional_t<EPI == EPI_STORE, Units1to7, UnitList<>>>{};
     else return UnitList<>{};
 }
+// k_matvec_v2_free<T, NU, R, EPI>: what mv_units has, and Q3_K's store form
+template <int T, int EPI> constexpr auto mv_free_units() {
+    if constexpr (T == GT_Q3_K) return std::conditional_t<EPI == EPI_STORE, Units1to7, UnitList<>>{};
+    else return mv_units<T, EPI>();
+}
 template <int T, int NU, int EPI> constexpr int mv_rows_per_group() {   // R: rows a wave has in flight per stage
     if (EPI == EPI_SILU_PAIR) return 2;
     if (EPI == EPI_REF) return 1;
@@ -278,7 +305,7 @@ template <int T, int NU, int EPI> constexpr int mv_rows_per_group() {   // R: ro
 }
 using MixUnits = UnitList<1, 2, 3, 4>;          // k_matvec_mix<T1, T2, NU, ..>
 // k_matvec_tn<T, NU, TN, PRO> (TN = 2..4 rows): every unit count without a preparation, K <= 6144 of Q4_0 and the k-quants with one; k_matvec_tn_mix: K <= 6144
-template <int T> constexpr auto mv_tn_units() { return std::conditional_t<tr_is_kquant<T>() || tr_is_q32<T>(), Units1to7, UnitList<>>{}; }
+template <int T> constexpr auto mv_tn_units() { return std::conditional_t<tr_reads_q8k<T>() || tr_is_q32<T>(), Units1to7, UnitList<>>{}; }
 template <int T> constexpr auto mv_tn_pro_units() { return std::conditional_t<T == GT_Q4_0 || T == GT_IQ4_NL || tr_is_kquant<T>(), Units1to3, UnitList<>>{}; }
 using TnMixUnits = Units1to3;
 using RefRowUnits = UnitList<1, 2, 3, 4, 6, 7>;  // k_mul_mat_ref_row / k_mul_mat_ref_rows (the 7B / 13B widths)
@@ -301,6 +328,7 @@ template <class F> static bool for_weight_type(int type, F &&f) {
     case GT_Q5_1: return f(std::integral_constant<int, GT_Q5_1>{});
     case GT_Q8_0: return f(std::integral_constant<int, GT_Q8_0>{});
     case GT_Q2_K: return f(std::integral_constant<int, GT_Q2_K>{});
+    case GT_Q3_K: return f(std::integral_constant<int, GT_Q3_K>{});
     case GT_Q4_K: return f(std::integral_constant<int, GT_Q4_K>{});
     case GT_Q5_K: return f(std::integral_constant<int, GT_Q5_K>{});
     case GT_Q6_K: return f(std::integral_constant<int, GT_Q6_K>{});
@@ -461,9 +489,9 @@ bool launch_mul_mat_ref_set(const QWeight *const *W, float *const *y, const floa
     if (n < 1 || n > 3) return false;
     RefSet S{}; S.n = n;
     for (int i = 0; i < n; i++) { if (W[i]->type != W[0]->type || W[i]->rows != W[0]->rows || W[i]->cols != W[0]->cols) return false; S.w[i] = *W[i]; S.y[i] = y[i]; S.res[i] = res ? res[i] : nullptr; }
-    return for_weight_type(W[0]->type, [&](auto t) {   // (Q8_0 / Q2_K / F16 / F32 rows have other unit widths: the generic kernel serves them)
+    return for_weight_type(W[0]->type, [&](auto t) {   // (Q8_0 / F16 / F32 rows have other unit widths, Q2_K has no persistent-wave form: the generic kernel serves them)
         constexpr int T = decltype(t)::value;
-        if constexpr (tr_is_q32<T>() || tr_is_kquant<T>()) return launch_mul_mat_ref_row_t<T>(S, A, tune, s); else return false;
+        if constexpr (tr_is_q32<T>() || tr_reads_q8k<T>()) return launch_mul_mat_ref_row_t<T>(S, A, tune, s); else return false;
     });
 }
 // Prompt rows in parity mode: one wave per WEIGHT row (persistent over rows wave, wave + n_waves, ...), the row's units in registers for all N activation rows -- the
@@ -514,7 +542,7 @@ void launch_mul_mat_ref(const QWeight &W, const ActQ &A, int N, float *y, int ld
     // prompt rows: the weight row stays in registers for all N activation rows (k-quants; the other types and unit counts take the generic kernel)
     if (N > 1 && for_weight_type(W.type, [&](auto t) {
             constexpr int T = decltype(t)::value;
-            if constexpr (tr_is_kquant<T>()) return launch_mul_mat_ref_rows_t<T>(W, A, N, y, ldy, residual, tune, s); else return false; })) return;
+            if constexpr (tr_reads_q8k<T>()) return launch_mul_mat_ref_rows_t<T>(W, A, N, y, ldy, residual, tune, s); else return false; })) return;
     if (!for_weight_type(W.type, [&](auto t) { launch_mul_mat_ref_t<decltype(t)::value>(W, A, N, y, ldy, residual, s); return true; }))
         throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
 }
@@ -604,7 +632,7 @@ template <int T, int PRO, int EPI>
 __device__ __forceinline__ void mv_pin_tail(const MatSet &ms, const ActQ &A, const Tables &tb) {
     asm volatile("" ::"s"(ms.w0.qs), "s"(ms.w0.qh), "s"(ms.w0.sc), "s"(ms.w0.d), "s"(ms.dmat), "s"(ms.y0), "s"(ms.dy), "s"(ms.res0), "s"(ms.dres), "s"(ms.n), "s"(ms.rows_each));
     if (PRO == PRO_SILU || EPI == EPI_SILU_PAIR) asm volatile("" ::"s"(tb.silu));
-    if (PRO == PRO_NONE && tr_is_kquant<T>()) asm volatile("" ::"s"(A.q8k), "s"(A.dk), "s"(A.bsk));
+    if (PRO == PRO_NONE && tr_reads_q8k<T>()) asm volatile("" ::"s"(A.q8k), "s"(A.dk), "s"(A.bsk));
 }
 template <int T, int NU, int R, int PRO, int EPI, bool IB = false>
 __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, const ProArgs &pa, const int n_groups, const int n_waves, const int wave, const int nthr) {
@@ -654,7 +682,7 @@ __device__ __forceinline__ void matvec_run(const MatSet &ms, const ActQ &A, cons
         L.xh = reinterpret_cast<__half *>(smem_mv + 128);                // F16 weights: the fp16 row takes the place of the two int8 images (2 K bytes)
         L.xf = nullptr;
         constexpr int RND = (NU * 64 * X::EPU / 4 + MV_FAT_MIN - 1) / MV_FAT_MIN;    // K <= NU * 64 * EPU elements, 4 per thread per round, >= MV_FAT_MIN threads
-        constexpr int mask = T == GT_F16 ? ACT_F16 : tr_is_kquant<T>() ? ACT_Q8K : ACT_Q80;
+        constexpr int mask = T == GT_F16 ? ACT_F16 : tr_reads_q8k<T>() ? ACT_Q8K : ACT_Q80;
         float4 xv[RND], yv[RND];
         bool in[RND];
 #pragma unroll
@@ -821,18 +849,22 @@ static void launch_v2_pro(bool issue_bar, dim3 grid, dim3 block, size_t lds, hip
     hipLaunchKernelGGL((k_matvec_v2<T, NU, R, PRO, EPI>), grid, block, lds, s, pa.x, pa.w, ms.w0.cols, (int)block.x, n_groups, n_waves, ms, A, pa.tb);
 }
 template <int T, int NU, int R, int EPI>
+static void launch_v2_free_t(const MatSet &ms, const ActQ &A, const ProArgs &pa, const LaunchTuning &tune, hipStream_t s) {   // the rows were prepared by a launch of their own
+    const int total_rows = ms.n * ms.rows_each;
+    const int n_groups = EPI == EPI_SILU_PAIR ? ms.rows_each : (total_rows + R - 1) / R;
+    note_kernel("k_matvec_v2_free<%d, %d, %d, %d>", T, NU, R, (int)EPI);
+    // EPI_REF: the block chain is a dependent sequence per wave (DPP move + fma per block): as many waves per SIMD as the registers admit, not the stream-optimal 8 per CU
+    // Q3_K (unless the tuning names a count): likewise.  Measured, 7B Q3_K decode step: 1.651 ms at 8 waves per CU, 1.612 at the register limit, the Q6_K image before
+    // 1.633 (profiles/q3k_native.md).  Supposed, not traced: at 14 bytes per unit the launch waits on its dependent v_dot4 chains, not on the stream
+    int n_waves = std::min(n_groups, tune.cus * (EPI == EPI_REF || (T == GT_Q3_K && !tune.mv_waves_per_cu) ? mv_max_wpc<NU>() : pick_waves_per_cu(tune, mv_max_wpc<NU>())));
+    n_waves = (n_waves + 3) & ~3;
+    hipLaunchKernelGGL((k_matvec_v2_free<T, NU, R, EPI>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, ms.w0.qs, ms.w0.qh, ms.w0.sc, ms.w0.d, A.q8k, ms.w0.cols, ms.rows_each,
+                       n_groups, n_waves, ms, A, pa.tb);
+}
+template <int T, int NU, int R, int EPI>
 static void launch_v2_t(const MatSet &ms, const ActQ &A, int pro, const ProArgs &pa, bool issue_bar, const LaunchTuning &tune, hipStream_t s) {
     const int total_rows = ms.n * ms.rows_each;
     const int n_groups = EPI == EPI_SILU_PAIR ? ms.rows_each : (total_rows + R - 1) / R;
-    if (pro == PRO_NONE) {
-        note_kernel("k_matvec_v2_free<%d, %d, %d, %d>", T, NU, R, (int)EPI);
-        // EPI_REF: the block chain is a dependent sequence per wave (DPP move + fma per block): as many waves per SIMD as the registers admit, not the stream-optimal 8 per CU
-        int n_waves = std::min(n_groups, tune.cus * (EPI == EPI_REF ? mv_max_wpc<NU>() : pick_waves_per_cu(tune, mv_max_wpc<NU>())));
-        n_waves = (n_waves + 3) & ~3;
-        hipLaunchKernelGGL((k_matvec_v2_free<T, NU, R, EPI>), dim3((unsigned)(n_waves / 4)), dim3(256), 0, s, ms.w0.qs, ms.w0.qh, ms.w0.sc, ms.w0.d, A.q8k, ms.w0.cols, ms.rows_each,
-                           n_groups, n_waves, ms, A, pa.tb);
-        return;
-    }
     const int LB = EPI == EPI_REF ? mv_fat_max_threads<NU>() : MV_FAT_MIN, WPB = LB / 64;
     const int n_blocks = std::min((n_groups + WPB - 1) / WPB, tune.cus);
     const int n_waves = n_blocks * WPB;
@@ -852,6 +884,9 @@ static bool launch_v2_type(const MatSet &ms, const ActQ &A, int pro, const ProAr
     const int nu = (ms.w0.cols / TrMV<T>::EPU + 63) / 64;
     auto launch = [&](auto e) {
         constexpr int EPI = decltype(e)::value;
+        if (pro == PRO_NONE) return mv_for_units<tr_is_narrow<T>()>(mv_free_units<T, EPI>(), nu, [&](auto n) {
+            constexpr int NU = decltype(n)::value;
+            launch_v2_free_t<T, NU, mv_rows_per_group<T, NU, EPI>(), EPI>(ms, A, pa, tune, s); });
         return mv_for_units<tr_is_narrow<T>()>(mv_units<T, EPI>(), nu, [&](auto n) {
             constexpr int NU = decltype(n)::value;
             launch_v2_t<T, NU, mv_rows_per_group<T, NU, EPI>(), EPI>(ms, A, pro, pa, issue_bar, tune, s); });
@@ -960,7 +995,7 @@ bool launch_matvec_set(const QWeight *const *W, float *const *y, const float *co
     ProArgs pa{}; pa.x = px; pa.w = pw; if (tb) pa.tb = *tb;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
-    // false: F32 / Q2_K rows, and rows wider than the type's unit counts (served by k_mul_mat)
+    // false: F32 / Q2_K rows, a Q3_K launch that would prepare its row, and rows wider than the type's unit counts (served by k_mul_mat)
     return for_weight_type(W[0]->type, [&](auto t) { return launch_v2_type<decltype(t)::value>(ms, A, pro, pa, epi, issue_bar, tune, s); });
 }
 
@@ -1032,7 +1067,7 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
     constexpr bool REG = mv_tn_reg<NU, TN>();
     typename X::AU ar[REG ? TN : 1][REG ? NU : 1];
     if (REG && PRO) {
-        constexpr int mask = tr_is_kquant<T>() ? ACT_Q8K : ACT_Q80;
+        constexpr int mask = tr_reads_q8k<T>() ? ACT_Q8K : ACT_Q80;
         double *red = reinterpret_cast<double *>(smem_tn);               // [TN][8 waves]
         if (PRO == 1) {
 #pragma unroll
@@ -1098,7 +1133,7 @@ __device__ __forceinline__ void matvec_tn_run(const MatSet &ms, const ActQ &A, c
             const size_t n16 = bytes / 16;
             for (size_t i = n16 * 16 + (size_t)tid; i < bytes; i += (size_t)nthr) reinterpret_cast<unsigned char *>(dst)[i] = reinterpret_cast<const unsigned char *>(src)[i];
         };
-        if (tr_is_kquant<T>()) {
+        if (tr_reads_q8k<T>()) {
             L.q8k = reinterpret_cast<int8_t *>(p); p += (size_t)TN * K;
             L.dk = reinterpret_cast<float *>(p); p += (size_t)TN * (K / 256) * 4;
             L.bsk = reinterpret_cast<int16_t *>(p);
@@ -1212,7 +1247,7 @@ static bool launch_tn_type(const MatSet &ms, const ActQ &A, int N, int ldy, cons
 // false -> shape / type outside the kernel's range (the caller falls back to launch_mul_mat per matrix).
 bool launch_matvec_rows(const QWeight *const *W, float *const *y, const float *const *residual, int n, const ActQ &A, int N, int ldy, const LaunchTuning &tune, hipStream_t s, const float *px, const float *pw, int ldx) {
     if (px && !matvec_rows_prologue_ok(W[0]->type, W[0]->cols)) return false;
-    if (N < 1 || N > 4 || !matvec_prologue_supported(W[0]->type, W[0]->cols)) return false;
+    if (N < 1 || N > 4 || !for_weight_type(W[0]->type, [&](auto t) { return mv_covers(mv_tn_units<decltype(t)::value>(), W[0]->type, W[0]->cols); })) return false;
     if (mv_tn_lds(W[0]->type, W[0]->cols, 4) > 150 * 1024) return false;
     MatSet ms;
     if (!fill_matset(ms, W, y, residual, n)) return false;
@@ -1401,6 +1436,9 @@ __device__ float dequant_elem(int type, const uint8_t *row, int e) {
     case GT_Q2_K: { const uint8_t *b = row + (e >> 8) * 84; const int i = e & 255, n = i >> 7, j = (i >> 5) & 3, l = i & 31; const uint8_t sc = b[i >> 4];
         const float d = h2f_bits(b[80] | (b[81] << 8)), dm = h2f_bits(b[82] | (b[83] << 8)); const float dl = d * (float)(sc & 0xF), ml = dm * (float)(sc >> 4);
         return dl * (float)((b[16 + 32 * n + l] >> (2 * j)) & 3) - ml; }
+    case GT_Q3_K: { const uint8_t *b = row + (e >> 8) * 110; const int i = e & 255, n = i >> 7, j = (i >> 5) & 3, l = i & 31, s = i >> 4; const float d = h2f_bits(b[108] | (b[109] << 8));
+        const int sc = ((s < 8 ? (b[96 + s] & 15) : (b[96 + s - 8] >> 4)) | (((b[104 + (s & 3)] >> (2 * (s >> 2))) & 3) << 4)) - 32;
+        const int q = (int)((b[32 + 32 * n + l] >> (2 * j)) & 3) - (((b[l] >> (4 * n + j)) & 1) ? 0 : 4); return d * (float)sc * (float)q; }   // exact: 11 + 6 + 3 bits
     case GT_Q4_K: { const uint8_t *b = row + (e >> 8) * 144; const int i = e & 255, s = i >> 5, l = i & 31; const float d = h2f_bits(b[0] | (b[1] << 8)), dm = h2f_bits(b[2] | (b[3] << 8)); int sc, m; sm_k4(s, b + 4, sc, m);
         const uint8_t qb = b[16 + (s >> 1) * 32 + l]; const int q = (s & 1) ? (qb >> 4) : (qb & 15); return (d * sc) * (float)q - dm * m; }
     case GT_Q5_K: { const uint8_t *b = row + (e >> 8) * 176; const int i = e & 255, s = i >> 5, l = i & 31; const float d = h2f_bits(b[0] | (b[1] << 8)), dm = h2f_bits(b[2] | (b[3] << 8)); int sc, m; sm_k4(s, b + 4, sc, m);

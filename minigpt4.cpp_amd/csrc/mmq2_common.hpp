@@ -1,4 +1,4 @@
-// What the kernels of the generation-2 prompt mat-mul family share (mmq2_kernels.hip: k-quants and Q4_0; mmq2_iq4.hip: IQ4_NL / IQ4_XS; mmq2_q32.hip: Q8_0 / Q5_0 / Q5_1 / Q4_1; mmq2_q2k.hip: Q2_K): the launch arguments, the LDS
+// What the kernels of the generation-2 prompt mat-mul family share (mmq2_kernels.hip: k-quants and Q4_0; mmq2_iq4.hip: IQ4_NL / IQ4_XS; mmq2_q32.hip: Q8_0 / Q5_0 / Q5_1 / Q4_1; mmq2_q2k.hip: Q2_K; mmq2_q3k.hip: Q3_K): the launch arguments, the LDS
 // image of an activation stage and its LDS-DMA requests (Q8_K rows: Mmq2Stage; Q8_0 rows: Mmq2Stage80), and the result store.
 #pragma once
 #include "kernels.hpp"
@@ -135,5 +135,7 @@ void launch_mmq2_iq4(int type, dim3 grid, hipStream_t s, const Mmq2Args &a, cons
 void launch_mmq2_q32(int type, dim3 grid, hipStream_t s, const Mmq2Args &a, const ActQ &A);
 // the Q2_K member (mmq2_q2k.hip): likewise; Q8_K rows, reads A.q8k and A.dk (the staged per-32 sums go unread)
 void launch_mmq2_q2k(int type, dim3 grid, hipStream_t s, const Mmq2Args &a, const ActQ &A);
+// the Q3_K member (mmq2_q3k.hip): likewise
+void launch_mmq2_q3k(int type, dim3 grid, hipStream_t s, const Mmq2Args &a, const ActQ &A);
 
 }  // namespace mg4

@@ -16,7 +16,8 @@
 //   * <= 256 VGPRs: two workgroups (8 waves) per CU, so one wave's scale arithmetic (VALU) overlaps another's MFMAs.
 // Members (mmq2_supported; all behind launch_mmq2_set): k_mmq2_q45k (Q4_K, Q5_K), k_mmq2_q6k (Q6_K), k_mmq2_q40 (Q4_0) and k_mmqh_q45k (fp16 form, off) in this file;
 // k_mmq2_iq4 (IQ4_NL, IQ4_XS) in mmq2_iq4.hip; k_mmq2_q32 (Q8_0, Q5_0, Q5_1, Q4_1) in mmq2_q32.hip; k_mmq2_q2k (Q2_K: the one k-quant whose sub-block scale x quant fits
-// ONE int8 byte, so its scales ride inside the operands with no digit split -- not one of the forms measured and removed below) in mmq2_q2k.hip.
+// ONE int8 byte, so its scales ride inside the operands with no digit split -- not one of the forms measured and removed below) in mmq2_q2k.hip; k_mmq2_q3k (Q3_K: the NEGATED product
+// -(s6 - 32) * (code - 4) is one int8 byte, likewise one operand chain) in mmq2_q3k.hip.
 // Per (row tile, super-block, token tile): 8 + 2 MFMAs (Q4_K / Q5_K) or 16 (Q6_K) and ~300 VALU instructions per wave -- the kernel is VALU-bound by the integer
 // sub-block scale multiply-adds ggml's format requires (one per output element per 32 weights: 1 VALU operation per 32 MFMA multiply-accumulates on a chip whose matrix
 // pipe is 64 x wider than its vector pipe), not by the matrix cores (PMC, profiles/r02e_pmc_mmq2.txt: two waves per SIMD issue 84 % of the time, MFMA 9 % busy).
@@ -710,7 +711,7 @@ void launch_slab_reduce(const float *slabs, int n_slabs, long long slab_stride, 
 
 static bool mmq2_is_q32(int type) { return type == GT_Q8_0 || type == GT_Q5_0 || type == GT_Q5_1 || type == GT_Q4_1; }   // the members of mmq2_q32.hip
 bool mmq2_supported(int type, int rows, int cols) {
-    return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0 || type == GT_IQ4_NL || type == GT_IQ4_XS || type == GT_Q2_K || mmq2_is_q32(type)) && cols % 256 == 0 && rows >= 32;
+    return (type == GT_Q4_K || type == GT_Q5_K || type == GT_Q6_K || type == GT_Q4_0 || type == GT_IQ4_NL || type == GT_IQ4_XS || type == GT_Q2_K || type == GT_Q3_K || mmq2_is_q32(type)) && cols % 256 == 0 && rows >= 32;
 }
 
 template <typename KernelT>
@@ -794,6 +795,7 @@ bool launch_mmq2_set(const QWeight *const *W, float *const *y, const float *cons
     if (type == GT_IQ4_NL || type == GT_IQ4_XS) launch_mmq2_iq4(type, grid, s, a, A);   // mmq2_iq4.hip; the K split above and the combine below are type-agnostic
     else if (mmq2_is_q32(type)) launch_mmq2_q32(type, grid, s, a, A);                    // mmq2_q32.hip; sizes its own dynamic LDS (the _1 members' stage has a second scale plane)
     else if (type == GT_Q2_K) launch_mmq2_q2k(type, grid, s, a, A);                      // mmq2_q2k.hip; half the transpose scratch: sizes its own dynamic LDS
+    else if (type == GT_Q3_K) launch_mmq2_q3k(type, grid, s, a, A);                      // mmq2_q3k.hip; likewise, plus its operand tables
     else switch (a.tiles_per_chunk) {
     case 1: mmq2_launch_tt<1>(type, grid, 2 * (q40 ? Mmq2Stage80<1>::BYTES : Mmq2Stage<1>::BYTES) + 16384, s, a, A, h16); break;
     case 2: mmq2_launch_tt<2>(type, grid, 2 * (q40 ? Mmq2Stage80<2>::BYTES : Mmq2Stage<2>::BYTES) + 16384, s, a, A, h16); break;

@@ -218,6 +218,39 @@ template <> struct Tr<GT_Q2_K> {   // decode (1..4 rows): the generic tile kerne
         acc = fmaf(-(dmin * a.d), (float)(m0 * a.bs_lo + m1 * a.bs_hi), acc);
     }
 };
+// Q3_K.  Planes (plan_qweight): per unit of 32 consecutive weights the low 2 bits in Q2_K's arrangement (p), the hmask bit pre-transposed like a 5-bit type's high bit
+// (P: low half dword k at bit 8 i + k, high half at 8 i + 4 + k, so ONE shift and mask puts it at bit 2), the two sub-block scales as int8 = 6-bit code - 32.  The 3-bit
+// code = low2 | hbit << 2 is an unsigned v_dot4 operand 0..7 and the weight is code - 4: per 16-weight sub-block s - 4 bsum, then the two scales with the exact 24-bit
+// multiplier -- ggml's vec_dot_q3_K_q8_K integers, and those of the Q6_K image that served Q3_K files before (sumf += (d_w * d_a) * sum).  14 bytes per unit against 26.
+// N >= 5 rows: k_mmq2_q3k (int8 MFMA, mmq2_q3k.hip).
+#define MG4_Q3_DOT8(L, H, P, lo, hi, s0, s1)                                                                                                                      \
+    s0 = dot4((L & 0x03030303) | ((P << 2) & 0x04040404), lo.x, s0); s0 = dot4(((L >> 2) & 0x03030303) | ((P << 1) & 0x04040404), lo.y, s0);                     \
+    s0 = dot4(((L >> 4) & 0x03030303) | (P & 0x04040404), lo.z, s0); s0 = dot4(((L >> 6) & 0x03030303) | ((P >> 1) & 0x04040404), lo.w, s0);                     \
+    s1 = dot4((H & 0x03030303) | ((P >> 2) & 0x04040404), hi.x, s1); s1 = dot4(((H >> 2) & 0x03030303) | ((P >> 3) & 0x04040404), hi.y, s1);                     \
+    s1 = dot4(((H >> 4) & 0x03030303) | ((P >> 4) & 0x04040404), hi.z, s1); s1 = dot4(((H >> 6) & 0x03030303) | ((P >> 5) & 0x04040404), hi.w, s1);
+template <> struct Tr<GT_Q3_K> {
+    static constexpr int EPU = 32;
+    struct WU { uint2 p; unsigned P; unsigned short sc, dh; };
+    using AU = AK;
+    static __device__ __forceinline__ void loadw(const QWeight &W, size_t g0, int u, WU &w) {
+        w.p = ldw<uint2>(W.qs + g0 * 8 + (unsigned)(u * 8)); w.P = ldw<unsigned>(W.qh + g0 * 4 + (unsigned)(u * 4)); w.sc = ldw<unsigned short>(W.sc + g0 * 2 + (unsigned)(u * 2));
+        w.dh = ldw<unsigned short>(W.d + (g0 >> 3) * 2 + (unsigned)((u >> 3) * 2)); }
+    static __device__ __forceinline__ void mkb(const QWeight &W, size_t g0, WBuf &B) { B.qs = mkbuf(W.qs + g0 * 8); B.qh = mkbuf(W.qh + g0 * 4); B.sc = mkbuf(W.sc + g0 * 2); B.d = mkbuf(W.d + (g0 >> 3) * 2); }
+    static __device__ __forceinline__ void loadb(const WBuf &B, int u, WU &w) { w.p = bld8(B.qs, u * 8); w.P = bld4(B.qh, u * 4); w.sc = bld2(B.sc, u * 2); w.dh = bld2(B.d, (u >> 3) * 2); }
+    static __device__ __forceinline__ void loada(const ActQ &A, int t, int K, int u, AU &a) { Tr<GT_Q2_K>::loada(A, t, K, u, a); }
+    static constexpr int GROUP = 8, TERMS = 1;
+    static __device__ __forceinline__ void ints(const WU &w, const AU &a, int &i0, int &i1) {
+        int s0 = 0, s1 = 0; const unsigned L = w.p.x, H = w.p.y, P = w.P;
+        MG4_Q3_DOT8(L, H, P, a.lo, a.hi, s0, s1)
+        s0 -= 4 * a.bs_lo; s1 -= 4 * a.bs_hi;
+        i0 = mul24((int)(signed char)(w.sc & 0xFF), s0) + mul24((int)(signed char)(w.sc >> 8), s1); i1 = 0;
+    }
+    static __device__ __forceinline__ void terms(const WU &w, const AU &a, int i0, int, float &f0, float &v0, float &f1, float &v1) { f0 = h2f_bits(w.dh) * a.d; v0 = (float)i0; f1 = v1 = 0.0f; }
+    static __device__ __forceinline__ void dot(const WU &w, const AU &a, float &acc) {
+        int i0, i1; ints(w, a, i0, i1);
+        acc = fmaf(h2f_bits(w.dh) * a.d, (float)i0, acc);
+    }
+};
 template <> struct Tr<GT_Q4_K> {
     static constexpr int EPU = 32;
     struct WU { int4 q; int4 h; };

@@ -109,11 +109,6 @@ static int test_mul_mat_impl(int ggml_type, const void *raw_w, int64_t n_in, int
 int minigpt4_amd_test_mul_mat(int ggml_type, const void *raw_w, int64_t n_in, int64_t n_out, const float *x, int64_t N, float *y) { return test_mul_mat_impl(ggml_type, raw_w, n_in, n_out, x, N, y, false); }
 int minigpt4_amd_test_mul_mat_ref(int ggml_type, const void *raw_w, int64_t n_in, int64_t n_out, const float *x, int64_t N, float *y) { return test_mul_mat_impl(ggml_type, raw_w, n_in, n_out, x, N, y, true); }
 static int test_mul_mat_impl(int ggml_type, const void *raw_w, int64_t n_in, int64_t n_out, const float *x, int64_t N, float *y, bool ref) {
-    if (ggml_type == GT_Q3_K && raw_w && n_in > 0 && n_out > 0 && n_in % 256 == 0) {   // the engine's load path: exact Q6_K image (quantize.hpp)
-        std::vector<uint8_t> q6((size_t)(n_in / 256 * n_out) * 210);
-        q3k_to_q6k(static_cast<const uint8_t *>(raw_w), q6.data(), (size_t)(n_in / 256 * n_out));
-        return test_mul_mat_impl(GT_Q6_K, q6.data(), n_in, n_out, x, N, y, ref);
-    }
     if (!raw_w || !x || !y || n_in <= 0 || n_out <= 0 || N <= 0 || !qweight_supported(ggml_type) || n_in % gt_block(ggml_type)) return 1;
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
@@ -638,19 +633,13 @@ int minigpt4_amd_test_rope_kv_slabs(int n_head, int hd, int n_ctx, int N, int po
     });
 }
 
-// The embedding gather (k_get_rows / dequant_elem) alone: one launch_get_rows over a raw table [n_rows][K] exactly as a model file stores it (Q3_K: re-encoded as Q6_K first,
-// as the engine's load path does).  out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard row; a token of -1 leaves its row at the fill.
+// The embedding gather (k_get_rows / dequant_elem) alone: one launch_get_rows over a raw table [n_rows][K] exactly as a model file stores it.
+// out [N + 1][K]: prefilled with 0xFF bytes, row N is a guard row; a token of -1 leaves its row at the fill.
 int minigpt4_amd_test_get_rows(int ggml_type, const void *raw_table, int n_rows, int64_t K, const int32_t *tokens, int N, float *out) {
     if (!raw_table || !tokens || !out || n_rows < 1 || n_rows > (1 << 20) || K < 1 || K > (1 << 20) || N < 1 || N > (1 << 16)) return 1;
-    if (ggml_type != GT_Q3_K && !qweight_supported(ggml_type)) return 1;
+    if (!qweight_supported(ggml_type)) return 1;
     if (K % gt_block(ggml_type)) return 1;
     for (int t = 0; t < N; t++) if (tokens[t] < -1 || tokens[t] >= n_rows) return 1;
-    if (ggml_type == GT_Q3_K) {
-        const size_t nb = (size_t)(K / 256) * (size_t)n_rows;
-        std::vector<uint8_t> q6(nb * 210);
-        q3k_to_q6k(static_cast<const uint8_t *>(raw_table), q6.data(), nb);
-        return minigpt4_amd_test_get_rows(GT_Q6_K, q6.data(), n_rows, K, tokens, N, out);
-    }
     if (device_count_noexcept() <= 0) { set_last_error("no HIP device"); return 2; }
     return guarded(3, [&]() -> int {
         const size_t raw_bytes = gt_nbytes(ggml_type, (size_t)K) * (size_t)n_rows, on = ((size_t)N + 1) * (size_t)K;

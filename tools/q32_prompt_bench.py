@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
-"""What a prompt pass and a batched step cost on a 7B file whose 2-D weights are Q8_0, Q5_0, Q5_1 or Q4_1 (k_mmq2_q32, csrc/mmq2_q32.hip) or Q2_K (--formats q2_k:
-k_mmq2_q2k, csrc/mmq2_q2k.hip); before those kernels: k_mul_mat<T, 2, 4>, one pass over the weights per four rows.
+"""What a prompt pass and a batched step cost on a 7B file whose 2-D weights are Q8_0, Q5_0, Q5_1 or Q4_1 (k_mmq2_q32, csrc/mmq2_q32.hip) Q2_K (--formats q2_k:
+k_mmq2_q2k, csrc/mmq2_q2k.hip) or Q3_K (--formats q3_k: the native 3.4-bit planes and k_mmq2_q3k, csrc/mmq2_q3k.hip; before them a Q6_K image of the file); before the
+other kernels: k_mul_mat<T, 2, 4>, one pass over the weights per four rows.
 One JSON line per format: medians of --reps (>= 5) alternated runs with max - min behind them, every run printed.
   p142 / p512   wall clock in ms of amd_eval_tokens + amd_logits around minigpt4_amd_sync for a 142-row (the image turn's size) and a 512-row prompt on an empty conversation
-  b8            ms per step of 16 greedy amd_end_chat_batch steps of 8 conversations (short prompts evaluated beforehand)
+  b4 / b8       ms per step of 16 greedy amd_end_chat_batch steps of 4 / 8 conversations (short prompts evaluated beforehand)
+  dec           ms per step of 64 greedy one-conversation decode steps (amd_decode_loop) behind a 16-token prompt
+  mem           MiB of device memory the process holds after minigpt4_model_load (hipMemGetInfo before / after)
 The files are synthetic (modelgen.headline_llm's conditioning, every 2-D tensor in the format); every run is a child process that loads the file, warms each measurement
 up once and measures it once.  With --parent-lib (a libminigpt4.so built from the parent commit) the runs alternate, parent first in each pair.
-    python tools/q32_prompt_bench.py [--formats q8_0,q5_0,q5_1,q4_1 | q2_k] [--reps 5] [--parent-lib PATH]        GPU only."""
+    python tools/q32_prompt_bench.py [--formats q8_0,q5_0,q5_1,q4_1 | q2_k | q3_k] [--reps 5] [--parent-lib PATH]        GPU only."""
 import argparse
+import ctypes
 import dataclasses
 import json
 import os
@@ -21,9 +25,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import _pkg  # noqa: E402
 
-FTYPE = {"q8_0": 7, "q5_0": 8, "q5_1": 9, "q4_1": 3, "q2_k": 10}
-MEASURES = ("p142", "p512", "b8")
-B, STEPS = 8, 16
+FTYPE = {"q8_0": 7, "q5_0": 8, "q5_1": 9, "q4_1": 3, "q2_k": 10, "q3_k": 11}
+MEASURES = ("p142", "p512", "b4", "b8", "dec", "mem")
+B, STEPS, DEC_STEPS = 8, 16, 64
 
 
 def stat(x):
@@ -51,9 +55,16 @@ def measure_once(lib, fmt):
     vp, lp = files(fmt)
     rng = np.random.default_rng(3)
     toks = [1] + rng.integers(3, 30000, 511).tolist()
+    hip = ctypes.CDLL("libamdhip64.so")
+
+    def free_mib():
+        free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+        return free.value / 2 ** 20
+    before = free_mib()
     ctx = lib.minigpt4_model_load(vp, lp, verbosity=0, n_ctx=1024, n_batch=512)
     sync = lambda: lib.library.minigpt4_amd_sync(ctx.ptr)   # noqa: E731
-    out = {}
+    out = {"mem": before - free_mib()}
     try:
         for rows in (142, 512):
             for rep in range(2):                                         # the first round is the warm-up
@@ -64,21 +75,31 @@ def measure_once(lib, fmt):
                 lib.amd_logits(ctx)
                 sync()
                 out[f"p{rows}"] = (time.perf_counter() - t0) * 1e3
-        lib.amd_set_conversations(ctx, B)
         for rep in range(2):
-            for s in range(B):
-                lib.amd_select_conversation(ctx, s)
-                lib.minigpt4_reset_chat(ctx)
-                lib.amd_eval_tokens(ctx, toks[:4 + s])
-                lib.amd_logits(ctx)
-            lib.amd_select_conversation(ctx, 0)
-            lib.amd_end_chat_batch(ctx, list(range(B)), temp=0.0)        # the first step of a round builds what the later ones replay
+            lib.minigpt4_reset_chat(ctx)
+            lib.amd_eval_tokens(ctx, toks[:16])
+            lib.amd_decode_loop(ctx, 8)
             sync()
             t0 = time.perf_counter()
-            for _ in range(STEPS):
-                lib.amd_end_chat_batch(ctx, list(range(B)), temp=0.0)
+            lib.amd_decode_loop(ctx, DEC_STEPS)
             sync()
-            out["b8"] = (time.perf_counter() - t0) * 1e3 / STEPS
+            out["dec"] = (time.perf_counter() - t0) * 1e3 / DEC_STEPS
+        lib.amd_set_conversations(ctx, B)
+        for nb in (4, B):
+            for rep in range(2):
+                for s in range(nb):
+                    lib.amd_select_conversation(ctx, s)
+                    lib.minigpt4_reset_chat(ctx)
+                    lib.amd_eval_tokens(ctx, toks[:4 + s])
+                    lib.amd_logits(ctx)
+                lib.amd_select_conversation(ctx, 0)
+                lib.amd_end_chat_batch(ctx, list(range(nb)), temp=0.0)   # the first step of a round builds what the later ones replay
+                sync()
+                t0 = time.perf_counter()
+                for _ in range(STEPS):
+                    lib.amd_end_chat_batch(ctx, list(range(nb)), temp=0.0)
+                sync()
+                out[f"b{nb}"] = (time.perf_counter() - t0) * 1e3 / STEPS
     finally:
         lib.minigpt4_free(ctx)
     return out
@@ -114,7 +135,7 @@ def main():
                 got = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("CHILD ")][-1][6:])
                 for k in MEASURES:
                     runs[arm][k].append(got[k])
-        print(json.dumps({"format": fmt, "unit": "ms (b8: per step)", "median_spread": {a: {k: stat(v) for k, v in r.items()} for a, r in runs.items()},
+        print(json.dumps({"format": fmt, "unit": "ms (b4, b8, dec: per step; mem: MiB)", "median_spread": {a: {k: stat(v) for k, v in r.items()} for a, r in runs.items()},
                           "runs": {a: {k: [round(x, 2) for x in v] for k, v in r.items()} for a, r in runs.items()}}), flush=True)
 
 
