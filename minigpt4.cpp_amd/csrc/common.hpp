@@ -20,11 +20,12 @@ enum Err : int {
 // ggml_type numbering (LLM file); the vision file's MiniGPT4DataType is mapped onto it by the loader.
 enum GType : int { GT_F32 = 0, GT_F16 = 1, GT_Q4_0 = 2, GT_Q4_1 = 3, GT_Q5_0 = 6, GT_Q5_1 = 7, GT_Q8_0 = 8, GT_Q8_1 = 9, GT_Q2_K = 10,
                    GT_Q3_K = 11, GT_Q4_K = 12, GT_Q5_K = 13, GT_Q6_K = 14, GT_Q8_K = 15, GT_I32 = 18, GT_I64 = 19,
-                   GT_IQ4_NL = 20, GT_IQ4_XS = 23 };   // the non-linear 4-bit formats: a 16-entry int8 codebook instead of q - 8 (qtraits.hpp)
+                   GT_IQ4_NL = 20, GT_IQ4_XS = 23,     // the non-linear 4-bit formats: a 16-entry int8 codebook instead of q - 8 (qtraits.hpp)
+                   GT_BF16 = 30 };                     // unquantised bfloat16 (GGUF files only)
 
-inline int gt_block(int t) { switch (t) { case GT_F32: case GT_F16: case GT_I32: case GT_I64: return 1; case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_Q8_K: case GT_IQ4_XS: return 256; default: return 32; } }
+inline int gt_block(int t) { switch (t) { case GT_F32: case GT_F16: case GT_BF16: case GT_I32: case GT_I64: return 1; case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_Q8_K: case GT_IQ4_XS: return 256; default: return 32; } }
 inline int gt_bytes(int t) {
-    switch (t) { case GT_F32: case GT_I32: return 4; case GT_F16: return 2; case GT_I64: return 8; case GT_Q4_0: return 18; case GT_Q4_1: return 20; case GT_Q5_0: return 22;
+    switch (t) { case GT_F32: case GT_I32: return 4; case GT_F16: case GT_BF16: return 2; case GT_I64: return 8; case GT_Q4_0: return 18; case GT_Q4_1: return 20; case GT_Q5_0: return 22;
         case GT_Q5_1: return 24; case GT_Q8_0: return 34; case GT_Q8_1: return 40; case GT_Q2_K: return 84; case GT_Q3_K: return 110; case GT_Q4_K: return 144;
         case GT_Q5_K: return 176; case GT_Q6_K: return 210; case GT_Q8_K: return 292; case GT_IQ4_NL: return 18; case GT_IQ4_XS: return 136; default: return 0; }
 }
@@ -65,7 +66,7 @@ template <typename K> inline hipError_t lds_optin_max(K kernel) {
 //   Q4_K/Q5_K/Q6_K      : 1 unit = 32 weights (8 units / super-block)
 //   Q2_K/Q3_K           : 1 unit = 32 consecutive weights = two 16-weight sub-blocks, 8 bytes of the 2-bit plane (8 units / super-block)
 //   IQ4_NL : 1 unit = 1 block (as Q4_0)                        IQ4_XS : 1 unit = 32 weights in element order (8 units / super-block)
-//   F16 : 8 weights, F32 : 4 weights
+//   F16 / BF16 : 8 weights, F32 : 4 weights
 struct QWeight {
     int type = -1;
     int rows = 0, cols = 0;          // n_out, n_in
@@ -96,14 +97,15 @@ struct ActQ {
     float *d1 = nullptr;     // [N][K/32]  Q8_1 d (float)
     float *s1 = nullptr;     // [N][K/32]  Q8_1 s = d * sum(q)
     int *sum0 = nullptr;     // [N][K/32]  sum(q) per block
-    __half *xh = nullptr;    // [N][K]     fp16-rounded activations (F16 weights)
+    __half *xh = nullptr;    // [N][K]     fp16-rounded activations (F16 weights); ACT_BF16: the same storage holds the rows rounded to bfloat16 (BF16 weights) --
+                             //            same size, and no launch mixes F16 and BF16 matrices (Engine::load_llm refuses a file that has both)
     float *xf = nullptr;     // [N][K]     fp32 activations (F32 weights)
     float *ws = nullptr; size_t ws_floats = 0;   // (optional) workspace that travels with the planes: K-split partial sums of the prefill mat-mul (mmq2_kernels.hip)
 };
-enum ActMask : int { ACT_Q8K = 1, ACT_Q80 = 2, ACT_F16 = 4, ACT_F32 = 8 };
+enum ActMask : int { ACT_Q8K = 1, ACT_Q80 = 2, ACT_F16 = 4, ACT_F32 = 8, ACT_BF16 = 16 };
 __host__ __device__ inline int act_mask_for(int wtype) {
     switch (wtype) { case GT_Q4_0: case GT_Q5_0: case GT_Q8_0: case GT_Q4_1: case GT_Q5_1: case GT_IQ4_NL: return ACT_Q80; case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_XS: return ACT_Q8K;
-        case GT_F16: return ACT_F16; case GT_F32: return ACT_F32; default: return 0; }
+        case GT_F16: return ACT_F16; case GT_F32: return ACT_F32; case GT_BF16: return ACT_BF16; default: return 0; }
 }
 
 }  // namespace mg4

@@ -337,7 +337,7 @@ void Engine::upload_qweight(const TensorMeta &t, const uint8_t *file_base, QWeig
     uint8_t *base = llm_arena_.take(need);
     plan_qweight(t.type, rows, cols, w, base);
     if (!moves_data()) return;                                              // LOAD_RECV / LOAD_PLAN: layout only
-    if (t.type == GT_F16 || t.type == GT_F32) { HIP_CHECK(hipMemcpy(base, file_base + t.offset, t.nbytes, hipMemcpyHostToDevice)); return; }
+    if (t.type == GT_F16 || t.type == GT_BF16 || t.type == GT_F32) { HIP_CHECK(hipMemcpy(base, file_base + t.offset, t.nbytes, hipMemcpyHostToDevice)); return; }
     if (t.nbytes > stage_cap_) throw HipError{hipErrorOutOfMemory, "staging buffer too small", __FILE__, __LINE__};
     HIP_CHECK(hipMemcpy(stage_, file_base + t.offset, t.nbytes, hipMemcpyHostToDevice));
     launch_repack(stage_, w, stream_);
@@ -382,13 +382,17 @@ int Engine::load_llm(const std::string &path) {
         mats.push_back({p + "feed_forward.w3.weight", {E, F}});
     }
     wbytes_token_ = 0;
+    bool any_f16 = false, any_bf16 = false;
     for (auto &m : mats) {
         const TensorMeta *t = need(m.first, m.second.first, m.second.second);
         if (!t) { MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
+        any_f16 = any_f16 || t->type == GT_F16; any_bf16 = any_bf16 || t->type == GT_BF16;
         total += plan_qweight(t->type, (int)t->ne[1], (int)t->ne[0], tmp, nullptr) + 256;
-        if (t->type != GT_F16 && t->type != GT_F32) max_raw = std::max(max_raw, t->nbytes);
+        if (t->type != GT_F16 && t->type != GT_BF16 && t->type != GT_F32) max_raw = std::max(max_raw, t->nbytes);
         wbytes_token_ += t->nbytes;                             // what a decoded token streams from HBM
     }
+    // the fp16 and the bfloat16 image of a prepared row share one plane (ActQ::xh), and a set launch prepares the rows of all its matrices at once
+    if (any_f16 && any_bf16) { set_last_error("LLM file: F16 and BF16 matrices in one file are not supported"); MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
     const TensorMeta *tt = llm_.find("tok_embeddings.weight");
     if (!tt || tt->ne.size() != 2 || tt->ne[0] != E || tt->ne[1] != V || !qweight_supported(tt->type)) { set_last_error("LLM file: bad tok_embeddings.weight"); MG4_ERR("%s", last_error().c_str()); return E_LoadLanguageModel; }
     total += tt->nbytes + 256;

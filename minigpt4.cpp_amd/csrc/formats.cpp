@@ -31,7 +31,7 @@ const char *gt_name(int t) {
     switch (t) { case GT_F32: return "f32"; case GT_F16: return "f16"; case GT_Q4_0: return "q4_0"; case GT_Q4_1: return "q4_1"; case GT_Q5_0: return "q5_0";
         case GT_Q5_1: return "q5_1"; case GT_Q8_0: return "q8_0"; case GT_Q8_1: return "q8_1"; case GT_Q2_K: return "q2_K"; case GT_Q3_K: return "q3_K";
         case GT_Q4_K: return "q4_K"; case GT_Q5_K: return "q5_K"; case GT_Q6_K: return "q6_K"; case GT_Q8_K: return "q8_K"; case GT_I32: return "i32"; case GT_I64: return "i64";
-        case GT_IQ4_NL: return "iq4_nl"; case GT_IQ4_XS: return "iq4_xs"; default: return "?"; }
+        case GT_IQ4_NL: return "iq4_nl"; case GT_IQ4_XS: return "iq4_xs"; case GT_BF16: return "bf16"; default: return "?"; }
 }
 
 // ---------------------------------------------------------------------------------------------------- mmap
@@ -162,7 +162,7 @@ int LLMFile::load(const std::string &path, bool vocab_only) {
         for (uint32_t i = 0; i < nd; i++) { const uint32_t d = r.u4(); if (d > (1u << 30)) { set_last_error("LLM file: absurd tensor shape"); return E_LoadLanguageModel; } t.ne.push_back(d); }
         if (t.nelements() > ((int64_t)1 << 40)) { set_last_error("LLM file: absurd tensor shape"); return E_LoadLanguageModel; }   // two dims <= 2^30: the product cannot overflow
         t.name = r.str(nl);
-        if (!r.ok || gt_bytes(t.type) == 0 || t.ne[0] % gt_block(t.type)) { set_last_error("LLM file: tensor " + t.name + " has an unusable type/shape"); return E_LoadLanguageModel; }
+        if (!r.ok || gt_bytes(t.type) == 0 || t.type == GT_BF16 || t.ne[0] % gt_block(t.type)) { set_last_error("LLM file: tensor " + t.name + " has an unusable type/shape"); return E_LoadLanguageModel; }   // (GGJT v3 has no BF16)
         r.pos = (r.pos + 31) & ~(size_t)31;
         t.offset = r.pos; t.nbytes = gt_nbytes(t.type, (size_t)t.nelements());
         if (!r.need(t.nbytes)) { set_last_error("LLM file: tensor " + t.name + " runs past EOF"); return E_LoadLanguageModel; }

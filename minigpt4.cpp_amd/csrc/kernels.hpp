@@ -101,6 +101,10 @@ void launch_slab_reduce(const float *slabs, int n_slabs, long long slab_stride, 
 bool launch_gemm_f16_silu_pair(const __half *A, int lda, const __half *W1, const __half *W3, int M, int N, int K, const Tables &tb, float *out, __half *out_h, int ldo, const LaunchTuning &tune, hipStream_t s);   // fp16(silu(A.W1^T) * (A.W3^T)) in one launch (F16 w1|w3 at prompt sizes)
 bool launch_gemm_f16_set(const __half *A, int lda, const __half *const *W, int n, int M, int N, int K, float *const *y, const float *const *residual, int ldo, float *ws,
                          size_t ws_floats, const LaunchTuning &tune, hipStream_t s, SlabSrc *defer = nullptr);
+// BF16 weights at N >= 16 prepared rows (A.xh holds them rounded to bfloat16): y[t][r] = W[r] . act[t] (+ residual[t][r]) on v_mfma_f32_32x32x16_bf16 (gemm_bf16.hip);
+// K split through A.ws when the tiles do not fill the chip (tune.mmq_ks forces a count), combined in fixed order by launch_slab_flush.  false -> K is no multiple of 8,
+// nothing launched
+bool launch_gemm_bf16(const QWeight &W, const ActQ &A, int N, float *y, int ldy, const float *residual, const LaunchTuning &tune, hipStream_t s);
 
 // decode (N = 1) persistent-wave mat-vec over 1..3 same-type, same-shape matrices (wq|wk|wv, w1|w3); false -> caller falls back to launch_mul_mat
 // pro: 0 = activations come from `A` (prepared by launch_rms_quant / launch_silu_mul_quant); 1 = rms_norm(px) * pw, 2 = px, 3 = silu(px) * pw are

@@ -83,7 +83,7 @@ size_t plan_qweight(int type, int rows, int cols, QWeight &w, uint8_t *base) {
     auto take = [&](size_t bytes) { uint8_t *p = base ? base + off : nullptr; off += al(bytes); return p; };
     switch (type) {
     case GT_F32: w.qs = take(n * 4); break;
-    case GT_F16: w.qs = take(n * 2); break;
+    case GT_F16: case GT_BF16: w.qs = take(n * 2); break;   // copied as they stand
     case GT_Q4_0: w.qs = take(n / 32 * 16); w.sc = take(n / 32 * 2); break;
     case GT_Q4_1: w.qs = take(n / 32 * 16); w.sc = take(n / 32 * 4); break;
     case GT_Q5_0: w.qs = take(n / 32 * 16); w.qh = take(n / 32 * 4); w.sc = take(n / 32 * 2); break;
@@ -104,7 +104,7 @@ size_t plan_qweight(int type, int rows, int cols, QWeight &w, uint8_t *base) {
     return off;
 }
 bool qweight_supported(int type) {
-    switch (type) { case GT_F32: case GT_F16: case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q8_0: case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_NL: case GT_IQ4_XS: return true; default: return false; }
+    switch (type) { case GT_F32: case GT_F16: case GT_BF16: case GT_Q4_0: case GT_Q4_1: case GT_Q5_0: case GT_Q5_1: case GT_Q8_0: case GT_Q2_K: case GT_Q3_K: case GT_Q4_K: case GT_Q5_K: case GT_Q6_K: case GT_IQ4_NL: case GT_IQ4_XS: return true; default: return false; }
 }
 
 // high-bit transposition for 5-bit types: element e of 32 (lo: e<16 -> dword k=e/4, byte i=e%4, slot w=k; hi: e>=16 -> w=4+k)
@@ -185,14 +185,14 @@ __global__ void k_repack(const uint8_t *__restrict__ raw, QWeight w, size_t n_un
         sc[sb * 16 + 8 + ib] = (uint8_t)(signed char)(ls - 32);
         for (int i = 0; i < 16; i++) qs[g * 16 + i] = b[8 + ib * 16 + i];
         break; }
-    case GT_F16: case GT_F32: { for (int i = 0; i < 16; i++) qs[g * 16 + i] = raw[g * 16 + i]; break; }
+    case GT_F16: case GT_BF16: case GT_F32: { for (int i = 0; i < 16; i++) qs[g * 16 + i] = raw[g * 16 + i]; break; }
     default: break;
     }
 }
 void launch_repack(const uint8_t *raw, const QWeight &w, hipStream_t s) {
     const size_t n = (size_t)w.rows * w.cols;
     size_t units;
-    switch (w.type) { case GT_F32: units = n / 4; break; case GT_F16: units = n / 8; break; case GT_Q8_0: units = n / 16; break; default: units = n / 32; }
+    switch (w.type) { case GT_F32: units = n / 4; break; case GT_F16: case GT_BF16: units = n / 8; break; case GT_Q8_0: units = n / 16; break; default: units = n / 32; }
     const int bs = 256;
     hipLaunchKernelGGL(k_repack, dim3((unsigned)((units + bs - 1) / bs)), dim3(bs), 0, s, raw, w, units);
 }
@@ -281,7 +281,7 @@ template <int T> constexpr bool tr_is_kquant() { return T == GT_Q4_K || T == GT_
 // Preparation fused into a Q3_K launch is a follow-up; it has to change tests/test_cpu_matvec_dispatch.py, which lists q3_k among the types the predicates refuse.
 template <int T> constexpr bool tr_reads_q8k() { return tr_is_kquant<T>() || T == GT_Q3_K; }   // the activation unit is an AK of the Q8_K planes
 template <int T> constexpr bool tr_is_q32() { return T == GT_Q4_0 || T == GT_Q4_1 || T == GT_Q5_0 || T == GT_Q5_1 || T == GT_IQ4_NL; }
-template <int T> constexpr bool tr_is_narrow() { return T == GT_Q8_0 || T == GT_F16; }   // 16-byte units of 16 / 8 weights: more units per row than the 32-weight types
+template <int T> constexpr bool tr_is_narrow() { return T == GT_Q8_0 || T == GT_F16 || T == GT_BF16; }   // 16-byte units of 16 / 8 weights: more units per row than the 32-weight types
 // k_matvec_v2<T, NU, R, PRO, EPI>.  Q8_0 / F16: only a few unit counts, a row takes the smallest one that covers it (the surplus units are masked like any ragged
 // tail) -- Q8_0: K <= 1024 | 4096 | 5120 | 11264; F16: K <= 512 | 1024 | 4096 | 5120.  Pair epilogue (w1|w3): K <= 6144.  EPI_REF: the k-quants of the headline files
 // (other types: k_mul_mat_ref_row).
@@ -292,9 +292,11 @@ template <int T, int EPI> constexpr auto mv_units() {
     else if constexpr (tr_is_q32<T>()) return std::conditional_t<EPI == EPI_SILU_PAIR, Units1to3, std::conditional_t<EPI == EPI_STORE, Units1to7, UnitList<>>>{};
     else return UnitList<>{};
 }
-// k_matvec_v2_free<T, NU, R, EPI>: what mv_units has, and Q3_K's store form
+// k_matvec_v2_free<T, NU, R, EPI>: what mv_units has, and the store forms of Q3_K and of BF16 -- BF16 is prologue-free like Q3_K (no entry in mv_units, so the three
+// predicates answer no and its rows come from a preparation launch in front), with F16's unit counts: K <= 512 | 1024 | 4096 | 5120
 template <int T, int EPI> constexpr auto mv_free_units() {
     if constexpr (T == GT_Q3_K) return std::conditional_t<EPI == EPI_STORE, Units1to7, UnitList<>>{};
+    else if constexpr (T == GT_BF16) return std::conditional_t<EPI == EPI_STORE, UnitList<1, 2, 8, 10>, UnitList<>>{};
     else return mv_units<T, EPI>();
 }
 template <int T, int NU, int EPI> constexpr int mv_rows_per_group() {   // R: rows a wave has in flight per stage
@@ -335,6 +337,7 @@ template <class F> static bool for_weight_type(int type, F &&f) {
     case GT_IQ4_NL: return f(std::integral_constant<int, GT_IQ4_NL>{});
     case GT_IQ4_XS: return f(std::integral_constant<int, GT_IQ4_XS>{});
     case GT_F16: return f(std::integral_constant<int, GT_F16>{});
+    case GT_BF16: return f(std::integral_constant<int, GT_BF16>{});
     case GT_F32: return f(std::integral_constant<int, GT_F32>{});
     default: return false;
     }
@@ -347,7 +350,7 @@ template <class F> static bool for_mixed_types(int t1, int t2, F &&f) {
 }
 // Largest K of a unit list for a type, 0: none.  A row is a whole number of the type's blocks (F16: of 16-byte units).
 template <class L> static bool mv_covers(L list, int type, int K) {
-    const int epu = type == GT_F16 ? 8 : type == GT_Q8_0 ? 16 : 32, block = type == GT_F16 ? 8 : gt_block(type);
+    const bool f16 = type == GT_F16 || type == GT_BF16; const int epu = f16 ? 8 : type == GT_Q8_0 ? 16 : 32, block = f16 ? 8 : gt_block(type);
     return K > 0 && K % block == 0 && K <= units_max(list) * 64 * epu;
 }
 bool matvec_prologue_supported(int type, int cols) { return for_weight_type(type, [&](auto t) { return mv_covers(mv_units<decltype(t)::value, EPI_STORE>(), type, cols); }); }
@@ -377,7 +380,7 @@ __global__ __launch_bounds__(256) void k_mul_mat_ref(const QWeight W, const ActQ
         const int n_here = min(64, U - u0);
         typename X::AU a; X::loada(A, t, K, uc, a);
         typename X::WU w; X::loadw(W, (size_t)row * U, uc, w);
-        if constexpr (T == GT_F16 || T == GT_F32) {
+        if constexpr (T == GT_F16 || T == GT_BF16 || T == GT_F32) {
             for (int g = 0; g < n_here; g++) { float c = acc; X::dot(w, a, c); acc = __shfl(c, g); }   // unit g continues the chain where unit g - 1 left it
         } else {
             acc = ref_chunk<T>(w, a, ok, n_here, acc);
@@ -1303,6 +1306,8 @@ void launch_mul_mat(const QWeight &W, const ActQ &A, int N, float *y, int ldy, c
         if (launch_mmq2_set(Wp, Yp, residual ? Rp : nullptr, 1, A, N, ldy, tune, s)) return;
     }
     if (W.type == GT_F16 && N >= 16 && W.cols % 8 == 0) { launch_gemm_f16(A.xh, W.cols, reinterpret_cast<const __half *>(W.qs), W.cols, N, W.rows, W.cols, nullptr, residual, false, Tables{}, y, nullptr, ldy, tune, s); return; }
+    // BF16 weights, prompt rows: the bf16-MFMA kernel of gemm_bf16.hip on the rows k_rms_quant / k_silu_mul_quant left in bfloat16 (rows 2 .. 15: the tile kernel below)
+    if (W.type == GT_BF16 && N >= 16 && launch_gemm_bf16(W, A, N, y, ldy, residual, tune, s)) return;
     if (!for_weight_type(W.type, [&](auto t) { launch_mul_mat_t<decltype(t)::value>(W, A, N, y, ldy, residual, s); return true; }))
         throw HipError{hipErrorInvalidValue, "unsupported weight type", __FILE__, __LINE__};
 }
@@ -1422,6 +1427,7 @@ __device__ float dequant_elem(int type, const uint8_t *row, int e) {
     switch (type) {
     case GT_F32: return reinterpret_cast<const float *>(row)[e];
     case GT_F16: return h2f_bits(reinterpret_cast<const unsigned short *>(row)[e]);
+    case GT_BF16: return __uint_as_float((unsigned)reinterpret_cast<const unsigned short *>(row)[e] << 16);   // the exact widening
     case GT_Q4_0: { const uint8_t *b = row + (e >> 5) * 18; const int j = e & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); const int q = j < 16 ? (b[2 + j] & 15) : (b[2 + j - 16] >> 4); return (float)(q - 8) * d; }
     case GT_IQ4_NL: { const uint8_t *b = row + (e >> 5) * 18; const int j = e & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); return d * (float)iq4_kv(j < 16 ? (b[2 + j] & 15) : (b[2 + j - 16] >> 4)); }
     case GT_IQ4_XS: { const uint8_t *b = row + (e >> 8) * 136; const int i = e & 255, ib = i >> 5, j = i & 31; const float d = h2f_bits(b[0] | (b[1] << 8)); const int sh = b[2] | (b[3] << 8);

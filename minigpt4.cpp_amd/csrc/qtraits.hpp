@@ -424,6 +424,24 @@ template <> struct Tr<GT_F16> {
         for (int i = 0; i < 4; i++) { acc = fmaf(h2f_bits(wq[i] & 0xFFFF), h2f_bits(aq[i] & 0xFFFF), acc); acc = fmaf(h2f_bits(wq[i] >> 16), h2f_bits(aq[i] >> 16), acc); }
     }
 };
+// BF16 (GGUF type 30).  ggml's vec_dot_type for it is BF16: the activation row is rounded to bfloat16 (nearest even, NaN stays NaN: v_cvt_pk_bf16_f32, which hipcc
+// emits for the conversion below on gfx950), products of two bfloat16 are exact in fp32, accumulation is fp32.  The rows live in the xh plane's storage (common.hpp).
+// A unit is 16 bytes = 8 weights, as for F16.  This form (the generic tile kernel and the oracle-order kernels) widens by shift / mask: one fma per element, in
+// element order; TrMV<GT_BF16> below is the decode mat-vec's.
+typedef __bf16 v2bf_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned f2bf_pk(float lo, float hi) { v2bf_t v; v.x = (__bf16)lo; v.y = (__bf16)hi; return __builtin_bit_cast(unsigned, v); }
+template <> struct Tr<GT_BF16> {
+    static constexpr int EPU = 8;
+    struct WU { int4 q; };
+    struct AU { int4 a; };
+    static __device__ __forceinline__ void loadw(const QWeight &W, size_t g0, int u, WU &w) { w.q = ldw<int4>(W.qs + g0 * 16 + (unsigned)(u * 16)); }
+    static __device__ __forceinline__ void loada(const ActQ &A, int t, int K, int u, AU &a) { a.a = ld16(reinterpret_cast<const uint8_t *>(A.xh) + ((size_t)t * K + (size_t)u * 8) * 2); }
+    static __device__ __forceinline__ void dot(const WU &w, const AU &a, float &acc) {
+        const unsigned wq[4] = {(unsigned)w.q.x, (unsigned)w.q.y, (unsigned)w.q.z, (unsigned)w.q.w}, aq[4] = {(unsigned)a.a.x, (unsigned)a.a.y, (unsigned)a.a.z, (unsigned)a.a.w};
+#pragma unroll
+        for (int i = 0; i < 4; i++) { acc = fmaf(__uint_as_float(wq[i] << 16), __uint_as_float(aq[i] << 16), acc); acc = fmaf(__uint_as_float(wq[i] & 0xFFFF0000u), __uint_as_float(aq[i] & 0xFFFF0000u), acc); }
+    }
+};
 template <> struct Tr<GT_F32> {
     static constexpr int EPU = 4;
     struct WU { float4 q; };
@@ -462,8 +480,19 @@ template <> struct TrMV<GT_F16> : Tr<GT_F16> {
     }
 };
 
+template <> struct TrMV<GT_BF16> : Tr<GT_BF16> {
+    static __device__ __forceinline__ void mkb(const QWeight &W, size_t g0, WBuf &B) { B.qs = mkbuf(W.qs + g0 * 16); }
+    static __device__ __forceinline__ void loadb(const WBuf &B, int u, WU &w) { w.q = bld16(B.qs, u * 16); }
+    static __device__ __forceinline__ void dot(const WU &w, const AU &a, float &acc) {   // v_dot2_f32_bf16: exact bfloat16 products, fp32 accumulate
+        acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, w.q.x), __builtin_bit_cast(v2bf_t, a.a.x), acc, false);
+        acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, w.q.y), __builtin_bit_cast(v2bf_t, a.a.y), acc, false);
+        acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, w.q.z), __builtin_bit_cast(v2bf_t, a.a.z), acc, false);
+        acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(v2bf_t, w.q.w), __builtin_bit_cast(v2bf_t, a.a.w), acc, false);
+    }
+};
+
 // =====================================================================================================================
-// activation preparation: (rms_norm * w | silu(a)*b | identity) -> {Q8_K, Q8_0/Q8_1, f16, f32}
+// activation preparation: (rms_norm * w | silu(a)*b | identity) -> {Q8_K, Q8_0/Q8_1, f16 | bf16, f32}
 // thread t of a 256-thread group owns 4 consecutive values; a wave = one 256-wide Q8_K block, 8 lanes = one 32-wide block.
 // =====================================================================================================================
 __device__ __forceinline__ void quant_emit4(const float v[4], const bool in_range, const int idx /*first element index in the row*/, const size_t row, const int K,
@@ -472,6 +501,7 @@ __device__ __forceinline__ void quant_emit4(const float v[4], const bool in_rang
     if (mask & ACT_F32) { if (in_range) *reinterpret_cast<float4 *>(A.xf + row * K + idx) = make_float4(v[0], v[1], v[2], v[3]); }
     if (mask & ACT_F16) { if (in_range) { __half2 h0 = __halves2half2(f2h_rn(v[0]), f2h_rn(v[1])), h1 = __halves2half2(f2h_rn(v[2]), f2h_rn(v[3]));
             uint2 o; o.x = *reinterpret_cast<unsigned *>(&h0); o.y = *reinterpret_cast<unsigned *>(&h1); *reinterpret_cast<uint2 *>(A.xh + row * K + idx) = o; } }
+    if (mask & ACT_BF16) { if (in_range) { uint2 o; o.x = f2bf_pk(v[0], v[1]); o.y = f2bf_pk(v[2], v[3]); *reinterpret_cast<uint2 *>(A.xh + row * K + idx) = o; } }   // the xh plane's storage
     if (mask & ACT_Q8K) {
         // signed value of the FIRST element with the largest magnitude in the 256-block (ggml quantize_row_q8_K): the wave = one block,
         // lanes are in element order, so it is the first maximum of the lowest lane whose local maximum equals the wave maximum.

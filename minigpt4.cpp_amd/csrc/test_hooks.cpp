@@ -118,7 +118,7 @@ static int test_mul_mat_impl(int ggml_type, const void *raw_w, int64_t n_in, int
         DevBuf d_raw(raw_bytes), d_planes(need), d_x((size_t)(N * n_in) * 4), d_y((size_t)(N * n_out) * 4);
         plan_qweight(ggml_type, (int)n_out, (int)n_in, W, d_planes.as<uint8_t>());
         HIP_CHECK(hipMemcpy(d_raw.p, raw_w, raw_bytes, hipMemcpyHostToDevice));
-        if (ggml_type == GT_F16 || ggml_type == GT_F32) HIP_CHECK(hipMemcpy(d_planes.p, raw_w, raw_bytes, hipMemcpyHostToDevice)); else launch_repack(d_raw.as<uint8_t>(), W, nullptr);
+        if (ggml_type == GT_F16 || ggml_type == GT_BF16 || ggml_type == GT_F32) HIP_CHECK(hipMemcpy(d_planes.p, raw_w, raw_bytes, hipMemcpyHostToDevice)); else launch_repack(d_raw.as<uint8_t>(), W, nullptr);
         HIP_CHECK(hipMemcpy(d_x.p, x, (size_t)(N * n_in) * 4, hipMemcpyHostToDevice));
         ActQ A; std::vector<std::unique_ptr<DevBuf>> keep; alloc_act(A, keep, (size_t)N, (size_t)n_in);
         launch_rms_quant(d_x.as<float>(), nullptr, (int)N, (int)n_in, A, act_mask_for(ggml_type), nullptr);
@@ -160,6 +160,9 @@ int minigpt4_amd_test_mmq2(int ggml_type, const void *raw_w, int n_mat, int64_t 
         if (ggml_type == GT_F16) {   // the F16 language-model set path (big MFMA GEMM, several matrices per launch / split K)
             const __half *Wh[3]; for (int i = 0; i < n_mat; i++) Wh[i] = reinterpret_cast<const __half *>(W[i].qs);
             ok = launch_gemm_f16_set(A.xh, (int)n_in, Wh, n_mat, (int)N, (int)n_out, (int)n_in, Yp, residual ? Rp : nullptr, (int)n_out, A.ws, A.ws_floats, tune, nullptr);
+        } else if (ggml_type == GT_BF16) {   // the BF16 prompt path as Engine::mul_mat_set reaches it: launch_mul_mat per matrix (gemm_bf16.hip; ks = 0: the launcher's own K split)
+            for (int i = 0; i < n_mat; i++) launch_mul_mat(W[i], A, (int)N, Yp[i], (int)n_out, residual ? Rp[i] : nullptr, tune, nullptr);
+            ok = true;
         } else {
             if (generation == 3) {   // load-time digit planes (mmq3_kernels.hip)
                 if (!mmq3_supported(ggml_type, (int)n_out, (int)n_in)) return 4;
@@ -218,7 +221,7 @@ static int test_matvec_impl(int type1, const void *raw1, int n1, int type2, cons
             for (int m = 0; m < n; m++) {
                 plan_qweight(type, R, K, dst[m], base + (size_t)m * need);
                 HIP_CHECK(hipMemcpy(d_raw.p, (const uint8_t *)raw + (size_t)m * raw_bytes, raw_bytes, hipMemcpyHostToDevice));
-                if (type == GT_F16 || type == GT_F32) HIP_CHECK(hipMemcpy(base + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), dst[m], nullptr);
+                if (type == GT_F16 || type == GT_BF16 || type == GT_F32) HIP_CHECK(hipMemcpy(base + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), dst[m], nullptr);
                 HIP_CHECK(hipDeviceSynchronize());
             }
         };
@@ -275,7 +278,7 @@ static int test_matvec_rows_impl(int ggml_type, const void *raw_w, int n_mat, in
         for (int m = 0; m < n_mat; m++) {
             plan_qweight(ggml_type, R, K, W[(size_t)m], planes.as<uint8_t>() + (size_t)m * need);
             HIP_CHECK(hipMemcpy(d_raw.p, (const uint8_t *)raw_w + (size_t)m * raw_bytes, raw_bytes, hipMemcpyHostToDevice));
-            if (ggml_type == GT_F16 || ggml_type == GT_F32) HIP_CHECK(hipMemcpy(planes.as<uint8_t>() + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), W[(size_t)m], nullptr);
+            if (ggml_type == GT_F16 || ggml_type == GT_BF16 || ggml_type == GT_F32) HIP_CHECK(hipMemcpy(planes.as<uint8_t>() + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), W[(size_t)m], nullptr);
             HIP_CHECK(hipDeviceSynchronize());
         }
         HIP_CHECK(hipMemcpy(d_x.p, x, (size_t)N * K * 4, hipMemcpyHostToDevice));
@@ -312,7 +315,7 @@ int minigpt4_amd_test_matvec_rows_mixed(int type_a, const void *raw_a, int n_a, 
             for (int m = 0; m < cnt; m++) {
                 plan_qweight(type, R, K, dst[m], base + (size_t)m * need);
                 HIP_CHECK(hipMemcpy(d_raw.p, (const uint8_t *)raw + (size_t)m * raw_bytes, raw_bytes, hipMemcpyHostToDevice));
-                if (type == GT_F16 || type == GT_F32) HIP_CHECK(hipMemcpy(base + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), dst[m], nullptr);
+                if (type == GT_F16 || type == GT_BF16 || type == GT_F32) HIP_CHECK(hipMemcpy(base + (size_t)m * need, d_raw.p, raw_bytes, hipMemcpyDeviceToDevice)); else launch_repack(d_raw.as<uint8_t>(), dst[m], nullptr);
                 HIP_CHECK(hipDeviceSynchronize());
             }
         };

@@ -413,7 +413,7 @@ def ggjt_to_gguf(src: str, dst: str, version: int = 3, alignment: int = 32, extr
 
 
 def write_q8_0_twin(src: str, dst: str) -> None:
-    """The GGJT file `src` with every IQ4_NL / IQ4_XS tensor re-encoded as Q8_0 (quants.iq4_to_q8_0), everything else unchanged.  The CPU oracle does not know the IQ4
+    """The GGJT file `src` with every IQ4_NL / IQ4_XS tensor re-encoded as Q8_0 (quants.iq4_to_q8_0) and every BF16 tensor widened to F32, everything else unchanged.  The CPU oracle does not know the IQ4
     formats; where the image is exact (IQ4_NL always, IQ4_XS written with d_bits=5) it evaluates the SAME weights from the twin."""
     f = read_llm_file(src)
     hp = f.hparams
@@ -426,6 +426,8 @@ def write_q8_0_twin(src: str, dst: str) -> None:
             raw, gt = f.raw(name), t.gtype
             if gt in (Q.GGML_IQ4_NL, Q.GGML_IQ4_XS):
                 raw, gt = Q.iq4_to_q8_0(raw, gt, int(np.prod(t.ne))), Q.GGML_Q8_0
+            elif gt == Q.GGML_BF16:      # the oracle does not know BF16 either: the same values as F32 (the widening is exact)
+                raw, gt = Q.dequantize_bf16(raw.view(np.uint16)).view(np.uint8), Q.GGML_F32
             nm = name.encode()
             out.write(struct.pack("<III", len(t.ne), len(nm), gt) + struct.pack(f"<{len(t.ne)}I", *t.ne) + nm)
             out.write(b"\0" * (_align(out.tell(), 32) - out.tell()))

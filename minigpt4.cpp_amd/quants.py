@@ -25,6 +25,7 @@ GGML_Q2_K, GGML_Q3_K, GGML_Q4_K, GGML_Q5_K, GGML_Q6_K, GGML_Q8_K = 10, 11, 12, 1
 GGML_I32 = 18  # not stored in LLM files; used internally for the vision file's I32/L64 tensors
 GGML_I64 = 19
 GGML_IQ4_NL, GGML_IQ4_XS = 20, 23  # the non-linear 4-bit formats (LLM files only): a nibble indexes KVALUES_IQ4NL
+GGML_BF16 = 30  # unquantised bfloat16 (GGUF LLM files only)
 
 # MiniGPT4DataType numbering (vision file / C API)
 MG4_F16, MG4_F32, MG4_I32, MG4_L64 = 0, 1, 2, 3
@@ -43,7 +44,7 @@ TYPE_NAMES = {
     GGML_F32: "f32", GGML_F16: "f16", GGML_Q4_0: "q4_0", GGML_Q4_1: "q4_1", GGML_Q5_0: "q5_0",
     GGML_Q5_1: "q5_1", GGML_Q8_0: "q8_0", GGML_Q4_K: "q4_k", GGML_Q5_K: "q5_k", GGML_Q6_K: "q6_k",
     GGML_Q2_K: "q2_k", GGML_Q3_K: "q3_k", GGML_I32: "i32", GGML_I64: "i64",
-    GGML_IQ4_NL: "iq4_nl", GGML_IQ4_XS: "iq4_xs",
+    GGML_IQ4_NL: "iq4_nl", GGML_IQ4_XS: "iq4_xs", GGML_BF16: "bf16",
 }
 NAME_TO_TYPE = {v: k for k, v in TYPE_NAMES.items()}
 
@@ -54,7 +55,7 @@ BLOCK = {
     GGML_Q8_0: (32, 34), GGML_Q8_1: (32, 40),
     GGML_Q2_K: (256, 84), GGML_Q3_K: (256, 110), GGML_Q4_K: (256, 144), GGML_Q5_K: (256, 176),
     GGML_Q6_K: (256, 210), GGML_Q8_K: (256, 292),
-    GGML_IQ4_NL: (32, 18), GGML_IQ4_XS: (256, 136),
+    GGML_IQ4_NL: (32, 18), GGML_IQ4_XS: (256, 136), GGML_BF16: (1, 2),
 }
 
 
@@ -591,6 +592,20 @@ def iq4_to_q8_0(buf, gtype: int, n: int) -> np.ndarray:
     return out.reshape(-1)
 
 
+# --------------------------------------------------------------------------- BF16
+def quantize_bf16(x: np.ndarray) -> np.ndarray:
+    """float32 -> bfloat16 bits (uint16), round to nearest even; NaN stays NaN (quiet bit set), as ggml_compute_fp32_to_bf16."""
+    u = np.ascontiguousarray(x, np.float32).reshape(-1).view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) >> np.uint32(16)).astype(np.uint16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, ((u >> np.uint32(16)) | np.uint32(0x40)).astype(np.uint16), r)
+
+
+def dequantize_bf16(bits: np.ndarray) -> np.ndarray:
+    """bfloat16 bits -> float32: the exact widening."""
+    return (np.ascontiguousarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
 # --------------------------------------------------------------------------- dispatch
 def quantize(gtype: int, x: np.ndarray, d_bits=None) -> np.ndarray:
     """float array -> raw bytes (uint8) in ggml block layout, row-major over the flattened array.  d_bits (IQ4_NL / IQ4_XS only): significant bits kept of every d."""
@@ -601,6 +616,8 @@ def quantize(gtype: int, x: np.ndarray, d_bits=None) -> np.ndarray:
         return x.astype(np.float32).reshape(-1).view(np.uint8)
     if gtype == GGML_F16:
         return x.astype(np.float16).reshape(-1).view(np.uint8)
+    if gtype == GGML_BF16:
+        return quantize_bf16(x).view(np.uint8)
     fn = {
         GGML_Q4_0: quantize_q4_0, GGML_Q4_1: quantize_q4_1, GGML_Q5_0: quantize_q5_0,
         GGML_Q5_1: quantize_q5_1, GGML_Q8_0: quantize_q8_0, GGML_Q4_K: quantize_q4_k,
@@ -615,6 +632,8 @@ def dequantize(gtype: int, buf, n: int) -> np.ndarray:
         return np.frombuffer(buf, np.float32, n).astype(np.float64)
     if gtype == GGML_F16:
         return np.frombuffer(buf, np.float16, n).astype(np.float64)
+    if gtype == GGML_BF16:
+        return dequantize_bf16(np.frombuffer(buf, np.uint16, n)).astype(np.float64)
     fn = {
         GGML_Q4_0: dequantize_q4_0, GGML_Q4_1: dequantize_q4_1, GGML_Q5_0: dequantize_q5_0,
         GGML_Q5_1: dequantize_q5_1, GGML_Q8_0: dequantize_q8_0, GGML_Q4_K: dequantize_q4_k,
